@@ -2,7 +2,7 @@
 """Headline benchmark: generated mel-frames/s (+ RTF) of 32-NFE F5-TTS-Base with CFG 2.0 and the Vocos vocoder on
 10 s synthetic utterances (BASELINE.json configs[1]).
 
-  python bench.py --gpus N --steps K --warmup W [--mode weak|strong] [--batch B] [--total-batch T] [--ragged]
+  python bench.py --gpus N --steps K --warmup W [--mode weak|strong] [--batch B] [--total-batch T] [--ragged] [--dump-outputs DIR]
   python bench.py --arch e2 --nfe 64 --batch 8        BASELINE configs[4] per GPU: E2-TTS Base (UNetT), 64 NFE, 8 chunks of 2340 frames (20 s)
 
 One process per GPU.  With --gpus N > 1 and no torchrun environment, this process only LAUNCHES N fresh children (one rank per
@@ -29,7 +29,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 N_REF, N_TOTAL, N_REF_IDS, N_GEN_IDS, STEPS_NFE, CFG, SWAY = 468, 1404, 60, 120, 32, 2.0, -1.0
-PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA, /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA peak of the MI355X
 TRAFFIC_FILES = [os.path.join(ROOT, "profiles", f) for f in ("r03_pmc_hbm_traffic.json", "r02_pmc_hbm_traffic.json")]   # rocprofv3 --pmc passes (tools/pmc_traffic.py), newest first
 E2_FRAMES = 2340   # one long-form chunk of configs[4]: 468 reference + 1872 generated frames (20 s)
 
@@ -58,7 +58,30 @@ def parse_args(argv=None):
     ap.add_argument("--arch", default="f5", choices=["f5", "e2"], help="f5 = F5-TTS-Base (DiT, 10 s units); e2 = E2-TTS Base (UNetT, 20 s chunks of 2340 frames: configs[4])")
     ap.add_argument("--nfe", type=int, default=None, help="Euler steps (default 32; configs[4] uses 64)")
     ap.add_argument("--cpu-full", action="store_true", help="cpu_baseline: one full 32-step run instead of 4 steps scaled x8 (about a minute of CPU time)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the waveforms the last timed step returned to DIR/wave_<k>.npy (float32, rank 0)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 60 << 20   # data budget of --dump-outputs; leaves room for the .npy headers under 64 MB
+
+
+def dump_outputs(waves, out_dir):
+    """Writes waves[k] as out_dir/wave_<k>.npy in float32.  When the waveforms exceed DUMP_BYTES, every one is cut to the same share of its
+    samples, at positions drawn from a fixed seed: the same arguments give the same positions, so two builds compare sample for sample."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = [w.detach().cpu().float().numpy().reshape(-1) for w in waves]
+    total = sum(a.nbytes for a in arrays)
+    keep = min(1.0, DUMP_BYTES / total) if total else 1.0
+    rng = np.random.default_rng(0)
+    for k, a in enumerate(arrays):
+        if keep < 1.0:
+            a = a[np.sort(rng.choice(a.size, int(a.size * keep), replace=False))]
+        np.save(os.path.join(out_dir, f"wave_{k:03d}.npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------ launcher (no GPU call in this process)
@@ -294,6 +317,8 @@ def run_rank(args):
         waves = one_step()
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(waves, args.dump_outputs)
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -154,6 +154,32 @@ def test_bench_launcher_does_not_hang_when_a_rank_dies():
     assert "rank 1 exit code 3" in r.stderr and "fake failure of rank 1" in r.stderr
 
 
+def test_bench_dump_outputs_is_exact_or_a_fixed_sample_under_64_mb(tmp_path):
+    """--dump-outputs: one float32 wave_<k>.npy per returned waveform; exact when they fit, otherwise the same seeded sample positions on every
+    run (so two builds compare sample for sample) and under 64 MB in all.  --steps below 1 is rejected, not run as an empty timed region."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    assert bench.parse_args(["--steps", "7", "--dump-outputs", str(tmp_path)]).steps == 7
+    g = torch.Generator().manual_seed(0)
+    small = [torch.randn(1000, generator=g), torch.randn(1700, generator=g)]
+    bench.dump_outputs(small, str(tmp_path / "small"))
+    for k, w in enumerate(small):
+        got = np.load(tmp_path / "small" / f"wave_{k:03d}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, w.numpy())
+    big = [torch.randn(n, generator=g) for n in (9_000_000, 8_000_000)]      # 68 MB of float32
+    for d in ("a", "b"):
+        bench.dump_outputs(big, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["wave_000.npy", "wave_001.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64e6
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    assert np.isin(np.load(tmp_path / "a" / "wave_001.npy"), big[1].numpy()).all()
+
+
 def test_strong_mode_sharding_covers_every_unit_once():
     from tts_indic_server_f5_amd.sharding import shard_units, unit_cost
     frames = [1404] * 64
