@@ -1,5 +1,6 @@
-import sys, os
-sys.path.insert(0, "/root/repo")
+import os
+import sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from tts_indic_server_f5_amd import synth
 from tts_indic_server_f5_amd.model import F5TTS_BASE, F5HipModel
@@ -15,5 +16,5 @@ four, _ = m.sample(cond.expand(4, -1, -1), text.expand(4, -1), 1404, y0=y0.expan
 four2, _ = m.sample(cond.expand(4, -1, -1), text.expand(4, -1), 1404, y0=y0.expand(4, -1, -1), **kw)
 two, _ = m.sample(cond.expand(2, -1, -1), text.expand(2, -1), 1404, y0=y0.expand(2, -1, -1), **kw)
 def r(a, b): return (a.float() - b.float()).pow(2).mean().sqrt().item()
-print("impl", os.environ.get("F5HIP_GEMM_IMPL"), "one vs one2", r(one, one2), "four vs four2", r(four, four2), "four[0] vs one", r(four[0], one[0]),
+print("one vs one2", r(one, one2), "four vs four2", r(four, four2), "four[0] vs one", r(four[0], one[0]),
       "four[0] vs four[3]", r(four[0], four[3]), "two[0] vs one", r(two[0], one[0]), "two[1] vs one", r(two[1], one[0]))

@@ -44,9 +44,8 @@ def main():
     print("# K sweep, FF1 epilogue")
     for K in (64, 256, 1024, 4096):
         run("FF1 K sweep", M, 2048, K, prec=3, act="gelu_tanh", out16=True)
-    if os.environ.get("F5HIP_GEMM_IMPL") is None:
-        print("# plain fp32-out, no residual")
-        run("plain N1024", M, 1024, 1024, prec=3)
+    print("# plain fp32-out, no residual")
+    run("plain N1024", M, 1024, 1024, prec=3)
 
 
 if __name__ == "__main__":

@@ -2,8 +2,7 @@
 
 In-tree on purpose: the .so travels to the GPU box with the repo snapshot.  Every kernel family is its own translation
 unit (csrc/tu_*.hip + f5hip.hip), compiled in parallel into csrc/_obj/ and re-compiled only when one of the files it
-includes changed; `--experiments` adds -DF5HIP_EXPERIMENTS (the measured-and-rejected kernels under csrc/experiments/ and
-the f5hip_debug_* entry points the tools/ scripts of round 1 use)."""
+includes changed."""
 from __future__ import annotations
 
 import concurrent.futures as cf
@@ -40,12 +39,12 @@ def _deps(path: str, seen: set[str] | None = None) -> set[str]:
     return seen
 
 
-def _compile(unit: str, flags: list[str], verbose: bool):
+def _compile(unit: str, verbose: bool):
     src, obj = os.path.join(CSRC, unit), os.path.join(OBJ, unit.replace(".hip", ".o"))
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     # -Rpass-analysis=kernel-resource-usage: per-kernel VGPR / scratch report.  A hot kernel that touches scratch pays a
     # scratch set-up per wave plus the spills (a run-time index into the by-value argument struct once cost every GEMM 7 us).
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-Rpass-analysis=kernel-resource-usage", *flags, *UNIT_FLAGS.get(unit, []), "-o", obj, src]
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-Rpass-analysis=kernel-resource-usage", *UNIT_FLAGS.get(unit, []), "-o", obj, src]
     if verbose:
         print("[build]", " ".join(cmd), flush=True)
     r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
@@ -67,14 +66,8 @@ def _compile(unit: str, flags: list[str], verbose: bool):
     return unit
 
 
-def build(force: bool = False, verbose: bool = True, experiments: bool = False) -> str:
+def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    flags = ["-DF5HIP_EXPERIMENTS"] if experiments else []
-    if os.environ.get("F5HIP_BUILD_ABL"):   # ablation variants of gemm5 (diagnostics): F5HIP_GEMM5_ABL=<n> then selects one at run time
-        flags.append("-DF5HIP_GEMM5_ABL")
-    stamp = os.path.join(OBJ, "flags.txt")
-    if not os.path.exists(stamp) or open(stamp).read() != " ".join(flags):
-        force = True
     stale = []
     for u in UNITS:
         obj = os.path.join(OBJ, u.replace(".hip", ".o"))
@@ -82,10 +75,8 @@ def build(force: bool = False, verbose: bool = True, experiments: bool = False) 
             stale.append(u)
     if stale:
         with cf.ThreadPoolExecutor(max_workers=min(len(stale), max(1, (os.cpu_count() or 2) - 1))) as ex:
-            for u in ex.map(lambda u: _compile(u, flags, verbose), stale):
+            for u in ex.map(lambda u: _compile(u, verbose), stale):
                 pass
-        with open(stamp, "w") as f:
-            f.write(" ".join(flags))
     objs = [os.path.join(OBJ, u.replace(".hip", ".o")) for u in UNITS]
     if stale or not os.path.exists(LIB) or any(os.path.getmtime(o) > os.path.getmtime(LIB) for o in objs):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -99,9 +90,7 @@ def build(force: bool = False, verbose: bool = True, experiments: bool = False) 
             lines += open(o + ".resources").read().splitlines()
     with open(os.path.join(CSRC, "kernel_resources.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
-    # (attn3's STAMPS = true instantiations exist only in --experiments builds, for tools/attn_stamps.py: not production kernels)
-    hot = [l.split("VGPR", 1)[1].strip() for l in lines if not l.lstrip().startswith("0 B") and any(k in l for k in HOT)
-           and not re.search(r"attn3_fwd_kernelILi\dELb\dELb1EE", l)]
+    hot = [l.split("VGPR", 1)[1].strip() for l in lines if not l.lstrip().startswith("0 B") and any(k in l for k in HOT)]
     if hot:
         raise RuntimeError("hot kernels use scratch memory: " + ", ".join(hot))
     build_torch_ops(verbose)
@@ -130,4 +119,4 @@ def build_torch_ops(verbose: bool = True) -> str:
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv, experiments="--experiments" in sys.argv)
+    build(force="--force" in sys.argv)

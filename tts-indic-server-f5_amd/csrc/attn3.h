@@ -1,8 +1,8 @@
 // attn3: flash-style attention forward.  S^T = K Q^T, so a query is a lane and its row statistics are in-register; exp(S) is directly the
-// B operand of O^T += V^T P^T.  A wave owns QB blocks of 32 queries; a workgroup = NW waves = one query tile of 32 QB NW queries; K / V^T
+// B operand of O^T += V^T P^T.  A wave owns a block of 32 queries; a workgroup = NW waves = one query tile of 32 NW queries; K / V^T
 // tiles of 64 keys stream through an LDS ring by LDS-DMA.
 //
-// History of the inner loop (MI355X, C2 shape N = 1404 x 16 heads x 2, tools/attn_stamps.py / attn_bench.py, profiles/r02_attn_bench.txt):
+// History of the inner loop (MI355X, C2 shape N = 1404 x 16 heads x 2, in-kernel stamps and tools/attn_bench.py, profiles/r02_attn_bench.txt):
 //   attn2   ~3800 cycles per KV tile and SIMD against ~1000 of MFMA and ~2200 of VALU: the per-tile barrier keeps the two waves of a SIMD
 //           in lockstep, so matrix and vector phases add up instead of overlapping;
 //   attn3a  each wave carries two score tiles, S_next = K_{j+1} Q^T issued before the softmax of S_cur: 2940 per tile, 45.7 us -- the
@@ -14,15 +14,14 @@
 //           (3) V^T stored in vt_col order (common.h): a PV fragment is one ds_read_b128, no register shuffle; fragment addresses from
 //               one lane constant by XOR;
 //           (4) fragments prefetched one half tile ahead (no MFMA waits on LDS latency);
-//           (5) XCD-aware workgroup numbering: the query tiles of one (sequence, head) share an L2;
-//           (6) QB = 2: 64 queries per wave, one wave per SIMD with the 512-register budget -- every K / V^T fragment read from LDS feeds two
-//               MFMAs, there is no partner wave to share the SIMD's issue slots with, and NW = 4 puts exactly one wave on each SIMD
-//               (with 6 waves of 32 queries two SIMDs carried two waves, two carried one, and every tile ended at a barrier).
+//           (5) XCD-aware workgroup numbering: the query tiles of one (sequence, head) share an L2.
+//   64 queries per wave (QB = 2 blocks of 32, one wave per SIMD with the 512-register budget, every K / V^T fragment read feeding two MFMAs)
+//   measured slower (profiles/r02_attn_bench.txt) and was removed; the per-wave arrays keep their query-block dimension QB = 1.
 #pragma once
 #include <type_traits>
 #include "attn_common.h"
 
-// NW = waves per workgroup (4, 6 or 8), QB = 32-query blocks per wave (1 or 2), NST = ring stages of 16 KiB.
+// NW = waves per workgroup (4, 6 or 8), NST = ring stages of 16 KiB.
 // SEG2: the keys are two row ranges (AttnArgs::seq_kv_row0 / seq_kv2_*): tile kt covers 64 rows of the first range while kt < nkt1, of the
 // second after it; the last tile of EACH range is masked.  SEG2 = false is the single-range kernel of the DiT / UNetT path.
 //
@@ -48,22 +47,17 @@
 // (The running-maximum formulation in the hot loop measured 45.7 us at C2 against 41.4 us for the fixed offset, before any of the
 // scheduling work.)
 #define A3_OFF_MARGIN 2.0f
-#ifndef A3_ABL
-// timing ablations of the hot loop (WRONG results, diagnostics only; tools/attn_ablate.sh builds one library per value and profiles/r03_attn_ablate.txt
-// holds the result): bit 0 no ring step (no wait / barrier / refill), bit 1 exp2 -> v_mul, bit 2 no LDS fragment reads, bit 3 no P V / row-sum MFMAs,
-// bit 4 no KV loop at all (launch + prologue + epilogue), bit 5 return behind the sequence meta loads (the launch alone)
-#define A3_ABL 0
-#endif
 #define A3_P_LIMIT 0x1p15f
-// BAL (NW = 8, QB = 1, 192 queries per workgroup): the SIMD-balanced form of the 6-block tile.  Eight waves put two on every SIMD; waves 0-3 own a
+// BAL (NW = 8, 192 queries per workgroup): the SIMD-balanced form of the 6-block tile.  Eight waves put two on every SIMD; waves 0-3 own a
 // query block each over all keys, waves 4 / 5 own blocks 4 / 5 over keys 0-31 of every tile and waves 6 / 7 the SAME blocks over keys 32-63,
 // so every SIMD carries three half tiles per tile (with six whole-block waves two SIMDs carry four and two carry two, and the per-tile barrier
 // makes the four the pace).  The two halves of blocks 4 / 5 keep their own offset, O and l and are merged once at the end through LDS.
-template <int NW, bool SEG2 = false, bool STAMPS = false, int NST = 5, int QB = 1, bool BAL = false>
-static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(QB == 2 ? 1 : 2, QB == 2 ? 1 : 2))) void attn3_fwd_kernel(const AttnArgs p) {
+template <int NW, bool SEG2 = false, int NST = 5, bool BAL = false>
+static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn3_fwd_kernel(const AttnArgs p) {
+    constexpr int QB = 1;          // 32-query blocks per wave
     constexpr int STAGE = 16384;   // one 64-key tile: 8 KiB of K rows + 8 KiB of V^T rows
     constexpr int P_HI = (16 + NW - 1) / NW, P_LO = 16 / NW;   // 1 KiB pieces of a KV tile per wave (pieces w, w + NW, ...)
-    static_assert(!BAL || (NW == 8 && QB == 1), "BAL is the 8-wave, 6-block form");
+    static_assert(!BAL || NW == 8, "BAL is the 8-wave, 6-block form");
     constexpr int QT = BAL ? 192 : 32 * QB * NW;                // queries per workgroup
     __shared__ __attribute__((aligned(16))) char smem[NST * STAGE];
     // Workgroup -> (query tile, head, sequence), XCD-aware: the hardware deals consecutive workgroup ids round-robin to the 8 XCDs, which would
@@ -86,7 +80,6 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     const int nkt1 = (kvlen + 63) >> 6;
     const int q0 = bx * QT;
     if (q0 >= len) return;
-    if (A3_ABL & 32) return;   // (ablation: the launch alone -- dispatch with this kernel's LDS / register footprint, kernarg + sequence meta loads)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 31, fh = lane >> 5;
@@ -105,7 +98,7 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
         for (int s = 0; s < 4; s++) qf[qb][s] = *reinterpret_cast<const f16x8*>(qrow + s * 16);
     }
     // The 32 SAMPLE keys that fix the softmax offsets of this wave's queries (below): 16 spread evenly over the (first) key range and 16 at
-    // every second position (every fourth at QB = 2) of the wave's own query block, clamped into the range -- all of them valid keys.  Their K
+    // every second position of the wave's own query block, clamped into the range -- all of them valid keys.  Their K
     // rows come straight from global memory in the fragment layout of a score MFMA's A operand (lane = key fr, 8 features per k-step).
     f16x8 ksamp[4];
     {
@@ -158,7 +151,7 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     };
     static_assert((NST - 2) * P_HI <= 32, "wait_landed covers 32 outstanding pieces");
     // the same wait with a compile-time tile count: the steady state of the ring.  (The switch above compiles to a chain of ~27 scalar
-    // compare / branch pairs; tools/attn_stamps.py showed 240-500 clocks per KV tile between the end of a tile and the end of its wait with
+    // compare / branch pairs; in-kernel stamps showed 240-500 clocks per KV tile between the end of a tile and the end of its wait with
     // every piece long landed -- the hot loop takes this path, the switch serves the first and last tiles.)
     auto wait_landed_steady = [&](auto t_) {
         constexpr int T = decltype(t_)::value;
@@ -193,19 +186,6 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
         for (int g = 0; g < 16; g++) { oacc[qb][0][g] = 0.0f; oacc[qb][1][g] = 0.0f; negm[qb][g] = 0.0f; }
     }
 
-    unsigned long long st_acc[6] = {0, 0, 0, 0, 0, 0}, st_prev = 0, st_t0 = 0, st_pro = 0;
-    unsigned long long st_r0 = 0;
-    if (STAMPS) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_t0)::"memory"); st_r0 = __builtin_amdgcn_s_memrealtime(); }
-    const bool st_on = STAMPS && p.dbg != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && wave == 0;
-#define A3_STAMP(I)                                                                                  \
-    if (STAMPS && st_on) {                                                                           \
-        unsigned long long t_;                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                           \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                  \
-        __builtin_amdgcn_sched_barrier(0);                                                           \
-        if ((I) >= 0) st_acc[(I) < 0 ? 0 : (I)] += t_ - st_prev;                                     \
-        st_prev = t_;                                                                                \
-    }
     const int nkt = nkt1 + (SEG2 ? (kv2_len + 63) >> 6 : 0);
     constexpr bool PAIR = true;   // one ring step per TWO tiles (see ring_step)
 #pragma unroll
@@ -265,18 +245,14 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
             // issued so far: tiles up to kt - 3 + NST (capped at nkt - 1); tiles kt + 1, kt + 2 must have landed
             if (kt - 3 + NST <= nkt - 1) wait_landed_steady(std::integral_constant<int, NST - 5>{});
             else wait_landed(max(0, nkt - 1 - (kt + 2)));
-            A3_STAMP(5);
             __builtin_amdgcn_s_barrier();
-            A3_STAMP(4);
             if (kt - 2 + NST < nkt) issue_tile(kt - 2 + NST);
             if (kt - 1 + NST < nkt) issue_tile(kt - 1 + NST);
             return;
         }
         if (nkt - 2 - kt >= NST - 3) wait_landed_steady(std::integral_constant<int, NST - 3>{});   // tiles kt + 2 .. kt + NST - 2 may stay in flight
         else wait_landed(nkt - 2 - kt);
-        A3_STAMP(5);
         __builtin_amdgcn_s_barrier();
-        A3_STAMP(4);
         if (kt + NST - 1 < nkt) issue_tile(kt + NST - 1);
     };
     // ---- one half tile of the FAST loop: straight-line, no branch on the data ------------------------------------------------------------
@@ -293,25 +269,18 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
         constexpr int H = decltype(h_t)::value;
         constexpr bool NEXT_TILE = decltype(next_tile_t)::value, MASK = decltype(mask_t)::value;
         constexpr bool HAS_NEXT = H == 0 || NEXT_TILE;
-        if (H == 0) {
-            if (!(A3_ABL & 1)) ring_step(kt);
-            A3_STAMP(0);
-        }
+        if (H == 0) ring_step(kt);
         // prefetch for the following half tile: H = 0 -> (kt, 1) multiplies K(kt + 1, rows 0-31) and V(kt, keys 32-63);
         //                                      H = 1 -> (kt + 1, 0) multiplies K(kt + 1, rows 32-63) and V(kt + 1, keys 0-31)
-        if (A3_ABL & 4) {
-            fill = use;
-        } else {
-            if (NEXT_TILE) qk_read(fill.k, kt + 1, H == 0 ? 0 : 1);
-            if (H == 0) {
-                const unsigned vb = stage_of(kt) + v_lane;
-                v_read(fill.v[0], vb, 1, 0);
-                v_read(fill.v[1], vb, 1, 1);
-            } else if (NEXT_TILE) {
-                const unsigned vb = stage_of(kt + 1) + v_lane;
-                v_read(fill.v[0], vb, 0, 0);
-                v_read(fill.v[1], vb, 0, 1);
-            }
+        if (NEXT_TILE) qk_read(fill.k, kt + 1, H == 0 ? 0 : 1);
+        if (H == 0) {
+            const unsigned vb = stage_of(kt) + v_lane;
+            v_read(fill.v[0], vb, 1, 0);
+            v_read(fill.v[1], vb, 1, 1);
+        } else if (NEXT_TILE) {
+            const unsigned vb = stage_of(kt + 1) + v_lane;
+            v_read(fill.v[0], vb, 0, 0);
+            v_read(fill.v[1], vb, 0, 1);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -325,12 +294,11 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
             float pe[16];
             f16x8 pf[2];
 #pragma unroll
-            for (int g = 0; g < 16; g++) pe[g] = (A3_ABL & 2) ? sc[qb][g] * 0.001f : __builtin_amdgcn_exp2f(sc[qb][g]);
+            for (int g = 0; g < 16; g++) pe[g] = __builtin_amdgcn_exp2f(sc[qb][g]);
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++) {
 #pragma unroll
                 for (int j = 0; j < 8; j++) pf[s2][j] = (_Float16)pe[8 * s2 + j];
-                if (A3_ABL & 8) { asm volatile("" ::"v"(pf[s2])); continue; }
 #pragma unroll
                 for (int dt = 0; dt < 2; dt++) oacc[qb][dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(use.v[s2][dt], pf[s2], oacc[qb][dt], 0, 0, 0);
                 lacc[qb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(lones, pf[s2], lacc[qb], 0, 0, 0);   // row sums (see lacc)
@@ -347,7 +315,6 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
             for (int qb = 0; qb < QB; qb++) mask_half(sc[qb], H == 0 ? kt : kt + 1, H == 0 ? 1 : 0);
         }
-        A3_STAMP(H == 0 ? 1 : 2);
     };
 
     // BAL, roles 1 / 2: one half tile per tile -- consumes block (kt, H), produces block (kt + 1, H); fragments read at the top of the step
@@ -421,14 +388,11 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
         v_read(fa.v[0], stage_of(0) + v_lane, 0, 0);
         v_read(fa.v[1], stage_of(0) + v_lane, 0, 1);
     }
-    A3_STAMP(-1);
-    st_pro = st_prev - st_t0;
     using T_ = std::true_type;
     using F_ = std::false_type;
     using H0 = std::integral_constant<int, 0>;
     using H1 = std::integral_constant<int, 1>;
-    if (A3_ABL & 16) {   // (ablation: no KV loop at all -- launch + prologue + epilogue)
-    } else if (!BAL || role == 0) {
+    if (!BAL || role == 0) {
         int kt = 0;
         for (; kt + 2 < nkt; kt++) {   // tiles whose successors are complete tiles: no masks
             fast_half(sa, kt, fa, fb, H0{}, T_{}, F_{});
@@ -469,7 +433,7 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     __syncthreads();
     if (__any(l_bad) && lane == 0) *redo_flag = 1;
     __syncthreads();
-    const bool redo = *redo_flag != 0 && !A3_ABL;
+    const bool redo = *redo_flag != 0;
     __syncthreads();
     if (redo) {   // GENERAL loop: running maximum, any input; plain code, one query block at a time
         float mrun[QB];
@@ -552,7 +516,6 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
         }
         if (role == 2) return;   // (no barrier after this point)
     }
-    if (STAMPS && st_on && lane == 0) { p.dbg[0] = st_acc[0]; p.dbg[1] = st_acc[1]; p.dbg[2] = st_acc[2]; p.dbg[3] = (unsigned long long)nkt; p.dbg[4] = st_acc[4]; p.dbg[5] = st_acc[5]; p.dbg[6] = st_pro; }
 
 #pragma unroll
     for (int qb = 0; qb < QB; qb++) {
@@ -580,7 +543,4 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                 }
         }
     }
-    A3_STAMP(-1);
-    if (STAMPS && st_on && lane == 0) { p.dbg[7] = st_prev - st_t0; p.dbg[8] = __builtin_amdgcn_s_memrealtime() - st_r0; }   // (stores issued, not retired)
-#undef A3_STAMP
 }

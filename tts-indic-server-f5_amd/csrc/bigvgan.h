@@ -24,7 +24,7 @@ struct f5hip_bigvgan {
     BvConv pre;
     std::vector<BvConv> ups;
     std::vector<BvRes> res;
-    float *post_alpha = nullptr, *post_beta = nullptr, *post_w = nullptr, *filt = nullptr;
+    float *post_alpha = nullptr, *post_beta = nullptr, *post_w = nullptr;
     // workspace
     size_t cap = 0;
     void* ws = nullptr;
@@ -34,70 +34,15 @@ struct f5hip_bigvgan {
 };
 
 // ------------------------------------------------------------------------------------------------ kernels
-// Anti-aliased SnakeBeta activation (alias_free_torch Activation1d, up = down = 2, 12 taps).  x fp32 [rows][ldx];
-// output split bf16 [rows][ldo] (conv A operand) or fp32 [rows][ldo].  Uniform sequences: pitch P rows, T valid.
-__global__ __launch_bounds__(256) void aa_snake_kernel(const float* x, int ldx, int C, int P, int T, const float* alpha_log,
-                                                       const float* beta_log, const float* filt, __bf16* out_hi, __bf16* out_lo,
-                                                       float* out_f32, int ldo) {
-    __shared__ float xs[76][64];
-    __shared__ float as[138][64];
-    __shared__ float f[12];
-    const int tid = threadIdx.x, cl = tid & 63, tg = tid >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    const int row0 = blockIdx.y * 64;
-    const int seq0 = (row0 / P) * P, t0 = row0 - seq0;
-    if (t0 >= T) return;
-    if (tid < 12) f[tid] = filt[tid];
-    const bool cok = c < C;
-    for (int r = tg; r < 76; r += 4) {
-        int ti = t0 - 6 + r;
-        ti = ti < 0 ? 0 : (ti > T - 1 ? T - 1 : ti);   // replicate padding of the up-sampler
-        xs[r][cl] = cok ? x[(size_t)(seq0 + ti) * ldx + c] : 0.0f;
-    }
-    __syncthreads();
-    const float ea = cok ? expf(alpha_log[c]) : 1.0f;
-    const float ib = cok ? 1.0f / (expf(beta_log[c]) + 1e-9f) : 0.0f;
-    for (int r = tg; r < 138; r += 4) {
-        int j = 2 * t0 - 5 + r;
-        j = j < 0 ? 0 : (j > 2 * T - 1 ? 2 * T - 1 : j);   // replicate padding of the down-sampler
-        const int t = j >> 1, odd = j & 1;
-        // up[j] = 2 * sum_q x[t - 3 + odd + q] * f[11 - odd - 2 q]
-        const int base = t - 3 + odd - (t0 - 6);
-        float u = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 6; q++) u += xs[base + q][cl] * f[11 - odd - 2 * q];
-        u *= 2.0f;
-        // sin on the hardware unit (v_sin_f32 takes revolutions): fp32 range reduction r = a / 2pi - rint(a / 2pi) keeps |a| < ~1e3 rad
-        // within ~1e-5 rad, far inside the 1e-4 waveform bound; libm sinf was ~half of this kernel's time
-        const float rev = u * ea * 0.15915494309189535f;
-        const float sn = __builtin_amdgcn_sinf(rev - rintf(rev));
-        as[r][cl] = u + ib * sn * sn;
-    }
-    __syncthreads();
-    for (int tt = tg; tt < 64; tt += 4) {
-        const int t = t0 + tt;
-        if (t >= T || !cok) continue;
-        float v = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 12; k++) v += as[2 * tt + k][cl] * f[k];
-        const size_t o = (size_t)(seq0 + t) * ldo + c;
-        if (out_f32) out_f32[o] = v;
-        if (out_hi) {
-            __bf16 h, l;
-            split_bf16(v, h, l);
-            out_hi[o] = h;
-            out_lo[o] = l;
-        }
-    }
-}
-
 struct AaFilt { float f[12]; };
 
-// Same operator as aa_snake_kernel, register-resident: a lane owns one channel and R consecutive time steps.  It loads the R + 10
+// Anti-aliased SnakeBeta activation (alias_free_torch Activation1d, up = down = 2, 12 taps), x fp32 [rows][ldx], uniform sequences of pitch
+// P rows with T valid.  Register-resident: a lane owns one channel and R consecutive time steps.  It loads the R + 10
 // inputs its outputs depend on (row index clamped = the replicate padding of the up-sampler; for a fixed register the lanes of a
 // segment read consecutive channels of one row, so the loads coalesce), forms the 2R + 10 up-sampled snake values (index clamped
 // to [0, 2T) = the replicate padding of the down-sampler: values past the end repeat the last one, values before 0 repeat value 0)
-// and the R low-passed outputs.  No LDS, no barrier: ~44 VALU operations and 2.6 v_sin per output instead of ~25 LDS reads.
+// and the R low-passed outputs.  No LDS, no barrier: ~44 VALU operations and 2.6 v_sin per output instead of ~25 LDS reads (the round-1
+// LDS-tiled kernel, removed).
 //   grid (C / cw, ceil(T / (nseg R)), sequences), 256 lanes = nseg segments x cw channels (cw | C, cw <= 64)
 //   OUT: 0 = fp32, 1 = split bf16 planes, 2 = one fp16 plane
 template <int R, int OUT>
@@ -267,7 +212,7 @@ void f5hip_bigvgan_destroy(f5hip_bigvgan* v) {
         for (int j = 0; j < 3; j++) { bv_free_conv(r.c1[j]); bv_free_conv(r.c2[j]); }
         for (int a = 0; a < 6; a++) { dev_free(r.alpha[a]); dev_free(r.beta[a]); }
     }
-    for (float* p : {v->post_alpha, v->post_beta, v->post_w, v->filt}) dev_free(p);
+    for (float* p : {v->post_alpha, v->post_beta, v->post_w}) dev_free(p);
     dev_free(v->ws);
     delete v;
 }
@@ -372,7 +317,6 @@ int f5hip_bigvgan_finalize(f5hip_bigvgan* v) {
         }
         float ff[12];
         for (int n = 0; n < ks; n++) ff[n] = (float)(f[n] / sum);
-        if (upload_f32(&v->filt, ff, 12)) return -4;
         memcpy(v->filt_h, ff, sizeof(ff));
     }
     v->host.clear();
@@ -386,9 +330,8 @@ static int bv_conv(f5hip_bigvgan* v, const BvConv& c, const Plane2& A, int M, in
     g.conv_kpt = c.c_in_pad / 32; g.conv_center = (c.k - 1) / 2; g.conv_dil = c.dil; g.conv_group_cols = 0;
     g.row_seq_start = nullptr; g.row_seq_end = nullptr; g.seq_pitch = P; g.seq_valid = T;
     g.act = act; g.res = res; g.ldres = ldo; g.out_f32 = out; g.ldo = ldo;
-    // conv5.h (window of the tile once in LDS, taps served from it) where it covers the shape; F5HIP_CONV5=0 keeps everything on gemm.h (A/B)
-    static const int use_conv5 = getenv("F5HIP_CONV5") ? atoi(getenv("F5HIP_CONV5")) : 1;
-    if (use_conv5 && v->nsplit >= 2) {
+    // conv5.h (window of the tile once in LDS, taps served from it) where it covers the shape, gemm.h otherwise
+    if (v->nsplit >= 2) {
         prof_begin(PROF_GEMM, st);
         const hipError_t e = f5_launch_conv5(v->nsplit, g, c.w.n_pad, st);
         prof_end(PROF_GEMM, st);
@@ -401,13 +344,6 @@ static int bv_conv(f5hip_bigvgan* v, const BvConv& c, const Plane2& A, int M, in
 // Activation1d over fp32 rows x [M][ch] -> the conv operand planes (out == nullptr) or fp32 rows out [M][ch]
 static int bv_snake(f5hip_bigvgan* v, const float* x, int ch, int cpad, int M, int P, int T, const float* alpha, const float* beta, float* out,
                     hipStream_t st) {
-    static const int old_kernel = getenv("F5HIP_BV_SNAKE") ? atoi(getenv("F5HIP_BV_SNAKE")) : 0;   // 1 = the round-1 LDS-tiled kernel (A/B; split-bf16 / fp32 outputs only)
-    if (old_kernel == 1 && (out || v->nsplit == 2)) {
-        hipLaunchKernelGGL(aa_snake_kernel, dim3((ch + 63) / 64, M / 64), dim3(256), 0, st, x, ch, ch, P, T, alpha, beta, v->filt, out ? (__bf16*)nullptr : v->act.hi,
-                           out ? (__bf16*)nullptr : v->act.lo, out, out ? ch : cpad);
-        CKL("aa_snake");
-        return 0;
-    }
     constexpr int R = 16;
     int cw = ch < 64 ? ch : 64;
     while (ch % cw) cw--;

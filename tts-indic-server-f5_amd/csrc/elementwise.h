@@ -6,14 +6,14 @@
 
 #include "ln_row.h"
 
-// Row -> workgroup mapping, XCD-matched (XCD = 1; speed only, any bijection is correct): consecutive workgroup ids go round-robin to the 8 XCDs
+// Row -> workgroup mapping, XCD-matched (speed only, any bijection is correct): consecutive workgroup ids go round-robin to the 8 XCDs
 // and the block GEMMs give XCD x the row slabs of rows [x M / 8, (x + 1) M / 8) (gemm5_tile_of_block) -- both the GEMM that just wrote the
 // residual rows this kernel reads and the GEMM that reads the operand rows it writes.  With the same blocking here a row stays in one XCD's L2
-// from the residual epilogue through the norm to the next GEMM's first fill instead of crossing the fabric twice (F5HIP_LN_XCD=0: off, A/B).
-template <int NV, int XCD = 1>
+// from the residual epilogue through the norm to the next GEMM's first fill instead of crossing the fabric twice.
+template <int NV>
 __global__ __launch_bounds__(256) void ln_kernel(const LnArgs p) {
     unsigned b = blockIdx.x;
-    if (XCD && (gridDim.x & 7) == 0) b = (b & 7) * (gridDim.x >> 3) + (b >> 3);
+    if ((gridDim.x & 7) == 0) b = (b & 7) * (gridDim.x >> 3) + (b >> 3);
     ln_row<NV>(p, b * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
 }
 
@@ -113,17 +113,6 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* x, int ldx
         split_bf16(v, hi, lo);
         out_hi[(size_t)row * ldo + col0 + c] = hi;
         if (out_lo) out_lo[(size_t)row * ldo + col0 + c] = lo;
-    }
-}
-
-// fp32 [rows][C] -> ONE fp16 plane [rows][ldo] at column col0 (saturating; the operand of a PREC_F16 GEMM), 4 columns per lane
-__global__ __launch_bounds__(256) void cast_rows_f16_kernel(const float* x, int ldx, int C, int M, __bf16* out, int ldo, int col0) {
-    const int row = blockIdx.x;
-    if (row >= M) return;
-    for (int c = threadIdx.x * 4; c < C; c += 1024) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + (size_t)row * ldx + c);
-        const float y[4] = {v[0], v[1], v[2], v[3]};
-        store_f16x4(out + (size_t)row * ldo + col0 + c, y);
     }
 }
 

@@ -16,13 +16,6 @@
 #include "elementwise.h"
 #include "gemm_launch.h"
 #include "host_util.h"
-#ifdef F5HIP_EXPERIMENTS   // measured-and-rejected kernels kept for A/B (stream-K GEMM, 8-wave all-consume GEMM, earlier attention kernels)
-#include "experiments/attn2.h"
-#include "experiments/gemm2.h"
-#include "experiments/gemm4.h"
-#include "gemm.h"
-#include "attn3.h"
-#endif
 
 // =================================================================================================
 // DiT model
@@ -36,21 +29,11 @@ struct TextBlock {
 struct f5hip_dit {
     f5hip_dit_config cfg;
     int nsplit = 2;       // operand planes of the state-touching GEMMs (1 bf16, 2 split bf16)
-#ifdef F5HIP_EXPERIMENTS
-    StreamKWs sk;         // stream-K partial-tile slots + flags (experiments/gemm4.h), owned by the handle: launches of one handle are stream-ordered
-#endif
     // per-handle settings (the process-wide setters are only their defaults)
     int attn_invariant = -1;          // f5hip_dit_set_attention_shape_invariant: -1 = follow f5hip_set_attention_shape_invariant
     ProfState* prof = nullptr;        // f5hip_dit_set_profiling: this handle's own HIP-event spans and totals (null: the process-wide state)
     HostStage up_meta, up_time[2];    // pinned staging of the per-call uploads (row metadata; the two planes of the sinusoid table)
     bool blk_f16 = false; // gemm_planes == 3: transformer-block GEMMs (QKV, out, FF1, FF2) take one fp16 plane per operand
-    bool skip_f16 = false; // UNetT (experiment, F5HIP_UNETT_SKIP_F16=1): the U-skip projections too
-    // LayerNorm fused behind the residual GEMMs (gemm5 LNE kernels: experiments builds only, measured slower): per-handle arrival
-    // counters and a host-visible time-out flag
-    unsigned* ln_sync = nullptr;   // [16] row slabs, monotonic
-    unsigned ln_epoch = 0;         // fused launches since the counters were zeroed (every one adds 16 arrivals to each of its slabs)
-    int ln_slabs = 0;              // row slabs of those launches: a launch with another count zeroes the counters first (stream-ordered)
-    int* ln_err = nullptr;         // host-mapped: a kernel sets it when its slab barrier timed out
     std::map<std::string, std::vector<float>> host;
     bool finalized = false;
     // packed weights
@@ -113,16 +96,7 @@ f5hip_dit* f5hip_dit_create(const f5hip_dit_config* cfg) {
     // both backbones: against the reference's own digests mixed mode measures 3.1e-4 rms (F5-Base, 32 NFE) and 4.9e-4 (E2-Base, N = 2340,
     // 64 NFE) of the 1e-3 bound; the U-skip projections, the final norm + proj_out and the input embedding stay split bf16
     m->blk_f16 = cfg->gemm_planes == 3;
-    m->skip_f16 = m->blk_f16 && cfg->arch == 1 && getenv("F5HIP_UNETT_SKIP_F16") && atoi(getenv("F5HIP_UNETT_SKIP_F16")) == 1;
     m->arch = cfg->arch;
-    if (hipMalloc((void**)&m->ln_sync, 16 * sizeof(unsigned)) != hipSuccess || hipMemset(m->ln_sync, 0, 16 * sizeof(unsigned)) != hipSuccess ||
-        hipHostMalloc((void**)&m->ln_err, sizeof(int), hipHostMallocMapped) != hipSuccess) {
-        set_error("hipMalloc LayerNorm-fusion state");
-        dev_free(m->ln_sync);
-        delete m;
-        return nullptr;
-    }
-    *m->ln_err = 0;
     m->td_pad = cfg->arch == 2 ? 0 : ceil_to(cfg->text_dim, 32);   // MMDiT: the text never enters the input projection (mmdit.py:64-70)
     m->gw = cfg->dim / 16;
     m->n_adaln = cfg->arch == 0 ? cfg->depth * 6 * cfg->dim + 2 * cfg->dim : 0;
@@ -151,12 +125,7 @@ void f5hip_dit_destroy(f5hip_dit* m) {
         free_packed(b.pw1); free_packed(b.pw2);
     }
     for (float* p : {m->text_emb, m->text_pos, m->rope_cos, m->rope_sin}) dev_free(p);
-    dev_free(m->ln_sync);
-    if (m->ln_err) (void)hipHostFree(m->ln_err);
     dev_free(m->ws.ptr);
-#ifdef F5HIP_EXPERIMENTS
-    streamk_ws_free(m->sk);
-#endif
     dev_free(m->meta);
     delete m->prof;
     m->up_meta.release(); m->up_time[0].release(); m->up_time[1].release();
@@ -342,7 +311,7 @@ int f5hip_dit_finalize(f5hip_dit* m) {
             if (upload_f32(&m->g_attn[l], ga->data(), D) || upload_f32(&m->g_ff[l], gf->data(), D)) return -4;
             if (l >= c.depth / 2) {
                 GETP(ws, p + "0.weight", (int64_t)D * 2 * D);
-                if (pack_linear(m->wskip[l], ws->data(), D, 2 * D, 2 * D, nullptr, 128, m->skip_f16)) return -4;
+                if (pack_linear(m->wskip[l], ws->data(), D, 2 * D, 2 * D, nullptr)) return -4;
             }
         }
     }
@@ -399,7 +368,7 @@ static int ensure_workspace(f5hip_dit* m, int rows_pad, int frames, int n_seq) {
         m->sinp = a.plane2(128 * 256); m->t1 = a.plane2((size_t)128 * D); m->st = a.plane2((size_t)128 * D);
         m->skipbuf.resize(m->arch == 1 ? c.depth / 2 : 0);
         for (auto& sb : m->skipbuf) sb = a.plane2(R * 2 * D);   // [R][2 D]: the concatenated operand [x || skip] of the U-skip Linear, built in place
-        // qk: +256 rows because the last 256-query tile of attn2 may read (never store) past the padded rows
+        // qk: +256 rows because the last query tile of the attention (up to 256 queries) may read (never store) past the padded rows
         m->qk = a.bf16((R + 256) * 2 * D); m->vt = a.bf16((size_t)D * R);
         if (!pass) {
             if (hipMalloc(&m->ws.ptr, a.used()) != hipSuccess) { m->ws.ptr = nullptr; m->cap_rows = 0; return fail(-5, "hipMalloc workspace %zu bytes", a.used()); }
@@ -521,72 +490,40 @@ static GemmArgs gemm_base(const Plane2& A, int lda, const PackedW& W, int M) {
     return a;
 }
 
-static int g_gemm_impl = -1;   // F5HIP_GEMM_IMPL: 0 = automatic; 1 = register-staged kernel only (gemm.h); 3 = gemm3 instead of gemm5 (A/B); 2 / 4 = experiments build only
-static long long g_counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // f5hip_get_counter: gemm5 launches with RB 11 / RB 8 / 1 x 4 consumer layout / gemm3 wide-tile launches / ... / gemm6 launches
-static int g_gemm6_mode = -1;   // F5HIP_GEMM6: 0 = never, 1 = whenever the shape is legal, 256 / 176 = that tile height whenever legal, unset = automatic (batch-mode shapes)
+static long long g_counters[6] = {0, 0, 0, 0, 0, 0};   // f5hip_get_counter: gemm5 launches with RB 11 / RB 8 / 1 x 4 consumer layout / gemm3 wide-tile launches / conv5 launches / gemm6 launches
 
-// Kernel choice per GEMM (measured: profiles/r02_fillrate_microbench.txt, profiles/r01_gemm_microbench.txt, tools/gemm_microbench.py):
-//   fp16 one-plane operands with K % 64 == 0 (the four transformer-block GEMMs of the DiT in mixed mode): gemm5, exact-fit tiles;
+// Kernel choice per GEMM (measured: profiles/r02_fillrate_microbench.txt, profiles/r01_gemm_microbench.txt):
+//   fp16 one-plane operands: gemm6 for the batch-mode shapes (gemm6_choose_rows), else gemm5 (exact-fit tiles) when K % 64 == 0,
+//   else gemm3; implicit-GEMM convolutions in fp16 on gemm.h;
 //   one 128 x 128 tile per CU or fewer, generic epilogue, bf16 / split-bf16 operands: gemm3 (warp-specialised LDS-DMA ring);
 //   everything else (implicit-GEMM convolutions, QKV in split-bf16, many-tile shapes): gemm.h, two 4-wave workgroups per CU.
-static int run_gemm_n(int nsplit, int mp, GemmArgs& a, const PackedW& W, int epi, bool conv, int bn, hipStream_t st, void* sk = nullptr) {
+static int run_gemm_n(int nsplit, int mp, GemmArgs& a, const PackedW& W, int epi, bool conv, int bn, hipStream_t st) {
     hipError_t e;
     const int np = W.n_pad;
     if (mp % 128 || np % bn || a.K % 32) return fail(-7, "gemm: bad padded shape %d x %d x %d", mp, np, a.K);
-    if (g_gemm_impl < 0) {
-        const char* env = getenv("F5HIP_GEMM_IMPL");
-        g_gemm_impl = env ? atoi(env) : 0;
-    }
-    (void)sk;
     prof_begin(PROF_GEMM, st);
     const long long tiles128 = (long long)(mp / 128) * (np / 128);
-    const bool use3 = !conv && (g_gemm_impl == 3 || (g_gemm_impl == 0 && tiles128 <= 256 && epi != EPI_QKV));
-#ifdef F5HIP_EXPERIMENTS
-    const int nk32 = a.K >> 5;
-    StreamKWs* skw = (StreamKWs*)sk;
-    if (g_gemm_impl == 4 && skw && !conv && nsplit != 2 && np % 128 == 0 && nk32 >= 16 && tiles128 >= 64) {   // stream-K: 5-25 % slower at every C2 shape
-        if (streamk_ws_init(*skw)) { prof_end(PROF_GEMM, st); return fail(-5, "stream-K workspace"); }
-        if (nsplit == 3) e = epi == EPI_QKV ? launch_gemm4_t<3, EPI_QKV>(a, mp, np, *skw, st) : launch_gemm4_t<3, EPI_GENERIC>(a, mp, np, *skw, st);
-        else e = epi == EPI_QKV ? launch_gemm4_t<1, EPI_QKV>(a, mp, np, *skw, st) : launch_gemm4_t<1, EPI_GENERIC>(a, mp, np, *skw, st);
-    } else if (g_gemm_impl == 2 && !conv && nsplit != 3) {
-        if (nsplit == 2) e = epi == EPI_QKV ? launch_gemm2_t<2, 128, 128, EPI_QKV>(a, mp, np, st) : launch_gemm2_t<2, 128, 128, EPI_GENERIC>(a, mp, np, st);
-        else e = epi == EPI_QKV ? launch_gemm2_t<1, 128, 128, EPI_QKV>(a, mp, np, st) : launch_gemm2_t<1, 128, 128, EPI_GENERIC>(a, mp, np, st);
-    } else
-#endif
-    if (nsplit == 3) {   // fp16 operands, one plane each
-        if (conv) {   // implicit-GEMM convolution (BigVGAN in fp16 mode): register-staged kernel
-            e = f5_launch_gemm_reg(3, bn, true, epi, a, mp, np, st);
-            prof_end(PROF_GEMM, st);
-            if (e != hipSuccess) return fail(-7, "gemm launch: %s", hipGetErrorString(e));
-            return 0;
-        }
+    if (nsplit == 3 && !conv) {   // fp16 operands, one plane each
         const Gemm5Choice c5 = gemm5_choose(a.M, np);
-        if (g_gemm6_mode < 0) {
-            const char* env6 = getenv("F5HIP_GEMM6");
-            g_gemm6_mode = env6 ? atoi(env6) : 2;
-        }
         // gemm6 (256 x 256 ping-pong tiles): the batch-mode shapes -- enough tiles to occupy the chip in their first round
-        const bool legal6 = g_gemm_impl == 0 && a.K % 64 == 0 && np % 256 == 0 && (epi != EPI_QKV || a.D % 256 == 0);
-        int rows6 = legal6 ? gemm6_choose_rows(a.M, np) : 0;
-        if (legal6 && (g_gemm6_mode == 1 || g_gemm6_mode == 256 || g_gemm6_mode == 176)) rows6 = g_gemm6_mode == 1 ? (rows6 ? rows6 : 256) : g_gemm6_mode;   // (forced: tools)
-        if (rows6 && g_gemm6_mode != 0) {
+        const bool legal6 = a.K % 64 == 0 && np % 256 == 0 && (epi != EPI_QKV || a.D % 256 == 0);
+        const int rows6 = legal6 ? gemm6_choose_rows(a.M, np) : 0;
+        if (rows6) {
             e = f5_launch_gemm6(epi, rows6, a, np, st);
-            g_counters[7]++;
-        } else if ((g_gemm_impl == 0 || g_gemm_impl == 5) && a.K % 64 == 0 && c5.rb) {
+            g_counters[5]++;
+        } else if (a.K % 64 == 0 && c5.rb) {
             e = epi == EPI_QKV ? f5_launch_gemm5_qkv(a, c5.rb, c5.cb, np, st) : f5_launch_gemm5_generic(a, c5.rb, c5.cb, np, st);
             g_counters[c5.rb == 11 ? 0 : 1]++;
             if (c5.cb >= 8) g_counters[2]++;
-        } else if (g_gemm_impl == 1) {
-            e = f5_launch_gemm_reg(3, 128, false, epi, a, mp, np, st);
         } else {
             // gemm3 (round 1): 128 x 256 tile in batch mode (>= 1024 tiles of 128 x 128), 128 x 128 otherwise
             const bool wide = tiles128 >= 1024 && np % 256 == 0;
             if (wide) g_counters[3]++;
             e = f5_launch_gemm3(3, epi, wide ? 256 : 128, a, mp, np, st);
         }
-    } else if (use3) {
+    } else if (!conv && tiles128 <= 256 && epi != EPI_QKV) {
         e = f5_launch_gemm3(nsplit, epi, 128, a, mp, np, st);
-    } else {
+    } else {   // (fp16 convolutions included: BigVGAN in fp16 mode)
         e = f5_launch_gemm_reg(nsplit, bn, conv, epi, a, mp, np, st);
     }
     prof_end(PROF_GEMM, st);
@@ -594,27 +531,18 @@ static int run_gemm_n(int nsplit, int mp, GemmArgs& a, const PackedW& W, int epi
     return 0;
 }
 static int run_gemm(f5hip_dit* m, GemmArgs& a, const PackedW& W, int epi, bool conv, int bn, hipStream_t st, int m_pad = -1) {
-#ifdef F5HIP_EXPERIMENTS
-    void* sk = &m->sk;
-#else
-    void* sk = nullptr;
-#endif
-    return run_gemm_n(W.f16 ? 3 : m->nsplit, m_pad > 0 ? m_pad : m->M_pad, a, W, epi, conv, bn, st, sk);
+    return run_gemm_n(W.f16 ? 3 : m->nsplit, m_pad > 0 ? m_pad : m->M_pad, a, W, epi, conv, bn, st);
 }
 
 static int run_ln(const LnArgs& a, hipStream_t st) {
     const int nv = (a.D + 255) / 256;
     dim3 grid((a.M + 3) / 4), blk(256);
     prof_begin(PROF_LN, st);
-    static const bool ln_xcd = !(getenv("F5HIP_LN_XCD") && atoi(getenv("F5HIP_LN_XCD")) == 0);
     switch (nv) {
         case 1: hipLaunchKernelGGL(ln_kernel<1>, grid, blk, 0, st, a); break;
         case 2: hipLaunchKernelGGL(ln_kernel<2>, grid, blk, 0, st, a); break;
         case 3: hipLaunchKernelGGL(ln_kernel<3>, grid, blk, 0, st, a); break;
-        case 4:
-            if (ln_xcd) hipLaunchKernelGGL((ln_kernel<4, 1>), grid, blk, 0, st, a);
-            else hipLaunchKernelGGL((ln_kernel<4, 0>), grid, blk, 0, st, a);
-            break;
+        case 4: hipLaunchKernelGGL(ln_kernel<4>, grid, blk, 0, st, a); break;
         case 5: case 6: hipLaunchKernelGGL(ln_kernel<6>, grid, blk, 0, st, a); break;
         default: return fail(-7, "ln: D=%d unsupported", a.D);
     }
@@ -624,95 +552,19 @@ static int run_ln(const LnArgs& a, hipStream_t st) {
     return 0;
 }
 
-// ---- LayerNorm fused behind a residual GEMM (EXPERIMENT, -DF5HIP_EXPERIMENTS builds with F5HIP_LN_FUSE=1) ------------------------------
-// Measured and not shipped (profiles/r02_ln_fusion.txt): bit-identical to the separate kernel, but the fused residual GEMM takes 31.2 us
-// against 18.8 us + 6.1 us for the GEMM and the stand-alone LayerNorm.  The in-kernel chain is five dependent L2 round trips of 1.5-2 us
-// (store acknowledgement -> arrival atomic -> poll -> row loads -> stores); a kernel boundary resolves the same dependency in ~2 us.
-#ifdef F5HIP_EXPERIMENTS
-// The slab barrier of the LNE kernels needs (a) every workgroup of the launch resident at once and (b) the 16 workgroups of a row slab on
-// ONE XCD (their only coherence point is that XCD's L2).  (b) holds under gemm5's tile order if the hardware deals workgroup b to XCD
-// b % 8: probed once per process with s_getreg XCC_ID.  F5HIP_LN_FUSE=0 turns the fusion off (A/B, and the fallback after a time-out).
-__global__ void xcc_probe_kernel(int* out) {
-    if (threadIdx.x == 0) {
-        unsigned id;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(id));
-        out[blockIdx.x] = (int)(id & 0xF);
-    }
-}
-static int g_ln_fuse = -1;   // -1 not probed, 0 off, 1 on
-static int g_num_cus = 0;
-static void ln_fuse_probe() {
-    if (g_ln_fuse >= 0) return;
-    g_ln_fuse = 0;
-    if (!getenv("F5HIP_LN_FUSE") || atoi(getenv("F5HIP_LN_FUSE")) != 1) return;   // opt-in
-    hipDeviceProp_t prop;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return;
-    g_num_cus = prop.multiProcessorCount;
-    const int nb = 512;
-    int* d = nullptr;
-    std::vector<int> h(nb, -1);
-    if (hipMalloc((void**)&d, nb * sizeof(int)) != hipSuccess) return;
-    hipLaunchKernelGGL(xcc_probe_kernel, dim3(nb), dim3(64), 0, 0, d);
-    const bool ok = hipGetLastError() == hipSuccess && hipMemcpy(h.data(), d, nb * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(d);
-    if (!ok) return;
-    for (int b = 0; b < nb; b++)
-        if (h[b] != h[b & 7]) return;               // workgroups b and b % 8 on different XCDs: no fusion
-    for (int x = 1; x < 8; x++)
-        for (int y = 0; y < x; y++)
-            if (h[x] == h[y]) return;               // fewer than 8 XCDs in the round robin
-    g_ln_fuse = 1;
-}
-
-#endif
-
-// Residual GEMM g (out projection / FF2: updates the stream h in place) followed by the LayerNorm `ln` over h: one LNE kernel when the
-// launch is one resident wave of exact-fit tiles with 16 column tiles per slab and 8 or 16 slabs (a slab then sits on one XCD) AND the
-// library is an experiments build with F5HIP_LN_FUSE=1; otherwise -- the shipped path -- two launches.
+// Residual GEMM g (out projection / FF2: updates the stream h in place) followed by the LayerNorm `ln` over h.  (Fusing the norm behind the
+// GEMM's epilogue measured slower -- 31.2 us against 18.8 + 6.1 us for the two launches: profiles/r02_ln_fusion.txt.)
 static int run_gemm_ln(f5hip_dit* m, GemmArgs& g, const PackedW& W, const LnArgs& ln, hipStream_t st) {
-#ifdef F5HIP_EXPERIMENTS
-    ln_fuse_probe();
-    if (g_ln_fuse == 1 && *m->ln_err) {             // a barrier of an earlier call timed out: its results were wrong; never again
-        g_ln_fuse = 0;
-        g_counters[6]++;
-        return fail(-9, "fused LayerNorm: a slab barrier timed out in an earlier launch (its output is invalid); the fusion is now off");
-    }
-    if (g_ln_fuse == 1 && W.f16 && !ln.dw_w && !ln.out_f32 && ln.D == 1024 && ln.ldx == 1024 && ln.x == g.out_f32 && g.ldo == 1024 && W.n == 1024 && g.K % 64 == 0 &&
-        g_gemm_impl == 0) {
-        const Gemm5Choice c5 = gemm5_choose(g.M, W.n_pad);
-        const int bm = c5.rb * 16, bnn = c5.cb * 16;
-        const int tiles_m = c5.rb ? (g.M + bm - 1) / bm : 0, tiles_n = c5.rb ? W.n_pad / bnn : 0;
-        if (c5.rb && c5.cb == 4 && tiles_n == 16 && (tiles_m == 8 || tiles_m == 16) && tiles_m * tiles_n <= g_num_cus) {
-            if (tiles_m != m->ln_slabs) {           // counters of slabs the earlier launches did not have would lag behind the epoch
-                if (hipMemsetAsync(m->ln_sync, 0, 16 * sizeof(unsigned), st) != hipSuccess) return fail(-6, "fused LayerNorm: counter reset");
-                m->ln_epoch = 0;
-                m->ln_slabs = tiles_m;
-            }
-            g.ln = ln;
-            g.ln_sync = m->ln_sync;
-            g.ln_target = ++m->ln_epoch * 16u;
-            g.ln_err = m->ln_err;
-            prof_begin(PROF_GEMM, st);
-            const hipError_t e = f5_launch_gemm5_generic_lne(g, c5.rb, c5.cb, W.n_pad, st);
-            prof_end(PROF_GEMM, st);
-            if (e != hipSuccess) return fail(-7, "gemm5 LNE launch: %s", hipGetErrorString(e));
-            g_counters[c5.rb == 11 ? 0 : 1]++;
-            g_counters[5]++;
-            return 0;
-        }
-    }
-#endif
     if (const int r = run_gemm(m, g, W, EPI_GENERIC, false, 64, st)) return r;
     return run_ln(ln, st);
 }
 
-// Diagnostics for tests: which GEMM path the launches since the last reset took ("gemm5_rb11", "gemm5_rb8", "gemm5_wide", "gemm3_wide", "gemm6"); name "reset" zeroes them.
+// Diagnostics for tests: which GEMM path the launches since the last reset took ("gemm5_rb11", "gemm5_rb8", "gemm5_wide", "gemm3_wide", "conv5", "gemm6"); name "reset" zeroes them.
 extern "C" int f5hip_get_counter(const char* name, int64_t* value) {
-    static const char* names[8] = {"gemm5_rb11", "gemm5_rb8", "gemm5_wide", "gemm3_wide", "conv5", "ln_fused", "ln_fuse_timeouts", "gemm6"};
+    static const char* names[6] = {"gemm5_rb11", "gemm5_rb8", "gemm5_wide", "gemm3_wide", "conv5", "gemm6"};
     if (!name) return fail(-1, "get_counter: null name");
     if (!strcmp(name, "reset")) { for (auto& c : g_counters) c = 0; return 0; }
-    for (int i = 0; i < 8; i++)
+    for (int i = 0; i < 6; i++)
         if (!strcmp(name, names[i])) { if (value) *value = g_counters[i]; return 0; }
     return fail(-1, "unknown counter %s", name);
 }
@@ -813,12 +665,9 @@ static int precompute_time(f5hip_dit* m, const float* t_host, int n_t, hipStream
     return r;
 }
 
-// rotary operands of a QKV launch over rows row_off ..: the per-row tables of the current layout (one load per row in the epilogue);
-// F5HIP_ROPE_ROWS=0: positions + the [pos][32] tables (two dependent loads; A/B)
+// rotary operands of a QKV launch over rows row_off ..: the per-row tables of the current layout (one load per row in the epilogue)
 static void set_rope(GemmArgs& q, const f5hip_dit* m, int row_off) {
-    static const bool per_row = !(getenv("F5HIP_ROPE_ROWS") && atoi(getenv("F5HIP_ROPE_ROWS")) == 0);
-    if (per_row) { q.row_pos = nullptr; q.rope_cos = m->rope_row_cos + (size_t)row_off * 32; q.rope_sin = m->rope_row_sin + (size_t)row_off * 32; }
-    else { q.row_pos = m->d_row_pos + row_off; q.rope_cos = m->rope_cos; q.rope_sin = m->rope_sin; }
+    q.row_pos = nullptr; q.rope_cos = m->rope_row_cos + (size_t)row_off * 32; q.rope_sin = m->rope_row_sin + (size_t)row_off * 32;
 }
 
 static int launch_attention(f5hip_dit* m, hipStream_t st) {
@@ -834,18 +683,8 @@ static int launch_attention(f5hip_dit* m, hipStream_t st) {
         n_att = 2 * m->n_seq;
     }
     prof_begin(PROF_ATTN, st);
-#ifdef F5HIP_EXPERIMENTS
-    static int attn_impl = -1;
-    if (attn_impl < 0) { const char* env = getenv("F5HIP_ATTN_IMPL"); attn_impl = env ? atoi(env) : 3; }
-    if (attn_impl == 1) hipLaunchKernelGGL(attn_fwd_kernel, dim3((m->max_len + 127) / 128, c.heads, m->n_seq), dim3(256), 0, st, at);
-    else if (attn_impl == 2) hipLaunchKernelGGL(attn2_fwd_kernel, dim3((m->max_len + 255) / 256, c.heads, m->n_seq), dim3(512), 0, st, at);
-    else
-#endif
-    {
-        static const int attn_sel = getenv("F5HIP_ATTN") ? atoi(getenv("F5HIP_ATTN")) : 3;   // 4 = experiments/attn4.h (A/B in -DF5HIP_EXPERIMENTS builds)
-        const hipError_t e = attn_sel == 4 && m->arch != 2 ? f5_launch_attn4(at, m->max_len, c.heads, n_att, st) : f5_launch_attn3(at, m->max_len, c.heads, n_att, st);
-        if (e != hipSuccess) { prof_end(PROF_ATTN, st); return fail(-7, "attention launch: %s", hipGetErrorString(e)); }
-    }
+    const hipError_t e = f5_launch_attn3(at, m->max_len, c.heads, n_att, st);
+    if (e != hipSuccess) { prof_end(PROF_ATTN, st); return fail(-7, "attention launch: %s", hipGetErrorString(e)); }
     prof_end(PROF_ATTN, st);
     CKL("attention");
     return 0;
@@ -869,15 +708,13 @@ static int forward_unett_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t 
             prof_begin(PROF_OTHER, st);
             // the skip is saved where its consumer wants it: columns D .. 2 D - 1 of that layer's [x || skip] operand (round 3: it used to go to a
             // [M][D] buffer and was copied behind x with hipMemcpy2DAsync at the consumer, ~55 % of the "other" kernel class at C5)
-            if (m->skip_f16) hipLaunchKernelGGL(cast_rows_f16_kernel, dim3(M), dim3(256), 0, st, m->h, D, D, M, m->skipbuf[l].hi, 2 * D, D);
-            else hipLaunchKernelGGL(split_rows_kernel, dim3(M), dim3(256), 0, st, m->h, D, D, M, (const int*)nullptr, m->skipbuf[l].hi, m->skipbuf[l].lo, 2 * D, D);
+            hipLaunchKernelGGL(split_rows_kernel, dim3(M), dim3(256), 0, st, m->h, D, D, M, (const int*)nullptr, m->skipbuf[l].hi, m->skipbuf[l].lo, 2 * D, D);
             prof_end(PROF_OTHER, st);
             CKL("skip save");
         } else {
             const Plane2& sk = m->skipbuf[c.depth - 1 - l];
             prof_begin(PROF_OTHER, st);
-            if (m->skip_f16) hipLaunchKernelGGL(cast_rows_f16_kernel, dim3(M), dim3(256), 0, st, m->h, D, D, M, sk.hi, 2 * D, 0);
-            else hipLaunchKernelGGL(split_rows_kernel, dim3(M), dim3(256), 0, st, m->h, D, D, M, (const int*)nullptr, sk.hi, sk.lo, 2 * D, 0);
+            hipLaunchKernelGGL(split_rows_kernel, dim3(M), dim3(256), 0, st, m->h, D, D, M, (const int*)nullptr, sk.hi, sk.lo, 2 * D, 0);
             prof_end(PROF_OTHER, st);
             CKL("skip concat x");
             GemmArgs sp = gemm_base(sk, 2 * D, m->wskip[l], M);
@@ -912,46 +749,6 @@ static int forward_unett_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t 
     CK(run_gemm(m, po, m->proj_out, EPI_GENERIC, false, 128, st));
     return 0;
 }
-
-// Diagnostics (F5HIP_DUMP_QKV = 100 * layer + step): checksums of one QKV projection by column block and a hash of every other workspace
-// buffer, printed to stderr.  This is how the 1-ulp rotary difference between tile widths was found.
-static void debug_dump_qkv(f5hip_dit* m, hipStream_t st) {
-    const int D = m->cfg.dim, F = m->cfg.ff_mult * D, M = m->M;
-   // F5HIP_DUMP_QKV = 100 * layer + step   // diagnostics: checksums of the first QKV projection by column block
-    (void)hipStreamSynchronize(st);
-            std::vector<unsigned short> hq((size_t)M * 2 * D), hv((size_t)D * m->M_pad);
-            (void)hipMemcpy(hq.data(), m->qk, hq.size() * 2, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(hv.data(), m->vt, hv.size() * 2, hipMemcpyDeviceToHost);
-            auto bf = [](unsigned short u) { unsigned v = (unsigned)u << 16; float f; memcpy(&f, &v, 4); return (double)f; };
-            const int edges[6] = {0, 64, 128, 256, 512, D};
-            for (int part = 0; part < 2; part++)
-                for (int e = 0; e < 5; e++) {
-                    double sum = 0, asum = 0;
-                    for (int r = 0; r < M; r++)
-                        for (int c = edges[e]; c < edges[e + 1]; c++) { const double x = bf(hq[(size_t)r * 2 * D + part * D + c]); sum += x; asum += fabs(x); }
-                    fprintf(stderr, "[dump_qkv] %s cols [%d,%d): sum %.6f abs %.6f\n", part ? "K" : "Q", edges[e], edges[e + 1], sum, asum);
-                }
-            for (int e = 0; e < 5; e++) {
-                double sum = 0, asum = 0;
-                for (int c = edges[e]; c < edges[e + 1]; c++)
-                    for (int r = 0; r < M; r++) { const double x = bf(hv[(size_t)c * m->M_pad + r]); sum += x; asum += fabs(x); }
-                fprintf(stderr, "[dump_qkv] V rows [%d,%d): sum %.6f abs %.6f\n", edges[e], edges[e + 1], sum, asum);
-            }
-            // side effects: word checksums of every other workspace buffer (an out-of-bounds store of the projection would show here)
-            struct { const char* name; const void* p; size_t bytes; } bufs[] = {
-                {"h", m->h, (size_t)M * D * 4}, {"h0", m->h0, (size_t)M * D * 4}, {"ce", m->ce, (size_t)M * D * 4}, {"pred", m->pred, (size_t)M * 128 * 4},
-                {"mod", m->mod, (size_t)128 * m->n_adaln * 4}, {"hn.hi", m->hn.hi, (size_t)M * D * 2}, {"hn.lo", m->hn.lo, (size_t)M * D * 2},
-                {"c1.hi", m->c1.hi, (size_t)M * D * 2}, {"ao.hi", m->ao.hi, (size_t)M * D * 2}, {"ao.lo", m->ao.lo, (size_t)M * D * 2},
-                {"ff.hi", m->ff.hi, (size_t)M * F * 2}, {"ff.lo", m->ff.lo, (size_t)M * F * 2}, {"xs.hi", m->xs.hi, (size_t)M * 128 * 2},
-                {"qk slack rows", m->qk + (size_t)M * 2 * D, (size_t)256 * 2 * D * 2}};
-            for (auto& b : bufs) {
-                std::vector<unsigned> w(b.bytes / 4);
-                (void)hipMemcpy(w.data(), b.p, b.bytes, hipMemcpyDeviceToHost);
-                unsigned long long acc = 0;
-                for (unsigned x : w) acc = acc * 1000003ull + x;
-                fprintf(stderr, "[dump_qkv] buffer %-14s hash %016llx\n", b.name, acc);
-            }
-        }
 
 // One DiT evaluation at time index ti for all laid-out sequences.  xs (split bf16 of x) must be current.
 // n_blocks < 0: full network, result in m->pred [M][128];  else stops after n_blocks blocks, result in m->h.
@@ -1023,10 +820,9 @@ static int forward_mmdit_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t 
 
 // One grouped convolution of ConvPositionEmbedding: the sliding-window kernel (conv5.h, 128-row tiles, one column tile per group) for the
 // DiT and MMDiT layouts, the implicit GEMM of gemm.h otherwise (UNetT: the time-token row at the head of every sequence has an empty
-// window of its own, which a per-tile bound cannot express) or with F5HIP_CONV5=0.
+// window of its own, which a per-tile bound cannot express).
 static int run_pos_conv(f5hip_dit* m, GemmArgs& g, const PackedW& W, hipStream_t st) {
-    static const int use_conv5 = getenv("F5HIP_CONV5") ? atoi(getenv("F5HIP_CONV5")) : 1;
-    if (use_conv5 && m->arch != 1 && m->nsplit == 2 && !W.f16) {
+    if (m->arch != 1 && m->nsplit == 2 && !W.f16) {
         prof_begin(PROF_GEMM, st);
         const hipError_t e = f5_launch_conv5(2, g, W.n_pad, st);
         prof_end(PROF_GEMM, st);
@@ -1060,8 +856,8 @@ static int forward_step(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {
     const int nb = n_blocks < 0 ? c.depth : n_blocks;
     if (m->arch == 1) return forward_unett_layers(m, ti, n_blocks, st);
     if (m->arch == 2) return forward_mmdit_layers(m, ti, n_blocks, st);
-    // Every LayerNorm but the first is launched together with the residual GEMM in front of it (run_gemm_ln: one kernel where the launch
-    // is exact-fit): the out projection carries norm 2 of its block, FF2 carries norm 1 of the next block or the final norm.
+    // Every LayerNorm but the first follows the residual GEMM in front of it (run_gemm_ln): the out projection is followed by norm 2 of
+    // its block, FF2 by norm 1 of the next block or the final norm.
     const float* mf = mod + (size_t)c.depth * 6 * D;   // final (scale, shift): F/model/modules.py:308
     auto block_ln = [&](const float* shift, const float* scale) {
         LnArgs ln; memset(&ln, 0, sizeof(ln));
@@ -1075,8 +871,6 @@ static int forward_step(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {
         GemmArgs q = gemm_base(m->hn, D, m->wqkv[l], M);
         q.D = D; set_rope(q, m, 0); q.qk = m->qk; q.vt = m->vt; q.ldvt = m->Rtot;
         CK(run_gemm(m, q, m->wqkv[l], EPI_QKV, false, 128, st));
-        static const int dump_qkv = getenv("F5HIP_DUMP_QKV") ? atoi(getenv("F5HIP_DUMP_QKV")) : -1;   // diagnostics, read once
-        if (dump_qkv >= 0 && l == dump_qkv / 100 && ti == dump_qkv % 100) debug_dump_qkv(m, st);
         CK(launch_attention(m, st));
         GemmArgs o = gemm_base(m->ao, D, m->wout[l], M);
         o.mul = ml + 2 * D; o.res = m->h; o.ldres = D; o.out_f32 = m->h; o.ldo = D;
@@ -1281,6 +1075,3 @@ int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, con
 #include "vocos.h"
 #include "bigvgan.h"
 #include "unit_ops.h"
-#ifdef F5HIP_EXPERIMENTS
-#include "experiments/debug_bench.h"
-#endif

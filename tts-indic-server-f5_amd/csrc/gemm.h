@@ -21,7 +21,7 @@
 F5_DEVICE int lds_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
 
 
-// ABL (diagnostics only, f5hip_debug_gemm_bench): 0 = normal, 1 = no global loads inside the k-loop, 2 = no LDS reads / MFMAs
+// ABL (timing ablations, diagnostics only; no launcher instantiates them): 0 = normal, 1 = no global loads inside the k-loop, 2 = no LDS reads / MFMAs
 template <int NSPLIT, int BN, bool CONV, int EPI, int ABL = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_kernel(const GemmArgs p) {
     constexpr int NPL = NSPLIT == 2 ? 2 : 1;   // NSPLIT = operand precision: 1 bf16, 2 split bf16 (3 MFMAs), 3 fp16 (PREC_F16)

@@ -2,7 +2,7 @@
 // Operand precision PREC (template NSPLIT): 1 = bf16, 2 = split bf16 (hi + lo planes, 3 MFMAs per k-step), 3 = fp16 (one plane).
 // One plane: 4 x 16 KiB ring, two workgroups per CU; split bf16: 4 x 32 KiB ring, one workgroup per CU.
 //
-// In-kernel s_memtime stamps of gemm.h (tools/gemm_stamps.py, profiles/) show where a k-step of a lone workgroup goes:
+// In-kernel s_memtime stamps of gemm.h (profiles/) show where a k-step of a lone workgroup goes:
 // 543 cycles ISSUING its 8 global loads per wave (the CU's texture-address path moves ~60 B/clk of these 64-byte row
 // segments), 940 cycles LDS reads + 24 MFMAs, 640 cycles waiting for the loads and writing LDS, 190 at the barrier --
 // 2300 cycles for 768 cycles of MFMA.  The load issue and the MFMAs are serial inside every wave.  Here they are on

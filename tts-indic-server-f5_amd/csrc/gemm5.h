@@ -29,8 +29,6 @@
 //   * the row phase is a rolled, one-deep software-pipelined loop over groups of 4 rows (residual of the next group in flight while the
 //     current one is finished), the (activation x residual x output x guard) variant chosen once per kernel outside it.
 #pragma once
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "gemm_epilogue.h"
@@ -70,9 +68,7 @@ F5_DEVICE int gemm5_tile_of_block(int b, int n_tiles) {
 // builtin global_load_lds in the same loop every wait degraded to lgkmcnt(0), "pending flat").
 // SWAP: the W fragment is the MFMA's A operand: acc[i][j][e] = C[token (rb0 + i) 16 + (lane & 15)][feature (cb0 + j) 16 + 4 (lane >> 4) + e];
 // !SWAP: acc[i][j][e] = C[token (rb0 + i) 16 + 4 (lane >> 4) + e][feature (cb0 + j) 16 + (lane & 15)].
-// ABL (diagnostics, -DF5HIP_GEMM5_ABL builds + F5HIP_GEMM5_ABL=<n> at run time; results are garbage): 1 = no MFMAs, 2 = no fragment
-// reads and no MFMAs, 3 = no LDS-DMA inside the loop, 4 = MFMAs only (no DMA, no fragment reads), 5 = s_memrealtime stamps.
-template <bool F16, int BM, int STAGE, int NST, int MRB, int MCB, bool SWAP, int ABL>
+template <bool F16, int BM, int STAGE, int NST, int MRB, int MCB, bool SWAP>
 F5_DEVICE void g5_consume(const char* smem, int nk, int rb0, int cb0, int lane, f32x4 (&acc)[MRB][MCB]) {
     // fragment byte offsets inside a stage: row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); block bases are multiples of 16 rows, so the
     // swizzle term depends on the lane only; k-half 1 is k-half 0 with chunk bit 2 flipped (^ 64 bytes)
@@ -86,7 +82,6 @@ F5_DEVICE void g5_consume(const char* smem, int nk, int rb0, int cb0, int lane, 
     auto a_ptr = [&](int kt, int ks) { return smem + (kt % NST) * STAGE + rb0 * 2048 + (ks ? (off0 ^ 64) : off0); };
     auto b_ptr = [&](int kt, int ks) { return smem + (kt % NST) * STAGE + (BM + cb0 * 16) * 128 + (ks ? (off0 ^ 64) : off0); };
     auto read_b = [&](int buf, const char* sb) {
-        if ((ABL == 2 || ABL == 4) && sb != b_ptr(0, 0)) return;
 #pragma unroll
         for (int j = 0; j < MCB; j++) fb[buf][j] = *reinterpret_cast<const bf16x8*>(sb + j * 2048);
     };
@@ -95,14 +90,10 @@ F5_DEVICE void g5_consume(const char* smem, int nk, int rb0, int cb0, int lane, 
         constexpr bool RELOAD = decltype(reload)::value;
 #pragma unroll
         for (int i = 0; i < MRB; i++) {
-            if (ABL == 1 || ABL == 2) {
-                asm volatile("" :: "v"(fa[i]), "v"(fb[buf][0]), "v"(fb[buf][MCB - 1]));
-            } else {
 #pragma unroll
-                for (int j = 0; j < MCB; j++)
-                    acc[i][j] = SWAP ? mfma_16x16x32<F16>(fb[buf][j], fa[i], acc[i][j]) : mfma_16x16x32<F16>(fa[i], fb[buf][j], acc[i][j]);
-            }
-            if (RELOAD && ABL != 2 && ABL != 4) fa[i] = *reinterpret_cast<const bf16x8*>(sa_next + i * 2048);
+            for (int j = 0; j < MCB; j++)
+                acc[i][j] = SWAP ? mfma_16x16x32<F16>(fb[buf][j], fa[i], acc[i][j]) : mfma_16x16x32<F16>(fa[i], fb[buf][j], acc[i][j]);
+            if (RELOAD) fa[i] = *reinterpret_cast<const bf16x8*>(sa_next + i * 2048);
         }
     };
     constexpr std::integral_constant<bool, true> ROLL{};
@@ -457,26 +448,11 @@ F5_DEVICE void g5_v_rows(const GemmArgs& p, const float* slab, int m0, int n0, i
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------------
-// LNE (EXPERIMENT, instantiated in -DF5HIP_EXPERIMENTS builds only): the LayerNorm that FOLLOWS this residual GEMM (out projection -> norm 2, FF2 -> the next block's norm 1) fused behind its epilogue.
-// Only launched as ONE resident wave of workgroups (grid <= CUs, one workgroup per CU by its LDS size) with 16 column tiles per row slab:
-// when a slab's 16 workgroups have stored their tiles of the residual stream they meet at a slab-local barrier (an arrival counter in L2:
-// the XCD-blocked tile order puts them on one XCD -- probed at start-up, f5hip.hip), then workgroup j normalises rows j * BM / 16 ... of
-// the slab (one wave per row, ln_finish = the stand-alone kernel's arithmetic, so the bits are the same) and writes the operand plane
-// of the next GEMM.  The rows are read with agent-scope loads (this CU's L1 may still hold the tile's own residual columns from before
-// the update).  MEASURED AND NOT SHIPPED: bit-identical, but 31.2 us against 18.8 + 6.1 us for the two kernels it replaces (and the same
-// norm fused in FRONT of the following GEMM measured 2-5 % slower end to end): DESIGN.md section 6, profiles/r02_ln_fusion.txt.  The spin is bounded (~50 ms):
-// on a time-out the workgroup sets *p.ln_err and carries on (wrong results, no hang); the host then stops using these kernels.
-F5_DEVICE f32x4 g5_load_f4_agent(const float* ptr) {
-    f32x4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(v) : "v"(ptr) : "memory");
-    return v;
-}
 // WD: W fragments straight from global memory (g5_consume_wd): the ring holds A rows only; needs the 1 x 4 consumer layout, K % 128 == 0, p.Wf.
-template <bool F16, int EPI, int RB, int CB, int WR, int NST, int ABL = 0, bool LNE = false, bool WD = false>
+template <bool F16, int EPI, int RB, int CB, int WR, int NST, bool WD = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm5_kernel(const GemmArgs p, const int tiles_n, const int n_rows_w) {
     using C = Gemm5Cfg<RB, CB, NST>;
-    static_assert(!WD || (WR == 1 && ABL == 0 && !LNE), "W-direct: 1 x 4 consumer layout, production kernels only");
+    static_assert(!WD || WR == 1, "W-direct: 1 x 4 consumer layout");
     constexpr int BM = C::BM, BN = C::BN, PIECES = WD ? BM / 8 : C::PIECES, STAGE = PIECES * 1024;
     constexpr int WC = 4 / WR;                                 // the 4 consumer waves tile the block grid WR (rows) x WC (columns)
     constexpr int MRB = (RB + WR - 1) / WR, MCB = CB / WC;
@@ -489,11 +465,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int tile = gemm5_tile_of_block(blockIdx.x, gridDim.x);
     const int m0 = (tile / tiles_n) * BM, n0 = (tile % tiles_n) * BN;
     const int nk = p.K >> 6;
-    unsigned long long ts[6] = {0, 0, 0, 0, 0, 0};
-    // time line: ABL == 5 builds keep the stamps in registers; the W-direct kernels write them straight to p.stamps when it is set (run time,
-    // tools/gemm5_stamps.py with F5HIP_GEMM5_STAMPS=1: no special build)
+    // time line: the W-direct kernels write it to p.stamps when that is set (run time, tools/gemm5_stamps.py with F5HIP_GEMM5_STAMPS=1)
     unsigned long long* const stamp_o = (WD && p.stamps && (tid == 0 || tid == 256)) ? p.stamps + ((size_t)blockIdx.x * 2 + (tid >> 8)) * 8 : nullptr;
-#define G5_STAMP(I) if constexpr (ABL == 5) { if (tid == 0 || tid == 256) ts[I] = __builtin_amdgcn_s_memrealtime(); } else if constexpr (WD) { if (stamp_o) stamp_o[I] = __builtin_amdgcn_s_memrealtime(); }
+#define G5_STAMP(I) if constexpr (WD) { if (stamp_o) stamp_o[I] = __builtin_amdgcn_s_memrealtime(); }
     G5_STAMP(0);
     // consumer geometry (also used by the epilogue): row blocks rb0 .. rb0 + nrb - 1, column blocks cb0 .. cb0 + MCB - 1
     const int cw = wave & 3;
@@ -530,10 +504,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             char* dst = smem + (kt % NST) * STAGE + pw * 1024;
 #pragma unroll
             for (int j = 0; j < P_HI; j++)
-                if ((ABL != 3 && ABL != 4) || kt < NST)
-                    if (j < P_LO || pw + 4 * j < PIECES)
-                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gsrc[j] + (size_t)kt * 128),
-                                                         (__attribute__((address_space(3))) void*)(dst + j * 4096), 16, 0, 0);
+                if (j < P_LO || pw + 4 * j < PIECES)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gsrc[j] + (size_t)kt * 128),
+                                                     (__attribute__((address_space(3))) void*)(dst + j * 4096), 16, 0, 0);
         };
         // this wave's pieces of a k-step have landed when at most `newer` younger k-steps of its own are still in flight
         auto wait_landed = [&](int newer) {
@@ -570,9 +543,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const char* wf = reinterpret_cast<const char*>(p.Wf) + (size_t)(n0 / 16 + cb0) * jstride + lane * 16;
         g5_consume_wd<F16, BM, STAGE, NST, MRB, MCB, true>(smem, wf, jstride, nk, rb0, lane, acc);
     } else if (swap) {
-        g5_consume<F16, BM, STAGE, NST, MRB, MCB, true, ABL>(smem, nk, rb0, cb0, lane, acc);
+        g5_consume<F16, BM, STAGE, NST, MRB, MCB, true>(smem, nk, rb0, cb0, lane, acc);
     } else {
-        g5_consume<F16, BM, STAGE, NST, MRB, MCB, false, ABL>(smem, nk, rb0, cb0, lane, acc);
+        g5_consume<F16, BM, STAGE, NST, MRB, MCB, false>(smem, nk, rb0, cb0, lane, acc);
     }
 
     G5_STAMP(2);
@@ -603,38 +576,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         __syncthreads();                                           // E2
         g5_v_rows<RB, CB, NST>(p, slab, m0, n0, 0, wave, lane);
     }
-    if constexpr (LNE) {
-        static_assert(EPI == EPI_GENERIC && Gemm5Cfg<RB, CB, NST>::BM % 16 == 0, "16 workgroups share the rows of a slab of the residual stream");
-        constexpr int ROWS = Gemm5Cfg<RB, CB, NST>::BM / 16;       // rows this workgroup normalises (11 or 8)
-        static_assert(ROWS <= 16, "at most two rows per wave");
-        const int slab_i = tile / tiles_n, j = tile - slab_i * tiles_n;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's part of the tile is in L2 (write-through L1)
-        __syncthreads();
-        if (tid == 0) {
-            __hip_atomic_fetch_add(p.ln_sync + slab_i, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            int spins = 0;
-            while ((int)(__hip_atomic_load(p.ln_sync + slab_i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - p.ln_target) < 0) {
-                if (++spins > (1 << 15)) { *p.ln_err = 1; break; }  // ~50 ms: the slab's other workgroups are not running
-                __builtin_amdgcn_s_sleep(1);
-            }
-        }
-        __syncthreads();
-        // rows wave and wave + 8 of this workgroup's share: every load (both rows, scale, shift) in flight before the first use
-        const int r0 = m0 + j * ROWS + wave, r1 = wave + 8 < ROWS ? r0 + 8 : p.ln.M;   // (r1 == M: no second row)
-        float4 v0[4], v1[4], sc[4], sh[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int c = (i * 64 + lane) * 4;
-            const f32x4 a = g5_load_f4_agent(p.ln.x + (size_t)min(r0, p.ln.M - 1) * p.ln.ldx + c);
-            const f32x4 b = g5_load_f4_agent(p.ln.x + (size_t)min(r1, p.ln.M - 1) * p.ln.ldx + c);
-            v0[i] = make_float4(a[0], a[1], a[2], a[3]);
-            v1[i] = make_float4(b[0], b[1], b[2], b[3]);
-        }
-        ln_load_mod<4>(p.ln, lane, sc, sh);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (the asm loads are invisible to the compiler's own counting)
-        ln_finish<4>(p.ln, r0, lane, v0, sc, sh);
-        ln_finish<4>(p.ln, r1, lane, v1, sc, sh);
-    }
     G5_STAMP(4);
     if constexpr (WD) {
         if (stamp_o) {
@@ -643,20 +584,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             stamp_o[6] = __builtin_amdgcn_s_memrealtime();
         }
     }
-    if constexpr (ABL == 5) {
-        if (p.stamps && (tid == 0 || tid == 256)) {
-            const unsigned long long t5 = __builtin_amdgcn_s_memrealtime();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const unsigned long long t6 = __builtin_amdgcn_s_memrealtime();
-            unsigned long long* o = p.stamps + ((size_t)blockIdx.x * 2 + (tid >> 8)) * 8;
-            for (int i = 0; i < 5; i++) o[i] = ts[i];
-            o[5] = t5; o[6] = t6; o[7] = 0;
-        }
-    }
 #undef G5_STAMP
 }
 
-template <bool F16, int EPI, int RB, int CB, int WR, int NST, int ABL = 0, bool LNE = false, bool WD = false>
+template <bool F16, int EPI, int RB, int CB, int WR, int NST, bool WD = false>
 static hipError_t launch_gemm5_t(const GemmArgs& a, int n_pad, hipStream_t st) {
     using C = Gemm5Cfg<RB, CB, NST>;
     // LDS: the ring (A rows only with W-direct) or the epilogue slab that aliases it, whichever is larger
@@ -665,55 +596,21 @@ static hipError_t launch_gemm5_t(const GemmArgs& a, int n_pad, hipStream_t st) {
     static_assert(lds <= 160 * 1024, "tile does not fit the LDS");
     if (WD && (!a.Wf || a.K % 128)) return hipErrorInvalidValue;
     static unsigned attr_mask = 0;
-    if (hipError_t e = f5_set_lds_attr(reinterpret_cast<const void*>(&gemm5_kernel<F16, EPI, RB, CB, WR, NST, ABL, LNE, WD>), lds, attr_mask); e != hipSuccess) return e;
+    if (hipError_t e = f5_set_lds_attr(reinterpret_cast<const void*>(&gemm5_kernel<F16, EPI, RB, CB, WR, NST, WD>), lds, attr_mask); e != hipSuccess) return e;
     const int tiles_m = (a.M + C::BM - 1) / C::BM, tiles_n = n_pad / C::BN;
-    if (LNE && (tiles_n != 16 || !a.ln_sync || !a.ln_err || a.ln.D != 1024 || a.ln.x != a.out_f32 || a.ln.dw_w)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((gemm5_kernel<F16, EPI, RB, CB, WR, NST, ABL, LNE, WD>), dim3(tiles_m * tiles_n), dim3(512), lds, st, a, tiles_n, n_pad);
+    hipLaunchKernelGGL((gemm5_kernel<F16, EPI, RB, CB, WR, NST, WD>), dim3(tiles_m * tiles_n), dim3(512), lds, st, a, tiles_n, n_pad);
     return hipGetLastError();
-}
-
-// residual GEMM + the LayerNorm behind it (out projection, FF2: generic epilogue, 64 columns = 16 column tiles of a 1024-wide stream)
-template <bool F16>
-static hipError_t launch_gemm5_lne(const GemmArgs& a, int rb, int cb, int n_pad, hipStream_t st) {
-    if (cb != 4) return hipErrorInvalidValue;
-    if (rb == 11) return launch_gemm5_t<F16, EPI_GENERIC, 11, 4, 4, 4, 0, true>(a, n_pad, st);
-    if (rb == 8) return launch_gemm5_t<F16, EPI_GENERIC, 8, 4, 4, 4, 0, true>(a, n_pad, st);
-    return hipErrorInvalidValue;
 }
 
 // (tile choice and the non-template entry points: gemm_launch.h / tu_gemm5_*.hip)
 template <bool F16, int EPI>
 static hipError_t launch_gemm5(const GemmArgs& a, int rb, int cb, int n_pad, hipStream_t st) {
-#ifdef F5HIP_GEMM5_ABL
-    static const int abl = getenv("F5HIP_GEMM5_ABL") ? atoi(getenv("F5HIP_GEMM5_ABL")) : 0;
-    if (EPI == EPI_QKV && rb == 11 && cb == 12) {
-        if (abl == 5) return launch_gemm5_t<F16, EPI_QKV, 11, 12, 1, 3, 5>(a, n_pad, st);
-        if (abl == 2) return launch_gemm5_t<F16, EPI_QKV, 11, 12, 1, 3, 2>(a, n_pad, st);
-        if (abl == 4) return launch_gemm5_t<F16, EPI_QKV, 11, 12, 1, 3, 4>(a, n_pad, st);
-    }
-    if (EPI == EPI_GENERIC && rb == 11 && (cb == 4 || cb == 8)) {
-        if (cb == 4) {
-            if (abl == 1) return launch_gemm5_t<F16, EPI_GENERIC, 11, 4, 4, 4, 1>(a, n_pad, st);
-            if (abl == 2) return launch_gemm5_t<F16, EPI_GENERIC, 11, 4, 4, 4, 2>(a, n_pad, st);
-            if (abl == 3) return launch_gemm5_t<F16, EPI_GENERIC, 11, 4, 4, 4, 3>(a, n_pad, st);
-            if (abl == 4) return launch_gemm5_t<F16, EPI_GENERIC, 11, 4, 4, 4, 4>(a, n_pad, st);
-            if (abl == 5) return launch_gemm5_t<F16, EPI_GENERIC, 11, 4, 4, 4, 5>(a, n_pad, st);
-        } else {
-            if (abl == 1) return launch_gemm5_t<F16, EPI_GENERIC, 11, 8, 2, 4, 1>(a, n_pad, st);
-            if (abl == 2) return launch_gemm5_t<F16, EPI_GENERIC, 11, 8, 2, 4, 2>(a, n_pad, st);
-            if (abl == 3) return launch_gemm5_t<F16, EPI_GENERIC, 11, 8, 2, 4, 3>(a, n_pad, st);
-            if (abl == 4) return launch_gemm5_t<F16, EPI_GENERIC, 11, 8, 2, 4, 4>(a, n_pad, st);
-            if (abl == 5) return launch_gemm5_t<F16, EPI_GENERIC, 11, 8, 2, 4, 5>(a, n_pad, st);
-        }
-    }
-#endif
-    // W-direct (fragment-ordered weights present, K a multiple of 128): the wide tiles, in the 1 x 4 consumer layout (F5HIP_GEMM5_WD=0: off, A/B)
-    static const bool wd_on = !(getenv("F5HIP_GEMM5_WD") && atoi(getenv("F5HIP_GEMM5_WD")) == 0);
-    if (wd_on && a.Wf && a.K % 128 == 0 && cb >= 8) {
-        if (rb == 11 && cb == 8) return launch_gemm5_t<F16, EPI, 11, 8, 1, 6, 0, false, true>(a, n_pad, st);
-        if (rb == 11 && cb == 12) return launch_gemm5_t<F16, EPI, 11, 12, 1, 6, 0, false, true>(a, n_pad, st);
-        if (rb == 8 && cb == 8) return launch_gemm5_t<F16, EPI, 8, 8, 1, 6, 0, false, true>(a, n_pad, st);
-        if (rb == 8 && cb == 12) return launch_gemm5_t<F16, EPI, 8, 12, 1, 6, 0, false, true>(a, n_pad, st);
+    // W-direct (fragment-ordered weights present, K a multiple of 128): the wide tiles, in the 1 x 4 consumer layout
+    if (a.Wf && a.K % 128 == 0 && cb >= 8) {
+        if (rb == 11 && cb == 8) return launch_gemm5_t<F16, EPI, 11, 8, 1, 6, true>(a, n_pad, st);
+        if (rb == 11 && cb == 12) return launch_gemm5_t<F16, EPI, 11, 12, 1, 6, true>(a, n_pad, st);
+        if (rb == 8 && cb == 8) return launch_gemm5_t<F16, EPI, 8, 8, 1, 6, true>(a, n_pad, st);
+        if (rb == 8 && cb == 12) return launch_gemm5_t<F16, EPI, 8, 12, 1, 6, true>(a, n_pad, st);
     }
     if (rb == 11) {
         if (cb == 4) return launch_gemm5_t<F16, EPI, 11, 4, 4, 4>(a, n_pad, st);

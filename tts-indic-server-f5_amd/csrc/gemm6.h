@@ -454,11 +454,11 @@ static hipError_t launch_gemm6_t(const GemmArgs& a, int n_pad, hipStream_t st) {
     static unsigned attr_mask = 0;
     if (hipError_t e = f5_set_lds_attr(reinterpret_cast<const void*>(&gemm6_kernel<F16, EPI, RBW>), C::LDS, attr_mask); e != hipSuccess) return e;
     const int tiles_m = (a.M + C::BM - 1) / C::BM, tiles_n = n_pad / C::BN, n_tiles = tiles_m * tiles_n;
-    static int n_cu = 0;                                            // persistent grid: one workgroup per CU (F5HIP_GEMM6_PERSIST=0: one per tile, A/B)
+    static int n_cu = 0;                                            // persistent grid: one workgroup per CU
     if (!n_cu) {
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        n_cu = (getenv("F5HIP_GEMM6_PERSIST") && atoi(getenv("F5HIP_GEMM6_PERSIST")) == 0) ? (1 << 30) : cus;
+        n_cu = cus;
     }
     hipLaunchKernelGGL((gemm6_kernel<F16, EPI, RBW>), dim3(n_tiles < n_cu ? n_tiles : n_cu), dim3(512), C::LDS, st, a, tiles_n, n_pad, n_tiles);
     return hipGetLastError();

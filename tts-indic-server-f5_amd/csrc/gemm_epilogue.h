@@ -67,13 +67,8 @@ struct GemmArgs {
     __bf16* qk;              // [M_pad][2 D]  fp16 bits (attention operands are fp16: attn3.h)
     __bf16* vt;              // [D][ldvt]     fp16 bits
     int ldvt;
-    // fused LayerNorm behind the epilogue (gemm5 LNE kernels): ln.x == out_f32 (the residual stream this GEMM updates); ln_sync[slab] counts
-    // the workgroups of a row slab that have stored their tile (monotonic: this launch waits for ln_target), *ln_err is set on a time-out
-    LnArgs ln;
-    unsigned* ln_sync;
-    unsigned ln_target;
-    int* ln_err;
-    // diagnostics (ABL == 3 builds only)
+    // diagnostics: per-workgroup s_memrealtime time line of the W-direct gemm5 kernels and of gemm6 (F5HIP_GEMM5_STAMPS /
+    // F5HIP_GEMM6_STAMPS, unit ops only), cycle stamps of conv5 (f5hip_op_conv1d); null on the path
     unsigned long long* stamps;
     int stamp_bx, stamp_by;
 };
@@ -201,7 +196,7 @@ F5_DEVICE void epi_qk_rows_t(const GemmArgs& p, const float* stg, int m_base, in
         float o[4];
         if (ROT) {
             // explicit product + fma: left to the compiler, the contraction of a*c - b*s differs between template instantiations (64- vs
-            // 128-wide wave tiles), a 1-ulp flip in a few q values that the 22-layer sampler amplifies to 5e-4 (tools/wide_pipeline_check.py)
+            // 128-wide wave tiles), a 1-ulp flip in a few q values that the 22-layer sampler amplifies to 5e-4
             o[0] = __builtin_fmaf(v[0], cs[q].x, -__fmul_rn(v[1], sn[q].x)) * qs;
             o[1] = __builtin_fmaf(v[1], cs[q].x, __fmul_rn(v[0], sn[q].x)) * qs;
             o[2] = __builtin_fmaf(v[2], cs[q].y, -__fmul_rn(v[3], sn[q].y)) * qs;

@@ -6,7 +6,7 @@
 #include "attn_common.h"
 #include "gemm_epilogue.h"
 
-// gemm.h: register-staged 128 x {128, 64} x 32 kernel (prec 1 bf16, 2 split bf16, 3 fp16); conv = implicit-GEMM operand
+// gemm.h: register-staged 128 x {128, 64} x 32 kernel (prec 1 bf16, 2 split bf16, 3 fp16 -- convolutions only); conv = implicit-GEMM operand
 hipError_t f5_launch_gemm_reg(int prec, int bn, bool conv, int epi, const GemmArgs& a, int m_pad, int n_pad, hipStream_t st);
 // gemm3.h: warp-specialised LDS-DMA kernel, 128 x bn (128, or 256 for one-plane operands) x 32
 hipError_t f5_launch_gemm3(int prec, int epi, int bn, const GemmArgs& a, int m_pad, int n_pad, hipStream_t st);
@@ -23,18 +23,11 @@ static inline int gemm6_choose_rows(int m_rows, int n_pad) {
     const double c256 = (double)((t256 + 255) / 256), c176 = 0.85 * (double)((t176 + 255) / 256);
     return c176 < c256 ? 176 : 256;
 }
-// a residual GEMM (64-column tiles of a 1024-wide stream) with the LayerNorm that follows it fused behind the epilogue (GemmArgs::ln ...):
-// one resident wave of workgroups, 16 column tiles per row slab; hipErrorInvalidValue otherwise.  Experiments builds only (measured
-// slower than the two launches it replaces).
-hipError_t f5_launch_gemm5_generic_lne(const GemmArgs& a, int rb, int cb, int n_pad, hipStream_t st);
 // conv5.h: sliding-window Conv1d (the window of a 256-row tile once in LDS, taps served from it); hipErrorInvalidValue = shape not covered
 hipError_t f5_launch_conv5(int prec, const GemmArgs& a, int n_pad, hipStream_t st);
 // attn3.h: flash attention forward, 256 queries per workgroup
 hipError_t f5_launch_attn3(const AttnArgs& a, int max_len, int heads, int n_seq, hipStream_t st);
 void f5_set_attn_shape_invariant(int on);
-hipError_t f5_launch_attn5(const AttnArgs& a, int max_len, int heads, int n_seq, hipStream_t st);   // attn5.h: ping-pong kernel (single key range)
-// experiments/attn4.h (unequal-height waves, 16 x 16 x 32 MFMA; attn3 unless built with -DF5HIP_EXPERIMENTS)
-hipError_t f5_launch_attn4(const AttnArgs& a, int max_len, int heads, int n_seq, hipStream_t st);
 
 // gemm5 tile choice: fewest operand bytes per CU over the whole launch = rounds on the 256 CUs x (BM + BN); ties -> the larger tile.
 // rb == 0: no instantiated tile divides n_pad.

@@ -19,7 +19,8 @@ static void op_pack_planes(const float* src, int R, int C, int R_pad, __bf16* hi
     hipLaunchKernelGGL(pack_weight_kernel, dim3(R_pad), dim3(256), 0, st, src, R, C, C, hi, f16 ? (__bf16*)nullptr : lo, C);
 }
 
-// diagnostics (-DF5HIP_GEMM5_ABL builds, F5HIP_GEMM5_ABL=5): s_memrealtime stamps (100 MHz) of wave 0 (consumer) and wave 4 (loader) of every workgroup
+// diagnostics of the W-direct gemm5 kernels (F5HIP_GEMM5_STAMPS=1, tools/gemm5_stamps.py): s_memrealtime stamps (100 MHz) of wave 0 (consumer)
+// and wave 4 (loader) of every workgroup
 template <typename Launch>
 static int gemm5_stamp_report(OpBufs& b, int M, int N, int K, hipStream_t st, Launch launch) {
     const int maxg = 4096;
@@ -278,10 +279,10 @@ __global__ __launch_bounds__(256) void op_unpack_planes_kernel(const __bf16* hi,
 
 // softmax(q k^T / 8 + key-padding mask) v per (sequence, head), head dim 64 (F/model/modules.py:424-436): q / k / v fp32 [sum(seq_len)][64 heads]
 // are rounded to fp16 like the QKV epilogue's outputs (q after the log2(e) / 8 scale); out fp32 [sum(seq_len)][64 heads] = split-bf16 planes summed.
-// impl 3 = attn3 (production), 4 = experiments/attn4.h (attn3 unless built with -DF5HIP_EXPERIMENTS).
+// impl must be 3 (attn3, the production kernel).
 extern "C" int f5hip_op_attention(int32_t n_seq, const int32_t* seq_len, const int32_t* kv_len, int32_t heads, const float* q_dev,
                                   const float* k_dev, const float* v_dev, float* out_dev, int32_t impl, int32_t iters, double* avg_us, void* stream) {
-    if (n_seq <= 0 || !seq_len || heads <= 0 || !q_dev || !k_dev || !v_dev || !out_dev || (impl != 3 && impl != 4 && impl != 5)) return fail(-1, "op_attention: bad argument");
+    if (n_seq <= 0 || !seq_len || heads <= 0 || !q_dev || !k_dev || !v_dev || !out_dev || impl != 3) return fail(-1, "op_attention: bad argument");
     hipStream_t st = (hipStream_t)stream;
     const int D = heads * 64;
     int M_pad = 0, F = 0, max_len = 0;
@@ -314,7 +315,7 @@ extern "C" int f5hip_op_attention(int32_t n_seq, const int32_t* seq_len, const i
     hipError_t e = hipSuccess;
     for (int it = -1; it < iters && e == hipSuccess; it++) {
         if (it == 0) (void)hipEventRecord(e0, st);
-        e = impl == 3 ? f5_launch_attn3(at, max_len, heads, n_seq, st) : impl == 5 ? f5_launch_attn5(at, max_len, heads, n_seq, st) : f5_launch_attn4(at, max_len, heads, n_seq, st);
+        e = f5_launch_attn3(at, max_len, heads, n_seq, st);
     }
     (void)hipEventRecord(e1, st);
     (void)hipEventSynchronize(e1);
