@@ -95,7 +95,11 @@ int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, con
 
 /* The fixed-grid solver both sample calls use: replaces CFM(odeint_kwargs=dict(method=...)) (F/model/cfm.py:37-41,72,200; set from
  * load_model(ode_method=...), F/infer/utils_infer.py:251).  0 = "euler" (default): x += dt * v(t_i, x).  1 = "midpoint":
- * x += dt * v(t_i + dt / 2, x + dt / 2 * v(t_i, x)), two backbone evaluations per step, at most 64 steps per call. */
+ * x += dt * v(t_i + dt / 2, x + dt / 2 * v(t_i, x)), two backbone evaluations per step, at most 64 steps per call.  2 = "rk4": torchdiffeq's
+ * fixed-grid rule (rk4_alt_step_func, the 3/8 rule), four backbone evaluations per step, at most 42 steps per call:
+ *   k1 = v(t_i, x), k2 = v(t_i + dt / 3, x + dt * k1 / 3), k3 = v(t_i + 2 dt / 3, x + dt * (k2 - k1 / 3)), k4 = v(t_{i+1}, x + dt * (k1 - k2 + k3)),
+ *   x += (k1 + 3 (k2 + k3) + k4) * dt / 8.
+ * `steps` is the number of grid intervals for every method. */
 int f5hip_dit_set_ode_method(f5hip_dit* m, int32_t method);
 
 /* Attention kernel choice.  0 (default): the fastest form per launch shape -- a launch with 192-query tiles (e.g. one 10 s utterance) runs

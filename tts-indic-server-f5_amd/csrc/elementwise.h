@@ -146,6 +146,51 @@ __global__ __launch_bounds__(128) void cfg_euler_kernel(float* xout /*[U][mel]*/
     }
 }
 
+// CFG combine + one stage of the fixed-grid RK4 step (torchdiffeq method="rk4": rk4_alt_step_func, the 3/8 rule), launched after the
+// forward of stage s = 1..4 of the interval [t0, t0 + dt]:
+//   s = 1: k1 = v(t0, y0)             next input y0 + dt * k1 / 3
+//   s = 2: k2 = v(t0 + dt/3, ..)      next input y0 + dt * (k2 - k1 / 3)
+//   s = 3: k3 = v(t0 + 2 dt/3, ..)    next input y0 + dt * (k1 - k2 + k3)
+//   s = 4: k4 = v(t0 + dt, ..)        y1 = y0 + (k1 + 3 (k2 + k3) + k4) * dt / 8
+// v as in cfg_euler_kernel.  Stages 1-3 keep k_s in their [U][mel] buffer and write the next stage's input only to the split-bf16 copy
+// of x (both branches); xstate holds y0 until stage 4 writes y1 there.
+__global__ __launch_bounds__(128) void cfg_rk4_stage_kernel(float* xstate /*[U][mel]*/, int mel, int U, const float* pred, int ldp,
+                                                            const int* urow_c, const int* urow_u, float cfg, float dt, int stage,
+                                                            float* k1, float* k2, float* k3, __bf16* xs_hi, __bf16* xs_lo, int ldx) {
+    const int u = blockIdx.x;
+    if (u >= U) return;
+    const int c = threadIdx.x;
+    if (c >= mel) return;
+    const int rc = urow_c[u], ru = urow_u[u];
+    const float pc = pred[(size_t)rc * ldp + c];
+    float v = pc;
+    if (ru >= 0) v = pc + (pc - pred[(size_t)ru * ldp + c]) * cfg;
+    const size_t i = (size_t)u * mel + c;
+    const float y0 = xstate[i];
+    float xn;
+    if (stage == 1) {
+        k1[i] = v;
+        xn = y0 + dt * v * (1.0f / 3.0f);
+    } else if (stage == 2) {
+        k2[i] = v;
+        xn = y0 + dt * (v - k1[i] * (1.0f / 3.0f));
+    } else if (stage == 3) {
+        k3[i] = v;
+        xn = y0 + dt * (k1[i] - k2[i] + v);
+    } else {
+        xn = y0 + (k1[i] + 3.0f * (k2[i] + k3[i]) + v) * dt * 0.125f;
+        xstate[i] = xn;
+    }
+    __bf16 hi, lo;
+    split_bf16(xn, hi, lo);
+    xs_hi[(size_t)rc * ldx + c] = hi;
+    xs_lo[(size_t)rc * ldx + c] = lo;
+    if (ru >= 0) {
+        xs_hi[(size_t)ru * ldx + c] = hi;
+        xs_lo[(size_t)ru * ldx + c] = lo;
+    }
+}
+
 // out = cond_mask ? cond : x  (F/model/cfm.py:204); one block per utterance frame
 __global__ __launch_bounds__(128) void final_select_kernel(const float* xstate, const float* cond, const int* frame_is_cond,
                                                            int mel, int U, float* out) {

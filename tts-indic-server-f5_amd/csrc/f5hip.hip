@@ -57,8 +57,8 @@ struct f5hip_dit {
     int cap_rows = 0, cap_frames = 0, cap_seq = 0;
     DevBuf ws;   // one arena, carved below
     float *h = nullptr, *h0 = nullptr, *ce = nullptr, *pred = nullptr, *te = nullptr, *ty = nullptr, *gx = nullptr,
-          *mod = nullptr, *xstate = nullptr, *xmid = nullptr, *temb = nullptr;
-    int ode_method = 0;   // 0 = Euler, 1 = explicit midpoint (f5hip_dit_set_ode_method)
+          *mod = nullptr, *xstate = nullptr, *xmid = nullptr, *temb = nullptr, *rk_k2 = nullptr, *rk_k3 = nullptr;
+    int ode_method = 0;   // 0 = Euler, 1 = explicit midpoint, 2 = RK4 (3/8 rule; stages k1..k3 in xmid, rk_k2, rk_k3) (f5hip_dit_set_ode_method)
     std::vector<Plane2> skipbuf;
     Plane2 hn, c1, ao, ff, xs, tn, tg, act, sinp, t1, st;
     __bf16 *qk = nullptr, *vt = nullptr;
@@ -370,6 +370,7 @@ static int ensure_workspace(f5hip_dit* m, int rows_pad, int frames, int n_seq) {
         for (auto& sb : m->skipbuf) sb = a.plane2(R * 2 * D);   // [R][2 D]: the concatenated operand [x || skip] of the U-skip Linear, built in place
         // qk: +256 rows because the last query tile of the attention (up to 256 queries) may read (never store) past the padded rows
         m->qk = a.bf16((R + 256) * 2 * D); m->vt = a.bf16((size_t)D * R);
+        m->rk_k2 = a.f32(U * c.mel_dim); m->rk_k3 = a.f32(U * c.mel_dim);
         if (!pass) {
             if (hipMalloc(&m->ws.ptr, a.used()) != hipSuccess) { m->ws.ptr = nullptr; m->cap_rows = 0; return fail(-5, "hipMalloc workspace %zu bytes", a.used()); }
             if (hipMemset(m->ws.ptr, 0, a.used()) != hipSuccess) return fail(-5, "hipMemset workspace");
@@ -988,7 +989,7 @@ int f5hip_dit_get_profile(f5hip_dit* m, const char* kernel_class, double* total_
 
 int f5hip_dit_set_ode_method(f5hip_dit* m, int32_t method) {
     if (!m) return fail(-1, "null model");
-    if (method != 0 && method != 1) return fail(-1, "ode method %d: 0 = euler, 1 = midpoint", method);
+    if (method < 0 || method > 2) return fail(-1, "ode method %d: 0 = euler, 1 = midpoint, 2 = rk4", method);
     m->ode_method = method;
     return 0;
 }
@@ -1041,7 +1042,7 @@ int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, con
             prof_end(PROF_OTHER, st);
             CKL("cfg_euler");
         }
-    } else {
+    } else if (m->ode_method == 1) {
         // explicit midpoint on the fixed grid (torchdiffeq method="midpoint"): time points 2i = t_i, 2i + 1 = t_i + dt_i / 2
         if (2 * steps > 128) return fail(-8, "midpoint: at most 64 steps per call (got %d)", steps);
         std::vector<float> t2((size_t)2 * steps);
@@ -1065,6 +1066,33 @@ int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, con
                                cfg_strength, dt, m->xs.hi, m->xs.lo, 128);
             prof_end(PROF_OTHER, st);
             CKL("cfg_euler full");
+        }
+    } else {
+        // RK4 on the fixed grid (torchdiffeq method="rk4", the 3/8 rule): time points 3i = t_i, 3i + 1 = t_i + dt_i / 3, 3i + 2 = t_i + 2 dt_i / 3;
+        // the last stage of step i is evaluated at t_{i+1} = point 3 (i + 1), shared with the first stage of step i + 1
+        if (3 * steps + 1 > 128) return fail(-8, "rk4: at most 42 steps per call (got %d)", steps);
+        std::vector<float> t3((size_t)3 * steps + 1);
+        {
+#pragma clang fp contract(off)
+            for (int i = 0; i < steps; i++) {   // stage times in fp32, rounded as torch rounds t0 + dt * (1/3) and t0 + dt * (2/3)
+                const float dt = t_grid[i + 1] - t_grid[i];
+                t3[3 * i] = t_grid[i];
+                t3[3 * i + 1] = t_grid[i] + dt * (1.0f / 3.0f);
+                t3[3 * i + 2] = t_grid[i] + dt * (2.0f / 3.0f);
+            }
+        }
+        t3[3 * steps] = t_grid[steps];
+        CK(precompute_time(m, t3.data(), 3 * steps + 1, st));
+        for (int i = 0; i < steps; i++) {
+            const float dt = t_grid[i + 1] - t_grid[i];
+            for (int s = 1; s <= 4; s++) {
+                CK(forward_step(m, 3 * i + s - 1, -1, st));
+                prof_begin(PROF_OTHER, st);
+                hipLaunchKernelGGL(cfg_rk4_stage_kernel, dim3(f0), dim3(128), 0, st, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
+                                   cfg_strength, dt, s, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128);
+                prof_end(PROF_OTHER, st);
+                CKL("cfg_rk4_stage");
+            }
         }
     }
     hipLaunchKernelGGL(final_select_kernel, dim3(f0), dim3(128), 0, st, m->xstate, cond_dev, m->d_frame_is_cond, mel, f0, out_dev);

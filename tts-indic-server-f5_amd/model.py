@@ -77,6 +77,10 @@ class MMDiTArch:
         return 0
 
 
+# torchdiffeq method name -> f5hip_dit_set_ode_method code (include/f5hip.h)
+_ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2}
+
+
 def _i32(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
 
@@ -91,12 +95,12 @@ class F5HipModel:
     def __init__(self, arch: DiTArch | UNetTArch | MMDiTArch, state_dict: dict, vocab_char_map: dict | None = None, gemm_planes: int = 3,
                  device: str | torch.device = "cuda:0", mel_spec_type: str = "vocos", odeint_kwargs: dict | None = None,
                  attn_shape_invariant: bool | None = None):
-        # odeint_kwargs: CFM's constructor argument (F/model/cfm.py:37-41), dict(method="euler") by default; "midpoint" is the other
-        # fixed-grid solver the reference names.  Adaptive torchdiffeq solvers are not offered.
+        # odeint_kwargs: CFM's constructor argument (F/model/cfm.py:37-41), dict(method="euler") by default; "midpoint" (the other solver
+        # the reference names) and "rk4" are torchdiffeq's other fixed-grid solvers.  Adaptive torchdiffeq solvers are not offered.
         self.odeint_kwargs = dict(odeint_kwargs) if odeint_kwargs is not None else dict(method="euler")
         method = self.odeint_kwargs.get("method", "euler")
-        if method not in ("euler", "midpoint") or set(self.odeint_kwargs) - {"method"}:
-            raise ValueError(f"odeint_kwargs={self.odeint_kwargs!r}: only method='euler' or 'midpoint' on the fixed grid is supported")
+        if method not in _ODE_METHODS or set(self.odeint_kwargs) - {"method"}:
+            raise ValueError(f"odeint_kwargs={self.odeint_kwargs!r}: only method='euler', 'midpoint' or 'rk4' on the fixed grid is supported")
         self.arch = arch
         self.device = torch.device(device)
         self.vocab_char_map = vocab_char_map
@@ -120,7 +124,7 @@ class F5HipModel:
             a = np.ascontiguousarray(v.detach().to(torch.float32).cpu().numpy())
             _lib.check(self._lib.f5hip_dit_load_param(self._h, k.encode(), _ptr(a), a.size), "load_param " + k)
         _lib.check(self._lib.f5hip_dit_finalize(self._h), "f5hip_dit_finalize")
-        _lib.check(self._lib.f5hip_dit_set_ode_method(self._h, 1 if method == "midpoint" else 0), "f5hip_dit_set_ode_method")
+        _lib.check(self._lib.f5hip_dit_set_ode_method(self._h, _ODE_METHODS[method]), "f5hip_dit_set_ode_method")
         self.set_attention_shape_invariant(attn_shape_invariant)
 
     def set_attention_shape_invariant(self, on: bool | None):
