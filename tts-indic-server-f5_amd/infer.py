@@ -1,11 +1,12 @@
 """Drop-in mirror of the reference's inference driver (F/infer/utils_infer.py): module constants (:40-53),
 `chunk_text` (:61-88), `infer_process` (:357-400) and `infer_batch_process` (:406-524), with the same
 signatures, defaults, return triple and quirks (UTF-8 byte budgets, `ref_audio_len = nw // 256`, float64
-cross-fade ramps), running the sampler and vocoder on the HIP objects (`F5HipModel`, `F5HipVocos`).
+cross-fade ramps), running the sampler and vocoder on the HIP objects (`F5HipModel`, `F5HipVocos`).  Also the
+reference's speech-edit script (F/infer/speech_edit.py:119-192) as `plan_edit` / `speech_edit` / `speech_edit_batch`.
 
 Host-side differences, all explicit:
-  * reference audio is read with the stdlib `wave` module (16-bit PCM WAV) or passed as a `(tensor, sr)` pair:
-    torchaudio is not part of this image;
+  * reference audio is read by `load_wav` (a RIFF chunk walker: PCM 8/16/24/32-bit, IEEE float 32/64-bit, WAVE_FORMAT_EXTENSIBLE)
+    or passed as a `(tensor, sr)` pair: torchaudio is not part of this image;
   * resampling to 24 kHz restates torchaudio.transforms.Resample (sinc interpolation, Hann window, width 6, rolloff
     0.99; third-party leaf, parity unpinned) on the host, like the reference does before `.to(device)`;
   * `preprocess_ref_audio_text` (silence clipping of the reference clip, ". " rule) is restated without pydub in `audio_prep.py`;
@@ -15,8 +16,12 @@ Host-side differences, all explicit:
 """
 from __future__ import annotations
 
+import dataclasses
+import math
+import os
 import re
-import wave as _wave
+import struct
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -138,14 +143,90 @@ def resample_sinc_hann(wave: torch.Tensor, orig_freq: int, new_freq: int, lowpas
     return out[..., :target].reshape(*shape[:-1], target)
 
 
-def load_wav(path):
-    """16-bit PCM WAV -> (float32 tensor [channels, samples] in [-1, 1), sample_rate) like torchaudio.load."""
-    with _wave.open(path, "rb") as f:
-        sr, ch, sw, n = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
-        raw = f.readframes(n)
-    if sw != 2:
-        raise ValueError("only 16-bit PCM WAV reference audio is supported")
-    a = np.frombuffer(raw, dtype="<i2").reshape(-1, ch).T.astype(np.float32) / 32768.0
+_WAVE_FORMAT_PCM, _WAVE_FORMAT_IEEE_FLOAT, _WAVE_FORMAT_EXTENSIBLE = 0x0001, 0x0003, 0xFFFE
+_KSDATAFORMAT_TAIL = b"\x00\x00\x00\x00\x10\x00\x80\x00\x00\xaa\x00\x38\x9b\x71"   # bytes 2..15 of every KSDATAFORMAT_SUBTYPE_* GUID
+_WAVE_FORMAT_NAMES = {0x0002: "MS ADPCM", 0x0006: "A-law", 0x0007: "mu-law", 0x0011: "IMA ADPCM", 0x0031: "GSM 6.10",
+                      0x0050: "MPEG", 0x0055: "MPEG Layer 3", 0x00FF: "AAC", 0x1610: "HE-AAC", 0xF1AC: "FLAC"}
+
+
+def _wave_format_name(tag):
+    return f"format code {tag:#06x}" + (f" ({_WAVE_FORMAT_NAMES[tag]})" if tag in _WAVE_FORMAT_NAMES else "")
+
+
+def load_wav(src):
+    """WAV file -> (float32 tensor [channels, samples], sample_rate), scaled like torchaudio.load: PCM 8-bit unsigned
+    ((x - 128) / 128), 16/24/32-bit signed (/ 2**15, / 2**23, / 2**31), IEEE float 32/64-bit as stored; WAVE_FORMAT_EXTENSIBLE with a
+    PCM or float sub-format; any channel count.  `src` is a path, the file's bytes, or a binary file object.  A small RIFF chunk walker
+    instead of the stdlib `wave` module, which reads neither float nor EXTENSIBLE files.  Anything else (FLAC, MP3, compressed WAV
+    format codes, a truncated file) raises ValueError naming what was found."""
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        data = bytes(src)
+    elif hasattr(src, "read"):
+        data = src.read()
+    else:
+        with open(os.fspath(src), "rb") as f:
+            data = f.read()
+    if data[:4] == b"fLaC":
+        raise ValueError("not a WAV file: FLAC stream ('fLaC' magic)")
+    if data[:3] == b"ID3" or (len(data) > 1 and data[0] == 0xFF and data[1] & 0xE0 == 0xE0):
+        raise ValueError("not a WAV file: MPEG audio (MP3) stream")
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+        raise ValueError(f"not a RIFF/WAVE file (starts with {data[:12]!r})")
+    fmt = body = None
+    pos = 12
+    while pos + 8 <= len(data):
+        cid, size = data[pos:pos + 4], struct.unpack_from("<I", data, pos + 4)[0]
+        start, end = pos + 8, pos + 8 + size
+        if cid == b"fmt ":
+            if end > len(data) or size < 16:
+                raise ValueError(f"truncated WAV: 'fmt ' chunk of {size} bytes, {len(data) - start} present")
+            fmt = data[start:end]
+        elif cid == b"data":
+            if end > len(data):
+                raise ValueError(f"truncated WAV: 'data' chunk declares {size} bytes, {len(data) - start} present")
+            body = data[start:end]
+            if fmt is not None:
+                break
+        pos = end + (size & 1)          # chunks are word-aligned
+    if fmt is None or body is None:
+        raise ValueError("truncated WAV: no " + ("'fmt '" if fmt is None else "'data'") + " chunk")
+    tag, ch, sr, _, _, bits = struct.unpack_from("<HHIIHH", fmt, 0)
+    if tag == _WAVE_FORMAT_EXTENSIBLE:
+        if len(fmt) < 40:
+            raise ValueError(f"truncated WAV: WAVE_FORMAT_EXTENSIBLE 'fmt ' chunk of {len(fmt)} bytes (needs 40)")
+        guid = fmt[24:40]
+        sub = struct.unpack_from("<H", guid, 0)[0]
+        if guid[2:] != _KSDATAFORMAT_TAIL:
+            raise ValueError(f"unsupported WAV: WAVE_FORMAT_EXTENSIBLE with sub-format GUID {guid.hex()}")
+        if sub not in (_WAVE_FORMAT_PCM, _WAVE_FORMAT_IEEE_FLOAT):
+            raise ValueError(f"unsupported WAV: WAVE_FORMAT_EXTENSIBLE with sub-format {_wave_format_name(sub)}")
+        tag = sub
+    if ch < 1:
+        raise ValueError(f"unsupported WAV: {ch} channels")
+    if tag == _WAVE_FORMAT_PCM and bits in (8, 16, 24, 32):
+        kind = "pcm"
+    elif tag == _WAVE_FORMAT_IEEE_FLOAT and bits in (32, 64):
+        kind = "float"
+    elif tag in (_WAVE_FORMAT_PCM, _WAVE_FORMAT_IEEE_FLOAT):
+        raise ValueError(f"unsupported WAV: {'PCM' if tag == _WAVE_FORMAT_PCM else 'IEEE float'} at {bits} bits per sample")
+    else:
+        raise ValueError(f"unsupported WAV: {_wave_format_name(tag)}")
+    width = bits // 8
+    n = len(body) // (width * ch)       # whole frames only, like wave.readframes
+    raw = body[:n * width * ch]
+    if kind == "float":
+        x = np.frombuffer(raw, dtype="<f4" if bits == 32 else "<f8").astype(np.float32)
+    elif bits == 8:
+        x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
+    elif bits == 16:
+        x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
+    elif bits == 24:
+        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        x = ((v << 8) >> 8).astype(np.float32) / 8388608.0      # sign-extend the 24-bit value
+    else:
+        x = np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
+    a = x.reshape(-1, ch).T
     return torch.from_numpy(np.ascontiguousarray(a)), sr
 
 
@@ -337,3 +418,203 @@ def infer_multi_voice(text_gen, voices, model_obj, vocoder, **kw):
         raise ValueError("nothing to synthesize")
     res = infer_requests([(voices[v]["ref_audio"], voices[v]["ref_text"], t) for v, t in pieces], model_obj, vocoder, **kw)
     return np.concatenate([w for w, _, _ in res]), target_sample_rate, [s for _, _, s in res]
+
+
+# ----------------------------------------- F/infer/speech_edit.py:119-192
+max_duration = 4096   # CFM.sample's default clamp (F/model/cfm.py:92,137)
+
+
+@dataclass(frozen=True)
+class EditPlan:
+    """What `plan_edit` derives from a recording's length and the spans to regenerate, at hop resolution.
+    `segments`: the conditioning wave as ((start, stop, zeros), ...) -- samples [start, stop) of the prepared recording followed by
+    `zeros` zero samples; `length`: its length L; `duration`: the frames requested from the sampler (L // 256); `edit_mask`: bool
+    [L // 256 + 1], True = keep the frame, False = regenerate it."""
+    segments: tuple
+    length: int
+    duration: int
+    edit_mask: torch.Tensor
+
+    def cond(self, audio):
+        """The conditioning wave [1, L] built from the prepared recording `audio` [1, n_samples]."""
+        parts = []
+        for start, stop, zeros in self.segments:
+            parts.append(audio[:, start:stop])
+            if zeros:
+                parts.append(torch.zeros(audio.shape[0], zeros, dtype=audio.dtype, device=audio.device))
+        return torch.cat(parts, dim=-1)
+
+
+def plan_edit(n_samples, parts_to_edit, fix_duration=None, mel_spec_type=mel_spec_type):
+    """The splice and mask arithmetic of F/infer/speech_edit.py:129-148 for a recording of `n_samples` samples at 24 kHz (after the
+    mono mix and the rms gain); `parts_to_edit` = [[start_s, end_s], ...] on that timeline, `fix_duration` = one length in seconds per
+    part or None.  Same rounding as the reference (Python's round: round(112.5) == 112) and the same truncation (the mask is padded with
+    True to L // 256 + 1, or cut there, as F.pad does with a negative pad).  `fix_duration` is not mutated (the reference pops it).
+
+    One deliberate difference: the reference builds the spliced wave but never uses it (the line that appends the tail and swaps it
+    in is commented out, speech_edit.py:147), so its `cond` is the original recording while a `fix_duration` mask is laid out on the
+    spliced timeline -- from the second part on that mask marks the wrong frames.  Here, with `fix_duration=None` the reference is
+    reproduced exactly (cond = the recording, L = n_samples); with `fix_duration` the splice that commented line describes is used (the
+    kept slices with each part replaced by zeros of its new length, then the tail), so every new span gets its requested length.
+
+    Rejected with ValueError before anything is sized by them: parts that are non-finite, empty, unsorted, overlapping or outside the
+    recording; a `fix_duration` of the wrong length or with non-finite or non-positive entries; and an edit whose final frame count
+    (the mel frames of `mel_spec_type`'s front-end + 1, cfm.py:136) exceeds the sampler's max_duration, which would clamp the output
+    below the mask.  The length and frame count are worked out from the segments first; the mask is built only for an edit that fits."""
+    sr = target_sample_rate
+    if mel_spec_type not in ("vocos", "bigvgan"):
+        raise ValueError(mel_spec_type)
+    parts = [list(p) for p in parts_to_edit]
+    if not parts:
+        raise ValueError("parts_to_edit is empty: give at least one [start, end] span in seconds")
+    spans, prev_end = [], 0.0
+    for i, p in enumerate(parts):
+        if len(p) != 2:
+            raise ValueError(f"parts_to_edit[{i}] = {p!r}: expected [start, end] in seconds")
+        start, end = float(p[0]), float(p[1])
+        if not (math.isfinite(start) and math.isfinite(end)):
+            raise ValueError(f"parts_to_edit[{i}] = {p!r}: start and end must be finite numbers of seconds")
+        if not end > start:
+            raise ValueError(f"parts_to_edit[{i}] = {p!r} is empty: end must be after start")
+        if start < 0 or round(end * sr) > n_samples:
+            raise ValueError(f"parts_to_edit[{i}] = {p!r} lies outside the recording (0 to {n_samples / sr:.4f} s)")
+        if start < prev_end:
+            raise ValueError(f"parts_to_edit[{i}] = {p!r} is unsorted or overlaps the previous part (which ends at {prev_end} s)")
+        spans.append((start, end))
+        prev_end = end
+    # the longest edit the sampler can hold: its final frame count (mel frames + 1, cfm.py:136) within max_duration
+    max_samples = (max_duration - 1 - _mel_frames(0, mel_spec_type)) * hop_length + hop_length - 1
+    if fix_duration is not None:
+        fix = [float(d) for d in fix_duration]
+        if len(fix) != len(spans):
+            raise ValueError(f"fix_duration has {len(fix)} entries for {len(spans)} parts_to_edit")
+        if any(not (math.isfinite(d) and d > 0) for d in fix):
+            raise ValueError(f"fix_duration = {list(fix_duration)!r}: every entry must be a finite, positive number of seconds")
+        if any(d * sr > max_samples for d in fix):   # (bounds every product below before anything is sized by it)
+            raise ValueError(f"fix_duration = {list(fix_duration)!r}: an edit longer than {max_samples / sr:.2f} s exceeds the sampler's "
+                             f"max_duration of {max_duration} frames")
+    # the conditioning wave's segments and length, worked out before the mask is built
+    offset = 0
+    segments, runs = [], []
+    for i, (start, end) in enumerate(spans):
+        part_dur = end - start if fix_duration is None else fix[i]
+        part_dur = part_dur * sr
+        start = start * sr
+        segments.append((round(offset), round(start), round(part_dur)))
+        runs.append((round((start - offset) / hop_length), round(part_dur / hop_length)))
+        offset = end * sr
+    if fix_duration is None:
+        segments = [(0, n_samples, 0)]
+    else:
+        segments.append((round(offset), n_samples, 0))
+    length = sum(stop - start + zeros for start, stop, zeros in segments)
+    if length > max_samples:
+        raise ValueError(f"the edited recording needs {_mel_frames(length, mel_spec_type) + 1} frames; the sampler's max_duration is "
+                         f"{max_duration} ({max_samples / sr:.2f} s)")
+    frames = length // hop_length + 1
+    mask = torch.ones(frames, dtype=torch.bool)          # padded with True to L // 256 + 1, or cut there (F.pad, speech_edit.py:148)
+    k = 0
+    for ones, zeros in runs:
+        k += ones
+        mask[min(k, frames):min(k + zeros, frames)] = False
+        k += zeros
+    return EditPlan(tuple(segments), length, length // hop_length, mask)
+
+
+def _mel_frames(n_samples, mel_spec_type):
+    """Frames of the mel front-end of `mel_spec_type` for a wave of n_samples: 1 + n // hop (vocos, centred STFT) or n // hop (bigvgan)."""
+    return n_samples // hop_length + (1 if mel_spec_type == "vocos" else 0)
+
+
+@dataclass(frozen=True)
+class PreparedEdit:
+    """The host part of one speech edit (`prepare_edit`): the conditioning wave [1, L], the target text's tokens, the plan, the mask cut to
+    the mel front-end's frames, the recording's measured rms, and the settings they were made with.  `speech_edit_batch` accepts it
+    wherever an (audio, target_text, parts_to_edit, fix_duration) tuple is expected."""
+    cond: torch.Tensor
+    tokens: list
+    plan: EditPlan
+    edit_mask: torch.Tensor
+    rms: torch.Tensor
+    mel_spec_type: str
+    target_rms: float
+
+
+def prepare_edit(audio, target_text, parts_to_edit, fix_duration=None, mel_spec_type=mel_spec_type, target_rms=target_rms, device=None,
+                 tokenizer=text_to_tokens):
+    """Host part of F/infer/speech_edit.py:120-163 for one edit, no device work: read the recording (a path, WAV bytes or a (tensor, sr)
+    pair), mono mix, rms gain to `target_rms` when below it, resample to 24 kHz, `plan_edit`, tokenise, build the conditioning wave.
+    Raises ValueError for an empty text, a text with more tokens than the recording has mel frames, or a rejected plan."""
+    if not isinstance(target_text, str) or not target_text.strip():
+        raise ValueError("target_text is empty: give the full transcript of the edited recording")
+    wav, sr = audio if isinstance(audio, tuple) else load_wav(audio)
+    wav, rms = _prepare_reference(wav, sr, target_rms, None)
+    plan = plan_edit(wav.shape[-1], parts_to_edit, fix_duration, mel_spec_type)
+    tokens = tokenizer([target_text])[0]
+    frames = _mel_frames(plan.length, mel_spec_type)
+    if len(tokens) > frames:
+        raise ValueError(f"target_text has {len(tokens)} tokens, more than the {frames} mel frames of the "
+                         f"{plan.length / target_sample_rate:.2f} s recording")
+    cond = plan.cond(wav)
+    return PreparedEdit(cond if device is None else cond.to(device), tokens, plan, plan.edit_mask[:frames], rms, mel_spec_type, target_rms)
+
+
+def speech_edit_batch(edits, model_obj, vocoder, mel_spec_type=mel_spec_type, target_rms=target_rms, nfe_step=nfe_step,
+                      cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None, device=None, tokenizer=text_to_tokens):
+    """Several speech edits in ONE sampler call: `edits` = [(audio, target_text, parts_to_edit, fix_duration) | PreparedEdit], `audio` a
+    path, the bytes of a WAV file, or a (tensor, sr) pair.  Returns one (wave float32, 24000, spec [100, T]) triple per edit, each what
+    `speech_edit` returns for that edit alone: every edit keeps the reference's batch-1 semantics (its own prompt length `lens` and its
+    own edit mask), its noise is drawn in order like sequential calls draw it, and it is vocoded and rms-restored on its own.  Bit for
+    bit this holds when the model handle runs the shape-invariant attention arithmetic (see `infer_requests`).
+
+    Per edit, F/infer/speech_edit.py:120-192: `prepare_edit` (mono mix, rms gain, 24 kHz, `plan_edit`, tokens); `sample(cond, text,
+    duration=L // 256, edit_mask)`; vocode every frame (`ref_audio_len = 0`); restore the rms.  Text goes through `text_to_tokens`, the
+    tokenisation `infer_process` uses (the script's non-pinyin branch wraps the list once more, `[text_list]`).
+    With mel_spec_type="bigvgan" the front-end yields L // 256 mel frames, one fewer than the reference's mask, which then fails to
+    broadcast in `cond_mask & edit_mask` (cfm.py:130); the mask is cut to the mel's frames here, its last entry having no frame.
+
+    The model object needs the reference's `sample()`; with `cond_mel` (F5HipModel) the edits are handed over as one padded mel batch,
+    any other object is driven edit by edit with the raw wave, like the reference does."""
+    if mel_spec_type not in ("vocos", "bigvgan"):
+        raise ValueError(mel_spec_type)
+    preps = []
+    for e in edits:
+        if isinstance(e, PreparedEdit):
+            if (e.mel_spec_type, e.target_rms) != (mel_spec_type, target_rms):
+                raise ValueError(f"PreparedEdit made for mel_spec_type={e.mel_spec_type!r}, target_rms={e.target_rms}; this call uses "
+                                 f"{mel_spec_type!r}, {target_rms}")
+            preps.append(e if device is None else dataclasses.replace(e, cond=e.cond.to(device)))
+        else:
+            audio, target_text, parts_to_edit, fix_duration = e
+            preps.append(prepare_edit(audio, target_text, parts_to_edit, fix_duration, mel_spec_type, target_rms, device, tokenizer))
+    knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+    if hasattr(model_obj, "cond_mel"):
+        mels = [model_obj.cond_mel(p.cond)[0] for p in preps]
+        lens = torch.tensor([m.shape[0] for m in mels], dtype=torch.long)
+        edit_mask = torch.zeros(len(preps), int(lens.max()), dtype=torch.bool)    # (past an edit's lens its cond_mask is False anyway)
+        for i, p in enumerate(preps):
+            edit_mask[i, :p.edit_mask.shape[0]] = p.edit_mask
+        out, _ = model_obj.sample(cond=torch.nn.utils.rnn.pad_sequence(mels, batch_first=True), text=[p.tokens for p in preps],
+                                  duration=torch.tensor([p.plan.duration for p in preps], dtype=torch.long), lens=lens,
+                                  edit_mask=edit_mask, **knobs)
+        # each edit's rows: its final duration max(lens + 1, L // 256) (cfm.py:136), i.e. lens + 1
+        gens = [out[i, :max(int(lens[i]) + 1, p.plan.duration)] for i, p in enumerate(preps)]
+    else:
+        gens = [model_obj.sample(cond=p.cond, text=[p.tokens], duration=p.plan.duration, edit_mask=p.edit_mask[None], **knobs)[0][0]
+                for p in preps]
+    res = []
+    for gen, p in zip(gens, preps):
+        wave, sr, spec = _vocode_and_join([gen], 0, p.rms, vocoder, mel_spec_type, target_rms, 0)
+        res.append((np.asarray(wave, dtype=np.float32), sr, spec))
+    return res
+
+
+def speech_edit(audio, target_text, parts_to_edit, model_obj, vocoder, fix_duration=None, mel_spec_type=mel_spec_type,
+                target_rms=target_rms, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
+                seed=None, device=None):
+    """F/infer/speech_edit.py:119-192 as a call: regenerate `parts_to_edit` ([[start_s, end_s], ...]) of the recording `audio` (a path,
+    WAV bytes or a (tensor, sr) pair) so that it speaks `target_text` (the full new transcript) in the same voice, keeping every other
+    frame.  Returns (wave float32, 24000, spec [100, T]).  `speech_edit_batch` with one edit; see there and `plan_edit`."""
+    return speech_edit_batch([(audio, target_text, parts_to_edit, fix_duration)], model_obj, vocoder, mel_spec_type=mel_spec_type,
+                             target_rms=target_rms, nfe_step=nfe_step, cfg_strength=cfg_strength,
+                             sway_sampling_coef=sway_sampling_coef, seed=seed, device=device)[0]

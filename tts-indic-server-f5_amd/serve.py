@@ -19,8 +19,12 @@ Differences, explicit:
     the library's shape-invariant attention mode (`batch_invariant=True`); without it the same utterance alone and inside a batch can take
     different attention kernels, which agree to the last bits per launch but -- in the mixed GEMM mode -- drift apart to that mode's
     rounding-noise floor over a sample (measured 4.4e-4 rms after two Euler steps, `profiles/r03_attn_mode_tapdiff.txt`).
+  * `POST /v1/audio/edit` + `TTSManager.edit`: the reference's speech-edit script (F/infer/speech_edit.py, a CLI there) as a route; the
+    recording arrives base64-encoded in a JSON body (multipart uploads need python-multipart, which this image does not have).
 """
 
+import base64
+import binascii
 import io
 import queue
 import threading
@@ -219,6 +223,22 @@ class TTSManager:
             raise ValueError("TTS model not loaded")
         return self.model(text, ref_audio_path=ref_audio_path, ref_text=ref_text)
 
+    def edit(self, audio, target_text, parts_to_edit, fix_duration=None):
+        """Speech editing (`infer.speech_edit`, F/infer/speech_edit.py): regenerate `parts_to_edit` of the recording `audio` (a path, WAV
+        bytes or a (tensor, sr) pair) so that it speaks `target_text`, with this manager's sampler settings.  The host preparation runs
+        outside the device lock, the sampler and vocoder under it (not through the micro-batcher); with a `ShardedSampler` on rank 0's own
+        model.  Returns the wave (float32, 24 kHz)."""
+        if not self.model:
+            raise ValueError("TTS model not loaded")
+        model_obj = getattr(self.model_obj, "local", self.model_obj)
+        # host work (read, mono mix, resample, plan, tokens) and every rejection happen before the device lock is taken
+        prep = infer.prepare_edit(audio, target_text, parts_to_edit, fix_duration, mel_spec_type=self.mel_spec_type)
+        with self._device_lock:
+            (wave, _, _), = infer.speech_edit_batch([prep], model_obj, self.vocoder, mel_spec_type=self.mel_spec_type,
+                                                    nfe_step=self.opts["nfe_step"], cfg_strength=self.opts["cfg_strength"],
+                                                    sway_sampling_coef=self.opts["sway_sampling_coef"])
+        return np.asarray(wave, dtype=np.float32)
+
 
 def wav_bytes(audio: np.ndarray, sample_rate: int = infer.target_sample_rate) -> io.BytesIO:
     a = np.asarray(audio)
@@ -256,7 +276,9 @@ def synthesize_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: st
 
 
 def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
-    """FastAPI app with the reference's `/v1/audio/speech` route (`S/routes/speech.py:19-41`)."""
+    """FastAPI app with the reference's `/v1/audio/speech` route (`S/routes/speech.py:19-41`) and `/v1/audio/edit` (speech editing:
+    JSON body {"audio": base64 WAV, "text": the full new transcript, "parts_to_edit": [[start_s, end_s], ...], "fix_duration": [...] | null}
+    -> the edited recording as WAV)."""
     from fastapi import APIRouter, FastAPI, HTTPException
     from pydantic import BaseModel
     from starlette.responses import StreamingResponse
@@ -268,6 +290,12 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         text: str
         ref_audio_name: str
         ref_text: str | None = None
+
+    class EditRequest(BaseModel):                    # F/infer/speech_edit.py's inputs; JSON (base64 WAV), not multipart
+        audio: str
+        text: str
+        parts_to_edit: list[list[float]]
+        fix_duration: list[float] | None = None
 
     router = APIRouter(prefix="/v1", tags=["speech"])
 
@@ -282,6 +310,26 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
             raise HTTPException(status_code=e.status_code, detail=e.detail)
         return StreamingResponse(buf, media_type="audio/wav", headers={"Content-Disposition": f"attachment; filename={filename}"})
 
+    def _run_edit(req):
+        if not tts_manager.model:
+            raise HTTPException(status_code=503, detail="TTS model not loaded")
+        try:
+            raw = base64.b64decode(req.audio, validate=True)
+        except (binascii.Error, ValueError):
+            raise HTTPException(status_code=400, detail="Audio must be a base64-encoded WAV file.")
+        if not req.text.strip():
+            raise HTTPException(status_code=400, detail="Text to synthesize cannot be empty.")
+        try:
+            audio = infer.load_wav(raw)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Invalid audio: {e}")
+        try:
+            wave = tts_manager.edit(audio, req.text, req.parts_to_edit, req.fix_duration)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        return StreamingResponse(wav_bytes(wave), media_type="audio/wav",
+                                 headers={"Content-Disposition": "attachment; filename=edited_speech.wav"})
+
     # The reference's handlers are `async def` around a blocking call, i.e. one request at a time.  Here the blocking part runs in
     # starlette's thread pool, so concurrent requests overlap and meet in the MicroBatcher queue (when the manager has one).
     from starlette.concurrency import run_in_threadpool
@@ -293,6 +341,10 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     @router.post("/audio/speech/voice", response_class=StreamingResponse)
     async def synthesize_with_voice(request: SynthesizeRequest):     # the generic form the reference's helper already supports
         return await run_in_threadpool(_run, request.text, request.ref_audio_name, request.ref_text, "synthesized_speech.wav")
+
+    @router.post("/audio/edit", response_class=StreamingResponse)
+    async def edit_speech(request: EditRequest):                    # speech editing (F/infer/speech_edit.py) over the same manager
+        return await run_in_threadpool(_run_edit, request)
 
     app = FastAPI(title="F5-TTS on MI355X (HIP path)")
     app.include_router(router)
