@@ -124,8 +124,10 @@ int f5hip_dit_get_profile(f5hip_dit* m, const char* kernel_class, double* total_
 int f5hip_set_profiling(int32_t enabled);
 int f5hip_get_profile(const char* kernel_class, double* total_ms, int64_t* launches);
 /* Launch counters of the GEMM dispatcher since the last reset (test instrumentation: proves which kernel a config exercised):
- * "gemm5_rb11" / "gemm5_rb8" (exact-fit tile heights 176 / 128), "gemm5_wide" (128- and 192-column tiles), "gemm3_wide",
- * "gemm6" (256 x 256 ping-pong tiles: the batch-mode shapes);
+ * "gemm5_rb11" / "gemm5_rb8" (exact-fit tile heights 176 / 128), "gemm5_wide" (128- and 192-column tiles), "gemm5_cb12" (192-column
+ * tiles only), "gemm3_wide" (fp16 128 x 256 tiles), "gemm3" (every gemm3 launch, wide or not), "conv5", "gemm6" (ping-pong tiles
+ * of 256 columns: the batch-mode shapes), "gemm6_r176" / "gemm6_r256" (gemm6 by tile height), "gemm_reg_bn64" / "gemm_reg_bn128"
+ * (every gemm.h launch by column-tile width, convolutions included);
  * name "reset" zeroes all of them (value may be NULL). */
 int f5hip_get_counter(const char* name, int64_t* value);
 
@@ -139,10 +141,13 @@ int f5hip_get_counter(const char* name, int64_t* value);
  *   row_keep_host uint8 [M] | NULL (host); prec 1 = bf16, 2 = split bf16 (bf16x3), 3 = fp16 operands, fp32 accumulate;
  *   act 0 none, 1 GELU(tanh), 2 GELU(erf), 3 Mish, 4 SiLU.  out_dev fp32 [M][N], or out16_dev: one fp16 plane [M][N] (the operand the
  *   next fp16 GEMM reads; saturates at +-65504).  iters > 0: also times `iters` launches with HIP events on `stream`, cycling through
- *   w_copies copies of the packed weights (a pool larger than the Infinity Cache makes them HBM-cold as in the real forward). */
+ *   w_copies copies of the packed weights (a pool larger than the Infinity Cache makes them HBM-cold as in the real forward).
+ *   bn: the column-tile width the call site asks for where the dispatcher picks the register-staged gemm.h kernel (bf16 / split-bf16
+ *   operands, many tiles): 0 or 128 (the projection / FF1 call sites), or 64 (the residual and UNetT skip call sites); the other
+ *   kernels ignore it. */
 int f5hip_op_gemm(int32_t M, int32_t N, int32_t K, const float* a_dev, const float* w_dev, const float* bias_dev, int32_t prec,
                   int32_t act, const float* mul_dev, const float* res_dev, const uint8_t* row_keep_host, float* out_dev,
-                  uint16_t* out16_dev, int32_t w_copies, int32_t iters, double* avg_us, void* stream);
+                  uint16_t* out16_dev, int32_t w_copies, int32_t iters, double* avg_us, void* stream, int32_t bn);
 /* f5hip_op_qkv: fused to_q | to_k | to_v projection with its epilogue: bias, rotary embedding on channels 0..63 (head 0, interleaved
  *   pairs) of q and k, q * log2(e) / 8 (the attention kernel's scores are base-2 exponents), V transposed (F/model/modules.py:409-426).  a_dev [M][D], w_dev [3 D][D], bias_dev [3 D], row_pos host
  *   int32 [M] (rotary position of every row, 0..4096); outputs fp16 (saturated): qk_dev [ceil128(M)][2 D], vt_dev [D][ceil128(M)] with the tokens of

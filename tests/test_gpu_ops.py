@@ -63,32 +63,76 @@ def _rel(got, ref):
     return ((got.double().cpu() - ref.cpu()).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt().clamp_min(1e-30)).item()
 
 
+# Every launch counter of the GEMM dispatcher (csrc/f5hip.hip run_gemm_n); a row names the ones its single launch must raise to 1, all others stay 0
+PATH_COUNTERS = ("gemm5_rb11", "gemm5_rb8", "gemm5_wide", "gemm5_cb12", "gemm3", "gemm3_wide", "gemm6", "gemm6_r176", "gemm6_r256",
+                 "gemm_reg_bn64", "gemm_reg_bn128", "conv5")
+G5_11_4, G5_11_8, G5_11_12 = ("gemm5_rb11",), ("gemm5_rb11", "gemm5_wide"), ("gemm5_rb11", "gemm5_wide", "gemm5_cb12")
+G5_8_4, G5_8_8 = ("gemm5_rb8",), ("gemm5_rb8", "gemm5_wide")
+G6_176, G6_256 = ("gemm6", "gemm6_r176"), ("gemm6", "gemm6_r256")
+G3, REG64, REG128 = ("gemm3",), ("gemm_reg_bn64",), ("gemm_reg_bn128",)
+
+
+def _assert_path(expected):
+    got = {n: _counter(n) for n in PATH_COUNTERS}
+    want = {n: int(n in expected) for n in PATH_COUNTERS}
+    assert got == want, f"dispatcher path: got {got}, expected {want}"
+
+
+# Expected paths follow csrc/gemm_launch.h: t256 / t176 = gemm6 tiles of 256 / 176 rows x 256 columns (gemm6 needs t256 or t176 >= 224; cost
+# = rounds of 256 CUs, x 0.85 for 176-row tiles); gemm5_choose = fewest rounds x (16 rb + 16 cb); t128 = 128 x 128 tiles (split-bf16 / bf16
+# operands: gemm3 when t128 <= 256, else gemm.h with the call site's bn).
 CASES = [
-    # (M, N, K, prec, act, bias, mul, res, row_keep, out16, expected counter)
-    (2816, 1024, 1024, 3, "none", True, True, True, False, False, "gemm5_rb11"),      # attention out-projection, C2 (176 x 64 tiles)
-    (2816, 1024, 2048, 3, "none", True, True, True, False, False, "gemm5_rb11"),      # FF2, C2
-    (2816, 2048, 1024, 3, "gelu_tanh", True, False, False, False, True, "gemm5_wide"),  # FF1, C2: fp16 plane out (176 x 128 tiles)
-    (2816, 1024, 1024, 3, "none", True, False, True, True, False, "gemm5_rb11"),      # masked rows (padded-batch semantics)
-    (1404, 1024, 1024, 3, "none", True, True, True, False, False, None),               # M not a multiple of any tile height: partial row slab
-    (1536, 768, 768, 3, "none", True, True, True, False, False, "gemm5_rb8"),         # F5-Small widths (C1): 128-row tiles
-    (2816, 100, 1024, 3, "none", True, False, False, False, False, None),              # N = mel_dim: partial column panel
-    (2816, 1024, 128, 3, "silu", True, False, False, False, False, None),              # K shorter than the ring depth
-    (22528, 1024, 1024, 3, "none", True, True, True, False, False, "gemm6"),           # C3 share: 8 utterances x 2 branches (batch mode: 256 x 256 ping-pong tiles)
-    (22528, 2048, 1024, 3, "gelu_tanh", True, False, False, False, True, "gemm6"),      # FF1 at the C3 share: fp16 plane out
-    (22528, 1024, 2048, 3, "none", True, True, True, False, False, "gemm6"),           # FF2 at the C3 share (32 K-tiles)
-    (22400, 1024, 1024, 3, "none", True, True, True, True, False, "gemm6"),            # ragged batch: the last 256-row tile has 128 valid rows; masked rows
-    (16384, 1024, 64, 3, "silu", True, False, False, False, False, "gemm6"),           # one K-tile only (prologue without a second tile)
-    (16384, 1024, 128, 3, "none", True, False, True, False, False, "gemm6"),           # two K-tiles
-    (2816, 1024, 1024, 2, "none", True, True, True, False, False, None),               # bf16x3 (strict mode)
-    (2816, 2048, 1024, 1, "gelu_tanh", True, False, False, False, False, None),        # plain bf16
-    (200, 512, 1024, 2, "gelu_erf", True, False, False, False, False, None),           # Vocos-sized, erf GELU
+    # (M, N, K, prec, act, bias, mul, res, row_keep, out16, bn, expected counters)
+    (2816, 1024, 1024, 3, "none", True, True, True, False, False, 128, G5_11_4),    # attention out-projection, C2 (176 x 64 tiles)
+    (2816, 1024, 2048, 3, "none", True, True, True, False, False, 128, G5_11_4),    # FF2, C2
+    (2816, 2048, 1024, 3, "gelu_tanh", True, False, False, False, True, 128, G5_11_8),   # FF1, C2: fp16 plane out (176 x 128 tiles)
+    (2816, 1024, 1024, 3, "none", True, False, True, True, False, 128, G5_11_4),    # masked rows (padded-batch semantics)
+    (1404, 1024, 1024, 3, "none", True, True, True, False, False, 128, G5_8_4),     # M not a multiple of any tile height: partial row slab (11 x 16 = 176 tiles of 128 x 64)
+    (1536, 768, 768, 3, "none", True, True, True, False, False, 128, G5_8_4),       # F5-Small widths (C1): 128-row tiles
+    (2816, 100, 1024, 3, "none", True, False, False, False, False, 128, G5_8_4),    # N = mel_dim: partial column panel (n_pad 128: rb 8 x cb 4, 44 tiles, cost 192)
+    (2816, 1024, 128, 3, "silu", True, False, False, False, False, 128, G5_11_4),   # K shorter than the ring depth
+    (22528, 1024, 1024, 3, "none", True, True, True, False, False, 128, G6_176),    # C3 share: 8 utterances x 2 branches (batch mode); t256 = 352 (2 rounds), t176 = 512 (1.7)
+    (22528, 2048, 1024, 3, "gelu_tanh", True, False, False, False, True, 128, G6_256),   # FF1 at the C3 share: fp16 plane out; t256 = 704 (3), t176 = 1024 (3.4)
+    (22528, 1024, 2048, 3, "none", True, True, True, False, False, 128, G6_176),    # FF2 at the C3 share (32 K-tiles)
+    # ragged batch, masked rows: t256 = 352 (2 rounds), t176 = 512 (1.7) -> 176-row tiles; 22400 = 127 x 176 + 48: the last tile has 48 valid rows
+    (22400, 1024, 1024, 3, "none", True, True, True, True, False, 128, G6_176),
+    (16384, 1024, 64, 3, "silu", True, False, False, False, False, 128, G6_256),    # one K-tile only (prologue without a second tile); t256 = 256 (1), t176 = 376 (1.7)
+    (16384, 1024, 128, 3, "none", True, False, True, False, False, 128, G6_256),    # two K-tiles
+    (2816, 1024, 1024, 2, "none", True, True, True, False, False, 128, G3),         # bf16x3 (strict mode): t128 = 176
+    (2816, 2048, 1024, 1, "gelu_tanh", True, False, False, False, False, 128, REG128),   # plain bf16: t128 = 352
+    (200, 512, 1024, 2, "gelu_erf", True, False, False, False, False, 128, G3),     # Vocos-sized, erf GELU: t128 = 8
+    # ---- the gemm.h call sites that pass bn = 64 (run_gemm_ln, the UNetT skip, Vocos pwconv2) and the remaining (kernel, template) pairs
+    (4864, 1024, 2048, 2, "none", False, False, False, False, False, 64, REG64),    # UNetT skip Linear(2 D -> D), one E2 chunk (C5): t128 = 38 x 8 = 304
+    (14592, 1024, 2048, 2, "none", False, False, False, False, False, 64, REG64),   # UNetT skip at the C5 share (3 chunks x 2 branches x 2432 rows): t128 = 912
+    (2816, 1024, 2048, 2, "none", True, True, True, False, False, 64, G3),          # strict-mode FF2, C2: t128 = 176 <= 256 -> gemm3 (bn unused)
+    (22528, 1024, 1024, 2, "none", True, True, True, False, False, 64, REG64),      # strict-mode out-projection at the C3 share: t128 = 1408
+    (22528, 1024, 1024, 1, "none", True, True, True, False, False, 64, REG64),      # plain-bf16 residual GEMM at the C3 share: t128 = 1408
+    (2816, 1024, 1024, 1, "none", True, True, True, False, False, 64, G3),          # plain-bf16 residual GEMM, C2: t128 = 176
+    (2816, 2048, 1024, 2, "gelu_tanh", True, False, False, False, False, 128, REG128),   # strict-mode FF1, C2: t128 = 352
+    (14592, 4096, 1024, 3, "gelu_tanh", True, False, False, False, True, 128, G6_256),   # E2 FF1 at the C5 share: t256 = 912 (4 rounds), t176 = 1328 (5.1)
+    (14592, 1024, 4096, 3, "none", True, True, True, False, False, 64, G6_256),     # E2 FF2 at the C5 share, 64 K-tiles: t256 = 228 (1 round), t176 = 332 (1.7)
+    # ragged 256-row tile: t256 = 57 x 4 = 228 (1 round), t176 = 332 (1.7); 14500 = 56 x 256 + 164: the last tile has 164 valid rows; masked rows
+    (14500, 1024, 1024, 3, "none", True, True, True, True, False, 64, G6_256),
+    (14500, 4096, 1024, 3, "gelu_tanh", True, False, False, False, True, 128, G6_256),   # ragged, wide N: t256 = 912 (4), t176 = 1328 (5.1)
+    # single E2 chunk FF2, 64 K-tiles: t256 = 76 and t176 = 112 (< 224: no gemm6); gemm5: rb 11 cb 8 = 28 x 8 = 224 tiles (1 round, cost 304)
+    # against rb 11 cb 4 = 448 (2 rounds, 480), rb 8 cb 8 = 304 (2, 512), rb 8 cb 4 = 608 (3, 576)
+    (4864, 1024, 4096, 3, "none", True, True, True, False, False, 64, G5_11_8),
+    # single E2 chunk FF1: t256 = 304 (2 rounds), t176 = 448 (1.7) -> 176-row tiles; 4864 = 27 x 176 + 112: the last tile has 112 valid rows
+    (4864, 4096, 1024, 3, "gelu_tanh", True, False, False, False, True, 128, G6_176),
+    (2816, 3072, 1024, 3, "none", True, True, True, False, False, 128, G5_11_12),   # QKV width through the generic epilogue: rb 11 cb 12 = 16 x 16 = 256 tiles (1 round)
+    # F5-Small FF1 at 1024 frames: rb 8 cb 8 = 16 x 12 = 192 tiles (1 round, cost 256) against rb 11 cb 8 = 144 (1, 304), rb 8 cb 12 = 128 (1, 320)
+    (2048, 1536, 768, 3, "gelu_tanh", True, False, False, False, True, 128, G5_8_8),
+    # F5-Small FF1, two utterances of 1024 frames: rb 8 cb 12 = 32 x 8 = 256 tiles (1 round, cost 320) against rb 11 cb 12 = 192 (1, 368)
+    (4096, 1536, 768, 3, "gelu_tanh", True, False, False, False, True, 128, ("gemm5_rb8", "gemm5_wide", "gemm5_cb12")),
+    (2816, 1024, 736, 3, "none", True, True, True, False, False, 128, G3),          # K % 64 == 32: the fp16 gemm3 fallback (t128 = 176, 128 x 128 tiles)
 ]
 
 
-@pytest.mark.parametrize("case", CASES, ids=[f"M{c[0]}_N{c[1]}_K{c[2]}_p{c[3]}_{c[4]}{'_keep' if c[8] else ''}{'_f16out' if c[9] else ''}" for c in CASES])
+@pytest.mark.parametrize("case", CASES, ids=[f"M{c[0]}_N{c[1]}_K{c[2]}_p{c[3]}_{c[4]}{'_keep' if c[8] else ''}{'_f16out' if c[9] else ''}{'_bn64' if c[10] == 64 else ''}"
+                                             for c in CASES])
 def test_gemm_unit_op(case):
     from tts_indic_server_f5_amd import ops
-    M, N, K, prec, act, use_bias, use_mul, use_res, use_keep, out16, counter = case
+    M, N, K, prec, act, use_bias, use_mul, use_res, use_keep, out16, bn, counters = case
     g = torch.Generator().manual_seed(M * 7 + N * 3 + K + prec)
     a = torch.randn(M, K, generator=g)
     w = torch.randn(N, K, generator=g) / K ** 0.5
@@ -107,16 +151,17 @@ def test_gemm_unit_op(case):
     if res is not None:
         ref = ref + res.double()
     _reset_counters()
-    out, _ = ops.gemm(a.to(DEV), w.to(DEV), bias, prec=prec, act=act, mul=mul, res=res, row_keep=keep, out16=out16)
-    if counter:
-        assert _counter(counter) == 1, f"{counter} path was not taken"
+    out, _ = ops.gemm(a.to(DEV), w.to(DEV), bias, prec=prec, act=act, mul=mul, res=res, row_keep=keep, out16=out16, bn=bn)
+    _assert_path(counters)
     assert torch.isfinite(out).all()
+    rel = _rel(out.float(), ref)
+    print(f"[parity] gemm M{M} N{N} K{K} prec {prec} {act} bn {bn} ({'+'.join(counters)}): rel rms {rel:.3e}")
     if out16:
         # one fp16 rounding of the output on top of the accumulation error
-        assert _rel(out.float(), ref) < 6e-4
+        assert rel < 6e-4
         assert (out.float().cpu() - ref.half().float()).abs().max() <= 2 * torch.finfo(torch.float16).eps * ref.abs().max()
     else:
-        assert _rel(out, ref) < (3e-4 if act in ("gelu_tanh", "silu", "mish") else 2e-5)   # hardware exp2 / rcp in the activations: ~1 ulp each
+        assert rel < (3e-4 if act in ("gelu_tanh", "silu", "mish") else 2e-5)   # hardware exp2 / rcp in the activations: ~1 ulp each
 
 
 def test_gemm_f16_output_saturates():
@@ -138,8 +183,24 @@ def test_gemm_f16_output_saturates():
     assert (out[~ok].float().cpu().abs()[big] == 65504.0).all()
 
 
-@pytest.mark.parametrize("M,D,prec", [(2816, 1024, 3), (1404, 1024, 3), (1536, 768, 3), (2816, 1024, 2), (300, 256, 2), (22528, 1024, 3), (8320, 768, 3)])
-def test_qkv_unit_op(M, D, prec):
+QKV_CASES = [
+    # (M, D, prec, rotary positions modulo, expected counters): N = 3 D through the QKV epilogue (gemm3 never takes it)
+    (2816, 1024, 3, 1405, G5_11_12),   # C2: rb 11 cb 12 = 16 x 16 = 256 tiles (1 round)
+    (1404, 1024, 3, 1405, G5_11_8),    # rb 11 cb 8 = 8 x 24 = 192 tiles (1 round, cost 304)
+    (1536, 768, 3, 1405, G5_8_8),      # C1 F5-Small: rb 8 cb 8 = 12 x 18 = 216 tiles (1 round, cost 256)
+    (1024, 768, 3, 1405, G5_11_4),     # rb 11 cb 4 = 6 x 36 = 216 tiles (1 round, cost 240)
+    (256, 768, 3, 1405, G5_8_4),       # rb 8 cb 4 = 2 x 36 = 72 tiles (1 round, cost 192)
+    (2560, 768, 3, 1405, ("gemm5_rb8", "gemm5_wide", "gemm5_cb12")),   # rb 8 cb 12 = 20 x 12 = 240 tiles (1 round, cost 320)
+    (2816, 1024, 2, 1405, REG128),     # strict mode: split-bf16 QKV always runs gemm.h (t128 = 528)
+    (300, 256, 2, 1405, REG128),
+    (22528, 1024, 3, 1405, G6_256),    # C3 share: t256 = 1056 (5 rounds), t176 = 1536 (5.1)
+    (8320, 768, 3, 1405, G6_176),      # t256 = 297 (2 rounds), t176 = 432 (1.7); 8320 = 47 x 176 + 48
+    (14592, 1024, 3, 2341, G6_256),    # E2 at the C5 share (3 chunks x 2 branches x 2432 rows): t256 = 684 (3 rounds), t176 = 996 (3.4)
+]
+
+
+@pytest.mark.parametrize("M,D,prec,npos,counters", QKV_CASES, ids=[f"{c[0]}-{c[1]}-{c[2]}" for c in QKV_CASES])
+def test_qkv_unit_op(M, D, prec, npos, counters):
     """Fused QKV projection + epilogue against a reference that applies x-transformers' interleaved rotary embedding to channels
     0..63 of q and k (head 0 only: F/model/modules.py:414-426), scales q by log2(e) / 8 (the attention kernel works in base-2 exponents) and rounds to fp16 like the kernel's outputs."""
     from oracle import dit_oracle as O
@@ -148,19 +209,16 @@ def test_qkv_unit_op(M, D, prec):
     a = torch.randn(M, D, generator=g)
     w = torch.randn(3 * D, D, generator=g) / D ** 0.5
     bias = torch.randn(3 * D, generator=g) * 0.1
-    pos = torch.arange(M) % 1405          # two sequences' worth of positions
+    pos = torch.arange(M) % npos          # sequences' worth of positions
     y = (_ref_matmul(a, w, prec) + bias.double()).float()
     q, k, v = y[:, :D].clone(), y[:, D:2 * D].clone(), y[:, 2 * D:]
-    freqs = O.rotary_freqs(1405, 64)[0][pos]           # [M, 64]
+    freqs = O.rotary_freqs(npos, 64)[0][pos]           # [M, 64]
     q[:, :64] = O.apply_rotary(q[None, :, :64], freqs[None])[0]
     k[:, :64] = O.apply_rotary(k[None, :, :64], freqs[None])[0]
     q = q * Q_SCALE
     _reset_counters()
     gq, gk, gv, _ = ops.qkv(a.to(DEV), w.to(DEV), bias, pos.numpy(), prec=prec)
-    if prec == 3 and M == 2816:
-        assert _counter("gemm5_wide") == 1 and _counter("gemm5_rb11") == 1
-    if M >= 8320:
-        assert _counter("gemm6") == 1          # batch-mode shapes: the 256 x 256 ping-pong kernel (all-Q, all-K and all-V tiles; 8320 = 32.5 row tiles)
+    _assert_path(counters)
     for name, got, ref in (("q", gq, q), ("k", gk, k), ("v", gv, v)):
         err = (got.cpu() - ref.half().float()).abs()
         # fp16 outputs: identical up to accumulation-order flips of the last fp16 bit on some elements
@@ -195,23 +253,69 @@ def test_qkv_and_attention_operands_saturate():
     assert (out.double().cpu() - ref).abs().max().item() < 2.5e-3
 
 
-@pytest.mark.parametrize("rms", [False, True])
-def test_layernorm_unit_op(rms):
-    from tts_indic_server_f5_amd import ops
-    g = torch.Generator().manual_seed(9)
-    M, D = 2816, 1024
-    x = torch.randn(M, D, generator=g) * 3 + 0.5
-    scale = torch.randn(D, generator=g) * 0.3
-    shift = torch.randn(D, generator=g) * 0.3
+def _ln_ref(x, scale, shift, mode):
+    """fp64 LayerNorm / RMSNorm of the fp32 rows x, with the op's modulation: AdaLN y = n (1 + scale) + shift, affine y = n scale + shift."""
     xd = x.double()
-    if rms:
-        ref = xd / xd.norm(dim=-1, keepdim=True).clamp_min(1e-12) * D ** 0.5 * scale.double()
-        out = ops.layernorm(x.to(DEV), scale, torch.zeros(D), gain_off=0.0, eps=0.0, rms=True)
-    else:
-        mu, var = xd.mean(-1, keepdim=True), xd.var(-1, unbiased=False, keepdim=True)
-        ref = (xd - mu) / (var + 1e-6).sqrt() * (1 + scale.double()) + shift.double()
-        out = ops.layernorm(x.to(DEV), scale, shift, gain_off=1.0, eps=1e-6)
-    assert _rel(out, ref) < 2e-6
+    if mode == "rms":
+        return xd / xd.norm(dim=-1, keepdim=True).clamp_min(1e-12) * x.shape[1] ** 0.5 * scale.double()
+    mu, var = xd.mean(-1, keepdim=True), xd.var(-1, unbiased=False, keepdim=True)
+    return (xd - mu) / (var + 1e-6).sqrt() * ((1.0 if mode == "adaln" else 0.0) + scale.double()) + shift.double()
+
+
+def _ln_run(x, scale, shift, mode):
+    from tts_indic_server_f5_amd import ops
+    if mode == "rms":
+        return ops.layernorm(x.to(DEV), scale, torch.zeros(x.shape[1]), gain_off=0.0, eps=0.0, rms=True)
+    return ops.layernorm(x.to(DEV), scale, shift, gain_off=1.0 if mode == "adaln" else 0.0, eps=1e-6)
+
+
+# D: every ln_kernel<NV> instantiation (NV = ceil(D / 256) = 1, 2, 3, 4, 6 -- 5 runs the NV = 6 kernel), and 1028 = 4 x 257, a width that
+# leaves lanes of the last float4 column group masked; M: the C2 rows, one row past a multiple of the 4 rows per workgroup, and one workgroup
+# that is not full (3 rows)
+@pytest.mark.parametrize("mode", ["adaln", "affine", "rms"])
+@pytest.mark.parametrize("D", [256, 512, 768, 1024, 1028, 1536])
+@pytest.mark.parametrize("M", [2816, 2817, 3])
+def test_layernorm_unit_op(mode, D, M):
+    g = torch.Generator().manual_seed(9 + D + M)
+    x = torch.randn(M, D, generator=g) * 3 + 0.5
+    scale = torch.randn(D, generator=g) * 0.3 + (1.0 if mode == "affine" else 0.0)
+    shift = torch.randn(D, generator=g) * 0.3
+    # a constant row (variance 0: the normalised row is 0, so the output is the shift; 2.5 sums exactly in fp32, so the mean is exact),
+    # or, under RMSNorm, an all-zero row (norm 0: the 1e-12 clamp keeps it finite and the output is 0)
+    x[M // 2] = 0.0 if mode == "rms" else 2.5
+    ref = _ln_ref(x, scale, shift, mode)
+    out = _ln_run(x, scale, shift, mode)
+    assert out.shape == (M, D) and torch.isfinite(out).all()
+    rel = _rel(out, ref)
+    print(f"[parity] layernorm {mode} M {M} D {D}: rel rms {rel:.3e}")
+    assert rel < 2e-6
+    assert (out[M // 2].double().cpu() - ref[M // 2]).abs().max().item() <= 1e-6
+
+
+@pytest.mark.parametrize("mode", ["adaln", "affine"])
+@pytest.mark.parametrize("D", [512, 1024, 1028, 1536])
+@pytest.mark.parametrize("ratio", [100.0, 1000.0])
+def test_layernorm_large_mean(mode, D, ratio):
+    """Rows whose mean is 100 / 1000 times their spread (|mu| / sigma), against fp64 on the same fp32 inputs.  The kernel subtracts the mean
+    it computed in a first pass (two-pass variance), so its error is that of the fp32 mean: a lane adds 4 NV elements in a row and the wave
+    sum adds the 64 lane sums in 6 levels, so (first order) |mean - mu| <= (4 NV + 6 + 1) u |mu| with u = 2^-24 (the +1: the division by D).
+    The subtraction x - mean is exact (Sterbenz) and shifts every normalised element by (mean - mu) / sigma, so the relative rms error is at
+    most (4 NV + 7) u |mu| / sigma on top of the 2e-6 of the |mu| / sigma <= 1 rows: 1.4e-4 / 1.4e-3 at NV = 4 for ratio 100 / 1000.
+    A one-pass variance (E[x^2] - E[x]^2) would be off by ~ u (|mu| / sigma)^2 = 6e-4 / 6e-2 instead."""
+    g = torch.Generator().manual_seed(31 + D + int(ratio))
+    M, sigma = 2817, 3.0
+    sign = torch.where(torch.rand(M, 1, generator=g) < 0.5, -1.0, 1.0)
+    x = sign * ratio * sigma * (1.0 + 0.1 * torch.rand(M, 1, generator=g)) + sigma * torch.randn(M, D, generator=g)
+    scale = torch.randn(D, generator=g) * 0.3 + (1.0 if mode == "affine" else 0.0)
+    shift = torch.randn(D, generator=g) * 0.3
+    ref = _ln_ref(x, scale, shift, mode)
+    out = _ln_run(x, scale, shift, mode)
+    assert torch.isfinite(out).all()
+    nv = 6 if D > 1024 else (D + 255) // 256
+    bound = 2e-6 + (4 * nv + 7) * 2.0 ** -24 * 1.1 * ratio
+    rel = _rel(out, ref)
+    print(f"[parity] layernorm {mode} D {D} |mu|/sigma {ratio:g}: rel rms {rel:.3e} (bound {bound:.2e})")
+    assert rel < bound
 
 
 @pytest.mark.parametrize("impl", [3])

@@ -491,7 +491,11 @@ static GemmArgs gemm_base(const Plane2& A, int lda, const PackedW& W, int M) {
     return a;
 }
 
-static long long g_counters[6] = {0, 0, 0, 0, 0, 0};   // f5hip_get_counter: gemm5 launches with RB 11 / RB 8 / 1 x 4 consumer layout / gemm3 wide-tile launches / conv5 launches / gemm6 launches
+// f5hip_get_counter: gemm5 launches with RB 11 / RB 8 / 1 x 4 consumer layout (cb 8 or 12) / gemm3 wide-tile launches / conv5 launches /
+// gemm6 launches; then gemm6 by tile height (176 / 256 rows), gemm5 with cb 12, every gemm3 launch, every gemm.h launch by bn (64 / 128)
+enum { CNT_GEMM5_RB11, CNT_GEMM5_RB8, CNT_GEMM5_WIDE, CNT_GEMM3_WIDE, CNT_CONV5, CNT_GEMM6, CNT_GEMM6_R176, CNT_GEMM6_R256, CNT_GEMM5_CB12,
+       CNT_GEMM3, CNT_GEMM_REG_BN64, CNT_GEMM_REG_BN128, CNT_COUNT };
+static long long g_counters[CNT_COUNT] = {};
 
 // Kernel choice per GEMM (measured: profiles/r02_fillrate_microbench.txt, profiles/r01_gemm_microbench.txt):
 //   fp16 one-plane operands: gemm6 for the batch-mode shapes (gemm6_choose_rows), else gemm5 (exact-fit tiles) when K % 64 == 0,
@@ -511,20 +515,25 @@ static int run_gemm_n(int nsplit, int mp, GemmArgs& a, const PackedW& W, int epi
         const int rows6 = legal6 ? gemm6_choose_rows(a.M, np) : 0;
         if (rows6) {
             e = f5_launch_gemm6(epi, rows6, a, np, st);
-            g_counters[5]++;
+            g_counters[CNT_GEMM6]++;
+            g_counters[rows6 == 176 ? CNT_GEMM6_R176 : CNT_GEMM6_R256]++;
         } else if (a.K % 64 == 0 && c5.rb) {
             e = epi == EPI_QKV ? f5_launch_gemm5_qkv(a, c5.rb, c5.cb, np, st) : f5_launch_gemm5_generic(a, c5.rb, c5.cb, np, st);
-            g_counters[c5.rb == 11 ? 0 : 1]++;
-            if (c5.cb >= 8) g_counters[2]++;
+            g_counters[c5.rb == 11 ? CNT_GEMM5_RB11 : CNT_GEMM5_RB8]++;
+            if (c5.cb >= 8) g_counters[CNT_GEMM5_WIDE]++;
+            if (c5.cb == 12) g_counters[CNT_GEMM5_CB12]++;
         } else {
             // gemm3 (round 1): 128 x 256 tile in batch mode (>= 1024 tiles of 128 x 128), 128 x 128 otherwise
             const bool wide = tiles128 >= 1024 && np % 256 == 0;
-            if (wide) g_counters[3]++;
+            if (wide) g_counters[CNT_GEMM3_WIDE]++;
+            g_counters[CNT_GEMM3]++;
             e = f5_launch_gemm3(3, epi, wide ? 256 : 128, a, mp, np, st);
         }
     } else if (!conv && tiles128 <= 256 && epi != EPI_QKV) {
+        g_counters[CNT_GEMM3]++;
         e = f5_launch_gemm3(nsplit, epi, 128, a, mp, np, st);
     } else {   // (fp16 convolutions included: BigVGAN in fp16 mode)
+        g_counters[bn == 64 ? CNT_GEMM_REG_BN64 : CNT_GEMM_REG_BN128]++;
         e = f5_launch_gemm_reg(nsplit, bn, conv, epi, a, mp, np, st);
     }
     prof_end(PROF_GEMM, st);
@@ -560,12 +569,13 @@ static int run_gemm_ln(f5hip_dit* m, GemmArgs& g, const PackedW& W, const LnArgs
     return run_ln(ln, st);
 }
 
-// Diagnostics for tests: which GEMM path the launches since the last reset took ("gemm5_rb11", "gemm5_rb8", "gemm5_wide", "gemm3_wide", "conv5", "gemm6"); name "reset" zeroes them.
+// Diagnostics for tests: which GEMM path the launches since the last reset took (names in the order of the CNT_ enum); name "reset" zeroes them.
 extern "C" int f5hip_get_counter(const char* name, int64_t* value) {
-    static const char* names[6] = {"gemm5_rb11", "gemm5_rb8", "gemm5_wide", "gemm3_wide", "conv5", "gemm6"};
+    static const char* names[CNT_COUNT] = {"gemm5_rb11", "gemm5_rb8", "gemm5_wide", "gemm3_wide", "conv5", "gemm6", "gemm6_r176", "gemm6_r256",
+                                           "gemm5_cb12", "gemm3", "gemm_reg_bn64", "gemm_reg_bn128"};
     if (!name) return fail(-1, "get_counter: null name");
     if (!strcmp(name, "reset")) { for (auto& c : g_counters) c = 0; return 0; }
-    for (int i = 0; i < 6; i++)
+    for (int i = 0; i < CNT_COUNT; i++)
         if (!strcmp(name, names[i])) { if (value) *value = g_counters[i]; return 0; }
     return fail(-1, "unknown counter %s", name);
 }
@@ -827,7 +837,7 @@ static int run_pos_conv(f5hip_dit* m, GemmArgs& g, const PackedW& W, hipStream_t
         prof_begin(PROF_GEMM, st);
         const hipError_t e = f5_launch_conv5(2, g, W.n_pad, st);
         prof_end(PROF_GEMM, st);
-        if (e == hipSuccess) { g_counters[4]++; return 0; }
+        if (e == hipSuccess) { g_counters[CNT_CONV5]++; return 0; }
         if (e != hipErrorInvalidValue) return fail(-7, "conv5 launch: %s", hipGetErrorString(e));
     }
     return run_gemm(m, g, W, EPI_GENERIC, true, 64, st);

@@ -108,9 +108,11 @@ static int gemm6_stamp_report(OpBufs& b, int M, int N, int K, hipStream_t st, La
 
 extern "C" int f5hip_op_gemm(int32_t M, int32_t N, int32_t K, const float* a_dev, const float* w_dev, const float* bias_dev, int32_t prec,
                              int32_t act, const float* mul_dev, const float* res_dev, const uint8_t* row_keep_host, float* out_dev,
-                             uint16_t* out16_dev, int32_t w_copies, int32_t iters, double* avg_us, void* stream) {
+                             uint16_t* out16_dev, int32_t w_copies, int32_t iters, double* avg_us, void* stream, int32_t bn) {
     if (M <= 0 || N <= 0 || K <= 0 || K % 32 || N % 4 || !a_dev || !w_dev || prec < 1 || prec > 3 || (!out_dev && !out16_dev))
         return fail(-1, "op_gemm: bad argument (need K %% 32 == 0, N %% 4 == 0, prec 1..3)");
+    if (bn == 0) bn = 128;
+    if (bn != 64 && bn != 128) return fail(-1, "op_gemm: bn must be 0, 64 or 128 (got %d)", bn);
     if (out16_dev && (res_dev || out_dev)) return fail(-1, "op_gemm: the 16-bit output is the (no residual, no fp32 output) epilogue");
     hipStream_t st = (hipStream_t)stream;
     const int M_pad = (M + 127) / 128 * 128, N_pad = (N + 127) / 128 * 128;
@@ -150,19 +152,19 @@ extern "C" int f5hip_op_gemm(int32_t M, int32_t N, int32_t K, const float* a_dev
     };
     {
         GemmArgs g = args_for(Ws[0]);
-        CK(run_gemm_n(prec, M_pad, g, Ws[0], EPI_GENERIC, false, 128, st));
+        CK(run_gemm_n(prec, M_pad, g, Ws[0], EPI_GENERIC, false, bn, st));
     }
     if (getenv("F5HIP_GEMM5_STAMPS"))
         CK(gemm5_stamp_report(b, M, N, K, st, [&](unsigned long long* d, int rep) {
             GemmArgs g = args_for(Ws[rep % w_copies]);
             g.stamps = d;
-            return run_gemm_n(prec, M_pad, g, Ws[rep % w_copies], EPI_GENERIC, false, 128, st);
+            return run_gemm_n(prec, M_pad, g, Ws[rep % w_copies], EPI_GENERIC, false, bn, st);
         }));
     if (getenv("F5HIP_GEMM6_STAMPS"))
         CK(gemm6_stamp_report(b, M, N, K, st, [&](unsigned long long* d, int rep) {
             GemmArgs g = args_for(Ws[rep % w_copies]);
             g.stamps = d;
-            return run_gemm_n(prec, M_pad, g, Ws[rep % w_copies], EPI_GENERIC, false, 128, st);
+            return run_gemm_n(prec, M_pad, g, Ws[rep % w_copies], EPI_GENERIC, false, bn, st);
         }));
     if (iters > 0 && avg_us) {
         // timing: the residual epilogue accumulates in place, so time into a scratch output
@@ -175,7 +177,7 @@ extern "C" int f5hip_op_gemm(int32_t M, int32_t N, int32_t K, const float* a_dev
             const PackedW& W = Ws[(it + 3) % w_copies];
             GemmArgs g = args_for(W);
             if (!out16_dev) { g.out_f32 = scratch; if (res_dev) g.res = scratch; }
-            CK(run_gemm_n(prec, M_pad, g, W, EPI_GENERIC, false, 128, st));
+            CK(run_gemm_n(prec, M_pad, g, W, EPI_GENERIC, false, bn, st));
         }
         (void)hipEventRecord(e1, st);
         (void)hipEventSynchronize(e1);

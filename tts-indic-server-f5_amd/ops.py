@@ -24,8 +24,10 @@ def _f32(t, dev):
     return None if t is None else t.to(dev, torch.float32).contiguous()
 
 
-def gemm(a, w, bias=None, *, prec=3, act="none", mul=None, res=None, row_keep=None, out16=False, w_copies=1, iters=0):
-    """out = (act(a @ w.T + bias), masked rows zeroed) * mul + res.  Returns (out, avg_us); out is fp32 [M, N], or the fp16 plane."""
+def gemm(a, w, bias=None, *, prec=3, act="none", mul=None, res=None, row_keep=None, out16=False, w_copies=1, iters=0, bn=128):
+    """out = (act(a @ w.T + bias), masked rows zeroed) * mul + res.  Returns (out, avg_us); out is fp32 [M, N], or the fp16 plane.
+    bn: the column-tile width a call site passes to the dispatcher (128, or 64 as the residual and UNetT skip GEMMs do); only the
+    register-staged gemm.h kernel reads it."""
     dev = a.device
     M, K = a.shape
     N = w.shape[0]
@@ -35,7 +37,7 @@ def gemm(a, w, bias=None, *, prec=3, act="none", mul=None, res=None, row_keep=No
     us = C.c_double(0.0)
     _lib.check(_lib.lib().f5hip_op_gemm(M, N, K, _p(a), _p(w), _p(bias), prec, ACT[act], _p(mul), _p(res), _p(keep),
                                         None if out16 else _p(out), _p(out) if out16 else None, w_copies, iters, C.byref(us),
-                                        _lib.current_stream_ptr()), "f5hip_op_gemm")
+                                        _lib.current_stream_ptr(), bn), "f5hip_op_gemm")
     return out, us.value
 
 
