@@ -18,7 +18,7 @@ struct BvRes { BvConv c1[3], c2[3]; float* alpha[6] = {}; float* beta[6] = {}; }
 struct f5hip_bigvgan {
     f5hip_bigvgan_config cfg;
     int nsplit = 2;
-    std::map<std::string, std::vector<float>> host;
+    ParamStore params;
     bool finalized = false;
     int n_up = 0, c0 = 0;
     BvConv pre;
@@ -218,20 +218,8 @@ void f5hip_bigvgan_destroy(f5hip_bigvgan* v) {
 }
 
 int f5hip_bigvgan_load_param(f5hip_bigvgan* v, const char* name, const float* data, int64_t numel) {
-    if (!v || !name || !data || numel <= 0) return fail(-1, "load_param: bad argument");
-    if (v->finalized) return fail(-2, "load_param after finalize");
-    v->host[name].assign(data, data + numel);
-    return 0;
+    return v ? v->params.load(v->finalized, name, data, numel) : fail(-1, "load_param: bad argument");
 }
-
-#define BGETP(var, name, numel)                                                                                    \
-    const std::vector<float>* var = nullptr;                                                                        \
-    {                                                                                                               \
-        auto it = v->host.find(name);                                                                               \
-        if (it == v->host.end()) return fail(-3, "missing parameter %s", std::string(name).c_str());                \
-        if ((int64_t)it->second.size() != (int64_t)(numel)) return fail(-3, "parameter %s: wrong size", std::string(name).c_str()); \
-        var = &it->second;                                                                                          \
-    }
 
 // Conv1d weight [co][ci][k] -> [co][tap][ci_pad]
 static int bv_pack_conv(BvConv& c, const std::vector<float>& w, const float* bias, int co, int ci, int k, int dil, bool f16) {
@@ -248,9 +236,10 @@ int f5hip_bigvgan_finalize(f5hip_bigvgan* v) {
     if (!v) return fail(-1, "null vocoder");
     if (v->finalized) return 0;
     const f5hip_bigvgan_config& c = v->cfg;
+    const ParamStore& P = v->params;
     const bool f16 = v->nsplit == 3;
     {
-        BGETP(w, "conv_pre.weight", (int64_t)v->c0 * c.num_mels * 7); BGETP(b, "conv_pre.bias", v->c0);
+        GET_PARAM(w, P, "conv_pre.weight", (int64_t)v->c0 * c.num_mels * 7); GET_PARAM(b, P, "conv_pre.bias", v->c0);
         // input rows are mel frames padded to 128 channels
         BvConv& p = v->pre; p.k = 7; p.dil = 1; p.c_in = c.num_mels; p.c_out = v->c0; p.c_in_pad = 128;
         std::vector<float> wp((size_t)v->c0 * 7 * 128, 0.0f);
@@ -263,8 +252,8 @@ int f5hip_bigvgan_finalize(f5hip_bigvgan* v) {
     v->res.resize(v->n_up * 3);
     for (int i = 0; i < v->n_up; i++) {
         const int ci = v->c0 >> i, co = v->c0 >> (i + 1), r = c.upsample_rates[i], k = 2 * r;
-        BGETP(w, "ups." + std::to_string(i) + ".0.weight", (int64_t)ci * co * k);
-        BGETP(b, "ups." + std::to_string(i) + ".0.bias", co);
+        GET_PARAM(w, P, "ups." + std::to_string(i) + ".0.weight", (int64_t)ci * co * k);
+        GET_PARAM(b, P, "ups." + std::to_string(i) + ".0.bias", co);
         BvConv& u = v->ups[i]; u.k = 3; u.dil = 1; u.c_in = ci; u.c_out = r * co; u.c_in_pad = ceil_to(ci, 32);
         const int K = 3 * u.c_in_pad;
         std::vector<float> wp((size_t)r * co * K, 0.0f), bp((size_t)r * co);
@@ -285,20 +274,20 @@ int f5hip_bigvgan_finalize(f5hip_bigvgan* v) {
             const int kk = c.resblock_kernel_sizes[j];
             const std::string q = "resblocks." + std::to_string(i * 3 + j) + ".";
             for (int d = 0; d < 3; d++) {
-                BGETP(w1, q + "convs1." + std::to_string(d) + ".weight", (int64_t)co * co * kk); BGETP(b1, q + "convs1." + std::to_string(d) + ".bias", co);
-                BGETP(w2, q + "convs2." + std::to_string(d) + ".weight", (int64_t)co * co * kk); BGETP(b2, q + "convs2." + std::to_string(d) + ".bias", co);
+                GET_PARAM(w1, P, q + "convs1." + std::to_string(d) + ".weight", (int64_t)co * co * kk); GET_PARAM(b1, P, q + "convs1." + std::to_string(d) + ".bias", co);
+                GET_PARAM(w2, P, q + "convs2." + std::to_string(d) + ".weight", (int64_t)co * co * kk); GET_PARAM(b2, P, q + "convs2." + std::to_string(d) + ".bias", co);
                 if (bv_pack_conv(rb.c1[d], *w1, b1->data(), co, co, kk, c.resblock_dilations[j * 3 + d], f16)) return -4;
                 if (bv_pack_conv(rb.c2[d], *w2, b2->data(), co, co, kk, 1, f16)) return -4;
             }
             for (int a = 0; a < 6; a++) {
-                BGETP(al, q + "activations." + std::to_string(a) + ".act.alpha", co); BGETP(be, q + "activations." + std::to_string(a) + ".act.beta", co);
+                GET_PARAM(al, P, q + "activations." + std::to_string(a) + ".act.alpha", co); GET_PARAM(be, P, q + "activations." + std::to_string(a) + ".act.beta", co);
                 if (upload_f32(&rb.alpha[a], al->data(), co) || upload_f32(&rb.beta[a], be->data(), co)) return -4;
             }
         }
     }
     {
         const int ch = v->c0 >> v->n_up;
-        BGETP(al, "activation_post.act.alpha", ch); BGETP(be, "activation_post.act.beta", ch); BGETP(w, "conv_post.weight", (int64_t)ch * 7);
+        GET_PARAM(al, P, "activation_post.act.alpha", ch); GET_PARAM(be, P, "activation_post.act.beta", ch); GET_PARAM(w, P, "conv_post.weight", (int64_t)ch * 7);
         if (upload_f32(&v->post_alpha, al->data(), ch) || upload_f32(&v->post_beta, be->data(), ch) || upload_f32(&v->post_w, w->data(), ch * 7)) return -4;
     }
     {   // kaiser_sinc_filter1d(cutoff 0.25, half_width 0.3, 12): alias_free_torch/filter.py
@@ -319,7 +308,7 @@ int f5hip_bigvgan_finalize(f5hip_bigvgan* v) {
         for (int n = 0; n < ks; n++) ff[n] = (float)(f[n] / sum);
         memcpy(v->filt_h, ff, sizeof(ff));
     }
-    v->host.clear();
+    v->params.host.clear();
     v->finalized = true;
     return 0;
 }

@@ -26,6 +26,12 @@ struct TextBlock {
     PackedW pw1, pw2;
 };
 
+// One residual stream's transformer-block linears, indexed by block.
+struct BlockWeights {
+    std::vector<PackedW> qkv, out, ff1, ff2;
+    void resize(int n) { qkv.resize(n); out.resize(n); ff1.resize(n); ff2.resize(n); }
+};
+
 struct f5hip_dit {
     f5hip_dit_config cfg;
     int nsplit = 2;       // operand planes of the state-touching GEMMs (1 bf16, 2 split bf16)
@@ -34,14 +40,15 @@ struct f5hip_dit {
     ProfState* prof = nullptr;        // f5hip_dit_set_profiling: this handle's own HIP-event spans and totals (null: the process-wide state)
     HostStage up_meta, up_time[2];    // pinned staging of the per-call uploads (row metadata; the two planes of the sinusoid table)
     bool blk_f16 = false; // gemm_planes == 3: transformer-block GEMMs (QKV, out, FF1, FF2) take one fp16 plane per operand
-    std::map<std::string, std::vector<float>> host;
+    ParamStore params;
     bool finalized = false;
     // packed weights
     PackedW time1, time2, adaln, wx, wct, conv1, conv2, proj_out;
-    std::vector<PackedW> wqkv, wout, wff1, wff2, wskip;   // wskip: UNetT skip projections (later half of the layers)
-    std::vector<PackedW> wqkv_c, wout_c, wff1_c, wff2_c;   // MMDiT text-stream weights (wout_c / wff*_c: all but the last, context-pre-only block)
-    std::vector<int> mod_c, mod_x;                         // MMDiT: offsets of the blocks' text / audio modulation vectors inside one row of `mod`
-    int mod_final = 0;
+    BlockWeights blk;                 // the audio stream (DiT, UNetT, MMDiT audio)
+    BlockWeights blk_c;               // MMDiT text stream (out / ff*: all but the last, context-pre-only block)
+    std::vector<PackedW> wskip;       // UNetT skip projections (later half of the layers)
+    std::vector<int> mod_c, mod_x;    // offsets of the blocks' text (MMDiT) / audio modulation vectors inside one row of `mod`
+    int mod_final = 0;                // offset of the final norm's (scale, shift)
     std::vector<float*> g_attn, g_ff;                     // UNetT RMSNorm gains
     float *g_out = nullptr, *zeros = nullptr;
     std::vector<TextBlock> tblk;
@@ -52,7 +59,7 @@ struct f5hip_dit {
                       // every sequence are rows of their own stream, laid out behind all audio rows (rows [M, M + Mc))
     int td_pad = 0;   // text_dim rounded up to 32 (K padding of the step-invariant input-projection operand)
     int gw = 0;       // conv_pos_embed channels per group
-    int n_adaln = 0;  // depth * 6 D + 2 D
+    int n_adaln = 0;  // floats in one row of `mod` (0 for UNetT)
     // workspace
     int cap_rows = 0, cap_frames = 0, cap_seq = 0;
     DevBuf ws;   // one arena, carved below
@@ -67,7 +74,7 @@ struct f5hip_dit {
     // per-call metadata (device pointers into `meta`)
     int *d_row_pos, *d_row_start, *d_row_end, *d_row_seq, *d_row_token, *d_row_frame, *d_row_condframe, *d_row_keep,
         *d_seq_row0, *d_seq_len, *d_seq_kvlen, *d_urow_c, *d_urow_u, *d_frame_is_cond;
-    int M = 0, M_pad = 0, n_seq = 0, n_frames = 0, max_len = 0;
+    int M = 0, n_seq = 0, n_frames = 0, max_len = 0;
     int Mc = 0, Rtot = 0;   // MMDiT: text-stream rows and all rows (= row pitch of the V^T buffer); Rtot == M otherwise
     int *d_j_row0 = nullptr, *d_j_len = nullptr, *d_j_kvlen = nullptr, *d_j_kv_row0 = nullptr, *d_j_kv2_row0 = nullptr, *d_j_kv2_len = nullptr;   // MMDiT joint attention: 2 n_seq pseudo-sequences
     bool any_masked = false;
@@ -99,11 +106,10 @@ f5hip_dit* f5hip_dit_create(const f5hip_dit_config* cfg) {
     m->arch = cfg->arch;
     m->td_pad = cfg->arch == 2 ? 0 : ceil_to(cfg->text_dim, 32);   // MMDiT: the text never enters the input projection (mmdit.py:64-70)
     m->gw = cfg->dim / 16;
-    m->n_adaln = cfg->arch == 0 ? cfg->depth * 6 * cfg->dim + 2 * cfg->dim : 0;
-    if (cfg->arch == 2) {   // per block [text: 6 D, or 2 D in the last (context-pre-only) block][audio: 6 D], then the final 2 D
+    if (cfg->arch != 1) {   // per block [MMDiT text: 6 D, or 2 D in the last (context-pre-only) block][audio: 6 D], then the final 2 D
         int off = 0;
         for (int l = 0; l < cfg->depth; l++) {
-            m->mod_c.push_back(off); off += (l == cfg->depth - 1 ? 2 : 6) * cfg->dim;
+            if (cfg->arch == 2) { m->mod_c.push_back(off); off += (l == cfg->depth - 1 ? 2 : 6) * cfg->dim; }
             m->mod_x.push_back(off); off += 6 * cfg->dim;
         }
         m->mod_final = off;
@@ -117,7 +123,9 @@ static void free_packed(PackedW& w) { dev_free(w.hi); dev_free(w.lo); dev_free(w
 void f5hip_dit_destroy(f5hip_dit* m) {
     if (!m) return;
     for (PackedW* w : {&m->time1, &m->time2, &m->adaln, &m->wx, &m->wct, &m->conv1, &m->conv2, &m->proj_out}) free_packed(*w);
-    for (auto* v : {&m->wqkv, &m->wout, &m->wff1, &m->wff2, &m->wskip, &m->wqkv_c, &m->wout_c, &m->wff1_c, &m->wff2_c}) for (auto& w : *v) free_packed(w);
+    for (BlockWeights* b : {&m->blk, &m->blk_c})
+        for (auto* v : {&b->qkv, &b->out, &b->ff1, &b->ff2}) for (auto& w : *v) free_packed(w);
+    for (auto& w : m->wskip) free_packed(w);
     for (auto* v : {&m->g_attn, &m->g_ff}) for (float* g : *v) dev_free(g);
     dev_free(m->g_out); dev_free(m->zeros);
     for (auto& b : m->tblk) {
@@ -133,75 +141,88 @@ void f5hip_dit_destroy(f5hip_dit* m) {
 }
 
 int f5hip_dit_load_param(f5hip_dit* m, const char* name, const float* data, int64_t numel) {
-    if (!m || !name || !data || numel <= 0) return fail(-1, "load_param: bad argument");
-    if (m->finalized) return fail(-2, "load_param after finalize");
-    m->host[name].assign(data, data + numel);
+    return m ? m->params.load(m->finalized, name, data, numel) : fail(-1, "load_param: bad argument");
+}
+
+#define CK(x) do { int _r = (x); if (_r) return _r; } while (0)
+#define CKL(name) do { hipError_t _e = hipGetLastError(); if (_e != hipSuccess) return fail(-7, "%s launch: %s", name, hipGetErrorString(_e)); } while (0)
+
+// Packs one stream's block-l linears: q | k | v concatenated into one [3 D, D] weight, the out projection `out` and the feed-forward `ff`
+// (FF1 and the QKV weight also in fragment order: the W-direct gemm5 kernels).  `attn` + to_{q,k,v} + `qkv_sfx` name the q / k / v
+// linears; `out` empty: a block without out projection and feed-forward (MMDiT's last, context-pre-only text block).
+static int pack_block(f5hip_dit* m, BlockWeights& w, int l, const std::string& attn, const char* qkv_sfx, const std::string& out, const std::string& ff) {
+    const int D = m->cfg.dim, F = m->cfg.ff_mult * D;
+    const ParamStore& P = m->params;
+    std::vector<float> wq((size_t)3 * D * D), bq(3 * D);
+    const char* nm[3] = {"to_q", "to_k", "to_v"};
+    for (int i = 0; i < 3; i++) {
+        GET_PARAM(wi, P, attn + nm[i] + qkv_sfx + ".weight", (int64_t)D * D);
+        GET_PARAM(bi, P, attn + nm[i] + qkv_sfx + ".bias", D);
+        memcpy(&wq[(size_t)i * D * D], wi->data(), sizeof(float) * D * D);
+        memcpy(&bq[(size_t)i * D], bi->data(), sizeof(float) * D);
+    }
+    if (pack_linear(w.qkv[l], wq.data(), 3 * D, D, D, bq.data(), 128, m->blk_f16) || pack_frag(w.qkv[l])) return -4;
+    if (out.empty()) return 0;
+    GET_PARAM(wo, P, out + ".weight", (int64_t)D * D); GET_PARAM(bo, P, out + ".bias", D);
+    if (pack_linear(w.out[l], wo->data(), D, D, D, bo->data(), 128, m->blk_f16)) return -4;
+    GET_PARAM(w1, P, ff + "ff.0.0.weight", (int64_t)F * D); GET_PARAM(b1, P, ff + "ff.0.0.bias", F);
+    if (pack_linear(w.ff1[l], w1->data(), F, D, D, b1->data(), 128, m->blk_f16) || pack_frag(w.ff1[l])) return -4;
+    GET_PARAM(w2, P, ff + "ff.2.weight", (int64_t)D * F); GET_PARAM(b2, P, ff + "ff.2.bias", D);
+    if (pack_linear(w.ff2[l], w2->data(), D, F, F, b2->data(), 128, m->blk_f16)) return -4;
     return 0;
 }
 
-static const std::vector<float>* get_param(f5hip_dit* m, const std::string& name, int64_t numel) {
-    auto it = m->host.find(name);
-    if (it == m->host.end()) { set_error("missing parameter %s", name.c_str()); return nullptr; }
-    if ((int64_t)it->second.size() != numel) {
-        set_error("parameter %s has %lld elements, expected %lld", name.c_str(), (long long)it->second.size(), (long long)numel);
-        return nullptr;
-    }
-    return &it->second;
+// Rotary tables (x-transformers 2.2.8 RotaryEmbedding): [4097][32] cos / sin of angle = pos * 10000^(-2i/64) in fp32.
+// 4097 rows: UNetT puts the time token at position 0, so a 4096-frame sequence reaches position 4096 (unett.py:184-188)
+static void rope_tables(std::vector<float>& rc, std::vector<float>& rs) {
+    rc.resize((size_t)4097 * 32); rs.resize((size_t)4097 * 32);
+    for (int pos = 0; pos < 4097; pos++)
+        for (int i = 0; i < 32; i++) {
+            float inv = 1.0f / powf(10000.0f, (float)(2 * i) / 64.0f);
+            float ang = (float)pos * inv;
+            rc[(size_t)pos * 32 + i] = (float)cos((double)ang);
+            rs[(size_t)pos * 32 + i] = (float)sin((double)ang);
+        }
 }
-
-#define GETP(var, name, numel) const std::vector<float>* var = get_param(m, name, numel); if (!var) return -3;
 
 int f5hip_dit_finalize(f5hip_dit* m) {
     if (!m) return fail(-1, "null model");
     if (m->finalized) return 0;
     const f5hip_dit_config& c = m->cfg;
-    const int D = c.dim, Td = c.text_dim, mel = c.mel_dim, F = c.ff_mult * D;
+    const ParamStore& P = m->params;
+    const int D = c.dim, Td = c.text_dim, mel = c.mel_dim;
     const std::string T = "transformer.";
     // --- time MLP + all AdaLN linears (one [depth*6D + 2D, D] matrix: modulation depends on t only) ---
     {
-        GETP(w0, T + "time_embed.time_mlp.0.weight", (int64_t)D * 256);
-        GETP(b0, T + "time_embed.time_mlp.0.bias", D);
-        GETP(w2, T + "time_embed.time_mlp.2.weight", (int64_t)D * D);
-        GETP(b2, T + "time_embed.time_mlp.2.bias", D);
+        GET_PARAM(w0, P, T + "time_embed.time_mlp.0.weight", (int64_t)D * 256);
+        GET_PARAM(b0, P, T + "time_embed.time_mlp.0.bias", D);
+        GET_PARAM(w2, P, T + "time_embed.time_mlp.2.weight", (int64_t)D * D);
+        GET_PARAM(b2, P, T + "time_embed.time_mlp.2.bias", D);
         if (pack_linear(m->time1, w0->data(), D, 256, 256, b0->data())) return -4;
         if (pack_linear(m->time2, w2->data(), D, D, D, b2->data())) return -4;
     }
-    if (m->arch == 0) {
+    if (m->arch != 1) {   // every AdaLN linear, at its offset in a row of `mod`: DiT attn_norm; MMDiTBlock attn_norm_c (AdaLayerNormZero, or _Final in
+                          // the last block) and attn_norm_x (F/model/modules.py:593-594); then norm_out
         std::vector<float> wa((size_t)m->n_adaln * D), ba(m->n_adaln);
-        for (int l = 0; l < c.depth; l++) {
-            std::string p = T + "transformer_blocks." + std::to_string(l) + ".attn_norm.linear.";
-            GETP(w, p + "weight", (int64_t)6 * D * D);
-            GETP(b, p + "bias", 6 * D);
-            memcpy(&wa[(size_t)l * 6 * D * D], w->data(), sizeof(float) * 6 * D * D);
-            memcpy(&ba[(size_t)l * 6 * D], b->data(), sizeof(float) * 6 * D);
-        }
-        GETP(wf, T + "norm_out.linear.weight", (int64_t)2 * D * D);
-        GETP(bfin, T + "norm_out.linear.bias", 2 * D);
-        memcpy(&wa[(size_t)c.depth * 6 * D * D], wf->data(), sizeof(float) * 2 * D * D);
-        memcpy(&ba[(size_t)c.depth * 6 * D], bfin->data(), sizeof(float) * 2 * D);
-        if (pack_linear(m->adaln, wa.data(), m->n_adaln, D, D, ba.data())) return -4;
-    }
-    if (m->arch == 2) {   // MMDiTBlock: attn_norm_c (AdaLayerNormZero, or _Final in the last block) and attn_norm_x (F/model/modules.py:593-594)
-        std::vector<float> wa((size_t)m->n_adaln * D), ba(m->n_adaln);
+        auto put = [&](int off, const std::string& name, int rows) {
+            const std::vector<float>* w = P.get(name + "weight", (int64_t)rows * D);
+            const std::vector<float>* b = w ? P.get(name + "bias", rows) : nullptr;
+            if (!b) return false;
+            memcpy(&wa[(size_t)off * D], w->data(), sizeof(float) * (size_t)rows * D);
+            memcpy(&ba[off], b->data(), sizeof(float) * rows);
+            return true;
+        };
         for (int l = 0; l < c.depth; l++) {
             const std::string p = T + "transformer_blocks." + std::to_string(l) + ".";
-            const int nc = (l == c.depth - 1 ? 2 : 6) * D;
-            GETP(wc, p + "attn_norm_c.linear.weight", (int64_t)nc * D); GETP(bc, p + "attn_norm_c.linear.bias", nc);
-            GETP(wxm, p + "attn_norm_x.linear.weight", (int64_t)6 * D * D); GETP(bxm, p + "attn_norm_x.linear.bias", 6 * D);
-            memcpy(&wa[(size_t)m->mod_c[l] * D], wc->data(), sizeof(float) * (size_t)nc * D);
-            memcpy(&ba[m->mod_c[l]], bc->data(), sizeof(float) * nc);
-            memcpy(&wa[(size_t)m->mod_x[l] * D], wxm->data(), sizeof(float) * (size_t)6 * D * D);
-            memcpy(&ba[m->mod_x[l]], bxm->data(), sizeof(float) * 6 * D);
+            if (m->arch == 2 && !put(m->mod_c[l], p + "attn_norm_c.linear.", (l == c.depth - 1 ? 2 : 6) * D)) return -3;
+            if (!put(m->mod_x[l], p + (m->arch == 2 ? "attn_norm_x.linear." : "attn_norm.linear."), 6 * D)) return -3;
         }
-        GETP(wf, T + "norm_out.linear.weight", (int64_t)2 * D * D);
-        GETP(bfin, T + "norm_out.linear.bias", 2 * D);
-        memcpy(&wa[(size_t)m->mod_final * D], wf->data(), sizeof(float) * 2 * D * D);
-        memcpy(&ba[m->mod_final], bfin->data(), sizeof(float) * 2 * D);
+        if (!put(m->mod_final, T + "norm_out.linear.", 2 * D)) return -3;
         if (pack_linear(m->adaln, wa.data(), m->n_adaln, D, D, ba.data())) return -4;
     }
     // --- text embedding ---
     {
-        GETP(e, T + "text_embed.text_embed.weight", (int64_t)(c.text_num_embeds + 1) * Td);
+        GET_PARAM(e, P, T + "text_embed.text_embed.weight", (int64_t)(c.text_num_embeds + 1) * Td);
         if (upload_f32(&m->text_emb, e->data(), e->size())) return -4;
         // precompute_freqs_cis (F/model/modules.py:196-207): [cos(pos w_j) || sin(pos w_j)], fp32 angle
         std::vector<float> tab((size_t)4096 * Td);
@@ -217,11 +238,11 @@ int f5hip_dit_finalize(f5hip_dit* m) {
         for (int i = 0; i < c.conv_layers; i++) {
             std::string p = T + "text_embed.text_blocks." + std::to_string(i) + ".";
             TextBlock& b = m->tblk[i];
-            GETP(dw, p + "dwconv.weight", (int64_t)Td * 7); GETP(db, p + "dwconv.bias", Td);
-            GETP(lw, p + "norm.weight", Td); GETP(lb, p + "norm.bias", Td);
-            GETP(w1, p + "pwconv1.weight", (int64_t)2 * Td * Td); GETP(b1, p + "pwconv1.bias", 2 * Td);
-            GETP(gg, p + "grn.gamma", 2 * Td); GETP(gb, p + "grn.beta", 2 * Td);
-            GETP(w2, p + "pwconv2.weight", (int64_t)2 * Td * Td); GETP(b2, p + "pwconv2.bias", Td);
+            GET_PARAM(dw, P, p + "dwconv.weight", (int64_t)Td * 7); GET_PARAM(db, P, p + "dwconv.bias", Td);
+            GET_PARAM(lw, P, p + "norm.weight", Td); GET_PARAM(lb, P, p + "norm.bias", Td);
+            GET_PARAM(w1, P, p + "pwconv1.weight", (int64_t)2 * Td * Td); GET_PARAM(b1, P, p + "pwconv1.bias", 2 * Td);
+            GET_PARAM(gg, P, p + "grn.gamma", 2 * Td); GET_PARAM(gb, P, p + "grn.beta", 2 * Td);
+            GET_PARAM(w2, P, p + "pwconv2.weight", (int64_t)2 * Td * Td); GET_PARAM(b2, P, p + "pwconv2.bias", Td);
             if (upload_f32(&b.dw_w, dw->data(), dw->size()) || upload_f32(&b.dw_b, db->data(), db->size()) ||
                 upload_f32(&b.ln_w, lw->data(), lw->size()) || upload_f32(&b.ln_b, lb->data(), lb->size()) ||
                 upload_f32(&b.gamma, gg->data(), gg->size()) || upload_f32(&b.beta, gb->data(), gb->size())) return -4;
@@ -233,8 +254,8 @@ int f5hip_dit_finalize(f5hip_dit* m) {
     {
         const bool mm = m->arch == 2;   // MMDiT: AudioEmbedding.linear over cat(x, cond) only (mmdit.py:60-70)
         const int Kin = 2 * mel + (mm ? 0 : Td);
-        GETP(w, T + (mm ? "audio_embed.linear.weight" : "input_embed.proj.weight"), (int64_t)D * Kin);
-        GETP(b, T + (mm ? "audio_embed.linear.bias" : "input_embed.proj.bias"), D);
+        GET_PARAM(w, P, T + (mm ? "audio_embed.linear.weight" : "input_embed.proj.weight"), (int64_t)D * Kin);
+        GET_PARAM(b, P, T + (mm ? "audio_embed.linear.bias" : "input_embed.proj.bias"), D);
         const int Kct = 128 + m->td_pad;
         std::vector<float> wx((size_t)D * 128, 0.0f), wct((size_t)D * Kct, 0.0f);
         for (int n = 0; n < D; n++) {
@@ -251,8 +272,8 @@ int f5hip_dit_finalize(f5hip_dit* m) {
     for (int which = 0; which < 2; which++) {
         const int gw = m->gw;
         std::string p = T + (m->arch == 2 ? "audio_embed" : "input_embed") + ".conv_pos_embed.conv1d." + std::to_string(which * 2) + ".";
-        GETP(w, p + "weight", (int64_t)D * gw * 31);
-        GETP(b, p + "bias", D);
+        GET_PARAM(w, P, p + "weight", (int64_t)D * gw * 31);
+        GET_PARAM(b, P, p + "bias", D);
         const int K = 31 * 64;
         std::vector<float> wp((size_t)16 * 64 * K, 0.0f), bp(16 * 64, 0.0f);
         for (int g = 0; g < 16; g++)
@@ -265,58 +286,27 @@ int f5hip_dit_finalize(f5hip_dit* m) {
         if (pack_linear(which ? m->conv2 : m->conv1, wp.data(), 16 * 64, K, K, bp.data())) return -4;
     }
     // --- transformer blocks ---
-    m->wqkv.resize(c.depth); m->wout.resize(c.depth); m->wff1.resize(c.depth); m->wff2.resize(c.depth);
+    m->blk.resize(c.depth);
+    if (m->arch == 2) m->blk_c.resize(c.depth);
     if (m->arch == 1) { m->wskip.resize(c.depth); m->g_attn.assign(c.depth, nullptr); m->g_ff.assign(c.depth, nullptr); }
-    if (m->arch == 2) { m->wqkv_c.resize(c.depth); m->wout_c.resize(c.depth); m->wff1_c.resize(c.depth); m->wff2_c.resize(c.depth); }
     for (int l = 0; l < c.depth; l++) {
         // DiT: transformer_blocks.{l}.attn.* / .ff.*  (F/model/modules.py:542-556);  UNetT: layers.{l}.{0 skip_proj, 1 attn_norm, 2 attn, 3 ff_norm, 4 ff}
         const std::string p = T + (m->arch != 1 ? "transformer_blocks." : "layers.") + std::to_string(l) + ".";
         const std::string pa = p + (m->arch != 1 ? "attn." : "2."), pf = p + (m->arch == 0 ? "ff." : (m->arch == 2 ? "ff_x." : "4."));
-        std::vector<float> wq((size_t)3 * D * D), bq(3 * D);
-        const char* nm[3] = {"to_q", "to_k", "to_v"};
-        for (int i = 0; i < 3; i++) {
-            GETP(w, pa + nm[i] + ".weight", (int64_t)D * D);
-            GETP(b, pa + nm[i] + ".bias", D);
-            memcpy(&wq[(size_t)i * D * D], w->data(), sizeof(float) * D * D);
-            memcpy(&bq[(size_t)i * D], b->data(), sizeof(float) * D);
-        }
-        if (pack_linear(m->wqkv[l], wq.data(), 3 * D, D, D, bq.data(), 128, m->blk_f16) || pack_frag(m->wqkv[l])) return -4;   // (+ fragment order: W-direct gemm5)
-        GETP(wo, pa + "to_out.0.weight", (int64_t)D * D); GETP(bo, pa + "to_out.0.bias", D);
-        if (pack_linear(m->wout[l], wo->data(), D, D, D, bo->data(), 128, m->blk_f16)) return -4;
-        GETP(w1, pf + "ff.0.0.weight", (int64_t)F * D); GETP(b1, pf + "ff.0.0.bias", F);
-        if (pack_linear(m->wff1[l], w1->data(), F, D, D, b1->data(), 128, m->blk_f16) || pack_frag(m->wff1[l])) return -4;
-        GETP(w2, pf + "ff.2.weight", (int64_t)D * F); GETP(b2, pf + "ff.2.bias", D);
-        if (pack_linear(m->wff2[l], w2->data(), D, F, F, b2->data(), 128, m->blk_f16)) return -4;
-        if (m->arch == 2) {   // the text stream's own projections (Attention(context_dim=...), F/model/modules.py:365-374) and feed-forward
-            std::vector<float> wqc((size_t)3 * D * D), bqc(3 * D);
-            const char* nmc[3] = {"to_q_c", "to_k_c", "to_v_c"};
-            for (int i = 0; i < 3; i++) {
-                GETP(w, pa + nmc[i] + ".weight", (int64_t)D * D);
-                GETP(b, pa + nmc[i] + ".bias", D);
-                memcpy(&wqc[(size_t)i * D * D], w->data(), sizeof(float) * D * D);
-                memcpy(&bqc[(size_t)i * D], b->data(), sizeof(float) * D);
-            }
-            if (pack_linear(m->wqkv_c[l], wqc.data(), 3 * D, D, D, bqc.data(), 128, m->blk_f16) || pack_frag(m->wqkv_c[l])) return -4;
-            if (l < c.depth - 1) {
-                GETP(woc, pa + "to_out_c.weight", (int64_t)D * D); GETP(boc, pa + "to_out_c.bias", D);
-                if (pack_linear(m->wout_c[l], woc->data(), D, D, D, boc->data(), 128, m->blk_f16)) return -4;
-                GETP(w1c, p + "ff_c.ff.0.0.weight", (int64_t)F * D); GETP(b1c, p + "ff_c.ff.0.0.bias", F);
-                if (pack_linear(m->wff1_c[l], w1c->data(), F, D, D, b1c->data(), 128, m->blk_f16) || pack_frag(m->wff1_c[l])) return -4;
-                GETP(w2c, p + "ff_c.ff.2.weight", (int64_t)D * F); GETP(b2c, p + "ff_c.ff.2.bias", D);
-                if (pack_linear(m->wff2_c[l], w2c->data(), D, F, F, b2c->data(), 128, m->blk_f16)) return -4;
-            }
-        }
+        CK(pack_block(m, m->blk, l, pa, "", pa + "to_out.0", pf));
+        // MMDiT: the text stream's own projections (Attention(context_dim=...), F/model/modules.py:365-374) and feed-forward
+        if (m->arch == 2) CK(pack_block(m, m->blk_c, l, pa, "_c", l < c.depth - 1 ? pa + "to_out_c" : "", p + "ff_c."));
         if (m->arch == 1) {
-            GETP(ga, p + "1.g", D); GETP(gf, p + "3.g", D);
+            GET_PARAM(ga, P, p + "1.g", D); GET_PARAM(gf, P, p + "3.g", D);
             if (upload_f32(&m->g_attn[l], ga->data(), D) || upload_f32(&m->g_ff[l], gf->data(), D)) return -4;
             if (l >= c.depth / 2) {
-                GETP(ws, p + "0.weight", (int64_t)D * 2 * D);
+                GET_PARAM(ws, P, p + "0.weight", (int64_t)D * 2 * D);
                 if (pack_linear(m->wskip[l], ws->data(), D, 2 * D, 2 * D, nullptr)) return -4;
             }
         }
     }
     if (m->arch == 1) {
-        GETP(go, T + "norm_out.g", D);
+        GET_PARAM(go, P, T + "norm_out.g", D);
         if (upload_f32(&m->g_out, go->data(), D)) return -4;
     }
     {
@@ -324,23 +314,18 @@ int f5hip_dit_finalize(f5hip_dit* m) {
         if (upload_f32(&m->zeros, z.data(), z.size())) return -4;
     }
     {
-        GETP(w, T + "proj_out.weight", (int64_t)mel * D); GETP(b, T + "proj_out.bias", mel);
+        GET_PARAM(w, P, T + "proj_out.weight", (int64_t)mel * D); GET_PARAM(b, P, T + "proj_out.bias", mel);
         if (pack_linear(m->proj_out, w->data(), mel, D, D, b->data())) return -4;
     }
-    // --- rotary tables (x-transformers 2.2.8 RotaryEmbedding): angle = pos * 10000^(-2i/64) in fp32 ---
     {
-        // 4097 rows: UNetT puts the time token at position 0, so a 4096-frame sequence reaches position 4096 (unett.py:184-188)
-        std::vector<float> rc((size_t)4097 * 32), rs((size_t)4097 * 32);
-        for (int pos = 0; pos < 4097; pos++)
-            for (int i = 0; i < 32; i++) {
-                float inv = 1.0f / powf(10000.0f, (float)(2 * i) / 64.0f);
-                float ang = (float)pos * inv;
-                rc[(size_t)pos * 32 + i] = (float)cos((double)ang);
-                rs[(size_t)pos * 32 + i] = (float)sin((double)ang);
-            }
+        std::vector<float> rc, rs;
+        rope_tables(rc, rs);
         if (upload_f32(&m->rope_cos, rc.data(), rc.size()) || upload_f32(&m->rope_sin, rs.data(), rs.size())) return -4;
     }
-    m->host.clear();
+    // pack_frag only enqueues its kernels: wait for every packing kernel and check them once before the weights are used
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(-4, "finalize: weight packing: %s", hipGetErrorString(e));
+    m->params.host.clear();
     m->finalized = true;
     return 0;
 }
@@ -474,7 +459,7 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
     // rotary factors per row of this layout (one load in the QKV epilogues instead of row_pos -> table)
     hipLaunchKernelGGL(rope_rows_kernel, dim3((R * 32 + 255) / 256), dim3(256), 0, st, m->d_row_pos, m->rope_cos, m->rope_sin, R, 4097, m->rope_row_cos, m->rope_row_sin);
     if (hipGetLastError() != hipSuccess) return fail(-7, "rope_rows_kernel launch");
-    m->M = rows_x; m->M_pad = rows_x; m->Mc = R - rows_x; m->Rtot = R; m->n_seq = S; m->n_frames = U;
+    m->M = rows_x; m->Mc = R - rows_x; m->Rtot = R; m->n_seq = S; m->n_frames = U;
     return 0;
 }
 
@@ -541,7 +526,7 @@ static int run_gemm_n(int nsplit, int mp, GemmArgs& a, const PackedW& W, int epi
     return 0;
 }
 static int run_gemm(f5hip_dit* m, GemmArgs& a, const PackedW& W, int epi, bool conv, int bn, hipStream_t st, int m_pad = -1) {
-    return run_gemm_n(W.f16 ? 3 : m->nsplit, m_pad > 0 ? m_pad : m->M_pad, a, W, epi, conv, bn, st);
+    return run_gemm_n(W.f16 ? 3 : m->nsplit, m_pad > 0 ? m_pad : m->M, a, W, epi, conv, bn, st);
 }
 
 static int run_ln(const LnArgs& a, hipStream_t st) {
@@ -562,13 +547,6 @@ static int run_ln(const LnArgs& a, hipStream_t st) {
     return 0;
 }
 
-// Residual GEMM g (out projection / FF2: updates the stream h in place) followed by the LayerNorm `ln` over h.  (Fusing the norm behind the
-// GEMM's epilogue measured slower -- 31.2 us against 18.8 + 6.1 us for the two launches: profiles/r02_ln_fusion.txt.)
-static int run_gemm_ln(f5hip_dit* m, GemmArgs& g, const PackedW& W, const LnArgs& ln, hipStream_t st) {
-    if (const int r = run_gemm(m, g, W, EPI_GENERIC, false, 64, st)) return r;
-    return run_ln(ln, st);
-}
-
 // Diagnostics for tests: which GEMM path the launches since the last reset took (names in the order of the CNT_ enum); name "reset" zeroes them.
 extern "C" int f5hip_get_counter(const char* name, int64_t* value) {
     static const char* names[CNT_COUNT] = {"gemm5_rb11", "gemm5_rb8", "gemm5_wide", "gemm3_wide", "conv5", "gemm6", "gemm6_r176", "gemm6_r256",
@@ -579,9 +557,6 @@ extern "C" int f5hip_get_counter(const char* name, int64_t* value) {
         if (!strcmp(name, names[i])) { if (value) *value = g_counters[i]; return 0; }
     return fail(-1, "unknown counter %s", name);
 }
-
-#define CK(x) do { int _r = (x); if (_r) return _r; } while (0)
-#define CKL(name) do { hipError_t _e = hipGetLastError(); if (_e != hipSuccess) return fail(-7, "%s launch: %s", name, hipGetErrorString(_e)); } while (0)
 
 // -------------------------------------------------------------------------------------------------
 // step-invariant precompute: text embedding for every sequence, cond/text part of the input projection
@@ -681,6 +656,55 @@ static void set_rope(GemmArgs& q, const f5hip_dit* m, int row_off) {
     q.row_pos = nullptr; q.rope_cos = m->rope_row_cos + (size_t)row_off * 32; q.rope_sin = m->rope_row_sin + (size_t)row_off * 32;
 }
 
+// One residual stream of the transformer blocks: rows [row0, row0 + rows) of every per-row buffer (h, hn, ao, ff, qk, V^T columns) --
+// the audio rows [0, M), or MMDiT's text rows [M, M + Mc) -- and its block weights.  keep: the out projection zeroes the padded rows of
+// masked sequences (row_keep; the audio stream only).
+struct Stream { int row0, rows; const BlockWeights* w; bool keep; };
+static Stream audio_stream(const f5hip_dit* m) { return {0, m->M, &m->blk, true}; }
+static Plane2 rows_from(const Plane2& p, size_t off) { return {p.hi + off, p.lo + off}; }
+
+// h += gate * (A W^T + b) over the stream's rows (gate null: none)
+static int block_residual(f5hip_dit* m, const Stream& s, const Plane2& A, int lda, const PackedW& W, const float* gate, const int* keep, hipStream_t st) {
+    const int D = m->cfg.dim;
+    GemmArgs g = gemm_base(A, lda, W, s.rows);
+    g.mul = gate; g.res = m->h + (size_t)s.row0 * D; g.ldres = D; g.out_f32 = m->h + (size_t)s.row0 * D; g.ldo = D; g.row_keep = keep;
+    return run_gemm(m, g, W, EPI_GENERIC, false, 64, st, s.rows);
+}
+
+// block l's QKV projection of the stream's rows hn: rotary q | k into qk, V^T into vt (rows of the current layout)
+static int block_qkv(f5hip_dit* m, const Stream& s, int l, hipStream_t st) {
+    const int D = m->cfg.dim;
+    const size_t r0 = s.row0;
+    GemmArgs q = gemm_base(rows_from(m->hn, r0 * D), D, s.w->qkv[l], s.rows);
+    q.D = D; set_rope(q, m, s.row0); q.qk = m->qk + r0 * 2 * D; q.vt = m->vt + r0; q.ldvt = m->Rtot;
+    return run_gemm(m, q, s.w->qkv[l], EPI_QKV, false, 128, st, s.rows);
+}
+
+// block l's out projection of the attention output ao into the stream
+static int block_out(f5hip_dit* m, const Stream& s, int l, const float* gate, hipStream_t st) {
+    const int D = m->cfg.dim;
+    return block_residual(m, s, rows_from(m->ao, (size_t)s.row0 * D), D, s.w->out[l], gate, s.keep && m->any_masked ? m->d_row_keep : nullptr, st);
+}
+
+// block l's feed-forward of the stream's rows hn: FF1 (GELU tanh) into ff, then FF2 into the stream
+static int block_ff(f5hip_dit* m, const Stream& s, int l, const float* gate, hipStream_t st) {
+    const int D = m->cfg.dim, F = m->cfg.ff_mult * D;
+    const Plane2 ff = rows_from(m->ff, (size_t)s.row0 * F);
+    GemmArgs f1 = gemm_base(rows_from(m->hn, (size_t)s.row0 * D), D, s.w->ff1[l], s.rows);
+    f1.act = ACT_GELU_TANH; f1.out_hi = ff.hi; f1.out_lo = ff.lo; f1.ldob = F; f1.f16_out = m->blk_f16 ? 1 : 0;
+    CK(run_gemm(m, f1, s.w->ff1[l], EPI_GENERIC, false, 128, st, s.rows));
+    return block_residual(m, s, ff, F, s.w->ff2[l], gate, nullptr, st);
+}
+
+// AdaLayerNorm of the stream's rows of h into hn: LayerNorm(h) * (1 + scale) + shift
+static int run_adaln(f5hip_dit* m, const Stream& s, const float* shift, const float* scale, bool f16, hipStream_t st) {
+    const int D = m->cfg.dim;
+    LnArgs ln; memset(&ln, 0, sizeof(ln));
+    ln.x = m->h + (size_t)s.row0 * D; ln.ldx = D; ln.M = s.rows; ln.D = D; ln.shift = shift; ln.scale = scale; ln.gain_off = 1.0f; ln.eps = 1e-6f;
+    ln.out_hi = m->hn.hi + (size_t)s.row0 * D; ln.out_lo = m->hn.lo + (size_t)s.row0 * D; ln.ldo = D; ln.f16_out = f16 ? 1 : 0;
+    return run_ln(ln, st);
+}
+
 static int launch_attention(f5hip_dit* m, hipStream_t st) {
     const f5hip_dit_config& c = m->cfg;
     AttnArgs at; memset(&at, 0, sizeof(at));
@@ -705,7 +729,8 @@ static int launch_attention(f5hip_dit* m, hipStream_t st) {
 //   x = attn(RMSNorm(x)) + x;  x = ff(RMSNorm(x)) + x,  U-skips: layer l >= depth/2 first does x = W_skip [x || skip(depth-1-l)].
 static int forward_unett_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {
     const f5hip_dit_config& c = m->cfg;
-    const int D = c.dim, F = c.ff_mult * D, M = m->M;
+    const int D = c.dim, M = m->M;
+    const Stream x = audio_stream(m);
     prof_begin(PROF_OTHER, st);
     hipLaunchKernelGGL(set_time_token_kernel, dim3(m->n_seq), dim3(256), 0, st, m->h, D, m->d_seq_row0, m->temb + (size_t)ti * D);
     prof_end(PROF_OTHER, st);
@@ -734,22 +759,13 @@ static int forward_unett_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t 
         }
         ln.scale = m->g_attn[l];
         ln.f16_out = m->blk_f16 ? 1 : 0;   // block norms feed the fp16 block GEMMs in mixed mode; the final norm (proj_out) stays split bf16
-        GemmArgs q = gemm_base(m->hn, D, m->wqkv[l], M);
-        q.D = D; set_rope(q, m, 0); q.qk = m->qk; q.vt = m->vt; q.ldvt = m->Rtot;
         CK(run_ln(ln, st));
-        CK(run_gemm(m, q, m->wqkv[l], EPI_QKV, false, 128, st));
+        CK(block_qkv(m, x, l, st));
         CK(launch_attention(m, st));
-        GemmArgs o = gemm_base(m->ao, D, m->wout[l], M);
-        o.res = m->h; o.ldres = D; o.out_f32 = m->h; o.ldo = D;
-        o.row_keep = m->any_masked ? m->d_row_keep : nullptr;
+        CK(block_out(m, x, l, nullptr, st));
         ln.scale = m->g_ff[l];
-        CK(run_gemm_ln(m, o, m->wout[l], ln, st));     // out projection + the feed-forward norm behind it
-        GemmArgs f1 = gemm_base(m->hn, D, m->wff1[l], M);
-        f1.act = ACT_GELU_TANH; f1.out_hi = m->ff.hi; f1.out_lo = m->ff.lo; f1.ldob = F; f1.f16_out = m->blk_f16 ? 1 : 0;
-        CK(run_gemm(m, f1, m->wff1[l], EPI_GENERIC, false, 128, st));
-        GemmArgs f2 = gemm_base(m->ff, F, m->wff2[l], M);
-        f2.res = m->h; f2.ldres = D; f2.out_f32 = m->h; f2.ldo = D;
-        CK(run_gemm(m, f2, m->wff2[l], EPI_GENERIC, false, 64, st));
+        CK(run_ln(ln, st));
+        CK(block_ff(m, x, l, nullptr, st));
     }
     if (n_blocks >= 0) return 0;
     ln.scale = m->g_out;
@@ -769,63 +785,36 @@ static int forward_unett_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t 
 // context-pre-only: the text stream is only normalised and projected to q / k / v, then dropped.
 static int forward_mmdit_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {
     const f5hip_dit_config& c = m->cfg;
-    const int D = c.dim, F = c.ff_mult * D, M = m->M, Mc = m->Mc;
+    const int D = c.dim, M = m->M, Mc = m->Mc;
     const float* mod = m->mod + (size_t)ti * m->n_adaln;
-    const size_t ro = (size_t)M;                                   // first text row
+    const Stream x = audio_stream(m), tx{M, Mc, &m->blk_c, false};
     // the text stream starts every forward from its step-invariant embedding
-    if (hipMemcpyAsync(m->h + ro * D, m->te + ro * D, sizeof(float) * (size_t)Mc * D, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(-6, "MMDiT: text stream copy");
-    const Plane2 hn_c{m->hn.hi + ro * D, m->hn.lo + ro * D}, ao_c{m->ao.hi + ro * D, m->ao.lo + ro * D}, ff_c{m->ff.hi + ro * F, m->ff.lo + ro * F};
-    auto ln_for = [&](bool text, const float* shift, const float* scale, bool f16) {
-        LnArgs ln; memset(&ln, 0, sizeof(ln));
-        ln.x = m->h + (text ? ro * D : 0); ln.ldx = D; ln.M = text ? Mc : M; ln.D = D; ln.shift = shift; ln.scale = scale; ln.gain_off = 1.0f; ln.eps = 1e-6f;
-        ln.out_hi = text ? hn_c.hi : m->hn.hi; ln.out_lo = text ? hn_c.lo : m->hn.lo; ln.ldo = D; ln.f16_out = f16 ? 1 : 0;
-        return ln;
-    };
+    if (hipMemcpyAsync(m->h + (size_t)M * D, m->te + (size_t)M * D, sizeof(float) * (size_t)Mc * D, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(-6, "MMDiT: text stream copy");
     const int nb = n_blocks < 0 ? c.depth : n_blocks;
     for (int l = 0; l < nb; l++) {
         const bool last = l == c.depth - 1;
         const float* mc = mod + m->mod_c[l];                       // text: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp; last block: scale, shift
         const float* mx = mod + m->mod_x[l];
-        CK(run_ln(last ? ln_for(true, mc + D, mc, m->blk_f16) : ln_for(true, mc, mc + D, m->blk_f16), st));
-        CK(run_ln(ln_for(false, mx, mx + D, m->blk_f16), st));
-        GemmArgs q = gemm_base(m->hn, D, m->wqkv[l], M);
-        q.D = D; set_rope(q, m, 0); q.qk = m->qk; q.vt = m->vt; q.ldvt = m->Rtot;
-        CK(run_gemm(m, q, m->wqkv[l], EPI_QKV, false, 128, st, M));
-        GemmArgs qc = gemm_base(hn_c, D, m->wqkv_c[l], Mc);
-        qc.D = D; set_rope(qc, m, ro);
-        qc.qk = m->qk + ro * 2 * D; qc.vt = m->vt + ro; qc.ldvt = m->Rtot;
-        CK(run_gemm(m, qc, m->wqkv_c[l], EPI_QKV, false, 128, st, Mc));
+        CK(last ? run_adaln(m, tx, mc + D, mc, m->blk_f16, st) : run_adaln(m, tx, mc, mc + D, m->blk_f16, st));
+        CK(run_adaln(m, x, mx, mx + D, m->blk_f16, st));
+        CK(block_qkv(m, x, l, st));
+        CK(block_qkv(m, tx, l, st));
         CK(launch_attention(m, st));
-        GemmArgs o = gemm_base(m->ao, D, m->wout[l], M);
-        o.mul = mx + 2 * D; o.res = m->h; o.ldres = D; o.out_f32 = m->h; o.ldo = D;
-        o.row_keep = m->any_masked ? m->d_row_keep : nullptr;
-        CK(run_gemm(m, o, m->wout[l], EPI_GENERIC, false, 64, st, M));
+        CK(block_out(m, x, l, mx + 2 * D, st));
         if (!last) {
-            GemmArgs oc = gemm_base(ao_c, D, m->wout_c[l], Mc);
-            oc.mul = mc + 2 * D; oc.res = m->h + ro * D; oc.ldres = D; oc.out_f32 = m->h + ro * D; oc.ldo = D;
-            CK(run_gemm(m, oc, m->wout_c[l], EPI_GENERIC, false, 64, st, Mc));
-            CK(run_ln(ln_for(true, mc + 3 * D, mc + 4 * D, m->blk_f16), st));
-            GemmArgs f1c = gemm_base(hn_c, D, m->wff1_c[l], Mc);
-            f1c.act = ACT_GELU_TANH; f1c.out_hi = ff_c.hi; f1c.out_lo = ff_c.lo; f1c.ldob = F; f1c.f16_out = m->blk_f16 ? 1 : 0;
-            CK(run_gemm(m, f1c, m->wff1_c[l], EPI_GENERIC, false, 128, st, Mc));
-            GemmArgs f2c = gemm_base(ff_c, F, m->wff2_c[l], Mc);
-            f2c.mul = mc + 5 * D; f2c.res = m->h + ro * D; f2c.ldres = D; f2c.out_f32 = m->h + ro * D; f2c.ldo = D;
-            CK(run_gemm(m, f2c, m->wff2_c[l], EPI_GENERIC, false, 64, st, Mc));
+            CK(block_out(m, tx, l, mc + 2 * D, st));
+            CK(run_adaln(m, tx, mc + 3 * D, mc + 4 * D, m->blk_f16, st));
+            CK(block_ff(m, tx, l, mc + 5 * D, st));
         }
-        CK(run_ln(ln_for(false, mx + 3 * D, mx + 4 * D, m->blk_f16), st));
-        GemmArgs f1 = gemm_base(m->hn, D, m->wff1[l], M);
-        f1.act = ACT_GELU_TANH; f1.out_hi = m->ff.hi; f1.out_lo = m->ff.lo; f1.ldob = F; f1.f16_out = m->blk_f16 ? 1 : 0;
-        CK(run_gemm(m, f1, m->wff1[l], EPI_GENERIC, false, 128, st, M));
-        GemmArgs f2 = gemm_base(m->ff, F, m->wff2[l], M);
-        f2.mul = mx + 5 * D; f2.res = m->h; f2.ldres = D; f2.out_f32 = m->h; f2.ldo = D;
-        CK(run_gemm(m, f2, m->wff2[l], EPI_GENERIC, false, 64, st, M));
+        CK(run_adaln(m, x, mx + 3 * D, mx + 4 * D, m->blk_f16, st));
+        CK(block_ff(m, x, l, mx + 5 * D, st));
     }
     if (n_blocks >= 0) return 0;
     const float* mf = mod + m->mod_final;                          // (scale, shift): F/model/modules.py:308
-    CK(run_ln(ln_for(false, mf + D, mf, false), st));
+    CK(run_adaln(m, x, mf + D, mf, false, st));
     GemmArgs po = gemm_base(m->hn, D, m->proj_out, M);
     po.out_f32 = m->pred; po.ldo = 128;
-    CK(run_gemm(m, po, m->proj_out, EPI_GENERIC, false, 128, st, M));
+    CK(run_gemm(m, po, m->proj_out, EPI_GENERIC, false, 128, st));
     return 0;
 }
 
@@ -845,7 +834,7 @@ static int run_pos_conv(f5hip_dit* m, GemmArgs& g, const PackedW& W, hipStream_t
 
 static int forward_step(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {
     const f5hip_dit_config& c = m->cfg;
-    const int D = c.dim, F = c.ff_mult * D, M = m->M;
+    const int D = c.dim, M = m->M;
     const float* mod = m->mod + (size_t)ti * m->n_adaln;
     // input projection: x part + precomputed cond/text part
     GemmArgs gi = gemm_base(m->xs, 128, m->wx, M);
@@ -867,47 +856,21 @@ static int forward_step(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {
     const int nb = n_blocks < 0 ? c.depth : n_blocks;
     if (m->arch == 1) return forward_unett_layers(m, ti, n_blocks, st);
     if (m->arch == 2) return forward_mmdit_layers(m, ti, n_blocks, st);
-    // Every LayerNorm but the first follows the residual GEMM in front of it (run_gemm_ln): the out projection is followed by norm 2 of
-    // its block, FF2 by norm 1 of the next block or the final norm.
-    const float* mf = mod + (size_t)c.depth * 6 * D;   // final (scale, shift): F/model/modules.py:308
-    auto block_ln = [&](const float* shift, const float* scale) {
-        LnArgs ln; memset(&ln, 0, sizeof(ln));
-        ln.x = m->h; ln.ldx = D; ln.M = M; ln.D = D; ln.shift = shift; ln.scale = scale; ln.gain_off = 1.0f; ln.eps = 1e-6f;
-        ln.out_hi = m->hn.hi; ln.out_lo = m->hn.lo; ln.ldo = D; ln.f16_out = m->blk_f16 ? 1 : 0;
-        return ln;
-    };
-    if (nb > 0) CK(run_ln(block_ln(mod, mod + D), st));
+    // Each LayerNorm is a launch of its own (fusing the norm into the epilogue of the residual GEMM in front of it measured slower -- 31.2 us
+    // against 18.8 + 6.1 us for the two launches: profiles/r02_ln_fusion.txt).
+    const Stream x = audio_stream(m);
     for (int l = 0; l < nb; l++) {
-        const float* ml = mod + (size_t)l * 6 * D;   // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-        GemmArgs q = gemm_base(m->hn, D, m->wqkv[l], M);
-        q.D = D; set_rope(q, m, 0); q.qk = m->qk; q.vt = m->vt; q.ldvt = m->Rtot;
-        CK(run_gemm(m, q, m->wqkv[l], EPI_QKV, false, 128, st));
+        const float* ml = mod + m->mod_x[l];   // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
+        CK(run_adaln(m, x, ml, ml + D, m->blk_f16, st));
+        CK(block_qkv(m, x, l, st));
         CK(launch_attention(m, st));
-        GemmArgs o = gemm_base(m->ao, D, m->wout[l], M);
-        o.mul = ml + 2 * D; o.res = m->h; o.ldres = D; o.out_f32 = m->h; o.ldo = D;
-        o.row_keep = m->any_masked ? m->d_row_keep : nullptr;
-        CK(run_gemm_ln(m, o, m->wout[l], block_ln(ml + 3 * D, ml + 4 * D), st));
-        GemmArgs f1 = gemm_base(m->hn, D, m->wff1[l], M);
-        f1.act = ACT_GELU_TANH; f1.out_hi = m->ff.hi; f1.out_lo = m->ff.lo; f1.ldob = F; f1.f16_out = m->blk_f16 ? 1 : 0;
-        CK(run_gemm(m, f1, m->wff1[l], EPI_GENERIC, false, 128, st));
-        GemmArgs f2 = gemm_base(m->ff, F, m->wff2[l], M);
-        f2.mul = ml + 5 * D; f2.res = m->h; f2.ldres = D; f2.out_f32 = m->h; f2.ldo = D;
-        if (l + 1 < nb) {
-            CK(run_gemm_ln(m, f2, m->wff2[l], block_ln(ml + 6 * D, ml + 7 * D), st));   // norm 1 of block l + 1
-        } else if (n_blocks < 0) {
-            LnArgs lf = block_ln(mf + D, mf);      // final norm: (scale, shift) order, split-bf16 planes for proj_out
-            lf.f16_out = 0;
-            CK(run_gemm_ln(m, f2, m->wff2[l], lf, st));
-        } else {
-            CK(run_gemm(m, f2, m->wff2[l], EPI_GENERIC, false, 64, st));
-        }
+        CK(block_out(m, x, l, ml + 2 * D, st));
+        CK(run_adaln(m, x, ml + 3 * D, ml + 4 * D, m->blk_f16, st));
+        CK(block_ff(m, x, l, ml + 5 * D, st));
     }
     if (n_blocks >= 0) return 0;
-    if (nb == 0) {                                     // (a model without blocks: the final norm has no GEMM to ride on)
-        LnArgs lf = block_ln(mf + D, mf);
-        lf.f16_out = 0;
-        CK(run_ln(lf, st));
-    }
+    const float* mf = mod + m->mod_final;   // final (scale, shift): F/model/modules.py:308; split-bf16 planes for proj_out
+    CK(run_adaln(m, x, mf + D, mf, false, st));
     GemmArgs po = gemm_base(m->hn, D, m->proj_out, M);
     po.out_f32 = m->pred; po.ldo = 128;
     CK(run_gemm(m, po, m->proj_out, EPI_GENERIC, false, 128, st));

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include <algorithm>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -131,6 +132,28 @@ struct HostStage {
         ptr = nullptr; ev = nullptr; cap = 0; pending = false;
     }
 };
+
+// Host copies of a handle's parameters between its load_param calls and its finalize (which packs them and clears the store).
+struct ParamStore {
+    std::map<std::string, std::vector<float>> host;
+    int load(bool finalized, const char* name, const float* data, int64_t numel) {
+        if (!name || !data || numel <= 0) return fail(-1, "load_param: bad argument");
+        if (finalized) return fail(-2, "load_param after finalize");
+        host[name].assign(data, data + numel);
+        return 0;
+    }
+    const std::vector<float>* get(const std::string& name, int64_t numel) const {
+        auto it = host.find(name);
+        if (it == host.end()) { set_error("missing parameter %s", name.c_str()); return nullptr; }
+        if ((int64_t)it->second.size() != numel) {
+            set_error("parameter %s has %lld elements, expected %lld", name.c_str(), (long long)it->second.size(), (long long)numel);
+            return nullptr;
+        }
+        return &it->second;
+    }
+};
+// inside a finalize: `var` = the parameter `name` of `numel` elements, or return -3
+#define GET_PARAM(var, store, name, numel) const std::vector<float>* var = (store).get(name, numel); if (!var) return -3;
 
 // fragment-ordered second copy of a one-plane fp16 weight (K a multiple of 128, rows a multiple of 16): GemmArgs::Wf
 static int pack_frag(PackedW& w, hipStream_t st = 0) {

@@ -205,16 +205,12 @@ extern "C" int f5hip_op_qkv(int32_t M, int32_t D, const float* a_dev, const floa
     A.hi = b.get<__bf16>((size_t)M_pad * D); A.lo = b.get<__bf16>((size_t)M_pad * D);
     W.hi = b.get<__bf16>((size_t)N_pad * D); W.lo = f16 ? nullptr : b.get<__bf16>((size_t)N_pad * D);
     float* bias = b.get<float>(N_pad);
-    float* rc = b.get<float>((size_t)4097 * 32); float* rs = b.get<float>((size_t)4097 * 32);
+    std::vector<float> hc, hs;
+    rope_tables(hc, hs);
+    float* rc = b.get<float>(hc.size()); float* rs = b.get<float>(hs.size());
     int* pos = b.get<int>(M_pad);
     if (!A.hi || !A.lo || !W.hi || (!f16 && !W.lo) || !bias || !rc || !rs || !pos) return fail(-5, "op_qkv: hipMalloc");
     W.n = N; W.k = D; W.n_pad = N_pad; W.k_pad = D; W.ld = D; W.bias = bias; W.f16 = f16;
-    std::vector<float> hc((size_t)4097 * 32), hs((size_t)4097 * 32);
-    for (int p = 0; p < 4097; p++)
-        for (int i = 0; i < 32; i++) {
-            const float ang = (float)p * (1.0f / powf(10000.0f, (float)(2 * i) / 64.0f));
-            hc[(size_t)p * 32 + i] = (float)cos((double)ang); hs[(size_t)p * 32 + i] = (float)sin((double)ang);
-        }
     std::vector<int> hp(M_pad, 0);
     for (int i = 0; i < M; i++) { if (row_pos[i] < 0 || row_pos[i] > 4096) return fail(-1, "op_qkv: row_pos out of range"); hp[i] = row_pos[i]; }
     if (hipMemcpyAsync(rc, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(rs, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess ||

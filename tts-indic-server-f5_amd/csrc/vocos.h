@@ -15,7 +15,7 @@ struct VocosBlock {
 struct f5hip_vocos {
     f5hip_vocos_config cfg;
     int nsplit = 2;
-    std::map<std::string, std::vector<float>> host;
+    ParamStore params;
     bool finalized = false;
     PackedW embed, head;
     float *norm_w = nullptr, *norm_b = nullptr, *fnorm_w = nullptr, *fnorm_b = nullptr;
@@ -172,58 +172,47 @@ void f5hip_vocos_destroy(f5hip_vocos* v) {
 }
 
 int f5hip_vocos_load_param(f5hip_vocos* v, const char* name, const float* data, int64_t numel) {
-    if (!v || !name || !data || numel <= 0) return fail(-1, "load_param: bad argument");
-    if (v->finalized) return fail(-2, "load_param after finalize");
-    v->host[name].assign(data, data + numel);
-    return 0;
+    return v ? v->params.load(v->finalized, name, data, numel) : fail(-1, "load_param: bad argument");
 }
-
-#define VGETP(var, name, numel)                                                                                     \
-    const std::vector<float>* var = nullptr;                                                                        \
-    {                                                                                                               \
-        auto it = v->host.find(name);                                                                               \
-        if (it == v->host.end()) return fail(-3, "missing parameter %s", std::string(name).c_str());                \
-        if ((int64_t)it->second.size() != (int64_t)(numel)) return fail(-3, "parameter %s: wrong size", std::string(name).c_str()); \
-        var = &it->second;                                                                                          \
-    }
 
 int f5hip_vocos_finalize(f5hip_vocos* v) {
     if (!v) return fail(-1, "null vocoder");
     if (v->finalized) return 0;
     const f5hip_vocos_config& c = v->cfg;
+    const ParamStore& P = v->params;
     const int C = c.in_channels, D = c.dim, I = c.intermediate_dim, NO = c.n_fft + 2;
     {   // embed Conv1d(C -> D, k=7) as a dense implicit GEMM: K = 7 taps x 128 (channels padded)
-        VGETP(w, "backbone.embed.weight", (int64_t)D * C * 7); VGETP(b, "backbone.embed.bias", D);
+        GET_PARAM(w, P, "backbone.embed.weight", (int64_t)D * C * 7); GET_PARAM(b, P, "backbone.embed.bias", D);
         std::vector<float> wp((size_t)D * 7 * 128, 0.0f);
         for (int co = 0; co < D; co++)
             for (int ci = 0; ci < C; ci++)
                 for (int tap = 0; tap < 7; tap++) wp[(size_t)co * 896 + tap * 128 + ci] = (*w)[((size_t)co * C + ci) * 7 + tap];
         if (pack_linear(v->embed, wp.data(), D, 896, 896, b->data())) return -4;
     }
-    VGETP(nw, "backbone.norm.weight", D); VGETP(nb, "backbone.norm.bias", D);
-    VGETP(fw_, "backbone.final_layer_norm.weight", D); VGETP(fb_, "backbone.final_layer_norm.bias", D);
+    GET_PARAM(nw, P, "backbone.norm.weight", D); GET_PARAM(nb, P, "backbone.norm.bias", D);
+    GET_PARAM(fw_, P, "backbone.final_layer_norm.weight", D); GET_PARAM(fb_, P, "backbone.final_layer_norm.bias", D);
     if (upload_f32(&v->norm_w, nw->data(), D) || upload_f32(&v->norm_b, nb->data(), D) || upload_f32(&v->fnorm_w, fw_->data(), D) ||
         upload_f32(&v->fnorm_b, fb_->data(), D)) return -4;
     v->blk.resize(c.num_layers);
     for (int i = 0; i < c.num_layers; i++) {
         std::string p = "backbone.convnext." + std::to_string(i) + ".";
         VocosBlock& b = v->blk[i];
-        VGETP(dw, p + "dwconv.weight", (int64_t)D * 7); VGETP(db, p + "dwconv.bias", D);
-        VGETP(lw, p + "norm.weight", D); VGETP(lb, p + "norm.bias", D);
-        VGETP(w1, p + "pwconv1.weight", (int64_t)I * D); VGETP(b1, p + "pwconv1.bias", I);
-        VGETP(w2, p + "pwconv2.weight", (int64_t)D * I); VGETP(b2, p + "pwconv2.bias", D);
-        VGETP(gm, p + "gamma", D);
+        GET_PARAM(dw, P, p + "dwconv.weight", (int64_t)D * 7); GET_PARAM(db, P, p + "dwconv.bias", D);
+        GET_PARAM(lw, P, p + "norm.weight", D); GET_PARAM(lb, P, p + "norm.bias", D);
+        GET_PARAM(w1, P, p + "pwconv1.weight", (int64_t)I * D); GET_PARAM(b1, P, p + "pwconv1.bias", I);
+        GET_PARAM(w2, P, p + "pwconv2.weight", (int64_t)D * I); GET_PARAM(b2, P, p + "pwconv2.bias", D);
+        GET_PARAM(gm, P, p + "gamma", D);
         if (upload_f32(&b.dw_w, dw->data(), dw->size()) || upload_f32(&b.dw_b, db->data(), D) || upload_f32(&b.ln_w, lw->data(), D) ||
             upload_f32(&b.ln_b, lb->data(), D) || upload_f32(&b.gamma, gm->data(), D)) return -4;
         if (pack_linear(b.pw1, w1->data(), I, D, D, b1->data())) return -4;
         if (pack_linear(b.pw2, w2->data(), D, I, I, b2->data())) return -4;
     }
     {
-        VGETP(w, "head.out.weight", (int64_t)NO * D); VGETP(b, "head.out.bias", NO);
+        GET_PARAM(w, P, "head.out.weight", (int64_t)NO * D); GET_PARAM(b, P, "head.out.bias", NO);
         if (pack_linear(v->head, w->data(), NO, D, D, b->data())) return -4;
     }
     if (make_fft_tables(&v->window, &v->twiddle, c.n_fft)) return -4;
-    v->host.clear();
+    v->params.host.clear();
     v->finalized = true;
     return 0;
 }
