@@ -396,7 +396,12 @@ def test_conv1d_vs_torch(impl, prec, tol, ci, co, k, dil, batch, P, T):
     w = torch.randn(co, ci, k, generator=g) / (ci * k) ** 0.5
     bias = torch.randn(co, generator=g)
     res = torch.randn(batch * P, co, generator=g)
+    _reset_counters()
     out, _, _ = ops.conv1d(x.to(DEV), w, bias, res.to(DEV), batch=batch, valid=T, dilation=dil, prec=prec, impl=impl)
+    if impl == 5:
+        assert _counter("conv5") == 1
+    else:   # gemm.h, 64-wide tiles for weights padded to 64 rows (c_out <= 64), else 128
+        assert _counter("conv5") == 0 and _counter("gemm_reg_bn64" if co <= 64 else "gemm_reg_bn128") == 1
     ref = _conv_ref(x, w, bias, res, batch, P, T, dil)
     got = out.cpu().view(batch, P, co)[:, :T].double()
     err = (got - ref).abs().max().item()

@@ -313,21 +313,17 @@ int f5hip_bigvgan_finalize(f5hip_bigvgan* v) {
     return 0;
 }
 
-static int bv_conv(f5hip_bigvgan* v, const BvConv& c, const Plane2& A, int M, int P, int T, int act, const float* res, float* out, int ldo,
-                   hipStream_t st) {
+// GemmArgs of the Conv1d c over M rows of operand planes A (sequences of pitch P rows, T of them valid): out [M][c_out] = conv + bias + res
+static GemmArgs conv_args(const BvConv& c, const Plane2& A, int M, int P, int T, const float* res, float* out) {
     GemmArgs g = gemm_base(A, c.c_in_pad, c.w, M);
-    g.conv_kpt = c.c_in_pad / 32; g.conv_center = (c.k - 1) / 2; g.conv_dil = c.dil; g.conv_group_cols = 0;
-    g.row_seq_start = nullptr; g.row_seq_end = nullptr; g.seq_pitch = P; g.seq_valid = T;
-    g.act = act; g.res = res; g.ldres = ldo; g.out_f32 = out; g.ldo = ldo;
-    // conv5.h (window of the tile once in LDS, taps served from it) where it covers the shape, gemm.h otherwise
-    if (v->nsplit >= 2) {
-        prof_begin(PROF_GEMM, st);
-        const hipError_t e = f5_launch_conv5(v->nsplit, g, c.w.n_pad, st);
-        prof_end(PROF_GEMM, st);
-        if (e == hipSuccess) { g_counters[4]++; return 0; }
-        if (e != hipErrorInvalidValue) return fail(-7, "conv5 launch: %s", hipGetErrorString(e));
-    }
-    return run_gemm_n(v->nsplit, M, g, c.w, EPI_GENERIC, true, c.w.n_pad % 128 ? 64 : 128, st);
+    g.conv_kpt = c.c_in_pad / 32; g.conv_center = (c.k - 1) / 2; g.conv_dil = c.dil; g.seq_pitch = P; g.seq_valid = T;
+    g.res = res; g.ldres = c.c_out; g.out_f32 = out; g.ldo = c.c_out;
+    return g;
+}
+
+static int bv_conv(f5hip_bigvgan* v, const BvConv& c, const Plane2& A, int M, int P, int T, const float* res, float* out, hipStream_t st) {
+    GemmArgs g = conv_args(c, A, M, P, T, res, out);
+    return run_conv(v->nsplit, g, c.w, v->nsplit >= 2, true, c.w.n_pad % 128 ? 64 : 128, st);
 }
 
 // Activation1d over fp32 rows x [M][ch] -> the conv operand planes (out == nullptr) or fp32 rows out [M][ch]
@@ -367,18 +363,11 @@ int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const
         }
     }
     if (max_f32 > v->cap) {
-        dev_free(v->ws);
-        Arena a;
-        for (int pass = 0; pass < 2; pass++) {
-            a.reset(pass ? (char*)v->ws : nullptr);
-            v->X = a.f32(max_f32); v->S = a.f32(max_f32); v->Tm = a.f32(max_f32);
-            for (int j = 0; j < 3; j++) v->Y[j] = a.f32(max_f32);
-            v->act = a.plane2(max_act + 4096); v->melp = a.plane2((size_t)batch * P0 * 128 + 4096);
-            if (!pass) {
-                if (hipMalloc(&v->ws, a.used()) != hipSuccess) { v->ws = nullptr; v->cap = 0; return fail(-5, "hipMalloc BigVGAN workspace %zu bytes", a.used()); }
-                if (hipMemset(v->ws, 0, a.used()) != hipSuccess) return fail(-5, "hipMemset BigVGAN workspace");
-            }
-        }
+        if (alloc_workspace(&v->ws, "BigVGAN workspace", [&](Arena& a) {
+                v->X = a.f32(max_f32); v->S = a.f32(max_f32); v->Tm = a.f32(max_f32);
+                for (int j = 0; j < 3; j++) v->Y[j] = a.f32(max_f32);
+                v->act = a.plane2(max_act + 4096); v->melp = a.plane2((size_t)batch * P0 * 128 + 4096);
+            })) { v->cap = 0; return -5; }
         v->cap = max_f32;
     }
     prof_begin(PROF_VOCOS, st);
@@ -387,7 +376,7 @@ int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const
     CKL("bv_mel_rows");
     int M = batch * P0, P = P0, T = T0;
     int ch = v->c0;
-    CK(bv_conv(v, v->pre, v->melp, M, P, T, ACT_NONE, nullptr, v->S, ch, st));   // S = conv_pre(mel)
+    CK(bv_conv(v, v->pre, v->melp, M, P, T, nullptr, v->S, st));   // S = conv_pre(mel)
     {   // operand planes of ups[0]
         const size_t n4 = (size_t)M * ch / 4;
         hipLaunchKernelGGL(bv_mean3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, v->S, v->S, v->S, 1, (size_t)M, ch, (float*)nullptr, v->act.hi, v->act.lo,
@@ -397,7 +386,7 @@ int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const
     for (int i = 0; i < v->n_up; i++) {
         const int r = c.upsample_rates[i], co = ch / 2, cpad = ceil_to(co, 32);
         // ups[i]: 3-tap implicit GEMM over the planes of the previous stage -> X viewed as [M][r*co] == [M*r][co]
-        CK(bv_conv(v, v->ups[i], v->act, M, P, T, ACT_NONE, nullptr, v->X, r * co, st));
+        CK(bv_conv(v, v->ups[i], v->act, M, P, T, nullptr, v->X, st));
         M *= r; P *= r; T *= r; ch = co;
         if (cpad != ch) {   // padded channels of the A operand must read as zero
             if (hipMemsetAsync(v->act.hi, 0, (size_t)M * cpad * 2, st) != hipSuccess || (v->nsplit == 2 && hipMemsetAsync(v->act.lo, 0, (size_t)M * cpad * 2, st) != hipSuccess))
@@ -409,9 +398,9 @@ int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const
             for (int d = 0; d < 3; d++) {
                 const float* in = d == 0 ? v->X : y;   // AMPBlock1: x = x + convs2[d](act(convs1[d](act(x))))
                 CK(bv_snake(v, in, ch, cpad, M, P, T, rb.alpha[2 * d], rb.beta[2 * d], nullptr, st));
-                CK(bv_conv(v, rb.c1[d], v->act, M, P, T, ACT_NONE, nullptr, v->Tm, ch, st));
+                CK(bv_conv(v, rb.c1[d], v->act, M, P, T, nullptr, v->Tm, st));
                 CK(bv_snake(v, v->Tm, ch, cpad, M, P, T, rb.alpha[2 * d + 1], rb.beta[2 * d + 1], nullptr, st));
-                CK(bv_conv(v, rb.c2[d], v->act, M, P, T, ACT_NONE, in, y, ch, st));
+                CK(bv_conv(v, rb.c2[d], v->act, M, P, T, in, y, st));
             }
         }
         // mean of the three blocks: the last stage keeps fp32 rows for activation_post, the others only feed the next up-sampler

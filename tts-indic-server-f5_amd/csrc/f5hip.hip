@@ -339,28 +339,20 @@ static int ensure_workspace(f5hip_dit* m, int rows_pad, int frames, int n_seq) {
     const int D = c.dim, Td = c.text_dim, F = c.ff_mult * D;
     const size_t R = (size_t)std::max(rows_pad, m->cap_rows), U = (size_t)std::max(frames, m->cap_frames),
                  S = (size_t)std::max(n_seq, m->cap_seq);
-    dev_free(m->ws.ptr);
-    Arena a;
-    // pass 1 sizes, pass 2 pointers
-    for (int pass = 0; pass < 2; pass++) {
-        a.reset(pass ? (char*)m->ws.ptr : nullptr);
-        m->h = a.f32(R * D); m->h0 = a.f32(R * D); m->ce = a.f32(R * D); m->pred = a.f32(R * 128);
-        m->te = a.f32(R * Td); m->ty = a.f32(R * 2 * Td); m->gx = a.f32(S * 2 * Td);
-        m->rope_row_cos = a.f32(R * 32); m->rope_row_sin = a.f32(R * 32);
-        m->mod = a.f32((size_t)128 * m->n_adaln + 64); m->xstate = a.f32(U * c.mel_dim); m->xmid = a.f32(U * c.mel_dim); m->temb = a.f32((size_t)128 * D);
-        m->hn = a.plane2(R * D + 256); m->c1 = a.plane2(R * D + 256); m->ao = a.plane2(R * D); m->ff = a.plane2(R * F);
-        m->xs = a.plane2(R * 128); m->tn = a.plane2(R * Td); m->tg = a.plane2(R * 2 * Td); m->act = a.plane2(R * (128 + m->td_pad));
-        m->sinp = a.plane2(128 * 256); m->t1 = a.plane2((size_t)128 * D); m->st = a.plane2((size_t)128 * D);
-        m->skipbuf.resize(m->arch == 1 ? c.depth / 2 : 0);
-        for (auto& sb : m->skipbuf) sb = a.plane2(R * 2 * D);   // [R][2 D]: the concatenated operand [x || skip] of the U-skip Linear, built in place
-        // qk: +256 rows because the last query tile of the attention (up to 256 queries) may read (never store) past the padded rows
-        m->qk = a.bf16((R + 256) * 2 * D); m->vt = a.bf16((size_t)D * R);
-        m->rk_k2 = a.f32(U * c.mel_dim); m->rk_k3 = a.f32(U * c.mel_dim);
-        if (!pass) {
-            if (hipMalloc(&m->ws.ptr, a.used()) != hipSuccess) { m->ws.ptr = nullptr; m->cap_rows = 0; return fail(-5, "hipMalloc workspace %zu bytes", a.used()); }
-            if (hipMemset(m->ws.ptr, 0, a.used()) != hipSuccess) return fail(-5, "hipMemset workspace");
-        }
-    }
+    if (alloc_workspace(&m->ws.ptr, "workspace", [&](Arena& a) {
+            m->h = a.f32(R * D); m->h0 = a.f32(R * D); m->ce = a.f32(R * D); m->pred = a.f32(R * 128);
+            m->te = a.f32(R * Td); m->ty = a.f32(R * 2 * Td); m->gx = a.f32(S * 2 * Td);
+            m->rope_row_cos = a.f32(R * 32); m->rope_row_sin = a.f32(R * 32);
+            m->mod = a.f32((size_t)128 * m->n_adaln + 64); m->xstate = a.f32(U * c.mel_dim); m->xmid = a.f32(U * c.mel_dim); m->temb = a.f32((size_t)128 * D);
+            m->hn = a.plane2(R * D + 256); m->c1 = a.plane2(R * D + 256); m->ao = a.plane2(R * D); m->ff = a.plane2(R * F);
+            m->xs = a.plane2(R * 128); m->tn = a.plane2(R * Td); m->tg = a.plane2(R * 2 * Td); m->act = a.plane2(R * (128 + m->td_pad));
+            m->sinp = a.plane2(128 * 256); m->t1 = a.plane2((size_t)128 * D); m->st = a.plane2((size_t)128 * D);
+            m->skipbuf.resize(m->arch == 1 ? c.depth / 2 : 0);
+            for (auto& sb : m->skipbuf) sb = a.plane2(R * 2 * D);   // [R][2 D]: the concatenated operand [x || skip] of the U-skip Linear, built in place
+            // qk: +256 rows because the last query tile of the attention (up to 256 queries) may read (never store) past the padded rows
+            m->qk = a.bf16((R + 256) * 2 * D); m->vt = a.bf16((size_t)D * R);
+            m->rk_k2 = a.f32(U * c.mel_dim); m->rk_k3 = a.f32(U * c.mel_dim);
+        })) { m->cap_rows = 0; return -5; }
     m->cap_rows = (int)R; m->cap_frames = (int)U; m->cap_seq = (int)S;
     const int need = (int)(R * 8 + S * 15 + U * 3 + 64);
     if (need > m->meta_cap) {
@@ -525,8 +517,29 @@ static int run_gemm_n(int nsplit, int mp, GemmArgs& a, const PackedW& W, int epi
     if (e != hipSuccess) return fail(-7, "gemm launch: %s", hipGetErrorString(e));
     return 0;
 }
+// One implicit-GEMM convolution over g.M rows: conv5.h (window of the tile once in LDS, taps served from it) when `conv5`, else gemm.h
+// (tile width bn).  A shape conv5 does not cover falls back to gemm.h when `fallback`, else fails.
+static int run_conv(int nsplit, GemmArgs& g, const PackedW& W, bool conv5, bool fallback, int bn, hipStream_t st) {
+    if (conv5) {
+        prof_begin(PROF_GEMM, st);
+        const hipError_t e = f5_launch_conv5(nsplit, g, W.n_pad, st);
+        prof_end(PROF_GEMM, st);
+        if (e == hipSuccess) { g_counters[CNT_CONV5]++; return 0; }
+        if (e != hipErrorInvalidValue || !fallback)
+            return fail(-7, "conv5 launch: %s", e == hipErrorInvalidValue ? "does not cover this shape" : hipGetErrorString(e));
+    }
+    return run_gemm_n(nsplit, g.M, g, W, EPI_GENERIC, true, bn, st);
+}
 static int run_gemm(f5hip_dit* m, GemmArgs& a, const PackedW& W, int epi, bool conv, int bn, hipStream_t st, int m_pad = -1) {
     return run_gemm_n(W.f16 ? 3 : m->nsplit, m_pad > 0 ? m_pad : m->M, a, W, epi, conv, bn, st);
+}
+
+// LnArgs of y = LN(x) (gain_off + scale) + shift over rows x [M][ldx] of width D; every other field zero
+static LnArgs ln_args(const float* x, int ldx, int M, int D, const float* scale, const float* shift, float gain_off, float eps) {
+    LnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.ldx = ldx; a.M = M; a.D = D; a.scale = scale; a.shift = shift; a.gain_off = gain_off; a.eps = eps;
+    return a;
 }
 
 static int run_ln(const LnArgs& a, hipStream_t st) {
@@ -582,8 +595,7 @@ static int precompute_text_and_ce(f5hip_dit* m, const float* cond_dev, hipStream
     prof_end(PROF_OTHER, st);
     for (int i = 0; i < c.conv_layers; i++) {
         TextBlock& b = m->tblk[i];
-        LnArgs ln; memset(&ln, 0, sizeof(ln));
-        ln.x = m->te; ln.ldx = Td; ln.M = M; ln.D = Td; ln.scale = b.ln_w; ln.shift = b.ln_b; ln.gain_off = 0.0f; ln.eps = 1e-6f;
+        LnArgs ln = ln_args(m->te, Td, M, Td, b.ln_w, b.ln_b, 0.0f, 1e-6f);
         ln.dw_w = b.dw_w; ln.dw_b = b.dw_b; ln.row_seq_start = m->d_row_start; ln.row_seq_end = m->d_row_end;
         ln.out_hi = m->tn.hi; ln.out_lo = m->tn.lo; ln.ldo = Td;
         CK(run_ln(ln, st));
@@ -699,8 +711,7 @@ static int block_ff(f5hip_dit* m, const Stream& s, int l, const float* gate, hip
 // AdaLayerNorm of the stream's rows of h into hn: LayerNorm(h) * (1 + scale) + shift
 static int run_adaln(f5hip_dit* m, const Stream& s, const float* shift, const float* scale, bool f16, hipStream_t st) {
     const int D = m->cfg.dim;
-    LnArgs ln; memset(&ln, 0, sizeof(ln));
-    ln.x = m->h + (size_t)s.row0 * D; ln.ldx = D; ln.M = s.rows; ln.D = D; ln.shift = shift; ln.scale = scale; ln.gain_off = 1.0f; ln.eps = 1e-6f;
+    LnArgs ln = ln_args(m->h + (size_t)s.row0 * D, D, s.rows, D, scale, shift, 1.0f, 1e-6f);
     ln.out_hi = m->hn.hi + (size_t)s.row0 * D; ln.out_lo = m->hn.lo + (size_t)s.row0 * D; ln.ldo = D; ln.f16_out = f16 ? 1 : 0;
     return run_ln(ln, st);
 }
@@ -736,8 +747,8 @@ static int forward_unett_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t 
     prof_end(PROF_OTHER, st);
     CKL("set_time_token");
     const int nb = n_blocks < 0 ? c.depth : n_blocks;
-    LnArgs ln; memset(&ln, 0, sizeof(ln));
-    ln.x = m->h; ln.ldx = D; ln.M = M; ln.D = D; ln.shift = m->zeros; ln.gain_off = 0.0f; ln.eps = 0.0f; ln.rms = 1;
+    LnArgs ln = ln_args(m->h, D, M, D, nullptr, m->zeros, 0.0f, 0.0f);
+    ln.rms = 1;
     ln.out_hi = m->hn.hi; ln.out_lo = m->hn.lo; ln.ldo = D;
     for (int l = 0; l < nb; l++) {
         if (l < c.depth / 2) {
@@ -822,14 +833,7 @@ static int forward_mmdit_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t 
 // DiT and MMDiT layouts, the implicit GEMM of gemm.h otherwise (UNetT: the time-token row at the head of every sequence has an empty
 // window of its own, which a per-tile bound cannot express).
 static int run_pos_conv(f5hip_dit* m, GemmArgs& g, const PackedW& W, hipStream_t st) {
-    if (m->arch != 1 && m->nsplit == 2 && !W.f16) {
-        prof_begin(PROF_GEMM, st);
-        const hipError_t e = f5_launch_conv5(2, g, W.n_pad, st);
-        prof_end(PROF_GEMM, st);
-        if (e == hipSuccess) { g_counters[CNT_CONV5]++; return 0; }
-        if (e != hipErrorInvalidValue) return fail(-7, "conv5 launch: %s", hipGetErrorString(e));
-    }
-    return run_gemm(m, g, W, EPI_GENERIC, true, 64, st);
+    return run_conv(W.f16 ? 3 : m->nsplit, g, W, m->arch != 1 && m->nsplit == 2 && !W.f16, true, 64, st);
 }
 
 static int forward_step(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {

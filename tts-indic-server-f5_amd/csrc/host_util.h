@@ -60,6 +60,30 @@ struct Arena {
     size_t used() const { return off; }
 };
 
+// A handle's workspace as one zeroed allocation: layout(a) carves every buffer from the Arena a, once to size it and once more over the
+// allocation to set the pointers.  *ws is freed first and is null after a failure.
+template <typename Layout>
+static int alloc_workspace(void** ws, const char* what, Layout layout) {
+    dev_free(*ws);
+    *ws = nullptr;
+    Arena a;
+    layout(a);
+    const size_t bytes = a.used();
+    if (hipMalloc(ws, bytes) != hipSuccess) { *ws = nullptr; return fail(-5, "hipMalloc %s %zu bytes", what, bytes); }
+    if (hipMemset(*ws, 0, bytes) != hipSuccess) { dev_free(*ws); *ws = nullptr; return fail(-5, "hipMemset %s", what); }
+    a.reset((char*)*ws);
+    layout(a);
+    return 0;
+}
+
+// Pageable host -> device copies of whole vectors on st (upload_sync(st, dst0, v0, dst1, v1, ...)), then a wait for them.
+static hipError_t upload_sync(hipStream_t st) { return hipStreamSynchronize(st); }
+template <typename T, typename... Rest>
+static hipError_t upload_sync(hipStream_t st, T* dst, const std::vector<T>& src, const Rest&... rest) {
+    const hipError_t e = hipMemcpyAsync(dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice, st);
+    return e != hipSuccess ? e : upload_sync(st, rest...);
+}
+
 static int upload_f32(float** dst, const float* src, size_t n) {
     if (hipMalloc((void**)dst, n * sizeof(float)) != hipSuccess) { *dst = nullptr; return fail(-4, "hipMalloc %zu floats", n); }
     if (hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(-4, "hipMemcpy H2D");
@@ -162,6 +186,27 @@ static int pack_frag(PackedW& w, hipStream_t st = 0) {
     if (hipMalloc((void**)&w.frag, n * 2) != hipSuccess) { w.frag = nullptr; return fail(-4, "hipMalloc fragment-ordered weight %d x %d", w.n_pad, w.k_pad); }
     hipLaunchKernelGGL(pack_frag_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, st, w.hi, w.n_pad, w.k_pad, w.ld, w.frag);
     return hipGetLastError() == hipSuccess ? 0 : fail(-4, "pack_frag_kernel");
+}
+
+// Runs launch(i) for i = 0 .. warmup + iters - 1 (an int-returning launch, 0 = success) and writes the average time of the last `iters`,
+// measured with HIP events, to *avg_us (when avg_us is non-null and iters > 0).  A failing launch ends the loop; its code is returned.
+template <typename Launch>
+static int time_launches(int warmup, int iters, double* avg_us, hipStream_t st, Launch launch) {
+    const bool timed = avg_us && iters > 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (timed) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); }
+    int rc = 0;
+    for (int i = 0; i < warmup + std::max(iters, 0) && !rc; i++) {
+        if (timed && i == warmup) (void)hipEventRecord(e0, st);
+        rc = launch(i);
+    }
+    if (!timed) return rc;
+    (void)hipEventRecord(e1, st);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.0f;
+    if (!rc && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *avg_us = (double)ms * 1e3 / iters;
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return rc;
 }
 
 // ---------------------------------------------------------------- HIP-event profiling per kernel class

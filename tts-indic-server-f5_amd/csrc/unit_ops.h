@@ -19,30 +19,47 @@ static void op_pack_planes(const float* src, int R, int C, int R_pad, __bf16* hi
     hipLaunchKernelGGL(pack_weight_kernel, dim3(R_pad), dim3(256), 0, st, src, R, C, C, hi, f16 ? (__bf16*)nullptr : lo, C);
 }
 
-// diagnostics of the W-direct gemm5 kernels (F5HIP_GEMM5_STAMPS=1, tools/gemm5_stamps.py): s_memrealtime stamps (100 MHz) of wave 0 (consumer)
-// and wave 4 (loader) of every workgroup
+// Stamp buffer of the diagnostics kernels, [4096 workgroups][16] words, zeroed and then written by launch(d, rep) for rep = 0, 1, 2.  h: its host
+// copy (left empty when the buffer cannot be allocated); ng: workgroups up to the last that stamped; tmin / tmax: first start, last end.
 template <typename Launch>
-static int gemm5_stamp_report(OpBufs& b, int M, int N, int K, hipStream_t st, Launch launch) {
+static int collect_stamps(OpBufs& b, hipStream_t st, Launch launch, std::vector<unsigned long long>& h, int& ng, unsigned long long& tmin,
+                          unsigned long long& tmax) {
     const int maxg = 4096;
     unsigned long long* d = b.get<unsigned long long>((size_t)maxg * 16);
     if (!d) return 0;
     (void)hipMemsetAsync(d, 0, sizeof(unsigned long long) * maxg * 16, st);
     for (int rep = 0; rep < 3; rep++) CK(launch(d, rep));
     (void)hipStreamSynchronize(st);
-    std::vector<unsigned long long> h((size_t)maxg * 16);
+    h.resize((size_t)maxg * 16);
     (void)hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost);
-    unsigned long long tmin = ~0ull, tmax = 0;
-    int ng = 0;
     for (int g2 = 0; g2 < maxg; g2++) if (h[(size_t)g2 * 16]) { ng = g2 + 1; tmin = std::min(tmin, h[(size_t)g2 * 16]); tmax = std::max(tmax, std::max(h[(size_t)g2 * 16 + 6], h[(size_t)g2 * 16 + 14])); }
+    return 0;
+}
+
+// one stderr line: fmt with the arguments `head`, then the min, median and max of v (nothing when v is empty)
+template <typename... Head>
+static void print_spread(std::vector<double> v, const char* fmt, Head... head) {
+    if (v.empty()) return;
+    std::sort(v.begin(), v.end());
+    fprintf(stderr, fmt, head..., v.front(), v[v.size() / 2], v.back());
+}
+
+// diagnostics of the W-direct gemm5 kernels (F5HIP_GEMM5_STAMPS=1, tools/gemm5_stamps.py): s_memrealtime stamps (100 MHz) of wave 0 (consumer)
+// and wave 4 (loader) of every workgroup
+template <typename Launch>
+static int gemm5_stamp_report(OpBufs& b, int M, int N, int K, hipStream_t st, Launch launch) {
+    std::vector<unsigned long long> h;
+    int ng = 0;
+    unsigned long long tmin = ~0ull, tmax = 0;
+    CK(collect_stamps(b, st, launch, h, ng, tmin, tmax));
+    if (h.empty()) return 0;
     const char* names[7] = {"start", "tile0 landed (loader)", "k-loop end", "E1 passed", "E2 passed (slab done)", "row phase issued", "stores drained"};
     fprintf(stderr, "[gemm5 stamps] M %d N %d K %d: %d workgroups, first start -> last end %.2f us\n", M, N, K, ng, (tmax - tmin) * 0.01);
     for (int w = 0; w < 2; w++)
         for (int i = 0; i < 7; i++) {
             std::vector<double> v;
             for (int g2 = 0; g2 < ng; g2++) { const unsigned long long t = h[(size_t)g2 * 16 + w * 8 + i]; if (t) v.push_back((t - tmin) * 0.01); }
-            if (v.empty()) continue;
-            std::sort(v.begin(), v.end());
-            fprintf(stderr, "[gemm5 stamps]   wave %d  %-26s min %6.2f  median %6.2f  max %6.2f us after the first workgroup started\n", w * 4, names[i], v.front(), v[v.size() / 2], v.back());
+            print_spread(v, "[gemm5 stamps]   wave %d  %-26s min %6.2f  median %6.2f  max %6.2f us after the first workgroup started\n", w * 4, names[i]);
         }
     // epilogue duration (E1 -> end of the row phase) by column slab of the tile (XCD-blocked order of gemm5_tile_of_block, 16 column slabs)
     if (ng == 256) {
@@ -52,8 +69,7 @@ static int gemm5_stamp_report(OpBufs& b, int M, int N, int K, hipStream_t st, La
                 const int tile = (g2 & 7) * (ng >> 3) + (g2 >> 3);
                 if (tile % 16 == tn) v.push_back((h[(size_t)g2 * 16 + 5] - h[(size_t)g2 * 16 + 3]) * 0.01);
             }
-            std::sort(v.begin(), v.end());
-            fprintf(stderr, "[gemm5 stamps]   column slab %2d: epilogue min %5.2f median %5.2f max %5.2f us\n", tn, v.front(), v[v.size() / 2], v.back());
+            print_spread(v, "[gemm5 stamps]   column slab %2d: epilogue min %5.2f median %5.2f max %5.2f us\n", tn);
         }
     }
     return 0;
@@ -62,17 +78,11 @@ static int gemm5_stamp_report(OpBufs& b, int M, int N, int K, hipStream_t st, La
 // diagnostics of gemm6 (F5HIP_GEMM6_STAMPS=1, tools/gemm6_stamps.py): per-workgroup time line from the kernel's run-time stamps
 template <typename Launch>
 static int gemm6_stamp_report(OpBufs& b, int M, int N, int K, hipStream_t st, Launch launch) {
-    const int maxg = 4096;
-    unsigned long long* d = b.get<unsigned long long>((size_t)maxg * 16);
-    if (!d) return 0;
-    (void)hipMemsetAsync(d, 0, sizeof(unsigned long long) * maxg * 16, st);
-    for (int rep = 0; rep < 3; rep++) CK(launch(d, rep));
-    (void)hipStreamSynchronize(st);
-    std::vector<unsigned long long> h((size_t)maxg * 16);
-    (void)hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost);
-    unsigned long long tmin = ~0ull, tmax = 0;
+    std::vector<unsigned long long> h;
     int ng = 0;
-    for (int g2 = 0; g2 < maxg; g2++) if (h[(size_t)g2 * 16]) { ng = g2 + 1; tmin = std::min(tmin, h[(size_t)g2 * 16]); tmax = std::max(tmax, std::max(h[(size_t)g2 * 16 + 6], h[(size_t)g2 * 16 + 14])); }
+    unsigned long long tmin = ~0ull, tmax = 0;
+    CK(collect_stamps(b, st, launch, h, ng, tmin, tmax));
+    if (h.empty()) return 0;
     fprintf(stderr, "[gemm6 stamps] M %d N %d K %d: %d workgroups, first start -> last end %.2f us\n", M, N, K, ng, (tmax - tmin) * 0.01);
     const char* names[6] = {"k-loop", "quarter 0", "quarter 1", "quarter 2", "quarter 3", "store drain"};
     for (int w = 0; w < 2; w++)
@@ -82,9 +92,7 @@ static int gemm6_stamp_report(OpBufs& b, int M, int N, int K, hipStream_t st, La
                 const unsigned long long t0 = h[(size_t)g2 * 16 + w * 8 + i], t1 = h[(size_t)g2 * 16 + w * 8 + i + 1];
                 if (t0 && t1) v.push_back((t1 - t0) * 0.01);
             }
-            if (v.empty()) continue;
-            std::sort(v.begin(), v.end());
-            fprintf(stderr, "[gemm6 stamps]   wave %d  %-12s duration min %6.2f  median %6.2f  max %6.2f us\n", w * 4, names[i], v.front(), v[v.size() / 2], v.back());
+            print_spread(v, "[gemm6 stamps]   wave %d  %-12s duration min %6.2f  median %6.2f  max %6.2f us\n", w * 4, names[i]);
         }
     {   // the shader clock the k-loops ran at: s_memtime cycles over s_memrealtime (100 MHz) ticks
         std::vector<double> v;
@@ -92,10 +100,7 @@ static int gemm6_stamp_report(OpBufs& b, int M, int N, int K, hipStream_t st, La
             const unsigned long long cyc = h[(size_t)g2 * 16 + 7], t0 = h[(size_t)g2 * 16], t1 = h[(size_t)g2 * 16 + 1];
             if (cyc && t1 > t0) v.push_back((double)cyc / ((double)(t1 - t0) * 10.0));   // cycles per ns = GHz
         }
-        if (!v.empty()) {
-            std::sort(v.begin(), v.end());
-            fprintf(stderr, "[gemm6 stamps]   shader clock during the k-loop: min %.2f  median %.2f  max %.2f GHz  (the 2.5 PFLOP/s roof is 2.4 GHz x 4096 FLOP / clk / CU x 256 CUs)\n", v.front(), v[v.size() / 2], v.back());
-        }
+        print_spread(v, "[gemm6 stamps]   shader clock during the k-loop: min %.2f  median %.2f  max %.2f GHz  (the 2.5 PFLOP/s roof is 2.4 GHz x 4096 FLOP / clk / CU x 256 CUs)\n");
     }
     {   // start times: how the rounds lay out
         std::vector<double> v;
@@ -140,8 +145,7 @@ extern "C" int f5hip_op_gemm(int32_t M, int32_t N, int32_t K, const float* a_dev
         keep = b.get<int>(M_pad);
         std::vector<int> hk(M_pad, 0);
         for (int i = 0; i < M; i++) hk[i] = row_keep_host[i];
-        if (!keep || hipMemcpyAsync(keep, hk.data(), sizeof(int) * M_pad, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return fail(-6, "op_gemm: row_keep upload");
+        if (!keep || upload_sync(st, keep, hk) != hipSuccess) return fail(-6, "op_gemm: row_keep upload");
     }
     auto args_for = [&](const PackedW& W) {
         GemmArgs g = gemm_base(A, K, W, M);
@@ -154,37 +158,23 @@ extern "C" int f5hip_op_gemm(int32_t M, int32_t N, int32_t K, const float* a_dev
         GemmArgs g = args_for(Ws[0]);
         CK(run_gemm_n(prec, M_pad, g, Ws[0], EPI_GENERIC, false, bn, st));
     }
-    if (getenv("F5HIP_GEMM5_STAMPS"))
-        CK(gemm5_stamp_report(b, M, N, K, st, [&](unsigned long long* d, int rep) {
-            GemmArgs g = args_for(Ws[rep % w_copies]);
-            g.stamps = d;
-            return run_gemm_n(prec, M_pad, g, Ws[rep % w_copies], EPI_GENERIC, false, bn, st);
-        }));
-    if (getenv("F5HIP_GEMM6_STAMPS"))
-        CK(gemm6_stamp_report(b, M, N, K, st, [&](unsigned long long* d, int rep) {
-            GemmArgs g = args_for(Ws[rep % w_copies]);
-            g.stamps = d;
-            return run_gemm_n(prec, M_pad, g, Ws[rep % w_copies], EPI_GENERIC, false, bn, st);
-        }));
+    auto stamped = [&](unsigned long long* d, int rep) {   // the diagnostics' launches cycle through the weight copies too
+        GemmArgs g = args_for(Ws[rep % w_copies]);
+        g.stamps = d;
+        return run_gemm_n(prec, M_pad, g, Ws[rep % w_copies], EPI_GENERIC, false, bn, st);
+    };
+    if (getenv("F5HIP_GEMM5_STAMPS")) CK(gemm5_stamp_report(b, M, N, K, st, stamped));
+    if (getenv("F5HIP_GEMM6_STAMPS")) CK(gemm6_stamp_report(b, M, N, K, st, stamped));
     if (iters > 0 && avg_us) {
         // timing: the residual epilogue accumulates in place, so time into a scratch output
         float* scratch = b.get<float>((size_t)M * N);
         if (!scratch) return fail(-5, "op_gemm: hipMalloc scratch");
-        hipEvent_t e0, e1;
-        (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-        for (int it = -3; it < iters; it++) {
-            if (it == 0) (void)hipEventRecord(e0, st);
-            const PackedW& W = Ws[(it + 3) % w_copies];
+        CK(time_launches(3, iters, avg_us, st, [&](int i) {
+            const PackedW& W = Ws[i % w_copies];
             GemmArgs g = args_for(W);
             if (!out16_dev) { g.out_f32 = scratch; if (res_dev) g.res = scratch; }
-            CK(run_gemm_n(prec, M_pad, g, W, EPI_GENERIC, false, bn, st));
-        }
-        (void)hipEventRecord(e1, st);
-        (void)hipEventSynchronize(e1);
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *avg_us = (double)ms * 1e3 / iters;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+            return run_gemm_n(prec, M_pad, g, W, EPI_GENERIC, false, bn, st);
+        }));
     }
     if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_gemm: %s", hipGetErrorString(hipGetLastError()));
     return 0;
@@ -213,9 +203,7 @@ extern "C" int f5hip_op_qkv(int32_t M, int32_t D, const float* a_dev, const floa
     W.n = N; W.k = D; W.n_pad = N_pad; W.k_pad = D; W.ld = D; W.bias = bias; W.f16 = f16;
     std::vector<int> hp(M_pad, 0);
     for (int i = 0; i < M; i++) { if (row_pos[i] < 0 || row_pos[i] > 4096) return fail(-1, "op_qkv: row_pos out of range"); hp[i] = row_pos[i]; }
-    if (hipMemcpyAsync(rc, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(rs, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(pos, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail(-6, "op_qkv: table upload");
+    if (upload_sync(st, rc, hc, rs, hs, pos, hp) != hipSuccess) return fail(-6, "op_qkv: table upload");
     op_pack_planes(w_dev, N, D, N_pad, W.hi, W.lo, f16, st);
     if (f16 && pack_frag(W, st)) return -5;
     if (W.frag) b.ptrs.push_back(W.frag);
@@ -230,16 +218,7 @@ extern "C" int f5hip_op_qkv(int32_t M, int32_t D, const float* a_dev, const floa
             g2.stamps = d;
             return run_gemm_n(prec, M_pad, g2, W, EPI_QKV, false, 128, st);
         }));
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    for (int it = -1; it < iters; it++) {
-        if (it == 0) (void)hipEventRecord(e0, st);
-        CK(run_gemm_n(prec, M_pad, g, W, EPI_QKV, false, 128, st));
-    }
-    (void)hipEventRecord(e1, st);
-    (void)hipEventSynchronize(e1);
-    if (iters > 0 && avg_us) { float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1); *avg_us = (double)ms * 1e3 / iters; }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    CK(time_launches(1, iters, avg_us, st, [&](int) { return run_gemm_n(prec, M_pad, g, W, EPI_QKV, false, 128, st); }));   // the warm-up launch writes the output
     if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_qkv: %s", hipGetErrorString(hipGetLastError()));
     return 0;
 }
@@ -249,9 +228,8 @@ extern "C" int f5hip_op_layernorm(int32_t M, int32_t D, const float* x_dev, cons
                                   int32_t rms, float* out_dev, void* stream) {
     if (M <= 0 || D <= 0 || D % 4 || !x_dev || !scale_dev || !shift_dev || !out_dev) return fail(-1, "op_layernorm: bad argument");
     hipStream_t st = (hipStream_t)stream;
-    LnArgs ln; memset(&ln, 0, sizeof(ln));
-    ln.x = x_dev; ln.ldx = D; ln.M = M; ln.D = D; ln.scale = scale_dev; ln.shift = shift_dev; ln.gain_off = gain_off; ln.eps = eps; ln.rms = rms;
-    ln.out_f32 = out_dev; ln.ldof = D;
+    LnArgs ln = ln_args(x_dev, D, M, D, scale_dev, shift_dev, gain_off, eps);
+    ln.rms = rms; ln.out_f32 = out_dev; ln.ldof = D;
     CK(run_ln(ln, st));
     return 0;
 }
@@ -275,56 +253,66 @@ __global__ __launch_bounds__(256) void op_unpack_planes_kernel(const __bf16* hi,
     for (int c = threadIdx.x; c < D; c += 256) out[(size_t)f * D + c] = (float)hi[(size_t)row * D + c] + (float)lo[(size_t)row * D + c];
 }
 
+// One (pseudo-)sequence of the attention unit ops: query rows row0 .. + len (frames frame0 .. + len of the caller's q / k / v / out) over the
+// key rows kv_row0 .. + kvlen and then, when kv2_len > 0, kv2_row0 .. + kv2_len (the two-range attn3 kernels)
+struct AttnSeq { int row0, len, frame0, kv_row0, kvlen, kv2_row0 = 0, kv2_len = 0; };
+
+// The attention unit ops over `seqs`, whose query rows tile a layout padded to 128 rows per (pseudo-)sequence: q / k / v fp32 frames are packed
+// into the rows, attn3 runs (timed like the other ops: the warm-up launch writes the output), and the split-bf16 output planes are summed back
+// into frame order.  qk, V^T and the output planes carry 256 zeroed slack rows: the last query tile may read (never store) past the padded rows.
+static int attention_op(const char* name, const std::vector<AttnSeq>& seqs, int heads, const float* q_dev, const float* k_dev, const float* v_dev,
+                        float* out_dev, int iters, double* avg_us, hipStream_t st) {
+    const int NS = (int)seqs.size(), D = heads * 64;
+    int M_pad = 0, F = 0, max_len = 0;
+    bool seg2 = false;
+    for (const AttnSeq& s : seqs) {
+        M_pad = std::max(M_pad, ceil_to(s.row0 + s.len, 128)); F += s.len; max_len = std::max(max_len, s.len);
+        seg2 |= s.kv2_len > 0;
+    }
+    const int ld = M_pad + 256;
+    std::vector<int> row_src(M_pad, -1), frame_row(F), meta(6 * NS);
+    for (int i = 0; i < NS; i++) {
+        const AttnSeq& s = seqs[i];
+        for (int j = 0; j < s.len; j++) { row_src[s.row0 + j] = s.frame0 + j; frame_row[s.frame0 + j] = s.row0 + j; }
+        const int fields[6] = {s.row0, s.len, s.kvlen, s.kv_row0, s.kv2_row0, s.kv2_len};   // AttnArgs::seq_row0 .. seq_kv2_len
+        for (int a = 0; a < 6; a++) meta[a * NS + i] = fields[a];
+    }
+    OpBufs b;
+    __bf16* qk = b.get<__bf16>((size_t)ld * 2 * D); __bf16* vt = b.get<__bf16>((size_t)D * ld);
+    __bf16* ohi = b.get<__bf16>((size_t)ld * D); __bf16* olo = b.get<__bf16>((size_t)ld * D);
+    int* d_rs = b.get<int>(M_pad); int* d_fr = b.get<int>(F); int* d_meta = b.get<int>(6 * NS);
+    if (!qk || !vt || !ohi || !olo || !d_rs || !d_fr || !d_meta) return fail(-5, "%s: hipMalloc", name);
+    if (hipMemsetAsync(qk, 0, sizeof(__bf16) * (size_t)ld * 2 * D, st) != hipSuccess || hipMemsetAsync(vt, 0, sizeof(__bf16) * (size_t)D * ld, st) != hipSuccess ||
+        upload_sync(st, d_rs, row_src, d_fr, frame_row, d_meta, meta) != hipSuccess)
+        return fail(-6, "%s: upload", name);
+    hipLaunchKernelGGL(op_pack_qkv_kernel, dim3(M_pad), dim3(256), 0, st, q_dev, k_dev, v_dev, D, d_rs, ld, qk, vt);
+    AttnArgs at; memset(&at, 0, sizeof(at));
+    at.qk = qk; at.vt = vt; at.D = D; at.ldvt = ld; at.seq_row0 = d_meta; at.seq_len = d_meta + NS; at.seq_kvlen = d_meta + 2 * NS;
+    if (seg2) { at.seq_kv_row0 = d_meta + 3 * NS; at.seq_kv2_row0 = d_meta + 4 * NS; at.seq_kv2_len = d_meta + 5 * NS; }
+    at.out_hi = ohi; at.out_lo = olo; at.shape_invariant = -1;
+    CK(time_launches(1, iters, avg_us, st, [&](int) {
+        const hipError_t e = f5_launch_attn3(at, max_len, heads, NS, st);
+        return e == hipSuccess ? 0 : fail(-7, "%s launch: %s", name, hipGetErrorString(e));
+    }));
+    hipLaunchKernelGGL(op_unpack_planes_kernel, dim3(F), dim3(256), 0, st, ohi, olo, D, d_fr, out_dev);
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "%s: %s", name, hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
 // softmax(q k^T / 8 + key-padding mask) v per (sequence, head), head dim 64 (F/model/modules.py:424-436): q / k / v fp32 [sum(seq_len)][64 heads]
 // are rounded to fp16 like the QKV epilogue's outputs (q after the log2(e) / 8 scale); out fp32 [sum(seq_len)][64 heads] = split-bf16 planes summed.
 // impl must be 3 (attn3, the production kernel).
 extern "C" int f5hip_op_attention(int32_t n_seq, const int32_t* seq_len, const int32_t* kv_len, int32_t heads, const float* q_dev,
                                   const float* k_dev, const float* v_dev, float* out_dev, int32_t impl, int32_t iters, double* avg_us, void* stream) {
     if (n_seq <= 0 || !seq_len || heads <= 0 || !q_dev || !k_dev || !v_dev || !out_dev || impl != 3) return fail(-1, "op_attention: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    const int D = heads * 64;
-    int M_pad = 0, F = 0, max_len = 0;
-    for (int i = 0; i < n_seq; i++) {
-        if (seq_len[i] <= 0 || seq_len[i] > 4096 || (kv_len && (kv_len[i] <= 0 || kv_len[i] > seq_len[i]))) return fail(-1, "op_attention: bad lengths");
-        M_pad += (seq_len[i] + 127) / 128 * 128; F += seq_len[i]; max_len = std::max(max_len, (int)seq_len[i]);
-    }
-    std::vector<int> row_src(M_pad, -1), frame_row(F), meta(3 * n_seq);
+    std::vector<AttnSeq> seqs;
     for (int i = 0, r0 = 0, f0 = 0; i < n_seq; i++) {
-        meta[i] = r0; meta[n_seq + i] = seq_len[i]; meta[2 * n_seq + i] = kv_len ? kv_len[i] : seq_len[i];
-        for (int j = 0; j < seq_len[i]; j++) { row_src[r0 + j] = f0 + j; frame_row[f0 + j] = r0 + j; }
-        r0 += (seq_len[i] + 127) / 128 * 128; f0 += seq_len[i];
+        if (seq_len[i] <= 0 || seq_len[i] > 4096 || (kv_len && (kv_len[i] <= 0 || kv_len[i] > seq_len[i]))) return fail(-1, "op_attention: bad lengths");
+        seqs.push_back({r0, seq_len[i], f0, r0, kv_len ? kv_len[i] : seq_len[i]});
+        r0 += ceil_to(seq_len[i], 128); f0 += seq_len[i];
     }
-    OpBufs b;
-    __bf16* qk = b.get<__bf16>((size_t)(M_pad + 256) * 2 * D); __bf16* vt = b.get<__bf16>((size_t)D * M_pad);
-    __bf16* ohi = b.get<__bf16>((size_t)M_pad * D); __bf16* olo = b.get<__bf16>((size_t)M_pad * D);
-    int* d_rs = b.get<int>(M_pad); int* d_fr = b.get<int>(F); int* d_meta = b.get<int>(3 * n_seq);
-    if (!qk || !vt || !ohi || !olo || !d_rs || !d_fr || !d_meta) return fail(-5, "op_attention: hipMalloc");
-    if (hipMemcpyAsync(d_rs, row_src.data(), sizeof(int) * M_pad, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(d_fr, frame_row.data(), sizeof(int) * F, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(d_meta, meta.data(), sizeof(int) * 3 * n_seq, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemsetAsync(qk, 0, sizeof(__bf16) * (size_t)(M_pad + 256) * 2 * D, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail(-6, "op_attention: upload");
-    hipLaunchKernelGGL(op_pack_qkv_kernel, dim3(M_pad), dim3(256), 0, st, q_dev, k_dev, v_dev, D, d_rs, M_pad, qk, vt);
-    AttnArgs at; memset(&at, 0, sizeof(at));
-    at.qk = qk; at.vt = vt; at.D = D; at.ldvt = M_pad; at.seq_row0 = d_meta; at.seq_len = d_meta + n_seq; at.seq_kvlen = d_meta + 2 * n_seq;
-    at.out_hi = ohi; at.out_lo = olo; at.shape_invariant = -1;
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    hipError_t e = hipSuccess;
-    for (int it = -1; it < iters && e == hipSuccess; it++) {
-        if (it == 0) (void)hipEventRecord(e0, st);
-        e = f5_launch_attn3(at, max_len, heads, n_seq, st);
-    }
-    (void)hipEventRecord(e1, st);
-    (void)hipEventSynchronize(e1);
-    if (iters > 0 && avg_us) { float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1); *avg_us = (double)ms * 1e3 / iters; }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(-7, "op_attention launch: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(op_unpack_planes_kernel, dim3(F), dim3(256), 0, st, ohi, olo, D, d_fr, out_dev);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_attention: %s", hipGetErrorString(hipGetLastError()));
-    return 0;
+    return attention_op("op_attention", seqs, heads, q_dev, k_dev, v_dev, out_dev, iters, avg_us, (hipStream_t)stream);
 }
-
 
 // Joint attention of the MMDiT blocks (JointAttnProcessor, F/model/modules.py:496-522): per sequence the queries and the keys are the
 // audio rows followed by the text rows; padding is masked on the audio keys only (x_kvlen <= x_len valid audio keys, every text key).
@@ -333,52 +321,20 @@ extern "C" int f5hip_op_attention(int32_t n_seq, const int32_t* seq_len, const i
 extern "C" int f5hip_op_joint_attention(int32_t n_seq, const int32_t* x_len, const int32_t* x_kvlen, const int32_t* c_len, int32_t heads,
                                         const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, void* stream) {
     if (n_seq <= 0 || !x_len || !c_len || heads <= 0 || !q_dev || !k_dev || !v_dev || !out_dev) return fail(-1, "op_joint_attention: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    const int D = heads * 64;
-    int Mx = 0, Mc = 0, Fx = 0, Fc = 0, max_len = 0;
+    int Mx = 0, Fx = 0;   // audio rows and frames come first, the text rows and tokens behind them
     for (int i = 0; i < n_seq; i++) {
         if (x_len[i] <= 0 || x_len[i] > 4096 || c_len[i] <= 0 || c_len[i] > 4096 || (x_kvlen && (x_kvlen[i] <= 0 || x_kvlen[i] > x_len[i])))
             return fail(-1, "op_joint_attention: bad lengths");
-        Mx += (x_len[i] + 127) / 128 * 128; Mc += (c_len[i] + 127) / 128 * 128; Fx += x_len[i]; Fc += c_len[i];
-        max_len = std::max(max_len, std::max((int)x_len[i], (int)c_len[i]));
+        Mx += ceil_to(x_len[i], 128); Fx += x_len[i];
     }
-    const int M_pad = Mx + Mc, F = Fx + Fc, NS = 2 * n_seq;
-    std::vector<int> row_src(M_pad, -1), frame_row(F), meta(6 * NS);
+    std::vector<AttnSeq> seqs;   // pseudo-sequence 2 i: the audio queries of sequence i, 2 i + 1: its text queries
     for (int i = 0, rx = 0, rc = Mx, fx = 0, fc = Fx; i < n_seq; i++) {
-        for (int j = 0; j < x_len[i]; j++) { row_src[rx + j] = fx + j; frame_row[fx + j] = rx + j; }
-        for (int j = 0; j < c_len[i]; j++) { row_src[rc + j] = fc + j; frame_row[fc + j] = rc + j; }
-        for (int q = 0; q < 2; q++) {              // pseudo-sequence 2 i: audio queries, 2 i + 1: text queries
-            const int s = 2 * i + q;
-            meta[s] = q ? rc : rx;                                  // seq_row0
-            meta[NS + s] = q ? c_len[i] : x_len[i];                 // seq_len
-            meta[2 * NS + s] = x_kvlen ? x_kvlen[i] : x_len[i];     // seq_kvlen (first key range: audio)
-            meta[3 * NS + s] = rx;                                  // seq_kv_row0
-            meta[4 * NS + s] = rc;                                  // seq_kv2_row0
-            meta[5 * NS + s] = c_len[i];                            // seq_kv2_len
-        }
-        rx += (x_len[i] + 127) / 128 * 128; rc += (c_len[i] + 127) / 128 * 128; fx += x_len[i]; fc += c_len[i];
+        const int kv = x_kvlen ? x_kvlen[i] : x_len[i];
+        seqs.push_back({rx, x_len[i], fx, rx, kv, rc, c_len[i]});
+        seqs.push_back({rc, c_len[i], fc, rx, kv, rc, c_len[i]});
+        rx += ceil_to(x_len[i], 128); rc += ceil_to(c_len[i], 128); fx += x_len[i]; fc += c_len[i];
     }
-    OpBufs b;
-    __bf16* qk = b.get<__bf16>((size_t)(M_pad + 256) * 2 * D); __bf16* vt = b.get<__bf16>((size_t)D * (M_pad + 256));
-    __bf16* ohi = b.get<__bf16>((size_t)(M_pad + 256) * D); __bf16* olo = b.get<__bf16>((size_t)(M_pad + 256) * D);
-    int* d_rs = b.get<int>(M_pad); int* d_fr = b.get<int>(F); int* d_meta = b.get<int>(6 * NS);
-    if (!qk || !vt || !ohi || !olo || !d_rs || !d_fr || !d_meta) return fail(-5, "op_joint_attention: hipMalloc");
-    if (hipMemcpyAsync(d_rs, row_src.data(), sizeof(int) * M_pad, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(d_fr, frame_row.data(), sizeof(int) * F, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(d_meta, meta.data(), sizeof(int) * 6 * NS, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemsetAsync(qk, 0, sizeof(__bf16) * (size_t)(M_pad + 256) * 2 * D, st) != hipSuccess ||
-        hipMemsetAsync(vt, 0, sizeof(__bf16) * (size_t)D * (M_pad + 256), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail(-6, "op_joint_attention: upload");
-    hipLaunchKernelGGL(op_pack_qkv_kernel, dim3(M_pad), dim3(256), 0, st, q_dev, k_dev, v_dev, D, d_rs, M_pad + 256, qk, vt);
-    AttnArgs at; memset(&at, 0, sizeof(at));
-    at.qk = qk; at.vt = vt; at.D = D; at.ldvt = M_pad + 256; at.seq_row0 = d_meta; at.seq_len = d_meta + NS; at.seq_kvlen = d_meta + 2 * NS;
-    at.seq_kv_row0 = d_meta + 3 * NS; at.seq_kv2_row0 = d_meta + 4 * NS; at.seq_kv2_len = d_meta + 5 * NS;
-    at.out_hi = ohi; at.out_lo = olo; at.shape_invariant = -1;
-    const hipError_t e = f5_launch_attn3(at, max_len, heads, NS, st);
-    if (e != hipSuccess) return fail(-7, "op_joint_attention launch: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(op_unpack_planes_kernel, dim3(F), dim3(256), 0, st, ohi, olo, D, d_fr, out_dev);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_joint_attention: %s", hipGetErrorString(hipGetLastError()));
-    return 0;
+    return attention_op("op_joint_attention", seqs, heads, q_dev, k_dev, v_dev, out_dev, 0, nullptr, (hipStream_t)stream);
 }
 
 // One Conv1d of the BigVGAN kind over channel-last rows -- batch sequences of pitch P rows, T valid -- through the library's two paths:
@@ -408,33 +364,15 @@ extern "C" int f5hip_op_conv1d(int32_t batch, int32_t P, int32_t T, int32_t c_in
     const size_t n4 = (size_t)M * c_in / 4;
     hipLaunchKernelGGL(bv_mean3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x_dev, x_dev, x_dev, 1, (size_t)M, c_in, (float*)nullptr, A.hi, A.lo, cpad,
                        prec == 3 ? 2 : 1);
-    auto run = [&](float* out, const float* res, unsigned long long* stm) -> int {
-        GemmArgs g = gemm_base(A, c.c_in_pad, c.w, M);
-        g.conv_kpt = c.c_in_pad / 32; g.conv_center = (k - 1) / 2; g.conv_dil = dil; g.seq_pitch = P; g.seq_valid = T;
-        g.res = res; g.ldres = c_out; g.out_f32 = out; g.ldo = c_out; g.stamps = stm;
-        if (impl == 5) {
-            const hipError_t e = f5_launch_conv5(prec, g, c.w.n_pad, st);
-            if (e != hipSuccess) return fail(-7, "op_conv1d: conv5 %s", e == hipErrorInvalidValue ? "does not cover this shape" : hipGetErrorString(e));
-            return 0;
-        }
-        return run_gemm_n(prec, M, g, c.w, EPI_GENERIC, true, c.w.n_pad % 128 ? 64 : 128, st);
+    auto run = [&](float* out, const float* res, unsigned long long* stm) {   // impl 5: conv5 or an error, never the gemm.h fallback
+        GemmArgs g = conv_args(c, A, M, P, T, res, out);
+        g.stamps = stm;
+        return run_conv(prec, g, c.w, impl == 5, false, c.w.n_pad % 128 ? 64 : 128, st);
     };
     int rc = run(out_dev, res_dev, nullptr);
     if (!rc && iters > 0 && avg_us) {
         float* scratch = b.get<float>((size_t)M * c_out);
-        if (!scratch) rc = fail(-5, "op_conv1d: hipMalloc scratch");
-        hipEvent_t e0, e1;
-        (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-        for (int it = -3; it < iters && !rc; it++) {
-            if (it == 0) (void)hipEventRecord(e0, st);
-            rc = run(scratch, nullptr, nullptr);
-        }
-        (void)hipEventRecord(e1, st);
-        (void)hipEventSynchronize(e1);
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *avg_us = 1e3 * ms / iters;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        rc = scratch ? time_launches(3, iters, avg_us, st, [&](int) { return run(scratch, nullptr, nullptr); }) : fail(-5, "op_conv1d: hipMalloc scratch");
         if (!rc && stamps) {
             (void)hipMemsetAsync(stamps, 0, (size_t)stamp_blocks * 16 * 8, st);
             rc = run(scratch, nullptr, stamps);

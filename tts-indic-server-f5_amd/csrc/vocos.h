@@ -224,17 +224,11 @@ int f5hip_vocos_decode(f5hip_vocos* v, int32_t batch, int32_t frames, const floa
     const f5hip_vocos_config& c = v->cfg;
     const int D = c.dim, I = c.intermediate_dim, T = frames, Tp = ceil_to(T, 128), M = batch * Tp, LDY = 1152;
     if (M > v->cap_rows) {
-        dev_free(v->ws); dev_free(v->meta);
-        Arena a;
-        for (int pass = 0; pass < 2; pass++) {
-            a.reset(pass ? (char*)v->ws : nullptr);
-            v->x = a.f32((size_t)M * D); v->y = a.f32((size_t)M * LDY); v->fw = a.f32((size_t)M * 1024);
-            v->melp = a.plane2((size_t)M * 128 + 1024); v->tn = a.plane2((size_t)M * D); v->hid = a.plane2((size_t)M * I);
-            if (!pass) {
-                if (hipMalloc(&v->ws, a.used()) != hipSuccess) { v->ws = nullptr; v->cap_rows = 0; return fail(-5, "hipMalloc vocos workspace"); }
-                if (hipMemset(v->ws, 0, a.used()) != hipSuccess) return fail(-5, "hipMemset vocos workspace");
-            }
-        }
+        dev_free(v->meta);
+        if (alloc_workspace(&v->ws, "vocos workspace", [&](Arena& a) {
+                v->x = a.f32((size_t)M * D); v->y = a.f32((size_t)M * LDY); v->fw = a.f32((size_t)M * 1024);
+                v->melp = a.plane2((size_t)M * 128 + 1024); v->tn = a.plane2((size_t)M * D); v->hid = a.plane2((size_t)M * I);
+            })) { v->meta = nullptr; v->cap_rows = 0; return -5; }
         if (hipMalloc((void**)&v->meta, sizeof(int) * ((size_t)M * 4 + batch)) != hipSuccess) { v->meta = nullptr; return fail(-5, "hipMalloc vocos meta"); }
         v->cap_rows = M;
     }
@@ -245,8 +239,7 @@ int f5hip_vocos_decode(f5hip_vocos* v, int32_t batch, int32_t frames, const floa
         seq_row0[b] = b * Tp;
         for (int t = 0; t < T; t++) { const int r = b * Tp + t; row_seq[r] = b; row_pos[r] = t; row_start[r] = b * Tp; row_end[r] = b * Tp + T; }
     }
-    if (hipMemcpyAsync(v->meta, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail(-6, "vocos metadata upload");
+    if (upload_sync(st, v->meta, h) != hipSuccess) return fail(-6, "vocos metadata upload");
     const int *d_row_seq = v->meta, *d_row_pos = v->meta + M, *d_row_start = v->meta + 2 * M, *d_row_end = v->meta + 3 * M, *d_seq_row0 = v->meta + 4 * M;
 
     prof_begin(PROF_VOCOS, st);
@@ -257,14 +250,12 @@ int f5hip_vocos_decode(f5hip_vocos* v, int32_t batch, int32_t frames, const floa
     e.conv_kpt = 4; e.conv_center = 3; e.conv_group_cols = 0; e.row_seq_start = d_row_start; e.row_seq_end = d_row_end;
     e.out_f32 = v->x; e.ldo = D;
     CK(run_gemm_n(v->nsplit, M, e, v->embed, EPI_GENERIC, true, 128, st));
-    LnArgs ln; memset(&ln, 0, sizeof(ln));
-    ln.x = v->x; ln.ldx = D; ln.M = M; ln.D = D; ln.scale = v->norm_w; ln.shift = v->norm_b; ln.gain_off = 0.0f; ln.eps = 1e-6f;
+    LnArgs ln = ln_args(v->x, D, M, D, v->norm_w, v->norm_b, 0.0f, 1e-6f);
     ln.out_f32 = v->x; ln.ldof = D;
     CK(run_ln(ln, st));
     for (int i = 0; i < c.num_layers; i++) {
         VocosBlock& b = v->blk[i];
-        LnArgs l2; memset(&l2, 0, sizeof(l2));
-        l2.x = v->x; l2.ldx = D; l2.M = M; l2.D = D; l2.scale = b.ln_w; l2.shift = b.ln_b; l2.gain_off = 0.0f; l2.eps = 1e-6f;
+        LnArgs l2 = ln_args(v->x, D, M, D, b.ln_w, b.ln_b, 0.0f, 1e-6f);
         l2.dw_w = b.dw_w; l2.dw_b = b.dw_b; l2.row_seq_start = d_row_start; l2.row_seq_end = d_row_end;
         l2.out_hi = v->tn.hi; l2.out_lo = v->tn.lo; l2.ldo = D;
         CK(run_ln(l2, st));
@@ -275,8 +266,7 @@ int f5hip_vocos_decode(f5hip_vocos* v, int32_t batch, int32_t frames, const floa
         g2.mul = b.gamma; g2.res = v->x; g2.ldres = D; g2.out_f32 = v->x; g2.ldo = D;
         CK(run_gemm_n(v->nsplit, M, g2, b.pw2, EPI_GENERIC, false, 64, st));
     }
-    LnArgs lf; memset(&lf, 0, sizeof(lf));
-    lf.x = v->x; lf.ldx = D; lf.M = M; lf.D = D; lf.scale = v->fnorm_w; lf.shift = v->fnorm_b; lf.gain_off = 0.0f; lf.eps = 1e-6f;
+    LnArgs lf = ln_args(v->x, D, M, D, v->fnorm_w, v->fnorm_b, 0.0f, 1e-6f);
     lf.out_hi = v->tn.hi; lf.out_lo = v->tn.lo; lf.ldo = D;
     CK(run_ln(lf, st));
     GemmArgs hd = gemm_base(v->tn, D, v->head, M);
@@ -293,86 +283,68 @@ int f5hip_vocos_decode(f5hip_vocos* v, int32_t batch, int32_t frames, const floa
 
 // ---------------------------------------------------------------------------------------- mel front-end
 struct MelTables { int n_fft = 0, n_mels = 0, sr = 0; float* window = nullptr; float2* twiddle = nullptr; float* fb = nullptr; };
-static MelTables g_mel;
+static MelTables g_mel, g_mel_bv;   // one set per front-end
 
+// mel scales: HTK, and Slaney's (linear below 1 kHz, logarithmic above)
 static double hz_to_mel_htk(double f) { return 2595.0 * log10(1.0 + f / 700.0); }
 static double mel_to_hz_htk(double m) { return 700.0 * (pow(10.0, m / 2595.0) - 1.0); }
+static double hz_to_mel_slaney(double f) { const double f_sp = 200.0 / 3, min_log_hz = 1000.0; return f >= min_log_hz ? min_log_hz / f_sp + log(f / min_log_hz) / (log(6.4) / 27.0) : f / f_sp; }
+static double mel_to_hz_slaney(double m) { const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp; return m >= min_log_mel ? min_log_hz * exp(log(6.4) / 27.0 * (m - min_log_mel)) : f_sp * m; }
+
+// [nf][n_mels] triangular filters over nf bins from 0 to fmax, their corners equally spaced on the mel scale; slaney: each scaled to unit area
+static std::vector<float> mel_filterbank(int nf, int n_mels, double fmax, double (*hz_to_mel)(double), double (*mel_to_hz)(double), bool slaney) {
+    const double m0 = hz_to_mel(0.0), m1 = hz_to_mel(fmax);
+    std::vector<double> mf(n_mels + 2);
+    for (int i = 0; i < n_mels + 2; i++) mf[i] = mel_to_hz(m0 + (m1 - m0) * (double)i / (double)(n_mels + 1));
+    std::vector<float> fb((size_t)nf * n_mels, 0.0f);
+    for (int k = 0; k < nf; k++) {
+        const double f = fmax * (double)k / (double)(nf - 1);
+        for (int j = 0; j < n_mels; j++) {
+            const double lower = (f - mf[j]) / (mf[j + 1] - mf[j]), upper = (mf[j + 2] - f) / (mf[j + 2] - mf[j + 1]);
+            const double w = std::max(0.0, std::min(lower, upper));
+            fb[(size_t)k * n_mels + j] = (float)(slaney ? w * (2.0 / (mf[j + 2] - mf[j])) : w);
+        }
+    }
+    return fb;
+}
+// torchaudio.functional.melscale_fbanks(n_freqs = 513, f_min = 0, f_max = sr/2, n_mels, sr, norm=None, "htk")
+static std::vector<float> htk_filterbank(int nf, int n_mels, int sr) { return mel_filterbank(nf, n_mels, sr / 2, hz_to_mel_htk, mel_to_hz_htk, false); }
+// librosa.filters.mel(sr, n_fft, n_mels, fmin=0, fmax=sr/2, htk=False, norm="slaney")
+static std::vector<float> slaney_filterbank(int nf, int n_mels, int sr) { return mel_filterbank(nf, n_mels, sr / 2.0, hz_to_mel_slaney, mel_to_hz_slaney, true); }
+
+// One mel front-end: its tables t (window, twiddles, filterbank(n_fft / 2 + 1, n_mels, sr)), rebuilt when (n_fft, n_mels, sr) changes,
+// then mel_frame_kernel over T frames at hop, the wave reflect-padded by `pad`
+static int mel_frames(MelTables& t, std::vector<float> (*filterbank)(int, int, int), int batch, int n_samples, const float* wave_dev, float* mel_dev,
+                      int n_fft, int hop, int n_mels, int sr, int pad, int T, float mag_eps, const char* name, hipStream_t st) {
+    if (t.n_fft != n_fft || t.n_mels != n_mels || t.sr != sr) {
+        dev_free(t.window); dev_free(t.twiddle); dev_free(t.fb);
+        t = MelTables();
+        if (make_fft_tables(&t.window, &t.twiddle, n_fft)) return -4;
+        const std::vector<float> fb = filterbank(n_fft / 2 + 1, n_mels, sr);
+        if (upload_f32(&t.fb, fb.data(), fb.size())) return -4;
+        t.n_fft = n_fft; t.n_mels = n_mels; t.sr = sr;
+    }
+    prof_begin(PROF_OTHER, st);
+    hipLaunchKernelGGL(mel_frame_kernel, dim3(T, batch), dim3(256), 0, st, wave_dev, n_samples, T, hop, n_mels, t.window, t.twiddle, t.fb, mel_dev, pad, mag_eps);
+    prof_end(PROF_OTHER, st);
+    CKL(name);
+    return 0;
+}
 
 int f5hip_mel_spectrogram(int32_t batch, int32_t n_samples, const float* wave_dev, float* mel_dev, int32_t n_fft, int32_t hop_length,
                           int32_t n_mels, int32_t sample_rate, void* stream) {
     if (batch <= 0 || n_samples <= n_fft / 2 || !wave_dev || !mel_dev) return fail(-1, "mel_spectrogram: bad argument");
     if (n_fft != 1024 || n_mels > 256) return fail(-1, "mel_spectrogram: only n_fft = 1024, n_mels <= 256");
-    hipStream_t st = (hipStream_t)stream;
-    if (g_mel.n_fft != n_fft || g_mel.n_mels != n_mels || g_mel.sr != sample_rate) {
-        dev_free(g_mel.window); dev_free(g_mel.twiddle); dev_free(g_mel.fb);
-        g_mel = MelTables();
-        if (make_fft_tables(&g_mel.window, &g_mel.twiddle, n_fft)) return -4;
-        // torchaudio.functional.melscale_fbanks(n_freqs = 513, f_min = 0, f_max = sr/2, n_mels, sr, norm=None, "htk")
-        const int nf = n_fft / 2 + 1;
-        const double fmax = sample_rate / 2;
-        std::vector<float> fb((size_t)nf * n_mels, 0.0f);
-        std::vector<double> fpts(n_mels + 2);
-        const double m0 = hz_to_mel_htk(0.0), m1 = hz_to_mel_htk(fmax);
-        for (int i = 0; i < n_mels + 2; i++) fpts[i] = mel_to_hz_htk(m0 + (m1 - m0) * (double)i / (double)(n_mels + 1));
-        for (int k = 0; k < nf; k++) {
-            const double f = fmax * (double)k / (double)(nf - 1);
-            for (int j = 0; j < n_mels; j++) {
-                const double down = (f - fpts[j]) / (fpts[j + 1] - fpts[j]);
-                const double up = (fpts[j + 2] - f) / (fpts[j + 2] - fpts[j + 1]);
-                const double val = std::max(0.0, std::min(down, up));
-                fb[(size_t)k * n_mels + j] = (float)val;
-            }
-        }
-        if (upload_f32(&g_mel.fb, fb.data(), fb.size())) return -4;
-        g_mel.n_fft = n_fft; g_mel.n_mels = n_mels; g_mel.sr = sample_rate;
-    }
-    const int T = 1 + n_samples / hop_length;
-    prof_begin(PROF_OTHER, st);
-    hipLaunchKernelGGL(mel_frame_kernel, dim3(T, batch), dim3(256), 0, st, wave_dev, n_samples, T, hop_length, n_mels, g_mel.window,
-                       g_mel.twiddle, g_mel.fb, mel_dev, n_fft / 2, 0.0f);
-    prof_end(PROF_OTHER, st);
-    CKL("mel_frame");
-    return 0;
+    return mel_frames(g_mel, htk_filterbank, batch, n_samples, wave_dev, mel_dev, n_fft, hop_length, n_mels, sample_rate, n_fft / 2,
+                      1 + n_samples / hop_length, 0.0f, "mel_frame", (hipStream_t)stream);
 }
 
 // ---- BigVGAN-style mel (F/model/modules.py:30-72): librosa Slaney filterbank, center=False after a reflect pad of (n_fft - hop) / 2
-static MelTables g_mel_bv;
-
 int f5hip_mel_spectrogram_bigvgan(int32_t batch, int32_t n_samples, const float* wave_dev, float* mel_dev, int32_t n_fft, int32_t hop_length,
                                   int32_t n_mels, int32_t sample_rate, void* stream) {
     if (batch <= 0 || n_samples < n_fft || !wave_dev || !mel_dev) return fail(-1, "mel_spectrogram_bigvgan: bad argument");
     if (n_fft != 1024 || n_mels > 256) return fail(-1, "mel_spectrogram_bigvgan: only n_fft = 1024, n_mels <= 256");
-    hipStream_t st = (hipStream_t)stream;
-    if (g_mel_bv.n_fft != n_fft || g_mel_bv.n_mels != n_mels || g_mel_bv.sr != sample_rate) {
-        dev_free(g_mel_bv.window); dev_free(g_mel_bv.twiddle); dev_free(g_mel_bv.fb);
-        g_mel_bv = MelTables();
-        if (make_fft_tables(&g_mel_bv.window, &g_mel_bv.twiddle, n_fft)) return -4;
-        // librosa.filters.mel(sr, n_fft, n_mels, fmin=0, fmax=sr/2, htk=False, norm="slaney")
-        const int nf = n_fft / 2 + 1;
-        const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
-        auto hz_to_mel = [&](double f) { return f >= min_log_hz ? min_log_mel + log(f / min_log_hz) / logstep : f / f_sp; };
-        auto mel_to_hz = [&](double m) { return m >= min_log_mel ? min_log_hz * exp(logstep * (m - min_log_mel)) : f_sp * m; };
-        const double fmax = sample_rate / 2.0, m0 = hz_to_mel(0.0), m1 = hz_to_mel(fmax);
-        std::vector<double> mf(n_mels + 2);
-        for (int i = 0; i < n_mels + 2; i++) mf[i] = mel_to_hz(m0 + (m1 - m0) * (double)i / (double)(n_mels + 1));
-        std::vector<float> fb((size_t)nf * n_mels, 0.0f);
-        for (int k = 0; k < nf; k++) {
-            const double f = fmax * (double)k / (double)(nf - 1);
-            for (int j = 0; j < n_mels; j++) {
-                const double lower = (f - mf[j]) / (mf[j + 1] - mf[j]), upper = (mf[j + 2] - f) / (mf[j + 2] - mf[j + 1]);
-                const double w = std::max(0.0, std::min(lower, upper)) * (2.0 / (mf[j + 2] - mf[j]));
-                fb[(size_t)k * n_mels + j] = (float)w;
-            }
-        }
-        if (upload_f32(&g_mel_bv.fb, fb.data(), fb.size())) return -4;
-        g_mel_bv.n_fft = n_fft; g_mel_bv.n_mels = n_mels; g_mel_bv.sr = sample_rate;
-    }
     const int pad = (n_fft - hop_length) / 2;
-    const int T = (n_samples + 2 * pad - n_fft) / hop_length + 1;
-    prof_begin(PROF_OTHER, st);
-    hipLaunchKernelGGL(mel_frame_kernel, dim3(T, batch), dim3(256), 0, st, wave_dev, n_samples, T, hop_length, n_mels, g_mel_bv.window,
-                       g_mel_bv.twiddle, g_mel_bv.fb, mel_dev, pad, 1e-9f);
-    prof_end(PROF_OTHER, st);
-    CKL("mel_frame (bigvgan)");
-    return 0;
+    return mel_frames(g_mel_bv, slaney_filterbank, batch, n_samples, wave_dev, mel_dev, n_fft, hop_length, n_mels, sample_rate, pad,
+                      (n_samples + 2 * pad - n_fft) / hop_length + 1, 1e-9f, "mel_frame (bigvgan)", (hipStream_t)stream);
 }
