@@ -199,6 +199,12 @@ int f5hip_vocos_finalize(f5hip_vocos* v);
  * wave_dev fp32 [batch][hop_length * (frames - 1)]. */
 int f5hip_vocos_decode(f5hip_vocos* v, int32_t batch, int32_t frames, const float* mel_dev, float* wave_dev,
                        void* stream);
+/* vocoder.decode(mel) (F/infer/utils_infer.py:472) over n mels of their own lengths in ONE call: frames host int32 [n], each >= 2;
+ * mel_dev fp32 [n][in_channels][T_max] (T_max = max frames[i]; item i valid for t < frames[i], the rest is not read) ->
+ * wave_dev fp32 packed, item i at offset hop_length * sum_{j<i} (frames[j] - 1), hop_length * (frames[i] - 1) samples long.
+ * Item i's wave equals f5hip_vocos_decode of that item alone, bit for bit. */
+int f5hip_vocos_decode_ragged(f5hip_vocos* v, int32_t n, const int32_t* frames, const float* mel_dev, float* wave_dev,
+                              void* stream);
 
 /* ---------------------------------------------------------------- BigVGAN vocoder --------------------- */
 

@@ -4,8 +4,10 @@
 // built by build.py into csrc/libf5hip_torch.so next to libf5hip.so, loaded with torch.ops.load_library (tts_indic_server_f5_amd/torch_ops.py).
 //   torch.ops.f5hip.cfm_sample(handle, dur, kv_len?, cond, cond_mask, text, y0, t_grid, cfg_strength) -> Tensor   F/model/cfm.py:160-204
 //   torch.ops.f5hip.vocos_decode(handle, mel) -> Tensor                                                          F/infer/utils_infer.py:472
+//   torch.ops.f5hip.vocos_decode_ragged(handle, mel, frames, channels, hop_length) -> Tensor (packed)                F/infer/utils_infer.py:472
 //   torch.ops.f5hip.bigvgan_forward(handle, mel, total_upsample) -> Tensor                                       F/infer/utils_infer.py:474
 #include <ATen/ATen.h>
+#include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
@@ -48,6 +50,25 @@ at::Tensor vocos_decode(int64_t handle, const at::Tensor& mel, int64_t hop_lengt
     return wave;
 }
 
+// mel [n, channels, T_max] fp32 device, frames [n] int32 host (item i valid for t < frames[i], each >= 2) -> packed wave
+// [hop_length * sum(frames[i] - 1)], item i at hop_length * sum_{j<i} (frames[j] - 1)
+at::Tensor vocos_decode_ragged(int64_t handle, const at::Tensor& mel, const at::Tensor& frames, int64_t channels, int64_t hop_length) {
+    check_dev_f32(mel, "mel"); check_host(frames, at::kInt, "frames");
+    TORCH_CHECK(mel.dim() == 3 && mel.size(1) == channels, "f5hip::vocos_decode_ragged: mel [n, ", channels, ", T_max]");
+    TORCH_CHECK(frames.dim() == 1 && frames.numel() == mel.size(0) && frames.numel() > 0, "f5hip::vocos_decode_ragged: frames.numel() == mel.size(0)");
+    const int32_t* f = frames.data_ptr<int32_t>();
+    int64_t total = 0;
+    for (int64_t i = 0; i < frames.numel(); i++) {
+        TORCH_CHECK(f[i] >= 2 && f[i] <= mel.size(2), "f5hip::vocos_decode_ragged: frames[", i, "] = ", f[i], " outside [2, mel.size(2) = ", mel.size(2), "]");
+        total += hop_length * (f[i] - 1);
+    }
+    const c10::DeviceGuard guard(mel.device());   // allocation and stream on the mel's device
+    at::Tensor wave = at::empty({total}, mel.options());
+    const int rc = f5hip_vocos_decode_ragged((f5hip_vocos*)handle, (int32_t)frames.numel(), f, mel.data_ptr<float>(), wave.data_ptr<float>(), stream_of(mel));
+    TORCH_CHECK(rc == 0, "f5hip_vocos_decode_ragged: ", f5hip_last_error());
+    return wave;
+}
+
 at::Tensor bigvgan_forward(int64_t handle, const at::Tensor& mel, int64_t total_upsample) {
     check_dev_f32(mel, "mel");
     TORCH_CHECK(mel.dim() == 3, "f5hip::bigvgan_forward: mel [b, 100, T]");
@@ -62,5 +83,6 @@ at::Tensor bigvgan_forward(int64_t handle, const at::Tensor& mel, int64_t total_
 TORCH_LIBRARY(f5hip, m) {
     m.def("cfm_sample(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor t_grid, float cfg_strength) -> Tensor", &cfm_sample);
     m.def("vocos_decode(int handle, Tensor mel, int hop_length) -> Tensor", &vocos_decode);
+    m.def("vocos_decode_ragged(int handle, Tensor mel, Tensor frames, int channels, int hop_length) -> Tensor", &vocos_decode_ragged);
     m.def("bigvgan_forward(int handle, Tensor mel, int total_upsample) -> Tensor", &bigvgan_forward);
 }

@@ -2,7 +2,7 @@
 // mel front-end, on the same GEMM / LayerNorm kernels as the DiT plus LDS radix-2 FFT kernels for
 // iSTFT / STFT.  Included at the end of f5hip.hip (same translation unit).
 //
-// decode(mel[B,100,T]):
+// decode(mel[B,100,T]), or a ragged batch of items with their own T (decode_ragged: one packed row space):
 //   x = Conv1d(100->512,k7,p3)(mel) -> LN -> 8 x [dwconv k7 -> LN -> 512->1536 -> GELU(erf) -> 1536->512 -> gamma* -> +res]
 //   -> LN -> Linear(512->1026) -> (mag = min(exp(.),1e2), phase) -> irfft(1024) * hann -> overlap-add / envelope
 #pragma once
@@ -28,6 +28,7 @@ struct f5hip_vocos {
     float *x = nullptr, *y = nullptr, *fw = nullptr;
     Plane2 melp, tn, hid;
     int* meta = nullptr;
+    size_t cap_meta = 0;   // ints in meta
 };
 
 // ---------------------------------------------------------------------------------------- FFT in LDS
@@ -86,23 +87,30 @@ __global__ __launch_bounds__(256) void istft_frame_kernel(const float* y, int ld
     for (int n = tid; n < 1024; n += 256) fw[(size_t)row * 1024 + n] = s[n].x * (1.0f / 1024.0f) * window[n];
 }
 
-// overlap-add + window-envelope normalisation + centre trim (torch.istft, center=True): out[b][hop*(T-1)]
-__global__ __launch_bounds__(256) void istft_ola_kernel(const float* fw, const int* seq_row0, int T, int hop, const float* window,
-                                                        float* out) {
-    const int b = blockIdx.y;
-    const int L = hop * (T - 1);
-    const int sidx = blockIdx.x * 256 + threadIdx.x;
-    if (sidx >= L) return;
+// overlap-add + window-envelope normalisation + centre trim (torch.istft, center=True), per item of a packed batch: item b has T_b = item_T[b]
+// frames starting at row seq_row0[b] and owns out[item_out0[b] .. item_out0[b + 1]) = hop * (T_b - 1) samples.  One thread per output
+// sample over the packed output; the item is found by bisection of item_out0 [n + 1].
+__global__ __launch_bounds__(256) void istft_ola_kernel(const float* fw, const int* seq_row0, const int* item_T, const int* item_out0, int n,
+                                                        int hop, const float* window, float* out) {
+    const int gidx = blockIdx.x * 256 + threadIdx.x;
+    if (gidx >= item_out0[n]) return;
+    int lo = 0, hi = n - 1;                        // last item whose output starts at or before gidx
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (item_out0[mid] <= gidx) lo = mid; else hi = mid - 1;
+    }
+    const int b = lo, T = item_T[b];
+    const int sidx = gidx - item_out0[b];
     const int p = sidx + 512;
     int t_hi = p / hop; if (t_hi > T - 1) t_hi = T - 1;
     int t_lo = (p - 1023 + hop - 1) / hop; if (t_lo < 0) t_lo = 0;
     float val = 0.0f, env = 0.0f;
     for (int t = t_lo; t <= t_hi; t++) {
-        const int n = p - t * hop;
-        val += fw[(size_t)(seq_row0[b] + t) * 1024 + n];
-        env += window[n] * window[n];
+        const int n_ = p - t * hop;
+        val += fw[(size_t)(seq_row0[b] + t) * 1024 + n_];
+        env += window[n_] * window[n_];
     }
-    out[(size_t)b * L + sidx] = val / env;
+    out[gidx] = val / env;
 }
 
 // STFT magnitude -> HTK mel filterbank -> log(clamp(., 1e-5)); one block per (frame, batch)
@@ -217,33 +225,50 @@ int f5hip_vocos_finalize(f5hip_vocos* v) {
     return 0;
 }
 
-int f5hip_vocos_decode(f5hip_vocos* v, int32_t batch, int32_t frames, const float* mel_dev, float* wave_dev, void* stream) {
-    if (!v || !v->finalized) return fail(-1, "vocoder not finalized");
-    if (batch <= 0 || frames < 2 || !mel_dev || !wave_dev) return fail(-1, "vocos_decode: bad argument");
-    hipStream_t st = (hipStream_t)stream;
+// n items, item i with frames[i] frames at mel_dev + i * C * t_stride (channel stride t_stride); every item gets its own 128-row padded slab,
+// so the embed conv and the depthwise convs see zeros at their item's bounds (row_start / row_end) and every kernel works row by row.
+// Output packed: item i at wave_dev + hop * sum_{j<i} (frames[j] - 1).
+static int vocos_decode_items(f5hip_vocos* v, int n, const int32_t* frames, int t_stride, const float* mel_dev, float* wave_dev, hipStream_t st) {
     const f5hip_vocos_config& c = v->cfg;
-    const int D = c.dim, I = c.intermediate_dim, T = frames, Tp = ceil_to(T, 128), M = batch * Tp, LDY = 1152;
+    const int D = c.dim, I = c.intermediate_dim, LDY = 1152;
+    long long m_ll = 0, l_ll = 0;
+    for (int b = 0; b < n; b++) {
+        if (frames[b] < 2 || frames[b] > t_stride) return fail(-1, "vocos_decode: item %d has %d frames (need 2 .. %d)", b, frames[b], t_stride);
+        m_ll += ceil_to(frames[b], 128);
+        l_ll += (long long)c.hop_length * (frames[b] - 1);
+    }
+    if (m_ll > (1LL << 24) || l_ll > 2147483647LL) return fail(-1, "vocos_decode: batch too large (%lld rows)", m_ll);
+    const int M = (int)m_ll;
+    const size_t meta_n = (size_t)M * 4 + (size_t)n * 3 + 1;
     if (M > v->cap_rows) {
-        dev_free(v->meta);
         if (alloc_workspace(&v->ws, "vocos workspace", [&](Arena& a) {
                 v->x = a.f32((size_t)M * D); v->y = a.f32((size_t)M * LDY); v->fw = a.f32((size_t)M * 1024);
                 v->melp = a.plane2((size_t)M * 128 + 1024); v->tn = a.plane2((size_t)M * D); v->hid = a.plane2((size_t)M * I);
-            })) { v->meta = nullptr; v->cap_rows = 0; return -5; }
-        if (hipMalloc((void**)&v->meta, sizeof(int) * ((size_t)M * 4 + batch)) != hipSuccess) { v->meta = nullptr; return fail(-5, "hipMalloc vocos meta"); }
+            })) { v->cap_rows = 0; return -5; }
         v->cap_rows = M;
     }
-    std::vector<int> h((size_t)M * 4 + batch, 0);
-    int* row_seq = &h[0]; int* row_pos = row_seq + M; int* row_start = row_pos + M; int* row_end = row_start + M; int* seq_row0 = row_end + M;
+    if (meta_n > v->cap_meta) {
+        dev_free(v->meta);
+        if (hipMalloc((void**)&v->meta, sizeof(int) * meta_n) != hipSuccess) { v->meta = nullptr; v->cap_meta = 0; return fail(-5, "hipMalloc vocos meta"); }
+        v->cap_meta = meta_n;
+    }
+    std::vector<int> h(meta_n, 0);
+    int* row_seq = &h[0]; int* row_pos = row_seq + M; int* row_start = row_pos + M; int* row_end = row_start + M;
+    int* seq_row0 = row_end + M; int* item_T = seq_row0 + n; int* item_out0 = item_T + n;
     for (int r = 0; r < M; r++) row_seq[r] = -1;
-    for (int b = 0; b < batch; b++) {
-        seq_row0[b] = b * Tp;
-        for (int t = 0; t < T; t++) { const int r = b * Tp + t; row_seq[r] = b; row_pos[r] = t; row_start[r] = b * Tp; row_end[r] = b * Tp + T; }
+    for (int b = 0, r0 = 0; b < n; b++) {
+        const int T = frames[b];
+        seq_row0[b] = r0; item_T[b] = T;
+        item_out0[b + 1] = item_out0[b] + c.hop_length * (T - 1);
+        for (int t = 0; t < T; t++) { const int r = r0 + t; row_seq[r] = b; row_pos[r] = t; row_start[r] = r0; row_end[r] = r0 + T; }
+        r0 += ceil_to(T, 128);
     }
     if (upload_sync(st, v->meta, h) != hipSuccess) return fail(-6, "vocos metadata upload");
-    const int *d_row_seq = v->meta, *d_row_pos = v->meta + M, *d_row_start = v->meta + 2 * M, *d_row_end = v->meta + 3 * M, *d_seq_row0 = v->meta + 4 * M;
+    const int *d_row_seq = v->meta, *d_row_pos = v->meta + M, *d_row_start = v->meta + 2 * M, *d_row_end = v->meta + 3 * M;
+    const int *d_seq_row0 = v->meta + 4 * M, *d_item_T = d_seq_row0 + n, *d_item_out0 = d_item_T + n;
 
     prof_begin(PROF_VOCOS, st);
-    hipLaunchKernelGGL(mel_to_rows_kernel, dim3(M), dim3(128), 0, st, mel_dev, c.in_channels, T, d_row_seq, d_row_pos, M, v->melp.hi, v->melp.lo);
+    hipLaunchKernelGGL(mel_to_rows_kernel, dim3(M), dim3(128), 0, st, mel_dev, c.in_channels, t_stride, d_row_seq, d_row_pos, M, v->melp.hi, v->melp.lo);
     CKL("mel_to_rows");
     // embed conv -> x (fp32), then LayerNorm in place
     GemmArgs e = gemm_base(v->melp, 128, v->embed, M);
@@ -274,11 +299,27 @@ int f5hip_vocos_decode(f5hip_vocos* v, int32_t batch, int32_t frames, const floa
     CK(run_gemm_n(v->nsplit, M, hd, v->head, EPI_GENERIC, false, 128, st));
     hipLaunchKernelGGL(istft_frame_kernel, dim3(M), dim3(256), 0, st, v->y, LDY, d_row_seq, M, v->window, v->twiddle, v->fw);
     CKL("istft_frame");
-    const int L = c.hop_length * (T - 1);
-    hipLaunchKernelGGL(istft_ola_kernel, dim3((L + 255) / 256, batch), dim3(256), 0, st, v->fw, d_seq_row0, T, c.hop_length, v->window, wave_dev);
+    const int L = (int)l_ll;
+    hipLaunchKernelGGL(istft_ola_kernel, dim3((L + 255) / 256), dim3(256), 0, st, v->fw, d_seq_row0, d_item_T, d_item_out0, n, c.hop_length,
+                       v->window, wave_dev);
     CKL("istft_ola");
     prof_end(PROF_VOCOS, st);
     return 0;
+}
+
+int f5hip_vocos_decode(f5hip_vocos* v, int32_t batch, int32_t frames, const float* mel_dev, float* wave_dev, void* stream) {
+    if (!v || !v->finalized) return fail(-1, "vocoder not finalized");
+    if (batch <= 0 || frames < 2 || !mel_dev || !wave_dev) return fail(-1, "vocos_decode: bad argument");
+    const std::vector<int32_t> f(batch, frames);   // uniform items: output item b at hop * b * (frames - 1), i.e. [batch][hop * (frames - 1)]
+    return vocos_decode_items(v, batch, f.data(), frames, mel_dev, wave_dev, (hipStream_t)stream);
+}
+
+int f5hip_vocos_decode_ragged(f5hip_vocos* v, int32_t n, const int32_t* frames, const float* mel_dev, float* wave_dev, void* stream) {
+    if (!v || !v->finalized) return fail(-1, "vocoder not finalized");
+    if (n <= 0 || !frames || !mel_dev || !wave_dev) return fail(-1, "vocos_decode_ragged: bad argument");
+    int t_max = 0;
+    for (int b = 0; b < n; b++) t_max = std::max(t_max, (int)frames[b]);
+    return vocos_decode_items(v, n, frames, t_max, mel_dev, wave_dev, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------- mel front-end

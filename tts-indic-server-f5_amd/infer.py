@@ -236,12 +236,48 @@ def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_ty
                   fix_duration=fix_duration, device=None):
     """F/infer/utils_infer.py:357-400."""
     audio, sr = ref_audio if isinstance(ref_audio, tuple) else load_wav(ref_audio)
-    max_chars = int(len(ref_text.encode("utf-8")) / (audio.shape[-1] / sr) * (25 - audio.shape[-1] / sr))
-    gen_text_batches = chunk_text(gen_text, max_chars=max_chars)
+    gen_text_batches = request_chunks(ref_text, audio.shape[-1] / sr, gen_text)
     return infer_batch_process((audio, sr), ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type=mel_spec_type,
                                progress=progress, target_rms=target_rms, cross_fade_duration=cross_fade_duration,
                                nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
                                speed=speed, fix_duration=fix_duration, device=device)
+
+
+def request_chunks(ref_text, ref_seconds, gen_text):
+    """The text chunks of one request (F/infer/utils_infer.py:379-381): a UTF-8 byte budget proportional to the reference's
+    bytes per second over what is left of 25 s, then `chunk_text`.  `ref_seconds` is the reference clip's length before resampling."""
+    max_chars = int(len(ref_text.encode("utf-8")) / ref_seconds * (25 - ref_seconds))
+    return chunk_text(gen_text, max_chars=max_chars)
+
+
+def infer_process_stream(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print,
+                         progress=None, target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step,
+                         cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, speed=speed,
+                         fix_duration=fix_duration, device=None):
+    """`infer_process` as a generator of float32 pieces at 24 kHz whose concatenation is `infer_process`'s wave (as float32).
+
+    The text is chunked exactly as `infer_process` does; chunk 0 is sampled and vocoded alone and its stable samples are yielded, then
+    the remaining chunks are sampled in ONE `sample_units` call and the rest follows (`StreamJoiner`: the last fade length of what has
+    been joined is held back until the next chunk's cross-fade is known).  Every chunk is an independent unit with batch-1 semantics and
+    noise is drawn unit by unit in order, so with the model handle in shape-invariant attention mode and the same generator state before
+    both calls (`torch.manual_seed`), the pieces equal `infer_process`'s wave to the last bit."""
+    audio, sr = ref_audio if isinstance(ref_audio, tuple) else load_wav(ref_audio)
+    chunks = request_chunks(ref_text, audio.shape[-1] / sr, gen_text)
+    voice, units = _plan_request((audio, sr), ref_text, chunks, target_rms, speed, fix_duration, device, text_to_tokens)
+    knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
+    joiner = StreamJoiner(cross_fade_duration)
+    for part in (units[:1], units[1:]):
+        if not part:
+            continue
+        mels = _sample(model_obj, voice, part, knobs)
+        (waves, _), = _chunk_waves([(mels, voice.ref_frames, voice.rms)], vocoder, mel_spec_type, target_rms)
+        for w in waves:
+            piece = joiner.push(w)
+            if len(piece):
+                yield piece.astype(np.float32)
+    piece = joiner.flush()
+    if len(piece):
+        yield piece.astype(np.float32)
 
 
 def _prepare_reference(audio, sr, rms_floor, device):
@@ -291,6 +327,40 @@ def cross_fade_concat(waves, fade_seconds, sample_rate=target_sample_rate):
     return out
 
 
+class StreamJoiner:
+    """`cross_fade_concat` one chunk wave at a time.  A later cross-fade rewrites at most the last int(fade_seconds * sample_rate)
+    samples of what has been joined so far (n = min(fade, len(out), len(next))), so `push(wave)` returns the samples that can no longer
+    change and holds back that many; `flush()` returns the rest.  The concatenation of every returned piece is `np.array_equal` to
+    `cross_fade_concat(waves, fade_seconds)`, dtype included (float64 from the first cross-fade on, like the reference's)."""
+
+    def __init__(self, fade_seconds, sample_rate=target_sample_rate):
+        self.fade = int(fade_seconds * sample_rate) if fade_seconds > 0 else 0
+        self.total = 0          # samples of the joined wave so far, emitted and held
+        self.held = None        # its last min(fade, total) samples
+
+    def push(self, wave):
+        nxt = np.asarray(wave)
+        if self.held is None:
+            local = nxt
+        else:
+            out = self.held
+            n = min(self.fade, len(out), len(nxt))
+            if n <= 0:
+                local = np.concatenate([out, nxt])
+            else:
+                ramp = np.linspace(0, 1, n)
+                local = np.concatenate([out[:-n], out[-n:] * ramp[::-1] + nxt[:n] * ramp, nxt[n:]])
+            self.total -= len(out)
+        self.total += len(local)
+        keep = min(self.fade, self.total)          # <= len(local): see the class note
+        self.held = local[len(local) - keep:]
+        return local[:len(local) - keep]
+
+    def flush(self):
+        held, self.held = self.held, None
+        return held if held is not None else np.zeros(0, dtype=np.float32)
+
+
 class PreparedVoice:
     """The per-voice part of `infer_process` done once: the reference wave after mono mix / rms gain / resampling
     (F/infer/utils_infer.py:423-433), its measured rms, its duration in seconds before resampling (the `max_chars` rule, :379) and --
@@ -322,18 +392,42 @@ def _plan_request(ref_audio, ref_text, gen_text_batches, target_rms, speed, fix_
     return voice, plan_units(ref_text, gen_text_batches, voice.ref_frames, speed, fix_duration, tokenizer)
 
 
-def _vocode_and_join(mels, ref_frames, rms, vocoder, mel_spec_type, target_rms, cross_fade_duration):
-    """Tail of infer_batch_process (F/infer/utils_infer.py:468-524): strip the reference frames, vocode, restore the rms, cross-fade."""
+def _sample(model_obj, voice, units, knobs):
+    """The mels [frames_i, mel] (reference frames included) of one request's units: one `sample_units` call when the model object offers
+    it, else the reference's batch-1 `.sample()` per unit."""
+    if hasattr(model_obj, "sample_units"):
+        return model_obj.sample_units(voice.cond(model_obj), units, **knobs)
+    return [model_obj.sample(cond=voice.audio, text=[tokens], duration=frames, **knobs)[0][0] for tokens, frames in units]
+
+
+def _chunk_waves(groups, vocoder, mel_spec_type, target_rms):
+    """Vocoder part of infer_batch_process's tail (F/infer/utils_infer.py:468-481) for the chunks of several requests: `groups` =
+    [(mels, ref_frames, rms)] -> per group ([wave_i], [spec_i]) as numpy, the reference frames stripped and the rms restored per chunk.
+    Vocos objects that offer `decode_ragged` vocode every chunk of every group in ONE call (each item equals its own `decode`, bit for
+    bit); any other vocoder (BigVGAN) is called chunk by chunk at batch 1 like the reference."""
     if mel_spec_type not in ("vocos", "bigvgan"):
         raise ValueError(mel_spec_type)
-    waves, specs = [], []
-    for mel in mels:
-        spec = mel.to(torch.float32)[ref_frames:, :].t()[None]                     # [1, mel, T] (:468-470)
-        wave = vocoder.decode(spec) if mel_spec_type == "vocos" else vocoder(spec)
-        if rms < target_rms:
-            wave = wave * rms / target_rms
-        waves.append(wave.squeeze().cpu().numpy())
-        specs.append(spec[0].cpu().numpy())
+    specs = [[mel.to(torch.float32)[ref_frames:, :].t()[None] for mel in mels] for mels, ref_frames, _ in groups]   # [1, mel, T] (:468-470)
+    flat = [spec for g in specs for spec in g]
+    if mel_spec_type == "vocos" and hasattr(vocoder, "decode_ragged") and flat:
+        raw = [w[None] for w in vocoder.decode_ragged([spec[0] for spec in flat])]
+    else:
+        raw = [vocoder.decode(spec) if mel_spec_type == "vocos" else vocoder(spec) for spec in flat]
+    out, k = [], 0
+    for (_, _, rms), g in zip(groups, specs):
+        waves = []
+        for wave in raw[k:k + len(g)]:
+            if rms < target_rms:
+                wave = wave * rms / target_rms
+            waves.append(wave.squeeze().cpu().numpy())
+        out.append((waves, [spec[0].cpu().numpy() for spec in g]))
+        k += len(g)
+    return out
+
+
+def _vocode_and_join(mels, ref_frames, rms, vocoder, mel_spec_type, target_rms, cross_fade_duration):
+    """Tail of infer_batch_process (F/infer/utils_infer.py:468-524): strip the reference frames, vocode, restore the rms, cross-fade."""
+    (waves, specs), = _chunk_waves([(mels, ref_frames, rms)], vocoder, mel_spec_type, target_rms)
     return cross_fade_concat(waves, cross_fade_duration), target_sample_rate, np.concatenate(specs, axis=1)
 
 
@@ -348,16 +442,14 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
     per chunk); any other object with the reference's `.sample()` is driven chunk by chunk like the reference does."""
     voice, units = _plan_request(ref_audio, ref_text, gen_text_batches, target_rms, speed, fix_duration, device, tokenizer)
     knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
-    if hasattr(model_obj, "sample_units"):
-        mels = model_obj.sample_units(voice.cond(model_obj), units, **knobs)        # list of [frames_i, mel] incl. the reference frames
-    else:
-        mels = [model_obj.sample(cond=voice.audio, text=[tokens], duration=frames, **knobs)[0][0] for tokens, frames in units]
+    mels = _sample(model_obj, voice, units, knobs)        # list of [frames_i, mel] incl. the reference frames
     return _vocode_and_join(mels, voice.ref_frames, voice.rms, vocoder, mel_spec_type, target_rms, cross_fade_duration)
 
 
 def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, target_rms=target_rms,
                    cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
-                   sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, tokenizer=text_to_tokens):
+                   sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, tokenizer=text_to_tokens,
+                   join=True):
     """Several `infer_process()` calls as ONE sampler batch: `requests` = [(ref_audio, ref_text, gen_text)], each with its own
     reference voice (a path, a (wave, sr) pair or a `PreparedVoice`); returns one (wave, sample_rate, spectrogram) triple per request, each what `infer_process` returns for
     that request alone: units keep the reference's batch-1 semantics (no padding against each other, no shared mask), and noise is drawn
@@ -366,12 +458,19 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     mode a lone unit and the same unit inside a batch may take different attention kernels (same values to the last bits per launch, but
     in the mixed GEMM mode last-bit differences grow to that mode's rounding-noise floor, 4.4e-4 rms after two Euler steps:
     `profiles/r03_attn_mode_tapdiff.txt`; either result is within the 1e-3 bound of the reference).  This is what the serving queue (`serve.MicroBatcher`) and the
-    multi-voice front-end hand to the GPU: the chunks of all waiting requests are packed back to back in one library call."""
+    multi-voice front-end hand to the GPU: the chunks of all waiting requests are packed back to back in one library call, and with a
+    Vocos object that offers `decode_ragged` they are vocoded in one call too.
+
+    `gen_text` is a string, chunked like `infer_process` does, or a list of chunk texts used as they are (a streamed request's first
+    chunk and its remaining chunks ride in different batches: `infer_process_stream`, `serve.TTSManager.synthesize_stream`).  Unseeded,
+    such a request draws its remaining chunks' noise one batch later than it would unstreamed, so under concurrency its result is a
+    different valid sample; alone, or with the generator reseeded, it is the same.  `join=False` returns ([wave_i], sample_rate,
+    [spec_i]) per request -- the per-chunk waves before the cross-fade -- instead of the joined triple."""
     plans, flat_units, flat_cond, flat_audio = [], [], [], []
     for ref_audio, ref_text, gen_text in requests:
         voice = ref_audio if isinstance(ref_audio, PreparedVoice) else PreparedVoice(ref_audio, target_rms, device)
-        max_chars = int(len(ref_text.encode("utf-8")) / voice.seconds * (25 - voice.seconds))                 # utils_infer.py:379
-        voice, units = _plan_request(voice, ref_text, chunk_text(gen_text, max_chars=max_chars), target_rms, speed, fix_duration, device, tokenizer)
+        chunks = list(gen_text) if isinstance(gen_text, (list, tuple)) else request_chunks(ref_text, voice.seconds, gen_text)
+        voice, units = _plan_request(voice, ref_text, chunks, target_rms, speed, fix_duration, device, tokenizer)
         plans.append((voice, len(units)))
         flat_units += units
         flat_cond += [voice.cond(model_obj)] * len(units)
@@ -381,10 +480,16 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
         mels = model_obj.sample_units(flat_cond, flat_units, **knobs)
     else:
         mels = [model_obj.sample(cond=a, text=[tokens], duration=frames, **knobs)[0][0] for a, (tokens, frames) in zip(flat_audio, flat_units)]
-    out, k = [], 0
+    groups, k = [], 0
     for voice, n in plans:
-        out.append(_vocode_and_join(mels[k:k + n], voice.ref_frames, voice.rms, vocoder, mel_spec_type, target_rms, cross_fade_duration))
+        groups.append((mels[k:k + n], voice.ref_frames, voice.rms))
         k += n
+    out = []
+    for waves, specs in _chunk_waves(groups, vocoder, mel_spec_type, target_rms):
+        if join:
+            out.append((cross_fade_concat(waves, cross_fade_duration), target_sample_rate, np.concatenate(specs, axis=1)))
+        else:
+            out.append((waves, target_sample_rate, specs))
     return out
 
 

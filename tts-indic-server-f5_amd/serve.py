@@ -26,7 +26,9 @@ Differences, explicit:
 import base64
 import binascii
 import io
+import logging
 import queue
+import struct
 import threading
 import time
 import wave as _wave
@@ -38,6 +40,7 @@ import numpy as np
 
 from . import infer
 
+log = logging.getLogger(__name__)
 
 @dataclass
 class Voice:
@@ -67,7 +70,10 @@ class MicroBatcher:
     flight at a time -- the library allows one call per handle -- and the next one forms while it runs, so under load the batch size
     grows by itself.  A failing batch is retried request by request so one bad request cannot fail its neighbours -- unless the error
     says the backend itself is gone (`no_retry`, e.g. a rank of a sharded job failed): then the whole batch fails at once.
-    `close()` resolves every request that is still queued with RuntimeError("MicroBatcher is closed"); nothing can be enqueued behind it."""
+    `close()` resolves every request that is still queued with RuntimeError("MicroBatcher is closed"); nothing can be enqueued behind it.
+    A request whose future was cancelled while it waited (a streaming client that went away) is dropped when its batch forms, before
+    `run_batch`; `submit(request, on_start=fn)` calls `fn()` on the worker thread once the request's batch has formed and before it runs,
+    so anything submitted from `fn` rides in a later batch (a stream's remaining chunks behind its first chunk)."""
 
     def __init__(self, run_batch: Callable[[list], list], max_requests: int = 16, max_wait_ms: float = 5.0):
         self.run_batch, self.max_requests, self.max_wait = run_batch, int(max_requests), max_wait_ms / 1e3
@@ -78,12 +84,12 @@ class MicroBatcher:
         self._thread = threading.Thread(target=self._loop, name="f5hip-microbatcher", daemon=True)
         self._thread.start()
 
-    def submit(self, request) -> Future:
+    def submit(self, request, on_start: Callable[[], None] | None = None) -> Future:
         f: Future = Future()
         with self._gate:
             if self._closed:
                 raise RuntimeError("MicroBatcher is closed")
-            self._q.put((request, f))
+            self._q.put((request, f, on_start) if on_start is not None else (request, f))
         return f
 
     def close(self, timeout: float = 30.0):
@@ -101,7 +107,7 @@ class MicroBatcher:
                 item = self._q.get_nowait()
             except queue.Empty:
                 return
-            if item is not None:
+            if item is not None and item[1].set_running_or_notify_cancel():
                 item[1].set_exception(RuntimeError("MicroBatcher is closed"))
 
     def _collect(self):
@@ -126,24 +132,55 @@ class MicroBatcher:
             batch = self._collect()
             if batch is None:       # the shutdown mark: every request submitted before close() has been served
                 break
+            batch = [item for item in batch if item[1].set_running_or_notify_cancel()]   # cancelled while queued: never run
+            if not batch:
+                continue
             self.batch_sizes.append(len(batch))
+            for item in batch:
+                if len(item) > 2:
+                    try:
+                        item[2]()
+                    except Exception:   # noqa: BLE001 -- a hook must not stop the worker; its owner sees the missing follow-up
+                        pass
             try:
-                results = self.run_batch([r for r, _ in batch])
+                results = self.run_batch([item[0] for item in batch])
                 if len(results) != len(batch):
                     raise RuntimeError(f"run_batch returned {len(results)} results for {len(batch)} requests")
-                for (_, f), res in zip(batch, results):
-                    f.set_result(res)
+                for item, res in zip(batch, results):
+                    item[1].set_result(res)
             except Exception as e:   # noqa: BLE001 -- isolate the failing request
                 if len(batch) == 1 or getattr(e, "no_retry", False):
-                    for _, f in batch:
-                        f.set_exception(e)
+                    for item in batch:
+                        item[1].set_exception(e)
                     continue
-                for r, f in batch:
+                for item in batch:
                     try:
-                        f.set_result(self.run_batch([r])[0])
+                        item[1].set_result(self.run_batch([item[0]])[0])
                     except Exception as e1:   # noqa: BLE001
-                        f.set_exception(e1)
+                        item[1].set_exception(e1)
         self._fail_pending()
+
+
+class SynthesisStream:
+    """Iterator of float32 pieces (`TTSManager.synthesize_stream`).  `close()` may be called from any thread, also while another thread
+    waits inside `next()`: it cancels the request's remaining chunks if their batch has not started, and the waiting `next()` then ends
+    with `concurrent.futures.CancelledError`."""
+
+    def __init__(self, gen, cancel):
+        self._gen, self._cancel = gen, cancel
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return next(self._gen)
+
+    def close(self):
+        self._cancel()
+        try:
+            self._gen.close()
+        except ValueError:          # the generator is running on another thread: it stops at its wait for the cancelled tail
+            pass
 
 
 class TTSManager:
@@ -188,9 +225,13 @@ class TTSManager:
         return self
 
     def _run_batch(self, requests):
+        """One `infer_requests` call.  A request whose text is a string gets its joined wave (float32); one whose text is a list of chunk
+        texts (a streamed request's head or tail) gets its per-chunk waves, for the caller's `infer.StreamJoiner`."""
         with self._device_lock:
-            res = infer.infer_requests(requests, self.model_obj, self.vocoder, mel_spec_type=self.mel_spec_type, **self.opts)
-        return [np.asarray(w, dtype=np.float32) for w, _, _ in res]
+            res = infer.infer_requests(requests, self.model_obj, self.vocoder, mel_spec_type=self.mel_spec_type, join=False, **self.opts)
+        fade = infer.cross_fade_duration
+        return [waves if isinstance(r[2], (list, tuple)) else np.asarray(infer.cross_fade_concat(waves, fade), dtype=np.float32)
+                for r, (waves, _, _) in zip(requests, res)]
 
     def close(self):
         """Unload: stop the batcher (requests already queued are served, later ones refused) and drop the model objects."""
@@ -223,6 +264,72 @@ class TTSManager:
             raise ValueError("TTS model not loaded")
         return self.model(text, ref_audio_path=ref_audio_path, ref_text=ref_text)
 
+    def synthesize_stream(self, text, ref_audio_path, ref_text):
+        """`synthesize` as an iterator of float32 pieces (24 kHz) whose concatenation is `synthesize`'s wave given the same noise (see
+        `infer.infer_process_stream`).  The request's first chunk is synthesized on its own and its stable samples come out as soon as it is
+        done; the remaining chunks follow as a second request.  With a micro-batcher the first chunk rides in the next batch and the
+        remaining chunks are queued once that batch has started, so they ride in a later one; without, the two run one after the other,
+        each under the device lock (released in between).  Closing the iterator early (client disconnect) cancels the remaining chunks
+        if their batch has not started.  Errors about the model or the voice are raised here, not on the first `next()`."""
+        if not self.model:
+            raise ValueError("TTS model not loaded")
+        voice, ref_text_n = self._voice(ref_audio_path, ref_text)
+        chunks = infer.request_chunks(ref_text_n, voice.seconds, text)
+        return self._stream(voice, ref_text_n, chunks[:1], chunks[1:])
+
+    def _stream(self, voice, ref_text, head, tail):
+        lock, state = threading.Lock(), {"closed": False, "tail": None, "error": None}
+        started = threading.Event()
+
+        def submit_tail():                        # on the batcher's thread, once the head's batch has formed
+            with lock:
+                try:
+                    if not state["closed"]:
+                        state["tail"] = self.batcher.submit((voice, ref_text, tail))
+                except Exception as e:    # noqa: BLE001 -- e.g. the batcher is closing: reported to the consumer
+                    state["error"] = e
+            started.set()
+
+        def cancel():
+            with lock:
+                state["closed"] = True
+                if state["tail"] is not None:
+                    state["tail"].cancel()        # a no-op once its batch has started or it is done
+
+        def pieces():
+            joiner = infer.StreamJoiner(infer.cross_fade_duration)
+            try:
+                if self.batcher is not None:
+                    head_f = self.batcher.submit((voice, ref_text, head), on_start=submit_tail if tail else None)
+                    head_waves = head_f.result(timeout=self.request_timeout_s)
+                else:
+                    head_waves = self._run_batch([(voice, ref_text, head)])[0]
+                for w in head_waves:
+                    piece = joiner.push(w)
+                    if len(piece):
+                        yield np.asarray(piece, dtype=np.float32)
+                if tail:
+                    if self.batcher is not None:
+                        started.wait(timeout=self.request_timeout_s)
+                        if state["error"] is not None:
+                            raise state["error"]
+                        if state["tail"] is None:     # closed before the tail was queued
+                            return
+                        tail_waves = state["tail"].result(timeout=self.request_timeout_s)
+                    else:
+                        tail_waves = self._run_batch([(voice, ref_text, tail)])[0]
+                    for w in tail_waves:
+                        piece = joiner.push(w)
+                        if len(piece):
+                            yield np.asarray(piece, dtype=np.float32)
+                piece = joiner.flush()
+                if len(piece):
+                    yield np.asarray(piece, dtype=np.float32)
+            finally:                              # normal end, error, or the consumer closed the stream
+                cancel()
+
+        return SynthesisStream(pieces(), cancel)
+
     def edit(self, audio, target_text, parts_to_edit, fix_duration=None):
         """Speech editing (`infer.speech_edit`, F/infer/speech_edit.py): regenerate `parts_to_edit` of the recording `audio` (a path, WAV
         bytes or a (tensor, sr) pair) so that it speaks `target_text`, with this manager's sampler settings.  The host preparation runs
@@ -252,6 +359,19 @@ def wav_bytes(audio: np.ndarray, sample_rate: int = infer.target_sample_rate) ->
     return buf
 
 
+def pcm16(audio: np.ndarray) -> bytes:
+    """Little-endian int16 PCM bytes of float samples, by `wav_bytes`'s rule: rint(x * 32768), clipped."""
+    a = np.clip(np.rint(np.asarray(audio).astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
+    return a.astype("<i2").tobytes()
+
+
+def wav_stream_header(sample_rate: int = infer.target_sample_rate) -> bytes:
+    """44-byte header of a 16-bit mono PCM WAV of unknown length: RIFF and `data` sizes are 0xFFFFFFFF (the usual streaming-WAV
+    convention; players read to the end of the stream)."""
+    return (b"RIFF" + struct.pack("<I", 0xFFFFFFFF) + b"WAVE" + b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, sample_rate, sample_rate * 2, 2, 16)
+            + b"data" + struct.pack("<I", 0xFFFFFFFF))
+
+
 class HTTPError(Exception):
     """Carries (status_code, detail) out of `synthesize_speech`; the route turns it into fastapi.HTTPException."""
 
@@ -275,21 +395,38 @@ def synthesize_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: st
     return wav_bytes(audio)
 
 
+def stream_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None):
+    """`synthesize_speech`'s checks, then `TTSManager.synthesize_stream`: an iterator of float32 pieces."""
+    voice = registry.get(ref_audio_name)
+    if voice is not None and not ref_text:
+        ref_text = voice.ref_text
+    if voice is None:
+        raise HTTPError(400, "Invalid reference audio name.")
+    if not text.strip():
+        raise HTTPError(400, "Text to synthesize cannot be empty.")
+    if not ref_text or not ref_text.strip():
+        raise HTTPError(400, "Reference text cannot be empty.")
+    return tts_manager.synthesize_stream(text, ref_audio_path=voice.audio_path, ref_text=ref_text)
+
+
 def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     """FastAPI app with the reference's `/v1/audio/speech` route (`S/routes/speech.py:19-41`) and `/v1/audio/edit` (speech editing:
     JSON body {"audio": base64 WAV, "text": the full new transcript, "parts_to_edit": [[start_s, end_s], ...], "fix_duration": [...] | null}
-    -> the edited recording as WAV)."""
+    -> the edited recording as WAV).  Both speech routes take `"stream": true`: the WAV then arrives chunk by chunk (`_run_stream`), its
+    PCM samples identical to the unstreamed response's."""
     from fastapi import APIRouter, FastAPI, HTTPException
     from pydantic import BaseModel
     from starlette.responses import StreamingResponse
 
     class KannadaSynthesizeRequest(BaseModel):       # S/utils/tts_utils.py:27-28
         text: str
+        stream: bool = False
 
     class SynthesizeRequest(BaseModel):              # S/utils/tts_utils.py:22-25
         text: str
         ref_audio_name: str
         ref_text: str | None = None
+        stream: bool = False
 
     class EditRequest(BaseModel):                    # F/infer/speech_edit.py's inputs; JSON (base64 WAV), not multipart
         audio: str
@@ -309,6 +446,39 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         except HTTPError as e:
             raise HTTPException(status_code=e.status_code, detail=e.detail)
         return StreamingResponse(buf, media_type="audio/wav", headers={"Content-Disposition": f"attachment; filename={filename}"})
+
+    def _run_stream(text, name, ref_text, filename):
+        """stream=true: the same checks as `_run`, then the first piece is synthesized BEFORE the response exists, so a bad request, an
+        unloaded model or a failing first chunk still comes back as a status code.  The body is a streaming WAV (`wav_stream_header`)
+        followed by int16 PCM pieces; a failure after the first bytes can only end the body early, and is logged."""
+        if not tts_manager.model:
+            raise HTTPException(status_code=503, detail="TTS model not loaded")
+        if not text.strip():
+            raise HTTPException(status_code=400, detail="Text to synthesize cannot be empty.")
+        try:
+            pieces = stream_speech(tts_manager, registry, text=text, ref_audio_name=name, ref_text=ref_text)
+            first = next(pieces, None)
+        except HTTPError as e:
+            raise HTTPException(status_code=e.status_code, detail=e.detail)
+        return StreamingResponse(_pcm_body(first, pieces), media_type="audio/wav",
+                                 headers={"Content-Disposition": f"attachment; filename={filename}"})
+
+    async def _pcm_body(first, pieces):
+        # the synthesis runs in the thread pool, one piece at a time; leaving early (client gone, error) closes the generator,
+        # which cancels the request's remaining chunks if their batch has not started
+        try:
+            yield wav_stream_header()
+            if first is not None:
+                yield pcm16(first)
+            while True:
+                piece = await run_in_threadpool(next, pieces, None)
+                if piece is None:
+                    break
+                yield pcm16(piece)
+        except Exception:   # noqa: BLE001 -- the status line is gone: end the body early
+            log.exception("streamed synthesis failed after the first bytes; the response body ends early")
+        finally:
+            pieces.close()
 
     def _run_edit(req):
         if not tts_manager.model:
@@ -336,11 +506,13 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
 
     @router.post("/audio/speech", response_class=StreamingResponse)
     async def synthesize_kannada(request: KannadaSynthesizeRequest):
-        return await run_in_threadpool(_run, request.text, registry.default_voice, None, "synthesized_kannada_speech.wav")
+        return await run_in_threadpool(_run_stream if request.stream else _run, request.text, registry.default_voice, None,
+                                       "synthesized_kannada_speech.wav")
 
     @router.post("/audio/speech/voice", response_class=StreamingResponse)
     async def synthesize_with_voice(request: SynthesizeRequest):     # the generic form the reference's helper already supports
-        return await run_in_threadpool(_run, request.text, request.ref_audio_name, request.ref_text, "synthesized_speech.wav")
+        return await run_in_threadpool(_run_stream if request.stream else _run, request.text, request.ref_audio_name, request.ref_text,
+                                       "synthesized_speech.wav")
 
     @router.post("/audio/edit", response_class=StreamingResponse)
     async def edit_speech(request: EditRequest):                    # speech editing (F/infer/speech_edit.py) over the same manager
@@ -369,7 +541,9 @@ class ShardedSampler:
     Failure: a rank whose local `sample_units` raises still joins the gather with a failure header; rank 0 then raises
     `ShardedJobError` after the collective has completed on every rank, and refuses later jobs (`failed`).
     Noise: every rank draws the noise of ITS units from its own generator (like the reference's per-call `torch.randn`, unseeded in
-    `infer_batch_process`), so an unseeded result is not reproducible across world sizes; pass `seed=` in the knobs for that."""
+    `infer_batch_process`), so an unseeded result is not reproducible across world sizes; pass `seed=` in the knobs for that.
+    Streaming (`TTSManager.synthesize_stream`) needs nothing here: a stream's first chunk and its remaining chunks arrive as units of
+    ordinary `sample_units` batches."""
 
     def __init__(self, local_model, device=None):
         import torch

@@ -1,6 +1,6 @@
 """Vocos vocoder object: stands where the reference passes `vocoder` (F/infer/utils_infer.py:92-115,472).
 
-`decode(mel[b, 100, T]) -> wave[b, 256 (T - 1)]` runs in libf5hip; state_dict keys are vocos 0.1.0's
+`decode(mel[b, 100, T]) -> wave[b, 256 (T - 1)]` and `decode_ragged([mel_i [100, T_i]]) -> [wave_i]` run in libf5hip; state_dict keys are vocos 0.1.0's
 (`backbone.embed.weight`, `backbone.convnext.{i}.*`, `backbone.final_layer_norm.*`, `head.out.*`)."""
 from __future__ import annotations
 
@@ -54,6 +54,31 @@ class F5HipVocos:
         _lib.check(self._lib.f5hip_vocos_decode(self._h, b, t, C.c_void_p(mel.data_ptr()), C.c_void_p(wave.data_ptr()),
                                                 _lib.current_stream_ptr()), "f5hip_vocos_decode")
         return wave
+
+    @torch.no_grad()
+    def decode_ragged(self, mels) -> list:
+        """`decode` of several mels of their own lengths in ONE library call (f5hip_vocos_decode_ragged): mels = [mel_i [C, T_i]] ->
+        [wave_i [hop (T_i - 1)]], each equal to `decode(mel_i[None])[0]` bit for bit (one padded row slab per item, row-wise kernels)."""
+        frames = [int(m.shape[-1]) for m in mels]
+        if not frames:
+            return []
+        c = int(mels[0].shape[0])
+        if any(m.dim() != 2 or m.shape[0] != c for m in mels):
+            raise _lib.F5HipError("decode_ragged: every mel must be [C, T] with the same C")
+        mel = torch.zeros(len(mels), c, max(frames), device=self.device, dtype=torch.float32)
+        for i, m in enumerate(mels):
+            mel[i, :, :frames[i]] = m
+        f = torch.tensor(frames, dtype=torch.int32)
+        if torch_ops.load():
+            try:
+                wave = torch_ops.ops().vocos_decode_ragged(int(self._h), mel, f, c, self.hop_length)
+            except RuntimeError as e:   # c10::Error from the operator's checks or the library
+                raise _lib.F5HipError(str(e)) from e
+        else:
+            wave = torch.empty(self.hop_length * sum(t - 1 for t in frames), device=self.device, dtype=torch.float32)
+            _lib.check(self._lib.f5hip_vocos_decode_ragged(self._h, len(frames), C.c_void_p(f.data_ptr()), C.c_void_p(mel.data_ptr()),
+                                                           C.c_void_p(wave.data_ptr()), _lib.current_stream_ptr()), "f5hip_vocos_decode_ragged")
+        return list(wave.split([self.hop_length * (t - 1) for t in frames]))
 
 
 class F5HipBigVGAN:
