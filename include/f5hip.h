@@ -93,6 +93,15 @@ int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, con
                             const uint8_t* cond_mask, const int32_t* text, int32_t nt_max, const float* y0_dev,
                             const float* t_grid, int32_t steps, float cfg_strength, float* out_dev, void* stream);
 
+/* f5hip_cfm_sample_masked with one CFG strength per unit: cfg_strength is a host array of n_utt floats.  A unit whose strength is
+ * < 1e-5 gets no unconditional sequence at all (the reference's early-out, cfm.py:162-175, per unit: its rows are neither laid out nor
+ * run through the backbone); every other unit gets its unconditional sequence and v = p + (p - p_uncond) * cfg_strength[u].  The
+ * strengths travel with the per-row metadata (no host sync).  A unit's result is what f5hip_cfm_sample_masked gives it with its own
+ * strength as the scalar, with every ODE method and backbone. */
+int f5hip_cfm_sample_units(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev,
+                           const uint8_t* cond_mask, const int32_t* text, int32_t nt_max, const float* y0_dev,
+                           const float* t_grid, int32_t steps, const float* cfg_strength, float* out_dev, void* stream);
+
 /* The fixed-grid solver both sample calls use: replaces CFM(odeint_kwargs=dict(method=...)) (F/model/cfm.py:37-41,72,200; set from
  * load_model(ode_method=...), F/infer/utils_infer.py:251).  0 = "euler" (default): x += dt * v(t_i, x).  1 = "midpoint":
  * x += dt * v(t_i + dt / 2, x + dt / 2 * v(t_i, x)), two backbone evaluations per step, at most 64 steps per call.  2 = "rk4": torchdiffeq's

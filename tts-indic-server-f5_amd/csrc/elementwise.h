@@ -123,8 +123,11 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* x, int ldx
 // Also refreshes the split-bf16 copy of x that feeds the next step's input projection for both branches.
 // xout = xbase + dt * v: xout == xbase for an Euler step; the midpoint rule writes its half step to a scratch state and takes the full
 // step from the untouched xbase.
+// kFrameCfg: the strength of frame u is cfg_frame[u] (f5hip_cfm_sample_units: one strength per unit, spread over its frames) instead of
+// the scalar `cfg`; the arithmetic is the same, so the scalar instantiation is the kernel the single-strength entry points always ran.
+template <bool kFrameCfg>
 __global__ __launch_bounds__(128) void cfg_euler_kernel(float* xout /*[U][mel]*/, const float* xbase, int mel, int U, const float* pred,
-                                                        int ldp, const int* urow_c, const int* urow_u, float cfg,
+                                                        int ldp, const int* urow_c, const int* urow_u, float cfg, const float* cfg_frame,
                                                         float dt, __bf16* xs_hi, __bf16* xs_lo, int ldx) {
     const int u = blockIdx.x;
     if (u >= U) return;
@@ -133,7 +136,7 @@ __global__ __launch_bounds__(128) void cfg_euler_kernel(float* xout /*[U][mel]*/
     const int rc = urow_c[u], ru = urow_u[u];
     const float pc = pred[(size_t)rc * ldp + c];
     float v = pc;
-    if (ru >= 0) v = pc + (pc - pred[(size_t)ru * ldp + c]) * cfg;
+    if (ru >= 0) v = pc + (pc - pred[(size_t)ru * ldp + c]) * (kFrameCfg ? cfg_frame[u] : cfg);
     const float xn = xbase[(size_t)u * mel + c] + dt * v;
     xout[(size_t)u * mel + c] = xn;
     __bf16 hi, lo;
@@ -153,10 +156,11 @@ __global__ __launch_bounds__(128) void cfg_euler_kernel(float* xout /*[U][mel]*/
 //   s = 3: k3 = v(t0 + 2 dt/3, ..)    next input y0 + dt * (k1 - k2 + k3)
 //   s = 4: k4 = v(t0 + dt, ..)        y1 = y0 + (k1 + 3 (k2 + k3) + k4) * dt / 8
 // v as in cfg_euler_kernel.  Stages 1-3 keep k_s in their [U][mel] buffer and write the next stage's input only to the split-bf16 copy
-// of x (both branches); xstate holds y0 until stage 4 writes y1 there.
+// of x (both branches); xstate holds y0 until stage 4 writes y1 there.  kFrameCfg as in cfg_euler_kernel.
+template <bool kFrameCfg>
 __global__ __launch_bounds__(128) void cfg_rk4_stage_kernel(float* xstate /*[U][mel]*/, int mel, int U, const float* pred, int ldp,
-                                                            const int* urow_c, const int* urow_u, float cfg, float dt, int stage,
-                                                            float* k1, float* k2, float* k3, __bf16* xs_hi, __bf16* xs_lo, int ldx) {
+                                                            const int* urow_c, const int* urow_u, float cfg, const float* cfg_frame, float dt,
+                                                            int stage, float* k1, float* k2, float* k3, __bf16* xs_hi, __bf16* xs_lo, int ldx) {
     const int u = blockIdx.x;
     if (u >= U) return;
     const int c = threadIdx.x;
@@ -164,7 +168,7 @@ __global__ __launch_bounds__(128) void cfg_rk4_stage_kernel(float* xstate /*[U][
     const int rc = urow_c[u], ru = urow_u[u];
     const float pc = pred[(size_t)rc * ldp + c];
     float v = pc;
-    if (ru >= 0) v = pc + (pc - pred[(size_t)ru * ldp + c]) * cfg;
+    if (ru >= 0) v = pc + (pc - pred[(size_t)ru * ldp + c]) * (kFrameCfg ? cfg_frame[u] : cfg);
     const size_t i = (size_t)u * mel + c;
     const float y0 = xstate[i];
     float xn;

@@ -74,6 +74,7 @@ struct f5hip_dit {
     // per-call metadata (device pointers into `meta`)
     int *d_row_pos, *d_row_start, *d_row_end, *d_row_seq, *d_row_token, *d_row_frame, *d_row_condframe, *d_row_keep,
         *d_seq_row0, *d_seq_len, *d_seq_kvlen, *d_urow_c, *d_urow_u, *d_frame_is_cond;
+    float* d_frame_cfg = nullptr;   // f5hip_cfm_sample_units: CFG strength per frame (its unit's), in `meta` behind the other arrays; else null
     int M = 0, n_seq = 0, n_frames = 0, max_len = 0;
     int Mc = 0, Rtot = 0;   // MMDiT: text-stream rows and all rows (= row pitch of the V^T buffer); Rtot == M otherwise
     int *d_j_row0 = nullptr, *d_j_len = nullptr, *d_j_kvlen = nullptr, *d_j_kv_row0 = nullptr, *d_j_kv2_row0 = nullptr, *d_j_kv2_len = nullptr;   // MMDiT joint attention: 2 n_seq pseudo-sequences
@@ -354,7 +355,7 @@ static int ensure_workspace(f5hip_dit* m, int rows_pad, int frames, int n_seq) {
             m->rk_k2 = a.f32(U * c.mel_dim); m->rk_k3 = a.f32(U * c.mel_dim);
         })) { m->cap_rows = 0; return -5; }
     m->cap_rows = (int)R; m->cap_frames = (int)U; m->cap_seq = (int)S;
-    const int need = (int)(R * 8 + S * 15 + U * 3 + 64);
+    const int need = (int)(R * 8 + S * 15 + U * 4 + 64);
     if (need > m->meta_cap) {
         dev_free(m->meta);
         if (hipMalloc((void**)&m->meta, sizeof(int) * need) != hipSuccess) { m->meta = nullptr; m->meta_cap = 0; return fail(-5, "hipMalloc meta"); }
@@ -368,8 +369,9 @@ struct SeqDesc { int len, kvlen, frame0 /* first frame in caller's packed arrays
 
 // Lays the sequences out (each padded to a multiple of 128 rows), builds the per-row metadata and uploads it.
 // UNetT: row 0 of every sequence is the time token (F/model/backbones/unett.py:184); frames follow at rows 1..len.
+// frame_cfg (n_frames floats, or null): per-frame CFG strengths, uploaded with the rest (m->d_frame_cfg).
 static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n_frames, const int32_t* text, int nt_max,
-                           const uint8_t* frame_is_cond, hipStream_t st) {
+                           const uint8_t* frame_is_cond, hipStream_t st, const float* frame_cfg = nullptr) {
     const int extra = m->arch == 1 ? 1 : 0;
     const bool mm = m->arch == 2;
     int rows = 0, rows_x = 0;
@@ -381,7 +383,10 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
     }
     if (ensure_workspace(m, rows, n_frames, (int)seqs.size())) return -5;
     const int R = rows, S = (int)seqs.size(), U = n_frames;
-    std::vector<int> hbuf((size_t)R * 8 + S * 3 + U * 3 + (mm ? 12 * S : 0), 0);
+    const size_t n_int = (size_t)R * 8 + S * 3 + U * 3 + (mm ? 12 * S : 0);
+    std::vector<int> hbuf(n_int + (frame_cfg ? U : 0), 0);
+    static_assert(sizeof(float) == sizeof(int), "frame_cfg rides in the int arena");
+    if (frame_cfg) memcpy(&hbuf[n_int], frame_cfg, sizeof(float) * U);
     int* row_pos = &hbuf[0]; int* row_start = row_pos + R; int* row_end = row_start + R; int* row_seq = row_end + R;
     int* row_token = row_seq + R; int* row_frame = row_token + R; int* row_condframe = row_frame + R; int* row_keep = row_condframe + R;
     int* seq_row0 = row_keep + R; int* seq_len = seq_row0 + S; int* seq_kvlen = seq_len + S;
@@ -448,6 +453,7 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
     m->d_urow_c = d; m->d_urow_u = d + U; m->d_frame_is_cond = d + 2 * U;
     d += 3 * U;
     m->d_j_row0 = d; m->d_j_len = d + 2 * S; m->d_j_kvlen = d + 4 * S; m->d_j_kv_row0 = d + 6 * S; m->d_j_kv2_row0 = d + 8 * S; m->d_j_kv2_len = d + 10 * S;
+    m->d_frame_cfg = frame_cfg ? reinterpret_cast<float*>(m->meta + n_int) : nullptr;
     // rotary factors per row of this layout (one load in the QKV epilogues instead of row_pos -> table)
     hipLaunchKernelGGL(rope_rows_kernel, dim3((R * 32 + 255) / 256), dim3(256), 0, st, m->d_row_pos, m->rope_cos, m->rope_sin, R, 4097, m->rope_row_cos, m->rope_row_sin);
     if (hipGetLastError() != hipSuccess) return fail(-7, "rope_rows_kernel launch");
@@ -971,16 +977,38 @@ int f5hip_dit_set_ode_method(f5hip_dit* m, int32_t method) {
     return 0;
 }
 
-int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
-                            const int32_t* text, int32_t nt_max, const float* y0_dev, const float* t_grid, int32_t steps,
-                            float cfg_strength, float* out_dev, void* stream) {
+// The CFG combine of one ODE stage: the scalar-strength kernel, or -- with a per-frame table (f5hip_cfm_sample_units) -- its per-frame twin.
+static void launch_cfg_euler(const f5hip_dit* m, int f0, hipStream_t st, float* xout, const float* xbase, float cfg, float dt) {
+    const int mel = m->cfg.mel_dim;
+    if (m->d_frame_cfg)
+        hipLaunchKernelGGL(cfg_euler_kernel<true>, dim3(f0), dim3(128), 0, st, xout, xbase, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
+                           0.0f, (const float*)m->d_frame_cfg, dt, m->xs.hi, m->xs.lo, 128);
+    else
+        hipLaunchKernelGGL(cfg_euler_kernel<false>, dim3(f0), dim3(128), 0, st, xout, xbase, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
+                           cfg, (const float*)nullptr, dt, m->xs.hi, m->xs.lo, 128);
+}
+
+static void launch_cfg_rk4(f5hip_dit* m, int f0, hipStream_t st, float cfg, float dt, int stage) {
+    const int mel = m->cfg.mel_dim;
+    if (m->d_frame_cfg)
+        hipLaunchKernelGGL(cfg_rk4_stage_kernel<true>, dim3(f0), dim3(128), 0, st, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
+                           0.0f, (const float*)m->d_frame_cfg, dt, stage, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128);
+    else
+        hipLaunchKernelGGL(cfg_rk4_stage_kernel<false>, dim3(f0), dim3(128), 0, st, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
+                           cfg, (const float*)nullptr, dt, stage, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128);
+}
+
+// f5hip_cfm_sample_masked (cfg_unit == null: one strength for the call) and f5hip_cfm_sample_units (cfg_unit: one strength per unit)
+static int cfm_sample_impl(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
+                           const int32_t* text, int32_t nt_max, const float* y0_dev, const float* t_grid, int32_t steps,
+                           float cfg_strength, const float* cfg_unit, float* out_dev, void* stream) {
     if (!m || !m->finalized) return fail(-1, "model not finalized");
     if (n_utt <= 0 || !dur || !cond_dev || !cond_mask || !text || !y0_dev || !t_grid || !out_dev || steps <= 0)
         return fail(-1, "cfm_sample: bad argument");
     ProfScope prof_scope(m->prof);
     hipStream_t st = (hipStream_t)stream;
-    const bool use_cfg = !(cfg_strength < 1e-5f);
     const int mel = m->cfg.mel_dim;
+    std::vector<float> frame_cfg;   // per-unit strengths spread over the unit's frames (cfg_unit only)
     std::vector<SeqDesc> seqs;
     int f0 = 0;
     m->h_seq_len.clear();
@@ -995,6 +1023,10 @@ int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, con
         seqs.push_back({dur[u], kv, f0, u, 0, 0, 0});
         seqs.back().c_len = std::max(c_len, 1);
         m->h_seq_len.push_back(dur[u]);
+        // the reference's early-out (cfm.py:162-175): below 1e-5 the unconditional branch is not evaluated at all -- per call, or per unit
+        const float cfg_u = cfg_unit ? cfg_unit[u] : cfg_strength;
+        const bool use_cfg = !(cfg_u < 1e-5f);
+        if (cfg_unit) frame_cfg.insert(frame_cfg.end(), dur[u], use_cfg ? cfg_u : 0.0f);
         if (use_cfg) {
             seqs.push_back({dur[u], kv, f0, u, 1, 1, 1});
             seqs.back().c_len = std::max(c_len, 1);
@@ -1002,7 +1034,7 @@ int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, con
         }
         f0 += dur[u];
     }
-    CK(setup_sequences(m, seqs, f0, text, nt_max, cond_mask, st));
+    CK(setup_sequences(m, seqs, f0, text, nt_max, cond_mask, st, cfg_unit ? frame_cfg.data() : nullptr));
     const int M = m->M;
     if (hipMemcpyAsync(m->xstate, y0_dev, sizeof(float) * (size_t)f0 * mel, hipMemcpyDeviceToDevice, st) != hipSuccess)
         return fail(-6, "y0 copy");
@@ -1014,8 +1046,7 @@ int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, con
         for (int i = 0; i < steps; i++) {
             CK(forward_step(m, i, -1, st));
             prof_begin(PROF_OTHER, st);
-            hipLaunchKernelGGL(cfg_euler_kernel, dim3(f0), dim3(128), 0, st, m->xstate, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                               cfg_strength, t_grid[i + 1] - t_grid[i], m->xs.hi, m->xs.lo, 128);
+            launch_cfg_euler(m, f0, st, m->xstate, m->xstate, cfg_strength, t_grid[i + 1] - t_grid[i]);
             prof_end(PROF_OTHER, st);
             CKL("cfg_euler");
         }
@@ -1033,14 +1064,12 @@ int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, con
             const float dt = t_grid[i + 1] - t_grid[i];
             CK(forward_step(m, 2 * i, -1, st));
             prof_begin(PROF_OTHER, st);
-            hipLaunchKernelGGL(cfg_euler_kernel, dim3(f0), dim3(128), 0, st, m->xmid, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                               cfg_strength, 0.5f * dt, m->xs.hi, m->xs.lo, 128);
+            launch_cfg_euler(m, f0, st, m->xmid, m->xstate, cfg_strength, 0.5f * dt);
             prof_end(PROF_OTHER, st);
             CKL("cfg_euler half");
             CK(forward_step(m, 2 * i + 1, -1, st));
             prof_begin(PROF_OTHER, st);
-            hipLaunchKernelGGL(cfg_euler_kernel, dim3(f0), dim3(128), 0, st, m->xstate, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                               cfg_strength, dt, m->xs.hi, m->xs.lo, 128);
+            launch_cfg_euler(m, f0, st, m->xstate, m->xstate, cfg_strength, dt);
             prof_end(PROF_OTHER, st);
             CKL("cfg_euler full");
         }
@@ -1065,8 +1094,7 @@ int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, con
             for (int s = 1; s <= 4; s++) {
                 CK(forward_step(m, 3 * i + s - 1, -1, st));
                 prof_begin(PROF_OTHER, st);
-                hipLaunchKernelGGL(cfg_rk4_stage_kernel, dim3(f0), dim3(128), 0, st, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                                   cfg_strength, dt, s, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128);
+                launch_cfg_rk4(m, f0, st, cfg_strength, dt, s);
                 prof_end(PROF_OTHER, st);
                 CKL("cfg_rk4_stage");
             }
@@ -1075,6 +1103,19 @@ int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, con
     hipLaunchKernelGGL(final_select_kernel, dim3(f0), dim3(128), 0, st, m->xstate, cond_dev, m->d_frame_is_cond, mel, f0, out_dev);
     CKL("final_select");
     return 0;
+}
+
+int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
+                            const int32_t* text, int32_t nt_max, const float* y0_dev, const float* t_grid, int32_t steps,
+                            float cfg_strength, float* out_dev, void* stream) {
+    return cfm_sample_impl(m, n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, t_grid, steps, cfg_strength, nullptr, out_dev, stream);
+}
+
+int f5hip_cfm_sample_units(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
+                           const int32_t* text, int32_t nt_max, const float* y0_dev, const float* t_grid, int32_t steps,
+                           const float* cfg_strength, float* out_dev, void* stream) {
+    if (!cfg_strength) return fail(-1, "cfm_sample_units: cfg_strength is null");
+    return cfm_sample_impl(m, n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, t_grid, steps, 0.0f, cfg_strength, out_dev, stream);
 }
 
 #include "vocos.h"

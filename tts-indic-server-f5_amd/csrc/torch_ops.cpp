@@ -3,6 +3,7 @@
 // c10::Error.  Handles are the opaque pointers the *_create functions of the ABI return, carried as int64.  Host C++ only (no kernels here):
 // built by build.py into csrc/libf5hip_torch.so next to libf5hip.so, loaded with torch.ops.load_library (tts_indic_server_f5_amd/torch_ops.py).
 //   torch.ops.f5hip.cfm_sample(handle, dur, kv_len?, cond, cond_mask, text, y0, t_grid, cfg_strength) -> Tensor   F/model/cfm.py:160-204
+//   torch.ops.f5hip.cfm_sample_units(handle, dur, kv_len?, cond, cond_mask, text, y0, t_grid, cfg_strength) -> Tensor  (one strength per unit)
 //   torch.ops.f5hip.vocos_decode(handle, mel) -> Tensor                                                          F/infer/utils_infer.py:472
 //   torch.ops.f5hip.vocos_decode_ragged(handle, mel, frames, channels, hop_length) -> Tensor (packed)                F/infer/utils_infer.py:472
 //   torch.ops.f5hip.bigvgan_forward(handle, mel, total_upsample) -> Tensor                                       F/infer/utils_infer.py:474
@@ -38,6 +39,28 @@ at::Tensor cfm_sample(int64_t handle, const at::Tensor& dur, const c10::optional
                                            cond.data_ptr<float>(), cond_mask.data_ptr<uint8_t>(), text.data_ptr<int32_t>(), (int32_t)text.size(1), y0.data_ptr<float>(),
                                            t_grid.data_ptr<float>(), (int32_t)t_grid.numel() - 1, (float)cfg_strength, out.data_ptr<float>(), stream_of(y0));
     TORCH_CHECK(rc == 0, "f5hip_cfm_sample: ", f5hip_last_error());
+    return out;
+}
+
+// cfm_sample with cfg_strength [b] fp32 host: one strength per unit (f5hip_cfm_sample_units; < 1e-5 drops that unit's unconditional rows).
+at::Tensor cfm_sample_units(int64_t handle, const at::Tensor& dur, const c10::optional<at::Tensor>& kv_len, const at::Tensor& cond, const at::Tensor& cond_mask,
+                            const at::Tensor& text, const at::Tensor& y0, const at::Tensor& t_grid, const at::Tensor& cfg_strength) {
+    check_host(dur, at::kInt, "dur"); check_host(cond_mask, at::kByte, "cond_mask"); check_host(text, at::kInt, "text"); check_host(t_grid, at::kFloat, "t_grid");
+    check_host(cfg_strength, at::kFloat, "cfg_strength");
+    check_dev_f32(cond, "cond"); check_dev_f32(y0, "y0");
+    TORCH_CHECK(text.dim() == 2 && text.size(0) == dur.numel() && t_grid.numel() >= 2 && cond.sizes() == y0.sizes(), "f5hip::cfm_sample_units: shapes");
+    TORCH_CHECK(cfg_strength.numel() == dur.numel(), "f5hip::cfm_sample_units: cfg_strength needs one value per unit (", cfg_strength.numel(), " for ", dur.numel(), ")");
+    if (kv_len.has_value()) {
+        check_host(*kv_len, at::kInt, "kv_len");
+        TORCH_CHECK(kv_len->numel() == dur.numel(), "f5hip::cfm_sample_units: kv_len needs one value per unit");
+    }
+    const int64_t rows = dur.sum().item<int64_t>();
+    TORCH_CHECK(cond.dim() == 2 && cond.size(0) == rows && cond_mask.numel() == rows, "f5hip::cfm_sample_units: cond / y0 / cond_mask need sum(dur) = ", rows, " rows");
+    at::Tensor out = at::empty_like(y0);
+    const int rc = f5hip_cfm_sample_units((f5hip_dit*)handle, (int32_t)dur.numel(), dur.data_ptr<int32_t>(), kv_len.has_value() ? kv_len->data_ptr<int32_t>() : nullptr,
+                                          cond.data_ptr<float>(), cond_mask.data_ptr<uint8_t>(), text.data_ptr<int32_t>(), (int32_t)text.size(1), y0.data_ptr<float>(),
+                                          t_grid.data_ptr<float>(), (int32_t)t_grid.numel() - 1, cfg_strength.data_ptr<float>(), out.data_ptr<float>(), stream_of(y0));
+    TORCH_CHECK(rc == 0, "f5hip_cfm_sample_units: ", f5hip_last_error());
     return out;
 }
 
@@ -82,6 +105,7 @@ at::Tensor bigvgan_forward(int64_t handle, const at::Tensor& mel, int64_t total_
 
 TORCH_LIBRARY(f5hip, m) {
     m.def("cfm_sample(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor t_grid, float cfg_strength) -> Tensor", &cfm_sample);
+    m.def("cfm_sample_units(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor t_grid, Tensor cfg_strength) -> Tensor", &cfm_sample_units);
     m.def("vocos_decode(int handle, Tensor mel, int hop_length) -> Tensor", &vocos_decode);
     m.def("vocos_decode_ragged(int handle, Tensor mel, Tensor frames, int channels, int hop_length) -> Tensor", &vocos_decode_ragged);
     m.def("bigvgan_forward(int handle, Tensor mel, int total_upsample) -> Tensor", &bigvgan_forward);

@@ -233,14 +233,15 @@ def load_wav(src):
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print,
                   progress=None, target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step,
                   cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, speed=speed,
-                  fix_duration=fix_duration, device=None):
-    """F/infer/utils_infer.py:357-400."""
+                  fix_duration=fix_duration, device=None, seed=None):
+    """F/infer/utils_infer.py:357-400.  `seed` (not in the reference's signature): the request's noise comes from its own CPU generator
+    (`request_generator`) instead of the global one."""
     audio, sr = ref_audio if isinstance(ref_audio, tuple) else load_wav(ref_audio)
     gen_text_batches = request_chunks(ref_text, audio.shape[-1] / sr, gen_text)
     return infer_batch_process((audio, sr), ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type=mel_spec_type,
                                progress=progress, target_rms=target_rms, cross_fade_duration=cross_fade_duration,
                                nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
-                               speed=speed, fix_duration=fix_duration, device=device)
+                               speed=speed, fix_duration=fix_duration, device=device, seed=seed)
 
 
 def request_chunks(ref_text, ref_seconds, gen_text):
@@ -253,23 +254,25 @@ def request_chunks(ref_text, ref_seconds, gen_text):
 def infer_process_stream(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print,
                          progress=None, target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step,
                          cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, speed=speed,
-                         fix_duration=fix_duration, device=None):
+                         fix_duration=fix_duration, device=None, seed=None):
     """`infer_process` as a generator of float32 pieces at 24 kHz whose concatenation is `infer_process`'s wave (as float32).
 
     The text is chunked exactly as `infer_process` does; chunk 0 is sampled and vocoded alone and its stable samples are yielded, then
     the remaining chunks are sampled in ONE `sample_units` call and the rest follows (`StreamJoiner`: the last fade length of what has
     been joined is held back until the next chunk's cross-fade is known).  Every chunk is an independent unit with batch-1 semantics and
     noise is drawn unit by unit in order, so with the model handle in shape-invariant attention mode and the same generator state before
-    both calls (`torch.manual_seed`), the pieces equal `infer_process`'s wave to the last bit."""
+    both calls (`torch.manual_seed`), the pieces equal `infer_process`'s wave to the last bit.  With `seed`, both calls draw from the
+    request's one generator (the remaining chunks after the first chunk's draws), so the pieces equal `infer_process(..., seed=seed)`."""
     audio, sr = ref_audio if isinstance(ref_audio, tuple) else load_wav(ref_audio)
     chunks = request_chunks(ref_text, audio.shape[-1] / sr, gen_text)
     voice, units = _plan_request((audio, sr), ref_text, chunks, target_rms, speed, fix_duration, device, text_to_tokens)
     knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
+    gen = request_generator(seed)
     joiner = StreamJoiner(cross_fade_duration)
     for part in (units[:1], units[1:]):
         if not part:
             continue
-        mels = _sample(model_obj, voice, part, knobs)
+        mels = _sample(model_obj, voice, part, knobs, gen)
         (waves, _), = _chunk_waves([(mels, voice.ref_frames, voice.rms)], vocoder, mel_spec_type, target_rms)
         for w in waves:
             piece = joiner.push(w)
@@ -392,11 +395,30 @@ def _plan_request(ref_audio, ref_text, gen_text_batches, target_rms, speed, fix_
     return voice, plan_units(ref_text, gen_text_batches, voice.ref_frames, speed, fix_duration, tokenizer)
 
 
-def _sample(model_obj, voice, units, knobs):
+def request_generator(seed):
+    """The CPU generator a request with `seed` draws its noise from: chunk k takes `randn(dur_k, mel)` after the draws of chunks 0..k-1, so
+    chunks get different noise and the global generator is not touched.  None without a seed."""
+    if seed is None:
+        return None
+    return torch.Generator().manual_seed(int(seed))
+
+
+def _seeded_kw(model_obj, gens):
+    """The `generators=` keyword of a `sample_units` call whose units carry generators (nothing when none does: unseeded calls are
+    today's calls).  Only model objects with `sample_units` take per-unit noise sources."""
+    if all(g is None for g in gens):
+        return {}
+    if not hasattr(model_obj, "sample_units"):
+        raise ValueError("a per-request seed needs a model object with sample_units (F5HipModel, ShardedSampler)")
+    return dict(generators=list(gens))
+
+
+def _sample(model_obj, voice, units, knobs, generator=None):
     """The mels [frames_i, mel] (reference frames included) of one request's units: one `sample_units` call when the model object offers
-    it, else the reference's batch-1 `.sample()` per unit."""
+    it, else the reference's batch-1 `.sample()` per unit.  `generator`: the request's own noise source (`request_generator`)."""
+    extra = _seeded_kw(model_obj, [generator] * len(units))
     if hasattr(model_obj, "sample_units"):
-        return model_obj.sample_units(voice.cond(model_obj), units, **knobs)
+        return model_obj.sample_units(voice.cond(model_obj), units, **knobs, **extra)
     return [model_obj.sample(cond=voice.audio, text=[tokens], duration=frames, **knobs)[0][0] for tokens, frames in units]
 
 
@@ -433,7 +455,7 @@ def _vocode_and_join(mels, ref_frames, rms, vocoder, mel_spec_type, target_rms, 
 
 def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type="vocos", progress=None,
                         target_rms=0.1, cross_fade_duration=0.15, nfe_step=32, cfg_strength=2.0, sway_sampling_coef=-1,
-                        speed=1, fix_duration=None, device=None, tokenizer=text_to_tokens):
+                        speed=1, fix_duration=None, device=None, tokenizer=text_to_tokens, seed=None):
     """F/infer/utils_infer.py:406-524, same signature and return triple.
 
     The reference loops over the chunks and calls `sample()` / the vocoder once per chunk with batch 1.  The chunks are independent
@@ -442,8 +464,12 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
     per chunk); any other object with the reference's `.sample()` is driven chunk by chunk like the reference does."""
     voice, units = _plan_request(ref_audio, ref_text, gen_text_batches, target_rms, speed, fix_duration, device, tokenizer)
     knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
-    mels = _sample(model_obj, voice, units, knobs)        # list of [frames_i, mel] incl. the reference frames
+    mels = _sample(model_obj, voice, units, knobs, request_generator(seed))   # list of [frames_i, mel] incl. the reference frames
     return _vocode_and_join(mels, voice.ref_frames, voice.rms, vocoder, mel_spec_type, target_rms, cross_fade_duration)
+
+
+# per-request options of `infer_requests` (the fourth element of a request) and of the serving routes
+REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed")
 
 
 def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, target_rms=target_rms,
@@ -465,21 +491,59 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     chunk and its remaining chunks ride in different batches: `infer_process_stream`, `serve.TTSManager.synthesize_stream`).  Unseeded,
     such a request draws its remaining chunks' noise one batch later than it would unstreamed, so under concurrency its result is a
     different valid sample; alone, or with the generator reseeded, it is the same.  `join=False` returns ([wave_i], sample_rate,
-    [spec_i]) per request -- the per-chunk waves before the cross-fade -- instead of the joined triple."""
-    plans, flat_units, flat_cond, flat_audio = [], [], [], []
-    for ref_audio, ref_text, gen_text in requests:
+    [spec_i]) per request -- the per-chunk waves before the cross-fade -- instead of the joined triple.
+
+    Per-request options: a request may carry a fourth element, a dict with any of `speed`, `nfe_step`, `cfg_strength`,
+    `sway_sampling_coef` and `seed` (`REQUEST_OPTIONS`); what it leaves out comes from this function's keyword arguments.  Requests that
+    share a time grid (`nfe_step`, `sway_sampling_coef`) are sampled in ONE `sample_units` call, each unit with its request's
+    `cfg_strength` (one float for the call when they all agree, as before; else one value per unit); each further grid is one more call
+    (the backbone's time modulation is per call), in order of first appearance, and all chunks are still vocoded together.  `speed` only
+    changes a request's planned frames.  With `seed`, the request's chunk k draws its noise from `request_generator(seed)` after chunks
+    0..k-1; a `generator` entry (a torch.Generator) continues that sequence instead -- what a streamed request's remaining chunks carry --
+    and is advanced only when this call succeeds.  A seeded request's result depends only on its own settings, not on its batch, with the
+    shape-invariant attention mode on one GPU (ranks > 0 of a `serve.ShardedSampler` do not switch to that mode yet); unseeded units draw
+    from the global generator in sampler-call order."""
+    defaults = dict(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None)
+    plans, calls = [], {}   # calls: (nfe_step, sway) -> [unit ids, ...] of one sampler call each
+    flat_units, flat_cond, flat_audio, flat_cfg, flat_gen, commits = [], [], [], [], [], []
+    for req in requests:
+        ref_audio, ref_text, gen_text = req[:3]
+        opts = dict(defaults, **(req[3] if len(req) > 3 and req[3] else {}))
+        unknown = set(opts) - set(REQUEST_OPTIONS) - {"generator"}
+        if unknown:
+            raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
         voice = ref_audio if isinstance(ref_audio, PreparedVoice) else PreparedVoice(ref_audio, target_rms, device)
         chunks = list(gen_text) if isinstance(gen_text, (list, tuple)) else request_chunks(ref_text, voice.seconds, gen_text)
-        voice, units = _plan_request(voice, ref_text, chunks, target_rms, speed, fix_duration, device, tokenizer)
+        voice, units = _plan_request(voice, ref_text, chunks, target_rms, opts["speed"], fix_duration, device, tokenizer)
+        gen = opts.get("generator")
+        if gen is not None:    # continue a sequence on a copy: the caller's generator moves only if the call succeeds
+            commits.append((gen, torch.Generator().set_state(gen.get_state())))
+            gen = commits[-1][1]
+        else:
+            gen = request_generator(opts["seed"])
+        key = (int(opts["nfe_step"]), opts["sway_sampling_coef"])
+        calls.setdefault(key, []).extend(range(len(flat_units), len(flat_units) + len(units)))
         plans.append((voice, len(units)))
         flat_units += units
         flat_cond += [voice.cond(model_obj)] * len(units)
         flat_audio += [voice.audio] * len(units)
-    knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
-    if hasattr(model_obj, "sample_units"):
-        mels = model_obj.sample_units(flat_cond, flat_units, **knobs)
-    else:
-        mels = [model_obj.sample(cond=a, text=[tokens], duration=frames, **knobs)[0][0] for a, (tokens, frames) in zip(flat_audio, flat_units)]
+        flat_cfg += [opts["cfg_strength"]] * len(units)
+        flat_gen += [gen] * len(units)
+    mels = [None] * len(flat_units)
+    for (steps, sway), ids in calls.items():
+        cfgs = [flat_cfg[i] for i in ids]
+        cfg = cfgs[0] if all(c == cfgs[0] for c in cfgs) else cfgs
+        knobs = dict(steps=steps, cfg_strength=cfg, sway_sampling_coef=sway)
+        extra = _seeded_kw(model_obj, [flat_gen[i] for i in ids])
+        if hasattr(model_obj, "sample_units"):
+            got = model_obj.sample_units([flat_cond[i] for i in ids], [flat_units[i] for i in ids], **knobs, **extra)
+        else:
+            got = [model_obj.sample(cond=flat_audio[i], text=[flat_units[i][0]], duration=flat_units[i][1], steps=steps,
+                                    cfg_strength=flat_cfg[i], sway_sampling_coef=sway)[0][0] for i in ids]
+        for i, mel in zip(ids, got):
+            mels[i] = mel
+    for gen, copy in commits:
+        gen.set_state(copy.get_state())
     groups, k = [], 0
     for voice, n in plans:
         groups.append((mels[k:k + n], voice.ref_frames, voice.rms))
@@ -665,7 +729,8 @@ def prepare_edit(audio, target_text, parts_to_edit, fix_duration=None, mel_spec_
 
 
 def speech_edit_batch(edits, model_obj, vocoder, mel_spec_type=mel_spec_type, target_rms=target_rms, nfe_step=nfe_step,
-                      cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None, device=None, tokenizer=text_to_tokens):
+                      cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None, device=None, tokenizer=text_to_tokens,
+                      generators=None):
     """Several speech edits in ONE sampler call: `edits` = [(audio, target_text, parts_to_edit, fix_duration) | PreparedEdit], `audio` a
     path, the bytes of a WAV file, or a (tensor, sr) pair.  Returns one (wave float32, 24000, spec [100, T]) triple per edit, each what
     `speech_edit` returns for that edit alone: every edit keeps the reference's batch-1 semantics (its own prompt length `lens` and its
@@ -679,7 +744,8 @@ def speech_edit_batch(edits, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     broadcast in `cond_mask & edit_mask` (cfm.py:130); the mask is cut to the mel's frames here, its last entry having no frame.
 
     The model object needs the reference's `sample()`; with `cond_mel` (F5HipModel) the edits are handed over as one padded mel batch,
-    any other object is driven edit by edit with the raw wave, like the reference does."""
+    any other object is driven edit by edit with the raw wave, like the reference does.  `generators` ([torch.Generator | None] per edit,
+    `request_generator`): an edit's noise comes from its own generator instead of the global one (F5HipModel only)."""
     if mel_spec_type not in ("vocos", "bigvgan"):
         raise ValueError(mel_spec_type)
     preps = []
@@ -693,6 +759,10 @@ def speech_edit_batch(edits, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
             audio, target_text, parts_to_edit, fix_duration = e
             preps.append(prepare_edit(audio, target_text, parts_to_edit, fix_duration, mel_spec_type, target_rms, device, tokenizer))
     knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+    if generators is not None and any(g is not None for g in generators):
+        if not hasattr(model_obj, "cond_mel") or len(generators) != len(preps):
+            raise ValueError("generators: one per edit, and a model object with cond_mel (F5HipModel)")
+        knobs["generators"] = list(generators)
     if hasattr(model_obj, "cond_mel"):
         mels = [model_obj.cond_mel(p.cond)[0] for p in preps]
         lens = torch.tensor([m.shape[0] for m in mels], dtype=torch.long)

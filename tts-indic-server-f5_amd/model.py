@@ -91,6 +91,22 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def unit_duration(cond_frames: int, n_tokens: int, frames: int, max_duration: int = 4096) -> int:
+    """The rows `sample()` lays out for a batch-1 unit: the planned `frames`, raised to lens + 1 where lens = max(prompt mel frames, text
+    tokens) (F/model/cfm.py:123-125,136-137), capped at `max_duration`.  A seeded unit's noise has this many rows."""
+    return min(max(max(int(n_tokens), int(cond_frames)) + 1, int(frames)), int(max_duration))
+
+
+def per_unit_cfg(cfg_strength, n: int):
+    """None for one scalar strength (f5hip_cfm_sample_masked), else the n per-unit strengths as fp32 (f5hip_cfm_sample_units)."""
+    if isinstance(cfg_strength, (int, float, np.floating, np.integer)) or (isinstance(cfg_strength, torch.Tensor) and cfg_strength.ndim == 0):
+        return None
+    cfg = np.ascontiguousarray(np.asarray([float(c) for c in cfg_strength], dtype=np.float32))
+    if cfg.shape != (n,):
+        raise ValueError(f"cfg_strength: one value per unit ({n}) or one float, got {cfg.shape[0]} values")
+    return cfg
+
+
 class F5HipModel:
     def __init__(self, arch: DiTArch | UNetTArch | MMDiTArch, state_dict: dict, vocab_char_map: dict | None = None, gemm_planes: int = 3,
                  device: str | torch.device = "cuda:0", mel_spec_type: str = "vocos", odeint_kwargs: dict | None = None,
@@ -190,13 +206,18 @@ class F5HipModel:
         return cond
 
     @torch.no_grad()
-    def sample_units(self, audio, units, *, steps=32, cfg_strength=2.0, sway_sampling_coef=-1.0, seed=None):
+    def sample_units(self, audio, units, *, steps=32, cfg_strength=2.0, sway_sampling_coef=-1.0, seed=None, generators=None, y0=None):
         """Independent sampling units in ONE sampler call: the text chunks of one request (independent `sample()` calls in the
         reference, F/infer/utils_infer.py:441-466), or the chunks of several requests with different voices (`infer.infer_requests`).
         `audio`: the reference wave [1, nw] (or its mel [1, n, mel]) shared by all units, or a list with one such tensor per unit;
         `units` = [(tokens, frames)].  Returns one [frames_i, mel] tensor per unit.  Every unit keeps batch-1 semantics with its own
         prompt length (`lens`), and noise is drawn unit by unit in order, i.e. the same draws the reference's sequential calls make
-        from the global generator."""
+        from the global generator.
+
+        Per-unit settings: `cfg_strength` is one float or one value per unit (a unit below 1e-5 runs no unconditional branch); `generators`
+        ([torch.Generator | None] per unit) draws a unit's noise from its own CPU generator instead of the global one, with the unit's final
+        duration (`unit_duration`), and `y0` ([tensor [dur_i, mel] | None] per unit) hands a unit its noise outright.  Units without either
+        keep drawing from the global generator, unit by unit in order.  The time grid (`steps`, `sway_sampling_coef`) is the call's."""
         b = len(units)
         frames = torch.tensor([int(f) for _, f in units], dtype=torch.long)
         lens = None
@@ -212,14 +233,14 @@ class F5HipModel:
         else:
             cond = (self.cond_mel(audio) if audio.ndim == 2 else audio.to(self.device, torch.float32)).expand(b, -1, -1)
         out, _ = self.sample(cond, [t for t, _ in units], frames, lens=lens, steps=steps, cfg_strength=cfg_strength,
-                             sway_sampling_coef=sway_sampling_coef, seed=seed)
+                             sway_sampling_coef=sway_sampling_coef, seed=seed, generators=generators, y0=y0)
         # (sample() raises a duration to lens + 1 like the reference does, cfm.py:136: the rows of unit i are its FINAL duration)
         return [out[i, :self._last_min_frames[i]] for i in range(b)]
 
     @torch.no_grad()
     def sample(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None,
                seed=None, max_duration=4096, vocoder=None, no_ref_audio=False, duplicate_test=False, t_inter=0.1,
-               edit_mask=None, y0=None, padded_batch=False):
+               edit_mask=None, y0=None, padded_batch=False, generators=None):
         """CFM.sample (F/model/cfm.py:82-210).  Returns (out [b, n, mel] on the device, None): the trajectory is
         not materialised (its only in-tree consumer drops it, F/infer/utils_infer.py:459).
 
@@ -228,7 +249,9 @@ class F5HipModel:
         computes when it is handed b > 1 items itself (cfm.py:151-154: every item padded to the longest, key-padding mask, zeroed
         attention rows, unmasked convolutions over the padding), padded rows included.
         `y0` ([b, n, mel] or list of [dur_i, mel]; host or device) overrides the noise, which is otherwise drawn exactly like the
-        reference's CPU path (per item `torch.manual_seed(seed)`; `torch.randn(dur, mel)` from the global CPU generator)."""
+        reference's CPU path (per item `torch.manual_seed(seed)`; `torch.randn(dur, mel)` from the global CPU generator).  Per item, a
+        list `y0` may hold None and `generators` ([torch.Generator | None]) draws the item's `randn(dur, mel)` from its own generator.
+        `cfg_strength`: one float (f5hip_cfm_sample_masked) or one value per item (f5hip_cfm_sample_units)."""
         if cond.ndim == 2:   # raw wave -> mel (cfm.py:103-106) with the extractor of mel_spec_type (modules.py:123-126)
             cond = self.cond_mel(cond)
         cond = cond.to(self.device, torch.float32)
@@ -262,14 +285,22 @@ class F5HipModel:
         lay = [nmax] * batch if padded else durs          # rows laid out per item
 
         # noise (cfm.py:181-186): per item randn(dur_i), zero padded to the laid-out length
+        if generators is not None and len(generators) != batch:
+            raise ValueError(f"generators: one per item ({batch}), got {len(generators)}")
+        cfg_units = per_unit_cfg(cfg_strength, batch)
         ys = []
         for i, dur in enumerate(durs):
-            if y0 is None:
+            given = y0[i] if y0 is not None else None
+            if given is not None:
+                if given.shape[0] < dur:
+                    raise ValueError(f"y0 of item {i}: {given.shape[0]} rows for a duration of {dur}")
+                yi = given[:dur].to(self.device, torch.float32)
+            elif generators is not None and generators[i] is not None:
+                yi = torch.randn(dur, self.num_channels, generator=generators[i]).to(self.device)
+            else:
                 if seed is not None:
                     torch.manual_seed(seed)
                 yi = torch.randn(dur, self.num_channels).to(self.device)
-            else:
-                yi = y0[i][:dur].to(self.device, torch.float32)
             if lay[i] > dur:
                 yi = torch.nn.functional.pad(yi, (0, 0, 0, lay[i] - dur))
             ys.append(yi)
@@ -291,7 +322,20 @@ class F5HipModel:
         text_np = _i32(text.numpy())
         tg = np.ascontiguousarray(t.numpy().astype(np.float32))
         d_np, kv_np = _i32(lay), _i32(durs)
-        if torch_ops.load():   # the TORCH_LIBRARY operator over the same C entry point (csrc/torch_ops.cpp)
+        if cfg_units is not None:   # one strength per item: f5hip_cfm_sample_units
+            if torch_ops.load():
+                try:
+                    out_packed = torch_ops.ops().cfm_sample_units(
+                        int(self._h), torch.from_numpy(d_np), torch.from_numpy(kv_np) if padded else None, cond_packed, torch.from_numpy(mask_packed),
+                        torch.from_numpy(text_np), y0_packed, torch.from_numpy(tg), torch.from_numpy(cfg_units))
+                except RuntimeError as e:
+                    raise _lib.F5HipError(str(e).split("\n")[0]) from None
+            else:
+                _lib.check(self._lib.f5hip_cfm_sample_units(
+                    self._h, batch, _ptr(d_np), _ptr(kv_np) if padded else None, _ptr(cond_packed), _ptr(mask_packed), _ptr(text_np),
+                    text_np.shape[1], _ptr(y0_packed), _ptr(tg), steps, _ptr(cfg_units), _ptr(out_packed), _lib.current_stream_ptr()),
+                    "f5hip_cfm_sample_units")
+        elif torch_ops.load():   # the TORCH_LIBRARY operator over the same C entry point (csrc/torch_ops.cpp)
             try:
                 out_packed = torch_ops.ops().cfm_sample(int(self._h), torch.from_numpy(d_np), torch.from_numpy(kv_np) if padded else None, cond_packed,
                                                         torch.from_numpy(mask_packed), torch.from_numpy(text_np), y0_packed, torch.from_numpy(tg), float(cfg_strength))

@@ -36,11 +36,49 @@ from concurrent.futures import Future
 from dataclasses import dataclass, field
 from typing import Callable
 
+import math
+
 import numpy as np
 
 from . import infer
 
 log = logging.getLogger(__name__)
+
+EDIT_OPTIONS = ("nfe_step", "cfg_strength", "sway_sampling_coef", "seed")   # a speech edit has no `speed`: its durations are planned
+# most ODE steps one library call accepts per method: 128 time points (f5hip precompute_time); midpoint uses 2 per step, RK4 3 per step + 1
+MAX_NFE_STEP = {"euler": 128, "midpoint": 64, "rk4": 42}
+
+
+def check_request_options(options: dict, ode_method: str = "euler", allowed=infer.REQUEST_OPTIONS) -> dict:
+    """The per-request sampler options a client set (None = not set, dropped), checked before anything is queued: ValueError with a message
+    the routes return as 400.  `speed` finite and > 0; `nfe_step` an integer in 1..MAX_NFE_STEP[ode_method]; `cfg_strength` and
+    `sway_sampling_coef` finite; `seed` an integer in 0..2**63 - 1."""
+    out = {}
+    for k, v in options.items():
+        if k not in allowed:
+            raise ValueError(f"unknown option {k!r} (allowed: {', '.join(allowed)})")
+        if v is None:
+            continue
+        if k in ("nfe_step", "seed"):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{k} must be an integer (got {v!r})")
+            v = int(v)
+            if k == "nfe_step":
+                hi = MAX_NFE_STEP[ode_method]
+                if not 1 <= v <= hi:
+                    raise ValueError(f"nfe_step must be between 1 and {hi} for the {ode_method} solver (got {v}).")
+            elif not 0 <= v < 2 ** 63:
+                raise ValueError(f"seed must be between 0 and 2**63 - 1 (got {v}).")
+        else:
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"{k} must be a number (got {v!r})")
+            v = float(v)
+            if not math.isfinite(v):
+                raise ValueError(f"{k} must be a finite number (got {v}).")
+            if k == "speed" and v <= 0:
+                raise ValueError(f"speed must be greater than 0 (got {v}).")
+        out[k] = v
+    return out
 
 @dataclass
 class Voice:
@@ -206,6 +244,16 @@ class TTSManager:
         self._device_lock = threading.Lock()
         self.request_timeout_s = 600.0       # a request never waits for its batch for ever
 
+    @property
+    def ode_method(self) -> str:
+        """The loaded handle's ODE method ("euler" when the model object does not say): bounds a request's `nfe_step`."""
+        local = getattr(self.model_obj, "local", self.model_obj)
+        return (getattr(local, "odeint_kwargs", None) or {}).get("method", "euler")
+
+    def request_options(self, allowed=infer.REQUEST_OPTIONS, **options) -> dict:
+        """`check_request_options` for this manager's solver: the options a request sets (absent / None ones fall back to `self.opts`)."""
+        return check_request_options(options, self.ode_method, allowed)
+
     def load(self, model_obj=None, vocoder=None):
         """Attach the sampler / vocoder objects (F5HipModel, F5HipVocos | F5HipBigVGAN), or build them with `loader`."""
         if not self.model:
@@ -253,31 +301,47 @@ class TTSManager:
                 self._prep_cache[key] = (infer.PreparedVoice(wav_path), ref_text_n)
             return self._prep_cache[key]
 
-    def _call(self, text, ref_audio_path, ref_text):
-        voice, ref_text_n = self._voice(ref_audio_path, ref_text)
-        if self.batcher is not None:   # wait for the batch this request rides in (the route runs in a worker thread, see create_app)
-            return self.batcher.submit((voice, ref_text_n, text)).result(timeout=self.request_timeout_s)
-        return self._run_batch([(voice, ref_text_n, text)])[0]
+    @staticmethod
+    def _request(voice, ref_text, text, opts):
+        """The batcher's request tuple: (voice, ref_text, text), plus the request's options when it sets any (`infer.infer_requests`)."""
+        return (voice, ref_text, text, opts) if opts else (voice, ref_text, text)
 
-    def synthesize(self, text, ref_audio_path, ref_text):
+    def _call(self, text, ref_audio_path, ref_text, **options):
+        voice, ref_text_n = self._voice(ref_audio_path, ref_text)
+        req = self._request(voice, ref_text_n, text, options)
+        if self.batcher is not None:   # wait for the batch this request rides in (the route runs in a worker thread, see create_app)
+            return self.batcher.submit(req).result(timeout=self.request_timeout_s)
+        return self._run_batch([req])[0]
+
+    def synthesize(self, text, ref_audio_path, ref_text, *, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None, seed=None):
+        """The wave of one request.  The sampler options are this request's own (None: `self.opts`); `seed` draws its noise from its own
+        generator (`infer.request_generator`), so the same seeded request gives the same audio whatever it is batched with (shape-invariant
+        attention, one GPU)."""
         if not self.model:
             raise ValueError("TTS model not loaded")
-        return self.model(text, ref_audio_path=ref_audio_path, ref_text=ref_text)
+        opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+        return self.model(text, ref_audio_path=ref_audio_path, ref_text=ref_text, **opts)
 
-    def synthesize_stream(self, text, ref_audio_path, ref_text):
+    def synthesize_stream(self, text, ref_audio_path, ref_text, *, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
+                          seed=None):
         """`synthesize` as an iterator of float32 pieces (24 kHz) whose concatenation is `synthesize`'s wave given the same noise (see
         `infer.infer_process_stream`).  The request's first chunk is synthesized on its own and its stable samples come out as soon as it is
         done; the remaining chunks follow as a second request.  With a micro-batcher the first chunk rides in the next batch and the
         remaining chunks are queued once that batch has started, so they ride in a later one; without, the two run one after the other,
         each under the device lock (released in between).  Closing the iterator early (client disconnect) cancels the remaining chunks
-        if their batch has not started.  Errors about the model or the voice are raised here, not on the first `next()`."""
+        if their batch has not started.  Errors about the model or the voice are raised here, not on the first `next()`.  Options as in
+        `synthesize`; with a `seed`, the first chunk and the remaining chunks draw from the request's one generator in chunk order, so the
+        pieces equal `synthesize`'s wave with that seed."""
         if not self.model:
             raise ValueError("TTS model not loaded")
+        opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
         voice, ref_text_n = self._voice(ref_audio_path, ref_text)
         chunks = infer.request_chunks(ref_text_n, voice.seconds, text)
-        return self._stream(voice, ref_text_n, chunks[:1], chunks[1:])
+        if "seed" in opts:   # head and tail continue one sequence; the tail's batch runs after the head's (one worker, one batch at a time)
+            opts["generator"] = infer.request_generator(opts.pop("seed"))
+        return self._stream(voice, ref_text_n, chunks[:1], chunks[1:], opts)
 
-    def _stream(self, voice, ref_text, head, tail):
+    def _stream(self, voice, ref_text, head, tail, opts=None):
         lock, state = threading.Lock(), {"closed": False, "tail": None, "error": None}
         started = threading.Event()
 
@@ -285,7 +349,7 @@ class TTSManager:
             with lock:
                 try:
                     if not state["closed"]:
-                        state["tail"] = self.batcher.submit((voice, ref_text, tail))
+                        state["tail"] = self.batcher.submit(self._request(voice, ref_text, tail, opts))
                 except Exception as e:    # noqa: BLE001 -- e.g. the batcher is closing: reported to the consumer
                     state["error"] = e
             started.set()
@@ -300,10 +364,10 @@ class TTSManager:
             joiner = infer.StreamJoiner(infer.cross_fade_duration)
             try:
                 if self.batcher is not None:
-                    head_f = self.batcher.submit((voice, ref_text, head), on_start=submit_tail if tail else None)
+                    head_f = self.batcher.submit(self._request(voice, ref_text, head, opts), on_start=submit_tail if tail else None)
                     head_waves = head_f.result(timeout=self.request_timeout_s)
                 else:
-                    head_waves = self._run_batch([(voice, ref_text, head)])[0]
+                    head_waves = self._run_batch([self._request(voice, ref_text, head, opts)])[0]
                 for w in head_waves:
                     piece = joiner.push(w)
                     if len(piece):
@@ -317,7 +381,7 @@ class TTSManager:
                             return
                         tail_waves = state["tail"].result(timeout=self.request_timeout_s)
                     else:
-                        tail_waves = self._run_batch([(voice, ref_text, tail)])[0]
+                        tail_waves = self._run_batch([self._request(voice, ref_text, tail, opts)])[0]
                     for w in tail_waves:
                         piece = joiner.push(w)
                         if len(piece):
@@ -330,20 +394,24 @@ class TTSManager:
 
         return SynthesisStream(pieces(), cancel)
 
-    def edit(self, audio, target_text, parts_to_edit, fix_duration=None):
+    def edit(self, audio, target_text, parts_to_edit, fix_duration=None, *, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
+             seed=None):
         """Speech editing (`infer.speech_edit`, F/infer/speech_edit.py): regenerate `parts_to_edit` of the recording `audio` (a path, WAV
-        bytes or a (tensor, sr) pair) so that it speaks `target_text`, with this manager's sampler settings.  The host preparation runs
-        outside the device lock, the sampler and vocoder under it (not through the micro-batcher); with a `ShardedSampler` on rank 0's own
-        model.  Returns the wave (float32, 24 kHz)."""
+        bytes or a (tensor, sr) pair) so that it speaks `target_text`, with this manager's sampler settings unless the call sets its own
+        (`seed`: the edit's noise from its own generator).  The host preparation runs outside the device lock, the sampler and vocoder
+        under it (not through the micro-batcher); with a `ShardedSampler` on rank 0's own model.  Returns the wave (float32, 24 kHz)."""
         if not self.model:
             raise ValueError("TTS model not loaded")
+        opts = dict(self.opts, **self.request_options(EDIT_OPTIONS, nfe_step=nfe_step, cfg_strength=cfg_strength,
+                                                      sway_sampling_coef=sway_sampling_coef, seed=seed))
         model_obj = getattr(self.model_obj, "local", self.model_obj)
         # host work (read, mono mix, resample, plan, tokens) and every rejection happen before the device lock is taken
         prep = infer.prepare_edit(audio, target_text, parts_to_edit, fix_duration, mel_spec_type=self.mel_spec_type)
+        extra = dict(generators=[infer.request_generator(opts["seed"])]) if opts.get("seed") is not None else {}
         with self._device_lock:
             (wave, _, _), = infer.speech_edit_batch([prep], model_obj, self.vocoder, mel_spec_type=self.mel_spec_type,
-                                                    nfe_step=self.opts["nfe_step"], cfg_strength=self.opts["cfg_strength"],
-                                                    sway_sampling_coef=self.opts["sway_sampling_coef"])
+                                                    nfe_step=opts["nfe_step"], cfg_strength=opts["cfg_strength"],
+                                                    sway_sampling_coef=opts["sway_sampling_coef"], **extra)
         return np.asarray(wave, dtype=np.float32)
 
 
@@ -380,8 +448,8 @@ class HTTPError(Exception):
         self.status_code, self.detail = status_code, detail
 
 
-def synthesize_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None):
-    """`S/utils/tts_utils.py:38-65` with the same checks in the same order and the same messages."""
+def synthesize_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None, **options):
+    """`S/utils/tts_utils.py:38-65` with the same checks in the same order and the same messages; `options` go to `TTSManager.synthesize`."""
     voice = registry.get(ref_audio_name)
     if voice is not None and not ref_text:
         ref_text = voice.ref_text
@@ -391,11 +459,11 @@ def synthesize_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: st
         raise HTTPError(400, "Text to synthesize cannot be empty.")
     if not ref_text or not ref_text.strip():
         raise HTTPError(400, "Reference text cannot be empty.")
-    audio = tts_manager.synthesize(text, ref_audio_path=voice.audio_path, ref_text=ref_text)
+    audio = tts_manager.synthesize(text, ref_audio_path=voice.audio_path, ref_text=ref_text, **options)
     return wav_bytes(audio)
 
 
-def stream_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None):
+def stream_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None, **options):
     """`synthesize_speech`'s checks, then `TTSManager.synthesize_stream`: an iterator of float32 pieces."""
     voice = registry.get(ref_audio_name)
     if voice is not None and not ref_text:
@@ -406,57 +474,76 @@ def stream_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, r
         raise HTTPError(400, "Text to synthesize cannot be empty.")
     if not ref_text or not ref_text.strip():
         raise HTTPError(400, "Reference text cannot be empty.")
-    return tts_manager.synthesize_stream(text, ref_audio_path=voice.audio_path, ref_text=ref_text)
+    return tts_manager.synthesize_stream(text, ref_audio_path=voice.audio_path, ref_text=ref_text, **options)
 
 
 def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     """FastAPI app with the reference's `/v1/audio/speech` route (`S/routes/speech.py:19-41`) and `/v1/audio/edit` (speech editing:
     JSON body {"audio": base64 WAV, "text": the full new transcript, "parts_to_edit": [[start_s, end_s], ...], "fix_duration": [...] | null}
     -> the edited recording as WAV).  Both speech routes take `"stream": true`: the WAV then arrives chunk by chunk (`_run_stream`), its
-    PCM samples identical to the unstreamed response's."""
+    PCM samples identical to the unstreamed response's.  Every route also takes the optional sampler fields `nfe_step`, `cfg_strength`,
+    `sway_sampling_coef`, `seed` and (speech routes) `speed`, checked before anything is queued (400 with `check_request_options`'s
+    message); an omitted field is the manager's setting.  With a `seed`, the same request returns the same audio."""
     from fastapi import APIRouter, FastAPI, HTTPException
     from pydantic import BaseModel
     from starlette.responses import StreamingResponse
 
-    class KannadaSynthesizeRequest(BaseModel):       # S/utils/tts_utils.py:27-28
+    class SamplerFields(BaseModel):                  # per-request sampler settings; None = the manager's (TTSManager.opts)
+        nfe_step: int | None = None
+        cfg_strength: float | None = None
+        sway_sampling_coef: float | None = None
+        seed: int | None = None
+
+    class KannadaSynthesizeRequest(SamplerFields):   # S/utils/tts_utils.py:27-28
         text: str
         stream: bool = False
+        speed: float | None = None
 
-    class SynthesizeRequest(BaseModel):              # S/utils/tts_utils.py:22-25
+    class SynthesizeRequest(SamplerFields):          # S/utils/tts_utils.py:22-25
         text: str
         ref_audio_name: str
         ref_text: str | None = None
         stream: bool = False
+        speed: float | None = None
 
-    class EditRequest(BaseModel):                    # F/infer/speech_edit.py's inputs; JSON (base64 WAV), not multipart
+    class EditRequest(SamplerFields):                # F/infer/speech_edit.py's inputs; JSON (base64 WAV), not multipart
         audio: str
         text: str
         parts_to_edit: list[list[float]]
         fix_duration: list[float] | None = None
 
+    def _options(req, allowed):
+        """The request's sampler fields, checked (400) before anything is queued."""
+        try:
+            return tts_manager.request_options(allowed, **{k: getattr(req, k) for k in allowed})
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+
     router = APIRouter(prefix="/v1", tags=["speech"])
 
-    def _run(text, name, ref_text, filename):
+    def _run(text, name, ref_text, filename, req):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
+        opts = _options(req, infer.REQUEST_OPTIONS)
         if not text.strip():
             raise HTTPException(status_code=400, detail="Text to synthesize cannot be empty.")
         try:
-            buf = synthesize_speech(tts_manager, registry, text=text, ref_audio_name=name, ref_text=ref_text)
+            buf = synthesize_speech(tts_manager, registry, text=text, ref_audio_name=name, ref_text=ref_text, **opts)
         except HTTPError as e:
             raise HTTPException(status_code=e.status_code, detail=e.detail)
         return StreamingResponse(buf, media_type="audio/wav", headers={"Content-Disposition": f"attachment; filename={filename}"})
 
-    def _run_stream(text, name, ref_text, filename):
+    def _run_stream(text, name, ref_text, filename, req):
         """stream=true: the same checks as `_run`, then the first piece is synthesized BEFORE the response exists, so a bad request, an
         unloaded model or a failing first chunk still comes back as a status code.  The body is a streaming WAV (`wav_stream_header`)
         followed by int16 PCM pieces; a failure after the first bytes can only end the body early, and is logged."""
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
+        opts = _options(req, infer.REQUEST_OPTIONS)
         if not text.strip():
             raise HTTPException(status_code=400, detail="Text to synthesize cannot be empty.")
         try:
-            pieces = stream_speech(tts_manager, registry, text=text, ref_audio_name=name, ref_text=ref_text)
+            pieces = stream_speech(tts_manager, registry, text=text, ref_audio_name=name, ref_text=ref_text, **opts)
             first = next(pieces, None)
         except HTTPError as e:
             raise HTTPException(status_code=e.status_code, detail=e.detail)
@@ -483,6 +570,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     def _run_edit(req):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
+        opts = _options(req, EDIT_OPTIONS)
         try:
             raw = base64.b64decode(req.audio, validate=True)
         except (binascii.Error, ValueError):
@@ -494,7 +582,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         except ValueError as e:
             raise HTTPException(status_code=400, detail=f"Invalid audio: {e}")
         try:
-            wave = tts_manager.edit(audio, req.text, req.parts_to_edit, req.fix_duration)
+            wave = tts_manager.edit(audio, req.text, req.parts_to_edit, req.fix_duration, **opts)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
         return StreamingResponse(wav_bytes(wave), media_type="audio/wav",
@@ -507,12 +595,12 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     @router.post("/audio/speech", response_class=StreamingResponse)
     async def synthesize_kannada(request: KannadaSynthesizeRequest):
         return await run_in_threadpool(_run_stream if request.stream else _run, request.text, registry.default_voice, None,
-                                       "synthesized_kannada_speech.wav")
+                                       "synthesized_kannada_speech.wav", request)
 
     @router.post("/audio/speech/voice", response_class=StreamingResponse)
     async def synthesize_with_voice(request: SynthesizeRequest):     # the generic form the reference's helper already supports
         return await run_in_threadpool(_run_stream if request.stream else _run, request.text, request.ref_audio_name, request.ref_text,
-                                       "synthesized_speech.wav")
+                                       "synthesized_speech.wav", request)
 
     @router.post("/audio/edit", response_class=StreamingResponse)
     async def edit_speech(request: EditRequest):                    # speech editing (F/infer/speech_edit.py) over the same manager
@@ -541,7 +629,11 @@ class ShardedSampler:
     Failure: a rank whose local `sample_units` raises still joins the gather with a failure header; rank 0 then raises
     `ShardedJobError` after the collective has completed on every rank, and refuses later jobs (`failed`).
     Noise: every rank draws the noise of ITS units from its own generator (like the reference's per-call `torch.randn`, unseeded in
-    `infer_batch_process`), so an unseeded result is not reproducible across world sizes; pass `seed=` in the knobs for that.
+    `infer_batch_process`), so an unseeded result is not reproducible across world sizes; pass `seed=` in the knobs for that.  Units with
+    their own generator (`generators=`, a seeded request's chunks) get their noise drawn HERE, on rank 0, in unit order at the unit's final
+    duration (`model.unit_duration`), and broadcast with the job: a seeded unit gets the same noise whichever rank samples it.
+    Per-unit `cfg_strength` (a list) is sliced to each rank's units.  (Ranks > 0 do not switch their handles to the shape-invariant
+    attention mode yet, so the bit-for-bit promises of a seeded request hold on one GPU.)
     Streaming (`TTSManager.synthesize_stream`) needs nothing here: a stream's first chunk and its remaining chunks arrive as units of
     ordinary `sample_units` batches."""
 
@@ -573,9 +665,27 @@ class ShardedSampler:
                 voices.append(a)
                 voice_of.append(len(voices) - 1)
         mels = [(self.local.cond_mel(a) if a.ndim == 2 else a)[0].to(torch.float32) for a in voices]
-        job = dict(units=[(list(t), int(f)) for t, f in units], voice_of=voice_of, mel_shapes=[tuple(m.shape) for m in mels], knobs=knobs)
+        knobs = dict(knobs)
+        gens, y0 = knobs.pop("generators", None), knobs.pop("y0", None)
+        cfg = knobs.get("cfg_strength")
+        per_unit = None if isinstance(cfg, (int, float, np.integer, np.floating)) or cfg is None else [float(c) for c in cfg]
+        if per_unit is not None:
+            if len(per_unit) != b:
+                raise ValueError(f"cfg_strength: one value per unit ({b}), got {len(per_unit)}")
+            knobs["cfg_strength"] = None      # replaced per rank by its units' slice
+        noise = list(y0) if y0 is not None else [None] * b
+        if gens is not None:
+            from .model import unit_duration
+            mel_dim = mels[0].shape[1]
+            for i, ((tokens, frames), g) in enumerate(zip(units, gens)):
+                if g is not None and noise[i] is None:
+                    dur = unit_duration(mels[voice_of[i]].shape[0], len(tokens), frames)
+                    noise[i] = torch.randn(dur, mel_dim, generator=g)
+        noise_rows = [0 if n is None else int(n.shape[0]) for n in noise]
+        job = dict(units=[(list(t), int(f)) for t, f in units], voice_of=voice_of, mel_shapes=[tuple(m.shape) for m in mels], knobs=knobs,
+                   cfg=per_unit, noise_rows=noise_rows)
         try:
-            return _run_sharded_job(self.local, job, mels, self.device)
+            return _run_sharded_job(self.local, job, mels, self.device, noise if any(noise_rows) else None)
         except ShardedJobError as e:
             self.failed = str(e)
             raise
@@ -585,9 +695,10 @@ class ShardedSampler:
             self.dist.broadcast_object_list([None], src=0)
 
 
-def _run_sharded_job(local_model, job, mels, device):
+def _run_sharded_job(local_model, job, mels, device, noise=None):
     """Collective part shared by rank 0 (`job`, `mels` given) and the workers (both None): returns the mels of all units on rank 0.
-    Every rank that entered the job's broadcast also enters its gather, whatever its local sampler did."""
+    Every rank that entered the job's broadcast also enters its gather, whatever its local sampler did.  `noise` (rank 0): per unit the
+    [dur, mel] noise drawn from its own generator, or None; broadcast in one payload when any unit has one (`job["noise_rows"]`)."""
     import sys
     import traceback
 
@@ -608,14 +719,30 @@ def _run_sharded_job(local_model, job, mels, device):
         for a, b in job["mel_shapes"]:
             mels.append(flat[k:k + a * b].view(a, b))
             k += a * b
+        rows, mel_dim = job.get("noise_rows") or [], job["mel_shapes"][0][1]
+        if any(rows):   # the seeded units' noise, drawn on rank 0
+            if rank == 0:
+                buf = torch.cat([n.reshape(-1).to(device, torch.float32) for n in noise if n is not None])
+            else:
+                buf = torch.empty(sum(rows) * mel_dim, dtype=torch.float32, device=device)
+            dist.broadcast(buf, src=0)
+            noise, k = [], 0
+            for r in rows:
+                noise.append(buf[k:k + r * mel_dim].view(r, mel_dim) if r else None)
+                k += r * mel_dim
     units = job["units"]
     shards = shard_units([f for _, f in units], world)
     mine = shards[rank]
     # payload of a rank: a status word (number of units, or -1: the local sampler failed), the row count of each unit, then their rows
     # (a unit's final duration can exceed the planned frames: sample() raises it to lens + 1 like the reference, cfm.py:136)
     local_error = None
+    knobs = dict(job["knobs"])
+    if job.get("cfg") is not None:        # per-unit CFG strengths: this rank's units
+        knobs["cfg_strength"] = [job["cfg"][i] for i in mine]
+    if noise is not None and any(noise[i] is not None for i in mine):
+        knobs["y0"] = [noise[i] for i in mine]
     try:
-        outs = local_model.sample_units([mels[job["voice_of"][i]][None] for i in mine], [units[i] for i in mine], **job["knobs"]) if mine else []
+        outs = local_model.sample_units([mels[job["voice_of"][i]][None] for i in mine], [units[i] for i in mine], **knobs) if mine else []
         if len(outs) != len(mine):
             raise RuntimeError(f"sample_units returned {len(outs)} mels for {len(mine)} units")
         head = torch.tensor([float(len(outs))] + [float(o.shape[0]) for o in outs], dtype=torch.float32, device=device)
