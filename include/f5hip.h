@@ -137,6 +137,9 @@ int f5hip_get_profile(const char* kernel_class, double* total_ms, int64_t* launc
  * tiles only), "gemm3_wide" (fp16 128 x 256 tiles), "gemm3" (every gemm3 launch, wide or not), "conv5", "gemm6" (ping-pong tiles
  * of 256 columns: the batch-mode shapes), "gemm6_r176" / "gemm6_r256" (gemm6 by tile height), "gemm_reg_bn64" / "gemm_reg_bn128"
  * (every gemm.h launch by column-tile width, convolutions included);
+ * and of the attention dispatcher, one per attn3 instance: "attn_bal8" (SIMD-balanced 8-wave, 9-stage ring), "attn_nw8_deep" /
+ * "attn_nw8" (8 waves, 9- / 5-stage ring), "attn_nw6_deep" / "attn_nw6" (6 waves, shape-invariant mode only), "attn_nw4", plus
+ * "attn_seg2" (every two-range launch, whatever its instance);
  * name "reset" zeroes all of them (value may be NULL). */
 int f5hip_get_counter(const char* name, int64_t* value);
 
@@ -166,15 +169,20 @@ int f5hip_op_qkv(int32_t M, int32_t D, const float* a_dev, const float* w_dev, c
 /* f5hip_op_attention: softmax(q k^T / 8 + key-padding mask) v per (sequence, head), head dim 64 -- F.scaled_dot_product_attention with the
  *   reference's [b, 1, 1, n] key mask (F/model/modules.py:424-436).  q_dev / k_dev / v_dev / out_dev fp32 [sum(seq_len)][64 heads], sequences
  *   packed back to back; kv_len[i] <= seq_len[i] valid keys (NULL: all).  Operands are rounded to fp16 (saturated) like the QKV epilogue's outputs.
- *   impl must be 3 (the production kernel, attn3); any other value fails. */
+ *   impl must be 3 (the production kernel, attn3); any other value fails.  shape_invariant: the launch's attention arithmetic, as
+ *   f5hip_set_attention_shape_invariant (1 / 0, or -1 = the process default).  out_format: what the kernel writes, read back into out_dev
+ *   as fp32 -- 0 split-bf16 planes (hi + lo), 1 one fp16 plane (the blocks' fp16 GEMM mode), 2 the bf16 hi plane alone (bf16 GEMM mode). */
 int f5hip_op_attention(int32_t n_seq, const int32_t* seq_len, const int32_t* kv_len, int32_t heads, const float* q_dev, const float* k_dev,
-                       const float* v_dev, float* out_dev, int32_t impl, int32_t iters, double* avg_us, void* stream);
+                       const float* v_dev, float* out_dev, int32_t impl, int32_t iters, double* avg_us, void* stream, int32_t shape_invariant,
+                       int32_t out_format);
 /* f5hip_op_joint_attention: the joint attention of the MMDiT blocks (JointAttnProcessor, F/model/modules.py:496-522): per sequence the
  *   queries and the keys are its audio rows followed by its text rows; only audio keys can be padding (x_kvlen[i] <= x_len[i] valid; NULL:
  *   all).  q_dev / k_dev / v_dev / out_dev fp32 [sum(x_len) + sum(c_len)][64 heads]: all audio frames sequence by sequence, then all
- *   text tokens sequence by sequence.  Operands are rounded to fp16 (saturated) like the QKV epilogue's outputs. */
+ *   text tokens sequence by sequence.  Operands are rounded to fp16 (saturated) like the QKV epilogue's outputs.  shape_invariant and
+ *   out_format as in f5hip_op_attention. */
 int f5hip_op_joint_attention(int32_t n_seq, const int32_t* x_len, const int32_t* x_kvlen, const int32_t* c_len, int32_t heads,
-                             const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, void* stream);
+                             const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, void* stream, int32_t shape_invariant,
+                             int32_t out_format);
 /* f5hip_op_layernorm: y = LN(x) * (gain_off + scale) + shift (AdaLN: gain_off 1; affine LN: gain_off 0; F/model/modules.py:285-290),
  *   rms = 1: x-transformers RMSNorm y = x / max(|x|_2, 1e-12) * sqrt(D) * scale.  All fp32 [M][D] / [D]. */
 int f5hip_op_layernorm(int32_t M, int32_t D, const float* x_dev, const float* scale_dev, const float* shift_dev, float gain_off, float eps,

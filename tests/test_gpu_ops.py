@@ -318,21 +318,141 @@ def test_layernorm_large_mean(mode, D, ratio):
     assert rel < bound
 
 
+# Every launch counter of the attention dispatcher (csrc/tu_attn.hip f5_launch_attn3): one per attn3 instance, plus two-range launches
+ATTN_COUNTERS = ("attn_bal8", "attn_nw8_deep", "attn_nw8", "attn_nw6_deep", "attn_nw6", "attn_nw4", "attn_seg2")
+
+
+def _attn_counters():
+    return {n: _counter(n) for n in ATTN_COUNTERS}
+
+
+def _assert_attn_path(instance, seg2, got=None):
+    got = _attn_counters() if got is None else got
+    want = {n: int(n == "attn_" + instance or (seg2 and n == "attn_seg2")) for n in ATTN_COUNTERS}
+    assert got == want, f"attention instance: got {got}, expected {want}"
+
+
+def _attn_ref(q, k, v, lens, kv, heads):
+    """fp64 softmax attention per packed sequence on the fp16-rounded operands (q after the log2(e) / 8 scale, undone in fp64)."""
+    qb, kb, vb = (q * Q_SCALE).half().double() * math.log(2.0), k.half().double(), v.half().double()
+    o, refs = 0, []
+    for i, L in enumerate(lens):
+        kl = L if kv is None else kv[i]
+        qs, ks, vs = (t[o:o + L].view(L, heads, 64).transpose(0, 1) for t in (qb, kb, vb))
+        s = qs @ ks.transpose(1, 2)
+        s[:, :, kl:] = float("-inf")
+        refs.append((torch.softmax(s, dim=-1) @ vs).transpose(0, 1).reshape(L, 64 * heads))
+        o += L
+    return torch.cat(refs)
+
+
+def _check_attn_formats(run, ref, instance, seg2, rel_bound, label):
+    """run(out_format) -> fp32 output of one attention launch; every output format against the fp64 reference, and the counters of each launch.
+
+    Split-bf16 planes (16 significand bits) carry the kernel's fp32 result o; their bounds, 2.5e-3 max and 5e-4 relative rms, cover the fp16
+    P and V operands over up to a few thousand keys.  The fp16 plane (mixed GEMM mode) is o rounded to nearest once: |fl(o) - o| <= 2^-11 |o|,
+    half an ulp, in the normal range (below 2^-14 the absolute half ulp, 2^-25, is far inside the bound).  So, elementwise,
+    |out - ref| <= 2.5e-3 + 2^-11 (|ref| + 2.5e-3), and over the whole output rel rms <= r + 2^-11 (1 + r) by the triangle inequality, r
+    the split planes' rms bound (rel_bound; None: none).
+    The bf16 hi plane (bf16 mode) is o rounded to bf16: the same with 2^-8 for 2^-11.  Both narrow formats must also be that rounding of the
+    split planes of the same launch shape (the same o): |out - split| <= (h + 2^-16) |split| + 2^-24, h the half ulp above and 2^-16 what
+    hi + lo may miss of o (2^-17) with slack."""
+    from tts_indic_server_f5_amd import ops
+    split = None
+    for fmt, h, name in ((ops.ATTN_OUT_SPLIT, 0.0, "split"), (ops.ATTN_OUT_F16, 2.0 ** -11, "fp16"), (ops.ATTN_OUT_BF16, 2.0 ** -8, "bf16")):
+        _reset_counters()
+        out = run(fmt)
+        _assert_attn_path(instance, seg2)
+        assert torch.isfinite(out).all(), (label, name)
+        out = out.double().cpu()
+        err = (out - ref).abs()
+        rel = _rel(out, ref)
+        print(f"[parity] {label} {instance} {name}: max err {err.max().item():.3e} rel rms {rel:.3e}")
+        assert (err <= 2.5e-3 + h * (ref.abs() + 2.5e-3)).all(), (label, name, err.max().item())
+        if rel_bound is not None:
+            assert rel < rel_bound + h * (1 + rel_bound), (label, name, rel)
+        if split is None:
+            split = out
+        else:
+            dev = (out - split).abs() - ((h + 2.0 ** -16) * split.abs() + 2.0 ** -24)
+            assert (dev <= 0).all(), (label, name, "not the rounding of the split planes", dev.max().item())
+
+
+def _hot_block(q, k, hot):
+    """Each (q_row, k_row): the 32 queries from q_row on (one query block when q_row is a multiple of 32) point at key k_row, a key that is
+    no query block's sample (odd, and not one of the 16 spread over the key range): logits ~360 nats above every other, so exactly those
+    blocks overflow the fixed-offset fast loop and take the running-maximum redo, next to blocks of the same workgroup that do not."""
+    for qr, kr in hot:
+        q[qr:qr + 32] = 20.0 * k[kr]
+
+
+# The instance table of f5_launch_attn3.  Cost rule: t_NW = ceil(max_len / 32 NW) query tiles per (sequence, head), wgs_NW = t_NW heads n_seq
+# workgroups (n_seq counts the 2 pseudo-sequences of a joint sequence), cost_NW = ceil(wgs_NW / 256) NW; the least cost wins, ties in the
+# order 8, 6, 4.  NW = 6 runs the balanced 8-wave kernel (bal8) unless the launch is shape-invariant; NW = 6 / 8 take the 9-stage ring
+# ("deep") when wgs <= 256.  Each row: wgs_8 / wgs_6 / wgs_4 -> cost_8 / cost_6 / cost_4.  inv: AttnArgs::shape_invariant (-1: the
+# process default, 0).  "overhang": the last query tile of a 6- or 8-wave workgroup reaches past the sequence's 128-row padding into the
+# next sequence's rows.  kv: key counts that end inside the first (1-32) or second (33-63) half of a 64-key tile, and kv = 1.
+N6_LENS = (385,) + tuple(385 - 11 * i for i in range(1, 32)) + (1,)                 # 33 sequences, 385 .. 44 and 1 frames
+N6_KV = tuple(L if i % 3 == 0 else max(1, L - 5 * i) for i, L in enumerate(N6_LENS))
+N8_LENS = tuple(577 - 37 * i for i in range(13))                                     # 13 sequences, 577 .. 133
+N8_KV = tuple(L if i % 2 == 0 else L - 9 * i for i, L in enumerate(N8_LENS))
+N8D_LENS = tuple(577 - 50 * i for i in range(11))                                    # 11 sequences, 577 .. 77
+N8D_KV = tuple(L if i % 2 == 0 else L - 13 * i for i, L in enumerate(N8D_LENS))
+BAL_HOT = ((224, 1001), (704, 701), (1120, 1033))   # blocks 1 (tile 1), 4 (tile 3: key 701 in the key half of waves 6 / 7), 5 (tile 5: key 1033
+#                                                      in the half of waves 4 / 5); the other blocks 4 / 5 of those tiles merge their key halves
+
+
 @pytest.mark.parametrize("impl", [3])
-@pytest.mark.parametrize("lens,kv,heads,k_gain", [((1404, 1404), None, 16, 1.0), ((300, 50, 257), (300, 41, 200), 4, 1.0), ((748,), None, 12, 1.0),
-                                                  ((64,), (1,), 2, 1.0), ((2341, 2341), None, 16, 1.0), ((33,), (33,), 2, 1.0), ((97, 160), (40, 129), 2, 1.0),
-                                                  ((1404, 300), (1404, 290), 4, 12.0), ((200,), None, 2, 40.0),
-                                                  # 6-wave workgroups with the 9-stage ring (one barrier per two tiles) next to sequences of 2 / 3 / 3 / 5 tiles
-                                                  ((1404, 70, 130, 200), (1404, 65, 130, 129), 8, 1.0), ((1404, 320, 130, 200), (1404, 300, 130, 129), 8, 12.0),
-                                                  # the balanced 8-wave kernel with key counts inside the first half tile (its key-half waves 6 / 7 then own nothing
-                                                  # valid), just past it, and one key; the last one also through the running-maximum redo
-                                                  ((1404, 1404), (1404, 20), 16, 1.0), ((1404, 1404), (33, 1), 16, 1.0), ((1500, 1310), (47, 1310), 16, 12.0)])
-def test_attention_unit_op(impl, lens, kv, heads, k_gain):
+@pytest.mark.parametrize("lens,kv,heads,k_gain,hot,inv,instance", [
+    # C2 (1404 x 16 x 2): 192 / 256 / 352 -> 8 / 6 / 8: NW = 6, 256 workgroups: bal8 (the default mode; shape-invariant: nw6_deep)
+    pytest.param((1404, 1404), None, 16, 1.0, (), -1, "bal8", id="lens0-None-16-1.0"),
+    # 300 x 4 x 3: 24 / 24 / 36 -> 8 / 6 / 4
+    pytest.param((300, 50, 257), (300, 41, 200), 4, 1.0, (), -1, "nw4", id="lens1-kv1-4-1.0"),
+    # C1 (748 x 12): 36 / 48 / 72 -> 8 / 6 / 4
+    pytest.param((748,), None, 12, 1.0, (), -1, "nw4", id="lens2-None-12-1.0"),
+    pytest.param((64,), (1,), 2, 1.0, (), -1, "nw4", id="lens3-kv3-2-1.0"),
+    # C5 (2341 x 16 x 2): 320 / 416 / 608 -> 16 / 12 / 12: NW = 6 (the tie goes to 6), 416 workgroups: bal8
+    pytest.param((2341, 2341), None, 16, 1.0, (), -1, "bal8", id="lens4-None-16-1.0"),
+    pytest.param((33,), (33,), 2, 1.0, (), -1, "nw4", id="lens5-kv5-2-1.0"),
+    pytest.param((97, 160), (40, 129), 2, 1.0, (), -1, "nw4", id="lens6-kv6-2-1.0"),
+    # 1404 x 4 x 2: 48 / 64 / 88 -> 8 / 6 / 4; k_gain: the redo
+    pytest.param((1404, 300), (1404, 290), 4, 12.0, (), -1, "nw4", id="lens7-kv7-4-12.0"),
+    pytest.param((200,), None, 2, 40.0, (), -1, "nw4", id="lens8-None-2-40.0"),
+    # 1404 x 8 x 4: 192 / 256 / 352 -> 8 / 6 / 8: NW = 6, 256 workgroups -- in the default mode the balanced 8-wave kernel with the 9-stage
+    # ring (one barrier per two tiles) next to sequences of 2 / 3 / 3 / 5 tiles; overhang: 1404's last tile (1344-1535) covers 70 rows of the next
+    pytest.param((1404, 70, 130, 200), (1404, 65, 130, 129), 8, 1.0, (), -1, "bal8", id="lens9-kv9-8-1.0"),
+    pytest.param((1404, 320, 130, 200), (1404, 300, 130, 129), 8, 12.0, (), -1, "bal8", id="lens10-kv10-8-12.0"),
+    # the balanced 8-wave kernel (C2 arithmetic as in row 0) with key counts inside the first half tile (its key-half waves 6 / 7 then own
+    # nothing valid), just past it, and one key; the last one also through the running-maximum redo (1500: 8 / 6 / 8 as 1404)
+    pytest.param((1404, 1404), (1404, 20), 16, 1.0, (), -1, "bal8", id="lens11-kv11-16-1.0"),
+    pytest.param((1404, 1404), (33, 1), 16, 1.0, (), -1, "bal8", id="lens12-kv12-16-1.0"),
+    pytest.param((1500, 1310), (47, 1310), 16, 12.0, (), -1, "bal8", id="lens13-kv13-16-12.0"),
+    # bal8: single blocks redone -- one whole-block wave, one block 4 whose overflow only key-half wave 6 sees, one block 5 only wave 5 sees
+    pytest.param((1404, 1404), None, 16, 1.0, BAL_HOT, 0, "bal8", id="bal8-hot-blocks"),
+    # nw4, shape-invariant, one block redone (1404 x 4 x 2 as row 7)
+    pytest.param((1404, 300), None, 4, 1.0, ((640, 701),), 1, "nw4", id="nw4-hot-block"),
+    # nw6_deep: the bal8 shapes above in shape-invariant mode (overhang into the next sequence: rows 9 / 10 / hot-blocks)
+    pytest.param((1404, 70, 130, 200), (1404, 65, 130, 129), 8, 1.0, (), 1, "nw6_deep", id="nw6_deep-ragged"),
+    pytest.param((1404, 1404), (33, 1), 16, 1.0, (), 1, "nw6_deep", id="nw6_deep-kv"),
+    pytest.param((1500, 1310), (47, 1310), 16, 12.0, (), 1, "nw6_deep", id="nw6_deep-gain"),
+    pytest.param((1404, 1404), None, 16, 1.0, BAL_HOT, 1, "nw6_deep", id="nw6_deep-hot-blocks"),
+    # nw6 (5-stage): 385 x 4 x 33: 264 / 396 / 528 -> 16 / 12 / 12 (tie: 6), 396 workgroups; overhang: 385's last tile (384-575) covers 64 rows
+    pytest.param(N6_LENS, N6_KV, 4, 1.0, ((64, 201),), 1, "nw6", id="nw6-hot-block"),
+    pytest.param(N6_LENS, N6_KV, 4, 12.0, (), 1, "nw6", id="nw6-gain"),
+    # nw8 (5-stage): 577 x 12 x 13: 468 / 624 / 780 -> 16 / 18 / 16 (tie: 8), 468 workgroups; overhang: 577's last tile (512-767), 128 rows
+    pytest.param(N8_LENS, N8_KV, 12, 1.0, ((288, 101),), -1, "nw8", id="nw8-hot-block"),
+    pytest.param(N8_LENS, N8_KV, 12, 12.0, (), 1, "nw8", id="nw8-gain"),
+    # nw8_deep: 577 x 6 x 11: 198 / 264 / 330 -> 8 / 12 / 8 (tie: 8), 198 workgroups
+    pytest.param(N8D_LENS, N8D_KV, 6, 1.0, ((288, 101),), 0, "nw8_deep", id="nw8_deep-hot-block"),
+    pytest.param(N8D_LENS, N8D_KV, 6, 12.0, (), 1, "nw8_deep", id="nw8_deep-gain"),
+])
+def test_attention_unit_op(impl, lens, kv, heads, k_gain, hot, inv, instance):
     """Attention kernel alone vs fp64 softmax attention on the fp16-rounded operands (q after the log2(e) / 8 scale, undone in fp64), incl. the key-padding mask
     (F/model/modules.py:429-434), ragged sequences, tiles that overhang a sequence, key counts that end inside either half of a 64-key tile,
-    and the C2 / C1 / C5 shapes.  k_gain > 1 multiplies every key at a position = 7 mod 16 from position 40 on (never one of a query block's
-    sample keys, csrc/attn3.h): logits tens to hundreds of nats above each query's maximum over its sample, which is what sends a workgroup
-    of attn3 from its fixed-offset fast loop to the running-maximum redo."""
+    and the C2 / C1 / C5 shapes, for every attn3 instance (asserted by the launch counters) in every output format (_check_attn_formats).
+    k_gain > 1 multiplies every key at a position = 15 mod 16 from position 47 on (never one of a query block's local sample keys, csrc/attn3.h):
+    logits tens to hundreds of nats above each query's maximum over its sample, which sends nearly every query block of attn3 from its
+    fixed-offset fast loop to the running-maximum redo; `hot` sends single blocks there (_hot_block)."""
     from tts_indic_server_f5_amd import ops
     g = torch.Generator().manual_seed(sum(lens) + heads)
     n, D = sum(lens), 64 * heads
@@ -344,23 +464,11 @@ def test_attention_unit_op(impl, lens, kv, heads, k_gain):
         for L in lens:
             k[o + 47:o + L:16] *= k_gain
             o += L
-    out, _ = ops.attention(q.to(DEV), k.to(DEV), v.to(DEV), lens, kv, heads=heads, impl=impl)
-    qb, kb, vb = (q * Q_SCALE).half().double() * math.log(2.0), k.half().double(), v.half().double()
-    o, refs = 0, []
-    for i, L in enumerate(lens):
-        kl = L if kv is None else kv[i]
-        qs, ks, vs = (t[o:o + L].view(L, heads, 64).transpose(0, 1) for t in (qb, kb, vb))
-        s = qs @ ks.transpose(1, 2)
-        s[:, :, kl:] = float("-inf")
-        refs.append((torch.softmax(s, dim=-1) @ vs).transpose(0, 1).reshape(L, D))
-        o += L
-    ref = torch.cat(refs)
-    # P is rounded to fp16 before the P V product (11 significand bits); the output planes carry 16 bits
-    assert torch.isfinite(out).all()
-    err, rel = (out.double().cpu() - ref).abs().max().item(), _rel(out, ref)
-    print(f"[parity] attention lens {lens} kv {kv} heads {heads} k_gain {k_gain}: max err {err:.3e} rel rms {rel:.3e}")
-    assert err < 2.5e-3
-    assert rel < 5e-4
+    _hot_block(q, k, hot)
+    ref = _attn_ref(q, k, v, lens, kv, heads)
+    qd, kd, vd = q.to(DEV), k.to(DEV), v.to(DEV)
+    _check_attn_formats(lambda fmt: ops.attention(qd, kd, vd, lens, kv, heads=heads, impl=impl, shape_invariant=inv, out_format=fmt)[0],
+                        ref, instance, False, 5e-4, f"attention lens {lens[:4]}{'...' if len(lens) > 4 else ''} heads {heads} k_gain {k_gain} hot {hot}")
 
 
 # ---------------------------------------------------------------------------------------------------------------- conv1d (BigVGAN convolutions)
@@ -410,20 +518,13 @@ def test_conv1d_vs_torch(impl, prec, tol, ci, co, k, dil, batch, P, T):
 
 
 # ---------------------------------------------------------------------------------------------------------------- MMDiT joint attention
-@pytest.mark.parametrize("x_len,c_len,x_kv", [([300], [21], None), ([1404, 257, 64], [240, 65, 7], [1404, 200, 33]), ([130, 129], [128, 1], [100, 129])])
-def test_joint_attention_vs_torch(x_len, c_len, x_kv):
-    """attn3's two-range kernels (keys = audio rows then text rows of the same sequence; queries from either) vs fp64 torch SDPA over
-    the concatenation, padding masked on the audio keys only (F/model/modules.py:506-514).  Same operand rounding and tolerance as the
-    single-range attention test."""
-    from tts_indic_server_f5_amd import ops
-    heads, D = 4, 256
-    g = torch.Generator().manual_seed(500 + sum(x_len))
-    Fx, Fc = sum(x_len), sum(c_len)
-    q, k, v = (torch.randn(Fx + Fc, D, generator=g) for _ in range(3))
-    out = ops.joint_attention(q.to(DEV), k.to(DEV), v.to(DEV), x_len, c_len, x_kv, heads=heads).cpu()
+def _joint_ref(q, k, v, x_len, c_len, x_kv, heads):
+    """fp64 joint attention (audio rows then text rows per sequence, padding masked on the audio keys) on the fp16-rounded operands, in the
+    op's row order: all audio frames, then all text tokens."""
+    D = 64 * heads
     bf = lambda t: t.to(torch.float16).double()
-    ox, oc = 0, Fx
-    worst = 0.0
+    ref = torch.empty(q.shape[0], D, dtype=torch.float64)
+    ox, oc = 0, sum(x_len)
     for i, (n, nt) in enumerate(zip(x_len, c_len)):
         sel = torch.cat([torch.arange(ox, ox + n), torch.arange(oc, oc + nt)])
         qq = (bf(q[sel] * Q_SCALE) * math.log(2.0)).view(n + nt, heads, 64).transpose(0, 1)
@@ -433,12 +534,58 @@ def test_joint_attention_vs_torch(x_len, c_len, x_kv):
         kv = n if x_kv is None else x_kv[i]
         key_ok = torch.cat([torch.arange(n) < kv, torch.ones(nt, dtype=torch.bool)])
         s = s.masked_fill(~key_ok[None, None, :], float("-inf"))
-        ref = (torch.softmax(s, dim=-1) @ vv).transpose(0, 1).reshape(n + nt, D)
-        err = (out[sel].double() - ref).abs().max().item()
-        worst = max(worst, err)
+        ref[sel] = (torch.softmax(s, dim=-1) @ vv).transpose(0, 1).reshape(n + nt, D)
         ox += n; oc += nt
-    print(f"[parity] joint attention x {x_len} c {c_len} kv {x_kv}: max err {worst:.3e}")
-    assert worst < 2.5e-3   # fp16 P and V operands (11 significand bits) over up to ~1.6 k keys; the single-range test uses the same bound
+    return ref
+
+
+# The two-range (SEG2) form of every instance; cost arithmetic as for test_attention_unit_op with n_seq = 2 pseudo-sequences per sequence
+J6_X, J6_C = tuple(385 - 17 * i for i in range(11)), tuple(1 + (37 * i) % 385 for i in range(11))
+J8_X, J8_C = tuple(577 - 41 * i for i in range(13)), tuple(1 + (53 * i) % 577 for i in range(13))
+J8D_X, J8D_C = tuple(577 - 50 * i for i in range(11)), tuple(1 + (61 * i) % 577 for i in range(11))
+
+
+@pytest.mark.parametrize("x_len,c_len,x_kv,heads,k_gain,inv,instance", [
+    # 300 x 4 x 2: 16 / 16 / 24 -> 8 / 6 / 4
+    pytest.param([300], [21], None, 4, 1.0, -1, "nw4", id="x_len0-c_len0-None"),
+    # 1404 x 4 x 6: 144 / 192 / 264 -> 8 / 6 / 8: NW = 6, 192 workgroups: bal8 (shape-invariant: nw6_deep)
+    pytest.param([1404, 257, 64], [240, 65, 7], [1404, 200, 33], 4, 1.0, -1, "bal8", id="x_len1-c_len1-x_kv1"),
+    # 130 x 4 x 4: 16 / 16 / 32 -> 8 / 6 / 4
+    pytest.param([130, 129], [128, 1], [100, 129], 4, 1.0, -1, "nw4", id="x_len2-c_len2-x_kv2"),
+    pytest.param([300], [21], None, 4, 12.0, 1, "nw4", id="nw4-gain"),
+    pytest.param([1404, 257, 64], [240, 65, 7], [1404, 200, 33], 4, 12.0, 0, "bal8", id="bal8-gain"),
+    pytest.param([1404, 257, 64], [240, 65, 7], [1404, 200, 33], 4, 1.0, 1, "nw6_deep", id="nw6_deep"),
+    pytest.param([1404, 257, 64], [240, 65, 7], [1404, 200, 33], 4, 12.0, 1, "nw6_deep", id="nw6_deep-gain"),
+    # 385 x 6 x 22: 264 / 396 / 528 -> 16 / 12 / 12 (tie: 6), 396 workgroups
+    pytest.param(J6_X, J6_C, tuple(L - 3 * i for i, L in enumerate(J6_X)), 6, 1.0, 1, "nw6", id="nw6"),
+    pytest.param(J6_X, J6_C, None, 6, 12.0, 1, "nw6", id="nw6-gain"),
+    # 577 x 6 x 26: 468 / 624 / 780 -> 16 / 18 / 16 (tie: 8), 468 workgroups
+    pytest.param(J8_X, J8_C, tuple(L - 5 * i for i, L in enumerate(J8_X)), 6, 1.0, -1, "nw8", id="nw8"),
+    pytest.param(J8_X, J8_C, None, 6, 12.0, 1, "nw8", id="nw8-gain"),
+    # 577 x 3 x 22: 198 / 264 / 330 -> 8 / 12 / 8 (tie: 8), 198 workgroups
+    pytest.param(J8D_X, J8D_C, tuple(L - 7 * i for i, L in enumerate(J8D_X)), 3, 1.0, 0, "nw8_deep", id="nw8_deep"),
+    pytest.param(J8D_X, J8D_C, None, 3, 12.0, 1, "nw8_deep", id="nw8_deep-gain"),
+])
+def test_joint_attention_vs_torch(x_len, c_len, x_kv, heads, k_gain, inv, instance):
+    """attn3's two-range kernels (keys = audio rows then text rows of the same sequence; queries from either) vs fp64 torch SDPA over
+    the concatenation, padding masked on the audio keys only (F/model/modules.py:506-514), for the two-range form of every instance in every
+    output format.  Same operand rounding and elementwise bounds as the single-range attention test (no rms bound: unit-variance q and k
+    give flat rows, outputs of rms ~ 0.05, which the absolute bound already covers); k_gain multiplies the audio keys at positions 47, 63,
+    ... of every sequence (the redo)."""
+    from tts_indic_server_f5_amd import ops
+    D = 64 * heads
+    g = torch.Generator().manual_seed(500 + sum(x_len))
+    Fx, Fc = sum(x_len), sum(c_len)
+    q, k, v = (torch.randn(Fx + Fc, D, generator=g) for _ in range(3))
+    if k_gain != 1.0:
+        o = 0
+        for n in x_len:
+            k[o + 47:o + n:16] *= k_gain
+            o += n
+    ref = _joint_ref(q, k, v, x_len, c_len, x_kv, heads)
+    qd, kd, vd = q.to(DEV), k.to(DEV), v.to(DEV)
+    _check_attn_formats(lambda fmt: ops.joint_attention(qd, kd, vd, x_len, c_len, x_kv, heads=heads, shape_invariant=inv, out_format=fmt),
+                        ref, instance, True, None, f"joint attention x {list(x_len)[:3]} c {list(c_len)[:3]} heads {heads} k_gain {k_gain}")
 
 
 def test_attention_random_shapes(monkeypatch):
@@ -452,4 +599,132 @@ def test_attention_random_shapes(monkeypatch):
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     monkeypatch.setattr(sys, "argv", ["attn_fuzz.py", "24", "3"])
+    mod.main()   # exits non-zero on the first case out of bounds
+
+
+# ---------------------------------------------------------------------------------------------------------------- shape invariance
+# In shape-invariant mode a sequence's attention output must not depend, bit for bit, on the launch it is part of (conftest.py
+# attn_shape_invariant, infer.infer_requests).  One sequence S moves across the invariant instances by its batch size alone (cost arithmetic
+# as for test_attention_unit_op; a joint sequence is 2 pseudo-sequences, so 8 heads there give the workgroup counts of 16 here):
+#   1404 frames x 16 heads: alone 96 / 128 / 176 -> 8 / 6 / 4: nw4;  + 1: 192 / 256 / 352 -> 8 / 6 / 8: nw6_deep;
+#                           + 3: 384 / 512 / 704 -> 16 / 12 / 12: nw6;  + 7: 768 / 1024 / 1408 -> 24 / 24 / 24: nw8 (5-stage)
+#   480 frames x 16 heads:  alone 32 / 48 / 64 -> 8 / 6 / 4: nw4;  + 5: 192 / 288 / 384 -> 8 / 12 / 8: nw8_deep
+# (companions: n_companions, position of S in the batch, instance)
+INV_LAUNCHES = {
+    1404: [(0, 0, "nw4"), (1, 0, "nw6_deep"), (1, 1, "nw6_deep"), (3, 0, "nw6"), (3, 2, "nw6"), (3, 3, "nw6"), (7, 0, "nw8"), (7, 4, "nw8"),
+           (7, 7, "nw8")],
+    480: [(0, 0, "nw4"), (5, 0, "nw8_deep"), (5, 3, "nw8_deep"), (5, 5, "nw8_deep")],
+}
+# one query block of S aimed at a key no block samples (_hot_block): NW = 4 / 6 / 8 put it into workgroups of 128 / 192 / 256 queries
+INV_HOT = {1404: (640, 701), 480: (288, 101)}
+
+
+def _inv_seq(kind, L, heads, seed):
+    """One sequence: (q, k, v) of its audio frames and, for a joint one, of its L // 7 + 1 text tokens (fp32, q and k with std 1.5)."""
+    g = torch.Generator().manual_seed(seed)
+    D = 64 * heads
+    parts = [L] + ([L // 7 + 1] if kind == "joint" else [])
+    return [tuple(torch.randn(n, D, generator=g) * s for s in (1.5, 1.5, 1.0)) for n in parts]
+
+
+def _inv_launch(kind, heads, seqs):
+    """One shape-invariant launch of the sequences `seqs` (split-bf16 output): (per-sequence outputs -- audio rows then text rows --,
+    the attention counters of the launch)."""
+    from tts_indic_server_f5_amd import ops
+    lens = [[p[0].shape[0] for p in s] for s in seqs]
+    # single range: the sequences back to back; joint: all audio parts, then all text parts
+    order = [s[0] for s in seqs] + ([s[1] for s in seqs] if kind == "joint" else [])
+    q, k, v = (torch.cat([p[j] for p in order]).to(DEV) for j in range(3))
+    _reset_counters()
+    if kind == "joint":
+        out = ops.joint_attention(q, k, v, [l[0] for l in lens], [l[1] for l in lens], None, heads=heads, shape_invariant=1)
+    else:
+        out, _ = ops.attention(q, k, v, [l[0] for l in lens], None, heads=heads, shape_invariant=1)
+    counters = _attn_counters()
+    rows = torch.split(out, [p[0].shape[0] for p in order])
+    n = len(seqs)
+    per_seq = [torch.cat([rows[i]] + ([rows[n + i]] if kind == "joint" else [])) for i in range(n)]
+    return per_seq, counters
+
+
+def _assert_same(got, want, label):
+    if torch.equal(got, want):
+        return
+    diff = (got - want).abs()
+    rows = diff.amax(dim=1).nonzero().flatten().tolist()
+    raise AssertionError(f"{label}: {len(rows)} rows differ (rows {rows[0]}..{rows[-1]}), max diff {diff.max().item():.3e}")
+
+
+def _s_reference(kind, s, heads):
+    (qx, kx, vx), *rest = s
+    if kind == "joint":
+        qc, kc, vc = rest[0]
+        ref = _joint_ref(torch.cat([qx, qc]), torch.cat([kx, kc]), torch.cat([vx, vc]), [qx.shape[0]], [qc.shape[0]], None, heads)
+    else:
+        ref = _attn_ref(qx, kx, vx, [qx.shape[0]], None, heads)
+    return ref
+
+
+@pytest.mark.parametrize("kind", ["single", "joint"])
+@pytest.mark.parametrize("L", [1404, 480])
+@pytest.mark.parametrize("hot", [False, True])
+def test_attention_shape_invariance(kind, L, hot):
+    """S's output is bit-identical alone and inside batches that put it on every shape-invariant instance, at first, middle and last position;
+    the counters prove the instances differ.  hot: one query block of S takes the running-maximum redo -- which queries are redone must not
+    depend on the workgroup size, so S's other rows (and the block itself) still match across instances.  S alone also against fp64."""
+    heads = 16 if kind == "single" else 8
+    S = _inv_seq(kind, L, heads, 7)
+    if hot:
+        _hot_block(S[0][0], S[0][1], (INV_HOT[L],))
+    comps = [_inv_seq(kind, L - (97 * i) % (L // 2), heads, 100 + i) for i in range(8)]
+    first, seen = None, set()
+    for n_comp, pos, instance in INV_LAUNCHES[L]:
+        batch = comps[:n_comp]
+        batch.insert(pos, S)
+        outs, counters = _inv_launch(kind, heads, batch)
+        _assert_attn_path(instance, kind == "joint", counters)
+        seen.add(instance)
+        if first is None:
+            first = outs[pos]
+            ref = _s_reference(kind, S, heads)
+            err = (first.double().cpu() - ref).abs().max().item()
+            print(f"[invariance] {kind} {L} hot {hot} alone: max err vs fp64 {err:.3e}")
+            assert err < 2.5e-3
+        else:
+            _assert_same(outs[pos], first, f"{kind} S = {L} x {heads} heads, hot block {hot}: {instance} ({n_comp} companions, S at {pos}) vs alone")
+    assert seen == {i for _, _, i in INV_LAUNCHES[L]} and len(seen) >= 2
+
+
+@pytest.mark.parametrize("kind", ["single", "joint"])
+def test_attention_neighbour_invariance(kind):
+    """The last query tile of a 6- or 8-wave workgroup reaches past S (1404 frames: rows 1344-1535 / 1280-1535) into the first 128 query
+    rows of the sequence after it.  Those rows are never stored for S, and their content must not change S's output either: with the
+    neighbour's first 128 queries hot (10x: logits far above their sample maximum against S's keys, so they overflow the fast loop in S's
+    workgroups) S must match S with a cold neighbour and S alone, on every instance whose tiles overhang."""
+    heads = 16 if kind == "single" else 8
+    L = 1404
+    S = _inv_seq(kind, L, heads, 7)
+    comps = [_inv_seq(kind, L - (97 * i) % (L // 2), heads, 100 + i) for i in range(8)]
+    hot_nb = [tuple(t.clone() for t in p) for p in comps[0]]
+    hot_nb[0][0][:128] *= 10.0
+    (alone,), counters = _inv_launch(kind, heads, [S])
+    _assert_attn_path("nw4", kind == "joint", counters)
+    for n_comp, instance in ((1, "nw6_deep"), (3, "nw6"), (7, "nw8")):
+        for nb, what in ((comps[0], "cold"), (hot_nb, "hot")):
+            outs, counters = _inv_launch(kind, heads, [S, nb] + comps[1:n_comp])
+            _assert_attn_path(instance, kind == "joint", counters)
+            _assert_same(outs[0], alone, f"{kind} S = {L} x {heads} heads, {what} neighbour: {instance} ({n_comp} companions) vs alone")
+
+
+def test_attention_random_shapes_invariant(monkeypatch):
+    """tools/attn_fuzz.py as test_attention_random_shapes, every launch shape-invariant (no balanced 8-wave kernel; NW = 6 launches run
+    the 6-wave instances)."""
+    import importlib.util
+    import os
+    import sys
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "attn_fuzz.py")
+    spec = importlib.util.spec_from_file_location("attn_fuzz", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    monkeypatch.setattr(sys, "argv", ["attn_fuzz.py", "24", "3", "1"])
     mod.main()   # exits non-zero on the first case out of bounds

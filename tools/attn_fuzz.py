@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised shapes for the attention kernel against fp64 softmax attention on the fp16-rounded operands (same reference and bounds as
 tests/test_gpu_ops.py::test_attention_unit_op): ragged batches, key counts ending anywhere in a tile, 1-16 heads, occasional large logits
-(the running-maximum redo), and the two-range (joint) kernels.  Usage: python tools/attn_fuzz.py [n_cases] [seed]"""
+(the running-maximum redo), and the two-range (joint) kernels.  Usage: python tools/attn_fuzz.py [n_cases] [seed] [shape_invariant]
+(shape_invariant: 1 / 0 for every launch, -1 = the process default, the default)"""
 import math
 import os
 import random
@@ -27,6 +28,7 @@ def ref_attn(q, k, v, heads, key_ok):
 def main():
     n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 7)
+    inv = int(sys.argv[3]) if len(sys.argv) > 3 else -1
     worst = 0.0
     for case in range(n_cases):
         heads = rng.choice([1, 2, 3, 4, 8, 12, 16])
@@ -47,7 +49,7 @@ def main():
             for L in lens:
                 k[o + min(40, L - 1):o + L] *= gain
                 o += L
-        out, _ = ops.attention(q.cuda(), k.cuda(), v.cuda(), lens, kv, heads=heads, impl=3)
+        out, _ = ops.attention(q.cuda(), k.cuda(), v.cuda(), lens, kv, heads=heads, impl=3, shape_invariant=inv)
         out = out.double().cpu()
         qb, kb, vb = (q * QS).half().double() * LN2, k.half().double(), v.half().double()
         o, err = 0, 0.0
@@ -71,7 +73,7 @@ def main():
         g = torch.Generator().manual_seed(1000 + case)
         Fx, Fc, D = sum(x_len), sum(c_len), 64 * heads
         q, k, v = (torch.randn(Fx + Fc, D, generator=g) for _ in range(3))
-        out = ops.joint_attention(q.cuda(), k.cuda(), v.cuda(), x_len, c_len, x_kv, heads=heads).double().cpu()
+        out = ops.joint_attention(q.cuda(), k.cuda(), v.cuda(), x_len, c_len, x_kv, heads=heads, shape_invariant=inv).double().cpu()
         bf = lambda t: t.to(torch.float16).double()
         ox, oc, err = 0, Fx, 0.0
         for n, nt, kvn in zip(x_len, c_len, x_kv):

@@ -40,10 +40,12 @@
 // keys have P <= 1/4, the true row maximum has P >= 1/4 (samples are keys), and every P within 2^-12 of it is still a normal number.
 // Whether every probability stayed below fp16's largest finite value is decided ONCE, after the loop, from the row sums themselves (they are
 // accumulated by the matrix pipe from the fp16 probabilities: an overflowed one makes its row sum inf; the inf it put into O is discarded with
-// it): if one did not -- a logit more than 18 binades = 12.5 nats above the query's maximum over its sample -- the WHOLE workgroup redoes its
-// tile with a plain running-maximum loop, correct
-// for any input and exercised by tests/test_gpu_ops.py (k_gain cases).  Because every variant of the kernel (and both key halves of a BAL
-// block) derives the offset from the same sample, variants differ only in the association of fp32 sums.
+// it): if one did not -- a logit more than 18 binades = 12.5 nats above the query's maximum over its sample -- the 32-query BLOCK of that
+// query redoes its keys with a plain running-maximum loop, correct for any input and exercised by tests/test_gpu_ops.py (k_gain and hot-block
+// cases).  Only queries of the sequence vote (rows past its end belong to its padding or to the next sequence), and the vote and the redo
+// are per block, not per workgroup: a block's 32 queries are the same in every variant, so which queries take the redo arithmetic does
+// not depend on the launch shape.  Because every variant of the kernel (and both key halves of a BAL block) derives the offset from the
+// same sample, variants differ only in the association of fp32 sums.
 // (The running-maximum formulation in the hot loop measured 45.7 us at C2 against 41.4 us for the fixed offset, before any of the
 // scheduling work.)
 #define A3_OFF_MARGIN 2.0f
@@ -414,8 +416,9 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
         for (int kt = 0; kt + 1 < nkt; kt++) half_only(sa[0], kt, H1{}, T_{});
         half_only(sa[0], nkt - 1, H1{}, F_{});
     }
-    // Did every probability stay in range (l_bad above)?  (The flag lives in the first bytes of the ring -- 5 x 16 KiB is exactly half a CU's LDS, two workgroups
-    // per CU -- hence the barriers: everybody done with the ring | flag cleared | flag set | flag read.)
+    // Did every probability of this block's queries stay in range (l_bad above)?  One bit per 32-query block, set by every wave of the block that
+    // saw an overflow (BAL: both key-half waves of blocks 4 / 5).  (The mask lives in the first bytes of the ring -- 5 x 16 KiB is exactly half a
+    // CU's LDS, two workgroups per CU -- hence the barriers: everybody done with the ring | mask cleared | bits set | mask read.)
     // the row sums of this wave's queries out of the 16 x 16 accumulators: query fr sits in lane fr & 15, register fr >> 4.  Kept as before as a
     // per-lane partial that the epilogue (and the BAL merge) adds over the two lane halves: the whole sum in lanes 0-31, zero in lanes 32-63.
     bool l_bad = false;
@@ -423,24 +426,28 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     for (int qb = 0; qb < QB; qb++) {
         const float l0 = __shfl(lacc[qb][0], fr & 15, 64), l1 = __shfl(lacc[qb][1], fr & 15, 64);
         const float lq = (fr >> 4) ? l1 : l0;
-        l_bad = l_bad || !(lq <= 3.0e38f);                 // inf (a probability overflowed fp16) or NaN
+        // inf (a probability overflowed fp16) or NaN, of a query of the sequence: rows past its end (its padding, or the next sequence's
+        // queries in the last tile of a 6- or 8-wave workgroup) must not send a block of this one to the redo
+        l_bad = l_bad || (q0 + (qblk + qb) * 32 + fr < len && !(lq <= 3.0e38f));
         lrun[qb] = fh ? 0.0f : lq;
     }
-    int* redo_flag = reinterpret_cast<int*>(smem);
+    int* redo_mask = reinterpret_cast<int*>(smem);
     attn_wait_vmcnt<0>();
     __syncthreads();
-    if (threadIdx.x == 0) *redo_flag = 0;
+    if (threadIdx.x == 0) *redo_mask = 0;
     __syncthreads();
-    if (__any(l_bad) && lane == 0) *redo_flag = 1;
+    if (__any(l_bad) && lane == 0) atomicOr(redo_mask, 1 << qblk);
     __syncthreads();
-    const bool redo = *redo_flag != 0;
+    const int mask = *redo_mask;
+    const bool redo = (mask >> qblk) & 1;   // this wave's block redoes; every wave takes part in the loop's tile moves and barriers if any does
     __syncthreads();
-    if (redo) {   // GENERAL loop: running maximum, any input; plain code, one query block at a time
+    if (mask) {   // GENERAL loop: running maximum, any input; plain code, one query block at a time
         float mrun[QB];
 #pragma unroll
         for (int qb = 0; qb < QB; qb++) {
-            lrun[qb] = 0.0f;
             mrun[qb] = -1e30f;
+            if (!redo) continue;
+            lrun[qb] = 0.0f;
 #pragma unroll
             for (int g = 0; g < 16; g++) { oacc[qb][0][g] = 0.0f; oacc[qb][1][g] = 0.0f; negm[qb][g] = 0.0f; }
         }
@@ -455,7 +462,9 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
             const unsigned vb = stage_of(gk) + v_lane;
 #pragma unroll 1
             for (int h = 0; h < 2; h++) {
-                if (BAL && role == 2) break;   // (waves 6 / 7 only move tiles and keep the barriers; blocks 4 / 5 are redone whole by waves 4 / 5)
+                // (waves of blocks that keep their fast-loop result, and BAL's waves 6 / 7, only move tiles and keep the barriers; blocks 4 / 5
+                // are redone whole by waves 4 / 5)
+                if (!redo || (BAL && role == 2)) break;
                 f16x8 kf[4];
                 qk_read(kf, gk, h);
 #pragma unroll
@@ -492,7 +501,7 @@ static __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     }
     if (BAL) {
         // merge the key halves of blocks 4 / 5: waves 6 / 7 hand (offset, l, O) to waves 4 / 5 through LDS (the ring is idle), which bring both to the
-        // larger offset -- exact power-of-two factors <= 1 -- and add.  After a redo the whole-block result of waves 4 / 5 stands alone.
+        // larger offset -- exact power-of-two factors <= 1 -- and add.  After a redo of its block the whole-block result of wave 4 / 5 stands alone.
         float* mbuf = reinterpret_cast<float*>(smem) + (size_t)(wave & 1) * 34 * 64;
         __syncthreads();
         if (role == 2 && !redo) {

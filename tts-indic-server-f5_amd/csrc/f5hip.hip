@@ -566,14 +566,23 @@ static int run_ln(const LnArgs& a, hipStream_t st) {
     return 0;
 }
 
-// Diagnostics for tests: which GEMM path the launches since the last reset took (names in the order of the CNT_ enum); name "reset" zeroes them.
+// Diagnostics for tests: which GEMM path the launches since the last reset took (names in the order of the CNT_ enum), and which attn3
+// instance (names in the order of tu_attn.hip's counters); name "reset" zeroes them all.
 extern "C" int f5hip_get_counter(const char* name, int64_t* value) {
     static const char* names[CNT_COUNT] = {"gemm5_rb11", "gemm5_rb8", "gemm5_wide", "gemm3_wide", "conv5", "gemm6", "gemm6_r176", "gemm6_r256",
                                            "gemm5_cb12", "gemm3", "gemm_reg_bn64", "gemm_reg_bn128"};
+    static const char* attn_names[F5_ATTN_CNT_COUNT] = {"attn_bal8", "attn_nw8_deep", "attn_nw8", "attn_nw6_deep", "attn_nw6", "attn_nw4", "attn_seg2"};
+    long long* attn = f5_attn_counters();
     if (!name) return fail(-1, "get_counter: null name");
-    if (!strcmp(name, "reset")) { for (auto& c : g_counters) c = 0; return 0; }
+    if (!strcmp(name, "reset")) {
+        for (auto& c : g_counters) c = 0;
+        for (int i = 0; i < F5_ATTN_CNT_COUNT; i++) attn[i] = 0;
+        return 0;
+    }
     for (int i = 0; i < CNT_COUNT; i++)
         if (!strcmp(name, names[i])) { if (value) *value = g_counters[i]; return 0; }
+    for (int i = 0; i < F5_ATTN_CNT_COUNT; i++)
+        if (!strcmp(name, attn_names[i])) { if (value) *value = attn[i]; return 0; }
     return fail(-1, "unknown counter %s", name);
 }
 

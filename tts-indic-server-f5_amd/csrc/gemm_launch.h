@@ -28,6 +28,9 @@ hipError_t f5_launch_conv5(int prec, const GemmArgs& a, int n_pad, hipStream_t s
 // attn3.h: flash attention forward, 256 queries per workgroup
 hipError_t f5_launch_attn3(const AttnArgs& a, int max_len, int heads, int n_seq, hipStream_t st);
 void f5_set_attn_shape_invariant(int on);
+// attn3 launches since the last reset: BAL 8-wave / NW8 9-stage / NW8 5-stage / NW6 9-stage / NW6 5-stage / NW4, then two-range (SEG2) launches
+enum { F5_ATTN_CNT_COUNT = 7 };
+long long* f5_attn_counters();
 
 // gemm5 tile choice: fewest operand bytes per CU over the whole launch = rounds on the 256 CUs x (BM + BN); ties -> the larger tile.
 // rb == 0: no instantiated tile divides n_pad.

@@ -15,9 +15,14 @@
 // slower, profiles/r03_attn5_pingpong.txt) and 16 x 16 x 32 MFMA blocks with unequal-height waves (profiles/r02_attn_bench.txt).
 static int g_attn_shape_invariant = 0;   // f5hip_set_attention_shape_invariant: the default of launches whose AttnArgs::shape_invariant is -1
 void f5_set_attn_shape_invariant(int on) { g_attn_shape_invariant = on != 0; }
+// Launch counters (test instrumentation, read through f5hip_get_counter): one per instance, in the order of attn3_launch, then two-range launches
+static long long g_attn_counters[F5_ATTN_CNT_COUNT] = {};
+long long* f5_attn_counters() { return g_attn_counters; }
 
 template <bool SEG2>
 static void attn3_launch(const AttnArgs& a, int best, bool deep, bool bal, dim3 grid, hipStream_t st) {
+    g_attn_counters[bal ? 0 : best == 8 ? (deep ? 1 : 2) : best == 6 ? (deep ? 3 : 4) : 5]++;
+    if (SEG2) g_attn_counters[6]++;
     if (bal) hipLaunchKernelGGL((attn3_fwd_kernel<8, SEG2, 9, true>), grid, dim3(512), 0, st, a);
     else if (best == 8 && deep) hipLaunchKernelGGL((attn3_fwd_kernel<8, SEG2, 9>), grid, dim3(512), 0, st, a);
     else if (best == 8) hipLaunchKernelGGL((attn3_fwd_kernel<8, SEG2, 5>), grid, dim3(512), 0, st, a);

@@ -248,9 +248,13 @@ __global__ __launch_bounds__(256) void op_pack_qkv_kernel(const float* q, const 
         reinterpret_cast<_Float16*>(vt)[(size_t)c * M_pad + vt_col(row)] = sat_f16(vv);
     }
 }
-__global__ __launch_bounds__(256) void op_unpack_planes_kernel(const __bf16* hi, const __bf16* lo, int D, const int* frame_row, float* out) {
+// the attention output back into frame order as fp32: hi + lo (split-bf16 planes), hi alone (lo == null: the bf16 plane), or hi read as one fp16 plane
+__global__ __launch_bounds__(256) void op_unpack_planes_kernel(const __bf16* hi, const __bf16* lo, int f16, int D, const int* frame_row, float* out) {
     const int f = blockIdx.x, row = frame_row[f];
-    for (int c = threadIdx.x; c < D; c += 256) out[(size_t)f * D + c] = (float)hi[(size_t)row * D + c] + (float)lo[(size_t)row * D + c];
+    for (int c = threadIdx.x; c < D; c += 256) {
+        const size_t i = (size_t)row * D + c;
+        out[(size_t)f * D + c] = f16 ? (float)reinterpret_cast<const _Float16*>(hi)[i] : (float)hi[i] + (lo ? (float)lo[i] : 0.0f);
+    }
 }
 
 // One (pseudo-)sequence of the attention unit ops: query rows row0 .. + len (frames frame0 .. + len of the caller's q / k / v / out) over the
@@ -258,10 +262,12 @@ __global__ __launch_bounds__(256) void op_unpack_planes_kernel(const __bf16* hi,
 struct AttnSeq { int row0, len, frame0, kv_row0, kvlen, kv2_row0 = 0, kv2_len = 0; };
 
 // The attention unit ops over `seqs`, whose query rows tile a layout padded to 128 rows per (pseudo-)sequence: q / k / v fp32 frames are packed
-// into the rows, attn3 runs (timed like the other ops: the warm-up launch writes the output), and the split-bf16 output planes are summed back
+// into the rows, attn3 runs (timed like the other ops: the warm-up launch writes the output) with AttnArgs::shape_invariant = `invariant`
+// and the output format `out_format` (0: split-bf16 planes, 1: one fp16 plane, 2: the bf16 hi plane alone), and the output is read back
 // into frame order.  qk, V^T and the output planes carry 256 zeroed slack rows: the last query tile may read (never store) past the padded rows.
 static int attention_op(const char* name, const std::vector<AttnSeq>& seqs, int heads, const float* q_dev, const float* k_dev, const float* v_dev,
-                        float* out_dev, int iters, double* avg_us, hipStream_t st) {
+                        float* out_dev, int iters, double* avg_us, int invariant, int out_format, hipStream_t st) {
+    if (invariant < -1 || invariant > 1 || out_format < 0 || out_format > 2) return fail(-1, "%s: bad shape_invariant / out_format", name);
     const int NS = (int)seqs.size(), D = heads * 64;
     int M_pad = 0, F = 0, max_len = 0;
     bool seg2 = false;
@@ -289,21 +295,22 @@ static int attention_op(const char* name, const std::vector<AttnSeq>& seqs, int 
     AttnArgs at; memset(&at, 0, sizeof(at));
     at.qk = qk; at.vt = vt; at.D = D; at.ldvt = ld; at.seq_row0 = d_meta; at.seq_len = d_meta + NS; at.seq_kvlen = d_meta + 2 * NS;
     if (seg2) { at.seq_kv_row0 = d_meta + 3 * NS; at.seq_kv2_row0 = d_meta + 4 * NS; at.seq_kv2_len = d_meta + 5 * NS; }
-    at.out_hi = ohi; at.out_lo = olo; at.shape_invariant = -1;
+    at.out_hi = ohi; at.out_lo = out_format == 0 ? olo : nullptr; at.f16_out = out_format == 1; at.shape_invariant = invariant;
     CK(time_launches(1, iters, avg_us, st, [&](int) {
         const hipError_t e = f5_launch_attn3(at, max_len, heads, NS, st);
         return e == hipSuccess ? 0 : fail(-7, "%s launch: %s", name, hipGetErrorString(e));
     }));
-    hipLaunchKernelGGL(op_unpack_planes_kernel, dim3(F), dim3(256), 0, st, ohi, olo, D, d_fr, out_dev);
+    hipLaunchKernelGGL(op_unpack_planes_kernel, dim3(F), dim3(256), 0, st, ohi, at.out_lo, at.f16_out, D, d_fr, out_dev);
     if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "%s: %s", name, hipGetErrorString(hipGetLastError()));
     return 0;
 }
 
 // softmax(q k^T / 8 + key-padding mask) v per (sequence, head), head dim 64 (F/model/modules.py:424-436): q / k / v fp32 [sum(seq_len)][64 heads]
-// are rounded to fp16 like the QKV epilogue's outputs (q after the log2(e) / 8 scale); out fp32 [sum(seq_len)][64 heads] = split-bf16 planes summed.
-// impl must be 3 (attn3, the production kernel).
+// are rounded to fp16 like the QKV epilogue's outputs (q after the log2(e) / 8 scale); out fp32 [sum(seq_len)][64 heads] = the output in
+// format out_format (attention_op).  impl must be 3 (attn3, the production kernel).
 extern "C" int f5hip_op_attention(int32_t n_seq, const int32_t* seq_len, const int32_t* kv_len, int32_t heads, const float* q_dev,
-                                  const float* k_dev, const float* v_dev, float* out_dev, int32_t impl, int32_t iters, double* avg_us, void* stream) {
+                                  const float* k_dev, const float* v_dev, float* out_dev, int32_t impl, int32_t iters, double* avg_us, void* stream,
+                                  int32_t shape_invariant, int32_t out_format) {
     if (n_seq <= 0 || !seq_len || heads <= 0 || !q_dev || !k_dev || !v_dev || !out_dev || impl != 3) return fail(-1, "op_attention: bad argument");
     std::vector<AttnSeq> seqs;
     for (int i = 0, r0 = 0, f0 = 0; i < n_seq; i++) {
@@ -311,7 +318,7 @@ extern "C" int f5hip_op_attention(int32_t n_seq, const int32_t* seq_len, const i
         seqs.push_back({r0, seq_len[i], f0, r0, kv_len ? kv_len[i] : seq_len[i]});
         r0 += ceil_to(seq_len[i], 128); f0 += seq_len[i];
     }
-    return attention_op("op_attention", seqs, heads, q_dev, k_dev, v_dev, out_dev, iters, avg_us, (hipStream_t)stream);
+    return attention_op("op_attention", seqs, heads, q_dev, k_dev, v_dev, out_dev, iters, avg_us, shape_invariant, out_format, (hipStream_t)stream);
 }
 
 // Joint attention of the MMDiT blocks (JointAttnProcessor, F/model/modules.py:496-522): per sequence the queries and the keys are the
@@ -319,7 +326,8 @@ extern "C" int f5hip_op_attention(int32_t n_seq, const int32_t* seq_len, const i
 // q / k / v / out fp32 [sum(x_len) + sum(c_len)][64 heads]: all audio frames sequence by sequence, then all text tokens sequence by
 // sequence.  Runs the two-range attn3 kernels over 2 n_seq pseudo-sequences (audio queries, text queries) that share the key ranges.
 extern "C" int f5hip_op_joint_attention(int32_t n_seq, const int32_t* x_len, const int32_t* x_kvlen, const int32_t* c_len, int32_t heads,
-                                        const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, void* stream) {
+                                        const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, void* stream,
+                                        int32_t shape_invariant, int32_t out_format) {
     if (n_seq <= 0 || !x_len || !c_len || heads <= 0 || !q_dev || !k_dev || !v_dev || !out_dev) return fail(-1, "op_joint_attention: bad argument");
     int Mx = 0, Fx = 0;   // audio rows and frames come first, the text rows and tokens behind them
     for (int i = 0; i < n_seq; i++) {
@@ -334,7 +342,7 @@ extern "C" int f5hip_op_joint_attention(int32_t n_seq, const int32_t* x_len, con
         seqs.push_back({rc, c_len[i], fc, rx, kv, rc, c_len[i]});
         rx += ceil_to(x_len[i], 128); rc += ceil_to(c_len[i], 128); fx += x_len[i]; fc += c_len[i];
     }
-    return attention_op("op_joint_attention", seqs, heads, q_dev, k_dev, v_dev, out_dev, 0, nullptr, (hipStream_t)stream);
+    return attention_op("op_joint_attention", seqs, heads, q_dev, k_dev, v_dev, out_dev, 0, nullptr, shape_invariant, out_format, (hipStream_t)stream);
 }
 
 // One Conv1d of the BigVGAN kind over channel-last rows -- batch sequences of pitch P rows, T valid -- through the library's two paths:

@@ -69,9 +69,14 @@ def layernorm(x, scale, shift, *, gain_off=1.0, eps=1e-6, rms=False):
     return out
 
 
-def attention(q, k, v, seq_len, kv_len=None, *, heads, impl=3, iters=0):
+# output formats of the attention unit ops (what the kernel writes; the op returns it as fp32): split-bf16 planes, one fp16 plane (the
+# blocks' fp16 GEMM mode), the bf16 hi plane alone (bf16 GEMM mode)
+ATTN_OUT_SPLIT, ATTN_OUT_F16, ATTN_OUT_BF16 = 0, 1, 2
+
+
+def attention(q, k, v, seq_len, kv_len=None, *, heads, impl=3, iters=0, shape_invariant=-1, out_format=ATTN_OUT_SPLIT):
     """softmax(q k^T / 8 + key mask) v per (sequence, head); q / k / v fp32 [sum(seq_len), 64 * heads] packed.  Returns (out, avg_us).
-    impl must be 3 (attn3, the production kernel)."""
+    impl must be 3 (attn3, the production kernel); shape_invariant 1 / 0 / -1 (the process default, f5hip_set_attention_shape_invariant)."""
     dev = q.device
     q, k, v = (_f32(t, dev) for t in (q, k, v))
     out = torch.empty_like(q)
@@ -79,7 +84,7 @@ def attention(q, k, v, seq_len, kv_len=None, *, heads, impl=3, iters=0):
     kl = None if kv_len is None else np.ascontiguousarray(np.asarray(kv_len, dtype=np.int32))
     us = C.c_double(0.0)
     _lib.check(_lib.lib().f5hip_op_attention(len(sl), _p(sl), _p(kl), heads, _p(q), _p(k), _p(v), _p(out), impl, iters, C.byref(us),
-                                             _lib.current_stream_ptr()), "f5hip_op_attention")
+                                             _lib.current_stream_ptr(), int(shape_invariant), int(out_format)), "f5hip_op_attention")
     return out, us.value
 
 
@@ -104,15 +109,16 @@ def conv1d(x, weight, bias=None, res=None, *, batch, valid, dilation=1, prec=2, 
     return out, us.value, st
 
 
-def joint_attention(q, k, v, x_len, c_len, x_kvlen=None, *, heads):
+def joint_attention(q, k, v, x_len, c_len, x_kvlen=None, *, heads, shape_invariant=-1, out_format=ATTN_OUT_SPLIT):
     """MMDiT joint attention: per sequence softmax(q [x ; c] k^T / 8 + mask on the padded audio keys) v over the concatenation of its audio
-    rows and its text rows.  q / k / v fp32 [sum(x_len) + sum(c_len), 64 * heads]: all audio frames first, then all text tokens."""
+    rows and its text rows.  q / k / v fp32 [sum(x_len) + sum(c_len), 64 * heads]: all audio frames first, then all text tokens.
+    shape_invariant and out_format as in attention()."""
     dev = q.device
     q, k, v = (_f32(t, dev) for t in (q, k, v))
     out = torch.empty_like(q)
     xl = np.ascontiguousarray(np.asarray(x_len, dtype=np.int32))
     cl = np.ascontiguousarray(np.asarray(c_len, dtype=np.int32))
     kl = None if x_kvlen is None else np.ascontiguousarray(np.asarray(x_kvlen, dtype=np.int32))
-    _lib.check(_lib.lib().f5hip_op_joint_attention(len(xl), _p(xl), _p(kl), _p(cl), heads, _p(q), _p(k), _p(v), _p(out), _lib.current_stream_ptr()),
-               "f5hip_op_joint_attention")
+    _lib.check(_lib.lib().f5hip_op_joint_attention(len(xl), _p(xl), _p(kl), _p(cl), heads, _p(q), _p(k), _p(v), _p(out), _lib.current_stream_ptr(),
+                                                   int(shape_invariant), int(out_format)), "f5hip_op_joint_attention")
     return out
