@@ -102,6 +102,17 @@ int f5hip_cfm_sample_units(f5hip_dit* m, int32_t n_utt, const int32_t* dur, cons
                            const uint8_t* cond_mask, const int32_t* text, int32_t nt_max, const float* y0_dev,
                            const float* t_grid, int32_t steps, const float* cfg_strength, float* out_dev, void* stream);
 
+/* f5hip_cfm_sample_units with one time grid per unit as well: unit u takes steps[u] >= 1 steps over its own grid, the steps[u] + 1 floats
+ * of t_grids that follow the grids of units 0..u-1 (sum(steps) + n_utt floats in all), and its own CFG strength cfg_strength[u].  With
+ * every ODE method and backbone, a unit's result is what f5hip_cfm_sample_units (or _masked) gives it alone with its grid and strength as
+ * the call's; when all units share one grid, the call IS f5hip_cfm_sample_units.  The union of the units' time points (Euler: steps[u]
+ * per unit, midpoint: 2 steps[u], RK4: 3 steps[u] + 1; equal values once) may hold at most 256 points -- checked before anything is
+ * launched.  The call runs max(steps) iterations; a unit whose steps are done is frozen and leaves the layout (counter "dit_rows": the
+ * summed backbone rows of the forwards). */
+int f5hip_cfm_sample_grids(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev,
+                           const uint8_t* cond_mask, const int32_t* text, int32_t nt_max, const float* y0_dev,
+                           const int32_t* steps, const float* t_grids, const float* cfg_strength, float* out_dev, void* stream);
+
 /* The fixed-grid solver both sample calls use: replaces CFM(odeint_kwargs=dict(method=...)) (F/model/cfm.py:37-41,72,200; set from
  * load_model(ode_method=...), F/infer/utils_infer.py:251).  0 = "euler" (default): x += dt * v(t_i, x).  1 = "midpoint":
  * x += dt * v(t_i + dt / 2, x + dt / 2 * v(t_i, x)), two backbone evaluations per step, at most 64 steps per call.  2 = "rk4": torchdiffeq's
@@ -139,7 +150,7 @@ int f5hip_get_profile(const char* kernel_class, double* total_ms, int64_t* launc
  * (every gemm.h launch by column-tile width, convolutions included);
  * and of the attention dispatcher, one per attn3 instance: "attn_bal8" (SIMD-balanced 8-wave, 9-stage ring), "attn_nw8_deep" /
  * "attn_nw8" (8 waves, 9- / 5-stage ring), "attn_nw6_deep" / "attn_nw6" (6 waves, shape-invariant mode only), "attn_nw4", plus
- * "attn_seg2" (every two-range launch, whatever its instance);
+ * "attn_seg2" (every two-range launch, whatever its instance), and "dit_rows" (the summed audio rows M of every backbone forward);
  * name "reset" zeroes all of them (value may be NULL). */
 int f5hip_get_counter(const char* name, int64_t* value);
 

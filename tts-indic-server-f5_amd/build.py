@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(CSRC, "libf5hip.so")
-UNITS = ["f5hip.hip", "tu_gemm_reg.hip", "tu_gemm3.hip", "tu_gemm5_generic.hip", "tu_gemm5_qkv.hip", "tu_gemm6.hip", "tu_conv5.hip", "tu_attn.hip"]
+UNITS = ["f5hip.hip", "tu_gemm_reg.hip", "tu_gemm3.hip", "tu_gemm5_generic.hip", "tu_gemm5_qkv.hip", "tu_gemm5_rowmul.hip", "tu_gemm6.hip", "tu_conv5.hip", "tu_attn.hip"]
 HOT = ("gemm", "conv5", "attn", "ln_kernel")   # kernels that must not touch scratch memory
 # Per-unit flags.  tu_attn: hipcc's SLP vectorizer turns the softmax row sums into v_pk_add_f32, which beside MFMAs costs more issue time than
 # the two v_add_f32 it replaces (MI355X_MICROARCH "packed f32 VALU ... an anti-lever beside MFMAs"); measured in profiles/r02_attn_bench.txt.

@@ -10,11 +10,18 @@
 // and the block GEMMs give XCD x the row slabs of rows [x M / 8, (x + 1) M / 8) (gemm5_tile_of_block) -- both the GEMM that just wrote the
 // residual rows this kernel reads and the GEMM that reads the operand rows it writes.  With the same blocking here a row stays in one XCD's L2
 // from the residual epilogue through the norm to the next GEMM's first fill instead of crossing the fabric twice.
-template <int NV>
+// ROW_MOD: every row takes its scale / shift from its own modulation row (LnArgs::row_mod; f5hip_cfm_sample_grids)
+template <int NV, bool ROW_MOD = false>
 __global__ __launch_bounds__(256) void ln_kernel(const LnArgs p) {
     unsigned b = blockIdx.x;
     if ((gridDim.x & 7) == 0) b = (b & 7) * (gridDim.x >> 3) + (b >> 3);
-    ln_row<NV>(p, b * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+    ln_row<NV, ROW_MOD>(p, b * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+}
+
+// f5hip_cfm_sample_grids: the time point of every row for one forward, row_tp[r] = unit_tp[row_unit[r]] (the row's unit, padding rows included)
+__global__ __launch_bounds__(256) void row_tp_kernel(const int* row_unit, const int* unit_tp, int R, int* row_tp) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r < R) row_tp[r] = unit_tp[row_unit[r]];
 }
 
 // Rotary factors per ROW: out_cos / out_sin [R][32] = table[row_pos[r]][32].  Once per sampler call (the positions do not change over the ODE steps):
@@ -125,14 +132,22 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* x, int ldx
 // step from the untouched xbase.
 // kFrameCfg: the strength of frame u is cfg_frame[u] (f5hip_cfm_sample_units: one strength per unit, spread over its frames) instead of
 // the scalar `cfg`; the arithmetic is the same, so the scalar instantiation is the kernel the single-strength entry points always ran.
-template <bool kFrameCfg>
+// kUnitDt (f5hip_cfm_sample_grids): the step of frame u is unit_dt[frame_unit[u]], and the frames of units >= n_act (their steps are done)
+// are left as they are.
+template <bool kFrameCfg, bool kUnitDt = false>
 __global__ __launch_bounds__(128) void cfg_euler_kernel(float* xout /*[U][mel]*/, const float* xbase, int mel, int U, const float* pred,
                                                         int ldp, const int* urow_c, const int* urow_u, float cfg, const float* cfg_frame,
-                                                        float dt, __bf16* xs_hi, __bf16* xs_lo, int ldx) {
+                                                        float dt, __bf16* xs_hi, __bf16* xs_lo, int ldx, const int* frame_unit,
+                                                        const float* unit_dt, int n_act) {
     const int u = blockIdx.x;
     if (u >= U) return;
     const int c = threadIdx.x;
     if (c >= mel) return;
+    if (kUnitDt) {
+        const int un = frame_unit[u];
+        if (un >= n_act) return;
+        dt = unit_dt[un];
+    }
     const int rc = urow_c[u], ru = urow_u[u];
     const float pc = pred[(size_t)rc * ldp + c];
     float v = pc;
@@ -156,15 +171,21 @@ __global__ __launch_bounds__(128) void cfg_euler_kernel(float* xout /*[U][mel]*/
 //   s = 3: k3 = v(t0 + 2 dt/3, ..)    next input y0 + dt * (k1 - k2 + k3)
 //   s = 4: k4 = v(t0 + dt, ..)        y1 = y0 + (k1 + 3 (k2 + k3) + k4) * dt / 8
 // v as in cfg_euler_kernel.  Stages 1-3 keep k_s in their [U][mel] buffer and write the next stage's input only to the split-bf16 copy
-// of x (both branches); xstate holds y0 until stage 4 writes y1 there.  kFrameCfg as in cfg_euler_kernel.
-template <bool kFrameCfg>
+// of x (both branches); xstate holds y0 until stage 4 writes y1 there.  kFrameCfg and kUnitDt as in cfg_euler_kernel.
+template <bool kFrameCfg, bool kUnitDt = false>
 __global__ __launch_bounds__(128) void cfg_rk4_stage_kernel(float* xstate /*[U][mel]*/, int mel, int U, const float* pred, int ldp,
                                                             const int* urow_c, const int* urow_u, float cfg, const float* cfg_frame, float dt,
-                                                            int stage, float* k1, float* k2, float* k3, __bf16* xs_hi, __bf16* xs_lo, int ldx) {
+                                                            int stage, float* k1, float* k2, float* k3, __bf16* xs_hi, __bf16* xs_lo, int ldx,
+                                                            const int* frame_unit, const float* unit_dt, int n_act) {
     const int u = blockIdx.x;
     if (u >= U) return;
     const int c = threadIdx.x;
     if (c >= mel) return;
+    if (kUnitDt) {
+        const int un = frame_unit[u];
+        if (un >= n_act) return;
+        dt = unit_dt[un];
+    }
     const int rc = urow_c[u], ru = urow_u[u];
     const float pc = pred[(size_t)rc * ldp + c];
     float v = pc;
@@ -246,4 +267,12 @@ __global__ __launch_bounds__(128) void gather_rows_kernel(const float* src, int 
 __global__ __launch_bounds__(256) void set_time_token_kernel(float* h, int D, const int* seq_row0, const float* temb) {
     float* row = h + (size_t)seq_row0[blockIdx.x] * D;
     for (int c = threadIdx.x; c < D; c += 256) row[c] = temb[c];
+}
+
+// f5hip_cfm_sample_grids: the time token of every sequence from its own time point (row_tp of its first row): temb[row_tp[row0]]
+__global__ __launch_bounds__(256) void set_time_token_rows_kernel(float* h, int D, const int* seq_row0, const float* temb, const int* row_tp) {
+    const int r0 = seq_row0[blockIdx.x];
+    float* row = h + (size_t)r0 * D;
+    const float* src = temb + (size_t)row_tp[r0] * D;
+    for (int c = threadIdx.x; c < D; c += 256) row[c] = src[c];
 }

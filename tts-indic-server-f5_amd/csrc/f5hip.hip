@@ -17,6 +17,9 @@
 #include "gemm_launch.h"
 #include "host_util.h"
 
+// Time points one sampler call can evaluate: the rows of the modulation table `mod`, of the time embeddings `temb` and of the sinusoid staging
+static constexpr int kMaxTimePoints = 256;
+
 // =================================================================================================
 // DiT model
 // =================================================================================================
@@ -38,7 +41,8 @@ struct f5hip_dit {
     // per-handle settings (the process-wide setters are only their defaults)
     int attn_invariant = -1;          // f5hip_dit_set_attention_shape_invariant: -1 = follow f5hip_set_attention_shape_invariant
     ProfState* prof = nullptr;        // f5hip_dit_set_profiling: this handle's own HIP-event spans and totals (null: the process-wide state)
-    HostStage up_meta, up_time[2];    // pinned staging of the per-call uploads (row metadata; the two planes of the sinusoid table)
+    HostStage up_meta, up_time[2], up_grid;   // pinned staging of the per-call uploads (row metadata; the two planes of the sinusoid table;
+                                              // f5hip_cfm_sample_grids' unit tables)
     bool blk_f16 = false; // gemm_planes == 3: transformer-block GEMMs (QKV, out, FF1, FF2) take one fp16 plane per operand
     ParamStore params;
     bool finalized = false;
@@ -77,6 +81,14 @@ struct f5hip_dit {
     float* d_frame_cfg = nullptr;   // f5hip_cfm_sample_units: CFG strength per frame (its unit's), in `meta` behind the other arrays; else null
     int M = 0, n_seq = 0, n_frames = 0, max_len = 0;
     int Mc = 0, Rtot = 0;   // MMDiT: text-stream rows and all rows (= row pitch of the V^T buffer); Rtot == M otherwise
+    int row_c0 = 0;         // MMDiT: first row of the text stream (all audio rows of the layout; M may be a prefix of them: cfm_sample_grids)
+    std::vector<int> h_seq_row0, h_seqc_row0;   // layout of the last setup_sequences: first audio / text (MMDiT) row per sequence, then the end
+    // f5hip_cfm_sample_grids: d_row_tp != null -> the modulation consumers read row r's vectors from row d_row_tp[r] of `mod` (and UNetT's time
+    // token from temb[d_row_tp[row0]]); forward_step is then called with ti = 0.  grid_meta: row_unit [R], row_tp [R], frame_unit [U], the unit
+    // time-point table and the per-unit step sizes.
+    int* d_row_tp = nullptr;
+    int* grid_meta = nullptr;
+    size_t grid_cap = 0;
     int *d_j_row0 = nullptr, *d_j_len = nullptr, *d_j_kvlen = nullptr, *d_j_kv_row0 = nullptr, *d_j_kv2_row0 = nullptr, *d_j_kv2_len = nullptr;   // MMDiT joint attention: 2 n_seq pseudo-sequences
     bool any_masked = false;
     std::vector<int> h_seq_len;
@@ -137,7 +149,8 @@ void f5hip_dit_destroy(f5hip_dit* m) {
     dev_free(m->ws.ptr);
     dev_free(m->meta);
     delete m->prof;
-    m->up_meta.release(); m->up_time[0].release(); m->up_time[1].release();
+    dev_free(m->grid_meta);
+    m->up_meta.release(); m->up_time[0].release(); m->up_time[1].release(); m->up_grid.release();
     delete m;
 }
 
@@ -344,10 +357,11 @@ static int ensure_workspace(f5hip_dit* m, int rows_pad, int frames, int n_seq) {
             m->h = a.f32(R * D); m->h0 = a.f32(R * D); m->ce = a.f32(R * D); m->pred = a.f32(R * 128);
             m->te = a.f32(R * Td); m->ty = a.f32(R * 2 * Td); m->gx = a.f32(S * 2 * Td);
             m->rope_row_cos = a.f32(R * 32); m->rope_row_sin = a.f32(R * 32);
-            m->mod = a.f32((size_t)128 * m->n_adaln + 64); m->xstate = a.f32(U * c.mel_dim); m->xmid = a.f32(U * c.mel_dim); m->temb = a.f32((size_t)128 * D);
+            m->mod = a.f32((size_t)kMaxTimePoints * m->n_adaln + 64); m->xstate = a.f32(U * c.mel_dim); m->xmid = a.f32(U * c.mel_dim);
+            m->temb = a.f32((size_t)kMaxTimePoints * D);
             m->hn = a.plane2(R * D + 256); m->c1 = a.plane2(R * D + 256); m->ao = a.plane2(R * D); m->ff = a.plane2(R * F);
             m->xs = a.plane2(R * 128); m->tn = a.plane2(R * Td); m->tg = a.plane2(R * 2 * Td); m->act = a.plane2(R * (128 + m->td_pad));
-            m->sinp = a.plane2(128 * 256); m->t1 = a.plane2((size_t)128 * D); m->st = a.plane2((size_t)128 * D);
+            m->sinp = a.plane2(kMaxTimePoints * 256); m->t1 = a.plane2((size_t)kMaxTimePoints * D); m->st = a.plane2((size_t)kMaxTimePoints * D);
             m->skipbuf.resize(m->arch == 1 ? c.depth / 2 : 0);
             for (auto& sb : m->skipbuf) sb = a.plane2(R * 2 * D);   // [R][2 D]: the concatenated operand [x || skip] of the U-skip Linear, built in place
             // qk: +256 rows because the last query tile of the attention (up to 256 queries) may read (never store) past the padded rows
@@ -393,6 +407,7 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
     int* urow_c = seq_kvlen + S; int* urow_u = urow_c + U; int* fic = urow_u + U;
     int r0 = 0;
     m->any_masked = false;
+    m->h_seq_row0.assign(S + 1, 0); m->h_seqc_row0.assign(S + 1, rows_x);
     for (int r = 0; r < R; r++) { row_seq[r] = -1; row_token[r] = -1; row_frame[r] = -1; row_condframe[r] = -1; }
     for (int u = 0; u < U; u++) { urow_c[u] = -1; urow_u[u] = -1; fic[u] = frame_is_cond ? frame_is_cond[u] : 0; }
     m->max_len = 0;
@@ -418,6 +433,7 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
             (q.branch ? urow_u : urow_c)[q.frame0 + i] = r;
         }
         r0 += ceil_to(q.len + extra, 128);
+        m->h_seq_row0[s + 1] = r0;
     }
     int* jm = fic + U;   // MMDiT joint attention: 6 arrays of 2 S pseudo-sequences (2 s: audio queries of sequence s, 2 s + 1: its text queries)
     if (mm) {
@@ -442,6 +458,7 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
             }
             m->max_len = std::max(m->max_len, q.c_len);
             rc0 += ceil_to(q.c_len, 128);
+            m->h_seqc_row0[s + 1] = rc0;
         }
     }
     if (const int r_ = m->up_meta.upload(m->meta, hbuf.data(), sizeof(int) * hbuf.size(), st)) return r_;   // (pinned staging: no host sync)
@@ -457,13 +474,15 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
     // rotary factors per row of this layout (one load in the QKV epilogues instead of row_pos -> table)
     hipLaunchKernelGGL(rope_rows_kernel, dim3((R * 32 + 255) / 256), dim3(256), 0, st, m->d_row_pos, m->rope_cos, m->rope_sin, R, 4097, m->rope_row_cos, m->rope_row_sin);
     if (hipGetLastError() != hipSuccess) return fail(-7, "rope_rows_kernel launch");
-    m->M = rows_x; m->Mc = R - rows_x; m->Rtot = R; m->n_seq = S; m->n_frames = U;
+    m->M = rows_x; m->Mc = R - rows_x; m->Rtot = R; m->n_seq = S; m->n_frames = U; m->row_c0 = rows_x;
     return 0;
 }
 
 // -------------------------------------------------------------------------------------------------
 // launch helpers
 // -------------------------------------------------------------------------------------------------
+static Plane2 rows_from(const Plane2& p, size_t off) { return {p.hi + off, p.lo + off}; }
+
 static GemmArgs gemm_base(const Plane2& A, int lda, const PackedW& W, int M) {
     GemmArgs a;
     memset(&a, 0, sizeof(a));
@@ -476,8 +495,9 @@ static GemmArgs gemm_base(const Plane2& A, int lda, const PackedW& W, int M) {
 
 // f5hip_get_counter: gemm5 launches with RB 11 / RB 8 / 1 x 4 consumer layout (cb 8 or 12) / gemm3 wide-tile launches / conv5 launches /
 // gemm6 launches; then gemm6 by tile height (176 / 256 rows), gemm5 with cb 12, every gemm3 launch, every gemm.h launch by bn (64 / 128)
+// ... and dit_rows: the summed (audio) rows M of every backbone forward
 enum { CNT_GEMM5_RB11, CNT_GEMM5_RB8, CNT_GEMM5_WIDE, CNT_GEMM3_WIDE, CNT_CONV5, CNT_GEMM6, CNT_GEMM6_R176, CNT_GEMM6_R256, CNT_GEMM5_CB12,
-       CNT_GEMM3, CNT_GEMM_REG_BN64, CNT_GEMM_REG_BN128, CNT_COUNT };
+       CNT_GEMM3, CNT_GEMM_REG_BN64, CNT_GEMM_REG_BN128, CNT_DIT_ROWS, CNT_COUNT };
 static long long g_counters[CNT_COUNT] = {};
 
 // Kernel choice per GEMM (measured: profiles/r02_fillrate_microbench.txt, profiles/r01_gemm_microbench.txt):
@@ -501,7 +521,8 @@ static int run_gemm_n(int nsplit, int mp, GemmArgs& a, const PackedW& W, int epi
             g_counters[CNT_GEMM6]++;
             g_counters[rows6 == 176 ? CNT_GEMM6_R176 : CNT_GEMM6_R256]++;
         } else if (a.K % 64 == 0 && c5.rb) {
-            e = epi == EPI_QKV ? f5_launch_gemm5_qkv(a, c5.rb, c5.cb, np, st) : f5_launch_gemm5_generic(a, c5.rb, c5.cb, np, st);
+            e = epi == EPI_QKV ? f5_launch_gemm5_qkv(a, c5.rb, c5.cb, np, st)
+              : epi == EPI_GENERIC_ROWMUL ? f5_launch_gemm5_rowmul(a, c5.rb, c5.cb, np, st) : f5_launch_gemm5_generic(a, c5.rb, c5.cb, np, st);
             g_counters[c5.rb == 11 ? CNT_GEMM5_RB11 : CNT_GEMM5_RB8]++;
             if (c5.cb >= 8) g_counters[CNT_GEMM5_WIDE]++;
             if (c5.cb == 12) g_counters[CNT_GEMM5_CB12]++;
@@ -548,11 +569,21 @@ static LnArgs ln_args(const float* x, int ldx, int M, int D, const float* scale,
     return a;
 }
 
-static int run_ln(const LnArgs& a, hipStream_t st) {
+// row_mod: scale / shift per row (LnArgs::row_mod; f5hip_cfm_sample_grids)
+static int run_ln(const LnArgs& a, hipStream_t st, bool row_mod = false) {
     const int nv = (a.D + 255) / 256;
     dim3 grid((a.M + 3) / 4), blk(256);
     prof_begin(PROF_LN, st);
-    switch (nv) {
+    if (row_mod) {
+        switch (nv) {
+            case 1: hipLaunchKernelGGL((ln_kernel<1, true>), grid, blk, 0, st, a); break;
+            case 2: hipLaunchKernelGGL((ln_kernel<2, true>), grid, blk, 0, st, a); break;
+            case 3: hipLaunchKernelGGL((ln_kernel<3, true>), grid, blk, 0, st, a); break;
+            case 4: hipLaunchKernelGGL((ln_kernel<4, true>), grid, blk, 0, st, a); break;
+            case 5: case 6: hipLaunchKernelGGL((ln_kernel<6, true>), grid, blk, 0, st, a); break;
+            default: return fail(-7, "ln: D=%d unsupported", a.D);
+        }
+    } else switch (nv) {
         case 1: hipLaunchKernelGGL(ln_kernel<1>, grid, blk, 0, st, a); break;
         case 2: hipLaunchKernelGGL(ln_kernel<2>, grid, blk, 0, st, a); break;
         case 3: hipLaunchKernelGGL(ln_kernel<3>, grid, blk, 0, st, a); break;
@@ -570,7 +601,7 @@ static int run_ln(const LnArgs& a, hipStream_t st) {
 // instance (names in the order of tu_attn.hip's counters); name "reset" zeroes them all.
 extern "C" int f5hip_get_counter(const char* name, int64_t* value) {
     static const char* names[CNT_COUNT] = {"gemm5_rb11", "gemm5_rb8", "gemm5_wide", "gemm3_wide", "conv5", "gemm6", "gemm6_r176", "gemm6_r256",
-                                           "gemm5_cb12", "gemm3", "gemm_reg_bn64", "gemm_reg_bn128"};
+                                           "gemm5_cb12", "gemm3", "gemm_reg_bn64", "gemm_reg_bn128", "dit_rows"};
     static const char* attn_names[F5_ATTN_CNT_COUNT] = {"attn_bal8", "attn_nw8_deep", "attn_nw8", "attn_nw6_deep", "attn_nw6", "attn_nw4", "attn_seg2"};
     long long* attn = f5_attn_counters();
     if (!name) return fail(-1, "get_counter: null name");
@@ -596,8 +627,9 @@ static int precompute_text_and_ce(f5hip_dit* m, const float* cond_dev, hipStream
     if (m->arch == 2) {
         // MMDiT TextEmbedding (mmdit.py:37-52): embedding + absolute position table for the rows of the text stream (rows [M, M + Mc) of
         // every per-row buffer); step invariant, copied into the stream at the start of each forward.  Padding rows stay zero.
-        hipLaunchKernelGGL(text_gather_kernel, dim3(m->Mc), dim3(256), 0, st, m->text_emb, m->text_pos, D, m->Mc, m->d_row_token + M,
-                           m->d_row_pos + M, 1, m->te + (size_t)M * D, D, 1023);
+        const int C0 = m->row_c0;
+        hipLaunchKernelGGL(text_gather_kernel, dim3(m->Mc), dim3(256), 0, st, m->text_emb, m->text_pos, D, m->Mc, m->d_row_token + C0,
+                           m->d_row_pos + C0, 1, m->te + (size_t)C0 * D, D, 1023);
     } else {
         hipLaunchKernelGGL(text_gather_kernel, dim3(M), dim3(256), 0, st, m->text_emb, m->text_pos, Td, M, m->d_row_token,
                            m->d_row_pos, c.conv_layers > 0 ? 1 : 0, m->te, Td, 4095);
@@ -643,13 +675,15 @@ static int precompute_text_and_ce(f5hip_dit* m, const float* cond_dev, hipStream
     return 0;
 }
 
-// time embedding + every AdaLN modulation vector for all steps at once (they depend on t only)
+// time embedding + every AdaLN modulation vector for all steps at once (they depend on t only).  The GEMM chain runs once per block of 128
+// time points over 128 padded rows, so a time point's vectors come out of the same kernels whichever block it sits in.
 static int precompute_time(f5hip_dit* m, const float* t_host, int n_t, hipStream_t st) {
     const f5hip_dit_config& c = m->cfg;
     const int D = c.dim;
-    if (n_t > 128) return fail(-8, "at most 128 time points per call (got %d)", n_t);
+    if (n_t > kMaxTimePoints) return fail(-8, "at most %d time points per call (got %d)", kMaxTimePoints, n_t);
+    const int t_pad = ceil_to(n_t, 128);
     // SinusPositionEmbedding (F/model/modules.py:154-161) on the host: the table is n_t x 256
-    std::vector<uint16_t> hi((size_t)128 * 256, 0), lo((size_t)128 * 256, 0);
+    std::vector<uint16_t> hi((size_t)t_pad * 256, 0), lo((size_t)t_pad * 256, 0);
     const float emb = logf(10000.0f) / (float)(128 - 1);
     for (int i = 0; i < n_t; i++)
         for (int k = 0; k < 128; k++) {
@@ -661,21 +695,24 @@ static int precompute_time(f5hip_dit* m, const float* t_host, int n_t, hipStream
         }
     CK(m->up_time[0].upload(m->sinp.hi, hi.data(), hi.size() * 2, st));
     CK(m->up_time[1].upload(m->sinp.lo, lo.data(), lo.size() * 2, st));
-    GemmArgs g1 = gemm_base(m->sinp, 256, m->time1, n_t);
-    g1.act = ACT_SILU; g1.out_hi = m->t1.hi; g1.out_lo = m->t1.lo; g1.ldob = D;
-    int r = run_gemm(m, g1, m->time1, EPI_GENERIC, false, 128, st, 128);
-    GemmArgs g2 = gemm_base(m->t1, D, m->time2, n_t);
-    if (m->arch == 1) {
-        g2.out_f32 = m->temb; g2.ldo = D;   // UNetT: the raw time embedding is prepended as a token (unett.py:184)
-        if (!r) r = run_gemm(m, g2, m->time2, EPI_GENERIC, false, 128, st, 128);
-        return r;
+    for (int t0 = 0; t0 < n_t; t0 += 128) {
+        const int nb = std::min(128, n_t - t0);
+        GemmArgs g1 = gemm_base(rows_from(m->sinp, (size_t)t0 * 256), 256, m->time1, nb);
+        g1.act = ACT_SILU; g1.out_hi = m->t1.hi + (size_t)t0 * D; g1.out_lo = m->t1.lo + (size_t)t0 * D; g1.ldob = D;
+        CK(run_gemm(m, g1, m->time1, EPI_GENERIC, false, 128, st, 128));
+        GemmArgs g2 = gemm_base(rows_from(m->t1, (size_t)t0 * D), D, m->time2, nb);
+        if (m->arch == 1) {
+            g2.out_f32 = m->temb + (size_t)t0 * D; g2.ldo = D;   // UNetT: the raw time embedding is prepended as a token (unett.py:184)
+            CK(run_gemm(m, g2, m->time2, EPI_GENERIC, false, 128, st, 128));
+            continue;
+        }
+        g2.act = ACT_SILU; g2.out_hi = m->st.hi + (size_t)t0 * D; g2.out_lo = m->st.lo + (size_t)t0 * D; g2.ldob = D;   // silu(t_emb): the only form AdaLN consumes
+        CK(run_gemm(m, g2, m->time2, EPI_GENERIC, false, 128, st, 128));
+        GemmArgs g3 = gemm_base(rows_from(m->st, (size_t)t0 * D), D, m->adaln, nb);
+        g3.out_f32 = m->mod + (size_t)t0 * m->n_adaln; g3.ldo = m->n_adaln;
+        CK(run_gemm(m, g3, m->adaln, EPI_GENERIC, false, 128, st, 128));
     }
-    g2.act = ACT_SILU; g2.out_hi = m->st.hi; g2.out_lo = m->st.lo; g2.ldob = D;   // silu(t_emb): the only form AdaLN consumes
-    if (!r) r = run_gemm(m, g2, m->time2, EPI_GENERIC, false, 128, st, 128);
-    GemmArgs g3 = gemm_base(m->st, D, m->adaln, n_t);
-    g3.out_f32 = m->mod; g3.ldo = m->n_adaln;
-    if (!r) r = run_gemm(m, g3, m->adaln, EPI_GENERIC, false, 128, st, 128);
-    return r;
+    return 0;
 }
 
 // rotary operands of a QKV launch over rows row_off ..: the per-row tables of the current layout (one load per row in the epilogue)
@@ -688,14 +725,16 @@ static void set_rope(GemmArgs& q, const f5hip_dit* m, int row_off) {
 // masked sequences (row_keep; the audio stream only).
 struct Stream { int row0, rows; const BlockWeights* w; bool keep; };
 static Stream audio_stream(const f5hip_dit* m) { return {0, m->M, &m->blk, true}; }
-static Plane2 rows_from(const Plane2& p, size_t off) { return {p.hi + off, p.lo + off}; }
 
 // h += gate * (A W^T + b) over the stream's rows (gate null: none)
+// (d_row_tp set: the gate of each row from its own modulation row -- the per-row-multiplier epilogue)
 static int block_residual(f5hip_dit* m, const Stream& s, const Plane2& A, int lda, const PackedW& W, const float* gate, const int* keep, hipStream_t st) {
     const int D = m->cfg.dim;
     GemmArgs g = gemm_base(A, lda, W, s.rows);
     g.mul = gate; g.res = m->h + (size_t)s.row0 * D; g.ldres = D; g.out_f32 = m->h + (size_t)s.row0 * D; g.ldo = D; g.row_keep = keep;
-    return run_gemm(m, g, W, EPI_GENERIC, false, 64, st, s.rows);
+    const bool per_row = gate && m->d_row_tp;
+    if (per_row) { g.row_mod = m->d_row_tp + s.row0; g.mod_ld = m->n_adaln; }
+    return run_gemm(m, g, W, per_row ? EPI_GENERIC_ROWMUL : EPI_GENERIC, false, 64, st, s.rows);
 }
 
 // block l's QKV projection of the stream's rows hn: rotary q | k into qk, V^T into vt (rows of the current layout)
@@ -728,7 +767,8 @@ static int run_adaln(f5hip_dit* m, const Stream& s, const float* shift, const fl
     const int D = m->cfg.dim;
     LnArgs ln = ln_args(m->h + (size_t)s.row0 * D, D, s.rows, D, scale, shift, 1.0f, 1e-6f);
     ln.out_hi = m->hn.hi + (size_t)s.row0 * D; ln.out_lo = m->hn.lo + (size_t)s.row0 * D; ln.ldo = D; ln.f16_out = f16 ? 1 : 0;
-    return run_ln(ln, st);
+    if (m->d_row_tp) { ln.row_mod = m->d_row_tp + s.row0; ln.mod_ld = m->n_adaln; }   // (scale / shift per row)
+    return run_ln(ln, st, m->d_row_tp != nullptr);
 }
 
 static int launch_attention(f5hip_dit* m, hipStream_t st) {
@@ -758,7 +798,8 @@ static int forward_unett_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t 
     const int D = c.dim, M = m->M;
     const Stream x = audio_stream(m);
     prof_begin(PROF_OTHER, st);
-    hipLaunchKernelGGL(set_time_token_kernel, dim3(m->n_seq), dim3(256), 0, st, m->h, D, m->d_seq_row0, m->temb + (size_t)ti * D);
+    if (m->d_row_tp) hipLaunchKernelGGL(set_time_token_rows_kernel, dim3(m->n_seq), dim3(256), 0, st, m->h, D, m->d_seq_row0, m->temb, (const int*)m->d_row_tp);
+    else hipLaunchKernelGGL(set_time_token_kernel, dim3(m->n_seq), dim3(256), 0, st, m->h, D, m->d_seq_row0, m->temb + (size_t)ti * D);
     prof_end(PROF_OTHER, st);
     CKL("set_time_token");
     const int nb = n_blocks < 0 ? c.depth : n_blocks;
@@ -811,11 +852,11 @@ static int forward_unett_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t 
 // context-pre-only: the text stream is only normalised and projected to q / k / v, then dropped.
 static int forward_mmdit_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {
     const f5hip_dit_config& c = m->cfg;
-    const int D = c.dim, M = m->M, Mc = m->Mc;
+    const int D = c.dim, M = m->M, Mc = m->Mc, C0 = m->row_c0;   // (C0 == M but in a cfm_sample_grids forward over a prefix of the units)
     const float* mod = m->mod + (size_t)ti * m->n_adaln;
-    const Stream x = audio_stream(m), tx{M, Mc, &m->blk_c, false};
+    const Stream x = audio_stream(m), tx{C0, Mc, &m->blk_c, false};
     // the text stream starts every forward from its step-invariant embedding
-    if (hipMemcpyAsync(m->h + (size_t)M * D, m->te + (size_t)M * D, sizeof(float) * (size_t)Mc * D, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(-6, "MMDiT: text stream copy");
+    if (hipMemcpyAsync(m->h + (size_t)C0 * D, m->te + (size_t)C0 * D, sizeof(float) * (size_t)Mc * D, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(-6, "MMDiT: text stream copy");
     const int nb = n_blocks < 0 ? c.depth : n_blocks;
     for (int l = 0; l < nb; l++) {
         const bool last = l == c.depth - 1;
@@ -855,6 +896,7 @@ static int forward_step(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {
     const f5hip_dit_config& c = m->cfg;
     const int D = c.dim, M = m->M;
     const float* mod = m->mod + (size_t)ti * m->n_adaln;
+    g_counters[CNT_DIT_ROWS] += M;
     // input projection: x part + precomputed cond/text part
     GemmArgs gi = gemm_base(m->xs, 128, m->wx, M);
     gi.bias = nullptr; gi.res = m->ce; gi.ldres = D; gi.out_f32 = m->h0; gi.ldo = D;
@@ -991,20 +1033,22 @@ static void launch_cfg_euler(const f5hip_dit* m, int f0, hipStream_t st, float* 
     const int mel = m->cfg.mel_dim;
     if (m->d_frame_cfg)
         hipLaunchKernelGGL(cfg_euler_kernel<true>, dim3(f0), dim3(128), 0, st, xout, xbase, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                           0.0f, (const float*)m->d_frame_cfg, dt, m->xs.hi, m->xs.lo, 128);
+                           0.0f, (const float*)m->d_frame_cfg, dt, m->xs.hi, m->xs.lo, 128, (const int*)nullptr, (const float*)nullptr, 0);
     else
         hipLaunchKernelGGL(cfg_euler_kernel<false>, dim3(f0), dim3(128), 0, st, xout, xbase, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                           cfg, (const float*)nullptr, dt, m->xs.hi, m->xs.lo, 128);
+                           cfg, (const float*)nullptr, dt, m->xs.hi, m->xs.lo, 128, (const int*)nullptr, (const float*)nullptr, 0);
 }
 
 static void launch_cfg_rk4(f5hip_dit* m, int f0, hipStream_t st, float cfg, float dt, int stage) {
     const int mel = m->cfg.mel_dim;
     if (m->d_frame_cfg)
         hipLaunchKernelGGL(cfg_rk4_stage_kernel<true>, dim3(f0), dim3(128), 0, st, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                           0.0f, (const float*)m->d_frame_cfg, dt, stage, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128);
+                           0.0f, (const float*)m->d_frame_cfg, dt, stage, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128,
+                           (const int*)nullptr, (const float*)nullptr, 0);
     else
         hipLaunchKernelGGL(cfg_rk4_stage_kernel<false>, dim3(f0), dim3(128), 0, st, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                           cfg, (const float*)nullptr, dt, stage, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128);
+                           cfg, (const float*)nullptr, dt, stage, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128,
+                           (const int*)nullptr, (const float*)nullptr, 0);
 }
 
 // f5hip_cfm_sample_masked (cfg_unit == null: one strength for the call) and f5hip_cfm_sample_units (cfg_unit: one strength per unit)
@@ -1051,6 +1095,7 @@ static int cfm_sample_impl(f5hip_dit* m, int32_t n_utt, const int32_t* dur, cons
     CKL("split x");
     CK(precompute_text_and_ce(m, cond_dev, st));
     if (m->ode_method == 0) {
+        if (steps > 128) return fail(-8, "at most 128 time points per call (got %d)", steps);
         CK(precompute_time(m, t_grid, steps, st));
         for (int i = 0; i < steps; i++) {
             CK(forward_step(m, i, -1, st));
@@ -1125,6 +1170,184 @@ int f5hip_cfm_sample_units(f5hip_dit* m, int32_t n_utt, const int32_t* dur, cons
                            const float* cfg_strength, float* out_dev, void* stream) {
     if (!cfg_strength) return fail(-1, "cfm_sample_units: cfg_strength is null");
     return cfm_sample_impl(m, n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, t_grid, steps, 0.0f, cfg_strength, out_dev, stream);
+}
+
+// -------------------------------------------------------------------------------------------------
+// f5hip_cfm_sample_grids: one time grid and one CFG strength per unit
+// -------------------------------------------------------------------------------------------------
+// The CFG combine of one ODE stage with per-frame strengths and per-unit steps (unit_dt: one value per unit in layout order); the frames of
+// units >= n_act are left as they are.  stage 0: Euler form (xout = xbase + dt v), 1..4: RK4 stage.
+static void launch_cfg_grid(const f5hip_dit* m, int f0, hipStream_t st, float* xout, const float* xbase, const int* frame_unit, const float* unit_dt,
+                            int n_act, int stage) {
+    const int mel = m->cfg.mel_dim;
+    if (stage == 0)
+        hipLaunchKernelGGL((cfg_euler_kernel<true, true>), dim3(f0), dim3(128), 0, st, xout, xbase, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
+                           0.0f, (const float*)m->d_frame_cfg, 0.0f, m->xs.hi, m->xs.lo, 128, frame_unit, unit_dt, n_act);
+    else
+        hipLaunchKernelGGL((cfg_rk4_stage_kernel<true, true>), dim3(f0), dim3(128), 0, st, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
+                           0.0f, (const float*)m->d_frame_cfg, 0.0f, stage, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128, frame_unit, unit_dt, n_act);
+}
+
+// Restores the handle's full layout and per-call modulation after a cfm_sample_grids call, however it ends.
+struct GridScope {
+    f5hip_dit* m;
+    ~GridScope() { m->d_row_tp = nullptr; m->M = m->row_c0; m->Mc = m->Rtot - m->row_c0; m->n_seq = (int)m->h_seq_row0.size() - 1; }
+};
+
+// Units are laid out by step count, descending (stable; a unit's conditional and unconditional sequences adjacent), so the units still
+// stepping at iteration i are a prefix of the layout: the forwards of iteration i run over the audio rows [0, M_i) (and MMDiT's text rows
+// [row_c0, row_c0 + Mc_i)) of those units only, and the CFG kernels leave the frames of the finished units alone.  Every unit's time points
+// (Euler t_i; midpoint t_i, t_i + dt_i / 2; RK4 t_i, t_i + dt_i / 3, t_i + 2 dt_i / 3, t_{i+1}, rounded as cfm_sample_impl rounds them) go
+// through one precompute_time over their union (equal fp32 values once); before each forward row_tp_kernel gives every row the time point of
+// its unit, and the modulation consumers read their vectors per row.
+int f5hip_cfm_sample_grids(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
+                           const int32_t* text, int32_t nt_max, const float* y0_dev, const int32_t* steps, const float* t_grids,
+                           const float* cfg_strength, float* out_dev, void* stream) {
+    if (!m || !m->finalized) return fail(-1, "model not finalized");
+    if (n_utt <= 0 || !dur || !cond_dev || !cond_mask || !text || !y0_dev || !steps || !t_grids || !cfg_strength || !out_dev)
+        return fail(-1, "cfm_sample_grids: bad argument");
+    std::vector<size_t> g0(n_utt);
+    std::vector<int> fo(n_utt + 1, 0);   // first frame of every unit in the caller's packed arrays
+    size_t off = 0;
+    for (int u = 0; u < n_utt; u++) {
+        if (steps[u] < 1) return fail(-1, "cfm_sample_grids: steps[%d] = %d (need >= 1)", u, steps[u]);
+        if (dur[u] <= 0 || dur[u] > 4096) return fail(-1, "dur[%d] = %d out of range", u, dur[u]);
+        const int kv = kv_len ? kv_len[u] : dur[u];
+        if (kv <= 0 || kv > dur[u]) return fail(-1, "kv_len[%d] = %d out of range (1..%d)", u, kv, dur[u]);
+        g0[u] = off;
+        off += (size_t)steps[u] + 1;
+        fo[u + 1] = fo[u] + dur[u];
+    }
+    bool one_grid = true;
+    for (int u = 1; u < n_utt && one_grid; u++)
+        one_grid = steps[u] == steps[0] && !memcmp(t_grids + g0[u], t_grids, sizeof(float) * ((size_t)steps[0] + 1));
+    if (one_grid)   // one grid for all: f5hip_cfm_sample_units' call, kernels and results
+        return cfm_sample_impl(m, n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, t_grids, steps[0], 0.0f, cfg_strength, out_dev, stream);
+
+    const int n = n_utt, method = m->ode_method, per = method == 0 ? 1 : (method == 1 ? 2 : 4);   // forwards per step
+    std::vector<int> order(n);
+    for (int u = 0; u < n; u++) order[u] = u;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return steps[a] > steps[b]; });
+    const int max_steps = steps[order[0]], n_fwd = max_steps * per;
+    // time points: utp[f][k] = point of forward f for the unit at layout position k (0 once its steps are done); udt[0][i][k] = dt_i, udt[1][i][k] = dt_i / 2
+    std::vector<float> pts;
+    std::map<uint32_t, int> pt_index;
+    auto point = [&](float t) {
+        uint32_t bits;
+        memcpy(&bits, &t, sizeof(bits));
+        auto it = pt_index.find(bits);
+        if (it != pt_index.end()) return it->second;
+        pt_index[bits] = (int)pts.size();
+        pts.push_back(t);
+        return (int)pts.size() - 1;
+    };
+    std::vector<int> utp((size_t)n_fwd * n, 0);
+    std::vector<float> udt((size_t)2 * max_steps * n, 0.0f);
+    {
+#pragma clang fp contract(off)
+        for (int k = 0; k < n; k++) {
+            const float* tg = t_grids + g0[order[k]];
+            for (int i = 0; i < steps[order[k]]; i++) {
+                const float dt = tg[i + 1] - tg[i];
+                udt[(size_t)i * n + k] = dt;
+                udt[(size_t)(max_steps + i) * n + k] = 0.5f * dt;
+                int* f = &utp[(size_t)i * per * n + k];
+                if (method == 0) {
+                    f[0] = point(tg[i]);
+                } else if (method == 1) {
+                    const float half = 0.5f * dt;
+                    f[0] = point(tg[i]);
+                    f[n] = point(tg[i] + half);
+                } else {   // stage times in fp32 as cfm_sample_impl (and torch) round t0 + dt * (1/3) and t0 + dt * (2/3)
+                    f[0] = point(tg[i]);
+                    f[n] = point(tg[i] + dt * (1.0f / 3.0f));
+                    f[2 * n] = point(tg[i] + dt * (2.0f / 3.0f));
+                    f[3 * n] = point(tg[i + 1]);
+                }
+            }
+        }
+    }
+    if ((int)pts.size() > kMaxTimePoints)
+        return fail(-8, "cfm_sample_grids: the units' grids need %d distinct time points, at most %d per call", (int)pts.size(), kMaxTimePoints);
+
+    ProfScope prof_scope(m->prof);
+    hipStream_t st = (hipStream_t)stream;
+    const int mel = m->cfg.mel_dim, U = fo[n];
+    std::vector<float> frame_cfg(U);
+    std::vector<int> frame_unit(U), seq_unit, seq_end(n);   // seq_end[k]: sequences of the units at layout positions 0..k
+    std::vector<SeqDesc> seqs;
+    m->h_seq_len.clear();
+    for (int k = 0; k < n; k++) {
+        const int u = order[k], kv = kv_len ? kv_len[u] : dur[u];
+        int c_len = nt_max;   // (as cfm_sample_impl)
+        if (!kv_len) { c_len = 0; while (c_len < nt_max && text[(size_t)u * nt_max + c_len] != -1) c_len++; }
+        const float cfg_u = cfg_strength[u];
+        const bool use_cfg = !(cfg_u < 1e-5f);
+        for (int f = fo[u]; f < fo[u + 1]; f++) { frame_cfg[f] = use_cfg ? cfg_u : 0.0f; frame_unit[f] = k; }
+        for (int b = 0; b < (use_cfg ? 2 : 1); b++) {
+            seqs.push_back({dur[u], kv, fo[u], u, b, b, b});
+            seqs.back().c_len = std::max(c_len, 1);
+            seq_unit.push_back(k);
+            m->h_seq_len.push_back(dur[u]);
+        }
+        seq_end[k] = (int)seqs.size();
+    }
+    CK(setup_sequences(m, seqs, U, text, nt_max, cond_mask, st, frame_cfg.data()));
+    GridScope scope{m};
+    const int R = m->Rtot, S = (int)seqs.size();
+    // grid_meta: row_unit [R] | frame_unit [U] | utp | udt (floats) -- uploaded -- then row_tp [R]
+    const size_t n_up = (size_t)R + U + utp.size() + udt.size(), need = n_up + R;
+    if (need > m->grid_cap) {
+        dev_free(m->grid_meta);
+        m->grid_cap = 0;
+        if (hipMalloc((void**)&m->grid_meta, sizeof(int) * need) != hipSuccess) { m->grid_meta = nullptr; return fail(-5, "hipMalloc grid tables"); }
+        m->grid_cap = need;
+    }
+    std::vector<int> hb(n_up, 0);
+    for (int s = 0; s < S; s++) {
+        for (int r = m->h_seq_row0[s]; r < m->h_seq_row0[s + 1]; r++) hb[r] = seq_unit[s];
+        for (int r = m->h_seqc_row0[s]; r < m->h_seqc_row0[s + 1]; r++) hb[r] = seq_unit[s];
+    }
+    memcpy(&hb[R], frame_unit.data(), sizeof(int) * U);
+    memcpy(&hb[(size_t)R + U], utp.data(), sizeof(int) * utp.size());
+    memcpy(&hb[(size_t)R + U + utp.size()], udt.data(), sizeof(float) * udt.size());
+    CK(m->up_grid.upload(m->grid_meta, hb.data(), sizeof(int) * n_up, st));
+    const int* d_row_unit = m->grid_meta;
+    const int* d_frame_unit = d_row_unit + R;
+    const int* d_utp = d_frame_unit + U;
+    const float* d_udt = reinterpret_cast<const float*>(d_utp + utp.size());
+    int* d_row_tp = m->grid_meta + n_up;
+
+    if (hipMemcpyAsync(m->xstate, y0_dev, sizeof(float) * (size_t)U * mel, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(-6, "y0 copy");
+    hipLaunchKernelGGL(split_rows_kernel, dim3(m->M), dim3(256), 0, st, m->xstate, mel, mel, m->M, m->d_row_frame, m->xs.hi, m->xs.lo, 128, 0);
+    CKL("split x");
+    CK(precompute_text_and_ce(m, cond_dev, st));
+    CK(precompute_time(m, pts.data(), (int)pts.size(), st));
+    m->d_row_tp = d_row_tp;
+    int n_act = n;
+    for (int i = 0; i < max_steps; i++) {
+        while (steps[order[n_act - 1]] <= i) n_act--;   // units whose steps are done leave the layout's tail
+        const int s_act = seq_end[n_act - 1];
+        m->M = m->h_seq_row0[s_act]; m->Mc = m->h_seqc_row0[s_act] - m->row_c0; m->n_seq = s_act;
+        const float* dt = d_udt + (size_t)i * n;
+        for (int s = 0; s < per; s++) {
+            prof_begin(PROF_OTHER, st);
+            hipLaunchKernelGGL(row_tp_kernel, dim3((R + 255) / 256), dim3(256), 0, st, d_row_unit, d_utp + ((size_t)i * per + s) * n, R, d_row_tp);
+            prof_end(PROF_OTHER, st);
+            CKL("row_tp");
+            CK(forward_step(m, 0, -1, st));
+            prof_begin(PROF_OTHER, st);
+            if (method == 0) launch_cfg_grid(m, U, st, m->xstate, m->xstate, d_frame_unit, dt, n_act, 0);
+            else if (method == 1 && s == 0) launch_cfg_grid(m, U, st, m->xmid, m->xstate, d_frame_unit, d_udt + (size_t)(max_steps + i) * n, n_act, 0);
+            else if (method == 1) launch_cfg_grid(m, U, st, m->xstate, m->xstate, d_frame_unit, dt, n_act, 0);
+            else launch_cfg_grid(m, U, st, nullptr, nullptr, d_frame_unit, dt, n_act, s + 1);
+            prof_end(PROF_OTHER, st);
+            CKL("cfg (grids)");
+        }
+    }
+    hipLaunchKernelGGL(final_select_kernel, dim3(U), dim3(128), 0, st, m->xstate, cond_dev, m->d_frame_is_cond, mel, U, out_dev);
+    CKL("final_select");
+    return 0;
 }
 
 #include "vocos.h"

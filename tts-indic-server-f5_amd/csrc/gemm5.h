@@ -265,7 +265,8 @@ F5_DEVICE f32x4 g5_epi_value(f32x4 acc, f32x4 bias, f32x4 mul, f32x4 res, bool z
 // Work unit = one group of 4 rows x the tile's NPAN panels of 64 columns (lane -> row lane >> 4, columns 4 (lane & 15) .. + 3 of each
 // panel); groups are dealt round-robin over the 8 waves; the loop is rolled, the next group's residual is loaded before the current
 // group is finished.
-template <int ACT, bool RES, bool OUTF, int OUTS, bool GUARD, int RB, int CB, int NST, typename WriteSlab>
+// ROWMUL: the multiplier of each row from its own modulation row (EPI_GENERIC_ROWMUL), loaded with the row group.
+template <int ACT, bool RES, bool OUTF, int OUTS, bool GUARD, int RB, int CB, int NST, typename WriteSlab, bool ROWMUL = false>
 F5_DEVICE void g5_generic_tail(const GemmArgs& p, const float* slab, int m0, int n0, int wave, int lane, WriteSlab write_slab) {
     using C = Gemm5Cfg<RB, CB, NST>;
     constexpr int NPAN = C::NPAN, NG = RB * 4;                 // row groups of the tile
@@ -279,7 +280,7 @@ F5_DEVICE void g5_generic_tail(const GemmArgs& p, const float* slab, int m0, int
         bv[pn] = (f32x4){0.f, 0.f, 0.f, 0.f};
         mv[pn] = (f32x4){1.f, 1.f, 1.f, 1.f};
         if (p.bias && nok[pn]) bv[pn] = *reinterpret_cast<const f32x4*>(p.bias + n);
-        if (p.mul && nok[pn]) mv[pn] = *reinterpret_cast<const f32x4*>(p.mul + n);
+        if (!ROWMUL && p.mul && nok[pn]) mv[pn] = *reinterpret_cast<const f32x4*>(p.mul + n);
     }
     f32x4 rs[RES ? NPAN : 1], rn[RES ? NPAN : 1];
     auto load_res = [&](int g, f32x4 (&dst)[RES ? NPAN : 1]) {
@@ -300,6 +301,12 @@ F5_DEVICE void g5_generic_tail(const GemmArgs& p, const float* slab, int m0, int
         const int rl = g * 4 + r_in, row = m0 + rl;
         int keep = 1;
         if (GUARD && p.row_keep && row < p.M) keep = p.row_keep[row];
+        if (ROWMUL) {
+            const float* mrow = (!GUARD || row < p.M) ? p.mul + (size_t)p.row_mod[row] * p.mod_ld : nullptr;
+#pragma unroll
+            for (int pn = 0; pn < NPAN; pn++)
+                mv[pn] = mrow && nok[pn] ? *reinterpret_cast<const f32x4*>(mrow + n0 + pn * 64 + c4) : (f32x4){1.f, 1.f, 1.f, 1.f};
+        }
 #pragma unroll
         for (int pn = 0; pn < NPAN; pn++) {
             const int n = n0 + pn * 64 + c4;
@@ -324,11 +331,13 @@ F5_DEVICE void g5_generic_tail(const GemmArgs& p, const float* slab, int m0, int
     }
 }
 
-template <int ACT, bool GUARD, int RB, int CB, int NST, typename WriteSlab>
+template <int ACT, bool GUARD, int RB, int CB, int NST, typename WriteSlab, bool ROWMUL = false>
 F5_DEVICE void g5_generic_variants(const GemmArgs& p, const float* slab, int m0, int n0, int wave, int lane, WriteSlab ws) {
     const bool res = p.res != nullptr, outf = p.out_f32 != nullptr, outs = p.out_hi != nullptr;
     // the (residual, fp32 out, 16-bit out) combinations in use on the path: same table as epi_generic_rows_g (gemm_epilogue.h)
-    if (ACT == ACT_NONE) {
+    if constexpr (ROWMUL) {
+        g5_generic_tail<ACT_NONE, true, true, 0, GUARD, RB, CB, NST, WriteSlab, true>(p, slab, m0, n0, wave, lane, ws);
+    } else if (ACT == ACT_NONE) {
         if (res) {
             if (outf && outs) g5_generic_tail<ACT, true, true, 1, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
             else if (outf) g5_generic_tail<ACT, true, true, 0, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
@@ -348,10 +357,15 @@ F5_DEVICE void g5_generic_variants(const GemmArgs& p, const float* slab, int m0,
     }
 }
 
-template <int RB, int CB, int NST, typename WriteSlab>
+template <int RB, int CB, int NST, typename WriteSlab, bool ROWMUL = false>
 F5_DEVICE void g5_generic_epilogue(const GemmArgs& p, const float* slab, int m0, int n0, int wave, int lane, WriteSlab ws) {
     // workgroup-uniform: interior tile without per-row special cases
     const bool interior = m0 + RB * 16 <= p.M && n0 + CB * 16 <= p.N && !p.row_keep;
+    if constexpr (ROWMUL) {
+        if (interior) g5_generic_variants<ACT_NONE, false, RB, CB, NST, WriteSlab, true>(p, slab, m0, n0, wave, lane, ws);
+        else g5_generic_variants<ACT_NONE, true, RB, CB, NST, WriteSlab, true>(p, slab, m0, n0, wave, lane, ws);
+        return;
+    }
 #define G5_ACT(A)                                                                                 \
     if (interior) g5_generic_variants<A, false, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);   \
     else g5_generic_variants<A, true, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
@@ -556,6 +570,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         g5_generic_epilogue<RB, CB, NST>(p, slab, m0, n0, wave, lane, [&]() {
             if (wave < 4) g5_write_slab<RB, CB, NST, WR, MRB, MCB, true, true>(acc, slab, rb0, nrb, cb0, lane, nullptr);
         });
+    } else if constexpr (EPI == EPI_GENERIC_ROWMUL) {
+        auto ws = [&]() {
+            if (wave < 4) g5_write_slab<RB, CB, NST, WR, MRB, MCB, true, true>(acc, slab, rb0, nrb, cb0, lane, nullptr);
+        };
+        g5_generic_epilogue<RB, CB, NST, decltype(ws), true>(p, slab, m0, n0, wave, lane, ws);
     } else if (swap) {
         // Q / K tile (possibly with V blocks behind the K | V boundary): row-major slab, rolled row phase; then the V blocks, if any
         const int f_lo = max(0, 2 * p.D - n0);                     // first V column of this tile (>= BN: none; 0: an all-V tile of a W-direct kernel)

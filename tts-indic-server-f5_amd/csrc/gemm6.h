@@ -216,7 +216,8 @@ F5_DEVICE void g6_kloop(const GemmArgs& p, char* smem, unsigned lds0, int m0, in
 // (Through the slab, four quarters of [write | barrier | row phase | barrier], the epilogue took 13-17 us of a 39-43 us tile:
 // profiles/r03_gemm6_stamps_slab_epilogue.txt.)
 // n_blk = row blocks of this wave that belong to the tile (RBW, or one fewer for the second group of a 176-row tile)
-template <int ACT, bool RES, bool OUTF, int OUTS, bool GUARD, int RBW>
+// ROWMUL: the multiplier of each row from its own modulation row (EPI_GENERIC_ROWMUL), loaded with the row block.
+template <int ACT, bool RES, bool OUTF, int OUTS, bool GUARD, int RBW, bool ROWMUL = false>
 F5_DEVICE void g6_direct_tail(const GemmArgs& p, f32x4 (&acc)[RBW][4], int m_w, int n_w, int n_blk, int lane) {
     const int fr = lane & 15, fq = lane >> 4;
     f32x4 bv[4], mv[4];
@@ -228,7 +229,7 @@ F5_DEVICE void g6_direct_tail(const GemmArgs& p, f32x4 (&acc)[RBW][4], int m_w, 
         bv[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
         mv[j] = (f32x4){1.f, 1.f, 1.f, 1.f};
         if (p.bias && nok[j]) bv[j] = *reinterpret_cast<const f32x4*>(p.bias + n);
-        if (p.mul && nok[j]) mv[j] = *reinterpret_cast<const f32x4*>(p.mul + n);
+        if (!ROWMUL && p.mul && nok[j]) mv[j] = *reinterpret_cast<const f32x4*>(p.mul + n);
     }
     f32x4 rs[RES ? 4 : 1], rn[RES ? 4 : 1];
     auto load_res = [&](int i, f32x4 (&dst)[RES ? 4 : 1]) {
@@ -248,6 +249,12 @@ F5_DEVICE void g6_direct_tail(const GemmArgs& p, f32x4 (&acc)[RBW][4], int m_w, 
         const int row = m_w + i * 16 + fr;
         int keep = 1;
         if (GUARD && p.row_keep && row < p.M) keep = p.row_keep[row];
+        if (ROWMUL) {
+            const float* mrow = (!GUARD || row < p.M) ? p.mul + (size_t)p.row_mod[row] * p.mod_ld : nullptr;
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                mv[j] = mrow && nok[j] ? *reinterpret_cast<const f32x4*>(mrow + n_w + j * 16 + fq * 4) : (f32x4){1.f, 1.f, 1.f, 1.f};
+        }
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int n = n_w + j * 16 + fq * 4;
@@ -272,11 +279,13 @@ F5_DEVICE void g6_direct_tail(const GemmArgs& p, f32x4 (&acc)[RBW][4], int m_w, 
     }
 }
 
-template <int ACT, bool GUARD, int RBW>
+template <int ACT, bool GUARD, int RBW, bool ROWMUL = false>
 F5_DEVICE void g6_direct_variants(const GemmArgs& p, f32x4 (&acc)[RBW][4], int m_w, int n_w, int n_blk, int lane) {
     const bool res = p.res != nullptr, outf = p.out_f32 != nullptr, outs = p.out_hi != nullptr;
     // the (residual, fp32 out, 16-bit out) combinations in use on the path: the table of g5_generic_variants
-    if (ACT == ACT_NONE) {
+    if constexpr (ROWMUL) {
+        g6_direct_tail<ACT_NONE, true, true, 0, GUARD, RBW, true>(p, acc, m_w, n_w, n_blk, lane);
+    } else if (ACT == ACT_NONE) {
         if (res) {
             if (outf && outs) g6_direct_tail<ACT, true, true, 1, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
             else if (outf) g6_direct_tail<ACT, true, true, 0, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
@@ -296,9 +305,14 @@ F5_DEVICE void g6_direct_variants(const GemmArgs& p, f32x4 (&acc)[RBW][4], int m
     }
 }
 
-template <int RBW>
+template <int RBW, bool ROWMUL = false>
 F5_DEVICE void g6_direct_epilogue(const GemmArgs& p, f32x4 (&acc)[RBW][4], int m0, int n0, int m_w, int n_w, int n_blk, int lane) {
     const bool interior = m0 + Gemm6Cfg<RBW>::BM <= p.M && n0 + Gemm6Cfg<RBW>::BN <= p.N && !p.row_keep;   // workgroup-uniform
+    if constexpr (ROWMUL) {
+        if (interior) g6_direct_variants<ACT_NONE, false, RBW, true>(p, acc, m_w, n_w, n_blk, lane);
+        else g6_direct_variants<ACT_NONE, true, RBW, true>(p, acc, m_w, n_w, n_blk, lane);
+        return;
+    }
 #define G6_ACT(A)                                                                         \
     if (interior) g6_direct_variants<A, false, RBW>(p, acc, m_w, n_w, n_blk, lane);       \
     else g6_direct_variants<A, true, RBW>(p, acc, m_w, n_w, n_blk, lane);
@@ -402,8 +416,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // rows of the LDS image this tile owns: all of them, or 176 of the 192 (the last row block of the second wave group is the next tile's)
         const int m_end = min(p.M, m0 + C::BM);
         const int n_blk = min(RBW, (C::BM - wr * RBW * 16) / 16);
-        if (EPI == EPI_GENERIC || swap) {
+        if (EPI == EPI_GENERIC || EPI == EPI_GENERIC_ROWMUL || swap) {
             if constexpr (EPI == EPI_GENERIC) g6_direct_epilogue<RBW>(p, acc, m0, n0, m0 + wr * RBW * 16, n0 + wc * 64, n_blk, lane);
+            else if constexpr (EPI == EPI_GENERIC_ROWMUL) g6_direct_epilogue<RBW, true>(p, acc, m0, n0, m0 + wr * RBW * 16, n0 + wc * 64, n_blk, lane);
             else g6_qk_direct<RBW>(p, acc, n0, m0 + wr * RBW * 16, n0 + wc * 64, n_blk, m_end, lane);   // Q / K tile
             G6_STAMP(stamp[2] = stamp[3] = stamp[4] = stamp[5] = __builtin_amdgcn_s_memrealtime())
         } else {

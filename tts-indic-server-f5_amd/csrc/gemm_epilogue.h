@@ -9,7 +9,9 @@
 #include "common.h"
 #include "ln_row.h"
 
-enum { EPI_GENERIC = 0, EPI_QKV = 1 };
+// EPI_GENERIC_ROWMUL: the generic epilogue with the multiplier taken per ROW -- mul + row_mod[row] * mod_ld (f5hip_cfm_sample_grids: the AdaLN
+// gates of the out / FF2 projections when the rows of one launch sit at different time points); residual + fp32 output, no activation, only
+enum { EPI_GENERIC = 0, EPI_QKV = 1, EPI_GENERIC_ROWMUL = 2 };
 
 // 64-byte LDS rows (32-deep k-steps of gemm.h / gemm3.h): 16-byte chunk XOR-swizzled with (row >> 2) & 3
 F5_DEVICE int lds_off2(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
@@ -59,9 +61,10 @@ struct GemmArgs {
     __bf16* out_lo;
     int ldob;
     int f16_out;          // 1: out_hi receives ONE fp16 plane (A operand of a PREC_F16 GEMM); only for the (no residual, no fp32 output) epilogues
-    // QKV epilogue
-    int D;                   // model dim (N == 3 D)
-    const int* row_pos;      // [M_pad] frame index inside the row's sequence, or null: rope_cos / rope_sin are per ROW ([M_pad][32], gathered once per call)
+    // QKV epilogue; EPI_GENERIC_ROWMUL shares two of its fields (the layout of the struct, and so every other kernel's argument offsets,
+    // stay as they are): the multiplier of row r is mul + row_mod[r] * mod_ld (row r of this launch's A / output)
+    union { int D; int mod_ld; };                // D: model dim (N == 3 D)
+    union { const int* row_pos; const int* row_mod; };   // row_pos: [M_pad] frame index inside the row's sequence, or null: rope_cos / rope_sin are per ROW ([M_pad][32], gathered once per call)
     const float* rope_cos;   // [max_pos][32]
     const float* rope_sin;
     __bf16* qk;              // [M_pad][2 D]  fp16 bits (attention operands are fp16: attn3.h)
@@ -79,7 +82,8 @@ struct GemmArgs {
 // GUARD = false is the interior fast path (whole wave tile inside M x N, no column groups, no row_keep): straight-line code, so
 // the compiler counts vmcnt exactly -- all residual loads in flight, stores never waited on.  With per-row-group exec
 // branches (GUARD = true) it falls back to s_waitcnt vmcnt(0) per group, which serialises every store's latency.
-template <int ACT, int WN, int ROWS, bool RES, bool OUTF, int OUTS, bool GUARD, int SLD = WN>   // OUTS: 0 none, 1 split bf16, 2 one fp16 plane; SLD: row stride of `stg` in floats
+// ROWMUL: the multiplier per row (EPI_GENERIC_ROWMUL), else one vector for the launch.
+template <int ACT, int WN, int ROWS, bool RES, bool OUTF, int OUTS, bool GUARD, int SLD = WN, bool ROWMUL = false>   // OUTS: 0 none, 1 split bf16, 2 one fp16 plane; SLD: row stride of `stg` in floats
 F5_DEVICE void epi_generic_rows_t(const GemmArgs& p, const float* stg, int m_base, int n_base, int lane) {
     constexpr int LPR = WN / 4, RPP = 64 / LPR, NQ = ROWS / RPP;
     const int c4 = (lane % LPR) * 4, r0 = lane / LPR;
@@ -92,8 +96,17 @@ F5_DEVICE void epi_generic_rows_t(const GemmArgs& p, const float* stg, int m_bas
     }
     f32x4 bv = {0.f, 0.f, 0.f, 0.f}, mv = {1.f, 1.f, 1.f, 1.f};
     if (p.bias && nok) bv = *reinterpret_cast<const f32x4*>(p.bias + n);
-    if (p.mul && nok) mv = *reinterpret_cast<const f32x4*>(p.mul + no);
+    if (!ROWMUL && p.mul && nok) mv = *reinterpret_cast<const f32x4*>(p.mul + no);
     const int mrow = m_base + r0;
+    f32x4 mq[ROWMUL ? NQ : 1];
+    if (ROWMUL) {
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            const int r = mrow + q * RPP;
+            mq[q] = (f32x4){1.f, 1.f, 1.f, 1.f};
+            if (!GUARD || (nok && r < p.M)) mq[q] = *reinterpret_cast<const f32x4*>(p.mul + (size_t)p.row_mod[r] * p.mod_ld + no);
+        }
+    }
     const float* rp = RES ? p.res + (size_t)mrow * p.ldres + no : nullptr;
     f32x4 rs[NQ];
     int keep[NQ];
@@ -118,7 +131,7 @@ F5_DEVICE void epi_generic_rows_t(const GemmArgs& p, const float* stg, int m_bas
             for (int e = 0; e < 4; e++) v[e] = apply_act(v[e], ACT);
         }
         if (GUARD && !keep[q]) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-        v = v * mv + rs[q];
+        v = v * (ROWMUL ? mq[ROWMUL ? q : 0] : mv) + rs[q];
         if (!GUARD || (nok && mrow + q * RPP < p.M)) {
             if (OUTF) *reinterpret_cast<f32x4*>(of + q * sf) = v;
             if (OUTS == 2) {
@@ -135,10 +148,12 @@ F5_DEVICE void epi_generic_rows_t(const GemmArgs& p, const float* stg, int m_bas
     }
 }
 
-template <int ACT, int WN, int ROWS, bool GUARD, int SLD = WN>
+template <int ACT, int WN, int ROWS, bool GUARD, int SLD = WN, bool ROWMUL = false>
 F5_DEVICE void epi_generic_rows_g(const GemmArgs& p, const float* stg, int m_base, int n_base, int lane) {
     const bool res = p.res != nullptr, outf = p.out_f32 != nullptr, outs = p.out_hi != nullptr;
-    if (ACT == ACT_NONE) {   // residual / plain projections: every output combination occurs
+    if constexpr (ROWMUL) {   // the gated residual projections: h += gate (A W^T + b), fp32 only
+        epi_generic_rows_t<ACT_NONE, WN, ROWS, true, true, 0, GUARD, SLD, true>(p, stg, m_base, n_base, lane);
+    } else if (ACT == ACT_NONE) {   // residual / plain projections: every output combination occurs
         if (res) {
             if (outf && outs) epi_generic_rows_t<ACT, WN, ROWS, true, true, 1, GUARD, SLD>(p, stg, m_base, n_base, lane);
             else if (outf) epi_generic_rows_t<ACT, WN, ROWS, true, true, 0, GUARD, SLD>(p, stg, m_base, n_base, lane);
@@ -158,12 +173,12 @@ F5_DEVICE void epi_generic_rows_g(const GemmArgs& p, const float* stg, int m_bas
     }
 }
 
-template <int ACT, int WN, int ROWS, int SLD = WN>
+template <int ACT, int WN, int ROWS, int SLD = WN, bool ROWMUL = false>
 F5_DEVICE void epi_generic_rows(const GemmArgs& p, const float* stg, int m_base, int n_base, int lane) {
     // wave-uniform: interior tile with both split planes (or none) and no per-row / per-group special cases
     const bool interior = m_base + ROWS <= p.M && n_base + WN <= p.N && !p.group_w && !p.row_keep && (!p.out_hi || p.out_lo || p.f16_out);
-    if (interior) epi_generic_rows_g<ACT, WN, ROWS, false, SLD>(p, stg, m_base, n_base, lane);
-    else epi_generic_rows_g<ACT, WN, ROWS, true, SLD>(p, stg, m_base, n_base, lane);
+    if (interior) epi_generic_rows_g<ACT, WN, ROWS, false, SLD, ROWMUL>(p, stg, m_base, n_base, lane);
+    else epi_generic_rows_g<ACT, WN, ROWS, true, SLD, ROWMUL>(p, stg, m_base, n_base, lane);
 }
 
 // Q / K blocks of the fused QKV projection: bias, rotary embedding on head 0 (x-transformers interleaved pairs, applied
@@ -272,7 +287,9 @@ F5_DEVICE void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[TM][TN], float* sl
             for (int g = 0; g < 16; g++) slab[(i * 32 + (g & 3) + 8 * (g >> 2) + 4 * fh) * WN + j * 32 + fr] = acc[i][j][g];
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     EPI_STAMP(1);
-    if (EPI == EPI_GENERIC) {
+    if constexpr (EPI == EPI_GENERIC_ROWMUL) {
+        epi_generic_rows<ACT_NONE, WN, ROWS, WN, true>(p, slab, m_wave, n_wave, lane);
+    } else if (EPI == EPI_GENERIC) {
         switch (p.act) {
             case ACT_GELU_TANH: epi_generic_rows<ACT_GELU_TANH, WN, ROWS>(p, slab, m_wave, n_wave, lane); break;
             case ACT_GELU_ERF: epi_generic_rows<ACT_GELU_ERF, WN, ROWS>(p, slab, m_wave, n_wave, lane); break;
@@ -296,7 +313,9 @@ F5_DEVICE void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[TM][TN], float* sl
 // QKV projection is stored transposed straight from the accumulators by the consumers alone (n_blk is workgroup-uniform).
 template <int EPI, int WN>
 F5_DEVICE void gemm_epilogue_rows32(const GemmArgs& p, const float* slab_half, int m_base, int n_wave, int lane) {
-    if (EPI == EPI_GENERIC) {
+    if constexpr (EPI == EPI_GENERIC_ROWMUL) {
+        epi_generic_rows<ACT_NONE, WN, 32, WN, true>(p, slab_half, m_base, n_wave, lane);
+    } else if (EPI == EPI_GENERIC) {
         switch (p.act) {
             case ACT_GELU_TANH: epi_generic_rows<ACT_GELU_TANH, WN, 32>(p, slab_half, m_base, n_wave, lane); break;
             case ACT_GELU_ERF: epi_generic_rows<ACT_GELU_ERF, WN, 32>(p, slab_half, m_base, n_wave, lane); break;

@@ -9,10 +9,12 @@
 // gemm.h: register-staged 128 x {128, 64} x 32 kernel (prec 1 bf16, 2 split bf16, 3 fp16 -- convolutions only); conv = implicit-GEMM operand
 hipError_t f5_launch_gemm_reg(int prec, int bn, bool conv, int epi, const GemmArgs& a, int m_pad, int n_pad, hipStream_t st);
 // gemm3.h: warp-specialised LDS-DMA kernel, 128 x bn (128, or 256 for one-plane operands) x 32
+// (gemm.h, gemm3.h, gemm6.h: epi = EPI_GENERIC, EPI_QKV or EPI_GENERIC_ROWMUL -- the last without convolutions)
 hipError_t f5_launch_gemm3(int prec, int epi, int bn, const GemmArgs& a, int m_pad, int n_pad, hipStream_t st);
 // gemm5.h: exact-fit (16 rb) x (16 cb) tiles, 64-deep k-steps, fp16 operands
 hipError_t f5_launch_gemm5_generic(const GemmArgs& a, int rb, int cb, int n_pad, hipStream_t st);
 hipError_t f5_launch_gemm5_qkv(const GemmArgs& a, int rb, int cb, int n_pad, hipStream_t st);
+hipError_t f5_launch_gemm5_rowmul(const GemmArgs& a, int rb, int cb, int n_pad, hipStream_t st);   // EPI_GENERIC_ROWMUL
 // gemm6.h: ping-pong tiles of `rows` (256 or 176) x 256 columns, fp16 operands: the batch-mode shapes (hipErrorInvalidValue: n_pad % 256, K % 64, D % 256)
 hipError_t f5_launch_gemm6(int epi, int rows, const GemmArgs& a, int n_pad, hipStream_t st);
 // gemm6 tile height: fewest (rounds on the 256 CUs) x (cost of a tile: a 176-row tile measures ~ 0.85 of a 256-row one -- k-loop 22.0 against

@@ -12,9 +12,13 @@
 struct LnArgs {
     const float* x; int ldx; int M; int D;
     const float* scale; const float* shift; float gain_off; float eps;
-    const float* dw_w; const float* dw_b; const int* row_seq_start; const int* row_seq_end;
+    const float* dw_w; const float* dw_b; const int* row_seq_start;
+    // ln_row<NV, true> (no depthwise conv, no fp32 output): row r takes scale / shift + row_mod[r] * mod_ld, its own modulation row.  The two
+    // share fields of those features, so the layout of the struct -- and the kernels' argument offsets -- stay as they are.
+    union { const int* row_seq_end; const int* row_mod; };
     __bf16* out_hi; __bf16* out_lo; int ldo;
-    float* out_f32; int ldof;
+    float* out_f32;
+    union { int ldof; int mod_ld; };
     int f16_out;   // 1: out_hi receives one fp16 plane (input of a PREC_F16 GEMM), out_lo unused
     int rms;   // 1: x-transformers RMSNorm, y = x / max(||x||_2, 1e-12) * sqrt(D) * scale[c]  (no mean subtraction)
 };
@@ -66,6 +70,22 @@ F5_DEVICE void ln_load_mod(const LnArgs& p, const int lane, float4 (&sc)[NV], fl
     }
 }
 
+// ln_load_mod of a row whose modulation vectors sit in modulation row row_mod[row] (f5hip_cfm_sample_grids: rows at different time points)
+template <int NV>
+F5_DEVICE void ln_load_mod_row(const LnArgs& p, const int row, const int lane, float4 (&sc)[NV], float4 (&sh)[NV]) {
+    const size_t off = (size_t)p.row_mod[row] * p.mod_ld;
+#pragma unroll
+    for (int i = 0; i < NV; i++) {
+        const int c = (i * 64 + lane) * 4;
+        sc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        sh[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < p.D) {
+            sc[i] = *reinterpret_cast<const float4*>(p.scale + off + c);
+            sh[i] = *reinterpret_cast<const float4*>(p.shift + off + c);
+        }
+    }
+}
+
 template <int NV>
 F5_DEVICE void ln_finish(const LnArgs& p, const int row, const int lane, const float4 (&v)[NV], const float4 (&sc)[NV], const float4 (&sh)[NV]) {
     if (row >= p.M) return;   // (wave-uniform)
@@ -109,12 +129,13 @@ F5_DEVICE void ln_finish(const LnArgs& p, const int row, const int lane, const f
     }
 }
 
-// one row by one wave (64 lanes x NV float4)
-template <int NV>
+// one row by one wave (64 lanes x NV float4); ROW_MOD: scale / shift per row (ln_load_mod_row)
+template <int NV, bool ROW_MOD = false>
 F5_DEVICE void ln_row(const LnArgs& p, const int row, const int lane) {
     if (row >= p.M) return;
     float4 v[NV], sc[NV], sh[NV];
     ln_load<NV>(p, row, lane, v);
-    ln_load_mod<NV>(p, lane, sc, sh);
+    if constexpr (ROW_MOD) ln_load_mod_row<NV>(p, row, lane, sc, sh);
+    else ln_load_mod<NV>(p, lane, sc, sh);
     ln_finish<NV>(p, row, lane, v, sc, sh);
 }

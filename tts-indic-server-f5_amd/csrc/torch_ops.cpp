@@ -4,6 +4,7 @@
 // built by build.py into csrc/libf5hip_torch.so next to libf5hip.so, loaded with torch.ops.load_library (tts_indic_server_f5_amd/torch_ops.py).
 //   torch.ops.f5hip.cfm_sample(handle, dur, kv_len?, cond, cond_mask, text, y0, t_grid, cfg_strength) -> Tensor   F/model/cfm.py:160-204
 //   torch.ops.f5hip.cfm_sample_units(handle, dur, kv_len?, cond, cond_mask, text, y0, t_grid, cfg_strength) -> Tensor  (one strength per unit)
+//   torch.ops.f5hip.cfm_sample_grids(handle, dur, kv_len?, cond, cond_mask, text, y0, steps, t_grids, cfg_strength) -> Tensor  (one grid per unit)
 //   torch.ops.f5hip.vocos_decode(handle, mel) -> Tensor                                                          F/infer/utils_infer.py:472
 //   torch.ops.f5hip.vocos_decode_ragged(handle, mel, frames, channels, hop_length) -> Tensor (packed)                F/infer/utils_infer.py:472
 //   torch.ops.f5hip.bigvgan_forward(handle, mel, total_upsample) -> Tensor                                       F/infer/utils_infer.py:474
@@ -64,6 +65,37 @@ at::Tensor cfm_sample_units(int64_t handle, const at::Tensor& dur, const c10::op
     return out;
 }
 
+// cfm_sample_units with one time grid per unit (f5hip_cfm_sample_grids): steps [b] int32 host (each >= 1), t_grids fp32 host, the b grids of
+// steps[u] + 1 points one after the other (sum(steps) + b floats).
+at::Tensor cfm_sample_grids(int64_t handle, const at::Tensor& dur, const c10::optional<at::Tensor>& kv_len, const at::Tensor& cond, const at::Tensor& cond_mask,
+                            const at::Tensor& text, const at::Tensor& y0, const at::Tensor& steps, const at::Tensor& t_grids, const at::Tensor& cfg_strength) {
+    check_host(dur, at::kInt, "dur"); check_host(cond_mask, at::kByte, "cond_mask"); check_host(text, at::kInt, "text"); check_host(t_grids, at::kFloat, "t_grids");
+    check_host(steps, at::kInt, "steps"); check_host(cfg_strength, at::kFloat, "cfg_strength");
+    check_dev_f32(cond, "cond"); check_dev_f32(y0, "y0");
+    TORCH_CHECK(text.dim() == 2 && text.size(0) == dur.numel() && cond.sizes() == y0.sizes(), "f5hip::cfm_sample_grids: shapes");
+    TORCH_CHECK(cfg_strength.numel() == dur.numel(), "f5hip::cfm_sample_grids: cfg_strength needs one value per unit (", cfg_strength.numel(), " for ", dur.numel(), ")");
+    TORCH_CHECK(steps.numel() == dur.numel(), "f5hip::cfm_sample_grids: steps needs one value per unit (", steps.numel(), " for ", dur.numel(), ")");
+    if (kv_len.has_value()) {
+        check_host(*kv_len, at::kInt, "kv_len");
+        TORCH_CHECK(kv_len->numel() == dur.numel(), "f5hip::cfm_sample_grids: kv_len needs one value per unit");
+    }
+    const int32_t* sp = steps.data_ptr<int32_t>();
+    int64_t points = 0;
+    for (int64_t u = 0; u < steps.numel(); u++) {
+        TORCH_CHECK(sp[u] >= 1, "f5hip::cfm_sample_grids: steps[", u, "] = ", sp[u], " (need >= 1)");
+        points += sp[u] + 1;
+    }
+    TORCH_CHECK(t_grids.numel() == points, "f5hip::cfm_sample_grids: t_grids needs sum(steps) + n = ", points, " values (got ", t_grids.numel(), ")");
+    const int64_t rows = dur.sum().item<int64_t>();
+    TORCH_CHECK(cond.dim() == 2 && cond.size(0) == rows && cond_mask.numel() == rows, "f5hip::cfm_sample_grids: cond / y0 / cond_mask need sum(dur) = ", rows, " rows");
+    at::Tensor out = at::empty_like(y0);
+    const int rc = f5hip_cfm_sample_grids((f5hip_dit*)handle, (int32_t)dur.numel(), dur.data_ptr<int32_t>(), kv_len.has_value() ? kv_len->data_ptr<int32_t>() : nullptr,
+                                          cond.data_ptr<float>(), cond_mask.data_ptr<uint8_t>(), text.data_ptr<int32_t>(), (int32_t)text.size(1), y0.data_ptr<float>(),
+                                          sp, t_grids.data_ptr<float>(), cfg_strength.data_ptr<float>(), out.data_ptr<float>(), stream_of(y0));
+    TORCH_CHECK(rc == 0, "f5hip_cfm_sample_grids: ", f5hip_last_error());
+    return out;
+}
+
 at::Tensor vocos_decode(int64_t handle, const at::Tensor& mel, int64_t hop_length) {
     check_dev_f32(mel, "mel");
     TORCH_CHECK(mel.dim() == 3, "f5hip::vocos_decode: mel [b, 100, T]");
@@ -106,6 +138,7 @@ at::Tensor bigvgan_forward(int64_t handle, const at::Tensor& mel, int64_t total_
 TORCH_LIBRARY(f5hip, m) {
     m.def("cfm_sample(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor t_grid, float cfg_strength) -> Tensor", &cfm_sample);
     m.def("cfm_sample_units(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor t_grid, Tensor cfg_strength) -> Tensor", &cfm_sample_units);
+    m.def("cfm_sample_grids(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor steps, Tensor t_grids, Tensor cfg_strength) -> Tensor", &cfm_sample_grids);
     m.def("vocos_decode(int handle, Tensor mel, int hop_length) -> Tensor", &vocos_decode);
     m.def("vocos_decode_ragged(int handle, Tensor mel, Tensor frames, int channels, int hop_length) -> Tensor", &vocos_decode_ragged);
     m.def("bigvgan_forward(int handle, Tensor mel, int total_upsample) -> Tensor", &bigvgan_forward);

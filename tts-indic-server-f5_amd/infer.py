@@ -494,18 +494,19 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     [spec_i]) per request -- the per-chunk waves before the cross-fade -- instead of the joined triple.
 
     Per-request options: a request may carry a fourth element, a dict with any of `speed`, `nfe_step`, `cfg_strength`,
-    `sway_sampling_coef` and `seed` (`REQUEST_OPTIONS`); what it leaves out comes from this function's keyword arguments.  Requests that
-    share a time grid (`nfe_step`, `sway_sampling_coef`) are sampled in ONE `sample_units` call, each unit with its request's
-    `cfg_strength` (one float for the call when they all agree, as before; else one value per unit); each further grid is one more call
-    (the backbone's time modulation is per call), in order of first appearance, and all chunks are still vocoded together.  `speed` only
-    changes a request's planned frames.  With `seed`, the request's chunk k draws its noise from `request_generator(seed)` after chunks
+    `sway_sampling_coef` and `seed` (`REQUEST_OPTIONS`); what it leaves out comes from this function's keyword arguments.  With a model
+    that declares `per_unit_time_grids` (`F5HipModel`: f5hip_cfm_sample_grids) all units are sampled in ONE `sample_units` call whatever
+    their time grids (`nfe_step`, `sway_sampling_coef`) and strengths: each knob goes in as one value when all units agree, else as one
+    value per unit.  With any other model, requests that share a time grid are sampled in one call and each further grid is one more call,
+    in order of first appearance.  All chunks are vocoded together either way.  `speed` only changes a request's planned frames.  With `seed`, the request's chunk k draws its noise from `request_generator(seed)` after chunks
     0..k-1; a `generator` entry (a torch.Generator) continues that sequence instead -- what a streamed request's remaining chunks carry --
     and is advanced only when this call succeeds.  A seeded request's result depends only on its own settings, not on its batch, with the
     shape-invariant attention mode on one GPU (ranks > 0 of a `serve.ShardedSampler` do not switch to that mode yet); unseeded units draw
-    from the global generator in sampler-call order."""
+    from the global generator in flat request order (unit by unit, request after request) when there is one sampler call, i.e. always
+    with a `per_unit_time_grids` model, and in sampler-call order otherwise."""
     defaults = dict(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None)
     plans, calls = [], {}   # calls: (nfe_step, sway) -> [unit ids, ...] of one sampler call each
-    flat_units, flat_cond, flat_audio, flat_cfg, flat_gen, commits = [], [], [], [], [], []
+    flat_units, flat_cond, flat_audio, flat_cfg, flat_gen, flat_grid, commits = [], [], [], [], [], [], []
     for req in requests:
         ref_audio, ref_text, gen_text = req[:3]
         opts = dict(defaults, **(req[3] if len(req) > 3 and req[3] else {}))
@@ -529,10 +530,18 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
         flat_audio += [voice.audio] * len(units)
         flat_cfg += [opts["cfg_strength"]] * len(units)
         flat_gen += [gen] * len(units)
+        flat_grid += [key] * len(units)
+    if len(calls) > 1 and getattr(model_obj, "per_unit_time_grids", False) and hasattr(model_obj, "sample_units"):
+        calls = {None: list(range(len(flat_units)))}   # one call for every grid
     mels = [None] * len(flat_units)
-    for (steps, sway), ids in calls.items():
-        cfgs = [flat_cfg[i] for i in ids]
-        cfg = cfgs[0] if all(c == cfgs[0] for c in cfgs) else cfgs
+
+    def one_or_list(vals):
+        return vals[0] if all(v == vals[0] for v in vals) else vals
+
+    for ids in calls.values():
+        steps = one_or_list([flat_grid[i][0] for i in ids])
+        sway = one_or_list([flat_grid[i][1] for i in ids])
+        cfg = one_or_list([flat_cfg[i] for i in ids])
         knobs = dict(steps=steps, cfg_strength=cfg, sway_sampling_coef=sway)
         extra = _seeded_kw(model_obj, [flat_gen[i] for i in ids])
         if hasattr(model_obj, "sample_units"):

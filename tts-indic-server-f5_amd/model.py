@@ -107,7 +107,21 @@ def per_unit_cfg(cfg_strength, n: int):
     return cfg
 
 
+def per_unit_values(value, n: int, name: str):
+    """`value` itself for one value shared by the n units, else the list of the n per-unit values (a list, tuple or 1-d array / tensor)."""
+    if value is None or isinstance(value, (int, float, np.floating, np.integer)) or (isinstance(value, torch.Tensor) and value.ndim == 0):
+        return value
+    vals = [v.item() if isinstance(v, (torch.Tensor, np.ndarray, np.generic)) else v for v in value]
+    if len(vals) != n:
+        raise ValueError(f"{name}: one value per unit ({n}) or one value, got {len(vals)} values")
+    return vals
+
+
 class F5HipModel:
+    # sample() / sample_units() take `steps` and `sway_sampling_coef` per unit too and sample units of different time grids in ONE call
+    # (f5hip_cfm_sample_grids); infer.infer_requests and serve.ShardedSampler look for this flag before they merge time grids
+    per_unit_time_grids = True
+
     def __init__(self, arch: DiTArch | UNetTArch | MMDiTArch, state_dict: dict, vocab_char_map: dict | None = None, gemm_planes: int = 3,
                  device: str | torch.device = "cuda:0", mel_spec_type: str = "vocos", odeint_kwargs: dict | None = None,
                  attn_shape_invariant: bool | None = None):
@@ -217,7 +231,8 @@ class F5HipModel:
         Per-unit settings: `cfg_strength` is one float or one value per unit (a unit below 1e-5 runs no unconditional branch); `generators`
         ([torch.Generator | None] per unit) draws a unit's noise from its own CPU generator instead of the global one, with the unit's final
         duration (`unit_duration`), and `y0` ([tensor [dur_i, mel] | None] per unit) hands a unit its noise outright.  Units without either
-        keep drawing from the global generator, unit by unit in order.  The time grid (`steps`, `sway_sampling_coef`) is the call's."""
+        keep drawing from the global generator, unit by unit in order.  `steps` and `sway_sampling_coef` are one value or one value per unit
+        (None allowed per unit for the sway): units of different time grids are sampled in the same call."""
         b = len(units)
         frames = torch.tensor([int(f) for _, f in units], dtype=torch.long)
         lens = None
@@ -251,7 +266,10 @@ class F5HipModel:
         `y0` ([b, n, mel] or list of [dur_i, mel]; host or device) overrides the noise, which is otherwise drawn exactly like the
         reference's CPU path (per item `torch.manual_seed(seed)`; `torch.randn(dur, mel)` from the global CPU generator).  Per item, a
         list `y0` may hold None and `generators` ([torch.Generator | None]) draws the item's `randn(dur, mel)` from its own generator.
-        `cfg_strength`: one float (f5hip_cfm_sample_masked) or one value per item (f5hip_cfm_sample_units)."""
+        `cfg_strength`: one float (f5hip_cfm_sample_masked) or one value per item (f5hip_cfm_sample_units).
+        `steps` / `sway_sampling_coef`: one value, or one value per item (sway None allowed per item).  Every item's grid is built as the
+        scalar call builds it; when they all come out equal the call is the one-grid call, otherwise f5hip_cfm_sample_grids samples every
+        item on its own grid in the same call (an item whose steps are done leaves the batch)."""
         if cond.ndim == 2:   # raw wave -> mel (cfm.py:103-106) with the extractor of mel_spec_type (modules.py:123-126)
             cond = self.cond_mel(cond)
         cond = cond.to(self.device, torch.float32)
@@ -306,13 +324,30 @@ class F5HipModel:
             ys.append(yi)
 
         t_start = 0.0
+        steps_u = per_unit_values(steps, batch, "steps")
+        sway_u = per_unit_values(sway_sampling_coef, batch, "sway_sampling_coef")
+        steps_u = [int(x) for x in steps_u] if isinstance(steps_u, list) else [int(steps_u)] * batch
+        sway_u = sway_u if isinstance(sway_u, list) else [sway_u] * batch
         if duplicate_test:   # cfm.py:190-194
             t_start = float(t_inter)
             ys = [(1 - t_start) * ys[i] + t_start * test_cond[i, :lay[i]] for i in range(batch)]
-            steps = int(steps * (1 - t_start))
-        t = torch.linspace(t_start, 1, steps + 1, dtype=torch.float32)            # cfm.py:196-198
-        if sway_sampling_coef is not None:
-            t = t + sway_sampling_coef * (torch.cos(torch.pi / 2 * t) - 1 + t)
+            steps_u = [int(x * (1 - t_start)) for x in steps_u]
+
+        def time_grid(n_steps, sway):
+            t = torch.linspace(t_start, 1, n_steps + 1, dtype=torch.float32)        # cfm.py:196-198
+            if sway is not None:
+                t = t + sway * (torch.cos(torch.pi / 2 * t) - 1 + t)
+            return t
+
+        grids, cache = [], {}
+        for n_steps, sway in zip(steps_u, sway_u):
+            key = (n_steps, None if sway is None else float(sway))
+            if key not in cache:
+                cache[key] = time_grid(n_steps, sway)
+            grids.append(cache[key])
+        t = grids[0]
+        one_grid = all(g.shape == t.shape and torch.equal(g, t) for g in grids[1:])
+        steps = steps_u[0]
 
         cond_packed = torch.cat([cond[i, :lay[i]] for i in range(batch)], dim=0).contiguous()
         mask_packed = np.ascontiguousarray(
@@ -322,7 +357,23 @@ class F5HipModel:
         text_np = _i32(text.numpy())
         tg = np.ascontiguousarray(t.numpy().astype(np.float32))
         d_np, kv_np = _i32(lay), _i32(durs)
-        if cfg_units is not None:   # one strength per item: f5hip_cfm_sample_units
+        if not one_grid:   # one grid (and strength) per item: f5hip_cfm_sample_grids
+            cfg_all = cfg_units if cfg_units is not None else np.full(batch, float(cfg_strength), dtype=np.float32)
+            steps_np = _i32(steps_u)
+            tgs = np.ascontiguousarray(torch.cat(grids).numpy().astype(np.float32))
+            if torch_ops.load():
+                try:
+                    out_packed = torch_ops.ops().cfm_sample_grids(
+                        int(self._h), torch.from_numpy(d_np), torch.from_numpy(kv_np) if padded else None, cond_packed, torch.from_numpy(mask_packed),
+                        torch.from_numpy(text_np), y0_packed, torch.from_numpy(steps_np), torch.from_numpy(tgs), torch.from_numpy(cfg_all))
+                except RuntimeError as e:
+                    raise _lib.F5HipError(str(e).split("\n")[0]) from None
+            else:
+                _lib.check(self._lib.f5hip_cfm_sample_grids(
+                    self._h, batch, _ptr(d_np), _ptr(kv_np) if padded else None, _ptr(cond_packed), _ptr(mask_packed), _ptr(text_np),
+                    text_np.shape[1], _ptr(y0_packed), _ptr(steps_np), _ptr(tgs), _ptr(cfg_all), _ptr(out_packed), _lib.current_stream_ptr()),
+                    "f5hip_cfm_sample_grids")
+        elif cfg_units is not None:   # one strength per item: f5hip_cfm_sample_units
             if torch_ops.load():
                 try:
                     out_packed = torch_ops.ops().cfm_sample_units(

@@ -632,7 +632,8 @@ class ShardedSampler:
     `infer_batch_process`), so an unseeded result is not reproducible across world sizes; pass `seed=` in the knobs for that.  Units with
     their own generator (`generators=`, a seeded request's chunks) get their noise drawn HERE, on rank 0, in unit order at the unit's final
     duration (`model.unit_duration`), and broadcast with the job: a seeded unit gets the same noise whichever rank samples it.
-    Per-unit `cfg_strength` (a list) is sliced to each rank's units.  (Ranks > 0 do not switch their handles to the shape-invariant
+    Per-unit `cfg_strength`, `steps` and `sway_sampling_coef` (lists) are sliced to each rank's units; the sampler declares
+    `per_unit_time_grids` when its local model does, so `infer.infer_requests` hands it units of different time grids in one call.  (Ranks > 0 do not switch their handles to the shape-invariant
     attention mode yet, so the bit-for-bit promises of a seeded request hold on one GPU.)
     Streaming (`TTSManager.synthesize_stream`) needs nothing here: a stream's first chunk and its remaining chunks arrive as units of
     ordinary `sample_units` batches."""
@@ -644,6 +645,10 @@ class ShardedSampler:
         self.device = device if device is not None else getattr(local_model, "device", torch.device("cpu"))
         self.vocab_char_map = getattr(local_model, "vocab_char_map", None)
         self.failed: str | None = None
+
+    @property
+    def per_unit_time_grids(self):
+        return bool(getattr(self.local, "per_unit_time_grids", False))
 
     # what infer.* needs from a model object
     def cond_mel(self, audio):
@@ -673,6 +678,14 @@ class ShardedSampler:
             if len(per_unit) != b:
                 raise ValueError(f"cfg_strength: one value per unit ({b}), got {len(per_unit)}")
             knobs["cfg_strength"] = None      # replaced per rank by its units' slice
+        grids = {}                            # per-unit time grids: sliced per rank like the strengths
+        for name in ("steps", "sway_sampling_coef"):
+            v = knobs.get(name)
+            if isinstance(v, (list, tuple)):
+                if len(v) != b:
+                    raise ValueError(f"{name}: one value per unit ({b}), got {len(v)}")
+                grids[name] = [None if x is None else (int(x) if name == "steps" else float(x)) for x in v]
+                knobs[name] = None
         noise = list(y0) if y0 is not None else [None] * b
         if gens is not None:
             from .model import unit_duration
@@ -684,6 +697,8 @@ class ShardedSampler:
         noise_rows = [0 if n is None else int(n.shape[0]) for n in noise]
         job = dict(units=[(list(t), int(f)) for t, f in units], voice_of=voice_of, mel_shapes=[tuple(m.shape) for m in mels], knobs=knobs,
                    cfg=per_unit, noise_rows=noise_rows)
+        if grids:
+            job["grids"] = grids
         try:
             return _run_sharded_job(self.local, job, mels, self.device, noise if any(noise_rows) else None)
         except ShardedJobError as e:
@@ -739,6 +754,8 @@ def _run_sharded_job(local_model, job, mels, device, noise=None):
     knobs = dict(job["knobs"])
     if job.get("cfg") is not None:        # per-unit CFG strengths: this rank's units
         knobs["cfg_strength"] = [job["cfg"][i] for i in mine]
+    for name, vals in (job.get("grids") or {}).items():   # per-unit steps / sway: this rank's units
+        knobs[name] = [vals[i] for i in mine]
     if noise is not None and any(noise[i] is not None for i in mine):
         knobs["y0"] = [noise[i] for i in mine]
     try:
