@@ -208,6 +208,24 @@ int f5hip_op_layernorm(int32_t M, int32_t D, const float* x_dev, const float* sc
 int f5hip_op_conv1d(int32_t batch, int32_t P, int32_t T, int32_t c_in, int32_t c_out, int32_t k, int32_t dil, const float* x_dev,
                     const float* w_host, const float* bias_host, const float* res_dev, float* out_dev, int32_t prec, int32_t impl,
                     int32_t iters, double* avg_us, uint64_t* stamps_host, int32_t stamp_blocks, void* stream);
+/* f5hip_op_bigvgan_snake: the generator's Activation1d(SnakeBeta) (2x Kaiser-sinc up-sampling with replicate padding, x + sin^2(x e^alpha) /
+ *   (e^beta + 1e-9), 2x low-pass down-sampling) over channel-last rows: `batch` sequences of pitch P rows, T valid (C % 4 == 0).  x_dev fp32
+ *   [batch P][C], alpha_log_dev / beta_log_dev fp32 [C] (the log-scale parameters).  out_format: 0 = fp32, 1 = split-bf16 planes, 2 = one fp16
+ *   plane (saturated); out_dev fp32 [out_rows][C] (out_rows >= batch P) receives the output as fp32.  Formats 1 / 2 run through planes
+ *   of out_rows rows loaded from out_dev, so rows the kernel does not write (t >= T, and rows past batch P) come back rounded to the format. */
+int f5hip_op_bigvgan_snake(int32_t batch, int32_t P, int32_t T, int32_t C, const float* x_dev, const float* alpha_log_dev,
+                           const float* beta_log_dev, int32_t out_format, float* out_dev, int64_t out_rows, void* stream);
+/* f5hip_op_bigvgan_upsample: one up-sampler of the generator, nn.ConvTranspose1d(c_in, c_out, 2 r, stride r, padding r / 2) + bias with
+ *   r even, run as its 3-tap implicit GEMM (phase-major columns) by the generator's convolution dispatch.  x_dev fp32 [batch P][c_in]
+ *   (P % 128 == 0, T valid, c_in % 4 == 0), w_host [c_in][c_out][2 r] (the module's weight layout), bias_host [c_out] or NULL; out_dev fp32
+ *   [batch P r][c_out] (rows >= r T of a sequence are unspecified).  prec 2 = split bf16, 3 = one fp16 plane. */
+int f5hip_op_bigvgan_upsample(int32_t batch, int32_t P, int32_t T, int32_t c_in, int32_t c_out, int32_t r, const float* x_dev,
+                              const float* w_host, const float* bias_host, float* out_dev, int32_t prec, void* stream);
+/* f5hip_op_bigvgan_conv_post: the generator's conv_post, nn.Conv1d(C, 1, 7, padding 3, no bias), then clamp(-1, 1).  a_dev fp32 [batch P][C]
+ *   (T valid rows per sequence), w_dev fp32 [C][7] (device), wave_dev fp32 [batch][T].  variant 0 = the kernel the generator picks, 1 = the
+ *   LDS-tiled kernel (fails when its tile exceeds 48 KB, C > 44), 2 = the kernel without the tile. */
+int f5hip_op_bigvgan_conv_post(int32_t batch, int32_t P, int32_t T, int32_t C, const float* a_dev, const float* w_dev, int32_t variant,
+                               float* wave_dev, void* stream);
 
 /* ---------------------------------------------------------------- Vocos vocoder ----------------------- */
 

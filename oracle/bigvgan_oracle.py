@@ -1,4 +1,4 @@
-"""fp32 CPU oracle of the BigVGAN v2 generator (TEST INFRASTRUCTURE ONLY).
+"""CPU oracle of the BigVGAN v2 generator (fp32, or float64 on float64 inputs) (TEST INFRASTRUCTURE ONLY).
 
 BigVGAN is third-party to the reference: an un-vendored git submodule (`third_party/BigVGAN`, call sites
 F/infer/utils_infer.py:7,116-129,474; mel front-end copied into F/model/modules.py:30-72).  This file restates the
@@ -31,8 +31,8 @@ class BigVGANConfig:
 BIGVGAN_V2_24K_100B_256X = BigVGANConfig()
 
 
-def kaiser_sinc_filter1d(cutoff: float, half_width: float, kernel_size: int) -> torch.Tensor:
-    """alias_free_torch/filter.py of BigVGAN: Kaiser-windowed sinc low-pass, normalised to unit DC gain."""
+def kaiser_sinc_filter1d(cutoff: float, half_width: float, kernel_size: int, dtype=torch.float32) -> torch.Tensor:
+    """alias_free_torch/filter.py of BigVGAN: Kaiser-windowed sinc low-pass, normalised to unit DC gain, evaluated in `dtype`."""
     even = kernel_size % 2 == 0
     half_size = kernel_size // 2
     delta_f = 4 * half_width
@@ -43,36 +43,35 @@ def kaiser_sinc_filter1d(cutoff: float, half_width: float, kernel_size: int) -> 
         beta = 0.5842 * (A - 21) ** 0.4 + 0.07886 * (A - 21.0)
     else:
         beta = 0.0
-    window = torch.kaiser_window(kernel_size, beta=beta, periodic=False)
-    time = (torch.arange(-half_size, half_size) + 0.5) if even else (torch.arange(kernel_size) - half_size)
+    window = torch.kaiser_window(kernel_size, beta=beta, periodic=False, dtype=dtype)
+    time = (torch.arange(-half_size, half_size, dtype=dtype) + 0.5) if even else (torch.arange(kernel_size, dtype=dtype) - half_size)
     filt = 2 * cutoff * window * torch.sinc(2 * cutoff * time)
     return filt / filt.sum()
 
 
-AA_FILTER = None
+AA_FILTER = {}
 
 
-def aa_filter() -> torch.Tensor:
-    """The one 12-tap filter both UpSample1d(2) and DownSample1d(2) use: cutoff 0.25, half_width 0.3."""
-    global AA_FILTER
-    if AA_FILTER is None:
-        AA_FILTER = kaiser_sinc_filter1d(0.25, 0.3, 12)
-    return AA_FILTER
+def aa_filter(dtype=torch.float32) -> torch.Tensor:
+    """The one 12-tap filter both UpSample1d(2) and DownSample1d(2) use: cutoff 0.25, half_width 0.3, in `dtype` (cached per dtype)."""
+    if dtype not in AA_FILTER:
+        AA_FILTER[dtype] = kaiser_sinc_filter1d(0.25, 0.3, 12, dtype)
+    return AA_FILTER[dtype]
 
 
 def upsample2(x: torch.Tensor) -> torch.Tensor:
-    """UpSample1d(ratio=2, kernel_size=12): replicate-pad 5, grouped conv_transpose (stride 2) * 2, crop 15 / 15."""
+    """UpSample1d(ratio=2, kernel_size=12): replicate-pad 5, grouped conv_transpose (stride 2) * 2, crop 15 / 15.  Follows x's dtype."""
     c = x.shape[1]
     x = F.pad(x, (5, 5), mode="replicate")
-    x = 2 * F.conv_transpose1d(x, aa_filter().view(1, 1, 12).expand(c, -1, -1), stride=2, groups=c)
+    x = 2 * F.conv_transpose1d(x, aa_filter(x.dtype).view(1, 1, 12).expand(c, -1, -1), stride=2, groups=c)
     return x[..., 15:-15]
 
 
 def downsample2(x: torch.Tensor) -> torch.Tensor:
-    """DownSample1d(ratio=2, kernel_size=12): replicate-pad (5, 6), grouped conv stride 2."""
+    """DownSample1d(ratio=2, kernel_size=12): replicate-pad (5, 6), grouped conv stride 2.  Follows x's dtype."""
     c = x.shape[1]
     x = F.pad(x, (5, 6), mode="replicate")
-    return F.conv1d(x, aa_filter().view(1, 1, 12).expand(c, -1, -1), stride=2, groups=c)
+    return F.conv1d(x, aa_filter(x.dtype).view(1, 1, 12).expand(c, -1, -1), stride=2, groups=c)
 
 
 def snake_beta(x: torch.Tensor, alpha_log: torch.Tensor, beta_log: torch.Tensor) -> torch.Tensor:
@@ -98,7 +97,8 @@ def amp_block1(sd, p: str, x: torch.Tensor, k: int, dilations) -> torch.Tensor:
 
 @torch.no_grad()
 def bigvgan_forward(sd: dict, cfg: BigVGANConfig, mel: torch.Tensor) -> torch.Tensor:
-    """BigVGAN.forward: mel [b, num_mels, T] -> wave [b, 1, T * prod(upsample_rates)], clamped to [-1, 1]."""
+    """BigVGAN.forward: mel [b, num_mels, T] -> wave [b, 1, T * prod(upsample_rates)], clamped to [-1, 1].  Runs in mel's dtype (the
+    state dict must match it): a float64 state dict and mel make it a float64 reference."""
     x = F.conv1d(mel, sd["conv_pre.weight"], sd["conv_pre.bias"], padding=3)
     nk = len(cfg.resblock_kernel_sizes)
     for i, (r, k) in enumerate(zip(cfg.upsample_rates, cfg.upsample_kernel_sizes)):

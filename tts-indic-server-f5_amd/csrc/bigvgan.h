@@ -232,6 +232,46 @@ static int bv_pack_conv(BvConv& c, const std::vector<float>& w, const float* bia
     return pack_linear(c.w, wp.data(), co, K, K, bias, co <= 64 ? 64 : 128, f16);
 }
 
+// kaiser_sinc_filter1d(cutoff 0.25, half_width 0.3, 12) of alias_free_torch/filter.py, evaluated in double and rounded to fp32
+static void bv_aa_filter(float out[12]) {
+    const int ks = 12, half = 6;
+    const double cutoff = 0.25, hw = 0.3, delta_f = 4 * hw, A = 2.285 * (half - 1) * M_PI * delta_f + 7.95;
+    const double beta = A > 50.0 ? 0.1102 * (A - 8.7) : (A >= 21.0 ? 0.5842 * pow(A - 21.0, 0.4) + 0.07886 * (A - 21.0) : 0.0);
+    auto i0 = [](double x) { double s = 1.0, t = 1.0; for (int k = 1; k < 50; k++) { t *= (x / (2.0 * k)) * (x / (2.0 * k)); s += t; } return s; };
+    double f[12], sum = 0.0;
+    for (int n = 0; n < ks; n++) {
+        const double r = 2.0 * n / (ks - 1) - 1.0;                       // torch.kaiser_window(periodic=False)
+        const double win = i0(beta * sqrt(1.0 - r * r)) / i0(beta);
+        const double tm = (n - half) + 0.5, xx = 2 * cutoff * tm;
+        const double sinc = fabs(xx) < 1e-12 ? 1.0 : sin(M_PI * xx) / (M_PI * xx);
+        f[n] = 2 * cutoff * win * sinc;
+        sum += f[n];
+    }
+    for (int n = 0; n < ks; n++) out[n] = (float)(f[n] / sum);
+}
+
+// ConvTranspose1d(ci -> co, k = 2 r, stride r, padding r / 2), weight [ci][co][k], as the 3-tap implicit GEMM over inputs t - 1, t, t + 1:
+// [r co][tap][ci_pad] with phase-major columns n = p co + o.  Output row r t + p takes input t through tap p + r / 2, and input t - 1
+// (p < r / 2, tap p + 3 r / 2) or t + 1 (p >= r / 2, tap p - r / 2); the third tap's weights stay zero
+static int bv_pack_ups(BvConv& u, const float* w, const float* b, int ci, int co, int r, bool f16) {
+    const int k = 2 * r;
+    u.k = 3; u.dil = 1; u.c_in = ci; u.c_out = r * co; u.c_in_pad = ceil_to(ci, 32);
+    const int K = 3 * u.c_in_pad;
+    std::vector<float> wp((size_t)r * co * K, 0.0f), bp((size_t)r * co);
+    for (int p = 0; p < r; p++)
+        for (int o = 0; o < co; o++) {
+            const size_t n = (size_t)p * co + o;
+            bp[n] = b[o];
+            for (int i2 = 0; i2 < ci; i2++) {
+                const float* wr = &w[((size_t)i2 * co + o) * k];   // ConvTranspose1d weight [c_in][c_out][k]
+                wp[n * K + 1 * u.c_in_pad + i2] = wr[p + r / 2];                       // input t
+                if (p < r / 2) wp[n * K + 0 * u.c_in_pad + i2] = wr[p + 3 * r / 2];   // input t - 1
+                else wp[n * K + 2 * u.c_in_pad + i2] = wr[p - r / 2];                  // input t + 1
+            }
+        }
+    return pack_linear(u.w, wp.data(), r * co, K, K, bp.data(), r * co <= 64 ? 64 : 128, f16);
+}
+
 int f5hip_bigvgan_finalize(f5hip_bigvgan* v) {
     if (!v) return fail(-1, "null vocoder");
     if (v->finalized) return 0;
@@ -254,21 +294,7 @@ int f5hip_bigvgan_finalize(f5hip_bigvgan* v) {
         const int ci = v->c0 >> i, co = v->c0 >> (i + 1), r = c.upsample_rates[i], k = 2 * r;
         GET_PARAM(w, P, "ups." + std::to_string(i) + ".0.weight", (int64_t)ci * co * k);
         GET_PARAM(b, P, "ups." + std::to_string(i) + ".0.bias", co);
-        BvConv& u = v->ups[i]; u.k = 3; u.dil = 1; u.c_in = ci; u.c_out = r * co; u.c_in_pad = ceil_to(ci, 32);
-        const int K = 3 * u.c_in_pad;
-        std::vector<float> wp((size_t)r * co * K, 0.0f), bp((size_t)r * co);
-        for (int p = 0; p < r; p++)
-            for (int o = 0; o < co; o++) {
-                const size_t n = (size_t)p * co + o;
-                bp[n] = (*b)[o];
-                for (int i2 = 0; i2 < ci; i2++) {
-                    const float* wr = &(*w)[((size_t)i2 * co + o) * k];   // ConvTranspose1d weight [c_in][c_out][k]
-                    wp[n * K + 1 * u.c_in_pad + i2] = wr[p + r / 2];                       // input t
-                    if (p < r / 2) wp[n * K + 0 * u.c_in_pad + i2] = wr[p + 3 * r / 2];   // input t - 1
-                    else wp[n * K + 2 * u.c_in_pad + i2] = wr[p - r / 2];                  // input t + 1
-                }
-            }
-        if (pack_linear(u.w, wp.data(), r * co, K, K, bp.data(), r * co <= 64 ? 64 : 128, f16)) return -4;
+        if (bv_pack_ups(v->ups[i], w->data(), b->data(), ci, co, r, f16)) return -4;
         for (int j = 0; j < 3; j++) {
             BvRes& rb = v->res[i * 3 + j];
             const int kk = c.resblock_kernel_sizes[j];
@@ -290,24 +316,7 @@ int f5hip_bigvgan_finalize(f5hip_bigvgan* v) {
         GET_PARAM(al, P, "activation_post.act.alpha", ch); GET_PARAM(be, P, "activation_post.act.beta", ch); GET_PARAM(w, P, "conv_post.weight", (int64_t)ch * 7);
         if (upload_f32(&v->post_alpha, al->data(), ch) || upload_f32(&v->post_beta, be->data(), ch) || upload_f32(&v->post_w, w->data(), ch * 7)) return -4;
     }
-    {   // kaiser_sinc_filter1d(cutoff 0.25, half_width 0.3, 12): alias_free_torch/filter.py
-        const int ks = 12, half = 6;
-        const double cutoff = 0.25, hw = 0.3, delta_f = 4 * hw, A = 2.285 * (half - 1) * M_PI * delta_f + 7.95;
-        const double beta = A > 50.0 ? 0.1102 * (A - 8.7) : (A >= 21.0 ? 0.5842 * pow(A - 21.0, 0.4) + 0.07886 * (A - 21.0) : 0.0);
-        auto i0 = [](double x) { double s = 1.0, t = 1.0; for (int k = 1; k < 50; k++) { t *= (x / (2.0 * k)) * (x / (2.0 * k)); s += t; } return s; };
-        double f[12], sum = 0.0;
-        for (int n = 0; n < ks; n++) {
-            const double r = 2.0 * n / (ks - 1) - 1.0;                       // torch.kaiser_window(periodic=False)
-            const double win = i0(beta * sqrt(1.0 - r * r)) / i0(beta);
-            const double tm = (n - half) + 0.5, xx = 2 * cutoff * tm;
-            const double sinc = fabs(xx) < 1e-12 ? 1.0 : sin(M_PI * xx) / (M_PI * xx);
-            f[n] = 2 * cutoff * win * sinc;
-            sum += f[n];
-        }
-        float ff[12];
-        for (int n = 0; n < ks; n++) ff[n] = (float)(f[n] / sum);
-        memcpy(v->filt_h, ff, sizeof(ff));
-    }
+    bv_aa_filter(v->filt_h);
     v->params.host.clear();
     v->finalized = true;
     return 0;
@@ -321,26 +330,51 @@ static GemmArgs conv_args(const BvConv& c, const Plane2& A, int M, int P, int T,
     return g;
 }
 
-static int bv_conv(f5hip_bigvgan* v, const BvConv& c, const Plane2& A, int M, int P, int T, const float* res, float* out, hipStream_t st) {
+// nsplit: operand planes (2 split bf16, 3 fp16, 1 bf16); conv5.h first where it covers the shape (nsplit >= 2), else gemm.h
+static int bv_conv(int nsplit, const BvConv& c, const Plane2& A, int M, int P, int T, const float* res, float* out, hipStream_t st) {
     GemmArgs g = conv_args(c, A, M, P, T, res, out);
-    return run_conv(v->nsplit, g, c.w, v->nsplit >= 2, true, c.w.n_pad % 128 ? 64 : 128, st);
+    return run_conv(nsplit, g, c.w, nsplit >= 2, true, c.w.n_pad % 128 ? 64 : 128, st);
 }
 
-// Activation1d over fp32 rows x [M][ch] -> the conv operand planes (out == nullptr) or fp32 rows out [M][ch]
-static int bv_snake(f5hip_bigvgan* v, const float* x, int ch, int cpad, int M, int P, int T, const float* alpha, const float* beta, float* out,
-                    hipStream_t st) {
+// Activation1d over fp32 rows x [M][ch] (sequences of pitch P rows, T valid): out_mode 0 -> fp32 rows out_f32 [M][ldo], 1 -> split-bf16
+// planes hi / lo [M][ldo], 2 -> one fp16 plane hi [M][ldo].  One lane per (channel, 16 time steps): cw channels x nseg segments fill the
+// 256 lanes of a workgroup (cw | ch, cw <= 64)
+static int bv_snake_launch(const float* x, int ch, int M, int P, int T, const float* alpha, const float* beta, const AaFilt& f, int out_mode,
+                           __bf16* hi, __bf16* lo, float* out_f32, int ldo, hipStream_t st) {
     constexpr int R = 16;
     int cw = ch < 64 ? ch : 64;
     while (ch % cw) cw--;
     if (ch == 96) cw = 32;   // 8 segments of 32 channels fill the 256 lanes; 64 would leave a half-empty second column block
     const int nseg = 256 / cw;
+    const dim3 grid(ch / cw, (T + nseg * R - 1) / (nseg * R), M / P);
+    if (out_mode == 0) hipLaunchKernelGGL((aa_snake2_kernel<R, 0>), grid, dim3(256), 0, st, x, ch, ch, cw, nseg, P, T, alpha, beta, f, (__bf16*)nullptr, (__bf16*)nullptr, out_f32, ldo);
+    else if (out_mode == 2) hipLaunchKernelGGL((aa_snake2_kernel<R, 2>), grid, dim3(256), 0, st, x, ch, ch, cw, nseg, P, T, alpha, beta, f, hi, (__bf16*)nullptr, (float*)nullptr, ldo);
+    else hipLaunchKernelGGL((aa_snake2_kernel<R, 1>), grid, dim3(256), 0, st, x, ch, ch, cw, nseg, P, T, alpha, beta, f, hi, lo, (float*)nullptr, ldo);
+    CKL("aa_snake2");
+    return 0;
+}
+
+// Activation1d over fp32 rows x [M][ch] -> the conv operand planes (out == nullptr) or fp32 rows out [M][ch]
+static int bv_snake(f5hip_bigvgan* v, const float* x, int ch, int cpad, int M, int P, int T, const float* alpha, const float* beta, float* out,
+                    hipStream_t st) {
     AaFilt f;
     memcpy(f.f, v->filt_h, sizeof(f.f));
-    const dim3 grid(ch / cw, (T + nseg * R - 1) / (nseg * R), M / P);
-    if (out) hipLaunchKernelGGL((aa_snake2_kernel<R, 0>), grid, dim3(256), 0, st, x, ch, ch, cw, nseg, P, T, alpha, beta, f, (__bf16*)nullptr, (__bf16*)nullptr, out, ch);
-    else if (v->nsplit == 3) hipLaunchKernelGGL((aa_snake2_kernel<R, 2>), grid, dim3(256), 0, st, x, ch, ch, cw, nseg, P, T, alpha, beta, f, v->act.hi, (__bf16*)nullptr, (float*)nullptr, cpad);
-    else hipLaunchKernelGGL((aa_snake2_kernel<R, 1>), grid, dim3(256), 0, st, x, ch, ch, cw, nseg, P, T, alpha, beta, f, v->act.hi, v->act.lo, (float*)nullptr, cpad);
-    CKL("aa_snake2");
+    if (out) return bv_snake_launch(x, ch, M, P, T, alpha, beta, f, 0, nullptr, nullptr, out, ch, st);
+    return bv_snake_launch(x, ch, M, P, T, alpha, beta, f, v->nsplit == 3 ? 2 : 1, v->act.hi, v->act.lo, nullptr, cpad, st);
+}
+
+// Dynamic LDS of bv_conv_post_kernel at C channels
+static size_t bv_conv_post_lds(int C) { return (size_t)(262 * (C + 1) + 7 * C) * sizeof(float); }
+
+// conv_post + clamp over fp32 rows a [batch P][lda] -> wave [batch][T].  variant 0: the LDS kernel when its tile fits in 48 KB, else the
+// naive kernel (what the generator runs); 1: the LDS kernel (fails when it would not fit); 2: the naive kernel
+static int bv_conv_post(const float* a, int lda, int C, int batch, int P, int T, const float* w, float* wave, int variant, hipStream_t st) {
+    const size_t lds = bv_conv_post_lds(C);
+    if (variant == 1 && lds > 48 * 1024) return fail(-1, "conv_post: the LDS kernel's tile does not fit at C = %d", C);
+    if (variant == 1 || (variant == 0 && lds <= 48 * 1024))
+        hipLaunchKernelGGL(bv_conv_post_kernel, dim3((T + 255) / 256, batch), dim3(256), lds, st, a, lda, C, P, T, w, wave);
+    else hipLaunchKernelGGL(bv_conv_post_naive_kernel, dim3((T + 255) / 256, batch), dim3(256), 0, st, a, lda, C, P, T, w, wave);
+    CKL("conv_post");
     return 0;
 }
 
@@ -376,7 +410,7 @@ int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const
     CKL("bv_mel_rows");
     int M = batch * P0, P = P0, T = T0;
     int ch = v->c0;
-    CK(bv_conv(v, v->pre, v->melp, M, P, T, nullptr, v->S, st));   // S = conv_pre(mel)
+    CK(bv_conv(v->nsplit, v->pre, v->melp, M, P, T, nullptr, v->S, st));   // S = conv_pre(mel)
     {   // operand planes of ups[0]
         const size_t n4 = (size_t)M * ch / 4;
         hipLaunchKernelGGL(bv_mean3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, v->S, v->S, v->S, 1, (size_t)M, ch, (float*)nullptr, v->act.hi, v->act.lo,
@@ -386,7 +420,7 @@ int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const
     for (int i = 0; i < v->n_up; i++) {
         const int r = c.upsample_rates[i], co = ch / 2, cpad = ceil_to(co, 32);
         // ups[i]: 3-tap implicit GEMM over the planes of the previous stage -> X viewed as [M][r*co] == [M*r][co]
-        CK(bv_conv(v, v->ups[i], v->act, M, P, T, nullptr, v->X, st));
+        CK(bv_conv(v->nsplit, v->ups[i], v->act, M, P, T, nullptr, v->X, st));
         M *= r; P *= r; T *= r; ch = co;
         if (cpad != ch) {   // padded channels of the A operand must read as zero
             if (hipMemsetAsync(v->act.hi, 0, (size_t)M * cpad * 2, st) != hipSuccess || (v->nsplit == 2 && hipMemsetAsync(v->act.lo, 0, (size_t)M * cpad * 2, st) != hipSuccess))
@@ -398,9 +432,9 @@ int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const
             for (int d = 0; d < 3; d++) {
                 const float* in = d == 0 ? v->X : y;   // AMPBlock1: x = x + convs2[d](act(convs1[d](act(x))))
                 CK(bv_snake(v, in, ch, cpad, M, P, T, rb.alpha[2 * d], rb.beta[2 * d], nullptr, st));
-                CK(bv_conv(v, rb.c1[d], v->act, M, P, T, nullptr, v->Tm, st));
+                CK(bv_conv(v->nsplit, rb.c1[d], v->act, M, P, T, nullptr, v->Tm, st));
                 CK(bv_snake(v, v->Tm, ch, cpad, M, P, T, rb.alpha[2 * d + 1], rb.beta[2 * d + 1], nullptr, st));
-                CK(bv_conv(v, rb.c2[d], v->act, M, P, T, in, y, st));
+                CK(bv_conv(v->nsplit, rb.c2[d], v->act, M, P, T, in, y, st));
             }
         }
         // mean of the three blocks: the last stage keeps fp32 rows for activation_post, the others only feed the next up-sampler
@@ -412,10 +446,7 @@ int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const
     }
     // activation_post -> fp32 (Tm), conv_post + clamp -> wave [B][T]
     CK(bv_snake(v, v->S, ch, ch, M, P, T, v->post_alpha, v->post_beta, v->Tm, st));
-    const size_t post_lds = (size_t)(262 * (ch + 1) + 7 * ch) * sizeof(float);
-    if (post_lds <= 48 * 1024) hipLaunchKernelGGL(bv_conv_post_kernel, dim3((T + 255) / 256, batch), dim3(256), post_lds, st, v->Tm, ch, ch, P, T, v->post_w, wave_dev);
-    else hipLaunchKernelGGL(bv_conv_post_naive_kernel, dim3((T + 255) / 256, batch), dim3(256), 0, st, v->Tm, ch, ch, P, T, v->post_w, wave_dev);
-    CKL("conv_post");
+    CK(bv_conv_post(v->Tm, ch, ch, batch, P, T, v->post_w, wave_dev, 0, st));
     prof_end(PROF_VOCOS, st);
     return 0;
 }

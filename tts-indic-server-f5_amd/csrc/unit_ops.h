@@ -392,3 +392,81 @@ extern "C" int f5hip_op_conv1d(int32_t batch, int32_t P, int32_t T, int32_t c_in
     bv_free_conv(c);
     return rc;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- BigVGAN unit ops
+// operand planes -> fp32, n elements: hi + lo (split bf16) or hi read as one fp16 plane
+__global__ __launch_bounds__(256) void op_planes_to_f32_kernel(const __bf16* hi, const __bf16* lo, int f16, size_t n, float* out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = f16 ? (float)reinterpret_cast<const _Float16*>(hi)[i] : (float)hi[i] + (float)lo[i];
+}
+
+// Activation1d(SnakeBeta) of the generator (bv_snake_launch: aa_snake2_kernel) over fp32 rows x [batch P][C], uniform sequences of pitch P
+// with T valid.  out_format 0: fp32 straight into out_dev; 1 / 2: split-bf16 / fp16 planes of out_rows rows, loaded from out_dev first (so
+// what the kernel does not write comes back as it was, up to that rounding) and read back into out_dev as fp32.
+extern "C" int f5hip_op_bigvgan_snake(int32_t batch, int32_t P, int32_t T, int32_t C, const float* x_dev, const float* alpha_log_dev,
+                                      const float* beta_log_dev, int32_t out_format, float* out_dev, int64_t out_rows, void* stream) {
+    if (batch <= 0 || P <= 0 || T <= 0 || T > P || C <= 0 || C % 4 || !x_dev || !alpha_log_dev || !beta_log_dev || !out_dev || out_format < 0 ||
+        out_format > 2 || out_rows < (int64_t)batch * P)
+        return fail(-1, "op_bigvgan_snake: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int M = batch * P;
+    AaFilt f;
+    bv_aa_filter(f.f);
+    OpBufs b;   // freed after the final synchronisation
+    int rc;
+    if (out_format == 0) {
+        rc = bv_snake_launch(x_dev, C, M, P, T, alpha_log_dev, beta_log_dev, f, 0, nullptr, nullptr, out_dev, C, st);
+    } else {
+        const size_t n = (size_t)out_rows * C, n4 = n / 4;
+        __bf16* hi = b.get<__bf16>(n); __bf16* lo = b.get<__bf16>(n);
+        if (!hi || !lo) return fail(-5, "op_bigvgan_snake: hipMalloc");
+        hipLaunchKernelGGL(bv_mean3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, out_dev, out_dev, out_dev, 1, (size_t)out_rows, C, (float*)nullptr,
+                           hi, lo, C, out_format == 2 ? 2 : 1);
+        rc = bv_snake_launch(x_dev, C, M, P, T, alpha_log_dev, beta_log_dev, f, out_format, hi, lo, nullptr, C, st);
+        if (!rc) hipLaunchKernelGGL(op_planes_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, hi, lo, out_format == 2 ? 1 : 0, n, out_dev);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(-7, "op_bigvgan_snake: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// One up-sampler of the generator: ConvTranspose1d(c_in -> c_out, k = 2 r, stride r, padding r / 2) + bias, packed by bv_pack_ups and run by
+// bv_conv (conv5.h where it covers the shape, else gemm.h).  x_dev fp32 [batch P][c_in] (P % 128 == 0, T valid), w_host [c_in][c_out][2 r],
+// bias_host [c_out] or NULL; out_dev fp32 [batch P r][c_out].  prec 2 = split bf16, 3 = one fp16 plane.
+extern "C" int f5hip_op_bigvgan_upsample(int32_t batch, int32_t P, int32_t T, int32_t c_in, int32_t c_out, int32_t r, const float* x_dev,
+                                         const float* w_host, const float* bias_host, float* out_dev, int32_t prec, void* stream) {
+    if (batch <= 0 || P <= 0 || T <= 0 || T > P || P % 128 || c_in <= 0 || c_in % 4 || c_out <= 0 || r < 2 || r % 2 || !x_dev || !w_host || !out_dev ||
+        (prec != 2 && prec != 3))
+        return fail(-1, "op_bigvgan_upsample: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int M = batch * P, cpad = ceil_to(c_in, 32);
+    std::vector<float> bias(c_out, 0.0f);
+    if (bias_host) bias.assign(bias_host, bias_host + c_out);
+    BvConv u;
+    if (bv_pack_ups(u, w_host, bias.data(), c_in, c_out, r, prec == 3)) return -4;
+    OpBufs b;
+    Plane2 A;
+    A.hi = b.get<__bf16>((size_t)M * cpad + 4096); A.lo = b.get<__bf16>((size_t)M * cpad + 4096);
+    if (!A.hi || !A.lo) { bv_free_conv(u); return fail(-5, "op_bigvgan_upsample: hipMalloc"); }
+    (void)hipMemsetAsync(A.hi, 0, ((size_t)M * cpad + 4096) * 2, st);
+    (void)hipMemsetAsync(A.lo, 0, ((size_t)M * cpad + 4096) * 2, st);
+    const size_t n4 = (size_t)M * c_in / 4;
+    hipLaunchKernelGGL(bv_mean3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x_dev, x_dev, x_dev, 1, (size_t)M, c_in, (float*)nullptr, A.hi, A.lo, cpad,
+                       prec == 3 ? 2 : 1);
+    int rc = bv_conv(prec, u, A, M, P, T, nullptr, out_dev, st);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(-6, "op_bigvgan_upsample: sync");
+    bv_free_conv(u);
+    return rc;
+}
+
+// conv_post + clamp of the generator (bv_conv_post): a_dev fp32 [batch P][C] (T valid rows per sequence), w_dev fp32 [C][7] (conv_post.weight),
+// wave_dev fp32 [batch][T].  variant 0: the generator's choice, 1: the LDS kernel (fails when its tile exceeds 48 KB), 2: the naive kernel.
+extern "C" int f5hip_op_bigvgan_conv_post(int32_t batch, int32_t P, int32_t T, int32_t C, const float* a_dev, const float* w_dev, int32_t variant,
+                                          float* wave_dev, void* stream) {
+    if (batch <= 0 || P <= 0 || T <= 0 || T > P || C <= 0 || !a_dev || !w_dev || !wave_dev || variant < 0 || variant > 2)
+        return fail(-1, "op_bigvgan_conv_post: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    int rc = bv_conv_post(a_dev, C, C, batch, P, T, w_dev, wave_dev, variant, st);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(-7, "op_bigvgan_conv_post: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}

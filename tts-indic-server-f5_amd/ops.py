@@ -109,6 +109,55 @@ def conv1d(x, weight, bias=None, res=None, *, batch, valid, dilation=1, prec=2, 
     return out, us.value, st
 
 
+# output formats of the BigVGAN snake op: fp32 rows, split-bf16 planes, one fp16 plane
+SNAKE_OUT_F32, SNAKE_OUT_SPLIT, SNAKE_OUT_F16 = 0, 1, 2
+
+
+def bigvgan_snake(x, alpha_log, beta_log, *, batch, valid, out_format=SNAKE_OUT_F32, out=None):
+    """The generator's Activation1d(SnakeBeta) over channel-last rows x fp32 [batch * P, C] (`valid` rows of each sequence are real).
+    out: optional fp32 [rows >= batch * P, C] the op writes into (rows it does not compute keep their contents, up to the format's
+    rounding); returns it."""
+    dev = x.device
+    x, alpha_log, beta_log = (_f32(t, dev) for t in (x, alpha_log, beta_log))
+    M, Cc = x.shape
+    if out is None:
+        out = torch.zeros(M, Cc, dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[1] == Cc and out.shape[0] >= M
+    _lib.check(_lib.lib().f5hip_op_bigvgan_snake(batch, M // batch, valid, Cc, _p(x), _p(alpha_log), _p(beta_log), out_format, _p(out),
+                                                 out.shape[0], _lib.current_stream_ptr()), "f5hip_op_bigvgan_snake")
+    return out
+
+
+def bigvgan_upsample(x, weight, bias=None, *, batch, valid, rate, prec=2):
+    """One generator up-sampler, ConvTranspose1d(c_in, c_out, 2 rate, stride rate, padding rate / 2) + bias, over channel-last rows
+    x fp32 [batch * P, c_in] (P % 128 == 0); weight [c_in, c_out, 2 rate] (nn.ConvTranspose1d layout).  Returns [batch * P * rate, c_out]."""
+    dev = x.device
+    x = _f32(x, dev)
+    c_in, c_out, k = weight.shape
+    assert k == 2 * rate
+    M = x.shape[0]
+    w = np.ascontiguousarray(weight.detach().to(torch.float32).cpu().numpy())
+    b = None if bias is None else np.ascontiguousarray(bias.detach().to(torch.float32).cpu().numpy())
+    out = torch.empty(M * rate, c_out, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().f5hip_op_bigvgan_upsample(batch, M // batch, valid, c_in, c_out, rate, _p(x), _p(w), _p(b), _p(out), prec,
+                                                    _lib.current_stream_ptr()), "f5hip_op_bigvgan_upsample")
+    return out
+
+
+def bigvgan_conv_post(a, weight, *, batch, valid, variant=0):
+    """The generator's conv_post (Conv1d(C, 1, 7, padding 3), no bias) + clamp(-1, 1) over channel-last rows a fp32 [batch * P, C];
+    weight [1, C, 7] or [C, 7].  variant 0 = the generator's choice, 1 = LDS-tiled kernel, 2 = the kernel without the tile.
+    Returns wave [batch, valid]."""
+    dev = a.device
+    a = _f32(a, dev)
+    M, Cc = a.shape
+    w = _f32(weight.reshape(Cc, 7), dev)
+    wave = torch.empty(batch, valid, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().f5hip_op_bigvgan_conv_post(batch, M // batch, valid, Cc, _p(a), _p(w), variant, _p(wave), _lib.current_stream_ptr()),
+               "f5hip_op_bigvgan_conv_post")
+    return wave
+
+
 def joint_attention(q, k, v, x_len, c_len, x_kvlen=None, *, heads, shape_invariant=-1, out_format=ATTN_OUT_SPLIT):
     """MMDiT joint attention: per sequence softmax(q [x ; c] k^T / 8 + mask on the padded audio keys) v over the concatenation of its audio
     rows and its text rows.  q / k / v fp32 [sum(x_len) + sum(c_len), 64 * heads]: all audio frames first, then all text tokens.

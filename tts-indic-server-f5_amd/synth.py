@@ -160,8 +160,15 @@ def bigvgan_param_specs(num_mels=100, upsample_rates=(4, 4, 2, 2, 2, 2), upsampl
     return s
 
 
-def bigvgan_state_dict(seed=SEED_BIGVGAN, **arch):
-    return make_state_dict(bigvgan_param_specs(**arch), seed)
+def bigvgan_state_dict(seed=SEED_BIGVGAN, snake_scale=None, **arch):
+    """snake_scale: standard deviation of the log-scale SnakeBeta alpha / beta (None: the default 0.2, N(0, 0.2^2) draws); the same draws are
+    rescaled, every other weight is unchanged."""
+    sd = make_state_dict(bigvgan_param_specs(**arch), seed)
+    if snake_scale is not None:
+        for name in sd:
+            if name.endswith(".act.alpha") or name.endswith(".act.beta"):
+                sd[name] = sd[name] * (snake_scale / 0.2)
+    return sd
 
 
 def _draw(shape, kind, g):
