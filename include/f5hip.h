@@ -66,7 +66,8 @@ int f5hip_dit_forward(f5hip_dit* m, int32_t n_seq, const int32_t* seq_len, const
                       const uint8_t* drop_audio_cond, const uint8_t* drop_text, int32_t n_blocks,
                       float* out_dev, float* h_out_dev, void* stream);
 
-/* Copies an internal fp32 activation of the last forward for parity taps: "text_embed" -> [sum(seq_len)][text_dim]. */
+/* Copies an internal fp32 activation of the last forward for parity taps: "text_embed" -> [sum(seq_len)][text_dim]; "text_rows" (MMDiT) ->
+ * the text stream's embedding as laid out, [text rows][text_dim] with every sequence's nt_max tokens padded to a multiple of 128 rows. */
 int f5hip_dit_read_tap(f5hip_dit* m, const char* tap, float* dst_dev, int64_t numel, void* stream);
 
 /* The ODE loop of CFM.sample (F/model/cfm.py:160-204): Euler over t_grid with classifier-free guidance,
@@ -226,6 +227,23 @@ int f5hip_op_bigvgan_upsample(int32_t batch, int32_t P, int32_t T, int32_t c_in,
  *   LDS-tiled kernel (fails when its tile exceeds 48 KB, C > 44), 2 = the kernel without the tile. */
 int f5hip_op_bigvgan_conv_post(int32_t batch, int32_t P, int32_t T, int32_t C, const float* a_dev, const float* w_dev, int32_t variant,
                                float* wave_dev, void* stream);
+/* f5hip_op_conv_pos_embed: the backbone's ConvPositionEmbedding, x + Mish(conv2(Mish(conv1(x)))) with two nn.Conv1d(D, D, 31, padding 15,
+ *   groups 16), over n_seq sequences of seq_len[s] frames (zero padding at the sequence bounds) laid out as the backbone lays them out.
+ *   x_dev fp32 [frames][D] (packed, D % 128 == 0, D <= 1024), w*_host [D][D / 16][31], b*_host [D].  lead = 1: a time-token row heads every
+ *   sequence (UNetT).  impl 5 = conv5.h (prec 2, lead 0 only), 0 = gemm.h; prec 2 = split bf16, 1 = bf16.  pad_nan = 1: padding rows, time-token
+ *   rows and the slack behind the last row of the internal buffers hold NaN instead of 0.  out_dev fp32 [frames][D]; c1_dev (or NULL) fp32
+ *   [frames][D] receives stage 1 as the second convolution reads it (hi + lo planes, the hi plane alone at prec 1). */
+int f5hip_op_conv_pos_embed(int32_t n_seq, const int32_t* seq_len, int32_t lead, int32_t D, const float* x_dev, const float* w1_host,
+                            const float* b1_host, const float* w2_host, const float* b2_host, int32_t impl, int32_t prec, int32_t pad_nan,
+                            float* out_dev, float* c1_dev, void* stream);
+/* f5hip_op_convnext_block: one ConvNeXtV2 text block (depthwise conv k 7 + LayerNorm, pwconv1 + GELU, GRN over each sequence, pwconv2 +
+ *   residual) as the backbone runs it, in split bf16, over n_seq sequences of seq_len[s] tokens.  x_dev fp32 [tokens][Td] (packed,
+ *   Td % 32 == 0); params_host: 10 host fp32 arrays dwconv.weight, dwconv.bias, norm.weight, norm.bias, pwconv1.weight, pwconv1.bias,
+ *   grn.gamma, grn.beta, pwconv2.weight, pwconv2.bias (module layouts).  pad_nan as above.  out_dev fp32 [tokens][Td]; each tap (or NULL)
+ *   receives a stage as the next kernel reads it: tap_ln_dev [tokens][Td] dwconv + LayerNorm, tap_ty_dev [tokens][2 Td] pwconv1 + GELU,
+ *   tap_grn_dev [tokens][2 Td] GRN. */
+int f5hip_op_convnext_block(int32_t n_seq, const int32_t* seq_len, int32_t Td, const float* x_dev, const float* const* params_host,
+                            int32_t pad_nan, float* out_dev, float* tap_ln_dev, float* tap_ty_dev, float* tap_grn_dev, void* stream);
 
 /* ---------------------------------------------------------------- Vocos vocoder ----------------------- */
 

@@ -113,9 +113,10 @@ def lens_to_mask(lens: torch.Tensor, length: int | None = None) -> torch.Tensor:
 
 
 def sinus_time_embed(t: torch.Tensor, dim: int = 256, scale: float = 1000.0) -> torch.Tensor:
-    """F/model/modules.py:154-161: [sin(1000 t f_k) || cos(..)], f_k = exp(-k ln(1e4)/(half-1))."""
+    """F/model/modules.py:154-161: [sin(1000 t f_k) || cos(..)], f_k = exp(-k ln(1e4)/(half-1)); in t's floating dtype."""
     half = dim // 2
-    f = torch.exp(torch.arange(half).float() * -(math.log(10000) / (half - 1)))
+    dt = t.dtype if t.is_floating_point() else torch.float32
+    f = torch.exp(torch.arange(half, dtype=dt) * -(math.log(10000) / (half - 1)))
     e = scale * t[:, None] * f[None, :]
     return torch.cat((e.sin(), e.cos()), dim=-1)
 
@@ -128,11 +129,12 @@ def time_embed(sd, t: torch.Tensor, p="transformer.time_embed.") -> torch.Tensor
     return F.linear(h, sd[p + "time_mlp.2.weight"], sd[p + "time_mlp.2.bias"])
 
 
-def text_pos_table(dim: int, end: int = 4096, theta: float = 10000.0) -> torch.Tensor:
-    """precompute_freqs_cis, F/model/modules.py:196-207: [cos(pos w_j) || sin(pos w_j)]."""
+def text_pos_table(dim: int, end: int = 4096, theta: float = 10000.0, dtype=torch.float32) -> torch.Tensor:
+    """precompute_freqs_cis, F/model/modules.py:196-207: [cos(pos w_j) || sin(pos w_j)].  The reference computes the table in fp32 (so
+    does the library: fp32 frequency and angle), so another `dtype` only widens the fp32 table."""
     w = 1.0 / (theta ** (torch.arange(0, dim, 2)[: dim // 2].float() / dim))
     ang = torch.outer(torch.arange(end), w).float()
-    return torch.cat([ang.cos(), ang.sin()], dim=-1)
+    return torch.cat([ang.cos(), ang.sin()], dim=-1).to(dtype)
 
 
 def grn(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
@@ -158,7 +160,7 @@ def convnext_v2_block(sd, p: str, x: torch.Tensor) -> torch.Tensor:
 
 def text_embed(sd, cfg: DiTConfig, text: torch.Tensor, seq_len: int, drop_text: bool,
                p="transformer.text_embed.") -> torch.Tensor:
-    """TextEmbedding.forward, F/model/backbones/dit.py:47-69."""
+    """TextEmbedding.forward, F/model/backbones/dit.py:47-69; in the embedding's dtype."""
     ids = (text + 1)[:, :seq_len]
     ids = F.pad(ids, (0, seq_len - ids.shape[1]), value=0)
     if drop_text:
@@ -166,7 +168,7 @@ def text_embed(sd, cfg: DiTConfig, text: torch.Tensor, seq_len: int, drop_text: 
     e = F.embedding(ids, sd[p + "text_embed.weight"])
     if cfg.conv_layers > 0:
         pos = torch.arange(seq_len).clamp(max=4095)  # get_pos_embed_indices, modules.py:210-219
-        e = e + text_pos_table(cfg.text_dim)[pos][None]
+        e = e + text_pos_table(cfg.text_dim, dtype=e.dtype)[pos][None]
         for i in range(cfg.conv_layers):
             e = convnext_v2_block(sd, f"{p}text_blocks.{i}.", e)
     return e
@@ -391,7 +393,7 @@ def mmdit_text_embed(sd, cfg: MMDiTConfig, text: torch.Tensor, drop_text: bool, 
         ids = torch.zeros_like(ids)
     e = F.embedding(ids, sd[p + "text_embed.weight"])
     pos = torch.arange(ids.shape[1]).clamp(max=1023)
-    return e + text_pos_table(cfg.dim, end=1024)[pos][None]
+    return e + text_pos_table(cfg.dim, end=1024, dtype=e.dtype)[pos][None]
 
 
 def mmdit_audio_embed(sd, x, cond, drop_audio_cond: bool, p="transformer.audio_embed.") -> torch.Tensor:

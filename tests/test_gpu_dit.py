@@ -333,3 +333,107 @@ def test_torch_custom_ops_equal_the_ctypes_path(tiny_model):
     finally:
         torch_ops._loaded = True
     assert torch.equal(via_ops, via_ctypes) and torch.equal(w_ops, w_ctypes)
+
+
+# ---------------------------------------------------------------- input side (text embedding, input embedding + conv position embedding) vs float64
+def _forward_ragged(model, seq_len, x, cond, text, drop_text):
+    """f5hip_dit_forward with per-sequence lengths and n_blocks = 0: the packed frames' h after the input embedding (+ conv position
+    embedding), [sum(seq_len), dim]"""
+    from tts_indic_server_f5_amd import _lib
+    import ctypes as C
+    n = len(seq_len)
+    sl = np.ascontiguousarray(np.asarray(seq_len, dtype=np.int32))
+    tx = np.ascontiguousarray(text.numpy().astype(np.int32))
+    da = np.zeros(n, dtype=np.uint8)
+    dt = np.ascontiguousarray(np.asarray(drop_text, dtype=np.uint8))
+    xd, cd = x.to(model.device).contiguous(), cond.to(model.device).contiguous()
+    h = torch.empty(int(sl.sum()), model.arch.dim, device=model.device, dtype=torch.float32)
+    p = lambda a: C.c_void_p(a.ctypes.data) if isinstance(a, np.ndarray) else C.c_void_p(a.data_ptr())
+    _lib.check(model._lib.f5hip_dit_forward(model._h, n, p(sl), p(sl), p(xd), p(cd), p(tx), tx.shape[1], 0.3, p(da), p(dt), 0, None, p(h),
+                                            _lib.current_stream_ptr()), "f5hip_dit_forward")
+    return h
+
+
+def _ragged_inputs(seq_len, nt, vocab, seed):
+    g = torch.Generator().manual_seed(seed)
+    frames = sum(seq_len)
+    x = torch.randn(frames, 100, generator=g)
+    cond = torch.randn(frames, 100, generator=g)
+    text = torch.randint(0, vocab, (len(seq_len), nt), generator=g)
+    return x, cond, text
+
+
+def _max_report(tag, got, ref, bound):
+    """max |got - ref| relative to max |ref|"""
+    e = (got.double().cpu() - ref).abs().max().item() / ref.abs().max().item()
+    print(f"[parity] {tag}: max err / max|ref| {e:.3e} (bound {bound:.0e})")
+    return e
+
+
+def test_base_ragged_input_side_vs_fp64(base_model):
+    """F5-Base width, a ragged batch of 3 (37, 129, 1404 frames): a text longer than its sequence (truncated), one shorter (filler 0 behind
+    it), one dropped.  The text embedding (4 ConvNeXtV2 blocks at text_dim 512) and the input embedding + conv position embedding against
+    the float64 oracle per sequence, max error relative to the sequence's max |ref|.  Measured on an MI355X, in both modes: text embedding
+    4.6e-6 .. 6.2e-6, input + conv position embedding 7.5e-6 .. 8.3e-6; the bound is 3e-5."""
+    seq_len = [37, 129, 1404]
+    x, cond, text = _ragged_inputs(seq_len, 300, 2545, 71)
+    text[1, 90:] = -1                                 # 90 tokens for 129 frames; sequence 0 has 300 for 37 frames
+    drop = [0, 0, 1]
+    h = _forward_ragged(base_model, seq_len, x, cond, text, drop).cpu()
+    te = base_model.read_tap("text_embed", sum(seq_len), 512).cpu()
+    sd = {k: v.double() for k, v in synth.dit_state_dict().items() if ".text_embed." in k or ".input_embed." in k}
+    cfg = O.DiTConfig()
+    f0 = 0
+    for i, n in enumerate(seq_len):
+        r_te = O.text_embed(sd, cfg, text[i:i + 1], n, bool(drop[i]))[0]
+        r_h = O.input_embed(sd, x[None, f0:f0 + n].double(), cond[None, f0:f0 + n].double(), r_te[None], False)[0]
+        assert _max_report(f"base ragged seq {i} (n {n}) text_embed", te[f0:f0 + n], r_te, 3e-5) < 3e-5
+        assert _max_report(f"base ragged seq {i} (n {n}) input + conv pos embed", h[f0:f0 + n], r_h, 3e-5) < 3e-5
+        f0 += n
+
+
+def test_e2_base_ragged_input_side_vs_fp64():
+    """E2-Base (UNetT layout: a time-token row heads every sequence, conv position embedding on gemm.h): the n_blocks = 0 output of a ragged
+    batch of 3 against the float64 oracle per sequence.  Measured on an MI355X: 5.1e-6 .. 6.3e-6 of max|ref|; the bound is 3e-5."""
+    from tts_indic_server_f5_amd.model import E2TTS_BASE, F5HipModel
+    m = F5HipModel(E2TTS_BASE, synth.unett_state_dict())
+    seq_len = [37, 129, 1404]
+    x, cond, text = _ragged_inputs(seq_len, 300, 2545, 72)
+    text[1, 90:] = -1
+    drop = [0, 0, 1]
+    h = _forward_ragged(m, seq_len, x, cond, text, drop).cpu()
+    sd = {k: v.double() for k, v in synth.unett_state_dict().items() if ".text_embed." in k or ".input_embed." in k}
+    cfg = O.UNetTConfig()
+    f0 = 0
+    for i, n in enumerate(seq_len):
+        r_te = O.text_embed(sd, cfg, text[i:i + 1], n, bool(drop[i]))
+        r_h = O.input_embed(sd, x[None, f0:f0 + n].double(), cond[None, f0:f0 + n].double(), r_te, False)[0]
+        assert _max_report(f"E2 base ragged seq {i} (n {n}) input + conv pos embed", h[f0:f0 + n], r_h, 3e-5) < 3e-5
+        f0 += n
+
+
+def test_mmdit_long_text_position_clamp_vs_fp64():
+    """MMDiT with 1100 text tokens: positions 1023 .. 1099 all take row 1023 of the position table (get_pos_embed_indices clamps below
+    max_pos = 1024).  The text stream's embedding against mmdit_text_embed in float64, for a kept and a dropped text.  The device sums two
+    fp32 values (one rounding, 2^-24 of the result) but its position table comes from the host's libm, torch's from its own fp32 kernels:
+    entries of magnitude <= 1 differ by up to 1.2e-7 (measured on CPU over the whole DiT table).  Bound per element: the rounding of the
+    sum (2^-24 |ref|, doubled) plus twice that table disagreement, 2^-23 |ref| + 2^-22."""
+    from tts_indic_server_f5_amd.model import F5HipModel, MMDiTArch
+    sd32 = synth.mmdit_state_dict(**MMTINY)
+    m = F5HipModel(MMDiTArch(**MMTINY), sd32)
+    cfg = O.MMDiTConfig(**MMTINY)
+    sd = {k: v.double() for k, v in sd32.items() if ".text_embed." in k}
+    seq_len, nt = [60, 200], 1100
+    x, cond, text = _ragged_inputs(seq_len, nt, 40, 73)
+    text[0, 1050:] = -1
+    drop = [0, 1]
+    _forward_ragged(m, seq_len, x, cond, text, drop)
+    pitch = (nt + 127) // 128 * 128
+    rows = m.read_tap("text_rows", len(seq_len) * pitch, cfg.dim).cpu()
+    for i in range(len(seq_len)):
+        ref = O.mmdit_text_embed(sd, cfg, text[i:i + 1], bool(drop[i]))[0]
+        got = rows[i * pitch:i * pitch + nt].double()
+        r = ((got - ref).abs() / (2.0 ** -23 * ref.abs() + 2.0 ** -22)).max().item()
+        print(f"[parity] mmdit text embed, {nt} tokens, seq {i} (drop {drop[i]}): max err {(got - ref).abs().max().item():.3e}, "
+              f"max err / bound {r:.3f}")
+        assert r <= 1.0

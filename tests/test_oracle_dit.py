@@ -212,3 +212,69 @@ def test_mmdit_oracle_vs_reference_fixture(golden_dir):
     out, _ = O.cfm_sample(sd, cfg, g["sample_cond"], g["sample_text"], 48, steps=8, cfg_strength=2.0, sway_sampling_coef=-1.0, seed=7,
                           forward_fn=lambda **kw: O.mmdit_forward(sd, cfg, **kw), keep_trajectory=False)
     _close(out, g["sample_out"], atol=5e-4, rtol=1e-4)
+
+
+def test_input_side_oracle_follows_dtype_fp32_bits_unchanged():
+    """text_pos_table, sinus_time_embed, text_embed, mmdit_text_embed, conv_pos_embed and input_embed follow their input's dtype; with fp32
+    inputs they are bit-identical to the fp32-only formulas they replace.  The position table stays fp32 data (the reference and the library
+    compute it in fp32) and is only widened for a float64 caller."""
+    import math
+    import torch.nn.functional as F
+
+    def pos_table_fp32(dim, end=4096):
+        w = 1.0 / (10000.0 ** (torch.arange(0, dim, 2)[: dim // 2].float() / dim))
+        ang = torch.outer(torch.arange(end), w).float()
+        return torch.cat([ang.cos(), ang.sin()], dim=-1)
+
+    def sinus_fp32(t, dim=256):
+        half = dim // 2
+        f = torch.exp(torch.arange(half).float() * -(math.log(10000) / (half - 1)))
+        e = 1000.0 * t[:, None] * f[None, :]
+        return torch.cat((e.sin(), e.cos()), dim=-1)
+
+    for dim, end in ((512, 4096), (64, 4096), (128, 1024)):
+        t32 = O.text_pos_table(dim, end=end)
+        assert t32.dtype == torch.float32 and torch.equal(t32, pos_table_fp32(dim, end))
+        t64 = O.text_pos_table(dim, end=end, dtype=torch.float64)
+        assert t64.dtype == torch.float64 and torch.equal(t64, t32.double())
+    t = torch.tensor([0.0, 0.25, 0.9])
+    assert torch.equal(O.sinus_time_embed(t), sinus_fp32(t))
+    s64 = O.sinus_time_embed(t.double())
+    assert s64.dtype == torch.float64 and (s64 - sinus_fp32(t).double()).abs().max() < 1e-4
+
+    sd = synth.dit_state_dict(**TINY)
+    g = torch.Generator().manual_seed(5)
+    text = torch.randint(0, 40, (1, 30), generator=g)
+    text[0, 20:] = -1
+    n = 45
+    te = O.text_embed(sd, TINY_CFG, text, n, False)
+    ids = F.pad((text + 1)[:, :n], (0, n - 30), value=0)
+    e = F.embedding(ids, sd["transformer.text_embed.text_embed.weight"]) + pos_table_fp32(TINY["text_dim"])[torch.arange(n)][None]
+    for i in range(TINY["conv_layers"]):
+        e = O.convnext_v2_block(sd, f"transformer.text_embed.text_blocks.{i}.", e)
+    assert te.dtype == torch.float32 and torch.equal(te, e)
+    x = torch.randn(1, n, 100, generator=g)
+    cond = torch.randn(1, n, 100, generator=g)
+    ie = O.input_embed(sd, x, cond, te, False)
+    p = "transformer.input_embed."
+    h = F.linear(torch.cat((x, cond, te), dim=-1), sd[p + "proj.weight"], sd[p + "proj.bias"])
+    y = h.permute(0, 2, 1)
+    for k in (0, 2):
+        y = F.mish(F.conv1d(y, sd[f"{p}conv_pos_embed.conv1d.{k}.weight"], sd[f"{p}conv_pos_embed.conv1d.{k}.bias"], padding=15, groups=16))
+    assert ie.dtype == torch.float32 and torch.equal(ie, y.permute(0, 2, 1) + h)
+
+    sd64 = {k: v.double() for k, v in sd.items()}
+    te64 = O.text_embed(sd64, TINY_CFG, text, n, False)
+    ie64 = O.input_embed(sd64, x.double(), cond.double(), te64, False)
+    assert te64.dtype == ie64.dtype == torch.float64
+    assert (te64 - te.double()).abs().max() < 1e-4 and (ie64 - ie.double()).abs().max() < 1e-4
+
+    mcfg = O.MMDiTConfig(dim=128, depth=3, heads=2, ff_mult=2, text_num_embeds=40)
+    msd = synth.mmdit_state_dict(dim=128, depth=3, heads=2, ff_mult=2, text_num_embeds=40)
+    long_text = torch.randint(0, 40, (1, 1100), generator=g)
+    mt = O.mmdit_text_embed(msd, mcfg, long_text, False)
+    me = F.embedding(long_text + 1, msd["transformer.text_embed.text_embed.weight"]) + \
+        pos_table_fp32(128, 1024)[torch.arange(1100).clamp(max=1023)][None]
+    assert mt.dtype == torch.float32 and torch.equal(mt, me)
+    mt64 = O.mmdit_text_embed({k: v.double() for k, v in msd.items()}, mcfg, long_text, False)
+    assert mt64.dtype == torch.float64 and (mt64 - me.double()).abs().max() < 1e-6

@@ -3,6 +3,8 @@
 //
 //     out[t][n] = bias[n] + sum_tap sum_c A[t + (tap - center) * dil][c] * W[n][tap][c]  (+ res[t][n]),   A rows outside the sequence = 0
 //
+// (grouped: c runs over the conv_group_cols channels of the output column's group; channels past them read as 0, whatever A holds there)
+//
 // gemm.h runs this as a GEMM whose A tile is re-read from L2 for every tap.  Here the rows a 256-row output tile depends on -- the
 // WINDOW, 256 + 2 * center * dil rows of one channel chunk -- are brought into LDS ONCE per chunk, and every tap reads its MFMA fragments
 // from that image at a row offset; only the weight tile of the (chunk, tap) streams through a ring.  Per k-step the L2 -> LDS fill drops
@@ -158,7 +160,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Conv5Cfg<NP
                 const int pl = idx / win_pieces, rem = idx - pl * win_pieces;
                 const int w = rem / CPR, c = rem - w * CPR;
                 const int g = m0 - halo + w;
-                const bool ok = g >= sstart && g < send;          // (the select sits here, not behind the load: the data is first touched now)
+                // (the select sits here, not behind the load: the data is first touched now).  Grouped convolution: a group narrower than
+                // the 64-channel window (conv_group_cols < 64) reads the next group's channels -- or, for the last group, the next row's --
+                // under zero weights; they are zeroed too, so that a NaN or Inf there cannot reach the group (0 * NaN = NaN)
+                const bool ok = g >= sstart && g < send && (RBW == 2 || chunk * CKC + c * 8 < p.conv_group_cols);
                 if (idx < win_total) *reinterpret_cast<u32x4*>(dstb + pl * win_plane + c5_off<ROWB>(w, c)) = ok ? v[i] : (u32x4){0u, 0u, 0u, 0u};
             }
         };

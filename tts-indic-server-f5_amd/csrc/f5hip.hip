@@ -161,6 +161,21 @@ int f5hip_dit_load_param(f5hip_dit* m, const char* name, const float* data, int6
 #define CK(x) do { int _r = (x); if (_r) return _r; } while (0)
 #define CKL(name) do { hipError_t _e = hipGetLastError(); if (_e != hipSuccess) return fail(-7, "%s launch: %s", name, hipGetErrorString(_e)); } while (0)
 
+// One grouped Conv1d(D, D, 31, groups 16) of ConvPositionEmbedding, w [D][D / 16][31] (nn.Conv1d layout), b [D], as 16 implicit GEMMs:
+// group g is output rows g * 64 .. + 64 and K = 31 taps x 64 channels, each padded with zero weights from D / 16 to 64.
+static int pack_conv_pos(PackedW& out, const float* w, const float* b, int D) {
+    const int gw = D / 16, K = 31 * 64;
+    std::vector<float> wp((size_t)16 * 64 * K, 0.0f), bp(16 * 64, 0.0f);
+    for (int g = 0; g < 16; g++)
+        for (int co = 0; co < gw; co++) {
+            bp[g * 64 + co] = b[g * gw + co];
+            for (int ci = 0; ci < gw; ci++)
+                for (int tap = 0; tap < 31; tap++)
+                    wp[((size_t)(g * 64 + co)) * K + tap * 64 + ci] = w[((size_t)(g * gw + co) * gw + ci) * 31 + tap];
+        }
+    return pack_linear(out, wp.data(), 16 * 64, K, K, bp.data());
+}
+
 // Packs one stream's block-l linears: q | k | v concatenated into one [3 D, D] weight, the out projection `out` and the feed-forward `ff`
 // (FF1 and the QKV weight also in fragment order: the W-direct gemm5 kernels).  `attn` + to_{q,k,v} + `qkv_sfx` name the q / k / v
 // linears; `out` empty: a block without out projection and feed-forward (MMDiT's last, context-pre-only text block).
@@ -284,20 +299,10 @@ int f5hip_dit_finalize(f5hip_dit* m) {
     }
     // --- conv_pos_embed: grouped Conv1d(D, D, 31, groups 16) as 16 implicit GEMMs, each padded to 64 x (31 x 64) ---
     for (int which = 0; which < 2; which++) {
-        const int gw = m->gw;
         std::string p = T + (m->arch == 2 ? "audio_embed" : "input_embed") + ".conv_pos_embed.conv1d." + std::to_string(which * 2) + ".";
-        GET_PARAM(w, P, p + "weight", (int64_t)D * gw * 31);
+        GET_PARAM(w, P, p + "weight", (int64_t)D * m->gw * 31);
         GET_PARAM(b, P, p + "bias", D);
-        const int K = 31 * 64;
-        std::vector<float> wp((size_t)16 * 64 * K, 0.0f), bp(16 * 64, 0.0f);
-        for (int g = 0; g < 16; g++)
-            for (int co = 0; co < gw; co++) {
-                bp[g * 64 + co] = (*b)[g * gw + co];
-                for (int ci = 0; ci < gw; ci++)
-                    for (int tap = 0; tap < 31; tap++)
-                        wp[((size_t)(g * 64 + co)) * K + tap * 64 + ci] = (*w)[((size_t)(g * gw + co) * gw + ci) * 31 + tap];
-            }
-        if (pack_linear(which ? m->conv2 : m->conv1, wp.data(), 16 * 64, K, K, bp.data())) return -4;
+        if (pack_conv_pos(which ? m->conv2 : m->conv1, w->data(), b->data(), D)) return -4;
     }
     // --- transformer blocks ---
     m->blk.resize(c.depth);
@@ -378,6 +383,18 @@ static int ensure_workspace(f5hip_dit* m, int rows_pad, int frames, int n_seq) {
     return 0;
 }
 
+// The packed row layout: every sequence starts at a multiple of 128 rows and takes ceil128(lead + len) rows.  Its `lead` leading rows (UNetT:
+// the time token) belong to it (row_seq) but keep start = end = 0, an empty convolution window; its frames r0 + lead .. + len carry the
+// sequence bounds [r0 + lead, r0 + lead + len).  Rows outside every sequence keep the defaults: start = end = 0, row_seq = -1.
+static int seq_rows(int len, int lead) { return ceil_to(len + lead, 128); }
+static void set_seq_bounds(int* row_start, int* row_end, int* row_seq, int r0, int lead, int len, int s) {
+    for (int j = 0; j < lead; j++) row_seq[r0 + j] = s;
+    for (int i = 0; i < len; i++) {
+        const int r = r0 + lead + i;
+        row_start[r] = r0 + lead; row_end[r] = r0 + lead + len; row_seq[r] = s;
+    }
+}
+
 struct SeqDesc { int len, kvlen, frame0 /* first frame in caller's packed arrays */, text_row, drop_audio, drop_text, branch /* 0 cond, 1 uncond */;
                  int c_len = 0 /* MMDiT: rows of the text stream (tokens incl. filler positions, as the reference's [b, nt] text tensor has them) */; };
 
@@ -389,11 +406,11 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
     const int extra = m->arch == 1 ? 1 : 0;
     const bool mm = m->arch == 2;
     int rows = 0, rows_x = 0;
-    for (auto& s : seqs) rows += ceil_to(s.len + extra, 128);
+    for (auto& s : seqs) rows += seq_rows(s.len, extra);
     rows_x = rows;
     if (mm) for (auto& s : seqs) {
         if (s.c_len <= 0 || s.c_len > 4096) return fail(-1, "MMDiT: a sequence needs 1..4096 text positions (got %d)", s.c_len);
-        rows += ceil_to(s.c_len, 128);
+        rows += seq_rows(s.c_len, 0);
     }
     if (ensure_workspace(m, rows, n_frames, (int)seqs.size())) return -5;
     const int R = rows, S = (int)seqs.size(), U = n_frames;
@@ -416,11 +433,11 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
         seq_row0[s] = r0; seq_len[s] = q.len + extra; seq_kvlen[s] = q.kvlen + extra;
         m->max_len = std::max(m->max_len, q.len + extra);
         if (q.kvlen < q.len) m->any_masked = true;
-        if (extra) { row_pos[r0] = 0; row_seq[r0] = s; row_keep[r0] = 1; }   // time token: start = end = 0 keeps it out of the convs
+        if (extra) { row_pos[r0] = 0; row_keep[r0] = 1; }   // time token: start = end = 0 keeps it out of the convs
+        set_seq_bounds(row_start, row_end, row_seq, r0, extra, q.len, s);
         for (int i = 0; i < q.len; i++) {
             const int r = r0 + extra + i;
             row_pos[r] = i + extra;                                   // rotary position (time token = 0)
-            row_start[r] = r0 + extra; row_end[r] = r0 + extra + q.len; row_seq[r] = s;
             int tok = 0;
             if (!q.drop_text && i < nt_max) tok = text[(size_t)q.text_row * nt_max + i] + 1;   // -1 pad -> filler 0
             // nn.Embedding raises IndexError on an id outside the table; here it would be an out-of-bounds read on the GPU
@@ -432,7 +449,7 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
             row_keep[r] = i < q.kvlen ? 1 : 0;
             (q.branch ? urow_u : urow_c)[q.frame0 + i] = r;
         }
-        r0 += ceil_to(q.len + extra, 128);
+        r0 += seq_rows(q.len, extra);
         m->h_seq_row0[s + 1] = r0;
     }
     int* jm = fic + U;   // MMDiT joint attention: 6 arrays of 2 S pseudo-sequences (2 s: audio queries of sequence s, 2 s + 1: its text queries)
@@ -440,12 +457,13 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
         int rc0 = rows_x;
         for (int s = 0; s < S; s++) {
             const SeqDesc& q = seqs[s];
+            set_seq_bounds(row_start, row_end, row_seq, rc0, 0, q.c_len, s);
             for (int i = 0; i < q.c_len; i++) {
                 const int r = rc0 + i;
                 int tok = 0;   // filler (the reference feeds text + 1 with -1 padding -> 0; all ids 0 when the text is dropped: mmdit.py:38-40)
                 if (!q.drop_text && i < nt_max) tok = text[(size_t)q.text_row * nt_max + i] + 1;
                 if (tok < 0 || tok > m->cfg.text_num_embeds) return fail(-1, "text token %d of sequence %d is outside the vocabulary (0..%d)", tok - 1, s, m->cfg.text_num_embeds - 1);
-                row_pos[r] = i; row_seq[r] = s; row_token[r] = tok; row_keep[r] = 1; row_start[r] = rc0; row_end[r] = rc0 + q.c_len;
+                row_pos[r] = i; row_token[r] = tok; row_keep[r] = 1;
             }
             for (int qd = 0; qd < 2; qd++) {
                 const int j = 2 * s + qd;
@@ -457,7 +475,7 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
                 jm[10 * S + j] = q.c_len;
             }
             m->max_len = std::max(m->max_len, q.c_len);
-            rc0 += ceil_to(q.c_len, 128);
+            rc0 += seq_rows(q.c_len, 0);
             m->h_seqc_row0[s + 1] = rc0;
         }
     }
@@ -620,6 +638,33 @@ extern "C" int f5hip_get_counter(const char* name, int64_t* value) {
 // -------------------------------------------------------------------------------------------------
 // step-invariant precompute: text embedding for every sequence, cond/text part of the input projection
 // -------------------------------------------------------------------------------------------------
+// One ConvNeXtV2 text block (F/model/modules.py:259-269) over the M rows of the layout, in place on te [M][Td]: the depthwise conv (k 7, zero
+// padding at the row bounds row_start / row_end) + LayerNorm into the planes tn, pw1 + GELU (erf) into ty [M][2 Td], the GRN column norms of
+// every sequence (rows seq_row0[s] .. + seq_len[s]) into gx [n_seq][2 Td], GRN into the planes tg (rows with row_seq < 0 are skipped), then
+// te += pw2; out_hi (or null) also receives the block output as split-bf16 planes of pitch ldob.  Operands in `nsplit` planes.
+static int run_text_block(int nsplit, const TextBlock& b, int Td, int M, int n_seq, float* te, const Plane2& tn, float* ty, const Plane2& tg,
+                          float* gx, const int* row_start, const int* row_end, const int* row_seq, const int* seq_row0, const int* seq_len,
+                          __bf16* out_hi, __bf16* out_lo, int ldob, hipStream_t st) {
+    LnArgs ln = ln_args(te, Td, M, Td, b.ln_w, b.ln_b, 0.0f, 1e-6f);
+    ln.dw_w = b.dw_w; ln.dw_b = b.dw_b; ln.row_seq_start = row_start; ln.row_seq_end = row_end;
+    ln.out_hi = tn.hi; ln.out_lo = tn.lo; ln.ldo = Td;
+    CK(run_ln(ln, st));
+    GemmArgs g1 = gemm_base(tn, Td, b.pw1, M);
+    g1.act = ACT_GELU_ERF; g1.out_f32 = ty; g1.ldo = 2 * Td;
+    CK(run_gemm_n(b.pw1.f16 ? 3 : nsplit, M, g1, b.pw1, EPI_GENERIC, false, 128, st));
+    prof_begin(PROF_OTHER, st);
+    hipLaunchKernelGGL(grn_stats_kernel, dim3((2 * Td + 255) / 256, n_seq), dim3(256), 0, st, ty, 2 * Td, 2 * Td, seq_row0, seq_len, gx);
+    CKL("grn_stats");
+    hipLaunchKernelGGL(grn_apply_kernel, dim3((M + 3) / 4), dim3(256), 0, st, ty, 2 * Td, 2 * Td, M, row_seq, gx, b.gamma, b.beta, tg.hi, tg.lo,
+                       2 * Td);
+    CKL("grn_apply");
+    prof_end(PROF_OTHER, st);
+    GemmArgs g2 = gemm_base(tg, 2 * Td, b.pw2, M);
+    g2.res = te; g2.ldres = Td; g2.out_f32 = te; g2.ldo = Td;
+    if (out_hi) { g2.out_hi = out_hi; g2.out_lo = out_lo; g2.ldob = ldob; }
+    return run_gemm_n(b.pw2.f16 ? 3 : nsplit, M, g2, b.pw2, EPI_GENERIC, false, 128, st);
+}
+
 static int precompute_text_and_ce(f5hip_dit* m, const float* cond_dev, hipStream_t st) {
     const f5hip_dit_config& c = m->cfg;
     const int D = c.dim, Td = c.text_dim, M = m->M, Kct = 128 + m->td_pad;
@@ -641,26 +686,9 @@ static int precompute_text_and_ce(f5hip_dit* m, const float* cond_dev, hipStream
     CKL("split cond");
     prof_end(PROF_OTHER, st);
     for (int i = 0; i < c.conv_layers; i++) {
-        TextBlock& b = m->tblk[i];
-        LnArgs ln = ln_args(m->te, Td, M, Td, b.ln_w, b.ln_b, 0.0f, 1e-6f);
-        ln.dw_w = b.dw_w; ln.dw_b = b.dw_b; ln.row_seq_start = m->d_row_start; ln.row_seq_end = m->d_row_end;
-        ln.out_hi = m->tn.hi; ln.out_lo = m->tn.lo; ln.ldo = Td;
-        CK(run_ln(ln, st));
-        GemmArgs g1 = gemm_base(m->tn, Td, b.pw1, M);
-        g1.act = ACT_GELU_ERF; g1.out_f32 = m->ty; g1.ldo = 2 * Td;
-        CK(run_gemm(m, g1, b.pw1, EPI_GENERIC, false, 128, st));
-        prof_begin(PROF_OTHER, st);
-        hipLaunchKernelGGL(grn_stats_kernel, dim3((2 * Td + 255) / 256, m->n_seq), dim3(256), 0, st, m->ty, 2 * Td, 2 * Td,
-                           m->d_seq_row0, m->d_seq_len, m->gx);
-        CKL("grn_stats");
-        hipLaunchKernelGGL(grn_apply_kernel, dim3((M + 3) / 4), dim3(256), 0, st, m->ty, 2 * Td, 2 * Td, M, m->d_row_seq, m->gx,
-                           b.gamma, b.beta, m->tg.hi, m->tg.lo, 2 * Td);
-        CKL("grn_apply");
-        prof_end(PROF_OTHER, st);
-        GemmArgs g2 = gemm_base(m->tg, 2 * Td, b.pw2, M);
-        g2.res = m->te; g2.ldres = Td; g2.out_f32 = m->te; g2.ldo = Td;
-        if (i == c.conv_layers - 1) { g2.out_hi = m->act.hi + 128; g2.out_lo = m->act.lo + 128; g2.ldob = Kct; }
-        CK(run_gemm(m, g2, b.pw2, EPI_GENERIC, false, 128, st));
+        const bool last = i == c.conv_layers - 1;   // the last block also writes the text columns of the step-invariant operand
+        CK(run_text_block(m->nsplit, m->tblk[i], Td, M, m->n_seq, m->te, m->tn, m->ty, m->tg, m->gx, m->d_row_start, m->d_row_end, m->d_row_seq,
+                          m->d_seq_row0, m->d_seq_len, last ? m->act.hi + 128 : nullptr, last ? m->act.lo + 128 : nullptr, Kct, st));
     }
     if (c.conv_layers == 0 && m->arch != 2) {   // (MMDiT: the text is not an input of the audio projection)
         prof_begin(PROF_OTHER, st);
@@ -885,11 +913,25 @@ static int forward_mmdit_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t 
     return 0;
 }
 
-// One grouped convolution of ConvPositionEmbedding: the sliding-window kernel (conv5.h, 128-row tiles, one column tile per group) for the
-// DiT and MMDiT layouts, the implicit GEMM of gemm.h otherwise (UNetT: the time-token row at the head of every sequence has an empty
-// window of its own, which a per-tile bound cannot express).
-static int run_pos_conv(f5hip_dit* m, GemmArgs& g, const PackedW& W, hipStream_t st) {
-    return run_conv(W.f16 ? 3 : m->nsplit, g, W, m->arch != 1 && m->nsplit == 2 && !W.f16, true, 64, st);
+// ConvPositionEmbedding (F/model/modules.py:171-176) over the M rows of the layout: h = Mish(GConv2(Mish(GConv1(hn)))) + h0, with hn the
+// operand planes of h0 and stage 1 in the planes c1 (both [M][D], plus slack past the last row: a group narrower than 64 channels is
+// read as 64).  Window rows outside [row_start, row_end) of the output row are zero.  conv5: the sliding-window kernel (conv5.h, 128-row
+// tiles, one column tile per group), which takes the bounds of a tile from its first row -- the DiT and MMDiT layouts in split bf16;
+// else the implicit GEMM of gemm.h (UNetT: the time-token row at the head of every sequence has an empty window of its own).
+static int run_conv_pos_embed(int nsplit, bool conv5, int D, int M, const Plane2& hn, const Plane2& c1, const float* h0, float* h,
+                              const PackedW& w1, const PackedW& w2, const int* row_start, const int* row_end, hipStream_t st) {
+    const int gw = D / 16;
+    for (int which = 0; which < 2; which++) {
+        const PackedW& W = which ? w2 : w1;
+        GemmArgs g = gemm_base(which ? c1 : hn, D, W, M);
+        g.conv_kpt = 2; g.conv_center = 15; g.conv_group_cols = gw; g.row_seq_start = row_start; g.row_seq_end = row_end;
+        g.group_w = gw; g.N = 16 * 64;
+        g.act = ACT_MISH;
+        if (which) { g.res = h0; g.ldres = D; g.out_f32 = h; g.ldo = D; }
+        else { g.out_hi = c1.hi; g.out_lo = c1.lo; g.ldob = D; }
+        CK(run_conv(W.f16 ? 3 : nsplit, g, W, conv5 && !W.f16, true, 64, st));
+    }
+    return 0;
 }
 
 static int forward_step(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {
@@ -903,16 +945,8 @@ static int forward_step(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {
     gi.out_hi = m->hn.hi; gi.out_lo = m->hn.lo; gi.ldob = D;
     CK(run_gemm(m, gi, m->wx, EPI_GENERIC, false, 128, st));
     // conv_pos_embed: Mish(GConv(Mish(GConv(h0)))) + h0   (F/model/modules.py:171-176, F/model/backbones/dit.py:86)
-    GemmArgs c1 = gemm_base(m->hn, D, m->conv1, M);
-    c1.conv_kpt = 2; c1.conv_center = 15; c1.conv_group_cols = m->gw; c1.row_seq_start = m->d_row_start; c1.row_seq_end = m->d_row_end;
-    c1.group_w = m->gw; c1.N = 16 * 64;
-    c1.act = ACT_MISH; c1.out_hi = m->c1.hi; c1.out_lo = m->c1.lo; c1.ldob = D;
-    CK(run_pos_conv(m, c1, m->conv1, st));
-    GemmArgs c2 = gemm_base(m->c1, D, m->conv2, M);
-    c2.conv_kpt = 2; c2.conv_center = 15; c2.conv_group_cols = m->gw; c2.row_seq_start = m->d_row_start; c2.row_seq_end = m->d_row_end;
-    c2.group_w = m->gw; c2.N = 16 * 64;
-    c2.act = ACT_MISH; c2.res = m->h0; c2.ldres = D; c2.out_f32 = m->h; c2.ldo = D;
-    CK(run_pos_conv(m, c2, m->conv2, st));
+    CK(run_conv_pos_embed(m->nsplit, m->arch != 1 && m->nsplit == 2, D, M, m->hn, m->c1, m->h0, m->h, m->conv1, m->conv2, m->d_row_start,
+                          m->d_row_end, st));
 
     const int nb = n_blocks < 0 ? c.depth : n_blocks;
     if (m->arch == 1) return forward_unett_layers(m, ti, n_blocks, st);
@@ -986,6 +1020,13 @@ int f5hip_dit_read_tap(f5hip_dit* m, const char* tap, float* dst_dev, int64_t nu
         if (numel != (int64_t)m->n_frames * Td) return fail(-1, "read_tap: numel mismatch");
         hipLaunchKernelGGL(gather_rows_kernel, dim3(m->n_frames), dim3(128), 0, st, m->te, Td, Td, m->n_frames, m->d_urow_c, dst_dev, Td);
         CKL("gather tap");
+        return 0;
+    }
+    if (!strcmp(tap, "text_rows")) {   // MMDiT: the text stream's embedding as laid out, rows [M, M + Mc) (every sequence padded to 128 rows)
+        const size_t n = (size_t)m->Mc * m->cfg.text_dim;
+        if (m->arch != 2 || numel != (int64_t)n) return fail(-1, "read_tap: text_rows needs an MMDiT handle and numel = text rows x text_dim");
+        if (hipMemcpyAsync(dst_dev, m->te + (size_t)m->row_c0 * m->cfg.text_dim, n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+            return fail(-6, "read_tap: copy");
         return 0;
     }
     return fail(-1, "unknown tap %s", tap);

@@ -55,6 +55,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
     }
     const int a_col0 = CONV ? (int)blockIdx.x * p.conv_group_cols : 0;
+    // grouped convolution: the k-tiles read 64 channels per tap from a_col0; those past the group's conv_group_cols (the next group's, or the
+    // next row's for the last group) meet zero weights and are loaded as 0, so that a NaN or Inf there cannot reach the group (0 * NaN = NaN)
+    const int a_cols = CONV && p.conv_group_cols > 0 ? p.conv_group_cols : 1 << 30;
 
     // register staging of the next k-tile (kept in named registers: plain arrays + fully unrolled static indexing)
     u32x4 ra[NPL * A_RPT], rb[NPL * B_RPT];
@@ -82,7 +85,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             _Pragma("unroll") for (int pl = 0; pl < NPL; pl++) {                                            \
                 if constexpr (CONV) {                                                                          \
                     const int src_ = m0 + lrow + 64 * i + shift_;                                              \
-                    const bool ok_ = src_ >= sstart[i] && src_ < send[i];                                      \
+                    const bool ok_ = src_ >= sstart[i] && src_ < send[i] && a_off_ + lchunk * 8 < a_cols;       \
                     u32x4 v_ = {0u, 0u, 0u, 0u};                                                         \
                     if (ok_) v_ = *reinterpret_cast<const u32x4*>(a_ptr[pl] + (ptrdiff_t)shift_ * p.lda + i * a_row64 + a_off_); \
                     ra[pl * A_RPT + i] = v_;                                                                   \

@@ -470,3 +470,150 @@ extern "C" int f5hip_op_bigvgan_conv_post(int32_t batch, int32_t P, int32_t T, i
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(-7, "op_bigvgan_conv_post: %s", hipGetErrorString(hipGetLastError()));
     return rc;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- DiT input-side unit ops
+// frame f of x [n][C] -> row frame_row[f] of dst (pitch ldd), and its split-bf16 planes (pitch ldd) when hi is not null
+__global__ __launch_bounds__(256) void op_scatter_rows_kernel(const float* x, int C, int n, const int* frame_row, float* dst, __bf16* hi, __bf16* lo,
+                                                              int ldd) {
+    const int f = blockIdx.x;
+    if (f >= n) return;
+    const size_t r = (size_t)frame_row[f];
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const float v = x[(size_t)f * C + c];
+        if (dst) dst[r * ldd + c] = v;
+        if (hi) {
+            __bf16 h, l;
+            split_bf16(v, h, l);
+            hi[r * ldd + c] = h;
+            lo[r * ldd + c] = l;
+        }
+    }
+}
+
+// row frame_row[f] of planes (pitch lds) -> dst [n][C] as fp32: hi + lo, or hi alone when lo is null (what a one-plane bf16 consumer reads)
+__global__ __launch_bounds__(256) void op_gather_planes_kernel(const __bf16* hi, const __bf16* lo, int lds, int C, int n, const int* frame_row, float* dst) {
+    const int f = blockIdx.x;
+    if (f >= n) return;
+    const size_t r = (size_t)frame_row[f];
+    for (int c = threadIdx.x; c < C; c += 256) dst[(size_t)f * C + c] = (float)hi[r * lds + c] + (lo ? (float)lo[r * lds + c] : 0.0f);
+}
+
+// The packed layout the backbone builds for n_seq sequences of seq_len frames with `lead` leading rows each (seq_rows / set_seq_bounds), on the
+// device: row_start, row_end, row_seq [R]; frame_row [frames]; seq_row0, seq_len [n_seq] (first row and rows of a sequence, lead included)
+struct OpLayout { int R = 0, frames = 0; int *row_start = nullptr, *row_end, *row_seq, *frame_row, *seq_row0, *seq_len; std::vector<int> h; };
+static int op_layout(OpBufs& b, int n_seq, const int32_t* seq_len, int lead, OpLayout& L, hipStream_t st) {
+    L.R = 0; L.frames = 0;
+    for (int s = 0; s < n_seq; s++) {
+        if (seq_len[s] <= 0 || seq_len[s] > 4096) return fail(-1, "seq_len[%d] = %d out of range", s, seq_len[s]);
+        L.R += seq_rows(seq_len[s], lead); L.frames += seq_len[s];
+    }
+    const int R = L.R, F = L.frames;
+    L.h.assign((size_t)3 * R + F + 2 * n_seq, 0);
+    int *rs = L.h.data(), *re = rs + R, *rq = re + R, *fr = rq + R, *s0 = fr + F, *sl = s0 + n_seq;
+    for (int r = 0; r < R; r++) rq[r] = -1;
+    for (int s = 0, r0 = 0, f0 = 0; s < n_seq; s++) {
+        set_seq_bounds(rs, re, rq, r0, lead, seq_len[s], s);
+        for (int i = 0; i < seq_len[s]; i++) fr[f0 + i] = r0 + lead + i;
+        s0[s] = r0; sl[s] = lead + seq_len[s];
+        r0 += seq_rows(seq_len[s], lead); f0 += seq_len[s];
+    }
+    int* d = b.get<int>(L.h.size());
+    if (!d) return fail(-5, "op layout: hipMalloc");
+    if (hipMemcpyAsync(d, L.h.data(), sizeof(int) * L.h.size(), hipMemcpyHostToDevice, st) != hipSuccess) return fail(-6, "op layout: upload");
+    L.row_start = d; L.row_end = d + R; L.row_seq = d + 2 * R; L.frame_row = d + 3 * R; L.seq_row0 = L.frame_row + F; L.seq_len = L.seq_row0 + n_seq;
+    return 0;
+}
+
+// n elements of T, every byte `pad` (0x00: zeros; 0xff: NaN in fp32, bf16 and fp16)
+template <typename T> static T* op_filled(OpBufs& b, size_t n, int pad, hipStream_t st) {
+    T* p = b.get<T>(n);
+    if (p) (void)hipMemsetAsync(p, pad, n * sizeof(T), st);
+    return p;
+}
+
+// ConvPositionEmbedding of the backbone (run_conv_pos_embed, weights packed by pack_conv_pos): out = h0 + Mish(conv2(Mish(conv1(h0)))) over
+// n_seq sequences of seq_len frames, x_dev fp32 [frames][D] (packed).  Weights in nn.Conv1d layout w [D][D / 16][31], bias [D] (host).
+// lead = 1: the UNetT layout (a time-token row heads every sequence).  impl 5 = conv5.h (prec 2, lead 0), 0 = gemm.h; prec 2 = split bf16,
+// 1 = bf16.  pad_nan: the padding rows, the time-token rows and the slack past the last row of every internal buffer hold NaN instead of 0.
+// c1_dev (or null) fp32 [frames][D]: stage 1 as the second convolution reads it (hi + lo; the hi plane alone at prec 1).
+extern "C" int f5hip_op_conv_pos_embed(int32_t n_seq, const int32_t* seq_len, int32_t lead, int32_t D, const float* x_dev, const float* w1_host,
+                                       const float* b1_host, const float* w2_host, const float* b2_host, int32_t impl, int32_t prec, int32_t pad_nan,
+                                       float* out_dev, float* c1_dev, void* stream) {
+    if (n_seq <= 0 || !seq_len || lead < 0 || lead > 1 || D <= 0 || D % 128 || D / 16 > 64 || !x_dev || !w1_host || !b1_host || !w2_host || !b2_host ||
+        !out_dev || (impl != 0 && impl != 5) || (prec != 1 && prec != 2) || (impl == 5 && (prec != 2 || lead)))
+        return fail(-1, "op_conv_pos_embed: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    OpBufs b;
+    OpLayout L;
+    CK(op_layout(b, n_seq, seq_len, lead, L, st));
+    const size_t n = (size_t)L.R * D, slack = 256;
+    const int pad = pad_nan ? 0xff : 0;
+    float* h0 = op_filled<float>(b, n + slack, pad, st);
+    float* h = op_filled<float>(b, n + slack, pad, st);
+    Plane2 hn, c1;
+    hn.hi = op_filled<__bf16>(b, n + slack, pad, st); hn.lo = op_filled<__bf16>(b, n + slack, pad, st);
+    c1.hi = op_filled<__bf16>(b, n + slack, pad, st); c1.lo = op_filled<__bf16>(b, n + slack, pad, st);
+    if (!h0 || !h || !hn.hi || !hn.lo || !c1.hi || !c1.lo) return fail(-5, "op_conv_pos_embed: hipMalloc");
+    hipLaunchKernelGGL(op_scatter_rows_kernel, dim3(L.frames), dim3(256), 0, st, x_dev, D, L.frames, L.frame_row, h0, hn.hi, hn.lo, D);
+    CKL("op scatter");
+    PackedW w1, w2;
+    int rc = pack_conv_pos(w1, w1_host, b1_host, D);
+    if (!rc) rc = pack_conv_pos(w2, w2_host, b2_host, D);
+    if (!rc) rc = run_conv_pos_embed(prec, impl == 5, D, L.R, hn, c1, h0, h, w1, w2, L.row_start, L.row_end, st);
+    if (!rc) {
+        hipLaunchKernelGGL(gather_rows_kernel, dim3(L.frames), dim3(128), 0, st, h, D, D, L.frames, L.frame_row, out_dev, D);
+        if (c1_dev) hipLaunchKernelGGL(op_gather_planes_kernel, dim3(L.frames), dim3(256), 0, st, c1.hi, prec == 2 ? c1.lo : nullptr, D, D, L.frames,
+                                       L.frame_row, c1_dev);
+        if (hipGetLastError() != hipSuccess) rc = fail(-7, "op_conv_pos_embed: gather launch");
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(-7, "op_conv_pos_embed: %s", hipGetErrorString(hipGetLastError()));
+    free_packed(w1); free_packed(w2);
+    return rc;
+}
+
+// One ConvNeXtV2 text block of the backbone (run_text_block, split-bf16 GEMMs) in place over n_seq sequences of seq_len tokens, x_dev fp32
+// [tokens][Td] (packed).  params_host: 10 host fp32 arrays in the module's layout -- dwconv.weight [Td][1][7], dwconv.bias, norm.weight,
+// norm.bias [Td], pwconv1.weight [2 Td][Td], pwconv1.bias, grn.gamma, grn.beta [2 Td], pwconv2.weight [Td][2 Td], pwconv2.bias [Td].
+// pad_nan: the padding rows of every internal buffer hold NaN instead of 0.  out_dev fp32 [tokens][Td]; the stage taps (each fp32 or
+// null) as the next kernel reads them: tap_ln [tokens][Td] dwconv + LayerNorm (hi + lo), tap_ty [tokens][2 Td] pwconv1 + GELU, tap_grn
+// [tokens][2 Td] GRN (hi + lo).
+extern "C" int f5hip_op_convnext_block(int32_t n_seq, const int32_t* seq_len, int32_t Td, const float* x_dev, const float* const* params_host,
+                                       int32_t pad_nan, float* out_dev, float* tap_ln_dev, float* tap_ty_dev, float* tap_grn_dev, void* stream) {
+    if (n_seq <= 0 || !seq_len || Td <= 0 || Td % 32 || Td > 1536 || !x_dev || !params_host || !out_dev) return fail(-1, "op_convnext_block: bad argument");
+    for (int i = 0; i < 10; i++) if (!params_host[i]) return fail(-1, "op_convnext_block: parameter %d is null", i);
+    hipStream_t st = (hipStream_t)stream;
+    OpBufs b;
+    OpLayout L;
+    CK(op_layout(b, n_seq, seq_len, 0, L, st));
+    const size_t n = (size_t)L.R * Td;
+    const int pad = pad_nan ? 0xff : 0;
+    float* te = op_filled<float>(b, n, pad, st);
+    float* ty = op_filled<float>(b, 2 * n, pad, st);
+    float* gx = op_filled<float>(b, (size_t)n_seq * 2 * Td, pad, st);
+    Plane2 tn, tg;
+    tn.hi = op_filled<__bf16>(b, n, pad, st); tn.lo = op_filled<__bf16>(b, n, pad, st);
+    tg.hi = op_filled<__bf16>(b, 2 * n, pad, st); tg.lo = op_filled<__bf16>(b, 2 * n, pad, st);
+    if (!te || !ty || !gx || !tn.hi || !tn.lo || !tg.hi || !tg.lo) return fail(-5, "op_convnext_block: hipMalloc");
+    hipLaunchKernelGGL(op_scatter_rows_kernel, dim3(L.frames), dim3(256), 0, st, x_dev, Td, L.frames, L.frame_row, te, (__bf16*)nullptr,
+                       (__bf16*)nullptr, Td);
+    CKL("op scatter");
+    const float* const* P = params_host;
+    TextBlock tb;
+    int rc = upload_f32(&tb.dw_w, P[0], (size_t)Td * 7) || upload_f32(&tb.dw_b, P[1], Td) || upload_f32(&tb.ln_w, P[2], Td) ||
+             upload_f32(&tb.ln_b, P[3], Td) || upload_f32(&tb.gamma, P[6], 2 * Td) || upload_f32(&tb.beta, P[7], 2 * Td) ||
+             pack_linear(tb.pw1, P[4], 2 * Td, Td, Td, P[5]) || pack_linear(tb.pw2, P[8], Td, 2 * Td, 2 * Td, P[9]) ? -4 : 0;
+    if (!rc) rc = run_text_block(2, tb, Td, L.R, n_seq, te, tn, ty, tg, gx, L.row_start, L.row_end, L.row_seq, L.seq_row0, L.seq_len, nullptr,
+                                 nullptr, 0, st);
+    if (!rc) {
+        hipLaunchKernelGGL(gather_rows_kernel, dim3(L.frames), dim3(128), 0, st, te, Td, Td, L.frames, L.frame_row, out_dev, Td);
+        if (tap_ln_dev) hipLaunchKernelGGL(op_gather_planes_kernel, dim3(L.frames), dim3(256), 0, st, tn.hi, tn.lo, Td, Td, L.frames, L.frame_row, tap_ln_dev);
+        if (tap_ty_dev) hipLaunchKernelGGL(gather_rows_kernel, dim3(L.frames), dim3(128), 0, st, ty, 2 * Td, 2 * Td, L.frames, L.frame_row, tap_ty_dev, 2 * Td);
+        if (tap_grn_dev) hipLaunchKernelGGL(op_gather_planes_kernel, dim3(L.frames), dim3(256), 0, st, tg.hi, tg.lo, 2 * Td, 2 * Td, L.frames, L.frame_row,
+                                            tap_grn_dev);
+        if (hipGetLastError() != hipSuccess) rc = fail(-7, "op_convnext_block: gather launch");
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(-7, "op_convnext_block: %s", hipGetErrorString(hipGetLastError()));
+    for (float* p : {tb.dw_w, tb.dw_b, tb.ln_w, tb.ln_b, tb.gamma, tb.beta}) dev_free(p);
+    free_packed(tb.pw1); free_packed(tb.pw2);
+    return rc;
+}

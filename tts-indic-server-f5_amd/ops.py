@@ -171,3 +171,47 @@ def joint_attention(q, k, v, x_len, c_len, x_kvlen=None, *, heads, shape_invaria
     _lib.check(_lib.lib().f5hip_op_joint_attention(len(xl), _p(xl), _p(kl), _p(cl), heads, _p(q), _p(k), _p(v), _p(out), _lib.current_stream_ptr(),
                                                    int(shape_invariant), int(out_format)), "f5hip_op_joint_attention")
     return out
+
+
+def _host_f32(t):
+    return np.ascontiguousarray(t.detach().to(torch.float32).cpu().numpy())
+
+
+def conv_pos_embed(x, w1, b1, w2, b2, *, seq_len, lead=0, impl=5, prec=2, taps=False, pad_nan=False):
+    """The backbone's ConvPositionEmbedding plus its residual, x + Mish(conv2(Mish(conv1(x)))), over packed sequences x fp32 [sum(seq_len), D];
+    weights [D, D / 16, 31] (nn.Conv1d, groups 16), biases [D].  lead=1: the UNetT layout (a time-token row heads every sequence).
+    impl 5 = conv5.h, 0 = gemm.h; prec 2 = split bf16, 1 = bf16.  pad_nan: NaN instead of 0 in the padding rows, the time-token rows and
+    the slack behind the internal buffers.  Returns out, or (out, stage 1 as the second convolution reads it) with taps."""
+    dev = x.device
+    x = _f32(x, dev)
+    frames, D = x.shape
+    sl = np.ascontiguousarray(np.asarray(seq_len, dtype=np.int32))
+    assert int(sl.sum()) == frames
+    hw = [_host_f32(t) for t in (w1, b1, w2, b2)]
+    out = torch.empty(frames, D, dtype=torch.float32, device=dev)
+    c1 = torch.empty(frames, D, dtype=torch.float32, device=dev) if taps else None
+    _lib.check(_lib.lib().f5hip_op_conv_pos_embed(len(sl), _p(sl), int(lead), D, _p(x), *(_p(a) for a in hw), int(impl), int(prec), int(pad_nan),
+                                                  _p(out), _p(c1), _lib.current_stream_ptr()), "f5hip_op_conv_pos_embed")
+    return (out, c1) if taps else out
+
+
+CONVNEXT_PARAMS = ("dwconv.weight", "dwconv.bias", "norm.weight", "norm.bias", "pwconv1.weight", "pwconv1.bias", "grn.gamma", "grn.beta",
+                   "pwconv2.weight", "pwconv2.bias")
+
+
+def convnext_block(x, params, *, seq_len, taps=False, pad_nan=False):
+    """One ConvNeXtV2 text block of the backbone over packed sequences x fp32 [sum(seq_len), Td]; params: the block's tensors by their
+    state-dict suffix (CONVNEXT_PARAMS).  Returns out, or (out, {"ln", "ty", "grn"}) with taps: each stage as the next kernel reads it."""
+    dev = x.device
+    x = _f32(x, dev)
+    n, Td = x.shape
+    sl = np.ascontiguousarray(np.asarray(seq_len, dtype=np.int32))
+    assert int(sl.sum()) == n
+    hp = [_host_f32(params[k]).reshape(-1) for k in CONVNEXT_PARAMS]
+    arr = (C.c_void_p * 10)(*(a.ctypes.data for a in hp))
+    out = torch.empty(n, Td, dtype=torch.float32, device=dev)
+    tp = {"ln": torch.empty(n, Td, dtype=torch.float32, device=dev), "ty": torch.empty(n, 2 * Td, dtype=torch.float32, device=dev),
+          "grn": torch.empty(n, 2 * Td, dtype=torch.float32, device=dev)} if taps else {}
+    _lib.check(_lib.lib().f5hip_op_convnext_block(len(sl), _p(sl), Td, _p(x), arr, int(pad_nan), _p(out), _p(tp.get("ln")), _p(tp.get("ty")),
+                                                  _p(tp.get("grn")), _lib.current_stream_ptr()), "f5hip_op_convnext_block")
+    return (out, tp) if taps else out
