@@ -19,6 +19,10 @@
 
 // Time points one sampler call can evaluate: the rows of the modulation table `mod`, of the time embeddings `temb` and of the sinusoid staging
 static constexpr int kMaxTimePoints = 256;
+// ... and the cap of a call whose units share one grid: one 128-point block of precompute_time's GEMM chain, the limit callers plan their
+// step counts against (serve.py).  The tables hold two such blocks, so a mixed-grid call has room for the union of its units' grids.
+static constexpr int kMaxGridPoints = 128;
+static_assert(kMaxGridPoints <= kMaxTimePoints, "a one-grid call's points are rows of the same tables");
 
 // =================================================================================================
 // DiT model
@@ -587,29 +591,26 @@ static LnArgs ln_args(const float* x, int ldx, int M, int D, const float* scale,
     return a;
 }
 
+// Launches the ln_kernel instance of a.D's width (NV vectors of 256 floats per row); false: no instance covers it
+template <bool ROW_MOD>
+static bool launch_ln(const LnArgs& a, hipStream_t st) {
+    dim3 grid((a.M + 3) / 4), blk(256);
+    switch ((a.D + 255) / 256) {
+        case 1: hipLaunchKernelGGL((ln_kernel<1, ROW_MOD>), grid, blk, 0, st, a); return true;
+        case 2: hipLaunchKernelGGL((ln_kernel<2, ROW_MOD>), grid, blk, 0, st, a); return true;
+        case 3: hipLaunchKernelGGL((ln_kernel<3, ROW_MOD>), grid, blk, 0, st, a); return true;
+        case 4: hipLaunchKernelGGL((ln_kernel<4, ROW_MOD>), grid, blk, 0, st, a); return true;
+        case 5: case 6: hipLaunchKernelGGL((ln_kernel<6, ROW_MOD>), grid, blk, 0, st, a); return true;
+        default: return false;
+    }
+}
+
 // row_mod: scale / shift per row (LnArgs::row_mod; f5hip_cfm_sample_grids)
 static int run_ln(const LnArgs& a, hipStream_t st, bool row_mod = false) {
-    const int nv = (a.D + 255) / 256;
-    dim3 grid((a.M + 3) / 4), blk(256);
     prof_begin(PROF_LN, st);
-    if (row_mod) {
-        switch (nv) {
-            case 1: hipLaunchKernelGGL((ln_kernel<1, true>), grid, blk, 0, st, a); break;
-            case 2: hipLaunchKernelGGL((ln_kernel<2, true>), grid, blk, 0, st, a); break;
-            case 3: hipLaunchKernelGGL((ln_kernel<3, true>), grid, blk, 0, st, a); break;
-            case 4: hipLaunchKernelGGL((ln_kernel<4, true>), grid, blk, 0, st, a); break;
-            case 5: case 6: hipLaunchKernelGGL((ln_kernel<6, true>), grid, blk, 0, st, a); break;
-            default: return fail(-7, "ln: D=%d unsupported", a.D);
-        }
-    } else switch (nv) {
-        case 1: hipLaunchKernelGGL(ln_kernel<1>, grid, blk, 0, st, a); break;
-        case 2: hipLaunchKernelGGL(ln_kernel<2>, grid, blk, 0, st, a); break;
-        case 3: hipLaunchKernelGGL(ln_kernel<3>, grid, blk, 0, st, a); break;
-        case 4: hipLaunchKernelGGL(ln_kernel<4>, grid, blk, 0, st, a); break;
-        case 5: case 6: hipLaunchKernelGGL(ln_kernel<6>, grid, blk, 0, st, a); break;
-        default: return fail(-7, "ln: D=%d unsupported", a.D);
-    }
+    const bool launched = row_mod ? launch_ln<true>(a, st) : launch_ln<false>(a, st);
     prof_end(PROF_LN, st);
+    if (!launched) return fail(-7, "ln: D=%d unsupported", a.D);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(-7, "ln launch: %s", hipGetErrorString(e));
     return 0;
@@ -799,6 +800,13 @@ static int run_adaln(f5hip_dit* m, const Stream& s, const float* shift, const fl
     return run_ln(ln, st, m->d_row_tp != nullptr);
 }
 
+// The tail of every backbone: proj_out over the final norm's planes hn into pred [M][128]
+static int run_proj_out(f5hip_dit* m, hipStream_t st) {
+    GemmArgs po = gemm_base(m->hn, m->cfg.dim, m->proj_out, m->M);
+    po.out_f32 = m->pred; po.ldo = 128;
+    return run_gemm(m, po, m->proj_out, EPI_GENERIC, false, 128, st);
+}
+
 static int launch_attention(f5hip_dit* m, hipStream_t st) {
     const f5hip_dit_config& c = m->cfg;
     AttnArgs at; memset(&at, 0, sizeof(at));
@@ -866,10 +874,7 @@ static int forward_unett_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t 
     ln.scale = m->g_out;
     ln.f16_out = 0;
     CK(run_ln(ln, st));
-    GemmArgs po = gemm_base(m->hn, D, m->proj_out, M);
-    po.out_f32 = m->pred; po.ldo = 128;
-    CK(run_gemm(m, po, m->proj_out, EPI_GENERIC, false, 128, st));
-    return 0;
+    return run_proj_out(m, st);
 }
 
 // One DiT evaluation at time index ti for all laid-out sequences.  xs (split bf16 of x) must be current.
@@ -907,10 +912,7 @@ static int forward_mmdit_layers(f5hip_dit* m, int ti, int n_blocks, hipStream_t 
     if (n_blocks >= 0) return 0;
     const float* mf = mod + m->mod_final;                          // (scale, shift): F/model/modules.py:308
     CK(run_adaln(m, x, mf + D, mf, false, st));
-    GemmArgs po = gemm_base(m->hn, D, m->proj_out, M);
-    po.out_f32 = m->pred; po.ldo = 128;
-    CK(run_gemm(m, po, m->proj_out, EPI_GENERIC, false, 128, st));
-    return 0;
+    return run_proj_out(m, st);
 }
 
 // ConvPositionEmbedding (F/model/modules.py:171-176) over the M rows of the layout: h = Mish(GConv2(Mish(GConv1(hn)))) + h0, with hn the
@@ -948,9 +950,9 @@ static int forward_step(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {
     CK(run_conv_pos_embed(m->nsplit, m->arch != 1 && m->nsplit == 2, D, M, m->hn, m->c1, m->h0, m->h, m->conv1, m->conv2, m->d_row_start,
                           m->d_row_end, st));
 
-    const int nb = n_blocks < 0 ? c.depth : n_blocks;
     if (m->arch == 1) return forward_unett_layers(m, ti, n_blocks, st);
     if (m->arch == 2) return forward_mmdit_layers(m, ti, n_blocks, st);
+    const int nb = n_blocks < 0 ? c.depth : n_blocks;
     // Each LayerNorm is a launch of its own (fusing the norm into the epilogue of the residual GEMM in front of it measured slower -- 31.2 us
     // against 18.8 + 6.1 us for the two launches: profiles/r02_ln_fusion.txt).
     const Stream x = audio_stream(m);
@@ -966,10 +968,7 @@ static int forward_step(f5hip_dit* m, int ti, int n_blocks, hipStream_t st) {
     if (n_blocks >= 0) return 0;
     const float* mf = mod + m->mod_final;   // final (scale, shift): F/model/modules.py:308; split-bf16 planes for proj_out
     CK(run_adaln(m, x, mf + D, mf, false, st));
-    GemmArgs po = gemm_base(m->hn, D, m->proj_out, M);
-    po.out_f32 = m->pred; po.ldo = 128;
-    CK(run_gemm(m, po, m->proj_out, EPI_GENERIC, false, 128, st));
-    return 0;
+    return run_proj_out(m, st);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1032,12 +1031,6 @@ int f5hip_dit_read_tap(f5hip_dit* m, const char* tap, float* dst_dev, int64_t nu
     return fail(-1, "unknown tap %s", tap);
 }
 
-int f5hip_cfm_sample(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const float* cond_dev, const uint8_t* cond_mask,
-                     const int32_t* text, int32_t nt_max, const float* y0_dev, const float* t_grid, int32_t steps,
-                     float cfg_strength, float* out_dev, void* stream) {
-    return f5hip_cfm_sample_masked(m, n_utt, dur, nullptr, cond_dev, cond_mask, text, nt_max, y0_dev, t_grid, steps, cfg_strength, out_dev, stream);
-}
-
 int f5hip_set_attention_shape_invariant(int32_t on) {
     f5_set_attn_shape_invariant(on);
     return 0;
@@ -1069,328 +1062,7 @@ int f5hip_dit_set_ode_method(f5hip_dit* m, int32_t method) {
     return 0;
 }
 
-// The CFG combine of one ODE stage: the scalar-strength kernel, or -- with a per-frame table (f5hip_cfm_sample_units) -- its per-frame twin.
-static void launch_cfg_euler(const f5hip_dit* m, int f0, hipStream_t st, float* xout, const float* xbase, float cfg, float dt) {
-    const int mel = m->cfg.mel_dim;
-    if (m->d_frame_cfg)
-        hipLaunchKernelGGL(cfg_euler_kernel<true>, dim3(f0), dim3(128), 0, st, xout, xbase, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                           0.0f, (const float*)m->d_frame_cfg, dt, m->xs.hi, m->xs.lo, 128, (const int*)nullptr, (const float*)nullptr, 0);
-    else
-        hipLaunchKernelGGL(cfg_euler_kernel<false>, dim3(f0), dim3(128), 0, st, xout, xbase, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                           cfg, (const float*)nullptr, dt, m->xs.hi, m->xs.lo, 128, (const int*)nullptr, (const float*)nullptr, 0);
-}
-
-static void launch_cfg_rk4(f5hip_dit* m, int f0, hipStream_t st, float cfg, float dt, int stage) {
-    const int mel = m->cfg.mel_dim;
-    if (m->d_frame_cfg)
-        hipLaunchKernelGGL(cfg_rk4_stage_kernel<true>, dim3(f0), dim3(128), 0, st, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                           0.0f, (const float*)m->d_frame_cfg, dt, stage, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128,
-                           (const int*)nullptr, (const float*)nullptr, 0);
-    else
-        hipLaunchKernelGGL(cfg_rk4_stage_kernel<false>, dim3(f0), dim3(128), 0, st, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                           cfg, (const float*)nullptr, dt, stage, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128,
-                           (const int*)nullptr, (const float*)nullptr, 0);
-}
-
-// f5hip_cfm_sample_masked (cfg_unit == null: one strength for the call) and f5hip_cfm_sample_units (cfg_unit: one strength per unit)
-static int cfm_sample_impl(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
-                           const int32_t* text, int32_t nt_max, const float* y0_dev, const float* t_grid, int32_t steps,
-                           float cfg_strength, const float* cfg_unit, float* out_dev, void* stream) {
-    if (!m || !m->finalized) return fail(-1, "model not finalized");
-    if (n_utt <= 0 || !dur || !cond_dev || !cond_mask || !text || !y0_dev || !t_grid || !out_dev || steps <= 0)
-        return fail(-1, "cfm_sample: bad argument");
-    ProfScope prof_scope(m->prof);
-    hipStream_t st = (hipStream_t)stream;
-    const int mel = m->cfg.mel_dim;
-    std::vector<float> frame_cfg;   // per-unit strengths spread over the unit's frames (cfg_unit only)
-    std::vector<SeqDesc> seqs;
-    int f0 = 0;
-    m->h_seq_len.clear();
-    for (int u = 0; u < n_utt; u++) {
-        if (dur[u] <= 0 || dur[u] > 4096) return fail(-1, "dur[%d] = %d out of range", u, dur[u]);
-        const int kv = kv_len ? kv_len[u] : dur[u];
-        if (kv <= 0 || kv > dur[u]) return fail(-1, "kv_len[%d] = %d out of range (1..%d)", u, kv, dur[u]);
-        // MMDiT text stream: with batch-1 semantics a unit's text tensor is its own tokens (the reference's per-item call pads nothing); with
-        // the padded-batch semantics every item carries the batch's nt positions, fillers included
-        int c_len = nt_max;
-        if (!kv_len) { c_len = 0; while (c_len < nt_max && text[(size_t)u * nt_max + c_len] != -1) c_len++; }
-        seqs.push_back({dur[u], kv, f0, u, 0, 0, 0});
-        seqs.back().c_len = std::max(c_len, 1);
-        m->h_seq_len.push_back(dur[u]);
-        // the reference's early-out (cfm.py:162-175): below 1e-5 the unconditional branch is not evaluated at all -- per call, or per unit
-        const float cfg_u = cfg_unit ? cfg_unit[u] : cfg_strength;
-        const bool use_cfg = !(cfg_u < 1e-5f);
-        if (cfg_unit) frame_cfg.insert(frame_cfg.end(), dur[u], use_cfg ? cfg_u : 0.0f);
-        if (use_cfg) {
-            seqs.push_back({dur[u], kv, f0, u, 1, 1, 1});
-            seqs.back().c_len = std::max(c_len, 1);
-            m->h_seq_len.push_back(dur[u]);
-        }
-        f0 += dur[u];
-    }
-    CK(setup_sequences(m, seqs, f0, text, nt_max, cond_mask, st, cfg_unit ? frame_cfg.data() : nullptr));
-    const int M = m->M;
-    if (hipMemcpyAsync(m->xstate, y0_dev, sizeof(float) * (size_t)f0 * mel, hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return fail(-6, "y0 copy");
-    hipLaunchKernelGGL(split_rows_kernel, dim3(M), dim3(256), 0, st, m->xstate, mel, mel, M, m->d_row_frame, m->xs.hi, m->xs.lo, 128, 0);
-    CKL("split x");
-    CK(precompute_text_and_ce(m, cond_dev, st));
-    if (m->ode_method == 0) {
-        if (steps > 128) return fail(-8, "at most 128 time points per call (got %d)", steps);
-        CK(precompute_time(m, t_grid, steps, st));
-        for (int i = 0; i < steps; i++) {
-            CK(forward_step(m, i, -1, st));
-            prof_begin(PROF_OTHER, st);
-            launch_cfg_euler(m, f0, st, m->xstate, m->xstate, cfg_strength, t_grid[i + 1] - t_grid[i]);
-            prof_end(PROF_OTHER, st);
-            CKL("cfg_euler");
-        }
-    } else if (m->ode_method == 1) {
-        // explicit midpoint on the fixed grid (torchdiffeq method="midpoint"): time points 2i = t_i, 2i + 1 = t_i + dt_i / 2
-        if (2 * steps > 128) return fail(-8, "midpoint: at most 64 steps per call (got %d)", steps);
-        std::vector<float> t2((size_t)2 * steps);
-        for (int i = 0; i < steps; i++) {
-            const float half = 0.5f * (t_grid[i + 1] - t_grid[i]);
-            t2[2 * i] = t_grid[i];
-            t2[2 * i + 1] = t_grid[i] + half;
-        }
-        CK(precompute_time(m, t2.data(), 2 * steps, st));
-        for (int i = 0; i < steps; i++) {
-            const float dt = t_grid[i + 1] - t_grid[i];
-            CK(forward_step(m, 2 * i, -1, st));
-            prof_begin(PROF_OTHER, st);
-            launch_cfg_euler(m, f0, st, m->xmid, m->xstate, cfg_strength, 0.5f * dt);
-            prof_end(PROF_OTHER, st);
-            CKL("cfg_euler half");
-            CK(forward_step(m, 2 * i + 1, -1, st));
-            prof_begin(PROF_OTHER, st);
-            launch_cfg_euler(m, f0, st, m->xstate, m->xstate, cfg_strength, dt);
-            prof_end(PROF_OTHER, st);
-            CKL("cfg_euler full");
-        }
-    } else {
-        // RK4 on the fixed grid (torchdiffeq method="rk4", the 3/8 rule): time points 3i = t_i, 3i + 1 = t_i + dt_i / 3, 3i + 2 = t_i + 2 dt_i / 3;
-        // the last stage of step i is evaluated at t_{i+1} = point 3 (i + 1), shared with the first stage of step i + 1
-        if (3 * steps + 1 > 128) return fail(-8, "rk4: at most 42 steps per call (got %d)", steps);
-        std::vector<float> t3((size_t)3 * steps + 1);
-        {
-#pragma clang fp contract(off)
-            for (int i = 0; i < steps; i++) {   // stage times in fp32, rounded as torch rounds t0 + dt * (1/3) and t0 + dt * (2/3)
-                const float dt = t_grid[i + 1] - t_grid[i];
-                t3[3 * i] = t_grid[i];
-                t3[3 * i + 1] = t_grid[i] + dt * (1.0f / 3.0f);
-                t3[3 * i + 2] = t_grid[i] + dt * (2.0f / 3.0f);
-            }
-        }
-        t3[3 * steps] = t_grid[steps];
-        CK(precompute_time(m, t3.data(), 3 * steps + 1, st));
-        for (int i = 0; i < steps; i++) {
-            const float dt = t_grid[i + 1] - t_grid[i];
-            for (int s = 1; s <= 4; s++) {
-                CK(forward_step(m, 3 * i + s - 1, -1, st));
-                prof_begin(PROF_OTHER, st);
-                launch_cfg_rk4(m, f0, st, cfg_strength, dt, s);
-                prof_end(PROF_OTHER, st);
-                CKL("cfg_rk4_stage");
-            }
-        }
-    }
-    hipLaunchKernelGGL(final_select_kernel, dim3(f0), dim3(128), 0, st, m->xstate, cond_dev, m->d_frame_is_cond, mel, f0, out_dev);
-    CKL("final_select");
-    return 0;
-}
-
-int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
-                            const int32_t* text, int32_t nt_max, const float* y0_dev, const float* t_grid, int32_t steps,
-                            float cfg_strength, float* out_dev, void* stream) {
-    return cfm_sample_impl(m, n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, t_grid, steps, cfg_strength, nullptr, out_dev, stream);
-}
-
-int f5hip_cfm_sample_units(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
-                           const int32_t* text, int32_t nt_max, const float* y0_dev, const float* t_grid, int32_t steps,
-                           const float* cfg_strength, float* out_dev, void* stream) {
-    if (!cfg_strength) return fail(-1, "cfm_sample_units: cfg_strength is null");
-    return cfm_sample_impl(m, n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, t_grid, steps, 0.0f, cfg_strength, out_dev, stream);
-}
-
-// -------------------------------------------------------------------------------------------------
-// f5hip_cfm_sample_grids: one time grid and one CFG strength per unit
-// -------------------------------------------------------------------------------------------------
-// The CFG combine of one ODE stage with per-frame strengths and per-unit steps (unit_dt: one value per unit in layout order); the frames of
-// units >= n_act are left as they are.  stage 0: Euler form (xout = xbase + dt v), 1..4: RK4 stage.
-static void launch_cfg_grid(const f5hip_dit* m, int f0, hipStream_t st, float* xout, const float* xbase, const int* frame_unit, const float* unit_dt,
-                            int n_act, int stage) {
-    const int mel = m->cfg.mel_dim;
-    if (stage == 0)
-        hipLaunchKernelGGL((cfg_euler_kernel<true, true>), dim3(f0), dim3(128), 0, st, xout, xbase, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                           0.0f, (const float*)m->d_frame_cfg, 0.0f, m->xs.hi, m->xs.lo, 128, frame_unit, unit_dt, n_act);
-    else
-        hipLaunchKernelGGL((cfg_rk4_stage_kernel<true, true>), dim3(f0), dim3(128), 0, st, m->xstate, mel, f0, m->pred, 128, m->d_urow_c, m->d_urow_u,
-                           0.0f, (const float*)m->d_frame_cfg, 0.0f, stage, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128, frame_unit, unit_dt, n_act);
-}
-
-// Restores the handle's full layout and per-call modulation after a cfm_sample_grids call, however it ends.
-struct GridScope {
-    f5hip_dit* m;
-    ~GridScope() { m->d_row_tp = nullptr; m->M = m->row_c0; m->Mc = m->Rtot - m->row_c0; m->n_seq = (int)m->h_seq_row0.size() - 1; }
-};
-
-// Units are laid out by step count, descending (stable; a unit's conditional and unconditional sequences adjacent), so the units still
-// stepping at iteration i are a prefix of the layout: the forwards of iteration i run over the audio rows [0, M_i) (and MMDiT's text rows
-// [row_c0, row_c0 + Mc_i)) of those units only, and the CFG kernels leave the frames of the finished units alone.  Every unit's time points
-// (Euler t_i; midpoint t_i, t_i + dt_i / 2; RK4 t_i, t_i + dt_i / 3, t_i + 2 dt_i / 3, t_{i+1}, rounded as cfm_sample_impl rounds them) go
-// through one precompute_time over their union (equal fp32 values once); before each forward row_tp_kernel gives every row the time point of
-// its unit, and the modulation consumers read their vectors per row.
-int f5hip_cfm_sample_grids(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
-                           const int32_t* text, int32_t nt_max, const float* y0_dev, const int32_t* steps, const float* t_grids,
-                           const float* cfg_strength, float* out_dev, void* stream) {
-    if (!m || !m->finalized) return fail(-1, "model not finalized");
-    if (n_utt <= 0 || !dur || !cond_dev || !cond_mask || !text || !y0_dev || !steps || !t_grids || !cfg_strength || !out_dev)
-        return fail(-1, "cfm_sample_grids: bad argument");
-    std::vector<size_t> g0(n_utt);
-    std::vector<int> fo(n_utt + 1, 0);   // first frame of every unit in the caller's packed arrays
-    size_t off = 0;
-    for (int u = 0; u < n_utt; u++) {
-        if (steps[u] < 1) return fail(-1, "cfm_sample_grids: steps[%d] = %d (need >= 1)", u, steps[u]);
-        if (dur[u] <= 0 || dur[u] > 4096) return fail(-1, "dur[%d] = %d out of range", u, dur[u]);
-        const int kv = kv_len ? kv_len[u] : dur[u];
-        if (kv <= 0 || kv > dur[u]) return fail(-1, "kv_len[%d] = %d out of range (1..%d)", u, kv, dur[u]);
-        g0[u] = off;
-        off += (size_t)steps[u] + 1;
-        fo[u + 1] = fo[u] + dur[u];
-    }
-    bool one_grid = true;
-    for (int u = 1; u < n_utt && one_grid; u++)
-        one_grid = steps[u] == steps[0] && !memcmp(t_grids + g0[u], t_grids, sizeof(float) * ((size_t)steps[0] + 1));
-    if (one_grid)   // one grid for all: f5hip_cfm_sample_units' call, kernels and results
-        return cfm_sample_impl(m, n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, t_grids, steps[0], 0.0f, cfg_strength, out_dev, stream);
-
-    const int n = n_utt, method = m->ode_method, per = method == 0 ? 1 : (method == 1 ? 2 : 4);   // forwards per step
-    std::vector<int> order(n);
-    for (int u = 0; u < n; u++) order[u] = u;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return steps[a] > steps[b]; });
-    const int max_steps = steps[order[0]], n_fwd = max_steps * per;
-    // time points: utp[f][k] = point of forward f for the unit at layout position k (0 once its steps are done); udt[0][i][k] = dt_i, udt[1][i][k] = dt_i / 2
-    std::vector<float> pts;
-    std::map<uint32_t, int> pt_index;
-    auto point = [&](float t) {
-        uint32_t bits;
-        memcpy(&bits, &t, sizeof(bits));
-        auto it = pt_index.find(bits);
-        if (it != pt_index.end()) return it->second;
-        pt_index[bits] = (int)pts.size();
-        pts.push_back(t);
-        return (int)pts.size() - 1;
-    };
-    std::vector<int> utp((size_t)n_fwd * n, 0);
-    std::vector<float> udt((size_t)2 * max_steps * n, 0.0f);
-    {
-#pragma clang fp contract(off)
-        for (int k = 0; k < n; k++) {
-            const float* tg = t_grids + g0[order[k]];
-            for (int i = 0; i < steps[order[k]]; i++) {
-                const float dt = tg[i + 1] - tg[i];
-                udt[(size_t)i * n + k] = dt;
-                udt[(size_t)(max_steps + i) * n + k] = 0.5f * dt;
-                int* f = &utp[(size_t)i * per * n + k];
-                if (method == 0) {
-                    f[0] = point(tg[i]);
-                } else if (method == 1) {
-                    const float half = 0.5f * dt;
-                    f[0] = point(tg[i]);
-                    f[n] = point(tg[i] + half);
-                } else {   // stage times in fp32 as cfm_sample_impl (and torch) round t0 + dt * (1/3) and t0 + dt * (2/3)
-                    f[0] = point(tg[i]);
-                    f[n] = point(tg[i] + dt * (1.0f / 3.0f));
-                    f[2 * n] = point(tg[i] + dt * (2.0f / 3.0f));
-                    f[3 * n] = point(tg[i + 1]);
-                }
-            }
-        }
-    }
-    if ((int)pts.size() > kMaxTimePoints)
-        return fail(-8, "cfm_sample_grids: the units' grids need %d distinct time points, at most %d per call", (int)pts.size(), kMaxTimePoints);
-
-    ProfScope prof_scope(m->prof);
-    hipStream_t st = (hipStream_t)stream;
-    const int mel = m->cfg.mel_dim, U = fo[n];
-    std::vector<float> frame_cfg(U);
-    std::vector<int> frame_unit(U), seq_unit, seq_end(n);   // seq_end[k]: sequences of the units at layout positions 0..k
-    std::vector<SeqDesc> seqs;
-    m->h_seq_len.clear();
-    for (int k = 0; k < n; k++) {
-        const int u = order[k], kv = kv_len ? kv_len[u] : dur[u];
-        int c_len = nt_max;   // (as cfm_sample_impl)
-        if (!kv_len) { c_len = 0; while (c_len < nt_max && text[(size_t)u * nt_max + c_len] != -1) c_len++; }
-        const float cfg_u = cfg_strength[u];
-        const bool use_cfg = !(cfg_u < 1e-5f);
-        for (int f = fo[u]; f < fo[u + 1]; f++) { frame_cfg[f] = use_cfg ? cfg_u : 0.0f; frame_unit[f] = k; }
-        for (int b = 0; b < (use_cfg ? 2 : 1); b++) {
-            seqs.push_back({dur[u], kv, fo[u], u, b, b, b});
-            seqs.back().c_len = std::max(c_len, 1);
-            seq_unit.push_back(k);
-            m->h_seq_len.push_back(dur[u]);
-        }
-        seq_end[k] = (int)seqs.size();
-    }
-    CK(setup_sequences(m, seqs, U, text, nt_max, cond_mask, st, frame_cfg.data()));
-    GridScope scope{m};
-    const int R = m->Rtot, S = (int)seqs.size();
-    // grid_meta: row_unit [R] | frame_unit [U] | utp | udt (floats) -- uploaded -- then row_tp [R]
-    const size_t n_up = (size_t)R + U + utp.size() + udt.size(), need = n_up + R;
-    if (need > m->grid_cap) {
-        dev_free(m->grid_meta);
-        m->grid_cap = 0;
-        if (hipMalloc((void**)&m->grid_meta, sizeof(int) * need) != hipSuccess) { m->grid_meta = nullptr; return fail(-5, "hipMalloc grid tables"); }
-        m->grid_cap = need;
-    }
-    std::vector<int> hb(n_up, 0);
-    for (int s = 0; s < S; s++) {
-        for (int r = m->h_seq_row0[s]; r < m->h_seq_row0[s + 1]; r++) hb[r] = seq_unit[s];
-        for (int r = m->h_seqc_row0[s]; r < m->h_seqc_row0[s + 1]; r++) hb[r] = seq_unit[s];
-    }
-    memcpy(&hb[R], frame_unit.data(), sizeof(int) * U);
-    memcpy(&hb[(size_t)R + U], utp.data(), sizeof(int) * utp.size());
-    memcpy(&hb[(size_t)R + U + utp.size()], udt.data(), sizeof(float) * udt.size());
-    CK(m->up_grid.upload(m->grid_meta, hb.data(), sizeof(int) * n_up, st));
-    const int* d_row_unit = m->grid_meta;
-    const int* d_frame_unit = d_row_unit + R;
-    const int* d_utp = d_frame_unit + U;
-    const float* d_udt = reinterpret_cast<const float*>(d_utp + utp.size());
-    int* d_row_tp = m->grid_meta + n_up;
-
-    if (hipMemcpyAsync(m->xstate, y0_dev, sizeof(float) * (size_t)U * mel, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(-6, "y0 copy");
-    hipLaunchKernelGGL(split_rows_kernel, dim3(m->M), dim3(256), 0, st, m->xstate, mel, mel, m->M, m->d_row_frame, m->xs.hi, m->xs.lo, 128, 0);
-    CKL("split x");
-    CK(precompute_text_and_ce(m, cond_dev, st));
-    CK(precompute_time(m, pts.data(), (int)pts.size(), st));
-    m->d_row_tp = d_row_tp;
-    int n_act = n;
-    for (int i = 0; i < max_steps; i++) {
-        while (steps[order[n_act - 1]] <= i) n_act--;   // units whose steps are done leave the layout's tail
-        const int s_act = seq_end[n_act - 1];
-        m->M = m->h_seq_row0[s_act]; m->Mc = m->h_seqc_row0[s_act] - m->row_c0; m->n_seq = s_act;
-        const float* dt = d_udt + (size_t)i * n;
-        for (int s = 0; s < per; s++) {
-            prof_begin(PROF_OTHER, st);
-            hipLaunchKernelGGL(row_tp_kernel, dim3((R + 255) / 256), dim3(256), 0, st, d_row_unit, d_utp + ((size_t)i * per + s) * n, R, d_row_tp);
-            prof_end(PROF_OTHER, st);
-            CKL("row_tp");
-            CK(forward_step(m, 0, -1, st));
-            prof_begin(PROF_OTHER, st);
-            if (method == 0) launch_cfg_grid(m, U, st, m->xstate, m->xstate, d_frame_unit, dt, n_act, 0);
-            else if (method == 1 && s == 0) launch_cfg_grid(m, U, st, m->xmid, m->xstate, d_frame_unit, d_udt + (size_t)(max_steps + i) * n, n_act, 0);
-            else if (method == 1) launch_cfg_grid(m, U, st, m->xstate, m->xstate, d_frame_unit, dt, n_act, 0);
-            else launch_cfg_grid(m, U, st, nullptr, nullptr, d_frame_unit, dt, n_act, s + 1);
-            prof_end(PROF_OTHER, st);
-            CKL("cfg (grids)");
-        }
-    }
-    hipLaunchKernelGGL(final_select_kernel, dim3(U), dim3(128), 0, st, m->xstate, cond_dev, m->d_frame_is_cond, mel, U, out_dev);
-    CKL("final_select");
-    return 0;
-}
-
+#include "cfm_sample.h"
 #include "vocos.h"
 #include "bigvgan.h"
 #include "unit_ops.h"

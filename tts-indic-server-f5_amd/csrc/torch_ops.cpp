@@ -28,57 +28,73 @@ void check_host(const at::Tensor& t, at::ScalarType ty, const char* name) {
 
 // The ODE loop of CFM.sample over packed rows: dur [b] int32 host (rows laid out per item), kv_len [b] int32 host or None (valid frames per item:
 // the reference's padded-batch semantics), cond [sum(dur), mel] fp32 device, cond_mask [sum(dur)] uint8 host, text [b, nt] int32 host (-1 padded),
-// y0 [sum(dur), mel] fp32 device, t_grid [steps + 1] fp32 host.  Returns the sampled mel rows [sum(dur), mel].
+// y0 [sum(dur), mel] fp32 device.  The three sampler operators differ in the time grid and the CFG strength only.
+struct SampleArgs {
+    const at::Tensor &dur, &cond, &cond_mask, &text, &y0;
+    const c10::optional<at::Tensor>& kv_len;
+    const int32_t* kv() const { return kv_len.has_value() ? kv_len->data_ptr<int32_t>() : nullptr; }
+};
+
+// The checks the sampler operators share; `op` names the operator in the messages
+void check_sample_args(const char* op, const SampleArgs& a) {
+    check_host(a.dur, at::kInt, "dur"); check_host(a.cond_mask, at::kByte, "cond_mask"); check_host(a.text, at::kInt, "text");
+    check_dev_f32(a.cond, "cond"); check_dev_f32(a.y0, "y0");
+    TORCH_CHECK(a.text.dim() == 2 && a.text.size(0) == a.dur.numel() && a.cond.sizes() == a.y0.sizes(), "f5hip::", op, ": shapes");
+    if (a.kv_len.has_value()) {
+        check_host(*a.kv_len, at::kInt, "kv_len");
+        TORCH_CHECK(a.kv_len->numel() == a.dur.numel(), "f5hip::", op, ": kv_len needs one value per unit");
+    }
+    const int64_t rows = a.dur.sum().item<int64_t>();
+    TORCH_CHECK(a.cond.dim() == 2 && a.cond.size(0) == rows && a.cond_mask.numel() == rows, "f5hip::", op, ": cond / y0 / cond_mask need sum(dur) = ", rows, " rows");
+}
+// a host fp32 / int32 array with one value per unit
+void check_per_unit(const char* op, const at::Tensor& t, at::ScalarType ty, const char* name, const SampleArgs& a) {
+    check_host(t, ty, name);
+    TORCH_CHECK(t.numel() == a.dur.numel(), "f5hip::", op, ": ", name, " needs one value per unit (", t.numel(), " for ", a.dur.numel(), ")");
+}
+void check_t_grid(const char* op, const at::Tensor& t_grid) {
+    check_host(t_grid, at::kFloat, "t_grid");
+    TORCH_CHECK(t_grid.numel() >= 2, "f5hip::", op, ": shapes");
+}
+
+// Calls the entry point `fn` of the C ABI: the arguments all of them share, `tail` (its time grid and strength), then the output and the stream
+template <class Fn, class... Tail>
+at::Tensor run_sample(const char* name, Fn fn, int64_t handle, const SampleArgs& a, Tail... tail) {
+    at::Tensor out = at::empty_like(a.y0);
+    const int rc = fn((f5hip_dit*)handle, (int32_t)a.dur.numel(), a.dur.data_ptr<int32_t>(), a.kv(), a.cond.data_ptr<float>(), a.cond_mask.data_ptr<uint8_t>(),
+                      a.text.data_ptr<int32_t>(), (int32_t)a.text.size(1), a.y0.data_ptr<float>(), tail..., out.data_ptr<float>(), stream_of(a.y0));
+    TORCH_CHECK(rc == 0, name, ": ", f5hip_last_error());
+    return out;
+}
+
+// t_grid [steps + 1] fp32 host.  Returns the sampled mel rows [sum(dur), mel].
 at::Tensor cfm_sample(int64_t handle, const at::Tensor& dur, const c10::optional<at::Tensor>& kv_len, const at::Tensor& cond, const at::Tensor& cond_mask,
                       const at::Tensor& text, const at::Tensor& y0, const at::Tensor& t_grid, double cfg_strength) {
-    check_host(dur, at::kInt, "dur"); check_host(cond_mask, at::kByte, "cond_mask"); check_host(text, at::kInt, "text"); check_host(t_grid, at::kFloat, "t_grid");
-    check_dev_f32(cond, "cond"); check_dev_f32(y0, "y0");
-    TORCH_CHECK(text.dim() == 2 && text.size(0) == dur.numel() && t_grid.numel() >= 2 && cond.sizes() == y0.sizes(), "f5hip::cfm_sample: shapes");
-    if (kv_len.has_value()) check_host(*kv_len, at::kInt, "kv_len");
-    at::Tensor out = at::empty_like(y0);
-    const int rc = f5hip_cfm_sample_masked((f5hip_dit*)handle, (int32_t)dur.numel(), dur.data_ptr<int32_t>(), kv_len.has_value() ? kv_len->data_ptr<int32_t>() : nullptr,
-                                           cond.data_ptr<float>(), cond_mask.data_ptr<uint8_t>(), text.data_ptr<int32_t>(), (int32_t)text.size(1), y0.data_ptr<float>(),
-                                           t_grid.data_ptr<float>(), (int32_t)t_grid.numel() - 1, (float)cfg_strength, out.data_ptr<float>(), stream_of(y0));
-    TORCH_CHECK(rc == 0, "f5hip_cfm_sample: ", f5hip_last_error());
-    return out;
+    const SampleArgs a{dur, cond, cond_mask, text, y0, kv_len};
+    check_sample_args("cfm_sample", a);
+    check_t_grid("cfm_sample", t_grid);
+    return run_sample("f5hip_cfm_sample", f5hip_cfm_sample_masked, handle, a, t_grid.data_ptr<float>(), (int32_t)t_grid.numel() - 1, (float)cfg_strength);
 }
 
 // cfm_sample with cfg_strength [b] fp32 host: one strength per unit (f5hip_cfm_sample_units; < 1e-5 drops that unit's unconditional rows).
 at::Tensor cfm_sample_units(int64_t handle, const at::Tensor& dur, const c10::optional<at::Tensor>& kv_len, const at::Tensor& cond, const at::Tensor& cond_mask,
                             const at::Tensor& text, const at::Tensor& y0, const at::Tensor& t_grid, const at::Tensor& cfg_strength) {
-    check_host(dur, at::kInt, "dur"); check_host(cond_mask, at::kByte, "cond_mask"); check_host(text, at::kInt, "text"); check_host(t_grid, at::kFloat, "t_grid");
-    check_host(cfg_strength, at::kFloat, "cfg_strength");
-    check_dev_f32(cond, "cond"); check_dev_f32(y0, "y0");
-    TORCH_CHECK(text.dim() == 2 && text.size(0) == dur.numel() && t_grid.numel() >= 2 && cond.sizes() == y0.sizes(), "f5hip::cfm_sample_units: shapes");
-    TORCH_CHECK(cfg_strength.numel() == dur.numel(), "f5hip::cfm_sample_units: cfg_strength needs one value per unit (", cfg_strength.numel(), " for ", dur.numel(), ")");
-    if (kv_len.has_value()) {
-        check_host(*kv_len, at::kInt, "kv_len");
-        TORCH_CHECK(kv_len->numel() == dur.numel(), "f5hip::cfm_sample_units: kv_len needs one value per unit");
-    }
-    const int64_t rows = dur.sum().item<int64_t>();
-    TORCH_CHECK(cond.dim() == 2 && cond.size(0) == rows && cond_mask.numel() == rows, "f5hip::cfm_sample_units: cond / y0 / cond_mask need sum(dur) = ", rows, " rows");
-    at::Tensor out = at::empty_like(y0);
-    const int rc = f5hip_cfm_sample_units((f5hip_dit*)handle, (int32_t)dur.numel(), dur.data_ptr<int32_t>(), kv_len.has_value() ? kv_len->data_ptr<int32_t>() : nullptr,
-                                          cond.data_ptr<float>(), cond_mask.data_ptr<uint8_t>(), text.data_ptr<int32_t>(), (int32_t)text.size(1), y0.data_ptr<float>(),
-                                          t_grid.data_ptr<float>(), (int32_t)t_grid.numel() - 1, cfg_strength.data_ptr<float>(), out.data_ptr<float>(), stream_of(y0));
-    TORCH_CHECK(rc == 0, "f5hip_cfm_sample_units: ", f5hip_last_error());
-    return out;
+    const SampleArgs a{dur, cond, cond_mask, text, y0, kv_len};
+    check_sample_args("cfm_sample_units", a);
+    check_t_grid("cfm_sample_units", t_grid);
+    check_per_unit("cfm_sample_units", cfg_strength, at::kFloat, "cfg_strength", a);
+    return run_sample("f5hip_cfm_sample_units", f5hip_cfm_sample_units, handle, a, t_grid.data_ptr<float>(), (int32_t)t_grid.numel() - 1, cfg_strength.data_ptr<float>());
 }
 
 // cfm_sample_units with one time grid per unit (f5hip_cfm_sample_grids): steps [b] int32 host (each >= 1), t_grids fp32 host, the b grids of
 // steps[u] + 1 points one after the other (sum(steps) + b floats).
 at::Tensor cfm_sample_grids(int64_t handle, const at::Tensor& dur, const c10::optional<at::Tensor>& kv_len, const at::Tensor& cond, const at::Tensor& cond_mask,
                             const at::Tensor& text, const at::Tensor& y0, const at::Tensor& steps, const at::Tensor& t_grids, const at::Tensor& cfg_strength) {
-    check_host(dur, at::kInt, "dur"); check_host(cond_mask, at::kByte, "cond_mask"); check_host(text, at::kInt, "text"); check_host(t_grids, at::kFloat, "t_grids");
-    check_host(steps, at::kInt, "steps"); check_host(cfg_strength, at::kFloat, "cfg_strength");
-    check_dev_f32(cond, "cond"); check_dev_f32(y0, "y0");
-    TORCH_CHECK(text.dim() == 2 && text.size(0) == dur.numel() && cond.sizes() == y0.sizes(), "f5hip::cfm_sample_grids: shapes");
-    TORCH_CHECK(cfg_strength.numel() == dur.numel(), "f5hip::cfm_sample_grids: cfg_strength needs one value per unit (", cfg_strength.numel(), " for ", dur.numel(), ")");
-    TORCH_CHECK(steps.numel() == dur.numel(), "f5hip::cfm_sample_grids: steps needs one value per unit (", steps.numel(), " for ", dur.numel(), ")");
-    if (kv_len.has_value()) {
-        check_host(*kv_len, at::kInt, "kv_len");
-        TORCH_CHECK(kv_len->numel() == dur.numel(), "f5hip::cfm_sample_grids: kv_len needs one value per unit");
-    }
+    const SampleArgs a{dur, cond, cond_mask, text, y0, kv_len};
+    check_sample_args("cfm_sample_grids", a);
+    check_host(t_grids, at::kFloat, "t_grids");
+    check_per_unit("cfm_sample_grids", cfg_strength, at::kFloat, "cfg_strength", a);
+    check_per_unit("cfm_sample_grids", steps, at::kInt, "steps", a);
     const int32_t* sp = steps.data_ptr<int32_t>();
     int64_t points = 0;
     for (int64_t u = 0; u < steps.numel(); u++) {
@@ -86,14 +102,7 @@ at::Tensor cfm_sample_grids(int64_t handle, const at::Tensor& dur, const c10::op
         points += sp[u] + 1;
     }
     TORCH_CHECK(t_grids.numel() == points, "f5hip::cfm_sample_grids: t_grids needs sum(steps) + n = ", points, " values (got ", t_grids.numel(), ")");
-    const int64_t rows = dur.sum().item<int64_t>();
-    TORCH_CHECK(cond.dim() == 2 && cond.size(0) == rows && cond_mask.numel() == rows, "f5hip::cfm_sample_grids: cond / y0 / cond_mask need sum(dur) = ", rows, " rows");
-    at::Tensor out = at::empty_like(y0);
-    const int rc = f5hip_cfm_sample_grids((f5hip_dit*)handle, (int32_t)dur.numel(), dur.data_ptr<int32_t>(), kv_len.has_value() ? kv_len->data_ptr<int32_t>() : nullptr,
-                                          cond.data_ptr<float>(), cond_mask.data_ptr<uint8_t>(), text.data_ptr<int32_t>(), (int32_t)text.size(1), y0.data_ptr<float>(),
-                                          sp, t_grids.data_ptr<float>(), cfg_strength.data_ptr<float>(), out.data_ptr<float>(), stream_of(y0));
-    TORCH_CHECK(rc == 0, "f5hip_cfm_sample_grids: ", f5hip_last_error());
-    return out;
+    return run_sample("f5hip_cfm_sample_grids", f5hip_cfm_sample_grids, handle, a, sp, t_grids.data_ptr<float>(), cfg_strength.data_ptr<float>());
 }
 
 at::Tensor vocos_decode(int64_t handle, const at::Tensor& mel, int64_t hop_length) {

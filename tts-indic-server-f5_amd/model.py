@@ -357,46 +357,29 @@ class F5HipModel:
         text_np = _i32(text.numpy())
         tg = np.ascontiguousarray(t.numpy().astype(np.float32))
         d_np, kv_np = _i32(lay), _i32(durs)
+        # One call: the TORCH_LIBRARY operator (csrc/torch_ops.cpp) when it is loaded, else the same C entry point through ctypes.  `arg`: how a
+        # host array travels; `extra`: what the entry point takes between y0 and the output (the operator reads `steps` off the grid).
+        use_op = torch_ops.load()
+        arg = torch.from_numpy if use_op else _ptr
+        grid = [arg(tg)] if use_op else [arg(tg), steps]
         if not one_grid:   # one grid (and strength) per item: f5hip_cfm_sample_grids
             cfg_all = cfg_units if cfg_units is not None else np.full(batch, float(cfg_strength), dtype=np.float32)
-            steps_np = _i32(steps_u)
-            tgs = np.ascontiguousarray(torch.cat(grids).numpy().astype(np.float32))
-            if torch_ops.load():
-                try:
-                    out_packed = torch_ops.ops().cfm_sample_grids(
-                        int(self._h), torch.from_numpy(d_np), torch.from_numpy(kv_np) if padded else None, cond_packed, torch.from_numpy(mask_packed),
-                        torch.from_numpy(text_np), y0_packed, torch.from_numpy(steps_np), torch.from_numpy(tgs), torch.from_numpy(cfg_all))
-                except RuntimeError as e:
-                    raise _lib.F5HipError(str(e).split("\n")[0]) from None
-            else:
-                _lib.check(self._lib.f5hip_cfm_sample_grids(
-                    self._h, batch, _ptr(d_np), _ptr(kv_np) if padded else None, _ptr(cond_packed), _ptr(mask_packed), _ptr(text_np),
-                    text_np.shape[1], _ptr(y0_packed), _ptr(steps_np), _ptr(tgs), _ptr(cfg_all), _ptr(out_packed), _lib.current_stream_ptr()),
-                    "f5hip_cfm_sample_grids")
+            steps_np, tgs = _i32(steps_u), np.ascontiguousarray(torch.cat(grids).numpy().astype(np.float32))
+            entry, extra = "cfm_sample_grids", [arg(steps_np), arg(tgs), arg(cfg_all)]
         elif cfg_units is not None:   # one strength per item: f5hip_cfm_sample_units
-            if torch_ops.load():
-                try:
-                    out_packed = torch_ops.ops().cfm_sample_units(
-                        int(self._h), torch.from_numpy(d_np), torch.from_numpy(kv_np) if padded else None, cond_packed, torch.from_numpy(mask_packed),
-                        torch.from_numpy(text_np), y0_packed, torch.from_numpy(tg), torch.from_numpy(cfg_units))
-                except RuntimeError as e:
-                    raise _lib.F5HipError(str(e).split("\n")[0]) from None
-            else:
-                _lib.check(self._lib.f5hip_cfm_sample_units(
-                    self._h, batch, _ptr(d_np), _ptr(kv_np) if padded else None, _ptr(cond_packed), _ptr(mask_packed), _ptr(text_np),
-                    text_np.shape[1], _ptr(y0_packed), _ptr(tg), steps, _ptr(cfg_units), _ptr(out_packed), _lib.current_stream_ptr()),
-                    "f5hip_cfm_sample_units")
-        elif torch_ops.load():   # the TORCH_LIBRARY operator over the same C entry point (csrc/torch_ops.cpp)
+            entry, extra = "cfm_sample_units", grid + [arg(cfg_units)]
+        else:
+            entry, extra = "cfm_sample", grid + [float(cfg_strength)]
+        kv = arg(kv_np) if padded else None
+        if use_op:
             try:
-                out_packed = torch_ops.ops().cfm_sample(int(self._h), torch.from_numpy(d_np), torch.from_numpy(kv_np) if padded else None, cond_packed,
-                                                        torch.from_numpy(mask_packed), torch.from_numpy(text_np), y0_packed, torch.from_numpy(tg), float(cfg_strength))
+                out_packed = getattr(torch_ops.ops(), entry)(int(self._h), arg(d_np), kv, cond_packed, arg(mask_packed), arg(text_np), y0_packed, *extra)
             except RuntimeError as e:
                 raise _lib.F5HipError(str(e).split("\n")[0]) from None
         else:
-            _lib.check(self._lib.f5hip_cfm_sample_masked(
-                self._h, batch, _ptr(d_np), _ptr(kv_np) if padded else None, _ptr(cond_packed), _ptr(mask_packed), _ptr(text_np),
-                text_np.shape[1], _ptr(y0_packed), _ptr(tg), steps, float(cfg_strength), _ptr(out_packed), _lib.current_stream_ptr()),
-                "f5hip_cfm_sample")
+            fn = getattr(self._lib, "f5hip_cfm_sample_masked" if entry == "cfm_sample" else "f5hip_" + entry)
+            _lib.check(fn(self._h, batch, arg(d_np), kv, _ptr(cond_packed), arg(mask_packed), arg(text_np), text_np.shape[1], _ptr(y0_packed),
+                          *extra, _ptr(out_packed), _lib.current_stream_ptr()), "f5hip_" + entry)
         if all(n == nmax for n in lay):
             out = out_packed.view(batch, nmax, self.num_channels)
         else:
