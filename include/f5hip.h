@@ -114,6 +114,27 @@ int f5hip_cfm_sample_grids(f5hip_dit* m, int32_t n_utt, const int32_t* dur, cons
                            const uint8_t* cond_mask, const int32_t* text, int32_t nt_max, const float* y0_dev,
                            const int32_t* steps, const float* t_grids, const float* cfg_strength, float* out_dev, void* stream);
 
+/* One SPAN of the ODE loop of CFM.sample (F/model/cfm.py:160-204): f5hip_cfm_sample_grids that can stop at a step boundary and be
+ * resumed by a later call.  The library keeps nothing between spans: a span is one more stateless sampler call.
+ *   y0_dev     per unit its CURRENT ODE state [dur, mel]: the noise (cfm.py:181-186) for its first span, else the rows the previous span
+ *              returned for it
+ *   steps[u], t_grids   this span only: steps[u] >= 1 steps over steps[u] + 1 points, a contiguous slice of the unit's whole grid
+ *              (cfm.py:196-198) with the whole grid's fp32 values.  Midpoint and RK4 spans end on step boundaries too; RK4's fourth
+ *              stage of the span's last step is evaluated at the slice's last point.
+ *   last[u]    host uint8 [n_utt].  != 0: the unit ends with this span and receives where(cond_mask, cond, x) (cfm.py:204) like every
+ *              other sampler call; 0: it receives the raw fp32 state of all its frames after its last step of the span, prompt frames
+ *              included -- what the next span takes as y0_dev.  Chosen per frame on the device by the final select kernel; the flags
+ *              ride in the per-call metadata upload.  Nothing else about the step loop depends on `last`.
+ * Units of a span may be at different points of grids of different lengths; everything f5hip_cfm_sample_grids says about layout, limits
+ * (256 distinct time points) and dispatch holds: equal span grids make it the one-grid call, and a span over every unit's whole grid with
+ * `last` all 1 launches the kernels of f5hip_cfm_sample_grids and returns its bits.  With the shape-invariant attention mode a unit
+ * sampled in spans, among any other units, equals the unit sampled alone in one call, bit for bit.  Every refusal (null `last`,
+ * steps[u] < 1, the dur / kv_len / time-point limits) comes before the first launch. */
+int f5hip_cfm_sample_span(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev,
+                          const uint8_t* cond_mask, const int32_t* text, int32_t nt_max, const float* y0_dev,
+                          const int32_t* steps, const float* t_grids, const float* cfg_strength, const uint8_t* last,
+                          float* out_dev, void* stream);
+
 /* The fixed-grid solver both sample calls use: replaces CFM(odeint_kwargs=dict(method=...)) (F/model/cfm.py:37-41,72,200; set from
  * load_model(ode_method=...), F/infer/utils_infer.py:251).  0 = "euler" (default): x += dt * v(t_i, x).  1 = "midpoint":
  * x += dt * v(t_i + dt / 2, x + dt / 2 * v(t_i, x)), two backbone evaluations per step, at most 64 steps per call.  2 = "rk4": torchdiffeq's

@@ -47,6 +47,8 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_cfm_sample_grids": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "f5hip_cfm_sample_span": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_dit_set_ode_method": (C.c_int, [C.c_void_p, C.c_int32]),
     "f5hip_dit_set_attention_shape_invariant": (C.c_int, [C.c_void_p, C.c_int32]),
     "f5hip_dit_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),

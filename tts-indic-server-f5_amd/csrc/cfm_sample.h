@@ -1,5 +1,5 @@
-// The ODE loop of CFM.sample (F/model/cfm.py:160-204): f5hip_cfm_sample, _masked, _units and _grids, every ODE method, driven by ONE
-// step loop (run_sampler).  Host orchestration only: the kernels are elementwise.h's.  Included at the end of f5hip.hip (same translation
+// The ODE loop of CFM.sample (F/model/cfm.py:160-204): f5hip_cfm_sample, _masked, _units, _grids and _span, every ODE method, driven by
+// ONE step loop (run_sampler).  Host orchestration only: the kernels are elementwise.h's.  Included at the end of f5hip.hip (same translation
 // unit: it drives setup_sequences, the precompute_* functions and forward_step).
 #pragma once
 
@@ -22,6 +22,7 @@ static void stage_times(int method, float t0, float t1, float t[4]) {
 struct SampleArgs {
     int32_t n_utt; const int32_t *dur, *kv_len; const float* cond_dev; const uint8_t* cond_mask; const int32_t* text; int32_t nt_max;
     const float* y0_dev; float* out_dev; void* stream;
+    const uint8_t* last = nullptr;   // f5hip_cfm_sample_span: per unit, != 0 = the unit ends with this call (null: every unit does)
     bool ok() const { return n_utt > 0 && dur && cond_dev && cond_mask && text && y0_dev && out_dev; }
 };
 
@@ -30,6 +31,7 @@ struct UnitLayout {
     std::vector<SeqDesc> seqs;
     std::vector<float> frame_cfg;   // per-unit strengths spread over the unit's frames (cfg_unit only)
     std::vector<int> frame_unit;    // layout position of every frame's unit
+    std::vector<uint8_t> frame_final;   // what the final select reads per frame: cond_mask of the units that end, 0 = keep the raw state (a.last only)
     std::vector<int> seq_unit;      // ... and of every sequence's
     std::vector<int> seq_end;       // seq_end[k]: sequences of the units at layout positions 0..k
     int n_frames = 0;
@@ -49,6 +51,7 @@ static int layout_units(f5hip_dit* m, const SampleArgs& a, const std::vector<int
     L.n_frames = fo[n];
     L.frame_unit.resize(fo[n]);
     if (cfg_unit) L.frame_cfg.resize(fo[n]);
+    if (a.last) L.frame_final.resize(fo[n]);
     L.seq_end.resize(n);
     m->h_seq_len.clear();
     for (int k = 0; k < n; k++) {
@@ -63,6 +66,7 @@ static int layout_units(f5hip_dit* m, const SampleArgs& a, const std::vector<int
         for (int f = fo[u]; f < fo[u + 1]; f++) {
             L.frame_unit[f] = k;
             if (cfg_unit) L.frame_cfg[f] = use_cfg ? cfg_u : 0.0f;
+            if (a.last) L.frame_final[f] = a.last[u] && a.cond_mask[f];
         }
         for (int b = 0; b < (use_cfg ? 2 : 1); b++) {
             L.seqs.push_back({a.dur[u], kv, fo[u], u, b, b, b});
@@ -208,6 +212,8 @@ struct GridScope {
 // [row_c0, row_c0 + Mc_i)) of those units only, and the CFG kernels leave the frames of the finished units alone.  Every unit's time points
 // go through one precompute_time over their union; before each forward row_tp_kernel gives every row the time point of its unit, and the
 // modulation consumers read their vectors per row (m->d_row_tp; forward_step with ti = 0).
+// a.last (f5hip_cfm_sample_span): the grids are spans of longer ones and y0 is the state so far; the step loop is the same, and the final
+// select keeps the raw state of every frame of a unit that does not end here (the per-frame flags of the metadata upload: layout_units).
 static int run_sampler(f5hip_dit* m, const SampleArgs& a, const float* t_grid, int steps, const int32_t* unit_steps, float cfg_strength,
                        const float* cfg_unit) {
     const int n = a.n_utt, method = m->ode_method, per = kOdeRules[method].forwards;
@@ -221,7 +227,7 @@ static int run_sampler(f5hip_dit* m, const SampleArgs& a, const float* t_grid, i
     CK(layout_units(m, a, order, cfg_strength, cfg_unit, L));
     CK(plan_times(method, order, t_grid, steps, unit_steps, P));   // (every refusal of a grid comes before the first launch)
     const int mel = m->cfg.mel_dim, U = L.n_frames;
-    CK(setup_sequences(m, L.seqs, U, a.text, a.nt_max, a.cond_mask, st, cfg_unit ? L.frame_cfg.data() : nullptr));
+    CK(setup_sequences(m, L.seqs, U, a.text, a.nt_max, a.cond_mask, st, cfg_unit ? L.frame_cfg.data() : nullptr, a.last ? L.frame_final.data() : nullptr));
     GridScope scope{m};
     GridTables T{};
     if (unit_steps) CK(upload_grid_tables(m, L, P, st, T));
@@ -288,19 +294,30 @@ int f5hip_cfm_sample_units(f5hip_dit* m, int32_t n_utt, const int32_t* dur, cons
     return sample_one_grid(m, {n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, out_dev, stream}, t_grid, steps, 0.0f, cfg_strength);
 }
 
-int f5hip_cfm_sample_grids(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
-                           const int32_t* text, int32_t nt_max, const float* y0_dev, const int32_t* steps, const float* t_grids,
-                           const float* cfg_strength, float* out_dev, void* stream) {
-    const SampleArgs a{n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, out_dev, stream};
+// The calls with one grid per unit: one grid for all is f5hip_cfm_sample_units' call, kernels and results
+static int sample_grids(const char* name, f5hip_dit* m, const SampleArgs& a, const int32_t* steps, const float* t_grids, const float* cfg_strength) {
     if (!m || !m->finalized) return fail(-1, "model not finalized");
-    if (!a.ok() || !steps || !t_grids || !cfg_strength) return fail(-1, "cfm_sample_grids: bad argument");
+    if (!a.ok() || !steps || !t_grids || !cfg_strength) return fail(-1, "%s: bad argument", name);
     bool one_grid = true;
     size_t g0 = 0;
-    for (int u = 0; u < n_utt; u++) {
-        if (steps[u] < 1) return fail(-1, "cfm_sample_grids: steps[%d] = %d (need >= 1)", u, steps[u]);
+    for (int u = 0; u < a.n_utt; u++) {
+        if (steps[u] < 1) return fail(-1, "%s: steps[%d] = %d (need >= 1)", name, u, steps[u]);
         one_grid = one_grid && steps[u] == steps[0] && !memcmp(t_grids + g0, t_grids, sizeof(float) * ((size_t)steps[0] + 1));
         g0 += (size_t)steps[u] + 1;
     }
-    if (one_grid) return sample_one_grid(m, a, t_grids, steps[0], 0.0f, cfg_strength);   // one grid for all: f5hip_cfm_sample_units' call, kernels and results
+    if (one_grid) return sample_one_grid(m, a, t_grids, steps[0], 0.0f, cfg_strength);
     return run_sampler(m, a, t_grids, 0, steps, 0.0f, cfg_strength);
+}
+
+int f5hip_cfm_sample_grids(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
+                           const int32_t* text, int32_t nt_max, const float* y0_dev, const int32_t* steps, const float* t_grids,
+                           const float* cfg_strength, float* out_dev, void* stream) {
+    return sample_grids("cfm_sample_grids", m, {n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, out_dev, stream}, steps, t_grids, cfg_strength);
+}
+
+int f5hip_cfm_sample_span(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
+                          const int32_t* text, int32_t nt_max, const float* y0_dev, const int32_t* steps, const float* t_grids,
+                          const float* cfg_strength, const uint8_t* last, float* out_dev, void* stream) {
+    if (!last) return fail(-1, "cfm_sample_span: last is null");
+    return sample_grids("cfm_sample_span", m, {n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, out_dev, stream, last}, steps, t_grids, cfg_strength);
 }

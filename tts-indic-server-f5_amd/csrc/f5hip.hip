@@ -405,8 +405,9 @@ struct SeqDesc { int len, kvlen, frame0 /* first frame in caller's packed arrays
 // Lays the sequences out (each padded to a multiple of 128 rows), builds the per-row metadata and uploads it.
 // UNetT: row 0 of every sequence is the time token (F/model/backbones/unett.py:184); frames follow at rows 1..len.
 // frame_cfg (n_frames floats, or null): per-frame CFG strengths, uploaded with the rest (m->d_frame_cfg).
+// frame_final (n_frames flags, or null = frame_is_cond): which frames the sampler's final select overwrites with the conditioning.
 static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n_frames, const int32_t* text, int nt_max,
-                           const uint8_t* frame_is_cond, hipStream_t st, const float* frame_cfg = nullptr) {
+                           const uint8_t* frame_is_cond, hipStream_t st, const float* frame_cfg = nullptr, const uint8_t* frame_final = nullptr) {
     const int extra = m->arch == 1 ? 1 : 0;
     const bool mm = m->arch == 2;
     int rows = 0, rows_x = 0;
@@ -430,7 +431,7 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
     m->any_masked = false;
     m->h_seq_row0.assign(S + 1, 0); m->h_seqc_row0.assign(S + 1, rows_x);
     for (int r = 0; r < R; r++) { row_seq[r] = -1; row_token[r] = -1; row_frame[r] = -1; row_condframe[r] = -1; }
-    for (int u = 0; u < U; u++) { urow_c[u] = -1; urow_u[u] = -1; fic[u] = frame_is_cond ? frame_is_cond[u] : 0; }
+    for (int u = 0; u < U; u++) { urow_c[u] = -1; urow_u[u] = -1; fic[u] = frame_final ? frame_final[u] : frame_is_cond ? frame_is_cond[u] : 0; }
     m->max_len = 0;
     for (int s = 0; s < S; s++) {
         const SeqDesc& q = seqs[s];

@@ -5,6 +5,7 @@
 //   torch.ops.f5hip.cfm_sample(handle, dur, kv_len?, cond, cond_mask, text, y0, t_grid, cfg_strength) -> Tensor   F/model/cfm.py:160-204
 //   torch.ops.f5hip.cfm_sample_units(handle, dur, kv_len?, cond, cond_mask, text, y0, t_grid, cfg_strength) -> Tensor  (one strength per unit)
 //   torch.ops.f5hip.cfm_sample_grids(handle, dur, kv_len?, cond, cond_mask, text, y0, steps, t_grids, cfg_strength) -> Tensor  (one grid per unit)
+//   torch.ops.f5hip.cfm_sample_span(handle, dur, kv_len?, cond, cond_mask, text, y0, steps, t_grids, cfg_strength, last) -> Tensor  (resumable span)
 //   torch.ops.f5hip.vocos_decode(handle, mel) -> Tensor                                                          F/infer/utils_infer.py:472
 //   torch.ops.f5hip.vocos_decode_ragged(handle, mel, frames, channels, hop_length) -> Tensor (packed)                F/infer/utils_infer.py:472
 //   torch.ops.f5hip.bigvgan_forward(handle, mel, total_upsample) -> Tensor                                       F/infer/utils_infer.py:474
@@ -86,23 +87,41 @@ at::Tensor cfm_sample_units(int64_t handle, const at::Tensor& dur, const c10::op
     return run_sample("f5hip_cfm_sample_units", f5hip_cfm_sample_units, handle, a, t_grid.data_ptr<float>(), (int32_t)t_grid.numel() - 1, cfg_strength.data_ptr<float>());
 }
 
+// The checks of the operators with one grid per unit: steps, t_grids and cfg_strength against the units
+void check_unit_grids(const char* op, const SampleArgs& a, const at::Tensor& steps, const at::Tensor& t_grids, const at::Tensor& cfg_strength) {
+    check_sample_args(op, a);
+    check_host(t_grids, at::kFloat, "t_grids");
+    check_per_unit(op, cfg_strength, at::kFloat, "cfg_strength", a);
+    check_per_unit(op, steps, at::kInt, "steps", a);
+    const int32_t* sp = steps.data_ptr<int32_t>();
+    int64_t points = 0;
+    for (int64_t u = 0; u < steps.numel(); u++) {
+        TORCH_CHECK(sp[u] >= 1, "f5hip::", op, ": steps[", u, "] = ", sp[u], " (need >= 1)");
+        points += sp[u] + 1;
+    }
+    TORCH_CHECK(t_grids.numel() == points, "f5hip::", op, ": t_grids needs sum(steps) + n = ", points, " values (got ", t_grids.numel(), ")");
+}
+
 // cfm_sample_units with one time grid per unit (f5hip_cfm_sample_grids): steps [b] int32 host (each >= 1), t_grids fp32 host, the b grids of
 // steps[u] + 1 points one after the other (sum(steps) + b floats).
 at::Tensor cfm_sample_grids(int64_t handle, const at::Tensor& dur, const c10::optional<at::Tensor>& kv_len, const at::Tensor& cond, const at::Tensor& cond_mask,
                             const at::Tensor& text, const at::Tensor& y0, const at::Tensor& steps, const at::Tensor& t_grids, const at::Tensor& cfg_strength) {
     const SampleArgs a{dur, cond, cond_mask, text, y0, kv_len};
-    check_sample_args("cfm_sample_grids", a);
-    check_host(t_grids, at::kFloat, "t_grids");
-    check_per_unit("cfm_sample_grids", cfg_strength, at::kFloat, "cfg_strength", a);
-    check_per_unit("cfm_sample_grids", steps, at::kInt, "steps", a);
-    const int32_t* sp = steps.data_ptr<int32_t>();
-    int64_t points = 0;
-    for (int64_t u = 0; u < steps.numel(); u++) {
-        TORCH_CHECK(sp[u] >= 1, "f5hip::cfm_sample_grids: steps[", u, "] = ", sp[u], " (need >= 1)");
-        points += sp[u] + 1;
-    }
-    TORCH_CHECK(t_grids.numel() == points, "f5hip::cfm_sample_grids: t_grids needs sum(steps) + n = ", points, " values (got ", t_grids.numel(), ")");
-    return run_sample("f5hip_cfm_sample_grids", f5hip_cfm_sample_grids, handle, a, sp, t_grids.data_ptr<float>(), cfg_strength.data_ptr<float>());
+    check_unit_grids("cfm_sample_grids", a, steps, t_grids, cfg_strength);
+    return run_sample("f5hip_cfm_sample_grids", f5hip_cfm_sample_grids, handle, a, steps.data_ptr<int32_t>(), t_grids.data_ptr<float>(), cfg_strength.data_ptr<float>());
+}
+
+// One resumable span of cfm_sample_grids (f5hip_cfm_sample_span): y0 is every unit's current ODE state, steps / t_grids describe this span (a
+// contiguous slice of the unit's whole grid), last [b] uint8 host: 1 = the unit ends here and gets where(cond_mask, cond, x), 0 = it gets
+// its raw state, prompt frames included, to be handed back as y0 of its next span.
+at::Tensor cfm_sample_span(int64_t handle, const at::Tensor& dur, const c10::optional<at::Tensor>& kv_len, const at::Tensor& cond, const at::Tensor& cond_mask,
+                           const at::Tensor& text, const at::Tensor& y0, const at::Tensor& steps, const at::Tensor& t_grids, const at::Tensor& cfg_strength,
+                           const at::Tensor& last) {
+    const SampleArgs a{dur, cond, cond_mask, text, y0, kv_len};
+    check_unit_grids("cfm_sample_span", a, steps, t_grids, cfg_strength);
+    check_per_unit("cfm_sample_span", last, at::kByte, "last", a);
+    return run_sample("f5hip_cfm_sample_span", f5hip_cfm_sample_span, handle, a, steps.data_ptr<int32_t>(), t_grids.data_ptr<float>(), cfg_strength.data_ptr<float>(),
+                      last.data_ptr<uint8_t>());
 }
 
 at::Tensor vocos_decode(int64_t handle, const at::Tensor& mel, int64_t hop_length) {
@@ -148,6 +167,7 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("cfm_sample(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor t_grid, float cfg_strength) -> Tensor", &cfm_sample);
     m.def("cfm_sample_units(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor t_grid, Tensor cfg_strength) -> Tensor", &cfm_sample_units);
     m.def("cfm_sample_grids(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor steps, Tensor t_grids, Tensor cfg_strength) -> Tensor", &cfm_sample_grids);
+    m.def("cfm_sample_span(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor steps, Tensor t_grids, Tensor cfg_strength, Tensor last) -> Tensor", &cfm_sample_span);
     m.def("vocos_decode(int handle, Tensor mel, int hop_length) -> Tensor", &vocos_decode);
     m.def("vocos_decode_ragged(int handle, Tensor mel, Tensor frames, int channels, int hop_length) -> Tensor", &vocos_decode_ragged);
     m.def("bigvgan_forward(int handle, Tensor mel, int total_upsample) -> Tensor", &bigvgan_forward);

@@ -16,6 +16,7 @@ Host-side differences, all explicit:
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import math
 import os
@@ -44,6 +45,7 @@ cfg_strength = 2.0
 sway_sampling_coef = -1.0
 speed = 1.0
 fix_duration = None
+span_steps = 8   # SpanScheduler: ODE steps per span (profiles/r07_admission_bench.txt; DESIGN.md "Resumable spans")
 
 
 def chunk_text(text, max_chars=135):
@@ -564,6 +566,147 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
         else:
             out.append((waves, target_sample_rate, specs))
     return out
+
+
+def request_wave(gen_text, waves, cross_fade_duration=cross_fade_duration):
+    """What a served request gets for its chunk waves: the per-chunk waves themselves when its text was a list of chunk texts (a streamed
+    request's head or tail, joined by the caller's `StreamJoiner`), else the joined wave as float32."""
+    if isinstance(gen_text, (list, tuple)):
+        return waves
+    return np.asarray(cross_fade_concat(waves, cross_fade_duration), dtype=np.float32)
+
+
+class SpanTicket:
+    """One admitted request of a `SpanScheduler`: its planned units, and -- once they have all ended -- `result` (`request_wave`)."""
+
+    def __init__(self, request, voice, units):
+        self.request, self.voice, self.units = request, voice, units
+        self.in_flight = self.cancelled = self.done = False
+        self.result = None
+
+    @property
+    def frames(self) -> int:
+        return sum(u.dur for u in self.units)
+
+    def cancel(self):
+        """Drops the request: its units leave at the next span boundary (nothing happens once it is done)."""
+        self.cancelled = True
+
+
+class SpanScheduler:
+    """Continuous batching over resumable sampler spans, synchronous and without threads: `admit(request)` plans a request (as
+    `infer_requests` plans it) and queues it; every `step()` is one span boundary followed by one span: cancelled tickets leave, waiting
+    tickets join in order of arrival while they fit, all units in flight advance by `span_steps` ODE steps of their own grids in ONE
+    `model_obj.advance` call (f5hip_cfm_sample_span), and the requests whose units have all ended are vocoded together (`_chunk_waves`:
+    ragged Vocos when the vocoder offers it) and returned.  So a request waits for at most one span of the others, not for their whole
+    batch, and with the shape-invariant attention mode its result is what `infer_requests` gives it alone with the same noise.
+
+    Requests are `infer_requests`' tuples, per-request options included.  Noise is drawn at admission: a seeded request (or one that carries
+    a `generator`) from its own generator in chunk order -- the generator moves only when the whole request was planned -- and an unseeded
+    one from the global generator, in admission order.  `max_frames` caps the summed rows (`dur`) of the units in flight; a request that
+    does not fit waits for a later boundary and nothing behind it overtakes it (a request larger than the cap runs when nothing else
+    is in flight).  `max_requests` caps the requests in flight the same way.  `span_units` has one entry per span: the units it advanced.
+    Every boundary pays one sequence set-up, one text / conditioning / time precompute and the packed state copies again, so a short span
+    buys its low admission wait with device time.  `span_steps` defaults to 8: measured on an MI355X (`tools/admission_bench.py`,
+    profiles/r07_admission_bench.txt) that boundary cost is 3.3 ms with 8 units in flight, 2.3 % of an 8-step span (4.6 % of a 4-step one),
+    and 8 is the shortest span whose median time to result on the trace was not above `MicroBatcher`'s."""
+
+    def __init__(self, model_obj, vocoder, span_steps=span_steps, max_frames=None, max_requests=None, mel_spec_type=mel_spec_type, target_rms=target_rms,
+                 cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
+                 speed=speed, fix_duration=fix_duration, device=None, tokenizer=text_to_tokens):
+        if not getattr(model_obj, "resumable_spans", False):
+            raise ValueError("SpanScheduler needs a model object with resumable spans (plan_unit / advance: F5HipModel)")
+        if int(span_steps) < 1:
+            raise ValueError(f"span_steps must be at least 1 (got {span_steps})")
+        self.model_obj, self.vocoder, self.span_steps = model_obj, vocoder, int(span_steps)
+        self.max_frames, self.max_requests = max_frames, max_requests
+        self.mel_spec_type, self.target_rms, self.cross_fade_duration = mel_spec_type, target_rms, cross_fade_duration
+        self.defaults = dict(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None)
+        self.fix_duration, self.device, self.tokenizer = fix_duration, device, tokenizer
+        self.waiting: list[SpanTicket] = []
+        self.in_flight: list[SpanTicket] = []
+        self.span_units: list[int] = []
+
+    @property
+    def busy(self) -> bool:
+        return bool(self.waiting or self.in_flight)
+
+    def admit(self, request) -> SpanTicket:
+        ref_audio, ref_text, gen_text = request[:3]
+        opts = dict(self.defaults, **(request[3] if len(request) > 3 and request[3] else {}))
+        unknown = set(opts) - set(REQUEST_OPTIONS) - {"generator"}
+        if unknown:
+            raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
+        voice = ref_audio if isinstance(ref_audio, PreparedVoice) else PreparedVoice(ref_audio, self.target_rms, self.device)
+        chunks = list(gen_text) if isinstance(gen_text, (list, tuple)) else request_chunks(ref_text, voice.seconds, gen_text)
+        voice, units = _plan_request(voice, ref_text, chunks, self.target_rms, opts["speed"], self.fix_duration, self.device, self.tokenizer)
+        own = opts.get("generator")
+        # a generator that continues a sequence is drawn from on a copy: the caller's moves only when every chunk was planned
+        gen = torch.Generator().set_state(own.get_state()) if own is not None else request_generator(opts["seed"])
+        cond = voice.cond(self.model_obj)
+        planned = [self.model_obj.plan_unit(cond, tokens, frames, steps=int(opts["nfe_step"]), cfg_strength=opts["cfg_strength"],
+                                            sway_sampling_coef=opts["sway_sampling_coef"], generator=gen) for tokens, frames in units]
+        if own is not None:
+            own.set_state(gen.get_state())
+        ticket = SpanTicket(request, voice, planned)
+        self.waiting.append(ticket)
+        return ticket
+
+    def _fits(self, ticket) -> bool:
+        if not self.in_flight:
+            return True
+        if self.max_requests is not None and len(self.in_flight) >= self.max_requests:
+            return False
+        return self.max_frames is None or sum(t.frames for t in self.in_flight) + ticket.frames <= self.max_frames
+
+    def _board(self):
+        """A span boundary: cancelled tickets leave, waiting ones join in order of arrival while they fit."""
+        self.in_flight = [t for t in self.in_flight if not t.cancelled]
+        self.waiting = [t for t in self.waiting if not t.cancelled]
+        while self.waiting and self._fits(self.waiting[0]):
+            ticket = self.waiting.pop(0)
+            ticket.in_flight = True
+            self.in_flight.append(ticket)
+
+    def _finish(self, tickets):
+        groups = [([u.mel for u in t.units], t.voice.ref_frames, t.voice.rms) for t in tickets]
+        for t, (waves, _) in zip(tickets, _chunk_waves(groups, self.vocoder, self.mel_spec_type, self.target_rms)):
+            t.result, t.done, t.in_flight = request_wave(t.request[2], waves, self.cross_fade_duration), True, False
+
+    def step(self) -> list:
+        """One boundary and one span.  Returns the tickets that finished, `result` set."""
+        self._board()
+        units = [u for t in self.in_flight for u in t.units if not u.done]
+        if not units:
+            return []
+        self.span_units.append(len(units))
+        self.model_obj.advance(units, self.span_steps)
+        finished = [t for t in self.in_flight if all(u.done for u in t.units)]
+        if finished:
+            self._finish(finished)   # (a ticket leaves `in_flight` only with its result: a failing vocoder call leaves it to `take_in_flight`)
+            self.in_flight = [t for t in self.in_flight if not t.done]
+        return finished
+
+    def take_in_flight(self) -> list:
+        """Removes and returns every ticket in flight (after a span that raised: the caller retries them with `run_alone`)."""
+        taken, self.in_flight = self.in_flight, []
+        for t in taken:
+            t.in_flight = False
+        return taken
+
+    def run_alone(self, ticket, lock=None) -> SpanTicket:
+        """The ticket's request on its own, from its first step, with the noise it drew at admission: its units are reset and advanced span
+        by span with nothing else in the call, then vocoded.  `lock` (a context manager, e.g. the device lock) is taken for each span and for
+        the vocoder call, not for the whole request, so whatever else waits for it waits for one span here too."""
+        lock = lock if lock is not None else contextlib.nullcontext()
+        for u in ticket.units:
+            u.reset()
+        while not all(u.done for u in ticket.units):
+            with lock:
+                self.model_obj.advance([u for u in ticket.units if not u.done], self.span_steps)
+        with lock:
+            self._finish([ticket])
+        return ticket
 
 
 _VOICE_TAG = re.compile(r"\[(\w+)\]")

@@ -8,6 +8,7 @@ libf5hip (HIP kernels); torch is used only to own device buffers and the stream.
 from __future__ import annotations
 
 import ctypes as C
+import types
 from dataclasses import dataclass
 
 import numpy as np
@@ -117,7 +118,70 @@ def per_unit_values(value, n: int, name: str):
     return vals
 
 
+def time_grid(n_steps: int, sway, t_start: float = 0.0):
+    """The fp32 time grid of CFM.sample (F/model/cfm.py:196-198): n_steps + 1 points from t_start to 1, sway-sampled unless `sway` is None."""
+    t = torch.linspace(t_start, 1, n_steps + 1, dtype=torch.float32)
+    if sway is not None:
+        t = t + sway * (torch.cos(torch.pi / 2 * t) - 1 + t)
+    return t
+
+
+def span_slices(units, max_steps: int):
+    """What one span asks of every unit: (take, last, t_grids) -- unit i takes take[i] = min(max_steps, remaining) steps, last[i] = 1 when that
+    brings it to its end, and t_grids holds the units' take[i] + 1 grid points from their cursors on, one slice after the other (slices
+    of the units' own fp32 arrays: the values of the whole grid, bit for bit)."""
+    units = list(units)
+    if not units or int(max_steps) < 1 or any(u.done for u in units):
+        raise ValueError("a span needs at least one unit, none of them done, and max_steps >= 1")
+    take = [min(int(max_steps), u.remaining) for u in units]
+    last = np.ascontiguousarray(np.asarray([k == u.remaining for k, u in zip(take, units)], dtype=np.uint8))
+    return take, last, np.ascontiguousarray(np.concatenate([u.grid[u.cursor:u.cursor + k + 1] for k, u in zip(take, units)]))
+
+
+class SpanUnit:
+    """One sampling unit that is advanced span by span (`F5HipModel.plan_unit` / `advance`): what `sample()` would hand the library for it
+    -- conditioning rows, their mask, the text row, the whole fp32 time grid, the CFG strength -- plus the ODE state on the device and
+    the step cursor.  `noise` is the state before the first step (kept so that the unit can start over: `reset()`); `mel` is the final
+    [dur, mel] result once the last step has run, else None."""
+
+    def __init__(self, cond, cond_mask, text, grid, cfg_strength, noise):
+        self.cond, self.cond_mask, self.text, self.grid, self.cfg_strength = cond, cond_mask, text, grid, float(cfg_strength)
+        self.noise, self.state = noise, noise.clone()
+        self.cursor, self.mel = 0, None
+
+    @property
+    def dur(self) -> int:
+        return int(self.state.shape[0])
+
+    @property
+    def steps(self) -> int:
+        return len(self.grid) - 1
+
+    @property
+    def remaining(self) -> int:
+        return self.steps - self.cursor
+
+    @property
+    def done(self) -> bool:
+        return self.mel is not None
+
+    def stepped(self, k: int, end) -> bool:
+        """After a span that wrote `state`: k steps on; at the end of the grid the state is the unit's mel.  True when it ended."""
+        self.cursor += k
+        if end:
+            self.mel = self.state
+        return bool(end)
+
+    def reset(self):
+        """Back to the first step with the noise the unit already drew."""
+        self.state.copy_(self.noise)
+        self.cursor, self.mel = 0, None
+
+
 class F5HipModel:
+    # plan_unit() / advance(): units are sampled in resumable spans (f5hip_cfm_sample_span), so new units can join between the spans of
+    # others; infer.SpanScheduler and serve.TTSManager(micro_batch=dict(span_steps=...)) look for this flag
+    resumable_spans = True
     # sample() / sample_units() take `steps` and `sway_sampling_coef` per unit too and sample units of different time grids in ONE call
     # (f5hip_cfm_sample_grids); infer.infer_requests and serve.ShardedSampler look for this flag before they merge time grids
     per_unit_time_grids = True
@@ -270,81 +334,12 @@ class F5HipModel:
         `steps` / `sway_sampling_coef`: one value, or one value per item (sway None allowed per item).  Every item's grid is built as the
         scalar call builds it; when they all come out equal the call is the one-grid call, otherwise f5hip_cfm_sample_grids samples every
         item on its own grid in the same call (an item whose steps are done leaves the batch)."""
-        if cond.ndim == 2:   # raw wave -> mel (cfm.py:103-106) with the extractor of mel_spec_type (modules.py:123-126)
-            cond = self.cond_mel(cond)
-        cond = cond.to(self.device, torch.float32)
-        batch, cond_seq_len = cond.shape[:2]
-        if lens is None:
-            lens = torch.full((batch,), cond_seq_len, dtype=torch.long)
-        lens = lens.cpu()
-        if isinstance(text, list):
-            assert self.vocab_char_map is not None, "string text needs a vocab_char_map"
-            text = list_str_to_idx(text, self.vocab_char_map)
-            assert text.shape[0] == batch
-        text = text.cpu()
-        text_lens = (text != -1).sum(dim=-1)
-        lens = torch.maximum(text_lens, lens)                                     # cfm.py:123-125
-        cond_mask = torch.arange(int(lens.amax()))[None, :] < lens[:, None]       # lens_to_mask
-        if edit_mask is not None:
-            cond_mask = cond_mask & edit_mask.cpu()
-        if isinstance(duration, int):
-            duration = torch.full((batch,), duration, dtype=torch.long)
-        duration = torch.maximum(lens + 1, duration.cpu()).clamp(max=max_duration)  # cfm.py:136-137
-        nmax = int(duration.amax())
-        test_cond = None
-        if duplicate_test:   # cfm.py:139-141: the prompt mel repeated once right behind itself
-            test_cond = torch.nn.functional.pad(cond, (0, 0, cond_seq_len, nmax - 2 * cond_seq_len), value=0.0)
-        cond = torch.nn.functional.pad(cond, (0, 0, 0, nmax - cond_seq_len), value=0.0)
-        cond_mask = torch.nn.functional.pad(cond_mask, (0, nmax - cond_mask.shape[-1]), value=False)
-
-        durs = [int(d) for d in duration]
+        p = self._plan_batch(cond, text, duration, lens=lens, steps=steps, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
+                             seed=seed, max_duration=max_duration, duplicate_test=duplicate_test, t_inter=t_inter, edit_mask=edit_mask, y0=y0,
+                             padded_batch=padded_batch, generators=generators)
+        batch, nmax, cond, cond_mask, text, durs, lay, padded = p.batch, p.nmax, p.cond, p.cond_mask, p.text, p.durs, p.lay, p.padded
+        cfg_units, ys, steps_u, grids = p.cfg_units, p.ys, p.steps_u, p.grids
         self._last_min_frames = durs
-        padded = bool(padded_batch) and batch > 1
-        lay = [nmax] * batch if padded else durs          # rows laid out per item
-
-        # noise (cfm.py:181-186): per item randn(dur_i), zero padded to the laid-out length
-        if generators is not None and len(generators) != batch:
-            raise ValueError(f"generators: one per item ({batch}), got {len(generators)}")
-        cfg_units = per_unit_cfg(cfg_strength, batch)
-        ys = []
-        for i, dur in enumerate(durs):
-            given = y0[i] if y0 is not None else None
-            if given is not None:
-                if given.shape[0] < dur:
-                    raise ValueError(f"y0 of item {i}: {given.shape[0]} rows for a duration of {dur}")
-                yi = given[:dur].to(self.device, torch.float32)
-            elif generators is not None and generators[i] is not None:
-                yi = torch.randn(dur, self.num_channels, generator=generators[i]).to(self.device)
-            else:
-                if seed is not None:
-                    torch.manual_seed(seed)
-                yi = torch.randn(dur, self.num_channels).to(self.device)
-            if lay[i] > dur:
-                yi = torch.nn.functional.pad(yi, (0, 0, 0, lay[i] - dur))
-            ys.append(yi)
-
-        t_start = 0.0
-        steps_u = per_unit_values(steps, batch, "steps")
-        sway_u = per_unit_values(sway_sampling_coef, batch, "sway_sampling_coef")
-        steps_u = [int(x) for x in steps_u] if isinstance(steps_u, list) else [int(steps_u)] * batch
-        sway_u = sway_u if isinstance(sway_u, list) else [sway_u] * batch
-        if duplicate_test:   # cfm.py:190-194
-            t_start = float(t_inter)
-            ys = [(1 - t_start) * ys[i] + t_start * test_cond[i, :lay[i]] for i in range(batch)]
-            steps_u = [int(x * (1 - t_start)) for x in steps_u]
-
-        def time_grid(n_steps, sway):
-            t = torch.linspace(t_start, 1, n_steps + 1, dtype=torch.float32)        # cfm.py:196-198
-            if sway is not None:
-                t = t + sway * (torch.cos(torch.pi / 2 * t) - 1 + t)
-            return t
-
-        grids, cache = [], {}
-        for n_steps, sway in zip(steps_u, sway_u):
-            key = (n_steps, None if sway is None else float(sway))
-            if key not in cache:
-                cache[key] = time_grid(n_steps, sway)
-            grids.append(cache[key])
         t = grids[0]
         one_grid = all(g.shape == t.shape and torch.equal(g, t) for g in grids[1:])
         steps = steps_u[0]
@@ -393,3 +388,127 @@ class F5HipModel:
         if vocoder is not None:
             out = vocoder(out.permute(0, 2, 1))
         return out, None
+
+    @torch.no_grad()
+    def plan_unit(self, cond, tokens, frames, *, steps=32, cfg_strength=2.0, sway_sampling_coef=-1.0, generator=None, y0=None) -> SpanUnit:
+        """Plans one unit as `sample_units` would sample it -- `cond` the prompt mel [1, n, mel] (or wave [1, nw]), `tokens` its text (a token list, or ids [nt]), `frames`
+        its planned rows -- without running a step: conditioning, mask, text row and time grid come from the code `sample()` uses, and the
+        noise is drawn here as `sample()` draws it (`y0` [dur, mel], else `generator`, else the global generator)."""
+        text = tokens.reshape(1, -1) if isinstance(tokens, torch.Tensor) else [tokens]
+        p = self._plan_batch(cond, text, torch.tensor([int(frames)], dtype=torch.long), lens=None, steps=int(steps), cfg_strength=float(cfg_strength),
+                             sway_sampling_coef=sway_sampling_coef, seed=None, max_duration=4096, duplicate_test=False, t_inter=0.1, edit_mask=None,
+                             y0=None if y0 is None else [y0], padded_batch=False, generators=None if generator is None else [generator])
+        dur = p.durs[0]
+        return SpanUnit(p.cond[0, :dur].contiguous(), np.ascontiguousarray(p.cond_mask[0, :dur].numpy().astype(np.uint8)), _i32(p.text.numpy()[0]),
+                        np.ascontiguousarray(p.grids[0].numpy().astype(np.float32)), cfg_strength, p.ys[0].contiguous())
+
+    @torch.no_grad()
+    def advance(self, units, max_steps: int):
+        """ONE f5hip_cfm_sample_span call over `units` (planned, not done): each takes min(max_steps, remaining) steps of its own grid from its
+        cursor on.  States and cursors are updated in place; a unit that reaches its end gets `mel` (the prompt rows overwritten with
+        the conditioning, cfm.py:204).  Returns the units that ended."""
+        units = list(units)
+        take, last, tgs = span_slices(units, max_steps)
+        nt = max(len(u.text) for u in units)
+        text_np = np.full((len(units), nt), -1, dtype=np.int32)
+        for i, u in enumerate(units):
+            text_np[i, :len(u.text)] = u.text
+        d_np, steps_np = _i32([u.dur for u in units]), _i32(take)
+        cfg = np.ascontiguousarray(np.asarray([u.cfg_strength for u in units], dtype=np.float32))
+        mask = np.ascontiguousarray(np.concatenate([u.cond_mask for u in units]))
+        cond = torch.cat([u.cond for u in units], dim=0)
+        y0 = torch.cat([u.state for u in units], dim=0)
+        if torch_ops.load():
+            f = torch.from_numpy
+            try:
+                out = torch_ops.ops().cfm_sample_span(int(self._h), f(d_np), None, cond, f(mask), f(text_np), y0, f(steps_np), f(tgs), f(cfg), f(last))
+            except RuntimeError as e:
+                raise _lib.F5HipError(str(e).split("\n")[0]) from None
+        else:
+            out = torch.empty_like(y0)
+            _lib.check(self._lib.f5hip_cfm_sample_span(self._h, len(units), _ptr(d_np), None, _ptr(cond), _ptr(mask), _ptr(text_np), nt, _ptr(y0),
+                                                       _ptr(steps_np), _ptr(tgs), _ptr(cfg), _ptr(last), _ptr(out), _lib.current_stream_ptr()),
+                       "f5hip_cfm_sample_span")
+        ended, o = [], 0
+        for u, k, end in zip(units, take, last):
+            u.state.copy_(out[o:o + u.dur])
+            o += u.dur
+            if u.stepped(k, end):
+                ended.append(u)
+        return ended
+
+    def _plan_batch(self, cond, text, duration, *, lens, steps, cfg_strength, sway_sampling_coef, seed, max_duration, duplicate_test, t_inter,
+                    edit_mask, y0, padded_batch, generators):
+        """Everything `sample()` decides before its library call (cfm.py:103-146,181-198), per item: the padded conditioning and its mask, the
+        text rows, the final durations and laid-out rows, the noise (drawn here, in item order) and the fp32 time grid.  The one place that
+        builds them: `sample()` hands them to one whole call, `plan_unit()` keeps them for a unit that is advanced span by span."""
+        if cond.ndim == 2:   # raw wave -> mel (cfm.py:103-106) with the extractor of mel_spec_type (modules.py:123-126)
+            cond = self.cond_mel(cond)
+        cond = cond.to(self.device, torch.float32)
+        batch, cond_seq_len = cond.shape[:2]
+        if lens is None:
+            lens = torch.full((batch,), cond_seq_len, dtype=torch.long)
+        lens = lens.cpu()
+        if isinstance(text, list):
+            assert self.vocab_char_map is not None, "string text needs a vocab_char_map"
+            text = list_str_to_idx(text, self.vocab_char_map)
+            assert text.shape[0] == batch
+        text = text.cpu()
+        text_lens = (text != -1).sum(dim=-1)
+        lens = torch.maximum(text_lens, lens)                                     # cfm.py:123-125
+        cond_mask = torch.arange(int(lens.amax()))[None, :] < lens[:, None]       # lens_to_mask
+        if edit_mask is not None:
+            cond_mask = cond_mask & edit_mask.cpu()
+        if isinstance(duration, int):
+            duration = torch.full((batch,), duration, dtype=torch.long)
+        duration = torch.maximum(lens + 1, duration.cpu()).clamp(max=max_duration)  # cfm.py:136-137
+        nmax = int(duration.amax())
+        test_cond = None
+        if duplicate_test:   # cfm.py:139-141: the prompt mel repeated once right behind itself
+            test_cond = torch.nn.functional.pad(cond, (0, 0, cond_seq_len, nmax - 2 * cond_seq_len), value=0.0)
+        cond = torch.nn.functional.pad(cond, (0, 0, 0, nmax - cond_seq_len), value=0.0)
+        cond_mask = torch.nn.functional.pad(cond_mask, (0, nmax - cond_mask.shape[-1]), value=False)
+
+        durs = [int(d) for d in duration]
+        padded = bool(padded_batch) and batch > 1
+        lay = [nmax] * batch if padded else durs          # rows laid out per item
+
+        # noise (cfm.py:181-186): per item randn(dur_i), zero padded to the laid-out length
+        if generators is not None and len(generators) != batch:
+            raise ValueError(f"generators: one per item ({batch}), got {len(generators)}")
+        cfg_units = per_unit_cfg(cfg_strength, batch)
+        ys = []
+        for i, dur in enumerate(durs):
+            given = y0[i] if y0 is not None else None
+            if given is not None:
+                if given.shape[0] < dur:
+                    raise ValueError(f"y0 of item {i}: {given.shape[0]} rows for a duration of {dur}")
+                yi = given[:dur].to(self.device, torch.float32)
+            elif generators is not None and generators[i] is not None:
+                yi = torch.randn(dur, self.num_channels, generator=generators[i]).to(self.device)
+            else:
+                if seed is not None:
+                    torch.manual_seed(seed)
+                yi = torch.randn(dur, self.num_channels).to(self.device)
+            if lay[i] > dur:
+                yi = torch.nn.functional.pad(yi, (0, 0, 0, lay[i] - dur))
+            ys.append(yi)
+
+        t_start = 0.0
+        steps_u = per_unit_values(steps, batch, "steps")
+        sway_u = per_unit_values(sway_sampling_coef, batch, "sway_sampling_coef")
+        steps_u = [int(x) for x in steps_u] if isinstance(steps_u, list) else [int(steps_u)] * batch
+        sway_u = sway_u if isinstance(sway_u, list) else [sway_u] * batch
+        if duplicate_test:   # cfm.py:190-194
+            t_start = float(t_inter)
+            ys = [(1 - t_start) * ys[i] + t_start * test_cond[i, :lay[i]] for i in range(batch)]
+            steps_u = [int(x * (1 - t_start)) for x in steps_u]
+
+        grids, cache = [], {}
+        for n_steps, sway in zip(steps_u, sway_u):
+            key = (n_steps, None if sway is None else float(sway))
+            if key not in cache:
+                cache[key] = time_grid(n_steps, sway, t_start)
+            grids.append(cache[key])
+        return types.SimpleNamespace(batch=batch, nmax=nmax, cond=cond, cond_mask=cond_mask, text=text, durs=durs, lay=lay, padded=padded,
+                                     cfg_units=cfg_units, ys=ys, steps_u=steps_u, grids=grids)

@@ -199,6 +199,131 @@ class MicroBatcher:
         self._fail_pending()
 
 
+class ContinuousBatcher:
+    """`MicroBatcher`'s interface over an `infer.SpanScheduler`: requests join the batch that is running at its next span boundary instead of
+    waiting for it to end.
+
+    `submit(request, on_start=None)` returns a `concurrent.futures.Future`.  One worker thread alternates between admission and spans: it
+    blocks on the queue only while nothing is in flight; otherwise it takes what has arrived without waiting, admits it
+    (`scheduler.admit`: the request is planned and draws its noise; `on_start()` is called right after, so what it submits is admitted at
+    the next boundary -- a stream's tail right behind its head), runs ONE span (`scheduler.step()`) under `lock` -- `TTSManager` passes
+    its device lock, so a speech edit runs between two spans -- and resolves the futures of the requests that finished.  A request whose
+    planning fails gets that error alone.  A future stays cancellable until it is resolved: cancelled while queued it is never admitted,
+    cancelled while in flight its units leave at the next boundary.  If a span raises, the requests in flight are retried one at a time
+    from their first step with the noise they already drew (`scheduler.run_alone`), so one bad request cannot fail its neighbours -- unless
+    the error is marked `no_retry` or only one request was in flight: then they fail at once.  `close()` as `MicroBatcher.close()`:
+    everything submitted before it is served, nothing stays unresolved, later submits are refused.  `batch_sizes`: per span, the units
+    it advanced."""
+
+    def __init__(self, scheduler, lock=None):
+        self.scheduler = scheduler
+        self._lock = lock if lock is not None else threading.Lock()
+        self._q: queue.Queue = queue.Queue()
+        self._closed = False
+        self._gate = threading.Lock()
+        self._futures: dict = {}                  # ticket -> future, admitted and unresolved (worker thread only)
+        self._thread = threading.Thread(target=self._loop, name="f5hip-continuous-batcher", daemon=True)
+        self._thread.start()
+
+    @property
+    def batch_sizes(self) -> list:
+        return self.scheduler.span_units
+
+    def submit(self, request, on_start: Callable[[], None] | None = None) -> Future:
+        f: Future = Future()
+        with self._gate:
+            if self._closed:
+                raise RuntimeError("ContinuousBatcher is closed")
+            self._q.put((request, f, on_start))
+        return f
+
+    def close(self, timeout: float = 30.0):
+        with self._gate:
+            if self._closed:
+                return
+            self._closed = True
+            self._q.put(None)                     # the shutdown mark: everything in front of it is still served
+        self._thread.join(timeout=timeout)
+        self._fail_pending()                      # (only non-empty if the worker thread did not get there: join timed out)
+
+    def _fail_pending(self):
+        while True:
+            try:
+                item = self._q.get_nowait()
+            except queue.Empty:
+                return
+            if item is not None and item[1].set_running_or_notify_cancel():
+                item[1].set_exception(RuntimeError("ContinuousBatcher is closed"))
+
+    @staticmethod
+    def _resolve(future, result=None, error=None):
+        if future.set_running_or_notify_cancel():     # False: cancelled in the meantime, its waiters are told
+            if error is not None:
+                future.set_exception(error)
+            else:
+                future.set_result(result)
+
+    def _admit(self, request, future, on_start):
+        if future.cancelled():                        # cancelled while queued: never admitted
+            future.set_running_or_notify_cancel()
+            return
+        try:
+            with self._lock:
+                ticket = self.scheduler.admit(request)
+        except Exception as e:   # noqa: BLE001 -- a request that cannot be planned fails alone
+            self._resolve(future, error=e)
+            return
+        self._futures[ticket] = future
+        if on_start is not None:
+            try:
+                on_start()
+            except Exception:   # noqa: BLE001 -- a hook must not stop the worker; its owner sees the missing follow-up
+                pass
+
+    def _span(self):
+        for ticket, future in list(self._futures.items()):
+            if future.cancelled():                    # cancelled while in flight (or waiting for room): leaves at this boundary
+                ticket.cancel()
+                future.set_running_or_notify_cancel()
+                del self._futures[ticket]
+        try:
+            with self._lock:
+                finished = self.scheduler.step()
+        except Exception as e:   # noqa: BLE001 -- isolate the failing request
+            failed = self.scheduler.take_in_flight()
+            for ticket in failed:
+                future = self._futures.pop(ticket)
+                if len(failed) == 1 or getattr(e, "no_retry", False):
+                    self._resolve(future, error=e)
+                    continue
+                try:
+                    self.scheduler.run_alone(ticket, lock=self._lock)     # the lock per span here too
+                    self._resolve(future, ticket.result)
+                except Exception as e1:   # noqa: BLE001
+                    self._resolve(future, error=e1)
+            return
+        for ticket in finished:
+            self._resolve(self._futures.pop(ticket), ticket.result)
+
+    def _loop(self):
+        closing = False
+        while not (closing and not self.scheduler.busy):
+            block = not self.scheduler.busy           # nothing to advance: wait for a request (or the shutdown mark)
+            while not closing:
+                try:
+                    item = self._q.get() if block else self._q.get_nowait()
+                except queue.Empty:
+                    break
+                block = False
+                if item is None:                      # nothing can follow the mark: submit() is closed
+                    closing = True
+                else:
+                    self._admit(*item)
+            if self.scheduler.busy:
+                self._span()
+        self._fail_pending()
+
+
 class SynthesisStream:
     """Iterator of float32 pieces (`TTSManager.synthesize_stream`).  `close()` may be called from any thread, also while another thread
     waits inside `next()`: it cancels the request's remaining chunks if their batch has not started, and the waiting `next()` then ends
@@ -229,8 +354,10 @@ class TTSManager:
                  micro_batch: dict | None = None, batch_invariant: bool = True):
         self.loader = loader
         self.batch_invariant = batch_invariant   # False: leave the model's attention mode alone (fastest kernel per launch shape)
-        self.micro_batch = micro_batch            # e.g. dict(max_requests=16, max_wait_ms=5): batch concurrent requests
-        self.batcher: MicroBatcher | None = None
+        self.micro_batch = micro_batch            # e.g. dict(max_requests=16, max_wait_ms=5): batch concurrent requests; with span_steps
+        #                                           (dict(span_steps=8, max_frames=32768); span_steps=None: infer.span_steps) requests join a
+        #                                           running batch between spans
+        self.batcher: MicroBatcher | ContinuousBatcher | None = None
         self.model = None
         self.model_obj = None
         self.vocoder = None
@@ -268,7 +395,19 @@ class TTSManager:
             if callable(setter) and self.batch_invariant:
                 setter(True)
             self.model = self._call
-            if self.micro_batch is not None:
+            if self.micro_batch is not None and "span_steps" in self.micro_batch:
+                # continuous batching: requests join the running batch at its next span boundary (infer.SpanScheduler)
+                if not getattr(model_obj, "resumable_spans", False):
+                    self.model = self.model_obj = self.vocoder = None
+                    raise ValueError("micro_batch with span_steps needs a model object that samples in resumable spans (F5HipModel); "
+                                     f"{type(model_obj).__name__} does not")
+                mb = dict(self.micro_batch)
+                mb.pop("max_wait_ms", None)      # nothing is waited for: a request joins at the next boundary
+                if mb["span_steps"] is None:     # dict(span_steps=None): the scheduler's default
+                    del mb["span_steps"]
+                sched = infer.SpanScheduler(model_obj, vocoder, mel_spec_type=self.mel_spec_type, **mb, **self.opts)
+                self.batcher = ContinuousBatcher(sched, lock=self._device_lock)
+            elif self.micro_batch is not None:
                 self.batcher = MicroBatcher(self._run_batch, **self.micro_batch)
         return self
 
@@ -277,9 +416,7 @@ class TTSManager:
         texts (a streamed request's head or tail) gets its per-chunk waves, for the caller's `infer.StreamJoiner`."""
         with self._device_lock:
             res = infer.infer_requests(requests, self.model_obj, self.vocoder, mel_spec_type=self.mel_spec_type, join=False, **self.opts)
-        fade = infer.cross_fade_duration
-        return [waves if isinstance(r[2], (list, tuple)) else np.asarray(infer.cross_fade_concat(waves, fade), dtype=np.float32)
-                for r, (waves, _, _) in zip(requests, res)]
+        return [infer.request_wave(r[2], waves) for r, (waves, _, _) in zip(requests, res)]
 
     def close(self):
         """Unload: stop the batcher (requests already queued are served, later ones refused) and drop the model objects."""
