@@ -318,6 +318,14 @@ int f5hip_bigvgan_finalize(f5hip_bigvgan* v);
 /* Replaces vocoder(mel) (F/infer/utils_infer.py:474): mel_dev fp32 [batch][num_mels][frames] ->
  * wave_dev fp32 [batch][frames * prod(upsample_rates)] (the reference's [batch, 1, n] squeezed), clamped to [-1, 1]. */
 int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const float* mel_dev, float* wave_dev, void* stream);
+/* vocoder(mel) (F/infer/utils_infer.py:474, which the reference runs once per chunk) over n mels of their own lengths in ONE call:
+ * frames host int32 [n], each >= 1; mel_dev fp32 [n][num_mels][T_max] (T_max = max frames[i]; item i valid for t < frames[i], the
+ * rest is not read) -> wave_dev fp32 packed, item i at offset total_up * sum_{j<i} frames[j], total_up * frames[i] samples long
+ * (total_up = prod(upsample_rates)).  Every stage is one launch for all items: the launch count does not depend on n.
+ * Item i's wave equals f5hip_bigvgan_forward of that item alone, bit for bit.  The (small) length tables are copied on `stream`,
+ * which the call waits for once before it launches. */
+int f5hip_bigvgan_forward_ragged(f5hip_bigvgan* v, int32_t n, const int32_t* frames, const float* mel_dev, float* wave_dev,
+                                 void* stream);
 
 /* ---------------------------------------------------------------- mel front-end ------------------------ */
 

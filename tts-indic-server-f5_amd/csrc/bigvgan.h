@@ -8,6 +8,10 @@
 //       columns); phase p uses taps (t, t-1) if p < r/2 else (t, t+1) -- the third tap's weights are zero
 //   Activation1d(SnakeBeta): fused [2x Kaiser-sinc upsample -> x + sin^2(x e^a)/(e^b + 1e-9) -> 2x low-pass downsample], one lane
 //       per (channel, run of 16 time steps), everything in registers (aa_snake2_kernel)
+// Ragged calls (f5hip_bigvgan_forward_ragged): item i has its own pitch ceil128(T_i) * prod(rates so far), so no tile is spent on the rows
+//       between a short item's end and the longest item's; every kernel finds an item's rows through small tables (BvRagged): per stage
+//       one [start, end) per 128-row block of the first stage (the conv GEMMs' row predicate: tile -> block is one division), and one
+//       entry per item in first-stage rows, scaled by prod(rates so far) (snake, conv_post: grid z = item).
 // Operand precision (f5hip_bigvgan_config.gemm_planes): 2 = split bf16 (three MFMAs per product, the parity default), 3 = one fp16
 //       plane (a third of the MFMA work and half the activation-plane traffic), 1 = plain bf16.
 #pragma once
@@ -31,6 +35,23 @@ struct f5hip_bigvgan {
     float *X = nullptr, *Y[3] = {}, *S = nullptr, *Tm = nullptr;
     Plane2 act, melp;
     float filt_h[12] = {};
+    int* meta = nullptr;   // tables of a ragged call (BvRagged)
+    size_t cap_meta = 0;
+};
+
+// Row layout of a ragged call.  Item order in rows: first the items whose pitch ceil128(T) is a multiple of 256 (rows_a first-stage rows),
+// then the others (rows_b) -- the two first-stage convolutions choose conv5.h or gemm.h by that, exactly as a call of the item alone does.
+//   items[j] = (first row, T, frames of the items before it in the CALLER's order = wave offset / total_up, index in the caller's order),
+//              in rows of the FIRST stage (one per mel frame): at a later stage they are multiplied by `scale` = prod(rates so far)
+//   nblk first-stage blocks of 128 rows; block b belongs to one item: blk_mel[b] = its index in the caller's order, and per stage s
+//   start(s)[b], end(s)[b] = its first row and the end of its valid rows at that stage (GemmArgs::row_seq_start / row_seq_end with seq_blk);
+//   start_b / end_b = the first stage's for the blocks behind rows_a, relative to row rows_a
+struct BvRagged {
+    int n = 0, t_stride = 0, rows_a = 0, rows_b = 0, nblk = 0;
+    const int4* items = nullptr;
+    const int *blk_mel = nullptr, *bounds = nullptr, *start_b = nullptr, *end_b = nullptr;
+    const int* start(int s) const { return bounds + (size_t)2 * s * nblk; }
+    const int* end(int s) const { return start(s) + nblk; }
 };
 
 // ------------------------------------------------------------------------------------------------ kernels
@@ -43,17 +64,24 @@ struct AaFilt { float f[12]; };
 // to [0, 2T) = the replicate padding of the down-sampler: values past the end repeat the last one, values before 0 repeat value 0)
 // and the R low-passed outputs.  No LDS, no barrier: ~44 VALU operations and 2.6 v_sin per output instead of ~25 LDS reads (the round-1
 // LDS-tiled kernel, removed).
+//   (items != null: ragged sequences, see BvRagged)
 //   grid (C / cw, ceil(T / (nseg R)), sequences), 256 lanes = nseg segments x cw channels (cw | C, cw <= 64)
 //   OUT: 0 = fp32, 1 = split bf16 planes, 2 = one fp16 plane
 template <int R, int OUT>
 __global__ __launch_bounds__(256) void aa_snake2_kernel(const float* __restrict__ x, int ldx, int C, int cw, int nseg, int P, int T,
                                                         const float* __restrict__ alpha_log, const float* __restrict__ beta_log, AaFilt flt,
-                                                        __bf16* __restrict__ out_hi, __bf16* __restrict__ out_lo, float* __restrict__ out_f32, int ldo) {
+                                                        __bf16* __restrict__ out_hi, __bf16* __restrict__ out_lo, float* __restrict__ out_f32, int ldo,
+                                                        const int4* __restrict__ items, int scale) {
     const int tid = threadIdx.x;
     const int seg = tid / cw, c = blockIdx.x * cw + (tid - seg * cw);
     const int t0 = (blockIdx.y * nseg + seg) * R;
+    size_t seq0 = (size_t)blockIdx.z * P;
+    if (items) {   // ragged: sequence z is item z, rows [items[z].x, + items[z].y) * scale (the grid's y covers the longest item)
+        const int4 it = items[blockIdx.z];
+        seq0 = (size_t)it.x * scale;
+        T = it.y * scale;
+    }
     if (seg >= nseg || t0 >= T || c >= C) return;
-    const size_t seq0 = (size_t)blockIdx.z * P;
     const float* xb = x + seq0 * ldx + c;
     float xv[R + 10];
 #pragma unroll
@@ -142,18 +170,40 @@ __global__ __launch_bounds__(128) void bv_mel_rows_kernel(const float* mel, int 
     if (lo) lo[(size_t)row * 128 + c] = l;
 }
 
+// the same for a ragged call: mel [n][C][t_stride], row -> its block's item (BvRagged); nothing beyond an item's T columns is read
+__global__ __launch_bounds__(128) void bv_mel_rows_ragged_kernel(const float* mel, int C, int t_stride, const int* blk_start, const int* blk_end, const int* blk_mel,
+                                                                 __bf16* hi, __bf16* lo, int f16) {
+    const int row = blockIdx.x, c = threadIdx.x;
+    const int t = row - blk_start[row >> 7];
+    float v = 0.0f;
+    if (row < blk_end[row >> 7] && c < C) v = mel[((size_t)blk_mel[row >> 7] * C + c) * t_stride + t];
+    if (f16) { reinterpret_cast<_Float16*>(hi)[(size_t)row * 128 + c] = sat_f16(v); return; }
+    __bf16 h, l;
+    split_bf16(v, h, l);
+    hi[(size_t)row * 128 + c] = h;
+    if (lo) lo[(size_t)row * 128 + c] = l;
+}
+
 // conv_post: Conv1d(C -> 1, k = 7, pad 3, no bias) + clamp(-1, 1);  a fp32 [rows][lda] -> wave [B][T].  256 outputs per workgroup: the
 // 262 input rows go through LDS (row pitch C + 1 floats: the lanes of a wave read consecutive rows, an odd pitch is conflict-free),
 // the weights are read as broadcasts.  Dynamic LDS = (262 (C + 1) + 7 C) floats.
+// items != null (ragged, BvRagged): sequence b is item b, its wave starts at items[b].z * scale and the grid's x covers the longest item.
 __global__ __launch_bounds__(256) void bv_conv_post_kernel(const float* __restrict__ a, int lda, int C, int P, int T, const float* __restrict__ w /*[C][7]*/,
-                                                           float* __restrict__ wave) {
+                                                           float* __restrict__ wave, const int4* __restrict__ items, int scale) {
     extern __shared__ float bvp_sm[];
     float* tile = bvp_sm;
     float* ws = bvp_sm + 262 * (C + 1);
     const int b = blockIdx.y, t0 = blockIdx.x * 256, tid = threadIdx.x;
+    int row0 = b * P;
+    size_t w0 = (size_t)b * T;
+    if (items) {
+        const int4 it = items[b];
+        row0 = it.x * scale; T = it.y * scale; w0 = (size_t)it.z * scale;
+        if (t0 >= T) return;   // (the whole workgroup: a shorter item's tail)
+    }
     for (int i = tid; i < 262 * C; i += 256) {
         const int r = i / C, c = i - r * C, ti = t0 - 3 + r;
-        tile[r * (C + 1) + c] = (ti >= 0 && ti < T) ? a[(size_t)(b * P + ti) * lda + c] : 0.0f;
+        tile[r * (C + 1) + c] = (ti >= 0 && ti < T) ? a[(size_t)(row0 + ti) * lda + c] : 0.0f;
     }
     for (int i = tid; i < 7 * C; i += 256) {
         const int k = i / C, c = i - k * C;
@@ -168,21 +218,28 @@ __global__ __launch_bounds__(256) void bv_conv_post_kernel(const float* __restri
         const float* wk = ws + k * C;
         for (int c = 0; c < C; c++) acc += wk[c] * row[c];
     }
-    wave[(size_t)b * T + t] = fminf(fmaxf(acc, -1.0f), 1.0f);
+    wave[w0 + t] = fminf(fmaxf(acc, -1.0f), 1.0f);
 }
 
 // the same operator without the LDS tile (channel counts whose tile would not fit)
-__global__ __launch_bounds__(256) void bv_conv_post_naive_kernel(const float* a, int lda, int C, int P, int T, const float* w /*[C][7]*/, float* wave) {
+__global__ __launch_bounds__(256) void bv_conv_post_naive_kernel(const float* a, int lda, int C, int P, int T, const float* w /*[C][7]*/, float* wave,
+                                                                 const int4* items, int scale) {
     const int b = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+    int row0 = b * P;
+    size_t w0 = (size_t)b * T;
+    if (items) {
+        const int4 it = items[b];
+        row0 = it.x * scale; T = it.y * scale; w0 = (size_t)it.z * scale;
+    }
     if (t >= T) return;
     float acc = 0.0f;
     for (int k = 0; k < 7; k++) {
         const int ti = t + k - 3;
         if (ti < 0 || ti >= T) continue;
-        const float* row = a + (size_t)(b * P + ti) * lda;
+        const float* row = a + (size_t)(row0 + ti) * lda;
         for (int c = 0; c < C; c++) acc += w[c * 7 + k] * row[c];
     }
-    wave[(size_t)b * T + t] = fminf(fmaxf(acc, -1.0f), 1.0f);
+    wave[w0 + t] = fminf(fmaxf(acc, -1.0f), 1.0f);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -214,6 +271,7 @@ void f5hip_bigvgan_destroy(f5hip_bigvgan* v) {
     }
     for (float* p : {v->post_alpha, v->post_beta, v->post_w}) dev_free(p);
     dev_free(v->ws);
+    dev_free(v->meta);
     delete v;
 }
 
@@ -322,45 +380,51 @@ int f5hip_bigvgan_finalize(f5hip_bigvgan* v) {
     return 0;
 }
 
-// GemmArgs of the Conv1d c over M rows of operand planes A (sequences of pitch P rows, T of them valid): out [M][c_out] = conv + bias + res
-static GemmArgs conv_args(const BvConv& c, const Plane2& A, int M, int P, int T, const float* res, float* out) {
+// GemmArgs of the Conv1d c over M rows of operand planes A (sequences of pitch P rows, T of them valid): out [M][c_out] = conv + bias + res.
+// blk > 0: ragged sequences, bounds [start, end) per block of blk rows (GemmArgs::seq_blk), every one of them starting at a multiple of P rows
+static GemmArgs conv_args(const BvConv& c, const Plane2& A, int M, int P, int T, const float* res, float* out, const int* start = nullptr,
+                          const int* end = nullptr, int blk = 0) {
     GemmArgs g = gemm_base(A, c.c_in_pad, c.w, M);
     g.conv_kpt = c.c_in_pad / 32; g.conv_center = (c.k - 1) / 2; g.conv_dil = c.dil; g.seq_pitch = P; g.seq_valid = T;
+    g.row_seq_start = start; g.row_seq_end = end; g.seq_blk = blk;
     g.res = res; g.ldres = c.c_out; g.out_f32 = out; g.ldo = c.c_out;
     return g;
 }
 
 // nsplit: operand planes (2 split bf16, 3 fp16, 1 bf16); conv5.h first where it covers the shape (nsplit >= 2), else gemm.h
-static int bv_conv(int nsplit, const BvConv& c, const Plane2& A, int M, int P, int T, const float* res, float* out, hipStream_t st) {
-    GemmArgs g = conv_args(c, A, M, P, T, res, out);
+static int bv_conv(int nsplit, const BvConv& c, const Plane2& A, int M, int P, int T, const float* res, float* out, hipStream_t st,
+                   const int* start = nullptr, const int* end = nullptr, int blk = 0) {
+    GemmArgs g = conv_args(c, A, M, P, T, res, out, start, end, blk);
     return run_conv(nsplit, g, c.w, nsplit >= 2, true, c.w.n_pad % 128 ? 64 : 128, st);
 }
 
 // Activation1d over fp32 rows x [M][ch] (sequences of pitch P rows, T valid): out_mode 0 -> fp32 rows out_f32 [M][ldo], 1 -> split-bf16
 // planes hi / lo [M][ldo], 2 -> one fp16 plane hi [M][ldo].  One lane per (channel, 16 time steps): cw channels x nseg segments fill the
-// 256 lanes of a workgroup (cw | ch, cw <= 64)
+// 256 lanes of a workgroup (cw | ch, cw <= 64).  items != null: the n_items ragged sequences of BvRagged at `scale`, T = the longest one's rows
 static int bv_snake_launch(const float* x, int ch, int M, int P, int T, const float* alpha, const float* beta, const AaFilt& f, int out_mode,
-                           __bf16* hi, __bf16* lo, float* out_f32, int ldo, hipStream_t st) {
+                           __bf16* hi, __bf16* lo, float* out_f32, int ldo, hipStream_t st, const int4* items = nullptr, int n_items = 0, int scale = 0) {
     constexpr int R = 16;
     int cw = ch < 64 ? ch : 64;
     while (ch % cw) cw--;
     if (ch == 96) cw = 32;   // 8 segments of 32 channels fill the 256 lanes; 64 would leave a half-empty second column block
     const int nseg = 256 / cw;
-    const dim3 grid(ch / cw, (T + nseg * R - 1) / (nseg * R), M / P);
-    if (out_mode == 0) hipLaunchKernelGGL((aa_snake2_kernel<R, 0>), grid, dim3(256), 0, st, x, ch, ch, cw, nseg, P, T, alpha, beta, f, (__bf16*)nullptr, (__bf16*)nullptr, out_f32, ldo);
-    else if (out_mode == 2) hipLaunchKernelGGL((aa_snake2_kernel<R, 2>), grid, dim3(256), 0, st, x, ch, ch, cw, nseg, P, T, alpha, beta, f, hi, (__bf16*)nullptr, (float*)nullptr, ldo);
-    else hipLaunchKernelGGL((aa_snake2_kernel<R, 1>), grid, dim3(256), 0, st, x, ch, ch, cw, nseg, P, T, alpha, beta, f, hi, lo, (float*)nullptr, ldo);
+    const dim3 grid(ch / cw, (T + nseg * R - 1) / (nseg * R), items ? n_items : M / P);
+    if (out_mode == 0) hipLaunchKernelGGL((aa_snake2_kernel<R, 0>), grid, dim3(256), 0, st, x, ch, ch, cw, nseg, P, T, alpha, beta, f, (__bf16*)nullptr, (__bf16*)nullptr, out_f32, ldo, items, scale);
+    else if (out_mode == 2) hipLaunchKernelGGL((aa_snake2_kernel<R, 2>), grid, dim3(256), 0, st, x, ch, ch, cw, nseg, P, T, alpha, beta, f, hi, (__bf16*)nullptr, (float*)nullptr, ldo, items, scale);
+    else hipLaunchKernelGGL((aa_snake2_kernel<R, 1>), grid, dim3(256), 0, st, x, ch, ch, cw, nseg, P, T, alpha, beta, f, hi, lo, (float*)nullptr, ldo, items, scale);
     CKL("aa_snake2");
     return 0;
 }
 
 // Activation1d over fp32 rows x [M][ch] -> the conv operand planes (out == nullptr) or fp32 rows out [M][ch]
 static int bv_snake(f5hip_bigvgan* v, const float* x, int ch, int cpad, int M, int P, int T, const float* alpha, const float* beta, float* out,
-                    hipStream_t st) {
+                    hipStream_t st, const BvRagged* rg = nullptr, int scale = 0) {
     AaFilt f;
     memcpy(f.f, v->filt_h, sizeof(f.f));
-    if (out) return bv_snake_launch(x, ch, M, P, T, alpha, beta, f, 0, nullptr, nullptr, out, ch, st);
-    return bv_snake_launch(x, ch, M, P, T, alpha, beta, f, v->nsplit == 3 ? 2 : 1, v->act.hi, v->act.lo, nullptr, cpad, st);
+    const int4* items = rg ? rg->items : nullptr;
+    const int n = rg ? rg->n : 0;
+    if (out) return bv_snake_launch(x, ch, M, P, T, alpha, beta, f, 0, nullptr, nullptr, out, ch, st, items, n, scale);
+    return bv_snake_launch(x, ch, M, P, T, alpha, beta, f, v->nsplit == 3 ? 2 : 1, v->act.hi, v->act.lo, nullptr, cpad, st, items, n, scale);
 }
 
 // Dynamic LDS of bv_conv_post_kernel at C channels
@@ -368,49 +432,69 @@ static size_t bv_conv_post_lds(int C) { return (size_t)(262 * (C + 1) + 7 * C) *
 
 // conv_post + clamp over fp32 rows a [batch P][lda] -> wave [batch][T].  variant 0: the LDS kernel when its tile fits in 48 KB, else the
 // naive kernel (what the generator runs); 1: the LDS kernel (fails when it would not fit); 2: the naive kernel
-static int bv_conv_post(const float* a, int lda, int C, int batch, int P, int T, const float* w, float* wave, int variant, hipStream_t st) {
+// items != null: `batch` ragged items (BvRagged) at `scale`, T = the longest one's rows, wave packed
+static int bv_conv_post(const float* a, int lda, int C, int batch, int P, int T, const float* w, float* wave, int variant, hipStream_t st,
+                        const int4* items = nullptr, int scale = 0) {
     const size_t lds = bv_conv_post_lds(C);
     if (variant == 1 && lds > 48 * 1024) return fail(-1, "conv_post: the LDS kernel's tile does not fit at C = %d", C);
     if (variant == 1 || (variant == 0 && lds <= 48 * 1024))
-        hipLaunchKernelGGL(bv_conv_post_kernel, dim3((T + 255) / 256, batch), dim3(256), lds, st, a, lda, C, P, T, w, wave);
-    else hipLaunchKernelGGL(bv_conv_post_naive_kernel, dim3((T + 255) / 256, batch), dim3(256), 0, st, a, lda, C, P, T, w, wave);
+        hipLaunchKernelGGL(bv_conv_post_kernel, dim3((T + 255) / 256, batch), dim3(256), lds, st, a, lda, C, P, T, w, wave, items, scale);
+    else hipLaunchKernelGGL(bv_conv_post_naive_kernel, dim3((T + 255) / 256, batch), dim3(256), 0, st, a, lda, C, P, T, w, wave, items, scale);
     CKL("conv_post");
     return 0;
 }
 
-int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const float* mel_dev, float* wave_dev, void* stream) {
-    if (!v || !v->finalized) return fail(-1, "vocoder not finalized");
-    if (batch <= 0 || frames <= 0 || !mel_dev || !wave_dev) return fail(-1, "bigvgan_forward: bad argument");
-    hipStream_t st = (hipStream_t)stream;
+// Workspace for M0 first-stage rows.  Largest stage: rows_i * C_i with rows_i = M0 * prod(rates), C_i = c0 >> (i+1)
+static int bv_reserve(f5hip_bigvgan* v, size_t M0) {
     const f5hip_bigvgan_config& c = v->cfg;
-    const int T0 = frames, P0 = ceil_to(T0, 128);
+    size_t max_f32 = M0 * v->c0, max_act = M0 * ceil_to(v->c0, 32);
+    size_t rows = M0;
+    for (int i = 0; i < v->n_up; i++) {
+        rows *= c.upsample_rates[i];
+        const int ch = v->c0 >> (i + 1);
+        max_f32 = std::max(max_f32, rows * ch);
+        max_act = std::max(max_act, rows * ceil_to(ch, 32));
+    }
+    if (max_f32 <= v->cap) return 0;
+    if (alloc_workspace(&v->ws, "BigVGAN workspace", [&](Arena& a) {
+            v->X = a.f32(max_f32); v->S = a.f32(max_f32); v->Tm = a.f32(max_f32);
+            for (int j = 0; j < 3; j++) v->Y[j] = a.f32(max_f32);
+            v->act = a.plane2(max_act + 4096); v->melp = a.plane2(M0 * 128 + 4096);
+        })) { v->cap = 0; return -5; }
+    v->cap = max_f32;
+    return 0;
+}
+
+// The generator over M0 first-stage rows.  rg == null: uniform sequences of pitch P0 rows with T0 valid, mel [M0 / P0][num_mels][T0] ->
+// wave [M0 / P0][total_up T0].  rg != null: the ragged layout rg (tables on the device), mel [n][num_mels][t_stride] -> packed wave; every
+// stage is still ONE launch per operator for all items, but for the two first-stage convolutions (conv_pre, ups[0]), which run once over
+// the items of 256-aligned pitch and once over the others.
+static int bv_generate(f5hip_bigvgan* v, int M0, int P0, int T0, const BvRagged* rg, const float* mel_dev, float* wave_dev, hipStream_t st) {
+    const f5hip_bigvgan_config& c = v->cfg;
     const int plane_mode = v->nsplit == 3 ? 2 : (v->nsplit == 2 ? 1 : 3);   // bv_mean3_kernel's output mode
-    // largest stage: rows_i * C_i with rows_i = batch * P0 * prod(rates), C_i = c0 >> (i+1)
-    size_t max_f32 = (size_t)batch * P0 * v->c0, max_act = (size_t)batch * P0 * ceil_to(v->c0, 32);
-    {
-        size_t rows = (size_t)batch * P0;
-        for (int i = 0; i < v->n_up; i++) {
-            rows *= c.upsample_rates[i];
-            const int ch = v->c0 >> (i + 1);
-            max_f32 = std::max(max_f32, rows * ch);
-            max_act = std::max(max_act, rows * ceil_to(ch, 32));
-        }
-    }
-    if (max_f32 > v->cap) {
-        if (alloc_workspace(&v->ws, "BigVGAN workspace", [&](Arena& a) {
-                v->X = a.f32(max_f32); v->S = a.f32(max_f32); v->Tm = a.f32(max_f32);
-                for (int j = 0; j < 3; j++) v->Y[j] = a.f32(max_f32);
-                v->act = a.plane2(max_act + 4096); v->melp = a.plane2((size_t)batch * P0 * 128 + 4096);
-            })) { v->cap = 0; return -5; }
-        v->cap = max_f32;
-    }
+    CK(bv_reserve(v, (size_t)M0));
     prof_begin(PROF_VOCOS, st);
-    // mel [B][num_mels][T] -> rows [B*P0][128] operand planes (uniform sequences: row = b * P0 + t)
-    hipLaunchKernelGGL(bv_mel_rows_kernel, dim3(batch * P0), dim3(128), 0, st, mel_dev, c.num_mels, T0, P0, v->melp.hi, v->melp.lo, v->nsplit == 3 ? 1 : 0);
+    // mel [B][num_mels][T] -> rows [M0][128] operand planes (uniform sequences: row = b * P0 + t)
+    if (rg) hipLaunchKernelGGL(bv_mel_rows_ragged_kernel, dim3(M0), dim3(128), 0, st, mel_dev, c.num_mels, rg->t_stride, rg->start(0), rg->end(0), rg->blk_mel, v->melp.hi, v->melp.lo, v->nsplit == 3 ? 1 : 0);
+    else hipLaunchKernelGGL(bv_mel_rows_kernel, dim3(M0), dim3(128), 0, st, mel_dev, c.num_mels, T0, P0, v->melp.hi, v->melp.lo, v->nsplit == 3 ? 1 : 0);
     CKL("bv_mel_rows");
-    int M = batch * P0, P = P0, T = T0;
+    int M = M0, P = P0, T = T0, scale = 1;
     int ch = v->c0;
-    CK(bv_conv(v->nsplit, v->pre, v->melp, M, P, T, nullptr, v->S, st));   // S = conv_pre(mel)
+    // a convolution at stage s (s up-samplers so far), residual res
+    auto conv = [&](const BvConv& cv, int s, const float* res, float* out) -> int {
+        if (!rg) return bv_conv(v->nsplit, cv, v->act, M, P, T, res, out, st);
+        return bv_conv(v->nsplit, cv, v->act, M, P, T, res, out, st, rg->start(s), rg->end(s), 128 * scale);
+    };
+    // a convolution over first-stage rows: ragged items of 256-aligned pitch (conv5.h takes them, as it does when such an item is alone), then the rest
+    auto conv0 = [&](const BvConv& cv, const Plane2& A, float* out) -> int {
+        if (!rg) return bv_conv(v->nsplit, cv, A, M, P, T, nullptr, out, st);
+        if (rg->rows_a) CK(bv_conv(v->nsplit, cv, A, rg->rows_a, 256, 0, nullptr, out, st, rg->start(0), rg->end(0), 128));
+        if (rg->rows_b)
+            CK(bv_conv(v->nsplit, cv, rows_from(A, (size_t)rg->rows_a * cv.c_in_pad), rg->rows_b, 128, 0, nullptr, out + (size_t)rg->rows_a * cv.c_out, st,
+                       rg->start_b, rg->end_b, 128));
+        return 0;
+    };
+    CK(conv0(v->pre, v->melp, v->S));   // S = conv_pre(mel)
     {   // operand planes of ups[0]
         const size_t n4 = (size_t)M * ch / 4;
         hipLaunchKernelGGL(bv_mean3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, v->S, v->S, v->S, 1, (size_t)M, ch, (float*)nullptr, v->act.hi, v->act.lo,
@@ -420,8 +504,9 @@ int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const
     for (int i = 0; i < v->n_up; i++) {
         const int r = c.upsample_rates[i], co = ch / 2, cpad = ceil_to(co, 32);
         // ups[i]: 3-tap implicit GEMM over the planes of the previous stage -> X viewed as [M][r*co] == [M*r][co]
-        CK(bv_conv(v->nsplit, v->ups[i], v->act, M, P, T, nullptr, v->X, st));
-        M *= r; P *= r; T *= r; ch = co;
+        if (i == 0) CK(conv0(v->ups[0], v->act, v->X));
+        else CK(conv(v->ups[i], i, nullptr, v->X));
+        M *= r; P *= r; T *= r; scale *= r; ch = co;
         if (cpad != ch) {   // padded channels of the A operand must read as zero
             if (hipMemsetAsync(v->act.hi, 0, (size_t)M * cpad * 2, st) != hipSuccess || (v->nsplit == 2 && hipMemsetAsync(v->act.lo, 0, (size_t)M * cpad * 2, st) != hipSuccess))
                 return fail(-6, "bigvgan memset");
@@ -431,10 +516,10 @@ int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const
             float* y = v->Y[j];
             for (int d = 0; d < 3; d++) {
                 const float* in = d == 0 ? v->X : y;   // AMPBlock1: x = x + convs2[d](act(convs1[d](act(x))))
-                CK(bv_snake(v, in, ch, cpad, M, P, T, rb.alpha[2 * d], rb.beta[2 * d], nullptr, st));
-                CK(bv_conv(v->nsplit, rb.c1[d], v->act, M, P, T, nullptr, v->Tm, st));
-                CK(bv_snake(v, v->Tm, ch, cpad, M, P, T, rb.alpha[2 * d + 1], rb.beta[2 * d + 1], nullptr, st));
-                CK(bv_conv(v->nsplit, rb.c2[d], v->act, M, P, T, in, y, st));
+                CK(bv_snake(v, in, ch, cpad, M, P, T, rb.alpha[2 * d], rb.beta[2 * d], nullptr, st, rg, scale));
+                CK(conv(rb.c1[d], i + 1, nullptr, v->Tm));
+                CK(bv_snake(v, v->Tm, ch, cpad, M, P, T, rb.alpha[2 * d + 1], rb.beta[2 * d + 1], nullptr, st, rg, scale));
+                CK(conv(rb.c2[d], i + 1, in, y));
             }
         }
         // mean of the three blocks: the last stage keeps fp32 rows for activation_post, the others only feed the next up-sampler
@@ -444,9 +529,73 @@ int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const
                            v->act.hi, v->act.lo, cpad, last ? 0 : plane_mode);
         CKL("bv_mean3");
     }
-    // activation_post -> fp32 (Tm), conv_post + clamp -> wave [B][T]
-    CK(bv_snake(v, v->S, ch, ch, M, P, T, v->post_alpha, v->post_beta, v->Tm, st));
-    CK(bv_conv_post(v->Tm, ch, ch, batch, P, T, v->post_w, wave_dev, 0, st));
+    // activation_post -> fp32 (Tm), conv_post + clamp -> wave [B][T] (ragged: packed)
+    CK(bv_snake(v, v->S, ch, ch, M, P, T, v->post_alpha, v->post_beta, v->Tm, st, rg, scale));
+    CK(bv_conv_post(v->Tm, ch, ch, rg ? rg->n : M / P, P, T, v->post_w, wave_dev, 0, st, rg ? rg->items : nullptr, scale));
     prof_end(PROF_VOCOS, st);
     return 0;
+}
+
+int f5hip_bigvgan_forward(f5hip_bigvgan* v, int32_t batch, int32_t frames, const float* mel_dev, float* wave_dev, void* stream) {
+    if (!v || !v->finalized) return fail(-1, "vocoder not finalized");
+    if (batch <= 0 || frames <= 0 || !mel_dev || !wave_dev) return fail(-1, "bigvgan_forward: bad argument");
+    const int P0 = ceil_to(frames, 128);
+    return bv_generate(v, batch * P0, P0, frames, nullptr, mel_dev, wave_dev, (hipStream_t)stream);
+}
+
+// Every item gets its own rows (BvRagged); the tables go up once, on the caller's stream, and every stage then runs as for a uniform batch:
+// the launch count does not depend on n.  No value of mel_dev beyond column frames[i] of item i is read.
+int f5hip_bigvgan_forward_ragged(f5hip_bigvgan* v, int32_t n, const int32_t* frames, const float* mel_dev, float* wave_dev, void* stream) {
+    if (!v || !v->finalized) return fail(-1, "vocoder not finalized");
+    if (n <= 0 || n > 65535 || !frames || !mel_dev || !wave_dev) return fail(-1, "bigvgan_forward_ragged: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    long long total_up = 1, m0 = 0, rows_a = 0;
+    for (int i = 0; i < v->n_up; i++) total_up *= v->cfg.upsample_rates[i];
+    int t_max = 0;
+    for (int i = 0; i < n; i++) {
+        if (frames[i] <= 0) return fail(-1, "bigvgan_forward_ragged: item %d has %d frames", i, frames[i]);
+        const int p = ceil_to(frames[i], 128);
+        m0 += p;
+        if (p % 256 == 0) rows_a += p;
+        t_max = std::max(t_max, (int)frames[i]);
+    }
+    if (m0 * total_up > 2147483647LL) return fail(-1, "bigvgan_forward_ragged: batch too large (%lld rows)", m0 * total_up);
+    const int M0 = (int)m0, nblk = M0 / 128, nblk_a = (int)rows_a / 128, nblk_b = nblk - nblk_a, ns = v->n_up + 1;
+    // device tables, one int buffer: items [n] int4, blk_mel [nblk], per stage start [nblk] + end [nblk], start_b [nblk_b], end_b [nblk_b]
+    const size_t meta_n = (size_t)n * 4 + nblk + (size_t)ns * 2 * nblk + (size_t)2 * nblk_b;
+    if (meta_n > v->cap_meta) {
+        dev_free(v->meta);
+        if (hipMalloc((void**)&v->meta, sizeof(int) * meta_n) != hipSuccess) { v->meta = nullptr; v->cap_meta = 0; return fail(-5, "hipMalloc bigvgan meta"); }
+        v->cap_meta = meta_n;
+    }
+    std::vector<int> h(meta_n, 0);
+    int* items = &h[0]; int* blk_mel = items + 4 * n; int* bounds = blk_mel + nblk; int* start_b = bounds + (size_t)ns * 2 * nblk; int* end_b = start_b + nblk_b;
+    {
+        std::vector<int> prefix(n + 1, 0);
+        for (int i = 0; i < n; i++) prefix[i + 1] = prefix[i] + frames[i];
+        int j = 0, r0 = 0;
+        for (int pass = 0; pass < 2; pass++)   // the items of 256-aligned pitch first
+            for (int i = 0; i < n; i++) {
+                const int p = ceil_to(frames[i], 128);
+                if ((p % 256 == 0) != (pass == 0)) continue;
+                items[4 * j] = r0; items[4 * j + 1] = frames[i]; items[4 * j + 2] = prefix[i]; items[4 * j + 3] = i;
+                for (int b = r0 / 128; b < (r0 + p) / 128; b++) {
+                    blk_mel[b] = i;
+                    int scale = 1;
+                    for (int s = 0; s < ns; s++) {
+                        bounds[(size_t)2 * s * nblk + b] = r0 * scale; bounds[(size_t)(2 * s + 1) * nblk + b] = (r0 + frames[i]) * scale;
+                        if (s < v->n_up) scale *= v->cfg.upsample_rates[s];
+                    }
+                    if (pass) { start_b[b - nblk_a] = r0 - (int)rows_a; end_b[b - nblk_a] = r0 - (int)rows_a + frames[i]; }
+                }
+                r0 += p; j++;
+            }
+    }
+    CK(bv_reserve(v, (size_t)M0));   // (before the upload: nothing is queued when the allocation fails)
+    if (upload_sync(st, v->meta, h) != hipSuccess) return fail(-6, "bigvgan metadata upload");
+    BvRagged rg;
+    rg.n = n; rg.t_stride = t_max; rg.rows_a = (int)rows_a; rg.rows_b = M0 - (int)rows_a; rg.nblk = nblk;
+    rg.items = reinterpret_cast<const int4*>(v->meta);
+    rg.blk_mel = v->meta + 4 * n; rg.bounds = rg.blk_mel + nblk; rg.start_b = rg.bounds + (size_t)ns * 2 * nblk; rg.end_b = rg.start_b + nblk_b;
+    return bv_generate(v, M0, 256, t_max, &rg, mel_dev, wave_dev, st);
 }

@@ -95,8 +95,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Conv5Cfg<NP
         const int pw = wave - 4, ll = tid - 256;
         const int mine = (PW - pw + 3) >> 2;                   // weight pieces pw, pw + 4, ... of every k-step
         // the tile lies in one sequence (BM divides the sequence pitch / padding): its bounds are those of its first row
-        const int sstart = p.row_seq_start ? p.row_seq_start[m0] : (m0 / p.seq_pitch) * p.seq_pitch;
-        const int send = p.row_seq_start ? p.row_seq_end[m0] : sstart + p.seq_valid;
+        // (seq_blk: the bounds tables hold one entry per block of rows, GemmArgs)
+        const int srow = p.seq_blk ? m0 / p.seq_blk : m0;
+        const int sstart = p.row_seq_start ? p.row_seq_start[srow] : (m0 / p.seq_pitch) * p.seq_pitch;
+        const int send = p.row_seq_start ? p.row_seq_end[srow] : sstart + p.seq_valid;
         const char* wsrc[P_HI];
 #pragma unroll
         for (int j = 0; j < P_HI; j++) {
@@ -417,7 +419,8 @@ static hipError_t launch_conv5(int prec, const GemmArgs& a, int n_pad, hipStream
         if (a.K % taps || a.K / taps != 64) return hipErrorInvalidValue;
         return launch_conv5_t<2, 64, 2, false, 0, 1>(a, n_pad, taps, st);
     }
-    if (a.row_seq_start || a.group_w || a.act || a.mul || a.row_keep || a.out_hi || !a.out_f32) return hipErrorInvalidValue;
+    // (bounds tables: only per block of rows -- the ragged BigVGAN forward, whose sequences start at multiples of seq_pitch)
+    if ((a.row_seq_start && (a.seq_blk <= 0 || !a.row_seq_end)) || a.group_w || a.act || a.mul || a.row_keep || a.out_hi || !a.out_f32) return hipErrorInvalidValue;
     if (a.lda <= 0 || a.K % a.lda) return hipErrorInvalidValue;
     const int taps = a.K / a.lda;
     const int dil = a.conv_dil > 1 ? a.conv_dil : 1;

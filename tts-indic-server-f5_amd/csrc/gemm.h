@@ -46,8 +46,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int i = 0; i < A_RPT; i++) {
             const int mr = m0 + lrow + 64 * i;
             if (p.row_seq_start) {
-                sstart[i] = p.row_seq_start[mr];
-                send[i] = p.row_seq_end[mr];
+                const int sr = p.seq_blk ? mr / p.seq_blk : mr;
+                sstart[i] = p.row_seq_start[sr];
+                send[i] = p.row_seq_end[sr];
             } else {
                 sstart[i] = (mr / p.seq_pitch) * p.seq_pitch;
                 send[i] = sstart[i] + p.seq_valid;

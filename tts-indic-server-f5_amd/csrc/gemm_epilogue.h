@@ -44,7 +44,7 @@ struct GemmArgs {
     int conv_center;      // (kernel_size - 1) / 2
     int conv_group_cols;  // A column base = blockIdx.x * conv_group_cols (grouped conv with BN == group width)
     int conv_dil;         // tap spacing in rows (0 is treated as 1): dilated Conv1d
-    const int* row_seq_start;   // per-row sequence bounds, or null: uniform sequences of seq_pitch rows with seq_valid valid ones
+    const int* row_seq_start;   // per-row sequence bounds (per block of rows: seq_blk), or null: uniform sequences of seq_pitch rows with seq_valid valid ones
     const int* row_seq_end;
     int seq_pitch, seq_valid;
     int group_w;          // > 0: N is laid out as groups padded to 64 columns; real column = (n/64)*group_w + n%64
@@ -74,6 +74,10 @@ struct GemmArgs {
     // F5HIP_GEMM6_STAMPS, unit ops only), cycle stamps of conv5 (f5hip_op_conv1d); null on the path
     unsigned long long* stamps;
     int stamp_bx, stamp_by;
+    // implicit-GEMM conv (appended, so the offsets above stay as they are): > 0 = row_seq_start / row_seq_end hold one entry per BLOCK of
+    // seq_blk rows instead of one per row (the ragged BigVGAN forward, whose sequences are whole blocks of 128 x the up-sampling so far):
+    // row r is bounded by entry r / seq_blk.  seq_pitch then states the alignment every sequence start has (conv5.h needs 256)
+    int seq_blk;
 };
 
 // one 32 x WN slice staged in `stg` (fp32, row stride WN): generic epilogue, lane owns 4 columns of 32 / RPP rows.

@@ -9,6 +9,7 @@
 //   torch.ops.f5hip.vocos_decode(handle, mel) -> Tensor                                                          F/infer/utils_infer.py:472
 //   torch.ops.f5hip.vocos_decode_ragged(handle, mel, frames, channels, hop_length) -> Tensor (packed)                F/infer/utils_infer.py:472
 //   torch.ops.f5hip.bigvgan_forward(handle, mel, total_upsample) -> Tensor                                       F/infer/utils_infer.py:474
+//   torch.ops.f5hip.bigvgan_forward_ragged(handle, mel, frames, channels, total_upsample) -> Tensor (packed)         F/infer/utils_infer.py:474
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -161,6 +162,27 @@ at::Tensor bigvgan_forward(int64_t handle, const at::Tensor& mel, int64_t total_
     return wave;
 }
 
+// mel [n, channels, T_max] fp32 device, frames [n] int32 host (item i valid for t < frames[i], each >= 1) -> packed wave
+// [total_upsample * sum(frames[i])], item i at total_upsample * sum_{j<i} frames[j]
+at::Tensor bigvgan_forward_ragged(int64_t handle, const at::Tensor& mel, const at::Tensor& frames, int64_t channels, int64_t total_upsample) {
+    check_dev_f32(mel, "mel"); check_host(frames, at::kInt, "frames");
+    TORCH_CHECK(mel.dim() == 3 && mel.size(1) == channels, "f5hip::bigvgan_forward_ragged: mel [n, ", channels, ", T_max]");
+    TORCH_CHECK(frames.dim() == 1 && frames.numel() == mel.size(0) && frames.numel() > 0, "f5hip::bigvgan_forward_ragged: frames.numel() == mel.size(0)");
+    const int32_t* f = frames.data_ptr<int32_t>();
+    int64_t total = 0, t_max = 0;
+    for (int64_t i = 0; i < frames.numel(); i++) {
+        TORCH_CHECK(f[i] >= 1 && f[i] <= mel.size(2), "f5hip::bigvgan_forward_ragged: frames[", i, "] = ", f[i], " outside [1, mel.size(2) = ", mel.size(2), "]");
+        total += total_upsample * f[i];
+        t_max = std::max<int64_t>(t_max, f[i]);
+    }
+    TORCH_CHECK(t_max == mel.size(2), "f5hip::bigvgan_forward_ragged: mel.size(2) = ", mel.size(2), " must be the longest item's frames (", t_max, ")");
+    const c10::DeviceGuard guard(mel.device());   // allocation and stream on the mel's device
+    at::Tensor wave = at::empty({total}, mel.options());
+    const int rc = f5hip_bigvgan_forward_ragged((f5hip_bigvgan*)handle, (int32_t)frames.numel(), f, mel.data_ptr<float>(), wave.data_ptr<float>(), stream_of(mel));
+    TORCH_CHECK(rc == 0, "f5hip_bigvgan_forward_ragged: ", f5hip_last_error());
+    return wave;
+}
+
 }   // namespace
 
 TORCH_LIBRARY(f5hip, m) {
@@ -171,4 +193,5 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("vocos_decode(int handle, Tensor mel, int hop_length) -> Tensor", &vocos_decode);
     m.def("vocos_decode_ragged(int handle, Tensor mel, Tensor frames, int channels, int hop_length) -> Tensor", &vocos_decode_ragged);
     m.def("bigvgan_forward(int handle, Tensor mel, int total_upsample) -> Tensor", &bigvgan_forward);
+    m.def("bigvgan_forward_ragged(int handle, Tensor mel, Tensor frames, int channels, int total_upsample) -> Tensor", &bigvgan_forward_ragged);
 }

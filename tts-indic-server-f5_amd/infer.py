@@ -427,14 +427,24 @@ def _sample(model_obj, voice, units, knobs, generator=None):
 def _chunk_waves(groups, vocoder, mel_spec_type, target_rms):
     """Vocoder part of infer_batch_process's tail (F/infer/utils_infer.py:468-481) for the chunks of several requests: `groups` =
     [(mels, ref_frames, rms)] -> per group ([wave_i], [spec_i]) as numpy, the reference frames stripped and the rms restored per chunk.
-    Vocos objects that offer `decode_ragged` vocode every chunk of every group in ONE call (each item equals its own `decode`, bit for
-    bit); any other vocoder (BigVGAN) is called chunk by chunk at batch 1 like the reference."""
+    Vocoder objects that offer `decode_ragged` vocode every chunk of every group in ONE call (each item equals its own `decode` /
+    `vocoder(spec)`, bit for bit): F5HipVocos for "vocos", and for "bigvgan" an object whose `decode_ragged` is the BigVGAN one, which it
+    says with `ragged_mel_spec_type == "bigvgan"` (F5HipBigVGAN; a Vocos-style `decode_ragged` returns hop (T - 1) samples per item, so
+    the method's name alone does not make it usable here).  Any other vocoder (the reference's modules) is called chunk by chunk at batch 1
+    like the reference, and so is a single BigVGAN chunk."""
     if mel_spec_type not in ("vocos", "bigvgan"):
         raise ValueError(mel_spec_type)
     specs = [[mel.to(torch.float32)[ref_frames:, :].t()[None] for mel in mels] for mels, ref_frames, _ in groups]   # [1, mel, T] (:468-470)
     flat = [spec for g in specs for spec in g]
-    if mel_spec_type == "vocos" and hasattr(vocoder, "decode_ragged") and flat:
-        raw = [w[None] for w in vocoder.decode_ragged([spec[0] for spec in flat])]
+    if mel_spec_type == "vocos":
+        ragged = hasattr(vocoder, "decode_ragged") and len(flat) > 0
+    else:
+        # A single chunk (a streamed request's head, a span boundary with one ticket) takes the plain forward: the ragged call runs the same
+        # kernels for it and adds the slab copy, the length tables and their upload, so at n = 1 it can only match or lose
+        ragged = hasattr(vocoder, "decode_ragged") and getattr(vocoder, "ragged_mel_spec_type", None) == "bigvgan" and len(flat) > 1
+    if ragged:
+        # shaped like `decode(spec)` [1, n] resp. `vocoder(spec)` [1, 1, n]
+        raw = [w[None] if mel_spec_type == "vocos" else w[None, None] for w in vocoder.decode_ragged([spec[0] for spec in flat])]
     else:
         raw = [vocoder.decode(spec) if mel_spec_type == "vocos" else vocoder(spec) for spec in flat]
     out, k = [], 0
@@ -487,7 +497,7 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     in the mixed GEMM mode last-bit differences grow to that mode's rounding-noise floor, 4.4e-4 rms after two Euler steps:
     `profiles/r03_attn_mode_tapdiff.txt`; either result is within the 1e-3 bound of the reference).  This is what the serving queue (`serve.MicroBatcher`) and the
     multi-voice front-end hand to the GPU: the chunks of all waiting requests are packed back to back in one library call, and with a
-    Vocos object that offers `decode_ragged` they are vocoded in one call too.
+    vocoder object that offers `decode_ragged` (F5HipVocos, F5HipBigVGAN) they are vocoded in one call too.
 
     `gen_text` is a string, chunked like `infer_process` does, or a list of chunk texts used as they are (a streamed request's first
     chunk and its remaining chunks ride in different batches: `infer_process_stream`, `serve.TTSManager.synthesize_stream`).  Unseeded,

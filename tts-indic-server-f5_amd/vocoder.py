@@ -83,8 +83,11 @@ class F5HipVocos:
 
 class F5HipBigVGAN:
     """BigVGAN v2 generator object: stands where the reference passes `vocoder` for mel_spec_type="bigvgan"
-    (F/infer/utils_infer.py:116-129,474): `vocoder(mel[b, 100, T]) -> wave[b, 1, 256 T]`.  state_dict keys are the generator's
+    (F/infer/utils_infer.py:116-129,474): `vocoder(mel[b, 100, T]) -> wave[b, 1, 256 T]`, and `decode_ragged([mel_i [100, T_i]]) -> [wave_i]`
+    for chunks of different lengths in one library call.  state_dict keys are the generator's
     after `remove_weight_norm()`; weight-norm'ed checkpoints (`weight_g` / `weight_v`) are folded here the same way."""
+
+    ragged_mel_spec_type = "bigvgan"   # what `infer._chunk_waves` asks before it hands every chunk of a batch to `decode_ragged`
 
     def __init__(self, state_dict: dict, num_mels=100, upsample_rates=(4, 4, 2, 2, 2, 2), upsample_kernel_sizes=(8, 8, 4, 4, 4, 4),
                  upsample_initial_channel=1536, resblock_kernel_sizes=(3, 7, 11),
@@ -94,6 +97,7 @@ class F5HipBigVGAN:
             raise _lib.F5HipError("F5HipBigVGAN needs a HIP device (no CPU fallback)")
         torch.cuda.set_device(self.device)
         self.total_up = int(np.prod(upsample_rates))
+        self.num_mels = num_mels
         self._lib = _lib.lib()
         cfg = _lib.BigVGANConfig()
         cfg.num_mels, cfg.num_upsamples, cfg.upsample_initial_channel, cfg.gemm_planes = num_mels, len(upsample_rates), upsample_initial_channel, gemm_planes
@@ -142,3 +146,27 @@ class F5HipBigVGAN:
         _lib.check(self._lib.f5hip_bigvgan_forward(self._h, b, t, C.c_void_p(mel.data_ptr()), C.c_void_p(wave.data_ptr()),
                                                    _lib.current_stream_ptr()), "f5hip_bigvgan_forward")
         return wave
+
+    @torch.no_grad()
+    def decode_ragged(self, mels) -> list:
+        """`vocoder(mel)` of several mels of their own lengths in ONE library call (f5hip_bigvgan_forward_ragged): mels = [mel_i [C, T_i]] ->
+        [wave_i [total_up T_i]], each equal to `vocoder(mel_i[None]).reshape(-1)` bit for bit (every item has its own rows and bounds)."""
+        frames = [int(m.shape[-1]) for m in mels]
+        if not frames:
+            return []
+        if any(m.dim() != 2 or m.shape[0] != self.num_mels for m in mels) or min(frames) < 1:
+            raise _lib.F5HipError(f"decode_ragged: every mel must be [{self.num_mels}, T] with T >= 1")
+        mel = torch.zeros(len(mels), self.num_mels, max(frames), device=self.device, dtype=torch.float32)
+        for i, m in enumerate(mels):
+            mel[i, :, :frames[i]] = m
+        f = torch.tensor(frames, dtype=torch.int32)
+        if torch_ops.load():
+            try:
+                wave = torch_ops.ops().bigvgan_forward_ragged(int(self._h), mel, f, self.num_mels, self.total_up)
+            except RuntimeError as e:   # c10::Error from the operator's checks or the library
+                raise _lib.F5HipError(str(e)) from e
+        else:
+            wave = torch.empty(self.total_up * sum(frames), device=self.device, dtype=torch.float32)
+            _lib.check(self._lib.f5hip_bigvgan_forward_ragged(self._h, len(frames), C.c_void_p(f.data_ptr()), C.c_void_p(mel.data_ptr()),
+                                                              C.c_void_p(wave.data_ptr()), _lib.current_stream_ptr()), "f5hip_bigvgan_forward_ragged")
+        return list(wave.split([self.total_up * t for t in frames]))
