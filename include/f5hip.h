@@ -193,6 +193,14 @@ int f5hip_get_counter(const char* name, int64_t* value);
 int f5hip_op_gemm(int32_t M, int32_t N, int32_t K, const float* a_dev, const float* w_dev, const float* bias_dev, int32_t prec,
                   int32_t act, const float* mul_dev, const float* res_dev, const uint8_t* row_keep_host, float* out_dev,
                   uint16_t* out16_dev, int32_t w_copies, int32_t iters, double* avg_us, void* stream, int32_t bn);
+/* f5hip_op_gemm_rowmul: f5hip_op_gemm with the multiplier taken per ROW, out = ((A W^T + bias), rows with row_keep == 0 zeroed) *
+ *   mul[row_mod[r]] + res -- the gated residual projections of a mixed-grid sampler call, whose rows sit at different time points.
+ *   mul_dev points into a table fp32 [n_mod_rows][mod_ld] at a column offset (16-byte aligned; mod_ld >= N, mod_ld % 4 == 0): row r reads
+ *   mul_dev + row_mod_host[r] * mod_ld .. + N.  row_mod_host int32 [M] (host).  These kernels are the (no activation, residual, fp32
+ *   output) epilogue only: res_dev and out_dev are required.  Everything else as in f5hip_op_gemm. */
+int f5hip_op_gemm_rowmul(int32_t M, int32_t N, int32_t K, const float* a_dev, const float* w_dev, const float* bias_dev, int32_t prec,
+                         const float* mul_dev, const int32_t* row_mod_host, int32_t mod_ld, int32_t n_mod_rows, const float* res_dev,
+                         const uint8_t* row_keep_host, float* out_dev, void* stream, int32_t bn);
 /* f5hip_op_qkv: fused to_q | to_k | to_v projection with its epilogue: bias, rotary embedding on channels 0..63 (head 0, interleaved
  *   pairs) of q and k, q * log2(e) / 8 (the attention kernel's scores are base-2 exponents), V transposed (F/model/modules.py:409-426).  a_dev [M][D], w_dev [3 D][D], bias_dev [3 D], row_pos host
  *   int32 [M] (rotary position of every row, 0..4096); outputs fp16 (saturated): qk_dev [ceil128(M)][2 D], vt_dev [D][ceil128(M)] with the tokens of
@@ -220,6 +228,40 @@ int f5hip_op_joint_attention(int32_t n_seq, const int32_t* x_len, const int32_t*
  *   rms = 1: x-transformers RMSNorm y = x / max(|x|_2, 1e-12) * sqrt(D) * scale.  All fp32 [M][D] / [D]. */
 int f5hip_op_layernorm(int32_t M, int32_t D, const float* x_dev, const float* scale_dev, const float* shift_dev, float gain_off, float eps,
                        int32_t rms, float* out_dev, void* stream);
+/* f5hip_op_layernorm_planes: f5hip_op_layernorm (no RMSNorm) through the 16-bit outputs the GEMMs read: out_format 0 = split-bf16 planes
+ *   (hi = bf16(y), lo = bf16(y - hi)), 1 = one fp16 plane (saturated); out_dev fp32 [M][D] receives hi + lo, or the fp16 values.
+ *   row_mod_host NULL: scale_dev / shift_dev [D].  Else int32 [M] (host): row r takes its vectors from scale_dev / shift_dev +
+ *   row_mod_host[r] * mod_ld, two column offsets (16-byte aligned) into one table fp32 [n_mod_rows][mod_ld], mod_ld >= D, mod_ld % 4 == 0
+ *   -- the per-row AdaLN of a mixed-grid sampler call. */
+int f5hip_op_layernorm_planes(int32_t M, int32_t D, const float* x_dev, const float* scale_dev, const float* shift_dev,
+                              const int32_t* row_mod_host, int32_t mod_ld, int32_t n_mod_rows, float gain_off, float eps, int32_t out_format,
+                              float* out_dev, void* stream);
+/* f5hip_op_cfg_step: one launch of the sampler's CFG combine + ODE update, v = p_c + (p_c - p_u) cfg (v = p_c for a frame without an
+ *   unconditional row), on the caller's buffers.  U frames of mel channels; pred_dev fp32 [rows][128] the backbone output, urow_c_host /
+ *   urow_u_host int32 [U] (host) the conditional / unconditional row of every frame (urow_u -1: none).
+ *   method 0: xout = xbase + dt v (xout_dev == xbase_dev: the Euler step in place; distinct: the midpoint rule's half step, xbase
+ *   untouched); method 2: stage `stage` + 1 (stage 0..3) of the fixed-grid RK4 step (3/8 rule) in place on xbase_dev, stage slopes in
+ *   k1_dev / k2_dev / k3_dev fp32 [U][mel]; method -1: no step (final select only).
+ *   Strength: cfg, or cfg_frame_dev fp32 [U] per frame.  Step size: dt, or (frame_unit_host not NULL, with cfg_frame_dev) per unit --
+ *   frame_unit_host int32 [U], unit_dt_host fp32 [n_units] (host) -- and the frames of units >= n_act are left as they are.
+ *   xs_dev fp32 [rows][128]: the split-bf16 copy of x; it is split into planes, the launch writes split(x_next) at both rows of every
+ *   frame it steps, and the planes come back as hi + lo.
+ *   final_flags_host uint8 [U] (host) not NULL: then out_dev [U][mel] = flag ? cond_dev : xbase_dev, the sampler's final select. */
+int f5hip_op_cfg_step(int32_t method, int32_t stage, int32_t U, int32_t mel, int32_t rows, float* xout_dev, float* xbase_dev,
+                      const float* pred_dev, const int32_t* urow_c_host, const int32_t* urow_u_host, float cfg, const float* cfg_frame_dev,
+                      float dt, const int32_t* frame_unit_host, const float* unit_dt_host, int32_t n_units, int32_t n_act, float* k1_dev,
+                      float* k2_dev, float* k3_dev, float* xs_dev, const uint8_t* final_flags_host, const float* cond_dev, float* out_dev,
+                      void* stream);
+/* f5hip_op_row_tp: the time point of every row of a mixed-grid call, row_tp_host[r] = unit_tp_host[row_unit_host[r]] (all host int32;
+ *   R rows, n_units units), computed by the sampler's kernel. */
+int f5hip_op_row_tp(int32_t R, const int32_t* row_unit_host, int32_t n_units, const int32_t* unit_tp_host, int32_t* row_tp_host,
+                    void* stream);
+/* f5hip_op_time_table: the per-call time precompute of a finalized handle over n_t <= 256 time points t_host (host), and what it leaves in
+ *   the handle's tables: sinus_dev fp32 [n_t][256] = the sinusoid embedding as the time MLP reads it (split bf16, hi + lo); mod_dev fp32
+ *   [n_t][mod_cols] = the AdaLN modulation rows (DiT / MMDiT; mod_cols must be the model's row width, 6 dim per block + 2 dim for DiT)
+ *   or NULL; temb_dev fp32 [n_t][dim] = the time embeddings (UNetT) or NULL. */
+int f5hip_op_time_table(f5hip_dit* m, const float* t_host, int32_t n_t, float* sinus_dev, float* mod_dev, int32_t mod_cols, float* temb_dev,
+                        void* stream);
 /* f5hip_op_conv1d: one nn.Conv1d(c_in, c_out, k, dilation = dil, padding = dil (k - 1) / 2) + bias + res of the BigVGAN generator (its
  *   AMPBlock1 convolutions: k 3 / 7 / 11, dilation 1 / 3 / 5) over channel-last rows: `batch` sequences of pitch P rows (P % 128 == 0), T valid,
  *   zero padding at the sequence bounds.  x_dev fp32 [batch P][c_in], w_host [c_out][c_in][k] (the module's weight layout), bias_host [c_out]

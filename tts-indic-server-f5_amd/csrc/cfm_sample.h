@@ -172,28 +172,44 @@ static int upload_grid_tables(f5hip_dit* m, const UnitLayout& L, const TimePlan&
 // m->d_frame_cfg), or step sizes per unit in layout order (unit_dt; the frames of units >= n_act are left as they are).
 struct CfgStep { float cfg, dt; const int* frame_unit; const float* unit_dt; int n_act; };
 
+// The buffers one CFG stage works on: the handle's (cfg_bufs), or a unit op's own (f5hip_op_cfg_step)
+struct CfgBufs {
+    float *xstate, *k1, *k2, *k3;   // [U][mel]: the state (the Euler kernels' xbase), RK4's stage slopes
+    const float* pred;              // [rows][128]
+    const int *urow_c, *urow_u;     // [U]: the frame's conditional / unconditional row (-1: none)
+    const float* frame_cfg;         // [U] strengths per frame, or null: the scalar of CfgStep
+    Plane2 xs;                      // [rows][128]: the split-bf16 copy of x the input projection reads
+    int mel;
+};
+static CfgBufs cfg_bufs(const f5hip_dit* m) {
+    return {m->xstate, m->xmid, m->rk_k2, m->rk_k3, m->pred, m->d_urow_c, m->d_urow_u, m->d_frame_cfg, m->xs, m->cfg.mel_dim};
+}
+
 template <bool FRAME_CFG, bool UNIT_DT>
-static void launch_cfg(const f5hip_dit* m, int f0, bool rk4, int stage, float* xout, const CfgStep& c, hipStream_t st) {
-    const int mel = m->cfg.mel_dim;
+static void launch_cfg(const CfgBufs& b, int f0, bool rk4, int stage, float* xout, const CfgStep& c, hipStream_t st) {
     const float cfg = FRAME_CFG ? 0.0f : c.cfg, dt = UNIT_DT ? 0.0f : c.dt;
     if (rk4)
-        hipLaunchKernelGGL((cfg_rk4_stage_kernel<FRAME_CFG, UNIT_DT>), dim3(f0), dim3(128), 0, st, m->xstate, mel, f0, m->pred, 128, m->d_urow_c,
-                           m->d_urow_u, cfg, (const float*)m->d_frame_cfg, dt, stage + 1, m->xmid, m->rk_k2, m->rk_k3, m->xs.hi, m->xs.lo, 128,
-                           c.frame_unit, c.unit_dt, c.n_act);
+        hipLaunchKernelGGL((cfg_rk4_stage_kernel<FRAME_CFG, UNIT_DT>), dim3(f0), dim3(128), 0, st, b.xstate, b.mel, f0, b.pred, 128, b.urow_c, b.urow_u,
+                           cfg, b.frame_cfg, dt, stage + 1, b.k1, b.k2, b.k3, b.xs.hi, b.xs.lo, 128, c.frame_unit, c.unit_dt, c.n_act);
     else
-        hipLaunchKernelGGL((cfg_euler_kernel<FRAME_CFG, UNIT_DT>), dim3(f0), dim3(128), 0, st, xout, (const float*)m->xstate, mel, f0, m->pred, 128,
-                           m->d_urow_c, m->d_urow_u, cfg, (const float*)m->d_frame_cfg, dt, m->xs.hi, m->xs.lo, 128, c.frame_unit, c.unit_dt, c.n_act);
+        hipLaunchKernelGGL((cfg_euler_kernel<FRAME_CFG, UNIT_DT>), dim3(f0), dim3(128), 0, st, xout, (const float*)b.xstate, b.mel, f0, b.pred, 128,
+                           b.urow_c, b.urow_u, cfg, b.frame_cfg, dt, b.xs.hi, b.xs.lo, 128, c.frame_unit, c.unit_dt, c.n_act);
+}
+
+// One kernel instance per form of the step: <false> scalar strength, <true> per-frame strength, <true, true> per-unit dt.  rk4: stage
+// `stage` + 1 of 4 in place on b.xstate; else xout = b.xstate + dt v.
+static void launch_cfg_form(const CfgBufs& b, int f0, bool rk4, int stage, float* xout, const CfgStep& c, hipStream_t st) {
+    if (c.frame_unit) launch_cfg<true, true>(b, f0, rk4, stage, xout, c, st);
+    else if (b.frame_cfg) launch_cfg<true, false>(b, f0, rk4, stage, xout, c, st);
+    else launch_cfg<false, false>(b, f0, rk4, stage, xout, c, st);
 }
 
 // The CFG combine and ODE update after forward `stage` of a step: Euler x += dt v; midpoint's first stage the half step from xstate into
-// xmid (the caller passes dt / 2), its second the full step; RK4 stage `stage` + 1 of 4.  One kernel instance per form of the step:
-// <false> scalar strength, <true> per-frame strength, <true, true> per-unit dt.
+// xmid (the caller passes dt / 2), its second the full step; RK4 stage `stage` + 1 of 4.
 static int cfg_stage(f5hip_dit* m, int method, int stage, int f0, const CfgStep& c, hipStream_t st) {
     float* xout = method == 1 && stage == 0 ? m->xmid : m->xstate;
     prof_begin(PROF_OTHER, st);
-    if (c.frame_unit) launch_cfg<true, true>(m, f0, method == 2, stage, xout, c, st);
-    else if (m->d_frame_cfg) launch_cfg<true, false>(m, f0, method == 2, stage, xout, c, st);
-    else launch_cfg<false, false>(m, f0, method == 2, stage, xout, c, st);
+    launch_cfg_form(cfg_bufs(m), f0, method == 2, stage, xout, c, st);
     prof_end(PROF_OTHER, st);
     CKL("cfg stage");
     return 0;

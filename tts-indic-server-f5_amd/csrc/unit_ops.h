@@ -14,6 +14,13 @@ struct OpBufs {
     }
 };
 
+// n elements of T, every byte `pad` (0x00: zeros; 0xff: NaN in fp32, bf16 and fp16)
+template <typename T> static T* op_filled(OpBufs& b, size_t n, int pad, hipStream_t st) {
+    T* p = b.get<T>(n);
+    if (p) (void)hipMemsetAsync(p, pad, n * sizeof(T), st);
+    return p;
+}
+
 // device fp32 [R][C] -> operand planes [R_pad][C] (prec 3: one fp16 plane; 2: split bf16; 1: bf16 hi only is read)
 static void op_pack_planes(const float* src, int R, int C, int R_pad, __bf16* hi, __bf16* lo, bool f16, hipStream_t st) {
     hipLaunchKernelGGL(pack_weight_kernel, dim3(R_pad), dim3(256), 0, st, src, R, C, C, hi, f16 ? (__bf16*)nullptr : lo, C);
@@ -111,9 +118,12 @@ static int gemm6_stamp_report(OpBufs& b, int M, int N, int K, hipStream_t st, La
     return 0;
 }
 
-extern "C" int f5hip_op_gemm(int32_t M, int32_t N, int32_t K, const float* a_dev, const float* w_dev, const float* bias_dev, int32_t prec,
-                             int32_t act, const float* mul_dev, const float* res_dev, const uint8_t* row_keep_host, float* out_dev,
-                             uint16_t* out16_dev, int32_t w_copies, int32_t iters, double* avg_us, void* stream, int32_t bn) {
+// f5hip_op_gemm and f5hip_op_gemm_rowmul: row_mod_host null = EPI_GENERIC with the multiplier vector mul_dev [N] (or none); else
+// EPI_GENERIC_ROWMUL, row r multiplied by mul_dev + row_mod_host[r] * mod_ld
+static int op_gemm_run(int32_t M, int32_t N, int32_t K, const float* a_dev, const float* w_dev, const float* bias_dev, int32_t prec, int32_t act,
+                       const float* mul_dev, const int32_t* row_mod_host, int32_t mod_ld, const float* res_dev, const uint8_t* row_keep_host,
+                       float* out_dev, uint16_t* out16_dev, int32_t w_copies, int32_t iters, double* avg_us, void* stream, int32_t bn) {
+    const int epi = row_mod_host ? EPI_GENERIC_ROWMUL : EPI_GENERIC;
     if (M <= 0 || N <= 0 || K <= 0 || K % 32 || N % 4 || !a_dev || !w_dev || prec < 1 || prec > 3 || (!out_dev && !out16_dev))
         return fail(-1, "op_gemm: bad argument (need K %% 32 == 0, N %% 4 == 0, prec 1..3)");
     if (bn == 0) bn = 128;
@@ -127,7 +137,7 @@ extern "C" int f5hip_op_gemm(int32_t M, int32_t N, int32_t K, const float* a_dev
     Plane2 A;
     A.hi = b.get<__bf16>((size_t)M_pad * K); A.lo = b.get<__bf16>((size_t)M_pad * K);
     float* bias = b.get<float>(N_pad);
-    int* keep = nullptr;
+    int *keep = nullptr, *row_mod = nullptr;
     if (!A.hi || !A.lo || !bias) return fail(-5, "op_gemm: hipMalloc");
     std::vector<PackedW> Ws(w_copies);
     for (auto& W : Ws) {
@@ -147,21 +157,28 @@ extern "C" int f5hip_op_gemm(int32_t M, int32_t N, int32_t K, const float* a_dev
         for (int i = 0; i < M; i++) hk[i] = row_keep_host[i];
         if (!keep || upload_sync(st, keep, hk) != hipSuccess) return fail(-6, "op_gemm: row_keep upload");
     }
+    if (row_mod_host) {   // (the padding rows name modulation row 0; no kernel reads a multiplier for them)
+        row_mod = b.get<int>(M_pad);
+        std::vector<int> hm(M_pad, 0);
+        std::copy(row_mod_host, row_mod_host + M, hm.begin());
+        if (!row_mod || upload_sync(st, row_mod, hm) != hipSuccess) return fail(-6, "op_gemm: row_mod upload");
+    }
     auto args_for = [&](const PackedW& W) {
         GemmArgs g = gemm_base(A, K, W, M);
         g.act = act; g.mul = mul_dev; g.res = res_dev; g.ldres = N; g.row_keep = keep;
+        if (row_mod) { g.row_mod = row_mod; g.mod_ld = mod_ld; }
         if (out16_dev) { g.out_hi = (__bf16*)out16_dev; g.ldob = N; g.f16_out = 1; }
         else { g.out_f32 = out_dev; g.ldo = N; }
         return g;
     };
     {
         GemmArgs g = args_for(Ws[0]);
-        CK(run_gemm_n(prec, M_pad, g, Ws[0], EPI_GENERIC, false, bn, st));
+        CK(run_gemm_n(prec, M_pad, g, Ws[0], epi, false, bn, st));
     }
     auto stamped = [&](unsigned long long* d, int rep) {   // the diagnostics' launches cycle through the weight copies too
         GemmArgs g = args_for(Ws[rep % w_copies]);
         g.stamps = d;
-        return run_gemm_n(prec, M_pad, g, Ws[rep % w_copies], EPI_GENERIC, false, bn, st);
+        return run_gemm_n(prec, M_pad, g, Ws[rep % w_copies], epi, false, bn, st);
     };
     if (getenv("F5HIP_GEMM5_STAMPS")) CK(gemm5_stamp_report(b, M, N, K, st, stamped));
     if (getenv("F5HIP_GEMM6_STAMPS")) CK(gemm6_stamp_report(b, M, N, K, st, stamped));
@@ -173,11 +190,31 @@ extern "C" int f5hip_op_gemm(int32_t M, int32_t N, int32_t K, const float* a_dev
             const PackedW& W = Ws[i % w_copies];
             GemmArgs g = args_for(W);
             if (!out16_dev) { g.out_f32 = scratch; if (res_dev) g.res = scratch; }
-            return run_gemm_n(prec, M_pad, g, W, EPI_GENERIC, false, bn, st);
+            return run_gemm_n(prec, M_pad, g, W, epi, false, bn, st);
         }));
     }
     if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_gemm: %s", hipGetErrorString(hipGetLastError()));
     return 0;
+}
+
+extern "C" int f5hip_op_gemm(int32_t M, int32_t N, int32_t K, const float* a_dev, const float* w_dev, const float* bias_dev, int32_t prec,
+                             int32_t act, const float* mul_dev, const float* res_dev, const uint8_t* row_keep_host, float* out_dev,
+                             uint16_t* out16_dev, int32_t w_copies, int32_t iters, double* avg_us, void* stream, int32_t bn) {
+    return op_gemm_run(M, N, K, a_dev, w_dev, bias_dev, prec, act, mul_dev, nullptr, 0, res_dev, row_keep_host, out_dev, out16_dev, w_copies, iters,
+                       avg_us, stream, bn);
+}
+
+// The gated residual projection of a mixed-grid call, out = ((A W^T + bias), rows with row_keep == 0 zeroed) * mul[row_mod[r]] + res: the
+// EPI_GENERIC_ROWMUL kernels, which are the (no activation, residual, fp32 output) epilogue only
+extern "C" int f5hip_op_gemm_rowmul(int32_t M, int32_t N, int32_t K, const float* a_dev, const float* w_dev, const float* bias_dev, int32_t prec,
+                                    const float* mul_dev, const int32_t* row_mod_host, int32_t mod_ld, int32_t n_mod_rows, const float* res_dev,
+                                    const uint8_t* row_keep_host, float* out_dev, void* stream, int32_t bn) {
+    if (!mul_dev || !row_mod_host || !res_dev || !out_dev || mod_ld < N || mod_ld % 4 || n_mod_rows <= 0 || ((uintptr_t)mul_dev & 15))
+        return fail(-1, "op_gemm_rowmul: bad argument (need mul, row_mod, res and out; mod_ld >= N, mod_ld %% 4 == 0, mul 16-byte aligned)");
+    for (int i = 0; i < M; i++)
+        if (row_mod_host[i] < 0 || row_mod_host[i] >= n_mod_rows) return fail(-1, "op_gemm_rowmul: row_mod[%d] = %d out of range", i, row_mod_host[i]);
+    return op_gemm_run(M, N, K, a_dev, w_dev, bias_dev, prec, ACT_NONE, mul_dev, row_mod_host, mod_ld, res_dev, row_keep_host, out_dev, nullptr, 1, 0,
+                       nullptr, stream, bn);
 }
 
 // Fused QKV projection with its epilogue (bias, rotary on head 0, q / 8, V transposed): F/model/modules.py:409-426.
@@ -255,6 +292,38 @@ __global__ __launch_bounds__(256) void op_unpack_planes_kernel(const __bf16* hi,
         const size_t i = (size_t)row * D + c;
         out[(size_t)f * D + c] = f16 ? (float)reinterpret_cast<const _Float16*>(hi)[i] : (float)hi[i] + (lo ? (float)lo[i] : 0.0f);
     }
+}
+
+// f5hip_op_layernorm's modulation through the PLANE stores of ln_finish, what the GEMMs read: out_format 0 = split-bf16 planes (hi + lo),
+// 1 = one fp16 plane, read back as fp32.  row_mod_host null: the plain ln_kernel instance, scale / shift [D]; else the ROW_MOD instance: row r
+// takes scale_dev / shift_dev + row_mod_host[r] * mod_ld (two column offsets into one [n_mod_rows][mod_ld] table).  The planes start as NaN.
+extern "C" int f5hip_op_layernorm_planes(int32_t M, int32_t D, const float* x_dev, const float* scale_dev, const float* shift_dev,
+                                         const int32_t* row_mod_host, int32_t mod_ld, int32_t n_mod_rows, float gain_off, float eps,
+                                         int32_t out_format, float* out_dev, void* stream) {
+    if (M <= 0 || D <= 0 || D % 4 || !x_dev || !scale_dev || !shift_dev || !out_dev || out_format < 0 || out_format > 1)
+        return fail(-1, "op_layernorm_planes: bad argument");
+    if (row_mod_host) {
+        if (mod_ld < D || mod_ld % 4 || n_mod_rows <= 0 || (((uintptr_t)scale_dev | (uintptr_t)shift_dev) & 15))
+            return fail(-1, "op_layernorm_planes: need mod_ld >= D, mod_ld %% 4 == 0 and 16-byte aligned scale / shift");
+        for (int i = 0; i < M; i++)
+            if (row_mod_host[i] < 0 || row_mod_host[i] >= n_mod_rows) return fail(-1, "op_layernorm_planes: row_mod[%d] = %d out of range", i, row_mod_host[i]);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    OpBufs b;
+    const size_t n = (size_t)M * D;
+    __bf16* hi = op_filled<__bf16>(b, n, 0xff, st); __bf16* lo = op_filled<__bf16>(b, n, 0xff, st);
+    int* idx = b.get<int>(2 * (size_t)M);   // the rows in order (op_unpack_planes_kernel's frame_row) | row_mod
+    if (!hi || !lo || !idx) return fail(-5, "op_layernorm_planes: hipMalloc");
+    std::vector<int> h(2 * (size_t)M, 0);
+    for (int i = 0; i < M; i++) { h[i] = i; if (row_mod_host) h[M + i] = row_mod_host[i]; }
+    if (upload_sync(st, idx, h) != hipSuccess) return fail(-6, "op_layernorm_planes: upload");
+    LnArgs ln = ln_args(x_dev, D, M, D, scale_dev, shift_dev, gain_off, eps);
+    ln.out_hi = hi; ln.out_lo = out_format == 0 ? lo : nullptr; ln.ldo = D; ln.f16_out = out_format == 1;
+    if (row_mod_host) { ln.row_mod = idx + M; ln.mod_ld = mod_ld; }
+    CK(run_ln(ln, st, row_mod_host != nullptr));
+    hipLaunchKernelGGL(op_unpack_planes_kernel, dim3(M), dim3(256), 0, st, hi, ln.out_lo, ln.f16_out, D, idx, out_dev);
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_layernorm_planes: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 // One (pseudo-)sequence of the attention unit ops: query rows row0 .. + len (frames frame0 .. + len of the caller's q / k / v / out) over the
@@ -524,13 +593,6 @@ static int op_layout(OpBufs& b, int n_seq, const int32_t* seq_len, int lead, OpL
     return 0;
 }
 
-// n elements of T, every byte `pad` (0x00: zeros; 0xff: NaN in fp32, bf16 and fp16)
-template <typename T> static T* op_filled(OpBufs& b, size_t n, int pad, hipStream_t st) {
-    T* p = b.get<T>(n);
-    if (p) (void)hipMemsetAsync(p, pad, n * sizeof(T), st);
-    return p;
-}
-
 // ConvPositionEmbedding of the backbone (run_conv_pos_embed, weights packed by pack_conv_pos): out = h0 + Mish(conv2(Mish(conv1(h0)))) over
 // n_seq sequences of seq_len frames, x_dev fp32 [frames][D] (packed).  Weights in nn.Conv1d layout w [D][D / 16][31], bias [D] (host).
 // lead = 1: the UNetT layout (a time-token row heads every sequence).  impl 5 = conv5.h (prec 2, lead 0), 0 = gemm.h; prec 2 = split bf16,
@@ -616,4 +678,108 @@ extern "C" int f5hip_op_convnext_block(int32_t n_seq, const int32_t* seq_len, in
     for (float* p : {tb.dw_w, tb.dw_b, tb.ln_w, tb.ln_b, tb.gamma, tb.beta}) dev_free(p);
     free_packed(tb.pw1); free_packed(tb.pw2);
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- ODE step and time-table unit ops
+// One launch of the sampler's CFG combine + ODE update (launch_cfg_form, the function cfg_stage calls) on the caller's buffers, plus (final_flags_host
+// not null) final_select_kernel.  U frames of `mel` channels; pred_dev and xs_dev fp32 [rows][128]; urow_c / urow_u host int32 [U] (urow_u -1: the
+// frame has no unconditional row).  method 0: the Euler kernels, xout = xbase + dt v (xout == xbase: in place; else the midpoint rule's half
+// step, xbase untouched); 2: RK4 stage `stage` + 1 of 4 in place on xbase (xout must be xbase or null), k1 / k2 / k3 [U][mel]; -1: no step.
+// The form: cfg_frame_dev null = scalar cfg; else per-frame strengths [U]; frame_unit_host + unit_dt_host [n_units] (with cfg_frame_dev) =
+// per-unit step sizes, frames of units >= n_act left alone.  xs_dev is split into the bf16 planes the kernels write, and read back as hi + lo.
+// Final select: out_dev [U][mel] = final_flags_host[u] ? cond_dev : xbase (after the step).
+extern "C" int f5hip_op_cfg_step(int32_t method, int32_t stage, int32_t U, int32_t mel, int32_t rows, float* xout_dev, float* xbase_dev,
+                                 const float* pred_dev, const int32_t* urow_c_host, const int32_t* urow_u_host, float cfg, const float* cfg_frame_dev,
+                                 float dt, const int32_t* frame_unit_host, const float* unit_dt_host, int32_t n_units, int32_t n_act, float* k1_dev,
+                                 float* k2_dev, float* k3_dev, float* xs_dev, const uint8_t* final_flags_host, const float* cond_dev, float* out_dev,
+                                 void* stream) {
+    const bool step = method >= 0, rk4 = method == 2, unit_dt = frame_unit_host != nullptr;
+    if (U <= 0 || mel <= 0 || mel > 128 || !xbase_dev || (method != -1 && method != 0 && method != 2))
+        return fail(-1, "op_cfg_step: bad argument (method -1, 0 or 2; mel <= 128)");
+    if (step && (rows <= 0 || !pred_dev || !urow_c_host || !urow_u_host || !xs_dev || (rk4 ? stage < 0 || stage > 3 || !k1_dev || !k2_dev || !k3_dev ||
+                 (xout_dev && xout_dev != xbase_dev) : !xout_dev)))
+        return fail(-1, "op_cfg_step: missing buffer of the step (rk4: stage 0..3, k1..k3, in place)");
+    if (unit_dt && (!unit_dt_host || !cfg_frame_dev || n_units <= 0 || n_act < 0 || n_act > n_units))
+        return fail(-1, "op_cfg_step: the per-unit form needs unit_dt, cfg_frame and 0 <= n_act <= n_units");
+    if (final_flags_host && (!cond_dev || !out_dev)) return fail(-1, "op_cfg_step: the final select needs cond and out");
+    hipStream_t st = (hipStream_t)stream;
+    OpBufs b;
+    if (step) {
+        for (int u = 0; u < U; u++)
+            if (urow_c_host[u] < 0 || urow_c_host[u] >= rows || urow_u_host[u] < -1 || urow_u_host[u] >= rows ||
+                (unit_dt && (frame_unit_host[u] < 0 || frame_unit_host[u] >= n_units)))
+                return fail(-1, "op_cfg_step: frame %d: row or unit out of range", u);
+        const size_t n = (size_t)rows * 128;
+        Plane2 xs;
+        xs.hi = b.get<__bf16>(n); xs.lo = b.get<__bf16>(n);
+        int* meta = b.get<int>((size_t)3 * U);
+        float* udt = unit_dt ? b.get<float>(n_units) : nullptr;
+        if (!xs.hi || !xs.lo || !meta || (unit_dt && !udt)) return fail(-5, "op_cfg_step: hipMalloc");
+        std::vector<int> hm((size_t)3 * U, 0);
+        for (int u = 0; u < U; u++) { hm[u] = urow_c_host[u]; hm[U + u] = urow_u_host[u]; if (unit_dt) hm[2 * (size_t)U + u] = frame_unit_host[u]; }
+        if (upload_sync(st, meta, hm) != hipSuccess) return fail(-6, "op_cfg_step: upload");
+        if (unit_dt && (hipMemcpyAsync(udt, unit_dt_host, sizeof(float) * n_units, hipMemcpyHostToDevice, st) != hipSuccess ||
+                        hipStreamSynchronize(st) != hipSuccess))
+            return fail(-6, "op_cfg_step: unit_dt upload");
+        hipLaunchKernelGGL(split_rows_kernel, dim3(rows), dim3(256), 0, st, (const float*)xs_dev, 128, 128, rows, (const int*)nullptr, xs.hi, xs.lo, 128, 0);
+        CKL("op_cfg_step split");
+        const CfgBufs cb{xbase_dev, k1_dev, k2_dev, k3_dev, pred_dev, meta, meta + U, cfg_frame_dev, xs, mel};
+        const CfgStep c{cfg, dt, unit_dt ? meta + 2 * (size_t)U : nullptr, udt, n_act};
+        launch_cfg_form(cb, U, rk4, stage, xout_dev, c, st);
+        CKL("op_cfg_step");
+        hipLaunchKernelGGL(op_planes_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, xs.hi, xs.lo, 0, n, xs_dev);
+        CKL("op_cfg_step planes");
+    }
+    if (final_flags_host) {
+        int* flags = b.get<int>(U);
+        std::vector<int> hf(final_flags_host, final_flags_host + U);
+        if (!flags || upload_sync(st, flags, hf) != hipSuccess) return fail(-6, "op_cfg_step: flag upload");
+        hipLaunchKernelGGL(final_select_kernel, dim3(U), dim3(128), 0, st, (const float*)xbase_dev, cond_dev, (const int*)flags, mel, U, out_dev);
+        CKL("op_cfg_step final_select");
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_cfg_step: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+// row_tp_kernel of a mixed-grid call: row_tp_host[r] = unit_tp_host[row_unit_host[r]] for R rows of n_units units (all host int32)
+extern "C" int f5hip_op_row_tp(int32_t R, const int32_t* row_unit_host, int32_t n_units, const int32_t* unit_tp_host, int32_t* row_tp_host, void* stream) {
+    if (R <= 0 || n_units <= 0 || !row_unit_host || !unit_tp_host || !row_tp_host) return fail(-1, "op_row_tp: bad argument");
+    for (int r = 0; r < R; r++)
+        if (row_unit_host[r] < 0 || row_unit_host[r] >= n_units) return fail(-1, "op_row_tp: row_unit[%d] = %d out of range", r, row_unit_host[r]);
+    hipStream_t st = (hipStream_t)stream;
+    OpBufs b;
+    int* d = b.get<int>((size_t)2 * R + n_units);   // row_unit | row_tp | unit_tp
+    if (!d) return fail(-5, "op_row_tp: hipMalloc");
+    std::vector<int> h((size_t)2 * R + n_units, -1);
+    std::copy(row_unit_host, row_unit_host + R, h.begin());
+    std::copy(unit_tp_host, unit_tp_host + n_units, h.begin() + 2 * (size_t)R);
+    if (upload_sync(st, d, h) != hipSuccess) return fail(-6, "op_row_tp: upload");
+    hipLaunchKernelGGL(row_tp_kernel, dim3((R + 255) / 256), dim3(256), 0, st, (const int*)d, (const int*)(d + 2 * (size_t)R), R, d + R);
+    CKL("op_row_tp");
+    if (hipMemcpyAsync(row_tp_host, d + R, sizeof(int) * R, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(-7, "op_row_tp: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+// precompute_time of a finalized handle over n_t time points (t_host), and what it left in the handle's tables: sinus_dev fp32 [n_t][256] the
+// sinusoid table as uploaded (hi + lo), mod_dev fp32 [n_t][mod_cols] the AdaLN modulation rows (mod_cols must be the handle's row width; DiT
+// and MMDiT) or null, temb_dev fp32 [n_t][dim] the time embeddings (UNetT) or null
+extern "C" int f5hip_op_time_table(f5hip_dit* m, const float* t_host, int32_t n_t, float* sinus_dev, float* mod_dev, int32_t mod_cols,
+                                   float* temb_dev, void* stream) {
+    if (!m || !m->finalized) return fail(-1, "model not finalized");
+    if (!t_host || n_t <= 0 || !sinus_dev) return fail(-1, "op_time_table: bad argument");
+    if (mod_dev && (m->arch == 1 || mod_cols != m->n_adaln)) return fail(-1, "op_time_table: mod has %d columns in this model (got %d)", m->n_adaln, mod_cols);
+    if (temb_dev && m->arch != 1) return fail(-1, "op_time_table: only UNetT keeps the time embeddings");
+    hipStream_t st = (hipStream_t)stream;
+    CK(ensure_workspace(m, 128, 1, 1));
+    CK(precompute_time(m, t_host, n_t, st));
+    const size_t ns = (size_t)n_t * 256;
+    hipLaunchKernelGGL(op_planes_to_f32_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, m->sinp.hi, m->sinp.lo, 0, ns, sinus_dev);
+    CKL("op_time_table planes");
+    if (mod_dev && hipMemcpyAsync(mod_dev, m->mod, sizeof(float) * (size_t)n_t * m->n_adaln, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return fail(-6, "op_time_table: mod copy");
+    if (temb_dev && hipMemcpyAsync(temb_dev, m->temb, sizeof(float) * (size_t)n_t * m->cfg.dim, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return fail(-6, "op_time_table: temb copy");
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_time_table: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
 }

@@ -215,3 +215,103 @@ def convnext_block(x, params, *, seq_len, taps=False, pad_nan=False):
     _lib.check(_lib.lib().f5hip_op_convnext_block(len(sl), _p(sl), Td, _p(x), arr, int(pad_nan), _p(out), _p(tp.get("ln")), _p(tp.get("ty")),
                                                   _p(tp.get("grn")), _lib.current_stream_ptr()), "f5hip_op_convnext_block")
     return (out, tp) if taps else out
+
+
+def _i32(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
+
+
+def _col_ptr(table, col):
+    """Pointer to column `col` of row 0 of a contiguous fp32 device table."""
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2
+    return C.c_void_p(table.data_ptr() + 4 * int(col))
+
+
+def gemm_rowmul(a, w, bias, table, col, row_mod, res, *, prec=3, row_keep=None, bn=64):
+    """f5hip_op_gemm_rowmul: out = ((a @ w.T + bias), masked rows zeroed) * table[row_mod[r], col : col + N] + res, the per-row-multiplier
+    epilogue of the gated residual projections.  table fp32 [T, mod_ld] on the device, row_mod int [M]; bn as in gemm() (the model's
+    residual call sites pass 64).  Returns out fp32 [M, N]."""
+    dev = a.device
+    M, K = a.shape
+    N = w.shape[0]
+    a, w, bias, res = (_f32(t, dev) for t in (a, w, bias, res))
+    assert table.device == a.device and col + N <= table.shape[1]
+    out = torch.empty(M, N, device=dev, dtype=torch.float32)
+    keep = None if row_keep is None else np.ascontiguousarray(row_keep.cpu().numpy().astype(np.uint8))
+    rm = _i32(row_mod)
+    assert rm.shape == (M,)
+    _lib.check(_lib.lib().f5hip_op_gemm_rowmul(M, N, K, _p(a), _p(w), _p(bias), prec, _col_ptr(table, col), _p(rm), table.shape[1], table.shape[0],
+                                               _p(res), _p(keep), _p(out), _lib.current_stream_ptr(), bn), "f5hip_op_gemm_rowmul")
+    return out
+
+
+# output formats of layernorm_planes (what the kernel writes; the op returns it as fp32): split-bf16 planes, one fp16 plane
+LN_OUT_SPLIT, LN_OUT_F16 = 0, 1
+
+
+def layernorm_planes(x, scale, shift, *, out_format=LN_OUT_SPLIT, gain_off=1.0, eps=1e-6, table=None, row_mod=None):
+    """LayerNorm + modulation through the 16-bit plane outputs the GEMMs read, returned as fp32.  Plain: scale / shift fp32 [D].  Per row
+    (table fp32 [T, mod_ld] on the device, row_mod int [M]): scale / shift are COLUMN OFFSETS into the table and row r takes
+    table[row_mod[r], scale : scale + D] and table[row_mod[r], shift : shift + D]."""
+    dev = x.device
+    M, D = x.shape
+    x = _f32(x, dev)
+    out = torch.empty_like(x)
+    if table is None:
+        scale, shift = _f32(scale, dev), _f32(shift, dev)
+        ps, ph, rm, ld, nrow = _p(scale), _p(shift), None, 0, 0
+    else:
+        assert table.device == x.device and max(scale, shift) + D <= table.shape[1]
+        rm = _i32(row_mod)
+        assert rm.shape == (M,)
+        ps, ph, ld, nrow = _col_ptr(table, scale), _col_ptr(table, shift), table.shape[1], table.shape[0]
+    _lib.check(_lib.lib().f5hip_op_layernorm_planes(M, D, _p(x), ps, ph, _p(rm), ld, nrow, float(gain_off), float(eps), int(out_format), _p(out),
+                                                    _lib.current_stream_ptr()), "f5hip_op_layernorm_planes")
+    return out
+
+
+CFG_EULER, CFG_RK4, CFG_NO_STEP = 0, 2, -1
+
+
+def cfg_step(method, stage, xout, xbase, pred, urow_c, urow_u, xs, *, cfg=0.0, cfg_frame=None, dt=0.0, frame_unit=None, unit_dt=None, n_act=0,
+             k=(None, None, None), final_flags=None, cond=None):
+    """One launch of the sampler's CFG combine + ODE update IN PLACE on the caller's fp32 device tensors (include/f5hip.h f5hip_op_cfg_step):
+    xout / xbase / k [U, mel], pred / xs [rows, 128].  final_flags (uint8 [U]) + cond: also the final select, whose result is returned."""
+    U, mel = xbase.shape
+    for t in (xout, xbase, pred, xs, cfg_frame, cond) + tuple(k):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda)
+    uc, uu = (None if a is None else _i32(a) for a in (urow_c, urow_u))
+    fu = None if frame_unit is None else _i32(frame_unit)
+    ud = None if unit_dt is None else np.ascontiguousarray(np.asarray(unit_dt, dtype=np.float32))
+    ff = None if final_flags is None else np.ascontiguousarray(np.asarray(final_flags, dtype=np.uint8))
+    out = torch.empty_like(xbase) if ff is not None else None
+    _lib.check(_lib.lib().f5hip_op_cfg_step(int(method), int(stage), U, mel, 0 if pred is None else pred.shape[0], _p(xout), _p(xbase), _p(pred), _p(uc),
+                                            _p(uu), float(cfg), _p(cfg_frame), float(dt), _p(fu), _p(ud), 0 if ud is None else len(ud), int(n_act),
+                                            _p(k[0]), _p(k[1]), _p(k[2]), _p(xs), _p(ff), _p(cond), _p(out), _lib.current_stream_ptr()),
+               "f5hip_op_cfg_step")
+    return out
+
+
+def row_tp(row_unit, unit_tp):
+    """row_tp[r] = unit_tp[row_unit[r]] by the sampler's kernel; int arrays in, numpy int32 out."""
+    ru, ut = _i32(row_unit), _i32(unit_tp)
+    out = np.full(ru.shape, -1, dtype=np.int32)
+    _lib.check(_lib.lib().f5hip_op_row_tp(len(ru), _p(ru), len(ut), _p(ut), _p(out), _lib.current_stream_ptr()), "f5hip_op_row_tp")
+    return out
+
+
+def time_table(model, t):
+    """The time precompute of a model.F5HipModel over the time points t (at most 256): (sinus [n_t, 256] as the time MLP reads it, mod
+    [n_t, n_adaln] the AdaLN modulation rows or None (UNetT), temb [n_t, dim] the time embeddings (UNetT) or None)."""
+    from .model import MMDiTArch, UNetTArch
+    arch, dev = model.arch, model.device
+    th = np.ascontiguousarray(np.asarray(t, dtype=np.float32))
+    n_t, D = len(th), arch.dim
+    unett = isinstance(arch, UNetTArch)
+    cols = 0 if unett else (6 * arch.depth + 2) * D + ((6 * (arch.depth - 1) + 2) * D if isinstance(arch, MMDiTArch) else 0)
+    sinus = torch.empty(n_t, 256, device=dev, dtype=torch.float32)
+    mod = None if unett else torch.empty(n_t, cols, device=dev, dtype=torch.float32)
+    temb = torch.empty(n_t, D, device=dev, dtype=torch.float32) if unett else None
+    _lib.check(_lib.lib().f5hip_op_time_table(model._h, _p(th), n_t, _p(sinus), _p(mod), cols, _p(temb), _lib.current_stream_ptr()),
+               "f5hip_op_time_table")
+    return sinus, mod, temb
