@@ -22,6 +22,7 @@ import math
 import os
 import re
 import struct
+import types
 from dataclasses import dataclass
 
 import numpy as np
@@ -266,8 +267,7 @@ def infer_process_stream(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_
     both calls (`torch.manual_seed`), the pieces equal `infer_process`'s wave to the last bit.  With `seed`, both calls draw from the
     request's one generator (the remaining chunks after the first chunk's draws), so the pieces equal `infer_process(..., seed=seed)`."""
     audio, sr = ref_audio if isinstance(ref_audio, tuple) else load_wav(ref_audio)
-    chunks = request_chunks(ref_text, audio.shape[-1] / sr, gen_text)
-    voice, units = _plan_request((audio, sr), ref_text, chunks, target_rms, speed, fix_duration, device, text_to_tokens)
+    voice, units = _plan_request((audio, sr), ref_text, gen_text, target_rms, speed, fix_duration, device, text_to_tokens)
     knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
     gen = request_generator(seed)
     joiner = StreamJoiner(cross_fade_duration)
@@ -276,13 +276,8 @@ def infer_process_stream(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_
             continue
         mels = _sample(model_obj, voice, part, knobs, gen)
         (waves, _), = _chunk_waves([(mels, voice.ref_frames, voice.rms)], vocoder, mel_spec_type, target_rms)
-        for w in waves:
-            piece = joiner.push(w)
-            if len(piece):
-                yield piece.astype(np.float32)
-    piece = joiner.flush()
-    if len(piece):
-        yield piece.astype(np.float32)
+        yield from joiner.pieces(waves)
+    yield from joiner.pieces(flush=True)
 
 
 def _prepare_reference(audio, sr, rms_floor, device):
@@ -365,6 +360,18 @@ class StreamJoiner:
         held, self.held = self.held, None
         return held if held is not None else np.zeros(0, dtype=np.float32)
 
+    def pieces(self, waves=(), flush=False):
+        """What a stream hands on: the non-empty pieces that pushing `waves` one after the other releases -- with `flush`, the held rest behind
+        them -- each as float32."""
+        for wave in waves:
+            piece = self.push(wave)
+            if len(piece):
+                yield np.asarray(piece, dtype=np.float32)
+        if flush:
+            piece = self.flush()
+            if len(piece):
+                yield np.asarray(piece, dtype=np.float32)
+
 
 class PreparedVoice:
     """The per-voice part of `infer_process` done once: the reference wave after mono mix / rms gain / resampling
@@ -388,13 +395,15 @@ class PreparedVoice:
         return self.mel
 
 
-def _plan_request(ref_audio, ref_text, gen_text_batches, target_rms, speed, fix_duration, device, tokenizer):
+def _plan_request(ref_audio, ref_text, gen_text, target_rms, speed, fix_duration, device, tokenizer):
     """Host prologue of infer_batch_process for one request (F/infer/utils_infer.py:423-454): prepared reference wave, its rms,
-    the frame count the reference strips afterwards, and one sampling unit per text chunk."""
+    the frame count the reference strips afterwards, and one sampling unit per text chunk.  `gen_text`: a list of chunk texts used as
+    they are, or a string chunked like `infer_process` does (`request_chunks`)."""
     voice = ref_audio if isinstance(ref_audio, PreparedVoice) else PreparedVoice(ref_audio, target_rms, device)
+    chunks = list(gen_text) if isinstance(gen_text, (list, tuple)) else request_chunks(ref_text, voice.seconds, gen_text)
     if len(ref_text[-1].encode("utf-8")) == 1:
         ref_text = ref_text + " "
-    return voice, plan_units(ref_text, gen_text_batches, voice.ref_frames, speed, fix_duration, tokenizer)
+    return voice, plan_units(ref_text, chunks, voice.ref_frames, speed, fix_duration, tokenizer)
 
 
 def request_generator(seed):
@@ -405,23 +414,24 @@ def request_generator(seed):
     return torch.Generator().manual_seed(int(seed))
 
 
-def _seeded_kw(model_obj, gens):
-    """The `generators=` keyword of a `sample_units` call whose units carry generators (nothing when none does: unseeded calls are
-    today's calls).  Only model objects with `sample_units` take per-unit noise sources."""
-    if all(g is None for g in gens):
-        return {}
-    if not hasattr(model_obj, "sample_units"):
+def _sample_units(model_obj, cond, audios, units, steps, cfg_strength, sway_sampling_coef, generators):
+    """The mels [frames_i, mel] (reference frames included) of `units`: ONE `sample_units` call when the model object offers it (`cond`: the
+    prompts, one tensor for all units or one per unit; `generators`, one or None per unit, is handed on only when a unit has one), else the
+    reference's batch-1 `.sample()` unit by unit on the waves `audios`.  Each knob: one value or one per unit."""
+    if hasattr(model_obj, "sample_units"):
+        extra = dict(generators=list(generators)) if any(g is not None for g in generators) else {}
+        return model_obj.sample_units(cond, units, steps=steps, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, **extra)
+    if any(g is not None for g in generators):
         raise ValueError("a per-request seed needs a model object with sample_units (F5HipModel, ShardedSampler)")
-    return dict(generators=list(gens))
+    per_unit = [v if isinstance(v, list) else [v] * len(units) for v in (steps, cfg_strength, sway_sampling_coef)]
+    return [model_obj.sample(cond=audio, text=[tokens], duration=frames, steps=n, cfg_strength=cfg, sway_sampling_coef=sway)[0][0]
+            for audio, (tokens, frames), n, cfg, sway in zip(audios, units, *per_unit)]
 
 
 def _sample(model_obj, voice, units, knobs, generator=None):
-    """The mels [frames_i, mel] (reference frames included) of one request's units: one `sample_units` call when the model object offers
-    it, else the reference's batch-1 `.sample()` per unit.  `generator`: the request's own noise source (`request_generator`)."""
-    extra = _seeded_kw(model_obj, [generator] * len(units))
-    if hasattr(model_obj, "sample_units"):
-        return model_obj.sample_units(voice.cond(model_obj), units, **knobs, **extra)
-    return [model_obj.sample(cond=voice.audio, text=[tokens], duration=frames, **knobs)[0][0] for tokens, frames in units]
+    """`_sample_units` for one request's units: one shared prompt, one set of knobs.  `generator`: the request's own noise source
+    (`request_generator`)."""
+    return _sample_units(model_obj, voice.cond(model_obj), [voice.audio] * len(units), units, generators=[generator] * len(units), **knobs)
 
 
 def _chunk_waves(groups, vocoder, mel_spec_type, target_rms):
@@ -484,6 +494,26 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed")
 
 
+def plan_request(request, defaults, *, target_rms, fix_duration, device, tokenizer):
+    """One request tuple (ref_audio, ref_text, gen_text[, options]) of `infer_requests` / `SpanScheduler.admit`, planned: `opts` (the
+    options over `defaults`, unknown ones rejected), `voice` (prepared), `units` (one per chunk; the text is chunked unless it is a list
+    of chunk texts) and `generator`, the request's noise source (None: the global one).  A `generator` the request carries is drawn from
+    on a copy: `commit()` moves the caller's to where the copy got, once the caller knows that the request went through."""
+    ref_audio, ref_text, gen_text = request[:3]
+    opts = dict(defaults, **(request[3] if len(request) > 3 and request[3] else {}))
+    unknown = set(opts) - set(REQUEST_OPTIONS) - {"generator"}
+    if unknown:
+        raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
+    voice, units = _plan_request(ref_audio, ref_text, gen_text, target_rms, opts["speed"], fix_duration, device, tokenizer)
+    own = opts.get("generator")
+    gen = torch.Generator().set_state(own.get_state()) if own is not None else request_generator(opts["seed"])
+
+    def commit():
+        if own is not None:
+            own.set_state(gen.get_state())
+    return types.SimpleNamespace(voice=voice, units=units, opts=opts, generator=gen, commit=commit)
+
+
 def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, target_rms=target_rms,
                    cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                    sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, tokenizer=text_to_tokens,
@@ -518,32 +548,20 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     with a `per_unit_time_grids` model, and in sampler-call order otherwise."""
     defaults = dict(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None)
     plans, calls = [], {}   # calls: (nfe_step, sway) -> [unit ids, ...] of one sampler call each
-    flat_units, flat_cond, flat_audio, flat_cfg, flat_gen, flat_grid, commits = [], [], [], [], [], [], []
+    flat_units, flat_cond, flat_audio, flat_cfg, flat_gen, flat_grid = [], [], [], [], [], []
     for req in requests:
-        ref_audio, ref_text, gen_text = req[:3]
-        opts = dict(defaults, **(req[3] if len(req) > 3 and req[3] else {}))
-        unknown = set(opts) - set(REQUEST_OPTIONS) - {"generator"}
-        if unknown:
-            raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
-        voice = ref_audio if isinstance(ref_audio, PreparedVoice) else PreparedVoice(ref_audio, target_rms, device)
-        chunks = list(gen_text) if isinstance(gen_text, (list, tuple)) else request_chunks(ref_text, voice.seconds, gen_text)
-        voice, units = _plan_request(voice, ref_text, chunks, target_rms, opts["speed"], fix_duration, device, tokenizer)
-        gen = opts.get("generator")
-        if gen is not None:    # continue a sequence on a copy: the caller's generator moves only if the call succeeds
-            commits.append((gen, torch.Generator().set_state(gen.get_state())))
-            gen = commits[-1][1]
-        else:
-            gen = request_generator(opts["seed"])
+        plan = plan_request(req, defaults, target_rms=target_rms, fix_duration=fix_duration, device=device, tokenizer=tokenizer)
+        voice, units, opts = plan.voice, plan.units, plan.opts
         key = (int(opts["nfe_step"]), opts["sway_sampling_coef"])
         calls.setdefault(key, []).extend(range(len(flat_units), len(flat_units) + len(units)))
-        plans.append((voice, len(units)))
+        plans.append(plan)
         flat_units += units
         flat_cond += [voice.cond(model_obj)] * len(units)
         flat_audio += [voice.audio] * len(units)
         flat_cfg += [opts["cfg_strength"]] * len(units)
-        flat_gen += [gen] * len(units)
+        flat_gen += [plan.generator] * len(units)
         flat_grid += [key] * len(units)
-    if len(calls) > 1 and getattr(model_obj, "per_unit_time_grids", False) and hasattr(model_obj, "sample_units"):
+    if len(calls) > 1 and getattr(model_obj, "per_unit_time_grids", False):
         calls = {None: list(range(len(flat_units)))}   # one call for every grid
     mels = [None] * len(flat_units)
 
@@ -551,24 +569,16 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
         return vals[0] if all(v == vals[0] for v in vals) else vals
 
     for ids in calls.values():
-        steps = one_or_list([flat_grid[i][0] for i in ids])
-        sway = one_or_list([flat_grid[i][1] for i in ids])
-        cfg = one_or_list([flat_cfg[i] for i in ids])
-        knobs = dict(steps=steps, cfg_strength=cfg, sway_sampling_coef=sway)
-        extra = _seeded_kw(model_obj, [flat_gen[i] for i in ids])
-        if hasattr(model_obj, "sample_units"):
-            got = model_obj.sample_units([flat_cond[i] for i in ids], [flat_units[i] for i in ids], **knobs, **extra)
-        else:
-            got = [model_obj.sample(cond=flat_audio[i], text=[flat_units[i][0]], duration=flat_units[i][1], steps=steps,
-                                    cfg_strength=flat_cfg[i], sway_sampling_coef=sway)[0][0] for i in ids]
+        got = _sample_units(model_obj, [flat_cond[i] for i in ids], [flat_audio[i] for i in ids], [flat_units[i] for i in ids],
+                            one_or_list([flat_grid[i][0] for i in ids]), one_or_list([flat_cfg[i] for i in ids]),
+                            one_or_list([flat_grid[i][1] for i in ids]), [flat_gen[i] for i in ids])
         for i, mel in zip(ids, got):
             mels[i] = mel
-    for gen, copy in commits:
-        gen.set_state(copy.get_state())
     groups, k = [], 0
-    for voice, n in plans:
-        groups.append((mels[k:k + n], voice.ref_frames, voice.rms))
-        k += n
+    for plan in plans:
+        plan.commit()   # every sampler call went through: the caller's generator moves
+        groups.append((mels[k:k + len(plan.units)], plan.voice.ref_frames, plan.voice.rms))
+        k += len(plan.units)
     out = []
     for waves, specs in _chunk_waves(groups, vocoder, mel_spec_type, target_rms):
         if join:
@@ -642,22 +652,13 @@ class SpanScheduler:
         return bool(self.waiting or self.in_flight)
 
     def admit(self, request) -> SpanTicket:
-        ref_audio, ref_text, gen_text = request[:3]
-        opts = dict(self.defaults, **(request[3] if len(request) > 3 and request[3] else {}))
-        unknown = set(opts) - set(REQUEST_OPTIONS) - {"generator"}
-        if unknown:
-            raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
-        voice = ref_audio if isinstance(ref_audio, PreparedVoice) else PreparedVoice(ref_audio, self.target_rms, self.device)
-        chunks = list(gen_text) if isinstance(gen_text, (list, tuple)) else request_chunks(ref_text, voice.seconds, gen_text)
-        voice, units = _plan_request(voice, ref_text, chunks, self.target_rms, opts["speed"], self.fix_duration, self.device, self.tokenizer)
-        own = opts.get("generator")
-        # a generator that continues a sequence is drawn from on a copy: the caller's moves only when every chunk was planned
-        gen = torch.Generator().set_state(own.get_state()) if own is not None else request_generator(opts["seed"])
+        plan = plan_request(request, self.defaults, target_rms=self.target_rms, fix_duration=self.fix_duration, device=self.device,
+                            tokenizer=self.tokenizer)
+        voice, opts = plan.voice, plan.opts
         cond = voice.cond(self.model_obj)
         planned = [self.model_obj.plan_unit(cond, tokens, frames, steps=int(opts["nfe_step"]), cfg_strength=opts["cfg_strength"],
-                                            sway_sampling_coef=opts["sway_sampling_coef"], generator=gen) for tokens, frames in units]
-        if own is not None:
-            own.set_state(gen.get_state())
+                                            sway_sampling_coef=opts["sway_sampling_coef"], generator=plan.generator) for tokens, frames in plan.units]
+        plan.commit()   # every chunk was planned: the caller's generator moves
         ticket = SpanTicket(request, voice, planned)
         self.waiting.append(ticket)
         return ticket

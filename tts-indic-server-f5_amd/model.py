@@ -311,10 +311,11 @@ class F5HipModel:
             cond = torch.nn.utils.rnn.pad_sequence(mels, batch_first=True)
         else:
             cond = (self.cond_mel(audio) if audio.ndim == 2 else audio.to(self.device, torch.float32)).expand(b, -1, -1)
-        out, _ = self.sample(cond, [t for t, _ in units], frames, lens=lens, steps=steps, cfg_strength=cfg_strength,
+        p = self._plan_batch(cond, [t for t, _ in units], frames, lens=lens, steps=steps, cfg_strength=cfg_strength,
                              sway_sampling_coef=sway_sampling_coef, seed=seed, generators=generators, y0=y0)
-        # (sample() raises a duration to lens + 1 like the reference does, cfm.py:136: the rows of unit i are its FINAL duration)
-        return [out[i, :self._last_min_frames[i]] for i in range(b)]
+        out = self._sample_planned(p)
+        # (a duration is raised to lens + 1 like the reference does, cfm.py:136: the rows of unit i are its FINAL duration)
+        return [out[i, :p.durs[i]] for i in range(b)]
 
     @torch.no_grad()
     def sample(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None,
@@ -337,57 +338,63 @@ class F5HipModel:
         p = self._plan_batch(cond, text, duration, lens=lens, steps=steps, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
                              seed=seed, max_duration=max_duration, duplicate_test=duplicate_test, t_inter=t_inter, edit_mask=edit_mask, y0=y0,
                              padded_batch=padded_batch, generators=generators)
-        batch, nmax, cond, cond_mask, text, durs, lay, padded = p.batch, p.nmax, p.cond, p.cond_mask, p.text, p.durs, p.lay, p.padded
-        cfg_units, ys, steps_u, grids = p.cfg_units, p.ys, p.steps_u, p.grids
-        self._last_min_frames = durs
-        t = grids[0]
-        one_grid = all(g.shape == t.shape and torch.equal(g, t) for g in grids[1:])
-        steps = steps_u[0]
-
-        cond_packed = torch.cat([cond[i, :lay[i]] for i in range(batch)], dim=0).contiguous()
-        mask_packed = np.ascontiguousarray(
-            torch.cat([cond_mask[i, :lay[i]] for i in range(batch)]).numpy().astype(np.uint8))
-        y0_packed = torch.cat(ys, dim=0).contiguous()
-        out_packed = torch.empty_like(y0_packed)
-        text_np = _i32(text.numpy())
-        tg = np.ascontiguousarray(t.numpy().astype(np.float32))
-        d_np, kv_np = _i32(lay), _i32(durs)
-        # One call: the TORCH_LIBRARY operator (csrc/torch_ops.cpp) when it is loaded, else the same C entry point through ctypes.  `arg`: how a
-        # host array travels; `extra`: what the entry point takes between y0 and the output (the operator reads `steps` off the grid).
-        use_op = torch_ops.load()
-        arg = torch.from_numpy if use_op else _ptr
-        grid = [arg(tg)] if use_op else [arg(tg), steps]
-        if not one_grid:   # one grid (and strength) per item: f5hip_cfm_sample_grids
-            cfg_all = cfg_units if cfg_units is not None else np.full(batch, float(cfg_strength), dtype=np.float32)
-            steps_np, tgs = _i32(steps_u), np.ascontiguousarray(torch.cat(grids).numpy().astype(np.float32))
-            entry, extra = "cfm_sample_grids", [arg(steps_np), arg(tgs), arg(cfg_all)]
-        elif cfg_units is not None:   # one strength per item: f5hip_cfm_sample_units
-            entry, extra = "cfm_sample_units", grid + [arg(cfg_units)]
-        else:
-            entry, extra = "cfm_sample", grid + [float(cfg_strength)]
-        kv = arg(kv_np) if padded else None
-        if use_op:
-            try:
-                out_packed = getattr(torch_ops.ops(), entry)(int(self._h), arg(d_np), kv, cond_packed, arg(mask_packed), arg(text_np), y0_packed, *extra)
-            except RuntimeError as e:
-                raise _lib.F5HipError(str(e).split("\n")[0]) from None
-        else:
-            fn = getattr(self._lib, "f5hip_cfm_sample_masked" if entry == "cfm_sample" else "f5hip_" + entry)
-            _lib.check(fn(self._h, batch, arg(d_np), kv, _ptr(cond_packed), arg(mask_packed), arg(text_np), text_np.shape[1], _ptr(y0_packed),
-                          *extra, _ptr(out_packed), _lib.current_stream_ptr()), "f5hip_" + entry)
-        if all(n == nmax for n in lay):
-            out = out_packed.view(batch, nmax, self.num_channels)
-        else:
-            out = torch.zeros(batch, nmax, self.num_channels, device=self.device, dtype=torch.float32)
-            o = 0
-            for i in range(batch):
-                out[i, :lay[i]] = out_packed[o:o + lay[i]]
-                o += lay[i]
+        out = self._sample_planned(p)
         if no_ref_audio:   # cfm.py:157-158: the final overwrite then copies zeros
-            out = torch.where(cond_mask[..., None].to(self.device), torch.zeros_like(out), out)
+            out = torch.where(p.cond_mask[..., None].to(self.device), torch.zeros_like(out), out)
         if vocoder is not None:
             out = vocoder(out.permute(0, 2, 1))
         return out, None
+
+    def _sample_planned(self, p):
+        """The one whole-grid library call for a planned batch (`_plan_batch`): packs the items' rows back to back, picks the entry point
+        -- one grid and one strength: f5hip_cfm_sample_masked; one grid, a strength per item: f5hip_cfm_sample_units; a grid per item:
+        f5hip_cfm_sample_grids -- and returns the result as [b, nmax, mel], zero behind an item's laid-out rows."""
+        batch, nmax, lay = p.batch, p.nmax, p.lay
+        t = p.grids[0]
+        cond_packed = torch.cat([p.cond[i, :lay[i]] for i in range(batch)], dim=0).contiguous()
+        mask_packed = np.ascontiguousarray(
+            torch.cat([p.cond_mask[i, :lay[i]] for i in range(batch)]).numpy().astype(np.uint8))
+        y0_packed = torch.cat(p.ys, dim=0).contiguous()
+        tg = np.ascontiguousarray(t.numpy().astype(np.float32))
+        if not all(g.shape == t.shape and torch.equal(g, t) for g in p.grids[1:]):
+            cfg_all = p.cfg_units if p.cfg_units is not None else np.full(batch, float(p.cfg_strength), dtype=np.float32)
+            entry, tail = "cfm_sample_grids", [_i32(p.steps_u), np.ascontiguousarray(torch.cat(p.grids).numpy().astype(np.float32)), cfg_all]
+        elif p.cfg_units is not None:
+            entry, tail = "cfm_sample_units", [tg, p.cfg_units]
+        else:
+            entry, tail = "cfm_sample", [tg, float(p.cfg_strength)]
+        out_packed = self._call_sampler(entry, [_i32(lay), _i32(p.durs) if p.padded else None, mask_packed, _i32(p.text.numpy())],
+                                        cond_packed, y0_packed, tail)
+        if all(n == nmax for n in lay):
+            return out_packed.view(batch, nmax, self.num_channels)
+        out = torch.zeros(batch, nmax, self.num_channels, device=self.device, dtype=torch.float32)
+        o = 0
+        for i in range(batch):
+            out[i, :lay[i]] = out_packed[o:o + lay[i]]
+            o += lay[i]
+        return out
+
+    def _call_sampler(self, entry, host_arrays, cond, y0, tail):
+        """ONE sampler call, `entry` one of cfm_sample / cfm_sample_units / cfm_sample_grids / cfm_sample_span: the TORCH_LIBRARY operator
+        (csrc/torch_ops.cpp) when it is loaded, else the same C entry point through ctypes.  `host_arrays` = (dur, kv_len | None, cond_mask,
+        text [b, nt]) and the arrays in `tail` (what the entry takes behind y0; a scalar strength travels as it is) are numpy arrays on the
+        host; `cond` and `y0` are the packed device rows.  Returns the packed result, shaped like `y0`."""
+        use_op = torch_ops.load()
+        wrap = torch.from_numpy if use_op else _ptr
+        dur, kv, mask, text = [wrap(a) if isinstance(a, np.ndarray) else a for a in host_arrays]
+        rest = [wrap(a) if isinstance(a, np.ndarray) else a for a in tail]
+        if use_op:
+            try:
+                return getattr(torch_ops.ops(), entry)(int(self._h), dur, kv, cond, mask, text, y0, *rest)
+            except RuntimeError as e:
+                raise _lib.F5HipError(str(e).split("\n")[0]) from None
+        if entry in ("cfm_sample", "cfm_sample_units"):   # the one-grid C entries take `steps` behind the grid (the operator reads it off the grid)
+            rest.insert(1, tail[0].size - 1)
+        out = torch.empty_like(y0)
+        fn = getattr(self._lib, "f5hip_cfm_sample_masked" if entry == "cfm_sample" else "f5hip_" + entry)
+        _lib.check(fn(self._h, len(host_arrays[0]), dur, kv, _ptr(cond), mask, text, host_arrays[3].shape[1], _ptr(y0), *rest, _ptr(out),
+                      _lib.current_stream_ptr()), "f5hip_" + entry)
+        return out
 
     @torch.no_grad()
     def plan_unit(self, cond, tokens, frames, *, steps=32, cfg_strength=2.0, sway_sampling_coef=-1.0, generator=None, y0=None) -> SpanUnit:
@@ -395,9 +402,9 @@ class F5HipModel:
         its planned rows -- without running a step: conditioning, mask, text row and time grid come from the code `sample()` uses, and the
         noise is drawn here as `sample()` draws it (`y0` [dur, mel], else `generator`, else the global generator)."""
         text = tokens.reshape(1, -1) if isinstance(tokens, torch.Tensor) else [tokens]
-        p = self._plan_batch(cond, text, torch.tensor([int(frames)], dtype=torch.long), lens=None, steps=int(steps), cfg_strength=float(cfg_strength),
-                             sway_sampling_coef=sway_sampling_coef, seed=None, max_duration=4096, duplicate_test=False, t_inter=0.1, edit_mask=None,
-                             y0=None if y0 is None else [y0], padded_batch=False, generators=None if generator is None else [generator])
+        p = self._plan_batch(cond, text, torch.tensor([int(frames)], dtype=torch.long), steps=int(steps), cfg_strength=float(cfg_strength),
+                             sway_sampling_coef=sway_sampling_coef, y0=None if y0 is None else [y0],
+                             generators=None if generator is None else [generator])
         dur = p.durs[0]
         return SpanUnit(p.cond[0, :dur].contiguous(), np.ascontiguousarray(p.cond_mask[0, :dur].numpy().astype(np.uint8)), _i32(p.text.numpy()[0]),
                         np.ascontiguousarray(p.grids[0].numpy().astype(np.float32)), cfg_strength, p.ys[0].contiguous())
@@ -413,22 +420,10 @@ class F5HipModel:
         text_np = np.full((len(units), nt), -1, dtype=np.int32)
         for i, u in enumerate(units):
             text_np[i, :len(u.text)] = u.text
-        d_np, steps_np = _i32([u.dur for u in units]), _i32(take)
         cfg = np.ascontiguousarray(np.asarray([u.cfg_strength for u in units], dtype=np.float32))
         mask = np.ascontiguousarray(np.concatenate([u.cond_mask for u in units]))
-        cond = torch.cat([u.cond for u in units], dim=0)
-        y0 = torch.cat([u.state for u in units], dim=0)
-        if torch_ops.load():
-            f = torch.from_numpy
-            try:
-                out = torch_ops.ops().cfm_sample_span(int(self._h), f(d_np), None, cond, f(mask), f(text_np), y0, f(steps_np), f(tgs), f(cfg), f(last))
-            except RuntimeError as e:
-                raise _lib.F5HipError(str(e).split("\n")[0]) from None
-        else:
-            out = torch.empty_like(y0)
-            _lib.check(self._lib.f5hip_cfm_sample_span(self._h, len(units), _ptr(d_np), None, _ptr(cond), _ptr(mask), _ptr(text_np), nt, _ptr(y0),
-                                                       _ptr(steps_np), _ptr(tgs), _ptr(cfg), _ptr(last), _ptr(out), _lib.current_stream_ptr()),
-                       "f5hip_cfm_sample_span")
+        out = self._call_sampler("cfm_sample_span", [_i32([u.dur for u in units]), None, mask, text_np], torch.cat([u.cond for u in units], dim=0),
+                                 torch.cat([u.state for u in units], dim=0), [_i32(take), tgs, cfg, last])
         ended, o = [], 0
         for u, k, end in zip(units, take, last):
             u.state.copy_(out[o:o + u.dur])
@@ -437,8 +432,8 @@ class F5HipModel:
                 ended.append(u)
         return ended
 
-    def _plan_batch(self, cond, text, duration, *, lens, steps, cfg_strength, sway_sampling_coef, seed, max_duration, duplicate_test, t_inter,
-                    edit_mask, y0, padded_batch, generators):
+    def _plan_batch(self, cond, text, duration, *, steps, cfg_strength, sway_sampling_coef, lens=None, seed=None, max_duration=4096,
+                    duplicate_test=False, t_inter=0.1, edit_mask=None, y0=None, padded_batch=False, generators=None):
         """Everything `sample()` decides before its library call (cfm.py:103-146,181-198), per item: the padded conditioning and its mask, the
         text rows, the final durations and laid-out rows, the noise (drawn here, in item order) and the fp32 time grid.  The one place that
         builds them: `sample()` hands them to one whole call, `plan_unit()` keeps them for a unit that is advanced span by span."""
@@ -511,4 +506,4 @@ class F5HipModel:
                 cache[key] = time_grid(n_steps, sway, t_start)
             grids.append(cache[key])
         return types.SimpleNamespace(batch=batch, nmax=nmax, cond=cond, cond_mask=cond_mask, text=text, durs=durs, lay=lay, padded=padded,
-                                     cfg_units=cfg_units, ys=ys, steps_u=steps_u, grids=grids)
+                                     cfg_strength=cfg_strength, cfg_units=cfg_units, ys=ys, steps_u=steps_u, grids=grids)

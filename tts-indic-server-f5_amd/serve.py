@@ -99,35 +99,28 @@ class VoiceRegistry:
         return self.voices.get(name)
 
 
-class MicroBatcher:
-    """Collects concurrent synthesis requests into one sampler batch.
+class _QueueWorker:
+    """What the two batchers share: the queue of (request, future, on_start) items, one worker thread running the subclass's `_loop`,
+    and the shutdown protocol -- `close()` puts a mark (None) behind everything that was accepted, refuses later submits, waits for the
+    worker and fails whatever it left behind with RuntimeError("<class name> is closed").  A subclass sets what its loop needs before it
+    calls `__init__` here, which starts the thread."""
 
-    `submit((ref_audio, ref_text, gen_text))` returns a `concurrent.futures.Future`; a single worker thread takes the first waiting
-    request, keeps collecting for at most `max_wait_ms` or until `max_requests` are waiting, runs `run_batch(list_of_requests)` (one
-    `infer.infer_requests` call = one library call over all chunks of all requests) and resolves the futures in order.  One batch is in
-    flight at a time -- the library allows one call per handle -- and the next one forms while it runs, so under load the batch size
-    grows by itself.  A failing batch is retried request by request so one bad request cannot fail its neighbours -- unless the error
-    says the backend itself is gone (`no_retry`, e.g. a rank of a sharded job failed): then the whole batch fails at once.
-    `close()` resolves every request that is still queued with RuntimeError("MicroBatcher is closed"); nothing can be enqueued behind it.
-    A request whose future was cancelled while it waited (a streaming client that went away) is dropped when its batch forms, before
-    `run_batch`; `submit(request, on_start=fn)` calls `fn()` on the worker thread once the request's batch has formed and before it runs,
-    so anything submitted from `fn` rides in a later batch (a stream's remaining chunks behind its first chunk)."""
-
-    def __init__(self, run_batch: Callable[[list], list], max_requests: int = 16, max_wait_ms: float = 5.0):
-        self.run_batch, self.max_requests, self.max_wait = run_batch, int(max_requests), max_wait_ms / 1e3
+    def __init__(self, thread_name: str):
         self._q: queue.Queue = queue.Queue()
         self._closed = False
         self._gate = threading.Lock()             # orders submit() against close(): no item can land behind the shutdown mark
-        self.batch_sizes: list[int] = []          # observability: sizes of the batches run so far
-        self._thread = threading.Thread(target=self._loop, name="f5hip-microbatcher", daemon=True)
+        self._thread = threading.Thread(target=self._loop, name=thread_name, daemon=True)
         self._thread.start()
+
+    def _closed_error(self):
+        return RuntimeError(f"{type(self).__name__} is closed")
 
     def submit(self, request, on_start: Callable[[], None] | None = None) -> Future:
         f: Future = Future()
         with self._gate:
             if self._closed:
-                raise RuntimeError("MicroBatcher is closed")
-            self._q.put((request, f, on_start) if on_start is not None else (request, f))
+                raise self._closed_error()
+            self._q.put((request, f, on_start))
         return f
 
     def close(self, timeout: float = 30.0):
@@ -146,7 +139,27 @@ class MicroBatcher:
             except queue.Empty:
                 return
             if item is not None and item[1].set_running_or_notify_cancel():
-                item[1].set_exception(RuntimeError("MicroBatcher is closed"))
+                item[1].set_exception(self._closed_error())
+
+
+class MicroBatcher(_QueueWorker):
+    """Collects concurrent synthesis requests into one sampler batch.
+
+    `submit((ref_audio, ref_text, gen_text))` returns a `concurrent.futures.Future`; a single worker thread takes the first waiting
+    request, keeps collecting for at most `max_wait_ms` or until `max_requests` are waiting, runs `run_batch(list_of_requests)` (one
+    `infer.infer_requests` call = one library call over all chunks of all requests) and resolves the futures in order.  One batch is in
+    flight at a time -- the library allows one call per handle -- and the next one forms while it runs, so under load the batch size
+    grows by itself.  A failing batch is retried request by request so one bad request cannot fail its neighbours -- unless the error
+    says the backend itself is gone (`no_retry`, e.g. a rank of a sharded job failed): then the whole batch fails at once.
+    `close()` resolves every request that is still queued with RuntimeError("MicroBatcher is closed"); nothing can be enqueued behind it.
+    A request whose future was cancelled while it waited (a streaming client that went away) is dropped when its batch forms, before
+    `run_batch`; `submit(request, on_start=fn)` calls `fn()` on the worker thread once the request's batch has formed and before it runs,
+    so anything submitted from `fn` rides in a later batch (a stream's remaining chunks behind its first chunk)."""
+
+    def __init__(self, run_batch: Callable[[list], list], max_requests: int = 16, max_wait_ms: float = 5.0):
+        self.run_batch, self.max_requests, self.max_wait = run_batch, int(max_requests), max_wait_ms / 1e3
+        self.batch_sizes: list[int] = []          # observability: sizes of the batches run so far
+        super().__init__("f5hip-microbatcher")
 
     def _collect(self):
         first = self._q.get()
@@ -174,10 +187,10 @@ class MicroBatcher:
             if not batch:
                 continue
             self.batch_sizes.append(len(batch))
-            for item in batch:
-                if len(item) > 2:
+            for _, _, on_start in batch:
+                if on_start is not None:
                     try:
-                        item[2]()
+                        on_start()
                     except Exception:   # noqa: BLE001 -- a hook must not stop the worker; its owner sees the missing follow-up
                         pass
             try:
@@ -199,7 +212,7 @@ class MicroBatcher:
         self._fail_pending()
 
 
-class ContinuousBatcher:
+class ContinuousBatcher(_QueueWorker):
     """`MicroBatcher`'s interface over an `infer.SpanScheduler`: requests join the batch that is running at its next span boundary instead of
     waiting for it to end.
 
@@ -218,42 +231,12 @@ class ContinuousBatcher:
     def __init__(self, scheduler, lock=None):
         self.scheduler = scheduler
         self._lock = lock if lock is not None else threading.Lock()
-        self._q: queue.Queue = queue.Queue()
-        self._closed = False
-        self._gate = threading.Lock()
         self._futures: dict = {}                  # ticket -> future, admitted and unresolved (worker thread only)
-        self._thread = threading.Thread(target=self._loop, name="f5hip-continuous-batcher", daemon=True)
-        self._thread.start()
+        super().__init__("f5hip-continuous-batcher")
 
     @property
     def batch_sizes(self) -> list:
         return self.scheduler.span_units
-
-    def submit(self, request, on_start: Callable[[], None] | None = None) -> Future:
-        f: Future = Future()
-        with self._gate:
-            if self._closed:
-                raise RuntimeError("ContinuousBatcher is closed")
-            self._q.put((request, f, on_start))
-        return f
-
-    def close(self, timeout: float = 30.0):
-        with self._gate:
-            if self._closed:
-                return
-            self._closed = True
-            self._q.put(None)                     # the shutdown mark: everything in front of it is still served
-        self._thread.join(timeout=timeout)
-        self._fail_pending()                      # (only non-empty if the worker thread did not get there: join timed out)
-
-    def _fail_pending(self):
-        while True:
-            try:
-                item = self._q.get_nowait()
-            except queue.Empty:
-                return
-            if item is not None and item[1].set_running_or_notify_cancel():
-                item[1].set_exception(RuntimeError("ContinuousBatcher is closed"))
 
     @staticmethod
     def _resolve(future, result=None, error=None):
@@ -505,10 +488,7 @@ class TTSManager:
                     head_waves = head_f.result(timeout=self.request_timeout_s)
                 else:
                     head_waves = self._run_batch([self._request(voice, ref_text, head, opts)])[0]
-                for w in head_waves:
-                    piece = joiner.push(w)
-                    if len(piece):
-                        yield np.asarray(piece, dtype=np.float32)
+                yield from joiner.pieces(head_waves)
                 if tail:
                     if self.batcher is not None:
                         started.wait(timeout=self.request_timeout_s)
@@ -519,13 +499,8 @@ class TTSManager:
                         tail_waves = state["tail"].result(timeout=self.request_timeout_s)
                     else:
                         tail_waves = self._run_batch([self._request(voice, ref_text, tail, opts)])[0]
-                    for w in tail_waves:
-                        piece = joiner.push(w)
-                        if len(piece):
-                            yield np.asarray(piece, dtype=np.float32)
-                piece = joiner.flush()
-                if len(piece):
-                    yield np.asarray(piece, dtype=np.float32)
+                    yield from joiner.pieces(tail_waves)
+                yield from joiner.pieces(flush=True)
             finally:                              # normal end, error, or the consumer closed the stream
                 cancel()
 
@@ -585,8 +560,9 @@ class HTTPError(Exception):
         self.status_code, self.detail = status_code, detail
 
 
-def synthesize_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None, **options):
-    """`S/utils/tts_utils.py:38-65` with the same checks in the same order and the same messages; `options` go to `TTSManager.synthesize`."""
+def _checked_voice(registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None):
+    """The checks of `S/utils/tts_utils.py:38-65`, in its order and with its messages: (voice, ref_text), the voice's own transcript
+    when the request brings none."""
     voice = registry.get(ref_audio_name)
     if voice is not None and not ref_text:
         ref_text = voice.ref_text
@@ -596,21 +572,19 @@ def synthesize_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: st
         raise HTTPError(400, "Text to synthesize cannot be empty.")
     if not ref_text or not ref_text.strip():
         raise HTTPError(400, "Reference text cannot be empty.")
+    return voice, ref_text
+
+
+def synthesize_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None, **options):
+    """`S/utils/tts_utils.py:38-65` with the same checks in the same order and the same messages; `options` go to `TTSManager.synthesize`."""
+    voice, ref_text = _checked_voice(registry, text, ref_audio_name, ref_text)
     audio = tts_manager.synthesize(text, ref_audio_path=voice.audio_path, ref_text=ref_text, **options)
     return wav_bytes(audio)
 
 
 def stream_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None, **options):
     """`synthesize_speech`'s checks, then `TTSManager.synthesize_stream`: an iterator of float32 pieces."""
-    voice = registry.get(ref_audio_name)
-    if voice is not None and not ref_text:
-        ref_text = voice.ref_text
-    if voice is None:
-        raise HTTPError(400, "Invalid reference audio name.")
-    if not text.strip():
-        raise HTTPError(400, "Text to synthesize cannot be empty.")
-    if not ref_text or not ref_text.strip():
-        raise HTTPError(400, "Reference text cannot be empty.")
+    voice, ref_text = _checked_voice(registry, text, ref_audio_name, ref_text)
     return tts_manager.synthesize_stream(text, ref_audio_path=voice.audio_path, ref_text=ref_text, **options)
 
 
@@ -658,12 +632,17 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
 
     router = APIRouter(prefix="/v1", tags=["speech"])
 
-    def _run(text, name, ref_text, filename, req):
+    def _speech_options(text, req):
+        """What both speech routes check first: a loaded model (503), the sampler fields and a non-empty text (400)."""
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
         opts = _options(req, infer.REQUEST_OPTIONS)
         if not text.strip():
             raise HTTPException(status_code=400, detail="Text to synthesize cannot be empty.")
+        return opts
+
+    def _run(text, name, ref_text, filename, req):
+        opts = _speech_options(text, req)
         try:
             buf = synthesize_speech(tts_manager, registry, text=text, ref_audio_name=name, ref_text=ref_text, **opts)
         except HTTPError as e:
@@ -674,11 +653,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         """stream=true: the same checks as `_run`, then the first piece is synthesized BEFORE the response exists, so a bad request, an
         unloaded model or a failing first chunk still comes back as a status code.  The body is a streaming WAV (`wav_stream_header`)
         followed by int16 PCM pieces; a failure after the first bytes can only end the body early, and is logged."""
-        if not tts_manager.model:
-            raise HTTPException(status_code=503, detail="TTS model not loaded")
-        opts = _options(req, infer.REQUEST_OPTIONS)
-        if not text.strip():
-            raise HTTPException(status_code=400, detail="Text to synthesize cannot be empty.")
+        opts = _speech_options(text, req)
         try:
             pieces = stream_speech(tts_manager, registry, text=text, ref_audio_name=name, ref_text=ref_text, **opts)
             first = next(pieces, None)
@@ -794,6 +769,7 @@ class ShardedSampler:
     def sample_units(self, audio, units, **knobs):
         if self.failed:
             raise ShardedJobError(f"sharded backend is down: {self.failed}")
+        from .model import per_unit_cfg, per_unit_values, unit_duration
         torch = self.torch
         b = len(units)
         audios = list(audio) if isinstance(audio, (list, tuple)) else [audio] * b
@@ -809,23 +785,17 @@ class ShardedSampler:
         mels = [(self.local.cond_mel(a) if a.ndim == 2 else a)[0].to(torch.float32) for a in voices]
         knobs = dict(knobs)
         gens, y0 = knobs.pop("generators", None), knobs.pop("y0", None)
-        cfg = knobs.get("cfg_strength")
-        per_unit = None if isinstance(cfg, (int, float, np.integer, np.floating)) or cfg is None else [float(c) for c in cfg]
-        if per_unit is not None:
-            if len(per_unit) != b:
-                raise ValueError(f"cfg_strength: one value per unit ({b}), got {len(per_unit)}")
-            knobs["cfg_strength"] = None      # replaced per rank by its units' slice
+        cfg, per_unit = knobs.get("cfg_strength"), None
+        if cfg is not None and per_unit_cfg(cfg, b) is not None:
+            per_unit, knobs["cfg_strength"] = [float(c) for c in cfg], None      # replaced per rank by its units' slice
         grids = {}                            # per-unit time grids: sliced per rank like the strengths
         for name in ("steps", "sway_sampling_coef"):
-            v = knobs.get(name)
-            if isinstance(v, (list, tuple)):
-                if len(v) != b:
-                    raise ValueError(f"{name}: one value per unit ({b}), got {len(v)}")
+            v = per_unit_values(knobs.get(name), b, name)
+            if isinstance(v, list):
                 grids[name] = [None if x is None else (int(x) if name == "steps" else float(x)) for x in v]
                 knobs[name] = None
         noise = list(y0) if y0 is not None else [None] * b
         if gens is not None:
-            from .model import unit_duration
             mel_dim = mels[0].shape[1]
             for i, ((tokens, frames), g) in enumerate(zip(units, gens)):
                 if g is not None and noise[i] is None:
