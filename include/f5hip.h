@@ -372,7 +372,9 @@ int f5hip_bigvgan_forward_ragged(f5hip_bigvgan* v, int32_t n, const int32_t* fra
 /* ---------------------------------------------------------------- mel front-end ------------------------ */
 
 /* Replaces MelSpec.forward with mel_spec_type="vocos" (F/model/modules.py:75-101,130-143): wave_dev fp32
- * [batch][n_samples] -> mel_dev fp32 [batch][n_mels][1 + n_samples / hop] (log of clamp(mel, 1e-5)). */
+ * [batch][n_samples] -> mel_dev fp32 [batch][n_mels][1 + n_samples / hop] (log of clamp(mel, 1e-5)).
+ * Accepted: n_fft = 1024, 1 <= hop_length <= n_fft, 1 <= n_mels <= 256, sample_rate >= 2, n_samples > n_fft / 2 (the BigVGAN variant below:
+ * n_samples >= n_fft); anything else returns an error before a launch. */
 int f5hip_mel_spectrogram(int32_t batch, int32_t n_samples, const float* wave_dev, float* mel_dev, int32_t n_fft,
                           int32_t hop_length, int32_t n_mels, int32_t sample_rate, void* stream);
 

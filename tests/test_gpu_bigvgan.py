@@ -5,6 +5,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from mel_ref import bigvgan_mel_float64 as _mel_float64  # noqa: E402
 from oracle import bigvgan_oracle as B  # noqa: E402
 from tts_indic_server_f5_amd import synth  # noqa: E402
 
@@ -60,27 +61,13 @@ def test_bigvgan_full_config():
     assert mx < 1e-4
 
 
-def _mel_float64(wave, monkeypatch):
-    """The oracle's mel front-end in float64: its window takes torch's default dtype, and its Slaney filterbank (returned as fp32, the
-    values the device tables hold too) is widened to float64 before the product."""
-    slaney = B.librosa_slaney_mel
-    monkeypatch.setattr(B, "librosa_slaney_mel", lambda *a, **k: slaney(*a, **k).double())
-    old = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float64)
-    try:
-        return B.bigvgan_mel_spectrogram(wave.double())
-    finally:
-        torch.set_default_dtype(old)
-        monkeypatch.undo()
-
-
 # 1024: the shortest wave the host accepts (n_samples >= n_fft; 513 is below it); 256 x 94: an exact multiple of the hop;
 # 256 x 94 + 255: one sample short of the next multiple
 @pytest.mark.parametrize("b,nw", [(1, 120_000), (2, 24_000 + 77), (1, 1024), (2, 256 * 94), (1, 256 * 94 + 255)])
-def test_mel_spectrogram_bigvgan(b, nw, monkeypatch):
+def test_mel_spectrogram_bigvgan(b, nw):
     from tts_indic_server_f5_amd.mel import mel_spectrogram_bigvgan
     wave = torch.cat([synth.ref_audio(nw, seed=1234 + i) for i in range(b)], dim=0)
-    ref = _mel_float64(wave, monkeypatch)
+    ref = _mel_float64(wave)
     got = mel_spectrogram_bigvgan(wave.cuda())
     assert got.shape == ref.shape == (b, 100, nw // 256)
     mx, rms = _report(f"bigvgan-mel b{b} nw{nw}", got, ref)

@@ -7,6 +7,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from mel_ref import LOG_CLAMP, float64 as _float64  # noqa: E402
 from oracle import vocos_oracle as V  # noqa: E402
 from tts_indic_server_f5_amd import synth  # noqa: E402
 
@@ -15,16 +16,6 @@ def _report(tag, got, ref):
     d = got.float().cpu() - ref.float().cpu()
     print(f"[parity] {tag}: rms_err {d.pow(2).mean().sqrt():.3e} max_err {d.abs().max():.3e} ref_rms {ref.float().pow(2).mean().sqrt():.3e}")
     return d.abs().max().item(), d.pow(2).mean().sqrt().item()
-
-
-def _float64(fn, *args):
-    """Run an oracle function unchanged in float64: its windows and filterbanks take torch's default dtype."""
-    old = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float64)
-    try:
-        return fn(*args)
-    finally:
-        torch.set_default_dtype(old)
 
 
 @pytest.fixture(scope="module")
@@ -96,6 +87,24 @@ def test_mel_spectrogram(b, nw):
     assert got.shape == ref.shape == (b, 100, 1 + nw // 256)
     mx, rms = _report(f"mel b{b} nw{nw}", got, ref)
     assert rms < 1e-3 and mx < 5e-3
+
+
+def test_vocos_decode_silence_frames(vocos):
+    """What the decoder sees after the front-end on a clip with digital silence: half the frames of a [2, 100, 64] mel hold log(1e-5) in
+    every channel (a run in the middle of item 0, the head and the tail of item 1), the others the random level of test_vocos_decode.
+    Against the float64 oracle under the same 1e-4 bound (6.9e-7 max measured on an MI355X)."""
+    sd = synth.vocos_state_dict()
+    g = torch.Generator().manual_seed(164)
+    mel = torch.randn(2, 100, 64, generator=g) * 1.5 - 1.0
+    mel[0, :, 16:48] = LOG_CLAMP
+    mel[1, :, :20] = LOG_CLAMP
+    mel[1, :, 52:] = LOG_CLAMP
+    assert (mel == mel.new_tensor(LOG_CLAMP)).all(1).sum().item() == 64          # half of the 128 frames
+    ref = _float64(V.vocos_decode, {k: v.double() for k, v in sd.items()}, mel.double())
+    got = vocos.decode(mel)
+    assert got.shape == ref.shape == (2, 256 * 63) and torch.isfinite(got).all()
+    mx, rms = _report("vocos silence frames b2 t64", got, ref)
+    assert mx < 1e-4
 
 
 def test_mel_then_vocos_roundtrip_lengths(vocos):

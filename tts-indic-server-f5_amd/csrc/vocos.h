@@ -132,7 +132,9 @@ __global__ __launch_bounds__(256) void mel_frame_kernel(const float* wave, int n
     if (tid < n_mels) {
         float acc = 0.0f;
         for (int k = 0; k <= 512; k++) acc += fb[k * n_mels + tid] * mag[k];
-        mel[((size_t)b * n_mels + tid) * T + t] = logf(fmaxf(acc, 1e-5f));
+        // log(clamp(acc, 1e-5)), clamped on the log side: the device logf is ~2 ulp (1.6e-6) off at 1e-5, and silent bins are to hold the
+        // fp32 value of log(1e-5) that the reference's front-end produces
+        mel[((size_t)b * n_mels + tid) * T + t] = fmaxf(logf(acc), -11.512925148f);
     }
 }
 
@@ -374,8 +376,9 @@ static int mel_frames(MelTables& t, std::vector<float> (*filterbank)(int, int, i
 
 int f5hip_mel_spectrogram(int32_t batch, int32_t n_samples, const float* wave_dev, float* mel_dev, int32_t n_fft, int32_t hop_length,
                           int32_t n_mels, int32_t sample_rate, void* stream) {
+    if (n_fft != 1024 || n_mels < 1 || n_mels > 256) return fail(-1, "mel_spectrogram: only n_fft = 1024, 1 <= n_mels <= 256");
+    if (hop_length < 1 || hop_length > n_fft || sample_rate < 2) return fail(-1, "mel_spectrogram: need 1 <= hop_length <= n_fft, sample_rate >= 2");
     if (batch <= 0 || n_samples <= n_fft / 2 || !wave_dev || !mel_dev) return fail(-1, "mel_spectrogram: bad argument");
-    if (n_fft != 1024 || n_mels > 256) return fail(-1, "mel_spectrogram: only n_fft = 1024, n_mels <= 256");
     return mel_frames(g_mel, htk_filterbank, batch, n_samples, wave_dev, mel_dev, n_fft, hop_length, n_mels, sample_rate, n_fft / 2,
                       1 + n_samples / hop_length, 0.0f, "mel_frame", (hipStream_t)stream);
 }
@@ -383,8 +386,9 @@ int f5hip_mel_spectrogram(int32_t batch, int32_t n_samples, const float* wave_de
 // ---- BigVGAN-style mel (F/model/modules.py:30-72): librosa Slaney filterbank, center=False after a reflect pad of (n_fft - hop) / 2
 int f5hip_mel_spectrogram_bigvgan(int32_t batch, int32_t n_samples, const float* wave_dev, float* mel_dev, int32_t n_fft, int32_t hop_length,
                                   int32_t n_mels, int32_t sample_rate, void* stream) {
+    if (n_fft != 1024 || n_mels < 1 || n_mels > 256) return fail(-1, "mel_spectrogram_bigvgan: only n_fft = 1024, 1 <= n_mels <= 256");
+    if (hop_length < 1 || hop_length > n_fft || sample_rate < 2) return fail(-1, "mel_spectrogram_bigvgan: need 1 <= hop_length <= n_fft, sample_rate >= 2");
     if (batch <= 0 || n_samples < n_fft || !wave_dev || !mel_dev) return fail(-1, "mel_spectrogram_bigvgan: bad argument");
-    if (n_fft != 1024 || n_mels > 256) return fail(-1, "mel_spectrogram_bigvgan: only n_fft = 1024, n_mels <= 256");
     const int pad = (n_fft - hop_length) / 2;
     return mel_frames(g_mel_bv, slaney_filterbank, batch, n_samples, wave_dev, mel_dev, n_fft, hop_length, n_mels, sample_rate, pad,
                       (n_samples + 2 * pad - n_fft) / hop_length + 1, 1e-9f, "mel_frame (bigvgan)", (hipStream_t)stream);
