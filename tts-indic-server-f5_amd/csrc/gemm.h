@@ -20,9 +20,7 @@
 
 F5_DEVICE int lds_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
 
-
-// ABL (timing ablations, diagnostics only; no launcher instantiates them): 0 = normal, 1 = no global loads inside the k-loop, 2 = no LDS reads / MFMAs
-template <int NSPLIT, int BN, bool CONV, int EPI, int ABL = 0>
+template <int NSPLIT, int BN, bool CONV, int EPI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_kernel(const GemmArgs p) {
     constexpr int NPL = NSPLIT == 2 ? 2 : 1;   // NSPLIT = operand precision: 1 bf16, 2 split bf16 (3 MFMAs), 3 fp16 (PREC_F16)
     constexpr bool F16 = NSPLIT == 3;
@@ -120,31 +118,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int g = 0; g < 16; g++) acc[i][j][g] = 0.0f;
 
-    // ABL == 3 (diagnostics): s_memtime stamps of workgroup (0,0) wave 0 accumulated per phase into p.stamps[0..7]
-    unsigned long long st_acc[6] = {0, 0, 0, 0, 0, 0}, st_prev = 0, st_begin = 0;
-#define STAMP(IDX)                                                                                   \
-    if constexpr (ABL == 3) {                                                                        \
-        unsigned long long t_;                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                           \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                  \
-        __builtin_amdgcn_sched_barrier(0);                                                           \
-        if ((IDX) >= 0) st_acc[(IDX) < 0 ? 0 : (IDX)] += t_ - st_prev; else st_begin = t_;           \
-        st_prev = t_;                                                                                \
-    }
-    STAMP(-1);
     LOAD_TILES(0);
     STORE_TILES(0);
     __syncthreads();
-    STAMP(0);   // prologue
 
     const int fr = lane & 31, fh = lane >> 5;
     for (int kt = 0; kt < nk; kt++) {
         const bool more = kt + 1 < nk;
-        if (more && ABL != 1) LOAD_TILES(kt + 1);
-        STAMP(1);   // global load issue
+        if (more) LOAD_TILES(kt + 1);
         const char* base = smem + (kt & 1) * STAGE;
 #pragma unroll
-        for (int s = 0; s < (ABL == 2 ? 0 : 2); s++) {
+        for (int s = 0; s < 2; s++) {
             bf16x8 af[NPL][TM], bf[NPL][TN];
             const int chunk = s * 2 + fh;
 #pragma unroll
@@ -167,38 +151,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     acc[i][j] = mfma_32x32x16<F16>(af[0][i], bf[0][j], acc[i][j]);
                 }
         }
-        STAMP(2);   // LDS reads + MFMAs
-        if (more && ABL != 1) STORE_TILES((kt + 1) & 1);
-        STAMP(3);   // wait for the global loads + LDS writes
+        if (more) STORE_TILES((kt + 1) & 1);
         __syncthreads();
-        STAMP(4);   // barrier
     }
 #undef LOAD_TILES
 #undef STORE_TILES
 
     // ---------------------------------------------------------------- epilogue (gemm_epilogue.h)
-    unsigned long long epi_dbg[4] = {0, 0, 0, 0};
-    gemm_epilogue<EPI, TM, TN>(p, acc, reinterpret_cast<float*>(smem) + wave * (TM * TN * 1024), m0 + wm * (TM * 32), n0 + wn * 64, n0, lane,
-                               ABL == 3 ? epi_dbg : nullptr);
-    STAMP(5);   // epilogue
-    if constexpr (ABL == 3) {
-        if (p.stamps && blockIdx.x == p.stamp_bx && blockIdx.y == p.stamp_by && tid == 0) {
-            for (int i = 0; i < 6; i++) p.stamps[i] = st_acc[i];
-            p.stamps[6] = st_prev - st_begin;
-            for (int i = 0; i < 4; i++) p.stamps[7 + i] = epi_dbg[i];
-        }
-    }
-#undef STAMP
+    gemm_epilogue<EPI, TM, TN>(p, acc, reinterpret_cast<float*>(smem) + wave * (TM * TN * 1024), m0 + wm * (TM * 32), n0 + wn * 64, n0, lane);
 }
 
-template <int NSPLIT, int BN, bool CONV, int EPI, int ABL = 0>
+template <int NSPLIT, int BN, bool CONV, int EPI>
 static hipError_t launch_gemm_t(const GemmArgs& a, int m_pad, int n_pad, hipStream_t st) {
     constexpr int EPI_LDS = (128 / (4 / (BN / 64)) / 32) * 2 * 4096 * 4;   // 4 waves x (TM x TN) x 4 KiB epilogue slabs
     constexpr int NPL = NSPLIT == 2 ? 2 : 1;
     constexpr int LDS = 2 * NPL * (128 + BN) * 64 < EPI_LDS ? EPI_LDS : 2 * NPL * (128 + BN) * 64;
     static unsigned attr_mask = 0;
-    if (hipError_t e = f5_set_lds_attr(reinterpret_cast<const void*>(&gemm_kernel<NSPLIT, BN, CONV, EPI, ABL>), LDS, attr_mask); e != hipSuccess) return e;
+    if (hipError_t e = f5_set_lds_attr(reinterpret_cast<const void*>(&gemm_kernel<NSPLIT, BN, CONV, EPI>), LDS, attr_mask); e != hipSuccess) return e;
     dim3 grid(n_pad / BN, m_pad / 128);
-    hipLaunchKernelGGL((gemm_kernel<NSPLIT, BN, CONV, EPI, ABL>), grid, dim3(256), LDS, st, a);
+    hipLaunchKernelGGL((gemm_kernel<NSPLIT, BN, CONV, EPI>), grid, dim3(256), LDS, st, a);
     return hipGetLastError();
 }

@@ -245,138 +245,91 @@ F5_DEVICE void g5_write_slab(f32x4 (&acc)[MRB][MCB], float* slab, int rb0, int n
     }
 }
 
-// The arithmetic of the generic epilogue on 4 consecutive features of one row, shared by every epilogue form of gemm5 / gemm6 (slab row
-// phase, direct-from-accumulator): one function, explicit fma, so that which kernel computed a row cannot change its bits.
-template <int ACT, bool RES>
-F5_DEVICE f32x4 g5_epi_value(f32x4 acc, f32x4 bias, f32x4 mul, f32x4 res, bool zero_row) {
-    f32x4 v = acc + bias;
-    if (ACT != ACT_NONE) {
-#pragma unroll
-        for (int e = 0; e < 4; e++) v[e] = apply_act(v[e], ACT);
-    }
-    if (zero_row) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int e = 0; e < 4; e++) v[e] = RES ? __builtin_fmaf(v[e], mul[e], res[e]) : __fmul_rn(v[e], mul[e]);
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // generic row phase: v = act(acc + bias); rows with row_keep == 0 -> 0; v = v * mul + res; fp32 and / or 16-bit outputs.
 // Work unit = one group of 4 rows x the tile's NPAN panels of 64 columns (lane -> row lane >> 4, columns 4 (lane & 15) .. + 3 of each
 // panel); groups are dealt round-robin over the 8 waves; the loop is rolled, the next group's residual is loaded before the current
 // group is finished.
 // ROWMUL: the multiplier of each row from its own modulation row (EPI_GENERIC_ROWMUL), loaded with the row group.
-template <int ACT, bool RES, bool OUTF, int OUTS, bool GUARD, int RB, int CB, int NST, typename WriteSlab, bool ROWMUL = false>
-F5_DEVICE void g5_generic_tail(const GemmArgs& p, const float* slab, int m0, int n0, int wave, int lane, WriteSlab write_slab) {
-    using C = Gemm5Cfg<RB, CB, NST>;
-    constexpr int NPAN = C::NPAN, NG = RB * 4;                 // row groups of the tile
-    const int r_in = lane >> 4, c4 = (lane & 15) * 4;
-    f32x4 bv[NPAN], mv[NPAN];
-    bool nok[NPAN];
-#pragma unroll
-    for (int pn = 0; pn < NPAN; pn++) {
-        const int n = n0 + pn * 64 + c4;
-        nok[pn] = GUARD ? n < p.N : true;
-        bv[pn] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        mv[pn] = (f32x4){1.f, 1.f, 1.f, 1.f};
-        if (p.bias && nok[pn]) bv[pn] = *reinterpret_cast<const f32x4*>(p.bias + n);
-        if (!ROWMUL && p.mul && nok[pn]) mv[pn] = *reinterpret_cast<const f32x4*>(p.mul + n);
-    }
-    f32x4 rs[RES ? NPAN : 1], rn[RES ? NPAN : 1];
-    auto load_res = [&](int g, f32x4 (&dst)[RES ? NPAN : 1]) {
-        if (!RES) return;
-        const int row = m0 + g * 4 + r_in;
-#pragma unroll
-        for (int pn = 0; pn < NPAN; pn++) {
-            dst[pn] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (g < NG && (!GUARD || (nok[pn] && row < p.M))) dst[pn] = *reinterpret_cast<const f32x4*>(p.res + (size_t)row * p.ldres + n0 + pn * 64 + c4);
-        }
-    };
-    load_res(wave, rs);                                            // in flight across the slab write and its barrier
-    write_slab();
-    __syncthreads();                                               // E2: the slab is complete
-#pragma unroll 1
-    for (int g = wave; g < NG; g += 8) {
-        load_res(g + 8, rn);
-        const int rl = g * 4 + r_in, row = m0 + rl;
-        int keep = 1;
-        if (GUARD && p.row_keep && row < p.M) keep = p.row_keep[row];
-        if (ROWMUL) {
-            const float* mrow = (!GUARD || row < p.M) ? p.mul + (size_t)p.row_mod[row] * p.mod_ld : nullptr;
-#pragma unroll
-            for (int pn = 0; pn < NPAN; pn++)
-                mv[pn] = mrow && nok[pn] ? *reinterpret_cast<const f32x4*>(mrow + n0 + pn * 64 + c4) : (f32x4){1.f, 1.f, 1.f, 1.f};
-        }
+template <int RB, int CB, int NST, bool ROWMUL>
+struct G5GenericTail {
+    template <int ACT, bool RES, bool OUTF, int OUTS, bool GUARD, typename WriteSlab>
+    static F5_DEVICE void run(const GemmArgs& p, const float* slab, int m0, int n0, int wave, int lane, WriteSlab write_slab) {
+        using C = Gemm5Cfg<RB, CB, NST>;
+        constexpr int NPAN = C::NPAN, NG = RB * 4;                 // row groups of the tile
+        const int r_in = lane >> 4, c4 = (lane & 15) * 4;
+        f32x4 bv[NPAN], mv[NPAN];
+        bool nok[NPAN];
 #pragma unroll
         for (int pn = 0; pn < NPAN; pn++) {
             const int n = n0 + pn * 64 + c4;
-            const f32x4 v = g5_epi_value<ACT, RES>(*reinterpret_cast<const f32x4*>(slab + rl * C::SLD + pn * 64 + c4), bv[pn], mv[pn], rs[RES ? pn : 0], GUARD && !keep);
-            if (!GUARD || (nok[pn] && row < p.M)) {
-                if (OUTF) *reinterpret_cast<f32x4*>(p.out_f32 + (size_t)row * p.ldo + n) = v;
-                const float vv[4] = {v[0], v[1], v[2], v[3]};
-                if (OUTS == 2) {
-                    store_f16x4(p.out_hi + (size_t)row * p.ldob + n, vv);
-                } else if (OUTS == 1) {
-                    bf16x4 hi, lo;
-                    split_bf16x4(vv, hi, lo);
-                    *reinterpret_cast<bf16x4*>(p.out_hi + (size_t)row * p.ldob + n) = hi;
-                    if (p.out_lo) *reinterpret_cast<bf16x4*>(p.out_lo + (size_t)row * p.ldob + n) = lo;
+            nok[pn] = GUARD ? n < p.N : true;
+            bv[pn] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            mv[pn] = (f32x4){1.f, 1.f, 1.f, 1.f};
+            if (p.bias && nok[pn]) bv[pn] = *reinterpret_cast<const f32x4*>(p.bias + n);
+            if (!ROWMUL && p.mul && nok[pn]) mv[pn] = *reinterpret_cast<const f32x4*>(p.mul + n);
+        }
+        f32x4 rs[RES ? NPAN : 1], rn[RES ? NPAN : 1];
+        auto load_res = [&](int g, f32x4 (&dst)[RES ? NPAN : 1]) {
+            if (!RES) return;
+            const int row = m0 + g * 4 + r_in;
+#pragma unroll
+            for (int pn = 0; pn < NPAN; pn++) {
+                dst[pn] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                if (g < NG && (!GUARD || (nok[pn] && row < p.M))) dst[pn] = *reinterpret_cast<const f32x4*>(p.res + (size_t)row * p.ldres + n0 + pn * 64 + c4);
+            }
+        };
+        load_res(wave, rs);                                            // in flight across the slab write and its barrier
+        write_slab();
+        __syncthreads();                                               // E2: the slab is complete
+#pragma unroll 1
+        for (int g = wave; g < NG; g += 8) {
+            load_res(g + 8, rn);
+            const int rl = g * 4 + r_in, row = m0 + rl;
+            int keep = 1;
+            if (GUARD && p.row_keep && row < p.M) keep = p.row_keep[row];
+            if (ROWMUL) {
+                const float* mrow = (!GUARD || row < p.M) ? p.mul + (size_t)p.row_mod[row] * p.mod_ld : nullptr;
+#pragma unroll
+                for (int pn = 0; pn < NPAN; pn++)
+                    mv[pn] = mrow && nok[pn] ? *reinterpret_cast<const f32x4*>(mrow + n0 + pn * 64 + c4) : (f32x4){1.f, 1.f, 1.f, 1.f};
+            }
+#pragma unroll
+            for (int pn = 0; pn < NPAN; pn++) {
+                const int n = n0 + pn * 64 + c4;
+                const f32x4 v = g5_epi_value<ACT, RES>(*reinterpret_cast<const f32x4*>(slab + rl * C::SLD + pn * 64 + c4), bv[pn], mv[pn], rs[RES ? pn : 0], GUARD && !keep);
+                if (!GUARD || (nok[pn] && row < p.M)) {
+                    if (OUTF) *reinterpret_cast<f32x4*>(p.out_f32 + (size_t)row * p.ldo + n) = v;
+                    const float vv[4] = {v[0], v[1], v[2], v[3]};
+                    if (OUTS == 2) {
+                        store_f16x4(p.out_hi + (size_t)row * p.ldob + n, vv);
+                    } else if (OUTS == 1) {
+                        bf16x4 hi, lo;
+                        split_bf16x4(vv, hi, lo);
+                        *reinterpret_cast<bf16x4*>(p.out_hi + (size_t)row * p.ldob + n) = hi;
+                        if (p.out_lo) *reinterpret_cast<bf16x4*>(p.out_lo + (size_t)row * p.ldob + n) = lo;
+                    }
                 }
             }
-        }
-        if (RES) {
+            if (RES) {
 #pragma unroll
-            for (int pn = 0; pn < NPAN; pn++) rs[pn] = rn[pn];
+                for (int pn = 0; pn < NPAN; pn++) rs[pn] = rn[pn];
+            }
         }
     }
-}
+};   // G5GenericTail
 
-template <int ACT, bool GUARD, int RB, int CB, int NST, typename WriteSlab, bool ROWMUL = false>
-F5_DEVICE void g5_generic_variants(const GemmArgs& p, const float* slab, int m0, int n0, int wave, int lane, WriteSlab ws) {
-    const bool res = p.res != nullptr, outf = p.out_f32 != nullptr, outs = p.out_hi != nullptr;
-    // the (residual, fp32 out, 16-bit out) combinations in use on the path: same table as epi_generic_rows_g (gemm_epilogue.h)
-    if constexpr (ROWMUL) {
-        g5_generic_tail<ACT_NONE, true, true, 0, GUARD, RB, CB, NST, WriteSlab, true>(p, slab, m0, n0, wave, lane, ws);
-    } else if (ACT == ACT_NONE) {
-        if (res) {
-            if (outf && outs) g5_generic_tail<ACT, true, true, 1, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-            else if (outf) g5_generic_tail<ACT, true, true, 0, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-            else g5_generic_tail<ACT, true, false, 1, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-        } else {
-            if (outf && outs) g5_generic_tail<ACT, false, true, 1, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-            else if (outf) g5_generic_tail<ACT, false, true, 0, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-            else if (p.f16_out) g5_generic_tail<ACT, false, false, 2, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-            else g5_generic_tail<ACT, false, false, 1, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-        }
-    } else {
-        if (res) g5_generic_tail<ACT, true, true, 0, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-        else if (outs && !outf && p.f16_out) g5_generic_tail<ACT, false, false, 2, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-        else if (outs && !outf) g5_generic_tail<ACT, false, false, 1, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-        else if (outf && !outs) g5_generic_tail<ACT, false, true, 0, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-        else g5_generic_tail<ACT, false, true, 1, GUARD, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-    }
-}
-
-template <int RB, int CB, int NST, typename WriteSlab, bool ROWMUL = false>
+template <int RB, int CB, int NST, bool ROWMUL, typename WriteSlab>
 F5_DEVICE void g5_generic_epilogue(const GemmArgs& p, const float* slab, int m0, int n0, int wave, int lane, WriteSlab ws) {
     // workgroup-uniform: interior tile without per-row special cases
     const bool interior = m0 + RB * 16 <= p.M && n0 + CB * 16 <= p.N && !p.row_keep;
-    if constexpr (ROWMUL) {
-        if (interior) g5_generic_variants<ACT_NONE, false, RB, CB, NST, WriteSlab, true>(p, slab, m0, n0, wave, lane, ws);
-        else g5_generic_variants<ACT_NONE, true, RB, CB, NST, WriteSlab, true>(p, slab, m0, n0, wave, lane, ws);
-        return;
+    using Tail = G5GenericTail<RB, CB, NST, ROWMUL>;
+    if constexpr (ROWMUL) {   // one variant, called directly: through epi_dispatch these kernels come out with another register allocation
+        if (interior) Tail::template run<ACT_NONE, true, true, 0, false>(p, slab, m0, n0, wave, lane, ws);
+        else Tail::template run<ACT_NONE, true, true, 0, true>(p, slab, m0, n0, wave, lane, ws);
+    } else {
+        epi_dispatch<Tail, false>(p, interior, slab, m0, n0, wave, lane, ws);
     }
-#define G5_ACT(A)                                                                                 \
-    if (interior) g5_generic_variants<A, false, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);   \
-    else g5_generic_variants<A, true, RB, CB, NST>(p, slab, m0, n0, wave, lane, ws);
-    switch (p.act) {
-        case ACT_GELU_TANH: G5_ACT(ACT_GELU_TANH) break;
-        case ACT_GELU_ERF: G5_ACT(ACT_GELU_ERF) break;
-        case ACT_MISH: G5_ACT(ACT_MISH) break;
-        case ACT_SILU: G5_ACT(ACT_SILU) break;
-        default: G5_ACT(ACT_NONE) break;
-    }
-#undef G5_ACT
 }
 
 // Q / K rows of the fused QKV projection: bias, rotary embedding on head 0 (x-transformers interleaved pairs, applied before the head
@@ -566,15 +519,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __syncthreads();                                               // E1: the ring is dead
     G5_STAMP(3);
     float* slab = reinterpret_cast<float*>(smem);
-    if constexpr (EPI == EPI_GENERIC) {
-        g5_generic_epilogue<RB, CB, NST>(p, slab, m0, n0, wave, lane, [&]() {
+    if constexpr (EPI == EPI_GENERIC || EPI == EPI_GENERIC_ROWMUL) {
+        g5_generic_epilogue<RB, CB, NST, EPI == EPI_GENERIC_ROWMUL>(p, slab, m0, n0, wave, lane, [&]() {
             if (wave < 4) g5_write_slab<RB, CB, NST, WR, MRB, MCB, true, true>(acc, slab, rb0, nrb, cb0, lane, nullptr);
         });
-    } else if constexpr (EPI == EPI_GENERIC_ROWMUL) {
-        auto ws = [&]() {
-            if (wave < 4) g5_write_slab<RB, CB, NST, WR, MRB, MCB, true, true>(acc, slab, rb0, nrb, cb0, lane, nullptr);
-        };
-        g5_generic_epilogue<RB, CB, NST, decltype(ws), true>(p, slab, m0, n0, wave, lane, ws);
     } else if (swap) {
         // Q / K tile (possibly with V blocks behind the K | V boundary): row-major slab, rolled row phase; then the V blocks, if any
         const int f_lo = max(0, 2 * p.D - n0);                     // first V column of this tile (>= BN: none; 0: an all-V tile of a W-direct kernel)

@@ -217,113 +217,76 @@ F5_DEVICE void g6_kloop(const GemmArgs& p, char* smem, unsigned lds0, int m0, in
 // profiles/r03_gemm6_stamps_slab_epilogue.txt.)
 // n_blk = row blocks of this wave that belong to the tile (RBW, or one fewer for the second group of a 176-row tile)
 // ROWMUL: the multiplier of each row from its own modulation row (EPI_GENERIC_ROWMUL), loaded with the row block.
-template <int ACT, bool RES, bool OUTF, int OUTS, bool GUARD, int RBW, bool ROWMUL = false>
-F5_DEVICE void g6_direct_tail(const GemmArgs& p, f32x4 (&acc)[RBW][4], int m_w, int n_w, int n_blk, int lane) {
-    const int fr = lane & 15, fq = lane >> 4;
-    f32x4 bv[4], mv[4];
-    bool nok[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int n = n_w + j * 16 + fq * 4;
-        nok[j] = GUARD ? n < p.N : true;
-        bv[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        mv[j] = (f32x4){1.f, 1.f, 1.f, 1.f};
-        if (p.bias && nok[j]) bv[j] = *reinterpret_cast<const f32x4*>(p.bias + n);
-        if (!ROWMUL && p.mul && nok[j]) mv[j] = *reinterpret_cast<const f32x4*>(p.mul + n);
-    }
-    f32x4 rs[RES ? 4 : 1], rn[RES ? 4 : 1];
-    auto load_res = [&](int i, f32x4 (&dst)[RES ? 4 : 1]) {
-        if (!RES) return;
-        const int row = m_w + i * 16 + fr;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            dst[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (i < n_blk && (!GUARD || (nok[j] && row < p.M))) dst[j] = *reinterpret_cast<const f32x4*>(p.res + (size_t)row * p.ldres + n_w + j * 16 + fq * 4);
-        }
-    };
-    load_res(0, rs);
-#pragma unroll
-    for (int i = 0; i < RBW; i++) {
-        if (i >= n_blk) break;                                 // (wave-uniform)
-        load_res(i + 1, rn);
-        const int row = m_w + i * 16 + fr;
-        int keep = 1;
-        if (GUARD && p.row_keep && row < p.M) keep = p.row_keep[row];
-        if (ROWMUL) {
-            const float* mrow = (!GUARD || row < p.M) ? p.mul + (size_t)p.row_mod[row] * p.mod_ld : nullptr;
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                mv[j] = mrow && nok[j] ? *reinterpret_cast<const f32x4*>(mrow + n_w + j * 16 + fq * 4) : (f32x4){1.f, 1.f, 1.f, 1.f};
-        }
+template <int RBW, bool ROWMUL>
+struct G6DirectTail {
+    template <int ACT, bool RES, bool OUTF, int OUTS, bool GUARD>
+    static F5_DEVICE void run(const GemmArgs& p, f32x4 (&acc)[RBW][4], int m_w, int n_w, int n_blk, int lane) {
+        const int fr = lane & 15, fq = lane >> 4;
+        f32x4 bv[4], mv[4];
+        bool nok[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int n = n_w + j * 16 + fq * 4;
-            const f32x4 v = g5_epi_value<ACT, RES>(acc[i][j], bv[j], mv[j], rs[RES ? j : 0], GUARD && !keep);
-            if (!GUARD || (nok[j] && row < p.M)) {
-                if (OUTF) *reinterpret_cast<f32x4*>(p.out_f32 + (size_t)row * p.ldo + n) = v;
-                const float vv[4] = {v[0], v[1], v[2], v[3]};
-                if (OUTS == 2) {
-                    store_f16x4(p.out_hi + (size_t)row * p.ldob + n, vv);
-                } else if (OUTS == 1) {
-                    bf16x4 hi, lo;
-                    split_bf16x4(vv, hi, lo);
-                    *reinterpret_cast<bf16x4*>(p.out_hi + (size_t)row * p.ldob + n) = hi;
-                    if (p.out_lo) *reinterpret_cast<bf16x4*>(p.out_lo + (size_t)row * p.ldob + n) = lo;
+            nok[j] = GUARD ? n < p.N : true;
+            bv[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            mv[j] = (f32x4){1.f, 1.f, 1.f, 1.f};
+            if (p.bias && nok[j]) bv[j] = *reinterpret_cast<const f32x4*>(p.bias + n);
+            if (!ROWMUL && p.mul && nok[j]) mv[j] = *reinterpret_cast<const f32x4*>(p.mul + n);
+        }
+        f32x4 rs[RES ? 4 : 1], rn[RES ? 4 : 1];
+        auto load_res = [&](int i, f32x4 (&dst)[RES ? 4 : 1]) {
+            if (!RES) return;
+            const int row = m_w + i * 16 + fr;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                dst[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                if (i < n_blk && (!GUARD || (nok[j] && row < p.M))) dst[j] = *reinterpret_cast<const f32x4*>(p.res + (size_t)row * p.ldres + n_w + j * 16 + fq * 4);
+            }
+        };
+        load_res(0, rs);
+#pragma unroll
+        for (int i = 0; i < RBW; i++) {
+            if (i >= n_blk) break;                                 // (wave-uniform)
+            load_res(i + 1, rn);
+            const int row = m_w + i * 16 + fr;
+            int keep = 1;
+            if (GUARD && p.row_keep && row < p.M) keep = p.row_keep[row];
+            if (ROWMUL) {
+                const float* mrow = (!GUARD || row < p.M) ? p.mul + (size_t)p.row_mod[row] * p.mod_ld : nullptr;
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    mv[j] = mrow && nok[j] ? *reinterpret_cast<const f32x4*>(mrow + n_w + j * 16 + fq * 4) : (f32x4){1.f, 1.f, 1.f, 1.f};
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int n = n_w + j * 16 + fq * 4;
+                const f32x4 v = g5_epi_value<ACT, RES>(acc[i][j], bv[j], mv[j], rs[RES ? j : 0], GUARD && !keep);
+                if (!GUARD || (nok[j] && row < p.M)) {
+                    // (the store of G5GenericTail, written out per family: through one shared function the 256-row kernel takes 246 registers, not 242)
+                    if (OUTF) *reinterpret_cast<f32x4*>(p.out_f32 + (size_t)row * p.ldo + n) = v;
+                    const float vv[4] = {v[0], v[1], v[2], v[3]};
+                    if (OUTS == 2) {
+                        store_f16x4(p.out_hi + (size_t)row * p.ldob + n, vv);
+                    } else if (OUTS == 1) {
+                        bf16x4 hi, lo;
+                        split_bf16x4(vv, hi, lo);
+                        *reinterpret_cast<bf16x4*>(p.out_hi + (size_t)row * p.ldob + n) = hi;
+                        if (p.out_lo) *reinterpret_cast<bf16x4*>(p.out_lo + (size_t)row * p.ldob + n) = lo;
+                    }
                 }
             }
-        }
-        if (RES) {
+            if (RES) {
 #pragma unroll
-            for (int j = 0; j < 4; j++) rs[j] = rn[j];
+                for (int j = 0; j < 4; j++) rs[j] = rn[j];
+            }
         }
     }
-}
+};   // G6DirectTail
 
-template <int ACT, bool GUARD, int RBW, bool ROWMUL = false>
-F5_DEVICE void g6_direct_variants(const GemmArgs& p, f32x4 (&acc)[RBW][4], int m_w, int n_w, int n_blk, int lane) {
-    const bool res = p.res != nullptr, outf = p.out_f32 != nullptr, outs = p.out_hi != nullptr;
-    // the (residual, fp32 out, 16-bit out) combinations in use on the path: the table of g5_generic_variants
-    if constexpr (ROWMUL) {
-        g6_direct_tail<ACT_NONE, true, true, 0, GUARD, RBW, true>(p, acc, m_w, n_w, n_blk, lane);
-    } else if (ACT == ACT_NONE) {
-        if (res) {
-            if (outf && outs) g6_direct_tail<ACT, true, true, 1, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
-            else if (outf) g6_direct_tail<ACT, true, true, 0, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
-            else g6_direct_tail<ACT, true, false, 1, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
-        } else {
-            if (outf && outs) g6_direct_tail<ACT, false, true, 1, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
-            else if (outf) g6_direct_tail<ACT, false, true, 0, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
-            else if (p.f16_out) g6_direct_tail<ACT, false, false, 2, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
-            else g6_direct_tail<ACT, false, false, 1, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
-        }
-    } else {
-        if (res) g6_direct_tail<ACT, true, true, 0, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
-        else if (outs && !outf && p.f16_out) g6_direct_tail<ACT, false, false, 2, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
-        else if (outs && !outf) g6_direct_tail<ACT, false, false, 1, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
-        else if (outf && !outs) g6_direct_tail<ACT, false, true, 0, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
-        else g6_direct_tail<ACT, false, true, 1, GUARD, RBW>(p, acc, m_w, n_w, n_blk, lane);
-    }
-}
-
-template <int RBW, bool ROWMUL = false>
+template <int RBW, bool ROWMUL>
 F5_DEVICE void g6_direct_epilogue(const GemmArgs& p, f32x4 (&acc)[RBW][4], int m0, int n0, int m_w, int n_w, int n_blk, int lane) {
     const bool interior = m0 + Gemm6Cfg<RBW>::BM <= p.M && n0 + Gemm6Cfg<RBW>::BN <= p.N && !p.row_keep;   // workgroup-uniform
-    if constexpr (ROWMUL) {
-        if (interior) g6_direct_variants<ACT_NONE, false, RBW, true>(p, acc, m_w, n_w, n_blk, lane);
-        else g6_direct_variants<ACT_NONE, true, RBW, true>(p, acc, m_w, n_w, n_blk, lane);
-        return;
-    }
-#define G6_ACT(A)                                                                         \
-    if (interior) g6_direct_variants<A, false, RBW>(p, acc, m_w, n_w, n_blk, lane);       \
-    else g6_direct_variants<A, true, RBW>(p, acc, m_w, n_w, n_blk, lane);
-    switch (p.act) {
-        case ACT_GELU_TANH: G6_ACT(ACT_GELU_TANH) break;
-        case ACT_GELU_ERF: G6_ACT(ACT_GELU_ERF) break;
-        case ACT_MISH: G6_ACT(ACT_MISH) break;
-        case ACT_SILU: G6_ACT(ACT_SILU) break;
-        default: G6_ACT(ACT_NONE) break;
-    }
-#undef G6_ACT
+    epi_dispatch<G6DirectTail<RBW, ROWMUL>, ROWMUL>(p, interior, acc, m_w, n_w, n_blk, lane);
 }
 
 // Q / K tiles of the QKV projection straight from the accumulators: g5_qk_rows' arithmetic (bias, rotary on head 0 -- the first 64 columns
@@ -357,7 +320,7 @@ F5_DEVICE void g6_qk_direct(const GemmArgs& p, f32x4 (&acc)[RBW][4], int n0, int
         for (int j = 0; j < 4; j++) {
             const f32x4 v = acc[i][j] + bv[j];
             float o[4];
-            if (rot) {
+            if (rot) {   // (explicit product + fma: see g5_qk_rows)
                 o[0] = __builtin_fmaf(v[0], cs[j].x, -__fmul_rn(v[1], sn[j].x)) * qs;
                 o[1] = __builtin_fmaf(v[1], cs[j].x, __fmul_rn(v[0], sn[j].x)) * qs;
                 o[2] = __builtin_fmaf(v[2], cs[j].y, -__fmul_rn(v[3], sn[j].y)) * qs;
@@ -416,9 +379,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // rows of the LDS image this tile owns: all of them, or 176 of the 192 (the last row block of the second wave group is the next tile's)
         const int m_end = min(p.M, m0 + C::BM);
         const int n_blk = min(RBW, (C::BM - wr * RBW * 16) / 16);
-        if (EPI == EPI_GENERIC || EPI == EPI_GENERIC_ROWMUL || swap) {
-            if constexpr (EPI == EPI_GENERIC) g6_direct_epilogue<RBW>(p, acc, m0, n0, m0 + wr * RBW * 16, n0 + wc * 64, n_blk, lane);
-            else if constexpr (EPI == EPI_GENERIC_ROWMUL) g6_direct_epilogue<RBW, true>(p, acc, m0, n0, m0 + wr * RBW * 16, n0 + wc * 64, n_blk, lane);
+        if (EPI != EPI_QKV || swap) {
+            if constexpr (EPI != EPI_QKV) g6_direct_epilogue<RBW, EPI == EPI_GENERIC_ROWMUL>(p, acc, m0, n0, m0 + wr * RBW * 16, n0 + wc * 64, n_blk, lane);
             else g6_qk_direct<RBW>(p, acc, n0, m0 + wr * RBW * 16, n0 + wc * 64, n_blk, m_end, lane);   // Q / K tile
             G6_STAMP(stamp[2] = stamp[3] = stamp[4] = stamp[5] = __builtin_amdgcn_s_memrealtime())
         } else {

@@ -1,4 +1,5 @@
-// Shared epilogue of the MFMA GEMM kernels (gemm.h, gemm2.h).
+// Epilogues of the MFMA GEMM kernels.  First the argument block and what gemm5.h and gemm6.h share: the (activation x guard x residual /
+// output) dispatch and the per-element arithmetic.  Then the slab epilogue of gemm.h / gemm3.h:
 //
 // A wave holds TM x TN accumulator tiles of 32 x 32 (v_mfma_f32_32x32x16_bf16 C/D layout: column on the lane,
 // rows (g&3) + 8 (g>>2) + 4 (lane>>5) in register g).  Each 32 x (32 TN) slice is transposed through a wave-private
@@ -10,7 +11,7 @@
 #include "ln_row.h"
 
 // EPI_GENERIC_ROWMUL: the generic epilogue with the multiplier taken per ROW -- mul + row_mod[row] * mod_ld (f5hip_cfm_sample_grids: the AdaLN
-// gates of the out / FF2 projections when the rows of one launch sit at different time points); residual + fp32 output, no activation, only
+// gates of the out / FF2 projections when the rows of one launch sit at different time points); residual + fp32 output only, no activation
 enum { EPI_GENERIC = 0, EPI_QKV = 1, EPI_GENERIC_ROWMUL = 2 };
 
 // 64-byte LDS rows (32-deep k-steps of gemm.h / gemm3.h): 16-byte chunk XOR-swizzled with (row >> 2) & 3
@@ -80,6 +81,82 @@ struct GemmArgs {
     int seq_blk;
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Shared by gemm5.h and gemm6.h.  epi_dispatch turns the run-time facts of a launch into compile-time ones, once per kernel and outside every loop, and runs
+//   Tail::run<ACT, RES, OUTF, OUTS, GUARD>(p, args...)
+// of the caller's row function ("tail"): ACT from p.act; GUARD = false for interior tiles (straight-line code without bounds, column-group or
+// row_keep tests); RES / OUTF / OUTS = residual present, fp32 output, 16-bit output (0 none, 1 split bf16, 2 one fp16 plane).
+// ROWMUL (EPI_GENERIC_ROWMUL, the gated residual projections h += gate (A W^T + b)) has one variant: no activation, residual, fp32 only.
+// (Plain function templates on purpose: with the tails handed over as lambdas the kernels came out with other register allocations.)
+// The slab epilogue below keeps its own switch and the same table (epi_generic_rows_g): routed through here, every gemm.h / gemm3.h kernel
+// compiled to other code and one measured 2 % slower.  For the same reason the store of four features, the rotary pair and the transposed
+// V store stay written out per family: each shared form tried changed the generated code of at least one family.
+template <class Tail, int ACT, bool GUARD, bool ROWMUL, typename... Args>
+F5_DEVICE void epi_with_variant(const GemmArgs& p, Args&&... args) {
+    const bool res = p.res != nullptr, outf = p.out_f32 != nullptr, outs = p.out_hi != nullptr;
+    // the (residual, fp32 out, 16-bit out) combinations in use on the path
+    if constexpr (ROWMUL) {
+        Tail::template run<ACT_NONE, true, true, 0, GUARD>(p, static_cast<Args&&>(args)...);
+    } else if (ACT == ACT_NONE) {   // residual / plain projections: every output combination occurs
+        if (res) {
+            if (outf && outs) Tail::template run<ACT, true, true, 1, GUARD>(p, static_cast<Args&&>(args)...);
+            else if (outf) Tail::template run<ACT, true, true, 0, GUARD>(p, static_cast<Args&&>(args)...);
+            else Tail::template run<ACT, true, false, 1, GUARD>(p, static_cast<Args&&>(args)...);
+        } else {
+            if (outf && outs) Tail::template run<ACT, false, true, 1, GUARD>(p, static_cast<Args&&>(args)...);
+            else if (outf) Tail::template run<ACT, false, true, 0, GUARD>(p, static_cast<Args&&>(args)...);
+            else if (p.f16_out) Tail::template run<ACT, false, false, 2, GUARD>(p, static_cast<Args&&>(args)...);
+            else Tail::template run<ACT, false, false, 1, GUARD>(p, static_cast<Args&&>(args)...);
+        }
+    } else {                 // activations: (no residual -> split or fp32) and (residual -> fp32) are the combinations in use
+        if (res) Tail::template run<ACT, true, true, 0, GUARD>(p, static_cast<Args&&>(args)...);
+        else if (outs && !outf && p.f16_out) Tail::template run<ACT, false, false, 2, GUARD>(p, static_cast<Args&&>(args)...);
+        else if (outs && !outf) Tail::template run<ACT, false, false, 1, GUARD>(p, static_cast<Args&&>(args)...);
+        else if (outf && !outs) Tail::template run<ACT, false, true, 0, GUARD>(p, static_cast<Args&&>(args)...);
+        else Tail::template run<ACT, false, true, 1, GUARD>(p, static_cast<Args&&>(args)...);
+    }
+}
+
+template <class Tail, int ACT, bool ROWMUL, typename... Args>
+F5_DEVICE void epi_with_guard(const GemmArgs& p, bool interior, Args&&... args) {
+    if (interior) epi_with_variant<Tail, ACT, false, ROWMUL>(p, static_cast<Args&&>(args)...);
+    else epi_with_variant<Tail, ACT, true, ROWMUL>(p, static_cast<Args&&>(args)...);
+}
+
+template <class Tail, bool ROWMUL, typename... Args>
+F5_DEVICE void epi_dispatch(const GemmArgs& p, bool interior, Args&&... args) {
+    if constexpr (ROWMUL) {
+        epi_with_guard<Tail, ACT_NONE, true>(p, interior, static_cast<Args&&>(args)...);
+    } else {
+        switch (p.act) {
+            case ACT_GELU_TANH: epi_with_guard<Tail, ACT_GELU_TANH, false>(p, interior, static_cast<Args&&>(args)...); break;
+            case ACT_GELU_ERF: epi_with_guard<Tail, ACT_GELU_ERF, false>(p, interior, static_cast<Args&&>(args)...); break;
+            case ACT_MISH: epi_with_guard<Tail, ACT_MISH, false>(p, interior, static_cast<Args&&>(args)...); break;
+            case ACT_SILU: epi_with_guard<Tail, ACT_SILU, false>(p, interior, static_cast<Args&&>(args)...); break;
+            default: epi_with_guard<Tail, ACT_NONE, false>(p, interior, static_cast<Args&&>(args)...); break;
+        }
+    }
+}
+
+// v = act(acc + bias); zero_row -> 0; v = v * mul + res, on 4 consecutive features of one row: the arithmetic of gemm5 / gemm6 in every
+// epilogue form (slab row phase, direct-from-accumulator), with explicit fma so that which kernel computed a row cannot change its bits.
+// The slab epilogue of gemm.h / gemm3.h below writes `v * m + rs` and leaves the contraction to the compiler: NOT the same bits -- without a
+// residual a masked row times a negative multiplier gives -0 + 0 = +0 there and -0 here, and the split-bf16 planes keep the sign.
+template <int ACT, bool RES>
+F5_DEVICE f32x4 g5_epi_value(f32x4 acc, f32x4 bias, f32x4 mul, f32x4 res, bool zero_row) {
+    f32x4 v = acc + bias;
+    if (ACT != ACT_NONE) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) v[e] = apply_act(v[e], ACT);
+    }
+    if (zero_row) v = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; e++) v[e] = RES ? __builtin_fmaf(v[e], mul[e], res[e]) : __fmul_rn(v[e], mul[e]);
+    return v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Slab epilogue of gemm.h / gemm3.h.
 // one 32 x WN slice staged in `stg` (fp32, row stride WN): generic epilogue, lane owns 4 columns of 32 / RPP rows.
 // RES / OUTF / OUTS (residual present, fp32 output, split-bf16 output) are compile-time so the hot variants carry no
 // per-element pointer tests; row pointers advance incrementally (one 64-bit add per row group instead of a 64-bit multiply).
@@ -247,24 +324,11 @@ F5_DEVICE void epi_qk_rows(const GemmArgs& p, const float* stg, int m_base, int 
 // the slab is wave-private, DS operations of one wave execute in order, so a wavefront-scope fence (compiler ordering
 // only, no instruction) is all that separates the transposing writes from the row reads.  The whole sub-tile is staged
 // at once so the accumulators are dead before the row phase (its residual prefetch needs their registers).
-template <int EPI, int TM, int TN, bool BAR = true>   // BAR = false: the slab does not alias the k-loop stages (gemm4.h), no workgroup barrier
-F5_DEVICE void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[TM][TN], float* slab, int m_wave, int n_wave, int n_blk, int lane,
-                              unsigned long long* dbg = nullptr) {
+template <int EPI, int TM, int TN>
+F5_DEVICE void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[TM][TN], float* slab, int m_wave, int n_wave, int n_blk, int lane) {
     constexpr int WN = TN * 32, ROWS = TM * 32;
-    unsigned long long dprev = 0;
-#define EPI_STAMP(IDX)                                                                               \
-    if (dbg) {                                                                                       \
-        unsigned long long t_;                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                           \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                  \
-        __builtin_amdgcn_sched_barrier(0);                                                           \
-        if ((IDX) >= 0) dbg[(IDX)] += t_ - dprev;                                                    \
-        dprev = t_;                                                                                  \
-    }
-    EPI_STAMP(-1);
     const int fr = lane & 31, fh = lane >> 5;
-    if (BAR) __syncthreads();
-    EPI_STAMP(0);
+    __syncthreads();
     if (EPI == EPI_QKV && n_blk >= 2 * p.D) {
         // V block: written transposed ([feature][token]) straight from the accumulators, 4 tokens = 8 bytes per store
 #pragma unroll
@@ -290,7 +354,6 @@ F5_DEVICE void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[TM][TN], float* sl
 #pragma unroll
             for (int g = 0; g < 16; g++) slab[(i * 32 + (g & 3) + 8 * (g >> 2) + 4 * fh) * WN + j * 32 + fr] = acc[i][j][g];
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    EPI_STAMP(1);
     if constexpr (EPI == EPI_GENERIC_ROWMUL) {
         epi_generic_rows<ACT_NONE, WN, ROWS, WN, true>(p, slab, m_wave, n_wave, lane);
     } else if (EPI == EPI_GENERIC) {
@@ -304,9 +367,6 @@ F5_DEVICE void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[TM][TN], float* sl
     } else {
         epi_qk_rows<WN, ROWS>(p, slab, m_wave, n_wave, lane);
     }
-    EPI_STAMP(2);
-    if (dbg) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); EPI_STAMP(3); }   // drain of the outstanding stores
-#undef EPI_STAMP
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

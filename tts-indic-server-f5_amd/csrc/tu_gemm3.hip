@@ -5,13 +5,13 @@
 hipError_t f5_launch_gemm3(int prec, int epi, int bn, const GemmArgs& a, int m_pad, int n_pad, hipStream_t st) {
     const bool qkv = epi == EPI_QKV;
     if (epi == EPI_GENERIC_ROWMUL) {
-        if (bn == 256) return prec == 3 ? launch_gemm3_t<3, EPI_GENERIC_ROWMUL, 0, 256>(a, m_pad, n_pad, st) : hipErrorInvalidValue;
+        if (bn == 256) return prec == 3 ? launch_gemm3_t<3, EPI_GENERIC_ROWMUL, 256>(a, m_pad, n_pad, st) : hipErrorInvalidValue;
         if (prec == 3) return launch_gemm3_t<3, EPI_GENERIC_ROWMUL>(a, m_pad, n_pad, st);
         if (prec == 2) return launch_gemm3_t<2, EPI_GENERIC_ROWMUL>(a, m_pad, n_pad, st);
         return launch_gemm3_t<1, EPI_GENERIC_ROWMUL>(a, m_pad, n_pad, st);
     }
     if (bn == 256) {
-        if (prec == 3) return qkv ? launch_gemm3_t<3, EPI_QKV, 0, 256>(a, m_pad, n_pad, st) : launch_gemm3_t<3, EPI_GENERIC, 0, 256>(a, m_pad, n_pad, st);
+        if (prec == 3) return qkv ? launch_gemm3_t<3, EPI_QKV, 256>(a, m_pad, n_pad, st) : launch_gemm3_t<3, EPI_GENERIC, 256>(a, m_pad, n_pad, st);
         return hipErrorInvalidValue;
     }
     if (prec == 3) return qkv ? launch_gemm3_t<3, EPI_QKV>(a, m_pad, n_pad, st) : launch_gemm3_t<3, EPI_GENERIC>(a, m_pad, n_pad, st);
