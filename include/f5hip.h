@@ -135,6 +135,25 @@ int f5hip_cfm_sample_span(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const
                           const int32_t* steps, const float* t_grids, const float* cfg_strength, const uint8_t* last,
                           float* out_dev, void* stream);
 
+/* f5hip_cfm_sample_span with one ODE method per unit as well: unit u is stepped by solver method[u] (host int32 [n_utt]: 0 euler, 1 midpoint,
+ * 2 rk4, the codes of f5hip_dit_set_ode_method) over its steps[u] >= 1 steps.  The handle's own method is ignored by this call and left
+ * unchanged.  `last` as in f5hip_cfm_sample_span; NULL = every unit ends (f5hip_cfm_sample_grids' result).
+ *   Unit u takes F_u = steps[u] * (1, 2 or 4) backbone forwards.  The units are laid out by F_u, descending, and the call runs max F_u
+ *   forwards: before forward f the layout shrinks to the units with F_u > f (counter "dit_rows"), and after it ONE launch steps every frame
+ *   by the rule and stage its unit is at -- the arithmetic of the one-method kernels, operation for operation.
+ *   The union of the units' time points, each by its own rule (Euler steps[u], midpoint 2 steps[u], RK4 3 steps[u] + 1; equal values once),
+ *   may hold at most 256 points.  RK4's fourth stage of a unit's last step is evaluated at its slice's last point.
+ * When all method[u] are equal the call IS f5hip_cfm_sample_span / _grids on a handle set to that method: same kernels, same bits.  With
+ * the shape-invariant attention mode a unit's result is what f5hip_cfm_sample_span / _grids gives it alone on a handle set to its method,
+ * bit for bit.  Every refusal (null `method`, a value outside 0..2, steps[u] < 1, the dur / kv_len / time-point limits) comes before the
+ * first launch. */
+int f5hip_cfm_sample_methods(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev,
+                             const uint8_t* cond_mask, const int32_t* text, int32_t nt_max, const float* y0_dev,
+                             const int32_t* steps, const float* t_grids, const float* cfg_strength,
+                             const int32_t* method /* host [n_utt], 0 euler / 1 midpoint / 2 rk4 */,
+                             const uint8_t* last /* as f5hip_cfm_sample_span; NULL = every unit ends */,
+                             float* out_dev, void* stream);
+
 /* The fixed-grid solver both sample calls use: replaces CFM(odeint_kwargs=dict(method=...)) (F/model/cfm.py:37-41,72,200; set from
  * load_model(ode_method=...), F/infer/utils_infer.py:251).  0 = "euler" (default): x += dt * v(t_i, x).  1 = "midpoint":
  * x += dt * v(t_i + dt / 2, x + dt / 2 * v(t_i, x)), two backbone evaluations per step, at most 64 steps per call.  2 = "rk4": torchdiffeq's
@@ -252,6 +271,16 @@ int f5hip_op_cfg_step(int32_t method, int32_t stage, int32_t U, int32_t mel, int
                       float dt, const int32_t* frame_unit_host, const float* unit_dt_host, int32_t n_units, int32_t n_act, float* k1_dev,
                       float* k2_dev, float* k3_dev, float* xs_dev, const uint8_t* final_flags_host, const float* cond_dev, float* out_dev,
                       void* stream);
+/* f5hip_op_cfg_mixed: one launch of the CFG combine + ODE update of a mixed-method sampler call (f5hip_cfm_sample_methods), in which
+ *   every frame is stepped by the rule of its unit.  Buffers as in f5hip_op_cfg_step (strengths per frame: cfg_frame_dev [U]; in place on
+ *   xstate_dev).  frame_unit_host int32 [U]; unit_op_host int32 / unit_dt_host fp32 [n_units] (host): per unit the op code and step size --
+ *   0 none (frame untouched), 1 Euler step, 2 midpoint half step (unit_dt holds dt / 2; xstate untouched, the next input goes to xs and
+ *   to the frame's rows of k1_dev), 3 midpoint full step, 4..7 RK4 stage 1..4 (slopes in k1_dev / k2_dev / k3_dev [U][mel]).  The
+ *   frames of units >= n_act are left as they are.  Per op code the result is f5hip_op_cfg_step's of that method / stage, bit for bit. */
+int f5hip_op_cfg_mixed(int32_t U, int32_t mel, int32_t rows, float* xstate_dev, const float* pred_dev, const int32_t* urow_c_host,
+                       const int32_t* urow_u_host, const float* cfg_frame_dev, const int32_t* frame_unit_host, const int32_t* unit_op_host,
+                       const float* unit_dt_host, int32_t n_units, int32_t n_act, float* k1_dev, float* k2_dev, float* k3_dev, float* xs_dev,
+                       void* stream);
 /* f5hip_op_row_tp: the time point of every row of a mixed-grid call, row_tp_host[r] = unit_tp_host[row_unit_host[r]] (all host int32;
  *   R rows, n_units units), computed by the sampler's kernel. */
 int f5hip_op_row_tp(int32_t R, const int32_t* row_unit_host, int32_t n_units, const int32_t* unit_tp_host, int32_t* row_tp_host,

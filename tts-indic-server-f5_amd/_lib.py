@@ -49,6 +49,8 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_cfm_sample_span": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "f5hip_cfm_sample_methods": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_dit_set_ode_method": (C.c_int, [C.c_void_p, C.c_int32]),
     "f5hip_dit_set_attention_shape_invariant": (C.c_int, [C.c_void_p, C.c_int32]),
     "f5hip_dit_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -70,6 +72,7 @@ SYMBOLS = {
                                             C.c_void_p]),
     "f5hip_op_cfg_step": (C.c_int, [C.c_int32] * 5 + [C.c_void_p] * 5 + [C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] +
                           [C.c_void_p] * 8),
+    "f5hip_op_cfg_mixed": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 8 + [C.c_int32, C.c_int32] + [C.c_void_p] * 5),
     "f5hip_op_row_tp": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_op_time_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "f5hip_op_joint_attention": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

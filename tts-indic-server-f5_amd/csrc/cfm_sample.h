@@ -1,5 +1,5 @@
-// The ODE loop of CFM.sample (F/model/cfm.py:160-204): f5hip_cfm_sample, _masked, _units, _grids and _span, every ODE method, driven by
-// ONE step loop (run_sampler).  Host orchestration only: the kernels are elementwise.h's.  Included at the end of f5hip.hip (same translation
+// The ODE loop of CFM.sample (F/model/cfm.py:160-204): f5hip_cfm_sample, _masked, _units, _grids, _span and _methods, every ODE method, driven
+// by ONE step loop (run_sampler).  Host orchestration only: the kernels are elementwise.h's.  Included at the end of f5hip.hip (same translation
 // unit: it drives setup_sequences, the precompute_* functions and forward_step).
 #pragma once
 
@@ -84,13 +84,20 @@ static int layout_units(f5hip_dit* m, const SampleArgs& a, const std::vector<int
 //   i * points + s of the table.
 //   Mixed grids (unit_steps): the union of the units' points, equal fp32 values once; utp[f][k] = point of forward f for the unit at layout
 //   position k (0 once its steps are done); udt[i][k] = dt_i and udt[max_steps + i][k] = dt_i / 2 of that unit.
+//   Mixed methods (unit_method as well): the union over every unit's stage times by its own rule; per forward f and layout position k the
+//   point utp[f][k], the op code uop[f][k] (CfgOp; CFG_OP_NONE once the unit's forwards are done) and the step size udt[f][k] (dt, or dt / 2
+//   for the midpoint rule's half step) of cfg_mixed_kernel.  max_forwards = the forwards of the call.
 struct TimePlan {
-    int max_steps = 0;
+    int max_steps = 0, max_forwards = 0;
     std::vector<float> pts, udt;
-    std::vector<int> utp;
+    std::vector<int> utp, uop;
 };
 
-static int plan_times(int method, const std::vector<int>& order, const float* t_grid, int steps, const int32_t* unit_steps, TimePlan& P) {
+// The forwards unit u of a mixed-method call takes
+static int unit_forwards(const int32_t* unit_steps, const int32_t* unit_method, int u) { return unit_steps[u] * kOdeRules[unit_method[u]].forwards; }
+
+static int plan_times(int method, const std::vector<int>& order, const float* t_grid, int steps, const int32_t* unit_steps, const int32_t* unit_method,
+                      TimePlan& P) {
     const OdeRule& rule = kOdeRules[method];
     float t[4];
     if (!unit_steps) {
@@ -121,6 +128,30 @@ static int plan_times(int method, const std::vector<int>& order, const float* t_
     size_t g0 = 0;
     std::vector<size_t> grid0(n);   // first point of every unit's grid in t_grid
     for (int u = 0; u < n; u++) { grid0[u] = g0; g0 += (size_t)unit_steps[u] + 1; }
+    if (unit_method) {
+        static const int kFirstOp[3] = {CFG_OP_EULER, CFG_OP_MID_HALF, CFG_OP_RK4_1};
+        P.max_forwards = unit_forwards(unit_steps, unit_method, order[0]);
+        P.utp.assign((size_t)P.max_forwards * n, 0);
+        P.uop.assign((size_t)P.max_forwards * n, CFG_OP_NONE);
+        P.udt.assign((size_t)P.max_forwards * n, 0.0f);
+        for (int k = 0; k < n; k++) {
+            const int u = order[k], mu = unit_method[u], fw = kOdeRules[mu].forwards;
+            const float* tg = t_grid + grid0[u];
+            for (int i = 0; i < unit_steps[u]; i++) {
+                const float dt = tg[i + 1] - tg[i];
+                stage_times(mu, tg[i], tg[i + 1], t);
+                for (int s = 0; s < fw; s++) {
+                    const size_t at = ((size_t)i * fw + s) * n + k;
+                    P.utp[at] = point(t[s]);
+                    P.uop[at] = kFirstOp[mu] + s;
+                    P.udt[at] = mu == 1 && s == 0 ? 0.5f * dt : dt;
+                }
+            }
+        }
+        if ((int)P.pts.size() > kMaxTimePoints)
+            return fail(-8, "cfm_sample_methods: the units' grids need %d distinct time points, at most %d per call", (int)P.pts.size(), kMaxTimePoints);
+        return 0;
+    }
     P.max_steps = unit_steps[order[0]];
     P.utp.assign((size_t)P.max_steps * per * n, 0);
     P.udt.assign((size_t)2 * P.max_steps * n, 0.0f);
@@ -139,12 +170,13 @@ static int plan_times(int method, const std::vector<int>& order, const float* t_
     return 0;
 }
 
-// The device tables of a mixed-grid call (in m->grid_meta): row_unit [R] | frame_unit [U] | utp | udt (floats) -- uploaded -- then row_tp [R]
-struct GridTables { const int *row_unit, *frame_unit, *utp; const float* udt; int* row_tp; };
+// The device tables of a mixed-grid call (in m->grid_meta): row_unit [R] | frame_unit [U] | utp | uop (mixed methods only) | udt (floats)
+// -- uploaded -- then row_tp [R]
+struct GridTables { const int *row_unit, *frame_unit, *utp, *uop; const float* udt; int* row_tp; };
 
 static int upload_grid_tables(f5hip_dit* m, const UnitLayout& L, const TimePlan& P, hipStream_t st, GridTables& T) {
     const int R = m->Rtot, U = L.n_frames, S = (int)L.seqs.size();
-    const size_t n_up = (size_t)R + U + P.utp.size() + P.udt.size(), need = n_up + R;
+    const size_t n_up = (size_t)R + U + P.utp.size() + P.uop.size() + P.udt.size(), need = n_up + R;
     if (need > m->grid_cap) {
         dev_free(m->grid_meta);
         m->grid_cap = 0;
@@ -158,12 +190,14 @@ static int upload_grid_tables(f5hip_dit* m, const UnitLayout& L, const TimePlan&
     }
     memcpy(&hb[R], L.frame_unit.data(), sizeof(int) * U);
     memcpy(&hb[(size_t)R + U], P.utp.data(), sizeof(int) * P.utp.size());
-    memcpy(&hb[(size_t)R + U + P.utp.size()], P.udt.data(), sizeof(float) * P.udt.size());
+    if (!P.uop.empty()) memcpy(&hb[(size_t)R + U + P.utp.size()], P.uop.data(), sizeof(int) * P.uop.size());
+    memcpy(&hb[(size_t)R + U + P.utp.size() + P.uop.size()], P.udt.data(), sizeof(float) * P.udt.size());
     CK(m->up_grid.upload(m->grid_meta, hb.data(), sizeof(int) * n_up, st));
     T.row_unit = m->grid_meta;
     T.frame_unit = T.row_unit + R;
     T.utp = T.frame_unit + U;
-    T.udt = reinterpret_cast<const float*>(T.utp + P.utp.size());
+    T.uop = T.utp + P.utp.size();
+    T.udt = reinterpret_cast<const float*>(T.uop + P.uop.size());
     T.row_tp = m->grid_meta + n_up;
     return 0;
 }
@@ -215,6 +249,12 @@ static int cfg_stage(f5hip_dit* m, int method, int stage, int f0, const CfgStep&
     return 0;
 }
 
+// The CFG combine and ODE update after one forward of a mixed-method call: every frame by its unit's op code and step size for this forward
+static void launch_cfg_mixed(const CfgBufs& b, int f0, const int* frame_unit, const int* unit_op, const float* unit_dt, int n_act, hipStream_t st) {
+    hipLaunchKernelGGL(cfg_mixed_kernel, dim3(f0), dim3(128), 0, st, b.xstate, b.mel, f0, b.pred, 128, b.urow_c, b.urow_u, b.frame_cfg, b.k1, b.k2, b.k3,
+                       b.xs.hi, b.xs.lo, 128, frame_unit, unit_op, unit_dt, n_act);
+}
+
 // Restores the handle's full layout and per-call modulation after a sampler call, however it ends (a mixed-grid call shrinks them)
 struct GridScope {
     f5hip_dit* m;
@@ -230,18 +270,24 @@ struct GridScope {
 // modulation consumers read their vectors per row (m->d_row_tp; forward_step with ti = 0).
 // a.last (f5hip_cfm_sample_span): the grids are spans of longer ones and y0 is the state so far; the step loop is the same, and the final
 // select keeps the raw state of every frame of a unit that does not end here (the per-frame flags of the metadata upload: layout_units).
-static int run_sampler(f5hip_dit* m, const SampleArgs& a, const float* t_grid, int steps, const int32_t* unit_steps, float cfg_strength,
-                       const float* cfg_unit) {
-    const int n = a.n_utt, method = m->ode_method, per = kOdeRules[method].forwards;
+// `method`: the solver of the call.  unit_method (f5hip_cfm_sample_methods; with unit_steps and cfg_unit, `method` unused): unit u steps by
+// rule unit_method[u], F_u = unit_steps[u] * forwards of its rule.  The units are laid out by F_u, descending (stable), so those still
+// running at forward f are a prefix of the layout; the loop runs over the forwards, f = 0 .. max F_u - 1: shrink to the active prefix,
+// row_tp_kernel, one forward, ONE cfg_mixed_kernel launch that steps every frame by its unit's op code for this forward (TimePlan).
+static int run_sampler(f5hip_dit* m, const SampleArgs& a, int method, const float* t_grid, int steps, const int32_t* unit_steps, float cfg_strength,
+                       const float* cfg_unit, const int32_t* unit_method = nullptr) {
+    const int n = a.n_utt, per = kOdeRules[method].forwards;
     std::vector<int> order(n);
     for (int u = 0; u < n; u++) order[u] = u;
-    if (unit_steps) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return unit_steps[x] > unit_steps[y]; });
+    if (unit_method)
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return unit_forwards(unit_steps, unit_method, x) > unit_forwards(unit_steps, unit_method, y); });
+    else if (unit_steps) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return unit_steps[x] > unit_steps[y]; });
     ProfScope prof_scope(m->prof);
     hipStream_t st = (hipStream_t)a.stream;
     UnitLayout L;
     TimePlan P;
     CK(layout_units(m, a, order, cfg_strength, cfg_unit, L));
-    CK(plan_times(method, order, t_grid, steps, unit_steps, P));   // (every refusal of a grid comes before the first launch)
+    CK(plan_times(method, order, t_grid, steps, unit_steps, unit_method, P));   // (every refusal of a grid comes before the first launch)
     const int mel = m->cfg.mel_dim, U = L.n_frames;
     CK(setup_sequences(m, L.seqs, U, a.text, a.nt_max, a.cond_mask, st, cfg_unit ? L.frame_cfg.data() : nullptr, a.last ? L.frame_final.data() : nullptr));
     GridScope scope{m};
@@ -256,6 +302,20 @@ static int run_sampler(f5hip_dit* m, const SampleArgs& a, const float* t_grid, i
 
     m->d_row_tp = T.row_tp;
     int n_act = n;
+    for (int f = 0; f < P.max_forwards; f++) {   // mixed methods (max_steps is 0: the loop over the steps below does not run)
+        while (unit_forwards(unit_steps, unit_method, order[n_act - 1]) <= f) n_act--;
+        const int s_act = L.seq_end[n_act - 1];
+        m->M = m->h_seq_row0[s_act]; m->Mc = m->h_seqc_row0[s_act] - m->row_c0; m->n_seq = s_act;
+        prof_begin(PROF_OTHER, st);
+        hipLaunchKernelGGL(row_tp_kernel, dim3((m->Rtot + 255) / 256), dim3(256), 0, st, T.row_unit, T.utp + (size_t)f * n, m->Rtot, T.row_tp);
+        prof_end(PROF_OTHER, st);
+        CKL("row_tp");
+        CK(forward_step(m, 0, -1, st));
+        prof_begin(PROF_OTHER, st);
+        launch_cfg_mixed(cfg_bufs(m), U, T.frame_unit, T.uop + (size_t)f * n, T.udt + (size_t)f * n, n_act, st);
+        prof_end(PROF_OTHER, st);
+        CKL("cfg mixed");
+    }
     for (int i = 0; i < P.max_steps; i++) {
         CfgStep full{cfg_strength, 0.0f, nullptr, nullptr, 0}, half = full;
         if (unit_steps) {
@@ -285,35 +345,46 @@ static int run_sampler(f5hip_dit* m, const SampleArgs& a, const float* t_grid, i
 }
 
 // The calls whose units share one grid
-static int sample_one_grid(f5hip_dit* m, const SampleArgs& a, const float* t_grid, int32_t steps, float cfg_strength, const float* cfg_unit) {
+static int sample_one_grid(f5hip_dit* m, const SampleArgs& a, int method, const float* t_grid, int32_t steps, float cfg_strength, const float* cfg_unit) {
     if (!m || !m->finalized) return fail(-1, "model not finalized");
     if (!a.ok() || !t_grid || steps <= 0) return fail(-1, "cfm_sample: bad argument");
-    return run_sampler(m, a, t_grid, steps, nullptr, cfg_strength, cfg_unit);
+    return run_sampler(m, a, method, t_grid, steps, nullptr, cfg_strength, cfg_unit);
 }
 
 int f5hip_cfm_sample(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const float* cond_dev, const uint8_t* cond_mask,
                      const int32_t* text, int32_t nt_max, const float* y0_dev, const float* t_grid, int32_t steps,
                      float cfg_strength, float* out_dev, void* stream) {
-    return sample_one_grid(m, {n_utt, dur, nullptr, cond_dev, cond_mask, text, nt_max, y0_dev, out_dev, stream}, t_grid, steps, cfg_strength, nullptr);
+    return sample_one_grid(m, {n_utt, dur, nullptr, cond_dev, cond_mask, text, nt_max, y0_dev, out_dev, stream}, m ? m->ode_method : 0, t_grid, steps, cfg_strength, nullptr);
 }
 
 int f5hip_cfm_sample_masked(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
                             const int32_t* text, int32_t nt_max, const float* y0_dev, const float* t_grid, int32_t steps,
                             float cfg_strength, float* out_dev, void* stream) {
-    return sample_one_grid(m, {n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, out_dev, stream}, t_grid, steps, cfg_strength, nullptr);
+    return sample_one_grid(m, {n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, out_dev, stream}, m ? m->ode_method : 0, t_grid, steps, cfg_strength, nullptr);
 }
 
 int f5hip_cfm_sample_units(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
                            const int32_t* text, int32_t nt_max, const float* y0_dev, const float* t_grid, int32_t steps,
                            const float* cfg_strength, float* out_dev, void* stream) {
     if (!cfg_strength) return fail(-1, "cfm_sample_units: cfg_strength is null");
-    return sample_one_grid(m, {n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, out_dev, stream}, t_grid, steps, 0.0f, cfg_strength);
+    return sample_one_grid(m, {n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, out_dev, stream}, m ? m->ode_method : 0, t_grid, steps, 0.0f, cfg_strength);
 }
 
-// The calls with one grid per unit: one grid for all is f5hip_cfm_sample_units' call, kernels and results
-static int sample_grids(const char* name, f5hip_dit* m, const SampleArgs& a, const int32_t* steps, const float* t_grids, const float* cfg_strength) {
+// The calls with one grid per unit: one grid for all is f5hip_cfm_sample_units' call, kernels and results.  unit_method null: every unit steps
+// by the handle's solver; else by its own (f5hip_cfm_sample_methods) -- all equal is the call with that solver, the mixed loop otherwise.
+static int sample_grids(const char* name, f5hip_dit* m, const SampleArgs& a, const int32_t* steps, const float* t_grids, const float* cfg_strength,
+                        const int32_t* unit_method = nullptr) {
     if (!m || !m->finalized) return fail(-1, "model not finalized");
     if (!a.ok() || !steps || !t_grids || !cfg_strength) return fail(-1, "%s: bad argument", name);
+    int method = m->ode_method;
+    if (unit_method) {
+        bool one_method = true;
+        for (int u = 0; u < a.n_utt; u++) {
+            if (unit_method[u] < 0 || unit_method[u] > 2) return fail(-1, "%s: method[%d] = %d (0 euler, 1 midpoint, 2 rk4)", name, u, unit_method[u]);
+            one_method = one_method && unit_method[u] == unit_method[0];
+        }
+        if (one_method) { method = unit_method[0]; unit_method = nullptr; }
+    }
     bool one_grid = true;
     size_t g0 = 0;
     for (int u = 0; u < a.n_utt; u++) {
@@ -321,8 +392,9 @@ static int sample_grids(const char* name, f5hip_dit* m, const SampleArgs& a, con
         one_grid = one_grid && steps[u] == steps[0] && !memcmp(t_grids + g0, t_grids, sizeof(float) * ((size_t)steps[0] + 1));
         g0 += (size_t)steps[u] + 1;
     }
-    if (one_grid) return sample_one_grid(m, a, t_grids, steps[0], 0.0f, cfg_strength);
-    return run_sampler(m, a, t_grids, 0, steps, 0.0f, cfg_strength);
+    if (unit_method) return run_sampler(m, a, 0, t_grids, 0, steps, 0.0f, cfg_strength, unit_method);
+    if (one_grid) return sample_one_grid(m, a, method, t_grids, steps[0], 0.0f, cfg_strength);
+    return run_sampler(m, a, method, t_grids, 0, steps, 0.0f, cfg_strength);
 }
 
 int f5hip_cfm_sample_grids(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
@@ -336,4 +408,12 @@ int f5hip_cfm_sample_span(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const
                           const float* cfg_strength, const uint8_t* last, float* out_dev, void* stream) {
     if (!last) return fail(-1, "cfm_sample_span: last is null");
     return sample_grids("cfm_sample_span", m, {n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, out_dev, stream, last}, steps, t_grids, cfg_strength);
+}
+
+int f5hip_cfm_sample_methods(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev, const uint8_t* cond_mask,
+                             const int32_t* text, int32_t nt_max, const float* y0_dev, const int32_t* steps, const float* t_grids,
+                             const float* cfg_strength, const int32_t* method, const uint8_t* last, float* out_dev, void* stream) {
+    if (!method) return fail(-1, "cfm_sample_methods: method is null");
+    return sample_grids("cfm_sample_methods", m, {n_utt, dur, kv_len, cond_dev, cond_mask, text, nt_max, y0_dev, out_dev, stream, last}, steps, t_grids,
+                        cfg_strength, method);
 }

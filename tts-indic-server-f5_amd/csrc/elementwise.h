@@ -134,6 +134,56 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* x, int ldx
 // the scalar `cfg`; the arithmetic is the same, so the scalar instantiation is the kernel the single-strength entry points always ran.
 // kUnitDt (f5hip_cfm_sample_grids): the step of frame u is unit_dt[frame_unit[u]], and the frames of units >= n_act (their steps are done)
 // are left as they are.
+// The arithmetic of the CFG / ODE kernels below, one helper per piece: cfg_euler_kernel, cfg_rk4_stage_kernel and cfg_mixed_kernel are built
+// from the same expressions, so a frame gets the same bits whichever of them steps it.
+// v = p_c + (p_c - p_u) * cfg for channel c of a frame (v = p_c without an unconditional row)
+__device__ __forceinline__ float cfg_velocity(const float* pred, int ldp, int rc, int ru, int c, float cfg) {
+    const float pc = pred[(size_t)rc * ldp + c];
+    float v = pc;
+    if (ru >= 0) v = pc + (pc - pred[(size_t)ru * ldp + c]) * cfg;
+    return v;
+}
+
+// xout[i] = xbase[i] + dt * v: the Euler step (xout == xbase), the midpoint rule's half step (xout a scratch state) and its full step
+__device__ __forceinline__ float euler_update(float* xout, const float* xbase, size_t i, float dt, float v) {
+    const float xn = xbase[i] + dt * v;
+    xout[i] = xn;
+    return xn;
+}
+
+// Stage `stage` (1..4) of the RK4 step on element i (see cfg_rk4_stage_kernel): keeps k_stage, returns the next forward's input (stage 4: y1,
+// written to xstate)
+__device__ __forceinline__ float rk4_stage_update(float* xstate, float* k1, float* k2, float* k3, size_t i, int stage, float dt, float v) {
+    const float y0 = xstate[i];
+    float xn;
+    if (stage == 1) {
+        k1[i] = v;
+        xn = y0 + dt * v * (1.0f / 3.0f);
+    } else if (stage == 2) {
+        k2[i] = v;
+        xn = y0 + dt * (v - k1[i] * (1.0f / 3.0f));
+    } else if (stage == 3) {
+        k3[i] = v;
+        xn = y0 + dt * (k1[i] - k2[i] + v);
+    } else {
+        xn = y0 + (k1[i] + 3.0f * (k2[i] + k3[i]) + v) * dt * 0.125f;
+        xstate[i] = xn;
+    }
+    return xn;
+}
+
+// split(xn) into channel c of both rows of the frame in the split-bf16 copy of x
+__device__ __forceinline__ void store_x_split(__bf16* xs_hi, __bf16* xs_lo, int ldx, int rc, int ru, int c, float xn) {
+    __bf16 hi, lo;
+    split_bf16(xn, hi, lo);
+    xs_hi[(size_t)rc * ldx + c] = hi;
+    xs_lo[(size_t)rc * ldx + c] = lo;
+    if (ru >= 0) {
+        xs_hi[(size_t)ru * ldx + c] = hi;
+        xs_lo[(size_t)ru * ldx + c] = lo;
+    }
+}
+
 template <bool kFrameCfg, bool kUnitDt = false>
 __global__ __launch_bounds__(128) void cfg_euler_kernel(float* xout /*[U][mel]*/, const float* xbase, int mel, int U, const float* pred,
                                                         int ldp, const int* urow_c, const int* urow_u, float cfg, const float* cfg_frame,
@@ -149,19 +199,9 @@ __global__ __launch_bounds__(128) void cfg_euler_kernel(float* xout /*[U][mel]*/
         dt = unit_dt[un];
     }
     const int rc = urow_c[u], ru = urow_u[u];
-    const float pc = pred[(size_t)rc * ldp + c];
-    float v = pc;
-    if (ru >= 0) v = pc + (pc - pred[(size_t)ru * ldp + c]) * (kFrameCfg ? cfg_frame[u] : cfg);
-    const float xn = xbase[(size_t)u * mel + c] + dt * v;
-    xout[(size_t)u * mel + c] = xn;
-    __bf16 hi, lo;
-    split_bf16(xn, hi, lo);
-    xs_hi[(size_t)rc * ldx + c] = hi;
-    xs_lo[(size_t)rc * ldx + c] = lo;
-    if (ru >= 0) {
-        xs_hi[(size_t)ru * ldx + c] = hi;
-        xs_lo[(size_t)ru * ldx + c] = lo;
-    }
+    const float v = cfg_velocity(pred, ldp, rc, ru, c, kFrameCfg ? cfg_frame[u] : cfg);
+    const float xn = euler_update(xout, xbase, (size_t)u * mel + c, dt, v);
+    store_x_split(xs_hi, xs_lo, ldx, rc, ru, c, xn);
 }
 
 // CFG combine + one stage of the fixed-grid RK4 step (torchdiffeq method="rk4": rk4_alt_step_func, the 3/8 rule), launched after the
@@ -187,33 +227,47 @@ __global__ __launch_bounds__(128) void cfg_rk4_stage_kernel(float* xstate /*[U][
         dt = unit_dt[un];
     }
     const int rc = urow_c[u], ru = urow_u[u];
-    const float pc = pred[(size_t)rc * ldp + c];
-    float v = pc;
-    if (ru >= 0) v = pc + (pc - pred[(size_t)ru * ldp + c]) * (kFrameCfg ? cfg_frame[u] : cfg);
+    const float v = cfg_velocity(pred, ldp, rc, ru, c, kFrameCfg ? cfg_frame[u] : cfg);
+    const float xn = rk4_stage_update(xstate, k1, k2, k3, (size_t)u * mel + c, stage, dt, v);
+    store_x_split(xs_hi, xs_lo, ldx, rc, ru, c, xn);
+}
+
+// What cfg_mixed_kernel does to the frames of a unit after one forward of a mixed-method call (f5hip_cfm_sample_methods)
+enum CfgOp : int {
+    CFG_OP_NONE = 0,       // the unit's steps are done: its frames are left as they are
+    CFG_OP_EULER = 1,      // x += dt v
+    CFG_OP_MID_HALF = 2,   // midpoint, first forward: xmid = x + (dt / 2) v (the table holds dt / 2), x untouched
+    CFG_OP_MID_FULL = 3,   // midpoint, second forward: x += dt v
+    CFG_OP_RK4_1 = 4,      // RK4 stage 1 .. 4: CFG_OP_RK4_1 + stage - 1
+    CFG_OP_COUNT = 8
+};
+
+// The CFG combine + ODE update of a call whose units use different solvers: one launch after every forward, each frame stepped by the
+// rule of its unit.  unit_op / unit_dt [n units]: this forward's op code (CfgOp) and step size per layout position, read through
+// frame_unit[u]; the op is uniform over a block (one frame), so no wave diverges.  Frames of units >= n_act, or with CFG_OP_NONE, are left
+// as they are.  Strengths per frame (cfg_frame).  k1 is the midpoint rule's scratch state as well as RK4's first slope, indexed by frame like
+// k2 / k3: the frames of different units are disjoint, so units of different methods share the buffers.  Per op the arithmetic is that of
+// cfg_euler_kernel<true, true> / cfg_rk4_stage_kernel<true, true> (the helpers above): the same bits.
+__global__ __launch_bounds__(128) void cfg_mixed_kernel(float* xstate /*[U][mel]*/, int mel, int U, const float* pred, int ldp, const int* urow_c,
+                                                        const int* urow_u, const float* cfg_frame, float* k1, float* k2, float* k3,
+                                                        __bf16* xs_hi, __bf16* xs_lo, int ldx, const int* frame_unit, const int* unit_op,
+                                                        const float* unit_dt, int n_act) {
+    const int u = blockIdx.x;
+    if (u >= U) return;
+    const int c = threadIdx.x;
+    if (c >= mel) return;
+    const int un = frame_unit[u];
+    if (un >= n_act) return;
+    const int op = unit_op[un];
+    if (op <= CFG_OP_NONE || op >= CFG_OP_COUNT) return;
+    const float dt = unit_dt[un];
+    const int rc = urow_c[u], ru = urow_u[u];
+    const float v = cfg_velocity(pred, ldp, rc, ru, c, cfg_frame[u]);
     const size_t i = (size_t)u * mel + c;
-    const float y0 = xstate[i];
     float xn;
-    if (stage == 1) {
-        k1[i] = v;
-        xn = y0 + dt * v * (1.0f / 3.0f);
-    } else if (stage == 2) {
-        k2[i] = v;
-        xn = y0 + dt * (v - k1[i] * (1.0f / 3.0f));
-    } else if (stage == 3) {
-        k3[i] = v;
-        xn = y0 + dt * (k1[i] - k2[i] + v);
-    } else {
-        xn = y0 + (k1[i] + 3.0f * (k2[i] + k3[i]) + v) * dt * 0.125f;
-        xstate[i] = xn;
-    }
-    __bf16 hi, lo;
-    split_bf16(xn, hi, lo);
-    xs_hi[(size_t)rc * ldx + c] = hi;
-    xs_lo[(size_t)rc * ldx + c] = lo;
-    if (ru >= 0) {
-        xs_hi[(size_t)ru * ldx + c] = hi;
-        xs_lo[(size_t)ru * ldx + c] = lo;
-    }
+    if (op >= CFG_OP_RK4_1) xn = rk4_stage_update(xstate, k1, k2, k3, i, op - CFG_OP_RK4_1 + 1, dt, v);
+    else xn = euler_update(op == CFG_OP_MID_HALF ? k1 : xstate, xstate, i, dt, v);
+    store_x_split(xs_hi, xs_lo, ldx, rc, ru, c, xn);
 }
 
 // out = cond_mask ? cond : x  (F/model/cfm.py:204); one block per utterance frame

@@ -6,6 +6,7 @@
 //   torch.ops.f5hip.cfm_sample_units(handle, dur, kv_len?, cond, cond_mask, text, y0, t_grid, cfg_strength) -> Tensor  (one strength per unit)
 //   torch.ops.f5hip.cfm_sample_grids(handle, dur, kv_len?, cond, cond_mask, text, y0, steps, t_grids, cfg_strength) -> Tensor  (one grid per unit)
 //   torch.ops.f5hip.cfm_sample_span(handle, dur, kv_len?, cond, cond_mask, text, y0, steps, t_grids, cfg_strength, last) -> Tensor  (resumable span)
+//   torch.ops.f5hip.cfm_sample_methods(handle, dur, kv_len?, cond, cond_mask, text, y0, steps, t_grids, cfg_strength, method, last?) -> Tensor  (one ODE method per unit)
 //   torch.ops.f5hip.vocos_decode(handle, mel) -> Tensor                                                          F/infer/utils_infer.py:472
 //   torch.ops.f5hip.vocos_decode_ragged(handle, mel, frames, channels, hop_length) -> Tensor (packed)                F/infer/utils_infer.py:472
 //   torch.ops.f5hip.bigvgan_forward(handle, mel, total_upsample) -> Tensor                                       F/infer/utils_infer.py:474
@@ -125,6 +126,19 @@ at::Tensor cfm_sample_span(int64_t handle, const at::Tensor& dur, const c10::opt
                       last.data_ptr<uint8_t>());
 }
 
+// cfm_sample_span with one ODE method per unit (f5hip_cfm_sample_methods): method [b] int32 host, 0 euler / 1 midpoint / 2 rk4; the handle's own
+// method is not read.  last [b] uint8 host as in cfm_sample_span, or None: every unit ends with the call.
+at::Tensor cfm_sample_methods(int64_t handle, const at::Tensor& dur, const c10::optional<at::Tensor>& kv_len, const at::Tensor& cond, const at::Tensor& cond_mask,
+                              const at::Tensor& text, const at::Tensor& y0, const at::Tensor& steps, const at::Tensor& t_grids, const at::Tensor& cfg_strength,
+                              const at::Tensor& method, const c10::optional<at::Tensor>& last) {
+    const SampleArgs a{dur, cond, cond_mask, text, y0, kv_len};
+    check_unit_grids("cfm_sample_methods", a, steps, t_grids, cfg_strength);
+    check_per_unit("cfm_sample_methods", method, at::kInt, "method", a);
+    if (last.has_value()) check_per_unit("cfm_sample_methods", *last, at::kByte, "last", a);
+    return run_sample("f5hip_cfm_sample_methods", f5hip_cfm_sample_methods, handle, a, steps.data_ptr<int32_t>(), t_grids.data_ptr<float>(),
+                      cfg_strength.data_ptr<float>(), method.data_ptr<int32_t>(), last.has_value() ? last->data_ptr<uint8_t>() : (const uint8_t*)nullptr);
+}
+
 at::Tensor vocos_decode(int64_t handle, const at::Tensor& mel, int64_t hop_length) {
     check_dev_f32(mel, "mel");
     TORCH_CHECK(mel.dim() == 3, "f5hip::vocos_decode: mel [b, 100, T]");
@@ -190,6 +204,7 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("cfm_sample_units(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor t_grid, Tensor cfg_strength) -> Tensor", &cfm_sample_units);
     m.def("cfm_sample_grids(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor steps, Tensor t_grids, Tensor cfg_strength) -> Tensor", &cfm_sample_grids);
     m.def("cfm_sample_span(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor steps, Tensor t_grids, Tensor cfg_strength, Tensor last) -> Tensor", &cfm_sample_span);
+    m.def("cfm_sample_methods(int handle, Tensor dur, Tensor? kv_len, Tensor cond, Tensor cond_mask, Tensor text, Tensor y0, Tensor steps, Tensor t_grids, Tensor cfg_strength, Tensor method, Tensor? last) -> Tensor", &cfm_sample_methods);
     m.def("vocos_decode(int handle, Tensor mel, int hop_length) -> Tensor", &vocos_decode);
     m.def("vocos_decode_ragged(int handle, Tensor mel, Tensor frames, int channels, int hop_length) -> Tensor", &vocos_decode_ragged);
     m.def("bigvgan_forward(int handle, Tensor mel, int total_upsample) -> Tensor", &bigvgan_forward);

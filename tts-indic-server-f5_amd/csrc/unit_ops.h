@@ -741,6 +741,47 @@ extern "C" int f5hip_op_cfg_step(int32_t method, int32_t stage, int32_t U, int32
     return 0;
 }
 
+// One launch of cfg_mixed_kernel (launch_cfg_mixed, what a mixed-method sampler call launches after every forward) on the caller's buffers:
+// buffers as in f5hip_op_cfg_step; frame_unit_host [U], unit_op_host / unit_dt_host [n_units] the op code (CfgOp, 0..7) and step size of
+// every unit for this forward; the frames of units >= n_act, or with op 0, are left as they are.  k1_dev is the midpoint rule's xmid too.
+extern "C" int f5hip_op_cfg_mixed(int32_t U, int32_t mel, int32_t rows, float* xstate_dev, const float* pred_dev, const int32_t* urow_c_host,
+                                  const int32_t* urow_u_host, const float* cfg_frame_dev, const int32_t* frame_unit_host, const int32_t* unit_op_host,
+                                  const float* unit_dt_host, int32_t n_units, int32_t n_act, float* k1_dev, float* k2_dev, float* k3_dev, float* xs_dev,
+                                  void* stream) {
+    if (U <= 0 || mel <= 0 || mel > 128 || rows <= 0 || !xstate_dev || !pred_dev || !urow_c_host || !urow_u_host || !cfg_frame_dev || !frame_unit_host ||
+        !unit_op_host || !unit_dt_host || !k1_dev || !k2_dev || !k3_dev || !xs_dev)
+        return fail(-1, "op_cfg_mixed: bad argument (mel <= 128, every buffer)");
+    if (n_units <= 0 || n_act < 0 || n_act > n_units) return fail(-1, "op_cfg_mixed: needs 0 <= n_act <= n_units");
+    for (int k = 0; k < n_units; k++)
+        if (unit_op_host[k] < CFG_OP_NONE || unit_op_host[k] >= CFG_OP_COUNT) return fail(-1, "op_cfg_mixed: unit_op[%d] = %d (0..7)", k, unit_op_host[k]);
+    for (int u = 0; u < U; u++)
+        if (urow_c_host[u] < 0 || urow_c_host[u] >= rows || urow_u_host[u] < -1 || urow_u_host[u] >= rows || frame_unit_host[u] < 0 ||
+            frame_unit_host[u] >= n_units)
+            return fail(-1, "op_cfg_mixed: frame %d: row or unit out of range", u);
+    hipStream_t st = (hipStream_t)stream;
+    OpBufs b;
+    const size_t n = (size_t)rows * 128;
+    Plane2 xs;
+    xs.hi = b.get<__bf16>(n); xs.lo = b.get<__bf16>(n);
+    int* meta = b.get<int>((size_t)3 * U + 2 * (size_t)n_units);   // urow_c | urow_u | frame_unit | unit_op | unit_dt (floats)
+    if (!xs.hi || !xs.lo || !meta) return fail(-5, "op_cfg_mixed: hipMalloc");
+    std::vector<int> hm((size_t)3 * U + 2 * (size_t)n_units, 0);
+    for (int u = 0; u < U; u++) { hm[u] = urow_c_host[u]; hm[U + u] = urow_u_host[u]; hm[2 * (size_t)U + u] = frame_unit_host[u]; }
+    std::copy(unit_op_host, unit_op_host + n_units, hm.begin() + 3 * (size_t)U);
+    memcpy(&hm[3 * (size_t)U + n_units], unit_dt_host, sizeof(float) * n_units);
+    if (upload_sync(st, meta, hm) != hipSuccess) return fail(-6, "op_cfg_mixed: upload");
+    hipLaunchKernelGGL(split_rows_kernel, dim3(rows), dim3(256), 0, st, (const float*)xs_dev, 128, 128, rows, (const int*)nullptr, xs.hi, xs.lo, 128, 0);
+    CKL("op_cfg_mixed split");
+    const CfgBufs cb{xstate_dev, k1_dev, k2_dev, k3_dev, pred_dev, meta, meta + U, cfg_frame_dev, xs, mel};
+    const int* uop = meta + 3 * (size_t)U;
+    launch_cfg_mixed(cb, U, meta + 2 * (size_t)U, uop, reinterpret_cast<const float*>(uop + n_units), n_act, st);
+    CKL("op_cfg_mixed");
+    hipLaunchKernelGGL(op_planes_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, xs.hi, xs.lo, 0, n, xs_dev);
+    CKL("op_cfg_mixed planes");
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_cfg_mixed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
 // row_tp_kernel of a mixed-grid call: row_tp_host[r] = unit_tp_host[row_unit_host[r]] for R rows of n_units units (all host int32)
 extern "C" int f5hip_op_row_tp(int32_t R, const int32_t* row_unit_host, int32_t n_units, const int32_t* unit_tp_host, int32_t* row_tp_host, void* stream) {
     if (R <= 0 || n_units <= 0 || !row_unit_host || !unit_tp_host || !row_tp_host) return fail(-1, "op_row_tp: bad argument");

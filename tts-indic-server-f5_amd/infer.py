@@ -236,15 +236,16 @@ def load_wav(src):
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print,
                   progress=None, target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step,
                   cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, speed=speed,
-                  fix_duration=fix_duration, device=None, seed=None):
+                  fix_duration=fix_duration, device=None, seed=None, ode_method=None):
     """F/infer/utils_infer.py:357-400.  `seed` (not in the reference's signature): the request's noise comes from its own CPU generator
-    (`request_generator`) instead of the global one."""
+    (`request_generator`) instead of the global one.  `ode_method` (neither): "euler", "midpoint" or "rk4" for this request instead of the
+    model object's solver."""
     audio, sr = ref_audio if isinstance(ref_audio, tuple) else load_wav(ref_audio)
     gen_text_batches = request_chunks(ref_text, audio.shape[-1] / sr, gen_text)
     return infer_batch_process((audio, sr), ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type=mel_spec_type,
                                progress=progress, target_rms=target_rms, cross_fade_duration=cross_fade_duration,
                                nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
-                               speed=speed, fix_duration=fix_duration, device=device, seed=seed)
+                               speed=speed, fix_duration=fix_duration, device=device, seed=seed, ode_method=ode_method)
 
 
 def request_chunks(ref_text, ref_seconds, gen_text):
@@ -257,7 +258,7 @@ def request_chunks(ref_text, ref_seconds, gen_text):
 def infer_process_stream(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print,
                          progress=None, target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step,
                          cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, speed=speed,
-                         fix_duration=fix_duration, device=None, seed=None):
+                         fix_duration=fix_duration, device=None, seed=None, ode_method=None):
     """`infer_process` as a generator of float32 pieces at 24 kHz whose concatenation is `infer_process`'s wave (as float32).
 
     The text is chunked exactly as `infer_process` does; chunk 0 is sampled and vocoded alone and its stable samples are yielded, then
@@ -268,7 +269,7 @@ def infer_process_stream(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_
     request's one generator (the remaining chunks after the first chunk's draws), so the pieces equal `infer_process(..., seed=seed)`."""
     audio, sr = ref_audio if isinstance(ref_audio, tuple) else load_wav(ref_audio)
     voice, units = _plan_request((audio, sr), ref_text, gen_text, target_rms, speed, fix_duration, device, text_to_tokens)
-    knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
+    knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, ode_method=ode_method)
     gen = request_generator(seed)
     joiner = StreamJoiner(cross_fade_duration)
     for part in (units[:1], units[1:]):
@@ -414,18 +415,23 @@ def request_generator(seed):
     return torch.Generator().manual_seed(int(seed))
 
 
-def _sample_units(model_obj, cond, audios, units, steps, cfg_strength, sway_sampling_coef, generators):
+def _sample_units(model_obj, cond, audios, units, steps, cfg_strength, sway_sampling_coef, generators, ode_method=None):
     """The mels [frames_i, mel] (reference frames included) of `units`: ONE `sample_units` call when the model object offers it (`cond`: the
     prompts, one tensor for all units or one per unit; `generators`, one or None per unit, is handed on only when a unit has one), else the
-    reference's batch-1 `.sample()` unit by unit on the waves `audios`.  Each knob: one value or one per unit."""
+    reference's batch-1 `.sample()` unit by unit on the waves `audios`.  Each knob: one value or one per unit.  `ode_method` (one name, or
+    one name or None per unit) is handed on only when a unit names a solver."""
+    methods = ode_method if isinstance(ode_method, list) else [ode_method] * len(units)
     if hasattr(model_obj, "sample_units"):
         extra = dict(generators=list(generators)) if any(g is not None for g in generators) else {}
+        if any(name is not None for name in methods):
+            extra["ode_method"] = ode_method
         return model_obj.sample_units(cond, units, steps=steps, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, **extra)
     if any(g is not None for g in generators):
         raise ValueError("a per-request seed needs a model object with sample_units (F5HipModel, ShardedSampler)")
     per_unit = [v if isinstance(v, list) else [v] * len(units) for v in (steps, cfg_strength, sway_sampling_coef)]
-    return [model_obj.sample(cond=audio, text=[tokens], duration=frames, steps=n, cfg_strength=cfg, sway_sampling_coef=sway)[0][0]
-            for audio, (tokens, frames), n, cfg, sway in zip(audios, units, *per_unit)]
+    return [model_obj.sample(cond=audio, text=[tokens], duration=frames, steps=n, cfg_strength=cfg, sway_sampling_coef=sway,
+                             **({} if name is None else dict(ode_method=name)))[0][0]
+            for audio, (tokens, frames), n, cfg, sway, name in zip(audios, units, *per_unit, methods)]
 
 
 def _sample(model_obj, voice, units, knobs, generator=None):
@@ -477,7 +483,7 @@ def _vocode_and_join(mels, ref_frames, rms, vocoder, mel_spec_type, target_rms, 
 
 def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type="vocos", progress=None,
                         target_rms=0.1, cross_fade_duration=0.15, nfe_step=32, cfg_strength=2.0, sway_sampling_coef=-1,
-                        speed=1, fix_duration=None, device=None, tokenizer=text_to_tokens, seed=None):
+                        speed=1, fix_duration=None, device=None, tokenizer=text_to_tokens, seed=None, ode_method=None):
     """F/infer/utils_infer.py:406-524, same signature and return triple.
 
     The reference loops over the chunks and calls `sample()` / the vocoder once per chunk with batch 1.  The chunks are independent
@@ -485,13 +491,13 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
     chunks packed back to back, each with the reference's batch-1 semantics, the reference-audio mel computed once instead of once
     per chunk); any other object with the reference's `.sample()` is driven chunk by chunk like the reference does."""
     voice, units = _plan_request(ref_audio, ref_text, gen_text_batches, target_rms, speed, fix_duration, device, tokenizer)
-    knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
+    knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, ode_method=ode_method)
     mels = _sample(model_obj, voice, units, knobs, request_generator(seed))   # list of [frames_i, mel] incl. the reference frames
     return _vocode_and_join(mels, voice.ref_frames, voice.rms, vocoder, mel_spec_type, target_rms, cross_fade_duration)
 
 
 # per-request options of `infer_requests` (the fourth element of a request) and of the serving routes
-REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed")
+REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method")
 
 
 def plan_request(request, defaults, *, target_rms, fix_duration, device, tokenizer):
@@ -536,10 +542,11 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     [spec_i]) per request -- the per-chunk waves before the cross-fade -- instead of the joined triple.
 
     Per-request options: a request may carry a fourth element, a dict with any of `speed`, `nfe_step`, `cfg_strength`,
-    `sway_sampling_coef` and `seed` (`REQUEST_OPTIONS`); what it leaves out comes from this function's keyword arguments.  With a model
+    `sway_sampling_coef`, `seed` and `ode_method` (`REQUEST_OPTIONS`); what it leaves out comes from this function's keyword arguments
+    (`ode_method`: from the model object, which is handed the option only for requests that set it).  With a model
     that declares `per_unit_time_grids` (`F5HipModel`: f5hip_cfm_sample_grids) all units are sampled in ONE `sample_units` call whatever
-    their time grids (`nfe_step`, `sway_sampling_coef`) and strengths: each knob goes in as one value when all units agree, else as one
-    value per unit.  With any other model, requests that share a time grid are sampled in one call and each further grid is one more call,
+    their time grids (`nfe_step`, `sway_sampling_coef`), strengths and solvers: each knob goes in as one value when all units agree, else as
+    one value per unit.  With any other model, requests that share a time grid are sampled in one call and each further grid is one more call,
     in order of first appearance.  All chunks are vocoded together either way.  `speed` only changes a request's planned frames.  With `seed`, the request's chunk k draws its noise from `request_generator(seed)` after chunks
     0..k-1; a `generator` entry (a torch.Generator) continues that sequence instead -- what a streamed request's remaining chunks carry --
     and is advanced only when this call succeeds.  A seeded request's result depends only on its own settings, not on its batch, with the
@@ -547,12 +554,12 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     from the global generator in flat request order (unit by unit, request after request) when there is one sampler call, i.e. always
     with a `per_unit_time_grids` model, and in sampler-call order otherwise."""
     defaults = dict(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None)
-    plans, calls = [], {}   # calls: (nfe_step, sway) -> [unit ids, ...] of one sampler call each
+    plans, calls = [], {}   # calls: (nfe_step, sway, ode_method) -> [unit ids, ...] of one sampler call each
     flat_units, flat_cond, flat_audio, flat_cfg, flat_gen, flat_grid = [], [], [], [], [], []
     for req in requests:
         plan = plan_request(req, defaults, target_rms=target_rms, fix_duration=fix_duration, device=device, tokenizer=tokenizer)
         voice, units, opts = plan.voice, plan.units, plan.opts
-        key = (int(opts["nfe_step"]), opts["sway_sampling_coef"])
+        key = (int(opts["nfe_step"]), opts["sway_sampling_coef"], opts.get("ode_method"))
         calls.setdefault(key, []).extend(range(len(flat_units), len(flat_units) + len(units)))
         plans.append(plan)
         flat_units += units
@@ -571,7 +578,7 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     for ids in calls.values():
         got = _sample_units(model_obj, [flat_cond[i] for i in ids], [flat_audio[i] for i in ids], [flat_units[i] for i in ids],
                             one_or_list([flat_grid[i][0] for i in ids]), one_or_list([flat_cfg[i] for i in ids]),
-                            one_or_list([flat_grid[i][1] for i in ids]), [flat_gen[i] for i in ids])
+                            one_or_list([flat_grid[i][1] for i in ids]), [flat_gen[i] for i in ids], one_or_list([flat_grid[i][2] for i in ids]))
         for i, mel in zip(ids, got):
             mels[i] = mel
     groups, k = [], 0
@@ -617,7 +624,7 @@ class SpanScheduler:
     """Continuous batching over resumable sampler spans, synchronous and without threads: `admit(request)` plans a request (as
     `infer_requests` plans it) and queues it; every `step()` is one span boundary followed by one span: cancelled tickets leave, waiting
     tickets join in order of arrival while they fit, all units in flight advance by `span_steps` ODE steps of their own grids in ONE
-    `model_obj.advance` call (f5hip_cfm_sample_span), and the requests whose units have all ended are vocoded together (`_chunk_waves`:
+    `model_obj.advance` call (f5hip_cfm_sample_span; a unit whose request names an `ode_method` is budgeted in backbone forwards, `model.span_slices`), and the requests whose units have all ended are vocoded together (`_chunk_waves`:
     ragged Vocos when the vocoder offers it) and returned.  So a request waits for at most one span of the others, not for their whole
     batch, and with the shape-invariant attention mode its result is what `infer_requests` gives it alone with the same noise.
 
@@ -656,8 +663,10 @@ class SpanScheduler:
                             tokenizer=self.tokenizer)
         voice, opts = plan.voice, plan.opts
         cond = voice.cond(self.model_obj)
+        extra = {} if opts.get("ode_method") is None else dict(ode_method=opts["ode_method"])   # (handed on only when the request sets it)
         planned = [self.model_obj.plan_unit(cond, tokens, frames, steps=int(opts["nfe_step"]), cfg_strength=opts["cfg_strength"],
-                                            sway_sampling_coef=opts["sway_sampling_coef"], generator=plan.generator) for tokens, frames in plan.units]
+                                            sway_sampling_coef=opts["sway_sampling_coef"], generator=plan.generator, **extra)
+                   for tokens, frames in plan.units]
         plan.commit()   # every chunk was planned: the caller's generator moves
         ticket = SpanTicket(request, voice, planned)
         self.waiting.append(ticket)
@@ -893,7 +902,7 @@ def prepare_edit(audio, target_text, parts_to_edit, fix_duration=None, mel_spec_
 
 def speech_edit_batch(edits, model_obj, vocoder, mel_spec_type=mel_spec_type, target_rms=target_rms, nfe_step=nfe_step,
                       cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None, device=None, tokenizer=text_to_tokens,
-                      generators=None):
+                      generators=None, ode_method=None):
     """Several speech edits in ONE sampler call: `edits` = [(audio, target_text, parts_to_edit, fix_duration) | PreparedEdit], `audio` a
     path, the bytes of a WAV file, or a (tensor, sr) pair.  Returns one (wave float32, 24000, spec [100, T]) triple per edit, each what
     `speech_edit` returns for that edit alone: every edit keeps the reference's batch-1 semantics (its own prompt length `lens` and its
@@ -908,7 +917,8 @@ def speech_edit_batch(edits, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
 
     The model object needs the reference's `sample()`; with `cond_mel` (F5HipModel) the edits are handed over as one padded mel batch,
     any other object is driven edit by edit with the raw wave, like the reference does.  `generators` ([torch.Generator | None] per edit,
-    `request_generator`): an edit's noise comes from its own generator instead of the global one (F5HipModel only)."""
+    `request_generator`): an edit's noise comes from its own generator instead of the global one (F5HipModel only).  `ode_method`: one
+    solver name for the call or one name (or None) per edit, handed to `sample()` only when an edit names one."""
     if mel_spec_type not in ("vocos", "bigvgan"):
         raise ValueError(mel_spec_type)
     preps = []
@@ -922,6 +932,9 @@ def speech_edit_batch(edits, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
             audio, target_text, parts_to_edit, fix_duration = e
             preps.append(prepare_edit(audio, target_text, parts_to_edit, fix_duration, mel_spec_type, target_rms, device, tokenizer))
     knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+    methods = list(ode_method) if isinstance(ode_method, (list, tuple)) else [ode_method] * len(preps)
+    if len(methods) != len(preps):
+        raise ValueError(f"ode_method: one name per edit ({len(preps)}) or one name, got {len(methods)}")
     if generators is not None and any(g is not None for g in generators):
         if not hasattr(model_obj, "cond_mel") or len(generators) != len(preps):
             raise ValueError("generators: one per edit, and a model object with cond_mel (F5HipModel)")
@@ -934,12 +947,12 @@ def speech_edit_batch(edits, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
             edit_mask[i, :p.edit_mask.shape[0]] = p.edit_mask
         out, _ = model_obj.sample(cond=torch.nn.utils.rnn.pad_sequence(mels, batch_first=True), text=[p.tokens for p in preps],
                                   duration=torch.tensor([p.plan.duration for p in preps], dtype=torch.long), lens=lens,
-                                  edit_mask=edit_mask, **knobs)
+                                  edit_mask=edit_mask, **knobs, **(dict(ode_method=ode_method) if any(m is not None for m in methods) else {}))
         # each edit's rows: its final duration max(lens + 1, L // 256) (cfm.py:136), i.e. lens + 1
         gens = [out[i, :max(int(lens[i]) + 1, p.plan.duration)] for i, p in enumerate(preps)]
     else:
-        gens = [model_obj.sample(cond=p.cond, text=[p.tokens], duration=p.plan.duration, edit_mask=p.edit_mask[None], **knobs)[0][0]
-                for p in preps]
+        gens = [model_obj.sample(cond=p.cond, text=[p.tokens], duration=p.plan.duration, edit_mask=p.edit_mask[None], **knobs,
+                                 **({} if name is None else dict(ode_method=name)))[0][0] for p, name in zip(preps, methods)]
     res = []
     for gen, p in zip(gens, preps):
         wave, sr, spec = _vocode_and_join([gen], 0, p.rms, vocoder, mel_spec_type, target_rms, 0)
@@ -949,10 +962,10 @@ def speech_edit_batch(edits, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
 
 def speech_edit(audio, target_text, parts_to_edit, model_obj, vocoder, fix_duration=None, mel_spec_type=mel_spec_type,
                 target_rms=target_rms, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
-                seed=None, device=None):
+                seed=None, device=None, ode_method=None):
     """F/infer/speech_edit.py:119-192 as a call: regenerate `parts_to_edit` ([[start_s, end_s], ...]) of the recording `audio` (a path,
     WAV bytes or a (tensor, sr) pair) so that it speaks `target_text` (the full new transcript) in the same voice, keeping every other
     frame.  Returns (wave float32, 24000, spec [100, T]).  `speech_edit_batch` with one edit; see there and `plan_edit`."""
     return speech_edit_batch([(audio, target_text, parts_to_edit, fix_duration)], model_obj, vocoder, mel_spec_type=mel_spec_type,
                              target_rms=target_rms, nfe_step=nfe_step, cfg_strength=cfg_strength,
-                             sway_sampling_coef=sway_sampling_coef, seed=seed, device=device)[0]
+                             sway_sampling_coef=sway_sampling_coef, seed=seed, device=device, ode_method=ode_method)[0]

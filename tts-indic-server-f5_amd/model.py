@@ -80,6 +80,8 @@ class MMDiTArch:
 
 # torchdiffeq method name -> f5hip_dit_set_ode_method code (include/f5hip.h)
 _ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2}
+# backbone forwards per step of every method
+ODE_FORWARDS = {"euler": 1, "midpoint": 2, "rk4": 4}
 
 
 def _i32(a):
@@ -118,6 +120,20 @@ def per_unit_values(value, n: int, name: str):
     return vals
 
 
+def per_unit_methods(ode_method, n: int):
+    """None when no unit names a solver (`ode_method` None), else the n per-unit names, None where a unit follows the handle: `ode_method` is
+    one name for all units or one name (or None) per unit."""
+    if ode_method is None:
+        return None
+    names = [ode_method] * n if isinstance(ode_method, str) else list(ode_method)
+    if len(names) != n:
+        raise ValueError(f"ode_method: one name per unit ({n}) or one name, got {len(names)} values")
+    for name in names:
+        if name is not None and name not in _ODE_METHODS:
+            raise ValueError(f"ode_method must be one of 'euler', 'midpoint', 'rk4' (got {name!r})")
+    return names if any(name is not None for name in names) else None
+
+
 def time_grid(n_steps: int, sway, t_start: float = 0.0):
     """The fp32 time grid of CFM.sample (F/model/cfm.py:196-198): n_steps + 1 points from t_start to 1, sway-sampled unless `sway` is None."""
     t = torch.linspace(t_start, 1, n_steps + 1, dtype=torch.float32)
@@ -126,26 +142,34 @@ def time_grid(n_steps: int, sway, t_start: float = 0.0):
     return t
 
 
-def span_slices(units, max_steps: int):
+def span_slices(units, max_steps: int, method: str = "euler"):
     """What one span asks of every unit: (take, last, t_grids) -- unit i takes take[i] = min(max_steps, remaining) steps, last[i] = 1 when that
     brings it to its end, and t_grids holds the units' take[i] + 1 grid points from their cursors on, one slice after the other (slices
-    of the units' own fp32 arrays: the values of the whole grid, bit for bit)."""
+    of the units' own fp32 arrays: the values of the whole grid, bit for bit).
+    A unit with a solver of its own (`unit.method`; `method` is the handle's) is budgeted in backbone forwards: it takes
+    min(remaining, max(1, max_steps * forwards(method) // forwards(unit.method))) steps, so a span costs every unit about the same number of
+    forwards, and a unit whose solver is the handle's takes max_steps like a unit without one."""
     units = list(units)
     if not units or int(max_steps) < 1 or any(u.done for u in units):
         raise ValueError("a span needs at least one unit, none of them done, and max_steps >= 1")
-    take = [min(int(max_steps), u.remaining) for u in units]
+    take = []
+    for u in units:
+        own = getattr(u, "method", None)
+        budget = int(max_steps) if own is None else max(1, int(max_steps) * ODE_FORWARDS[method] // ODE_FORWARDS[own])
+        take.append(min(budget, u.remaining))
     last = np.ascontiguousarray(np.asarray([k == u.remaining for k, u in zip(take, units)], dtype=np.uint8))
     return take, last, np.ascontiguousarray(np.concatenate([u.grid[u.cursor:u.cursor + k + 1] for k, u in zip(take, units)]))
 
 
 class SpanUnit:
     """One sampling unit that is advanced span by span (`F5HipModel.plan_unit` / `advance`): what `sample()` would hand the library for it
-    -- conditioning rows, their mask, the text row, the whole fp32 time grid, the CFG strength -- plus the ODE state on the device and
-    the step cursor.  `noise` is the state before the first step (kept so that the unit can start over: `reset()`); `mel` is the final
+    -- conditioning rows, their mask, the text row, the whole fp32 time grid, the CFG strength, the ODE method (None: the handle's) -- plus
+    the ODE state on the device and the step cursor.  `noise` is the state before the first step (kept so that the unit can start over: `reset()`); `mel` is the final
     [dur, mel] result once the last step has run, else None."""
 
-    def __init__(self, cond, cond_mask, text, grid, cfg_strength, noise):
+    def __init__(self, cond, cond_mask, text, grid, cfg_strength, noise, method=None):
         self.cond, self.cond_mask, self.text, self.grid, self.cfg_strength = cond, cond_mask, text, grid, float(cfg_strength)
+        self.method = method
         self.noise, self.state = noise, noise.clone()
         self.cursor, self.mel = 0, None
 
@@ -221,6 +245,11 @@ class F5HipModel:
         _lib.check(self._lib.f5hip_dit_set_ode_method(self._h, _ODE_METHODS[method]), "f5hip_dit_set_ode_method")
         self.set_attention_shape_invariant(attn_shape_invariant)
 
+    @property
+    def ode_method(self) -> str:
+        """The handle's solver (odeint_kwargs): what a unit without an `ode_method` of its own is stepped by."""
+        return self.odeint_kwargs.get("method", "euler")
+
     def set_attention_shape_invariant(self, on: bool | None):
         """This handle's attention arithmetic (include/f5hip.h): True = a sequence's output does not depend on what it is batched with,
         False = the fastest kernel per launch shape, None = follow the process default (f5hip_set_attention_shape_invariant)."""
@@ -284,7 +313,8 @@ class F5HipModel:
         return cond
 
     @torch.no_grad()
-    def sample_units(self, audio, units, *, steps=32, cfg_strength=2.0, sway_sampling_coef=-1.0, seed=None, generators=None, y0=None):
+    def sample_units(self, audio, units, *, steps=32, cfg_strength=2.0, sway_sampling_coef=-1.0, seed=None, generators=None, y0=None,
+                     ode_method=None):
         """Independent sampling units in ONE sampler call: the text chunks of one request (independent `sample()` calls in the
         reference, F/infer/utils_infer.py:441-466), or the chunks of several requests with different voices (`infer.infer_requests`).
         `audio`: the reference wave [1, nw] (or its mel [1, n, mel]) shared by all units, or a list with one such tensor per unit;
@@ -296,7 +326,8 @@ class F5HipModel:
         ([torch.Generator | None] per unit) draws a unit's noise from its own CPU generator instead of the global one, with the unit's final
         duration (`unit_duration`), and `y0` ([tensor [dur_i, mel] | None] per unit) hands a unit its noise outright.  Units without either
         keep drawing from the global generator, unit by unit in order.  `steps` and `sway_sampling_coef` are one value or one value per unit
-        (None allowed per unit for the sway): units of different time grids are sampled in the same call."""
+        (None allowed per unit for the sway): units of different time grids are sampled in the same call.  `ode_method`: None (the handle's
+        solver), one name, or one name (or None) per unit: units of different solvers are sampled in the same call too (`sample`)."""
         b = len(units)
         frames = torch.tensor([int(f) for _, f in units], dtype=torch.long)
         lens = None
@@ -312,7 +343,7 @@ class F5HipModel:
         else:
             cond = (self.cond_mel(audio) if audio.ndim == 2 else audio.to(self.device, torch.float32)).expand(b, -1, -1)
         p = self._plan_batch(cond, [t for t, _ in units], frames, lens=lens, steps=steps, cfg_strength=cfg_strength,
-                             sway_sampling_coef=sway_sampling_coef, seed=seed, generators=generators, y0=y0)
+                             sway_sampling_coef=sway_sampling_coef, seed=seed, generators=generators, y0=y0, ode_method=ode_method)
         out = self._sample_planned(p)
         # (a duration is raised to lens + 1 like the reference does, cfm.py:136: the rows of unit i are its FINAL duration)
         return [out[i, :p.durs[i]] for i in range(b)]
@@ -320,7 +351,7 @@ class F5HipModel:
     @torch.no_grad()
     def sample(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None,
                seed=None, max_duration=4096, vocoder=None, no_ref_audio=False, duplicate_test=False, t_inter=0.1,
-               edit_mask=None, y0=None, padded_batch=False, generators=None):
+               edit_mask=None, y0=None, padded_batch=False, generators=None, ode_method=None):
         """CFM.sample (F/model/cfm.py:82-210).  Returns (out [b, n, mel] on the device, None): the trajectory is
         not materialised (its only in-tree consumer drops it, F/infer/utils_infer.py:459).
 
@@ -334,10 +365,13 @@ class F5HipModel:
         `cfg_strength`: one float (f5hip_cfm_sample_masked) or one value per item (f5hip_cfm_sample_units).
         `steps` / `sway_sampling_coef`: one value, or one value per item (sway None allowed per item).  Every item's grid is built as the
         scalar call builds it; when they all come out equal the call is the one-grid call, otherwise f5hip_cfm_sample_grids samples every
-        item on its own grid in the same call (an item whose steps are done leaves the batch)."""
+        item on its own grid in the same call (an item whose steps are done leaves the batch).
+        `ode_method`: None = the handle's solver (odeint_kwargs); else "euler" / "midpoint" / "rk4" for all items, or one name (or None) per
+        item.  When some item's solver differs from the handle's, f5hip_cfm_sample_methods steps every item by its own rule in the same
+        call; an item's result is what it gets alone on a handle built with its method."""
         p = self._plan_batch(cond, text, duration, lens=lens, steps=steps, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
                              seed=seed, max_duration=max_duration, duplicate_test=duplicate_test, t_inter=t_inter, edit_mask=edit_mask, y0=y0,
-                             padded_batch=padded_batch, generators=generators)
+                             padded_batch=padded_batch, generators=generators, ode_method=ode_method)
         out = self._sample_planned(p)
         if no_ref_audio:   # cfm.py:157-158: the final overwrite then copies zeros
             out = torch.where(p.cond_mask[..., None].to(self.device), torch.zeros_like(out), out)
@@ -348,7 +382,8 @@ class F5HipModel:
     def _sample_planned(self, p):
         """The one whole-grid library call for a planned batch (`_plan_batch`): packs the items' rows back to back, picks the entry point
         -- one grid and one strength: f5hip_cfm_sample_masked; one grid, a strength per item: f5hip_cfm_sample_units; a grid per item:
-        f5hip_cfm_sample_grids -- and returns the result as [b, nmax, mel], zero behind an item's laid-out rows."""
+        f5hip_cfm_sample_grids; some item's ODE method is not the handle's: f5hip_cfm_sample_methods -- and returns the result as
+        [b, nmax, mel], zero behind an item's laid-out rows."""
         batch, nmax, lay = p.batch, p.nmax, p.lay
         t = p.grids[0]
         cond_packed = torch.cat([p.cond[i, :lay[i]] for i in range(batch)], dim=0).contiguous()
@@ -356,7 +391,11 @@ class F5HipModel:
             torch.cat([p.cond_mask[i, :lay[i]] for i in range(batch)]).numpy().astype(np.uint8))
         y0_packed = torch.cat(p.ys, dim=0).contiguous()
         tg = np.ascontiguousarray(t.numpy().astype(np.float32))
-        if not all(g.shape == t.shape and torch.equal(g, t) for g in p.grids[1:]):
+        if any(name != self.ode_method for name in p.methods):
+            cfg_all = p.cfg_units if p.cfg_units is not None else np.full(batch, float(p.cfg_strength), dtype=np.float32)
+            entry, tail = "cfm_sample_methods", [_i32(p.steps_u), np.ascontiguousarray(torch.cat(p.grids).numpy().astype(np.float32)), cfg_all,
+                                                 _i32([_ODE_METHODS[name] for name in p.methods]), None]
+        elif not all(g.shape == t.shape and torch.equal(g, t) for g in p.grids[1:]):
             cfg_all = p.cfg_units if p.cfg_units is not None else np.full(batch, float(p.cfg_strength), dtype=np.float32)
             entry, tail = "cfm_sample_grids", [_i32(p.steps_u), np.ascontiguousarray(torch.cat(p.grids).numpy().astype(np.float32)), cfg_all]
         elif p.cfg_units is not None:
@@ -375,9 +414,9 @@ class F5HipModel:
         return out
 
     def _call_sampler(self, entry, host_arrays, cond, y0, tail):
-        """ONE sampler call, `entry` one of cfm_sample / cfm_sample_units / cfm_sample_grids / cfm_sample_span: the TORCH_LIBRARY operator
+        """ONE sampler call, `entry` one of cfm_sample / cfm_sample_units / cfm_sample_grids / cfm_sample_span / cfm_sample_methods: the TORCH_LIBRARY operator
         (csrc/torch_ops.cpp) when it is loaded, else the same C entry point through ctypes.  `host_arrays` = (dur, kv_len | None, cond_mask,
-        text [b, nt]) and the arrays in `tail` (what the entry takes behind y0; a scalar strength travels as it is) are numpy arrays on the
+        text [b, nt]) and the arrays in `tail` (what the entry takes behind y0; a scalar strength travels as it is, None as a null) are numpy arrays on the
         host; `cond` and `y0` are the packed device rows.  Returns the packed result, shaped like `y0`."""
         use_op = torch_ops.load()
         wrap = torch.from_numpy if use_op else _ptr
@@ -397,33 +436,42 @@ class F5HipModel:
         return out
 
     @torch.no_grad()
-    def plan_unit(self, cond, tokens, frames, *, steps=32, cfg_strength=2.0, sway_sampling_coef=-1.0, generator=None, y0=None) -> SpanUnit:
+    def plan_unit(self, cond, tokens, frames, *, steps=32, cfg_strength=2.0, sway_sampling_coef=-1.0, generator=None, y0=None,
+                  ode_method=None) -> SpanUnit:
         """Plans one unit as `sample_units` would sample it -- `cond` the prompt mel [1, n, mel] (or wave [1, nw]), `tokens` its text (a token list, or ids [nt]), `frames`
         its planned rows -- without running a step: conditioning, mask, text row and time grid come from the code `sample()` uses, and the
-        noise is drawn here as `sample()` draws it (`y0` [dur, mel], else `generator`, else the global generator)."""
+        noise is drawn here as `sample()` draws it (`y0` [dur, mel], else `generator`, else the global generator).  `ode_method`: the unit's own
+        solver (None: the handle's); `advance` steps units of different solvers in one call."""
+        if ode_method is not None and ode_method not in _ODE_METHODS:
+            raise ValueError(f"ode_method must be one of 'euler', 'midpoint', 'rk4' (got {ode_method!r})")
         text = tokens.reshape(1, -1) if isinstance(tokens, torch.Tensor) else [tokens]
         p = self._plan_batch(cond, text, torch.tensor([int(frames)], dtype=torch.long), steps=int(steps), cfg_strength=float(cfg_strength),
                              sway_sampling_coef=sway_sampling_coef, y0=None if y0 is None else [y0],
                              generators=None if generator is None else [generator])
         dur = p.durs[0]
         return SpanUnit(p.cond[0, :dur].contiguous(), np.ascontiguousarray(p.cond_mask[0, :dur].numpy().astype(np.uint8)), _i32(p.text.numpy()[0]),
-                        np.ascontiguousarray(p.grids[0].numpy().astype(np.float32)), cfg_strength, p.ys[0].contiguous())
+                        np.ascontiguousarray(p.grids[0].numpy().astype(np.float32)), cfg_strength, p.ys[0].contiguous(), method=ode_method)
 
     @torch.no_grad()
     def advance(self, units, max_steps: int):
         """ONE f5hip_cfm_sample_span call over `units` (planned, not done): each takes min(max_steps, remaining) steps of its own grid from its
         cursor on.  States and cursors are updated in place; a unit that reaches its end gets `mel` (the prompt rows overwritten with
-        the conditioning, cfm.py:204).  Returns the units that ended."""
+        the conditioning, cfm.py:204).  Returns the units that ended.  Units planned with a solver of their own are budgeted in backbone
+        forwards (`span_slices`); when one of them differs from the handle's, the call is f5hip_cfm_sample_methods."""
         units = list(units)
-        take, last, tgs = span_slices(units, max_steps)
+        take, last, tgs = span_slices(units, max_steps, self.ode_method)
+        methods = [getattr(u, "method", None) or self.ode_method for u in units]
+        entry, extra = "cfm_sample_span", [last]
+        if any(name != self.ode_method for name in methods):
+            entry, extra = "cfm_sample_methods", [_i32([_ODE_METHODS[name] for name in methods]), last]
         nt = max(len(u.text) for u in units)
         text_np = np.full((len(units), nt), -1, dtype=np.int32)
         for i, u in enumerate(units):
             text_np[i, :len(u.text)] = u.text
         cfg = np.ascontiguousarray(np.asarray([u.cfg_strength for u in units], dtype=np.float32))
         mask = np.ascontiguousarray(np.concatenate([u.cond_mask for u in units]))
-        out = self._call_sampler("cfm_sample_span", [_i32([u.dur for u in units]), None, mask, text_np], torch.cat([u.cond for u in units], dim=0),
-                                 torch.cat([u.state for u in units], dim=0), [_i32(take), tgs, cfg, last])
+        out = self._call_sampler(entry, [_i32([u.dur for u in units]), None, mask, text_np], torch.cat([u.cond for u in units], dim=0),
+                                 torch.cat([u.state for u in units], dim=0), [_i32(take), tgs, cfg, *extra])
         ended, o = [], 0
         for u, k, end in zip(units, take, last):
             u.state.copy_(out[o:o + u.dur])
@@ -433,9 +481,10 @@ class F5HipModel:
         return ended
 
     def _plan_batch(self, cond, text, duration, *, steps, cfg_strength, sway_sampling_coef, lens=None, seed=None, max_duration=4096,
-                    duplicate_test=False, t_inter=0.1, edit_mask=None, y0=None, padded_batch=False, generators=None):
+                    duplicate_test=False, t_inter=0.1, edit_mask=None, y0=None, padded_batch=False, generators=None, ode_method=None):
         """Everything `sample()` decides before its library call (cfm.py:103-146,181-198), per item: the padded conditioning and its mask, the
-        text rows, the final durations and laid-out rows, the noise (drawn here, in item order) and the fp32 time grid.  The one place that
+        text rows, the final durations and laid-out rows, the noise (drawn here, in item order), the fp32 time grid and the ODE method
+        (`methods`: a name per item, the handle's where the item names none).  The one place that
         builds them: `sample()` hands them to one whole call, `plan_unit()` keeps them for a unit that is advanced span by span."""
         if cond.ndim == 2:   # raw wave -> mel (cfm.py:103-106) with the extractor of mel_spec_type (modules.py:123-126)
             cond = self.cond_mel(cond)
@@ -506,4 +555,5 @@ class F5HipModel:
                 cache[key] = time_grid(n_steps, sway, t_start)
             grids.append(cache[key])
         return types.SimpleNamespace(batch=batch, nmax=nmax, cond=cond, cond_mask=cond_mask, text=text, durs=durs, lay=lay, padded=padded,
-                                     cfg_strength=cfg_strength, cfg_units=cfg_units, ys=ys, steps_u=steps_u, grids=grids)
+                                     cfg_strength=cfg_strength, cfg_units=cfg_units, ys=ys, steps_u=steps_u, grids=grids,
+                                     methods=[name or self.ode_method for name in per_unit_methods(ode_method, batch) or [None] * batch])

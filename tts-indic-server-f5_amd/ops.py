@@ -292,6 +292,24 @@ def cfg_step(method, stage, xout, xbase, pred, urow_c, urow_u, xs, *, cfg=0.0, c
     return out
 
 
+# op codes of cfg_mixed (csrc/elementwise.h CfgOp): RK4 stage s is CFG_OP_RK4_1 + s - 1
+CFG_OP_NONE, CFG_OP_EULER, CFG_OP_MID_HALF, CFG_OP_MID_FULL, CFG_OP_RK4_1 = 0, 1, 2, 3, 4
+
+
+def cfg_mixed(xstate, pred, urow_c, urow_u, xs, cfg_frame, frame_unit, unit_op, unit_dt, n_act, k):
+    """One launch of the CFG combine + ODE update of a mixed-method sampler call IN PLACE on the caller's fp32 device tensors (include/f5hip.h
+    f5hip_op_cfg_mixed): xstate / k[0..2] [U, mel], pred / xs [rows, 128], cfg_frame [U]; frame_unit [U], unit_op / unit_dt [n_units] on the
+    host: every frame is stepped by its unit's op code and step size."""
+    U, mel = xstate.shape
+    for t in (xstate, pred, xs, cfg_frame) + tuple(k):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda
+    uc, uu, fu, uo = (_i32(a) for a in (urow_c, urow_u, frame_unit, unit_op))
+    ud = np.ascontiguousarray(np.asarray(unit_dt, dtype=np.float32))
+    assert uo.shape == ud.shape and fu.shape == (U,)
+    _lib.check(_lib.lib().f5hip_op_cfg_mixed(U, mel, pred.shape[0], _p(xstate), _p(pred), _p(uc), _p(uu), _p(cfg_frame), _p(fu), _p(uo), _p(ud), len(uo),
+                                             int(n_act), _p(k[0]), _p(k[1]), _p(k[2]), _p(xs), _lib.current_stream_ptr()), "f5hip_op_cfg_mixed")
+
+
 def row_tp(row_unit, unit_tp):
     """row_tp[r] = unit_tp[row_unit[r]] by the sampler's kernel; int arrays in, numpy int32 out."""
     ru, ut = _i32(row_unit), _i32(unit_tp)

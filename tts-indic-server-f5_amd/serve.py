@@ -44,7 +44,7 @@ from . import infer
 
 log = logging.getLogger(__name__)
 
-EDIT_OPTIONS = ("nfe_step", "cfg_strength", "sway_sampling_coef", "seed")   # a speech edit has no `speed`: its durations are planned
+EDIT_OPTIONS = ("nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method")   # a speech edit has no `speed`: its durations are planned
 # most ODE steps one library call accepts per method: 128 time points (f5hip precompute_time); midpoint uses 2 per step, RK4 3 per step + 1
 MAX_NFE_STEP = {"euler": 128, "midpoint": 64, "rk4": 42}
 
@@ -52,14 +52,22 @@ MAX_NFE_STEP = {"euler": 128, "midpoint": 64, "rk4": 42}
 def check_request_options(options: dict, ode_method: str = "euler", allowed=infer.REQUEST_OPTIONS) -> dict:
     """The per-request sampler options a client set (None = not set, dropped), checked before anything is queued: ValueError with a message
     the routes return as 400.  `speed` finite and > 0; `nfe_step` an integer in 1..MAX_NFE_STEP[ode_method]; `cfg_strength` and
-    `sway_sampling_coef` finite; `seed` an integer in 0..2**63 - 1."""
+    `sway_sampling_coef` finite; `seed` an integer in 0..2**63 - 1; `ode_method` one of MAX_NFE_STEP's names.  `ode_method` (the argument)
+    is the model's solver: `nfe_step`'s upper limit follows the request's own `ode_method` when it sets one, else the model's."""
     out = {}
+    own = options.get("ode_method") if "ode_method" in allowed else None
+    if own is not None:
+        if not isinstance(own, str) or own not in MAX_NFE_STEP:
+            raise ValueError(f"ode_method must be one of 'euler', 'midpoint', 'rk4' (got {own!r})")
+        ode_method = own
     for k, v in options.items():
         if k not in allowed:
             raise ValueError(f"unknown option {k!r} (allowed: {', '.join(allowed)})")
         if v is None:
             continue
-        if k in ("nfe_step", "seed"):
+        if k == "ode_method":
+            pass
+        elif k in ("nfe_step", "seed"):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"{k} must be an integer (got {v!r})")
             v = int(v)
@@ -433,17 +441,20 @@ class TTSManager:
             return self.batcher.submit(req).result(timeout=self.request_timeout_s)
         return self._run_batch([req])[0]
 
-    def synthesize(self, text, ref_audio_path, ref_text, *, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None, seed=None):
+    def synthesize(self, text, ref_audio_path, ref_text, *, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None, seed=None,
+                   ode_method=None):
         """The wave of one request.  The sampler options are this request's own (None: `self.opts`); `seed` draws its noise from its own
         generator (`infer.request_generator`), so the same seeded request gives the same audio whatever it is batched with (shape-invariant
-        attention, one GPU)."""
+        attention, one GPU).  `ode_method` ("euler", "midpoint", "rk4"; None: the model's): requests of different solvers share a batch, and
+        the option reaches the model object only for a request that sets it."""
         if not self.model:
             raise ValueError("TTS model not loaded")
-        opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+        opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
+                                    ode_method=ode_method)
         return self.model(text, ref_audio_path=ref_audio_path, ref_text=ref_text, **opts)
 
     def synthesize_stream(self, text, ref_audio_path, ref_text, *, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
-                          seed=None):
+                          seed=None, ode_method=None):
         """`synthesize` as an iterator of float32 pieces (24 kHz) whose concatenation is `synthesize`'s wave given the same noise (see
         `infer.infer_process_stream`).  The request's first chunk is synthesized on its own and its stable samples come out as soon as it is
         done; the remaining chunks follow as a second request.  With a micro-batcher the first chunk rides in the next batch and the
@@ -451,10 +462,11 @@ class TTSManager:
         each under the device lock (released in between).  Closing the iterator early (client disconnect) cancels the remaining chunks
         if their batch has not started.  Errors about the model or the voice are raised here, not on the first `next()`.  Options as in
         `synthesize`; with a `seed`, the first chunk and the remaining chunks draw from the request's one generator in chunk order, so the
-        pieces equal `synthesize`'s wave with that seed."""
+        pieces equal `synthesize`'s wave with that seed.  The remaining chunks keep the first chunk's `ode_method`."""
         if not self.model:
             raise ValueError("TTS model not loaded")
-        opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+        opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
+                                    ode_method=ode_method)
         voice, ref_text_n = self._voice(ref_audio_path, ref_text)
         chunks = infer.request_chunks(ref_text_n, voice.seconds, text)
         if "seed" in opts:   # head and tail continue one sequence; the tail's batch runs after the head's (one worker, one batch at a time)
@@ -507,19 +519,21 @@ class TTSManager:
         return SynthesisStream(pieces(), cancel)
 
     def edit(self, audio, target_text, parts_to_edit, fix_duration=None, *, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
-             seed=None):
+             seed=None, ode_method=None):
         """Speech editing (`infer.speech_edit`, F/infer/speech_edit.py): regenerate `parts_to_edit` of the recording `audio` (a path, WAV
         bytes or a (tensor, sr) pair) so that it speaks `target_text`, with this manager's sampler settings unless the call sets its own
-        (`seed`: the edit's noise from its own generator).  The host preparation runs outside the device lock, the sampler and vocoder
+        (`seed`: the edit's noise from its own generator; `ode_method`: the edit's solver, handed on only when set).  The host preparation runs outside the device lock, the sampler and vocoder
         under it (not through the micro-batcher); with a `ShardedSampler` on rank 0's own model.  Returns the wave (float32, 24 kHz)."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = dict(self.opts, **self.request_options(EDIT_OPTIONS, nfe_step=nfe_step, cfg_strength=cfg_strength,
-                                                      sway_sampling_coef=sway_sampling_coef, seed=seed))
+                                                      sway_sampling_coef=sway_sampling_coef, seed=seed, ode_method=ode_method))
         model_obj = getattr(self.model_obj, "local", self.model_obj)
         # host work (read, mono mix, resample, plan, tokens) and every rejection happen before the device lock is taken
         prep = infer.prepare_edit(audio, target_text, parts_to_edit, fix_duration, mel_spec_type=self.mel_spec_type)
         extra = dict(generators=[infer.request_generator(opts["seed"])]) if opts.get("seed") is not None else {}
+        if opts.get("ode_method") is not None:
+            extra["ode_method"] = opts["ode_method"]
         with self._device_lock:
             (wave, _, _), = infer.speech_edit_batch([prep], model_obj, self.vocoder, mel_spec_type=self.mel_spec_type,
                                                     nfe_step=opts["nfe_step"], cfg_strength=opts["cfg_strength"],
@@ -593,8 +607,9 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     JSON body {"audio": base64 WAV, "text": the full new transcript, "parts_to_edit": [[start_s, end_s], ...], "fix_duration": [...] | null}
     -> the edited recording as WAV).  Both speech routes take `"stream": true`: the WAV then arrives chunk by chunk (`_run_stream`), its
     PCM samples identical to the unstreamed response's.  Every route also takes the optional sampler fields `nfe_step`, `cfg_strength`,
-    `sway_sampling_coef`, `seed` and (speech routes) `speed`, checked before anything is queued (400 with `check_request_options`'s
-    message); an omitted field is the manager's setting.  With a `seed`, the same request returns the same audio."""
+    `sway_sampling_coef`, `seed`, `ode_method` ("euler", "midpoint" or "rk4": the request's ODE solver) and (speech routes) `speed`, checked
+    before anything is queued (400 with `check_request_options`'s message); an omitted field is the manager's setting (`ode_method`: the
+    model's).  With a `seed`, the same request returns the same audio."""
     from fastapi import APIRouter, FastAPI, HTTPException
     from pydantic import BaseModel
     from starlette.responses import StreamingResponse
@@ -604,6 +619,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         cfg_strength: float | None = None
         sway_sampling_coef: float | None = None
         seed: int | None = None
+        ode_method: str | None = None
 
     class KannadaSynthesizeRequest(SamplerFields):   # S/utils/tts_utils.py:27-28
         text: str
@@ -744,7 +760,8 @@ class ShardedSampler:
     `infer_batch_process`), so an unseeded result is not reproducible across world sizes; pass `seed=` in the knobs for that.  Units with
     their own generator (`generators=`, a seeded request's chunks) get their noise drawn HERE, on rank 0, in unit order at the unit's final
     duration (`model.unit_duration`), and broadcast with the job: a seeded unit gets the same noise whichever rank samples it.
-    Per-unit `cfg_strength`, `steps` and `sway_sampling_coef` (lists) are sliced to each rank's units; the sampler declares
+    Per-unit `cfg_strength`, `steps`, `sway_sampling_coef` and `ode_method` (lists) are sliced to each rank's units (one `ode_method` name
+    for all units rides in the job's knobs as it is); the sampler declares
     `per_unit_time_grids` when its local model does, so `infer.infer_requests` hands it units of different time grids in one call.  (Ranks > 0 do not switch their handles to the shape-invariant
     attention mode yet, so the bit-for-bit promises of a seeded request hold on one GPU.)
     Streaming (`TTSManager.synthesize_stream`) needs nothing here: a stream's first chunk and its remaining chunks arrive as units of
@@ -794,6 +811,10 @@ class ShardedSampler:
             if isinstance(v, list):
                 grids[name] = [None if x is None else (int(x) if name == "steps" else float(x)) for x in v]
                 knobs[name] = None
+        if isinstance(knobs.get("ode_method"), (list, tuple)):   # per-unit solvers: sliced per rank too
+            grids["ode_method"] = list(knobs.pop("ode_method"))
+            if len(grids["ode_method"]) != b:
+                raise ValueError(f"ode_method: one name per unit ({b}) or one name, got {len(grids['ode_method'])} values")
         noise = list(y0) if y0 is not None else [None] * b
         if gens is not None:
             mel_dim = mels[0].shape[1]
@@ -861,7 +882,7 @@ def _run_sharded_job(local_model, job, mels, device, noise=None):
     knobs = dict(job["knobs"])
     if job.get("cfg") is not None:        # per-unit CFG strengths: this rank's units
         knobs["cfg_strength"] = [job["cfg"][i] for i in mine]
-    for name, vals in (job.get("grids") or {}).items():   # per-unit steps / sway: this rank's units
+    for name, vals in (job.get("grids") or {}).items():   # per-unit steps / sway / solver: this rank's units
         knobs[name] = [vals[i] for i in mine]
     if noise is not None and any(noise[i] is not None for i in mine):
         knobs["y0"] = [noise[i] for i in mine]

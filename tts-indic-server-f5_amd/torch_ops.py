@@ -1,6 +1,8 @@
 """torch.ops.f5hip.*: the hot path as PyTorch custom operators (TORCH_LIBRARY registration in csrc/torch_ops.cpp over the C ABI of libf5hip;
 north_star: "host Python calling HIP through PyTorch-ROCm custom ops").  `load()` registers them (once); `F5HipModel.sample`, `F5HipVocos.decode` / `decode_ragged`
-and `F5HipBigVGAN.__call__` go through them when the extension is present and through ctypes otherwise -- the same C entry points either way."""
+and `F5HipBigVGAN.__call__` go through them when the extension is present and through ctypes otherwise -- the same C entry points either way.
+The sampler operators: cfm_sample, cfm_sample_units, cfm_sample_grids, cfm_sample_span and cfm_sample_methods (one ODE method per unit);
+`F5HipModel._call_sampler` is their one caller."""
 from __future__ import annotations
 
 import os
