@@ -413,6 +413,22 @@ int f5hip_mel_spectrogram(int32_t batch, int32_t n_samples, const float* wave_de
 int f5hip_mel_spectrogram_bigvgan(int32_t batch, int32_t n_samples, const float* wave_dev, float* mel_dev, int32_t n_fft,
                                   int32_t hop_length, int32_t n_mels, int32_t sample_rate, void* stream);
 
+/* ---------------------------------------------------------------- reference-audio front-end ------------ */
+
+/* Prologue of infer_batch_process (F/infer/utils_infer.py:423-433) for n clips of one sample-rate pair, in one call:
+ * mono mix (mean over channels), rms = sqrt(mean(x^2)) of the mono clip, gain x * rms_floor / rms when rms < rms_floor,
+ * torchaudio.transforms.Resample(orig_freq, new_freq) (sinc_interp_hann, width 6, rolloff 0.99).
+ *   n_in[i], channels[i]  host; clip i = channels[i] planes of n_in[i] fp32 samples (load_wav's layout), clips packed back to back in wave_dev
+ *   taps_dev              fp32 [nf][2*width+of]: the table infer.resample_taps builds (the values resample_sinc_hann convolves with)
+ *   out_dev               packed mono fp32; clip i holds n_out[i] = ceil(nf * n_in[i] / of) samples
+ *   rms_dev               fp32 [n]: the measured rms BEFORE the gain (what the output path restores)
+ * orig_freq == new_freq: no taps, out = the gained mono clip.
+ * Two launches, no host sync between them (the length tables are copied on `stream`, which the call waits for once before it launches);
+ * the sum of squares is accumulated in fp64 in a fixed order, so a clip's samples and rms do not depend on what else is in the call.
+ * Refused before the first launch: n < 1, n_in[i] < 1, channels[i] < 1, a null table when the rates differ, sum(n_out) above 2^31 - 1. */
+int f5hip_ref_frontend(int32_t n, const int32_t* n_in, const int32_t* channels, const float* wave_dev, int32_t orig_freq, int32_t new_freq,
+                       const float* taps_dev, float rms_floor, float* out_dev, float* rms_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

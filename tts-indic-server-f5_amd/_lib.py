@@ -99,6 +99,8 @@ SYMBOLS = {
                                                 C.c_int32, C.c_void_p]),
     "f5hip_mel_spectrogram": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_void_p]),
+    "f5hip_ref_frontend": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
 }
 
 

@@ -67,8 +67,12 @@ class PcmSegment:
 
     def _cum_squares(self) -> np.ndarray:          # exact in int64: 2^30 per sample
         if self._csq is None:
-            sq = (self.frames.astype(np.int64) ** 2).sum(axis=1)
-            self._csq = np.concatenate([[0], np.cumsum(sq)])
+            sq = self.frames.astype(np.int64)
+            np.multiply(sq, sq, out=sq)
+            sq = sq[:, 0] if sq.shape[1] == 1 else sq.sum(axis=1)
+            csq = np.zeros(len(sq) + 1, dtype=np.int64)
+            np.cumsum(sq, out=csq[1:])
+            self._csq = csq
         return self._csq
 
     def rms_ms(self, start_ms, end_ms) -> int:
@@ -79,6 +83,23 @@ class PcmSegment:
             return 0
         c = self._cum_squares()
         return int(math.sqrt(float(c[b] - c[a]) / n))
+
+    def _frames(self, ms: np.ndarray) -> np.ndarray:
+        """`_frame` of every entry of an integer millisecond array (the same float product, truncated, clipped)."""
+        return np.clip((ms * (self.rate / 1000.0)).astype(np.int64), 0, self.frames.shape[0])
+
+    def rms_windows(self, start_ms: np.ndarray, end_ms: np.ndarray) -> np.ndarray:
+        """`rms_ms(start_ms[i], end_ms[i])` for every i at once, as int64: the sums are differences of the exact int64 cumulative squares,
+        then the same float conversion, division, square root and truncation as `rms_ms`."""
+        n_ms = len(self)
+        a = self._frames(np.clip(np.asarray(start_ms, dtype=np.int64), 0, n_ms))
+        b = self._frames(np.clip(np.asarray(end_ms, dtype=np.int64), 0, n_ms))
+        n = (b - a) * self.frames.shape[1]
+        c = self._cum_squares()
+        out = np.zeros(a.shape, dtype=np.int64)
+        ok = n > 0
+        out[ok] = np.sqrt((c[b[ok]] - c[a[ok]]).astype(np.float64) / n[ok]).astype(np.int64)
+        return out
 
     @property
     def rms(self) -> int:
@@ -99,28 +120,24 @@ class PcmSegment:
 
 
 def detect_silence(seg: PcmSegment, min_silence_len=1000, silence_thresh=-16, seek_step=1):
-    """pydub.silence.detect_silence: [start_ms, end_ms] ranges whose every `min_silence_len` window has rms <= threshold."""
+    """pydub.silence.detect_silence: [start_ms, end_ms] ranges whose every `min_silence_len` window has rms <= threshold.
+    All windows are measured in one pass over the cumulative squares (`rms_windows`)."""
     seg_len = len(seg)
     if seg_len < min_silence_len:
         return []
     thresh = (10 ** (silence_thresh / 20.0)) * _MAX_AMP
     last = seg_len - min_silence_len
-    starts = list(range(0, last + 1, seek_step))
+    starts = np.arange(0, last + 1, seek_step, dtype=np.int64)
     if last % seek_step:
-        starts.append(last)
-    silent = [i for i in starts if seg.rms_ms(i, i + min_silence_len) <= thresh]
-    if not silent:
+        starts = np.append(starts, last)
+    silent = starts[seg.rms_windows(starts, starts + min_silence_len) <= thresh]
+    if not len(silent):
         return []
-    ranges = []
-    prev = silent[0]
-    cur = prev
-    for i in silent[1:]:
-        if i != prev + seek_step and i > prev + min_silence_len:
-            ranges.append([cur, prev + min_silence_len])
-            cur = i
-        prev = i
-    ranges.append([cur, prev + min_silence_len])
-    return ranges
+    # a new range starts at a silent window that neither continues the previous one nor begins inside it
+    cut = np.flatnonzero((silent[1:] != silent[:-1] + seek_step) & (silent[1:] > silent[:-1] + min_silence_len))
+    first = np.concatenate([silent[:1], silent[cut + 1]])
+    end = np.concatenate([silent[cut], silent[-1:]]) + min_silence_len
+    return [[int(a), int(b)] for a, b in zip(first, end)]
 
 
 def detect_nonsilent(seg: PcmSegment, min_silence_len=1000, silence_thresh=-16, seek_step=1):
@@ -151,20 +168,32 @@ def split_on_silence(seg: PcmSegment, min_silence_len=1000, silence_thresh=-16, 
     return [seg.slice_ms(max(s, 0), min(e, len(seg))) for s, e in ranges]
 
 
+def _dbfs_of_rms(r: int) -> float:
+    return -math.inf if r == 0 else 20.0 * math.log10(r / _MAX_AMP)
+
+
+def _where_dbfs(rms: np.ndarray, pred) -> np.ndarray:
+    """pred(dBFS) of every window rms, the dBFS worked out by the scalar rule once per distinct rms value."""
+    values, inverse = np.unique(rms, return_inverse=True)
+    return np.array([bool(pred(_dbfs_of_rms(int(v)))) for v in values], dtype=bool)[inverse]
+
+
 def detect_leading_silence(seg: PcmSegment, silence_threshold=-50.0, chunk_size=10) -> int:
-    trim = 0
-    while seg.dbfs_ms(trim, trim + chunk_size) < silence_threshold and trim < len(seg):
-        trim += chunk_size
-    return min(trim, len(seg))
+    n_ms = len(seg)
+    trims = np.arange(0, n_ms, chunk_size, dtype=np.int64)        # the positions the reference's loop can stop at before the end
+    loud = ~_where_dbfs(seg.rms_windows(trims, trims + chunk_size), lambda db: db < silence_threshold)
+    hit = np.flatnonzero(loud)
+    return int(trims[hit[0]]) if len(hit) else n_ms
 
 
 def remove_silence_edges(seg: PcmSegment, silence_threshold=-42) -> PcmSegment:
     """F/infer/utils_infer.py:263-277: leading silence in 10 ms chunks, trailing silence one millisecond at a time."""
     seg = seg.slice_ms(detect_leading_silence(seg, silence_threshold), len(seg) + 1)
     end = seg.duration_seconds
-    for ms in range(len(seg) - 1, -1, -1):
-        if seg.dbfs_ms(ms, ms + 1) > silence_threshold:
-            break
+    ms = np.arange(len(seg), dtype=np.int64)
+    loud = np.flatnonzero(_where_dbfs(seg.rms_windows(ms, ms + 1), lambda db: db > silence_threshold))
+    quiet_tail = len(seg) - 1 - int(loud[-1]) if len(loud) else len(seg)
+    for _ in range(quiet_tail):       # the reference's own running subtraction, rounding included
         end -= 0.001
     return seg.slice_ms(0, int(end * 1000))
 
@@ -182,9 +211,9 @@ def _clip_at_pause(seg: PcmSegment, min_silence_len: int, silence_thresh: int, s
 _ref_text_cache: dict = {}   # audio md5 -> transcription (the reference caches ASR output only; kept for interface parity)
 
 
-def preprocess_ref_audio_text(ref_audio_orig: str, ref_text: str, clip_short: bool = True, show_info=print, device=None):
-    """F/infer/utils_infer.py:282-350.  Returns (path of the processed temporary WAV, normalised ref_text)."""
-    seg = PcmSegment.from_wav(ref_audio_orig)
+def preprocess_ref_segment(seg: PcmSegment, clip_short: bool = True, show_info=print) -> PcmSegment:
+    """The audio part of F/infer/utils_infer.py:282-350 between reading the clip and writing the temporary WAV: clip at a pause
+    (`clip_short`), strip the silent edges, append 50 ms of silence."""
     if seg.rate < 11025:
         raise ValueError("reference audio below 11025 Hz is not supported on this path")
     if clip_short:
@@ -195,7 +224,19 @@ def preprocess_ref_audio_text(ref_audio_orig: str, ref_text: str, clip_short: bo
         if len(seg) > 15000:
             seg = seg.slice_ms(0, 15000)
             show_info("Audio is over 15s, clipping short. (3)")
-    seg = remove_silence_edges(seg) + PcmSegment.silent(50, seg.rate, seg.frames.shape[1])
+    return remove_silence_edges(seg) + PcmSegment.silent(50, seg.rate, seg.frames.shape[1])
+
+
+def normalize_ref_text(ref_text: str) -> str:
+    """The ". " rule at the end of the reference text (F/infer/utils_infer.py:343-348)."""
+    if not ref_text.endswith(". ") and not ref_text.endswith("。"):
+        ref_text += " " if ref_text.endswith(".") else ". "
+    return ref_text
+
+
+def preprocess_ref_audio_text(ref_audio_orig: str, ref_text: str, clip_short: bool = True, show_info=print, device=None):
+    """F/infer/utils_infer.py:282-350.  Returns (path of the processed temporary WAV, normalised ref_text)."""
+    seg = preprocess_ref_segment(PcmSegment.from_wav(ref_audio_orig), clip_short, show_info)
     with tempfile.NamedTemporaryFile(delete=False, suffix=".wav") as f:
         path = f.name
     seg.export_wav(path)
@@ -207,6 +248,4 @@ def preprocess_ref_audio_text(ref_audio_orig: str, ref_text: str, clip_short: bo
             ref_text = _ref_text_cache[audio_hash]
         else:
             raise NotImplementedError("empty ref_text: the reference transcribes the clip with a Whisper ASR pipeline, which is not on this path")
-    if not ref_text.endswith(". ") and not ref_text.endswith("。"):
-        ref_text += " " if ref_text.endswith(".") else ". "
-    return path, ref_text
+    return path, normalize_ref_text(ref_text)

@@ -11,10 +11,15 @@
 //   torch.ops.f5hip.vocos_decode_ragged(handle, mel, frames, channels, hop_length) -> Tensor (packed)                F/infer/utils_infer.py:472
 //   torch.ops.f5hip.bigvgan_forward(handle, mel, total_upsample) -> Tensor                                       F/infer/utils_infer.py:474
 //   torch.ops.f5hip.bigvgan_forward_ragged(handle, mel, frames, channels, total_upsample) -> Tensor (packed)         F/infer/utils_infer.py:474
+//   torch.ops.f5hip.ref_frontend(wave, n_in, channels, orig_freq, new_freq, taps?, rms_floor) -> (Tensor packed, Tensor rms)   F/infer/utils_infer.py:423-433
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
+
+#include <cmath>
+#include <numeric>
+#include <tuple>
 
 #include "../../include/f5hip.h"
 
@@ -197,6 +202,42 @@ at::Tensor bigvgan_forward_ragged(int64_t handle, const at::Tensor& mel, const a
     return wave;
 }
 
+// wave fp32 device, the clips packed back to back (clip i = channels[i] planes of n_in[i] samples); n_in / channels [n] int32 host; taps fp32
+// device [nf][2 width + of] (infer.resample_taps) or None when the rates are equal -> (packed mono clips at new_freq, clip i holding
+// ceil(nf n_in[i] / of) samples; rms [n] fp32 device, measured before the gain)
+std::tuple<at::Tensor, at::Tensor> ref_frontend(const at::Tensor& wave, const at::Tensor& n_in, const at::Tensor& channels, int64_t orig_freq, int64_t new_freq,
+                                                const c10::optional<at::Tensor>& taps, double rms_floor) {
+    check_dev_f32(wave, "wave"); check_host(n_in, at::kInt, "n_in"); check_host(channels, at::kInt, "channels");
+    TORCH_CHECK(n_in.dim() == 1 && n_in.numel() > 0 && channels.numel() == n_in.numel(), "f5hip::ref_frontend: n_in and channels need one value per clip");
+    TORCH_CHECK(orig_freq >= 1 && new_freq >= 1 && orig_freq <= INT32_MAX && new_freq <= INT32_MAX, "f5hip::ref_frontend: sample rates");
+    if (taps.has_value()) check_dev_f32(*taps, "taps");
+    const int64_t g = std::gcd(orig_freq, new_freq), of = orig_freq / g, nf = new_freq / g;
+    const int32_t *ni = n_in.data_ptr<int32_t>(), *ch = channels.data_ptr<int32_t>();
+    int64_t total_in = 0, total_out = 0;
+    for (int64_t i = 0; i < n_in.numel(); i++) {
+        TORCH_CHECK(ni[i] >= 1 && ch[i] >= 1, "f5hip::ref_frontend: clip ", i, " has ", ni[i], " samples in ", ch[i], " channels");
+        total_in += (int64_t)ni[i] * ch[i];
+        total_out += (nf * ni[i] + of - 1) / of;
+    }
+    TORCH_CHECK(wave.numel() == total_in, "f5hip::ref_frontend: wave needs sum(n_in * channels) = ", total_in, " samples (got ", wave.numel(), ")");
+    TORCH_CHECK(total_out <= INT32_MAX, "f5hip::ref_frontend: the outputs of the call exceed 2^31 - 1 samples");
+    if (orig_freq != new_freq) {
+        TORCH_CHECK(taps.has_value(), "f5hip::ref_frontend: ", orig_freq, " -> ", new_freq, " Hz needs the tap table");
+        // the library derives the row length itself (torchaudio's lowpass_filter_width 6, rolloff 0.99): a table of any other shape would be
+        // read with the wrong stride
+        const int64_t width = (int64_t)std::ceil(6.0 * (double)of / ((double)std::min(of, nf) * 0.99));
+        TORCH_CHECK(taps->dim() == 2 && taps->size(0) == nf && taps->size(1) == 2 * width + of, "f5hip::ref_frontend: taps must be [nf = ", nf,
+                    "][2 * width + of = ", 2 * width + of, "] (lowpass_filter_width 6, rolloff 0.99); got ", taps->sizes());
+    }
+    const c10::DeviceGuard guard(wave.device());   // allocations and stream on the wave's device
+    at::Tensor out = at::empty({total_out}, wave.options()), rms = at::empty({n_in.numel()}, wave.options());
+    const int rc = f5hip_ref_frontend((int32_t)n_in.numel(), ni, ch, wave.data_ptr<float>(), (int32_t)orig_freq, (int32_t)new_freq,
+                                      taps.has_value() && orig_freq != new_freq ? taps->data_ptr<float>() : (const float*)nullptr, (float)rms_floor,
+                                      out.data_ptr<float>(), rms.data_ptr<float>(), stream_of(wave));
+    TORCH_CHECK(rc == 0, "f5hip_ref_frontend: ", f5hip_last_error());
+    return {out, rms};
+}
+
 }   // namespace
 
 TORCH_LIBRARY(f5hip, m) {
@@ -209,4 +250,5 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("vocos_decode_ragged(int handle, Tensor mel, Tensor frames, int channels, int hop_length) -> Tensor", &vocos_decode_ragged);
     m.def("bigvgan_forward(int handle, Tensor mel, int total_upsample) -> Tensor", &bigvgan_forward);
     m.def("bigvgan_forward_ragged(int handle, Tensor mel, Tensor frames, int channels, int total_upsample) -> Tensor", &bigvgan_forward_ragged);
+    m.def("ref_frontend(Tensor wave, Tensor n_in, Tensor channels, int orig_freq, int new_freq, Tensor? taps, float rms_floor) -> (Tensor, Tensor)", &ref_frontend);
 }

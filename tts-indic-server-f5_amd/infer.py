@@ -16,12 +16,14 @@ Host-side differences, all explicit:
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import dataclasses
 import math
 import os
 import re
 import struct
+import threading
 import types
 from dataclasses import dataclass
 
@@ -117,25 +119,67 @@ def text_to_tokens(text_list):
     return out
 
 
-def resample_sinc_hann(wave: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6,
-                       rolloff: float = 0.99) -> torch.Tensor:
-    """torchaudio.transforms.Resample(orig_freq, new_freq) (call site F/infer/utils_infer.py:430-432), default
-    "sinc_interp_hann" method of torchaudio 2.6: polyphase windowed-sinc kernel applied as a strided conv1d.
-    wave [channels, n] -> [channels, ceil(n * new / orig)]."""
-    import math
-    if orig_freq == new_freq:
-        return wave
-    g = math.gcd(int(orig_freq), int(new_freq))
-    of, nf = int(orig_freq) // g, int(new_freq) // g
+MAX_TAP_TABLE_BYTES = 4 << 20   # resample_taps refuses larger tables (the largest supported pair, 11 025 -> 24 000 Hz, needs 206 KB)
+TAP_TABLE_CACHE = 16             # rate pairs kept, on the host and per device: an upload chooses its rate, so neither cache may grow with it
+_tap_tables: collections.OrderedDict = collections.OrderedDict()   # (orig_freq, new_freq, lowpass_filter_width, rolloff) -> resample_taps result
+
+
+_tap_lock = threading.Lock()     # route handlers look tables up from a thread pool
+
+
+def _lru_get(cache, key):
+    with _tap_lock:
+        hit = cache.get(key)
+        if hit is not None:
+            cache.move_to_end(key)
+        return hit
+
+
+def _lru_put(cache, key, value):
+    with _tap_lock:
+        cache[key] = value
+        while len(cache) > TAP_TABLE_CACHE:
+            cache.popitem(last=False)
+        return value
+
+
+def resample_taps(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """The polyphase kernel of torchaudio.transforms.Resample(orig_freq, new_freq) ("sinc_interp_hann", torchaudio 2.6):
+    (of, nf, width, taps fp32 [nf, 2 * width + of]) with of : nf the reduced rate pair -- computed in fp64, then cast to fp32.  Output
+    j = q * nf + p of a clip is sum_k taps[p][k] * xpad[q * of + k], xpad = the clip with `width` zeros in front and `width + of` behind.
+    Cached per rate pair, the `TAP_TABLE_CACHE` most recently used ones (treat the table as read-only).  A table above 4 MiB raises ValueError (e.g. 44 101 -> 24 000 Hz: several GB)."""
+    key = (int(orig_freq), int(new_freq), lowpass_filter_width, rolloff)
+    hit = _lru_get(_tap_tables, key)
+    if hit is not None:
+        return hit
+    if key[0] < 1 or key[1] < 1:
+        raise ValueError(f"sample rates must be positive (got {orig_freq} -> {new_freq})")
+    g = math.gcd(key[0], key[1])
+    of, nf = key[0] // g, key[1] // g
     base_freq = min(of, nf) * rolloff
     width = math.ceil(lowpass_filter_width * of / base_freq)
+    nbytes = 4 * nf * (2 * width + of)
+    if nbytes > MAX_TAP_TABLE_BYTES:
+        raise ValueError(f"resampling {orig_freq} -> {new_freq} Hz needs a {nf} x {2 * width + of} tap table ({nbytes} bytes, limit {MAX_TAP_TABLE_BYTES}): "
+                         "unsupported sample-rate pair")
     idx = torch.arange(-width, width + of, dtype=torch.float64)[None, None] / of
     t = torch.arange(0, -nf, -1, dtype=torch.float64)[:, None, None] / nf + idx
     t = (t * base_freq).clamp(-lowpass_filter_width, lowpass_filter_width)
     window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
     t = t * math.pi
     kernels = torch.where(t == 0, torch.ones_like(t), t.sin() / t) * window * (base_freq / of)
-    kernels = kernels.to(torch.float32)
+    return _lru_put(_tap_tables, key, (of, nf, width, kernels.to(torch.float32)[:, 0].contiguous()))
+
+
+def resample_sinc_hann(wave: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6,
+                       rolloff: float = 0.99) -> torch.Tensor:
+    """torchaudio.transforms.Resample(orig_freq, new_freq) (call site F/infer/utils_infer.py:430-432), default
+    "sinc_interp_hann" method of torchaudio 2.6: polyphase windowed-sinc kernel (`resample_taps`) applied as a strided conv1d.
+    wave [channels, n] -> [channels, ceil(n * new / orig)]."""
+    if orig_freq == new_freq:
+        return wave
+    of, nf, width, taps = resample_taps(orig_freq, new_freq, lowpass_filter_width, rolloff)
+    kernels = taps[:, None]
     shape = wave.shape
     w = wave.reshape(-1, shape[-1]).to(torch.float32)
     length = w.shape[-1]
@@ -144,6 +188,14 @@ def resample_sinc_hann(wave: torch.Tensor, orig_freq: int, new_freq: int, lowpas
     out = out.transpose(1, 2).reshape(w.shape[0], -1)
     target = math.ceil(nf * length / of)
     return out[..., :target].reshape(*shape[:-1], target)
+
+
+def resampled_length(n: int, orig_freq: int, new_freq: int) -> int:
+    """Samples `resample_sinc_hann` returns for n: ceil(nf * n / of), in integers (its math.ceil of the float quotient gives the same for
+    every clip length in reach: an exact quotient is an exact float, and no other comes within an ulp of an integer below 2^52)."""
+    g = math.gcd(int(orig_freq), int(new_freq))
+    of, nf = int(orig_freq) // g, int(new_freq) // g
+    return -(-nf * int(n) // of)
 
 
 _WAVE_FORMAT_PCM, _WAVE_FORMAT_IEEE_FLOAT, _WAVE_FORMAT_EXTENSIBLE = 0x0001, 0x0003, 0xFFFE
@@ -378,7 +430,11 @@ class PreparedVoice:
     """The per-voice part of `infer_process` done once: the reference wave after mono mix / rms gain / resampling
     (F/infer/utils_infer.py:423-433), its measured rms, its duration in seconds before resampling (the `max_chars` rule, :379) and --
     filled in by the first request that uses it -- the reference mel on the device (the "reference latents": 188 KB for a 5 s
-    prompt).  `serve.TTSManager` keeps one per voice; `infer_requests` accepts it wherever a `ref_audio` is expected."""
+    prompt).  `serve.TTSManager` keeps one per voice; `infer_requests` accepts it wherever a `ref_audio` is expected.
+
+    `PreparedVoice.deferred((wave, sr), target_rms)` is the same voice before any arithmetic on its samples: `seconds` and `ref_frames`
+    follow from the clip's length alone (so a request can be planned), `audio` / `rms` / `mel` are filled in by `prepare_voices` -- one
+    ragged front-end call on the device for all deferred voices of a batch (`infer_requests`, `SpanScheduler`)."""
 
     def __init__(self, ref_audio, target_rms=0.1, device=None):
         wav, sr = ref_audio if isinstance(ref_audio, tuple) else load_wav(ref_audio)
@@ -386,14 +442,88 @@ class PreparedVoice:
         self.audio, self.rms = _prepare_reference(wav, sr, target_rms, device)
         self.ref_frames = self.audio.shape[-1] // hop_length
         self.mel = None
+        self.pending = None
+
+    @classmethod
+    def deferred(cls, ref_audio, target_rms=0.1):
+        wav, sr = ref_audio
+        if wav.dim() != 2 or wav.shape[-1] < 1:
+            raise ValueError(f"reference audio must be [channels, samples] with at least one sample (got {tuple(wav.shape)})")
+        if sr != target_sample_rate:
+            resample_taps(sr, target_sample_rate)   # an unsupported rate pair is refused here, before anything is queued
+        voice = cls.__new__(cls)
+        voice.seconds = wav.shape[-1] / sr
+        voice.ref_frames = resampled_length(wav.shape[-1], sr, target_sample_rate) // hop_length
+        voice.audio = voice.rms = voice.mel = None
+        voice.pending = (wav, int(sr), target_rms)
+        return voice
 
     def cond(self, model_obj):
         """What to hand the sampler as the prompt: the cached mel [1, n, mel] when the model object can compute one, else the wave."""
+        if self.pending is not None:
+            _prepare_deferred([self], model_obj)
         if not hasattr(model_obj, "cond_mel"):
             return self.audio
         if self.mel is None:
             self.mel = model_obj.cond_mel(self.audio)
         return self.mel
+
+
+def prepare_voices(clips, target_rms=0.1, device="cuda"):
+    """The reference-audio front-end (mono mix, rms, gain, resampling to 24 kHz) of several voices at once on the device: one upload of the
+    packed clips and ONE `ops.ref_frontend` call (two launches) per distinct sample rate, then one download of all rms values.
+    `clips` = [(wave [ch, n] fp32, sr)] -> [PreparedVoice], or deferred `PreparedVoice`s, which are filled in place (and returned).
+    The mel stays lazy (`cond`), one call per clip.  `device=None` runs the host `_prepare_reference` clip by clip instead (what a model
+    object without the device front-end gets: the reference's modules, CPU stand-ins) and leaves the result on the host, like the eager
+    constructor does."""
+    voices = [c if isinstance(c, PreparedVoice) else PreparedVoice.deferred(c, target_rms) for c in clips]
+    todo = [v for v in voices if v.pending is not None]
+    if device is None:
+        for v in todo:
+            wav, sr, floor = v.pending
+            v.audio, v.rms = _prepare_reference(wav, sr, floor, None)
+            v.pending = None
+        return voices
+    from . import ops
+    groups = {}
+    for v in todo:
+        groups.setdefault((v.pending[1], float(v.pending[2])), []).append(v)
+    done = []
+    for (sr, floor), vs in groups.items():
+        packed = torch.cat([v.pending[0].to(torch.float32).reshape(-1) for v in vs]).to(device)
+        taps = None if sr == target_sample_rate else _device_taps(sr, target_sample_rate, packed.device)
+        out, rms, n_out = ops.ref_frontend(packed, [v.pending[0].shape[-1] for v in vs], [v.pending[0].shape[0] for v in vs], sr,
+                                           target_sample_rate, taps, floor)
+        done.append((vs, out.split(n_out), rms))
+    if done:
+        all_rms = torch.cat([rms for _, _, rms in done]).cpu()   # the one download
+        k = 0
+        for vs, outs, _ in done:
+            for v, audio in zip(vs, outs):
+                v.audio, v.rms, v.pending = audio[None], all_rms[k], None
+                k += 1
+    return voices
+
+
+_taps_on_device: collections.OrderedDict = collections.OrderedDict()   # (orig_freq, new_freq, device) -> the tap table there
+
+
+def _device_taps(orig_freq, new_freq, device):
+    key = (int(orig_freq), int(new_freq), str(device))
+    hit = _lru_get(_taps_on_device, key)
+    return hit if hit is not None else _lru_put(_taps_on_device, key, resample_taps(orig_freq, new_freq)[3].to(device))
+
+
+def _prepare_deferred(voices, model_obj):
+    """The deferred voices among `voices` (each once) through the model object's `prepare_voices` (F5HipModel, ShardedSampler: the device
+    front-end, one ragged call), or through the host front-end when it has none."""
+    todo = list({id(v): v for v in voices if v.pending is not None}.values())
+    if not todo:
+        return
+    if hasattr(model_obj, "prepare_voices"):
+        model_obj.prepare_voices(todo)
+    else:
+        prepare_voices(todo, device=None)
 
 
 def _plan_request(ref_audio, ref_text, gen_text, target_rms, speed, fix_duration, device, tokenizer):
@@ -554,14 +684,14 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     from the global generator in flat request order (unit by unit, request after request) when there is one sampler call, i.e. always
     with a `per_unit_time_grids` model, and in sampler-call order otherwise."""
     defaults = dict(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None)
-    plans, calls = [], {}   # calls: (nfe_step, sway, ode_method) -> [unit ids, ...] of one sampler call each
+    calls = {}   # calls: (nfe_step, sway, ode_method) -> [unit ids, ...] of one sampler call each
     flat_units, flat_cond, flat_audio, flat_cfg, flat_gen, flat_grid = [], [], [], [], [], []
-    for req in requests:
-        plan = plan_request(req, defaults, target_rms=target_rms, fix_duration=fix_duration, device=device, tokenizer=tokenizer)
+    plans = [plan_request(req, defaults, target_rms=target_rms, fix_duration=fix_duration, device=device, tokenizer=tokenizer) for req in requests]
+    _prepare_deferred([plan.voice for plan in plans], model_obj)   # uploaded clips: one ragged front-end call for all of them
+    for plan in plans:
         voice, units, opts = plan.voice, plan.units, plan.opts
         key = (int(opts["nfe_step"]), opts["sway_sampling_coef"], opts.get("ode_method"))
         calls.setdefault(key, []).extend(range(len(flat_units), len(flat_units) + len(units)))
-        plans.append(plan)
         flat_units += units
         flat_cond += [voice.cond(model_obj)] * len(units)
         flat_audio += [voice.audio] * len(units)
@@ -657,6 +787,11 @@ class SpanScheduler:
     @property
     def busy(self) -> bool:
         return bool(self.waiting or self.in_flight)
+
+    def prepare(self, requests):
+        """The device front-end of the deferred voices (`PreparedVoice.deferred`: uploaded clips) among `requests`, in ONE `prepare_voices`
+        call, ahead of their `admit`; a voice that is still deferred at `admit` is prepared there, alone."""
+        _prepare_deferred([r[0] for r in requests if isinstance(r[0], PreparedVoice)], self.model_obj)
 
     def admit(self, request) -> SpanTicket:
         plan = plan_request(request, self.defaults, target_rms=self.target_rms, fix_duration=self.fix_duration, device=self.device,

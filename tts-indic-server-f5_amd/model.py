@@ -312,6 +312,12 @@ class F5HipModel:
         assert cond.shape[-1] == self.num_channels
         return cond
 
+    def prepare_voices(self, voices):
+        """The reference-audio front-end of deferred `infer.PreparedVoice`s on this model's device: `infer.prepare_voices`, one ragged
+        f5hip_ref_frontend call per distinct sample rate."""
+        from .infer import prepare_voices
+        return prepare_voices(voices, device=self.device)
+
     @torch.no_grad()
     def sample_units(self, audio, units, *, steps=32, cfg_strength=2.0, sway_sampling_coef=-1.0, seed=None, generators=None, y0=None,
                      ode_method=None):

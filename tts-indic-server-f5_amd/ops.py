@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, torch_ops
 
 ACT = {"none": 0, "gelu_tanh": 1, "gelu_erf": 2, "mish": 3, "silu": 4}
 
@@ -333,3 +333,37 @@ def time_table(model, t):
     _lib.check(_lib.lib().f5hip_op_time_table(model._h, _p(th), n_t, _p(sinus), _p(mod), cols, _p(temb), _lib.current_stream_ptr()),
                "f5hip_op_time_table")
     return sinus, mod, temb
+
+
+def ref_frontend(wave, n_in, channels, orig_freq, new_freq, taps=None, rms_floor=0.1):
+    """The reference-audio front-end of several clips of one sample-rate pair in ONE library call (include/f5hip.h f5hip_ref_frontend): mono
+    mix, rms, gain up to `rms_floor`, polyphase sinc resampling.  wave: fp32 device tensor, the clips packed back to back, clip i as
+    channels[i] planes of n_in[i] samples; taps: fp32 device [nf, 2 width + of] (`infer.resample_taps`), not needed when the rates are
+    equal.  Returns (out packed fp32 device, rms [n] fp32 device -- measured before the gain --, [n_out_i]); clip i's part of `out` and its
+    rms equal its own call's, bit for bit."""
+    ni = np.ascontiguousarray(np.asarray(n_in, dtype=np.int32))
+    ch = np.ascontiguousarray(np.asarray(channels, dtype=np.int32))
+    assert wave.dtype == torch.float32 and wave.is_contiguous() and wave.is_cuda
+    assert taps is None or (taps.dtype == torch.float32 and taps.is_contiguous() and taps.is_cuda)
+    g = int(np.gcd(int(orig_freq), int(new_freq)))
+    of, nf = int(orig_freq) // g, int(new_freq) // g
+    n_out = [(nf * int(v) + of - 1) // of for v in ni]
+    if of != nf:   # the library derives the row length itself (lowpass_filter_width 6, rolloff 0.99): refuse a table of another shape
+        width = int(np.ceil(6.0 * of / (min(of, nf) * 0.99)))
+        if taps is None or tuple(taps.shape) != (nf, 2 * width + of):
+            raise _lib.F5HipError(f"ref_frontend: taps must be [{nf}, {2 * width + of}] for {orig_freq} -> {new_freq} Hz "
+                                  f"(got {None if taps is None else tuple(taps.shape)})")
+    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
+        try:
+            out, rms = torch_ops.ops().ref_frontend(wave, torch.from_numpy(ni), torch.from_numpy(ch), int(orig_freq), int(new_freq), taps, float(rms_floor))
+        except RuntimeError as e:   # c10::Error from the operator's checks or the library
+            raise _lib.F5HipError(str(e)) from e
+    else:
+        if len(ni) < 1 or len(ch) != len(ni) or int((ni.astype(np.int64) * ch).sum()) != wave.numel():
+            raise _lib.F5HipError("ref_frontend: wave needs sum(n_in * channels) samples, one (n_in, channels) pair per clip")
+        with torch.cuda.device(wave.device):
+            out = torch.empty(max(sum(n_out), 0), device=wave.device, dtype=torch.float32)
+            rms = torch.empty(len(ni), device=wave.device, dtype=torch.float32)
+            _lib.check(_lib.lib().f5hip_ref_frontend(len(ni), _p(ni), _p(ch), _p(wave), int(orig_freq), int(new_freq), _p(taps), float(rms_floor),
+                                                     _p(out), _p(rms), _lib.current_stream_ptr()), "f5hip_ref_frontend")
+    return out, rms, n_out

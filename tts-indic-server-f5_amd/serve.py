@@ -25,6 +25,8 @@ Differences, explicit:
 
 import base64
 import binascii
+import collections
+import hashlib
 import io
 import logging
 import queue
@@ -40,7 +42,7 @@ import math
 
 import numpy as np
 
-from . import infer
+from . import audio_prep, infer
 
 log = logging.getLogger(__name__)
 
@@ -87,6 +89,12 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
                 raise ValueError(f"speed must be greater than 0 (got {v}).")
         out[k] = v
     return out
+
+
+# Whether uploaded reference clips take the device front-end unless `TTSManager(device_frontend=...)` says otherwise: it does when it beat
+# the host front-end for ONE clip by more than that run's own spread (tools/ref_frontend_bench.py, profiles/ref_frontend_bench.txt)
+DEVICE_FRONTEND_DEFAULT = True
+
 
 @dataclass
 class Voice:
@@ -226,7 +234,8 @@ class ContinuousBatcher(_QueueWorker):
 
     `submit(request, on_start=None)` returns a `concurrent.futures.Future`.  One worker thread alternates between admission and spans: it
     blocks on the queue only while nothing is in flight; otherwise it takes what has arrived without waiting, admits it
-    (`scheduler.admit`: the request is planned and draws its noise; `on_start()` is called right after, so what it submits is admitted at
+    (`scheduler.admit`: the request is planned and draws its noise -- an uploaded clip's front-end runs first, together with those of the
+    uploads already queued, `_prepare`; `on_start()` is called right after, so what it submits is admitted at
     the next boundary -- a stream's tail right behind its head), runs ONE span (`scheduler.step()`) under `lock` -- `TTSManager` passes
     its device lock, so a speech edit runs between two spans -- and resolves the futures of the requests that finished.  A request whose
     planning fails gets that error alone.  A future stays cancellable until it is resolved: cancelled while queued it is never admitted,
@@ -254,10 +263,27 @@ class ContinuousBatcher(_QueueWorker):
             else:
                 future.set_result(result)
 
+    def _prepare(self, request):
+        """Ahead of admitting a request whose voice is an upload that is still deferred: its front-end together with that of every deferred
+        voice already waiting in the queue, in ONE `scheduler.prepare` call under the lock, so uploads that arrive together share one
+        ragged device call and the queued ones find their voice prepared when their turn comes.  Admission itself stays one request at a
+        time, in order.  A failure here is logged and left to the admissions: each then prepares its own voice and fails alone."""
+        prepare = getattr(self.scheduler, "prepare", None)
+        if prepare is None or getattr(request[0], "pending", None) is None:
+            return
+        with self._q.mutex:
+            queued = [item[0] for item in self._q.queue if item is not None and not item[1].cancelled()]
+        try:
+            with self._lock:
+                prepare([request] + [r for r in queued if getattr(r[0], "pending", None) is not None])
+        except Exception:   # noqa: BLE001
+            log.exception("preparing uploaded reference clips together failed; each request now prepares its own")
+
     def _admit(self, request, future, on_start):
         if future.cancelled():                        # cancelled while queued: never admitted
             future.set_running_or_notify_cancel()
             return
+        self._prepare(request)
         try:
             with self._lock:
                 ticket = self.scheduler.admit(request)
@@ -342,7 +368,7 @@ class TTSManager:
 
     def __init__(self, loader: Callable[[], tuple] | None = None, nfe_step: int = infer.nfe_step, cfg_strength: float = infer.cfg_strength,
                  sway_sampling_coef: float = infer.sway_sampling_coef, speed: float = infer.speed, mel_spec_type: str = "vocos",
-                 micro_batch: dict | None = None, batch_invariant: bool = True):
+                 micro_batch: dict | None = None, batch_invariant: bool = True, clip_cache: int = 64, device_frontend: bool | None = None):
         self.loader = loader
         self.batch_invariant = batch_invariant   # False: leave the model's attention mode alone (fastest kernel per launch shape)
         self.micro_batch = micro_batch            # e.g. dict(max_requests=16, max_wait_ms=5): batch concurrent requests; with span_steps
@@ -356,6 +382,16 @@ class TTSManager:
         self.mel_spec_type = mel_spec_type
         self._prep_cache: dict = {}   # prompt path -> (PreparedVoice, ref_text): clip / trim / resample / mel run once per voice
         self._prep_lock = threading.Lock()   # route handlers run in a thread pool: concurrent first requests of a voice prepare it once
+        # Uploaded clips (`synthesize_clip`): (sha1 of the upload, ref_text, clip_short) -> (PreparedVoice, ref_text), least recently used
+        # first, at most `clip_cache` entries (each holds the prepared wave and its device mel).  `_clip_lock` guards the two tables only;
+        # the preparation itself runs under the key's own lock, so one slow upload does not stall other voices.
+        self.clip_cache = int(clip_cache)
+        self._clip_cache: collections.OrderedDict = collections.OrderedDict()
+        self._clip_key_locks: dict = {}      # key -> [lock, threads using it]
+        self._clip_lock = threading.Lock()
+        # True: an uploaded clip's mono mix / rms gain / resampling run on the device (`infer.prepare_voices`, one ragged call for all new
+        # voices of a batch); False: on the host, before the request is queued.  None: DEVICE_FRONTEND_DEFAULT (profiles/ref_frontend_bench.txt)
+        self.device_frontend = DEVICE_FRONTEND_DEFAULT if device_frontend is None else bool(device_frontend)
         # The library allows ONE call in flight per handle (include/f5hip.h), the sampler keeps per-call state and noise comes from torch's
         # global generator: every entry into the device path takes this lock.  Without a batcher, concurrent HTTP requests therefore run one
         # after the other, like the reference's blocking `async def` handlers (S/routes/speech.py:19-41).
@@ -440,6 +476,99 @@ class TTSManager:
         if self.batcher is not None:   # wait for the batch this request rides in (the route runs in a worker thread, see create_app)
             return self.batcher.submit(req).result(timeout=self.request_timeout_s)
         return self._run_batch([req])[0]
+
+    def _clip_voice(self, ref_audio, ref_text, clip_short=True):
+        """(PreparedVoice, normalised ref_text) of an uploaded clip -- WAV bytes or a (wave [ch, n], sr) pair -- prepared once per
+        (content, ref_text, clip_short) and kept in the LRU cache.  Host work only: read, quantise to int16 (16-bit PCM passes through bit for
+        bit; any other format as clip(round(x * 32768), -32768, 32767) -- pydub would hand those to ffmpeg), the silence pre-step
+        (`audio_prep.preprocess_ref_segment`), back to float32.  With `device_frontend` the voice is deferred: its mono mix / gain /
+        resampling run on the device with the batch it first rides in.  Everything that can be refused is refused here with ValueError,
+        before anything is queued: an empty `ref_text`, an unreadable WAV, a rate below 11 025 Hz, non-finite samples, a clip that is
+        empty or all-zero after the pre-step, a rate pair whose tap table is refused."""
+        import torch
+        if not ref_text or not ref_text.strip():
+            raise ValueError("Reference text cannot be empty.")
+        h = hashlib.sha1()
+        if isinstance(ref_audio, tuple):
+            arr = np.ascontiguousarray(ref_audio[0].detach().cpu().numpy())
+            h.update(repr((arr.shape, str(arr.dtype), int(ref_audio[1]))).encode())
+            h.update(arr.tobytes())
+        else:
+            ref_audio = bytes(ref_audio)
+            h.update(ref_audio)
+        key = (h.hexdigest(), ref_text, bool(clip_short))
+        with self._clip_lock:
+            if key in self._clip_cache:
+                self._clip_cache.move_to_end(key)
+                return self._clip_cache[key]
+            entry = self._clip_key_locks.setdefault(key, [threading.Lock(), 0])
+            entry[1] += 1
+        try:
+            with entry[0]:
+                with self._clip_lock:
+                    if key in self._clip_cache:      # prepared while this thread waited for the key
+                        self._clip_cache.move_to_end(key)
+                        return self._clip_cache[key]
+                if isinstance(ref_audio, tuple):
+                    wave, sr = ref_audio[0].detach().cpu().to(torch.float32), int(ref_audio[1])
+                else:
+                    try:
+                        wave, sr = infer.load_wav(ref_audio)
+                    except ValueError as e:
+                        raise ValueError(f"Invalid audio: {e}") from e
+                if wave.dim() != 2 or wave.shape[0] < 1:
+                    raise ValueError(f"Invalid audio: expected [channels, samples] (got {tuple(wave.shape)})")
+                x = wave.numpy()
+                if not np.isfinite(x).all():
+                    raise ValueError("Invalid audio: the clip has non-finite samples.")
+                pcm = np.clip(np.rint(x.astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
+                seg = audio_prep.preprocess_ref_segment(audio_prep.PcmSegment(np.ascontiguousarray(pcm.T), sr), clip_short, show_info=lambda *_: None)
+                if seg.frames.shape[0] == 0 or not seg.frames.any():
+                    raise ValueError("Invalid audio: the clip is empty or silent.")
+                clip = (torch.from_numpy(np.ascontiguousarray((seg.frames.astype(np.float32) / 32768.0).T)), seg.rate)
+                if seg.rate != infer.target_sample_rate:
+                    infer.resample_taps(seg.rate, infer.target_sample_rate)      # refuses a rate pair it has no table for
+                voice = infer.PreparedVoice.deferred(clip) if self.device_frontend else infer.PreparedVoice(clip)
+                value = (voice, audio_prep.normalize_ref_text(ref_text))
+                with self._clip_lock:
+                    self._clip_cache[key] = value
+                    while len(self._clip_cache) > max(self.clip_cache, 0):
+                        self._clip_cache.popitem(last=False)
+                return value
+        finally:
+            with self._clip_lock:
+                entry[1] -= 1
+                if entry[1] == 0:
+                    self._clip_key_locks.pop(key, None)
+
+    def synthesize_clip(self, text, ref_audio, ref_text, *, clip_short=True, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
+                        seed=None, ode_method=None):
+        """`synthesize` with the caller's own reference clip instead of a registered voice: `ref_audio` is a WAV file's bytes or a
+        (wave [ch, n], sr) pair, `ref_text` its transcript; `clip_short` as in `preprocess_ref_audio_text`.  The clip never touches the
+        disk (`_clip_voice`); the request then takes the same batcher path as `synthesize`, with the same options."""
+        if not self.model:
+            raise ValueError("TTS model not loaded")
+        opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
+                                    ode_method=ode_method)
+        voice, ref_text_n = self._clip_voice(ref_audio, ref_text, clip_short)
+        req = self._request(voice, ref_text_n, text, opts)
+        if self.batcher is not None:
+            return self.batcher.submit(req).result(timeout=self.request_timeout_s)
+        return self._run_batch([req])[0]
+
+    def synthesize_clip_stream(self, text, ref_audio, ref_text, *, clip_short=True, speed=None, nfe_step=None, cfg_strength=None,
+                               sway_sampling_coef=None, seed=None, ode_method=None):
+        """`synthesize_stream` with an uploaded reference clip (`synthesize_clip`): an iterator of float32 pieces whose concatenation is
+        `synthesize_clip`'s wave given the same noise."""
+        if not self.model:
+            raise ValueError("TTS model not loaded")
+        opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
+                                    ode_method=ode_method)
+        voice, ref_text_n = self._clip_voice(ref_audio, ref_text, clip_short)
+        chunks = infer.request_chunks(ref_text_n, voice.seconds, text)
+        if "seed" in opts:
+            opts["generator"] = infer.request_generator(opts.pop("seed"))
+        return self._stream(voice, ref_text_n, chunks[:1], chunks[1:], opts)
 
     def synthesize(self, text, ref_audio_path, ref_text, *, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None, seed=None,
                    ode_method=None):
@@ -605,7 +734,8 @@ def stream_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, r
 def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     """FastAPI app with the reference's `/v1/audio/speech` route (`S/routes/speech.py:19-41`) and `/v1/audio/edit` (speech editing:
     JSON body {"audio": base64 WAV, "text": the full new transcript, "parts_to_edit": [[start_s, end_s], ...], "fix_duration": [...] | null}
-    -> the edited recording as WAV).  Both speech routes take `"stream": true`: the WAV then arrives chunk by chunk (`_run_stream`), its
+    -> the edited recording as WAV), plus `/v1/audio/speech/clone`: `/v1/audio/speech/voice` with the caller's own reference clip
+    ({"text", "ref_audio": base64 WAV, "ref_text", "clip_short": true, ...}) instead of a registered voice's name.  The speech routes take `"stream": true`: the WAV then arrives chunk by chunk (`_run_stream`), its
     PCM samples identical to the unstreamed response's.  Every route also takes the optional sampler fields `nfe_step`, `cfg_strength`,
     `sway_sampling_coef`, `seed`, `ode_method` ("euler", "midpoint" or "rk4": the request's ODE solver) and (speech routes) `speed`, checked
     before anything is queued (400 with `check_request_options`'s message); an omitted field is the manager's setting (`ode_method`: the
@@ -638,6 +768,14 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         text: str
         parts_to_edit: list[list[float]]
         fix_duration: list[float] | None = None
+
+    class CloneRequest(SamplerFields):               # zero-shot cloning from the caller's own clip; JSON (base64 WAV), not multipart
+        text: str
+        ref_audio: str
+        ref_text: str
+        clip_short: bool = True
+        stream: bool = False
+        speed: float | None = None
 
     def _options(req, allowed):
         """The request's sampler fields, checked (400) before anything is queued."""
@@ -695,6 +833,25 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         finally:
             pieces.close()
 
+    def _run_clone(req):
+        """`/v1/audio/speech/clone`: the speech routes' checks, then the clip's (`TTSManager._clip_voice`: 400 with its message), then
+        `synthesize_clip` -- or, with stream=true, `synthesize_clip_stream` with the first piece synthesized before the response exists."""
+        opts = _speech_options(req.text, req)
+        try:
+            raw = base64.b64decode(req.ref_audio, validate=True)
+        except (binascii.Error, ValueError):
+            raise HTTPException(status_code=400, detail="Audio must be a base64-encoded WAV file.")
+        headers = {"Content-Disposition": "attachment; filename=synthesized_speech.wav"}
+        try:
+            if req.stream:
+                pieces = tts_manager.synthesize_clip_stream(req.text, raw, req.ref_text, clip_short=req.clip_short, **opts)
+                first = next(pieces, None)
+                return StreamingResponse(_pcm_body(first, pieces), media_type="audio/wav", headers=headers)
+            wave = tts_manager.synthesize_clip(req.text, raw, req.ref_text, clip_short=req.clip_short, **opts)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        return StreamingResponse(wav_bytes(wave), media_type="audio/wav", headers=headers)
+
     def _run_edit(req):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
@@ -729,6 +886,10 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     async def synthesize_with_voice(request: SynthesizeRequest):     # the generic form the reference's helper already supports
         return await run_in_threadpool(_run_stream if request.stream else _run, request.text, request.ref_audio_name, request.ref_text,
                                        "synthesized_speech.wav", request)
+
+    @router.post("/audio/speech/clone", response_class=StreamingResponse)
+    async def synthesize_with_clip(request: CloneRequest):          # the caller's own reference clip (TTSManager.synthesize_clip)
+        return await run_in_threadpool(_run_clone, request)
 
     @router.post("/audio/edit", response_class=StreamingResponse)
     async def edit_speech(request: EditRequest):                    # speech editing (F/infer/speech_edit.py) over the same manager
@@ -782,6 +943,11 @@ class ShardedSampler:
     # what infer.* needs from a model object
     def cond_mel(self, audio):
         return self.local.cond_mel(audio)
+
+    def prepare_voices(self, voices):
+        if hasattr(self.local, "prepare_voices"):
+            return self.local.prepare_voices(voices)
+        return infer.prepare_voices(voices, device=None)
 
     def sample_units(self, audio, units, **knobs):
         if self.failed:
