@@ -429,6 +429,28 @@ int f5hip_mel_spectrogram_bigvgan(int32_t batch, int32_t n_samples, const float*
 int f5hip_ref_frontend(int32_t n, const int32_t* n_in, const int32_t* channels, const float* wave_dev, int32_t orig_freq, int32_t new_freq,
                        const float* taps_dev, float rms_floor, float* out_dev, float* rms_dev, void* stream);
 
+/* ---------------------------------------------------------------- waveform back-end ------------------ */
+
+/* Tail of infer_batch_process (F/infer/utils_infer.py:485-519: the cross-fade join of a request's chunk waves) and
+ * remove_silence_for_generated_wav (F/infer/utils_infer.py:530-539) for n requests in one call: chunk waves in, finished 16-bit PCM out.
+ *   chunks_per_request[i]  host, >= 1; the chunks of all requests follow each other in chunk_dev / chunk_len, in request and chunk order
+ *   chunk_dev[c]           host array of device pointers: chunk c's fp32 samples (4-byte aligned), the rms gain already applied
+ *   chunk_len[c]           host, samples of chunk c (>= 1)
+ *   fade                   cross-fade length in samples; 0: plain concatenation
+ *   remove_silence[i]      host (or null: none), non-zero: pauses of 1 s or more below -50 dBFS are cut down to 500 ms on each side
+ *   pcm_dev                int16, 16-byte aligned; request i starts at sum_{j<i} ((N_j + 7) & ~7) with N = sum(len) - (k - 1) fade joined samples
+ *   len_dev                int32 [n]: the samples request i ends up with (N_i without silence removal)
+ * Joined sample j is a chunk sample, or in a fade prev[len - F + t] * ramp[F - 1 - t] + next[t] * ramp[t] in fp64 (ramp = np.linspace(0, 1, F),
+ * products and sum rounded one by one), rounded to fp32; the PCM is rint(x * 32768), half to even, clipped to [-32768, 32767].  With every
+ * chunk at least 2 * fade samples long this equals the reference's nested cross-fade bit for bit; the silence rule is pydub's
+ * split_on_silence(min_silence_len=1000, silence_thresh=-50, keep_silence=500, seek_step=10) on integers.
+ * One launch, three when a request asks for silence removal (counters wave_finish_launches, wave_finish_requests); the length tables are
+ * copied on `stream`, which the call waits for once before it launches.  A request's samples do not depend on what else is in the call.
+ * Refused before the first launch: n < 1, a request without chunks, an empty chunk, fade < 0, with fade > 0 a chunk shorter than 2 * fade
+ * in a request of several chunks, sample_rate != 24000, more than 2^31 - 1 samples in or out. */
+int f5hip_wave_finish(int32_t n, const int32_t* chunks_per_request, const float* const* chunk_dev, const int32_t* chunk_len, int32_t fade,
+                      const uint8_t* remove_silence, int32_t sample_rate, int16_t* pcm_dev, int32_t* len_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

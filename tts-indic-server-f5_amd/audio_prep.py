@@ -249,3 +249,21 @@ def preprocess_ref_audio_text(ref_audio_orig: str, ref_text: str, clip_short: bo
         else:
             raise NotImplementedError("empty ref_text: the reference transcribes the clip with a Whisper ASR pipeline, which is not on this path")
     return path, normalize_ref_text(ref_text)
+
+
+def remove_silence_pcm(pcm_int16, rate: int = 24000) -> np.ndarray:
+    """`remove_silence_for_generated_wav` (F/infer/utils_infer.py:530-539) on mono int16 samples: `split_on_silence(min_silence_len=1000,
+    silence_thresh=-50, keep_silence=500, seek_step=10)` and the pieces concatenated, so every pause of 1 s or more shrinks to the 500 ms
+    on each side of it.  Like pydub's millisecond slicing, the result ends at `min(int(len_ms * rate / 1000), n)`: up to half a millisecond
+    of samples past the last whole millisecond is dropped, and a wave without any pause comes back as that prefix.
+
+    It acts on the int16 samples the routes emit, `rint(float32_wave * 32768)` clipped (`serve.pcm16`).  The reference runs the step on
+    the file `sf.write` produced, and libsndfile's float -> PCM_16 scale may differ from that rule by one LSB; parity with it is unpinned,
+    like the rest of this module."""
+    pcm = np.asarray(pcm_int16)
+    if pcm.dtype != np.int16 or pcm.ndim != 1:
+        raise ValueError(f"remove_silence_pcm: mono int16 samples expected (got {pcm.dtype}, {pcm.ndim} dimensions)")
+    pieces = split_on_silence(PcmSegment(pcm, rate), min_silence_len=1000, silence_thresh=-50, keep_silence=500, seek_step=10)
+    if not pieces:
+        return np.zeros(0, dtype=np.int16)
+    return np.ascontiguousarray(np.concatenate([p.frames[:, 0] for p in pieces]))

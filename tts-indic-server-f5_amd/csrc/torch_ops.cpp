@@ -20,7 +20,9 @@
 #include <cmath>
 #include <numeric>
 #include <tuple>
+#include <vector>
 
+//   torch.ops.f5hip.wave_finish(chunks[], chunks_per_request, fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/utils_infer.py:485-519,530-539
 #include "../../include/f5hip.h"
 
 namespace {
@@ -238,6 +240,49 @@ std::tuple<at::Tensor, at::Tensor> ref_frontend(const at::Tensor& wave, const at
     return {out, rms};
 }
 
+// chunks: the chunk waves of all requests in request and chunk order, each a contiguous 1-D fp32 device tensor (views of the vocoder's packed
+// output as they are: the library reads them through a pointer table); chunks_per_request [n] int32 host; fade in samples; remove_silence [n]
+// uint8 host -> (pcm int16 device, request i at sum_{j<i} ((N_j + 7) & ~7); lengths [n] int32 device)
+std::tuple<at::Tensor, at::Tensor> wave_finish(at::TensorList chunks, const at::Tensor& chunks_per_request, int64_t fade, const at::Tensor& remove_silence,
+                                               int64_t sample_rate) {
+    check_host(chunks_per_request, at::kInt, "chunks_per_request"); check_host(remove_silence, at::kByte, "remove_silence");
+    const int64_t n = chunks_per_request.numel();
+    TORCH_CHECK(chunks_per_request.dim() == 1 && n > 0 && remove_silence.numel() == n, "f5hip::wave_finish: chunks_per_request and remove_silence need one value per request");
+    TORCH_CHECK(fade >= 0 && fade <= INT32_MAX, "f5hip::wave_finish: the fade length must not be negative (got ", fade, ")");
+    TORCH_CHECK(sample_rate == 24000, "f5hip::wave_finish: the sample rate must be 24000 (got ", sample_rate, ")");
+    const int32_t* kp = chunks_per_request.data_ptr<int32_t>();
+    int64_t total_chunks = 0;
+    for (int64_t i = 0; i < n; i++) {
+        TORCH_CHECK(kp[i] >= 1, "f5hip::wave_finish: request ", i, " has ", kp[i], " chunks");
+        total_chunks += kp[i];
+    }
+    TORCH_CHECK((int64_t)chunks.size() == total_chunks, "f5hip::wave_finish: chunks needs sum(chunks_per_request) = ", total_chunks, " tensors (got ", chunks.size(), ")");
+    std::vector<const float*> ptrs(total_chunks);
+    std::vector<int32_t> lens(total_chunks);
+    int64_t total_out = 0, c = 0;
+    for (int64_t i = 0; i < n; i++) {
+        int64_t joined = 0;
+        for (int32_t j = 0; j < kp[i]; j++, c++) {
+            const at::Tensor& w = chunks[c];
+            check_dev_f32(w, "chunk");
+            TORCH_CHECK(w.dim() == 1 && w.numel() >= 1 && w.numel() <= INT32_MAX && w.device() == chunks[0].device(),
+                        "f5hip::wave_finish: chunk ", j, " of request ", i, " must be a non-empty 1-D tensor on the first chunk's device");
+            TORCH_CHECK(kp[i] == 1 || fade == 0 || w.numel() >= 2 * fade, "f5hip::wave_finish: chunk ", j, " of request ", i, " has ", w.numel(),
+                        " samples, fewer than 2 x fade = ", 2 * fade, ": its fades would overlap");
+            ptrs[c] = w.data_ptr<float>(); lens[c] = (int32_t)w.numel();
+            joined += w.numel() - (j ? fade : 0);
+        }
+        total_out += (joined + 7) & ~(int64_t)7;
+        TORCH_CHECK(total_out <= INT32_MAX, "f5hip::wave_finish: the outputs of the call exceed 2^31 - 1 samples");
+    }
+    const c10::DeviceGuard guard(chunks[0].device());   // allocations and stream on the chunks' device
+    at::Tensor pcm = at::empty({total_out}, chunks[0].options().dtype(at::kShort)), lengths = at::empty({n}, chunks[0].options().dtype(at::kInt));
+    const int rc = f5hip_wave_finish((int32_t)n, kp, ptrs.data(), lens.data(), (int32_t)fade, remove_silence.data_ptr<uint8_t>(), (int32_t)sample_rate,
+                                     pcm.data_ptr<int16_t>(), lengths.data_ptr<int32_t>(), stream_of(chunks[0]));
+    TORCH_CHECK(rc == 0, "f5hip_wave_finish: ", f5hip_last_error());
+    return {pcm, lengths};
+}
+
 }   // namespace
 
 TORCH_LIBRARY(f5hip, m) {
@@ -251,4 +296,5 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("bigvgan_forward(int handle, Tensor mel, int total_upsample) -> Tensor", &bigvgan_forward);
     m.def("bigvgan_forward_ragged(int handle, Tensor mel, Tensor frames, int channels, int total_upsample) -> Tensor", &bigvgan_forward_ragged);
     m.def("ref_frontend(Tensor wave, Tensor n_in, Tensor channels, int orig_freq, int new_freq, Tensor? taps, float rms_floor) -> (Tensor, Tensor)", &ref_frontend);
+    m.def("wave_finish(Tensor[] chunks, Tensor chunks_per_request, int fade, Tensor remove_silence, int sample_rate) -> (Tensor, Tensor)", &wave_finish);
 }

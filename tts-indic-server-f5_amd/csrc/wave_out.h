@@ -1,0 +1,404 @@
+// Waveform back-end on the device: the tail of infer_batch_process (F/infer/utils_infer.py:485-519, the cross-fade join) and
+// remove_silence_for_generated_wav (:530-539) for n requests in ONE call -- chunk waves in, each request's finished 16-bit PCM out.
+// Included at the end of f5hip.hip (same translation unit).  A memory-bound gather: no MFMA, no atomics.
+//
+//   wave_join_kernel      one block per 3840-sample tile (16 cells of 10 ms) of a request's joined wave; a thread owns 8 consecutive samples:
+//                         two 16-byte loads where they lie in one chunk's body and the address allows, one 16-byte store.  A sample of a
+//                         fade region is prev[len - F + i] * ramp[F - 1 - i] + next[i] * ramp[i] in fp64, two products and a sum that are
+//                         NOT contracted (numpy rounds each; `#pragma clang fp contract(off)`), rounded to fp32; then rint(x * 32768) clipped.  For a request that asked for
+//                         silence removal the PCM goes to a scratch buffer and the block also leaves the sum of squares of each of its cells.
+//   wave_silence_kernel   one block per flagged request: pydub's detect_silence / detect_nonsilent / split_on_silence (audio_prep.py) with
+//                         min_silence_len 1000, silence_thresh -50, keep_silence 500, seek_step 10 on integers -> the kept sample ranges
+//   wave_compact_kernel   copies the kept ranges of the scratch PCM to the output
+// One launch when no request is flagged, else three, whatever n and the chunk counts.  A request's bits depend on that request alone.
+//
+// Exactness.  With every chunk at least 2 F samples long the nested fades of cross_fade_concat never overlap, so joined sample j is either one
+// chunk sample or one fade of two chunk samples, and the closed form above is the host's arithmetic operation for operation (ramp[i] =
+// i * (1.0 / (F - 1)), ramp[F - 1] = 1.0: np.linspace(0, 1, F)).  The silence test rms <= 10^(-50/20) * 32768 = 103.6 with rms =
+// int(sqrt(S / n)) is S < 104^2 n = 10816 n on the integer sum of squares S (n <= 24000: S / n cannot round up across 10816).
+#pragma once
+
+struct WfChunk {
+    const float* x;
+    int len, pos;        // samples; first joined sample the chunk covers (its fade-in included)
+};
+struct WfReq {
+    int chunk0, k;       // its chunks
+    int n;               // joined samples
+    int flag;            // silence removal
+    long long off;       // its first sample in the output (a multiple of 8: 16-byte stores)
+    long long joff;      // flagged: its first sample in the scratch PCM
+    long long cell0;     // flagged: its first cell sum
+    long long cnt0;      // flagged: its silent-window prefix counts
+    int bucket0, range0; // flagged: its bucket and range slots
+    int tile0;           // its first block of the join launch
+    int pad;
+};
+struct WfFlagged { int req, tile0; };           // a flagged request and its first block of the compaction launch
+struct WfRange { int sa, sb, dst; };            // kept samples [sa, sb) of the joined PCM go to dst ..
+
+constexpr int kWfCell = 240;                    // 10 ms at 24 kHz
+constexpr int kWfTile = 16 * kWfCell;           // joined samples per join block
+constexpr int kWfGroups = kWfTile / 8;          // 8-sample groups per tile, 30 per cell
+constexpr int kWfCompactTile = 4096;
+constexpr int kWfWindowCells = 100;             // min_silence_len / seek_step
+constexpr long long kWfLoud = 104 * 104;        // S >= 10816 n: rms >= 104 > 103.6
+
+F5_DEVICE double wf_ramp(int i, int F, double step) {
+#pragma clang fp contract(off)
+    return i == F - 1 ? (F > 1 ? 1.0 : 0.0) : (double)i * step;
+}
+
+// joined sample j of a request, c its chunk (the last one whose pos <= j)
+F5_DEVICE float wf_sample(const WfChunk* __restrict__ ch, int c, int F, double step, int j) {
+    // numpy rounds both products and the sum, so nothing here may become an FMA.  Plain * and + under this pragma: hipcc's __dmul_rn and
+    // __dadd_rn are inline `x * y` / `x + y` compiled with contraction allowed, and were fused into v_fmac_f64 once inlined.
+#pragma clang fp contract(off)
+    const WfChunk cur = ch[c];
+    const int i = j - cur.pos;
+    if (c > 0 && i < F) {
+        const WfChunk prev = ch[c - 1];
+        const double a = (double)prev.x[prev.len - F + i] * wf_ramp(F - 1 - i, F, step);
+        const double b = (double)cur.x[i] * wf_ramp(i, F, step);
+        return (float)(a + b);
+    }
+    return cur.x[i];
+}
+
+F5_DEVICE int wf_quantise(float v) {   // serve.pcm16: rint(x * 32768) (exact product, half to even), clipped
+    const double r = rint((double)v * 32768.0);
+    return (int)fmax(fmin(r, 32767.0), -32768.0);
+}
+
+// last entry whose first block (member `first`) is at or before b
+template <typename T, int T::*first>
+F5_DEVICE int wf_find(const T* e, int n, int b) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (e[mid].*first <= b) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// sum of red[0 .. 256) by a fixed binary tree; every thread returns the total
+F5_DEVICE long long wf_block_sum(long long* red, int tid, long long v) {
+    red[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    const long long total = red[0];
+    __syncthreads();
+    return total;
+}
+
+__global__ __launch_bounds__(256) void wave_join_kernel(const WfReq* __restrict__ reqs, int n, const WfChunk* __restrict__ chunks, int F, double step,
+                                                        short* __restrict__ out, short* __restrict__ joined, long long* __restrict__ cells,
+                                                        int* __restrict__ out_len) {
+    __shared__ long long part[kWfGroups];
+    const int tid = threadIdx.x;
+    const int r = wf_find<WfReq, &WfReq::tile0>(reqs, n, blockIdx.x);
+    const WfReq q = reqs[r];
+    const int tile = blockIdx.x - q.tile0;
+    const WfChunk* ch = chunks + q.chunk0;
+    short* dst = q.flag ? joined + q.joff : out + q.off;
+    if (tile == 0 && tid == 0 && !q.flag) out_len[r] = q.n;
+    for (int g = tid; g < kWfGroups; g += 256) {
+        const long long j = (long long)tile * kWfTile + 8 * g;   // (64-bit: the last tile of a request near 2^31 samples ends past INT_MAX)
+        long long ss = 0;
+        if (j < q.n) {
+            int c = 0;
+            {
+                int hi = q.k - 1;
+                while (c < hi) {
+                    const int mid = (c + hi + 1) >> 1;
+                    if (ch[mid].pos <= j) c = mid; else hi = mid - 1;
+                }
+            }
+            const WfChunk cur = ch[c];
+            const int i = (int)j - cur.pos;
+            const long long body_end = c + 1 < q.k ? ch[c + 1].pos : q.n;   // one past the last joined sample that is this chunk's alone
+            int v[8];   // the 8 quantised samples (a sample past the end is 0)
+            if ((c == 0 || i >= F) && j + 8 <= body_end) {
+                const float* p = cur.x + i;
+                float f[8];
+                if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+                    const float4 lo = reinterpret_cast<const float4*>(p)[0], hi4 = reinterpret_cast<const float4*>(p)[1];
+                    f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w; f[4] = hi4.x; f[5] = hi4.y; f[6] = hi4.z; f[7] = hi4.w;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; e++) f[e] = p[e];
+                }
+#pragma unroll
+                for (int e = 0; e < 8; e++) v[e] = wf_quantise(f[e]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    v[e] = 0;
+                    if (j + e < q.n) {
+                        if (c + 1 < q.k && ch[c + 1].pos <= j + e) c++;   // (a chunk starts at least one sample after the one before it: one step at most)
+                        v[e] = wf_quantise(wf_sample(ch, c, F, step, (int)(j + e)));
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; e++) ss += (long long)(v[e] * v[e]);
+            if (j + 8 <= q.n) {
+                int4 w;
+                w.x = (v[0] & 0xffff) | (v[1] << 16); w.y = (v[2] & 0xffff) | (v[3] << 16);
+                w.z = (v[4] & 0xffff) | (v[5] << 16); w.w = (v[6] & 0xffff) | (v[7] << 16);
+                *reinterpret_cast<int4*>(dst + j) = w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; e++)
+                    if (j + e < q.n) dst[j + e] = (short)v[e];
+            }
+        }
+        part[g] = ss;
+    }
+    if (!q.flag) return;
+    __syncthreads();
+    const long long ci = (long long)tile * (kWfTile / kWfCell) + tid;   // cell of the request
+    if (tid < kWfTile / kWfCell && ci * kWfCell < q.n) {
+        long long s = 0;
+        for (int e = 0; e < kWfCell / 8; e++) s += part[tid * (kWfCell / 8) + e];
+        cells[q.cell0 + ci] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void wave_silence_kernel(const WfReq* __restrict__ reqs, const WfFlagged* __restrict__ flagged,
+                                                           const short* __restrict__ joined, const long long* __restrict__ cells, int* __restrict__ cnt,
+                                                           int2* __restrict__ buckets, WfRange* __restrict__ ranges, int* __restrict__ nranges,
+                                                           int* __restrict__ out_len) {
+    __shared__ long long red[256];
+    __shared__ int runsum[256];
+    const int tid = threadIdx.x;
+    const int r = flagged[blockIdx.x].req;
+    const WfReq q = reqs[r];
+    const int N = q.n;
+    // len(seg) = round(1000 N / 24000), Python's round: half to even
+    const int whole = N / 24, rem = N % 24;
+    const int len_ms = whole + ((rem > 12 || (rem == 12 && (whole & 1))) ? 1 : 0);
+    const int keep_end = (int)min(24LL * len_ms, (long long)N);   // where millisecond slicing ends the wave
+    WfRange* rg = ranges + q.range0;
+    if (len_ms < 1000) {   // shorter than one window: nothing is silent
+        if (tid == 0) { rg[0] = WfRange{0, keep_end, 0}; nranges[r] = 1; out_len[r] = keep_end; }
+        return;
+    }
+    const int last = len_ms - 1000, A = last / 10 + 1, nc = (N + kWfCell - 1) / kWfCell;
+    const long long* cell = cells + q.cell0;
+    int* pc = cnt + q.cnt0;   // pc[i] = silent windows among the aligned windows 0 .. i - 1 (A + 1 entries)
+
+    // aligned window i starts at 10 i ms = cell i and covers cells [i, i + 100), cut at the wave's end; a thread slides over its run of windows
+    const int run = (A + 255) / 256, i0 = min(tid * run, A), i1 = min(i0 + run, A);
+    int local = 0;
+    if (i0 < i1) {
+        long long S = 0;
+        for (int c = i0; c < min(i0 + kWfWindowCells, nc); c++) S += cell[c];
+        for (int i = i0; i < i1; i++) {
+            const long long nwin = min(24LL * (10 * i + 1000), (long long)N) - (long long)kWfCell * i;
+            local += S < kWfLoud * nwin ? 1 : 0;
+            pc[i + 1] = local;
+            S -= cell[i];
+            if (i + kWfWindowCells < nc) S += cell[i + kWfWindowCells];
+        }
+    }
+    runsum[tid] = local;
+    __syncthreads();
+    if (tid == 0) {
+        int acc = 0;
+        for (int t = 0; t < 256; t++) { const int v = runsum[t]; runsum[t] = acc; acc += v; }
+        pc[0] = 0;
+    }
+    __syncthreads();
+    for (int i = i0; i < i1; i++) pc[i + 1] += runsum[tid];
+
+    // the extra window at `last` when last % 10 != 0: it starts inside a cell, so it is summed from the samples
+    const bool extra = last % 10 != 0;
+    long long acc = 0;
+    if (extra) {
+        const short* x = joined + q.joff;
+        for (long long s = 24LL * last + tid; s < keep_end; s += 256) acc += (long long)x[s] * x[s];
+    }
+    const long long extra_sum = wf_block_sum(red, tid, acc);   // (its barriers also publish pc[])
+    const bool extra_silent = extra && extra_sum < kWfLoud * (keep_end - 24LL * last);
+
+    // detect_silence opens a new range at a silent start that is neither 10 ms nor at most 1000 ms behind the previous silent start: aligned
+    // window i opens one iff none of the 100 windows before it is silent, and closes one iff none of the 100 after it is.  Range starts lie more
+    // than 1000 ms apart, and so do range ends: a bucket of 100 windows holds at most one of each.
+    const int nb = (A + kWfWindowCells - 1) / kWfWindowCells;
+    int2* bk = buckets + q.bucket0;
+    for (int b = tid; b < nb; b += 256) {
+        int st = -1, en = -1;
+        for (int i = kWfWindowCells * b; i < min(kWfWindowCells * (b + 1), A); i++) {
+            if (pc[i + 1] == pc[i]) continue;
+            if (pc[i] == pc[max(i - kWfWindowCells, 0)]) st = i;
+            if (pc[min(i + kWfWindowCells + 1, A)] == pc[i + 1]) en = i;
+        }
+        bk[b] = make_int2(st, en);
+    }
+    __syncthreads();
+    if (tid != 0) return;
+
+    // detect_nonsilent + split_on_silence over the (few) silent ranges, in order: the non-silent range [p, s] ms keeps the samples
+    // [24 max(p - 500, 0), min(24 min(s + 500, len_ms), N)).  With keep_silence 500 and min_silence_len 1000 two padded ranges never overlap.
+    int nr = 0, dst = 0, prev_end = 0;
+    bool first = true;
+    auto nonsilent = [&](int p, int s) {
+        const bool empty_head = first && p == 0 && s == 0;   // detect_nonsilent drops a leading [0, 0]
+        first = false;
+        if (empty_head) return;
+        const int a = max(p - 500, 0), b = min(s + 500, len_ms);
+        const int sa = 24 * a, sb = (int)min(24LL * b, (long long)N);
+        rg[nr++] = WfRange{sa, sb, dst};
+        dst += sb - sa;
+    };
+    bool have = false;            // a silent range whose end the extra window may still move
+    int ps = 0, pe = 0, pen = 0, cur = 0;
+    for (int b = 0; b < nb; b++) {
+        const int2 e = bk[b];
+        if (e.x >= 0) cur = 10 * e.x;
+        if (e.y >= 0) {
+            if (have) { nonsilent(prev_end, ps); prev_end = pe; }
+            have = true; ps = cur; pe = 10 * e.y + 1000; pen = e.y;
+        }
+    }
+    if (extra_silent) {
+        if (have && last <= 10 * pen + 1000) {
+            pe = len_ms;                                   // it continues the last range
+        } else {
+            if (have) { nonsilent(prev_end, ps); prev_end = pe; }
+            have = true; ps = last; pe = len_ms;
+        }
+    }
+    if (have) { nonsilent(prev_end, ps); prev_end = pe; }
+    if (!have || pe != len_ms) nonsilent(prev_end, len_ms);
+    nranges[r] = nr;
+    out_len[r] = dst;
+}
+
+__global__ __launch_bounds__(256) void wave_compact_kernel(const WfReq* __restrict__ reqs, const WfFlagged* __restrict__ flagged, int nflag,
+                                                           const short* __restrict__ joined, const WfRange* __restrict__ ranges,
+                                                           const int* __restrict__ nranges, short* __restrict__ out) {
+    const int f = wf_find<WfFlagged, &WfFlagged::tile0>(flagged, nflag, blockIdx.x);
+    const int r = flagged[f].req;
+    const WfReq q = reqs[r];
+    const WfRange* rg = ranges + q.range0;
+    const int nr = nranges[r];
+    if (nr < 1) return;
+    const short* src = joined + q.joff;
+    short* dst = out + q.off;
+    const long long x0 = (long long)(blockIdx.x - flagged[f].tile0) * kWfCompactTile;
+    for (int m = 0; m < kWfCompactTile / 256; m++) {
+        const long long x = x0 + m * 256 + threadIdx.x;
+        if (x >= q.n) break;
+        int lo = 0, hi = nr - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (rg[mid].sa <= x) lo = mid; else hi = mid - 1;
+        }
+        const WfRange k = rg[lo];
+        if (x >= k.sa && x < k.sb) dst[k.dst + (int)x - k.sa] = src[x];
+    }
+}
+
+struct WfWorkspace {
+    WfReq* reqs = nullptr; size_t cap_reqs = 0;
+    WfChunk* chunks = nullptr; size_t cap_chunks = 0;
+    WfFlagged* flagged = nullptr; size_t cap_flagged = 0;
+    short* joined = nullptr; size_t cap_joined = 0;
+    long long* cells = nullptr; size_t cap_cells = 0;
+    int* cnt = nullptr; size_t cap_cnt = 0;
+    int2* buckets = nullptr; size_t cap_buckets = 0;
+    WfRange* ranges = nullptr; size_t cap_ranges = 0;
+    int* nranges = nullptr; size_t cap_nranges = 0;
+};
+static WfWorkspace g_wf_ws[32];   // one per device ordinal
+
+int f5hip_wave_finish(int32_t n, const int32_t* chunks_per_request, const float* const* chunk_dev, const int32_t* chunk_len, int32_t fade,
+                      const uint8_t* remove_silence, int32_t sample_rate, int16_t* pcm_dev, int32_t* len_dev, void* stream) {
+    if (n < 1 || !chunks_per_request || !chunk_dev || !chunk_len || !pcm_dev || !len_dev) return fail(-1, "wave_finish: bad argument");
+    if (sample_rate != 24000) return fail(-1, "wave_finish: the sample rate must be 24000 (got %d)", sample_rate);
+    if (fade < 0) return fail(-1, "wave_finish: the fade length must not be negative (got %d)", fade);
+    if (reinterpret_cast<uintptr_t>(pcm_dev) & 15) return fail(-1, "wave_finish: the output must be 16-byte aligned");
+    const int F = fade;
+    std::vector<WfReq> h(n);
+    std::vector<WfChunk> hc;
+    std::vector<WfFlagged> hf;
+    long long off = 0, joff = 0, ncell = 0, ncnt = 0, nbucket = 0, nrange = 0, tiles = 0, ctiles = 0, total_in = 0;
+    for (int i = 0; i < n; i++) {
+        const int k = chunks_per_request[i];
+        if (k < 1) return fail(-1, "wave_finish: request %d has %d chunks", i, k);
+        WfReq& q = h[i];
+        memset(&q, 0, sizeof(q));
+        q.chunk0 = (int)hc.size(); q.k = k;
+        long long pos = 0;
+        for (int c = 0; c < k; c++) {
+            const size_t ci = hc.size();
+            const int len = chunk_len[ci];
+            if (!chunk_dev[ci] || len < 1) return fail(-1, "wave_finish: chunk %d of request %d is empty", c, i);
+            if (k > 1 && F > 0 && len < 2 * (long long)F)
+                return fail(-1, "wave_finish: chunk %d of request %d has %d samples, fewer than 2 x fade = %lld: its fades would overlap", c, i, len,
+                            2 * (long long)F);
+            if (reinterpret_cast<uintptr_t>(chunk_dev[ci]) & 3) return fail(-1, "wave_finish: chunk %d of request %d is not 4-byte aligned", c, i);
+            if (c > 0) pos -= F;
+            total_in += len;
+            if (total_in > 2147483647LL) return fail(-1, "wave_finish: the chunks of the call exceed 2^31 - 1 samples");
+            hc.push_back(WfChunk{chunk_dev[ci], len, (int)pos});
+            pos += len;
+        }
+        q.n = (int)pos;   // (<= total_in)
+        q.flag = remove_silence && remove_silence[i] ? 1 : 0;
+        q.off = off; q.tile0 = (int)tiles;
+        off += (pos + 7) & ~7LL;
+        tiles += (pos + kWfTile - 1) / kWfTile;
+        if (off > 2147483647LL) return fail(-1, "wave_finish: the outputs of the call exceed 2^31 - 1 samples");
+        if (q.flag) {
+            q.joff = joff; q.cell0 = ncell; q.cnt0 = ncnt; q.bucket0 = (int)nbucket; q.range0 = (int)nrange;
+            hf.push_back(WfFlagged{i, (int)ctiles});
+            joff += (pos + 7) & ~7LL;
+            ncell += (pos + kWfCell - 1) / kWfCell;
+            ncnt += pos / kWfCell + 2;       // aligned windows + 1
+            nbucket += pos / 24000 + 2;
+            nrange += pos / 24000 + 4;       // silent ranges start more than 1000 ms apart; one kept range more than silent ones
+            ctiles += (pos + kWfCompactTile - 1) / kWfCompactTile;
+        }
+    }
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return fail(-6, "wave_finish: hipGetDevice");
+    WfWorkspace& ws = g_wf_ws[dev & 31];
+    CK(ref_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_finish requests"));
+    CK(ref_reserve(&ws.chunks, &ws.cap_chunks, hc.size(), "wave_finish chunks"));
+    if (!hf.empty()) {
+        CK(ref_reserve(&ws.flagged, &ws.cap_flagged, hf.size(), "wave_finish flags"));
+        CK(ref_reserve(&ws.joined, &ws.cap_joined, (size_t)joff, "wave_finish joined PCM"));
+        CK(ref_reserve(&ws.cells, &ws.cap_cells, (size_t)ncell, "wave_finish cells"));
+        CK(ref_reserve(&ws.cnt, &ws.cap_cnt, (size_t)ncnt, "wave_finish window counts"));
+        CK(ref_reserve(&ws.buckets, &ws.cap_buckets, (size_t)nbucket, "wave_finish buckets"));
+        CK(ref_reserve(&ws.ranges, &ws.cap_ranges, (size_t)nrange, "wave_finish ranges"));
+        CK(ref_reserve(&ws.nranges, &ws.cap_nranges, (size_t)n, "wave_finish range counts"));
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t up = hf.empty() ? upload_sync(st, ws.reqs, h, ws.chunks, hc) : upload_sync(st, ws.reqs, h, ws.chunks, hc, ws.flagged, hf);
+    if (up != hipSuccess) return fail(-6, "wave_finish metadata upload");
+
+    const double step = F > 1 ? 1.0 / (double)(F - 1) : 0.0;   // np.linspace's step
+    hipLaunchKernelGGL(wave_join_kernel, dim3((unsigned)tiles), dim3(256), 0, st, ws.reqs, n, ws.chunks, F, step, (short*)pcm_dev, ws.joined, ws.cells,
+                       (int*)len_dev);
+    CKL("wave_join");
+    g_counters[CNT_WAVE_LAUNCHES]++;
+    if (!hf.empty()) {
+        hipLaunchKernelGGL(wave_silence_kernel, dim3((unsigned)hf.size()), dim3(256), 0, st, ws.reqs, ws.flagged, ws.joined, ws.cells, ws.cnt, ws.buckets,
+                           ws.ranges, ws.nranges, (int*)len_dev);
+        CKL("wave_silence");
+        hipLaunchKernelGGL(wave_compact_kernel, dim3((unsigned)ctiles), dim3(256), 0, st, ws.reqs, ws.flagged, (int)hf.size(), ws.joined, ws.ranges,
+                           ws.nranges, (short*)pcm_dev);
+        CKL("wave_compact");
+        g_counters[CNT_WAVE_LAUNCHES] += 2;
+    }
+    g_counters[CNT_WAVE_REQUESTS] += n;
+    return 0;
+}

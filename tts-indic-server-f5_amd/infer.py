@@ -570,9 +570,11 @@ def _sample(model_obj, voice, units, knobs, generator=None):
     return _sample_units(model_obj, voice.cond(model_obj), [voice.audio] * len(units), units, generators=[generator] * len(units), **knobs)
 
 
-def _chunk_waves(groups, vocoder, mel_spec_type, target_rms):
+def _chunk_waves(groups, vocoder, mel_spec_type, target_rms, on_device=False, want_specs=True):
     """Vocoder part of infer_batch_process's tail (F/infer/utils_infer.py:468-481) for the chunks of several requests: `groups` =
     [(mels, ref_frames, rms)] -> per group ([wave_i], [spec_i]) as numpy, the reference frames stripped and the rms restored per chunk.
+    `on_device`: the waves stay where the vocoder left them, as 1-D tensors (views of `decode_ragged`'s packed output where no gain applies),
+    for `finish_requests`; `want_specs=False`: no spectrogram is downloaded and `[spec_i]` is None (the serving path drops them).
     Vocoder objects that offer `decode_ragged` vocode every chunk of every group in ONE call (each item equals its own `decode` /
     `vocoder(spec)`, bit for bit): F5HipVocos for "vocos", and for "bigvgan" an object whose `decode_ragged` is the BigVGAN one, which it
     says with `ragged_mel_spec_type == "bigvgan"` (F5HipBigVGAN; a Vocos-style `decode_ragged` returns hop (T - 1) samples per item, so
@@ -599,8 +601,13 @@ def _chunk_waves(groups, vocoder, mel_spec_type, target_rms):
         for wave in raw[k:k + len(g)]:
             if rms < target_rms:
                 wave = wave * rms / target_rms
-            waves.append(wave.squeeze().cpu().numpy())
-        out.append((waves, [spec[0].cpu().numpy() for spec in g]))
+            if on_device:
+                waves.append(wave.reshape(-1))
+            else:
+                waves.append(wave.squeeze().cpu().numpy())
+                backend_stats["d2h_copies"] += int(wave.is_cuda)
+        out.append((waves, [spec[0].cpu().numpy() for spec in g] if want_specs else None))
+        backend_stats["d2h_copies"] += sum(int(spec.is_cuda) for spec in g) if want_specs else 0
         k += len(g)
     return out
 
@@ -627,7 +634,7 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 
 
 # per-request options of `infer_requests` (the fourth element of a request) and of the serving routes
-REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method")
+REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "remove_silence")
 
 
 def plan_request(request, defaults, *, target_rms, fix_duration, device, tokenizer):
@@ -640,6 +647,8 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
     unknown = set(opts) - set(REQUEST_OPTIONS) - {"generator"}
     if unknown:
         raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
+    if opts.get("remove_silence") and isinstance(gen_text, (list, tuple)):
+        raise ValueError("remove_silence needs the request's whole wave: it is not available for a list of chunk texts (a streamed request)")
     voice, units = _plan_request(ref_audio, ref_text, gen_text, target_rms, opts["speed"], fix_duration, device, tokenizer)
     own = opts.get("generator")
     gen = torch.Generator().set_state(own.get_state()) if own is not None else request_generator(opts["seed"])
@@ -653,7 +662,7 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
 def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, target_rms=target_rms,
                    cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                    sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, tokenizer=text_to_tokens,
-                   join=True):
+                   join=True, finish=None):
     """Several `infer_process()` calls as ONE sampler batch: `requests` = [(ref_audio, ref_text, gen_text)], each with its own
     reference voice (a path, a (wave, sr) pair or a `PreparedVoice`); returns one (wave, sample_rate, spectrogram) triple per request, each what `infer_process` returns for
     that request alone: units keep the reference's batch-1 semantics (no padding against each other, no shared mask), and noise is drawn
@@ -682,7 +691,12 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     and is advanced only when this call succeeds.  A seeded request's result depends only on its own settings, not on its batch, with the
     shape-invariant attention mode on one GPU (ranks > 0 of a `serve.ShardedSampler` do not switch to that mode yet); unseeded units draw
     from the global generator in flat request order (unit by unit, request after request) when there is one sampler call, i.e. always
-    with a `per_unit_time_grids` model, and in sampler-call order otherwise."""
+    with a `per_unit_time_grids` model, and in sampler-call order otherwise.
+
+    `remove_silence` (bool, per request): the reference's `remove_silence_for_generated_wav` on the finished wave; such a request's wave is
+    int16 PCM (`audio_prep.remove_silence_pcm` of its quantised joined wave), and it needs the whole wave: ValueError with `join=False` or a
+    list of chunk texts.  `finish` = dict(device_backend=..., want=...): what the serving path asks for -- the list of `finish_requests`
+    results (one wave per request, no triples) with no spectrogram downloaded."""
     defaults = dict(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None)
     calls = {}   # calls: (nfe_step, sway, ode_method) -> [unit ids, ...] of one sampler call each
     flat_units, flat_cond, flat_audio, flat_cfg, flat_gen, flat_grid = [], [], [], [], [], []
@@ -716,9 +730,19 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
         plan.commit()   # every sampler call went through: the caller's generator moves
         groups.append((mels[k:k + len(plan.units)], plan.voice.ref_frames, plan.voice.rms))
         k += len(plan.units)
+    silence = [bool(plan.opts.get("remove_silence")) for plan in plans]
+    if finish is not None:
+        backend = bool(finish.get("device_backend"))
+        chunk_waves = [waves for waves, _ in _chunk_waves(groups, vocoder, mel_spec_type, target_rms, on_device=backend, want_specs=False)]
+        return finish_requests(chunk_waves, [req[2] for req in requests], cross_fade_duration, silence, **finish)
+    if any(silence) and not join:
+        raise ValueError("remove_silence needs the request's whole wave: it is not available with join=False")
     out = []
-    for waves, specs in _chunk_waves(groups, vocoder, mel_spec_type, target_rms):
-        if join:
+    for flag, (waves, specs) in zip(silence, _chunk_waves(groups, vocoder, mel_spec_type, target_rms)):
+        if flag:
+            wave, = finish_requests([waves], [""], cross_fade_duration, [True])
+            out.append((wave, target_sample_rate, np.concatenate(specs, axis=1)))
+        elif join:
             out.append((cross_fade_concat(waves, cross_fade_duration), target_sample_rate, np.concatenate(specs, axis=1)))
         else:
             out.append((waves, target_sample_rate, specs))
@@ -733,11 +757,87 @@ def request_wave(gen_text, waves, cross_fade_duration=cross_fade_duration):
     return np.asarray(cross_fade_concat(waves, cross_fade_duration), dtype=np.float32)
 
 
+def quantise_pcm16(wave) -> np.ndarray:
+    """int16 PCM of float samples by the routes' rule (`serve.wav_bytes`, `serve.pcm16`): rint(x * 32768) in float64, half to even, clipped."""
+    return np.clip(np.rint(np.asarray(wave).astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
+
+
+# What `finish_requests` and `_chunk_waves` did since the last `backend_stats.clear()`: requests finished on the device / on the host,
+# `ops.wave_finish` calls, and device-to-host copies (chunk waves, spectrograms, PCM, lengths)
+backend_stats: collections.Counter = collections.Counter()
+
+
+def _host_chunk(wave):
+    """A chunk wave as numpy, downloaded (and counted) when `_chunk_waves(on_device=True)` left it on the device."""
+    if torch.is_tensor(wave):
+        backend_stats["d2h_copies"] += int(wave.is_cuda)
+        return wave.cpu().numpy()
+    return wave
+
+
+def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cross_fade_duration, remove_silence=None, device_backend=False,
+                    want="float"):
+    """From the chunk waves of several requests (rms restored; numpy, or tensors as `_chunk_waves(on_device=True)` leaves them) to what each
+    request gets.  A request whose text is a list of chunk texts (a streamed request's head or tail) gets its chunk waves as they are, like
+    `request_wave`.  Any other request gets its joined wave: float32 (`request_wave`) with want="float", int16 PCM (`quantise_pcm16` of that)
+    with want="pcm16" -- and, with its `remove_silence` flag set, `audio_prep.remove_silence_pcm` of that PCM whatever `want` says.
+
+    `device_backend=True` (needs want="pcm16") makes ONE `ops.wave_finish` call for all eligible requests of the batch -- join, quantisation
+    and silence removal on the device, bit for bit the host arithmetic -- and then at most two device-to-host copies: the lengths (only when
+    a request asked for silence removal) and the samples.  Not eligible, and finished on the host in the same call (counted in
+    `backend_stats`): a list text, chunk waves that are not on a HIP device, and a request of several chunks with one shorter than twice the
+    fade, where the reference's nested cross-fades overlap and the kernel's closed form does not hold."""
+    if want not in ("float", "pcm16"):
+        raise ValueError(f'want must be "float" or "pcm16" (got {want!r})')
+    if device_backend and want != "pcm16":
+        raise ValueError('the device back-end produces int16 PCM: device_backend=True needs want="pcm16"')
+    n = len(chunk_waves_per_request)
+    flags = [False] * n if remove_silence is None else [bool(f) for f in remove_silence]
+    if len(gen_texts) != n or len(flags) != n:
+        raise ValueError("finish_requests: one text and one remove_silence flag per request")
+    fade = int(cross_fade_duration * target_sample_rate) if cross_fade_duration > 0 else 0
+    out, on_device = [None] * n, []
+    for i, (waves, text) in enumerate(zip(chunk_waves_per_request, gen_texts)):
+        if isinstance(text, (list, tuple)):
+            if flags[i]:
+                raise ValueError("remove_silence needs the request's whole wave: it is not available for a list of chunk texts")
+            out[i] = [_host_chunk(w) for w in waves]
+        elif device_backend and all(torch.is_tensor(w) and w.is_cuda for w in waves) and (len(waves) == 1 or min(len(w) for w in waves) >= 2 * fade):
+            on_device.append(i)
+            continue
+        else:
+            wave = request_wave(text, [_host_chunk(w) for w in waves], cross_fade_duration)
+            if flags[i]:
+                from .audio_prep import remove_silence_pcm
+                wave = remove_silence_pcm(quantise_pcm16(wave), target_sample_rate)
+            elif want == "pcm16":
+                wave = quantise_pcm16(wave)
+            out[i] = wave
+        backend_stats["host_requests"] += 1
+    if on_device:
+        from . import ops
+        chunks = [w.to(torch.float32).contiguous() for i in on_device for w in chunk_waves_per_request[i]]
+        silence = [flags[i] for i in on_device]
+        pcm, lengths, offsets = ops.wave_finish(chunks, [len(chunk_waves_per_request[i]) for i in on_device], fade, silence, target_sample_rate)
+        if any(silence):
+            lengths = lengths.cpu().tolist()
+            backend_stats["d2h_copies"] += 1
+        else:   # without silence removal a request keeps its joined length
+            lengths = [sum(len(w) for w in chunk_waves_per_request[i]) - (len(chunk_waves_per_request[i]) - 1) * fade for i in on_device]
+        host = pcm.cpu().numpy()
+        backend_stats["d2h_copies"] += 1
+        for i, off, length in zip(on_device, offsets, lengths):
+            out[i] = host[off:off + length].copy()   # (a request's result does not keep the batch's buffer alive)
+        backend_stats["device_calls"] += 1
+        backend_stats["device_requests"] += len(on_device)
+    return out
+
+
 class SpanTicket:
     """One admitted request of a `SpanScheduler`: its planned units, and -- once they have all ended -- `result` (`request_wave`)."""
 
-    def __init__(self, request, voice, units):
-        self.request, self.voice, self.units = request, voice, units
+    def __init__(self, request, voice, units, remove_silence=False):
+        self.request, self.voice, self.units, self.remove_silence = request, voice, units, bool(remove_silence)
         self.in_flight = self.cancelled = self.done = False
         self.result = None
 
@@ -766,11 +866,14 @@ class SpanScheduler:
     Every boundary pays one sequence set-up, one text / conditioning / time precompute and the packed state copies again, so a short span
     buys its low admission wait with device time.  `span_steps` defaults to 8: measured on an MI355X (`tools/admission_bench.py`,
     profiles/r07_admission_bench.txt) that boundary cost is 3.3 ms with 8 units in flight, 2.3 % of an 8-step span (4.6 % of a 4-step one),
-    and 8 is the shortest span whose median time to result on the trace was not above `MicroBatcher`'s."""
+    and 8 is the shortest span whose median time to result on the trace was not above `MicroBatcher`'s.
+
+    Finished requests leave through `finish_requests` (a request's `remove_silence` option included); with `device_backend=True` their chunk
+    waves stay on the device and their results are int16 PCM from one `ops.wave_finish` call per boundary."""
 
     def __init__(self, model_obj, vocoder, span_steps=span_steps, max_frames=None, max_requests=None, mel_spec_type=mel_spec_type, target_rms=target_rms,
                  cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
-                 speed=speed, fix_duration=fix_duration, device=None, tokenizer=text_to_tokens):
+                 speed=speed, fix_duration=fix_duration, device=None, tokenizer=text_to_tokens, device_backend=False):
         if not getattr(model_obj, "resumable_spans", False):
             raise ValueError("SpanScheduler needs a model object with resumable spans (plan_unit / advance: F5HipModel)")
         if int(span_steps) < 1:
@@ -780,6 +883,7 @@ class SpanScheduler:
         self.mel_spec_type, self.target_rms, self.cross_fade_duration = mel_spec_type, target_rms, cross_fade_duration
         self.defaults = dict(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None)
         self.fix_duration, self.device, self.tokenizer = fix_duration, device, tokenizer
+        self.device_backend = bool(device_backend)   # finished requests leave as int16 PCM, joined and quantised on the device (`finish_requests`)
         self.waiting: list[SpanTicket] = []
         self.in_flight: list[SpanTicket] = []
         self.span_units: list[int] = []
@@ -803,7 +907,7 @@ class SpanScheduler:
                                             sway_sampling_coef=opts["sway_sampling_coef"], generator=plan.generator, **extra)
                    for tokens, frames in plan.units]
         plan.commit()   # every chunk was planned: the caller's generator moves
-        ticket = SpanTicket(request, voice, planned)
+        ticket = SpanTicket(request, voice, planned, opts.get("remove_silence"))
         self.waiting.append(ticket)
         return ticket
 
@@ -825,8 +929,12 @@ class SpanScheduler:
 
     def _finish(self, tickets):
         groups = [([u.mel for u in t.units], t.voice.ref_frames, t.voice.rms) for t in tickets]
-        for t, (waves, _) in zip(tickets, _chunk_waves(groups, self.vocoder, self.mel_spec_type, self.target_rms)):
-            t.result, t.done, t.in_flight = request_wave(t.request[2], waves, self.cross_fade_duration), True, False
+        chunk_waves = [waves for waves, _ in _chunk_waves(groups, self.vocoder, self.mel_spec_type, self.target_rms, on_device=self.device_backend,
+                                                          want_specs=False)]
+        results = finish_requests(chunk_waves, [t.request[2] for t in tickets], self.cross_fade_duration, [t.remove_silence for t in tickets],
+                                  device_backend=self.device_backend, want="pcm16" if self.device_backend else "float")
+        for t, result in zip(tickets, results):
+            t.result, t.done, t.in_flight = result, True, False
 
     def step(self) -> list:
         """One boundary and one span.  Returns the tickets that finished, `result` set."""

@@ -367,3 +367,42 @@ def ref_frontend(wave, n_in, channels, orig_freq, new_freq, taps=None, rms_floor
             _lib.check(_lib.lib().f5hip_ref_frontend(len(ni), _p(ni), _p(ch), _p(wave), int(orig_freq), int(new_freq), _p(taps), float(rms_floor),
                                                      _p(out), _p(rms), _lib.current_stream_ptr()), "f5hip_ref_frontend")
     return out, rms, n_out
+
+
+def wave_finish(chunks, chunks_per_request, fade, remove_silence=None, sample_rate=24000):
+    """The waveform back-end for several requests in ONE library call (include/f5hip.h f5hip_wave_finish): `chunks` = the chunk waves of all
+    requests in request and chunk order, each a 1-D contiguous fp32 device tensor with the rms gain applied (views of a vocoder's packed
+    output are read in place); `chunks_per_request` [n]; `fade` in samples; `remove_silence` one bool per request (None: none).  Joins each
+    request's chunks with the reference's linear cross-fade, quantises to int16 by `serve.pcm16`'s rule and, for a flagged request, applies
+    `audio_prep.remove_silence_pcm`'s rule.  Returns (pcm int16 device, lengths [n] int32 device, offsets): request i's samples are
+    pcm[offsets[i] : offsets[i] + lengths[i]].  Refused (F5HipError): a chunk shorter than 2 * fade in a request of several chunks, a negative
+    fade, a rate other than 24 000, more than 2^31 - 1 samples."""
+    k = np.ascontiguousarray(np.asarray(chunks_per_request, dtype=np.int32))
+    flags = np.zeros(len(k), dtype=np.uint8) if remove_silence is None else np.ascontiguousarray(np.asarray(remove_silence, dtype=bool).astype(np.uint8))
+    chunks = list(chunks)
+    if len(k) < 1 or len(flags) != len(k) or (k < 1).any() or int(k.sum()) != len(chunks):
+        raise _lib.F5HipError("wave_finish: one chunk count (>= 1) and one flag per request, sum(chunks_per_request) chunk waves")
+    for w in chunks:
+        if not (torch.is_tensor(w) and w.dtype == torch.float32 and w.is_cuda and w.dim() == 1 and w.is_contiguous() and w.numel() >= 1):
+            raise _lib.F5HipError("wave_finish: every chunk must be a non-empty contiguous 1-D fp32 device tensor")
+    fade = int(fade)
+    offsets, off, c = [], 0, 0
+    for kk in k:
+        offsets.append(off)
+        off += (sum(int(w.numel()) for w in chunks[c:c + kk]) - (int(kk) - 1) * max(fade, 0) + 7) & ~7
+        c += int(kk)
+    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
+        try:
+            pcm, lengths = torch_ops.ops().wave_finish(chunks, torch.from_numpy(k), fade, torch.from_numpy(flags), int(sample_rate))
+        except RuntimeError as e:   # c10::Error from the operator's checks or the library
+            raise _lib.F5HipError(str(e)) from e
+    else:
+        ptrs = np.array([w.data_ptr() for w in chunks], dtype=np.uint64)
+        lens = np.array([w.numel() for w in chunks], dtype=np.int32)
+        dev = chunks[0].device
+        with torch.cuda.device(dev):
+            pcm = torch.empty(max(off, 0), device=dev, dtype=torch.int16)
+            lengths = torch.empty(len(k), device=dev, dtype=torch.int32)
+            _lib.check(_lib.lib().f5hip_wave_finish(len(k), _p(k), _p(ptrs), _p(lens), fade, _p(flags), int(sample_rate), _p(pcm), _p(lengths),
+                                                    _lib.current_stream_ptr()), "f5hip_wave_finish")
+    return pcm, lengths, offsets

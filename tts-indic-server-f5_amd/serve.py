@@ -55,7 +55,8 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
     """The per-request sampler options a client set (None = not set, dropped), checked before anything is queued: ValueError with a message
     the routes return as 400.  `speed` finite and > 0; `nfe_step` an integer in 1..MAX_NFE_STEP[ode_method]; `cfg_strength` and
     `sway_sampling_coef` finite; `seed` an integer in 0..2**63 - 1; `ode_method` one of MAX_NFE_STEP's names.  `ode_method` (the argument)
-    is the model's solver: `nfe_step`'s upper limit follows the request's own `ode_method` when it sets one, else the model's."""
+    is the model's solver: `nfe_step`'s upper limit follows the request's own `ode_method` when it sets one, else the model's.
+    `remove_silence` a bool (False is dropped like None: the request is then what it is without the option)."""
     out = {}
     own = options.get("ode_method") if "ode_method" in allowed else None
     if own is not None:
@@ -69,6 +70,12 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
             continue
         if k == "ode_method":
             pass
+        elif k == "remove_silence":
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"remove_silence must be true or false (got {v!r})")
+            if not v:
+                continue
+            v = True
         elif k in ("nfe_step", "seed"):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"{k} must be an integer (got {v!r})")
@@ -94,6 +101,11 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
 # Whether uploaded reference clips take the device front-end unless `TTSManager(device_frontend=...)` says otherwise: it does when it beat
 # the host front-end for ONE clip by more than that run's own spread (tools/ref_frontend_bench.py, profiles/ref_frontend_bench.txt)
 DEVICE_FRONTEND_DEFAULT = True
+# Whether finished waves are joined, quantised and stripped of pauses on the device unless `TTSManager(device_backend=...)` says otherwise.
+# Off: turning it on changes what `synthesize` returns (int16 PCM instead of float32), and the rule above asks for a win at ONE request by
+# more than the run's own spread (tools/wave_backend_bench.py, profiles/wave_backend_bench.txt; DESIGN "Waveform back-end")
+DEVICE_BACKEND_DEFAULT = False
+STREAM_REMOVE_SILENCE = "remove_silence needs the request's whole wave: it is not available on a streaming path"
 
 
 @dataclass
@@ -368,7 +380,8 @@ class TTSManager:
 
     def __init__(self, loader: Callable[[], tuple] | None = None, nfe_step: int = infer.nfe_step, cfg_strength: float = infer.cfg_strength,
                  sway_sampling_coef: float = infer.sway_sampling_coef, speed: float = infer.speed, mel_spec_type: str = "vocos",
-                 micro_batch: dict | None = None, batch_invariant: bool = True, clip_cache: int = 64, device_frontend: bool | None = None):
+                 micro_batch: dict | None = None, batch_invariant: bool = True, clip_cache: int = 64, device_frontend: bool | None = None,
+                 device_backend: bool | None = None):
         self.loader = loader
         self.batch_invariant = batch_invariant   # False: leave the model's attention mode alone (fastest kernel per launch shape)
         self.micro_batch = micro_batch            # e.g. dict(max_requests=16, max_wait_ms=5): batch concurrent requests; with span_steps
@@ -392,6 +405,10 @@ class TTSManager:
         # True: an uploaded clip's mono mix / rms gain / resampling run on the device (`infer.prepare_voices`, one ragged call for all new
         # voices of a batch); False: on the host, before the request is queued.  None: DEVICE_FRONTEND_DEFAULT (profiles/ref_frontend_bench.txt)
         self.device_frontend = DEVICE_FRONTEND_DEFAULT if device_frontend is None else bool(device_frontend)
+        # True: a batch's chunk waves stay on the device and ONE `ops.wave_finish` call turns them into every request's int16 PCM (cross-fade,
+        # quantisation, `remove_silence`), downloaded once; a non-streamed request's result is then that int16 array, which `wav_bytes` passes
+        # through -- the same bytes as the float32 wave gives.  False: joined on the host, float32 as before.  None: DEVICE_BACKEND_DEFAULT
+        self.device_backend = DEVICE_BACKEND_DEFAULT if device_backend is None else bool(device_backend)
         # The library allows ONE call in flight per handle (include/f5hip.h), the sampler keeps per-call state and noise comes from torch's
         # global generator: every entry into the device path takes this lock.  Without a batcher, concurrent HTTP requests therefore run one
         # after the other, like the reference's blocking `async def` handlers (S/routes/speech.py:19-41).
@@ -432,18 +449,19 @@ class TTSManager:
                 mb.pop("max_wait_ms", None)      # nothing is waited for: a request joins at the next boundary
                 if mb["span_steps"] is None:     # dict(span_steps=None): the scheduler's default
                     del mb["span_steps"]
-                sched = infer.SpanScheduler(model_obj, vocoder, mel_spec_type=self.mel_spec_type, **mb, **self.opts)
+                sched = infer.SpanScheduler(model_obj, vocoder, mel_spec_type=self.mel_spec_type, device_backend=self.device_backend, **mb, **self.opts)
                 self.batcher = ContinuousBatcher(sched, lock=self._device_lock)
             elif self.micro_batch is not None:
                 self.batcher = MicroBatcher(self._run_batch, **self.micro_batch)
         return self
 
     def _run_batch(self, requests):
-        """One `infer_requests` call.  A request whose text is a string gets its joined wave (float32); one whose text is a list of chunk
-        texts (a streamed request's head or tail) gets its per-chunk waves, for the caller's `infer.StreamJoiner`."""
+        """One `infer_requests` call.  A request whose text is a string gets its joined wave (float32; int16 PCM with `device_backend`, or
+        when it asked for `remove_silence`); one whose text is a list of chunk texts (a streamed request's head or tail) gets its per-chunk
+        waves, for the caller's `infer.StreamJoiner`.  `infer.finish_requests` does the joining, on the device with `device_backend`."""
+        finish = dict(device_backend=self.device_backend, want="pcm16" if self.device_backend else "float")
         with self._device_lock:
-            res = infer.infer_requests(requests, self.model_obj, self.vocoder, mel_spec_type=self.mel_spec_type, join=False, **self.opts)
-        return [infer.request_wave(r[2], waves) for r, (waves, _, _) in zip(requests, res)]
+            return infer.infer_requests(requests, self.model_obj, self.vocoder, mel_spec_type=self.mel_spec_type, finish=finish, **self.opts)
 
     def close(self):
         """Unload: stop the batcher (requests already queued are served, later ones refused) and drop the model objects."""
@@ -542,14 +560,14 @@ class TTSManager:
                     self._clip_key_locks.pop(key, None)
 
     def synthesize_clip(self, text, ref_audio, ref_text, *, clip_short=True, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
-                        seed=None, ode_method=None):
+                        seed=None, ode_method=None, remove_silence=None):
         """`synthesize` with the caller's own reference clip instead of a registered voice: `ref_audio` is a WAV file's bytes or a
         (wave [ch, n], sr) pair, `ref_text` its transcript; `clip_short` as in `preprocess_ref_audio_text`.  The clip never touches the
         disk (`_clip_voice`); the request then takes the same batcher path as `synthesize`, with the same options."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                    ode_method=ode_method)
+                                    ode_method=ode_method, remove_silence=remove_silence)
         voice, ref_text_n = self._clip_voice(ref_audio, ref_text, clip_short)
         req = self._request(voice, ref_text_n, text, opts)
         if self.batcher is not None:
@@ -557,13 +575,15 @@ class TTSManager:
         return self._run_batch([req])[0]
 
     def synthesize_clip_stream(self, text, ref_audio, ref_text, *, clip_short=True, speed=None, nfe_step=None, cfg_strength=None,
-                               sway_sampling_coef=None, seed=None, ode_method=None):
+                               sway_sampling_coef=None, seed=None, ode_method=None, remove_silence=None):
         """`synthesize_stream` with an uploaded reference clip (`synthesize_clip`): an iterator of float32 pieces whose concatenation is
         `synthesize_clip`'s wave given the same noise."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                    ode_method=ode_method)
+                                    ode_method=ode_method, remove_silence=remove_silence)
+        if opts.get("remove_silence"):
+            raise ValueError(STREAM_REMOVE_SILENCE)
         voice, ref_text_n = self._clip_voice(ref_audio, ref_text, clip_short)
         chunks = infer.request_chunks(ref_text_n, voice.seconds, text)
         if "seed" in opts:
@@ -571,19 +591,21 @@ class TTSManager:
         return self._stream(voice, ref_text_n, chunks[:1], chunks[1:], opts)
 
     def synthesize(self, text, ref_audio_path, ref_text, *, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None, seed=None,
-                   ode_method=None):
+                   ode_method=None, remove_silence=None):
         """The wave of one request.  The sampler options are this request's own (None: `self.opts`); `seed` draws its noise from its own
         generator (`infer.request_generator`), so the same seeded request gives the same audio whatever it is batched with (shape-invariant
         attention, one GPU).  `ode_method` ("euler", "midpoint", "rk4"; None: the model's): requests of different solvers share a batch, and
-        the option reaches the model object only for a request that sets it."""
+        the option reaches the model object only for a request that sets it.  `remove_silence=True`: the reference's
+        `remove_silence_for_generated_wav` -- pauses of 1 s or more shrink to 500 ms on each side -- and the result is int16 PCM
+        (`audio_prep.remove_silence_pcm` of the quantised wave); with `device_backend` every result is int16 PCM."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                    ode_method=ode_method)
+                                    ode_method=ode_method, remove_silence=remove_silence)
         return self.model(text, ref_audio_path=ref_audio_path, ref_text=ref_text, **opts)
 
     def synthesize_stream(self, text, ref_audio_path, ref_text, *, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
-                          seed=None, ode_method=None):
+                          seed=None, ode_method=None, remove_silence=None):
         """`synthesize` as an iterator of float32 pieces (24 kHz) whose concatenation is `synthesize`'s wave given the same noise (see
         `infer.infer_process_stream`).  The request's first chunk is synthesized on its own and its stable samples come out as soon as it is
         done; the remaining chunks follow as a second request.  With a micro-batcher the first chunk rides in the next batch and the
@@ -595,7 +617,9 @@ class TTSManager:
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                    ode_method=ode_method)
+                                    ode_method=ode_method, remove_silence=remove_silence)
+        if opts.get("remove_silence"):   # removal needs the whole wave
+            raise ValueError(STREAM_REMOVE_SILENCE)
         voice, ref_text_n = self._voice(ref_audio_path, ref_text)
         chunks = infer.request_chunks(ref_text_n, voice.seconds, text)
         if "seed" in opts:   # head and tail continue one sequence; the tail's batch runs after the head's (one worker, one batch at a time)
@@ -673,7 +697,7 @@ class TTSManager:
 def wav_bytes(audio: np.ndarray, sample_rate: int = infer.target_sample_rate) -> io.BytesIO:
     a = np.asarray(audio)
     if a.dtype != np.int16:
-        a = np.clip(np.rint(a.astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
+        a = infer.quantise_pcm16(a)
     buf = io.BytesIO()
     with _wave.open(buf, "wb") as f:
         f.setnchannels(1); f.setsampwidth(2); f.setframerate(sample_rate)
@@ -684,8 +708,7 @@ def wav_bytes(audio: np.ndarray, sample_rate: int = infer.target_sample_rate) ->
 
 def pcm16(audio: np.ndarray) -> bytes:
     """Little-endian int16 PCM bytes of float samples, by `wav_bytes`'s rule: rint(x * 32768), clipped."""
-    a = np.clip(np.rint(np.asarray(audio).astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
-    return a.astype("<i2").tobytes()
+    return infer.quantise_pcm16(audio).astype("<i2").tobytes()
 
 
 def wav_stream_header(sample_rate: int = infer.target_sample_rate) -> bytes:
@@ -737,7 +760,8 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     -> the edited recording as WAV), plus `/v1/audio/speech/clone`: `/v1/audio/speech/voice` with the caller's own reference clip
     ({"text", "ref_audio": base64 WAV, "ref_text", "clip_short": true, ...}) instead of a registered voice's name.  The speech routes take `"stream": true`: the WAV then arrives chunk by chunk (`_run_stream`), its
     PCM samples identical to the unstreamed response's.  Every route also takes the optional sampler fields `nfe_step`, `cfg_strength`,
-    `sway_sampling_coef`, `seed`, `ode_method` ("euler", "midpoint" or "rk4": the request's ODE solver) and (speech routes) `speed`, checked
+    `sway_sampling_coef`, `seed`, `ode_method` ("euler", "midpoint" or "rk4": the request's ODE solver) and (speech routes) `speed` and
+    `remove_silence` (true: pauses of 1 s or more are cut down to 500 ms on each side; 400 together with `"stream": true`), checked
     before anything is queued (400 with `check_request_options`'s message); an omitted field is the manager's setting (`ode_method`: the
     model's).  With a `seed`, the same request returns the same audio."""
     from fastapi import APIRouter, FastAPI, HTTPException
@@ -755,6 +779,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         text: str
         stream: bool = False
         speed: float | None = None
+        remove_silence: bool | None = None
 
     class SynthesizeRequest(SamplerFields):          # S/utils/tts_utils.py:22-25
         text: str
@@ -762,6 +787,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         ref_text: str | None = None
         stream: bool = False
         speed: float | None = None
+        remove_silence: bool | None = None
 
     class EditRequest(SamplerFields):                # F/infer/speech_edit.py's inputs; JSON (base64 WAV), not multipart
         audio: str
@@ -776,6 +802,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         clip_short: bool = True
         stream: bool = False
         speed: float | None = None
+        remove_silence: bool | None = None
 
     def _options(req, allowed):
         """The request's sampler fields, checked (400) before anything is queued."""
@@ -791,6 +818,8 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
         opts = _options(req, infer.REQUEST_OPTIONS)
+        if req.stream and opts.get("remove_silence"):
+            raise HTTPException(status_code=400, detail=STREAM_REMOVE_SILENCE)
         if not text.strip():
             raise HTTPException(status_code=400, detail="Text to synthesize cannot be empty.")
         return opts
