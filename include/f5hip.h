@@ -451,6 +451,33 @@ int f5hip_ref_frontend(int32_t n, const int32_t* n_in, const int32_t* channels, 
 int f5hip_wave_finish(int32_t n, const int32_t* chunks_per_request, const float* const* chunk_dev, const int32_t* chunk_len, int32_t fade,
                       const uint8_t* remove_silence, int32_t sample_rate, int16_t* pcm_dev, int32_t* len_dev, void* stream);
 
+/* The delivery format of n finished requests, in one call: their 24 kHz int16 PCM (f5hip_wave_finish's pcm_dev, still on the device) resampled
+ * to new_freq and encoded.  Not in the reference, whose route always answers with 24 kHz PCM; the definition is infer.resample_pcm16 /
+ * infer.encode_g711, which this call equals bit for bit.
+ *   pcm_dev, in_off[i]     request i's samples start at pcm_dev + in_off[i] (host array, in samples; any sign: separate allocations work)
+ *   max_len[i]             host, >= 0: an upper bound of request i's length, which sizes its blocks and its part of out_dev
+ *   len_dev                device int32 [n] or null: the actual lengths (f5hip_wave_finish's len_dev; clamped to [0, max_len[i]]); null:
+ *                          max_len
+ *   new_freq               output rate; 24000: no resampling
+ *   encoding               0: int16 PCM, 1: G.711 mu-law, 2: G.711 A-law (CPython's audioop.lin2ulaw / lin2alaw at width 2), one byte per sample
+ *   taps_dev               fp32 [nf][2*width+of]: the table infer.resample_taps(24000, new_freq) builds; null when new_freq == 24000
+ *   out_dev, out_off[i]    16-byte aligned; request i's samples / code bytes start at byte out_off[i] (host array, multiples of 16), its part
+ *                          at least ceil(nf * max_len[i] / of) samples long
+ *   out_len_dev            int32 [n]: ceil(nf * len_i / of), the samples request i ends up with
+ * Output j = q nf + p is rint(sum_k (double)taps[p][k] * (double)xpad[q of + k]), k ascending, half to even, clipped to [-32768, 32767], with
+ * xpad the request's samples between zeros (`width` in front): integer samples times fp32 taps are exact in fp64, so the sum has the bits of
+ * numpy's multiply-then-add.  One launch whatever n (counters wave_encode_launches, wave_encode_requests), no atomics, a request's bytes
+ * depend on that request alone; the request table is copied on `stream`, which the call waits for once before it launches.
+ * Refused before the launch: n < 1, a null pointer (len_dev and, at 24000, taps_dev excepted), an unknown encoding, a null table when the
+ * rates differ, a negative max_len, a misaligned pointer or output offset, more than 2^31 - 1 samples in or out, a rate whose window and tap
+ * table do not fit the LDS together (the seven rates of infer.OUTPUT_SAMPLE_RATES all fit). */
+int f5hip_wave_encode(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, int32_t new_freq,
+                      int32_t encoding, const float* taps_dev, uint8_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, void* stream);
+
+/* Input samples one block of f5hip_wave_encode owns at new_freq (a whole number of polyphase blocks); 0 for a rate it refuses.  For tests,
+ * which place request lengths around it. */
+int f5hip_wave_encode_tile(int32_t new_freq);
+
 #ifdef __cplusplus
 }
 #endif

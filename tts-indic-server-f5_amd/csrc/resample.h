@@ -92,6 +92,17 @@ __global__ __launch_bounds__(256) void ref_reduce_kernel(const RefClip* __restri
     if (tid == 0) partials[b] = total;
 }
 
+// the tap table (nt floats) into LDS at tp (16-byte aligned) by a block of 256 threads: 16-byte loads where the table's address allows
+F5_DEVICE void ref_stage_taps(float* tp, const float* __restrict__ taps, int nt, int tid) {
+    if ((reinterpret_cast<uintptr_t>(taps) & 15) == 0) {
+        const float4* t4 = reinterpret_cast<const float4*>(taps);
+        for (int i = tid; i < nt / 4; i += 256) reinterpret_cast<float4*>(tp)[i] = t4[i];
+        for (int i = (nt & ~3) + tid; i < nt; i += 256) tp[i] = taps[i];
+    } else {
+        for (int i = tid; i < nt; i += 256) tp[i] = taps[i];
+    }
+}
+
 // MODE 0: tap table staged in LDS; 1: tap table read through L2; 2: orig_freq == new_freq (no taps: out = the gained mono clip)
 template <int MODE>
 __global__ __launch_bounds__(256) void ref_resample_kernel(const RefClip* __restrict__ clips, int n, const float* __restrict__ wave,
@@ -128,16 +139,7 @@ __global__ __launch_bounds__(256) void ref_resample_kernel(const RefClip* __rest
         }
         xs[i] = v;
     }
-    if (MODE == 0) {
-        const int nt = nf * L;
-        if ((reinterpret_cast<uintptr_t>(taps) & 15) == 0) {
-            const float4* t4 = reinterpret_cast<const float4*>(taps);
-            for (int i = tid; i < nt / 4; i += 256) reinterpret_cast<float4*>(tp)[i] = t4[i];
-            for (int i = (nt & ~3) + tid; i < nt; i += 256) tp[i] = taps[i];
-        } else {
-            for (int i = tid; i < nt; i += 256) tp[i] = taps[i];
-        }
-    }
+    if (MODE == 0) ref_stage_taps(tp, taps, nf * L, tid);
     __syncthreads();
 
     const int n_local = tq * nf;
@@ -178,19 +180,24 @@ static int ref_reserve(T** p, size_t* cap, size_t need, const char* what) {
 
 static int ref_gcd(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
 
+// The reduced rate pair of : nf of a resampling and the shape of its tap table (infer.resample_taps): rows of L = 2 width + of taps.
+// Equal rates: 1 : 1 and no table.
+struct RefRatePair { int of, nf, width, L; };
+static RefRatePair ref_rate_pair(int orig_freq, int new_freq) {
+    if (orig_freq == new_freq) return RefRatePair{1, 1, 0, 0};
+    const int g = ref_gcd(orig_freq, new_freq), of = orig_freq / g, nf = new_freq / g;
+    const int width = (int)ceil(6.0 * of / (std::min(of, nf) * 0.99));   // torchaudio: lowpass_filter_width 6, rolloff 0.99
+    return RefRatePair{of, nf, width, 2 * width + of};
+}
+
 int f5hip_ref_frontend(int32_t n, const int32_t* n_in, const int32_t* channels, const float* wave_dev, int32_t orig_freq, int32_t new_freq,
                        const float* taps_dev, float rms_floor, float* out_dev, float* rms_dev, void* stream) {
     if (n < 1 || !n_in || !channels || !wave_dev || !out_dev || !rms_dev) return fail(-1, "ref_frontend: bad argument");
     if (orig_freq < 1 || new_freq < 1) return fail(-1, "ref_frontend: sample rates must be positive (%d -> %d)", orig_freq, new_freq);
     const bool identity = orig_freq == new_freq;
     if (!identity && !taps_dev) return fail(-1, "ref_frontend: %d -> %d Hz needs the tap table", orig_freq, new_freq);
-    int of = 1, nf = 1, width = 0, L = 0;
-    if (!identity) {
-        const int g = ref_gcd(orig_freq, new_freq);
-        of = orig_freq / g; nf = new_freq / g;
-        width = (int)ceil(6.0 * of / (std::min(of, nf) * 0.99));   // torchaudio: lowpass_filter_width 6, rolloff 0.99
-        L = 2 * width + of;
-    }
+    const RefRatePair rp = ref_rate_pair(orig_freq, new_freq);
+    const int of = rp.of, nf = rp.nf, width = rp.width, L = rp.L;
     // Tile: a block owns tq polyphase blocks.  With the table in LDS the tile grows with the table (2 staged taps per output at most), while
     // window + table fit the CU's LDS; else the small tile, with the table in LDS if that fits, else read through L2.  An output's bits do
     // not depend on the tile: one thread adds its terms in k order whatever block it runs in.

@@ -23,6 +23,7 @@
 #include <vector>
 
 //   torch.ops.f5hip.wave_finish(chunks[], chunks_per_request, fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/utils_infer.py:485-519,530-539
+//   torch.ops.f5hip.wave_encode(pcm[], in_off, max_len, len_dev?, new_freq, encoding, taps?) -> (Tensor bytes uint8, Tensor lengths int32, Tensor offsets int64 host)
 #include "../../include/f5hip.h"
 
 namespace {
@@ -283,6 +284,65 @@ std::tuple<at::Tensor, at::Tensor> wave_finish(at::TensorList chunks, const at::
     return {pcm, lengths};
 }
 
+// pcm: ONE int16 device tensor that holds every request (f5hip_wave_finish's packed PCM) or one tensor per request; in_off [n] int64 host (request
+// i starts at sample in_off[i] of its tensor); max_len [n] int32 host; len_dev [n] int32 device or None; taps as ref_frontend's, for 24000 ->
+// new_freq -> (out uint8 device: int16 samples little-endian, or G.711 code bytes; out_len [n] int32 device; out_off [n] int64 host, bytes)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_encode(at::TensorList pcm, const at::Tensor& in_off, const at::Tensor& max_len,
+                                                           const c10::optional<at::Tensor>& len_dev, int64_t new_freq, int64_t encoding,
+                                                           const c10::optional<at::Tensor>& taps) {
+    check_host(in_off, at::kLong, "in_off"); check_host(max_len, at::kInt, "max_len");
+    const int64_t n = max_len.numel();
+    TORCH_CHECK(max_len.dim() == 1 && n > 0 && in_off.numel() == n, "f5hip::wave_encode: in_off and max_len need one value per request");
+    TORCH_CHECK((int64_t)pcm.size() == 1 || (int64_t)pcm.size() == n, "f5hip::wave_encode: pcm is one tensor or one per request (got ", pcm.size(), " for ", n, ")");
+    TORCH_CHECK(encoding >= 0 && encoding <= 2, "f5hip::wave_encode: unknown encoding ", encoding, " (0 pcm16, 1 mu-law, 2 A-law)");
+    TORCH_CHECK(new_freq >= 1 && new_freq <= INT32_MAX, "f5hip::wave_encode: the sample rate must be positive (got ", new_freq, ")");
+    const int64_t g = std::gcd((int64_t)24000, new_freq), of = 24000 / g, nf = new_freq / g;
+    if (new_freq != 24000) {
+        TORCH_CHECK(taps.has_value(), "f5hip::wave_encode: 24000 -> ", new_freq, " Hz needs the tap table");
+        check_dev_f32(*taps, "taps");
+        const int64_t width = (int64_t)std::ceil(6.0 * (double)of / ((double)std::min(of, nf) * 0.99));
+        TORCH_CHECK(taps->dim() == 2 && taps->size(0) == nf && taps->size(1) == 2 * width + of, "f5hip::wave_encode: taps must be [nf = ", nf,
+                    "][2 * width + of = ", 2 * width + of, "] (lowpass_filter_width 6, rolloff 0.99); got ", taps->sizes());
+    }
+    for (const at::Tensor& t : pcm)
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kShort && t.is_contiguous() && t.dim() == 1 && t.device() == pcm[0].device(),
+                    "f5hip::wave_encode: pcm must be contiguous 1-D int16 tensors on one HIP device");
+    if (len_dev.has_value())
+        TORCH_CHECK(len_dev->is_cuda() && len_dev->scalar_type() == at::kInt && len_dev->is_contiguous() && len_dev->numel() == n &&
+                    len_dev->device() == pcm[0].device(), "f5hip::wave_encode: len_dev must be a contiguous int32 tensor with one value per request on the pcm's device");
+    const int64_t* io = in_off.data_ptr<int64_t>();
+    const int32_t* ml = max_len.data_ptr<int32_t>();
+    const int64_t bps = encoding == 0 ? 2 : 1;
+    at::Tensor anchor;                               // offsets are relative to the first tensor that has an address
+    for (const at::Tensor& t : pcm)
+        if (t.numel() && !anchor.defined()) anchor = t;
+    if (!anchor.defined()) anchor = at::zeros({8}, pcm[0].options());
+    const int16_t* base = anchor.data_ptr<int16_t>();
+    std::vector<int64_t> rel(n);
+    at::Tensor out_off = at::empty({n}, at::TensorOptions().dtype(at::kLong));
+    int64_t* oo = out_off.data_ptr<int64_t>();
+    int64_t total_in = 0, total_out = 0, bytes = 0;
+    for (int64_t i = 0; i < n; i++) {
+        const at::Tensor& t = pcm[pcm.size() == 1 ? 0 : i];
+        TORCH_CHECK(ml[i] >= 0 && io[i] >= 0 && io[i] + ml[i] <= t.numel(), "f5hip::wave_encode: request ", i, " reads samples [", io[i], ", ", io[i] + ml[i],
+                    ") of a tensor of ", t.numel());
+        rel[i] = ml[i] ? (t.data_ptr<int16_t>() - base) + io[i] : 0;   // (an empty tensor has no address to speak of)
+        const int64_t n_out = (nf * ml[i] + of - 1) / of;
+        total_in += ml[i]; total_out += n_out;
+        TORCH_CHECK(total_in <= INT32_MAX && total_out <= INT32_MAX, "f5hip::wave_encode: the call exceeds 2^31 - 1 samples in or out");
+        oo[i] = bytes;
+        bytes += (n_out * bps + 15) & ~(int64_t)15;
+    }
+    const c10::DeviceGuard guard(pcm[0].device());   // allocations and stream on the pcm's device
+    // (a call of empty requests still has an address to give)
+    at::Tensor out = at::empty({std::max<int64_t>(bytes, 16)}, pcm[0].options().dtype(at::kByte)).narrow(0, 0, bytes), out_len = at::empty({n}, pcm[0].options().dtype(at::kInt));
+    const int rc = f5hip_wave_encode((int32_t)n, base, rel.data(), ml, len_dev.has_value() ? len_dev->data_ptr<int32_t>() : (const int32_t*)nullptr,
+                                     (int32_t)new_freq, (int32_t)encoding, new_freq != 24000 ? taps->data_ptr<float>() : (const float*)nullptr,
+                                     out.data_ptr<uint8_t>(), oo, out_len.data_ptr<int32_t>(), stream_of(pcm[0]));
+    TORCH_CHECK(rc == 0, "f5hip_wave_encode: ", f5hip_last_error());
+    return {out, out_len, out_off};
+}
+
 }   // namespace
 
 TORCH_LIBRARY(f5hip, m) {
@@ -297,4 +357,5 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("bigvgan_forward_ragged(int handle, Tensor mel, Tensor frames, int channels, int total_upsample) -> Tensor", &bigvgan_forward_ragged);
     m.def("ref_frontend(Tensor wave, Tensor n_in, Tensor channels, int orig_freq, int new_freq, Tensor? taps, float rms_floor) -> (Tensor, Tensor)", &ref_frontend);
     m.def("wave_finish(Tensor[] chunks, Tensor chunks_per_request, int fade, Tensor remove_silence, int sample_rate) -> (Tensor, Tensor)", &wave_finish);
+    m.def("wave_encode(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int new_freq, int encoding, Tensor? taps) -> (Tensor, Tensor, Tensor)", &wave_encode);
 }

@@ -11,6 +11,11 @@
 //                         min_silence_len 1000, silence_thresh -50, keep_silence 500, seek_step 10 on integers -> the kept sample ranges
 //   wave_compact_kernel   copies the kept ranges of the scratch PCM to the output
 // One launch when no request is flagged, else three, whatever n and the chunk counts.  A request's bits depend on that request alone.
+//   wave_encode_kernel    (f5hip_wave_encode) the finished 24 kHz PCM of n requests -> another sample rate and G.711: the resampler of resample.h
+//                         run in the other direction on integers, with an encoder behind it.  One block per tile of `tq` polyphase blocks of a
+//                         request: the int16 window and -- when it fits -- the tap table in LDS, one thread per output summing
+//                         taps[p][k] * xpad[q * of + k] in fp64, k ascending, then rint (half to even), clip, encode; the tile's bytes are
+//                         packed in LDS and leave in 16-byte stores.  One launch whatever n.
 //
 // Exactness.  With every chunk at least 2 F samples long the nested fades of cross_fade_concat never overlap, so joined sample j is either one
 // chunk sample or one fade of two chunk samples, and the closed form above is the host's arithmetic operation for operation (ramp[i] =
@@ -400,5 +405,157 @@ int f5hip_wave_finish(int32_t n, const int32_t* chunks_per_request, const float*
         g_counters[CNT_WAVE_LAUNCHES] += 2;
     }
     g_counters[CNT_WAVE_REQUESTS] += n;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ delivery format: sample rate and G.711
+// Output j = q nf + p of a request is rint(sum_k (double)taps[p][k] * (double)xpad[q of + k]), k ascending, clipped to int16: xpad = its samples
+// with `width` zeros in front and zeros behind (an index predicate against the request's own length, never a read of its neighbour).  The
+// samples are integers and the taps fp32, so every product is exact in fp64 and an fma gives the bits of a multiply followed by an add:
+// infer.resample_pcm16 (numpy) is this arithmetic operation for operation.  The encoders are CPython's audioop.lin2ulaw / lin2alaw at width 2.
+struct WeReq {
+    long long in_off;    // its first sample, relative to pcm_dev
+    long long out_off;   // its first output byte (a multiple of 16: 16-byte stores)
+    int cap;             // upper bound of its length (the length itself without len_dev)
+    int tile0;           // its first block
+};
+
+constexpr int kWeTileOutputs = 4096;            // outputs a block aims for; a tile holds a multiple of 16 outputs, so it starts on a 16-byte boundary
+constexpr int kWeEncodings = 3;                 // 0 pcm16, 1 mu-law, 2 A-law
+
+F5_DEVICE int we_ilog2(int m) { return 31 - __clz(m); }   // floor(log2 m), m >= 1
+
+F5_DEVICE int we_mulaw(int s) {   // audioop.lin2ulaw: 14-bit magnitude, clipped where the bias would leave the last segment, bias 0x21
+    const int x = s >> 2, sign = x < 0 ? 0x7F : 0xFF;
+    const int m = min(abs(x), 8158) + 0x21, seg = we_ilog2(m) - 5;
+    return ((seg << 4) | ((m >> (seg + 1)) & 15)) ^ sign;
+}
+
+F5_DEVICE int we_alaw(int s) {    // audioop.lin2alaw: 13-bit, a negative value as -x - 1
+    const int x = s >> 3, mask = x >= 0 ? 0xD5 : 0x55;
+    const int m = x >= 0 ? x : -x - 1, seg = max(we_ilog2(max(m, 1)) - 4, 0);
+    return ((seg << 4) | ((m >> (seg < 2 ? 1 : seg)) & 15)) ^ mask;
+}
+
+// RESAMPLE: the tap table staged in LDS (every rate the entry point accepts: a table that does not fit is refused); else new_freq == 24000
+// (no taps: the samples themselves)
+template <bool RESAMPLE>
+__global__ __launch_bounds__(256) void wave_encode_kernel(const WeReq* __restrict__ reqs, int n, const short* __restrict__ pcm,
+                                                          const int* __restrict__ len_dev, const float* __restrict__ taps, int of, int nf, int width,
+                                                          int L, int tq, int enc, unsigned char* __restrict__ out, int* __restrict__ out_len) {
+    extern __shared__ __attribute__((aligned(16))) char we_sm[];
+    const int tid = threadIdx.x;
+    const int r = wf_find<WeReq, &WeReq::tile0>(reqs, n, blockIdx.x);
+    const WeReq q = reqs[r];
+    const int tile = blockIdx.x - q.tile0;
+    const int len = len_dev ? min(max(len_dev[r], 0), q.cap) : q.cap;   // (never past what the host sized the buffers for)
+    const long long n_out = ((long long)nf * len + of - 1) / of;
+    if (tile == 0 && tid == 0) out_len[r] = (int)n_out;
+    const int n_local = tq * nf;                                        // outputs of a full tile
+    const long long j0 = (long long)tile * n_local;
+    if (j0 >= n_out) return;                                            // a tile past the request's actual length (the whole block leaves)
+
+    const int nx = tq * of + 2 * width;                                 // the window of xpad this tile reads: xpad[q0 * of .. q0 * of + nx)
+    short* xs = reinterpret_cast<short*>(we_sm);
+    unsigned char* ys = reinterpret_cast<unsigned char*>(we_sm + ((2 * nx + 15) & ~15));        // the tile's output bytes
+    float* tp = reinterpret_cast<float*>(ys + 2 * n_local);            // (n_local is a multiple of 16: 16-byte aligned)
+    const short* x = pcm + q.in_off;
+    const long long src0 = (long long)tile * tq * of - width;
+    for (int i = tid; i < nx; i += 256) {
+        const long long src = src0 + i;
+        xs[i] = src >= 0 && src < len ? x[src] : (short)0;
+    }
+    if (RESAMPLE) ref_stage_taps(tp, taps, nf * L, tid);
+    __syncthreads();
+
+    const int valid = (int)min((long long)n_local, n_out - j0);         // outputs of this tile
+    for (int jl = tid; jl < valid; jl += 256) {
+        int v;
+        if (!RESAMPLE) {
+            v = xs[jl];
+        } else {
+            const int ql = jl / nf, p = jl - ql * nf;
+            const float* t = tp + p * L;
+            const short* xq = xs + ql * of;
+            double acc = 0.0;
+            for (int k = 0; k < L; k++) acc = fma((double)t[k], (double)xq[k], acc);
+            v = (int)fmax(fmin(rint(acc), 32767.0), -32768.0);
+        }
+        if (enc == 0) reinterpret_cast<short*>(ys)[jl] = (short)v;
+        else ys[jl] = (unsigned char)(enc == 1 ? we_mulaw(v) : we_alaw(v));
+    }
+    __syncthreads();
+
+    const int bps = enc == 0 ? 2 : 1, nbytes = valid * bps;
+    unsigned char* dst = out + q.out_off + j0 * bps;                    // (16-byte aligned: out_off and j0 are multiples of 16)
+    for (int b = 16 * tid; b < nbytes; b += 16 * 256) {
+        if (b + 16 <= nbytes) {
+            *reinterpret_cast<int4*>(dst + b) = *reinterpret_cast<const int4*>(ys + b);
+        } else {
+            for (int e = b; e < nbytes; e++) dst[e] = ys[e];            // the ragged end of the request
+        }
+    }
+}
+
+struct WeWorkspace { WeReq* reqs = nullptr; size_t cap_reqs = 0; };
+static WeWorkspace g_we_ws[32];   // one per device ordinal
+
+// (tq, LDS bytes) of a rate pair; tq = 0: window, output tile and tap table do not fit the LDS together
+struct WeTile { int tq, lds; };
+static WeTile we_tile(const RefRatePair& rp) {
+    const int unit = 16 / ref_gcd(rp.nf, 16);                           // tq * nf must be a multiple of 16
+    const long long tq = ((kWeTileOutputs + (long long)rp.nf - 1) / rp.nf + unit - 1) / unit * unit;
+    const long long base = ((2 * (tq * rp.of + 2 * rp.width) + 15) & ~15LL) + 2 * tq * rp.nf, table = 4LL * rp.nf * rp.L;
+    if (base + table > kRefLdsMax) return WeTile{0, 0};
+    return WeTile{(int)tq, (int)(base + table)};
+}
+
+int f5hip_wave_encode_tile(int32_t new_freq) {
+    if (new_freq < 1) return 0;
+    const RefRatePair rp = ref_rate_pair(24000, new_freq);
+    return we_tile(rp).tq * rp.of;
+}
+
+int f5hip_wave_encode(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, int32_t new_freq,
+                      int32_t encoding, const float* taps_dev, uint8_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, void* stream) {
+    if (n < 1 || !pcm_dev || !in_off || !max_len || !out_dev || !out_off || !out_len_dev) return fail(-1, "wave_encode: bad argument");
+    if (encoding < 0 || encoding >= kWeEncodings) return fail(-1, "wave_encode: unknown encoding %d (0 pcm16, 1 mu-law, 2 A-law)", encoding);
+    if (new_freq < 1) return fail(-1, "wave_encode: the sample rate must be positive (got %d)", new_freq);
+    const bool identity = new_freq == 24000;
+    if (!identity && !taps_dev) return fail(-1, "wave_encode: 24000 -> %d Hz needs the tap table", new_freq);
+    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 1) || (reinterpret_cast<uintptr_t>(out_dev) & 15))
+        return fail(-1, "wave_encode: the input must be 2-byte aligned and the output 16-byte aligned");
+    const RefRatePair rp = ref_rate_pair(24000, new_freq);
+    const WeTile t = we_tile(rp);
+    if (!t.tq) return fail(-1, "wave_encode: 24000 -> %d Hz is not supported (%d : %d: its tap table does not fit the LDS)", new_freq, rp.of, rp.nf);
+    std::vector<WeReq> h(n);
+    long long total_in = 0, total_out = 0, tiles = 0;
+    for (int i = 0; i < n; i++) {
+        if (max_len[i] < 0) return fail(-1, "wave_encode: request %d has a negative length bound (%d)", i, max_len[i]);
+        if (out_off[i] < 0 || (out_off[i] & 15)) return fail(-1, "wave_encode: the output offset of request %d is not a multiple of 16 bytes", i);
+        const long long n_out = ((long long)rp.nf * max_len[i] + rp.of - 1) / rp.of, nq = (n_out + rp.nf - 1) / rp.nf;
+        total_in += max_len[i]; total_out += n_out;
+        if (total_in > 2147483647LL || total_out > 2147483647LL) return fail(-1, "wave_encode: the call exceeds 2^31 - 1 samples in or out");
+        h[i] = WeReq{in_off[i], out_off[i], max_len[i], (int)tiles};
+        tiles += std::max<long long>((nq + t.tq - 1) / t.tq, 1);      // (an empty request keeps one block: it writes its length)
+    }
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return fail(-6, "wave_encode: hipGetDevice");
+    WeWorkspace& ws = g_we_ws[dev & 31];
+    CK(ref_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_encode requests"));
+    static unsigned lds_attr_done = 0;
+    if (t.lds > 64 * 1024 && f5_set_lds_attr((const void*)wave_encode_kernel<true>, kRefLdsMax, lds_attr_done) != hipSuccess)
+        return fail(-7, "wave_encode: LDS opt-in");
+    hipStream_t st = (hipStream_t)stream;
+    if (upload_sync(st, ws.reqs, h) != hipSuccess) return fail(-6, "wave_encode metadata upload");
+#define F5_WE_LAUNCH(RESAMPLE)                                                                                                                 \
+    hipLaunchKernelGGL(wave_encode_kernel<RESAMPLE>, dim3((unsigned)tiles), dim3(256), t.lds, st, ws.reqs, n, (const short*)pcm_dev, (const int*)len_dev, \
+                       taps_dev, rp.of, rp.nf, rp.width, rp.L, t.tq, encoding, (unsigned char*)out_dev, (int*)out_len_dev)
+    if (identity) F5_WE_LAUNCH(false);
+    else F5_WE_LAUNCH(true);
+#undef F5_WE_LAUNCH
+    CKL("wave_encode");
+    g_counters[CNT_WAVE_ENCODE_LAUNCHES]++;
+    g_counters[CNT_WAVE_ENCODE_REQUESTS] += n;
     return 0;
 }

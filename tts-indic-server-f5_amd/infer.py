@@ -634,7 +634,8 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 
 
 # per-request options of `infer_requests` (the fourth element of a request) and of the serving routes
-REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "remove_silence")
+_PLAIN = (target_sample_rate, "pcm16")   # the delivery format of a request that sets neither `sample_rate` nor `encoding`
+REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "remove_silence", "sample_rate", "encoding")
 
 
 def plan_request(request, defaults, *, target_rms, fix_duration, device, tokenizer):
@@ -649,6 +650,9 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
         raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
     if opts.get("remove_silence") and isinstance(gen_text, (list, tuple)):
         raise ValueError("remove_silence needs the request's whole wave: it is not available for a list of chunk texts (a streamed request)")
+    if delivery_format(opts.get("sample_rate"), opts.get("encoding")) != _PLAIN and isinstance(gen_text, (list, tuple)):
+        raise ValueError("sample_rate / encoding apply to a request's joined wave: a list of chunk texts (a streamed request) gets them from "
+                         "its caller, piece by piece (StreamResampler, encode_g711)")
     voice, units = _plan_request(ref_audio, ref_text, gen_text, target_rms, opts["speed"], fix_duration, device, tokenizer)
     own = opts.get("generator")
     gen = torch.Generator().set_state(own.get_state()) if own is not None else request_generator(opts["seed"])
@@ -695,7 +699,10 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
 
     `remove_silence` (bool, per request): the reference's `remove_silence_for_generated_wav` on the finished wave; such a request's wave is
     int16 PCM (`audio_prep.remove_silence_pcm` of its quantised joined wave), and it needs the whole wave: ValueError with `join=False` or a
-    list of chunk texts.  `finish` = dict(device_backend=..., want=...): what the serving path asks for -- the list of `finish_requests`
+    list of chunk texts.  `sample_rate` (one of OUTPUT_SAMPLE_RATES) and `encoding` ("pcm16", "mulaw", "alaw"), per request: the delivery
+    format, a pure function of the request's 24 kHz int16 PCM (`deliver_pcm16`: after silence removal, `resample_pcm16`, then `encode_g711`);
+    such a request's wave is int16 at that rate or uint8 code bytes, its triple names that rate, and like `remove_silence` it needs the whole
+    wave.  `finish` = dict(device_backend=..., want=...): what the serving path asks for -- the list of `finish_requests`
     results (one wave per request, no triples) with no spectrogram downloaded."""
     defaults = dict(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None)
     calls = {}   # calls: (nfe_step, sway, ode_method) -> [unit ids, ...] of one sampler call each
@@ -731,17 +738,19 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
         groups.append((mels[k:k + len(plan.units)], plan.voice.ref_frames, plan.voice.rms))
         k += len(plan.units)
     silence = [bool(plan.opts.get("remove_silence")) for plan in plans]
+    formats = [delivery_format(plan.opts.get("sample_rate"), plan.opts.get("encoding")) for plan in plans]
     if finish is not None:
         backend = bool(finish.get("device_backend"))
         chunk_waves = [waves for waves, _ in _chunk_waves(groups, vocoder, mel_spec_type, target_rms, on_device=backend, want_specs=False)]
-        return finish_requests(chunk_waves, [req[2] for req in requests], cross_fade_duration, silence, **finish)
-    if any(silence) and not join:
-        raise ValueError("remove_silence needs the request's whole wave: it is not available with join=False")
+        return finish_requests(chunk_waves, [req[2] for req in requests], cross_fade_duration, silence, sample_rate=[f[0] for f in formats],
+                               encoding=[f[1] for f in formats], **finish)
+    if (any(silence) or any(f != _PLAIN for f in formats)) and not join:
+        raise ValueError("remove_silence, sample_rate and encoding need the request's whole wave: they are not available with join=False")
     out = []
-    for flag, (waves, specs) in zip(silence, _chunk_waves(groups, vocoder, mel_spec_type, target_rms)):
-        if flag:
-            wave, = finish_requests([waves], [""], cross_fade_duration, [True])
-            out.append((wave, target_sample_rate, np.concatenate(specs, axis=1)))
+    for flag, fmt, (waves, specs) in zip(silence, formats, _chunk_waves(groups, vocoder, mel_spec_type, target_rms)):
+        if flag or fmt != _PLAIN:
+            wave, = finish_requests([waves], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1])
+            out.append((wave, fmt[0], np.concatenate(specs, axis=1)))
         elif join:
             out.append((cross_fade_concat(waves, cross_fade_duration), target_sample_rate, np.concatenate(specs, axis=1)))
         else:
@@ -762,8 +771,167 @@ def quantise_pcm16(wave) -> np.ndarray:
     return np.clip(np.rint(np.asarray(wave).astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
 
 
+# ----------------------------------------- delivery format: output sample rate and G.711 (not in the reference, whose route always answers 24 kHz PCM)
+OUTPUT_SAMPLE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
+OUTPUT_ENCODINGS = ("pcm16", "mulaw", "alaw")     # their position is the library's encoding code (include/f5hip.h f5hip_wave_encode)
+
+
+def _polyphase_pcm(xpad, taps64, of, nq):
+    """Polyphase blocks 0 .. nq - 1 over xpad (float64, at least nq * of + L - of samples): out[q * nf + p] = sum_k taps64[p][k] * xpad[q * of + k],
+    k ascending, each product and each sum rounded to fp64 on its own; then rint (half to even), clipped, as int16."""
+    nf, L = taps64.shape
+    acc = np.zeros((nq, nf), dtype=np.float64)
+    for k in range(L):
+        acc += xpad[k:k + (nq - 1) * of + 1:of, None] * taps64[None, :, k]
+    return np.clip(np.rint(acc), -32768, 32767).astype(np.int16).reshape(-1)
+
+
+def _output_taps(new_freq):
+    if int(new_freq) not in OUTPUT_SAMPLE_RATES:
+        raise ValueError(f"sample_rate must be one of {list(OUTPUT_SAMPLE_RATES)} (got {new_freq!r})")
+    of, nf, width, taps = resample_taps(target_sample_rate, int(new_freq))
+    return of, nf, width, taps.numpy().astype(np.float64)
+
+
+def _as_pcm16(pcm):
+    pcm = np.asarray(pcm)
+    if pcm.dtype != np.int16 or pcm.ndim != 1:
+        raise ValueError(f"expected 1-D int16 PCM (got {pcm.dtype}, {pcm.ndim}-D)")
+    return pcm
+
+
+def resample_pcm16(pcm, new_freq) -> np.ndarray:
+    """24 kHz int16 PCM [n] at `new_freq` (one of OUTPUT_SAMPLE_RATES): int16 [resampled_length(n, 24000, new_freq)].  Output j = q nf + p is
+    rint(sum_k (double)taps[p][k] * (double)xpad[q of + k]) -- `resample_taps`' fp32 table, k ascending, fp64 accumulation, xpad = the samples
+    with `width` zeros in front and zeros behind -- half to even, clipped to [-32768, 32767].  Integer samples times fp32 taps are exact in
+    fp64 (16 + 24 bits), so a fused multiply-add and numpy's multiply-then-add give the same bits: the device kernel (csrc/wave_out.h
+    wave_encode_kernel) is held to this function with no tolerance.  24000 returns its input."""
+    pcm = _as_pcm16(pcm)
+    if int(new_freq) == target_sample_rate:
+        return pcm
+    of, nf, width, taps64 = _output_taps(new_freq)
+    m = resampled_length(len(pcm), target_sample_rate, new_freq)
+    if m == 0:
+        return np.zeros(0, dtype=np.int16)
+    nq = -(-m // nf)
+    xpad = np.zeros(nq * of + 2 * width, dtype=np.float64)
+    xpad[width:width + len(pcm)] = pcm
+    return _polyphase_pcm(xpad, taps64, of, nq)[:m]
+
+
+class StreamResampler:
+    """`resample_pcm16` one piece at a time: `feed(piece)` returns the outputs of every polyphase block whose input window is complete and keeps
+    the tail it still needs, `flush()` the rest (zeros behind the last sample).  The concatenation of everything returned equals
+    `resample_pcm16` of the concatenated input, bit for bit, whatever the piece sizes: an output's terms and their order do not depend on
+    when it is computed."""
+
+    def __init__(self, new_freq):
+        self.new_freq = int(new_freq)
+        self.identity = self.new_freq == target_sample_rate
+        if not self.identity:
+            self.of, self.nf, self.width, self.taps64 = _output_taps(new_freq)
+            self.tail = np.zeros(self.width, dtype=np.float64)   # xpad from block `q` on: the zeros in front at first
+        self.n = self.q = 0                                      # samples fed; polyphase blocks emitted
+
+    def feed(self, piece):
+        piece = _as_pcm16(piece)
+        if self.identity:
+            return piece
+        self.n += len(piece)
+        self.tail = np.concatenate([self.tail, piece.astype(np.float64)])
+        ready = max((self.n - self.width) // self.of, 0)         # block q needs xpad[q of .. q of + 2 width + of): width + n of it exist
+        if ready <= self.q:
+            return np.zeros(0, dtype=np.int16)
+        out = _polyphase_pcm(self.tail, self.taps64, self.of, ready - self.q)
+        self.tail = self.tail[(ready - self.q) * self.of:]
+        self.q = ready
+        return out
+
+    def flush(self):
+        if self.identity:
+            return np.zeros(0, dtype=np.int16)
+        m = resampled_length(self.n, target_sample_rate, self.new_freq)
+        nq = -(-m // self.nf) - self.q
+        if nq <= 0:
+            return np.zeros(0, dtype=np.int16)
+        xpad = np.zeros(nq * self.of + 2 * self.width, dtype=np.float64)
+        xpad[:len(self.tail)] = self.tail
+        out = _polyphase_pcm(xpad, self.taps64, self.of, nq)[:m - self.q * self.nf]
+        self.q, self.tail = self.q + nq, np.zeros(0, dtype=np.float64)
+        return out
+
+
+def _check_law(law):
+    if law not in ("mulaw", "alaw"):
+        raise ValueError(f'law must be "mulaw" or "alaw" (got {law!r})')
+
+
+def encode_g711(pcm, law) -> np.ndarray:
+    """G.711 code bytes (uint8) of int16 PCM: CPython's `audioop.lin2ulaw` / `lin2alaw` at width 2, in closed form.  mu-law works on the 14-bit
+    value s >> 2 (magnitude clipped at 8158, bias 0x21), A-law on the 13-bit value s >> 3 (a negative value as -x - 1); the segment is the
+    position of the leading bit."""
+    _check_law(law)
+    s = np.asarray(pcm)
+    if s.dtype != np.int16:
+        raise ValueError(f"expected int16 PCM (got {s.dtype})")
+    ilog2 = lambda m: np.frexp(m.astype(np.float64))[1] - 1   # noqa: E731  floor(log2 m), m >= 1
+    if law == "mulaw":
+        x = s.astype(np.int32) >> 2
+        sign = np.where(x < 0, 0x7F, 0xFF)
+        m = np.minimum(np.abs(x), 8158) + 0x21
+        seg = ilog2(m) - 5
+        code = ((seg << 4) | ((m >> (seg + 1)) & 15)) ^ sign
+    else:
+        x = s.astype(np.int32) >> 3
+        mask = np.where(x >= 0, 0xD5, 0x55)
+        m = np.where(x >= 0, x, -x - 1)
+        seg = np.maximum(ilog2(np.maximum(m, 1)) - 4, 0)
+        code = ((seg << 4) | ((m >> np.where(seg < 2, 1, seg)) & 15)) ^ mask
+    return code.astype(np.uint8)
+
+
+def decode_g711(codes, law) -> np.ndarray:
+    """int16 PCM of G.711 code bytes: `audioop.ulaw2lin` / `alaw2lin` at width 2."""
+    _check_law(law)
+    c = np.asarray(codes)
+    if c.dtype != np.uint8:
+        raise ValueError(f"expected uint8 codes (got {c.dtype})")
+    c = c.astype(np.int32)
+    if law == "mulaw":
+        u = ~c & 0xFF
+        t = (((u & 0x0F) << 3) + 0x84) << ((u & 0x70) >> 4)
+        out = np.where(u & 0x80, 0x84 - t, t - 0x84)
+    else:
+        a = c ^ 0x55
+        seg = (a & 0x70) >> 4
+        t = (a & 0x0F) << 4
+        t = np.where(seg == 0, t + 8, (t + 0x108) << np.maximum(seg - 1, 0))
+        out = np.where(a & 0x80, t, -t)
+    return out.astype(np.int16)
+
+
+def delivery_format(sample_rate=None, encoding=None):
+    """(rate, encoding) of a request with None filled in (24000, "pcm16"), checked against OUTPUT_SAMPLE_RATES / OUTPUT_ENCODINGS."""
+    rate = target_sample_rate if sample_rate is None else sample_rate
+    enc = "pcm16" if encoding is None else encoding
+    if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or int(rate) not in OUTPUT_SAMPLE_RATES:
+        raise ValueError(f"sample_rate must be one of {list(OUTPUT_SAMPLE_RATES)} (got {sample_rate!r})")
+    if not isinstance(enc, str) or enc not in OUTPUT_ENCODINGS:
+        raise ValueError(f"encoding must be one of {list(OUTPUT_ENCODINGS)} (got {encoding!r})")
+    return int(rate), enc
+
+
+def deliver_pcm16(pcm, sample_rate=None, encoding=None) -> np.ndarray:
+    """The delivery format of a request's canonical result, its 24 kHz int16 PCM: `resample_pcm16`, then `encode_g711` -- int16 at
+    `sample_rate`, or uint8 code bytes.  (24000, "pcm16") returns the PCM itself."""
+    rate, enc = delivery_format(sample_rate, encoding)
+    pcm = resample_pcm16(pcm, rate)
+    return pcm if enc == "pcm16" else encode_g711(pcm, enc)
+
+
 # What `finish_requests` and `_chunk_waves` did since the last `backend_stats.clear()`: requests finished on the device / on the host,
-# `ops.wave_finish` calls, and device-to-host copies (chunk waves, spectrograms, PCM, lengths)
+# `ops.wave_finish` calls, `ops.wave_encode` calls and the requests they encoded (`encode_calls`, `encode_requests`), and device-to-host copies
+# (chunk waves, spectrograms, PCM, encoded samples, lengths)
 backend_stats: collections.Counter = collections.Counter()
 
 
@@ -775,8 +943,15 @@ def _host_chunk(wave):
     return wave
 
 
+def _per_request(value, n, what):
+    vals = list(value) if isinstance(value, (list, tuple)) else [value] * n
+    if len(vals) != n:
+        raise ValueError(f"finish_requests: one {what} or one per request ({n}), got {len(vals)}")
+    return vals
+
+
 def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cross_fade_duration, remove_silence=None, device_backend=False,
-                    want="float"):
+                    want="float", sample_rate=None, encoding=None):
     """From the chunk waves of several requests (rms restored; numpy, or tensors as `_chunk_waves(on_device=True)` leaves them) to what each
     request gets.  A request whose text is a list of chunk texts (a streamed request's head or tail) gets its chunk waves as they are, like
     `request_wave`.  Any other request gets its joined wave: float32 (`request_wave`) with want="float", int16 PCM (`quantise_pcm16` of that)
@@ -786,7 +961,15 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     and silence removal on the device, bit for bit the host arithmetic -- and then at most two device-to-host copies: the lengths (only when
     a request asked for silence removal) and the samples.  Not eligible, and finished on the host in the same call (counted in
     `backend_stats`): a list text, chunk waves that are not on a HIP device, and a request of several chunks with one shorter than twice the
-    fade, where the reference's nested cross-fades overlap and the kernel's closed form does not hold."""
+    fade, where the reference's nested cross-fades overlap and the kernel's closed form does not hold.
+
+    `sample_rate` / `encoding`: one value or one per request; None, 24000 and "pcm16" mean the result described above.  Any other request
+    gets `deliver_pcm16` of its int16 PCM (quantised whatever `want` says, after silence removal): int16 at that rate, or uint8 G.711 codes.
+    With `device_backend` the requests `ops.wave_finish` finished go through ONE `ops.wave_encode` call per distinct (rate, encoding) pair,
+    chained on the same stream with no download in between (a flagged request's length stays on the device); per pair at most two copies come
+    back, the lengths (only with silence removal) and the encoded samples, and nothing of those requests' 24 kHz PCM.  Like every ragged call
+    of the library each `wave_encode` call copies its small request table on the stream and waits for that copy before it launches, so the
+    host does wait once per pair for what is queued in front of it (`wave_finish`'s kernels); no data comes back in that wait."""
     if want not in ("float", "pcm16"):
         raise ValueError(f'want must be "float" or "pcm16" (got {want!r})')
     if device_backend and want != "pcm16":
@@ -795,12 +978,13 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     flags = [False] * n if remove_silence is None else [bool(f) for f in remove_silence]
     if len(gen_texts) != n or len(flags) != n:
         raise ValueError("finish_requests: one text and one remove_silence flag per request")
+    formats = [delivery_format(r, e) for r, e in zip(_per_request(sample_rate, n, "sample_rate"), _per_request(encoding, n, "encoding"))]
     fade = int(cross_fade_duration * target_sample_rate) if cross_fade_duration > 0 else 0
     out, on_device = [None] * n, []
     for i, (waves, text) in enumerate(zip(chunk_waves_per_request, gen_texts)):
         if isinstance(text, (list, tuple)):
-            if flags[i]:
-                raise ValueError("remove_silence needs the request's whole wave: it is not available for a list of chunk texts")
+            if flags[i] or formats[i] != _PLAIN:
+                raise ValueError("remove_silence, sample_rate and encoding need the request's whole wave: they are not available for a list of chunk texts")
             out[i] = [_host_chunk(w) for w in waves]
         elif device_backend and all(torch.is_tensor(w) and w.is_cuda for w in waves) and (len(waves) == 1 or min(len(w) for w in waves) >= 2 * fade):
             on_device.append(i)
@@ -810,24 +994,49 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
             if flags[i]:
                 from .audio_prep import remove_silence_pcm
                 wave = remove_silence_pcm(quantise_pcm16(wave), target_sample_rate)
-            elif want == "pcm16":
+            elif want == "pcm16" or formats[i] != _PLAIN:
                 wave = quantise_pcm16(wave)
-            out[i] = wave
+            out[i] = wave if formats[i] == _PLAIN else deliver_pcm16(wave, *formats[i])
         backend_stats["host_requests"] += 1
     if on_device:
         from . import ops
+        # the plain requests first: their PCM is then one prefix of the packed buffer, and what comes down of it holds no other request's
+        on_device.sort(key=lambda i: formats[i] != _PLAIN)
+        plain = sum(formats[i] == _PLAIN for i in on_device)
         chunks = [w.to(torch.float32).contiguous() for i in on_device for w in chunk_waves_per_request[i]]
         silence = [flags[i] for i in on_device]
+        joined = [sum(len(w) for w in chunk_waves_per_request[i]) - (len(chunk_waves_per_request[i]) - 1) * fade for i in on_device]
         pcm, lengths, offsets = ops.wave_finish(chunks, [len(chunk_waves_per_request[i]) for i in on_device], fade, silence, target_sample_rate)
-        if any(silence):
-            lengths = lengths.cpu().tolist()
+        if plain:
+            if any(silence[:plain]):
+                kept = lengths[:plain].cpu().tolist()
+                backend_stats["d2h_copies"] += 1
+            else:   # without silence removal a request keeps its joined length
+                kept = joined[:plain]
+            host = pcm[:offsets[plain - 1] + joined[plain - 1]].cpu().numpy()
             backend_stats["d2h_copies"] += 1
-        else:   # without silence removal a request keeps its joined length
-            lengths = [sum(len(w) for w in chunk_waves_per_request[i]) - (len(chunk_waves_per_request[i]) - 1) * fade for i in on_device]
-        host = pcm.cpu().numpy()
-        backend_stats["d2h_copies"] += 1
-        for i, off, length in zip(on_device, offsets, lengths):
-            out[i] = host[off:off + length].copy()   # (a request's result does not keep the batch's buffer alive)
+            for i, off, length in zip(on_device[:plain], offsets, kept):
+                out[i] = host[off:off + length].copy()   # (a request's result does not keep the batch's buffer alive)
+        groups = {}
+        for k in range(plain, len(on_device)):
+            groups.setdefault(formats[on_device[k]], []).append(k)
+        for (rate, enc), ks in groups.items():   # one call per delivery format, behind wave_finish on the same stream
+            taps = _device_taps(target_sample_rate, rate, pcm.device) if rate != target_sample_rate else None
+            contiguous = ks == list(range(ks[0], ks[-1] + 1))
+            sel = lengths[ks[0]:ks[-1] + 1] if contiguous else lengths[torch.tensor(ks, device=lengths.device)]   # (gathered on the device)
+            data, out_len, out_off = ops.wave_encode(pcm, [offsets[k] for k in ks], [joined[k] for k in ks], sel, rate, enc, taps)
+            if any(silence[k] for k in ks):
+                counts = out_len.cpu().tolist()
+                backend_stats["d2h_copies"] += 1
+            else:
+                counts = [resampled_length(joined[k], target_sample_rate, rate) for k in ks]
+            host = data.cpu().numpy()
+            backend_stats["d2h_copies"] += 1
+            for k, off, m in zip(ks, out_off, counts):
+                raw = host[off:off + m * (2 if enc == "pcm16" else 1)].copy()
+                out[on_device[k]] = raw.view("<i2") if enc == "pcm16" else raw
+            backend_stats["encode_calls"] += 1
+            backend_stats["encode_requests"] += len(ks)
         backend_stats["device_calls"] += 1
         backend_stats["device_requests"] += len(on_device)
     return out
@@ -836,8 +1045,9 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
 class SpanTicket:
     """One admitted request of a `SpanScheduler`: its planned units, and -- once they have all ended -- `result` (`request_wave`)."""
 
-    def __init__(self, request, voice, units, remove_silence=False):
+    def __init__(self, request, voice, units, remove_silence=False, sample_rate=None, encoding=None):
         self.request, self.voice, self.units, self.remove_silence = request, voice, units, bool(remove_silence)
+        self.sample_rate, self.encoding = delivery_format(sample_rate, encoding)
         self.in_flight = self.cancelled = self.done = False
         self.result = None
 
@@ -868,7 +1078,7 @@ class SpanScheduler:
     profiles/r07_admission_bench.txt) that boundary cost is 3.3 ms with 8 units in flight, 2.3 % of an 8-step span (4.6 % of a 4-step one),
     and 8 is the shortest span whose median time to result on the trace was not above `MicroBatcher`'s.
 
-    Finished requests leave through `finish_requests` (a request's `remove_silence` option included); with `device_backend=True` their chunk
+    Finished requests leave through `finish_requests` (a request's `remove_silence`, `sample_rate` and `encoding` options included); with `device_backend=True` their chunk
     waves stay on the device and their results are int16 PCM from one `ops.wave_finish` call per boundary."""
 
     def __init__(self, model_obj, vocoder, span_steps=span_steps, max_frames=None, max_requests=None, mel_spec_type=mel_spec_type, target_rms=target_rms,
@@ -907,7 +1117,7 @@ class SpanScheduler:
                                             sway_sampling_coef=opts["sway_sampling_coef"], generator=plan.generator, **extra)
                    for tokens, frames in plan.units]
         plan.commit()   # every chunk was planned: the caller's generator moves
-        ticket = SpanTicket(request, voice, planned, opts.get("remove_silence"))
+        ticket = SpanTicket(request, voice, planned, opts.get("remove_silence"), opts.get("sample_rate"), opts.get("encoding"))
         self.waiting.append(ticket)
         return ticket
 
@@ -932,7 +1142,8 @@ class SpanScheduler:
         chunk_waves = [waves for waves, _ in _chunk_waves(groups, self.vocoder, self.mel_spec_type, self.target_rms, on_device=self.device_backend,
                                                           want_specs=False)]
         results = finish_requests(chunk_waves, [t.request[2] for t in tickets], self.cross_fade_duration, [t.remove_silence for t in tickets],
-                                  device_backend=self.device_backend, want="pcm16" if self.device_backend else "float")
+                                  device_backend=self.device_backend, want="pcm16" if self.device_backend else "float",
+                                  sample_rate=[t.sample_rate for t in tickets], encoding=[t.encoding for t in tickets])
         for t, result in zip(tickets, results):
             t.result, t.done, t.in_flight = result, True, False
 

@@ -406,3 +406,75 @@ def wave_finish(chunks, chunks_per_request, fade, remove_silence=None, sample_ra
             _lib.check(_lib.lib().f5hip_wave_finish(len(k), _p(k), _p(ptrs), _p(lens), fade, _p(flags), int(sample_rate), _p(pcm), _p(lengths),
                                                     _lib.current_stream_ptr()), "f5hip_wave_finish")
     return pcm, lengths, offsets
+
+
+WAVE_ENCODINGS = ("pcm16", "mulaw", "alaw")   # the library's encoding codes 0, 1, 2 (infer.OUTPUT_ENCODINGS)
+
+
+def wave_encode_tile(sample_rate):
+    """24 kHz input samples one block of `wave_encode` owns at `sample_rate` (0: a rate the library refuses)."""
+    return int(_lib.lib().f5hip_wave_encode_tile(int(sample_rate)))
+
+
+def wave_encode(pcm, in_off, max_len, len_dev, sample_rate, encoding, taps=None):
+    """The delivery format of several finished requests in ONE library call and one launch (include/f5hip.h f5hip_wave_encode): their 24 kHz
+    int16 PCM on the device -> `sample_rate`, then "pcm16", "mulaw" or "alaw" (or the code 0, 1, 2).  `pcm`: one int16 device tensor that holds
+    every request (`wave_finish`'s packed PCM; request i starts at sample in_off[i]) or one tensor per request (in_off[i] within its own);
+    `max_len` [n]: an upper bound of each length, which sizes the output; `len_dev`: int32 device [n], the actual lengths (`wave_finish`'s
+    `lengths`, never needed on the host), or None: `max_len`; `taps`: fp32 device table of `infer.resample_taps(24000, sample_rate)`, not
+    needed at 24 000.  Returns (data uint8 device, out_len int32 device [n], offsets): request i's result is
+    data[offsets[i] : offsets[i] + out_len[i] * bytes_per_sample] -- little-endian int16 samples, or one code byte per sample --, bit for bit
+    `infer.deliver_pcm16` of its PCM."""
+    tensors = [pcm] if torch.is_tensor(pcm) else list(pcm)
+    io = np.ascontiguousarray(np.asarray(in_off, dtype=np.int64))
+    ml = np.ascontiguousarray(np.asarray(max_len, dtype=np.int32))
+    n = len(ml)
+    code = WAVE_ENCODINGS.index(encoding) if encoding in WAVE_ENCODINGS else encoding
+    if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or not 0 <= int(code) <= 2:
+        raise _lib.F5HipError(f"wave_encode: unknown encoding {encoding!r} (one of {list(WAVE_ENCODINGS)} or its code)")
+    code, rate = int(code), int(sample_rate)
+    if n < 1 or len(io) != n or len(tensors) not in (1, n):
+        raise _lib.F5HipError("wave_encode: one offset and one length bound per request; pcm is one tensor or one per request")
+    for t in tensors:
+        if not (torch.is_tensor(t) and t.dtype == torch.int16 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.device == tensors[0].device):
+            raise _lib.F5HipError("wave_encode: pcm must be contiguous 1-D int16 tensors on one device")
+    if len_dev is not None and not (torch.is_tensor(len_dev) and len_dev.dtype == torch.int32 and len_dev.is_cuda and len_dev.numel() == n
+                                    and len_dev.device == tensors[0].device):
+        raise _lib.F5HipError("wave_encode: len_dev must be an int32 tensor with one value per request on the pcm's device")
+    if rate < 1:
+        raise _lib.F5HipError(f"wave_encode: the sample rate must be positive (got {sample_rate})")
+    g = int(np.gcd(24000, rate))
+    of, nf = 24000 // g, rate // g
+    if rate != 24000:
+        width = int(np.ceil(6.0 * of / (min(of, nf) * 0.99)))
+        if taps is None or not (taps.dtype == torch.float32 and taps.is_contiguous() and taps.is_cuda) or tuple(taps.shape) != (nf, 2 * width + of):
+            raise _lib.F5HipError(f"wave_encode: taps must be a contiguous fp32 device tensor [{nf}, {2 * width + of}] for 24000 -> {rate} Hz "
+                                  f"(got {None if taps is None else tuple(taps.shape)})")
+    if len_dev is not None:
+        len_dev = len_dev.contiguous()
+    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
+        try:
+            data, out_len, out_off = torch_ops.ops().wave_encode(tensors, torch.from_numpy(io), torch.from_numpy(ml), len_dev, rate, code, taps)
+        except RuntimeError as e:   # c10::Error from the operator's checks or the library
+            raise _lib.F5HipError(str(e)) from e
+        return data, out_len, out_off.tolist()
+    bps = 2 if code == 0 else 1
+    anchor = next((t for t in tensors if t.numel()), None)   # offsets are relative to the first tensor that has an address
+    if anchor is None:
+        anchor = torch.zeros(8, device=tensors[0].device, dtype=torch.int16)
+    base = anchor.data_ptr()
+    rel, out_off, nbytes = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), 0
+    for i in range(n):
+        t = tensors[0 if len(tensors) == 1 else i]
+        if ml[i] < 0 or io[i] < 0 or int(io[i]) + int(ml[i]) > t.numel():
+            raise _lib.F5HipError(f"wave_encode: request {i} reads samples [{io[i]}, {int(io[i]) + int(ml[i])}) of a tensor of {t.numel()}")
+        rel[i] = (t.data_ptr() - base) // 2 + int(io[i]) if ml[i] else 0   # (an empty tensor has no address to speak of)
+        out_off[i] = nbytes
+        nbytes += (((nf * int(ml[i]) + of - 1) // of) * bps + 15) & ~15
+    dev = tensors[0].device
+    with torch.cuda.device(dev):
+        data = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)[:nbytes]   # (a call of empty requests still has an address to give)
+        out_len = torch.empty(n, device=dev, dtype=torch.int32)
+        _lib.check(_lib.lib().f5hip_wave_encode(n, C.c_void_p(base), _p(rel), _p(ml), _p(len_dev), rate, code, _p(taps) if rate != 24000 else None, _p(data),
+                                                _p(out_off), _p(out_len), _lib.current_stream_ptr()), "f5hip_wave_encode")
+    return data, out_len, out_off.tolist()

@@ -56,7 +56,8 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
     the routes return as 400.  `speed` finite and > 0; `nfe_step` an integer in 1..MAX_NFE_STEP[ode_method]; `cfg_strength` and
     `sway_sampling_coef` finite; `seed` an integer in 0..2**63 - 1; `ode_method` one of MAX_NFE_STEP's names.  `ode_method` (the argument)
     is the model's solver: `nfe_step`'s upper limit follows the request's own `ode_method` when it sets one, else the model's.
-    `remove_silence` a bool (False is dropped like None: the request is then what it is without the option)."""
+    `remove_silence` a bool (False is dropped like None: the request is then what it is without the option).  `sample_rate` an integer in
+    `infer.OUTPUT_SAMPLE_RATES`, `encoding` one of `infer.OUTPUT_ENCODINGS`; 24000 and "pcm16", what a request gets anyway, are dropped too."""
     out = {}
     own = options.get("ode_method") if "ode_method" in allowed else None
     if own is not None:
@@ -76,6 +77,17 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
             if not v:
                 continue
             v = True
+        elif k == "sample_rate":
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in infer.OUTPUT_SAMPLE_RATES:
+                raise ValueError(f"sample_rate must be one of {', '.join(str(r) for r in infer.OUTPUT_SAMPLE_RATES)} (got {v!r})")
+            if int(v) == infer.target_sample_rate:
+                continue
+            v = int(v)
+        elif k == "encoding":
+            if not isinstance(v, str) or v not in infer.OUTPUT_ENCODINGS:
+                raise ValueError(f"encoding must be one of {', '.join(repr(e) for e in infer.OUTPUT_ENCODINGS)} (got {v!r})")
+            if v == "pcm16":
+                continue
         elif k in ("nfe_step", "seed"):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"{k} must be an integer (got {v!r})")
@@ -560,14 +572,14 @@ class TTSManager:
                     self._clip_key_locks.pop(key, None)
 
     def synthesize_clip(self, text, ref_audio, ref_text, *, clip_short=True, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
-                        seed=None, ode_method=None, remove_silence=None):
+                        seed=None, ode_method=None, remove_silence=None, sample_rate=None, encoding=None):
         """`synthesize` with the caller's own reference clip instead of a registered voice: `ref_audio` is a WAV file's bytes or a
         (wave [ch, n], sr) pair, `ref_text` its transcript; `clip_short` as in `preprocess_ref_audio_text`.  The clip never touches the
         disk (`_clip_voice`); the request then takes the same batcher path as `synthesize`, with the same options."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                    ode_method=ode_method, remove_silence=remove_silence)
+                                    ode_method=ode_method, remove_silence=remove_silence, sample_rate=sample_rate, encoding=encoding)
         voice, ref_text_n = self._clip_voice(ref_audio, ref_text, clip_short)
         req = self._request(voice, ref_text_n, text, opts)
         if self.batcher is not None:
@@ -575,13 +587,13 @@ class TTSManager:
         return self._run_batch([req])[0]
 
     def synthesize_clip_stream(self, text, ref_audio, ref_text, *, clip_short=True, speed=None, nfe_step=None, cfg_strength=None,
-                               sway_sampling_coef=None, seed=None, ode_method=None, remove_silence=None):
-        """`synthesize_stream` with an uploaded reference clip (`synthesize_clip`): an iterator of float32 pieces whose concatenation is
-        `synthesize_clip`'s wave given the same noise."""
+                               sway_sampling_coef=None, seed=None, ode_method=None, remove_silence=None, sample_rate=None, encoding=None):
+        """`synthesize_stream` with an uploaded reference clip (`synthesize_clip`): an iterator of pieces (float32; in the delivery format
+        with `sample_rate` / `encoding`) whose concatenation is `synthesize_clip`'s wave given the same noise."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                    ode_method=ode_method, remove_silence=remove_silence)
+                                    ode_method=ode_method, remove_silence=remove_silence, sample_rate=sample_rate, encoding=encoding)
         if opts.get("remove_silence"):
             raise ValueError(STREAM_REMOVE_SILENCE)
         voice, ref_text_n = self._clip_voice(ref_audio, ref_text, clip_short)
@@ -591,21 +603,24 @@ class TTSManager:
         return self._stream(voice, ref_text_n, chunks[:1], chunks[1:], opts)
 
     def synthesize(self, text, ref_audio_path, ref_text, *, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None, seed=None,
-                   ode_method=None, remove_silence=None):
+                   ode_method=None, remove_silence=None, sample_rate=None, encoding=None):
         """The wave of one request.  The sampler options are this request's own (None: `self.opts`); `seed` draws its noise from its own
         generator (`infer.request_generator`), so the same seeded request gives the same audio whatever it is batched with (shape-invariant
         attention, one GPU).  `ode_method` ("euler", "midpoint", "rk4"; None: the model's): requests of different solvers share a batch, and
         the option reaches the model object only for a request that sets it.  `remove_silence=True`: the reference's
         `remove_silence_for_generated_wav` -- pauses of 1 s or more shrink to 500 ms on each side -- and the result is int16 PCM
-        (`audio_prep.remove_silence_pcm` of the quantised wave); with `device_backend` every result is int16 PCM."""
+        (`audio_prep.remove_silence_pcm` of the quantised wave); with `device_backend` every result is int16 PCM.  `sample_rate` (one of
+        `infer.OUTPUT_SAMPLE_RATES`) and `encoding` ("pcm16", "mulaw", "alaw"): the delivery format, `infer.deliver_pcm16` of the request's
+        24 kHz int16 PCM -- int16 at that rate, or uint8 G.711 code bytes -- computed on the device with `device_backend`, the same bytes
+        either way; 24000 and "pcm16" (or None) change nothing."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                    ode_method=ode_method, remove_silence=remove_silence)
+                                    ode_method=ode_method, remove_silence=remove_silence, sample_rate=sample_rate, encoding=encoding)
         return self.model(text, ref_audio_path=ref_audio_path, ref_text=ref_text, **opts)
 
     def synthesize_stream(self, text, ref_audio_path, ref_text, *, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
-                          seed=None, ode_method=None, remove_silence=None):
+                          seed=None, ode_method=None, remove_silence=None, sample_rate=None, encoding=None):
         """`synthesize` as an iterator of float32 pieces (24 kHz) whose concatenation is `synthesize`'s wave given the same noise (see
         `infer.infer_process_stream`).  The request's first chunk is synthesized on its own and its stable samples come out as soon as it is
         done; the remaining chunks follow as a second request.  With a micro-batcher the first chunk rides in the next batch and the
@@ -613,11 +628,14 @@ class TTSManager:
         each under the device lock (released in between).  Closing the iterator early (client disconnect) cancels the remaining chunks
         if their batch has not started.  Errors about the model or the voice are raised here, not on the first `next()`.  Options as in
         `synthesize`; with a `seed`, the first chunk and the remaining chunks draw from the request's one generator in chunk order, so the
-        pieces equal `synthesize`'s wave with that seed.  The remaining chunks keep the first chunk's `ode_method`."""
+        pieces equal `synthesize`'s wave with that seed.  The remaining chunks keep the first chunk's `ode_method`.  With `sample_rate` /
+        `encoding` the pieces come in the delivery format (int16 at that rate, or uint8 code bytes): each float32 piece goes through
+        `infer.quantise_pcm16`, an `infer.StreamResampler` and the encoder on the host, and their concatenation equals `synthesize`'s result
+        with the same options byte for byte."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                    ode_method=ode_method, remove_silence=remove_silence)
+                                    ode_method=ode_method, remove_silence=remove_silence, sample_rate=sample_rate, encoding=encoding)
         if opts.get("remove_silence"):   # removal needs the whole wave
             raise ValueError(STREAM_REMOVE_SILENCE)
         voice, ref_text_n = self._voice(ref_audio_path, ref_text)
@@ -629,6 +647,8 @@ class TTSManager:
     def _stream(self, voice, ref_text, head, tail, opts=None):
         lock, state = threading.Lock(), {"closed": False, "tail": None, "error": None}
         started = threading.Event()
+        opts = dict(opts or {})               # the delivery format is applied here, piece by piece: the head and tail requests stay plain
+        fmt = infer.delivery_format(opts.pop("sample_rate", None), opts.pop("encoding", None))
 
         def submit_tail():                        # on the batcher's thread, once the head's batch has formed
             with lock:
@@ -669,18 +689,35 @@ class TTSManager:
             finally:                              # normal end, error, or the consumer closed the stream
                 cancel()
 
-        return SynthesisStream(pieces(), cancel)
+        def delivered():
+            resampler = infer.StreamResampler(fmt[0])
+            encode = (lambda pcm: pcm) if fmt[1] == "pcm16" else (lambda pcm: infer.encode_g711(pcm, fmt[1]))
+            gen = pieces()
+            try:
+                for piece in gen:
+                    out = resampler.feed(infer.quantise_pcm16(piece))
+                    if len(out):
+                        yield encode(out)
+                out = resampler.flush()
+                if len(out):
+                    yield encode(out)
+            finally:
+                gen.close()
+
+        return SynthesisStream(pieces() if fmt == (infer.target_sample_rate, "pcm16") else delivered(), cancel)
 
     def edit(self, audio, target_text, parts_to_edit, fix_duration=None, *, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
-             seed=None, ode_method=None):
+             seed=None, ode_method=None, sample_rate=None, encoding=None):
         """Speech editing (`infer.speech_edit`, F/infer/speech_edit.py): regenerate `parts_to_edit` of the recording `audio` (a path, WAV
         bytes or a (tensor, sr) pair) so that it speaks `target_text`, with this manager's sampler settings unless the call sets its own
         (`seed`: the edit's noise from its own generator; `ode_method`: the edit's solver, handed on only when set).  The host preparation runs outside the device lock, the sampler and vocoder
-        under it (not through the micro-batcher); with a `ShardedSampler` on rank 0's own model.  Returns the wave (float32, 24 kHz)."""
+        under it (not through the micro-batcher); with a `ShardedSampler` on rank 0's own model.  Returns the wave (float32, 24 kHz) -- with
+        `sample_rate` / `encoding`, `infer.deliver_pcm16` of its int16 PCM (host functions)."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = dict(self.opts, **self.request_options(EDIT_OPTIONS, nfe_step=nfe_step, cfg_strength=cfg_strength,
                                                       sway_sampling_coef=sway_sampling_coef, seed=seed, ode_method=ode_method))
+        fmt = self.request_options(("sample_rate", "encoding"), sample_rate=sample_rate, encoding=encoding)
         model_obj = getattr(self.model_obj, "local", self.model_obj)
         # host work (read, mono mix, resample, plan, tokens) and every rejection happen before the device lock is taken
         prep = infer.prepare_edit(audio, target_text, parts_to_edit, fix_duration, mel_spec_type=self.mel_spec_type)
@@ -691,17 +728,46 @@ class TTSManager:
             (wave, _, _), = infer.speech_edit_batch([prep], model_obj, self.vocoder, mel_spec_type=self.mel_spec_type,
                                                     nfe_step=opts["nfe_step"], cfg_strength=opts["cfg_strength"],
                                                     sway_sampling_coef=opts["sway_sampling_coef"], **extra)
-        return np.asarray(wave, dtype=np.float32)
+        wave = np.asarray(wave, dtype=np.float32)
+        return infer.deliver_pcm16(infer.quantise_pcm16(wave), fmt.get("sample_rate"), fmt.get("encoding")) if fmt else wave
 
 
-def wav_bytes(audio: np.ndarray, sample_rate: int = infer.target_sample_rate) -> io.BytesIO:
+_G711_TAGS = {"mulaw": 7, "alaw": 6}   # WAVE_FORMAT_MULAW, WAVE_FORMAT_ALAW
+
+
+def _g711_header(encoding, sample_rate, n, riff_size, data_size):
+    """RIFF header of a mono G.711 WAV: an 18-byte `fmt ` chunk (format tag 7 / 6, 8 bits per sample, block align 1, byte rate = sample rate,
+    cbSize 0), a `fact` chunk with the sample count, and the `data` chunk's header."""
+    return (b"RIFF" + struct.pack("<I", riff_size) + b"WAVE" + b"fmt " + struct.pack("<IHHIIHHH", 18, _G711_TAGS[encoding], 1, sample_rate, sample_rate, 1, 8, 0)
+            + b"fact" + struct.pack("<II", 4, n) + b"data" + struct.pack("<I", data_size))
+
+
+def delivery_bytes(audio, encoding: str = "pcm16") -> bytes:
+    """The body bytes of samples in any of the forms a request's result takes: uint8 G.711 codes as they are, int16 PCM little-endian, float
+    samples by `pcm16`'s rule -- and, for a G.711 `encoding`, PCM that is not encoded yet through `infer.encode_g711`."""
     a = np.asarray(audio)
+    if a.dtype == np.uint8:
+        return a.tobytes()
     if a.dtype != np.int16:
         a = infer.quantise_pcm16(a)
+    if encoding != "pcm16":
+        return infer.encode_g711(a, encoding).tobytes()
+    return a.astype("<i2").tobytes()
+
+
+def wav_bytes(audio: np.ndarray, sample_rate: int = infer.target_sample_rate, encoding: str = "pcm16") -> io.BytesIO:
+    """A mono WAV file of `audio` (`delivery_bytes`) at `sample_rate`: 16-bit PCM, or G.711 (`_g711_header`) for "mulaw" / "alaw"."""
+    if encoding not in infer.OUTPUT_ENCODINGS:
+        raise ValueError(f"encoding must be one of {list(infer.OUTPUT_ENCODINGS)} (got {encoding!r})")
+    body = delivery_bytes(audio, encoding)
     buf = io.BytesIO()
-    with _wave.open(buf, "wb") as f:
-        f.setnchannels(1); f.setsampwidth(2); f.setframerate(sample_rate)
-        f.writeframes(a.astype("<i2").tobytes())
+    if encoding == "pcm16":
+        with _wave.open(buf, "wb") as f:
+            f.setnchannels(1); f.setsampwidth(2); f.setframerate(sample_rate)
+            f.writeframes(body)
+    else:
+        pad = len(body) & 1                      # chunks are word-aligned
+        buf.write(_g711_header(encoding, sample_rate, len(body), 4 + 26 + 12 + 8 + len(body) + pad, len(body)) + body + b"\x00" * pad)
     buf.seek(0)
     return buf
 
@@ -711,9 +777,11 @@ def pcm16(audio: np.ndarray) -> bytes:
     return infer.quantise_pcm16(audio).astype("<i2").tobytes()
 
 
-def wav_stream_header(sample_rate: int = infer.target_sample_rate) -> bytes:
-    """44-byte header of a 16-bit mono PCM WAV of unknown length: RIFF and `data` sizes are 0xFFFFFFFF (the usual streaming-WAV
-    convention; players read to the end of the stream)."""
+def wav_stream_header(sample_rate: int = infer.target_sample_rate, encoding: str = "pcm16") -> bytes:
+    """Header of a mono WAV of unknown length: RIFF and `data` sizes are 0xFFFFFFFF (the usual streaming-WAV convention; players read to the
+    end of the stream).  16-bit PCM: 44 bytes; G.711: 58 bytes, the `fact` chunk's sample count 0xFFFFFFFF too."""
+    if encoding != "pcm16":
+        return _g711_header(encoding, sample_rate, 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF)
     return (b"RIFF" + struct.pack("<I", 0xFFFFFFFF) + b"WAVE" + b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, sample_rate, sample_rate * 2, 2, 16)
             + b"data" + struct.pack("<I", 0xFFFFFFFF))
 
@@ -741,11 +809,31 @@ def _checked_voice(registry: VoiceRegistry, text: str, ref_audio_name: str, ref_
     return voice, ref_text
 
 
-def synthesize_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None, **options):
-    """`S/utils/tts_utils.py:38-65` with the same checks in the same order and the same messages; `options` go to `TTSManager.synthesize`."""
+RESPONSE_FORMATS = {"wav": "audio/wav", "pcm": "audio/pcm"}   # response_format -> media type; "pcm": headerless samples / code bytes
+
+
+def check_response_format(response_format) -> str:
+    """"wav" (None: the default) or "pcm"; anything else is a ValueError the routes return as 400."""
+    fmt = "wav" if response_format is None else response_format
+    if not isinstance(fmt, str) or fmt not in RESPONSE_FORMATS:
+        raise ValueError(f"response_format must be one of {', '.join(repr(f) for f in RESPONSE_FORMATS)} (got {response_format!r})")
+    return fmt
+
+
+def response_body(audio, options: dict, response_format: str = "wav") -> io.BytesIO:
+    """The response body of a request's result in the delivery format its `options` name: a WAV file (`wav_bytes`), or with "pcm" the
+    headerless little-endian samples / code bytes."""
+    rate, enc = infer.delivery_format(options.get("sample_rate"), options.get("encoding"))
+    return io.BytesIO(delivery_bytes(audio, enc)) if response_format == "pcm" else wav_bytes(audio, rate, enc)
+
+
+def synthesize_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None,
+                      response_format: str = "wav", **options):
+    """`S/utils/tts_utils.py:38-65` with the same checks in the same order and the same messages; `options` go to `TTSManager.synthesize`,
+    and the body comes in the delivery format they name (`response_body`)."""
     voice, ref_text = _checked_voice(registry, text, ref_audio_name, ref_text)
     audio = tts_manager.synthesize(text, ref_audio_path=voice.audio_path, ref_text=ref_text, **options)
-    return wav_bytes(audio)
+    return response_body(audio, options, response_format)
 
 
 def stream_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None, **options):
@@ -763,7 +851,9 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     `sway_sampling_coef`, `seed`, `ode_method` ("euler", "midpoint" or "rk4": the request's ODE solver) and (speech routes) `speed` and
     `remove_silence` (true: pauses of 1 s or more are cut down to 500 ms on each side; 400 together with `"stream": true`), checked
     before anything is queued (400 with `check_request_options`'s message); an omitted field is the manager's setting (`ode_method`: the
-    model's).  With a `seed`, the same request returns the same audio."""
+    model's).  With a `seed`, the same request returns the same audio.  The delivery format, on every route: `sample_rate` (one of
+    `infer.OUTPUT_SAMPLE_RATES`), `encoding` ("pcm16", "mulaw" or "alaw": G.711, one byte per sample) and `response_format` ("wav", or "pcm"
+    for the headerless samples / code bytes as `audio/pcm`); streamed or not, the body's samples are the same bytes."""
     from fastapi import APIRouter, FastAPI, HTTPException
     from pydantic import BaseModel
     from starlette.responses import StreamingResponse
@@ -774,6 +864,9 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         sway_sampling_coef: float | None = None
         seed: int | None = None
         ode_method: str | None = None
+        sample_rate: int | None = None               # the delivery format (infer.deliver_pcm16); None = 24 kHz 16-bit PCM in a WAV
+        encoding: str | None = None
+        response_format: str | None = None
 
     class KannadaSynthesizeRequest(SamplerFields):   # S/utils/tts_utils.py:27-28
         text: str
@@ -811,6 +904,24 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
 
+    def _response_format(req):
+        try:
+            return check_response_format(req.response_format)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+
+    def _blocks(buf, size=1 << 16):
+        """The body in 64 KiB blocks.  (Iterating the BytesIO itself yields "lines": a body is cut at every 0x0A byte, which G.711 code bytes
+        are full of, and every piece costs a hop through the thread pool.)"""
+        while True:
+            block = buf.read(size)
+            if not block:
+                return
+            yield block
+
+    def _headers(filename, fmt):
+        return {"Content-Disposition": f"attachment; filename={filename if fmt == 'wav' else filename.rsplit('.', 1)[0] + '.pcm'}"}
+
     router = APIRouter(prefix="/v1", tags=["speech"])
 
     def _speech_options(text, req):
@@ -825,38 +936,39 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         return opts
 
     def _run(text, name, ref_text, filename, req):
-        opts = _speech_options(text, req)
+        opts, fmt = _speech_options(text, req), _response_format(req)
         try:
-            buf = synthesize_speech(tts_manager, registry, text=text, ref_audio_name=name, ref_text=ref_text, **opts)
+            buf = synthesize_speech(tts_manager, registry, text=text, ref_audio_name=name, ref_text=ref_text, response_format=fmt, **opts)
         except HTTPError as e:
             raise HTTPException(status_code=e.status_code, detail=e.detail)
-        return StreamingResponse(buf, media_type="audio/wav", headers={"Content-Disposition": f"attachment; filename={filename}"})
+        return StreamingResponse(_blocks(buf), media_type=RESPONSE_FORMATS[fmt], headers=_headers(filename, fmt))
 
     def _run_stream(text, name, ref_text, filename, req):
         """stream=true: the same checks as `_run`, then the first piece is synthesized BEFORE the response exists, so a bad request, an
         unloaded model or a failing first chunk still comes back as a status code.  The body is a streaming WAV (`wav_stream_header`)
-        followed by int16 PCM pieces; a failure after the first bytes can only end the body early, and is logged."""
-        opts = _speech_options(text, req)
+        followed by the pieces in the delivery format (int16 PCM, or G.711 code bytes; no header with response_format "pcm"); a failure after the first bytes can only end the body early, and is logged."""
+        opts, fmt = _speech_options(text, req), _response_format(req)
         try:
             pieces = stream_speech(tts_manager, registry, text=text, ref_audio_name=name, ref_text=ref_text, **opts)
             first = next(pieces, None)
         except HTTPError as e:
             raise HTTPException(status_code=e.status_code, detail=e.detail)
-        return StreamingResponse(_pcm_body(first, pieces), media_type="audio/wav",
-                                 headers={"Content-Disposition": f"attachment; filename={filename}"})
+        return StreamingResponse(_pcm_body(first, pieces, opts, fmt), media_type=RESPONSE_FORMATS[fmt], headers=_headers(filename, fmt))
 
-    async def _pcm_body(first, pieces):
+    async def _pcm_body(first, pieces, opts, fmt):
         # the synthesis runs in the thread pool, one piece at a time; leaving early (client gone, error) closes the generator,
         # which cancels the request's remaining chunks if their batch has not started
         try:
-            yield wav_stream_header()
+            rate, enc = infer.delivery_format(opts.get("sample_rate"), opts.get("encoding"))
+            if fmt == "wav":
+                yield wav_stream_header(rate, enc)
             if first is not None:
-                yield pcm16(first)
+                yield delivery_bytes(first, enc)
             while True:
                 piece = await run_in_threadpool(next, pieces, None)
                 if piece is None:
                     break
-                yield pcm16(piece)
+                yield delivery_bytes(piece, enc)
         except Exception:   # noqa: BLE001 -- the status line is gone: end the body early
             log.exception("streamed synthesis failed after the first bytes; the response body ends early")
         finally:
@@ -865,26 +977,26 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     def _run_clone(req):
         """`/v1/audio/speech/clone`: the speech routes' checks, then the clip's (`TTSManager._clip_voice`: 400 with its message), then
         `synthesize_clip` -- or, with stream=true, `synthesize_clip_stream` with the first piece synthesized before the response exists."""
-        opts = _speech_options(req.text, req)
+        opts, fmt = _speech_options(req.text, req), _response_format(req)
         try:
             raw = base64.b64decode(req.ref_audio, validate=True)
         except (binascii.Error, ValueError):
             raise HTTPException(status_code=400, detail="Audio must be a base64-encoded WAV file.")
-        headers = {"Content-Disposition": "attachment; filename=synthesized_speech.wav"}
+        headers = _headers("synthesized_speech.wav", fmt)
         try:
             if req.stream:
                 pieces = tts_manager.synthesize_clip_stream(req.text, raw, req.ref_text, clip_short=req.clip_short, **opts)
                 first = next(pieces, None)
-                return StreamingResponse(_pcm_body(first, pieces), media_type="audio/wav", headers=headers)
+                return StreamingResponse(_pcm_body(first, pieces, opts, fmt), media_type=RESPONSE_FORMATS[fmt], headers=headers)
             wave = tts_manager.synthesize_clip(req.text, raw, req.ref_text, clip_short=req.clip_short, **opts)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
-        return StreamingResponse(wav_bytes(wave), media_type="audio/wav", headers=headers)
+        return StreamingResponse(_blocks(response_body(wave, opts, fmt)), media_type=RESPONSE_FORMATS[fmt], headers=headers)
 
     def _run_edit(req):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
-        opts = _options(req, EDIT_OPTIONS)
+        opts, fmt = _options(req, EDIT_OPTIONS + ("sample_rate", "encoding")), _response_format(req)
         try:
             raw = base64.b64decode(req.audio, validate=True)
         except (binascii.Error, ValueError):
@@ -899,8 +1011,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
             wave = tts_manager.edit(audio, req.text, req.parts_to_edit, req.fix_duration, **opts)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
-        return StreamingResponse(wav_bytes(wave), media_type="audio/wav",
-                                 headers={"Content-Disposition": "attachment; filename=edited_speech.wav"})
+        return StreamingResponse(_blocks(response_body(wave, opts, fmt)), media_type=RESPONSE_FORMATS[fmt], headers=_headers("edited_speech.wav", fmt))
 
     # The reference's handlers are `async def` around a blocking call, i.e. one request at a time.  Here the blocking part runs in
     # starlette's thread pool, so concurrent requests overlap and meet in the MicroBatcher queue (when the manager has one).
