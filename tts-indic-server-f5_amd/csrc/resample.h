@@ -11,6 +11,7 @@
 // A clip's bits depend on nothing but the clip: no atomics, every reduction tree is a function of the clip's length, and the zero padding
 // is an index predicate against the clip's own [0, n_in) (never a read of the neighbour in the packed buffer).
 #pragma once
+#include "ragged_util.h"
 
 struct RefClip {
     long long in_off;   // first float of the clip in wave_dev (channel c at in_off + c * n_in)
@@ -24,7 +25,6 @@ constexpr int kRefChunk = 4096;               // samples per partial (16 per thr
 constexpr int kRefTileOutputs = 2048;         // outputs a resample block aims for ...
 constexpr int kRefTileOutputsMax = 8192;      // ... or, with the table in LDS, half as many as the table has taps, up to this: every block copies the
                                               // whole table (zeros included), so a block that stages 26 K taps for 2 K outputs moves mostly table
-constexpr int kRefLdsMax = 160 * 1024;        // LDS of one CU
 constexpr int kRefRedBytes = 256 * 8;         // the fp64 reduction scratch in front of the dynamic LDS
 
 // mono sample i of a clip: the mean over its channel planes, summed in fp64 in channel order and rounded to fp32 once (one channel: the
@@ -34,31 +34,6 @@ F5_DEVICE float ref_mono(const float* __restrict__ x, int n_in, int ch, int i) {
     double s = (double)x[i];
     for (int c = 1; c < ch; c++) s += (double)x[(size_t)c * n_in + i];
     return (float)(s / (double)ch);
-}
-
-// sum of red[0 .. 256) by a fixed binary tree; every thread returns the total
-F5_DEVICE double ref_block_sum(double* red, int tid, double v) {
-    red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double total = red[0];
-    __syncthreads();
-    return total;
-}
-
-// last clip whose first block (member `first`) is at or before b
-template <int RefClip::*first>
-F5_DEVICE int ref_find_clip(const RefClip* clips, int n, int b) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (clips[mid].*first <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
 }
 
 __global__ __launch_bounds__(256) void ref_reduce_kernel(const RefClip* __restrict__ clips, int n, int total_parts, const float* __restrict__ wave,
@@ -76,7 +51,7 @@ __global__ __launch_bounds__(256) void ref_reduce_kernel(const RefClip* __restri
         range[p] = last ? make_int2(first, last) : make_int2(0, 0);
         return;
     }
-    const RefClip c = clips[ref_find_clip<&RefClip::part0>(clips, n, b)];
+    const RefClip c = clips[last_at_or_before<&RefClip::part0>(clips, n, b)];
     const float* x = wave + c.in_off;
     const long long i0 = (long long)(b - c.part0) * kRefChunk;   // (64-bit: the last chunk of a clip near 2^31 samples ends past INT_MAX)
     double acc = 0.0;
@@ -88,19 +63,8 @@ __global__ __launch_bounds__(256) void ref_reduce_kernel(const RefClip* __restri
             acc += m * m;
         }
     }
-    const double total = ref_block_sum(red, tid, acc);
+    const double total = block_sum(red, tid, acc);
     if (tid == 0) partials[b] = total;
-}
-
-// the tap table (nt floats) into LDS at tp (16-byte aligned) by a block of 256 threads: 16-byte loads where the table's address allows
-F5_DEVICE void ref_stage_taps(float* tp, const float* __restrict__ taps, int nt, int tid) {
-    if ((reinterpret_cast<uintptr_t>(taps) & 15) == 0) {
-        const float4* t4 = reinterpret_cast<const float4*>(taps);
-        for (int i = tid; i < nt / 4; i += 256) reinterpret_cast<float4*>(tp)[i] = t4[i];
-        for (int i = (nt & ~3) + tid; i < nt; i += 256) tp[i] = taps[i];
-    } else {
-        for (int i = tid; i < nt; i += 256) tp[i] = taps[i];
-    }
 }
 
 // MODE 0: tap table staged in LDS; 1: tap table read through L2; 2: orig_freq == new_freq (no taps: out = the gained mono clip)
@@ -113,7 +77,7 @@ __global__ __launch_bounds__(256) void ref_resample_kernel(const RefClip* __rest
     double* red = reinterpret_cast<double*>(ref_sm);
     float* xs = reinterpret_cast<float*>(ref_sm + kRefRedBytes);
     const int tid = threadIdx.x;
-    const int ci = ref_find_clip<&RefClip::tile0>(clips, n, blockIdx.x);
+    const int ci = last_at_or_before<&RefClip::tile0>(clips, n, (int)blockIdx.x);
     const RefClip c = clips[ci];
     const int tile = blockIdx.x - c.tile0;
     const int nx = tq * of + 2 * width;            // the window of xpad this tile reads: xpad[q0 * of .. q0 * of + nx)
@@ -122,7 +86,7 @@ __global__ __launch_bounds__(256) void ref_resample_kernel(const RefClip* __rest
     // the clip's rms: its partials in slot order, thread t taking slots t, t + 256, ..., then the fixed tree
     double acc = 0.0;
     for (int i = tid; i < c.nparts; i += 256) acc += partials[c.part0 + i];
-    const double sumsq = ref_block_sum(red, tid, acc);
+    const double sumsq = block_sum(red, tid, acc);
     const float rms = (float)sqrt(sumsq / (double)c.n_in);
     if (tile == 0 && tid == 0) rms_out[ci] = rms;
     const bool gain = rms < rms_floor;
@@ -139,7 +103,7 @@ __global__ __launch_bounds__(256) void ref_resample_kernel(const RefClip* __rest
         }
         xs[i] = v;
     }
-    if (MODE == 0) ref_stage_taps(tp, taps, nf * L, tid);
+    if (MODE == 0) stage_taps(tp, taps, nf * L, tid);
     __syncthreads();
 
     const int n_local = tq * nf;
@@ -166,44 +130,20 @@ struct RefWorkspace {
     double* partials = nullptr; size_t cap_parts = 0;
     int2* range = nullptr; size_t cap_range = 0;
 };
-static RefWorkspace g_ref_ws[32];   // one per device ordinal
-
-template <typename T>
-static int ref_reserve(T** p, size_t* cap, size_t need, const char* what) {
-    if (need <= *cap) return 0;
-    dev_free(*p);
-    *p = nullptr; *cap = 0;
-    if (hipMalloc((void**)p, sizeof(T) * need) != hipSuccess) { *p = nullptr; return fail(-5, "hipMalloc %s", what); }
-    *cap = need;
-    return 0;
-}
-
-static int ref_gcd(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
-
-// The reduced rate pair of : nf of a resampling and the shape of its tap table (infer.resample_taps): rows of L = 2 width + of taps.
-// Equal rates: 1 : 1 and no table.
-struct RefRatePair { int of, nf, width, L; };
-static RefRatePair ref_rate_pair(int orig_freq, int new_freq) {
-    if (orig_freq == new_freq) return RefRatePair{1, 1, 0, 0};
-    const int g = ref_gcd(orig_freq, new_freq), of = orig_freq / g, nf = new_freq / g;
-    const int width = (int)ceil(6.0 * of / (std::min(of, nf) * 0.99));   // torchaudio: lowpass_filter_width 6, rolloff 0.99
-    return RefRatePair{of, nf, width, 2 * width + of};
-}
-
 int f5hip_ref_frontend(int32_t n, const int32_t* n_in, const int32_t* channels, const float* wave_dev, int32_t orig_freq, int32_t new_freq,
                        const float* taps_dev, float rms_floor, float* out_dev, float* rms_dev, void* stream) {
     if (n < 1 || !n_in || !channels || !wave_dev || !out_dev || !rms_dev) return fail(-1, "ref_frontend: bad argument");
     if (orig_freq < 1 || new_freq < 1) return fail(-1, "ref_frontend: sample rates must be positive (%d -> %d)", orig_freq, new_freq);
     const bool identity = orig_freq == new_freq;
     if (!identity && !taps_dev) return fail(-1, "ref_frontend: %d -> %d Hz needs the tap table", orig_freq, new_freq);
-    const RefRatePair rp = ref_rate_pair(orig_freq, new_freq);
+    const RatePair rp = rate_pair(orig_freq, new_freq);
     const int of = rp.of, nf = rp.nf, width = rp.width, L = rp.L;
     // Tile: a block owns tq polyphase blocks.  With the table in LDS the tile grows with the table (2 staged taps per output at most), while
     // window + table fit the CU's LDS; else the small tile, with the table in LDS if that fits, else read through L2.  An output's bits do
     // not depend on the tile: one thread adds its terms in k order whatever block it runs in.
     const long long table = (long long)nf * L;
     auto window = [&](int q) { return (((long long)q * of + 2 * width) + 3) & ~3LL; };
-    auto fits = [&](int q, bool with_table) { return kRefRedBytes + 4 * (window(q) + (with_table ? table : 0)) <= kRefLdsMax; };
+    auto fits = [&](int q, bool with_table) { return kRefRedBytes + 4 * (window(q) + (with_table ? table : 0)) <= kLdsMax; };
     int tq = std::max(1, kRefTileOutputs / nf);
     if (table > (1LL << 28) || !fits(tq, false)) return fail(-1, "ref_frontend: %d -> %d Hz is not supported (%d : %d)", orig_freq, new_freq, of, nf);
     bool taps_lds = !identity && fits(tq, true);
@@ -229,14 +169,14 @@ int f5hip_ref_frontend(int32_t n, const int32_t* n_in, const int32_t* channels, 
     }
     const int range_blocks = identity ? 0 : (nf + 255) / 256;
     if (parts + range_blocks > 2147483647LL || tiles > 2147483647LL) return fail(-1, "ref_frontend: call too large");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(-6, "ref_frontend: hipGetDevice");
-    RefWorkspace& ws = g_ref_ws[dev & 31];
-    CK(ref_reserve(&ws.clips, &ws.cap_clips, (size_t)n, "ref_frontend clips"));
-    CK(ref_reserve(&ws.partials, &ws.cap_parts, (size_t)parts, "ref_frontend partials"));
-    CK(ref_reserve(&ws.range, &ws.cap_range, (size_t)nf, "ref_frontend tap ranges"));
+    RefWorkspace* const wsp = device_workspace<RefWorkspace>("ref_frontend");
+    if (!wsp) return -6;
+    RefWorkspace& ws = *wsp;
+    CK(dev_reserve(&ws.clips, &ws.cap_clips, (size_t)n, "ref_frontend clips"));
+    CK(dev_reserve(&ws.partials, &ws.cap_parts, (size_t)parts, "ref_frontend partials"));
+    CK(dev_reserve(&ws.range, &ws.cap_range, (size_t)nf, "ref_frontend tap ranges"));
     static unsigned lds_attr_done = 0;
-    if (taps_lds && lds > 64 * 1024 && f5_set_lds_attr((const void*)ref_resample_kernel<0>, kRefLdsMax, lds_attr_done) != hipSuccess)
+    if (taps_lds && lds > 64 * 1024 && f5_set_lds_attr((const void*)ref_resample_kernel<0>, kLdsMax, lds_attr_done) != hipSuccess)
         return fail(-7, "ref_frontend: LDS opt-in");
     hipStream_t st = (hipStream_t)stream;
     if (upload_sync(st, ws.clips, h) != hipSuccess) return fail(-6, "ref_frontend metadata upload");

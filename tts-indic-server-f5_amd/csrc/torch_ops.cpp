@@ -18,13 +18,13 @@
 #include <torch/library.h>
 
 #include <cmath>
-#include <numeric>
 #include <tuple>
 #include <vector>
 
 //   torch.ops.f5hip.wave_finish(chunks[], chunks_per_request, fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/utils_infer.py:485-519,530-539
 //   torch.ops.f5hip.wave_encode(pcm[], in_off, max_len, len_dev?, new_freq, encoding, taps?) -> (Tensor bytes uint8, Tensor lengths int32, Tensor offsets int64 host)
 #include "../../include/f5hip.h"
+#include "rate_pair.h"
 
 namespace {
 
@@ -214,7 +214,8 @@ std::tuple<at::Tensor, at::Tensor> ref_frontend(const at::Tensor& wave, const at
     TORCH_CHECK(n_in.dim() == 1 && n_in.numel() > 0 && channels.numel() == n_in.numel(), "f5hip::ref_frontend: n_in and channels need one value per clip");
     TORCH_CHECK(orig_freq >= 1 && new_freq >= 1 && orig_freq <= INT32_MAX && new_freq <= INT32_MAX, "f5hip::ref_frontend: sample rates");
     if (taps.has_value()) check_dev_f32(*taps, "taps");
-    const int64_t g = std::gcd(orig_freq, new_freq), of = orig_freq / g, nf = new_freq / g;
+    const RatePair rp = rate_pair((int)orig_freq, (int)new_freq);
+    const int64_t of = rp.of, nf = rp.nf;
     const int32_t *ni = n_in.data_ptr<int32_t>(), *ch = channels.data_ptr<int32_t>();
     int64_t total_in = 0, total_out = 0;
     for (int64_t i = 0; i < n_in.numel(); i++) {
@@ -226,11 +227,9 @@ std::tuple<at::Tensor, at::Tensor> ref_frontend(const at::Tensor& wave, const at
     TORCH_CHECK(total_out <= INT32_MAX, "f5hip::ref_frontend: the outputs of the call exceed 2^31 - 1 samples");
     if (orig_freq != new_freq) {
         TORCH_CHECK(taps.has_value(), "f5hip::ref_frontend: ", orig_freq, " -> ", new_freq, " Hz needs the tap table");
-        // the library derives the row length itself (torchaudio's lowpass_filter_width 6, rolloff 0.99): a table of any other shape would be
-        // read with the wrong stride
-        const int64_t width = (int64_t)std::ceil(6.0 * (double)of / ((double)std::min(of, nf) * 0.99));
-        TORCH_CHECK(taps->dim() == 2 && taps->size(0) == nf && taps->size(1) == 2 * width + of, "f5hip::ref_frontend: taps must be [nf = ", nf,
-                    "][2 * width + of = ", 2 * width + of, "] (lowpass_filter_width 6, rolloff 0.99); got ", taps->sizes());
+        // the library derives the row length itself (rate_pair.h): a table of any other shape would be read with the wrong stride
+        TORCH_CHECK(taps->dim() == 2 && taps->size(0) == nf && taps->size(1) == rp.L, "f5hip::ref_frontend: taps must be [nf = ", nf,
+                    "][2 * width + of = ", rp.L, "] (rate_pair.h: torchaudio's defaults); got ", taps->sizes());
     }
     const c10::DeviceGuard guard(wave.device());   // allocations and stream on the wave's device
     at::Tensor out = at::empty({total_out}, wave.options()), rms = at::empty({n_in.numel()}, wave.options());
@@ -296,13 +295,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_encode(at::TensorList pcm, c
     TORCH_CHECK((int64_t)pcm.size() == 1 || (int64_t)pcm.size() == n, "f5hip::wave_encode: pcm is one tensor or one per request (got ", pcm.size(), " for ", n, ")");
     TORCH_CHECK(encoding >= 0 && encoding <= 2, "f5hip::wave_encode: unknown encoding ", encoding, " (0 pcm16, 1 mu-law, 2 A-law)");
     TORCH_CHECK(new_freq >= 1 && new_freq <= INT32_MAX, "f5hip::wave_encode: the sample rate must be positive (got ", new_freq, ")");
-    const int64_t g = std::gcd((int64_t)24000, new_freq), of = 24000 / g, nf = new_freq / g;
+    const RatePair rp = rate_pair(24000, (int)new_freq);
+    const int64_t of = rp.of, nf = rp.nf;
     if (new_freq != 24000) {
         TORCH_CHECK(taps.has_value(), "f5hip::wave_encode: 24000 -> ", new_freq, " Hz needs the tap table");
         check_dev_f32(*taps, "taps");
-        const int64_t width = (int64_t)std::ceil(6.0 * (double)of / ((double)std::min(of, nf) * 0.99));
-        TORCH_CHECK(taps->dim() == 2 && taps->size(0) == nf && taps->size(1) == 2 * width + of, "f5hip::wave_encode: taps must be [nf = ", nf,
-                    "][2 * width + of = ", 2 * width + of, "] (lowpass_filter_width 6, rolloff 0.99); got ", taps->sizes());
+        TORCH_CHECK(taps->dim() == 2 && taps->size(0) == nf && taps->size(1) == rp.L, "f5hip::wave_encode: taps must be [nf = ", nf,
+                    "][2 * width + of = ", rp.L, "] (rate_pair.h: torchaudio's defaults); got ", taps->sizes());
     }
     for (const at::Tensor& t : pcm)
         TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kShort && t.is_contiguous() && t.dim() == 1 && t.device() == pcm[0].device(),

@@ -22,6 +22,7 @@
 // i * (1.0 / (F - 1)), ramp[F - 1] = 1.0: np.linspace(0, 1, F)).  The silence test rms <= 10^(-50/20) * 32768 = 103.6 with rms =
 // int(sqrt(S / n)) is S < 104^2 n = 10816 n on the integer sum of squares S (n <= 24000: S / n cannot round up across 10816).
 #pragma once
+#include "ragged_util.h"
 
 struct WfChunk {
     const float* x;
@@ -75,37 +76,12 @@ F5_DEVICE int wf_quantise(float v) {   // serve.pcm16: rint(x * 32768) (exact pr
     return (int)fmax(fmin(r, 32767.0), -32768.0);
 }
 
-// last entry whose first block (member `first`) is at or before b
-template <typename T, int T::*first>
-F5_DEVICE int wf_find(const T* e, int n, int b) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (e[mid].*first <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// sum of red[0 .. 256) by a fixed binary tree; every thread returns the total
-F5_DEVICE long long wf_block_sum(long long* red, int tid, long long v) {
-    red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const long long total = red[0];
-    __syncthreads();
-    return total;
-}
-
 __global__ __launch_bounds__(256) void wave_join_kernel(const WfReq* __restrict__ reqs, int n, const WfChunk* __restrict__ chunks, int F, double step,
                                                         short* __restrict__ out, short* __restrict__ joined, long long* __restrict__ cells,
                                                         int* __restrict__ out_len) {
     __shared__ long long part[kWfGroups];
     const int tid = threadIdx.x;
-    const int r = wf_find<WfReq, &WfReq::tile0>(reqs, n, blockIdx.x);
+    const int r = last_at_or_before<&WfReq::tile0>(reqs, n, (int)blockIdx.x);
     const WfReq q = reqs[r];
     const int tile = blockIdx.x - q.tile0;
     const WfChunk* ch = chunks + q.chunk0;
@@ -115,14 +91,7 @@ __global__ __launch_bounds__(256) void wave_join_kernel(const WfReq* __restrict_
         const long long j = (long long)tile * kWfTile + 8 * g;   // (64-bit: the last tile of a request near 2^31 samples ends past INT_MAX)
         long long ss = 0;
         if (j < q.n) {
-            int c = 0;
-            {
-                int hi = q.k - 1;
-                while (c < hi) {
-                    const int mid = (c + hi + 1) >> 1;
-                    if (ch[mid].pos <= j) c = mid; else hi = mid - 1;
-                }
-            }
+            int c = last_at_or_before<&WfChunk::pos>(ch, q.k, j);
             const WfChunk cur = ch[c];
             const int i = (int)j - cur.pos;
             const long long body_end = c + 1 < q.k ? ch[c + 1].pos : q.n;   // one past the last joined sample that is this chunk's alone
@@ -228,7 +197,7 @@ __global__ __launch_bounds__(256) void wave_silence_kernel(const WfReq* __restri
         const short* x = joined + q.joff;
         for (long long s = 24LL * last + tid; s < keep_end; s += 256) acc += (long long)x[s] * x[s];
     }
-    const long long extra_sum = wf_block_sum(red, tid, acc);   // (its barriers also publish pc[])
+    const long long extra_sum = block_sum(red, tid, acc);   // (its barriers also publish pc[])
     const bool extra_silent = extra && extra_sum < kWfLoud * (keep_end - 24LL * last);
 
     // detect_silence opens a new range at a silent start that is neither 10 ms nor at most 1000 ms behind the previous silent start: aligned
@@ -288,7 +257,7 @@ __global__ __launch_bounds__(256) void wave_silence_kernel(const WfReq* __restri
 __global__ __launch_bounds__(256) void wave_compact_kernel(const WfReq* __restrict__ reqs, const WfFlagged* __restrict__ flagged, int nflag,
                                                            const short* __restrict__ joined, const WfRange* __restrict__ ranges,
                                                            const int* __restrict__ nranges, short* __restrict__ out) {
-    const int f = wf_find<WfFlagged, &WfFlagged::tile0>(flagged, nflag, blockIdx.x);
+    const int f = last_at_or_before<&WfFlagged::tile0>(flagged, nflag, (int)blockIdx.x);
     const int r = flagged[f].req;
     const WfReq q = reqs[r];
     const WfRange* rg = ranges + q.range0;
@@ -300,12 +269,7 @@ __global__ __launch_bounds__(256) void wave_compact_kernel(const WfReq* __restri
     for (int m = 0; m < kWfCompactTile / 256; m++) {
         const long long x = x0 + m * 256 + threadIdx.x;
         if (x >= q.n) break;
-        int lo = 0, hi = nr - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (rg[mid].sa <= x) lo = mid; else hi = mid - 1;
-        }
-        const WfRange k = rg[lo];
+        const WfRange k = rg[last_at_or_before<&WfRange::sa>(rg, nr, x)];
         if (x >= k.sa && x < k.sb) dst[k.dst + (int)x - k.sa] = src[x];
     }
 }
@@ -321,7 +285,6 @@ struct WfWorkspace {
     WfRange* ranges = nullptr; size_t cap_ranges = 0;
     int* nranges = nullptr; size_t cap_nranges = 0;
 };
-static WfWorkspace g_wf_ws[32];   // one per device ordinal
 
 int f5hip_wave_finish(int32_t n, const int32_t* chunks_per_request, const float* const* chunk_dev, const int32_t* chunk_len, int32_t fade,
                       const uint8_t* remove_silence, int32_t sample_rate, int16_t* pcm_dev, int32_t* len_dev, void* stream) {
@@ -372,19 +335,19 @@ int f5hip_wave_finish(int32_t n, const int32_t* chunks_per_request, const float*
             ctiles += (pos + kWfCompactTile - 1) / kWfCompactTile;
         }
     }
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(-6, "wave_finish: hipGetDevice");
-    WfWorkspace& ws = g_wf_ws[dev & 31];
-    CK(ref_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_finish requests"));
-    CK(ref_reserve(&ws.chunks, &ws.cap_chunks, hc.size(), "wave_finish chunks"));
+    WfWorkspace* const wsp = device_workspace<WfWorkspace>("wave_finish");
+    if (!wsp) return -6;
+    WfWorkspace& ws = *wsp;
+    CK(dev_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_finish requests"));
+    CK(dev_reserve(&ws.chunks, &ws.cap_chunks, hc.size(), "wave_finish chunks"));
     if (!hf.empty()) {
-        CK(ref_reserve(&ws.flagged, &ws.cap_flagged, hf.size(), "wave_finish flags"));
-        CK(ref_reserve(&ws.joined, &ws.cap_joined, (size_t)joff, "wave_finish joined PCM"));
-        CK(ref_reserve(&ws.cells, &ws.cap_cells, (size_t)ncell, "wave_finish cells"));
-        CK(ref_reserve(&ws.cnt, &ws.cap_cnt, (size_t)ncnt, "wave_finish window counts"));
-        CK(ref_reserve(&ws.buckets, &ws.cap_buckets, (size_t)nbucket, "wave_finish buckets"));
-        CK(ref_reserve(&ws.ranges, &ws.cap_ranges, (size_t)nrange, "wave_finish ranges"));
-        CK(ref_reserve(&ws.nranges, &ws.cap_nranges, (size_t)n, "wave_finish range counts"));
+        CK(dev_reserve(&ws.flagged, &ws.cap_flagged, hf.size(), "wave_finish flags"));
+        CK(dev_reserve(&ws.joined, &ws.cap_joined, (size_t)joff, "wave_finish joined PCM"));
+        CK(dev_reserve(&ws.cells, &ws.cap_cells, (size_t)ncell, "wave_finish cells"));
+        CK(dev_reserve(&ws.cnt, &ws.cap_cnt, (size_t)ncnt, "wave_finish window counts"));
+        CK(dev_reserve(&ws.buckets, &ws.cap_buckets, (size_t)nbucket, "wave_finish buckets"));
+        CK(dev_reserve(&ws.ranges, &ws.cap_ranges, (size_t)nrange, "wave_finish ranges"));
+        CK(dev_reserve(&ws.nranges, &ws.cap_nranges, (size_t)n, "wave_finish range counts"));
     }
     hipStream_t st = (hipStream_t)stream;
     const hipError_t up = hf.empty() ? upload_sync(st, ws.reqs, h, ws.chunks, hc) : upload_sync(st, ws.reqs, h, ws.chunks, hc, ws.flagged, hf);
@@ -445,7 +408,7 @@ __global__ __launch_bounds__(256) void wave_encode_kernel(const WeReq* __restric
                                                           int L, int tq, int enc, unsigned char* __restrict__ out, int* __restrict__ out_len) {
     extern __shared__ __attribute__((aligned(16))) char we_sm[];
     const int tid = threadIdx.x;
-    const int r = wf_find<WeReq, &WeReq::tile0>(reqs, n, blockIdx.x);
+    const int r = last_at_or_before<&WeReq::tile0>(reqs, n, (int)blockIdx.x);
     const WeReq q = reqs[r];
     const int tile = blockIdx.x - q.tile0;
     const int len = len_dev ? min(max(len_dev[r], 0), q.cap) : q.cap;   // (never past what the host sized the buffers for)
@@ -465,7 +428,7 @@ __global__ __launch_bounds__(256) void wave_encode_kernel(const WeReq* __restric
         const long long src = src0 + i;
         xs[i] = src >= 0 && src < len ? x[src] : (short)0;
     }
-    if (RESAMPLE) ref_stage_taps(tp, taps, nf * L, tid);
+    if (RESAMPLE) stage_taps(tp, taps, nf * L, tid);
     __syncthreads();
 
     const int valid = (int)min((long long)n_local, n_out - j0);         // outputs of this tile
@@ -498,21 +461,20 @@ __global__ __launch_bounds__(256) void wave_encode_kernel(const WeReq* __restric
 }
 
 struct WeWorkspace { WeReq* reqs = nullptr; size_t cap_reqs = 0; };
-static WeWorkspace g_we_ws[32];   // one per device ordinal
 
 // (tq, LDS bytes) of a rate pair; tq = 0: window, output tile and tap table do not fit the LDS together
 struct WeTile { int tq, lds; };
-static WeTile we_tile(const RefRatePair& rp) {
-    const int unit = 16 / ref_gcd(rp.nf, 16);                           // tq * nf must be a multiple of 16
+static WeTile we_tile(const RatePair& rp) {
+    const int unit = 16 / rate_gcd(rp.nf, 16);                           // tq * nf must be a multiple of 16
     const long long tq = ((kWeTileOutputs + (long long)rp.nf - 1) / rp.nf + unit - 1) / unit * unit;
     const long long base = ((2 * (tq * rp.of + 2 * rp.width) + 15) & ~15LL) + 2 * tq * rp.nf, table = 4LL * rp.nf * rp.L;
-    if (base + table > kRefLdsMax) return WeTile{0, 0};
+    if (base + table > kLdsMax) return WeTile{0, 0};
     return WeTile{(int)tq, (int)(base + table)};
 }
 
 int f5hip_wave_encode_tile(int32_t new_freq) {
     if (new_freq < 1) return 0;
-    const RefRatePair rp = ref_rate_pair(24000, new_freq);
+    const RatePair rp = rate_pair(24000, new_freq);
     return we_tile(rp).tq * rp.of;
 }
 
@@ -525,7 +487,7 @@ int f5hip_wave_encode(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, 
     if (!identity && !taps_dev) return fail(-1, "wave_encode: 24000 -> %d Hz needs the tap table", new_freq);
     if ((reinterpret_cast<uintptr_t>(pcm_dev) & 1) || (reinterpret_cast<uintptr_t>(out_dev) & 15))
         return fail(-1, "wave_encode: the input must be 2-byte aligned and the output 16-byte aligned");
-    const RefRatePair rp = ref_rate_pair(24000, new_freq);
+    const RatePair rp = rate_pair(24000, new_freq);
     const WeTile t = we_tile(rp);
     if (!t.tq) return fail(-1, "wave_encode: 24000 -> %d Hz is not supported (%d : %d: its tap table does not fit the LDS)", new_freq, rp.of, rp.nf);
     std::vector<WeReq> h(n);
@@ -539,12 +501,12 @@ int f5hip_wave_encode(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, 
         h[i] = WeReq{in_off[i], out_off[i], max_len[i], (int)tiles};
         tiles += std::max<long long>((nq + t.tq - 1) / t.tq, 1);      // (an empty request keeps one block: it writes its length)
     }
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(-6, "wave_encode: hipGetDevice");
-    WeWorkspace& ws = g_we_ws[dev & 31];
-    CK(ref_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_encode requests"));
+    WeWorkspace* const wsp = device_workspace<WeWorkspace>("wave_encode");
+    if (!wsp) return -6;
+    WeWorkspace& ws = *wsp;
+    CK(dev_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_encode requests"));
     static unsigned lds_attr_done = 0;
-    if (t.lds > 64 * 1024 && f5_set_lds_attr((const void*)wave_encode_kernel<true>, kRefLdsMax, lds_attr_done) != hipSuccess)
+    if (t.lds > 64 * 1024 && f5_set_lds_attr((const void*)wave_encode_kernel<true>, kLdsMax, lds_attr_done) != hipSuccess)
         return fail(-7, "wave_encode: LDS opt-in");
     hipStream_t st = (hipStream_t)stream;
     if (upload_sync(st, ws.reqs, h) != hipSuccess) return fail(-6, "wave_encode metadata upload");

@@ -5,10 +5,12 @@ cross-fade ramps), running the sampler and vocoder on the HIP objects (`F5HipMod
 reference's speech-edit script (F/infer/speech_edit.py:119-192) as `plan_edit` / `speech_edit` / `speech_edit_batch`.
 
 Host-side differences, all explicit:
-  * reference audio is read by `load_wav` (a RIFF chunk walker: PCM 8/16/24/32-bit, IEEE float 32/64-bit, WAVE_FORMAT_EXTENSIBLE)
-    or passed as a `(tensor, sr)` pair: torchaudio is not part of this image;
-  * resampling to 24 kHz restates torchaudio.transforms.Resample (sinc interpolation, Hann window, width 6, rolloff
-    0.99; third-party leaf, parity unpinned) on the host, like the reference does before `.to(device)`;
+  * reference audio is read by `wave_codec.load_wav` (a RIFF chunk walker: PCM 8/16/24/32-bit, IEEE float 32/64-bit,
+    WAVE_FORMAT_EXTENSIBLE) or passed as a `(tensor, sr)` pair: torchaudio is not part of this image;
+  * resampling to 24 kHz restates torchaudio.transforms.Resample (sinc interpolation, Hann window, width 6, rolloff 0.99; third-party
+    leaf, parity unpinned) on the host, like the reference does before `.to(device)`: `wave_codec.resample_sinc_hann`;
+  * what the driver has no counterpart for -- WAV reading, the resamplers and their tap tables, G.711, the delivery format of a request --
+    lives in the leaf module `wave_codec`; its public names are handed on here (`infer.load_wav`, `infer.deliver_pcm16`, ...);
   * `preprocess_ref_audio_text` (silence clipping of the reference clip, ". " rule) is restated without pydub in `audio_prep.py`;
   * `convert_char_to_pinyin` (jieba + pypinyin) is replaced by `text_to_tokens`, which reproduces the reference's
     behaviour for text without CJK characters (per-character tokens, the same punctuation translation table)
@@ -20,18 +22,20 @@ import collections
 import contextlib
 import dataclasses
 import math
-import os
 import re
-import struct
-import threading
 import types
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
-from .audio_prep import preprocess_ref_audio_text, remove_silence_edges  # noqa: F401  (F/infer/utils_infer.py:263-350)
+from . import wave_codec
+from .audio_prep import preprocess_ref_audio_text, remove_silence_edges, remove_silence_pcm  # noqa: F401  (F/infer/utils_infer.py:263-350)
 from .loaders import DiT, MMDiT, UNetT, load_checkpoint, load_model, load_vocoder  # noqa: F401  (F/infer/utils_infer.py:92-130,175-260)
+from .wave_codec import (MAX_TAP_TABLE_BYTES, OUTPUT_ENCODINGS, OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, StreamResampler, decode_g711,  # noqa: F401
+                         deliver_pcm16, delivery_format, encode_g711, load_wav, quantise_pcm16, rate_pair, resample_pcm16, resample_sinc_hann,
+                         resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
+from .wave_codec import _device_taps, _tap_tables  # noqa: F401  (the two caches: used below, and read as infer._X by the tests that bound them)
 
 # ----------------------------------------- F/infer/utils_infer.py:40-53
 target_sample_rate = 24000
@@ -49,6 +53,7 @@ sway_sampling_coef = -1.0
 speed = 1.0
 fix_duration = None
 span_steps = 8   # SpanScheduler: ODE steps per span (profiles/r07_admission_bench.txt; DESIGN.md "Resumable spans")
+assert target_sample_rate == wave_codec.SAMPLE_RATE   # wave_codec is a leaf module and keeps its own constant
 
 
 def chunk_text(text, max_chars=135):
@@ -117,172 +122,6 @@ def text_to_tokens(text_list):
             chars.extend(seg)
         out.append(chars)
     return out
-
-
-MAX_TAP_TABLE_BYTES = 4 << 20   # resample_taps refuses larger tables (the largest supported pair, 11 025 -> 24 000 Hz, needs 206 KB)
-TAP_TABLE_CACHE = 16             # rate pairs kept, on the host and per device: an upload chooses its rate, so neither cache may grow with it
-_tap_tables: collections.OrderedDict = collections.OrderedDict()   # (orig_freq, new_freq, lowpass_filter_width, rolloff) -> resample_taps result
-
-
-_tap_lock = threading.Lock()     # route handlers look tables up from a thread pool
-
-
-def _lru_get(cache, key):
-    with _tap_lock:
-        hit = cache.get(key)
-        if hit is not None:
-            cache.move_to_end(key)
-        return hit
-
-
-def _lru_put(cache, key, value):
-    with _tap_lock:
-        cache[key] = value
-        while len(cache) > TAP_TABLE_CACHE:
-            cache.popitem(last=False)
-        return value
-
-
-def resample_taps(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
-    """The polyphase kernel of torchaudio.transforms.Resample(orig_freq, new_freq) ("sinc_interp_hann", torchaudio 2.6):
-    (of, nf, width, taps fp32 [nf, 2 * width + of]) with of : nf the reduced rate pair -- computed in fp64, then cast to fp32.  Output
-    j = q * nf + p of a clip is sum_k taps[p][k] * xpad[q * of + k], xpad = the clip with `width` zeros in front and `width + of` behind.
-    Cached per rate pair, the `TAP_TABLE_CACHE` most recently used ones (treat the table as read-only).  A table above 4 MiB raises ValueError (e.g. 44 101 -> 24 000 Hz: several GB)."""
-    key = (int(orig_freq), int(new_freq), lowpass_filter_width, rolloff)
-    hit = _lru_get(_tap_tables, key)
-    if hit is not None:
-        return hit
-    if key[0] < 1 or key[1] < 1:
-        raise ValueError(f"sample rates must be positive (got {orig_freq} -> {new_freq})")
-    g = math.gcd(key[0], key[1])
-    of, nf = key[0] // g, key[1] // g
-    base_freq = min(of, nf) * rolloff
-    width = math.ceil(lowpass_filter_width * of / base_freq)
-    nbytes = 4 * nf * (2 * width + of)
-    if nbytes > MAX_TAP_TABLE_BYTES:
-        raise ValueError(f"resampling {orig_freq} -> {new_freq} Hz needs a {nf} x {2 * width + of} tap table ({nbytes} bytes, limit {MAX_TAP_TABLE_BYTES}): "
-                         "unsupported sample-rate pair")
-    idx = torch.arange(-width, width + of, dtype=torch.float64)[None, None] / of
-    t = torch.arange(0, -nf, -1, dtype=torch.float64)[:, None, None] / nf + idx
-    t = (t * base_freq).clamp(-lowpass_filter_width, lowpass_filter_width)
-    window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
-    t = t * math.pi
-    kernels = torch.where(t == 0, torch.ones_like(t), t.sin() / t) * window * (base_freq / of)
-    return _lru_put(_tap_tables, key, (of, nf, width, kernels.to(torch.float32)[:, 0].contiguous()))
-
-
-def resample_sinc_hann(wave: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6,
-                       rolloff: float = 0.99) -> torch.Tensor:
-    """torchaudio.transforms.Resample(orig_freq, new_freq) (call site F/infer/utils_infer.py:430-432), default
-    "sinc_interp_hann" method of torchaudio 2.6: polyphase windowed-sinc kernel (`resample_taps`) applied as a strided conv1d.
-    wave [channels, n] -> [channels, ceil(n * new / orig)]."""
-    if orig_freq == new_freq:
-        return wave
-    of, nf, width, taps = resample_taps(orig_freq, new_freq, lowpass_filter_width, rolloff)
-    kernels = taps[:, None]
-    shape = wave.shape
-    w = wave.reshape(-1, shape[-1]).to(torch.float32)
-    length = w.shape[-1]
-    w = torch.nn.functional.pad(w, (width, width + of))
-    out = torch.nn.functional.conv1d(w[:, None], kernels, stride=of)
-    out = out.transpose(1, 2).reshape(w.shape[0], -1)
-    target = math.ceil(nf * length / of)
-    return out[..., :target].reshape(*shape[:-1], target)
-
-
-def resampled_length(n: int, orig_freq: int, new_freq: int) -> int:
-    """Samples `resample_sinc_hann` returns for n: ceil(nf * n / of), in integers (its math.ceil of the float quotient gives the same for
-    every clip length in reach: an exact quotient is an exact float, and no other comes within an ulp of an integer below 2^52)."""
-    g = math.gcd(int(orig_freq), int(new_freq))
-    of, nf = int(orig_freq) // g, int(new_freq) // g
-    return -(-nf * int(n) // of)
-
-
-_WAVE_FORMAT_PCM, _WAVE_FORMAT_IEEE_FLOAT, _WAVE_FORMAT_EXTENSIBLE = 0x0001, 0x0003, 0xFFFE
-_KSDATAFORMAT_TAIL = b"\x00\x00\x00\x00\x10\x00\x80\x00\x00\xaa\x00\x38\x9b\x71"   # bytes 2..15 of every KSDATAFORMAT_SUBTYPE_* GUID
-_WAVE_FORMAT_NAMES = {0x0002: "MS ADPCM", 0x0006: "A-law", 0x0007: "mu-law", 0x0011: "IMA ADPCM", 0x0031: "GSM 6.10",
-                      0x0050: "MPEG", 0x0055: "MPEG Layer 3", 0x00FF: "AAC", 0x1610: "HE-AAC", 0xF1AC: "FLAC"}
-
-
-def _wave_format_name(tag):
-    return f"format code {tag:#06x}" + (f" ({_WAVE_FORMAT_NAMES[tag]})" if tag in _WAVE_FORMAT_NAMES else "")
-
-
-def load_wav(src):
-    """WAV file -> (float32 tensor [channels, samples], sample_rate), scaled like torchaudio.load: PCM 8-bit unsigned
-    ((x - 128) / 128), 16/24/32-bit signed (/ 2**15, / 2**23, / 2**31), IEEE float 32/64-bit as stored; WAVE_FORMAT_EXTENSIBLE with a
-    PCM or float sub-format; any channel count.  `src` is a path, the file's bytes, or a binary file object.  A small RIFF chunk walker
-    instead of the stdlib `wave` module, which reads neither float nor EXTENSIBLE files.  Anything else (FLAC, MP3, compressed WAV
-    format codes, a truncated file) raises ValueError naming what was found."""
-    if isinstance(src, (bytes, bytearray, memoryview)):
-        data = bytes(src)
-    elif hasattr(src, "read"):
-        data = src.read()
-    else:
-        with open(os.fspath(src), "rb") as f:
-            data = f.read()
-    if data[:4] == b"fLaC":
-        raise ValueError("not a WAV file: FLAC stream ('fLaC' magic)")
-    if data[:3] == b"ID3" or (len(data) > 1 and data[0] == 0xFF and data[1] & 0xE0 == 0xE0):
-        raise ValueError("not a WAV file: MPEG audio (MP3) stream")
-    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
-        raise ValueError(f"not a RIFF/WAVE file (starts with {data[:12]!r})")
-    fmt = body = None
-    pos = 12
-    while pos + 8 <= len(data):
-        cid, size = data[pos:pos + 4], struct.unpack_from("<I", data, pos + 4)[0]
-        start, end = pos + 8, pos + 8 + size
-        if cid == b"fmt ":
-            if end > len(data) or size < 16:
-                raise ValueError(f"truncated WAV: 'fmt ' chunk of {size} bytes, {len(data) - start} present")
-            fmt = data[start:end]
-        elif cid == b"data":
-            if end > len(data):
-                raise ValueError(f"truncated WAV: 'data' chunk declares {size} bytes, {len(data) - start} present")
-            body = data[start:end]
-            if fmt is not None:
-                break
-        pos = end + (size & 1)          # chunks are word-aligned
-    if fmt is None or body is None:
-        raise ValueError("truncated WAV: no " + ("'fmt '" if fmt is None else "'data'") + " chunk")
-    tag, ch, sr, _, _, bits = struct.unpack_from("<HHIIHH", fmt, 0)
-    if tag == _WAVE_FORMAT_EXTENSIBLE:
-        if len(fmt) < 40:
-            raise ValueError(f"truncated WAV: WAVE_FORMAT_EXTENSIBLE 'fmt ' chunk of {len(fmt)} bytes (needs 40)")
-        guid = fmt[24:40]
-        sub = struct.unpack_from("<H", guid, 0)[0]
-        if guid[2:] != _KSDATAFORMAT_TAIL:
-            raise ValueError(f"unsupported WAV: WAVE_FORMAT_EXTENSIBLE with sub-format GUID {guid.hex()}")
-        if sub not in (_WAVE_FORMAT_PCM, _WAVE_FORMAT_IEEE_FLOAT):
-            raise ValueError(f"unsupported WAV: WAVE_FORMAT_EXTENSIBLE with sub-format {_wave_format_name(sub)}")
-        tag = sub
-    if ch < 1:
-        raise ValueError(f"unsupported WAV: {ch} channels")
-    if tag == _WAVE_FORMAT_PCM and bits in (8, 16, 24, 32):
-        kind = "pcm"
-    elif tag == _WAVE_FORMAT_IEEE_FLOAT and bits in (32, 64):
-        kind = "float"
-    elif tag in (_WAVE_FORMAT_PCM, _WAVE_FORMAT_IEEE_FLOAT):
-        raise ValueError(f"unsupported WAV: {'PCM' if tag == _WAVE_FORMAT_PCM else 'IEEE float'} at {bits} bits per sample")
-    else:
-        raise ValueError(f"unsupported WAV: {_wave_format_name(tag)}")
-    width = bits // 8
-    n = len(body) // (width * ch)       # whole frames only, like wave.readframes
-    raw = body[:n * width * ch]
-    if kind == "float":
-        x = np.frombuffer(raw, dtype="<f4" if bits == 32 else "<f8").astype(np.float32)
-    elif bits == 8:
-        x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
-    elif bits == 16:
-        x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
-    elif bits == 24:
-        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
-        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
-        x = ((v << 8) >> 8).astype(np.float32) / 8388608.0      # sign-extend the 24-bit value
-    else:
-        x = np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
-    a = x.reshape(-1, ch).T
-    return torch.from_numpy(np.ascontiguousarray(a)), sr
 
 
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print,
@@ -371,13 +210,17 @@ def cross_fade_concat(waves, fade_seconds, sample_rate=target_sample_rate):
         return np.concatenate(waves)
     out = waves[0]
     for nxt in waves[1:]:
-        n = min(int(fade_seconds * sample_rate), len(out), len(nxt))
-        if n <= 0:
-            out = np.concatenate([out, nxt])
-            continue
-        ramp = np.linspace(0, 1, n)
-        out = np.concatenate([out[:-n], out[-n:] * ramp[::-1] + nxt[:n] * ramp, nxt[n:]])
+        out = _cross_fade(out, nxt, int(fade_seconds * sample_rate))
     return out
+
+
+def _cross_fade(out, nxt, fade):
+    """One join of `cross_fade_concat`: `nxt` behind `out`, faded over n = min(fade, len(out), len(nxt)) samples (n <= 0: appended)."""
+    n = min(fade, len(out), len(nxt))
+    if n <= 0:
+        return np.concatenate([out, nxt])
+    ramp = np.linspace(0, 1, n)
+    return np.concatenate([out[:-n], out[-n:] * ramp[::-1] + nxt[:n] * ramp, nxt[n:]])
 
 
 class StreamJoiner:
@@ -396,14 +239,8 @@ class StreamJoiner:
         if self.held is None:
             local = nxt
         else:
-            out = self.held
-            n = min(self.fade, len(out), len(nxt))
-            if n <= 0:
-                local = np.concatenate([out, nxt])
-            else:
-                ramp = np.linspace(0, 1, n)
-                local = np.concatenate([out[:-n], out[-n:] * ramp[::-1] + nxt[:n] * ramp, nxt[n:]])
-            self.total -= len(out)
+            local = _cross_fade(self.held, nxt, self.fade)
+            self.total -= len(self.held)
         self.total += len(local)
         keep = min(self.fade, self.total)          # <= len(local): see the class note
         self.held = local[len(local) - keep:]
@@ -503,15 +340,6 @@ def prepare_voices(clips, target_rms=0.1, device="cuda"):
                 v.audio, v.rms, v.pending = audio[None], all_rms[k], None
                 k += 1
     return voices
-
-
-_taps_on_device: collections.OrderedDict = collections.OrderedDict()   # (orig_freq, new_freq, device) -> the tap table there
-
-
-def _device_taps(orig_freq, new_freq, device):
-    key = (int(orig_freq), int(new_freq), str(device))
-    hit = _lru_get(_taps_on_device, key)
-    return hit if hit is not None else _lru_put(_taps_on_device, key, resample_taps(orig_freq, new_freq)[3].to(device))
 
 
 def _prepare_deferred(voices, model_obj):
@@ -636,6 +464,17 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 # per-request options of `infer_requests` (the fourth element of a request) and of the serving routes
 _PLAIN = (target_sample_rate, "pcm16")   # the delivery format of a request that sets neither `sample_rate` nor `encoding`
 REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "remove_silence", "sample_rate", "encoding")
+WHOLE_WAVE = ("remove_silence, sample_rate and encoding need the request's whole wave: they are not available for a list of chunk texts (a streamed "
+              "request, whose owner applies the delivery format piece by piece: StreamResampler, encode_g711) or with join=False")
+
+
+def needs_whole_wave(opts, streamed=False) -> bool:
+    """Whether a request's options apply to its joined wave, so that it cannot be handed out chunk by chunk (`WHOLE_WAVE`): `remove_silence`,
+    and a delivery format (`sample_rate`, `encoding`) other than 24 kHz "pcm16".  `streamed`: the format does not count -- a stream's owner
+    (`serve.TTSManager._stream`) takes it off the request and applies it to the pieces itself."""
+    if opts.get("remove_silence"):
+        return True
+    return not streamed and delivery_format(opts.get("sample_rate"), opts.get("encoding")) != _PLAIN
 
 
 def plan_request(request, defaults, *, target_rms, fix_duration, device, tokenizer):
@@ -648,11 +487,8 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
     unknown = set(opts) - set(REQUEST_OPTIONS) - {"generator"}
     if unknown:
         raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
-    if opts.get("remove_silence") and isinstance(gen_text, (list, tuple)):
-        raise ValueError("remove_silence needs the request's whole wave: it is not available for a list of chunk texts (a streamed request)")
-    if delivery_format(opts.get("sample_rate"), opts.get("encoding")) != _PLAIN and isinstance(gen_text, (list, tuple)):
-        raise ValueError("sample_rate / encoding apply to a request's joined wave: a list of chunk texts (a streamed request) gets them from "
-                         "its caller, piece by piece (StreamResampler, encode_g711)")
+    if needs_whole_wave(opts) and isinstance(gen_text, (list, tuple)):
+        raise ValueError(WHOLE_WAVE)
     voice, units = _plan_request(ref_audio, ref_text, gen_text, target_rms, opts["speed"], fix_duration, device, tokenizer)
     own = opts.get("generator")
     gen = torch.Generator().set_state(own.get_state()) if own is not None else request_generator(opts["seed"])
@@ -744,11 +580,12 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
         chunk_waves = [waves for waves, _ in _chunk_waves(groups, vocoder, mel_spec_type, target_rms, on_device=backend, want_specs=False)]
         return finish_requests(chunk_waves, [req[2] for req in requests], cross_fade_duration, silence, sample_rate=[f[0] for f in formats],
                                encoding=[f[1] for f in formats], **finish)
-    if (any(silence) or any(f != _PLAIN for f in formats)) and not join:
-        raise ValueError("remove_silence, sample_rate and encoding need the request's whole wave: they are not available with join=False")
+    whole = [needs_whole_wave(plan.opts) for plan in plans]
+    if any(whole) and not join:
+        raise ValueError(WHOLE_WAVE)
     out = []
-    for flag, fmt, (waves, specs) in zip(silence, formats, _chunk_waves(groups, vocoder, mel_spec_type, target_rms)):
-        if flag or fmt != _PLAIN:
+    for needs, flag, fmt, (waves, specs) in zip(whole, silence, formats, _chunk_waves(groups, vocoder, mel_spec_type, target_rms)):
+        if needs:
             wave, = finish_requests([waves], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1])
             out.append((wave, fmt[0], np.concatenate(specs, axis=1)))
         elif join:
@@ -764,169 +601,6 @@ def request_wave(gen_text, waves, cross_fade_duration=cross_fade_duration):
     if isinstance(gen_text, (list, tuple)):
         return waves
     return np.asarray(cross_fade_concat(waves, cross_fade_duration), dtype=np.float32)
-
-
-def quantise_pcm16(wave) -> np.ndarray:
-    """int16 PCM of float samples by the routes' rule (`serve.wav_bytes`, `serve.pcm16`): rint(x * 32768) in float64, half to even, clipped."""
-    return np.clip(np.rint(np.asarray(wave).astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
-
-
-# ----------------------------------------- delivery format: output sample rate and G.711 (not in the reference, whose route always answers 24 kHz PCM)
-OUTPUT_SAMPLE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
-OUTPUT_ENCODINGS = ("pcm16", "mulaw", "alaw")     # their position is the library's encoding code (include/f5hip.h f5hip_wave_encode)
-
-
-def _polyphase_pcm(xpad, taps64, of, nq):
-    """Polyphase blocks 0 .. nq - 1 over xpad (float64, at least nq * of + L - of samples): out[q * nf + p] = sum_k taps64[p][k] * xpad[q * of + k],
-    k ascending, each product and each sum rounded to fp64 on its own; then rint (half to even), clipped, as int16."""
-    nf, L = taps64.shape
-    acc = np.zeros((nq, nf), dtype=np.float64)
-    for k in range(L):
-        acc += xpad[k:k + (nq - 1) * of + 1:of, None] * taps64[None, :, k]
-    return np.clip(np.rint(acc), -32768, 32767).astype(np.int16).reshape(-1)
-
-
-def _output_taps(new_freq):
-    if int(new_freq) not in OUTPUT_SAMPLE_RATES:
-        raise ValueError(f"sample_rate must be one of {list(OUTPUT_SAMPLE_RATES)} (got {new_freq!r})")
-    of, nf, width, taps = resample_taps(target_sample_rate, int(new_freq))
-    return of, nf, width, taps.numpy().astype(np.float64)
-
-
-def _as_pcm16(pcm):
-    pcm = np.asarray(pcm)
-    if pcm.dtype != np.int16 or pcm.ndim != 1:
-        raise ValueError(f"expected 1-D int16 PCM (got {pcm.dtype}, {pcm.ndim}-D)")
-    return pcm
-
-
-def resample_pcm16(pcm, new_freq) -> np.ndarray:
-    """24 kHz int16 PCM [n] at `new_freq` (one of OUTPUT_SAMPLE_RATES): int16 [resampled_length(n, 24000, new_freq)].  Output j = q nf + p is
-    rint(sum_k (double)taps[p][k] * (double)xpad[q of + k]) -- `resample_taps`' fp32 table, k ascending, fp64 accumulation, xpad = the samples
-    with `width` zeros in front and zeros behind -- half to even, clipped to [-32768, 32767].  Integer samples times fp32 taps are exact in
-    fp64 (16 + 24 bits), so a fused multiply-add and numpy's multiply-then-add give the same bits: the device kernel (csrc/wave_out.h
-    wave_encode_kernel) is held to this function with no tolerance.  24000 returns its input."""
-    pcm = _as_pcm16(pcm)
-    if int(new_freq) == target_sample_rate:
-        return pcm
-    of, nf, width, taps64 = _output_taps(new_freq)
-    m = resampled_length(len(pcm), target_sample_rate, new_freq)
-    if m == 0:
-        return np.zeros(0, dtype=np.int16)
-    nq = -(-m // nf)
-    xpad = np.zeros(nq * of + 2 * width, dtype=np.float64)
-    xpad[width:width + len(pcm)] = pcm
-    return _polyphase_pcm(xpad, taps64, of, nq)[:m]
-
-
-class StreamResampler:
-    """`resample_pcm16` one piece at a time: `feed(piece)` returns the outputs of every polyphase block whose input window is complete and keeps
-    the tail it still needs, `flush()` the rest (zeros behind the last sample).  The concatenation of everything returned equals
-    `resample_pcm16` of the concatenated input, bit for bit, whatever the piece sizes: an output's terms and their order do not depend on
-    when it is computed."""
-
-    def __init__(self, new_freq):
-        self.new_freq = int(new_freq)
-        self.identity = self.new_freq == target_sample_rate
-        if not self.identity:
-            self.of, self.nf, self.width, self.taps64 = _output_taps(new_freq)
-            self.tail = np.zeros(self.width, dtype=np.float64)   # xpad from block `q` on: the zeros in front at first
-        self.n = self.q = 0                                      # samples fed; polyphase blocks emitted
-
-    def feed(self, piece):
-        piece = _as_pcm16(piece)
-        if self.identity:
-            return piece
-        self.n += len(piece)
-        self.tail = np.concatenate([self.tail, piece.astype(np.float64)])
-        ready = max((self.n - self.width) // self.of, 0)         # block q needs xpad[q of .. q of + 2 width + of): width + n of it exist
-        if ready <= self.q:
-            return np.zeros(0, dtype=np.int16)
-        out = _polyphase_pcm(self.tail, self.taps64, self.of, ready - self.q)
-        self.tail = self.tail[(ready - self.q) * self.of:]
-        self.q = ready
-        return out
-
-    def flush(self):
-        if self.identity:
-            return np.zeros(0, dtype=np.int16)
-        m = resampled_length(self.n, target_sample_rate, self.new_freq)
-        nq = -(-m // self.nf) - self.q
-        if nq <= 0:
-            return np.zeros(0, dtype=np.int16)
-        xpad = np.zeros(nq * self.of + 2 * self.width, dtype=np.float64)
-        xpad[:len(self.tail)] = self.tail
-        out = _polyphase_pcm(xpad, self.taps64, self.of, nq)[:m - self.q * self.nf]
-        self.q, self.tail = self.q + nq, np.zeros(0, dtype=np.float64)
-        return out
-
-
-def _check_law(law):
-    if law not in ("mulaw", "alaw"):
-        raise ValueError(f'law must be "mulaw" or "alaw" (got {law!r})')
-
-
-def encode_g711(pcm, law) -> np.ndarray:
-    """G.711 code bytes (uint8) of int16 PCM: CPython's `audioop.lin2ulaw` / `lin2alaw` at width 2, in closed form.  mu-law works on the 14-bit
-    value s >> 2 (magnitude clipped at 8158, bias 0x21), A-law on the 13-bit value s >> 3 (a negative value as -x - 1); the segment is the
-    position of the leading bit."""
-    _check_law(law)
-    s = np.asarray(pcm)
-    if s.dtype != np.int16:
-        raise ValueError(f"expected int16 PCM (got {s.dtype})")
-    ilog2 = lambda m: np.frexp(m.astype(np.float64))[1] - 1   # noqa: E731  floor(log2 m), m >= 1
-    if law == "mulaw":
-        x = s.astype(np.int32) >> 2
-        sign = np.where(x < 0, 0x7F, 0xFF)
-        m = np.minimum(np.abs(x), 8158) + 0x21
-        seg = ilog2(m) - 5
-        code = ((seg << 4) | ((m >> (seg + 1)) & 15)) ^ sign
-    else:
-        x = s.astype(np.int32) >> 3
-        mask = np.where(x >= 0, 0xD5, 0x55)
-        m = np.where(x >= 0, x, -x - 1)
-        seg = np.maximum(ilog2(np.maximum(m, 1)) - 4, 0)
-        code = ((seg << 4) | ((m >> np.where(seg < 2, 1, seg)) & 15)) ^ mask
-    return code.astype(np.uint8)
-
-
-def decode_g711(codes, law) -> np.ndarray:
-    """int16 PCM of G.711 code bytes: `audioop.ulaw2lin` / `alaw2lin` at width 2."""
-    _check_law(law)
-    c = np.asarray(codes)
-    if c.dtype != np.uint8:
-        raise ValueError(f"expected uint8 codes (got {c.dtype})")
-    c = c.astype(np.int32)
-    if law == "mulaw":
-        u = ~c & 0xFF
-        t = (((u & 0x0F) << 3) + 0x84) << ((u & 0x70) >> 4)
-        out = np.where(u & 0x80, 0x84 - t, t - 0x84)
-    else:
-        a = c ^ 0x55
-        seg = (a & 0x70) >> 4
-        t = (a & 0x0F) << 4
-        t = np.where(seg == 0, t + 8, (t + 0x108) << np.maximum(seg - 1, 0))
-        out = np.where(a & 0x80, t, -t)
-    return out.astype(np.int16)
-
-
-def delivery_format(sample_rate=None, encoding=None):
-    """(rate, encoding) of a request with None filled in (24000, "pcm16"), checked against OUTPUT_SAMPLE_RATES / OUTPUT_ENCODINGS."""
-    rate = target_sample_rate if sample_rate is None else sample_rate
-    enc = "pcm16" if encoding is None else encoding
-    if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or int(rate) not in OUTPUT_SAMPLE_RATES:
-        raise ValueError(f"sample_rate must be one of {list(OUTPUT_SAMPLE_RATES)} (got {sample_rate!r})")
-    if not isinstance(enc, str) or enc not in OUTPUT_ENCODINGS:
-        raise ValueError(f"encoding must be one of {list(OUTPUT_ENCODINGS)} (got {encoding!r})")
-    return int(rate), enc
-
-
-def deliver_pcm16(pcm, sample_rate=None, encoding=None) -> np.ndarray:
-    """The delivery format of a request's canonical result, its 24 kHz int16 PCM: `resample_pcm16`, then `encode_g711` -- int16 at
-    `sample_rate`, or uint8 code bytes.  (24000, "pcm16") returns the PCM itself."""
-    rate, enc = delivery_format(sample_rate, encoding)
-    pcm = resample_pcm16(pcm, rate)
-    return pcm if enc == "pcm16" else encode_g711(pcm, enc)
 
 
 # What `finish_requests` and `_chunk_waves` did since the last `backend_stats.clear()`: requests finished on the device / on the host,
@@ -983,71 +657,86 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     out, on_device = [None] * n, []
     for i, (waves, text) in enumerate(zip(chunk_waves_per_request, gen_texts)):
         if isinstance(text, (list, tuple)):
-            if flags[i] or formats[i] != _PLAIN:
-                raise ValueError("remove_silence, sample_rate and encoding need the request's whole wave: they are not available for a list of chunk texts")
+            if needs_whole_wave(dict(remove_silence=flags[i], sample_rate=formats[i][0], encoding=formats[i][1])):
+                raise ValueError(WHOLE_WAVE)
             out[i] = [_host_chunk(w) for w in waves]
         elif device_backend and all(torch.is_tensor(w) and w.is_cuda for w in waves) and (len(waves) == 1 or min(len(w) for w in waves) >= 2 * fade):
             on_device.append(i)
             continue
         else:
-            wave = request_wave(text, [_host_chunk(w) for w in waves], cross_fade_duration)
-            if flags[i]:
-                from .audio_prep import remove_silence_pcm
-                wave = remove_silence_pcm(quantise_pcm16(wave), target_sample_rate)
-            elif want == "pcm16" or formats[i] != _PLAIN:
-                wave = quantise_pcm16(wave)
-            out[i] = wave if formats[i] == _PLAIN else deliver_pcm16(wave, *formats[i])
+            out[i] = _finish_on_host(waves, text, cross_fade_duration, flags[i], formats[i], want)
         backend_stats["host_requests"] += 1
     if on_device:
-        from . import ops
         # the plain requests first: their PCM is then one prefix of the packed buffer, and what comes down of it holds no other request's
         on_device.sort(key=lambda i: formats[i] != _PLAIN)
-        plain = sum(formats[i] == _PLAIN for i in on_device)
-        chunks = [w.to(torch.float32).contiguous() for i in on_device for w in chunk_waves_per_request[i]]
-        silence = [flags[i] for i in on_device]
-        joined = [sum(len(w) for w in chunk_waves_per_request[i]) - (len(chunk_waves_per_request[i]) - 1) * fade for i in on_device]
-        pcm, lengths, offsets = ops.wave_finish(chunks, [len(chunk_waves_per_request[i]) for i in on_device], fade, silence, target_sample_rate)
-        if plain:
-            if any(silence[:plain]):
-                kept = lengths[:plain].cpu().tolist()
-                backend_stats["d2h_copies"] += 1
-            else:   # without silence removal a request keeps its joined length
-                kept = joined[:plain]
-            host = pcm[:offsets[plain - 1] + joined[plain - 1]].cpu().numpy()
+        done = _finish_on_device([chunk_waves_per_request[i] for i in on_device], fade, [flags[i] for i in on_device], [formats[i] for i in on_device])
+        for i, wave in zip(on_device, done):
+            out[i] = wave
+    return out
+
+
+def _finish_on_host(waves, text, cross_fade_duration, flag, fmt, want):
+    """`finish_requests` for one request on the host: join, quantisation, silence removal and the delivery format in numpy."""
+    wave = request_wave(text, [_host_chunk(w) for w in waves], cross_fade_duration)
+    if flag:
+        wave = remove_silence_pcm(quantise_pcm16(wave), target_sample_rate)
+    elif want == "pcm16" or fmt != _PLAIN:
+        wave = quantise_pcm16(wave)
+    return wave if fmt == _PLAIN else deliver_pcm16(wave, *fmt)
+
+
+def _finish_on_device(requests, fade, silence, formats):
+    """`finish_requests` for the requests the device back-end takes: `requests` = their chunk waves (device tensors), the plain-format ones
+    first; `silence`, `formats` per request.  ONE `ops.wave_finish` call, then one `ops.wave_encode` call per distinct delivery format behind
+    it on the same stream.  Returns one result per request."""
+    from . import ops
+    out = [None] * len(requests)
+    plain = sum(fmt == _PLAIN for fmt in formats)
+    chunks = [w.to(torch.float32).contiguous() for waves in requests for w in waves]
+    joined = [sum(len(w) for w in waves) - (len(waves) - 1) * fade for waves in requests]
+    pcm, lengths, offsets = ops.wave_finish(chunks, [len(waves) for waves in requests], fade, silence, target_sample_rate)
+    if plain:
+        if any(silence[:plain]):
+            kept = lengths[:plain].cpu().tolist()
             backend_stats["d2h_copies"] += 1
-            for i, off, length in zip(on_device[:plain], offsets, kept):
-                out[i] = host[off:off + length].copy()   # (a request's result does not keep the batch's buffer alive)
-        groups = {}
-        for k in range(plain, len(on_device)):
-            groups.setdefault(formats[on_device[k]], []).append(k)
-        for (rate, enc), ks in groups.items():   # one call per delivery format, behind wave_finish on the same stream
-            taps = _device_taps(target_sample_rate, rate, pcm.device) if rate != target_sample_rate else None
-            contiguous = ks == list(range(ks[0], ks[-1] + 1))
-            sel = lengths[ks[0]:ks[-1] + 1] if contiguous else lengths[torch.tensor(ks, device=lengths.device)]   # (gathered on the device)
-            data, out_len, out_off = ops.wave_encode(pcm, [offsets[k] for k in ks], [joined[k] for k in ks], sel, rate, enc, taps)
-            if any(silence[k] for k in ks):
-                counts = out_len.cpu().tolist()
-                backend_stats["d2h_copies"] += 1
-            else:
-                counts = [resampled_length(joined[k], target_sample_rate, rate) for k in ks]
-            host = data.cpu().numpy()
+        else:   # without silence removal a request keeps its joined length
+            kept = joined[:plain]
+        host = pcm[:offsets[plain - 1] + joined[plain - 1]].cpu().numpy()
+        backend_stats["d2h_copies"] += 1
+        for k, (off, length) in enumerate(zip(offsets, kept)):
+            out[k] = host[off:off + length].copy()   # (a request's result does not keep the batch's buffer alive)
+    groups = {}
+    for k in range(plain, len(requests)):
+        groups.setdefault(formats[k], []).append(k)
+    for (rate, enc), ks in groups.items():   # one call per delivery format, behind wave_finish on the same stream
+        taps = _device_taps(target_sample_rate, rate, pcm.device) if rate != target_sample_rate else None
+        contiguous = ks == list(range(ks[0], ks[-1] + 1))
+        sel = lengths[ks[0]:ks[-1] + 1] if contiguous else lengths[torch.tensor(ks, device=lengths.device)]   # (gathered on the device)
+        data, out_len, out_off = ops.wave_encode(pcm, [offsets[k] for k in ks], [joined[k] for k in ks], sel, rate, enc, taps)
+        if any(silence[k] for k in ks):
+            counts = out_len.cpu().tolist()
             backend_stats["d2h_copies"] += 1
-            for k, off, m in zip(ks, out_off, counts):
-                raw = host[off:off + m * (2 if enc == "pcm16" else 1)].copy()
-                out[on_device[k]] = raw.view("<i2") if enc == "pcm16" else raw
-            backend_stats["encode_calls"] += 1
-            backend_stats["encode_requests"] += len(ks)
-        backend_stats["device_calls"] += 1
-        backend_stats["device_requests"] += len(on_device)
+        else:
+            counts = [resampled_length(joined[k], target_sample_rate, rate) for k in ks]
+        host = data.cpu().numpy()
+        backend_stats["d2h_copies"] += 1
+        for k, off, m in zip(ks, out_off, counts):
+            raw = host[off:off + m * (2 if enc == "pcm16" else 1)].copy()
+            out[k] = raw.view("<i2") if enc == "pcm16" else raw
+        backend_stats["encode_calls"] += 1
+        backend_stats["encode_requests"] += len(ks)
+    backend_stats["device_calls"] += 1
+    backend_stats["device_requests"] += len(requests)
     return out
 
 
 class SpanTicket:
-    """One admitted request of a `SpanScheduler`: its planned units, and -- once they have all ended -- `result` (`request_wave`)."""
+    """One admitted request of a `SpanScheduler`: its planned units, what its planned options (`plan_request`'s `opts`) say about the finished
+    wave, and -- once the units have all ended -- `result` (`request_wave`)."""
 
-    def __init__(self, request, voice, units, remove_silence=False, sample_rate=None, encoding=None):
-        self.request, self.voice, self.units, self.remove_silence = request, voice, units, bool(remove_silence)
-        self.sample_rate, self.encoding = delivery_format(sample_rate, encoding)
+    def __init__(self, request, voice, units, opts):
+        self.request, self.voice, self.units, self.remove_silence = request, voice, units, bool(opts.get("remove_silence"))
+        self.sample_rate, self.encoding = delivery_format(opts.get("sample_rate"), opts.get("encoding"))
         self.in_flight = self.cancelled = self.done = False
         self.result = None
 
@@ -1117,7 +806,7 @@ class SpanScheduler:
                                             sway_sampling_coef=opts["sway_sampling_coef"], generator=plan.generator, **extra)
                    for tokens, frames in plan.units]
         plan.commit()   # every chunk was planned: the caller's generator moves
-        ticket = SpanTicket(request, voice, planned, opts.get("remove_silence"), opts.get("sample_rate"), opts.get("encoding"))
+        ticket = SpanTicket(request, voice, planned, opts)
         self.waiting.append(ticket)
         return ticket
 

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib, torch_ops
+from .wave_codec import rate_pair
 
 ACT = {"none": 0, "gelu_tanh": 1, "gelu_erf": 2, "mish": 3, "silu": 4}
 
@@ -345,13 +346,11 @@ def ref_frontend(wave, n_in, channels, orig_freq, new_freq, taps=None, rms_floor
     ch = np.ascontiguousarray(np.asarray(channels, dtype=np.int32))
     assert wave.dtype == torch.float32 and wave.is_contiguous() and wave.is_cuda
     assert taps is None or (taps.dtype == torch.float32 and taps.is_contiguous() and taps.is_cuda)
-    g = int(np.gcd(int(orig_freq), int(new_freq)))
-    of, nf = int(orig_freq) // g, int(new_freq) // g
+    of, nf, _, L = rate_pair(orig_freq, new_freq)
     n_out = [(nf * int(v) + of - 1) // of for v in ni]
-    if of != nf:   # the library derives the row length itself (lowpass_filter_width 6, rolloff 0.99): refuse a table of another shape
-        width = int(np.ceil(6.0 * of / (min(of, nf) * 0.99)))
-        if taps is None or tuple(taps.shape) != (nf, 2 * width + of):
-            raise _lib.F5HipError(f"ref_frontend: taps must be [{nf}, {2 * width + of}] for {orig_freq} -> {new_freq} Hz "
+    if of != nf:   # the library derives the row length itself (csrc/rate_pair.h): refuse a table of another shape
+        if taps is None or tuple(taps.shape) != (nf, L):
+            raise _lib.F5HipError(f"ref_frontend: taps must be [{nf}, {L}] for {orig_freq} -> {new_freq} Hz "
                                   f"(got {None if taps is None else tuple(taps.shape)})")
     if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
         try:
@@ -443,12 +442,10 @@ def wave_encode(pcm, in_off, max_len, len_dev, sample_rate, encoding, taps=None)
         raise _lib.F5HipError("wave_encode: len_dev must be an int32 tensor with one value per request on the pcm's device")
     if rate < 1:
         raise _lib.F5HipError(f"wave_encode: the sample rate must be positive (got {sample_rate})")
-    g = int(np.gcd(24000, rate))
-    of, nf = 24000 // g, rate // g
+    of, nf, _, L = rate_pair(24000, rate)
     if rate != 24000:
-        width = int(np.ceil(6.0 * of / (min(of, nf) * 0.99)))
-        if taps is None or not (taps.dtype == torch.float32 and taps.is_contiguous() and taps.is_cuda) or tuple(taps.shape) != (nf, 2 * width + of):
-            raise _lib.F5HipError(f"wave_encode: taps must be a contiguous fp32 device tensor [{nf}, {2 * width + of}] for 24000 -> {rate} Hz "
+        if taps is None or not (taps.dtype == torch.float32 and taps.is_contiguous() and taps.is_cuda) or tuple(taps.shape) != (nf, L):
+            raise _lib.F5HipError(f"wave_encode: taps must be a contiguous fp32 device tensor [{nf}, {L}] for 24000 -> {rate} Hz "
                                   f"(got {None if taps is None else tuple(taps.shape)})")
     if len_dev is not None:
         len_dev = len_dev.contiguous()

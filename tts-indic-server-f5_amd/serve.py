@@ -10,7 +10,8 @@ Differences, explicit:
   * reference voices come from `VoiceRegistry` (name -> local 16-bit WAV + transcript); the reference downloads the prompt WAV
     from GitHub on every request (`tts_utils.py:40-46`), which this deployment target (no egress) cannot and should not do;
   * the response body is 16-bit PCM WAV at 24 kHz written with the stdlib (`soundfile`'s default WAV subtype for float input
-    is PCM_16 as well);
+    is PCM_16 as well); the bytes of a body -- `wav_bytes`, `wav_stream_header`, `delivery_bytes`, `pcm16` -- are made in the leaf module
+    `wave_codec`, next to the delivery formats they write, and handed on here under the same names;
   * `TTSManager.load()` takes the model / vocoder objects (or a loader callable): checkpoints are not fetched from the hub;
   * `TTSManager(micro_batch=dict(max_requests=16, max_wait_ms=5))`: concurrent requests are collected for a few milliseconds and synthesized as ONE
     sampler batch (`infer.infer_requests`); with `ShardedSampler` as the model object that batch is dealt over the GPUs of the node
@@ -30,10 +31,9 @@ import hashlib
 import io
 import logging
 import queue
-import struct
 import threading
 import time
-import wave as _wave
+import types
 from concurrent.futures import Future
 from dataclasses import dataclass, field
 from typing import Callable
@@ -43,6 +43,7 @@ import math
 import numpy as np
 
 from . import audio_prep, infer
+from .wave_codec import delivery_bytes, pcm16, wav_bytes, wav_stream_header  # noqa: F401  (handed on: serve.wav_bytes, serve.pcm16, ...)
 
 log = logging.getLogger(__name__)
 
@@ -77,16 +78,10 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
             if not v:
                 continue
             v = True
-        elif k == "sample_rate":
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in infer.OUTPUT_SAMPLE_RATES:
-                raise ValueError(f"sample_rate must be one of {', '.join(str(r) for r in infer.OUTPUT_SAMPLE_RATES)} (got {v!r})")
-            if int(v) == infer.target_sample_rate:
-                continue
-            v = int(v)
-        elif k == "encoding":
-            if not isinstance(v, str) or v not in infer.OUTPUT_ENCODINGS:
-                raise ValueError(f"encoding must be one of {', '.join(repr(e) for e in infer.OUTPUT_ENCODINGS)} (got {v!r})")
-            if v == "pcm16":
+        elif k in ("sample_rate", "encoding"):
+            i = ("sample_rate", "encoding").index(k)
+            v = infer.delivery_format(**{k: v})[i]      # ValueError: "<name> must be one of ..."
+            if v == infer.delivery_format()[i]:         # 24000 / "pcm16": what a request gets anyway
                 continue
         elif k in ("nfe_step", "seed"):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
@@ -501,11 +496,7 @@ class TTSManager:
         return (voice, ref_text, text, opts) if opts else (voice, ref_text, text)
 
     def _call(self, text, ref_audio_path, ref_text, **options):
-        voice, ref_text_n = self._voice(ref_audio_path, ref_text)
-        req = self._request(voice, ref_text_n, text, options)
-        if self.batcher is not None:   # wait for the batch this request rides in (the route runs in a worker thread, see create_app)
-            return self.batcher.submit(req).result(timeout=self.request_timeout_s)
-        return self._run_batch([req])[0]
+        return self._serve(lambda: self._voice(ref_audio_path, ref_text), text, options)
 
     def _clip_voice(self, ref_audio, ref_text, clip_short=True):
         """(PreparedVoice, normalised ref_text) of an uploaded clip -- WAV bytes or a (wave [ch, n], sr) pair -- prepared once per
@@ -571,40 +562,43 @@ class TTSManager:
                 if entry[1] == 0:
                     self._clip_key_locks.pop(key, None)
 
-    def synthesize_clip(self, text, ref_audio, ref_text, *, clip_short=True, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
-                        seed=None, ode_method=None, remove_silence=None, sample_rate=None, encoding=None):
-        """`synthesize` with the caller's own reference clip instead of a registered voice: `ref_audio` is a WAV file's bytes or a
-        (wave [ch, n], sr) pair, `ref_text` its transcript; `clip_short` as in `preprocess_ref_audio_text`.  The clip never touches the
-        disk (`_clip_voice`); the request then takes the same batcher path as `synthesize`, with the same options."""
+    def _serve(self, resolve_voice, text, options, stream=False):
+        """What the four `synthesize*` methods do once they know where the voice comes from (`resolve_voice`: `_voice` or `_clip_voice`, called
+        after the options are checked): the model must be loaded, `options` go through `request_options` (an unknown name is a ValueError),
+        then the request runs -- through the batcher, or alone under the device lock -- or, with `stream`, becomes a `SynthesisStream`: no
+        option that needs the whole wave, the first chunk and the remaining chunks as two requests that share one generator when it is seeded
+        (the tail's batch runs after the head's: one worker, one batch at a time)."""
         if not self.model:
             raise ValueError("TTS model not loaded")
-        opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                    ode_method=ode_method, remove_silence=remove_silence, sample_rate=sample_rate, encoding=encoding)
-        voice, ref_text_n = self._clip_voice(ref_audio, ref_text, clip_short)
-        req = self._request(voice, ref_text_n, text, opts)
-        if self.batcher is not None:
+        opts = self.request_options(**options)
+        if stream and infer.needs_whole_wave(opts, streamed=True):
+            raise ValueError(STREAM_REMOVE_SILENCE)
+        voice, ref_text = resolve_voice()
+        if stream:
+            chunks = infer.request_chunks(ref_text, voice.seconds, text)
+            if "seed" in opts:
+                opts["generator"] = infer.request_generator(opts.pop("seed"))
+            return self._stream(voice, ref_text, chunks[:1], chunks[1:], opts)
+        req = self._request(voice, ref_text, text, opts)
+        if self.batcher is not None:   # wait for the batch this request rides in (the route runs in a worker thread, see create_app)
             return self.batcher.submit(req).result(timeout=self.request_timeout_s)
         return self._run_batch([req])[0]
 
-    def synthesize_clip_stream(self, text, ref_audio, ref_text, *, clip_short=True, speed=None, nfe_step=None, cfg_strength=None,
-                               sway_sampling_coef=None, seed=None, ode_method=None, remove_silence=None, sample_rate=None, encoding=None):
+    def synthesize_clip(self, text, ref_audio, ref_text, *, clip_short=True, **options):
+        """`synthesize` with the caller's own reference clip instead of a registered voice: `ref_audio` is a WAV file's bytes or a
+        (wave [ch, n], sr) pair, `ref_text` its transcript; `clip_short` as in `preprocess_ref_audio_text`.  The clip never touches the
+        disk (`_clip_voice`); the request then takes the same batcher path as `synthesize`, with the same options."""
+        return self._serve(lambda: self._clip_voice(ref_audio, ref_text, clip_short), text, options)
+
+    def synthesize_clip_stream(self, text, ref_audio, ref_text, *, clip_short=True, **options):
         """`synthesize_stream` with an uploaded reference clip (`synthesize_clip`): an iterator of pieces (float32; in the delivery format
         with `sample_rate` / `encoding`) whose concatenation is `synthesize_clip`'s wave given the same noise."""
-        if not self.model:
-            raise ValueError("TTS model not loaded")
-        opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                    ode_method=ode_method, remove_silence=remove_silence, sample_rate=sample_rate, encoding=encoding)
-        if opts.get("remove_silence"):
-            raise ValueError(STREAM_REMOVE_SILENCE)
-        voice, ref_text_n = self._clip_voice(ref_audio, ref_text, clip_short)
-        chunks = infer.request_chunks(ref_text_n, voice.seconds, text)
-        if "seed" in opts:
-            opts["generator"] = infer.request_generator(opts.pop("seed"))
-        return self._stream(voice, ref_text_n, chunks[:1], chunks[1:], opts)
+        return self._serve(lambda: self._clip_voice(ref_audio, ref_text, clip_short), text, options, stream=True)
 
-    def synthesize(self, text, ref_audio_path, ref_text, *, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None, seed=None,
-                   ode_method=None, remove_silence=None, sample_rate=None, encoding=None):
-        """The wave of one request.  The sampler options are this request's own (None: `self.opts`); `seed` draws its noise from its own
+    def synthesize(self, text, ref_audio_path, ref_text, **options):
+        """The wave of one request.  `options`: any of `infer.REQUEST_OPTIONS`, by keyword -- a name that is not among them is refused by
+        `request_options` with ValueError (not the interpreter's TypeError: the four `synthesize*` methods take `**options`).  The sampler
+        options (`speed`, `nfe_step`, `cfg_strength`, `sway_sampling_coef`) are this request's own (None: `self.opts`); `seed` draws its noise from its own
         generator (`infer.request_generator`), so the same seeded request gives the same audio whatever it is batched with (shape-invariant
         attention, one GPU).  `ode_method` ("euler", "midpoint", "rk4"; None: the model's): requests of different solvers share a batch, and
         the option reaches the model object only for a request that sets it.  `remove_silence=True`: the reference's
@@ -615,12 +609,9 @@ class TTSManager:
         either way; 24000 and "pcm16" (or None) change nothing."""
         if not self.model:
             raise ValueError("TTS model not loaded")
-        opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                    ode_method=ode_method, remove_silence=remove_silence, sample_rate=sample_rate, encoding=encoding)
-        return self.model(text, ref_audio_path=ref_audio_path, ref_text=ref_text, **opts)
+        return self.model(text, ref_audio_path=ref_audio_path, ref_text=ref_text, **options)   # (`_call`, which checks the options)
 
-    def synthesize_stream(self, text, ref_audio_path, ref_text, *, speed=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
-                          seed=None, ode_method=None, remove_silence=None, sample_rate=None, encoding=None):
+    def synthesize_stream(self, text, ref_audio_path, ref_text, **options):
         """`synthesize` as an iterator of float32 pieces (24 kHz) whose concatenation is `synthesize`'s wave given the same noise (see
         `infer.infer_process_stream`).  The request's first chunk is synthesized on its own and its stable samples come out as soon as it is
         done; the remaining chunks follow as a second request.  With a micro-batcher the first chunk rides in the next batch and the
@@ -631,18 +622,8 @@ class TTSManager:
         pieces equal `synthesize`'s wave with that seed.  The remaining chunks keep the first chunk's `ode_method`.  With `sample_rate` /
         `encoding` the pieces come in the delivery format (int16 at that rate, or uint8 code bytes): each float32 piece goes through
         `infer.quantise_pcm16`, an `infer.StreamResampler` and the encoder on the host, and their concatenation equals `synthesize`'s result
-        with the same options byte for byte."""
-        if not self.model:
-            raise ValueError("TTS model not loaded")
-        opts = self.request_options(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                    ode_method=ode_method, remove_silence=remove_silence, sample_rate=sample_rate, encoding=encoding)
-        if opts.get("remove_silence"):   # removal needs the whole wave
-            raise ValueError(STREAM_REMOVE_SILENCE)
-        voice, ref_text_n = self._voice(ref_audio_path, ref_text)
-        chunks = infer.request_chunks(ref_text_n, voice.seconds, text)
-        if "seed" in opts:   # head and tail continue one sequence; the tail's batch runs after the head's (one worker, one batch at a time)
-            opts["generator"] = infer.request_generator(opts.pop("seed"))
-        return self._stream(voice, ref_text_n, chunks[:1], chunks[1:], opts)
+        with the same options byte for byte.  `remove_silence` needs the whole wave: ValueError."""
+        return self._serve(lambda: self._voice(ref_audio_path, ref_text), text, options, stream=True)
 
     def _stream(self, voice, ref_text, head, tail, opts=None):
         lock, state = threading.Lock(), {"closed": False, "tail": None, "error": None}
@@ -732,60 +713,6 @@ class TTSManager:
         return infer.deliver_pcm16(infer.quantise_pcm16(wave), fmt.get("sample_rate"), fmt.get("encoding")) if fmt else wave
 
 
-_G711_TAGS = {"mulaw": 7, "alaw": 6}   # WAVE_FORMAT_MULAW, WAVE_FORMAT_ALAW
-
-
-def _g711_header(encoding, sample_rate, n, riff_size, data_size):
-    """RIFF header of a mono G.711 WAV: an 18-byte `fmt ` chunk (format tag 7 / 6, 8 bits per sample, block align 1, byte rate = sample rate,
-    cbSize 0), a `fact` chunk with the sample count, and the `data` chunk's header."""
-    return (b"RIFF" + struct.pack("<I", riff_size) + b"WAVE" + b"fmt " + struct.pack("<IHHIIHHH", 18, _G711_TAGS[encoding], 1, sample_rate, sample_rate, 1, 8, 0)
-            + b"fact" + struct.pack("<II", 4, n) + b"data" + struct.pack("<I", data_size))
-
-
-def delivery_bytes(audio, encoding: str = "pcm16") -> bytes:
-    """The body bytes of samples in any of the forms a request's result takes: uint8 G.711 codes as they are, int16 PCM little-endian, float
-    samples by `pcm16`'s rule -- and, for a G.711 `encoding`, PCM that is not encoded yet through `infer.encode_g711`."""
-    a = np.asarray(audio)
-    if a.dtype == np.uint8:
-        return a.tobytes()
-    if a.dtype != np.int16:
-        a = infer.quantise_pcm16(a)
-    if encoding != "pcm16":
-        return infer.encode_g711(a, encoding).tobytes()
-    return a.astype("<i2").tobytes()
-
-
-def wav_bytes(audio: np.ndarray, sample_rate: int = infer.target_sample_rate, encoding: str = "pcm16") -> io.BytesIO:
-    """A mono WAV file of `audio` (`delivery_bytes`) at `sample_rate`: 16-bit PCM, or G.711 (`_g711_header`) for "mulaw" / "alaw"."""
-    if encoding not in infer.OUTPUT_ENCODINGS:
-        raise ValueError(f"encoding must be one of {list(infer.OUTPUT_ENCODINGS)} (got {encoding!r})")
-    body = delivery_bytes(audio, encoding)
-    buf = io.BytesIO()
-    if encoding == "pcm16":
-        with _wave.open(buf, "wb") as f:
-            f.setnchannels(1); f.setsampwidth(2); f.setframerate(sample_rate)
-            f.writeframes(body)
-    else:
-        pad = len(body) & 1                      # chunks are word-aligned
-        buf.write(_g711_header(encoding, sample_rate, len(body), 4 + 26 + 12 + 8 + len(body) + pad, len(body)) + body + b"\x00" * pad)
-    buf.seek(0)
-    return buf
-
-
-def pcm16(audio: np.ndarray) -> bytes:
-    """Little-endian int16 PCM bytes of float samples, by `wav_bytes`'s rule: rint(x * 32768), clipped."""
-    return infer.quantise_pcm16(audio).astype("<i2").tobytes()
-
-
-def wav_stream_header(sample_rate: int = infer.target_sample_rate, encoding: str = "pcm16") -> bytes:
-    """Header of a mono WAV of unknown length: RIFF and `data` sizes are 0xFFFFFFFF (the usual streaming-WAV convention; players read to the
-    end of the stream).  16-bit PCM: 44 bytes; G.711: 58 bytes, the `fact` chunk's sample count 0xFFFFFFFF too."""
-    if encoding != "pcm16":
-        return _g711_header(encoding, sample_rate, 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF)
-    return (b"RIFF" + struct.pack("<I", 0xFFFFFFFF) + b"WAVE" + b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, sample_rate, sample_rate * 2, 2, 16)
-            + b"data" + struct.pack("<I", 0xFFFFFFFF))
-
-
 class HTTPError(Exception):
     """Carries (status_code, detail) out of `synthesize_speech`; the route turns it into fastapi.HTTPException."""
 
@@ -842,6 +769,51 @@ def stream_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, r
     return tts_manager.synthesize_stream(text, ref_audio_path=voice.audio_path, ref_text=ref_text, **options)
 
 
+def request_models():
+    """The routes' request models by name (`create_app`): pydantic is imported here, on first use, like fastapi is there."""
+    from pydantic import BaseModel
+
+    class SamplerFields(BaseModel):                  # per-request sampler settings; None = the manager's (TTSManager.opts)
+        nfe_step: int | None = None
+        cfg_strength: float | None = None
+        sway_sampling_coef: float | None = None
+        seed: int | None = None
+        ode_method: str | None = None
+        sample_rate: int | None = None               # the delivery format (infer.deliver_pcm16); None = 24 kHz 16-bit PCM in a WAV
+        encoding: str | None = None
+        response_format: str | None = None
+
+    class SpeechFields(SamplerFields):               # what the three speech routes take on top: with SamplerFields, every infer.REQUEST_OPTIONS name
+        speed: float | None = None
+        remove_silence: bool | None = None
+
+    class KannadaSynthesizeRequest(SpeechFields):    # S/utils/tts_utils.py:27-28
+        text: str
+        stream: bool = False
+
+    class SynthesizeRequest(SpeechFields):           # S/utils/tts_utils.py:22-25
+        text: str
+        ref_audio_name: str
+        ref_text: str | None = None
+        stream: bool = False
+
+    class EditRequest(SamplerFields):                # F/infer/speech_edit.py's inputs; JSON (base64 WAV), not multipart
+        audio: str
+        text: str
+        parts_to_edit: list[list[float]]
+        fix_duration: list[float] | None = None
+
+    class CloneRequest(SpeechFields):                # zero-shot cloning from the caller's own clip; JSON (base64 WAV), not multipart
+        text: str
+        ref_audio: str
+        ref_text: str
+        clip_short: bool = True
+        stream: bool = False
+
+    return types.SimpleNamespace(KannadaSynthesizeRequest=KannadaSynthesizeRequest, SynthesizeRequest=SynthesizeRequest, CloneRequest=CloneRequest,
+                                 EditRequest=EditRequest)
+
+
 def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     """FastAPI app with the reference's `/v1/audio/speech` route (`S/routes/speech.py:19-41`) and `/v1/audio/edit` (speech editing:
     JSON body {"audio": base64 WAV, "text": the full new transcript, "parts_to_edit": [[start_s, end_s], ...], "fix_duration": [...] | null}
@@ -855,47 +827,9 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     `infer.OUTPUT_SAMPLE_RATES`), `encoding` ("pcm16", "mulaw" or "alaw": G.711, one byte per sample) and `response_format` ("wav", or "pcm"
     for the headerless samples / code bytes as `audio/pcm`); streamed or not, the body's samples are the same bytes."""
     from fastapi import APIRouter, FastAPI, HTTPException
-    from pydantic import BaseModel
     from starlette.responses import StreamingResponse
 
-    class SamplerFields(BaseModel):                  # per-request sampler settings; None = the manager's (TTSManager.opts)
-        nfe_step: int | None = None
-        cfg_strength: float | None = None
-        sway_sampling_coef: float | None = None
-        seed: int | None = None
-        ode_method: str | None = None
-        sample_rate: int | None = None               # the delivery format (infer.deliver_pcm16); None = 24 kHz 16-bit PCM in a WAV
-        encoding: str | None = None
-        response_format: str | None = None
-
-    class KannadaSynthesizeRequest(SamplerFields):   # S/utils/tts_utils.py:27-28
-        text: str
-        stream: bool = False
-        speed: float | None = None
-        remove_silence: bool | None = None
-
-    class SynthesizeRequest(SamplerFields):          # S/utils/tts_utils.py:22-25
-        text: str
-        ref_audio_name: str
-        ref_text: str | None = None
-        stream: bool = False
-        speed: float | None = None
-        remove_silence: bool | None = None
-
-    class EditRequest(SamplerFields):                # F/infer/speech_edit.py's inputs; JSON (base64 WAV), not multipart
-        audio: str
-        text: str
-        parts_to_edit: list[list[float]]
-        fix_duration: list[float] | None = None
-
-    class CloneRequest(SamplerFields):               # zero-shot cloning from the caller's own clip; JSON (base64 WAV), not multipart
-        text: str
-        ref_audio: str
-        ref_text: str
-        clip_short: bool = True
-        stream: bool = False
-        speed: float | None = None
-        remove_silence: bool | None = None
+    models = request_models()
 
     def _options(req, allowed):
         """The request's sampler fields, checked (400) before anything is queued."""
@@ -929,7 +863,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
         opts = _options(req, infer.REQUEST_OPTIONS)
-        if req.stream and opts.get("remove_silence"):
+        if req.stream and infer.needs_whole_wave(opts, streamed=True):
             raise HTTPException(status_code=400, detail=STREAM_REMOVE_SILENCE)
         if not text.strip():
             raise HTTPException(status_code=400, detail="Text to synthesize cannot be empty.")
@@ -1018,21 +952,21 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     from starlette.concurrency import run_in_threadpool
 
     @router.post("/audio/speech", response_class=StreamingResponse)
-    async def synthesize_kannada(request: KannadaSynthesizeRequest):
+    async def synthesize_kannada(request: models.KannadaSynthesizeRequest):
         return await run_in_threadpool(_run_stream if request.stream else _run, request.text, registry.default_voice, None,
                                        "synthesized_kannada_speech.wav", request)
 
     @router.post("/audio/speech/voice", response_class=StreamingResponse)
-    async def synthesize_with_voice(request: SynthesizeRequest):     # the generic form the reference's helper already supports
+    async def synthesize_with_voice(request: models.SynthesizeRequest):     # the generic form the reference's helper already supports
         return await run_in_threadpool(_run_stream if request.stream else _run, request.text, request.ref_audio_name, request.ref_text,
                                        "synthesized_speech.wav", request)
 
     @router.post("/audio/speech/clone", response_class=StreamingResponse)
-    async def synthesize_with_clip(request: CloneRequest):          # the caller's own reference clip (TTSManager.synthesize_clip)
+    async def synthesize_with_clip(request: models.CloneRequest):          # the caller's own reference clip (TTSManager.synthesize_clip)
         return await run_in_threadpool(_run_clone, request)
 
     @router.post("/audio/edit", response_class=StreamingResponse)
-    async def edit_speech(request: EditRequest):                    # speech editing (F/infer/speech_edit.py) over the same manager
+    async def edit_speech(request: models.EditRequest):                    # speech editing (F/infer/speech_edit.py) over the same manager
         return await run_in_threadpool(_run_edit, request)
 
     app = FastAPI(title="F5-TTS on MI355X (HIP path)")
