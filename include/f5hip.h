@@ -67,7 +67,9 @@ int f5hip_dit_forward(f5hip_dit* m, int32_t n_seq, const int32_t* seq_len, const
                       float* out_dev, float* h_out_dev, void* stream);
 
 /* Copies an internal fp32 activation of the last forward for parity taps: "text_embed" -> [sum(seq_len)][text_dim]; "text_rows" (MMDiT) ->
- * the text stream's embedding as laid out, [text rows][text_dim] with every sequence's nt_max tokens padded to a multiple of 128 rows. */
+ * the text stream's embedding as laid out, [text rows][text_dim] with every sequence's nt_max tokens padded to a multiple of 128 rows;
+ * "text_stream" (MMDiT) -> the text residual stream behind the blocks that forward ran (n_blocks; its embedding for 0), [text rows][dim] in the
+ * same layout.  Behind the last, context-pre-only block the stream is dropped: the rows then still hold what the block before it left. */
 int f5hip_dit_read_tap(f5hip_dit* m, const char* tap, float* dst_dev, int64_t numel, void* stream);
 
 /* The ODE loop of CFM.sample (F/model/cfm.py:160-204): Euler over t_grid with classifier-free guidance,

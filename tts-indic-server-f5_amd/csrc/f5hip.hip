@@ -1034,6 +1034,13 @@ int f5hip_dit_read_tap(f5hip_dit* m, const char* tap, float* dst_dev, int64_t nu
             return fail(-6, "read_tap: copy");
         return 0;
     }
+    if (!strcmp(tap, "text_stream")) {   // MMDiT: the text residual stream behind the blocks the last forward ran, rows laid out like "text_rows"
+        const size_t n = (size_t)m->Mc * m->cfg.dim;
+        if (m->arch != 2 || numel != (int64_t)n) return fail(-1, "read_tap: text_stream needs an MMDiT handle and numel = text rows x dim");
+        if (hipMemcpyAsync(dst_dev, m->h + (size_t)m->row_c0 * m->cfg.dim, n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+            return fail(-6, "read_tap: copy");
+        return 0;
+    }
     return fail(-1, "unknown tap %s", tap);
 }
 
