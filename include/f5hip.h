@@ -110,8 +110,8 @@ int f5hip_cfm_sample_units(f5hip_dit* m, int32_t n_utt, const int32_t* dur, cons
  * every ODE method and backbone, a unit's result is what f5hip_cfm_sample_units (or _masked) gives it alone with its grid and strength as
  * the call's; when all units share one grid, the call IS f5hip_cfm_sample_units.  The union of the units' time points (Euler: steps[u]
  * per unit, midpoint: 2 steps[u], RK4: 3 steps[u] + 1; equal values once) may hold at most 256 points -- checked before anything is
- * launched.  The call runs max(steps) iterations; a unit whose steps are done is frozen and leaves the layout (counter "dit_rows": the
- * summed backbone rows of the forwards). */
+ * launched.  The call runs the forwards of the unit with the most steps; a unit whose steps are done is frozen and leaves the layout
+ * (counter "dit_rows": the summed backbone rows of the forwards). */
 int f5hip_cfm_sample_grids(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const int32_t* kv_len, const float* cond_dev,
                            const uint8_t* cond_mask, const int32_t* text, int32_t nt_max, const float* y0_dev,
                            const int32_t* steps, const float* t_grids, const float* cfg_strength, float* out_dev, void* stream);
@@ -142,7 +142,7 @@ int f5hip_cfm_sample_span(f5hip_dit* m, int32_t n_utt, const int32_t* dur, const
  * unchanged.  `last` as in f5hip_cfm_sample_span; NULL = every unit ends (f5hip_cfm_sample_grids' result).
  *   Unit u takes F_u = steps[u] * (1, 2 or 4) backbone forwards.  The units are laid out by F_u, descending, and the call runs max F_u
  *   forwards: before forward f the layout shrinks to the units with F_u > f (counter "dit_rows"), and after it ONE launch steps every frame
- *   by the rule and stage its unit is at -- the arithmetic of the one-method kernels, operation for operation.
+ *   by the rule and stage its unit is at -- the one update kernel of every sampler call, here with op and step size per unit.
  *   The union of the units' time points, each by its own rule (Euler steps[u], midpoint 2 steps[u], RK4 3 steps[u] + 1; equal values once),
  *   may hold at most 256 points.  RK4's fourth stage of a unit's last step is evaluated at its slice's last point.
  * When all method[u] are equal the call IS f5hip_cfm_sample_span / _grids on a handle set to that method: same kernels, same bits.  With
@@ -257,8 +257,8 @@ int f5hip_op_layernorm(int32_t M, int32_t D, const float* x_dev, const float* sc
 int f5hip_op_layernorm_planes(int32_t M, int32_t D, const float* x_dev, const float* scale_dev, const float* shift_dev,
                               const int32_t* row_mod_host, int32_t mod_ld, int32_t n_mod_rows, float gain_off, float eps, int32_t out_format,
                               float* out_dev, void* stream);
-/* f5hip_op_cfg_step: one launch of the sampler's CFG combine + ODE update, v = p_c + (p_c - p_u) cfg (v = p_c for a frame without an
- *   unconditional row), on the caller's buffers.  U frames of mel channels; pred_dev fp32 [rows][128] the backbone output, urow_c_host /
+/* f5hip_op_cfg_step: one launch of the sampler's CFG combine + ODE update (cfg_step_kernel), v = p_c + (p_c - p_u) cfg (v = p_c for a
+ *   frame without an unconditional row), on the caller's buffers.  U frames of mel channels; pred_dev fp32 [rows][128] the backbone output, urow_c_host /
  *   urow_u_host int32 [U] (host) the conditional / unconditional row of every frame (urow_u -1: none).
  *   method 0: xout = xbase + dt v (xout_dev == xbase_dev: the Euler step in place; distinct: the midpoint rule's half step, xbase
  *   untouched); method 2: stage `stage` + 1 (stage 0..3) of the fixed-grid RK4 step (3/8 rule) in place on xbase_dev, stage slopes in
@@ -273,9 +273,9 @@ int f5hip_op_cfg_step(int32_t method, int32_t stage, int32_t U, int32_t mel, int
                       float dt, const int32_t* frame_unit_host, const float* unit_dt_host, int32_t n_units, int32_t n_act, float* k1_dev,
                       float* k2_dev, float* k3_dev, float* xs_dev, const uint8_t* final_flags_host, const float* cond_dev, float* out_dev,
                       void* stream);
-/* f5hip_op_cfg_mixed: one launch of the CFG combine + ODE update of a mixed-method sampler call (f5hip_cfm_sample_methods), in which
- *   every frame is stepped by the rule of its unit.  Buffers as in f5hip_op_cfg_step (strengths per frame: cfg_frame_dev [U]; in place on
- *   xstate_dev).  frame_unit_host int32 [U]; unit_op_host int32 / unit_dt_host fp32 [n_units] (host): per unit the op code and step size --
+/* f5hip_op_cfg_mixed: one launch of the same kernel as a sampler call with per-unit grids or methods launches it (f5hip_cfm_sample_grids,
+ *   _span, _methods), in which every frame is stepped by this forward's op of its unit.  Buffers as in f5hip_op_cfg_step (strengths per
+ *   frame: cfg_frame_dev [U]; in place on xstate_dev).  frame_unit_host int32 [U]; unit_op_host int32 / unit_dt_host fp32 [n_units] (host): per unit the op code and step size --
  *   0 none (frame untouched), 1 Euler step, 2 midpoint half step (unit_dt holds dt / 2; xstate untouched, the next input goes to xs and
  *   to the frame's rows of k1_dev), 3 midpoint full step, 4..7 RK4 stage 1..4 (slopes in k1_dev / k2_dev / k3_dev [U][mel]).  The
  *   frames of units >= n_act are left as they are.  Per op code the result is f5hip_op_cfg_step's of that method / stage, bit for bit. */

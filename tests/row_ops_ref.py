@@ -1,5 +1,5 @@
 """fp64 references shared by tests/test_gpu_row_ops.py (GPU) and tests/test_row_ops_reference.py (CPU, which pins them): the 16-bit
-operand formats of csrc/common.h and the CFG + ODE step formulas written above cfg_euler_kernel / cfg_rk4_stage_kernel
+operand formats of csrc/common.h and the CFG + ODE step formulas written above cfg_step_kernel
 (csrc/elementwise.h)."""
 import torch
 

@@ -2,7 +2,7 @@
 F5HipModel.sample / sample_units / plan_unit).  A unit stepped by its own solver inside a mixed-method call equals the same unit sampled
 alone, through the one-method path, on a handle built with that solver, bit for bit (shape-invariant attention), for DiT, UNetT and MMDiT,
 whole grids and spans, and stays within north_star's 1e-3 RMS of the CPU oracle's sampler; units whose forwards are done stop costing
-backbone rows ("dit_rows"); cfg_mixed_kernel alone against fp64 and against the one-method kernels; the serving manager samples requests
+backbone rows ("dit_rows"); the per-unit instance of cfg_step_kernel alone against fp64 and against the one-op instance; the serving manager samples requests
 of different solvers in one call."""
 import ctypes as C
 import os
@@ -234,7 +234,7 @@ def test_cfm_sample_methods_torch_op_equals_ctypes_and_checks_arguments(attn_sha
     assert torch.equal(via_op, out)
 
 
-# ---------------------------------------------------------------------------------------------------------------- cfg_mixed_kernel alone
+# ---------------------------------------------------------------------------------------------------------------- cfg_step_kernel<per unit> alone
 DEV = "cuda"
 MEL, ROWS = 100, 64
 EPS16 = 16 * 2.0 ** -24           # tests/test_gpu_row_ops.py: at most 16 rounded fp32 operations, each relative to a partial sum bounded by S
@@ -266,7 +266,7 @@ def _mixed_layout(frames):
 
 @pytest.mark.parametrize("case", list(MIXED_CASES))
 def test_cfg_mixed_kernel_vs_fp64_and_one_method_kernels(case):
-    """One launch of cfg_mixed_kernel through f5hip_op_cfg_mixed: every stepped element against the fp64 formulas of tests/row_ops_ref.py on
+    """One launch of the per-unit instance of cfg_step_kernel through f5hip_op_cfg_mixed: every stepped element against the fp64 formulas of tests/row_ops_ref.py on
     the same fp32 inputs, |got - ref| <= 16 x 2^-24 x S (S: the absolute sum of the fp64 expression's terms; the bound derived in
     tests/test_gpu_row_ops.py), plus the split's 2^-16 |ref| where x_next exists only in xs; frames with op "none" or of a unit >= n_act,
     and every cell no frame owns, keep what they held; and per op code the frames are bit-equal to f5hip_op_cfg_step of that method /

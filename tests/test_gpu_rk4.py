@@ -1,4 +1,4 @@
-"""GPU: the fixed-grid RK4 solver (CFM(odeint_kwargs=dict(method="rk4")), f5hip_dit_set_ode_method(h, 2): cfg_rk4_stage_kernel, four
+"""GPU: the fixed-grid RK4 solver (CFM(odeint_kwargs=dict(method="rk4")), f5hip_dit_set_ode_method(h, 2): cfg_step_kernel's RK4 ops, four
 backbone evaluations per step) against the CPU RK4 sampler of tests/rk4_oracle.py, for all three backbones and every entry point.  The
 rule itself is pinned by tests/test_rk4_rule.py (torchdiffeq is absent: unpinned leaf).  Tolerances: north_star's 1e-3 RMS on mel frames."""
 import numpy as np

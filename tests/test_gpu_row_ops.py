@@ -270,8 +270,8 @@ def _check_xs(xs, want_rows, act, exact, tol=None):
 @pytest.mark.parametrize("form", ["scalar", "frame", "unit"])
 @pytest.mark.parametrize("step", STEPS)
 def test_cfg_step_kernels(step, form):
-    """One launch of cfg_euler_kernel (in place, and the midpoint rule's half step into another buffer) and of each stage of
-    cfg_rk4_stage_kernel, in the scalar-strength, per-frame-strength and per-unit-dt (n_act = 2 of 4 units) forms, against the fp64
+    """One launch of cfg_step_kernel per op -- the Euler step in place, the midpoint rule's half step into another buffer and each stage of
+    RK4 --, in the scalar-strength, per-frame-strength and per-unit-dt (n_act = 2 of 4 units) forms, against the fp64
     formulas on the same fp32 inputs.  Elementwise |got - ref| <= 16 x 2^-24 x S, S the sum of the absolute values of every term of the
     fp64 expression; xs of stages 1..3 (x_next exists nowhere else) to that bound plus the split's 2^-16 |ref|."""
     st = _StepState(1000 + STEPS.index(step))
@@ -318,7 +318,9 @@ def test_cfg_step_kernels(step, form):
 @pytest.mark.parametrize("step", STEPS)
 def test_cfg_step_forms_agree(step):
     """The scalar form with strength c is the per-frame form with cfg_frame == c, and the per-unit-dt form with every unit_dt equal and all
-    units active is the per-frame form, bit for bit in every buffer."""
+    units active is the per-frame form, bit for bit in every buffer.  With n_act = 2 of the 4 units the per-unit form is the per-frame form
+    on the active units' frames, bit for bit in every buffer, and leaves the idle units' frames of every buffer as they were: the prefix
+    shrink every sampler call with per-unit columns relies on."""
     st = _StepState(2000 + STEPS.index(step))
     same = lambda a, b: all(torch.equal(a[n], b[n]) for n in ("x", "xout", "xs")) and all(torch.equal(p, q) for p, q in zip(a["k"], b["k"]))
     scalar = st.run(step, "scalar")
@@ -329,6 +331,21 @@ def test_cfg_step_forms_agree(step):
     unit = st.run(step, "unit", cfg_frame=cfg_frame, unit_dt=(DT_SCALAR,) * 4, n_act=4)
     assert same(frame, unit)
     assert not same(scalar, frame)
+    part = st.run(step, "unit", cfg_frame=cfg_frame, unit_dt=(DT_SCALAR,) * 4, n_act=2)
+    act = torch.from_numpy(FUNIT < 2)
+    before = dict(x=st.x, xout=torch.full_like(st.x, XOUT_SENTINEL) if step == "half" else st.x)
+    for name, got, full, was in [(n, part[n], frame[n], before[n]) for n in ("x", "xout")] + \
+            [(f"k{j + 1}", part["k"][j], frame["k"][j], st.k[j]) for j in range(3)]:
+        assert torch.equal(got[act], full[act]), f"{name}: active frames differ from the per-frame form"
+        assert torch.equal(got[~act], was[~act]), f"{name}: idle frames touched"
+    for rows in (URC, URU):
+        r = torch.from_numpy(rows).long()
+        on, off = r[act & (r >= 0)], r[~act & (r >= 0)]
+        assert torch.equal(part["xs"][on], frame["xs"][on]), "xs: active frames differ from the per-frame form"
+        assert (part["xs"][off] == XS_SENTINEL).all(), "xs: idle frames touched"
+    owned = torch.zeros(ROWS, dtype=torch.bool)
+    owned[torch.from_numpy(np.concatenate([URC, URU[URU >= 0]])).long()] = True
+    assert (part["xs"][~owned] == XS_SENTINEL).all(), "xs: rows of no frame touched"
 
 
 @pytest.mark.parametrize("form", ["scalar", "frame", "unit"])

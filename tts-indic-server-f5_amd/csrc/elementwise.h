@@ -1,5 +1,5 @@
 // HBM/L2-bound row kernels of the DiT / Vocos paths: LayerNorm (+AdaLN modulation, + optional depthwise
-// conv k=7 in front), GRN, embedding gather, CFG + Euler update, packing helpers.  One wave (64 lanes) per
+// conv k=7 in front), GRN, embedding gather, CFG + ODE update, packing helpers.  One wave (64 lanes) per
 // row, float4 loads, wave-shuffle reductions, fp32 statistics, split-bf16 outputs that feed the MFMA GEMMs.
 #pragma once
 #include "common.h"
@@ -124,18 +124,20 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* x, int ldx
 }
 
 // ------------------------------------------------------------------------------------------------
-// CFG combine + Euler step (F/model/cfm.py:176 and torchdiffeq fixed-grid Euler):
-//   v = p + (p - p0) * cfg ;  x += dt * v
-// pred: [M_pad][ldp] rows of the conditional branch at row_c[u], unconditional at row_u[u] (or -1).
-// Also refreshes the split-bf16 copy of x that feeds the next step's input projection for both branches.
-// xout = xbase + dt * v: xout == xbase for an Euler step; the midpoint rule writes its half step to a scratch state and takes the full
-// step from the untouched xbase.
-// kFrameCfg: the strength of frame u is cfg_frame[u] (f5hip_cfm_sample_units: one strength per unit, spread over its frames) instead of
-// the scalar `cfg`; the arithmetic is the same, so the scalar instantiation is the kernel the single-strength entry points always ran.
-// kUnitDt (f5hip_cfm_sample_grids): the step of frame u is unit_dt[frame_unit[u]], and the frames of units >= n_act (their steps are done)
-// are left as they are.
-// The arithmetic of the CFG / ODE kernels below, one helper per piece: cfg_euler_kernel, cfg_rk4_stage_kernel and cfg_mixed_kernel are built
-// from the same expressions, so a frame gets the same bits whichever of them steps it.
+// CFG combine + ODE update (F/model/cfm.py:176 and torchdiffeq's fixed-grid solvers): v = p + (p - p0) * cfg, then one op of a solver (CfgOp).
+// pred: [M_pad][ldp] rows of the conditional branch at urow_c[u], unconditional at urow_u[u] (or -1).
+// Every op also refreshes the split-bf16 copy of x that feeds the next forward's input projection, for both branches.
+// What cfg_step_kernel does to a frame after one forward
+enum CfgOp : int {
+    CFG_OP_NONE = 0,       // the unit's steps are done: its frames are left as they are
+    CFG_OP_EULER = 1,      // x += dt v
+    CFG_OP_MID_HALF = 2,   // midpoint, first forward: k1 = x + dt v (dt is half the step), x untouched
+    CFG_OP_MID_FULL = 3,   // midpoint, second forward: x += dt v
+    CFG_OP_RK4_1 = 4,      // RK4 stage 1 .. 4: CFG_OP_RK4_1 + stage - 1
+    CFG_OP_COUNT = 8
+};
+
+// The arithmetic of cfg_step_kernel, one helper per piece.
 // v = p_c + (p_c - p_u) * cfg for channel c of a frame (v = p_c without an unconditional row)
 __device__ __forceinline__ float cfg_velocity(const float* pred, int ldp, int rc, int ru, int c, float cfg) {
     const float pc = pred[(size_t)rc * ldp + c];
@@ -151,8 +153,14 @@ __device__ __forceinline__ float euler_update(float* xout, const float* xbase, s
     return xn;
 }
 
-// Stage `stage` (1..4) of the RK4 step on element i (see cfg_rk4_stage_kernel): keeps k_stage, returns the next forward's input (stage 4: y1,
-// written to xstate)
+// Stage `stage` (1..4) of the fixed-grid RK4 step on element i (torchdiffeq method="rk4": rk4_alt_step_func, the 3/8 rule), after the forward
+// of that stage of the interval [t0, t0 + dt]:
+//   1: k1 = v(t0, y0)             next input y0 + dt * k1 / 3
+//   2: k2 = v(t0 + dt/3, ..)      next input y0 + dt * (k2 - k1 / 3)
+//   3: k3 = v(t0 + 2 dt/3, ..)    next input y0 + dt * (k1 - k2 + k3)
+//   4: k4 = v(t0 + dt, ..)        y1 = y0 + (k1 + 3 (k2 + k3) + k4) * dt / 8
+// Stages 1-3 keep k_s in their [U][mel] buffer and return the next stage's input, which goes only to the split-bf16 copy of x; xstate holds
+// y0 until stage 4 writes y1 there.
 __device__ __forceinline__ float rk4_stage_update(float* xstate, float* k1, float* k2, float* k3, size_t i, int stage, float dt, float v) {
     const float y0 = xstate[i];
     float xn;
@@ -184,83 +192,27 @@ __device__ __forceinline__ void store_x_split(__bf16* xs_hi, __bf16* xs_lo, int 
     }
 }
 
-template <bool kFrameCfg, bool kUnitDt = false>
-__global__ __launch_bounds__(128) void cfg_euler_kernel(float* xout /*[U][mel]*/, const float* xbase, int mel, int U, const float* pred,
-                                                        int ldp, const int* urow_c, const int* urow_u, float cfg, const float* cfg_frame,
-                                                        float dt, __bf16* xs_hi, __bf16* xs_lo, int ldx, const int* frame_unit,
-                                                        const float* unit_dt, int n_act) {
+// The one update kernel of the sampler, launched once after every forward: one block per frame, the frame's strength from cfg_frame[u].
+// kPerUnit = false: every frame takes the op `op` (CfgOp) with step size `dt`.  kPerUnit = true: frame u takes unit_op[frame_unit[u]] and
+// unit_dt[frame_unit[u]], this forward's op and step size of its unit by layout position; the frames of units >= n_act, or with
+// CFG_OP_NONE, are left as they are.  The op is uniform over a block, so no wave diverges.  k1 is the midpoint rule's scratch state as well
+// as RK4's first slope, indexed by frame like k2 / k3: the frames of different units are disjoint, so units of different methods share them.
+template <bool kPerUnit>
+__global__ __launch_bounds__(128) void cfg_step_kernel(float* xstate /*[U][mel]*/, int mel, int U, const float* pred, int ldp, const int* urow_c,
+                                                       const int* urow_u, const float* cfg_frame, int op, float dt, float* k1, float* k2, float* k3,
+                                                       __bf16* xs_hi, __bf16* xs_lo, int ldx, const int* frame_unit, const int* unit_op,
+                                                       const float* unit_dt, int n_act) {
     const int u = blockIdx.x;
     if (u >= U) return;
     const int c = threadIdx.x;
     if (c >= mel) return;
-    if (kUnitDt) {
+    if (kPerUnit) {
         const int un = frame_unit[u];
         if (un >= n_act) return;
+        op = unit_op[un];
         dt = unit_dt[un];
     }
-    const int rc = urow_c[u], ru = urow_u[u];
-    const float v = cfg_velocity(pred, ldp, rc, ru, c, kFrameCfg ? cfg_frame[u] : cfg);
-    const float xn = euler_update(xout, xbase, (size_t)u * mel + c, dt, v);
-    store_x_split(xs_hi, xs_lo, ldx, rc, ru, c, xn);
-}
-
-// CFG combine + one stage of the fixed-grid RK4 step (torchdiffeq method="rk4": rk4_alt_step_func, the 3/8 rule), launched after the
-// forward of stage s = 1..4 of the interval [t0, t0 + dt]:
-//   s = 1: k1 = v(t0, y0)             next input y0 + dt * k1 / 3
-//   s = 2: k2 = v(t0 + dt/3, ..)      next input y0 + dt * (k2 - k1 / 3)
-//   s = 3: k3 = v(t0 + 2 dt/3, ..)    next input y0 + dt * (k1 - k2 + k3)
-//   s = 4: k4 = v(t0 + dt, ..)        y1 = y0 + (k1 + 3 (k2 + k3) + k4) * dt / 8
-// v as in cfg_euler_kernel.  Stages 1-3 keep k_s in their [U][mel] buffer and write the next stage's input only to the split-bf16 copy
-// of x (both branches); xstate holds y0 until stage 4 writes y1 there.  kFrameCfg and kUnitDt as in cfg_euler_kernel.
-template <bool kFrameCfg, bool kUnitDt = false>
-__global__ __launch_bounds__(128) void cfg_rk4_stage_kernel(float* xstate /*[U][mel]*/, int mel, int U, const float* pred, int ldp,
-                                                            const int* urow_c, const int* urow_u, float cfg, const float* cfg_frame, float dt,
-                                                            int stage, float* k1, float* k2, float* k3, __bf16* xs_hi, __bf16* xs_lo, int ldx,
-                                                            const int* frame_unit, const float* unit_dt, int n_act) {
-    const int u = blockIdx.x;
-    if (u >= U) return;
-    const int c = threadIdx.x;
-    if (c >= mel) return;
-    if (kUnitDt) {
-        const int un = frame_unit[u];
-        if (un >= n_act) return;
-        dt = unit_dt[un];
-    }
-    const int rc = urow_c[u], ru = urow_u[u];
-    const float v = cfg_velocity(pred, ldp, rc, ru, c, kFrameCfg ? cfg_frame[u] : cfg);
-    const float xn = rk4_stage_update(xstate, k1, k2, k3, (size_t)u * mel + c, stage, dt, v);
-    store_x_split(xs_hi, xs_lo, ldx, rc, ru, c, xn);
-}
-
-// What cfg_mixed_kernel does to the frames of a unit after one forward of a mixed-method call (f5hip_cfm_sample_methods)
-enum CfgOp : int {
-    CFG_OP_NONE = 0,       // the unit's steps are done: its frames are left as they are
-    CFG_OP_EULER = 1,      // x += dt v
-    CFG_OP_MID_HALF = 2,   // midpoint, first forward: xmid = x + (dt / 2) v (the table holds dt / 2), x untouched
-    CFG_OP_MID_FULL = 3,   // midpoint, second forward: x += dt v
-    CFG_OP_RK4_1 = 4,      // RK4 stage 1 .. 4: CFG_OP_RK4_1 + stage - 1
-    CFG_OP_COUNT = 8
-};
-
-// The CFG combine + ODE update of a call whose units use different solvers: one launch after every forward, each frame stepped by the
-// rule of its unit.  unit_op / unit_dt [n units]: this forward's op code (CfgOp) and step size per layout position, read through
-// frame_unit[u]; the op is uniform over a block (one frame), so no wave diverges.  Frames of units >= n_act, or with CFG_OP_NONE, are left
-// as they are.  Strengths per frame (cfg_frame).  k1 is the midpoint rule's scratch state as well as RK4's first slope, indexed by frame like
-// k2 / k3: the frames of different units are disjoint, so units of different methods share the buffers.  Per op the arithmetic is that of
-// cfg_euler_kernel<true, true> / cfg_rk4_stage_kernel<true, true> (the helpers above): the same bits.
-__global__ __launch_bounds__(128) void cfg_mixed_kernel(float* xstate /*[U][mel]*/, int mel, int U, const float* pred, int ldp, const int* urow_c,
-                                                        const int* urow_u, const float* cfg_frame, float* k1, float* k2, float* k3,
-                                                        __bf16* xs_hi, __bf16* xs_lo, int ldx, const int* frame_unit, const int* unit_op,
-                                                        const float* unit_dt, int n_act) {
-    const int u = blockIdx.x;
-    if (u >= U) return;
-    const int c = threadIdx.x;
-    if (c >= mel) return;
-    const int un = frame_unit[u];
-    if (un >= n_act) return;
-    const int op = unit_op[un];
     if (op <= CFG_OP_NONE || op >= CFG_OP_COUNT) return;
-    const float dt = unit_dt[un];
     const int rc = urow_c[u], ru = urow_u[u];
     const float v = cfg_velocity(pred, ldp, rc, ru, c, cfg_frame[u]);
     const size_t i = (size_t)u * mel + c;

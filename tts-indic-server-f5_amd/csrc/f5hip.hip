@@ -82,7 +82,7 @@ struct f5hip_dit {
     // per-call metadata (device pointers into `meta`)
     int *d_row_pos, *d_row_start, *d_row_end, *d_row_seq, *d_row_token, *d_row_frame, *d_row_condframe, *d_row_keep,
         *d_seq_row0, *d_seq_len, *d_seq_kvlen, *d_urow_c, *d_urow_u, *d_frame_is_cond;
-    float* d_frame_cfg = nullptr;   // f5hip_cfm_sample_units: CFG strength per frame (its unit's), in `meta` behind the other arrays; else null
+    float* d_frame_cfg = nullptr;   // CFG strength per frame (its unit's, or the call's), in `meta` with the other arrays (MetaLayout)
     int M = 0, n_seq = 0, n_frames = 0, max_len = 0;
     int Mc = 0, Rtot = 0;   // MMDiT: text-stream rows and all rows (= row pitch of the V^T buffer); Rtot == M otherwise
     int row_c0 = 0;         // MMDiT: first row of the text stream (all audio rows of the layout; M may be a prefix of them: cfm_sample_grids)
@@ -356,6 +356,26 @@ int f5hip_dit_finalize(f5hip_dit* m) {
 // -------------------------------------------------------------------------------------------------
 // workspace
 // -------------------------------------------------------------------------------------------------
+// The per-call int metadata arena (f5hip_dit::meta) of a layout of R rows, S sequences and U frames: the offset of every array, in ints, and
+// the total.  The host fill and the device pointers (setup_sequences) and the capacity (ensure_workspace) all read it.
+struct MetaLayout {
+    size_t row_pos, row_start, row_end, row_seq, row_token, row_frame, row_condframe, row_keep;   // [R]
+    size_t seq_row0, seq_len, seq_kvlen;                                                          // [S]
+    size_t urow_c, urow_u, frame_is_cond;                                                         // [U]
+    size_t j_row0, j_len, j_kvlen, j_kv_row0, j_kv2_row0, j_kv2_len;   // MMDiT joint attention: [2 S] pseudo-sequences (empty otherwise)
+    size_t frame_cfg;                                                  // [U] floats
+    size_t total = 0;
+    MetaLayout(size_t R, size_t S, size_t U, bool mmdit) {
+        auto take = [&](size_t n) { const size_t at = total; total += n; return at; };
+        for (size_t* o : {&row_pos, &row_start, &row_end, &row_seq, &row_token, &row_frame, &row_condframe, &row_keep}) *o = take(R);
+        for (size_t* o : {&seq_row0, &seq_len, &seq_kvlen}) *o = take(S);
+        for (size_t* o : {&urow_c, &urow_u, &frame_is_cond}) *o = take(U);
+        for (size_t* o : {&j_row0, &j_len, &j_kvlen, &j_kv_row0, &j_kv2_row0, &j_kv2_len}) *o = take(mmdit ? 2 * S : 0);
+        frame_cfg = take(U);
+    }
+};
+static_assert(sizeof(float) == sizeof(int), "frame_cfg rides in the int arena");
+
 static int ensure_workspace(f5hip_dit* m, int rows_pad, int frames, int n_seq) {
     if (rows_pad <= m->cap_rows && frames <= m->cap_frames && n_seq <= m->cap_seq) return 0;
     const f5hip_dit_config& c = m->cfg;
@@ -378,7 +398,7 @@ static int ensure_workspace(f5hip_dit* m, int rows_pad, int frames, int n_seq) {
             m->rk_k2 = a.f32(U * c.mel_dim); m->rk_k3 = a.f32(U * c.mel_dim);
         })) { m->cap_rows = 0; return -5; }
     m->cap_rows = (int)R; m->cap_frames = (int)U; m->cap_seq = (int)S;
-    const int need = (int)(R * 8 + S * 15 + U * 4 + 64);
+    const int need = (int)MetaLayout(R, S, U, m->arch == 2).total;
     if (need > m->meta_cap) {
         dev_free(m->meta);
         if (hipMalloc((void**)&m->meta, sizeof(int) * need) != hipSuccess) { m->meta = nullptr; m->meta_cap = 0; return fail(-5, "hipMalloc meta"); }
@@ -404,7 +424,7 @@ struct SeqDesc { int len, kvlen, frame0 /* first frame in caller's packed arrays
 
 // Lays the sequences out (each padded to a multiple of 128 rows), builds the per-row metadata and uploads it.
 // UNetT: row 0 of every sequence is the time token (F/model/backbones/unett.py:184); frames follow at rows 1..len.
-// frame_cfg (n_frames floats, or null): per-frame CFG strengths, uploaded with the rest (m->d_frame_cfg).
+// frame_cfg (n_frames floats, or null = zeros): per-frame CFG strengths, uploaded with the rest (m->d_frame_cfg).
 // frame_final (n_frames flags, or null = frame_is_cond): which frames the sampler's final select overwrites with the conditioning.
 static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n_frames, const int32_t* text, int nt_max,
                            const uint8_t* frame_is_cond, hipStream_t st, const float* frame_cfg = nullptr, const uint8_t* frame_final = nullptr) {
@@ -419,14 +439,14 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
     }
     if (ensure_workspace(m, rows, n_frames, (int)seqs.size())) return -5;
     const int R = rows, S = (int)seqs.size(), U = n_frames;
-    const size_t n_int = (size_t)R * 8 + S * 3 + U * 3 + (mm ? 12 * S : 0);
-    std::vector<int> hbuf(n_int + (frame_cfg ? U : 0), 0);
-    static_assert(sizeof(float) == sizeof(int), "frame_cfg rides in the int arena");
-    if (frame_cfg) memcpy(&hbuf[n_int], frame_cfg, sizeof(float) * U);
-    int* row_pos = &hbuf[0]; int* row_start = row_pos + R; int* row_end = row_start + R; int* row_seq = row_end + R;
-    int* row_token = row_seq + R; int* row_frame = row_token + R; int* row_condframe = row_frame + R; int* row_keep = row_condframe + R;
-    int* seq_row0 = row_keep + R; int* seq_len = seq_row0 + S; int* seq_kvlen = seq_len + S;
-    int* urow_c = seq_kvlen + S; int* urow_u = urow_c + U; int* fic = urow_u + U;
+    const MetaLayout ml(R, S, U, mm);
+    std::vector<int> hbuf(ml.total, 0);
+    if (frame_cfg) memcpy(&hbuf[ml.frame_cfg], frame_cfg, sizeof(float) * U);
+    int* const hb = hbuf.data();
+    int* row_pos = hb + ml.row_pos; int* row_start = hb + ml.row_start; int* row_end = hb + ml.row_end; int* row_seq = hb + ml.row_seq;
+    int* row_token = hb + ml.row_token; int* row_frame = hb + ml.row_frame; int* row_condframe = hb + ml.row_condframe; int* row_keep = hb + ml.row_keep;
+    int* seq_row0 = hb + ml.seq_row0; int* seq_len = hb + ml.seq_len; int* seq_kvlen = hb + ml.seq_kvlen;
+    int* urow_c = hb + ml.urow_c; int* urow_u = hb + ml.urow_u; int* fic = hb + ml.frame_is_cond;
     int r0 = 0;
     m->any_masked = false;
     m->h_seq_row0.assign(S + 1, 0); m->h_seqc_row0.assign(S + 1, rows_x);
@@ -457,8 +477,7 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
         r0 += seq_rows(q.len, extra);
         m->h_seq_row0[s + 1] = r0;
     }
-    int* jm = fic + U;   // MMDiT joint attention: 6 arrays of 2 S pseudo-sequences (2 s: audio queries of sequence s, 2 s + 1: its text queries)
-    if (mm) {
+    if (mm) {   // joint attention: 2 S pseudo-sequences (2 s: audio queries of sequence s, 2 s + 1: its text queries)
         int rc0 = rows_x;
         for (int s = 0; s < S; s++) {
             const SeqDesc& q = seqs[s];
@@ -472,12 +491,12 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
             }
             for (int qd = 0; qd < 2; qd++) {
                 const int j = 2 * s + qd;
-                jm[j] = qd ? rc0 : seq_row0[s];                 // query rows
-                jm[2 * S + j] = qd ? q.c_len : q.len;
-                jm[4 * S + j] = q.kvlen;                        // first key range: the audio rows, padding masked
-                jm[6 * S + j] = seq_row0[s];
-                jm[8 * S + j] = rc0;                            // second key range: the text rows, never masked (F/model/modules.py:508)
-                jm[10 * S + j] = q.c_len;
+                hb[ml.j_row0 + j] = qd ? rc0 : seq_row0[s];   // query rows
+                hb[ml.j_len + j] = qd ? q.c_len : q.len;
+                hb[ml.j_kvlen + j] = q.kvlen;                 // first key range: the audio rows, padding masked
+                hb[ml.j_kv_row0 + j] = seq_row0[s];
+                hb[ml.j_kv2_row0 + j] = rc0;                  // second key range: the text rows, never masked (F/model/modules.py:508)
+                hb[ml.j_kv2_len + j] = q.c_len;
             }
             m->max_len = std::max(m->max_len, q.c_len);
             rc0 += seq_rows(q.c_len, 0);
@@ -485,15 +504,14 @@ static int setup_sequences(f5hip_dit* m, const std::vector<SeqDesc>& seqs, int n
         }
     }
     if (const int r_ = m->up_meta.upload(m->meta, hbuf.data(), sizeof(int) * hbuf.size(), st)) return r_;   // (pinned staging: no host sync)
-    int* d = m->meta;
-    m->d_row_pos = d; m->d_row_start = d + R; m->d_row_end = d + 2 * R; m->d_row_seq = d + 3 * R; m->d_row_token = d + 4 * R;
-    m->d_row_frame = d + 5 * R; m->d_row_condframe = d + 6 * R; m->d_row_keep = d + 7 * R;
-    d += 8 * R;
-    m->d_seq_row0 = d; m->d_seq_len = d + S; m->d_seq_kvlen = d + 2 * S; d += 3 * S;
-    m->d_urow_c = d; m->d_urow_u = d + U; m->d_frame_is_cond = d + 2 * U;
-    d += 3 * U;
-    m->d_j_row0 = d; m->d_j_len = d + 2 * S; m->d_j_kvlen = d + 4 * S; m->d_j_kv_row0 = d + 6 * S; m->d_j_kv2_row0 = d + 8 * S; m->d_j_kv2_len = d + 10 * S;
-    m->d_frame_cfg = frame_cfg ? reinterpret_cast<float*>(m->meta + n_int) : nullptr;
+    int* const d = m->meta;
+    m->d_row_pos = d + ml.row_pos; m->d_row_start = d + ml.row_start; m->d_row_end = d + ml.row_end; m->d_row_seq = d + ml.row_seq;
+    m->d_row_token = d + ml.row_token; m->d_row_frame = d + ml.row_frame; m->d_row_condframe = d + ml.row_condframe; m->d_row_keep = d + ml.row_keep;
+    m->d_seq_row0 = d + ml.seq_row0; m->d_seq_len = d + ml.seq_len; m->d_seq_kvlen = d + ml.seq_kvlen;
+    m->d_urow_c = d + ml.urow_c; m->d_urow_u = d + ml.urow_u; m->d_frame_is_cond = d + ml.frame_is_cond;
+    m->d_j_row0 = d + ml.j_row0; m->d_j_len = d + ml.j_len; m->d_j_kvlen = d + ml.j_kvlen; m->d_j_kv_row0 = d + ml.j_kv_row0;
+    m->d_j_kv2_row0 = d + ml.j_kv2_row0; m->d_j_kv2_len = d + ml.j_kv2_len;
+    m->d_frame_cfg = reinterpret_cast<float*>(d + ml.frame_cfg);
     // rotary factors per row of this layout (one load in the QKV epilogues instead of row_pos -> table)
     hipLaunchKernelGGL(rope_rows_kernel, dim3((R * 32 + 255) / 256), dim3(256), 0, st, m->d_row_pos, m->rope_cos, m->rope_sin, R, 4097, m->rope_row_cos, m->rope_row_sin);
     if (hipGetLastError() != hipSuccess) return fail(-7, "rope_rows_kernel launch");

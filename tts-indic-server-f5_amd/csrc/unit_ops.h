@@ -681,12 +681,53 @@ extern "C" int f5hip_op_convnext_block(int32_t n_seq, const int32_t* seq_len, in
 }
 
 // ---------------------------------------------------------------------------------------------------------------- ODE step and time-table unit ops
-// One launch of the sampler's CFG combine + ODE update (launch_cfg_form, the function cfg_stage calls) on the caller's buffers, plus (final_flags_host
-// not null) final_select_kernel.  U frames of `mel` channels; pred_dev and xs_dev fp32 [rows][128]; urow_c / urow_u host int32 [U] (urow_u -1: the
-// frame has no unconditional row).  method 0: the Euler kernels, xout = xbase + dt v (xout == xbase: in place; else the midpoint rule's half
-// step, xbase untouched); 2: RK4 stage `stage` + 1 of 4 in place on xbase (xout must be xbase or null), k1 / k2 / k3 [U][mel]; -1: no step.
-// The form: cfg_frame_dev null = scalar cfg; else per-frame strengths [U]; frame_unit_host + unit_dt_host [n_units] (with cfg_frame_dev) =
-// per-unit step sizes, frames of units >= n_act left alone.  xs_dev is split into the bf16 planes the kernels write, and read back as hi + lo.
+// What f5hip_op_cfg_step and f5hip_op_cfg_mixed share: checks every frame's rows and unit, stages urow_c | urow_u | frame_unit | the scalar
+// strength spread over the frames (floats) [U each] | unit_op | unit_dt (floats) [n_units each] in one upload and xs_dev as the bf16 planes
+// the kernel writes, launches cfg_step_kernel once (launch_cfg_step, the sampler's own launch) and reads the planes back as hi + lo.
+// cb: the caller's state, slopes, pred and strengths (frame_cfg null: every frame takes `cfg`); its rows and planes are filled in here.
+// frame_unit_host null: `op` and `dt` for every frame; else unit_op_host (null: `op` for every unit) and unit_dt_host [n_units].
+static int op_cfg_launch(const char* name, CfgBufs cb, int U, int rows, const int32_t* urow_c_host, const int32_t* urow_u_host, float cfg, int op,
+                         float dt, const int32_t* frame_unit_host, const int32_t* unit_op_host, const float* unit_dt_host, int n_units, int n_act,
+                         float* xs_dev, hipStream_t st) {
+    if (!frame_unit_host) n_units = 0;
+    for (int u = 0; u < U; u++)
+        if (urow_c_host[u] < 0 || urow_c_host[u] >= rows || urow_u_host[u] < -1 || urow_u_host[u] >= rows ||
+            (frame_unit_host && (frame_unit_host[u] < 0 || frame_unit_host[u] >= n_units)))
+            return fail(-1, "%s: frame %d: row or unit out of range", name, u);
+    OpBufs b;
+    const size_t n = (size_t)rows * 128, o_unit = 2 * (size_t)U, o_cfg = 3 * (size_t)U, o_op = 4 * (size_t)U, o_dt = o_op + n_units;
+    cb.xs.hi = b.get<__bf16>(n); cb.xs.lo = b.get<__bf16>(n);
+    int* meta = b.get<int>(o_dt + n_units);
+    if (!cb.xs.hi || !cb.xs.lo || !meta) return fail(-5, "%s: hipMalloc", name);
+    std::vector<int> hm(o_dt + n_units, 0);
+    for (int u = 0; u < U; u++) {
+        hm[u] = urow_c_host[u]; hm[U + u] = urow_u_host[u];
+        if (frame_unit_host) hm[o_unit + u] = frame_unit_host[u];
+        memcpy(&hm[o_cfg + u], &cfg, sizeof(float));
+    }
+    for (int k = 0; k < n_units; k++) hm[o_op + k] = unit_op_host ? unit_op_host[k] : op;
+    if (n_units) memcpy(&hm[o_dt], unit_dt_host, sizeof(float) * n_units);
+    if (upload_sync(st, meta, hm) != hipSuccess) return fail(-6, "%s: upload", name);
+    hipLaunchKernelGGL(split_rows_kernel, dim3(rows), dim3(256), 0, st, (const float*)xs_dev, 128, 128, rows, (const int*)nullptr, cb.xs.hi, cb.xs.lo, 128, 0);
+    CKL("op cfg split");
+    cb.urow_c = meta; cb.urow_u = meta + U;
+    if (!cb.frame_cfg) cb.frame_cfg = reinterpret_cast<const float*>(meta + o_cfg);
+    launch_cfg_step(cb, U, op, dt, frame_unit_host ? meta + o_unit : nullptr, meta + o_op, reinterpret_cast<const float*>(meta + o_dt), n_act, st);
+    CKL("op cfg step");
+    hipLaunchKernelGGL(op_planes_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cb.xs.hi, cb.xs.lo, 0, n, xs_dev);
+    CKL("op cfg planes");
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "%s: %s", name, hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+// One launch of the sampler's CFG combine + ODE update (cfg_step_kernel) on the caller's buffers, plus (final_flags_host not null)
+// final_select_kernel.  U frames of `mel` channels; pred_dev and xs_dev fp32 [rows][128]; urow_c / urow_u host int32 [U] (urow_u -1: the
+// frame has no unconditional row).  method 0: xout = xbase + dt v -- xout == xbase the Euler step in place (CFG_OP_EULER), else the midpoint
+// rule's half step with xout as its scratch state, xbase untouched (CFG_OP_MID_HALF); 2: RK4 stage `stage` + 1 of 4 in place on xbase (xout
+// must be xbase or null), k1 / k2 / k3 [U][mel]; -1: no step.
+// The form: cfg_frame_dev null = scalar cfg, spread over the frames here; else per-frame strengths [U]; frame_unit_host + unit_dt_host
+// [n_units] (with cfg_frame_dev) = the per-unit instance with the one op for every unit, frames of units >= n_act left alone.
+// xs_dev is split into the bf16 planes the kernel writes, and read back as hi + lo.
 // Final select: out_dev [U][mel] = final_flags_host[u] ? cond_dev : xbase (after the step).
 extern "C" int f5hip_op_cfg_step(int32_t method, int32_t stage, int32_t U, int32_t mel, int32_t rows, float* xout_dev, float* xbase_dev,
                                  const float* pred_dev, const int32_t* urow_c_host, const int32_t* urow_u_host, float cfg, const float* cfg_frame_dev,
@@ -703,47 +744,27 @@ extern "C" int f5hip_op_cfg_step(int32_t method, int32_t stage, int32_t U, int32
         return fail(-1, "op_cfg_step: the per-unit form needs unit_dt, cfg_frame and 0 <= n_act <= n_units");
     if (final_flags_host && (!cond_dev || !out_dev)) return fail(-1, "op_cfg_step: the final select needs cond and out");
     hipStream_t st = (hipStream_t)stream;
-    OpBufs b;
     if (step) {
-        for (int u = 0; u < U; u++)
-            if (urow_c_host[u] < 0 || urow_c_host[u] >= rows || urow_u_host[u] < -1 || urow_u_host[u] >= rows ||
-                (unit_dt && (frame_unit_host[u] < 0 || frame_unit_host[u] >= n_units)))
-                return fail(-1, "op_cfg_step: frame %d: row or unit out of range", u);
-        const size_t n = (size_t)rows * 128;
-        Plane2 xs;
-        xs.hi = b.get<__bf16>(n); xs.lo = b.get<__bf16>(n);
-        int* meta = b.get<int>((size_t)3 * U);
-        float* udt = unit_dt ? b.get<float>(n_units) : nullptr;
-        if (!xs.hi || !xs.lo || !meta || (unit_dt && !udt)) return fail(-5, "op_cfg_step: hipMalloc");
-        std::vector<int> hm((size_t)3 * U, 0);
-        for (int u = 0; u < U; u++) { hm[u] = urow_c_host[u]; hm[U + u] = urow_u_host[u]; if (unit_dt) hm[2 * (size_t)U + u] = frame_unit_host[u]; }
-        if (upload_sync(st, meta, hm) != hipSuccess) return fail(-6, "op_cfg_step: upload");
-        if (unit_dt && (hipMemcpyAsync(udt, unit_dt_host, sizeof(float) * n_units, hipMemcpyHostToDevice, st) != hipSuccess ||
-                        hipStreamSynchronize(st) != hipSuccess))
-            return fail(-6, "op_cfg_step: unit_dt upload");
-        hipLaunchKernelGGL(split_rows_kernel, dim3(rows), dim3(256), 0, st, (const float*)xs_dev, 128, 128, rows, (const int*)nullptr, xs.hi, xs.lo, 128, 0);
-        CKL("op_cfg_step split");
-        const CfgBufs cb{xbase_dev, k1_dev, k2_dev, k3_dev, pred_dev, meta, meta + U, cfg_frame_dev, xs, mel};
-        const CfgStep c{cfg, dt, unit_dt ? meta + 2 * (size_t)U : nullptr, udt, n_act};
-        launch_cfg_form(cb, U, rk4, stage, xout_dev, c, st);
-        CKL("op_cfg_step");
-        hipLaunchKernelGGL(op_planes_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, xs.hi, xs.lo, 0, n, xs_dev);
-        CKL("op_cfg_step planes");
+        const int op = rk4 ? CFG_OP_RK4_1 + stage : xout_dev == xbase_dev ? CFG_OP_EULER : CFG_OP_MID_HALF;
+        const CfgBufs cb{xbase_dev, rk4 ? k1_dev : xout_dev, k2_dev, k3_dev, pred_dev, nullptr, nullptr, cfg_frame_dev, {}, mel};
+        CK(op_cfg_launch("op_cfg_step", cb, U, rows, urow_c_host, urow_u_host, cfg, op, dt, frame_unit_host, nullptr, unit_dt_host, n_units, n_act, xs_dev, st));
     }
     if (final_flags_host) {
+        OpBufs b;
         int* flags = b.get<int>(U);
         std::vector<int> hf(final_flags_host, final_flags_host + U);
         if (!flags || upload_sync(st, flags, hf) != hipSuccess) return fail(-6, "op_cfg_step: flag upload");
         hipLaunchKernelGGL(final_select_kernel, dim3(U), dim3(128), 0, st, (const float*)xbase_dev, cond_dev, (const int*)flags, mel, U, out_dev);
         CKL("op_cfg_step final_select");
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_cfg_step: %s", hipGetErrorString(hipGetLastError()));
     }
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_cfg_step: %s", hipGetErrorString(hipGetLastError()));
     return 0;
 }
 
-// One launch of cfg_mixed_kernel (launch_cfg_mixed, what a mixed-method sampler call launches after every forward) on the caller's buffers:
-// buffers as in f5hip_op_cfg_step; frame_unit_host [U], unit_op_host / unit_dt_host [n_units] the op code (CfgOp, 0..7) and step size of
-// every unit for this forward; the frames of units >= n_act, or with op 0, are left as they are.  k1_dev is the midpoint rule's xmid too.
+// One launch of the per-unit instance of cfg_step_kernel (what a sampler call with per-unit columns launches after every forward) on the
+// caller's buffers: buffers as in f5hip_op_cfg_step; frame_unit_host [U], unit_op_host / unit_dt_host [n_units] the op code (CfgOp, 0..7) and
+// step size of every unit for this forward; the frames of units >= n_act, or with op 0, are left as they are.  k1_dev is the midpoint rule's
+// xmid too.
 extern "C" int f5hip_op_cfg_mixed(int32_t U, int32_t mel, int32_t rows, float* xstate_dev, const float* pred_dev, const int32_t* urow_c_host,
                                   const int32_t* urow_u_host, const float* cfg_frame_dev, const int32_t* frame_unit_host, const int32_t* unit_op_host,
                                   const float* unit_dt_host, int32_t n_units, int32_t n_act, float* k1_dev, float* k2_dev, float* k3_dev, float* xs_dev,
@@ -754,32 +775,9 @@ extern "C" int f5hip_op_cfg_mixed(int32_t U, int32_t mel, int32_t rows, float* x
     if (n_units <= 0 || n_act < 0 || n_act > n_units) return fail(-1, "op_cfg_mixed: needs 0 <= n_act <= n_units");
     for (int k = 0; k < n_units; k++)
         if (unit_op_host[k] < CFG_OP_NONE || unit_op_host[k] >= CFG_OP_COUNT) return fail(-1, "op_cfg_mixed: unit_op[%d] = %d (0..7)", k, unit_op_host[k]);
-    for (int u = 0; u < U; u++)
-        if (urow_c_host[u] < 0 || urow_c_host[u] >= rows || urow_u_host[u] < -1 || urow_u_host[u] >= rows || frame_unit_host[u] < 0 ||
-            frame_unit_host[u] >= n_units)
-            return fail(-1, "op_cfg_mixed: frame %d: row or unit out of range", u);
-    hipStream_t st = (hipStream_t)stream;
-    OpBufs b;
-    const size_t n = (size_t)rows * 128;
-    Plane2 xs;
-    xs.hi = b.get<__bf16>(n); xs.lo = b.get<__bf16>(n);
-    int* meta = b.get<int>((size_t)3 * U + 2 * (size_t)n_units);   // urow_c | urow_u | frame_unit | unit_op | unit_dt (floats)
-    if (!xs.hi || !xs.lo || !meta) return fail(-5, "op_cfg_mixed: hipMalloc");
-    std::vector<int> hm((size_t)3 * U + 2 * (size_t)n_units, 0);
-    for (int u = 0; u < U; u++) { hm[u] = urow_c_host[u]; hm[U + u] = urow_u_host[u]; hm[2 * (size_t)U + u] = frame_unit_host[u]; }
-    std::copy(unit_op_host, unit_op_host + n_units, hm.begin() + 3 * (size_t)U);
-    memcpy(&hm[3 * (size_t)U + n_units], unit_dt_host, sizeof(float) * n_units);
-    if (upload_sync(st, meta, hm) != hipSuccess) return fail(-6, "op_cfg_mixed: upload");
-    hipLaunchKernelGGL(split_rows_kernel, dim3(rows), dim3(256), 0, st, (const float*)xs_dev, 128, 128, rows, (const int*)nullptr, xs.hi, xs.lo, 128, 0);
-    CKL("op_cfg_mixed split");
-    const CfgBufs cb{xstate_dev, k1_dev, k2_dev, k3_dev, pred_dev, meta, meta + U, cfg_frame_dev, xs, mel};
-    const int* uop = meta + 3 * (size_t)U;
-    launch_cfg_mixed(cb, U, meta + 2 * (size_t)U, uop, reinterpret_cast<const float*>(uop + n_units), n_act, st);
-    CKL("op_cfg_mixed");
-    hipLaunchKernelGGL(op_planes_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, xs.hi, xs.lo, 0, n, xs_dev);
-    CKL("op_cfg_mixed planes");
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_cfg_mixed: %s", hipGetErrorString(hipGetLastError()));
-    return 0;
+    const CfgBufs cb{xstate_dev, k1_dev, k2_dev, k3_dev, pred_dev, nullptr, nullptr, cfg_frame_dev, {}, mel};
+    return op_cfg_launch("op_cfg_mixed", cb, U, rows, urow_c_host, urow_u_host, 0.0f, CFG_OP_NONE, 0.0f, frame_unit_host, unit_op_host, unit_dt_host, n_units,
+                         n_act, xs_dev, (hipStream_t)stream);
 }
 
 // row_tp_kernel of a mixed-grid call: row_tp_host[r] = unit_tp_host[row_unit_host[r]] for R rows of n_units units (all host int32)
