@@ -415,6 +415,20 @@ int f5hip_mel_spectrogram(int32_t batch, int32_t n_samples, const float* wave_de
 int f5hip_mel_spectrogram_bigvgan(int32_t batch, int32_t n_samples, const float* wave_dev, float* mel_dev, int32_t n_fft,
                                   int32_t hop_length, int32_t n_mels, int32_t sample_rate, void* stream);
 
+/* Both mel front-ends for n clips of their own lengths in one launch: the reference mels of the new voices of a batch (a multi-voice script
+ * brings several), straight from f5hip_ref_frontend's packed output.
+ *   n_samples[i]           host, samples of clip i: > n_fft / 2 (variant 0), >= n_fft (variant 1), as in the two calls above
+ *   wave_dev[i]            host array of device pointers: clip i's fp32 samples (4-byte aligned); the clips need not be contiguous
+ *   mel_dev                fp32 [sum T][n_mels], frame-major and packed: clip i owns rows sum_{j<i} T_j .. + T_i, the layout the sampler's cond
+ *                          has; T_i = 1 + n_samples[i] / hop (variant 0) or (n_samples[i] + 2 pad - n_fft) / hop + 1, pad = (n_fft - hop) / 2
+ *   variant                0: f5hip_mel_spectrogram's front-end (vocos), 1: f5hip_mel_spectrogram_bigvgan's
+ * Each clip is reflect-padded at its own bounds, and its rows equal its own single-clip call's (transposed) bit for bit: the same frame
+ * code, FFT and filterbank summation order.  One launch whatever n (counters mel_ragged_launches, mel_ragged_items); the clip table is
+ * copied on `stream`, which the call waits for once before it launches.
+ * Refused before the launch: n < 1, a null pointer, a clip too short for its variant, an unknown variant, the geometry the calls above refuse. */
+int f5hip_mel_spectrogram_ragged(int32_t n, const int32_t* n_samples, const float* const* wave_dev, float* mel_dev, int32_t n_fft, int32_t hop_length,
+                                 int32_t n_mels, int32_t sample_rate, int32_t variant, void* stream);
+
 /* ---------------------------------------------------------------- reference-audio front-end ------------ */
 
 /* Prologue of infer_batch_process (F/infer/utils_infer.py:423-433) for n clips of one sample-rate pair, in one call:
@@ -452,6 +466,20 @@ int f5hip_ref_frontend(int32_t n, const int32_t* n_in, const int32_t* channels, 
  * in a request of several chunks, sample_rate != 24000, more than 2^31 - 1 samples in or out. */
 int f5hip_wave_finish(int32_t n, const int32_t* chunks_per_request, const float* const* chunk_dev, const int32_t* chunk_len, int32_t fade,
                       const uint8_t* remove_silence, int32_t sample_rate, int16_t* pcm_dev, int32_t* len_dev, void* stream);
+
+/* f5hip_wave_finish with a choice per join: the pieces of a multi-voice script (F/infer/infer_cli.py:181-208) are cross-faded inside a
+ * voice's piece and concatenated between pieces, so a request's chunks are joined as infer.join_segments joins them.
+ *   chunk_fade[c]          host, one per chunk of the call (or null): non-zero: chunk c cross-fades into the chunk before it in its request over
+ *                          `fade` samples; 0: it butts against it.  A request's first chunk is ignored.  A gap is a chunk that points at zeros.
+ * Request i then has N = sum(len) - fade * (its fading joins) joined samples.  Everything else is f5hip_wave_finish's contract: the fade
+ * arithmetic, the quantisation, the output offsets ((N_j + 7) & ~7), len_dev, the silence rule, one launch or three, the same counters, a
+ * request's samples independent of the call.  With chunk_fade == null this IS f5hip_wave_finish (which is that call).
+ * Refused before the first launch: what f5hip_wave_finish refuses (its 2 * fade rule only with chunk_fade == null), and with fade > 0 a chunk
+ * shorter than (fade if it fades in) + (fade if its successor fades in): exactly where the host's nested cross-fade would take fewer than
+ * `fade` samples or touch a sample twice.  With that the result equals infer.join_segments + quantise_pcm16 bit for bit. */
+int f5hip_wave_finish_joins(int32_t n, const int32_t* chunks_per_request, const float* const* chunk_dev, const int32_t* chunk_len, int32_t fade,
+                            const uint8_t* chunk_fade, const uint8_t* remove_silence, int32_t sample_rate, int16_t* pcm_dev, int32_t* len_dev,
+                            void* stream);
 
 /* The delivery format of n finished requests, in one call: their 24 kHz int16 PCM (f5hip_wave_finish's pcm_dev, still on the device) resampled
  * to new_freq and encoded.  Not in the reference, whose route always answers with 24 kHz PCM; the definition is infer.resample_pcm16 /

@@ -22,6 +22,8 @@
 #include <vector>
 
 //   torch.ops.f5hip.wave_finish(chunks[], chunks_per_request, fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/utils_infer.py:485-519,530-539
+//   torch.ops.f5hip.wave_finish_joins(chunks[], chunks_per_request, fade, chunk_fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/infer_cli.py:181-208
+//   torch.ops.f5hip.mel_spectrogram_ragged(waves[], n_fft, hop_length, n_mels, sample_rate, variant) -> Tensor mel [sum T, n_mels]   F/model/modules.py:30-143
 //   torch.ops.f5hip.wave_encode(pcm[], in_off, max_len, len_dev?, new_freq, encoding, taps?) -> (Tensor bytes uint8, Tensor lengths int32, Tensor offsets int64 host)
 #include "../../include/f5hip.h"
 #include "rate_pair.h"
@@ -243,8 +245,9 @@ std::tuple<at::Tensor, at::Tensor> ref_frontend(const at::Tensor& wave, const at
 // chunks: the chunk waves of all requests in request and chunk order, each a contiguous 1-D fp32 device tensor (views of the vocoder's packed
 // output as they are: the library reads them through a pointer table); chunks_per_request [n] int32 host; fade in samples; remove_silence [n]
 // uint8 host -> (pcm int16 device, request i at sum_{j<i} ((N_j + 7) & ~7); lengths [n] int32 device)
-std::tuple<at::Tensor, at::Tensor> wave_finish(at::TensorList chunks, const at::Tensor& chunks_per_request, int64_t fade, const at::Tensor& remove_silence,
-                                               int64_t sample_rate) {
+// chunk_fade: null (every join fades: f5hip_wave_finish), or one byte per chunk of the call (f5hip_wave_finish_joins)
+static std::tuple<at::Tensor, at::Tensor> wave_finish_impl(at::TensorList chunks, const at::Tensor& chunks_per_request, int64_t fade, const uint8_t* chunk_fade,
+                                                           const at::Tensor& remove_silence, int64_t sample_rate) {
     check_host(chunks_per_request, at::kInt, "chunks_per_request"); check_host(remove_silence, at::kByte, "remove_silence");
     const int64_t n = chunks_per_request.numel();
     TORCH_CHECK(chunks_per_request.dim() == 1 && n > 0 && remove_silence.numel() == n, "f5hip::wave_finish: chunks_per_request and remove_silence need one value per request");
@@ -267,20 +270,66 @@ std::tuple<at::Tensor, at::Tensor> wave_finish(at::TensorList chunks, const at::
             check_dev_f32(w, "chunk");
             TORCH_CHECK(w.dim() == 1 && w.numel() >= 1 && w.numel() <= INT32_MAX && w.device() == chunks[0].device(),
                         "f5hip::wave_finish: chunk ", j, " of request ", i, " must be a non-empty 1-D tensor on the first chunk's device");
-            TORCH_CHECK(kp[i] == 1 || fade == 0 || w.numel() >= 2 * fade, "f5hip::wave_finish: chunk ", j, " of request ", i, " has ", w.numel(),
+            TORCH_CHECK(chunk_fade || kp[i] == 1 || fade == 0 || w.numel() >= 2 * fade, "f5hip::wave_finish: chunk ", j, " of request ", i, " has ", w.numel(),
                         " samples, fewer than 2 x fade = ", 2 * fade, ": its fades would overlap");
+            const int64_t fin = j > 0 && (!chunk_fade || chunk_fade[c]) ? fade : 0, fout = j + 1 < kp[i] && (!chunk_fade || chunk_fade[c + 1]) ? fade : 0;
+            TORCH_CHECK(w.numel() >= fin + fout, "f5hip::wave_finish: chunk ", j, " of request ", i, " has ", w.numel(), " samples, fewer than its fades (", fin,
+                        " in, ", fout, " out): they would overlap");
             ptrs[c] = w.data_ptr<float>(); lens[c] = (int32_t)w.numel();
-            joined += w.numel() - (j ? fade : 0);
+            joined += w.numel() - fin;
         }
         total_out += (joined + 7) & ~(int64_t)7;
         TORCH_CHECK(total_out <= INT32_MAX, "f5hip::wave_finish: the outputs of the call exceed 2^31 - 1 samples");
     }
     const c10::DeviceGuard guard(chunks[0].device());   // allocations and stream on the chunks' device
     at::Tensor pcm = at::empty({total_out}, chunks[0].options().dtype(at::kShort)), lengths = at::empty({n}, chunks[0].options().dtype(at::kInt));
-    const int rc = f5hip_wave_finish((int32_t)n, kp, ptrs.data(), lens.data(), (int32_t)fade, remove_silence.data_ptr<uint8_t>(), (int32_t)sample_rate,
-                                     pcm.data_ptr<int16_t>(), lengths.data_ptr<int32_t>(), stream_of(chunks[0]));
+    const int rc = f5hip_wave_finish_joins((int32_t)n, kp, ptrs.data(), lens.data(), (int32_t)fade, chunk_fade, remove_silence.data_ptr<uint8_t>(),
+                                           (int32_t)sample_rate, pcm.data_ptr<int16_t>(), lengths.data_ptr<int32_t>(), stream_of(chunks[0]));
     TORCH_CHECK(rc == 0, "f5hip_wave_finish: ", f5hip_last_error());
     return {pcm, lengths};
+}
+
+std::tuple<at::Tensor, at::Tensor> wave_finish(at::TensorList chunks, const at::Tensor& chunks_per_request, int64_t fade, const at::Tensor& remove_silence,
+                                               int64_t sample_rate) {
+    return wave_finish_impl(chunks, chunks_per_request, fade, nullptr, remove_silence, sample_rate);
+}
+
+// wave_finish with chunk_fade [sum(chunks_per_request)] uint8 host: non-zero where a chunk cross-fades into the one before it, 0 where it butts
+std::tuple<at::Tensor, at::Tensor> wave_finish_joins(at::TensorList chunks, const at::Tensor& chunks_per_request, int64_t fade, const at::Tensor& chunk_fade,
+                                                     const at::Tensor& remove_silence, int64_t sample_rate) {
+    check_host(chunk_fade, at::kByte, "chunk_fade");
+    TORCH_CHECK(chunk_fade.dim() == 1 && chunk_fade.numel() == (int64_t)chunks.size(), "f5hip::wave_finish_joins: chunk_fade needs one value per chunk (",
+                chunks.size(), "), got ", chunk_fade.numel());
+    return wave_finish_impl(chunks, chunks_per_request, fade, chunk_fade.data_ptr<uint8_t>(), remove_silence, sample_rate);
+}
+
+// waves: one contiguous 1-D fp32 device tensor per clip (views of ref_frontend's packed output as they are: the library reads them through a
+// pointer table); variant 0 vocos, 1 bigvgan -> mel [sum T, n_mels] fp32 device, frame-major and packed in clip order
+at::Tensor mel_spectrogram_ragged(at::TensorList waves, int64_t n_fft, int64_t hop_length, int64_t n_mels, int64_t sample_rate, int64_t variant) {
+    const int64_t n = (int64_t)waves.size();
+    TORCH_CHECK(n > 0, "f5hip::mel_spectrogram_ragged: no clips");
+    TORCH_CHECK(variant == 0 || variant == 1, "f5hip::mel_spectrogram_ragged: unknown variant ", variant, " (0 vocos, 1 bigvgan)");
+    TORCH_CHECK(n_fft == 1024 && hop_length >= 1 && hop_length <= n_fft && n_mels >= 1 && n_mels <= 256, "f5hip::mel_spectrogram_ragged: only n_fft = 1024, 1 <= hop_length <= n_fft, 1 <= n_mels <= 256");
+    const int64_t pad = (n_fft - hop_length) / 2;
+    std::vector<const float*> ptrs(n);
+    std::vector<int32_t> lens(n);
+    int64_t rows = 0;
+    for (int64_t i = 0; i < n; i++) {
+        const at::Tensor& w = waves[i];
+        check_dev_f32(w, "wave");
+        TORCH_CHECK(w.dim() == 1 && w.numel() <= INT32_MAX && w.device() == waves[0].device(), "f5hip::mel_spectrogram_ragged: clip ", i, " must be a 1-D tensor on the first clip's device");
+        TORCH_CHECK(variant ? w.numel() >= n_fft : w.numel() > n_fft / 2, "f5hip::mel_spectrogram_ragged: clip ", i, " has ", w.numel(), " samples (needs ",
+                    variant ? ">= " : "> ", variant ? n_fft : n_fft / 2, ")");
+        ptrs[i] = w.data_ptr<float>(); lens[i] = (int32_t)w.numel();
+        rows += variant ? (w.numel() + 2 * pad - n_fft) / hop_length + 1 : 1 + w.numel() / hop_length;
+    }
+    TORCH_CHECK(rows * n_mels <= INT32_MAX, "f5hip::mel_spectrogram_ragged: the output exceeds 2^31 - 1 values");
+    const c10::DeviceGuard guard(waves[0].device());
+    at::Tensor mel = at::empty({rows, n_mels}, waves[0].options());
+    const int rc = f5hip_mel_spectrogram_ragged((int32_t)n, lens.data(), ptrs.data(), mel.data_ptr<float>(), (int32_t)n_fft, (int32_t)hop_length, (int32_t)n_mels,
+                                                (int32_t)sample_rate, (int32_t)variant, stream_of(waves[0]));
+    TORCH_CHECK(rc == 0, "f5hip_mel_spectrogram_ragged: ", f5hip_last_error());
+    return mel;
 }
 
 // pcm: ONE int16 device tensor that holds every request (f5hip_wave_finish's packed PCM) or one tensor per request; in_off [n] int64 host (request
@@ -356,5 +405,7 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("bigvgan_forward_ragged(int handle, Tensor mel, Tensor frames, int channels, int total_upsample) -> Tensor", &bigvgan_forward_ragged);
     m.def("ref_frontend(Tensor wave, Tensor n_in, Tensor channels, int orig_freq, int new_freq, Tensor? taps, float rms_floor) -> (Tensor, Tensor)", &ref_frontend);
     m.def("wave_finish(Tensor[] chunks, Tensor chunks_per_request, int fade, Tensor remove_silence, int sample_rate) -> (Tensor, Tensor)", &wave_finish);
+    m.def("wave_finish_joins(Tensor[] chunks, Tensor chunks_per_request, int fade, Tensor chunk_fade, Tensor remove_silence, int sample_rate) -> (Tensor, Tensor)", &wave_finish_joins);
+    m.def("mel_spectrogram_ragged(Tensor[] waves, int n_fft, int hop_length, int n_mels, int sample_rate, int variant) -> Tensor", &mel_spectrogram_ragged);
     m.def("wave_encode(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int new_freq, int encoding, Tensor? taps) -> (Tensor, Tensor, Tensor)", &wave_encode);
 }

@@ -6,6 +6,7 @@
 //   x = Conv1d(100->512,k7,p3)(mel) -> LN -> 8 x [dwconv k7 -> LN -> 512->1536 -> GELU(erf) -> 1536->512 -> gamma* -> +res]
 //   -> LN -> Linear(512->1026) -> (mag = min(exp(.),1e2), phase) -> irfft(1024) * hann -> overlap-add / envelope
 #pragma once
+#include "ragged_util.h"
 
 struct VocosBlock {
     float *dw_w = nullptr, *dw_b = nullptr, *ln_w = nullptr, *ln_b = nullptr, *gamma = nullptr;
@@ -113,13 +114,11 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* fw, const i
     out[gidx] = val / env;
 }
 
-// STFT magnitude -> HTK mel filterbank -> log(clamp(., 1e-5)); one block per (frame, batch)
-__global__ __launch_bounds__(256) void mel_frame_kernel(const float* wave, int nw, int T, int hop, int n_mels, const float* window,
-                                                        const float2* tw, const float* fb /*[513][n_mels]*/, float* mel, int pad, float mag_eps) {
-    __shared__ float2 s[1024];
-    __shared__ float mag[520];
-    const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const float* w = wave + (size_t)b * nw;
+// One frame of the mel front-ends, by a block of 256 threads: frame t of the wave w [nw] -> out[m * stride], m < n_mels.  The two kernels
+// below differ only in where a block finds its wave and puts its row, so an item's frame has the same bits from either.
+F5_DEVICE void mel_frame(float2* s /*[1024] LDS*/, float* mag /*[520] LDS*/, const float* w, int nw, int t, int hop, int n_mels, const float* window,
+                         const float2* tw, const float* fb /*[513][n_mels]*/, float* out, size_t stride, int pad, float mag_eps) {
+    const int tid = threadIdx.x;
     for (int n = tid; n < 1024; n += 256) {
         int idx = t * hop - pad + n;               // reflect padding by `pad` samples on both sides
         if (idx < 0) idx = -idx;
@@ -134,8 +133,30 @@ __global__ __launch_bounds__(256) void mel_frame_kernel(const float* wave, int n
         for (int k = 0; k <= 512; k++) acc += fb[k * n_mels + tid] * mag[k];
         // log(clamp(acc, 1e-5)), clamped on the log side: the device logf is ~2 ulp (1.6e-6) off at 1e-5, and silent bins are to hold the
         // fp32 value of log(1e-5) that the reference's front-end produces
-        mel[((size_t)b * n_mels + tid) * T + t] = fmaxf(logf(acc), -11.512925148f);
+        out[(size_t)tid * stride] = fmaxf(logf(acc), -11.512925148f);
     }
+}
+
+// STFT magnitude -> HTK mel filterbank -> log(clamp(., 1e-5)); one block per (frame, batch); mel [batch][n_mels][T]
+__global__ __launch_bounds__(256) void mel_frame_kernel(const float* wave, int nw, int T, int hop, int n_mels, const float* window,
+                                                        const float2* tw, const float* fb /*[513][n_mels]*/, float* mel, int pad, float mag_eps) {
+    __shared__ float2 s[1024];
+    __shared__ float mag[520];
+    const int t = blockIdx.x, b = blockIdx.y;
+    mel_frame(s, mag, wave + (size_t)b * nw, nw, t, hop, n_mels, window, tw, fb, mel + (size_t)b * n_mels * T + t, (size_t)T, pad, mag_eps);
+}
+
+// The same for n clips of their own lengths in one launch (f5hip_mel_spectrogram_ragged): one block per frame of the packed output
+// mel [sum T][n_mels] (frame-major: the sampler's cond layout); the block finds its clip by bisection of the clips' first rows.  Each clip
+// is read through its own pointer and reflect-padded at its own bounds.
+struct MelItem { const float* w; int nw, row0; };   // a clip, its samples, its first row of the packed output
+__global__ __launch_bounds__(256) void mel_frame_ragged_kernel(const MelItem* __restrict__ items, int n, int hop, int n_mels, const float* window,
+                                                               const float2* tw, const float* fb, float* mel, int pad, float mag_eps) {
+    __shared__ float2 s[1024];
+    __shared__ float mag[520];
+    const int row = blockIdx.x;
+    const MelItem it = items[last_at_or_before<&MelItem::row0>(items, n, row)];
+    mel_frame(s, mag, it.w, it.nw, row - it.row0, hop, n_mels, window, tw, fb, mel + (size_t)row * n_mels, 1, pad, mag_eps);
 }
 
 // ---------------------------------------------------------------------------------------- host side
@@ -355,10 +376,8 @@ static std::vector<float> htk_filterbank(int nf, int n_mels, int sr) { return me
 // librosa.filters.mel(sr, n_fft, n_mels, fmin=0, fmax=sr/2, htk=False, norm="slaney")
 static std::vector<float> slaney_filterbank(int nf, int n_mels, int sr) { return mel_filterbank(nf, n_mels, sr / 2.0, hz_to_mel_slaney, mel_to_hz_slaney, true); }
 
-// One mel front-end: its tables t (window, twiddles, filterbank(n_fft / 2 + 1, n_mels, sr)), rebuilt when (n_fft, n_mels, sr) changes,
-// then mel_frame_kernel over T frames at hop, the wave reflect-padded by `pad`
-static int mel_frames(MelTables& t, std::vector<float> (*filterbank)(int, int, int), int batch, int n_samples, const float* wave_dev, float* mel_dev,
-                      int n_fft, int hop, int n_mels, int sr, int pad, int T, float mag_eps, const char* name, hipStream_t st) {
+// The tables t of one mel front-end (window, twiddles, filterbank(n_fft / 2 + 1, n_mels, sr)), rebuilt when (n_fft, n_mels, sr) changes
+static int mel_tables(MelTables& t, std::vector<float> (*filterbank)(int, int, int), int n_fft, int n_mels, int sr) {
     if (t.n_fft != n_fft || t.n_mels != n_mels || t.sr != sr) {
         dev_free(t.window); dev_free(t.twiddle); dev_free(t.fb);
         t = MelTables();
@@ -367,6 +386,13 @@ static int mel_frames(MelTables& t, std::vector<float> (*filterbank)(int, int, i
         if (upload_f32(&t.fb, fb.data(), fb.size())) return -4;
         t.n_fft = n_fft; t.n_mels = n_mels; t.sr = sr;
     }
+    return 0;
+}
+
+// One mel front-end: its tables, then mel_frame_kernel over T frames at hop, the wave reflect-padded by `pad`
+static int mel_frames(MelTables& t, std::vector<float> (*filterbank)(int, int, int), int batch, int n_samples, const float* wave_dev, float* mel_dev,
+                      int n_fft, int hop, int n_mels, int sr, int pad, int T, float mag_eps, const char* name, hipStream_t st) {
+    CK(mel_tables(t, filterbank, n_fft, n_mels, sr));
     prof_begin(PROF_OTHER, st);
     hipLaunchKernelGGL(mel_frame_kernel, dim3(T, batch), dim3(256), 0, st, wave_dev, n_samples, T, hop, n_mels, t.window, t.twiddle, t.fb, mel_dev, pad, mag_eps);
     prof_end(PROF_OTHER, st);
@@ -392,4 +418,42 @@ int f5hip_mel_spectrogram_bigvgan(int32_t batch, int32_t n_samples, const float*
     const int pad = (n_fft - hop_length) / 2;
     return mel_frames(g_mel_bv, slaney_filterbank, batch, n_samples, wave_dev, mel_dev, n_fft, hop_length, n_mels, sample_rate, pad,
                       (n_samples + 2 * pad - n_fft) / hop_length + 1, 1e-9f, "mel_frame (bigvgan)", (hipStream_t)stream);
+}
+
+// ---- both front-ends for n clips of their own lengths, one launch (F5HipModel.prepare_voices: the reference mels of a batch's new voices)
+struct MelRaggedWorkspace { MelItem* items = nullptr; size_t cap_items = 0; };
+
+int f5hip_mel_spectrogram_ragged(int32_t n, const int32_t* n_samples, const float* const* wave_dev, float* mel_dev, int32_t n_fft, int32_t hop_length,
+                                 int32_t n_mels, int32_t sample_rate, int32_t variant, void* stream) {
+    if (variant != 0 && variant != 1) return fail(-1, "mel_spectrogram_ragged: unknown variant %d (0 vocos, 1 bigvgan)", variant);
+    if (n_fft != 1024 || n_mels < 1 || n_mels > 256) return fail(-1, "mel_spectrogram_ragged: only n_fft = 1024, 1 <= n_mels <= 256");
+    if (hop_length < 1 || hop_length > n_fft || sample_rate < 2) return fail(-1, "mel_spectrogram_ragged: need 1 <= hop_length <= n_fft, sample_rate >= 2");
+    if (n < 1 || !n_samples || !wave_dev || !mel_dev) return fail(-1, "mel_spectrogram_ragged: bad argument");
+    const int pad = variant ? (n_fft - hop_length) / 2 : n_fft / 2;
+    std::vector<MelItem> h(n);
+    long long rows = 0;
+    for (int i = 0; i < n; i++) {
+        const int nw = n_samples[i];
+        if (!wave_dev[i] || (variant ? nw < n_fft : nw <= n_fft / 2))
+            return fail(-1, "mel_spectrogram_ragged: clip %d has %d samples (needs %s %d) or no data", i, nw, variant ? ">=" : ">", variant ? n_fft : n_fft / 2);
+        if (reinterpret_cast<uintptr_t>(wave_dev[i]) & 3) return fail(-1, "mel_spectrogram_ragged: clip %d is not 4-byte aligned", i);
+        h[i] = MelItem{wave_dev[i], nw, (int)rows};
+        rows += variant ? (nw + 2 * pad - n_fft) / hop_length + 1 : 1 + nw / hop_length;   // the single-clip rule of the variant (>= 1)
+        if (rows * n_mels > 2147483647LL) return fail(-1, "mel_spectrogram_ragged: the output exceeds 2^31 - 1 values");
+    }
+    MelTables& t = variant ? g_mel_bv : g_mel;
+    CK(mel_tables(t, variant ? slaney_filterbank : htk_filterbank, n_fft, n_mels, sample_rate));
+    MelRaggedWorkspace* const ws = device_workspace<MelRaggedWorkspace>("mel_spectrogram_ragged");
+    if (!ws) return -6;
+    CK(dev_reserve(&ws->items, &ws->cap_items, (size_t)n, "mel_spectrogram_ragged clips"));
+    hipStream_t st = (hipStream_t)stream;
+    if (upload_sync(st, ws->items, h) != hipSuccess) return fail(-6, "mel_spectrogram_ragged metadata upload");
+    prof_begin(PROF_OTHER, st);
+    hipLaunchKernelGGL(mel_frame_ragged_kernel, dim3((unsigned)rows), dim3(256), 0, st, ws->items, n, hop_length, n_mels, t.window, t.twiddle, t.fb, mel_dev,
+                       pad, variant ? 1e-9f : 0.0f);
+    prof_end(PROF_OTHER, st);
+    CKL("mel_frame_ragged");
+    g_counters[CNT_MEL_RAGGED_LAUNCHES]++;
+    g_counters[CNT_MEL_RAGGED_ITEMS] += n;
+    return 0;
 }

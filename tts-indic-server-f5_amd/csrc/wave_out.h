@@ -21,12 +21,18 @@
 // chunk sample or one fade of two chunk samples, and the closed form above is the host's arithmetic operation for operation (ramp[i] =
 // i * (1.0 / (F - 1)), ramp[F - 1] = 1.0: np.linspace(0, 1, F)).  The silence test rms <= 10^(-50/20) * 32768 = 103.6 with rms =
 // int(sqrt(S / n)) is S < 104^2 n = 10816 n on the integer sum of squares S (n <= 24000: S / n cannot round up across 10816).
+// Segments (f5hip_wave_finish_joins: a multi-voice script).  Each chunk carries its own fade-in, F or 0: a chunk with 0 butts against the one
+// before it, which is np.concatenate of the cross_fade_concat of each run of fading chunks (infer.join_segments).  The closed form holds where
+// every chunk is at least as long as the fades it takes part in (F in, if it fades in, plus F out, if its successor does): then each
+// _cross_fade takes n = F on samples no earlier fade touched.  Butt-joined chunks may be a single sample long (a gap is a chunk of zeros), so
+// an 8-sample group can span several chunks and the slow path walks them.
 #pragma once
 #include "ragged_util.h"
 
 struct WfChunk {
     const float* x;
     int len, pos;        // samples; first joined sample the chunk covers (its fade-in included)
+    int fade;            // its fade-in: F where it cross-fades into the chunk before it, 0 where it butts against it (and for a first chunk)
 };
 struct WfReq {
     int chunk0, k;       // its chunks
@@ -62,7 +68,7 @@ F5_DEVICE float wf_sample(const WfChunk* __restrict__ ch, int c, int F, double s
 #pragma clang fp contract(off)
     const WfChunk cur = ch[c];
     const int i = j - cur.pos;
-    if (c > 0 && i < F) {
+    if (i < cur.fade) {   // (a request's first chunk has none)
         const WfChunk prev = ch[c - 1];
         const double a = (double)prev.x[prev.len - F + i] * wf_ramp(F - 1 - i, F, step);
         const double b = (double)cur.x[i] * wf_ramp(i, F, step);
@@ -96,7 +102,7 @@ __global__ __launch_bounds__(256) void wave_join_kernel(const WfReq* __restrict_
             const int i = (int)j - cur.pos;
             const long long body_end = c + 1 < q.k ? ch[c + 1].pos : q.n;   // one past the last joined sample that is this chunk's alone
             int v[8];   // the 8 quantised samples (a sample past the end is 0)
-            if ((c == 0 || i >= F) && j + 8 <= body_end) {
+            if (i >= cur.fade && j + 8 <= body_end) {
                 const float* p = cur.x + i;
                 float f[8];
                 if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
@@ -113,7 +119,7 @@ __global__ __launch_bounds__(256) void wave_join_kernel(const WfReq* __restrict_
                 for (int e = 0; e < 8; e++) {
                     v[e] = 0;
                     if (j + e < q.n) {
-                        if (c + 1 < q.k && ch[c + 1].pos <= j + e) c++;   // (a chunk starts at least one sample after the one before it: one step at most)
+                        while (c + 1 < q.k && ch[c + 1].pos <= j + e) c++;   // (butt-joined chunks may be shorter than the group: several steps)
                         v[e] = wf_quantise(wf_sample(ch, c, F, step, (int)(j + e)));
                     }
                 }
@@ -286,8 +292,9 @@ struct WfWorkspace {
     int* nranges = nullptr; size_t cap_nranges = 0;
 };
 
-int f5hip_wave_finish(int32_t n, const int32_t* chunks_per_request, const float* const* chunk_dev, const int32_t* chunk_len, int32_t fade,
-                      const uint8_t* remove_silence, int32_t sample_rate, int16_t* pcm_dev, int32_t* len_dev, void* stream) {
+int f5hip_wave_finish_joins(int32_t n, const int32_t* chunks_per_request, const float* const* chunk_dev, const int32_t* chunk_len, int32_t fade,
+                            const uint8_t* chunk_fade, const uint8_t* remove_silence, int32_t sample_rate, int16_t* pcm_dev, int32_t* len_dev,
+                            void* stream) {
     if (n < 1 || !chunks_per_request || !chunk_dev || !chunk_len || !pcm_dev || !len_dev) return fail(-1, "wave_finish: bad argument");
     if (sample_rate != 24000) return fail(-1, "wave_finish: the sample rate must be 24000 (got %d)", sample_rate);
     if (fade < 0) return fail(-1, "wave_finish: the fade length must not be negative (got %d)", fade);
@@ -308,14 +315,20 @@ int f5hip_wave_finish(int32_t n, const int32_t* chunks_per_request, const float*
             const size_t ci = hc.size();
             const int len = chunk_len[ci];
             if (!chunk_dev[ci] || len < 1) return fail(-1, "wave_finish: chunk %d of request %d is empty", c, i);
-            if (k > 1 && F > 0 && len < 2 * (long long)F)
+            // without chunk_fade every join fades; with it chunk c fades into its predecessor where chunk_fade[c] is set, else butts against it
+            const int fin = c > 0 && (!chunk_fade || chunk_fade[ci]) ? F : 0;
+            const int fout = c + 1 < k && (!chunk_fade || chunk_fade[ci + 1]) ? F : 0;
+            if (!chunk_fade && k > 1 && F > 0 && len < 2 * (long long)F)
                 return fail(-1, "wave_finish: chunk %d of request %d has %d samples, fewer than 2 x fade = %lld: its fades would overlap", c, i, len,
                             2 * (long long)F);
+            if (len < (long long)fin + fout)
+                return fail(-1, "wave_finish: chunk %d of request %d has %d samples, fewer than its fades (%d in, %d out): they would overlap", c, i,
+                            len, fin, fout);
             if (reinterpret_cast<uintptr_t>(chunk_dev[ci]) & 3) return fail(-1, "wave_finish: chunk %d of request %d is not 4-byte aligned", c, i);
-            if (c > 0) pos -= F;
+            pos -= fin;   // (pos never decreases along a request: len >= fin + fout; where two chunks share one, the later owns the sample)
             total_in += len;
             if (total_in > 2147483647LL) return fail(-1, "wave_finish: the chunks of the call exceed 2^31 - 1 samples");
-            hc.push_back(WfChunk{chunk_dev[ci], len, (int)pos});
+            hc.push_back(WfChunk{chunk_dev[ci], len, (int)pos, fin});
             pos += len;
         }
         q.n = (int)pos;   // (<= total_in)
@@ -369,6 +382,11 @@ int f5hip_wave_finish(int32_t n, const int32_t* chunks_per_request, const float*
     }
     g_counters[CNT_WAVE_REQUESTS] += n;
     return 0;
+}
+
+int f5hip_wave_finish(int32_t n, const int32_t* chunks_per_request, const float* const* chunk_dev, const int32_t* chunk_len, int32_t fade,
+                      const uint8_t* remove_silence, int32_t sample_rate, int16_t* pcm_dev, int32_t* len_dev, void* stream) {
+    return f5hip_wave_finish_joins(n, chunks_per_request, chunk_dev, chunk_len, fade, nullptr, remove_silence, sample_rate, pcm_dev, len_dev, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ delivery format: sample rate and G.711

@@ -250,17 +250,113 @@ class StreamJoiner:
         held, self.held = self.held, None
         return held if held is not None else np.zeros(0, dtype=np.float32)
 
-    def pieces(self, waves=(), flush=False):
-        """What a stream hands on: the non-empty pieces that pushing `waves` one after the other releases -- with `flush`, the held rest behind
-        them -- each as float32."""
+    def cut(self):
+        """A butt join (`join_segments`: between two pieces of a script, around a gap): releases what is held -- nothing fades into it any
+        more -- and the next `push` starts without a fade, like the first one."""
+        self.total = 0
+        return self.flush()
+
+    def pieces(self, waves=(), flush=False, cut=False):
+        """What a stream hands on: the non-empty pieces that pushing `waves` one after the other releases -- with `flush` or `cut`, the held
+        rest behind them -- each as float32."""
         for wave in waves:
             piece = self.push(wave)
             if len(piece):
                 yield np.asarray(piece, dtype=np.float32)
-        if flush:
-            piece = self.flush()
+        if flush or cut:
+            piece = self.cut() if cut else self.flush()
             if len(piece):
                 yield np.asarray(piece, dtype=np.float32)
+
+
+def join_segments(chunk_waves_per_segment, cross_fade_duration=cross_fade_duration, gap_samples=0):
+    """The wave of a multi-voice script (F/infer/infer_cli.py:198-208): `np.concatenate` of `cross_fade_concat(segment)` per segment -- the
+    chunks of one voice's piece are cross-faded, the pieces butt against each other -- with `gap_samples` float32 zeros between consecutive
+    segments (0: the reference's `np.concatenate` exactly), as float32 like `request_wave`."""
+    parts = []
+    for i, waves in enumerate(chunk_waves_per_segment):
+        if i and gap_samples > 0:
+            parts.append(np.zeros(int(gap_samples), dtype=np.float32))
+        parts.append(cross_fade_concat(list(waves), cross_fade_duration))
+    return np.asarray(np.concatenate(parts), dtype=np.float32)
+
+
+MAX_SCRIPT_SEGMENTS = 64
+MAX_SCRIPT_GAP = 5.0   # seconds
+
+
+def check_script_gap(gap) -> float:
+    """A script's `gap` in seconds, refused with ValueError unless it is a number with 0 <= gap <= `MAX_SCRIPT_GAP`."""
+    if isinstance(gap, bool) or not isinstance(gap, (int, float)) or not (math.isfinite(gap) and 0 <= gap <= MAX_SCRIPT_GAP):
+        raise ValueError(f"gap must be a number of seconds between 0 and {MAX_SCRIPT_GAP:g} (got {gap!r})")
+    return float(gap)
+
+
+class ScriptRequest:
+    """A multi-voice script as ONE request, accepted wherever `infer_requests`, `SpanScheduler.admit` and `SpanScheduler.prepare` accept a
+    request tuple: `segments` = [(ref_audio | PreparedVoice, ref_text, text[, speed])], one per piece in order, each planned like a plain
+    request with its own voice, chunking and (optionally) speed; `options` as a plain request's fourth element (`REQUEST_OPTIONS`: they
+    hold for every segment, `speed` where a segment names none, and `remove_silence` / `sample_rate` / `encoding` apply to the joined
+    script); `gap`: seconds of silence between consecutive segments, 0 <= gap <= 5, int(gap * 24000) samples.  Its result is
+    `join_segments` of its segments' chunk waves, finished like a plain request's joined wave.  With every `text` a list of chunk texts
+    (a streamed script's tail) the result is the per-chunk waves, one list per segment, for the caller's cut-aware `StreamJoiner`.
+    Refused here with ValueError: no segment or more than 64, a malformed segment, an empty text, texts of both kinds, a gap out of range."""
+
+    def __init__(self, segments, options=None, gap=0.0):
+        segments = [tuple(seg) for seg in segments]
+        if not 1 <= len(segments) <= MAX_SCRIPT_SEGMENTS:
+            raise ValueError(f"a script needs between 1 and {MAX_SCRIPT_SEGMENTS} pieces (got {len(segments)})")
+        for i, seg in enumerate(segments):
+            if len(seg) not in (3, 4):
+                raise ValueError(f"script segment {i}: expected (ref_audio, ref_text, text[, speed]), got {len(seg)} elements")
+            text = seg[2]
+            if isinstance(text, (list, tuple)):
+                ok = len(text) > 0 and all(isinstance(t, str) and t.strip() for t in text)
+            else:
+                ok = isinstance(text, str) and bool(text.strip())
+            if not ok:
+                raise ValueError(f"script segment {i} has no text to synthesize")
+            if not isinstance(seg[1], str) or not seg[1].strip():
+                raise ValueError(f"script segment {i}: the reference text cannot be empty")
+            if len(seg) == 4 and seg[3] is not None and not (isinstance(seg[3], (int, float)) and math.isfinite(seg[3]) and seg[3] > 0):
+                raise ValueError(f"script segment {i}: speed must be a positive number (got {seg[3]!r})")
+        kinds = {isinstance(seg[2], (list, tuple)) for seg in segments}
+        if len(kinds) > 1:
+            raise ValueError("a script's texts are all strings, or all lists of chunk texts (a streamed script's tail)")
+        self.segments, self.options, self.gap = segments, dict(options or {}), check_script_gap(gap)
+        self.chunked = kinds.pop()
+
+    @property
+    def gap_samples(self) -> int:
+        return int(self.gap * target_sample_rate)
+
+    @property
+    def text(self):
+        """What `finish_requests` takes as the request's text: a list (per-chunk waves come back) for a chunked script, else a string."""
+        return [seg[2] for seg in self.segments] if self.chunked else " ".join(seg[2] for seg in self.segments)
+
+
+class SegmentedWaves(list):
+    """The chunk waves of a script request for `finish_requests`: one list of chunk waves per segment, and the gap between segments."""
+
+    def __init__(self, segments, gap_samples=0):
+        super().__init__(list(waves) for waves in segments)
+        self.gap_samples = int(gap_samples)
+
+
+def request_voices(request):
+    """The reference voices of a request tuple or `ScriptRequest` as they were handed in (paths, pairs, `PreparedVoice`s), one per segment."""
+    return [seg[0] for seg in request.segments] if isinstance(request, ScriptRequest) else [request[0]]
+
+
+def request_text(request):
+    return request.text if isinstance(request, ScriptRequest) else request[2]
+
+
+def request_chunk_waves(plan, groups):
+    """`_chunk_waves`' output for a plan's groups -> what `finish_requests` takes for the request."""
+    waves = [w for w, _ in groups]
+    return SegmentedWaves(waves, plan.script.gap_samples) if plan.script is not None else waves[0]
 
 
 class PreparedVoice:
@@ -310,7 +406,8 @@ def prepare_voices(clips, target_rms=0.1, device="cuda"):
     """The reference-audio front-end (mono mix, rms, gain, resampling to 24 kHz) of several voices at once on the device: one upload of the
     packed clips and ONE `ops.ref_frontend` call (two launches) per distinct sample rate, then one download of all rms values.
     `clips` = [(wave [ch, n] fp32, sr)] -> [PreparedVoice], or deferred `PreparedVoice`s, which are filled in place (and returned).
-    The mel stays lazy (`cond`), one call per clip.  `device=None` runs the host `_prepare_reference` clip by clip instead (what a model
+    The mel stays lazy here (`cond`), one call per clip; a model object with `cond_mel_ragged` (`F5HipModel.prepare_voices`) fills the mel of
+    every voice this call prepared in one launch behind it.  `device=None` runs the host `_prepare_reference` clip by clip instead (what a model
     object without the device front-end gets: the reference's modules, CPU stand-ins) and leaves the result on the host, like the eager
     constructor does."""
     voices = [c if isinstance(c, PreparedVoice) else PreparedVoice.deferred(c, target_rms) for c in clips]
@@ -480,23 +577,30 @@ def needs_whole_wave(opts, streamed=False) -> bool:
 def plan_request(request, defaults, *, target_rms, fix_duration, device, tokenizer):
     """One request tuple (ref_audio, ref_text, gen_text[, options]) of `infer_requests` / `SpanScheduler.admit`, planned: `opts` (the
     options over `defaults`, unknown ones rejected), `voice` (prepared), `units` (one per chunk; the text is chunked unless it is a list
-    of chunk texts) and `generator`, the request's noise source (None: the global one).  A `generator` the request carries is drawn from
+    of chunk texts) and `generator`, the request's noise source (None: the global one).  A `ScriptRequest` is planned segment by segment:
+    `parts` = [(voice, units)] per segment (a plain request has one part), `units` all of them in order -- one generator, so chunk k of the
+    script draws after chunks 0..k-1 of the whole script -- `voice` the first segment's, `script` the request itself (None: a tuple).  A `generator` the request carries is drawn from
     on a copy: `commit()` moves the caller's to where the copy got, once the caller knows that the request went through."""
-    ref_audio, ref_text, gen_text = request[:3]
-    opts = dict(defaults, **(request[3] if len(request) > 3 and request[3] else {}))
+    script = request if isinstance(request, ScriptRequest) else None
+    own_opts = script.options if script is not None else (request[3] if len(request) > 3 and request[3] else {})
+    opts = dict(defaults, **own_opts)
     unknown = set(opts) - set(REQUEST_OPTIONS) - {"generator"}
     if unknown:
         raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
-    if needs_whole_wave(opts) and isinstance(gen_text, (list, tuple)):
+    if needs_whole_wave(opts) and isinstance(request_text(request), (list, tuple)):
         raise ValueError(WHOLE_WAVE)
-    voice, units = _plan_request(ref_audio, ref_text, gen_text, target_rms, opts["speed"], fix_duration, device, tokenizer)
+    # one (voice, units) part per segment; a plain request is its own single segment
+    segments = script.segments if script is not None else [tuple(request[:3])]
+    parts = [_plan_request(seg[0], seg[1], seg[2], target_rms, seg[3] if len(seg) > 3 and seg[3] is not None else opts["speed"], fix_duration,
+                           device, tokenizer) for seg in segments]
+    voice, units = parts[0][0], [u for _, us in parts for u in us]
     own = opts.get("generator")
     gen = torch.Generator().set_state(own.get_state()) if own is not None else request_generator(opts["seed"])
 
     def commit():
         if own is not None:
             own.set_state(gen.get_state())
-    return types.SimpleNamespace(voice=voice, units=units, opts=opts, generator=gen, commit=commit)
+    return types.SimpleNamespace(voice=voice, units=units, opts=opts, generator=gen, commit=commit, parts=parts, script=script)
 
 
 def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, target_rms=target_rms,
@@ -538,23 +642,27 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     list of chunk texts.  `sample_rate` (one of OUTPUT_SAMPLE_RATES) and `encoding` ("pcm16", "mulaw", "alaw"), per request: the delivery
     format, a pure function of the request's 24 kHz int16 PCM (`deliver_pcm16`: after silence removal, `resample_pcm16`, then `encode_g711`);
     such a request's wave is int16 at that rate or uint8 code bytes, its triple names that rate, and like `remove_silence` it needs the whole
-    wave.  `finish` = dict(device_backend=..., want=...): what the serving path asks for -- the list of `finish_requests`
+    wave.  A `ScriptRequest` (a multi-voice script: one segment per piece, each with its own voice) is accepted in place of a tuple: its
+    segments' units ride in the same sampler call, one prompt per unit, and the same vocoder call, one group per segment; its triple is
+    (`join_segments` of its segments' chunk waves, rate, [spectrogram per segment]), with `join=False` the chunk waves and spectrograms per
+    segment, and its whole-wave options apply to the joined script.  `finish` = dict(device_backend=..., want=...): what the serving path asks for -- the list of `finish_requests`
     results (one wave per request, no triples) with no spectrogram downloaded."""
     defaults = dict(speed=speed, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None)
     calls = {}   # calls: (nfe_step, sway, ode_method) -> [unit ids, ...] of one sampler call each
     flat_units, flat_cond, flat_audio, flat_cfg, flat_gen, flat_grid = [], [], [], [], [], []
     plans = [plan_request(req, defaults, target_rms=target_rms, fix_duration=fix_duration, device=device, tokenizer=tokenizer) for req in requests]
-    _prepare_deferred([plan.voice for plan in plans], model_obj)   # uploaded clips: one ragged front-end call for all of them
+    _prepare_deferred([voice for plan in plans for voice, _ in plan.parts], model_obj)   # uploaded clips: one ragged front-end call for all of them
     for plan in plans:
-        voice, units, opts = plan.voice, plan.units, plan.opts
+        opts = plan.opts
         key = (int(opts["nfe_step"]), opts["sway_sampling_coef"], opts.get("ode_method"))
-        calls.setdefault(key, []).extend(range(len(flat_units), len(flat_units) + len(units)))
-        flat_units += units
-        flat_cond += [voice.cond(model_obj)] * len(units)
-        flat_audio += [voice.audio] * len(units)
-        flat_cfg += [opts["cfg_strength"]] * len(units)
-        flat_gen += [plan.generator] * len(units)
-        flat_grid += [key] * len(units)
+        for voice, units in plan.parts:   # (a script: its segments one after the other, each unit with its own voice's prompt)
+            calls.setdefault(key, []).extend(range(len(flat_units), len(flat_units) + len(units)))
+            flat_units += units
+            flat_cond += [voice.cond(model_obj)] * len(units)
+            flat_audio += [voice.audio] * len(units)
+            flat_cfg += [opts["cfg_strength"]] * len(units)
+            flat_gen += [plan.generator] * len(units)
+            flat_grid += [key] * len(units)
     if len(calls) > 1 and getattr(model_obj, "per_unit_time_grids", False):
         calls = {None: list(range(len(flat_units)))}   # one call for every grid
     mels = [None] * len(flat_units)
@@ -571,20 +679,34 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     groups, k = [], 0
     for plan in plans:
         plan.commit()   # every sampler call went through: the caller's generator moves
-        groups.append((mels[k:k + len(plan.units)], plan.voice.ref_frames, plan.voice.rms))
-        k += len(plan.units)
+        for voice, units in plan.parts:   # one group per segment: each voice's rms is restored on its own chunks
+            groups.append((mels[k:k + len(units)], voice.ref_frames, voice.rms))
+            k += len(units)
+    per_plan = np.cumsum([0] + [len(plan.parts) for plan in plans])   # a plan's groups: [per_plan[i], per_plan[i + 1])
     silence = [bool(plan.opts.get("remove_silence")) for plan in plans]
     formats = [delivery_format(plan.opts.get("sample_rate"), plan.opts.get("encoding")) for plan in plans]
     if finish is not None:
         backend = bool(finish.get("device_backend"))
-        chunk_waves = [waves for waves, _ in _chunk_waves(groups, vocoder, mel_spec_type, target_rms, on_device=backend, want_specs=False)]
-        return finish_requests(chunk_waves, [req[2] for req in requests], cross_fade_duration, silence, sample_rate=[f[0] for f in formats],
+        got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms, on_device=backend, want_specs=False)
+        chunk_waves = [request_chunk_waves(plan, got[per_plan[i]:per_plan[i + 1]]) for i, plan in enumerate(plans)]
+        return finish_requests(chunk_waves, [request_text(req) for req in requests], cross_fade_duration, silence, sample_rate=[f[0] for f in formats],
                                encoding=[f[1] for f in formats], **finish)
     whole = [needs_whole_wave(plan.opts) for plan in plans]
     if any(whole) and not join:
         raise ValueError(WHOLE_WAVE)
     out = []
-    for needs, flag, fmt, (waves, specs) in zip(whole, silence, formats, _chunk_waves(groups, vocoder, mel_spec_type, target_rms)):
+    got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms)
+    for i, (plan, needs, flag, fmt) in enumerate(zip(plans, whole, silence, formats)):
+        mine = got[per_plan[i]:per_plan[i + 1]]
+        if plan.script is not None:   # (wave, rate, [spectrogram per segment]) like `infer_multi_voice`; join=False: per-segment lists
+            seg_specs = [np.concatenate(specs, axis=1) for _, specs in mine]
+            if needs or join:
+                wave, = finish_requests([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1])
+                out.append((wave, fmt[0], seg_specs))
+            else:
+                out.append(([waves for waves, _ in mine], target_sample_rate, [specs for _, specs in mine]))
+            continue
+        (waves, specs), = mine
         if needs:
             wave, = finish_requests([waves], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1])
             out.append((wave, fmt[0], np.concatenate(specs, axis=1)))
@@ -628,7 +750,9 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
                     want="float", sample_rate=None, encoding=None):
     """From the chunk waves of several requests (rms restored; numpy, or tensors as `_chunk_waves(on_device=True)` leaves them) to what each
     request gets.  A request whose text is a list of chunk texts (a streamed request's head or tail) gets its chunk waves as they are, like
-    `request_wave`.  Any other request gets its joined wave: float32 (`request_wave`) with want="float", int16 PCM (`quantise_pcm16` of that)
+    `request_wave`; a script's (`SegmentedWaves`: one list of chunk waves per segment) as one list per segment.  Any other request gets its
+    joined wave -- `join_segments` for a script, which is eligible for the device call when every chunk is at least as long as the fades it
+    takes part in (`_script_on_device`) and then rides in the same single call, `ops.wave_finish_joins` --: float32 (`request_wave`) with want="float", int16 PCM (`quantise_pcm16` of that)
     with want="pcm16" -- and, with its `remove_silence` flag set, `audio_prep.remove_silence_pcm` of that PCM whatever `want` says.
 
     `device_backend=True` (needs want="pcm16") makes ONE `ops.wave_finish` call for all eligible requests of the batch -- join, quantisation
@@ -656,11 +780,15 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     fade = int(cross_fade_duration * target_sample_rate) if cross_fade_duration > 0 else 0
     out, on_device = [None] * n, []
     for i, (waves, text) in enumerate(zip(chunk_waves_per_request, gen_texts)):
+        script = isinstance(waves, SegmentedWaves)
         if isinstance(text, (list, tuple)):
             if needs_whole_wave(dict(remove_silence=flags[i], sample_rate=formats[i][0], encoding=formats[i][1])):
                 raise ValueError(WHOLE_WAVE)
-            out[i] = [_host_chunk(w) for w in waves]
-        elif device_backend and all(torch.is_tensor(w) and w.is_cuda for w in waves) and (len(waves) == 1 or min(len(w) for w in waves) >= 2 * fade):
+            out[i] = [[_host_chunk(w) for w in seg] for seg in waves] if script else [_host_chunk(w) for w in waves]
+        elif script and device_backend and _script_on_device(waves, fade):
+            on_device.append(i)
+            continue
+        elif not script and device_backend and all(torch.is_tensor(w) and w.is_cuda for w in waves) and (len(waves) == 1 or min(len(w) for w in waves) >= 2 * fade):
             on_device.append(i)
             continue
         else:
@@ -669,15 +797,43 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     if on_device:
         # the plain requests first: their PCM is then one prefix of the packed buffer, and what comes down of it holds no other request's
         on_device.sort(key=lambda i: formats[i] != _PLAIN)
-        done = _finish_on_device([chunk_waves_per_request[i] for i in on_device], fade, [flags[i] for i in on_device], [formats[i] for i in on_device])
+        done = _finish_on_device([_device_request(chunk_waves_per_request[i]) for i in on_device], fade, [flags[i] for i in on_device],
+                                 [formats[i] for i in on_device])
         for i, wave in zip(on_device, done):
             out[i] = wave
     return out
 
 
+def _script_on_device(segments, fade):
+    """Whether the device back-end takes a script's chunk waves: all on a HIP device, and every chunk at least as long as the fades it
+    takes part in (`fade` if it fades into its predecessor, plus `fade` if its successor fades into it) -- where `join_segments`' nested
+    cross-fades take `fade` samples that no other fade touched, which is the kernel's closed form."""
+    if not all(torch.is_tensor(w) and w.is_cuda for seg in segments for w in seg):
+        return False
+    return all(len(w) >= (fade if c > 0 else 0) + (fade if c + 1 < len(seg) else 0) for seg in segments for c, w in enumerate(seg))
+
+
+def _device_request(waves):
+    """A request for `_finish_on_device`: (chunk waves, fades) -- `fades` None for a plain request (every join fades), else one bool per
+    chunk: a segment's first chunk butts against what is in front of it, and so does a gap (a chunk of zeros) and what follows it."""
+    if not isinstance(waves, SegmentedWaves):
+        return list(waves), None
+    chunks, fades = [], []
+    for i, seg in enumerate(waves):
+        if i and waves.gap_samples > 0:
+            chunks.append(torch.zeros(waves.gap_samples, dtype=torch.float32, device=seg[0].device))
+            fades.append(False)
+        chunks += list(seg)
+        fades += [False] + [True] * (len(seg) - 1)
+    return chunks, fades
+
+
 def _finish_on_host(waves, text, cross_fade_duration, flag, fmt, want):
     """`finish_requests` for one request on the host: join, quantisation, silence removal and the delivery format in numpy."""
-    wave = request_wave(text, [_host_chunk(w) for w in waves], cross_fade_duration)
+    if isinstance(waves, SegmentedWaves):
+        wave = join_segments([[_host_chunk(w) for w in seg] for seg in waves], cross_fade_duration, waves.gap_samples)
+    else:
+        wave = request_wave(text, [_host_chunk(w) for w in waves], cross_fade_duration)
     if flag:
         wave = remove_silence_pcm(quantise_pcm16(wave), target_sample_rate)
     elif want == "pcm16" or fmt != _PLAIN:
@@ -686,15 +842,20 @@ def _finish_on_host(waves, text, cross_fade_duration, flag, fmt, want):
 
 
 def _finish_on_device(requests, fade, silence, formats):
-    """`finish_requests` for the requests the device back-end takes: `requests` = their chunk waves (device tensors), the plain-format ones
-    first; `silence`, `formats` per request.  ONE `ops.wave_finish` call, then one `ops.wave_encode` call per distinct delivery format behind
-    it on the same stream.  Returns one result per request."""
+    """`finish_requests` for the requests the device back-end takes: `requests` = (chunk waves (device tensors), fades: `_device_request`), the
+    plain-format ones first; `silence`, `formats` per request.  ONE `ops.wave_finish` call -- `ops.wave_finish_joins` when a script is among
+    them -- then one `ops.wave_encode` call per distinct delivery format behind it on the same stream.  Returns one result per request."""
     from . import ops
     out = [None] * len(requests)
     plain = sum(fmt == _PLAIN for fmt in formats)
-    chunks = [w.to(torch.float32).contiguous() for waves in requests for w in waves]
-    joined = [sum(len(w) for w in waves) - (len(waves) - 1) * fade for waves in requests]
-    pcm, lengths, offsets = ops.wave_finish(chunks, [len(waves) for waves in requests], fade, silence, target_sample_rate)
+    chunks = [w.to(torch.float32).contiguous() for waves, _ in requests for w in waves]
+    fades = [[False] + [True] * (len(waves) - 1) if f is None else f for waves, f in requests]
+    joined = [sum(len(w) for w in waves) - sum(f[1:]) * fade for (waves, _), f in zip(requests, fades)]
+    counts = [len(waves) for waves, _ in requests]
+    if all(f is None for _, f in requests):
+        pcm, lengths, offsets = ops.wave_finish(chunks, counts, fade, silence, target_sample_rate)
+    else:
+        pcm, lengths, offsets = ops.wave_finish_joins(chunks, counts, fade, [x for f in fades for x in f], silence, target_sample_rate)
     if plain:
         if any(silence[:plain]):
             kept = lengths[:plain].cpu().tolist()
@@ -734,8 +895,10 @@ class SpanTicket:
     """One admitted request of a `SpanScheduler`: its planned units, what its planned options (`plan_request`'s `opts`) say about the finished
     wave, and -- once the units have all ended -- `result` (`request_wave`)."""
 
-    def __init__(self, request, voice, units, opts):
+    def __init__(self, request, voice, units, opts, parts=None, script=None):
         self.request, self.voice, self.units, self.remove_silence = request, voice, units, bool(opts.get("remove_silence"))
+        self.parts = parts if parts is not None else [(voice, units)]   # [(voice, its units)]: one per segment of a script
+        self.script = script
         self.sample_rate, self.encoding = delivery_format(opts.get("sample_rate"), opts.get("encoding"))
         self.in_flight = self.cancelled = self.done = False
         self.result = None
@@ -794,19 +957,22 @@ class SpanScheduler:
     def prepare(self, requests):
         """The device front-end of the deferred voices (`PreparedVoice.deferred`: uploaded clips) among `requests`, in ONE `prepare_voices`
         call, ahead of their `admit`; a voice that is still deferred at `admit` is prepared there, alone."""
-        _prepare_deferred([r[0] for r in requests if isinstance(r[0], PreparedVoice)], self.model_obj)
+        _prepare_deferred([v for r in requests for v in request_voices(r) if isinstance(v, PreparedVoice)], self.model_obj)
 
     def admit(self, request) -> SpanTicket:
         plan = plan_request(request, self.defaults, target_rms=self.target_rms, fix_duration=self.fix_duration, device=self.device,
                             tokenizer=self.tokenizer)
-        voice, opts = plan.voice, plan.opts
-        cond = voice.cond(self.model_obj)
+        opts = plan.opts
+        _prepare_deferred([voice for voice, _ in plan.parts], self.model_obj)   # (a script's uploads that are still deferred: one call)
         extra = {} if opts.get("ode_method") is None else dict(ode_method=opts["ode_method"])   # (handed on only when the request sets it)
-        planned = [self.model_obj.plan_unit(cond, tokens, frames, steps=int(opts["nfe_step"]), cfg_strength=opts["cfg_strength"],
-                                            sway_sampling_coef=opts["sway_sampling_coef"], generator=plan.generator, **extra)
-                   for tokens, frames in plan.units]
+        parts = []
+        for voice, units in plan.parts:   # segment after segment: the noise is drawn in the script's flat chunk order
+            cond = voice.cond(self.model_obj)
+            parts.append((voice, [self.model_obj.plan_unit(cond, tokens, frames, steps=int(opts["nfe_step"]), cfg_strength=opts["cfg_strength"],
+                                                           sway_sampling_coef=opts["sway_sampling_coef"], generator=plan.generator, **extra)
+                                  for tokens, frames in units]))
         plan.commit()   # every chunk was planned: the caller's generator moves
-        ticket = SpanTicket(request, voice, planned, opts)
+        ticket = SpanTicket(request, plan.voice, [u for _, us in parts for u in us], opts, parts, plan.script)
         self.waiting.append(ticket)
         return ticket
 
@@ -827,10 +993,11 @@ class SpanScheduler:
             self.in_flight.append(ticket)
 
     def _finish(self, tickets):
-        groups = [([u.mel for u in t.units], t.voice.ref_frames, t.voice.rms) for t in tickets]
-        chunk_waves = [waves for waves, _ in _chunk_waves(groups, self.vocoder, self.mel_spec_type, self.target_rms, on_device=self.device_backend,
-                                                          want_specs=False)]
-        results = finish_requests(chunk_waves, [t.request[2] for t in tickets], self.cross_fade_duration, [t.remove_silence for t in tickets],
+        groups = [([u.mel for u in units], voice.ref_frames, voice.rms) for t in tickets for voice, units in t.parts]   # one per segment
+        got = _chunk_waves(groups, self.vocoder, self.mel_spec_type, self.target_rms, on_device=self.device_backend, want_specs=False)
+        first = np.cumsum([0] + [len(t.parts) for t in tickets])
+        chunk_waves = [request_chunk_waves(t, got[first[i]:first[i + 1]]) for i, t in enumerate(tickets)]
+        results = finish_requests(chunk_waves, [request_text(t.request) for t in tickets], self.cross_fade_duration, [t.remove_silence for t in tickets],
                                   device_backend=self.device_backend, want="pcm16" if self.device_backend else "float",
                                   sample_rate=[t.sample_rate for t in tickets], encoding=[t.encoding for t in tickets])
         for t, result in zip(tickets, results):

@@ -5,7 +5,9 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+import numpy as np
+
+from . import _lib, torch_ops
 
 
 def _out(b, n_mels, frames, device):
@@ -48,3 +50,47 @@ def mel_spectrogram_bigvgan(wave: torch.Tensor, n_fft=1024, hop_length=256, n_me
                                                         hop_length, n_mel_channels, target_sample_rate,
                                                         _lib.current_stream_ptr()), "f5hip_mel_spectrogram_bigvgan")
     return mel
+
+
+MEL_VARIANTS = ("vocos", "bigvgan")   # the library's variant codes 0, 1
+
+
+def mel_frames(n_samples, variant, n_fft=1024, hop_length=256):
+    """Frames of a clip of `n_samples`: the single-clip rule of `mel_spectrogram` ("vocos") or `mel_spectrogram_bigvgan` ("bigvgan")."""
+    return 1 + n_samples // hop_length if variant == "vocos" else (n_samples + 2 * ((n_fft - hop_length) // 2) - n_fft) // hop_length + 1
+
+
+@torch.no_grad()
+def mel_spectrogram_ragged(waves, variant="vocos", n_fft=1024, hop_length=256, n_mel_channels=100, target_sample_rate=24000):
+    """Both front-ends for several clips of their own lengths in ONE library call and one launch (include/f5hip.h
+    f5hip_mel_spectrogram_ragged): `waves` = one 1-D contiguous fp32 device tensor per clip (views of a packed buffer are read in place).
+    Returns (mel [sum T, n_mels] fp32 device, frame-major and packed in clip order, [T_i]); clip i's rows equal
+    `mel_spectrogram(clip_i[None])[0].T` (resp. `mel_spectrogram_bigvgan`) bit for bit."""
+    if variant not in MEL_VARIANTS:
+        raise _lib.F5HipError(f"mel_spectrogram_ragged: unknown variant {variant!r} (one of {list(MEL_VARIANTS)})")
+    waves = list(waves)
+    if not waves:
+        raise _lib.F5HipError("mel_spectrogram_ragged: no clips")
+    for w in waves:
+        if not (torch.is_tensor(w) and w.dtype == torch.float32 and w.is_cuda and w.dim() == 1 and w.is_contiguous() and w.device == waves[0].device):
+            raise _lib.F5HipError("mel_spectrogram_ragged: every clip must be a contiguous 1-D fp32 tensor on one HIP device (no CPU fallback)")
+    code = MEL_VARIANTS.index(variant)
+    short = n_fft if code else n_fft // 2 + 1
+    for i, w in enumerate(waves):
+        if w.numel() < short:
+            raise _lib.F5HipError(f"mel_spectrogram_ragged: clip {i} has {w.numel()} samples (the {variant} front-end needs at least {short})")
+    frames = [mel_frames(int(w.numel()), variant, n_fft, hop_length) if hop_length > 0 else 0 for w in waves]
+    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
+        try:
+            mel = torch_ops.ops().mel_spectrogram_ragged(waves, n_fft, hop_length, n_mel_channels, target_sample_rate, code)
+        except RuntimeError as e:   # c10::Error from the operator's checks or the library
+            raise _lib.F5HipError(str(e)) from e
+    else:
+        ptrs = np.array([w.data_ptr() for w in waves], dtype=np.uint64)
+        lens = np.array([w.numel() for w in waves], dtype=np.int32)
+        with torch.cuda.device(waves[0].device):
+            mel = torch.empty(max(sum(frames), 0), max(n_mel_channels, 0), device=waves[0].device, dtype=torch.float32)
+            _lib.check(_lib.lib().f5hip_mel_spectrogram_ragged(len(waves), C.c_void_p(lens.ctypes.data), C.c_void_p(ptrs.ctypes.data), C.c_void_p(mel.data_ptr()),
+                                                               n_fft, hop_length, n_mel_channels, target_sample_rate, code, _lib.current_stream_ptr()),
+                       "f5hip_mel_spectrogram_ragged")
+    return mel, frames

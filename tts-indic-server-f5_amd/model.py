@@ -312,11 +312,27 @@ class F5HipModel:
         assert cond.shape[-1] == self.num_channels
         return cond
 
+    def cond_mel_ragged(self, audios):
+        """`cond_mel` for several reference waves of their own lengths ([1, nw] or [nw] each, on this model's device) in ONE launch
+        (f5hip_mel_spectrogram_ragged): [mel_i [1, n_i, mel]], views of one packed buffer, each `cond_mel(audio_i)` bit for bit."""
+        from .mel import mel_spectrogram_ragged
+        waves = [a.to(self.device, torch.float32).reshape(-1) for a in audios]   # (views: a prepared voice's wave is read where it lies)
+        mel, frames = mel_spectrogram_ragged(waves, "bigvgan" if self.mel_spec_type == "bigvgan" else "vocos", n_mel_channels=self.num_channels)
+        return [m[None] for m in mel.split(frames)]
+
     def prepare_voices(self, voices):
         """The reference-audio front-end of deferred `infer.PreparedVoice`s on this model's device: `infer.prepare_voices`, one ragged
-        f5hip_ref_frontend call per distinct sample rate."""
-        from .infer import prepare_voices
-        return prepare_voices(voices, device=self.device)
+        f5hip_ref_frontend call per distinct sample rate -- and then the reference mel of every voice it just prepared in ONE
+        `cond_mel_ragged` call, read straight from the front-end's packed output (a script that brings four uploads launches one mel kernel,
+        not four back to back)."""
+        from .infer import PreparedVoice, prepare_voices
+        ready = {id(v) for v in voices if isinstance(v, PreparedVoice) and v.pending is None}
+        out = prepare_voices(voices, device=self.device)
+        fresh = list({id(v): v for v in out if id(v) not in ready and v.mel is None}.values())
+        if fresh:
+            for v, mel in zip(fresh, self.cond_mel_ragged([v.audio for v in fresh])):
+                v.mel = mel
+        return out
 
     @torch.no_grad()
     def sample_units(self, audio, units, *, steps=32, cfg_strength=2.0, sway_sampling_coef=-1.0, seed=None, generators=None, y0=None,

@@ -376,6 +376,24 @@ def wave_finish(chunks, chunks_per_request, fade, remove_silence=None, sample_ra
     `audio_prep.remove_silence_pcm`'s rule.  Returns (pcm int16 device, lengths [n] int32 device, offsets): request i's samples are
     pcm[offsets[i] : offsets[i] + lengths[i]].  Refused (F5HipError): a chunk shorter than 2 * fade in a request of several chunks, a negative
     fade, a rate other than 24 000, more than 2^31 - 1 samples."""
+    return _wave_finish(chunks, chunks_per_request, fade, None, remove_silence, sample_rate)
+
+
+def wave_finish_joins(chunks, chunks_per_request, fade, chunk_fade, remove_silence=None, sample_rate=24000):
+    """`wave_finish` with a choice per join (include/f5hip.h f5hip_wave_finish_joins): `chunk_fade` one bool per chunk of the call -- True: the
+    chunk cross-fades into the one before it in its request over `fade` samples, False: it butts against it (a request's first chunk is
+    ignored) -- so a multi-voice script's request is joined as `infer.join_segments` joins it, a gap being a chunk of zeros.  None is
+    `wave_finish`.  Refused instead of the 2 * fade rule: a chunk shorter than the fades it takes part in (`fade` if it fades in, plus `fade`
+    if its successor does)."""
+    chunks = list(chunks)
+    if chunk_fade is not None:
+        chunk_fade = np.ascontiguousarray(np.asarray(chunk_fade, dtype=bool).astype(np.uint8))
+        if chunk_fade.ndim != 1 or len(chunk_fade) != len(chunks):
+            raise _lib.F5HipError(f"wave_finish_joins: chunk_fade needs one value per chunk ({len(chunks)}), got {chunk_fade.shape}")
+    return _wave_finish(chunks, chunks_per_request, fade, chunk_fade, remove_silence, sample_rate)
+
+
+def _wave_finish(chunks, chunks_per_request, fade, chunk_fade, remove_silence, sample_rate):
     k = np.ascontiguousarray(np.asarray(chunks_per_request, dtype=np.int32))
     flags = np.zeros(len(k), dtype=np.uint8) if remove_silence is None else np.ascontiguousarray(np.asarray(remove_silence, dtype=bool).astype(np.uint8))
     chunks = list(chunks)
@@ -387,12 +405,17 @@ def wave_finish(chunks, chunks_per_request, fade, remove_silence=None, sample_ra
     fade = int(fade)
     offsets, off, c = [], 0, 0
     for kk in k:
+        fading = int(kk) - 1 if chunk_fade is None else int(np.count_nonzero(chunk_fade[c + 1:c + kk]))
         offsets.append(off)
-        off += (sum(int(w.numel()) for w in chunks[c:c + kk]) - (int(kk) - 1) * max(fade, 0) + 7) & ~7
+        off += (sum(int(w.numel()) for w in chunks[c:c + kk]) - fading * max(fade, 0) + 7) & ~7
         c += int(kk)
     if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
         try:
-            pcm, lengths = torch_ops.ops().wave_finish(chunks, torch.from_numpy(k), fade, torch.from_numpy(flags), int(sample_rate))
+            if chunk_fade is None:
+                pcm, lengths = torch_ops.ops().wave_finish(chunks, torch.from_numpy(k), fade, torch.from_numpy(flags), int(sample_rate))
+            else:
+                pcm, lengths = torch_ops.ops().wave_finish_joins(chunks, torch.from_numpy(k), fade, torch.from_numpy(chunk_fade), torch.from_numpy(flags),
+                                                                 int(sample_rate))
         except RuntimeError as e:   # c10::Error from the operator's checks or the library
             raise _lib.F5HipError(str(e)) from e
     else:
@@ -402,8 +425,8 @@ def wave_finish(chunks, chunks_per_request, fade, remove_silence=None, sample_ra
         with torch.cuda.device(dev):
             pcm = torch.empty(max(off, 0), device=dev, dtype=torch.int16)
             lengths = torch.empty(len(k), device=dev, dtype=torch.int32)
-            _lib.check(_lib.lib().f5hip_wave_finish(len(k), _p(k), _p(ptrs), _p(lens), fade, _p(flags), int(sample_rate), _p(pcm), _p(lengths),
-                                                    _lib.current_stream_ptr()), "f5hip_wave_finish")
+            _lib.check(_lib.lib().f5hip_wave_finish_joins(len(k), _p(k), _p(ptrs), _p(lens), fade, _p(chunk_fade), _p(flags), int(sample_rate), _p(pcm),
+                                                          _p(lengths), _lib.current_stream_ptr()), "f5hip_wave_finish")
     return pcm, lengths, offsets
 
 

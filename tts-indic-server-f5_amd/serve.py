@@ -288,13 +288,16 @@ class ContinuousBatcher(_QueueWorker):
         ragged device call and the queued ones find their voice prepared when their turn comes.  Admission itself stays one request at a
         time, in order.  A failure here is logged and left to the admissions: each then prepares its own voice and fails alone."""
         prepare = getattr(self.scheduler, "prepare", None)
-        if prepare is None or getattr(request[0], "pending", None) is None:
+        def deferred(r):
+            return any(getattr(v, "pending", None) is not None for v in infer.request_voices(r))
+
+        if prepare is None or not deferred(request):
             return
         with self._q.mutex:
             queued = [item[0] for item in self._q.queue if item is not None and not item[1].cancelled()]
         try:
             with self._lock:
-                prepare([request] + [r for r in queued if getattr(r[0], "pending", None) is not None])
+                prepare([request] + [r for r in queued if deferred(r)])
         except Exception:   # noqa: BLE001
             log.exception("preparing uploaded reference clips together failed; each request now prepares its own")
 
@@ -626,16 +629,26 @@ class TTSManager:
         return self._serve(lambda: self._voice(ref_audio_path, ref_text), text, options, stream=True)
 
     def _stream(self, voice, ref_text, head, tail, opts=None):
-        lock, state = threading.Lock(), {"closed": False, "tail": None, "error": None}
-        started = threading.Event()
         opts = dict(opts or {})               # the delivery format is applied here, piece by piece: the head and tail requests stay plain
         fmt = infer.delivery_format(opts.pop("sample_rate", None), opts.pop("encoding", None))
+        return self._stream_requests(self._request(voice, ref_text, head, opts), self._request(voice, ref_text, tail, opts) if tail else None, fmt)
+
+    def _stream_requests(self, head_request, tail_request, fmt, tail_pieces=None):
+        """A stream of two requests: the head's chunk waves, then (unless None) the tail's, through one `infer.StreamJoiner` and the delivery
+        format `fmt`.  `tail_pieces(joiner, result)`: the pieces the tail's result releases (default: its chunk waves pushed in order; a
+        script cuts the joiner between its segments)."""
+        lock, state = threading.Lock(), {"closed": False, "tail": None, "error": None}
+        started = threading.Event()
+        tail = tail_request is not None
+        if tail_pieces is None:
+            def tail_pieces(joiner, waves):
+                return joiner.pieces(waves)
 
         def submit_tail():                        # on the batcher's thread, once the head's batch has formed
             with lock:
                 try:
                     if not state["closed"]:
-                        state["tail"] = self.batcher.submit(self._request(voice, ref_text, tail, opts))
+                        state["tail"] = self.batcher.submit(tail_request)
                 except Exception as e:    # noqa: BLE001 -- e.g. the batcher is closing: reported to the consumer
                     state["error"] = e
             started.set()
@@ -650,10 +663,10 @@ class TTSManager:
             joiner = infer.StreamJoiner(infer.cross_fade_duration)
             try:
                 if self.batcher is not None:
-                    head_f = self.batcher.submit(self._request(voice, ref_text, head, opts), on_start=submit_tail if tail else None)
+                    head_f = self.batcher.submit(head_request, on_start=submit_tail if tail else None)
                     head_waves = head_f.result(timeout=self.request_timeout_s)
                 else:
-                    head_waves = self._run_batch([self._request(voice, ref_text, head, opts)])[0]
+                    head_waves = self._run_batch([head_request])[0]
                 yield from joiner.pieces(head_waves)
                 if tail:
                     if self.batcher is not None:
@@ -664,8 +677,8 @@ class TTSManager:
                             return
                         tail_waves = state["tail"].result(timeout=self.request_timeout_s)
                     else:
-                        tail_waves = self._run_batch([self._request(voice, ref_text, tail, opts)])[0]
-                    yield from joiner.pieces(tail_waves)
+                        tail_waves = self._run_batch([tail_request])[0]
+                    yield from tail_pieces(joiner, tail_waves)
                 yield from joiner.pieces(flush=True)
             finally:                              # normal end, error, or the consumer closed the stream
                 cancel()
@@ -686,6 +699,87 @@ class TTSManager:
                 gen.close()
 
         return SynthesisStream(pieces() if fmt == (infer.target_sample_rate, "pcm16") else delivered(), cancel)
+
+    def _script_segments(self, text, voices, gap):
+        """The host part of a script request, every refusal a ValueError before anything is queued: `voices` needs "main", `text` at least
+        one non-empty piece and at most `infer.MAX_SCRIPT_SEGMENTS` (`infer.split_voice_tags`), `gap` its range; then each voice the text
+        uses is resolved once -- a registered one by `_voice`, an uploaded one by `_clip_voice` (its SHA-1 LRU, deferred with
+        `device_frontend`: the new clips of the script are then prepared in the ONE front-end call of the batch the script rides in).
+        Returns [(voice, ref_text, piece text, speed | None)]."""
+        if not isinstance(voices, dict) or "main" not in voices:
+            raise ValueError('voices needs a "main" entry')
+        if not isinstance(text, str) or not text.strip():
+            raise ValueError("Text to synthesize cannot be empty.")
+        pieces = infer.split_voice_tags(text, voices)
+        if not pieces:
+            raise ValueError("Text to synthesize cannot be empty.")
+        if len(pieces) > infer.MAX_SCRIPT_SEGMENTS:
+            raise ValueError(f"a script needs between 1 and {infer.MAX_SCRIPT_SEGMENTS} pieces (got {len(pieces)})")
+        infer.check_script_gap(gap)
+        resolved = {}
+        for tag in dict.fromkeys(tag for tag, _ in pieces):
+            spec = dict(voices[tag])
+            unknown = set(spec) - {"ref_audio_path", "ref_audio", "ref_text", "clip_short", "speed"}
+            if unknown or ("ref_audio_path" in spec) == ("ref_audio" in spec):
+                raise ValueError(f"voice {tag!r}: give ref_audio_path or ref_audio, ref_text and optionally clip_short, speed "
+                                 f"(got {sorted(spec)})")
+            speed = self.request_options(("speed",), speed=spec.get("speed")).get("speed")
+            if not spec.get("ref_text") or not spec["ref_text"].strip():
+                raise ValueError("Reference text cannot be empty.")
+            if "ref_audio_path" in spec:
+                voice, ref_text = self._voice(spec["ref_audio_path"], spec["ref_text"])
+            else:
+                voice, ref_text = self._clip_voice(spec["ref_audio"], spec["ref_text"], spec.get("clip_short", True))
+            resolved[tag] = (voice, ref_text, speed)
+        return [(resolved[tag][0], resolved[tag][1], piece, resolved[tag][2]) for tag, piece in pieces]
+
+    def synthesize_script(self, text, voices, *, gap=0.0, **options):
+        """A multi-voice script (F/infer/infer_cli.py:166-208) as ONE request: `text` with `[tag]` marks (`infer.split_voice_tags`: a piece
+        without a known tag is spoken by "main"), `voices` = {tag: dict(ref_audio_path=..., ref_text=...) | dict(ref_audio=<WAV bytes or
+        (wave, sr)>, ref_text=..., clip_short=True)}, each with an optional `speed`; `gap`: seconds of silence between pieces (0 to 5).
+        `options`: `infer.REQUEST_OPTIONS` as in `synthesize`, for the whole script -- one `seed` for all its chunks in order, and
+        `remove_silence` / `sample_rate` / `encoding` on the joined wave.  The script is one item of its batch (`infer.ScriptRequest`): its
+        pieces are sampled and vocoded with everything else in the batch, cross-faded inside a piece and concatenated between pieces
+        (`infer.join_segments`) -- with `device_backend` in the batch's single `ops.wave_finish_joins` call, as int16 PCM."""
+        return self._script(text, voices, gap, options)
+
+    def synthesize_script_stream(self, text, voices, *, gap=0.0, **options):
+        """`synthesize_script` as an iterator of pieces whose concatenation is its wave given the same noise: the head is the first chunk
+        of the first piece, the tail the rest of the script as one request of per-chunk texts; the joiner is cut between pieces
+        (`infer.StreamJoiner.cut`).  Delivery format and `remove_silence` as in `synthesize_stream`."""
+        return self._script(text, voices, gap, options, stream=True)
+
+    def _script(self, text, voices, gap, options, stream=False):
+        if not self.model:
+            raise ValueError("TTS model not loaded")
+        opts = self.request_options(**options)
+        if stream and infer.needs_whole_wave(opts, streamed=True):
+            raise ValueError(STREAM_REMOVE_SILENCE)
+        segments = self._script_segments(text, voices, gap)
+        if not stream:
+            req = infer.ScriptRequest(segments, opts, gap)
+            if self.batcher is not None:
+                return self.batcher.submit(req).result(timeout=self.request_timeout_s)
+            return self._run_batch([req])[0]
+        if "seed" in opts:
+            opts["generator"] = infer.request_generator(opts.pop("seed"))
+        fmt = infer.delivery_format(opts.pop("sample_rate", None), opts.pop("encoding", None))
+        chunked = [(voice, ref_text, infer.request_chunks(ref_text, voice.seconds, piece), speed) for voice, ref_text, piece, speed in segments]
+        voice, ref_text, chunks, speed = chunked[0]
+        head = self._request(voice, ref_text, chunks[:1], dict(opts, speed=speed) if speed is not None else opts)
+        continues = len(chunks) > 1                   # the tail's first segment is the rest of the head's piece: no cut in front of it
+        rest = ([(voice, ref_text, chunks[1:], speed)] if continues else []) + chunked[1:]
+        gap_samples = int(float(gap) * infer.target_sample_rate)
+
+        def tail_pieces(joiner, per_segment):
+            for k, waves in enumerate(per_segment):
+                if k or not continues:
+                    yield from joiner.pieces(cut=True)
+                    if gap_samples:
+                        yield from joiner.pieces([np.zeros(gap_samples, dtype=np.float32)], cut=True)
+                yield from joiner.pieces(waves)
+
+        return self._stream_requests(head, infer.ScriptRequest(rest, opts, gap) if rest else None, fmt, tail_pieces)
 
     def edit(self, audio, target_text, parts_to_edit, fix_duration=None, *, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
              seed=None, ode_method=None, sample_rate=None, encoding=None):
@@ -810,15 +904,30 @@ def request_models():
         clip_short: bool = True
         stream: bool = False
 
+    class ScriptVoice(BaseModel):                    # one voice of a script: a registered name, or the caller's own clip (base64 WAV)
+        ref_audio_name: str | None = None
+        ref_audio: str | None = None
+        ref_text: str | None = None
+        clip_short: bool = True
+        speed: float | None = None
+
+    class ScriptRequest(SpeechFields):               # F/infer/infer_cli.py:166-208: `[tag]` text and a voices table; JSON, not TOML
+        text: str
+        voices: dict[str, ScriptVoice]
+        gap: float = 0.0
+        stream: bool = False
+
     return types.SimpleNamespace(KannadaSynthesizeRequest=KannadaSynthesizeRequest, SynthesizeRequest=SynthesizeRequest, CloneRequest=CloneRequest,
-                                 EditRequest=EditRequest)
+                                 EditRequest=EditRequest, ScriptRequest=ScriptRequest, ScriptVoice=ScriptVoice)
 
 
 def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     """FastAPI app with the reference's `/v1/audio/speech` route (`S/routes/speech.py:19-41`) and `/v1/audio/edit` (speech editing:
     JSON body {"audio": base64 WAV, "text": the full new transcript, "parts_to_edit": [[start_s, end_s], ...], "fix_duration": [...] | null}
     -> the edited recording as WAV), plus `/v1/audio/speech/clone`: `/v1/audio/speech/voice` with the caller's own reference clip
-    ({"text", "ref_audio": base64 WAV, "ref_text", "clip_short": true, ...}) instead of a registered voice's name.  The speech routes take `"stream": true`: the WAV then arrives chunk by chunk (`_run_stream`), its
+    ({"text", "ref_audio": base64 WAV, "ref_text", "clip_short": true, ...}) instead of a registered voice's name, and
+    `/v1/audio/speech/script`: a multi-voice script ({"text": "[main] ... [town] ...", "voices": {tag: {"ref_audio_name" | "ref_audio":
+    base64 WAV, "ref_text", "clip_short"?, "speed"?}}, "gap": seconds between pieces, ...}) as one request.  The speech routes take `"stream": true`: the WAV then arrives chunk by chunk (`_run_stream`), its
     PCM samples identical to the unstreamed response's.  Every route also takes the optional sampler fields `nfe_step`, `cfg_strength`,
     `sway_sampling_coef`, `seed`, `ode_method` ("euler", "midpoint" or "rk4": the request's ODE solver) and (speech routes) `speed` and
     `remove_silence` (true: pauses of 1 s or more are cut down to 500 ms on each side; 400 together with `"stream": true`), checked
@@ -927,6 +1036,39 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
             raise HTTPException(status_code=400, detail=str(e))
         return StreamingResponse(_blocks(response_body(wave, opts, fmt)), media_type=RESPONSE_FORMATS[fmt], headers=headers)
 
+    def _run_script(req):
+        """`/v1/audio/speech/script`: the speech routes' checks, each voice's (a registered name as on `/voice`, a clip as on `/clone`),
+        then `synthesize_script` -- or, with stream=true, `synthesize_script_stream` with the first piece synthesized before the response."""
+        opts, fmt = _speech_options(req.text, req), _response_format(req)
+        voices = {}
+        for tag, v in req.voices.items():
+            spec = dict(ref_text=v.ref_text, speed=v.speed)
+            if (v.ref_audio_name is None) == (v.ref_audio is None):
+                raise HTTPException(status_code=400, detail=f"Voice {tag!r} needs either ref_audio_name or ref_audio.")
+            if v.ref_audio_name is not None:
+                voice = registry.get(v.ref_audio_name)
+                if voice is None:
+                    raise HTTPException(status_code=400, detail="Invalid reference audio name.")
+                spec.update(ref_audio_path=voice.audio_path, ref_text=v.ref_text or voice.ref_text)
+            else:
+                try:
+                    spec.update(ref_audio=base64.b64decode(v.ref_audio, validate=True), clip_short=v.clip_short)
+                except (binascii.Error, ValueError):
+                    raise HTTPException(status_code=400, detail="Audio must be a base64-encoded WAV file.")
+            if not spec["ref_text"] or not spec["ref_text"].strip():
+                raise HTTPException(status_code=400, detail="Reference text cannot be empty.")
+            voices[tag] = spec
+        headers = _headers("synthesized_script.wav", fmt)
+        try:
+            if req.stream:
+                pieces = tts_manager.synthesize_script_stream(req.text, voices, gap=req.gap, **opts)
+                first = next(pieces, None)
+                return StreamingResponse(_pcm_body(first, pieces, opts, fmt), media_type=RESPONSE_FORMATS[fmt], headers=headers)
+            wave = tts_manager.synthesize_script(req.text, voices, gap=req.gap, **opts)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        return StreamingResponse(_blocks(response_body(wave, opts, fmt)), media_type=RESPONSE_FORMATS[fmt], headers=headers)
+
     def _run_edit(req):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
@@ -964,6 +1106,10 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     @router.post("/audio/speech/clone", response_class=StreamingResponse)
     async def synthesize_with_clip(request: models.CloneRequest):          # the caller's own reference clip (TTSManager.synthesize_clip)
         return await run_in_threadpool(_run_clone, request)
+
+    @router.post("/audio/speech/script", response_class=StreamingResponse)
+    async def synthesize_script(request: models.ScriptRequest):            # a multi-voice `[tag]` script as one request (TTSManager.synthesize_script)
+        return await run_in_threadpool(_run_script, request)
 
     @router.post("/audio/edit", response_class=StreamingResponse)
     async def edit_speech(request: models.EditRequest):                    # speech editing (F/infer/speech_edit.py) over the same manager
