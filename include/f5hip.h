@@ -508,6 +508,34 @@ int f5hip_wave_encode(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, 
  * which place request lengths around it. */
 int f5hip_wave_encode_tile(int32_t new_freq);
 
+/* Lossless delivery: the int16 PCM of n requests at the delivery rate, still on the device (f5hip_wave_finish's pcm_dev, or the output of
+ * f5hip_wave_encode with encoding 0 when the rate is not 24000), -> each request's complete native FLAC stream (RFC 9639), byte for byte
+ * infer.encode_flac of its samples.  Not in the reference.  The format, with no freedom left:
+ *   stream     "fLaC", one STREAMINFO block (last-block flag, length 34): min = max block size 4096, the true min / max frame size and total
+ *              sample count, MD5 zero ("not computed"); 42 bytes, alone for an empty request (total 0, frame sizes 0); then the frames
+ *   frame      mono, 16 bits, fixed block size 4096 (sync 0xFFF8, the frame number coded; block-size code 1100, for the short last frame 0111
+ *              with a 16-bit b - 1), the rate's code, CRC-8; one subframe, no wasted bits; zero padding to a byte; CRC-16
+ *   subframe   CONSTANT when all samples of the block are equal; else the fixed-predictor order o in 0..4, o < b, with the fewest bits (ties:
+ *              the lower order); VERBATIM only when strictly smaller than that
+ *   residual   coding method 00, never the escape code; partition order 4 for a full block and 0 for the short last one; per partition the
+ *              Rice parameter k in 0..14 that minimises sum(u >> k) + n (1 + k) (ties: the smaller k), u = 2 r for r >= 0, else -2 r - 1
+ *   pcm_dev, in_off[i], max_len[i], len_dev    as in f5hip_wave_encode
+ *   sample_rate            one of 8000, 16000, 22050, 24000, 32000, 44100, 48000: only the streams' rate fields depend on it
+ *   out_dev, out_off[i]    16-byte aligned; request i's stream starts at byte out_off[i] (host array, multiples of 16), its part at least
+ *                          f5hip_wave_flac_bound(max_len[i]) bytes long
+ *   out_len_dev            int32 [n]: the bytes of request i's stream
+ * At most three launches whatever n (frames into a fixed-stride scratch buffer; a scan of the frame sizes per request, which writes the
+ * stream header; the frames packed behind it), no host sync between them (counters wave_flac_launches, wave_flac_requests); a request's
+ * bytes depend on that request alone; the request table is copied on `stream`, which the call waits for once before it launches.
+ * Refused before the first launch: n < 1, a null pointer (len_dev excepted), a rate outside the table, a negative max_len, a misaligned
+ * pointer or output offset, more than 2^31 - 1 samples in or bytes out. */
+int f5hip_wave_flac(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, int32_t sample_rate,
+                    uint8_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, void* stream);
+
+/* Upper bound of the bytes of a stream of max_len samples: 42 + 2 max_len + 16 ceil(max_len / 4096) (no frame is larger than its samples as
+ * VERBATIM plus 16 bytes); 0 for a negative length. */
+int64_t f5hip_wave_flac_bound(int32_t max_len);
+
 #ifdef __cplusplus
 }
 #endif

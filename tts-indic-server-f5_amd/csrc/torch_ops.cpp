@@ -24,6 +24,7 @@
 //   torch.ops.f5hip.wave_finish(chunks[], chunks_per_request, fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/utils_infer.py:485-519,530-539
 //   torch.ops.f5hip.wave_finish_joins(chunks[], chunks_per_request, fade, chunk_fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/infer_cli.py:181-208
 //   torch.ops.f5hip.mel_spectrogram_ragged(waves[], n_fft, hop_length, n_mels, sample_rate, variant) -> Tensor mel [sum T, n_mels]   F/model/modules.py:30-143
+//   torch.ops.f5hip.wave_flac(pcm[], in_off, max_len, len_dev?, sample_rate) -> (Tensor streams uint8, Tensor lengths int32, Tensor offsets int64 host)
 //   torch.ops.f5hip.wave_encode(pcm[], in_off, max_len, len_dev?, new_freq, encoding, taps?) -> (Tensor bytes uint8, Tensor lengths int32, Tensor offsets int64 host)
 #include "../../include/f5hip.h"
 #include "rate_pair.h"
@@ -391,6 +392,50 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_encode(at::TensorList pcm, c
     return {out, out_len, out_off};
 }
 
+// pcm, in_off, max_len, len_dev as wave_encode's, the samples at `sample_rate` already -> (out uint8 device: request i's native FLAC stream at
+// byte out_off[i]; out_len [n] int32 device: its bytes; out_off [n] int64 host)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_flac(at::TensorList pcm, const at::Tensor& in_off, const at::Tensor& max_len,
+                                                         const c10::optional<at::Tensor>& len_dev, int64_t sample_rate) {
+    check_host(in_off, at::kLong, "in_off"); check_host(max_len, at::kInt, "max_len");
+    const int64_t n = max_len.numel();
+    TORCH_CHECK(max_len.dim() == 1 && n > 0 && in_off.numel() == n, "f5hip::wave_flac: in_off and max_len need one value per request");
+    TORCH_CHECK((int64_t)pcm.size() == 1 || (int64_t)pcm.size() == n, "f5hip::wave_flac: pcm is one tensor or one per request (got ", pcm.size(), " for ", n, ")");
+    TORCH_CHECK(sample_rate >= 1 && sample_rate <= INT32_MAX, "f5hip::wave_flac: the sample rate must be positive (got ", sample_rate, ")");
+    for (const at::Tensor& t : pcm)
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kShort && t.is_contiguous() && t.dim() == 1 && t.device() == pcm[0].device(),
+                    "f5hip::wave_flac: pcm must be contiguous 1-D int16 tensors on one HIP device");
+    if (len_dev.has_value())
+        TORCH_CHECK(len_dev->is_cuda() && len_dev->scalar_type() == at::kInt && len_dev->is_contiguous() && len_dev->numel() == n &&
+                    len_dev->device() == pcm[0].device(), "f5hip::wave_flac: len_dev must be a contiguous int32 tensor with one value per request on the pcm's device");
+    const int64_t* io = in_off.data_ptr<int64_t>();
+    const int32_t* ml = max_len.data_ptr<int32_t>();
+    at::Tensor anchor;                               // offsets are relative to the first tensor that has an address
+    for (const at::Tensor& t : pcm)
+        if (t.numel() && !anchor.defined()) anchor = t;
+    if (!anchor.defined()) anchor = at::zeros({8}, pcm[0].options());
+    const int16_t* base = anchor.data_ptr<int16_t>();
+    std::vector<int64_t> rel(n);
+    at::Tensor out_off = at::empty({n}, at::TensorOptions().dtype(at::kLong));
+    int64_t* oo = out_off.data_ptr<int64_t>();
+    int64_t total_in = 0, bytes = 0;
+    for (int64_t i = 0; i < n; i++) {
+        const at::Tensor& t = pcm[pcm.size() == 1 ? 0 : i];
+        TORCH_CHECK(ml[i] >= 0 && io[i] >= 0 && io[i] + ml[i] <= t.numel(), "f5hip::wave_flac: request ", i, " reads samples [", io[i], ", ", io[i] + ml[i],
+                    ") of a tensor of ", t.numel());
+        rel[i] = ml[i] ? (t.data_ptr<int16_t>() - base) + io[i] : 0;   // (an empty tensor has no address to speak of)
+        total_in += ml[i];
+        oo[i] = bytes;
+        bytes += (f5hip_wave_flac_bound(ml[i]) + 15) & ~(int64_t)15;
+        TORCH_CHECK(total_in <= INT32_MAX && bytes <= INT32_MAX, "f5hip::wave_flac: the call exceeds 2^31 - 1 samples in or bytes out");
+    }
+    const c10::DeviceGuard guard(pcm[0].device());   // allocations and stream on the pcm's device
+    at::Tensor out = at::empty({bytes}, pcm[0].options().dtype(at::kByte)), out_len = at::empty({n}, pcm[0].options().dtype(at::kInt));
+    const int rc = f5hip_wave_flac((int32_t)n, base, rel.data(), ml, len_dev.has_value() ? len_dev->data_ptr<int32_t>() : (const int32_t*)nullptr,
+                                   (int32_t)sample_rate, out.data_ptr<uint8_t>(), oo, out_len.data_ptr<int32_t>(), stream_of(pcm[0]));
+    TORCH_CHECK(rc == 0, "f5hip_wave_flac: ", f5hip_last_error());
+    return {out, out_len, out_off};
+}
+
 }   // namespace
 
 TORCH_LIBRARY(f5hip, m) {
@@ -408,4 +453,5 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("wave_finish_joins(Tensor[] chunks, Tensor chunks_per_request, int fade, Tensor chunk_fade, Tensor remove_silence, int sample_rate) -> (Tensor, Tensor)", &wave_finish_joins);
     m.def("mel_spectrogram_ragged(Tensor[] waves, int n_fft, int hop_length, int n_mels, int sample_rate, int variant) -> Tensor", &mel_spectrogram_ragged);
     m.def("wave_encode(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int new_freq, int encoding, Tensor? taps) -> (Tensor, Tensor, Tensor)", &wave_encode);
+    m.def("wave_flac(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int sample_rate) -> (Tensor, Tensor, Tensor)", &wave_flac);
 }

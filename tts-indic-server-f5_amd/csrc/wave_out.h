@@ -1,6 +1,6 @@
 // Waveform back-end on the device: the tail of infer_batch_process (F/infer/utils_infer.py:485-519, the cross-fade join) and
 // remove_silence_for_generated_wav (:530-539) for n requests in ONE call -- chunk waves in, each request's finished 16-bit PCM out.
-// Included at the end of f5hip.hip (same translation unit).  A memory-bound gather: no MFMA, no atomics.
+// Included at the end of f5hip.hip (same translation unit).  A memory-bound gather: no MFMA, no atomics (the FLAC encoder's LDS bit buffer excepted).
 //
 //   wave_join_kernel      one block per 3840-sample tile (16 cells of 10 ms) of a request's joined wave; a thread owns 8 consecutive samples:
 //                         two 16-byte loads where they lie in one chunk's body and the address allows, one 16-byte store.  A sample of a
@@ -16,6 +16,8 @@
 //                         request: the int16 window and -- when it fits -- the tap table in LDS, one thread per output summing
 //                         taps[p][k] * xpad[q * of + k] in fp64, k ascending, then rint (half to even), clip, encode; the tile's bytes are
 //                         packed in LDS and leave in 16-byte stores.  One launch whatever n.
+//   wave_flac_*_kernel    (f5hip_wave_flac) the int16 PCM of n requests at the delivery rate -> each request's native FLAC stream, three
+//                         launches whatever n: see "delivery format: FLAC" below.
 //
 // Exactness.  With every chunk at least 2 F samples long the nested fades of cross_fade_concat never overlap, so joined sample j is either one
 // chunk sample or one fade of two chunk samples, and the closed form above is the host's arithmetic operation for operation (ramp[i] =
@@ -537,5 +539,455 @@ int f5hip_wave_encode(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, 
     CKL("wave_encode");
     g_counters[CNT_WAVE_ENCODE_LAUNCHES]++;
     g_counters[CNT_WAVE_ENCODE_REQUESTS] += n;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ delivery format: FLAC
+// f5hip_wave_flac: the int16 PCM of n requests at the delivery rate -> each request's complete native FLAC stream (RFC 9639), byte for byte
+// wave_codec.encode_flac (the subset and the choice rule are written down there and in include/f5hip.h).  Integer arithmetic only.
+//   wave_flac_frame_kernel  one block per (request, frame of 4096) up to ceil(max_len / 4096); a block past the request's actual length
+//                           leaves.  The block's samples go to LDS; a thread owns 16 consecutive samples, so the 16 threads of a quarter
+//                           wave own one Rice partition of 256: the five residual sets are differenced in registers, and for each order the
+//                           15 sums sum(u >> k) of a partition are one 16-lane butterfly each.  80 threads pick the parameter of one
+//                           (order, partition) pair, every thread then picks the subframe by the rule.  The code lengths are prefix-summed
+//                           over the block and each code goes into a zeroed LDS bit buffer with at most two LDS atomicOr: its unary zeros are
+//                           there already, so a code is the one bit and the k low bits.  A chosen subframe is never larger than VERBATIM, so
+//                           the buffer is sized for that.  CRC-8 by one lane (at most 10 bytes); CRC-16 by all 256: the frame right-aligned
+//                           in 256 slices of 33 bytes (zeros in front change nothing with initial value 0), one slice per thread, then a
+//                           binary tree a * x^(8 * 33 * 2^j) + b in GF(2)[x] mod 0x18005 -- CRC is linear, so slices combine.  The frame
+//                           leaves in 16-byte stores for its slot of a fixed-stride scratch buffer, its size for `sizes`.
+//   wave_flac_scan_kernel   one block per request: the exclusive scan of its frame sizes, their minimum and maximum; writes the 42-byte
+//                           stream header (total samples, min / max frame size, MD5 zero) and the stream's length.
+//   wave_flac_pack_kernel   one block per (request, frame): the frame from its slot to its place behind the header -- a byte-granular
+//                           destination: bytes up to the first 4-byte boundary, 4-byte stores, bytes again.
+// Three launches whatever n (one when every request is empty by its bound), no host sync between them; a request's bytes depend on that
+// request alone.  Vector stores and LDS atomics in plain C++.
+struct FlReq {
+    long long in_off;    // its first sample, relative to pcm_dev
+    long long out_off;   // its stream's first byte (a multiple of 16)
+    int cap;             // upper bound of its length (the length itself without len_dev)
+    int frame0;          // its first block of the frame and pack launches = its first scratch slot
+};
+
+constexpr int kFlBlock = 4096;
+constexpr int kFlHeader = 42;
+constexpr int kFlSlot = 8208;                   // bytes of a scratch slot: header 11 + VERBATIM 1 + 8192 + CRC-16 2 = 8206, up to 16
+constexpr int kFlWords = kFlSlot / 4;
+constexpr int kFlOrders = 5, kFlParams = 15, kFlParts = 16;
+constexpr int kFlSlice = 33;                    // CRC-16 slice of a thread: 256 * 33 >= 8204
+// The size contract, in one place: a frame is at most 11 header bytes (2 sync, 2 codes, a frame number below 2^21 in 4, the 16-bit block
+// size, CRC-8), a subframe that is at most VERBATIM (1 + 2 b bytes: the choice rule takes FIXED only when it is no larger) and 2 bytes of
+// CRC-16, i.e. 2 b + 14.  So every bit position `fl_put` sees lies inside the slot, and a request's frames together stay inside
+// f5hip_wave_flac_bound (2 bytes a sample + 16 a frame behind the header), by which the caller sized its part of the output.  The three
+// range checks below (`fl_put`'s word index, the clamp of a frame's byte count, the pack kernel's end of the request's part) never fire
+// under this contract and decide no byte of a stream; they stay as the backstop that keeps a broken contract -- a changed choice rule,
+// a caller's wrong bound -- from writing outside the LDS buffer or the request's part of the output.
+static_assert(11 + 1 + 2 * kFlBlock + 2 <= kFlSlot && kFlSlot % 16 == 0 && 256 * kFlSlice >= kFlSlot - 4, "wave_flac slot size");
+
+__host__ __device__ constexpr unsigned fl_gf_mul(unsigned a, unsigned b) {   // a * b in GF(2)[x] mod x^16 + x^15 + x^2 + 1
+    unsigned r = 0;
+    for (int i = 15; i >= 0; i--) {
+        r = ((r << 1) ^ ((r & 0x8000u) ? 0x8005u : 0u)) & 0xffffu;
+        if ((b >> i) & 1u) r ^= a;
+    }
+    return r;
+}
+__host__ __device__ constexpr unsigned fl_x_pow(int bits) {                   // x^bits mod the polynomial
+    unsigned r = 1;
+    for (int i = 0; i < bits; i++) r = ((r << 1) ^ ((r & 0x8000u) ? 0x8005u : 0u)) & 0xffffu;
+    return r;
+}
+__host__ __device__ constexpr unsigned fl_slice_pow(int level) {              // x^(8 * kFlSlice * 2^level)
+    unsigned r = fl_x_pow(8 * kFlSlice);
+    for (int i = 0; i < level; i++) r = fl_gf_mul(r, r);
+    return r;
+}
+
+F5_DEVICE unsigned fl_crc16_byte(unsigned c, unsigned byte) {
+    c ^= byte << 8;
+#pragma unroll
+    for (int i = 0; i < 8; i++) c = ((c << 1) ^ ((c & 0x8000u) ? 0x8005u : 0u)) & 0xffffu;
+    return c;
+}
+F5_DEVICE unsigned fl_crc8_byte(unsigned c, unsigned byte) {
+    c ^= byte;
+#pragma unroll
+    for (int i = 0; i < 8; i++) c = ((c << 1) ^ ((c & 0x80u) ? 0x07u : 0u)) & 0xffu;
+    return c;
+}
+
+// nbits (1 .. 32) of v at bit `pos` of the bit buffer w: big-endian words, bit 0 the most significant of word 0; the buffer starts zeroed
+F5_DEVICE void fl_put(unsigned* w, int pos, unsigned v, int nbits) {
+    const int i = pos >> 5, sh = 32 - (pos & 31) - nbits;
+    if (i < 0 || i >= kFlWords) return;
+    if (sh >= 0) {
+        atomicOr(&w[i], v << sh);
+    } else {
+        atomicOr(&w[i], v >> -sh);
+        if (i + 1 < kFlWords) atomicOr(&w[i + 1], v << (32 + sh));
+    }
+}
+F5_DEVICE unsigned fl_byte(const unsigned* w, int j) { return (w[j >> 2] >> (24 - 8 * (j & 3))) & 255u; }
+F5_DEVICE int fl_len(const int* len_dev, int r, int cap) { return len_dev ? min(max(len_dev[r], 0), cap) : cap; }
+
+__global__ __launch_bounds__(256) void wave_flac_frame_kernel(const FlReq* __restrict__ reqs, int n, const short* __restrict__ pcm,
+                                                              const int* __restrict__ len_dev, int rate_code, unsigned* __restrict__ scratch,
+                                                              int* __restrict__ sizes) {
+    __shared__ short xs[kFlBlock];
+    __shared__ __attribute__((aligned(16))) unsigned bitw[kFlWords];
+    __shared__ unsigned sums[kFlOrders][kFlParams][kFlParts];   // sum(u >> k) of the 256 samples of a partition (u = 0 before the order's first residual)
+    __shared__ unsigned best_s[kFlOrders][kFlParts];
+    __shared__ int best_k[kFlOrders][kFlParts];
+    __shared__ int wave_total[4];
+    __shared__ unsigned wave_crc[4];
+    __shared__ int differs;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int r = last_at_or_before<&FlReq::frame0>(reqs, n, (int)blockIdx.x);
+    const FlReq q = reqs[r];
+    const int f = blockIdx.x - q.frame0;
+    const int len = fl_len(len_dev, r, q.cap);
+    const long long s0 = (long long)f * kFlBlock;
+    if (s0 >= len) return;                                              // a frame past the request's actual length (the whole block leaves)
+    const int b = (int)min((long long)kFlBlock, len - s0);
+    const bool full = b == kFlBlock;
+    const int parts = full ? kFlParts : 1, orders = min(kFlOrders, b);
+
+    // the thread's 16 samples: two 16-byte loads where the address allows and the block has them all
+    const short* x = pcm + q.in_off + s0;
+    int h[20];                                                          // h[4 + e] = sample 16 tid + e; h[0 .. 3] the four before them
+    const int g0 = 16 * tid;
+    if (g0 + 16 <= b && (reinterpret_cast<uintptr_t>(x + g0) & 15) == 0) {
+        const int4 lo = reinterpret_cast<const int4*>(x + g0)[0], hi = reinterpret_cast<const int4*>(x + g0)[1];
+        const int w8[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+        for (int e = 0; e < 8; e++) { h[4 + 2 * e] = (short)(w8[e] & 0xffff); h[5 + 2 * e] = w8[e] >> 16; }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 16; e++) h[4 + e] = g0 + e < b ? (int)x[g0 + e] : 0;
+    }
+#pragma unroll
+    for (int e = 0; e < 16; e++) xs[g0 + e] = (short)h[4 + e];
+    for (int i = tid; i < kFlWords; i += 256) bitw[i] = 0;
+    if (tid == 0) differs = 0;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; e++) h[e] = g0 + e - 4 >= 0 ? (int)xs[g0 + e - 4] : 0;
+    {
+        const int first = xs[0];
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < 16; e++) any |= g0 + e < b && h[4 + e] != first;
+        if (any) differs = 1;
+    }
+
+    // the five residual sets, one after the other: cur[j] is the order's difference at sample g0 - 4 + j, valid from j = order on
+    {
+        int cur[20];
+#pragma unroll
+        for (int j = 0; j < 20; j++) cur[j] = h[j];
+#pragma unroll
+        for (int o = 0; o < kFlOrders; o++) {
+            if (o > 0) {
+#pragma unroll
+                for (int j = 19; j >= 1; j--) cur[j] -= cur[j - 1];
+            }
+            unsigned u[16];
+#pragma unroll
+            for (int e = 0; e < 16; e++) {
+                const int g = g0 + e, res = cur[4 + e];
+                u[e] = g >= o && g < b ? (unsigned)((res << 1) ^ (res >> 31)) : 0u;
+            }
+#pragma unroll
+            for (int k = 0; k < kFlParams; k++) {
+                unsigned s = 0;
+#pragma unroll
+                for (int e = 0; e < 16; e++) s += u[e] >> k;
+                s += __shfl_xor(s, 8);
+                s += __shfl_xor(s, 4);
+                s += __shfl_xor(s, 2);
+                s += __shfl_xor(s, 1);
+                if ((tid & 15) == 0) sums[o][k][tid >> 4] = s;
+            }
+        }
+    }
+    __syncthreads();
+
+    // the Rice parameter of each (order, partition): the k that minimises S_k = sum(u >> k) + n (1 + k), ties to the smaller k
+    if (tid < kFlOrders * kFlParts) {
+        const int o = tid >> 4, p = tid & 15;
+        if (o < orders && p < parts) {
+            const unsigned cnt = full ? 256u - (p == 0 ? o : 0) : (unsigned)(b - o);
+            unsigned bs = 0xffffffffu;
+            int bk = 0;
+            for (int k = 0; k < kFlParams; k++) {
+                unsigned long long s = 0;
+                if (full) s = sums[o][k][p];
+                else for (int pp = 0; pp < kFlParts; pp++) s += sums[o][k][pp];
+                s += (unsigned long long)cnt * (1 + k);
+                if (s < bs) { bs = (unsigned)s; bk = k; }                 // (the minimum is far below 2^32: S_14 <= n (64 + 15))
+            }
+            best_s[o][p] = bs;
+            best_k[o][p] = bk;
+        }
+    }
+    __syncthreads();
+
+    // the subframe: CONSTANT (-1) when all samples are equal, else the fixed order with the fewest bits (ties to the lower order), VERBATIM (5)
+    // only when strictly smaller
+    int kind = 0;
+    long long best_bits = 0;
+    for (int o = 0; o < orders; o++) {
+        long long bits = 8 + 16 * o + 2 + 4;
+        for (int p = 0; p < parts; p++) bits += 4 + (long long)best_s[o][p];
+        if (o == 0 || bits < best_bits) { best_bits = bits; kind = o; }
+    }
+    if (8 + 16LL * b < best_bits) kind = 5;
+    if (!differs) kind = -1;
+
+    // the frame header: sync and fixed block size, block-size and rate codes, mono 16 bits, the frame number, b - 1 for a short block, CRC-8
+    const int nb = f < 0x80 ? 1 : f < 0x800 ? 2 : f < 0x10000 ? 3 : 4;   // (f < 2^19: a call holds fewer than 2^31 samples)
+    const int hlen = 4 + nb + (full ? 0 : 2) + 1;
+    if (tid == 0) {
+        unsigned char hd[11];
+        int m = 0;
+        hd[m++] = 0xff; hd[m++] = 0xf8; hd[m++] = (unsigned char)(((full ? 0x0c : 0x07) << 4) | rate_code); hd[m++] = 0x08;
+        if (nb == 1) {
+            hd[m++] = (unsigned char)f;
+        } else {
+            hd[m++] = (unsigned char)(((0xff << (8 - nb)) & 0xff) | (f >> (6 * (nb - 1))));
+            for (int k = nb - 2; k >= 0; k--) hd[m++] = (unsigned char)(0x80 | ((f >> (6 * k)) & 0x3f));
+        }
+        if (!full) { hd[m++] = (unsigned char)((b - 1) >> 8); hd[m++] = (unsigned char)((b - 1) & 0xff); }
+        unsigned c = 0;
+        for (int i = 0; i < m; i++) c = fl_crc8_byte(c, hd[i]);
+        hd[m++] = (unsigned char)c;
+        for (int i = 0; i < m; i++) fl_put(bitw, 8 * i, hd[i], 8);
+    }
+    const int base0 = 8 * hlen;
+    int nbits;
+    if (kind == -1) {
+        if (tid == 0) fl_put(bitw, base0 + 8, (unsigned)xs[0] & 0xffffu, 16);   // (the subframe header byte is 0)
+        nbits = base0 + 24;
+    } else if (kind == 5) {
+        if (tid == 0) fl_put(bitw, base0, 0x02u, 8);
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+            if (g0 + e < b) fl_put(bitw, base0 + 8 + 16 * (g0 + e), (unsigned)h[4 + e] & 0xffffu, 16);
+        nbits = base0 + 8 + 16 * b;
+    } else {
+        const int o = kind, p = full ? tid >> 4 : 0, k = best_k[o][p];
+        int cur[20];
+#pragma unroll
+        for (int j = 0; j < 20; j++) cur[j] = h[j];
+#pragma unroll
+        for (int d = 0; d < kFlOrders - 1; d++) {
+            if (d < o) {
+#pragma unroll
+                for (int j = 19; j >= 1; j--) cur[j] -= cur[j - 1];
+            }
+        }
+        unsigned u[16];
+        int mine = 0;                                                    // bits of the thread's codes
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            const int g = g0 + e, res = cur[4 + e];
+            u[e] = (unsigned)((res << 1) ^ (res >> 31));
+            if (g >= o && g < b) mine += (int)(u[e] >> k) + 1 + k;
+        }
+        int incl = mine;                                                 // inclusive scan over the wave, then over the four waves
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) wave_total[wv] = incl;
+        __syncthreads();
+        int before = incl - mine, total = 0;
+        for (int w = 0; w < 4; w++) { if (w < wv) before += wave_total[w]; total += wave_total[w]; }
+        const int base = base0 + 8 + 16 * o + 6;                         // behind the subframe header, the warm-up, coding method 00 and the partition order
+        if (tid == 0) {
+            fl_put(bitw, base0, (unsigned)((8 | o) << 1), 8);
+            for (int j = 0; j < o; j++) fl_put(bitw, base0 + 8 + 16 * j, (unsigned)xs[j] & 0xffffu, 16);
+            if (full) fl_put(bitw, base - 4, 4u, 4);
+        }
+        if (full ? (tid & 15) == 0 : tid == 0) fl_put(bitw, base + 4 * p + before, (unsigned)k, 4);
+        int pos = base + 4 * (p + 1) + before;
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            const int g = g0 + e;
+            if (g >= o && g < b) {
+                const int quot = (int)(u[e] >> k);
+                fl_put(bitw, pos + quot, (1u << k) | (u[e] & ((1u << k) - 1u)), k + 1);
+                pos += quot + 1 + k;
+            }
+        }
+        nbits = base + 4 * parts + total;
+    }
+    const int nbytes = min((nbits + 7) >> 3, kFlSlot - 2);              // (never more: a chosen subframe is at most VERBATIM)
+    __syncthreads();
+
+    // CRC-16 of the nbytes in front of it: the frame right-aligned in 256 slices, one per thread, combined by a fixed tree
+    {
+        const int pad = 256 * kFlSlice - nbytes;
+        constexpr unsigned pw[8] = {fl_slice_pow(0), fl_slice_pow(1), fl_slice_pow(2), fl_slice_pow(3),
+                                    fl_slice_pow(4), fl_slice_pow(5), fl_slice_pow(6), fl_slice_pow(7)};
+        unsigned c = 0;
+        for (int i = 0; i < kFlSlice; i++) {
+            const int j = tid * kFlSlice + i - pad;
+            if (j >= 0) c = fl_crc16_byte(c, fl_byte(bitw, j));
+        }
+#pragma unroll
+        for (int level = 0; level < 6; level++) {
+            const unsigned other = __shfl_down(c, 1 << level);
+            if ((lane & ((2 << level) - 1)) == 0) c = fl_gf_mul(c, pw[level]) ^ other;
+        }
+        if (lane == 0) wave_crc[wv] = c;
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned a = fl_gf_mul(wave_crc[0], pw[6]) ^ wave_crc[1], bb = fl_gf_mul(wave_crc[2], pw[6]) ^ wave_crc[3];
+            fl_put(bitw, 8 * nbytes, fl_gf_mul(a, pw[7]) ^ bb, 16);
+        }
+        __syncthreads();
+    }
+
+    const int total_bytes = nbytes + 2;
+    uint4* dst = reinterpret_cast<uint4*>(scratch + (size_t)blockIdx.x * kFlWords);
+    for (int i = tid; 16 * i < total_bytes; i += 256) {
+        const uint4 v = reinterpret_cast<const uint4*>(bitw)[i];
+        dst[i] = make_uint4(__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z), __builtin_bswap32(v.w));
+    }
+    if (tid == 0) sizes[blockIdx.x] = total_bytes;
+}
+
+__global__ __launch_bounds__(256) void wave_flac_scan_kernel(const FlReq* __restrict__ reqs, const int* __restrict__ len_dev,
+                                                             const int* __restrict__ sizes, unsigned* __restrict__ frame_off, int rate,
+                                                             unsigned char* __restrict__ out, int* __restrict__ out_len) {
+    __shared__ unsigned runsum[256];
+    __shared__ int runmin[256], runmax[256];
+    const int tid = threadIdx.x, r = blockIdx.x;
+    const FlReq q = reqs[r];
+    const int len = fl_len(len_dev, r, q.cap);
+    const int frames = (int)(((long long)len + kFlBlock - 1) / kFlBlock);
+    const int run = (frames + 255) / 256, i0 = min(tid * run, frames), i1 = min(i0 + run, frames);
+    unsigned local = 0;
+    int mn = 0x7fffffff, mx = 0;
+    for (int i = i0; i < i1; i++) {
+        const int s = sizes[q.frame0 + i];
+        local += (unsigned)s; mn = min(mn, s); mx = max(mx, s);
+    }
+    runsum[tid] = local; runmin[tid] = mn; runmax[tid] = mx;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned acc = 0;
+        for (int t = 0; t < 256; t++) { const unsigned v = runsum[t]; runsum[t] = acc; acc += v; mn = min(mn, runmin[t]); mx = max(mx, runmax[t]); }
+        if (frames == 0) mn = 0;
+        // "fLaC", STREAMINFO as the last metadata block, 34 bytes: block size 4096 twice, min / max frame size, rate (20 bits), channels - 1
+        // (3), bits - 1 (5), total samples (36), MD5 zero ("not computed")
+        unsigned char* o = out + q.out_off;
+        const unsigned long long info = ((unsigned long long)rate << 44) | (15ULL << 36) | (unsigned long long)len;
+        const unsigned char head[18] = {'f', 'L', 'a', 'C', 0x80, 0, 0, 34, 0x10, 0x00, 0x10, 0x00,
+                                        (unsigned char)(mn >> 16), (unsigned char)(mn >> 8), (unsigned char)mn,
+                                        (unsigned char)(mx >> 16), (unsigned char)(mx >> 8), (unsigned char)mx};
+        for (int i = 0; i < 18; i++) o[i] = head[i];
+        for (int i = 0; i < 8; i++) o[18 + i] = (unsigned char)(info >> (56 - 8 * i));
+        for (int i = 26; i < kFlHeader; i++) o[i] = 0;
+        out_len[r] = kFlHeader + (int)acc;
+    }
+    __syncthreads();
+    unsigned acc = runsum[tid];
+    for (int i = i0; i < i1; i++) { frame_off[q.frame0 + i] = acc; acc += (unsigned)sizes[q.frame0 + i]; }
+}
+
+__global__ __launch_bounds__(256) void wave_flac_pack_kernel(const FlReq* __restrict__ reqs, int n, const int* __restrict__ len_dev,
+                                                             const unsigned char* __restrict__ scratch, const int* __restrict__ sizes,
+                                                             const unsigned* __restrict__ frame_off, unsigned char* __restrict__ out) {
+    const int tid = threadIdx.x;
+    const int r = last_at_or_before<&FlReq::frame0>(reqs, n, (int)blockIdx.x);
+    const FlReq q = reqs[r];
+    const int f = blockIdx.x - q.frame0;
+    if ((long long)f * kFlBlock >= fl_len(len_dev, r, q.cap)) return;
+    const unsigned char* src = scratch + (size_t)blockIdx.x * kFlSlot;
+    unsigned char* dst = out + q.out_off + kFlHeader + frame_off[blockIdx.x];
+    const int nbytes = sizes[blockIdx.x];
+    // (never past the request's part of the output, which the host sized by the bound below)
+    if ((long long)frame_off[blockIdx.x] + nbytes > 2LL * q.cap + 16LL * (((long long)q.cap + kFlBlock - 1) / kFlBlock)) return;
+    const int head = min(nbytes, (int)((4 - (reinterpret_cast<uintptr_t>(dst) & 3)) & 3));   // bytes up to the destination's 4-byte boundary
+    if (tid < head) dst[tid] = src[tid];
+    const int words = (nbytes - head) >> 2;
+    for (int i = tid; i < words; i += 256) {
+        const unsigned char* s = src + head + 4 * i;
+        *reinterpret_cast<unsigned*>(dst + head + 4 * i) = (unsigned)s[0] | ((unsigned)s[1] << 8) | ((unsigned)s[2] << 16) | ((unsigned)s[3] << 24);
+    }
+    const int done = head + 4 * words;
+    if (tid < nbytes - done) dst[done + tid] = src[done + tid];
+}
+
+struct FlWorkspace {
+    FlReq* reqs = nullptr; size_t cap_reqs = 0;
+    unsigned* scratch = nullptr; size_t cap_scratch = 0;
+    int* sizes = nullptr; size_t cap_sizes = 0;
+    unsigned* frame_off = nullptr; size_t cap_frame_off = 0;
+};
+
+static int fl_rate_code(int rate) {
+    switch (rate) {
+        case 8000: return 4; case 16000: return 5; case 22050: return 6; case 24000: return 7; case 32000: return 8; case 44100: return 9;
+        case 48000: return 10; default: return -1;
+    }
+}
+
+// the stream header, the samples as VERBATIM and 16 bytes of frame around them (header <= 11, subframe header 1, CRC-16 2)
+int64_t f5hip_wave_flac_bound(int32_t max_len) {
+    if (max_len < 0) return 0;
+    return kFlHeader + 2LL * max_len + 16LL * (((long long)max_len + kFlBlock - 1) / kFlBlock);
+}
+
+int f5hip_wave_flac(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, int32_t sample_rate,
+                    uint8_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, void* stream) {
+    if (n < 1 || !pcm_dev || !in_off || !max_len || !out_dev || !out_off || !out_len_dev) return fail(-1, "wave_flac: bad argument");
+    const int code = fl_rate_code(sample_rate);
+    if (code < 0) return fail(-1, "wave_flac: the sample rate must be one of 8000, 16000, 22050, 24000, 32000, 44100, 48000 (got %d)", sample_rate);
+    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 1) || (reinterpret_cast<uintptr_t>(out_dev) & 15))
+        return fail(-1, "wave_flac: the input must be 2-byte aligned and the output 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(len_dev) & 3) || (reinterpret_cast<uintptr_t>(out_len_dev) & 3))
+        return fail(-1, "wave_flac: the lengths must be 4-byte aligned");
+    std::vector<FlReq> h(n);
+    long long total_in = 0, total_out = 0, frames = 0;
+    for (int i = 0; i < n; i++) {
+        if (max_len[i] < 0) return fail(-1, "wave_flac: request %d has a negative length bound (%d)", i, max_len[i]);
+        if (out_off[i] < 0 || (out_off[i] & 15)) return fail(-1, "wave_flac: the output offset of request %d is not a multiple of 16 bytes", i);
+        total_in += max_len[i]; total_out += f5hip_wave_flac_bound(max_len[i]);
+        if (total_in > 2147483647LL || total_out > 2147483647LL) return fail(-1, "wave_flac: the call exceeds 2^31 - 1 samples in or bytes out");
+        h[i] = FlReq{in_off[i], out_off[i], max_len[i], (int)frames};
+        frames += ((long long)max_len[i] + kFlBlock - 1) / kFlBlock;
+    }
+    FlWorkspace* const wsp = device_workspace<FlWorkspace>("wave_flac");
+    if (!wsp) return -6;
+    FlWorkspace& ws = *wsp;
+    CK(dev_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_flac requests"));
+    if (frames) {
+        CK(dev_reserve(&ws.scratch, &ws.cap_scratch, (size_t)frames * kFlWords, "wave_flac frames"));
+        CK(dev_reserve(&ws.sizes, &ws.cap_sizes, (size_t)frames, "wave_flac frame sizes"));
+        CK(dev_reserve(&ws.frame_off, &ws.cap_frame_off, (size_t)frames, "wave_flac frame offsets"));
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (upload_sync(st, ws.reqs, h) != hipSuccess) return fail(-6, "wave_flac metadata upload");
+    if (frames) {
+        hipLaunchKernelGGL(wave_flac_frame_kernel, dim3((unsigned)frames), dim3(256), 0, st, ws.reqs, n, (const short*)pcm_dev, (const int*)len_dev, code,
+                           ws.scratch, ws.sizes);
+        CKL("wave_flac_frame");
+        g_counters[CNT_WAVE_FLAC_LAUNCHES]++;
+    }
+    hipLaunchKernelGGL(wave_flac_scan_kernel, dim3((unsigned)n), dim3(256), 0, st, ws.reqs, (const int*)len_dev, ws.sizes, ws.frame_off, (int)sample_rate,
+                       (unsigned char*)out_dev, (int*)out_len_dev);
+    CKL("wave_flac_scan");
+    g_counters[CNT_WAVE_FLAC_LAUNCHES]++;
+    if (frames) {
+        hipLaunchKernelGGL(wave_flac_pack_kernel, dim3((unsigned)frames), dim3(256), 0, st, ws.reqs, n, (const int*)len_dev,
+                           (const unsigned char*)ws.scratch, ws.sizes, ws.frame_off, (unsigned char*)out_dev);
+        CKL("wave_flac_pack");
+        g_counters[CNT_WAVE_FLAC_LAUNCHES]++;
+    }
+    g_counters[CNT_WAVE_FLAC_REQUESTS] += n;
     return 0;
 }

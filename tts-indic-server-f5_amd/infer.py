@@ -32,9 +32,10 @@ import torch
 from . import wave_codec
 from .audio_prep import preprocess_ref_audio_text, remove_silence_edges, remove_silence_pcm  # noqa: F401  (F/infer/utils_infer.py:263-350)
 from .loaders import DiT, MMDiT, UNetT, load_checkpoint, load_model, load_vocoder  # noqa: F401  (F/infer/utils_infer.py:92-130,175-260)
-from .wave_codec import (MAX_TAP_TABLE_BYTES, OUTPUT_ENCODINGS, OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, StreamResampler, decode_g711,  # noqa: F401
-                         deliver_pcm16, delivery_format, encode_g711, load_wav, quantise_pcm16, rate_pair, resample_pcm16, resample_sinc_hann,
-                         resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
+from .wave_codec import (ALL_ENCODINGS, FLAC_BLOCK, FLAC_ENCODINGS, FLAC_HEADER_BYTES, MAX_TAP_TABLE_BYTES, OUTPUT_ENCODINGS,  # noqa: F401
+                         OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, StreamFlacEncoder, StreamResampler, decode_flac, decode_g711, deliver_pcm16,
+                         delivery_format, encode_flac, encode_g711, flac_crc8, flac_crc16, flac_stream_header, load_wav, quantise_pcm16,
+                         rate_pair, resample_pcm16, resample_sinc_hann, resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
 from .wave_codec import _device_taps, _tap_tables  # noqa: F401  (the two caches: used below, and read as infer._X by the tests that bound them)
 
 # ----------------------------------------- F/infer/utils_infer.py:40-53
@@ -639,9 +640,9 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
 
     `remove_silence` (bool, per request): the reference's `remove_silence_for_generated_wav` on the finished wave; such a request's wave is
     int16 PCM (`audio_prep.remove_silence_pcm` of its quantised joined wave), and it needs the whole wave: ValueError with `join=False` or a
-    list of chunk texts.  `sample_rate` (one of OUTPUT_SAMPLE_RATES) and `encoding` ("pcm16", "mulaw", "alaw"), per request: the delivery
-    format, a pure function of the request's 24 kHz int16 PCM (`deliver_pcm16`: after silence removal, `resample_pcm16`, then `encode_g711`);
-    such a request's wave is int16 at that rate or uint8 code bytes, its triple names that rate, and like `remove_silence` it needs the whole
+    list of chunk texts.  `sample_rate` (one of OUTPUT_SAMPLE_RATES) and `encoding` ("pcm16", "mulaw", "alaw", "flac"), per request: the delivery
+    format, a pure function of the request's 24 kHz int16 PCM (`deliver_pcm16`: after silence removal, `resample_pcm16`, then `encode_g711`
+    or `encode_flac`); such a request's wave is int16 at that rate, uint8 code bytes or the uint8 bytes of a FLAC stream, its triple names that rate, and like `remove_silence` it needs the whole
     wave.  A `ScriptRequest` (a multi-voice script: one segment per piece, each with its own voice) is accepted in place of a tuple: its
     segments' units ride in the same sampler call, one prompt per unit, and the same vocoder call, one group per segment; its triple is
     (`join_segments` of its segments' chunk waves, rate, [spectrogram per segment]), with `join=False` the chunk waves and spectrograms per
@@ -727,7 +728,7 @@ def request_wave(gen_text, waves, cross_fade_duration=cross_fade_duration):
 
 # What `finish_requests` and `_chunk_waves` did since the last `backend_stats.clear()`: requests finished on the device / on the host,
 # `ops.wave_finish` calls, `ops.wave_encode` calls and the requests they encoded (`encode_calls`, `encode_requests`), and device-to-host copies
-# (chunk waves, spectrograms, PCM, encoded samples, lengths)
+# (chunk waves, spectrograms, PCM, encoded samples, lengths); `flac_bytes` is the size of the FLAC stream downloads
 backend_stats: collections.Counter = collections.Counter()
 
 
@@ -767,7 +768,13 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     chained on the same stream with no download in between (a flagged request's length stays on the device); per pair at most two copies come
     back, the lengths (only with silence removal) and the encoded samples, and nothing of those requests' 24 kHz PCM.  Like every ragged call
     of the library each `wave_encode` call copies its small request table on the stream and waits for that copy before it launches, so the
-    host does wait once per pair for what is queued in front of it (`wave_finish`'s kernels); no data comes back in that wait."""
+    host does wait once per pair for what is queued in front of it (`wave_finish`'s kernels); no data comes back in that wait.
+
+    `encoding="flac"`: the request gets the uint8 array that holds `encode_flac` of its PCM at `sample_rate`.  With `device_backend` the flac
+    requests of a batch take ONE `ops.wave_flac` call per distinct rate behind `wave_finish` / `wave_encode` on the same stream
+    (`backend_stats["flac_calls"]`, `["flac_requests"]`), and two copies come back per rate: the streams' lengths, then the streams, joined
+    on the device, in one download of exactly their bytes (`["flac_bytes"]`); on the host, or with a model without the device back-end,
+    `encode_flac` makes the same bytes.  Every `wave_encode` / `wave_flac` call of the batch is queued before the first of these copies."""
     if want not in ("float", "pcm16"):
         raise ValueError(f'want must be "float" or "pcm16" (got {want!r})')
     if device_backend and want != "pcm16":
@@ -844,7 +851,9 @@ def _finish_on_host(waves, text, cross_fade_duration, flag, fmt, want):
 def _finish_on_device(requests, fade, silence, formats):
     """`finish_requests` for the requests the device back-end takes: `requests` = (chunk waves (device tensors), fades: `_device_request`), the
     plain-format ones first; `silence`, `formats` per request.  ONE `ops.wave_finish` call -- `ops.wave_finish_joins` when a script is among
-    them -- then one `ops.wave_encode` call per distinct delivery format behind it on the same stream.  Returns one result per request."""
+    them -- then one `ops.wave_encode` call per distinct delivery format behind it on the same stream, and for the "flac" requests one
+    `ops.wave_flac` call per distinct rate (behind a `wave_encode(..., "pcm16")` call where the rate is not 24 kHz).  Returns one result per
+    request."""
     from . import ops
     out = [None] * len(requests)
     plain = sum(fmt == _PLAIN for fmt in formats)
@@ -868,24 +877,60 @@ def _finish_on_device(requests, fade, silence, formats):
             out[k] = host[off:off + length].copy()   # (a request's result does not keep the batch's buffer alive)
     groups = {}
     for k in range(plain, len(requests)):
-        groups.setdefault(formats[k], []).append(k)
+        if formats[k][1] not in FLAC_ENCODINGS:
+            groups.setdefault(formats[k], []).append(k)
+    flac_rates = {}
+    for k in range(plain, len(requests)):
+        if formats[k][1] in FLAC_ENCODINGS:
+            flac_rates.setdefault(formats[k][0], []).append(k)
+    # every group's kernels are queued first, and only then does anything come down: a mixed micro-batch does not wait for one group's copies
+    # before the next group's launches
+    queued_flac, queued = [], []
+    for rate, ks in flac_rates.items():   # FLAC: one `ops.wave_flac` call per distinct rate, behind the resampler's where the rate is not 24 kHz
+        contiguous = ks == list(range(ks[0], ks[-1] + 1))
+        sel = lengths[ks[0]:ks[-1] + 1] if contiguous else lengths[torch.tensor(ks, device=lengths.device)]   # (gathered on the device)
+        if rate == target_sample_rate:
+            src, src_off, bounds = pcm, [offsets[k] for k in ks], [joined[k] for k in ks]
+        else:
+            data, sel, out_off = ops.wave_encode(pcm, [offsets[k] for k in ks], [joined[k] for k in ks], sel, rate, "pcm16",
+                                                 _device_taps(target_sample_rate, rate, pcm.device))
+            src, src_off = data.view(torch.int16), [off // 2 for off in out_off]
+            bounds = [resampled_length(joined[k], target_sample_rate, rate) for k in ks]
+            backend_stats["encode_calls"] += 1
+            backend_stats["encode_requests"] += len(ks)
+        queued_flac.append((ks,) + tuple(ops.wave_flac(src, src_off, bounds, sel, rate)))
+        backend_stats["flac_calls"] += 1
+        backend_stats["flac_requests"] += len(ks)
     for (rate, enc), ks in groups.items():   # one call per delivery format, behind wave_finish on the same stream
         taps = _device_taps(target_sample_rate, rate, pcm.device) if rate != target_sample_rate else None
         contiguous = ks == list(range(ks[0], ks[-1] + 1))
         sel = lengths[ks[0]:ks[-1] + 1] if contiguous else lengths[torch.tensor(ks, device=lengths.device)]   # (gathered on the device)
-        data, out_len, out_off = ops.wave_encode(pcm, [offsets[k] for k in ks], [joined[k] for k in ks], sel, rate, enc, taps)
-        if any(silence[k] for k in ks):
-            counts = out_len.cpu().tolist()
-            backend_stats["d2h_copies"] += 1
-        else:
-            counts = [resampled_length(joined[k], target_sample_rate, rate) for k in ks]
-        host = data.cpu().numpy()
-        backend_stats["d2h_copies"] += 1
-        for k, off, m in zip(ks, out_off, counts):
-            raw = host[off:off + m * (2 if enc == "pcm16" else 1)].copy()
-            out[k] = raw.view("<i2") if enc == "pcm16" else raw
+        queued.append((rate, enc, ks) + tuple(ops.wave_encode(pcm, [offsets[k] for k in ks], [joined[k] for k in ks], sel, rate, enc, taps)))
         backend_stats["encode_calls"] += 1
         backend_stats["encode_requests"] += len(ks)
+    for ks, streams, stream_len, stream_off in queued_flac:
+        sizes = stream_len.cpu().tolist()                                    # (a stream's length is known on the device alone)
+        # `wave_flac` puts each stream at the offset its VERBATIM bound allows for, so between two streams lies room that nobody wrote:
+        # the streams are joined on the device, and ONE download brings exactly their bytes and nothing of their PCM
+        slices = [streams[off:off + m] for off, m in zip(stream_off, sizes)]
+        host = (slices[0] if len(slices) == 1 else torch.cat(slices)).cpu().numpy()
+        backend_stats["d2h_copies"] += 2
+        backend_stats["flac_bytes"] += host.nbytes
+        at = 0
+        for k, m in zip(ks, sizes):
+            out[k] = host[at:at + m].copy()
+            at += m
+    for rate, enc, ks, data, out_len, out_off in queued:
+        if any(silence[k] for k in ks):
+            sizes = out_len.cpu().tolist()
+            backend_stats["d2h_copies"] += 1
+        else:
+            sizes = [resampled_length(joined[k], target_sample_rate, rate) for k in ks]
+        host = data.cpu().numpy()
+        backend_stats["d2h_copies"] += 1
+        for k, off, m in zip(ks, out_off, sizes):
+            raw = host[off:off + m * (2 if enc == "pcm16" else 1)].copy()
+            out[k] = raw.view("<i2") if enc == "pcm16" else raw
     backend_stats["device_calls"] += 1
     backend_stats["device_requests"] += len(requests)
     return out

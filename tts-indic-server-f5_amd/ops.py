@@ -498,3 +498,50 @@ def wave_encode(pcm, in_off, max_len, len_dev, sample_rate, encoding, taps=None)
         _lib.check(_lib.lib().f5hip_wave_encode(n, C.c_void_p(base), _p(rel), _p(ml), _p(len_dev), rate, code, _p(taps) if rate != 24000 else None, _p(data),
                                                 _p(out_off), _p(out_len), _lib.current_stream_ptr()), "f5hip_wave_encode")
     return data, out_len, out_off.tolist()
+
+
+def wave_flac(pcm, in_off, max_len, len_dev, sample_rate):
+    """The FLAC streams of several finished requests in ONE library call and at most three launches (include/f5hip.h f5hip_wave_flac): their
+    int16 PCM at `sample_rate`, on the device -> each request's complete native FLAC stream.  `pcm`, `in_off`, `max_len`, `len_dev` as in
+    `wave_encode`: `wave_finish`'s packed PCM and device lengths at 24 kHz, or `wave_encode(..., "pcm16")`'s data viewed as int16 (offsets in
+    samples) and its `out_len` at another rate.  Returns (data uint8 device, out_len int32 device [n], offsets): request i's stream is
+    data[offsets[i] : offsets[i] + out_len[i]], byte for byte `infer.encode_flac` of its samples."""
+    tensors = [pcm] if torch.is_tensor(pcm) else list(pcm)
+    io = np.ascontiguousarray(np.asarray(in_off, dtype=np.int64))
+    ml = np.ascontiguousarray(np.asarray(max_len, dtype=np.int32))
+    n, rate = len(ml), int(sample_rate)
+    if n < 1 or len(io) != n or len(tensors) not in (1, n):
+        raise _lib.F5HipError("wave_flac: one offset and one length bound per request; pcm is one tensor or one per request")
+    for t in tensors:
+        if not (torch.is_tensor(t) and t.dtype == torch.int16 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.device == tensors[0].device):
+            raise _lib.F5HipError("wave_flac: pcm must be contiguous 1-D int16 tensors on one device")
+    if len_dev is not None and not (torch.is_tensor(len_dev) and len_dev.dtype == torch.int32 and len_dev.is_cuda and len_dev.numel() == n
+                                    and len_dev.device == tensors[0].device):
+        raise _lib.F5HipError("wave_flac: len_dev must be an int32 tensor with one value per request on the pcm's device")
+    if len_dev is not None:
+        len_dev = len_dev.contiguous()
+    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
+        try:
+            data, out_len, out_off = torch_ops.ops().wave_flac(tensors, torch.from_numpy(io), torch.from_numpy(ml), len_dev, rate)
+        except RuntimeError as e:   # c10::Error from the operator's checks or the library
+            raise _lib.F5HipError(str(e)) from e
+        return data, out_len, out_off.tolist()
+    anchor = next((t for t in tensors if t.numel()), None)   # offsets are relative to the first tensor that has an address
+    if anchor is None:
+        anchor = torch.zeros(8, device=tensors[0].device, dtype=torch.int16)
+    base = anchor.data_ptr()
+    rel, out_off, nbytes = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), 0
+    for i in range(n):
+        t = tensors[0 if len(tensors) == 1 else i]
+        if ml[i] < 0 or io[i] < 0 or int(io[i]) + int(ml[i]) > t.numel():
+            raise _lib.F5HipError(f"wave_flac: request {i} reads samples [{io[i]}, {int(io[i]) + int(ml[i])}) of a tensor of {t.numel()}")
+        rel[i] = (t.data_ptr() - base) // 2 + int(io[i]) if ml[i] else 0   # (an empty tensor has no address to speak of)
+        out_off[i] = nbytes
+        nbytes += (int(_lib.lib().f5hip_wave_flac_bound(int(ml[i]))) + 15) & ~15
+    dev = tensors[0].device
+    with torch.cuda.device(dev):
+        data = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        out_len = torch.empty(n, device=dev, dtype=torch.int32)
+        _lib.check(_lib.lib().f5hip_wave_flac(n, C.c_void_p(base), _p(rel), _p(ml), _p(len_dev), rate, _p(data), _p(out_off), _p(out_len),
+                                              _lib.current_stream_ptr()), "f5hip_wave_flac")
+    return data, out_len, out_off.tolist()

@@ -58,7 +58,8 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
     `sway_sampling_coef` finite; `seed` an integer in 0..2**63 - 1; `ode_method` one of MAX_NFE_STEP's names.  `ode_method` (the argument)
     is the model's solver: `nfe_step`'s upper limit follows the request's own `ode_method` when it sets one, else the model's.
     `remove_silence` a bool (False is dropped like None: the request is then what it is without the option).  `sample_rate` an integer in
-    `infer.OUTPUT_SAMPLE_RATES`, `encoding` one of `infer.OUTPUT_ENCODINGS`; 24000 and "pcm16", what a request gets anyway, are dropped too."""
+    `infer.OUTPUT_SAMPLE_RATES`, `encoding` one of `infer.OUTPUT_ENCODINGS` or "flac" (`infer.FLAC_ENCODINGS`); 24000 and "pcm16", what a
+    request gets anyway, are dropped too."""
     out = {}
     own = options.get("ode_method") if "ode_method" in allowed else None
     if own is not None:
@@ -607,9 +608,10 @@ class TTSManager:
         the option reaches the model object only for a request that sets it.  `remove_silence=True`: the reference's
         `remove_silence_for_generated_wav` -- pauses of 1 s or more shrink to 500 ms on each side -- and the result is int16 PCM
         (`audio_prep.remove_silence_pcm` of the quantised wave); with `device_backend` every result is int16 PCM.  `sample_rate` (one of
-        `infer.OUTPUT_SAMPLE_RATES`) and `encoding` ("pcm16", "mulaw", "alaw"): the delivery format, `infer.deliver_pcm16` of the request's
-        24 kHz int16 PCM -- int16 at that rate, or uint8 G.711 code bytes -- computed on the device with `device_backend`, the same bytes
-        either way; 24000 and "pcm16" (or None) change nothing."""
+        `infer.OUTPUT_SAMPLE_RATES`) and `encoding` ("pcm16", "mulaw", "alaw", "flac"): the delivery format, `infer.deliver_pcm16` of the
+        request's 24 kHz int16 PCM -- int16 at that rate, uint8 G.711 code bytes, or with "flac" a uint8 array that holds the lossless FLAC
+        stream of the samples at that rate (`infer.encode_flac`) -- computed on the device with `device_backend`, the same bytes either way;
+        24000 and "pcm16" (or None) change nothing."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         return self.model(text, ref_audio_path=ref_audio_path, ref_text=ref_text, **options)   # (`_call`, which checks the options)
@@ -625,7 +627,10 @@ class TTSManager:
         pieces equal `synthesize`'s wave with that seed.  The remaining chunks keep the first chunk's `ode_method`.  With `sample_rate` /
         `encoding` the pieces come in the delivery format (int16 at that rate, or uint8 code bytes): each float32 piece goes through
         `infer.quantise_pcm16`, an `infer.StreamResampler` and the encoder on the host, and their concatenation equals `synthesize`'s result
-        with the same options byte for byte.  `remove_silence` needs the whole wave: ValueError."""
+        with the same options byte for byte.  With "flac" the pieces are uint8: the 42-byte stream header with the totals unknown (zero)
+        first -- it comes from the first `next()` once the first chunk is synthesized, so a failing first chunk raises there before any
+        byte --, then the frames each piece completes (`infer.StreamFlacEncoder`), then the short last frame; behind the header they equal
+        `synthesize`'s stream, and both decode to the same samples.  `remove_silence` needs the whole wave: ValueError."""
         return self._serve(lambda: self._voice(ref_audio_path, ref_text), text, options, stream=True)
 
     def _stream(self, voice, ref_text, head, tail, opts=None):
@@ -685,16 +690,36 @@ class TTSManager:
 
         def delivered():
             resampler = infer.StreamResampler(fmt[0])
-            encode = (lambda pcm: pcm) if fmt[1] == "pcm16" else (lambda pcm: infer.encode_g711(pcm, fmt[1]))
+            flac = infer.StreamFlacEncoder(fmt[0]) if fmt[1] in infer.FLAC_ENCODINGS else None
+            if flac is not None:                  # uint8 pieces: the frames each piece completes
+                encode = lambda pcm: np.frombuffer(flac.feed(pcm), dtype=np.uint8)   # noqa: E731
+            else:
+                encode = (lambda pcm: pcm) if fmt[1] == "pcm16" else (lambda pcm: infer.encode_g711(pcm, fmt[1]))
             gen = pieces()
             try:
+                # flac: the 42 bytes (totals unknown) go out once the first piece is there, never before it: the consumer's first `next()`
+                # still runs the head request, so a failing head is an exception there and not a body of a bare header
+                header = flac is not None
                 for piece in gen:
+                    if header:
+                        header = False
+                        yield np.frombuffer(flac.header(), dtype=np.uint8)
                     out = resampler.feed(infer.quantise_pcm16(piece))
                     if len(out):
-                        yield encode(out)
+                        out = encode(out)
+                        if len(out):
+                            yield out
+                if header:                        # (a request without a piece is the header alone)
+                    yield np.frombuffer(flac.header(), dtype=np.uint8)
                 out = resampler.flush()
                 if len(out):
-                    yield encode(out)
+                    out = encode(out)
+                    if len(out):
+                        yield out
+                if flac is not None:
+                    out = flac.flush()            # the short last frame
+                    if out:
+                        yield np.frombuffer(out, dtype=np.uint8)
             finally:
                 gen.close()
 
@@ -831,6 +856,7 @@ def _checked_voice(registry: VoiceRegistry, text: str, ref_audio_name: str, ref_
 
 
 RESPONSE_FORMATS = {"wav": "audio/wav", "pcm": "audio/pcm"}   # response_format -> media type; "pcm": headerless samples / code bytes
+MEDIA_TYPES = dict(RESPONSE_FORMATS, flac="audio/flac")       # container -> media type: FLAC (`encoding: "flac"`) is its own container
 
 
 def check_response_format(response_format) -> str:
@@ -841,10 +867,23 @@ def check_response_format(response_format) -> str:
     return fmt
 
 
+def container_format(response_format, encoding=None) -> str:
+    """The container of a response body: `check_response_format`'s "wav" or "pcm" -- or "flac" for `encoding` "flac", which is its own
+    container: `response_format` must then be absent (ValueError, a 400 on the routes, for "wav" or "pcm" beside it)."""
+    if encoding not in infer.FLAC_ENCODINGS:
+        return check_response_format(response_format)
+    if response_format is not None:
+        check_response_format(response_format)
+        raise ValueError(f'encoding "flac" is its own container (audio/flac): response_format must be absent (got {response_format!r})')
+    return "flac"
+
+
 def response_body(audio, options: dict, response_format: str = "wav") -> io.BytesIO:
-    """The response body of a request's result in the delivery format its `options` name: a WAV file (`wav_bytes`), or with "pcm" the
-    headerless little-endian samples / code bytes."""
+    """The response body of a request's result in the delivery format its `options` name: a WAV file (`wav_bytes`), with "pcm" the
+    headerless little-endian samples / code bytes, and for `encoding` "flac" the FLAC stream the result holds."""
     rate, enc = infer.delivery_format(options.get("sample_rate"), options.get("encoding"))
+    if enc in infer.FLAC_ENCODINGS:
+        return io.BytesIO(delivery_bytes(audio, enc))
     return io.BytesIO(delivery_bytes(audio, enc)) if response_format == "pcm" else wav_bytes(audio, rate, enc)
 
 
@@ -934,7 +973,9 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     before anything is queued (400 with `check_request_options`'s message); an omitted field is the manager's setting (`ode_method`: the
     model's).  With a `seed`, the same request returns the same audio.  The delivery format, on every route: `sample_rate` (one of
     `infer.OUTPUT_SAMPLE_RATES`), `encoding` ("pcm16", "mulaw" or "alaw": G.711, one byte per sample) and `response_format` ("wav", or "pcm"
-    for the headerless samples / code bytes as `audio/pcm`); streamed or not, the body's samples are the same bytes."""
+    for the headerless samples / code bytes as `audio/pcm`); streamed or not, the body's samples are the same bytes.  `encoding: "flac"` is
+    its own container: the body is the native FLAC stream of the samples (`infer.encode_flac`, lossless) as `audio/flac` with a `.flac` file
+    name, and `response_format` must be absent (400 with "wav" or "pcm" beside it); streamed, the stream header comes with the totals unknown."""
     from fastapi import APIRouter, FastAPI, HTTPException
     from starlette.responses import StreamingResponse
 
@@ -947,9 +988,9 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
 
-    def _response_format(req):
+    def _response_format(req, opts):
         try:
-            return check_response_format(req.response_format)
+            return container_format(req.response_format, opts.get("encoding"))
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
 
@@ -963,7 +1004,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
             yield block
 
     def _headers(filename, fmt):
-        return {"Content-Disposition": f"attachment; filename={filename if fmt == 'wav' else filename.rsplit('.', 1)[0] + '.pcm'}"}
+        return {"Content-Disposition": f"attachment; filename={filename if fmt == 'wav' else filename.rsplit('.', 1)[0] + '.' + fmt}"}
 
     router = APIRouter(prefix="/v1", tags=["speech"])
 
@@ -979,24 +1020,29 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         return opts
 
     def _run(text, name, ref_text, filename, req):
-        opts, fmt = _speech_options(text, req), _response_format(req)
+        opts = _speech_options(text, req)
+        fmt = _response_format(req, opts)
         try:
             buf = synthesize_speech(tts_manager, registry, text=text, ref_audio_name=name, ref_text=ref_text, response_format=fmt, **opts)
         except HTTPError as e:
             raise HTTPException(status_code=e.status_code, detail=e.detail)
-        return StreamingResponse(_blocks(buf), media_type=RESPONSE_FORMATS[fmt], headers=_headers(filename, fmt))
+        return StreamingResponse(_blocks(buf), media_type=MEDIA_TYPES[fmt], headers=_headers(filename, fmt))
 
     def _run_stream(text, name, ref_text, filename, req):
         """stream=true: the same checks as `_run`, then the first piece is synthesized BEFORE the response exists, so a bad request, an
         unloaded model or a failing first chunk still comes back as a status code.  The body is a streaming WAV (`wav_stream_header`)
-        followed by the pieces in the delivery format (int16 PCM, or G.711 code bytes; no header with response_format "pcm"); a failure after the first bytes can only end the body early, and is logged."""
-        opts, fmt = _speech_options(text, req), _response_format(req)
+        followed by the pieces in the delivery format (int16 PCM, or G.711 code bytes; no header with response_format "pcm").  With
+        encoding "flac" the body is the FLAC stream alone (`audio/flac`): its 42-byte header with the totals unknown, which the manager's
+        stream hands out only once the first chunk is there, then the frames as they complete.  A failure after the first bytes can only
+        end the body early, and is logged."""
+        opts = _speech_options(text, req)
+        fmt = _response_format(req, opts)
         try:
             pieces = stream_speech(tts_manager, registry, text=text, ref_audio_name=name, ref_text=ref_text, **opts)
             first = next(pieces, None)
         except HTTPError as e:
             raise HTTPException(status_code=e.status_code, detail=e.detail)
-        return StreamingResponse(_pcm_body(first, pieces, opts, fmt), media_type=RESPONSE_FORMATS[fmt], headers=_headers(filename, fmt))
+        return StreamingResponse(_pcm_body(first, pieces, opts, fmt), media_type=MEDIA_TYPES[fmt], headers=_headers(filename, fmt))
 
     async def _pcm_body(first, pieces, opts, fmt):
         # the synthesis runs in the thread pool, one piece at a time; leaving early (client gone, error) closes the generator,
@@ -1020,7 +1066,8 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     def _run_clone(req):
         """`/v1/audio/speech/clone`: the speech routes' checks, then the clip's (`TTSManager._clip_voice`: 400 with its message), then
         `synthesize_clip` -- or, with stream=true, `synthesize_clip_stream` with the first piece synthesized before the response exists."""
-        opts, fmt = _speech_options(req.text, req), _response_format(req)
+        opts = _speech_options(req.text, req)
+        fmt = _response_format(req, opts)
         try:
             raw = base64.b64decode(req.ref_audio, validate=True)
         except (binascii.Error, ValueError):
@@ -1030,16 +1077,17 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
             if req.stream:
                 pieces = tts_manager.synthesize_clip_stream(req.text, raw, req.ref_text, clip_short=req.clip_short, **opts)
                 first = next(pieces, None)
-                return StreamingResponse(_pcm_body(first, pieces, opts, fmt), media_type=RESPONSE_FORMATS[fmt], headers=headers)
+                return StreamingResponse(_pcm_body(first, pieces, opts, fmt), media_type=MEDIA_TYPES[fmt], headers=headers)
             wave = tts_manager.synthesize_clip(req.text, raw, req.ref_text, clip_short=req.clip_short, **opts)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
-        return StreamingResponse(_blocks(response_body(wave, opts, fmt)), media_type=RESPONSE_FORMATS[fmt], headers=headers)
+        return StreamingResponse(_blocks(response_body(wave, opts, fmt)), media_type=MEDIA_TYPES[fmt], headers=headers)
 
     def _run_script(req):
         """`/v1/audio/speech/script`: the speech routes' checks, each voice's (a registered name as on `/voice`, a clip as on `/clone`),
         then `synthesize_script` -- or, with stream=true, `synthesize_script_stream` with the first piece synthesized before the response."""
-        opts, fmt = _speech_options(req.text, req), _response_format(req)
+        opts = _speech_options(req.text, req)
+        fmt = _response_format(req, opts)
         voices = {}
         for tag, v in req.voices.items():
             spec = dict(ref_text=v.ref_text, speed=v.speed)
@@ -1063,16 +1111,17 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
             if req.stream:
                 pieces = tts_manager.synthesize_script_stream(req.text, voices, gap=req.gap, **opts)
                 first = next(pieces, None)
-                return StreamingResponse(_pcm_body(first, pieces, opts, fmt), media_type=RESPONSE_FORMATS[fmt], headers=headers)
+                return StreamingResponse(_pcm_body(first, pieces, opts, fmt), media_type=MEDIA_TYPES[fmt], headers=headers)
             wave = tts_manager.synthesize_script(req.text, voices, gap=req.gap, **opts)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
-        return StreamingResponse(_blocks(response_body(wave, opts, fmt)), media_type=RESPONSE_FORMATS[fmt], headers=headers)
+        return StreamingResponse(_blocks(response_body(wave, opts, fmt)), media_type=MEDIA_TYPES[fmt], headers=headers)
 
     def _run_edit(req):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
-        opts, fmt = _options(req, EDIT_OPTIONS + ("sample_rate", "encoding")), _response_format(req)
+        opts = _options(req, EDIT_OPTIONS + ("sample_rate", "encoding"))
+        fmt = _response_format(req, opts)
         try:
             raw = base64.b64decode(req.audio, validate=True)
         except (binascii.Error, ValueError):
@@ -1087,7 +1136,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
             wave = tts_manager.edit(audio, req.text, req.parts_to_edit, req.fix_duration, **opts)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
-        return StreamingResponse(_blocks(response_body(wave, opts, fmt)), media_type=RESPONSE_FORMATS[fmt], headers=_headers("edited_speech.wav", fmt))
+        return StreamingResponse(_blocks(response_body(wave, opts, fmt)), media_type=MEDIA_TYPES[fmt], headers=_headers("edited_speech.wav", fmt))
 
     # The reference's handlers are `async def` around a blocking call, i.e. one request at a time.  Here the blocking part runs in
     # starlette's thread pool, so concurrent requests overlap and meet in the MicroBatcher queue (when the manager has one).

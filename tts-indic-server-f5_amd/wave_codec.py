@@ -1,6 +1,6 @@
 """Waves in and out of the server, with nothing of the model in it: reading WAV files (`load_wav`), torchaudio's polyphase sinc resampler
 (`rate_pair`, `resample_taps`, `resample_sinc_hann`) with its tap-table caches, the integer resampler of finished PCM (`resample_pcm16`,
-`StreamResampler`), G.711 (`encode_g711`, `decode_g711`), the delivery format of a request (`delivery_format`, `deliver_pcm16`) and the bytes
+`StreamResampler`), G.711 (`encode_g711`, `decode_g711`), FLAC (`encode_flac`, `decode_flac`, `StreamFlacEncoder`), the delivery format of a request (`delivery_format`, `deliver_pcm16`) and the bytes
 of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
 round; `infer` and `serve` hand every public name on (`infer.load_wav`, `serve.wav_bytes`, ...)."""
 from __future__ import annotations
@@ -213,6 +213,8 @@ def quantise_pcm16(wave) -> np.ndarray:
 # ----------------------------------------- delivery format: output sample rate and G.711 (not in the reference, whose route always answers 24 kHz PCM)
 OUTPUT_SAMPLE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
 OUTPUT_ENCODINGS = ("pcm16", "mulaw", "alaw")     # their position is the library's encoding code (include/f5hip.h f5hip_wave_encode)
+FLAC_ENCODINGS = ("flac",)                        # beside them, not among them: a FLAC result is a whole stream (`encode_flac`), not samples
+ALL_ENCODINGS = OUTPUT_ENCODINGS + FLAC_ENCODINGS
 
 
 def _polyphase_pcm(xpad, taps64, of, nq):
@@ -348,21 +350,24 @@ def decode_g711(codes, law) -> np.ndarray:
 
 
 def delivery_format(sample_rate=None, encoding=None):
-    """(rate, encoding) of a request with None filled in (24000, "pcm16"), checked against OUTPUT_SAMPLE_RATES / OUTPUT_ENCODINGS."""
+    """(rate, encoding) of a request with None filled in (24000, "pcm16"), checked against OUTPUT_SAMPLE_RATES and OUTPUT_ENCODINGS +
+    FLAC_ENCODINGS."""
     rate = SAMPLE_RATE if sample_rate is None else sample_rate
     enc = "pcm16" if encoding is None else encoding
     if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or int(rate) not in OUTPUT_SAMPLE_RATES:
         raise ValueError(f"sample_rate must be one of {list(OUTPUT_SAMPLE_RATES)} (got {sample_rate!r})")
-    if not isinstance(enc, str) or enc not in OUTPUT_ENCODINGS:
-        raise ValueError(f"encoding must be one of {list(OUTPUT_ENCODINGS)} (got {encoding!r})")
+    if not isinstance(enc, str) or enc not in ALL_ENCODINGS:
+        raise ValueError(f"encoding must be one of {list(ALL_ENCODINGS)} (got {encoding!r})")
     return int(rate), enc
 
 
 def deliver_pcm16(pcm, sample_rate=None, encoding=None) -> np.ndarray:
-    """The delivery format of a request's canonical result, its 24 kHz int16 PCM: `resample_pcm16`, then `encode_g711` -- int16 at
-    `sample_rate`, or uint8 code bytes.  (24000, "pcm16") returns the PCM itself."""
+    """The delivery format of a request's canonical result, its 24 kHz int16 PCM: `resample_pcm16`, then `encode_g711` or `encode_flac` --
+    int16 at `sample_rate`, uint8 code bytes, or a uint8 array that holds the FLAC stream.  (24000, "pcm16") returns the PCM itself."""
     rate, enc = delivery_format(sample_rate, encoding)
     pcm = resample_pcm16(pcm, rate)
+    if enc in FLAC_ENCODINGS:
+        return encode_flac(pcm, rate)
     return pcm if enc == "pcm16" else encode_g711(pcm, enc)
 
 
@@ -377,11 +382,14 @@ def _g711_header(encoding, sample_rate, n, riff_size, data_size):
 
 
 def delivery_bytes(audio, encoding: str = "pcm16") -> bytes:
-    """The body bytes of samples in any of the forms a request's result takes: uint8 G.711 codes as they are, int16 PCM little-endian, float
-    samples by `pcm16`'s rule -- and, for a G.711 `encoding`, PCM that is not encoded yet through `encode_g711`."""
+    """The body bytes of samples in any of the forms a request's result takes: uint8 G.711 codes or FLAC stream bytes as they are, int16
+    PCM little-endian, float samples by `pcm16`'s rule -- and, for a G.711 `encoding`, PCM that is not encoded yet through `encode_g711`
+    ("flac" needs the rate as well: `encode_flac`)."""
     a = np.asarray(audio)
     if a.dtype == np.uint8:
         return a.tobytes()
+    if encoding in FLAC_ENCODINGS:
+        raise ValueError("delivery_bytes: a FLAC body is the stream `encode_flac` / `deliver_pcm16` made (uint8), not samples")
     if a.dtype != np.int16:
         a = quantise_pcm16(a)
     if encoding != "pcm16":
@@ -418,3 +426,360 @@ def wav_stream_header(sample_rate: int = SAMPLE_RATE, encoding: str = "pcm16") -
         return _g711_header(encoding, sample_rate, 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF)
     return (b"RIFF" + struct.pack("<I", 0xFFFFFFFF) + b"WAVE" + b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, sample_rate, sample_rate * 2, 2, 16)
             + b"data" + struct.pack("<I", 0xFFFFFFFF))
+
+
+# ----------------------------------------- FLAC (RFC 9639), the fixed-predictor subset: the one compressed delivery format, lossless, integer
+# arithmetic with no freedom left once the choice rule is written down -- so the device encoder (csrc/wave_out.h wave_flac_*) is held to
+# `encode_flac` byte for byte like every other back-end kernel.
+#   stream    "fLaC", one STREAMINFO block (last-block flag, length 34): min = max block size 4096, the true min / max frame size and total
+#             sample count, MD5 all zero ("not computed": a device-side result must not need the PCM on the host); 42 bytes; then the frames
+#   frame     sync 0xFFF8 (fixed block size: the FRAME number is coded), block-size code 1100 (4096) or, for the short last frame, 0111 with a
+#             16-bit b - 1; the rate's code; channel code 0000; sample-size code 100; the frame number UTF-8-like; CRC-8; ONE subframe without
+#             wasted bits; zero padding to a byte; CRC-16
+#   subframe  CONSTANT when all samples of the block are equal; else the fixed order o in 0..4, o < b, with the fewest bits (ties: the lower
+#             order); VERBATIM only when strictly smaller than that.  Bits: CONSTANT 8 + 16, VERBATIM 8 + 16 b, FIXED 8 + 16 o + 2 + 4 +
+#             sum over partitions (4 + S_k)
+#   residual  coding method 00 (4-bit Rice parameters), never the escape code; a full block has partition order 4 (16 partitions of 256, the
+#             first with 256 - o residuals), the short last block partition order 0; per partition k in 0..14 minimises S_k = sum(u >> k) +
+#             n (1 + k) (ties: the smaller k), u = 2 r for r >= 0 and -2 r - 1 otherwise; a code is u >> k zero bits, a one, the low k bits
+FLAC_BLOCK = 4096
+FLAC_HEADER_BYTES = 42
+FLAC_RATE_CODES = {8000: 4, 16000: 5, 22050: 6, 24000: 7, 32000: 8, 44100: 9, 48000: 10}
+_FLAC_MAX_K = 14
+_FLAC_PARTITION_ORDER = 4
+
+
+def _crc_table(poly, bits):
+    top, mask, table = 1 << (bits - 1), (1 << bits) - 1, []
+    for b in range(256):
+        c = b << (bits - 8)
+        for _ in range(8):
+            c = ((c << 1) ^ poly) & mask if c & top else (c << 1) & mask
+        table.append(c)
+    return table
+
+
+_CRC8_TABLE, _CRC16_TABLE = _crc_table(0x07, 8), _crc_table(0x8005, 16)
+
+
+def flac_crc8(data) -> int:
+    """CRC-8 of a frame header: polynomial 0x07, initial value 0 (of b"123456789": 0xF4)."""
+    c = 0
+    for b in bytes(data):
+        c = _CRC8_TABLE[c ^ b]
+    return c
+
+
+def flac_crc16(data) -> int:
+    """CRC-16 of a frame: polynomial 0x8005, initial value 0, not reflected (of b"123456789": 0xFEE8)."""
+    c, t = 0, _CRC16_TABLE
+    for b in bytes(data):
+        c = ((c << 8) & 0xFFFF) ^ t[(c >> 8) ^ b]
+    return c
+
+
+def _flac_number(v):
+    """A frame number in the format's UTF-8-like coding: 7 bits in one byte, else 11, 16, 21, 26, 31 or 36 bits in 2 .. 7."""
+    if v < 0x80:
+        return bytes([v])
+    n = 2
+    while n < 7 and v >= 1 << (5 * n + 1):
+        n += 1
+    lead = (0xFF << (8 - n)) & 0xFF
+    return bytes([lead | (v >> (6 * (n - 1)))] + [0x80 | ((v >> (6 * k)) & 0x3F) for k in range(n - 2, -1, -1)])
+
+
+def _flac_rate(sample_rate):
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, np.integer)) or int(sample_rate) not in FLAC_RATE_CODES:
+        raise ValueError(f"sample_rate must be one of {list(OUTPUT_SAMPLE_RATES)} (got {sample_rate!r})")
+    return int(sample_rate)
+
+
+def flac_stream_header(sample_rate, total=0, min_frame=0, max_frame=0) -> bytes:
+    """The 42 bytes in front of the frames: "fLaC" and STREAMINFO (mono, 16 bits, block size 4096, MD5 zero); zeros mean "unknown"."""
+    rate = _flac_rate(sample_rate)
+    info = (struct.pack(">HH", FLAC_BLOCK, FLAC_BLOCK) + min_frame.to_bytes(3, "big") + max_frame.to_bytes(3, "big")
+            + ((rate << 44) | (0 << 41) | (15 << 36) | total).to_bytes(8, "big") + bytes(16))
+    return b"fLaC" + bytes([0x80]) + len(info).to_bytes(3, "big") + info
+
+
+def _flac_plan(x):
+    """The choice rule on blocks x int64 [F, b] of one size: (kind [F]: -1 CONSTANT, 0..4 the fixed order, 5 VERBATIM; ks [F, P]: the chosen
+    order's Rice parameters; us: per order the zigzag residuals [F, b - o]).  About 75 passes over the blocks: 5 orders x 15 parameters."""
+    F, b = x.shape
+    parts = 1 << _FLAC_PARTITION_ORDER if b == FLAC_BLOCK else 1
+    plen = b // parts
+    orders = min(5, b)
+    bits = np.empty((orders, F), dtype=np.int64)
+    ks = np.empty((orders, F, parts), dtype=np.int64)
+    us, r = [], x
+    for o in range(orders):
+        if o:
+            r = np.diff(r, axis=1)
+        u = np.where(r >= 0, 2 * r, -2 * r - 1)
+        us.append(u)
+        padded = np.concatenate([np.zeros((F, o), dtype=np.int64), u], axis=1).reshape(F, parts, plen)   # (a zero adds nothing to sum(u >> k))
+        n = np.full(parts, plen, dtype=np.int64)
+        n[0] -= o
+        s = np.stack([(padded >> k).sum(axis=2) + n * (1 + k) for k in range(_FLAC_MAX_K + 1)])        # [15, F, parts]
+        ks[o] = s.argmin(axis=0)                                                                        # (the first minimum: the smaller k)
+        bits[o] = 8 + 16 * o + 2 + 4 + (4 + s.min(axis=0)).sum(axis=1)
+    kind = bits.argmin(axis=0)                                                                          # (the first minimum: the lower order)
+    best = bits[kind, np.arange(F)]
+    kind = np.where(8 + 16 * b < best, 5, kind)
+    kind = np.where((x == x[:, :1]).all(axis=1), -1, kind)
+    return kind, ks[np.minimum(np.maximum(kind, 0), orders - 1), np.arange(F)], us
+
+
+def _be16_bits(v):
+    return np.unpackbits(np.asarray(v).astype(">i2").view(np.uint8))
+
+
+def _flac_frame(x, number, rate_code, kind, ks, u):
+    """One frame's bytes: block x (int64 [b]) as frame `number`, with `_flac_plan`'s choice for it (u: the chosen order's residuals)."""
+    b = len(x)
+    head = bytes([0xFF, 0xF8, ((0x0C if b == FLAC_BLOCK else 0x07) << 4) | rate_code, 0x08]) + _flac_number(number)
+    if b != FLAC_BLOCK:
+        head += (b - 1).to_bytes(2, "big")
+    head += bytes([flac_crc8(head)])
+    if kind == -1:
+        body = bytes([0x00]) + int(x[0]).to_bytes(2, "big", signed=True)
+    elif kind == 5:
+        body = bytes([0x02]) + x.astype(">i2").tobytes()
+    else:
+        o, parts = int(kind), len(ks)
+        plen = b // parts
+        k = np.repeat(ks, plen)[o:]
+        q = u >> k
+        length = q + 1 + k
+        lead = 8 + 16 * o + 6                                    # subframe header, warm-up, coding method and partition order
+        bounds = np.concatenate([[0], np.cumsum(length)])        # code i starts at bounds[i] + lead + 4 * (partitions opened up to it)
+        opened = np.repeat(np.arange(1, parts + 1), plen)[o:]
+        start = lead + 4 * opened + bounds[:-1]
+        nbits = lead + 4 * parts + int(bounds[-1])
+        bit = np.zeros((nbits + 7) // 8 * 8, dtype=np.uint8)
+        bit[:8] = np.unpackbits(np.array([(8 | o) << 1], dtype=np.uint8))
+        bit[8:8 + 16 * o] = _be16_bits(x[:o])
+        bit[8 + 16 * o + 2:lead] = np.unpackbits(np.array([_FLAC_PARTITION_ORDER if parts > 1 else 0], dtype=np.uint8))[4:]
+        first = np.concatenate([[0], np.arange(1, parts) * plen - o])          # the first residual of each partition
+        pstart = start[first] - 4
+        for j in range(4):
+            bit[pstart + j] = (ks >> (3 - j)) & 1
+        bit[start + q] = 1
+        for j in range(_FLAC_MAX_K):                              # low bit j of the codes whose parameter reaches it, most significant first
+            m = k > j
+            bit[(start + q + 1 + j)[m]] = ((u[m] >> (k[m] - 1 - j)) & 1).astype(np.uint8)
+        body = np.packbits(bit).tobytes()
+    frame = head + body
+    return frame + flac_crc16(frame).to_bytes(2, "big")
+
+
+def _flac_frames(pcm, first_number, rate_code):
+    """The frames of int16 PCM whose first block is frame `first_number`: whole blocks of 4096 and, if samples remain, one short block."""
+    n = len(pcm)
+    full, out = n // FLAC_BLOCK, []
+    groups = [pcm[:full * FLAC_BLOCK].astype(np.int64).reshape(full, FLAC_BLOCK)] if full else []
+    if n % FLAC_BLOCK:
+        groups.append(pcm[full * FLAC_BLOCK:].astype(np.int64)[None])
+    for x in groups:
+        const = (x == x[:, :1]).all(axis=1)                       # (not planned: a long silence costs one comparison per sample)
+        busy = np.flatnonzero(~const)
+        kind, ks, us = _flac_plan(x[busy]) if len(busy) else (None, None, None)
+        where = {int(f): i for i, f in enumerate(busy)}
+        for f in range(len(x)):
+            number = first_number + len(out)
+            if const[f]:
+                out.append(_flac_frame(x[f], number, rate_code, -1, None, None))
+            else:
+                i = where[f]
+                out.append(_flac_frame(x[f], number, rate_code, int(kind[i]), ks[i], us[kind[i]][i] if 0 <= kind[i] < 5 else None))
+    return out
+
+
+def encode_flac(pcm, sample_rate) -> np.ndarray:
+    """The native FLAC stream (uint8) of mono int16 PCM at `sample_rate` (one of OUTPUT_SAMPLE_RATES), in the subset and by the choice rule
+    written above this function: a pure function of the samples and the rate, which `ops.wave_flac` equals byte for byte.  An empty input
+    is the 42-byte header alone, with total 0 and frame sizes 0."""
+    pcm, rate = _as_pcm16(pcm), _flac_rate(sample_rate)
+    frames = _flac_frames(pcm, 0, FLAC_RATE_CODES[rate])
+    sizes = [len(f) for f in frames] or [0]
+    return np.frombuffer(flac_stream_header(rate, len(pcm), min(sizes), max(sizes)) + b"".join(frames), dtype=np.uint8).copy()
+
+
+class StreamFlacEncoder:
+    """`encode_flac` one piece at a time: `header()` is the 42 bytes with total samples 0 and frame sizes 0 (unknown length), `feed(piece)`
+    the bytes of every 4096-sample frame the piece completes, `flush()` the short last frame.  The concatenation of everything `feed` and
+    `flush` return equals `encode_flac(...)[42:]` of the concatenated input, whatever the piece sizes: a frame depends on its own samples
+    and its number alone."""
+
+    def __init__(self, sample_rate):
+        self.sample_rate = _flac_rate(sample_rate)
+        self.code = FLAC_RATE_CODES[self.sample_rate]
+        self.pending = np.zeros(0, dtype=np.int16)
+        self.frames = 0
+
+    def header(self) -> bytes:
+        return flac_stream_header(self.sample_rate)
+
+    def _emit(self, pcm):
+        frames = _flac_frames(pcm, self.frames, self.code)
+        self.frames += len(frames)
+        return b"".join(frames)
+
+    def feed(self, piece) -> bytes:
+        self.pending = np.concatenate([self.pending, _as_pcm16(piece)])
+        whole = len(self.pending) // FLAC_BLOCK * FLAC_BLOCK
+        ready, self.pending = self.pending[:whole], self.pending[whole:]
+        return self._emit(ready)
+
+    def flush(self) -> bytes:
+        ready, self.pending = self.pending, np.zeros(0, dtype=np.int16)
+        return self._emit(ready)
+
+
+class _FlacBits:
+    """Big-endian bit reader over bytes: one Python integer (a read is a shift and a mask) and, for the unary parts, one byte per bit."""
+
+    def __init__(self, data):
+        self.n = 8 * len(data)
+        self.v = int.from_bytes(data, "big")
+        self.bits = None
+        self.data = data
+        self.pos = 0
+
+    def read(self, bits):
+        if self.pos + bits > self.n:
+            raise ValueError("truncated FLAC stream")
+        self.pos += bits
+        return (self.v >> (self.n - self.pos)) & ((1 << bits) - 1)
+
+    def signed(self, bits):
+        v = self.read(bits)
+        return v - (1 << bits) if bits and v >> (bits - 1) else v
+
+    def unary(self):
+        """Zero bits up to the next one bit, which is consumed."""
+        if self.bits is None:
+            self.bits = np.unpackbits(np.frombuffer(self.data, dtype=np.uint8)).tobytes()
+        one = self.bits.find(b"\x01", self.pos)
+        if one < 0:
+            raise ValueError("truncated FLAC stream")
+        zeros, self.pos = one - self.pos, one + 1
+        return zeros
+
+
+_FLAC_BLOCK_SIZES = {1: 192, 2: 576, 3: 1152, 4: 2304, 5: 4608, **{c: 256 << (c - 8) for c in range(8, 16)}}
+
+
+def _flac_residual(rd, b, o):
+    method = rd.read(2)
+    if method > 1:
+        raise ValueError(f"unsupported FLAC stream: residual coding method {method}")
+    pbits, porder = 4 + method, rd.read(4)
+    if b % (1 << porder) or (b >> porder) < o:
+        raise ValueError("corrupt FLAC stream: partition order does not fit the block")
+    out = []
+    for p in range(1 << porder):
+        n = (b >> porder) - (o if p == 0 else 0)
+        k = rd.read(pbits)
+        if k == (1 << pbits) - 1:                                # the escape code: n raw values
+            raw = rd.read(5)
+            out += [rd.signed(raw) for _ in range(n)]
+            continue
+        for _ in range(n):
+            u = (rd.unary() << k) | rd.read(k)
+            out.append(u >> 1 if not u & 1 else -(u >> 1) - 1)
+    return np.array(out, dtype=np.int64)
+
+
+def _flac_unpredict(warm, res):
+    """The samples of a fixed subframe of order len(warm): the order's differences summed back up, level by level."""
+    o = len(warm)
+    levels = [np.asarray(warm, dtype=np.int64)]                   # levels[j]: the j-th differences known from the warm-up, from index j on
+    for _ in range(o):
+        levels.append(np.diff(levels[-1]))
+    seq = res
+    for j in range(o - 1, -1, -1):                                # the (j+1)-th differences from index o on -> the j-th from index o on
+        seq = levels[j][-1] + np.cumsum(seq)
+    return np.concatenate([levels[0], seq])
+
+
+def decode_flac(stream):
+    """(int16 PCM, sample_rate) of a native FLAC stream: any mono 16-bit stream of CONSTANT, VERBATIM and FIXED subframes -- `encode_flac`'s
+    own, and an upload's.  Both CRCs of every frame are checked.  Anything else (more channels, another sample size, an LPC subframe, a bad
+    checksum, a truncated or malformed stream) raises ValueError."""
+    data = bytes(stream.tobytes() if isinstance(stream, np.ndarray) else stream)
+    if data[:4] != b"fLaC":
+        raise ValueError(f"not a FLAC stream (starts with {data[:4]!r})")
+    pos, info = 4, None
+    while True:
+        if pos + 4 > len(data):
+            raise ValueError("truncated FLAC stream: metadata")
+        kind, size = data[pos] & 0x7F, int.from_bytes(data[pos + 1:pos + 4], "big")
+        last, pos = data[pos] >> 7, pos + 4
+        if pos + size > len(data):
+            raise ValueError("truncated FLAC stream: metadata")
+        if info is None:
+            if kind != 0 or size != 34:
+                raise ValueError("corrupt FLAC stream: the first metadata block is not STREAMINFO")
+            info = int.from_bytes(data[pos + 10:pos + 18], "big")
+        pos += size
+        if last:
+            break
+    rate, channels, bps, total = info >> 44, ((info >> 41) & 7) + 1, ((info >> 36) & 31) + 1, info & ((1 << 36) - 1)
+    if channels != 1 or bps != 16:
+        raise ValueError(f"unsupported FLAC stream: {channels} channel(s) at {bps} bits (mono 16-bit only)")
+    blocks, count = [], 0
+    while pos < len(data):
+        start = pos
+        rd = _FlacBits(data[pos:pos + 16])
+        if rd.n < 40 or rd.read(15) != 0x7FFC:
+            raise ValueError(f"corrupt FLAC stream: no frame sync at byte {pos}")
+        rd.read(1)                                               # blocking strategy: the coded number is not needed to decode
+        bs_code, rate_code, ch_code, size_code, reserved = rd.read(4), rd.read(4), rd.read(4), rd.read(3), rd.read(1)
+        if ch_code != 0 or size_code not in (0, 4) or reserved or bs_code == 0 or rate_code == 15:
+            raise ValueError("unsupported FLAC stream: a frame that is not mono 16-bit")
+        lead = rd.read(8)
+        extra = 0 if lead < 0x80 else 8 - (lead ^ 0xFF).bit_length() - 1 if lead >= 0xC0 and lead != 0xFF else -1
+        if extra < 0:
+            raise ValueError("corrupt FLAC stream: frame number")
+        for _ in range(extra):
+            if rd.read(8) >> 6 != 2:
+                raise ValueError("corrupt FLAC stream: frame number")
+        b = rd.read(8) + 1 if bs_code == 6 else rd.read(16) + 1 if bs_code == 7 else _FLAC_BLOCK_SIZES[bs_code]
+        rd.read({12: 8, 13: 16, 14: 16}.get(rate_code, 0))
+        hlen = rd.pos // 8
+        if flac_crc8(data[pos:pos + hlen]) != rd.read(8):
+            raise ValueError(f"corrupt FLAC stream: header CRC-8 of the frame at byte {start}")
+        rd = _FlacBits(data[pos + hlen + 1:pos + hlen + 1 + 8 * b + 1024])   # (four times VERBATIM: no sane subframe is larger)
+        if rd.read(1):
+            raise ValueError("corrupt FLAC stream: subframe padding bit")
+        typ, wasted = rd.read(6), rd.read(1)
+        if wasted:
+            wasted = rd.unary() + 1
+        depth = 16 - wasted
+        if depth < 1:
+            raise ValueError("corrupt FLAC stream: wasted bits")
+        if typ == 0:
+            x = np.full(b, rd.signed(depth), dtype=np.int64)
+        elif typ == 1:
+            x = np.array([rd.signed(depth) for _ in range(b)], dtype=np.int64)
+        elif 8 <= typ <= 12 and typ - 8 <= b:
+            warm = [rd.signed(depth) for _ in range(typ - 8)]
+            x = _flac_unpredict(warm, _flac_residual(rd, b, typ - 8))
+        else:
+            raise ValueError(f"unsupported FLAC stream: subframe type {typ:#04x} (CONSTANT, VERBATIM and FIXED only)")
+        x = x << wasted
+        if len(x) != b or x.min() < -32768 or x.max() > 32767:
+            raise ValueError("corrupt FLAC stream: samples outside 16 bits")
+        end = pos + hlen + 1 + (rd.pos + 7) // 8
+        if end + 2 > len(data):
+            raise ValueError("truncated FLAC stream: frame")
+        if flac_crc16(data[start:end]) != int.from_bytes(data[end:end + 2], "big"):
+            raise ValueError(f"corrupt FLAC stream: CRC-16 of the frame at byte {start}")
+        blocks.append(x.astype(np.int16))
+        count += b
+        pos = end + 2
+    if total and total != count:
+        raise ValueError(f"corrupt FLAC stream: STREAMINFO names {total} samples, the frames hold {count}")
+    return (np.concatenate(blocks) if blocks else np.zeros(0, dtype=np.int16)), int(rate)
