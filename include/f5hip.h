@@ -536,6 +536,34 @@ int f5hip_wave_flac(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, co
  * VERBATIM plus 16 bytes); 0 for a negative length. */
 int64_t f5hip_wave_flac_bound(int32_t max_len);
 
+/* Loudness target: the 24 kHz int16 PCM of n requests, still on the device (f5hip_wave_finish's pcm_dev), moved IN PLACE to each flagged
+ * request's programme loudness (ITU-R BS.1770-4, mono), bit for bit wave_codec.normalise_loudness_pcm16.  Not in the reference.  It runs
+ * behind f5hip_wave_finish and before f5hip_wave_encode / f5hip_wave_flac.  The arithmetic, integers up to one sqrt:
+ *   K-weighting  y[j] = sum_k h[k] x[j - k], zeros in front; h = 1024 integer taps, rint(2^16 k_true[k]) of the two K-weighting biquads designed
+ *                for 24 kHz (csrc/loudness_taps.inc = wave_codec.loudness_taps(); sum |h| = 212 915, so |y| < 2^33); z[j] = y[j] >> 14, floor
+ *   sub-blocks   e[s] = sum of z^2 over the 2400 samples of sub-block s (< 2^50); only whole sub-blocks count
+ *   blocks       E[b] = (e[b] + e[b+1] + e[b+2] + e[b+3]) >> 8: 400 ms, 75 % overlap, floor(len / 2400) - 3 of them
+ *   gates        E[b] > 75535 = floor(10^((-70 + 0.691) / 10) 9600 2^26); then E[b] > floor(S1 / (10 n1)) over the blocks that pass the first;
+ *                n2, S2 = count and sum of the blocks that pass both (int64: exact for any request below 2^31 samples)
+ *   gain         g = sqrt(K_T n2 / S2), then min(g, 29203 / peak) with peak = max |x| (a sample-peak ceiling of -1 dBFS); x <- clip(rint(x g)),
+ *                half to even: int -> fp64, *, /, sqrt, /, min, *, rint, one correctly rounded fp64 operation each.  n2 == 0 (shorter than
+ *                400 ms, or nothing above the gates): g = 1 and the samples are not written
+ *   pcm_dev, in_off[i], max_len[i], len_dev    as in f5hip_wave_encode, pcm_dev writable
+ *   gain_k                 host double [n]: K_T = 10^((target + 0.691) / 10) 9600 2^26 of request i's target in LUFS; <= 0: the request is left
+ *                          alone (neither its samples nor its stats row are written)
+ *   stats_dev              int64 [n][4], 8-byte aligned: n2, S2, peak, the bits of g, for each flagged request
+ * Three launches whatever n (the K-weighting FIR in exact fp64 FMAs with the sub-block sums and tile peaks; one workgroup per flagged request
+ * for the gates and g; the gain), none when no request is flagged, no host sync between them (counters wave_loudness_launches,
+ * wave_loudness_requests); no atomics, vector stores; a request's bytes depend on that request alone, and neither an unflagged request nor
+ * the bytes between requests are written; the request table is copied on `stream`, which the call waits for once before it launches.
+ * Refused before the first launch: n < 1, a null pointer (len_dev excepted), a negative max_len or offset, a misaligned pointer, a
+ * non-finite gain_k, more than 2^31 - 1 samples. */
+int f5hip_wave_loudness(int32_t n, int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, const double* gain_k,
+                        int64_t* stats_dev, void* stream);
+
+/* Samples one block of f5hip_wave_loudness's first launch owns (two sub-blocks).  For tests, which place request lengths around it. */
+int f5hip_wave_loudness_tile(void);
+
 #ifdef __cplusplus
 }
 #endif

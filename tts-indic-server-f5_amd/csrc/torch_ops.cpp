@@ -436,6 +436,42 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_flac(at::TensorList pcm, con
     return {out, out_len, out_off};
 }
 
+// pcm: the int16 device tensor that holds every request (f5hip_wave_finish's packed PCM), normalised IN PLACE; in_off, max_len, len_dev as
+// wave_encode's; gain_k [n] float64 host: K_T per request, <= 0 leaves the request alone -> stats int64 device [n, 4]: n2, S2, peak, the bits
+// of g (zeros for a request that was left alone)
+at::Tensor wave_loudness(at::Tensor pcm, const at::Tensor& in_off, const at::Tensor& max_len, const c10::optional<at::Tensor>& len_dev,
+                         const at::Tensor& gain_k) {
+    check_host(in_off, at::kLong, "in_off"); check_host(max_len, at::kInt, "max_len"); check_host(gain_k, at::kDouble, "gain_k");
+    const int64_t n = max_len.numel();
+    TORCH_CHECK(max_len.dim() == 1 && n > 0 && in_off.numel() == n && gain_k.numel() == n,
+                "f5hip::wave_loudness: in_off, max_len and gain_k need one value per request");
+    TORCH_CHECK(pcm.is_cuda() && pcm.scalar_type() == at::kShort && pcm.is_contiguous() && pcm.dim() == 1,
+                "f5hip::wave_loudness: pcm must be a contiguous 1-D int16 tensor on a HIP device");
+    if (len_dev.has_value())
+        TORCH_CHECK(len_dev->is_cuda() && len_dev->scalar_type() == at::kInt && len_dev->is_contiguous() && len_dev->numel() == n &&
+                    len_dev->device() == pcm.device(), "f5hip::wave_loudness: len_dev must be a contiguous int32 tensor with one value per request on the pcm's device");
+    const int64_t* io = in_off.data_ptr<int64_t>();
+    const int32_t* ml = max_len.data_ptr<int32_t>();
+    const double* gk = gain_k.data_ptr<double>();
+    int64_t total = 0;
+    bool any = false;
+    for (int64_t i = 0; i < n; i++) {
+        TORCH_CHECK(ml[i] >= 0 && io[i] >= 0 && io[i] + ml[i] <= pcm.numel(), "f5hip::wave_loudness: request ", i, " covers samples [", io[i], ", ",
+                    io[i] + ml[i], ") of a tensor of ", pcm.numel());
+        TORCH_CHECK(std::isfinite(gk[i]), "f5hip::wave_loudness: the gain constant of request ", i, " is not finite");
+        total += ml[i];
+        TORCH_CHECK(total <= INT32_MAX, "f5hip::wave_loudness: the call exceeds 2^31 - 1 samples");
+        any = any || gk[i] > 0.0;
+    }
+    const c10::DeviceGuard guard(pcm.device());
+    at::Tensor stats = at::zeros({n, 4}, pcm.options().dtype(at::kLong));
+    if (!any || pcm.numel() == 0) return stats;      // nothing to launch (an empty tensor has no address to give)
+    const int rc = f5hip_wave_loudness((int32_t)n, pcm.data_ptr<int16_t>(), io, ml, len_dev.has_value() ? len_dev->data_ptr<int32_t>() : (const int32_t*)nullptr,
+                                       gk, stats.data_ptr<int64_t>(), stream_of(pcm));
+    TORCH_CHECK(rc == 0, "f5hip_wave_loudness: ", f5hip_last_error());
+    return stats;
+}
+
 }   // namespace
 
 TORCH_LIBRARY(f5hip, m) {
@@ -454,4 +490,5 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("mel_spectrogram_ragged(Tensor[] waves, int n_fft, int hop_length, int n_mels, int sample_rate, int variant) -> Tensor", &mel_spectrogram_ragged);
     m.def("wave_encode(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int new_freq, int encoding, Tensor? taps) -> (Tensor, Tensor, Tensor)", &wave_encode);
     m.def("wave_flac(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int sample_rate) -> (Tensor, Tensor, Tensor)", &wave_flac);
+    m.def("wave_loudness(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor gain_k) -> Tensor", &wave_loudness);
 }

@@ -18,6 +18,8 @@
 //                         packed in LDS and leave in 16-byte stores.  One launch whatever n.
 //   wave_flac_*_kernel    (f5hip_wave_flac) the int16 PCM of n requests at the delivery rate -> each request's native FLAC stream, three
 //                         launches whatever n: see "delivery format: FLAC" below.
+//   wave_kweight / wave_gate / wave_gain_kernel  (f5hip_wave_loudness) the finished 24 kHz PCM of the flagged requests, in place, to their
+//                         BS.1770 loudness targets, three launches whatever n: see "loudness" below.
 //
 // Exactness.  With every chunk at least 2 F samples long the nested fades of cross_fade_concat never overlap, so joined sample j is either one
 // chunk sample or one fade of two chunk samples, and the closed form above is the host's arithmetic operation for operation (ramp[i] =
@@ -989,5 +991,247 @@ int f5hip_wave_flac(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, co
         g_counters[CNT_WAVE_FLAC_LAUNCHES]++;
     }
     g_counters[CNT_WAVE_FLAC_REQUESTS] += n;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ loudness: BS.1770 target, in place
+// f5hip_wave_loudness: the 24 kHz int16 PCM of n requests, in place, to each flagged request's loudness target -- wave_codec.measure_loudness
+// and normalise_loudness_pcm16 bit for bit (the definition is written down there and in include/f5hip.h).  Integers up to one sqrt: no sum
+// depends on the order of its terms, so the tiling below decides no bit.
+//   wave_kweight_kernel  one block of 192 threads per (flagged request, tile of two 100 ms sub-blocks = 4800 samples).  The tile's samples and
+//                        the kLdTaps - 1 before them go to LDS as fp32 (exact), the tap table as fp64.  A thread owns 25 consecutive outputs
+//                        (a stride of 25 words: no LDS bank conflict) and keeps the 25 samples they need plus the next 7 in a ring of 32
+//                        registers whose slot numbers are compile-time constants (the tap loop is unrolled by 32): a tap costs one broadcast
+//                        tap read, one sample read and 25 fp64 FMAs, and no register moves.  fp64 FMA, not a 64-bit integer MAC: |y| <=
+//                        sum|h| 32768 < 2^33, so every partial sum is an integer below 2^53 and the FMA is exact, and v_fma_f64 issues at
+//                        half the fp32 rate (78.6 TFLOPS fp64 vector in the MI355X data sheet) where the 32 x 32 + 64 integer MAC
+//                        (v_mad_i64_i32) is a quarter-rate instruction and h x (32 767 h does not fit 32 bits) leaves no cheaper one.  z = y >> 14
+//                        on the integer, z^2 summed per thread, then per sub-block (96 threads each) in int64; the tile's max |x| beside it.
+//   wave_gate_kernel     one block per flagged request: E[b] = (e[b] + .. + e[b+3]) >> 8, the absolute gate, the relative gate from the block
+//                        sums (int64, a fixed tree: exact anyway), the peak over the tiles; g and the stats row by one thread.
+//   wave_gain_kernel     the launch-1 grid again: pcm = clip(rint(x g)), 8 samples in a 16-byte load and store where the address allows.
+// Three launches whatever n, none when no request is flagged; no host sync between them; a request's bytes depend on that request alone.
+constexpr int kLdTaps = 1024;                   // wave_codec.LOUDNESS_TAPS
+constexpr int kLdSub = 2400;                    // 100 ms sub-block
+constexpr int kLdRun = 25;                      // consecutive outputs of a thread
+constexpr int kLdThreads = 192;                 // 96 threads a sub-block
+constexpr int kLdTile = kLdThreads * kLdRun;    // 4800: two sub-blocks
+constexpr int kLdRing = 32;                     // the register ring: kLdRun samples in use and kLdRing - kLdRun = 7 read ahead
+constexpr int kLdFront = 8;                     // zeros in front of the LDS window: the read-ahead of the last taps lands there
+constexpr int kLdWindow = kLdFront + kLdTaps - 1 + kLdTile;
+constexpr int kLdYShift = 14, kLdEShift = 8;
+constexpr long long kLdGateAbs = 75535;         // floor(10^((-70 + 0.691) / 10) * 9600 * 2^26): wave_codec.LOUDNESS_GATE_ABS
+constexpr double kLdPeakCeiling = 29203.0;      // -1 dBFS: wave_codec.LOUDNESS_PEAK_CEILING
+__device__ const int kLdTapTable[kLdTaps] = {
+#include "loudness_taps.inc"
+};
+constexpr long long kLdTapAbsSum = 212915;      // sum |h| (loudness_taps.inc states it; tests hold the file to wave_codec.loudness_taps())
+// the bit budget: |y| <= sum|h| 2^15 is exact in fp64 and in int64, |z| < 2^19, a sub-block's sum of z^2 < 2^50, a request's gated sum < 2^63
+static_assert(kLdTapAbsSum * 32768 < (1LL << 53), "wave_loudness: y must be exact in fp64");
+static_assert(((kLdTapAbsSum * 32768) >> kLdYShift) < (1LL << 19), "wave_loudness: |z| < 2^19");
+static_assert((double)kLdSub * (double)(1LL << 38) < (double)(1LL << 50), "wave_loudness: e < 2^50");
+static_assert(kLdTile == 2 * kLdSub && kLdThreads % 2 == 0 && kLdTaps % kLdRing == 0 && kLdRing - kLdRun <= kLdFront && kLdTile % 8 == 0,
+              "wave_loudness tiling");
+
+struct LdReq {
+    long long in_off;    // its first sample, relative to pcm_dev
+    double gain_k;       // K_T of its target
+    int cap;             // upper bound of its length (the length itself without len_dev)
+    int req;             // its index in the call: len_dev and stats row
+    int tile0;           // its first block of launches 1 and 3 = its first peak slot; its sub-block sums start at 2 * tile0
+    int tiles;
+};
+
+F5_DEVICE int ld_len(const int* len_dev, const LdReq& q) { return len_dev ? min(max(len_dev[q.req], 0), q.cap) : q.cap; }
+
+F5_DEVICE void ld_taps32(double (&acc)[kLdRun], double (&w)[kLdRing], const double* __restrict__ tp, const float* __restrict__ xq) {
+    // one group of 32 taps (tp: its first tap): slot numbers are constants; xq = the thread's first sample minus the group's first tap index
+#pragma unroll
+    for (int k = 0; k < kLdRing; k++) {
+        const double t = tp[k];
+        w[(kLdRing + kLdRun - k) & (kLdRing - 1)] = (double)xq[-k - (kLdRing - kLdRun)];   // x[j0 - k - 7]: tap k + 7's first sample
+#pragma unroll
+        for (int r = 0; r < kLdRun; r++) acc[r] = fma(t, w[(kLdRing + r - k) & (kLdRing - 1)], acc[r]);
+    }
+}
+
+__global__ __launch_bounds__(kLdThreads) void wave_kweight_kernel(const LdReq* __restrict__ reqs, int nf, const short* __restrict__ pcm,
+                                                                  const int* __restrict__ len_dev, long long* __restrict__ sub,
+                                                                  int* __restrict__ peaks) {
+    __shared__ __attribute__((aligned(16))) double tp[kLdTaps];
+    __shared__ float xs[kLdWindow];
+    __shared__ long long part[kLdThreads];
+    __shared__ int pk[kLdThreads];
+    const int tid = threadIdx.x;
+    const int f = last_at_or_before<&LdReq::tile0>(reqs, nf, (int)blockIdx.x);
+    const LdReq q = reqs[f];
+    const int tile = blockIdx.x - q.tile0;
+    const int len = ld_len(len_dev, q);
+    const long long j0 = (long long)tile * kLdTile;
+    if (j0 >= len) {                                                    // a tile past the request's actual length: no sub-block, no sample
+        if (tid == 0) peaks[blockIdx.x] = 0;
+        return;
+    }
+    const short* x = pcm + q.in_off;
+    int peak = 0;
+    for (int i = tid; i < kLdWindow; i += kLdThreads) {
+        const long long src = j0 - (kLdTaps - 1) - kLdFront + i;
+        const int v = src >= 0 && src < len ? (int)x[src] : 0;
+        xs[i] = (float)v;
+        if (src >= j0) peak = max(peak, abs(v));
+    }
+    for (int i = tid; i < kLdTaps; i += kLdThreads) tp[i] = (double)kLdTapTable[i];
+    __syncthreads();
+
+    // the thread's 25 outputs start at xb; ring slot (r & 31) holds xb[r] for r = -6 .. 24 before tap 0 (tap 0 fills slot 25 before anything reads it)
+    const float* xb = xs + kLdFront + kLdTaps - 1 + tid * kLdRun;
+    double acc[kLdRun], w[kLdRing];
+#pragma unroll
+    for (int r = 0; r < kLdRun; r++) acc[r] = 0.0;
+#pragma unroll
+    for (int r = kLdRun - kLdRing + 1; r < kLdRun; r++) w[r & (kLdRing - 1)] = (double)xb[r];
+    for (int k0 = 0; k0 < kLdTaps; k0 += kLdRing) ld_taps32(acc, w, tp + k0, xb - k0);
+
+    long long ss = 0;
+#pragma unroll
+    for (int r = 0; r < kLdRun; r++) {
+        const long long z = (long long)acc[r] >> kLdYShift;             // (an arithmetic shift: floor)
+        ss += z * z;
+    }
+    part[tid] = ss;
+    pk[tid] = peak;
+    __syncthreads();
+    if (tid < 2) {                                                      // sub-block `tid` of the tile: only a whole one counts
+        const long long s = 2LL * tile + tid;
+        if ((s + 1) * kLdSub <= len) {
+            long long e = 0;
+            for (int t = 0; t < kLdThreads / 2; t++) e += part[tid * (kLdThreads / 2) + t];
+            sub[2LL * q.tile0 + s] = e;
+        }
+    } else if (tid == 64) {
+        int m = 0;
+        for (int t = 0; t < kLdThreads; t++) m = max(m, pk[t]);
+        peaks[blockIdx.x] = m;
+    }
+}
+
+__global__ __launch_bounds__(256) void wave_gate_kernel(const LdReq* __restrict__ reqs, const int* __restrict__ len_dev,
+                                                        const long long* __restrict__ sub, const int* __restrict__ peaks,
+                                                        long long* __restrict__ stats) {
+    __shared__ long long red[256];
+    const int tid = threadIdx.x;
+    const LdReq q = reqs[blockIdx.x];
+    const int len = ld_len(len_dev, q);
+    const int ns = len / kLdSub, nb = max(ns - 3, 0);
+    const long long* e = sub + 2LL * q.tile0;
+    long long n1 = 0, S1 = 0;
+    for (int b = tid; b < nb; b += 256) {
+        const long long E = (e[b] + e[b + 1] + e[b + 2] + e[b + 3]) >> kLdEShift;
+        if (E > kLdGateAbs) { n1++; S1 += E; }
+    }
+    n1 = block_sum(red, tid, n1);
+    S1 = block_sum(red, tid, S1);
+    long long n2 = 0, S2 = 0;
+    if (n1 > 0) {
+        const long long rel = S1 / (10 * n1);
+        for (int b = tid; b < nb; b += 256) {
+            const long long E = (e[b] + e[b + 1] + e[b + 2] + e[b + 3]) >> kLdEShift;
+            if (E > kLdGateAbs && E > rel) { n2++; S2 += E; }
+        }
+    }
+    n2 = block_sum(red, tid, n2);
+    S2 = block_sum(red, tid, S2);
+    long long peak = 0;
+    const int used = (int)(((long long)len + kLdTile - 1) / kLdTile);   // (tiles past the length hold 0 anyway)
+    for (int t = tid; t < used; t += 256) peak = max(peak, (long long)peaks[q.tile0 + t]);
+    red[tid] = peak;
+    __syncthreads();
+    if (tid != 0) return;
+    for (int t = 1; t < 256; t++) peak = max(peak, red[t]);
+    double g = 1.0;
+    if (n2 > 0) {   // one correctly rounded fp64 operation per step, as wave_codec.loudness_gain: no product feeds a sum
+        g = sqrt(q.gain_k * (double)n2 / (double)S2);
+        g = fmin(g, kLdPeakCeiling / (double)peak);
+    }
+    long long* row = stats + 4LL * q.req;
+    row[0] = n2; row[1] = S2; row[2] = peak; row[3] = __double_as_longlong(g);
+}
+
+__global__ __launch_bounds__(256) void wave_gain_kernel(const LdReq* __restrict__ reqs, int nf, short* __restrict__ pcm,
+                                                        const int* __restrict__ len_dev, const long long* __restrict__ stats) {
+    const int f = last_at_or_before<&LdReq::tile0>(reqs, nf, (int)blockIdx.x);
+    const LdReq q = reqs[f];
+    const long long* row = stats + 4LL * q.req;
+    if (row[0] == 0) return;                                            // nothing passed the gates: the request stays as it is
+    const double g = __longlong_as_double(row[3]);
+    const int len = ld_len(len_dev, q);
+    const long long j0 = (long long)(blockIdx.x - q.tile0) * kLdTile;
+    short* x = pcm + q.in_off;
+    for (int grp = threadIdx.x; grp < kLdTile / 8; grp += 256) {
+        const long long j = j0 + 8 * grp;
+        if (j >= len) break;
+        if (j + 8 <= len && (reinterpret_cast<uintptr_t>(x + j) & 15) == 0) {
+            const int4 in = *reinterpret_cast<const int4*>(x + j);
+            const int w8[4] = {in.x, in.y, in.z, in.w};
+            int o[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int lo = (int)fmax(fmin(rint((double)(short)(w8[e] & 0xffff) * g), 32767.0), -32768.0);
+                const int hi = (int)fmax(fmin(rint((double)(w8[e] >> 16) * g), 32767.0), -32768.0);
+                o[e] = (lo & 0xffff) | (hi << 16);
+            }
+            *reinterpret_cast<int4*>(x + j) = make_int4(o[0], o[1], o[2], o[3]);
+        } else {
+            for (int e = 0; e < 8 && j + e < len; e++) x[j + e] = (short)(int)fmax(fmin(rint((double)x[j + e] * g), 32767.0), -32768.0);
+        }
+    }
+}
+
+struct LdWorkspace {
+    LdReq* reqs = nullptr; size_t cap_reqs = 0;
+    long long* sub = nullptr; size_t cap_sub = 0;
+    int* peaks = nullptr; size_t cap_peaks = 0;
+};
+
+int f5hip_wave_loudness_tile(void) { return kLdTile; }
+
+int f5hip_wave_loudness(int32_t n, int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, const double* gain_k,
+                        int64_t* stats_dev, void* stream) {
+    if (n < 1 || !pcm_dev || !in_off || !max_len || !gain_k || !stats_dev) return fail(-1, "wave_loudness: bad argument");
+    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 1) || (reinterpret_cast<uintptr_t>(len_dev) & 3) || (reinterpret_cast<uintptr_t>(stats_dev) & 7))
+        return fail(-1, "wave_loudness: the samples must be 2-byte aligned, the lengths 4-byte and the stats 8-byte");
+    std::vector<LdReq> h;
+    long long total = 0, tiles = 0;
+    for (int i = 0; i < n; i++) {
+        if (max_len[i] < 0) return fail(-1, "wave_loudness: request %d has a negative length bound (%d)", i, max_len[i]);
+        if (in_off[i] < 0) return fail(-1, "wave_loudness: request %d has a negative offset", i);
+        if (!std::isfinite(gain_k[i])) return fail(-1, "wave_loudness: the gain constant of request %d is not finite", i);
+        total += max_len[i];
+        if (total > 2147483647LL) return fail(-1, "wave_loudness: the call exceeds 2^31 - 1 samples");
+        if (!(gain_k[i] > 0.0)) continue;                               // <= 0: the request is left alone
+        const long long t = std::max<long long>(((long long)max_len[i] + kLdTile - 1) / kLdTile, 1);   // (an empty request keeps one block)
+        h.push_back(LdReq{in_off[i], gain_k[i], max_len[i], i, (int)tiles, (int)t});
+        tiles += t;
+    }
+    if (h.empty()) return 0;
+    LdWorkspace* const wsp = device_workspace<LdWorkspace>("wave_loudness");
+    if (!wsp) return -6;
+    LdWorkspace& ws = *wsp;
+    CK(dev_reserve(&ws.reqs, &ws.cap_reqs, h.size(), "wave_loudness requests"));
+    CK(dev_reserve(&ws.sub, &ws.cap_sub, (size_t)(2 * tiles), "wave_loudness sub-block sums"));
+    CK(dev_reserve(&ws.peaks, &ws.cap_peaks, (size_t)tiles, "wave_loudness peaks"));
+    hipStream_t st = (hipStream_t)stream;
+    if (upload_sync(st, ws.reqs, h) != hipSuccess) return fail(-6, "wave_loudness metadata upload");
+    const int nf = (int)h.size();
+    hipLaunchKernelGGL(wave_kweight_kernel, dim3((unsigned)tiles), dim3(kLdThreads), 0, st, ws.reqs, nf, (const short*)pcm_dev, (const int*)len_dev, ws.sub,
+                       ws.peaks);
+    CKL("wave_kweight");
+    hipLaunchKernelGGL(wave_gate_kernel, dim3((unsigned)nf), dim3(256), 0, st, ws.reqs, (const int*)len_dev, ws.sub, ws.peaks, (long long*)stats_dev);
+    CKL("wave_gate");
+    hipLaunchKernelGGL(wave_gain_kernel, dim3((unsigned)tiles), dim3(256), 0, st, ws.reqs, nf, (short*)pcm_dev, (const int*)len_dev,
+                       (const long long*)stats_dev);
+    CKL("wave_gain");
+    g_counters[CNT_WAVE_LOUDNESS_LAUNCHES] += 3;
+    g_counters[CNT_WAVE_LOUDNESS_REQUESTS] += nf;
     return 0;
 }

@@ -36,6 +36,8 @@ from .wave_codec import (ALL_ENCODINGS, FLAC_BLOCK, FLAC_ENCODINGS, FLAC_HEADER_
                          OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, StreamFlacEncoder, StreamResampler, decode_flac, decode_g711, deliver_pcm16,
                          delivery_format, encode_flac, encode_g711, flac_crc8, flac_crc16, flac_stream_header, load_wav, quantise_pcm16,
                          rate_pair, resample_pcm16, resample_sinc_hann, resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
+from .wave_codec import (LOUDNESS_GATE_ABS, LOUDNESS_PEAK_CEILING, LOUDNESS_RANGE, LOUDNESS_TAPS, check_loudness, loudness_gain,  # noqa: F401
+                         loudness_gain_constant, loudness_lufs, loudness_taps, measure_loudness, normalise_loudness_pcm16)
 from .wave_codec import _device_taps, _tap_tables  # noqa: F401  (the two caches: used below, and read as infer._X by the tests that bound them)
 
 # ----------------------------------------- F/infer/utils_infer.py:40-53
@@ -561,18 +563,26 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 
 # per-request options of `infer_requests` (the fourth element of a request) and of the serving routes
 _PLAIN = (target_sample_rate, "pcm16")   # the delivery format of a request that sets neither `sample_rate` nor `encoding`
-REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "remove_silence", "sample_rate", "encoding")
+REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "remove_silence", "sample_rate", "encoding",
+                   "loudness")
 WHOLE_WAVE = ("remove_silence, sample_rate and encoding need the request's whole wave: they are not available for a list of chunk texts (a streamed "
               "request, whose owner applies the delivery format piece by piece: StreamResampler, encode_g711) or with join=False")
+WHOLE_WAVE_LOUDNESS = ("loudness is measured on the request's whole wave: it is not available for a list of chunk texts, on a streaming path or "
+                       "with join=False")
 
 
 def needs_whole_wave(opts, streamed=False) -> bool:
     """Whether a request's options apply to its joined wave, so that it cannot be handed out chunk by chunk (`WHOLE_WAVE`): `remove_silence`,
-    and a delivery format (`sample_rate`, `encoding`) other than 24 kHz "pcm16".  `streamed`: the format does not count -- a stream's owner
+    `loudness`, and a delivery format (`sample_rate`, `encoding`) other than 24 kHz "pcm16".  `streamed`: the format does not count -- a stream's owner
     (`serve.TTSManager._stream`) takes it off the request and applies it to the pieces itself."""
-    if opts.get("remove_silence"):
+    if opts.get("remove_silence") or opts.get("loudness") is not None:
         return True
     return not streamed and delivery_format(opts.get("sample_rate"), opts.get("encoding")) != _PLAIN
+
+
+def whole_wave_message(opts) -> str:
+    """The refusal of a request that `needs_whole_wave` where it cannot have it: `WHOLE_WAVE_LOUDNESS` when `loudness` is the reason."""
+    return WHOLE_WAVE_LOUDNESS if opts.get("loudness") is not None and not opts.get("remove_silence") else WHOLE_WAVE
 
 
 def plan_request(request, defaults, *, target_rms, fix_duration, device, tokenizer):
@@ -588,8 +598,10 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
     unknown = set(opts) - set(REQUEST_OPTIONS) - {"generator"}
     if unknown:
         raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
+    if opts.get("loudness") is not None:
+        opts["loudness"] = check_loudness(opts["loudness"])
     if needs_whole_wave(opts) and isinstance(request_text(request), (list, tuple)):
-        raise ValueError(WHOLE_WAVE)
+        raise ValueError(whole_wave_message(opts))
     # one (voice, units) part per segment; a plain request is its own single segment
     segments = script.segments if script is not None else [tuple(request[:3])]
     parts = [_plan_request(seg[0], seg[1], seg[2], target_rms, seg[3] if len(seg) > 3 and seg[3] is not None else opts["speed"], fix_duration,
@@ -643,7 +655,9 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     list of chunk texts.  `sample_rate` (one of OUTPUT_SAMPLE_RATES) and `encoding` ("pcm16", "mulaw", "alaw", "flac"), per request: the delivery
     format, a pure function of the request's 24 kHz int16 PCM (`deliver_pcm16`: after silence removal, `resample_pcm16`, then `encode_g711`
     or `encode_flac`); such a request's wave is int16 at that rate, uint8 code bytes or the uint8 bytes of a FLAC stream, its triple names that rate, and like `remove_silence` it needs the whole
-    wave.  A `ScriptRequest` (a multi-voice script: one segment per piece, each with its own voice) is accepted in place of a tuple: its
+    wave.  `loudness` (LUFS, -40 .. -5, per request): the programme loudness (ITU-R BS.1770-4) the request's 24 kHz int16 PCM is moved to
+    after silence removal and before the delivery format (`normalise_loudness_pcm16`: the sample peak stays at or below -1 dBFS); such a
+    request's wave is int16 PCM and it needs the whole wave.  A `ScriptRequest` (a multi-voice script: one segment per piece, each with its own voice) is accepted in place of a tuple: its
     segments' units ride in the same sampler call, one prompt per unit, and the same vocoder call, one group per segment; its triple is
     (`join_segments` of its segments' chunk waves, rate, [spectrogram per segment]), with `join=False` the chunk waves and spectrograms per
     segment, and its whole-wave options apply to the joined script.  `finish` = dict(device_backend=..., want=...): what the serving path asks for -- the list of `finish_requests`
@@ -686,30 +700,31 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     per_plan = np.cumsum([0] + [len(plan.parts) for plan in plans])   # a plan's groups: [per_plan[i], per_plan[i + 1])
     silence = [bool(plan.opts.get("remove_silence")) for plan in plans]
     formats = [delivery_format(plan.opts.get("sample_rate"), plan.opts.get("encoding")) for plan in plans]
+    loud = [plan.opts.get("loudness") for plan in plans]
     if finish is not None:
         backend = bool(finish.get("device_backend"))
         got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms, on_device=backend, want_specs=False)
         chunk_waves = [request_chunk_waves(plan, got[per_plan[i]:per_plan[i + 1]]) for i, plan in enumerate(plans)]
         return finish_requests(chunk_waves, [request_text(req) for req in requests], cross_fade_duration, silence, sample_rate=[f[0] for f in formats],
-                               encoding=[f[1] for f in formats], **finish)
+                               encoding=[f[1] for f in formats], loudness=loud, **finish)
     whole = [needs_whole_wave(plan.opts) for plan in plans]
     if any(whole) and not join:
-        raise ValueError(WHOLE_WAVE)
+        raise ValueError(whole_wave_message(next(plan.opts for plan, w in zip(plans, whole) if w)))
     out = []
     got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms)
-    for i, (plan, needs, flag, fmt) in enumerate(zip(plans, whole, silence, formats)):
+    for i, (plan, needs, flag, fmt, lufs) in enumerate(zip(plans, whole, silence, formats, loud)):
         mine = got[per_plan[i]:per_plan[i + 1]]
         if plan.script is not None:   # (wave, rate, [spectrogram per segment]) like `infer_multi_voice`; join=False: per-segment lists
             seg_specs = [np.concatenate(specs, axis=1) for _, specs in mine]
             if needs or join:
-                wave, = finish_requests([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1])
+                wave, = finish_requests([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1], loudness=lufs)
                 out.append((wave, fmt[0], seg_specs))
             else:
                 out.append(([waves for waves, _ in mine], target_sample_rate, [specs for _, specs in mine]))
             continue
         (waves, specs), = mine
         if needs:
-            wave, = finish_requests([waves], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1])
+            wave, = finish_requests([waves], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1], loudness=lufs)
             out.append((wave, fmt[0], np.concatenate(specs, axis=1)))
         elif join:
             out.append((cross_fade_concat(waves, cross_fade_duration), target_sample_rate, np.concatenate(specs, axis=1)))
@@ -728,7 +743,8 @@ def request_wave(gen_text, waves, cross_fade_duration=cross_fade_duration):
 
 # What `finish_requests` and `_chunk_waves` did since the last `backend_stats.clear()`: requests finished on the device / on the host,
 # `ops.wave_finish` calls, `ops.wave_encode` calls and the requests they encoded (`encode_calls`, `encode_requests`), and device-to-host copies
-# (chunk waves, spectrograms, PCM, encoded samples, lengths); `flac_bytes` is the size of the FLAC stream downloads
+# (chunk waves, spectrograms, PCM, encoded samples, lengths); `flac_bytes` is the size of the FLAC stream downloads; `loudness_calls` /
+# `loudness_requests`: `ops.wave_loudness` calls and the requests they normalised
 backend_stats: collections.Counter = collections.Counter()
 
 
@@ -748,7 +764,7 @@ def _per_request(value, n, what):
 
 
 def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cross_fade_duration, remove_silence=None, device_backend=False,
-                    want="float", sample_rate=None, encoding=None):
+                    want="float", sample_rate=None, encoding=None, loudness=None):
     """From the chunk waves of several requests (rms restored; numpy, or tensors as `_chunk_waves(on_device=True)` leaves them) to what each
     request gets.  A request whose text is a list of chunk texts (a streamed request's head or tail) gets its chunk waves as they are, like
     `request_wave`; a script's (`SegmentedWaves`: one list of chunk waves per segment) as one list per segment.  Any other request gets its
@@ -774,7 +790,13 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     requests of a batch take ONE `ops.wave_flac` call per distinct rate behind `wave_finish` / `wave_encode` on the same stream
     (`backend_stats["flac_calls"]`, `["flac_requests"]`), and two copies come back per rate: the streams' lengths, then the streams, joined
     on the device, in one download of exactly their bytes (`["flac_bytes"]`); on the host, or with a model without the device back-end,
-    `encode_flac` makes the same bytes.  Every `wave_encode` / `wave_flac` call of the batch is queued before the first of these copies."""
+    `encode_flac` makes the same bytes.  Every `wave_encode` / `wave_flac` call of the batch is queued before the first of these copies.
+
+    `loudness`: one target in LUFS (`check_loudness`) or one per request, None for a request that keeps its level.  Such a request's int16
+    PCM (quantised whatever `want` says, after silence removal) goes through `normalise_loudness_pcm16` before the delivery format.  With
+    `device_backend` the flagged requests of the batch take ONE `ops.wave_loudness` call directly behind `wave_finish` on the same stream,
+    in place and before any `wave_encode` / `wave_flac` call is queued, with the lengths still on the device: no copy comes back for it
+    (`backend_stats["loudness_calls"]`, `["loudness_requests"]`), and a batch without a flagged request makes no call."""
     if want not in ("float", "pcm16"):
         raise ValueError(f'want must be "float" or "pcm16" (got {want!r})')
     if device_backend and want != "pcm16":
@@ -784,13 +806,15 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     if len(gen_texts) != n or len(flags) != n:
         raise ValueError("finish_requests: one text and one remove_silence flag per request")
     formats = [delivery_format(r, e) for r, e in zip(_per_request(sample_rate, n, "sample_rate"), _per_request(encoding, n, "encoding"))]
+    loud = [check_loudness(v) for v in _per_request(loudness, n, "loudness")]
     fade = int(cross_fade_duration * target_sample_rate) if cross_fade_duration > 0 else 0
     out, on_device = [None] * n, []
     for i, (waves, text) in enumerate(zip(chunk_waves_per_request, gen_texts)):
         script = isinstance(waves, SegmentedWaves)
         if isinstance(text, (list, tuple)):
-            if needs_whole_wave(dict(remove_silence=flags[i], sample_rate=formats[i][0], encoding=formats[i][1])):
-                raise ValueError(WHOLE_WAVE)
+            whole = dict(remove_silence=flags[i], sample_rate=formats[i][0], encoding=formats[i][1], loudness=loud[i])
+            if needs_whole_wave(whole):
+                raise ValueError(whole_wave_message(whole))
             out[i] = [[_host_chunk(w) for w in seg] for seg in waves] if script else [_host_chunk(w) for w in waves]
         elif script and device_backend and _script_on_device(waves, fade):
             on_device.append(i)
@@ -799,13 +823,13 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
             on_device.append(i)
             continue
         else:
-            out[i] = _finish_on_host(waves, text, cross_fade_duration, flags[i], formats[i], want)
+            out[i] = _finish_on_host(waves, text, cross_fade_duration, flags[i], formats[i], want, loud[i])
         backend_stats["host_requests"] += 1
     if on_device:
         # the plain requests first: their PCM is then one prefix of the packed buffer, and what comes down of it holds no other request's
         on_device.sort(key=lambda i: formats[i] != _PLAIN)
         done = _finish_on_device([_device_request(chunk_waves_per_request[i]) for i in on_device], fade, [flags[i] for i in on_device],
-                                 [formats[i] for i in on_device])
+                                 [formats[i] for i in on_device], [loud[i] for i in on_device])
         for i, wave in zip(on_device, done):
             out[i] = wave
     return out
@@ -835,25 +859,29 @@ def _device_request(waves):
     return chunks, fades
 
 
-def _finish_on_host(waves, text, cross_fade_duration, flag, fmt, want):
-    """`finish_requests` for one request on the host: join, quantisation, silence removal and the delivery format in numpy."""
+def _finish_on_host(waves, text, cross_fade_duration, flag, fmt, want, loudness=None):
+    """`finish_requests` for one request on the host: join, quantisation, silence removal, the loudness target and the delivery format in
+    numpy."""
     if isinstance(waves, SegmentedWaves):
         wave = join_segments([[_host_chunk(w) for w in seg] for seg in waves], cross_fade_duration, waves.gap_samples)
     else:
         wave = request_wave(text, [_host_chunk(w) for w in waves], cross_fade_duration)
     if flag:
         wave = remove_silence_pcm(quantise_pcm16(wave), target_sample_rate)
-    elif want == "pcm16" or fmt != _PLAIN:
+    elif want == "pcm16" or fmt != _PLAIN or loudness is not None:
         wave = quantise_pcm16(wave)
+    if loudness is not None:
+        wave = normalise_loudness_pcm16(wave, loudness)
     return wave if fmt == _PLAIN else deliver_pcm16(wave, *fmt)
 
 
-def _finish_on_device(requests, fade, silence, formats):
+def _finish_on_device(requests, fade, silence, formats, loudness=None):
     """`finish_requests` for the requests the device back-end takes: `requests` = (chunk waves (device tensors), fades: `_device_request`), the
     plain-format ones first; `silence`, `formats` per request.  ONE `ops.wave_finish` call -- `ops.wave_finish_joins` when a script is among
     them -- then one `ops.wave_encode` call per distinct delivery format behind it on the same stream, and for the "flac" requests one
-    `ops.wave_flac` call per distinct rate (behind a `wave_encode(..., "pcm16")` call where the rate is not 24 kHz).  Returns one result per
-    request."""
+    `ops.wave_flac` call per distinct rate (behind a `wave_encode(..., "pcm16")` call where the rate is not 24 kHz).  `loudness`: a target per
+    request or None; when any is set, ONE `ops.wave_loudness` call normalises those requests in place directly behind `wave_finish`, before
+    anything else is queued.  Returns one result per request."""
     from . import ops
     out = [None] * len(requests)
     plain = sum(fmt == _PLAIN for fmt in formats)
@@ -865,6 +893,10 @@ def _finish_on_device(requests, fade, silence, formats):
         pcm, lengths, offsets = ops.wave_finish(chunks, counts, fade, silence, target_sample_rate)
     else:
         pcm, lengths, offsets = ops.wave_finish_joins(chunks, counts, fade, [x for f in fades for x in f], silence, target_sample_rate)
+    if loudness is not None and any(v is not None for v in loudness):   # in place, lengths still on the device: nothing comes back for it
+        ops.wave_loudness(pcm, offsets, joined, lengths, [None if v is None else loudness_gain_constant(v) for v in loudness])
+        backend_stats["loudness_calls"] += 1
+        backend_stats["loudness_requests"] += sum(v is not None for v in loudness)
     if plain:
         if any(silence[:plain]):
             kept = lengths[:plain].cpu().tolist()
@@ -945,6 +977,7 @@ class SpanTicket:
         self.parts = parts if parts is not None else [(voice, units)]   # [(voice, its units)]: one per segment of a script
         self.script = script
         self.sample_rate, self.encoding = delivery_format(opts.get("sample_rate"), opts.get("encoding"))
+        self.loudness = check_loudness(opts.get("loudness"))
         self.in_flight = self.cancelled = self.done = False
         self.result = None
 
@@ -975,7 +1008,7 @@ class SpanScheduler:
     profiles/r07_admission_bench.txt) that boundary cost is 3.3 ms with 8 units in flight, 2.3 % of an 8-step span (4.6 % of a 4-step one),
     and 8 is the shortest span whose median time to result on the trace was not above `MicroBatcher`'s.
 
-    Finished requests leave through `finish_requests` (a request's `remove_silence`, `sample_rate` and `encoding` options included); with `device_backend=True` their chunk
+    Finished requests leave through `finish_requests` (a request's `remove_silence`, `loudness`, `sample_rate` and `encoding` options included); with `device_backend=True` their chunk
     waves stay on the device and their results are int16 PCM from one `ops.wave_finish` call per boundary."""
 
     def __init__(self, model_obj, vocoder, span_steps=span_steps, max_frames=None, max_requests=None, mel_spec_type=mel_spec_type, target_rms=target_rms,
@@ -1044,7 +1077,8 @@ class SpanScheduler:
         chunk_waves = [request_chunk_waves(t, got[first[i]:first[i + 1]]) for i, t in enumerate(tickets)]
         results = finish_requests(chunk_waves, [request_text(t.request) for t in tickets], self.cross_fade_duration, [t.remove_silence for t in tickets],
                                   device_backend=self.device_backend, want="pcm16" if self.device_backend else "float",
-                                  sample_rate=[t.sample_rate for t in tickets], encoding=[t.encoding for t in tickets])
+                                  sample_rate=[t.sample_rate for t in tickets], encoding=[t.encoding for t in tickets],
+                                  loudness=[t.loudness for t in tickets])
         for t, result in zip(tickets, results):
             t.result, t.done, t.in_flight = result, True, False
 

@@ -545,3 +545,47 @@ def wave_flac(pcm, in_off, max_len, len_dev, sample_rate):
         _lib.check(_lib.lib().f5hip_wave_flac(n, C.c_void_p(base), _p(rel), _p(ml), _p(len_dev), rate, _p(data), _p(out_off), _p(out_len),
                                               _lib.current_stream_ptr()), "f5hip_wave_flac")
     return data, out_len, out_off.tolist()
+
+
+def wave_loudness_tile():
+    """Samples one block of `wave_loudness`'s first launch owns (two 100 ms sub-blocks)."""
+    return int(_lib.lib().f5hip_wave_loudness_tile())
+
+
+def wave_loudness(pcm, in_off, max_len, len_dev, gain_k):
+    """The loudness target of several finished requests in ONE library call and three launches (include/f5hip.h f5hip_wave_loudness): their
+    24 kHz int16 PCM on the device, normalised IN PLACE.  `pcm`: the int16 device tensor that holds every request (`wave_finish`'s packed
+    PCM; request i starts at sample in_off[i]); `max_len`, `len_dev` as in `wave_encode`; `gain_k` [n]: `wave_codec.loudness_gain_constant`
+    of each request's target, 0 (or None) for a request that is left alone.  A call without a flagged request launches nothing.  Returns
+    stats, int64 device [n, 4]: n2, S2, peak and the bits of the gain g of each flagged request (zeros for the others) --
+    `wave_codec.measure_loudness` and `loudness_gain` of its samples, and afterwards its samples are `normalise_loudness_pcm16`'s, bit for
+    bit."""
+    io = np.ascontiguousarray(np.asarray(in_off, dtype=np.int64))
+    ml = np.ascontiguousarray(np.asarray(max_len, dtype=np.int32))
+    gk = np.ascontiguousarray(np.asarray([0.0 if k is None else k for k in gain_k], dtype=np.float64))
+    n = len(ml)
+    if n < 1 or len(io) != n or len(gk) != n:
+        raise _lib.F5HipError("wave_loudness: one offset, one length bound and one gain constant per request")
+    if not (torch.is_tensor(pcm) and pcm.dtype == torch.int16 and pcm.is_cuda and pcm.dim() == 1 and pcm.is_contiguous()):
+        raise _lib.F5HipError("wave_loudness: pcm must be a contiguous 1-D int16 device tensor")
+    if len_dev is not None and not (torch.is_tensor(len_dev) and len_dev.dtype == torch.int32 and len_dev.is_cuda and len_dev.numel() == n
+                                    and len_dev.device == pcm.device):
+        raise _lib.F5HipError("wave_loudness: len_dev must be an int32 tensor with one value per request on the pcm's device")
+    if not np.isfinite(gk).all():
+        raise _lib.F5HipError("wave_loudness: a gain constant is not finite")
+    if len_dev is not None:
+        len_dev = len_dev.contiguous()
+    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
+        try:
+            return torch_ops.ops().wave_loudness(pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(gk))
+        except RuntimeError as e:   # c10::Error from the operator's checks or the library
+            raise _lib.F5HipError(str(e)) from e
+    for i in range(n):
+        if ml[i] < 0 or io[i] < 0 or int(io[i]) + int(ml[i]) > pcm.numel():
+            raise _lib.F5HipError(f"wave_loudness: request {i} covers samples [{io[i]}, {int(io[i]) + int(ml[i])}) of a tensor of {pcm.numel()}")
+    with torch.cuda.device(pcm.device):
+        stats = torch.zeros(n, 4, device=pcm.device, dtype=torch.int64)
+        if (gk > 0).any() and pcm.numel():
+            _lib.check(_lib.lib().f5hip_wave_loudness(n, _p(pcm), _p(io), _p(ml), _p(len_dev), _p(gk), _p(stats), _lib.current_stream_ptr()),
+                       "f5hip_wave_loudness")
+    return stats

@@ -59,7 +59,7 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
     is the model's solver: `nfe_step`'s upper limit follows the request's own `ode_method` when it sets one, else the model's.
     `remove_silence` a bool (False is dropped like None: the request is then what it is without the option).  `sample_rate` an integer in
     `infer.OUTPUT_SAMPLE_RATES`, `encoding` one of `infer.OUTPUT_ENCODINGS` or "flac" (`infer.FLAC_ENCODINGS`); 24000 and "pcm16", what a
-    request gets anyway, are dropped too."""
+    request gets anyway, are dropped too.  `loudness` a finite number of LUFS within `infer.LOUDNESS_RANGE` (`infer.check_loudness`), not a bool."""
     out = {}
     own = options.get("ode_method") if "ode_method" in allowed else None
     if own is not None:
@@ -84,6 +84,8 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
             v = infer.delivery_format(**{k: v})[i]      # ValueError: "<name> must be one of ..."
             if v == infer.delivery_format()[i]:         # 24000 / "pcm16": what a request gets anyway
                 continue
+        elif k == "loudness":
+            v = infer.check_loudness(v)                 # ValueError: "loudness must be ..."
         elif k in ("nfe_step", "seed"):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"{k} must be an integer (got {v!r})")
@@ -114,6 +116,15 @@ DEVICE_FRONTEND_DEFAULT = True
 # more than the run's own spread (tools/wave_backend_bench.py, profiles/wave_backend_bench.txt; DESIGN "Waveform back-end")
 DEVICE_BACKEND_DEFAULT = False
 STREAM_REMOVE_SILENCE = "remove_silence needs the request's whole wave: it is not available on a streaming path"
+STREAM_LOUDNESS = "loudness is measured on the request's whole wave: it is not available on a streaming path"
+
+
+def stream_refusal(opts):
+    """The message a streaming path refuses `opts` with, or None: an option that needs the whole wave (`infer.needs_whole_wave`; the
+    delivery format does not count, a stream applies it piece by piece)."""
+    if not infer.needs_whole_wave(opts, streamed=True):
+        return None
+    return STREAM_REMOVE_SILENCE if opts.get("remove_silence") else STREAM_LOUDNESS
 
 
 @dataclass
@@ -575,8 +586,8 @@ class TTSManager:
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = self.request_options(**options)
-        if stream and infer.needs_whole_wave(opts, streamed=True):
-            raise ValueError(STREAM_REMOVE_SILENCE)
+        if stream and stream_refusal(opts):
+            raise ValueError(stream_refusal(opts))
         voice, ref_text = resolve_voice()
         if stream:
             chunks = infer.request_chunks(ref_text, voice.seconds, text)
@@ -611,7 +622,9 @@ class TTSManager:
         `infer.OUTPUT_SAMPLE_RATES`) and `encoding` ("pcm16", "mulaw", "alaw", "flac"): the delivery format, `infer.deliver_pcm16` of the
         request's 24 kHz int16 PCM -- int16 at that rate, uint8 G.711 code bytes, or with "flac" a uint8 array that holds the lossless FLAC
         stream of the samples at that rate (`infer.encode_flac`) -- computed on the device with `device_backend`, the same bytes either way;
-        24000 and "pcm16" (or None) change nothing."""
+        24000 and "pcm16" (or None) change nothing.  `loudness` (LUFS, -40 .. -5): the result is int16 PCM moved to that programme
+        loudness (ITU-R BS.1770-4; `infer.normalise_loudness_pcm16`, sample peak at most -1 dBFS) after silence removal and before the
+        delivery format -- in the batch's one `ops.wave_loudness` call with `device_backend`, the same bytes either way."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         return self.model(text, ref_audio_path=ref_audio_path, ref_text=ref_text, **options)   # (`_call`, which checks the options)
@@ -630,7 +643,7 @@ class TTSManager:
         with the same options byte for byte.  With "flac" the pieces are uint8: the 42-byte stream header with the totals unknown (zero)
         first -- it comes from the first `next()` once the first chunk is synthesized, so a failing first chunk raises there before any
         byte --, then the frames each piece completes (`infer.StreamFlacEncoder`), then the short last frame; behind the header they equal
-        `synthesize`'s stream, and both decode to the same samples.  `remove_silence` needs the whole wave: ValueError."""
+        `synthesize`'s stream, and both decode to the same samples.  `remove_silence` and `loudness` need the whole wave: ValueError."""
         return self._serve(lambda: self._voice(ref_audio_path, ref_text), text, options, stream=True)
 
     def _stream(self, voice, ref_text, head, tail, opts=None):
@@ -763,7 +776,7 @@ class TTSManager:
         without a known tag is spoken by "main"), `voices` = {tag: dict(ref_audio_path=..., ref_text=...) | dict(ref_audio=<WAV bytes or
         (wave, sr)>, ref_text=..., clip_short=True)}, each with an optional `speed`; `gap`: seconds of silence between pieces (0 to 5).
         `options`: `infer.REQUEST_OPTIONS` as in `synthesize`, for the whole script -- one `seed` for all its chunks in order, and
-        `remove_silence` / `sample_rate` / `encoding` on the joined wave.  The script is one item of its batch (`infer.ScriptRequest`): its
+        `remove_silence` / `loudness` / `sample_rate` / `encoding` on the joined wave (so two voices of different prompt levels come out at one programme loudness).  The script is one item of its batch (`infer.ScriptRequest`): its
         pieces are sampled and vocoded with everything else in the batch, cross-faded inside a piece and concatenated between pieces
         (`infer.join_segments`) -- with `device_backend` in the batch's single `ops.wave_finish_joins` call, as int16 PCM."""
         return self._script(text, voices, gap, options)
@@ -778,8 +791,8 @@ class TTSManager:
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = self.request_options(**options)
-        if stream and infer.needs_whole_wave(opts, streamed=True):
-            raise ValueError(STREAM_REMOVE_SILENCE)
+        if stream and stream_refusal(opts):
+            raise ValueError(stream_refusal(opts))
         segments = self._script_segments(text, voices, gap)
         if not stream:
             req = infer.ScriptRequest(segments, opts, gap)
@@ -807,17 +820,19 @@ class TTSManager:
         return self._stream_requests(head, infer.ScriptRequest(rest, opts, gap) if rest else None, fmt, tail_pieces)
 
     def edit(self, audio, target_text, parts_to_edit, fix_duration=None, *, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
-             seed=None, ode_method=None, sample_rate=None, encoding=None):
+             seed=None, ode_method=None, sample_rate=None, encoding=None, loudness=None):
         """Speech editing (`infer.speech_edit`, F/infer/speech_edit.py): regenerate `parts_to_edit` of the recording `audio` (a path, WAV
         bytes or a (tensor, sr) pair) so that it speaks `target_text`, with this manager's sampler settings unless the call sets its own
         (`seed`: the edit's noise from its own generator; `ode_method`: the edit's solver, handed on only when set).  The host preparation runs outside the device lock, the sampler and vocoder
         under it (not through the micro-batcher); with a `ShardedSampler` on rank 0's own model.  Returns the wave (float32, 24 kHz) -- with
-        `sample_rate` / `encoding`, `infer.deliver_pcm16` of its int16 PCM (host functions)."""
+        `sample_rate` / `encoding`, `infer.deliver_pcm16` of its int16 PCM (host functions); with `loudness` (LUFS), that PCM first goes through
+        `infer.normalise_loudness_pcm16` and the result is int16."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = dict(self.opts, **self.request_options(EDIT_OPTIONS, nfe_step=nfe_step, cfg_strength=cfg_strength,
                                                       sway_sampling_coef=sway_sampling_coef, seed=seed, ode_method=ode_method))
         fmt = self.request_options(("sample_rate", "encoding"), sample_rate=sample_rate, encoding=encoding)
+        loudness = self.request_options(("loudness",), loudness=loudness).get("loudness")
         model_obj = getattr(self.model_obj, "local", self.model_obj)
         # host work (read, mono mix, resample, plan, tokens) and every rejection happen before the device lock is taken
         prep = infer.prepare_edit(audio, target_text, parts_to_edit, fix_duration, mel_spec_type=self.mel_spec_type)
@@ -829,7 +844,10 @@ class TTSManager:
                                                     nfe_step=opts["nfe_step"], cfg_strength=opts["cfg_strength"],
                                                     sway_sampling_coef=opts["sway_sampling_coef"], **extra)
         wave = np.asarray(wave, dtype=np.float32)
-        return infer.deliver_pcm16(infer.quantise_pcm16(wave), fmt.get("sample_rate"), fmt.get("encoding")) if fmt else wave
+        if loudness is None and not fmt:
+            return wave
+        pcm = infer.normalise_loudness_pcm16(infer.quantise_pcm16(wave), loudness)       # (None: the PCM as it is)
+        return infer.deliver_pcm16(pcm, fmt.get("sample_rate"), fmt.get("encoding")) if fmt else pcm
 
 
 class HTTPError(Exception):
@@ -914,6 +932,7 @@ def request_models():
         ode_method: str | None = None
         sample_rate: int | None = None               # the delivery format (infer.deliver_pcm16); None = 24 kHz 16-bit PCM in a WAV
         encoding: str | None = None
+        loudness: float | None = None                # programme loudness target in LUFS (infer.normalise_loudness_pcm16); None = the level as synthesized
         response_format: str | None = None
 
     class SpeechFields(SamplerFields):               # what the three speech routes take on top: with SamplerFields, every infer.REQUEST_OPTIONS name
@@ -975,7 +994,10 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     `infer.OUTPUT_SAMPLE_RATES`), `encoding` ("pcm16", "mulaw" or "alaw": G.711, one byte per sample) and `response_format` ("wav", or "pcm"
     for the headerless samples / code bytes as `audio/pcm`); streamed or not, the body's samples are the same bytes.  `encoding: "flac"` is
     its own container: the body is the native FLAC stream of the samples (`infer.encode_flac`, lossless) as `audio/flac` with a `.flac` file
-    name, and `response_format` must be absent (400 with "wav" or "pcm" beside it); streamed, the stream header comes with the totals unknown."""
+    name, and `response_format` must be absent (400 with "wav" or "pcm" beside it); streamed, the stream header comes with the totals unknown.
+    `loudness` (a number of LUFS from -40 to -5, every route): the body's samples are moved to that programme loudness (ITU-R BS.1770-4) with
+    the sample peak at most -1 dBFS, after silence removal and before the delivery format; it is measured on the whole wave, so it is a 400
+    together with `"stream": true` (`STREAM_LOUDNESS`)."""
     from fastapi import APIRouter, FastAPI, HTTPException
     from starlette.responses import StreamingResponse
 
@@ -1013,8 +1035,8 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
         opts = _options(req, infer.REQUEST_OPTIONS)
-        if req.stream and infer.needs_whole_wave(opts, streamed=True):
-            raise HTTPException(status_code=400, detail=STREAM_REMOVE_SILENCE)
+        if req.stream and stream_refusal(opts):
+            raise HTTPException(status_code=400, detail=stream_refusal(opts))
         if not text.strip():
             raise HTTPException(status_code=400, detail="Text to synthesize cannot be empty.")
         return opts
@@ -1120,7 +1142,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     def _run_edit(req):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
-        opts = _options(req, EDIT_OPTIONS + ("sample_rate", "encoding"))
+        opts = _options(req, EDIT_OPTIONS + ("sample_rate", "encoding", "loudness"))
         fmt = _response_format(req, opts)
         try:
             raw = base64.b64decode(req.audio, validate=True)

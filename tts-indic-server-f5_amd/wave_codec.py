@@ -1,6 +1,6 @@
 """Waves in and out of the server, with nothing of the model in it: reading WAV files (`load_wav`), torchaudio's polyphase sinc resampler
 (`rate_pair`, `resample_taps`, `resample_sinc_hann`) with its tap-table caches, the integer resampler of finished PCM (`resample_pcm16`,
-`StreamResampler`), G.711 (`encode_g711`, `decode_g711`), FLAC (`encode_flac`, `decode_flac`, `StreamFlacEncoder`), the delivery format of a request (`delivery_format`, `deliver_pcm16`) and the bytes
+`StreamResampler`), the BS.1770 loudness meter and normaliser (`measure_loudness`, `normalise_loudness_pcm16`), G.711 (`encode_g711`, `decode_g711`), FLAC (`encode_flac`, `decode_flac`, `StreamFlacEncoder`), the delivery format of a request (`delivery_format`, `deliver_pcm16`) and the bytes
 of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
 round; `infer` and `serve` hand every public name on (`infer.load_wav`, `serve.wav_bytes`, ...)."""
 from __future__ import annotations
@@ -369,6 +369,140 @@ def deliver_pcm16(pcm, sample_rate=None, encoding=None) -> np.ndarray:
     if enc in FLAC_ENCODINGS:
         return encode_flac(pcm, rate)
     return pcm if enc == "pcm16" else encode_g711(pcm, enc)
+
+
+# ----------------------------------------- loudness: the mono programme loudness of ITU-R BS.1770-4 on a request's 24 kHz int16 PCM, in integers
+# up to one sqrt, so that the device meter (csrc/wave_out.h wave_kweight_kernel / wave_gate_kernel / wave_gain_kernel) is held to these
+# functions bit for bit: no sum below depends on the order of its terms.
+#   K-weighting  y[j] = sum_k h[k] x[j - k] (zeros in front), h = `loudness_taps()`: the impulse response of the two K-weighting biquads
+#                designed for 24 kHz, LOUDNESS_TAPS = 1024 taps at 2^16, rounded; z[j] = y[j] >> 14 (floor)
+#   sub-blocks   e[s] = sum of z^2 over the 2400 samples (100 ms) of sub-block s; only whole sub-blocks count
+#   blocks       400 ms with 75 % overlap: E[b] = (e[b] + e[b+1] + e[b+2] + e[b+3]) >> 8, ns - 3 of them
+#   gates        absolute E[b] > LOUDNESS_GATE_ABS (-70 LUFS); relative E[b] > floor(S1 / (10 n1)) (-10 LU) over the blocks that pass the
+#                absolute one; n2, S2: count and sum of the blocks that pass both
+#   scale        z is y / 2^14 = 2^2 x 32768 x (K-weighted sample at full scale 1), so a block's mean square is E 2^8 / (9600 2^34)
+# Bit budget: sum |h| = 212 915 < 2^17.7, so |y| < 2^32.7 (exact in fp64 and in int64), |z| < 2^18.7, e < 2400 2^37.4 < 2^48.7,
+# E < 2^42.7, and S below 2^62.5 for any request below 2^31 samples (fewer than 2^19.8 blocks).
+LOUDNESS_TAPS = 1024
+LOUDNESS_TAP_SHIFT, LOUDNESS_Y_SHIFT, LOUDNESS_E_SHIFT = 16, 14, 8
+LOUDNESS_SUBBLOCK = 2400                               # 100 ms
+LOUDNESS_BLOCK = 4 * LOUDNESS_SUBBLOCK                 # 400 ms
+_LOUDNESS_SCALE = float(LOUDNESS_BLOCK) * 2.0 ** 26    # E of a block whose mean square is 1 (full scale): 9600 2^34 / 2^8
+LOUDNESS_GATE_ABS = math.floor(10.0 ** ((-70.0 + 0.691) / 10.0) * _LOUDNESS_SCALE)
+LOUDNESS_PEAK_CEILING = 29203                          # sample-peak ceiling of a normalised wave: -1 dBFS, floor(32767 * 10^(-1/20))
+LOUDNESS_RANGE = (-40.0, -5.0)                         # targets a request may name, LUFS
+_loudness_taps = None
+
+
+def _kweight_biquads(fs):
+    """(b, a) of the K-weighting shelf and high-pass for the rate fs, a[0] = 1: the analytic form libebur128 and pyloudnorm use (at
+    48 kHz the table of BS.1770)."""
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = math.tan(math.pi * f0 / fs)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    shelf = ([(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0],
+             [1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = math.tan(math.pi * f0 / fs)
+    a0 = 1.0 + K / Q + K * K
+    high = ([1.0, -2.0, 1.0], [1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+    return shelf, high
+
+
+def loudness_taps() -> np.ndarray:
+    """The K-weighting filter as LOUDNESS_TAPS integer taps (int64, read-only): h[k] = rint(2^16 k_true[k]), k_true the impulse response of
+    the two biquads of `_kweight_biquads(24000)`, run in fp64.  Computed once.  The taps from index 916 on round to zero."""
+    global _loudness_taps
+    if _loudness_taps is None:
+        x = [1.0] + [0.0] * (LOUDNESS_TAPS - 1)
+        for b, a in _kweight_biquads(float(SAMPLE_RATE)):
+            y, x1, x2, y1, y2 = [], 0.0, 0.0, 0.0, 0.0
+            for v in x:
+                w = b[0] * v + b[1] * x1 + b[2] * x2 - a[1] * y1 - a[2] * y2
+                x2, x1, y2, y1 = x1, v, y1, w
+                y.append(w)
+            x = y
+        taps = np.rint(np.asarray(x, dtype=np.float64) * 2.0 ** LOUDNESS_TAP_SHIFT).astype(np.int64)
+        # the bit budget every later step leans on: |y| <= sum|h| 32768 < 2^33 (exact in fp64), |z| = |y| >> 14 < 2^19
+        assert (int(np.abs(taps).sum()) * 32768) >> LOUDNESS_Y_SHIFT < 1 << 19, int(np.abs(taps).sum())
+        taps.setflags(write=False)
+        _loudness_taps = taps
+    return _loudness_taps
+
+
+def measure_loudness(pcm):
+    """(n2, S2, peak) of 24 kHz int16 PCM by the definition above, Python integers: the count and the sum of the gated 400 ms block
+    energies E, and max |x|.  A wave shorter than 9600 samples has no block: n2 = 0."""
+    pcm = _as_pcm16(pcm)
+    n = len(pcm)
+    peak = int(np.abs(pcm.astype(np.int32)).max()) if n else 0
+    ns = n // LOUDNESS_SUBBLOCK
+    if ns < 4:
+        return 0, 0, peak
+    h = np.trim_zeros(loudness_taps(), "b").astype(np.float64)
+    # every product and every partial sum is an integer below 2^53 in magnitude: the fp64 convolution is exact in any order
+    y = np.convolve(pcm[:ns * LOUDNESS_SUBBLOCK].astype(np.float64), h)[:ns * LOUDNESS_SUBBLOCK].astype(np.int64)
+    z = y >> LOUDNESS_Y_SHIFT
+    e = (z * z).reshape(ns, LOUDNESS_SUBBLOCK).sum(axis=1)
+    E = (e[:-3] + e[1:-2] + e[2:-1] + e[3:]) >> LOUDNESS_E_SHIFT
+    E = E[E > LOUDNESS_GATE_ABS]
+    if not len(E):
+        return 0, 0, peak
+    S1 = sum(int(v) for v in E)
+    E = E[E > S1 // (10 * len(E))]
+    return len(E), sum(int(v) for v in E), peak
+
+
+def loudness_lufs(n2, S2):
+    """The loudness in LUFS of `measure_loudness`' (n2, S2): -0.691 + 10 log10 of the gated blocks' mean square; None when nothing passed
+    the gates."""
+    if not n2:
+        return None
+    return -0.691 + 10.0 * math.log10(S2 * 2.0 ** LOUDNESS_E_SHIFT / (n2 * float(LOUDNESS_BLOCK) * 2.0 ** 34))
+
+
+def check_loudness(target):
+    """A request's `loudness` option: None (absent), or a finite number of LUFS within LOUDNESS_RANGE, returned as float; a bool, any
+    other type and a value outside the range are a ValueError."""
+    if target is None:
+        return None
+    if isinstance(target, (bool, np.bool_)) or not isinstance(target, (int, float, np.integer, np.floating)):
+        raise ValueError(f"loudness must be a number of LUFS (got {target!r})")
+    target = float(target)
+    if not math.isfinite(target) or not LOUDNESS_RANGE[0] <= target <= LOUDNESS_RANGE[1]:
+        raise ValueError(f"loudness must be between {LOUDNESS_RANGE[0]:g} and {LOUDNESS_RANGE[1]:g} LUFS (got {target}).")
+    return target
+
+
+def loudness_gain_constant(target) -> float:
+    """K_T of a target in LUFS: the E of a block at that loudness, 10^((target + 0.691) / 10) 9600 2^26 in fp64 -- what the device call
+    takes per request (`ops.wave_loudness`)."""
+    return 10.0 ** ((float(target) + 0.691) / 10.0) * _LOUDNESS_SCALE
+
+
+def loudness_gain(n2, S2, peak, gain_k) -> float:
+    """The gain that moves (n2, S2, peak) to K_T = `gain_k`: sqrt(K_T n2 / S2), at most LOUDNESS_PEAK_CEILING / peak; 1.0 when nothing
+    passed the gates.  One correctly rounded fp64 operation per step: int -> fp64, *, /, sqrt, /, min."""
+    if not n2:
+        return 1.0
+    return min(math.sqrt(gain_k * float(n2) / float(S2)), float(LOUDNESS_PEAK_CEILING) / float(peak))
+
+
+def normalise_loudness_pcm16(pcm, target) -> np.ndarray:
+    """24 kHz int16 PCM moved to `target` LUFS (`check_loudness`; None returns the input): out = clip(rint(x g)) in fp64, half to even, g =
+    `loudness_gain` of `measure_loudness(pcm)` -- so the peak stays at or below LOUDNESS_PEAK_CEILING unless it was above before and the
+    wave is quieter than the target.  A wave without a gated block (shorter than 400 ms, or silent) comes back unchanged.  What
+    `ops.wave_loudness` equals byte for byte."""
+    pcm, target = _as_pcm16(pcm), check_loudness(target)
+    if target is None:
+        return pcm
+    n2, S2, peak = measure_loudness(pcm)
+    if not n2:
+        return pcm
+    g = loudness_gain(n2, S2, peak, loudness_gain_constant(target))
+    return np.clip(np.rint(pcm.astype(np.float64) * g), -32768, 32767).astype(np.int16)
 
 
 _G711_TAGS = {"mulaw": 7, "alaw": 6}   # WAVE_FORMAT_MULAW, WAVE_FORMAT_ALAW
