@@ -363,6 +363,18 @@ int f5hip_vocos_decode(f5hip_vocos* v, int32_t batch, int32_t frames, const floa
  * Item i's wave equals f5hip_vocos_decode of that item alone, bit for bit. */
 int f5hip_vocos_decode_ragged(f5hip_vocos* v, int32_t n, const int32_t* frames, const float* mel_dev, float* wave_dev,
                               void* stream);
+/* Parity taps: f5hip_vocos_decode_ragged's own launch sequence (same arguments n, frames, mel_dev), stopped behind n_blocks ConvNeXt blocks, with
+ * the valid rows of its workspace copied out packed, item after item without the 128-row padding of the library's row layout:
+ *   n_blocks   0 .. num_layers: stop behind that many blocks (0: embed conv + backbone.norm only); -1: the whole decode
+ *   x_dev      fp32 [sum frames][dim]: the residual stream where the call stopped (for -1 behind the last block, in front of the final norm)
+ *   n_blocks = -1 also fills (they may be null otherwise, and are then left alone)
+ *   y_dev      fp32 [sum frames][n_fft + 2]: the head output, log-magnitude | phase
+ *   fw_dev     fp32 [sum frames][n_fft]: the windowed inverse-FFT frames in front of the overlap-add
+ *   wave_dev   as f5hip_vocos_decode_ragged, and the same bits
+ * n items of equal length give f5hip_vocos_decode's layout.  Refused before any launch: n_blocks outside -1 .. num_layers, a null pointer
+ * among the buffers the call fills, an item of fewer than 2 frames. */
+int f5hip_vocos_decode_taps(f5hip_vocos* v, int32_t n, const int32_t* frames, const float* mel_dev, int32_t n_blocks,
+                            float* x_dev, float* y_dev, float* fw_dev, float* wave_dev, void* stream);
 
 /* ---------------------------------------------------------------- BigVGAN vocoder --------------------- */
 

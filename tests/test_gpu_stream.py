@@ -9,6 +9,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import vocos_ref as R  # noqa: E402
 from oracle import vocos_oracle as V  # noqa: E402
 from tts_indic_server_f5_amd import _lib, infer, serve, synth  # noqa: E402
 
@@ -65,6 +66,10 @@ def test_decode_ragged_vs_oracle(vocos):
         mx = (w.cpu() - ref).abs().max().item()
         print(f"[parity] decode_ragged T={t}: max_err {mx:.3e}")
         assert mx < 1e-4
+    # and by the rule of tests/test_gpu_vocos_stages.py: within 3 x the split-bf16 operand model's own distance from float64
+    (g_max, g_rms), (m_max, m_rms) = R.decode_errors(R.Weights(sd), mels, got, 2)
+    print(f"[parity] decode_ragged: gpu_err max {g_max:.3e} rms {g_rms:.3e}   model_err max {m_max:.3e} rms {m_rms:.3e}")
+    assert g_max <= 3.0 * m_max and g_rms <= 3.0 * m_rms
 
 
 def test_decode_ragged_rejects_bad_frames(vocos):

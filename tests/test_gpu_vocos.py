@@ -7,6 +7,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import vocos_ref as R  # noqa: E402
 from mel_ref import LOG_CLAMP, float64 as _float64  # noqa: E402
 from oracle import vocos_oracle as V  # noqa: E402
 from tts_indic_server_f5_amd import synth  # noqa: E402
@@ -16,6 +17,17 @@ def _report(tag, got, ref):
     d = got.float().cpu() - ref.float().cpu()
     print(f"[parity] {tag}: rms_err {d.pow(2).mean().sqrt():.3e} max_err {d.abs().max():.3e} ref_rms {ref.float().pow(2).mean().sqrt():.3e}")
     return d.abs().max().item(), d.pow(2).mean().sqrt().item()
+
+
+def _within_model(tag, sd, mel, got):
+    """The whole decode against float64 by the rule of tests/test_gpu_vocos_stages.py: max and rms of GPU - float64 within 3 x those of
+    the split-bf16 operand model chained over all stages (tests/vocos_ref.py) on the same mel [b, 100, t].  Measured on an MI355X over the
+    cases of this file: gpu_err / model_err 1.19 .. 1.29 (max) and 1.20 .. 1.30 (rms); the model is 3.8e-7 .. 5.8e-7 max off float64 at
+    the synthetic level, 2.6e-6 with the log-magnitudes raised by ln 5 and 3.2e-5 by ln 100."""
+    (g_max, g_rms), (m_max, m_rms) = R.decode_errors(R.Weights(sd), list(mel), list(got), 2)
+    print(f"[parity] {tag}: gpu_err max {g_max:.3e} rms {g_rms:.3e}   model_err max {m_max:.3e} rms {m_rms:.3e}   "
+          f"gpu_err / model_err {g_max / m_max:.2f} / {g_rms / m_rms:.2f}")
+    assert g_max <= 3.0 * m_max and g_rms <= 3.0 * m_rms
 
 
 @pytest.fixture(scope="module")
@@ -33,6 +45,7 @@ def test_vocos_decode(vocos, b, t):
     assert got.shape == ref.shape == (b, 256 * (t - 1))
     mx, rms = _report(f"vocos b{b} t{t}", got, ref)
     assert mx < 1e-4
+    _within_model(f"vocos b{b} t{t}", synth.vocos_state_dict(), mel, got)
 
 
 def _shifted_vocos_decode(shift):
@@ -48,6 +61,7 @@ def _shifted_vocos_decode(shift):
     ref = _float64(V.vocos_decode, {k: v.double() for k, v in sd.items()}, mel.double())
     got = F5HipVocos(sd).decode(mel)
     assert got.shape == ref.shape == (2, 256 * 199) and torch.isfinite(got).all()
+    _within_model(f"vocos log-magnitudes + {shift:.2f}", sd, mel, got)
     return got, ref
 
 
@@ -105,6 +119,7 @@ def test_vocos_decode_silence_frames(vocos):
     assert got.shape == ref.shape == (2, 256 * 63) and torch.isfinite(got).all()
     mx, rms = _report("vocos silence frames b2 t64", got, ref)
     assert mx < 1e-4
+    _within_model("vocos silence frames b2 t64", sd, mel, got)
 
 
 def test_mel_then_vocos_roundtrip_lengths(vocos):

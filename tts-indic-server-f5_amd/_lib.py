@@ -89,6 +89,7 @@ SYMBOLS = {
     "f5hip_vocos_finalize": (C.c_int, [C.c_void_p]),
     "f5hip_vocos_decode": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_vocos_decode_ragged": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "f5hip_vocos_decode_taps": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
     "f5hip_bigvgan_create": (C.c_void_p, [C.POINTER(BigVGANConfig)]),
     "f5hip_bigvgan_destroy": (None, [C.c_void_p]),
     "f5hip_bigvgan_load_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),

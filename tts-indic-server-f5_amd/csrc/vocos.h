@@ -248,10 +248,26 @@ int f5hip_vocos_finalize(f5hip_vocos* v) {
     return 0;
 }
 
+// Parity taps of one decode (f5hip_vocos_decode_taps): where to stop and where the valid rows of the workspace go
+struct VocosTaps { int n_blocks; float *x, *y, *fw; };
+
+// Copies the items' valid rows (item b: frames[b] rows from slab row seq_row0[b]) of src [rows][ld], `width` floats each, to dst packed
+static int vocos_copy_rows(const float* src, int ld, int width, int n, const int32_t* frames, const int* seq_row0, float* dst, hipStream_t st) {
+    for (int b = 0; b < n; b++) {
+        if (hipMemcpy2DAsync(dst, sizeof(float) * width, src + (size_t)seq_row0[b] * ld, sizeof(float) * ld, sizeof(float) * width, frames[b],
+                             hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(-6, "vocos taps: copy");
+        dst += (size_t)frames[b] * width;
+    }
+    return 0;
+}
+
 // n items, item i with frames[i] frames at mel_dev + i * C * t_stride (channel stride t_stride); every item gets its own 128-row padded slab,
 // so the embed conv and the depthwise convs see zeros at their item's bounds (row_start / row_end) and every kernel works row by row.
-// Output packed: item i at wave_dev + hop * sum_{j<i} (frames[j] - 1).
-static int vocos_decode_items(f5hip_vocos* v, int n, const int32_t* frames, int t_stride, const float* mel_dev, float* wave_dev, hipStream_t st) {
+// Output packed: item i at wave_dev + hop * sum_{j<i} (frames[j] - 1).  With `taps` the same launches stop behind taps->n_blocks ConvNeXt blocks
+// (< 0: none left out) and the valid rows of the residual stream -- behind a whole decode also of the head output and the windowed frames --
+// are copied out.
+static int vocos_decode_items(f5hip_vocos* v, int n, const int32_t* frames, int t_stride, const float* mel_dev, float* wave_dev, hipStream_t st,
+                              const VocosTaps* taps = nullptr) {
     const f5hip_vocos_config& c = v->cfg;
     const int D = c.dim, I = c.intermediate_dim, LDY = 1152;
     long long m_ll = 0, l_ll = 0;
@@ -301,7 +317,8 @@ static int vocos_decode_items(f5hip_vocos* v, int n, const int32_t* frames, int 
     LnArgs ln = ln_args(v->x, D, M, D, v->norm_w, v->norm_b, 0.0f, 1e-6f);
     ln.out_f32 = v->x; ln.ldof = D;
     CK(run_ln(ln, st));
-    for (int i = 0; i < c.num_layers; i++) {
+    const int nb = taps && taps->n_blocks >= 0 ? taps->n_blocks : c.num_layers;
+    for (int i = 0; i < nb; i++) {
         VocosBlock& b = v->blk[i];
         LnArgs l2 = ln_args(v->x, D, M, D, b.ln_w, b.ln_b, 0.0f, 1e-6f);
         l2.dw_w = b.dw_w; l2.dw_b = b.dw_b; l2.row_seq_start = d_row_start; l2.row_seq_end = d_row_end;
@@ -313,6 +330,10 @@ static int vocos_decode_items(f5hip_vocos* v, int n, const int32_t* frames, int 
         GemmArgs g2 = gemm_base(v->hid, I, b.pw2, M);
         g2.mul = b.gamma; g2.res = v->x; g2.ldres = D; g2.out_f32 = v->x; g2.ldo = D;
         CK(run_gemm_n(v->nsplit, M, g2, b.pw2, EPI_GENERIC, false, 64, st));
+    }
+    if (taps && taps->n_blocks >= 0) {
+        prof_end(PROF_VOCOS, st);
+        return vocos_copy_rows(v->x, D, D, n, frames, seq_row0, taps->x, st);
     }
     LnArgs lf = ln_args(v->x, D, M, D, v->fnorm_w, v->fnorm_b, 0.0f, 1e-6f);
     lf.out_hi = v->tn.hi; lf.out_lo = v->tn.lo; lf.ldo = D;
@@ -327,6 +348,11 @@ static int vocos_decode_items(f5hip_vocos* v, int n, const int32_t* frames, int 
                        v->window, wave_dev);
     CKL("istft_ola");
     prof_end(PROF_VOCOS, st);
+    if (taps) {   // the stream behind the last block is still in x: the final norm writes operand planes
+        CK(vocos_copy_rows(v->x, D, D, n, frames, seq_row0, taps->x, st));
+        CK(vocos_copy_rows(v->y, LDY, c.n_fft + 2, n, frames, seq_row0, taps->y, st));
+        CK(vocos_copy_rows(v->fw, 1024, 1024, n, frames, seq_row0, taps->fw, st));
+    }
     return 0;
 }
 
@@ -343,6 +369,18 @@ int f5hip_vocos_decode_ragged(f5hip_vocos* v, int32_t n, const int32_t* frames, 
     int t_max = 0;
     for (int b = 0; b < n; b++) t_max = std::max(t_max, (int)frames[b]);
     return vocos_decode_items(v, n, frames, t_max, mel_dev, wave_dev, (hipStream_t)stream);
+}
+
+int f5hip_vocos_decode_taps(f5hip_vocos* v, int32_t n, const int32_t* frames, const float* mel_dev, int32_t n_blocks, float* x_dev, float* y_dev,
+                            float* fw_dev, float* wave_dev, void* stream) {
+    if (!v || !v->finalized) return fail(-1, "vocoder not finalized");
+    if (n <= 0 || !frames || !mel_dev || !x_dev) return fail(-1, "vocos_decode_taps: bad argument");
+    if (n_blocks < -1 || n_blocks > v->cfg.num_layers) return fail(-1, "vocos_decode_taps: n_blocks = %d (need -1 .. %d)", n_blocks, v->cfg.num_layers);
+    if (n_blocks < 0 && (!y_dev || !fw_dev || !wave_dev)) return fail(-1, "vocos_decode_taps: a whole decode needs y_dev, fw_dev and wave_dev");
+    int t_max = 0;
+    for (int b = 0; b < n; b++) t_max = std::max(t_max, (int)frames[b]);
+    const VocosTaps taps{n_blocks, x_dev, y_dev, fw_dev};
+    return vocos_decode_items(v, n, frames, t_max, mel_dev, wave_dev, (hipStream_t)stream, &taps);
 }
 
 // ---------------------------------------------------------------------------------------- mel front-end

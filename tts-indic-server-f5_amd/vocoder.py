@@ -19,7 +19,7 @@ class F5HipVocos:
         if self.device.type != "cuda":
             raise _lib.F5HipError("F5HipVocos needs a HIP device (no CPU fallback)")
         torch.cuda.set_device(self.device)
-        self.hop_length = hop_length
+        self.hop_length, self.dim, self.n_fft = hop_length, dim, n_fft
         self._lib = _lib.lib()
         cfg = _lib.VocosConfig(in_channels, dim, intermediate_dim, num_layers, n_fft, hop_length, gemm_planes)
         self._h = self._lib.f5hip_vocos_create(C.byref(cfg))
@@ -79,6 +79,27 @@ class F5HipVocos:
             _lib.check(self._lib.f5hip_vocos_decode_ragged(self._h, len(frames), C.c_void_p(f.data_ptr()), C.c_void_p(mel.data_ptr()),
                                                            C.c_void_p(wave.data_ptr()), _lib.current_stream_ptr()), "f5hip_vocos_decode_ragged")
         return list(wave.split([self.hop_length * (t - 1) for t in frames]))
+
+    @torch.no_grad()
+    def decode_taps(self, mel: torch.Tensor, frames, n_blocks: int = -1) -> dict:
+        """Parity taps (f5hip_vocos_decode_taps): the ragged decode of mel [n, C, T_max], item i valid for t < frames[i], stopped behind
+        `n_blocks` ConvNeXt blocks (0: embed conv + norm; -1: the whole decode).  Returns the valid rows packed item after item:
+        {"x": [sum frames, dim]}, and for -1 also "y" [sum frames, n_fft + 2], "fw" [sum frames, n_fft] and "wave" [hop sum (frames - 1)].
+        What mel holds behind an item's last frame is the caller's (`decode_ragged` puts zeros there); the library does not read it."""
+        frames = [int(t) for t in frames]
+        if mel.dim() != 3 or mel.shape[0] != len(frames) or not frames or mel.shape[2] != max(frames):
+            raise _lib.F5HipError("decode_taps: mel must be [n, C, max(frames)] with one entry of frames per item")
+        mel = mel.to(self.device, torch.float32).contiguous()
+        f = torch.tensor(frames, dtype=torch.int32)
+        rows = sum(frames)
+        new = lambda *shape: torch.empty(*shape, device=self.device, dtype=torch.float32)
+        out = {"x": new(rows, self.dim)}
+        if n_blocks == -1:
+            out.update(y=new(rows, self.n_fft + 2), fw=new(rows, self.n_fft), wave=new(self.hop_length * (rows - len(frames))))
+        ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None
+        _lib.check(self._lib.f5hip_vocos_decode_taps(self._h, len(frames), C.c_void_p(f.data_ptr()), C.c_void_p(mel.data_ptr()), n_blocks,
+                                                     ptr("x"), ptr("y"), ptr("fw"), ptr("wave"), _lib.current_stream_ptr()), "f5hip_vocos_decode_taps")
+        return out
 
 
 class F5HipBigVGAN:
