@@ -576,6 +576,38 @@ int f5hip_wave_loudness(int32_t n, int16_t* pcm_dev, const int64_t* in_off, cons
 /* Samples one block of f5hip_wave_loudness's first launch owns (two sub-blocks).  For tests, which place request lengths around it. */
 int f5hip_wave_loudness_tile(void);
 
+/* FLAC in: n native FLAC streams (RFC 9639) -- uploaded reference clips and recordings, which the reference reads with torchaudio.load
+ * (F/infer/utils_infer.py:376) -- packed at arbitrary byte offsets in one device buffer -> each stream's samples as int32 planes
+ * [channels, total], bit for bit wave_codec.read_flac, which defines the format accepted: every subframe type, LPC order 1 .. 32, both Rice
+ * methods with escapes, every stereo mode, fixed and variable blocking; both CRCs of every frame, every reserved code, the numbering, block
+ * sizes, sample size, rate and channel count against STREAMINFO, samples inside their bit depth, residuals inside 32 bits, the total.  The
+ * caller parses the metadata (STREAMINFO, where the frames begin), applies the cap on the declared length and checks the MD5 afterwards.
+ *   data_dev, nbytes       the packed buffer; no alignment is asked of it or of the streams in it
+ *   begin[i], end[i]       stream i's frames are bytes [begin[i], end[i]) (host arrays): ascending, not overlapping
+ *   info                   host int32 [n][8]: channels, bits, rate, STREAMINFO's min and max block size (0: not named), cap (samples per channel
+ *                          its output has room for: f5hip_flac_decode_bound), needs_host (non-zero: do not decode it), 0
+ *   total[i]               STREAMINFO's total samples, 0: unknown;  max_samples[i]: the most the stream may decode to
+ *   out_dev, out_off[i]    int32: channel c of stream i at out_dev + out_off[i] + c * cap
+ *   status_dev             int32 [n][2]: status (0 decoded; 1 refused; 2 needs the host; 3 both were found) and the samples per channel
+ * The device takes 1 .. 2 channels, 8 .. 24 bits and block sizes up to 16 384; a stream outside that has status 2 before any launch, and a
+ * stream whose frames outrun the slot pool, the record table or its output gets it on the way.  The caller decodes every stream whose status
+ * is not 0 with the host definition, which either returns its samples or raises: a refusal's text never comes from the device.
+ * FIVE launches whatever n (scan: one thread per byte offset finds candidate frame headers; offsets: candidate ids and slot addresses by prefix
+ * sums; frame: one wavefront per candidate, false ones included; chain: one wave per stream follows end offset -> next frame from the first
+ * byte, so a false sync is never visited; pack: stereo reconstruction into the output), no host sync between them (counters
+ * flac_decode_launches, flac_decode_streams); nothing depends on the order of atomics; every read is bounded by the stream's end and every
+ * write by the candidate's slot (csrc/flac_in_core.h, which tools/flac_in_check.cpp runs on the CPU under sanitizers); the stream table is
+ * copied on `stream`, which the call waits for once before it launches.
+ * Refused before the first launch: n < 1, a null pointer, nbytes outside 1 .. 2^31 - 1025, streams that overlap or leave the buffer, a
+ * STREAMINFO field out of range, a misaligned output. */
+int f5hip_flac_decode(int32_t n, const uint8_t* data_dev, int64_t nbytes, const int64_t* begin, const int64_t* end, const int32_t* info,
+                      const int64_t* total, const int64_t* max_samples, int32_t* out_dev, const int64_t* out_off, int32_t* status_dev, void* stream);
+
+/* Samples per channel a stream's output needs: STREAMINFO's total or, when it names none, 2 * stream_bytes + 16 384 (a stream that packs more
+ * into its bytes gets status 2); never more than 64 * stream_bytes + 16 384, so that memory stays in proportion to the upload whatever
+ * STREAMINFO declares, and never more than max_samples. */
+int64_t f5hip_flac_decode_bound(int64_t total, int64_t stream_bytes, int64_t max_samples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,8 @@ import wave as _wave
 
 import numpy as np
 
+from . import wave_codec
+
 _MAX_AMP = 32768.0   # AudioSegment.max_possible_amplitude for 16-bit samples
 
 
@@ -38,6 +40,11 @@ class PcmSegment:
 
     @classmethod
     def from_wav(cls, path: str) -> "PcmSegment":
+        with open(path, "rb") as f:
+            head = f.read(8)
+        if wave_codec.is_flac(head):                                  # a FLAC voice file: any depth, quantised by the routes' rule
+            wav, rate = wave_codec.load_audio(path)
+            return cls(wave_codec.quantise_pcm16(wav.numpy().T), rate)
         with _wave.open(path, "rb") as f:
             rate, ch, sw, n = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
             raw = f.readframes(n)

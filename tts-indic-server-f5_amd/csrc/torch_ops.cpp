@@ -25,6 +25,7 @@
 //   torch.ops.f5hip.wave_finish_joins(chunks[], chunks_per_request, fade, chunk_fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/infer_cli.py:181-208
 //   torch.ops.f5hip.mel_spectrogram_ragged(waves[], n_fft, hop_length, n_mels, sample_rate, variant) -> Tensor mel [sum T, n_mels]   F/model/modules.py:30-143
 //   torch.ops.f5hip.wave_flac(pcm[], in_off, max_len, len_dev?, sample_rate) -> (Tensor streams uint8, Tensor lengths int32, Tensor offsets int64 host)
+//   torch.ops.f5hip.flac_decode(data, begin, end, info, total, max_samples) -> (Tensor statuses and planes int32, Tensor offsets int64 host)
 //   torch.ops.f5hip.wave_encode(pcm[], in_off, max_len, len_dev?, new_freq, encoding, taps?) -> (Tensor bytes uint8, Tensor lengths int32, Tensor offsets int64 host)
 #include "../../include/f5hip.h"
 #include "rate_pair.h"
@@ -436,6 +437,38 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_flac(at::TensorList pcm, con
     return {out, out_len, out_off};
 }
 
+// data: the packed streams, uint8 on the device; begin, end, total, max_samples [n] int64 host; info [n, 8] int32 host (channels, bits, rate,
+// min block, max block, cap, needs_host, 0) as f5hip_flac_decode's -> (out int32 device: [n, 2] status and samples per channel, then the planes:
+// channel c of stream i at out_off[i] + c * cap; out_off [n] int64 host)
+std::tuple<at::Tensor, at::Tensor> flac_decode(const at::Tensor& data, const at::Tensor& begin, const at::Tensor& end, const at::Tensor& info,
+                                               const at::Tensor& total, const at::Tensor& max_samples) {
+    check_host(begin, at::kLong, "begin"); check_host(end, at::kLong, "end"); check_host(info, at::kInt, "info");
+    check_host(total, at::kLong, "total"); check_host(max_samples, at::kLong, "max_samples");
+    const int64_t n = begin.numel();
+    TORCH_CHECK(begin.dim() == 1 && n > 0 && n <= INT32_MAX / 2 && end.numel() == n && total.numel() == n && max_samples.numel() == n && info.dim() == 2 &&
+                info.size(0) == n && info.size(1) == 8, "f5hip::flac_decode: begin, end, total, max_samples need one value per stream and info [n, 8]");
+    TORCH_CHECK(data.is_cuda() && data.scalar_type() == at::kByte && data.is_contiguous() && data.dim() == 1 && data.numel() > 0,
+                "f5hip::flac_decode: data must be a non-empty contiguous 1-D uint8 tensor on a HIP device");
+    const int32_t* f = info.data_ptr<int32_t>();
+    at::Tensor out_off = at::empty({n}, at::TensorOptions().dtype(at::kLong));
+    int64_t* oo = out_off.data_ptr<int64_t>();
+    int64_t words = 2 * n;
+    for (int64_t i = 0; i < n; i++) {
+        TORCH_CHECK(f[8 * i] >= 1 && f[8 * i] <= 8 && f[8 * i + 5] >= 0, "f5hip::flac_decode: stream ", i, " has ", f[8 * i], " channels and room for ", f[8 * i + 5],
+                    " samples");
+        oo[i] = words;
+        if (!f[8 * i + 6]) words += (int64_t)f[8 * i] * f[8 * i + 5];
+        TORCH_CHECK(words <= (int64_t)1 << 40, "f5hip::flac_decode: the call's streams declare more samples than one call takes");
+    }
+    const c10::DeviceGuard guard(data.device());
+    at::Tensor out = at::empty({words}, data.options().dtype(at::kInt));
+    const int rc = f5hip_flac_decode((int32_t)n, data.data_ptr<uint8_t>(), data.numel(), begin.data_ptr<int64_t>(), end.data_ptr<int64_t>(), f,
+                                     total.data_ptr<int64_t>(), max_samples.data_ptr<int64_t>(), out.data_ptr<int32_t>(), oo, out.data_ptr<int32_t>(),
+                                     stream_of(data));
+    TORCH_CHECK(rc == 0, "f5hip_flac_decode: ", f5hip_last_error());
+    return {out, out_off};
+}
+
 // pcm: the int16 device tensor that holds every request (f5hip_wave_finish's packed PCM), normalised IN PLACE; in_off, max_len, len_dev as
 // wave_encode's; gain_k [n] float64 host: K_T per request, <= 0 leaves the request alone -> stats int64 device [n, 4]: n2, S2, peak, the bits
 // of g (zeros for a request that was left alone)
@@ -490,5 +523,6 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("mel_spectrogram_ragged(Tensor[] waves, int n_fft, int hop_length, int n_mels, int sample_rate, int variant) -> Tensor", &mel_spectrogram_ragged);
     m.def("wave_encode(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int new_freq, int encoding, Tensor? taps) -> (Tensor, Tensor, Tensor)", &wave_encode);
     m.def("wave_flac(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int sample_rate) -> (Tensor, Tensor, Tensor)", &wave_flac);
+    m.def("flac_decode(Tensor data, Tensor begin, Tensor end, Tensor info, Tensor total, Tensor max_samples) -> (Tensor, Tensor)", &flac_decode);
     m.def("wave_loudness(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor gain_k) -> Tensor", &wave_loudness);
 }

@@ -5,8 +5,9 @@ cross-fade ramps), running the sampler and vocoder on the HIP objects (`F5HipMod
 reference's speech-edit script (F/infer/speech_edit.py:119-192) as `plan_edit` / `speech_edit` / `speech_edit_batch`.
 
 Host-side differences, all explicit:
-  * reference audio is read by `wave_codec.load_wav` (a RIFF chunk walker: PCM 8/16/24/32-bit, IEEE float 32/64-bit,
-    WAVE_FORMAT_EXTENSIBLE) or passed as a `(tensor, sr)` pair: torchaudio is not part of this image;
+  * reference audio is read by `wave_codec.load_audio`: WAV through `load_wav` (a RIFF chunk walker: PCM 8/16/24/32-bit, IEEE float
+    32/64-bit, WAVE_FORMAT_EXTENSIBLE), native FLAC through `read_flac` (the whole format in Python integers; `ops.flac_decode` is the
+    same function on the device), or passed as a `(tensor, sr)` pair: torchaudio is not part of this image;
   * resampling to 24 kHz restates torchaudio.transforms.Resample (sinc interpolation, Hann window, width 6, rolloff 0.99; third-party
     leaf, parity unpinned) on the host, like the reference does before `.to(device)`: `wave_codec.resample_sinc_hann`;
   * what the driver has no counterpart for -- WAV reading, the resamplers and their tap tables, G.711, the delivery format of a request --
@@ -34,7 +35,7 @@ from .audio_prep import preprocess_ref_audio_text, remove_silence_edges, remove_
 from .loaders import DiT, MMDiT, UNetT, load_checkpoint, load_model, load_vocoder  # noqa: F401  (F/infer/utils_infer.py:92-130,175-260)
 from .wave_codec import (ALL_ENCODINGS, FLAC_BLOCK, FLAC_ENCODINGS, FLAC_HEADER_BYTES, MAX_TAP_TABLE_BYTES, OUTPUT_ENCODINGS,  # noqa: F401
                          OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, StreamFlacEncoder, StreamResampler, decode_flac, decode_g711, deliver_pcm16,
-                         delivery_format, encode_flac, encode_g711, flac_crc8, flac_crc16, flac_stream_header, load_wav, quantise_pcm16,
+                         delivery_format, encode_flac, encode_g711, flac_crc8, flac_crc16, flac_stream_header, load_audio, load_wav, quantise_pcm16, read_flac,
                          rate_pair, resample_pcm16, resample_sinc_hann, resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
 from .wave_codec import (LOUDNESS_GATE_ABS, LOUDNESS_PEAK_CEILING, LOUDNESS_RANGE, LOUDNESS_TAPS, check_loudness, loudness_gain,  # noqa: F401
                          loudness_gain_constant, loudness_lufs, loudness_taps, measure_loudness, normalise_loudness_pcm16)
@@ -134,7 +135,7 @@ def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_ty
     """F/infer/utils_infer.py:357-400.  `seed` (not in the reference's signature): the request's noise comes from its own CPU generator
     (`request_generator`) instead of the global one.  `ode_method` (neither): "euler", "midpoint" or "rk4" for this request instead of the
     model object's solver."""
-    audio, sr = ref_audio if isinstance(ref_audio, tuple) else load_wav(ref_audio)
+    audio, sr = ref_audio if isinstance(ref_audio, tuple) else load_audio(ref_audio)
     gen_text_batches = request_chunks(ref_text, audio.shape[-1] / sr, gen_text)
     return infer_batch_process((audio, sr), ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type=mel_spec_type,
                                progress=progress, target_rms=target_rms, cross_fade_duration=cross_fade_duration,
@@ -161,7 +162,7 @@ def infer_process_stream(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_
     noise is drawn unit by unit in order, so with the model handle in shape-invariant attention mode and the same generator state before
     both calls (`torch.manual_seed`), the pieces equal `infer_process`'s wave to the last bit.  With `seed`, both calls draw from the
     request's one generator (the remaining chunks after the first chunk's draws), so the pieces equal `infer_process(..., seed=seed)`."""
-    audio, sr = ref_audio if isinstance(ref_audio, tuple) else load_wav(ref_audio)
+    audio, sr = ref_audio if isinstance(ref_audio, tuple) else load_audio(ref_audio)
     voice, units = _plan_request((audio, sr), ref_text, gen_text, target_rms, speed, fix_duration, device, text_to_tokens)
     knobs = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, ode_method=ode_method)
     gen = request_generator(seed)
@@ -373,7 +374,7 @@ class PreparedVoice:
     ragged front-end call on the device for all deferred voices of a batch (`infer_requests`, `SpanScheduler`)."""
 
     def __init__(self, ref_audio, target_rms=0.1, device=None):
-        wav, sr = ref_audio if isinstance(ref_audio, tuple) else load_wav(ref_audio)
+        wav, sr = ref_audio if isinstance(ref_audio, tuple) else load_audio(ref_audio)
         self.seconds = wav.shape[-1] / sr
         self.audio, self.rms = _prepare_reference(wav, sr, target_rms, device)
         self.ref_frames = self.audio.shape[-1] // hop_length
@@ -1277,7 +1278,7 @@ def prepare_edit(audio, target_text, parts_to_edit, fix_duration=None, mel_spec_
     Raises ValueError for an empty text, a text with more tokens than the recording has mel frames, or a rejected plan."""
     if not isinstance(target_text, str) or not target_text.strip():
         raise ValueError("target_text is empty: give the full transcript of the edited recording")
-    wav, sr = audio if isinstance(audio, tuple) else load_wav(audio)
+    wav, sr = audio if isinstance(audio, tuple) else load_audio(audio)
     wav, rms = _prepare_reference(wav, sr, target_rms, None)
     plan = plan_edit(wav.shape[-1], parts_to_edit, fix_duration, mel_spec_type)
     tokens = tokenizer([target_text])[0]

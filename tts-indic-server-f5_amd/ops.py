@@ -589,3 +589,73 @@ def wave_loudness(pcm, in_off, max_len, len_dev, gain_k):
             _lib.check(_lib.lib().f5hip_wave_loudness(n, _p(pcm), _p(io), _p(ml), _p(len_dev), _p(gk), _p(stats), _lib.current_stream_ptr()),
                        "f5hip_wave_loudness")
     return stats
+
+
+def flac_decode_packed(buffer, spans, device=None):
+    """`flac_decode` of streams that already lie in one byte buffer: `spans[i] = (first, last + 1)` byte of stream i ("fLaC" included), in
+    ascending order and not overlapping; whatever lies between them is not looked at."""
+    from . import wave_codec
+    buf = np.frombuffer(bytes(buffer), dtype=np.uint8) if not isinstance(buffer, np.ndarray) else np.ascontiguousarray(buffer, dtype=np.uint8)
+    n = len(spans)
+    if n < 1:
+        raise _lib.F5HipError("flac_decode: at least one stream")
+    streams, infos = [], []
+    for a, b in spans:                                        # everything that needs no samples is refused here, before the device is touched
+        if not 0 <= a <= b <= len(buf):
+            raise _lib.F5HipError(f"flac_decode: stream bytes [{a}, {b}) of a buffer of {len(buf)}")
+        streams.append(buf[a:b].tobytes())
+        infos.append(wave_codec.flac_stream_info(streams[-1]))
+    host = [wave_codec.flac_needs_host(f) for f in infos]
+    results = [None] * n
+    if not all(host):
+        begin = np.array([a + f["first"] for (a, _), f in zip(spans, infos)], dtype=np.int64)
+        end = np.array([b for _, b in spans], dtype=np.int64)
+        total = np.array([f["total"] for f in infos], dtype=np.int64)
+        most = np.array([wave_codec.FLAC_MAX_SECONDS * f["rate"] for f in infos], dtype=np.int64)
+        bound = _lib.lib().f5hip_flac_decode_bound
+        info = np.zeros((n, 8), dtype=np.int32)
+        for i, f in enumerate(infos):
+            cap = int(bound(int(total[i]), int(end[i] - begin[i]), int(most[i])))
+            info[i] = (f["channels"], f["bits"], f["rate"], f["min_block"], f["max_block"], cap, int(host[i]), 0)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        with torch.cuda.device(dev):
+            data = torch.from_numpy(buf.copy()).to(dev)
+            if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
+                try:
+                    out, out_off = torch_ops.ops().flac_decode(data, torch.from_numpy(begin), torch.from_numpy(end), torch.from_numpy(info),
+                                                               torch.from_numpy(total), torch.from_numpy(most))
+                except RuntimeError as e:   # c10::Error from the operator's checks or the library
+                    raise _lib.F5HipError(str(e)) from e
+                out_off = out_off.numpy()
+            else:
+                out_off, words = np.zeros(n, dtype=np.int64), 2 * n
+                for i in range(n):
+                    out_off[i] = words
+                    words += 0 if host[i] else int(info[i, 0]) * int(info[i, 5])
+                out = torch.empty(words, device=dev, dtype=torch.int32)
+                _lib.check(_lib.lib().f5hip_flac_decode(n, _p(data), data.numel(), _p(begin), _p(end), _p(info), _p(total), _p(most), _p(out), _p(out_off),
+                                                        _p(out), _lib.current_stream_ptr()), "f5hip_flac_decode")
+            got = out.cpu().numpy()                           # the one download: statuses and samples
+        for i, f in enumerate(infos):
+            if got[2 * i] == 0:
+                cap, count = int(info[i, 5]), int(got[2 * i + 1])
+                planes = got[out_off[i]:out_off[i] + f["channels"] * cap].reshape(f["channels"], cap)[:, :count].copy()
+                wave_codec.flac_check_md5(planes, f)
+                results[i] = (planes, int(f["rate"]), int(f["bits"]))
+    for i in range(n):                                        # outside the limits, or refused: the definition decodes it or raises
+        if results[i] is None:
+            results[i] = wave_codec.read_flac(streams[i])
+    return results
+
+
+def flac_decode(streams, device=None):
+    """Native FLAC streams (bytes each) -> [(samples int32 [channels, n], sample_rate, bits)], `wave_codec.read_flac` of each, decoded on the
+    device in ONE library call and five launches (include/f5hip.h f5hip_flac_decode) with one upload and one download.  A stream outside the
+    device's limits (more than 2 channels, a depth outside 8 .. 24 bits, a block over 16 384) and every stream the device does not accept are
+    decoded by `read_flac` on the host, so the samples -- or the ValueError -- are the definition's either way."""
+    streams = [bytes(s.tobytes() if isinstance(s, np.ndarray) else s) for s in streams]
+    spans, at = [], 0
+    for s in streams:
+        spans.append((at, at + len(s)))
+        at += len(s)
+    return flac_decode_packed(b"".join(streams), spans, device)

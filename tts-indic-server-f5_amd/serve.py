@@ -115,6 +115,11 @@ DEVICE_FRONTEND_DEFAULT = True
 # Off: turning it on changes what `synthesize` returns (int16 PCM instead of float32), and the rule above asks for a win at ONE request by
 # more than the run's own spread (tools/wave_backend_bench.py, profiles/wave_backend_bench.txt; DESIGN "Waveform back-end")
 DEVICE_BACKEND_DEFAULT = False
+# Whether FLAC uploads and recordings are decoded on the device (`ops.flac_decode`) unless `TTSManager(device_decode=...)` says otherwise: it
+# is on because the device beat the host's `read_flac` for ONE clip on the MI355X -- 10 s stereo 44.1 kHz, block 4096, LPC order 8: host
+# 1426.2 ms (1423.3 .. 1434.7), device 13.7 ms (13.6 .. 13.9), upload, download and MD5 included (tools/flac_decode_bench.py,
+# profiles/flac_decode_bench.txt).  The samples are the same either way.
+DEVICE_DECODE_DEFAULT = True
 STREAM_REMOVE_SILENCE = "remove_silence needs the request's whole wave: it is not available on a streaming path"
 STREAM_LOUDNESS = "loudness is measured on the request's whole wave: it is not available on a streaming path"
 
@@ -403,7 +408,7 @@ class TTSManager:
     def __init__(self, loader: Callable[[], tuple] | None = None, nfe_step: int = infer.nfe_step, cfg_strength: float = infer.cfg_strength,
                  sway_sampling_coef: float = infer.sway_sampling_coef, speed: float = infer.speed, mel_spec_type: str = "vocos",
                  micro_batch: dict | None = None, batch_invariant: bool = True, clip_cache: int = 64, device_frontend: bool | None = None,
-                 device_backend: bool | None = None):
+                 device_backend: bool | None = None, device_decode: bool | None = None):
         self.loader = loader
         self.batch_invariant = batch_invariant   # False: leave the model's attention mode alone (fastest kernel per launch shape)
         self.micro_batch = micro_batch            # e.g. dict(max_requests=16, max_wait_ms=5): batch concurrent requests; with span_steps
@@ -431,6 +436,10 @@ class TTSManager:
         # quantisation, `remove_silence`), downloaded once; a non-streamed request's result is then that int16 array, which `wav_bytes` passes
         # through -- the same bytes as the float32 wave gives.  False: joined on the host, float32 as before.  None: DEVICE_BACKEND_DEFAULT
         self.device_backend = DEVICE_BACKEND_DEFAULT if device_backend is None else bool(device_backend)
+        # True: a FLAC upload or recording is decoded by `ops.flac_decode` (one library call, five launches, under the device lock; with a
+        # `ShardedSampler` on rank 0's device); False: by `wave_codec.read_flac` on the host.  None: DEVICE_DECODE_DEFAULT.  WAV never
+        # touches the device here.
+        self.device_decode = DEVICE_DECODE_DEFAULT if device_decode is None else bool(device_decode)
         # The library allows ONE call in flight per handle (include/f5hip.h), the sampler keeps per-call state and noise comes from torch's
         # global generator: every entry into the device path takes this lock.  Without a batcher, concurrent HTTP requests therefore run one
         # after the other, like the reference's blocking `async def` handlers (S/routes/speech.py:19-41).
@@ -495,6 +504,25 @@ class TTSManager:
             closer()                             # ShardedSampler: releases the worker ranks
         self.model = self.model_obj = self.vocoder = None
 
+    def _decode_flac(self, data):
+        """`load_audio`'s FLAC reader for this manager: what needs no samples is refused first (`flac_stream_info`: the metadata chain,
+        STREAMINFO's limits, the cap), then the stream is decoded on the device under the device lock -- or, without `device_decode` or
+        without a loaded model's device, by `read_flac`."""
+        import torch
+        infer.wave_codec.flac_stream_info(data)
+        model_obj = getattr(self.model_obj, "local", self.model_obj)
+        device = getattr(model_obj, "device", None)
+        if not self.device_decode or device is None or torch.device(device).type != "cuda":
+            return infer.read_flac(data)
+        from . import ops
+        with self._device_lock:
+            return ops.flac_decode([data], device=device)[0]
+
+    def decode_audio(self, src):
+        """(float32 wave [channels, n], sample_rate) of an upload or a recording -- a path, the file's bytes or a binary file object; WAV
+        or native FLAC (`infer.load_audio`), FLAC through `_decode_flac`.  ValueError for anything unreadable."""
+        return infer.load_audio(src, flac=self._decode_flac)
+
     def _voice(self, ref_audio_path, ref_text):
         """Once per voice: the reference's pre-step (clip to 15 s / trim silence, `preprocess_ref_audio_text`), then the prologue of
         every `infer_process` call for it (mono, rms gain, 24 kHz) and -- on first use -- its mel on the device."""
@@ -549,7 +577,7 @@ class TTSManager:
                     wave, sr = ref_audio[0].detach().cpu().to(torch.float32), int(ref_audio[1])
                 else:
                     try:
-                        wave, sr = infer.load_wav(ref_audio)
+                        wave, sr = self.decode_audio(ref_audio)
                     except ValueError as e:
                         raise ValueError(f"Invalid audio: {e}") from e
                 if wave.dim() != 2 or wave.shape[0] < 1:
@@ -834,7 +862,10 @@ class TTSManager:
         fmt = self.request_options(("sample_rate", "encoding"), sample_rate=sample_rate, encoding=encoding)
         loudness = self.request_options(("loudness",), loudness=loudness).get("loudness")
         model_obj = getattr(self.model_obj, "local", self.model_obj)
-        # host work (read, mono mix, resample, plan, tokens) and every rejection happen before the device lock is taken
+        # host work (read, mono mix, resample, plan, tokens) and every rejection happen before the device lock is taken (a FLAC recording is
+        # decoded under it with `device_decode`, after everything that needs no samples has been refused)
+        if not isinstance(audio, tuple):
+            audio = self.decode_audio(audio)
         prep = infer.prepare_edit(audio, target_text, parts_to_edit, fix_duration, mel_spec_type=self.mel_spec_type)
         extra = dict(generators=[infer.request_generator(opts["seed"])]) if opts.get("seed") is not None else {}
         if opts.get("ode_method") is not None:
@@ -1151,7 +1182,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         if not req.text.strip():
             raise HTTPException(status_code=400, detail="Text to synthesize cannot be empty.")
         try:
-            audio = infer.load_wav(raw)
+            audio = tts_manager.decode_audio(raw)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=f"Invalid audio: {e}")
         try:

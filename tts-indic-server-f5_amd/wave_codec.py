@@ -1,11 +1,12 @@
 """Waves in and out of the server, with nothing of the model in it: reading WAV files (`load_wav`), torchaudio's polyphase sinc resampler
 (`rate_pair`, `resample_taps`, `resample_sinc_hann`) with its tap-table caches, the integer resampler of finished PCM (`resample_pcm16`,
-`StreamResampler`), the BS.1770 loudness meter and normaliser (`measure_loudness`, `normalise_loudness_pcm16`), G.711 (`encode_g711`, `decode_g711`), FLAC (`encode_flac`, `decode_flac`, `StreamFlacEncoder`), the delivery format of a request (`delivery_format`, `deliver_pcm16`) and the bytes
+`StreamResampler`), the BS.1770 loudness meter and normaliser (`measure_loudness`, `normalise_loudness_pcm16`), G.711 (`encode_g711`, `decode_g711`), FLAC (`encode_flac`, `decode_flac`, `StreamFlacEncoder`; the whole format in: `read_flac`, `load_audio`), the delivery format of a request (`delivery_format`, `deliver_pcm16`) and the bytes
 of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
 round; `infer` and `serve` hand every public name on (`infer.load_wav`, `serve.wav_bytes`, ...)."""
 from __future__ import annotations
 
 import collections
+import hashlib
 import io
 import math
 import os
@@ -917,3 +918,285 @@ def decode_flac(stream):
     if total and total != count:
         raise ValueError(f"corrupt FLAC stream: STREAMINFO names {total} samples, the frames hold {count}")
     return (np.concatenate(blocks) if blocks else np.zeros(0, dtype=np.int16)), int(rate)
+
+
+# --- FLAC in: the whole native format (RFC 9639), defined on the host in Python integers -----------------------------------------
+# `read_flac` is the definition that the device decoder (csrc/flac_in_core.h, csrc/flac_in.h, `ops.flac_decode`) equals bit for bit:
+# the two accept the same streams and return the same samples.  `decode_flac` above stays the narrow reader of `encode_flac`'s subset.
+FLAC_MAX_SECONDS = 600                      # audio per stream: a few bytes of CONSTANT frames can declare 2**36 samples
+FLAC_DEVICE_MAX_BLOCK = 16384               # the device decoder's limits (include/f5hip.h f5hip_flac_decode): wider streams are
+FLAC_DEVICE_MAX_CHANNELS = 2                # decoded by `read_flac` on the host
+FLAC_DEVICE_BITS = (8, 24)
+_FLAC_RATES = {1: 88200, 2: 176400, 3: 192000, 4: 8000, 5: 16000, 6: 22050, 7: 24000, 8: 32000, 9: 44100, 10: 48000, 11: 96000}
+_FLAC_SAMPLE_SIZES = {1: 8, 2: 12, 4: 16, 5: 20, 6: 24, 7: 32}
+_FLAC_FIXED = ((), (1,), (2, -1), (3, -3, 1), (4, -6, 4, -1))   # the fixed predictors as LPC coefficients at shift 0
+
+
+def _audio_bytes(src) -> bytes:
+    if isinstance(src, np.ndarray):
+        return src.tobytes()
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        return bytes(src)
+    if hasattr(src, "read"):
+        return src.read()
+    with open(os.fspath(src), "rb") as f:
+        return f.read()
+
+
+def flac_stream_info(data):
+    """The STREAMINFO fields of a native FLAC stream and where its frames begin, as a dict (min_block, max_block, rate, channels, bits,
+    total, md5, first: the byte after the last metadata block).  Refuses (ValueError) what needs no samples to refuse: the magic, the
+    metadata chain, a sample size under 4 bits, rate 0, and a declared total beyond FLAC_MAX_SECONDS."""
+    if data[:4] != b"fLaC":
+        raise ValueError(f"not a FLAC stream (starts with {bytes(data[:4])!r})")
+    pos, info = 4, None
+    while True:
+        if pos + 4 > len(data):
+            raise ValueError("truncated FLAC stream: metadata")
+        kind, size = data[pos] & 0x7F, int.from_bytes(data[pos + 1:pos + 4], "big")
+        last, pos = data[pos] >> 7, pos + 4
+        if pos + size > len(data):
+            raise ValueError("truncated FLAC stream: metadata")
+        if info is None:
+            if kind != 0 or size != 34:
+                raise ValueError("corrupt FLAC stream: the first metadata block is not STREAMINFO")
+            info = data[pos:pos + 34]
+        pos += size
+        if last:
+            break
+    word = int.from_bytes(info[10:18], "big")
+    out = dict(min_block=int.from_bytes(info[0:2], "big"), max_block=int.from_bytes(info[2:4], "big"), rate=word >> 44,
+               channels=((word >> 41) & 7) + 1, bits=((word >> 36) & 31) + 1, total=word & ((1 << 36) - 1), md5=bytes(info[18:34]), first=pos)
+    if out["bits"] < 4:
+        raise ValueError(f"corrupt FLAC stream: STREAMINFO names {out['bits']} bits per sample")
+    if out["rate"] == 0:
+        raise ValueError("unsupported FLAC stream: sample rate 0")
+    if out["total"] > FLAC_MAX_SECONDS * out["rate"]:
+        raise ValueError(f"FLAC stream too long: STREAMINFO names {out['total']} samples at {out['rate']} Hz (at most {FLAC_MAX_SECONDS} s)")
+    return out
+
+
+def flac_needs_host(info) -> bool:
+    """Whether a stream (its `flac_stream_info`) lies outside the device decoder's limits."""
+    return info["channels"] > FLAC_DEVICE_MAX_CHANNELS or not FLAC_DEVICE_BITS[0] <= info["bits"] <= FLAC_DEVICE_BITS[1]
+
+
+def flac_check_md5(samples, info):
+    """The last check of a decoded stream, on the host for both decoders: STREAMINFO's MD5, when non-zero, against the interleaved
+    little-endian samples at ceil(bits / 8) bytes each."""
+    if info["md5"] == bytes(16):
+        return
+    width = (info["bits"] + 7) // 8
+    raw = np.ascontiguousarray(samples.T).astype("<i4").view(np.uint8).reshape(-1, 4)[:, :width]
+    found = hashlib.md5(raw.tobytes()).digest()
+    if found != info["md5"]:
+        raise ValueError(f"corrupt FLAC stream: STREAMINFO's MD5 is {info['md5'].hex()}, the samples' {found.hex()}")
+
+
+def _flac_frame_header(data, pos, info):
+    """The header of the frame at byte `pos`: dict(variable, block, rate, code (the channel code), channels, bits, number, size: its
+    bytes, the CRC-8 included)."""
+    rd = _FlacBits(data[pos:pos + 16])
+    if rd.read(14) != 0x3FFE:
+        raise ValueError(f"corrupt FLAC stream: no frame sync at byte {pos}")
+    if rd.read(1):
+        raise ValueError(f"corrupt FLAC stream: reserved bit after the sync of the frame at byte {pos}")
+    variable = rd.read(1)
+    bs_code, rate_code, ch_code, size_code = rd.read(4), rd.read(4), rd.read(4), rd.read(3)
+    if bs_code == 0:
+        raise ValueError(f"corrupt FLAC stream: reserved block-size code 0 in the frame at byte {pos}")
+    if rate_code == 15:
+        raise ValueError(f"corrupt FLAC stream: invalid sample-rate code 15 in the frame at byte {pos}")
+    if ch_code > 10:
+        raise ValueError(f"corrupt FLAC stream: reserved channel code {ch_code} in the frame at byte {pos}")
+    if size_code == 3:
+        raise ValueError(f"corrupt FLAC stream: reserved sample-size code 3 in the frame at byte {pos}")
+    if rd.read(1):
+        raise ValueError(f"corrupt FLAC stream: reserved bit in the header of the frame at byte {pos}")
+    lead = rd.read(8)
+    extra = 0 if lead < 0x80 else 7 - (lead ^ 0xFF).bit_length() if 0xC0 <= lead <= (0xFE if variable else 0xFC) else -1
+    if extra < 0:
+        raise ValueError(f"corrupt FLAC stream: coded number of the frame at byte {pos} (lead byte {lead:#04x})")
+    number = lead if not extra else lead & (0x7F >> (extra + 1))
+    for _ in range(extra):
+        c = rd.read(8)
+        if c >> 6 != 2:
+            raise ValueError(f"corrupt FLAC stream: coded number of the frame at byte {pos} (continuation byte {c:#04x})")
+        number = (number << 6) | (c & 0x3F)
+    block = rd.read(8) + 1 if bs_code == 6 else rd.read(16) + 1 if bs_code == 7 else _FLAC_BLOCK_SIZES[bs_code]
+    if block > 65535:
+        raise ValueError(f"corrupt FLAC stream: block size {block} in the frame at byte {pos}")
+    rate = (info["rate"] if rate_code == 0 else rd.read(8) * 1000 if rate_code == 12 else rd.read(16) if rate_code == 13
+            else rd.read(16) * 10 if rate_code == 14 else _FLAC_RATES[rate_code])
+    size = rd.pos // 8
+    if flac_crc8(data[pos:pos + size]) != rd.read(8):
+        raise ValueError(f"corrupt FLAC stream: header CRC-8 of the frame at byte {pos}")
+    return dict(variable=variable, block=block, rate=rate, code=ch_code, channels=ch_code + 1 if ch_code < 8 else 2,
+                bits=_FLAC_SAMPLE_SIZES[size_code] if size_code else info["bits"], number=number, size=size + 1)
+
+
+def _flac_restore(warm, res, coefs, shift, depth):
+    """warm-up + residuals -> samples by `s[i] = res[i] + (sum(coefs[j] * s[i-1-j]) >> shift)`, in Python integers; stops with ValueError
+    at the first sample outside `depth` bits, so no later value is ever built on one."""
+    lo, hi = -(1 << (depth - 1)), (1 << (depth - 1)) - 1
+    s = [int(v) for v in warm]
+    for v in s:
+        if not lo <= v <= hi:                                    # (only a 1-bit depth's warm-up can be here: signed(depth) is in range)
+            raise ValueError(f"corrupt FLAC stream: samples outside {depth} bits")
+    o = len(coefs)
+    rev = tuple(reversed(coefs))                                 # rev[j] multiplies s[i - o + j]
+    for i, r in enumerate(res.tolist(), o):
+        acc = 0
+        for c, v in zip(rev, s[i - o:i]):
+            acc += c * v
+        v = r + (acc >> shift)
+        if not lo <= v <= hi:
+            raise ValueError(f"corrupt FLAC stream: samples outside {depth} bits")
+        s.append(v)
+    return s
+
+
+def _flac_subframe(rd, b, depth):
+    """One subframe of `b` samples at `depth` bits, from the bit reader: a list of Python integers."""
+    if rd.read(1):
+        raise ValueError("corrupt FLAC stream: subframe padding bit")
+    typ, wasted = rd.read(6), rd.read(1)
+    if wasted:
+        wasted = rd.unary() + 1
+    depth -= wasted
+    if depth < 1:
+        raise ValueError(f"corrupt FLAC stream: {wasted} wasted bits leave no sample bits")
+    if typ == 0:
+        x = [rd.signed(depth)] * b
+    elif typ == 1:
+        x = [rd.signed(depth) for _ in range(b)]
+    elif 8 <= typ <= 12 or typ >= 32:
+        o = typ - 8 if typ < 32 else typ - 31
+        if o > b:
+            raise ValueError(f"corrupt FLAC stream: predictor order {o} in a block of {b}")
+        warm = [rd.signed(depth) for _ in range(o)]
+        if typ < 32:
+            coefs, shift = _FLAC_FIXED[o], 0
+        else:
+            precision = rd.read(4) + 1
+            if precision == 16:
+                raise ValueError("corrupt FLAC stream: invalid LPC precision code 1111")
+            shift = rd.signed(5)
+            if shift < 0:
+                raise ValueError(f"corrupt FLAC stream: negative LPC shift {shift}")
+            coefs = tuple(rd.signed(precision) for _ in range(o))
+        res = _flac_residual(rd, b, o)
+        if len(res) and (res.min() < -(1 << 31) or res.max() >= 1 << 31):
+            raise ValueError("corrupt FLAC stream: a residual outside 32 bits")
+        x = _flac_restore(warm, res, coefs, shift, depth)
+    else:
+        raise ValueError(f"corrupt FLAC stream: reserved subframe type {typ:#04x}")
+    return [v << wasted for v in x] if wasted else x
+
+
+def _flac_frame_body(data, start, hdr, info):
+    """The subframes and CRC-16 of the frame at `start`: (channel lists before stereo reconstruction, the frame's end).  The bit reader
+    takes a window of the stream and the parse is repeated on a larger one if it runs out, so reads are bounded by the stream alone."""
+    b, body = hdr["block"], start + hdr["size"]
+    window = hdr["channels"] * (b * hdr["bits"] // 8 + 64) + 1024
+    while True:
+        rd = _FlacBits(data[body:body + window])
+        try:
+            chans = []
+            for c in range(hdr["channels"]):
+                side = (hdr["code"] in (8, 10) and c == 1) or (hdr["code"] == 9 and c == 0)
+                chans.append(_flac_subframe(rd, b, hdr["bits"] + side))
+            end = body + (rd.pos + 7) // 8
+            if end + 2 > len(data):
+                raise ValueError("truncated FLAC stream: frame")
+            break
+        except ValueError as e:
+            if not str(e).startswith("truncated") or body + window >= len(data):
+                raise
+            window *= 4
+    if flac_crc16(data[start:end]) != int.from_bytes(data[end:end + 2], "big"):
+        raise ValueError(f"corrupt FLAC stream: CRC-16 of the frame at byte {start}")
+    return chans, end + 2
+
+
+def flac_unstereo(code, a, b):
+    """Channel planes (int64 arrays) of a two-channel frame from its coded pair: 8 left/side, 9 side/right, 10 mid/side."""
+    if code == 8:
+        return a, a - b
+    if code == 9:
+        return a + b, b
+    if code == 10:
+        m = (a << 1) | (b & 1)
+        return (m + b) >> 1, (m - b) >> 1
+    return a, b
+
+
+def read_flac(stream):
+    """(samples int32 [channels, n], sample_rate, bits) of a native FLAC stream (RFC 9639): every subframe type, LPC order, Rice method,
+    stereo mode, bit depth, channel count and blocking strategy.  Checked, each a ValueError naming what was found: both CRCs of every
+    frame, every reserved code, frame / sample numbers in sequence, block sizes, sample size, rate and channel count against STREAMINFO,
+    samples inside their bit depth, residuals inside 32 bits, STREAMINFO's total and MD5 when non-zero, and FLAC_MAX_SECONDS of audio
+    (against STREAMINFO before decoding, against the running count while decoding).  Serial Python: seconds per clip; `ops.flac_decode`
+    is the same function on the device."""
+    data = _audio_bytes(stream)
+    info = flac_stream_info(data)
+    pos, count, index, first, planes = info["first"], 0, 0, None, []
+    cap = FLAC_MAX_SECONDS * info["rate"]
+    lo, hi = -(1 << (info["bits"] - 1)), (1 << (info["bits"] - 1)) - 1
+    while pos < len(data):
+        try:
+            hdr = _flac_frame_header(data, pos, info)
+        except ValueError as e:
+            if str(e).startswith("truncated"):
+                raise ValueError(f"truncated FLAC stream: header of the frame at byte {pos}") from None
+            raise
+        b = hdr["block"]
+        if (hdr["channels"], hdr["bits"], hdr["rate"]) != (info["channels"], info["bits"], info["rate"]):
+            raise ValueError(f"unsupported FLAC stream: the frame at byte {pos} has {hdr['channels']} channel(s) at {hdr['bits']} bits and "
+                             f"{hdr['rate']} Hz, STREAMINFO {info['channels']} at {info['bits']} and {info['rate']}")
+        if first is None:
+            first = hdr
+        if hdr["variable"] != first["variable"]:
+            raise ValueError(f"corrupt FLAC stream: the blocking strategy changes at byte {pos}")
+        if hdr["number"] != (count if hdr["variable"] else index):
+            raise ValueError(f"corrupt FLAC stream: the frame at byte {pos} is numbered {hdr['number']}, "
+                             f"expected {count if hdr['variable'] else index}")
+        if info["max_block"] and b > info["max_block"]:
+            raise ValueError(f"corrupt FLAC stream: block of {b} at byte {pos}, STREAMINFO's largest is {info['max_block']}")
+        if count + b > cap:
+            raise ValueError(f"FLAC stream too long: more than {FLAC_MAX_SECONDS} s at {info['rate']} Hz")
+        chans, end = _flac_frame_body(data, pos, hdr, info)
+        if end < len(data):                                       # not the last frame, which alone may be short
+            if b < info["min_block"]:
+                raise ValueError(f"corrupt FLAC stream: block of {b} at byte {pos}, STREAMINFO's smallest is {info['min_block']}")
+            if not hdr["variable"] and b != first["block"]:
+                raise ValueError(f"corrupt FLAC stream: block of {b} at byte {pos} in a fixed-blocking stream of {first['block']}")
+        x = np.array(chans, dtype=np.int64)
+        if hdr["code"] >= 8:
+            x = np.stack(flac_unstereo(hdr["code"], x[0], x[1]))
+            if x.min() < lo or x.max() > hi:
+                raise ValueError(f"corrupt FLAC stream: samples outside {info['bits']} bits")
+        planes.append(x.astype(np.int32))
+        count, index, pos = count + b, index + 1, end
+    samples = np.concatenate(planes, axis=1) if planes else np.zeros((info["channels"], 0), dtype=np.int32)
+    if info["total"] and info["total"] != count:
+        raise ValueError(f"corrupt FLAC stream: STREAMINFO names {info['total']} samples, the frames hold {count}")
+    flac_check_md5(samples, info)
+    return samples, int(info["rate"]), int(info["bits"])
+
+
+def is_flac(data) -> bool:
+    """The sniffing rule of `load_audio`: "fLaC" followed by a STREAMINFO block header (type 0, last or not, length 34)."""
+    return len(data) >= 8 and bytes(data[:4]) == b"fLaC" and data[4] & 0x7F == 0 and bytes(data[5:8]) == b"\x00\x00\x22"
+
+
+def load_audio(src, flac=None):
+    """`load_wav` that also takes native FLAC: a source that starts with "fLaC" and a STREAMINFO block header goes to `flac` (default
+    `read_flac`; the server passes the device decoder) and is scaled like PCM in a WAV file, / 2**(bits - 1), exact in float32 up to 24
+    bits; everything else goes to `load_wav` unchanged, its refusals included."""
+    data = _audio_bytes(src)
+    if not is_flac(data):
+        return load_wav(data)
+    samples, rate, bits = (flac or read_flac)(data)
+    x = torch.from_numpy(np.ascontiguousarray(samples).astype(np.float64) / float(1 << (bits - 1))).to(torch.float32)
+    return x, rate
