@@ -27,7 +27,11 @@
 //     the row-major slab with ONE ds_write_b128 instead of four ds_write_b32 (all-V tiles of the QKV projection keep the other order:
 //     4 consecutive tokens per lane = one ds_write_b128 into the transposed slab their [feature][token] output wants);
 //   * the row phase is a rolled, one-deep software-pipelined loop over groups of 4 rows (residual of the next group in flight while the
-//     current one is finished), the (activation x residual x output x guard) variant chosen once per kernel outside it.
+//     current one is finished), the (activation x residual x output x guard) variant chosen once per kernel outside it;
+//   * the QKV launch ends with its slowest column slab (256 workgroups, one round), so its slab kinds are levelled
+//     (profiles/qkv_epilogue_stamps_{before,after}.txt): the rotary rows run the same rolled loop as the plain ones, with all their
+//     cos / sin loads issued back to back ahead of the slab write (g5_qk_rows); a tile that straddles K | V keeps a compact row-major
+//     slab and the transposed one side by side, one write pass and one barrier for both row phases (g5_write_straddle).
 #pragma once
 #include <type_traits>
 
@@ -213,12 +217,11 @@ F5_DEVICE void g5_consume_wd(const char* smem, const char* wf, size_t wf_jstride
 // consumers: accumulators -> slab.  ROWMAJOR: slab[token][feature] (stride SLD); else slab[feature][token] (stride SLDT, + bias: V blocks).
 // One ds_write_b128 per block when the lane's 4 values are contiguous in the target (SWAP & ROWMAJOR, or !SWAP & transposed).
 template <int RB, int CB, int NST, int WR, int MRB, int MCB, bool SWAP, bool ROWMAJOR>
-F5_DEVICE void g5_write_slab(f32x4 (&acc)[MRB][MCB], float* slab, int rb0, int nrb, int cb0, int lane, const float* bias_tile, int j_first = 0) {
+F5_DEVICE void g5_write_slab(f32x4 (&acc)[MRB][MCB], float* slab, int rb0, int nrb, int cb0, int lane, const float* bias_tile) {
     using C = Gemm5Cfg<RB, CB, NST>;
     const int fr = lane & 15, fq = lane >> 4;
 #pragma unroll
     for (int j = 0; j < MCB; j++) {
-        if (j < j_first) continue;                             // (straddling K | V tile: only the V blocks go to the transposed slab)
         f32x4 bj = {0.f, 0.f, 0.f, 0.f};
         if (!ROWMAJOR) {
             if (SWAP) bj = *reinterpret_cast<const f32x4*>(bias_tile + (cb0 + j) * 16 + fq * 4);
@@ -231,7 +234,7 @@ F5_DEVICE void g5_write_slab(f32x4 (&acc)[MRB][MCB], float* slab, int rb0, int n
                     *reinterpret_cast<f32x4*>(slab + ((rb0 + i) * 16 + fr) * C::SLD + (cb0 + j) * 16 + fq * 4) = acc[i][j];
                 } else if (!SWAP && !ROWMAJOR) {
                     *reinterpret_cast<f32x4*>(slab + ((cb0 + j) * 16 + fr) * C::SLDT + (rb0 + i) * 16 + fq * 4) = acc[i][j] + bj;
-                } else if (SWAP) {                             // transposed from the SWAP layout: four scalars (V blocks of a straddling tile)
+                } else if (SWAP) {                             // transposed from the SWAP layout: four scalars (all-V tiles of a W-direct kernel)
                     float* d = slab + ((cb0 + j) * 16 + fq * 4) * C::SLDT + (rb0 + i) * 16 + fr;
 #pragma unroll
                     for (int e = 0; e < 4; e++) d[e * C::SLDT] = acc[i][j][e] + bj[e];
@@ -239,6 +242,35 @@ F5_DEVICE void g5_write_slab(f32x4 (&acc)[MRB][MCB], float* slab, int rb0, int n
                     float* d = slab + ((rb0 + i) * 16 + fq * 4) * C::SLD + (cb0 + j) * 16 + fr;
 #pragma unroll
                     for (int e = 0; e < 4; e++) d[e * C::SLD] = acc[i][j][e];
+                }
+            }
+        }
+    }
+}
+
+// consumers of a QKV tile that straddles K | V at tile column f_lo (SWAP layout): column blocks in front of the boundary (a multiple of 16)
+// go to the row-major slab of stride `sld`, one ds_write_b128 each; those behind it, + bias, to the transposed slab `tslab` (indexed by the
+// tile column), four scalars each.  The two regions are disjoint (gemm5_kernel).
+template <int RB, int CB, int NST, int WR, int MRB, int MCB>
+F5_DEVICE void g5_write_straddle(f32x4 (&acc)[MRB][MCB], float* slab, float* tslab, int sld, int f_lo, int rb0, int nrb, int cb0, int lane,
+                                 const float* bias_tile) {
+    using C = Gemm5Cfg<RB, CB, NST>;
+    const int fr = lane & 15, fq = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < MCB; j++) {
+        const int f0 = (cb0 + j) * 16;
+        if (f0 < f_lo) {                                       // (wave-uniform)
+#pragma unroll
+            for (int i = 0; i < MRB; i++)
+                if (RB % WR == 0 || i < nrb) *reinterpret_cast<f32x4*>(slab + ((rb0 + i) * 16 + fr) * sld + f0 + fq * 4) = acc[i][j];
+        } else {
+            const f32x4 bj = *reinterpret_cast<const f32x4*>(bias_tile + f0 + fq * 4);
+#pragma unroll
+            for (int i = 0; i < MRB; i++) {
+                if (RB % WR == 0 || i < nrb) {
+                    float* d = tslab + (f0 + fq * 4) * C::SLDT + (rb0 + i) * 16 + fr;
+#pragma unroll
+                    for (int e = 0; e < 4; e++) d[e * C::SLDT] = acc[i][j][e] + bj[e];
                 }
             }
         }
@@ -335,8 +367,11 @@ F5_DEVICE void g5_generic_epilogue(const GemmArgs& p, const float* slab, int m0,
 // Q / K rows of the fused QKV projection: bias, rotary embedding on head 0 (x-transformers interleaved pairs, applied before the head
 // split: F/model/modules.py:414-419), q * log2(e) / 8 (softmax scale, base-2 exponents), fp16 row-major [M][2 D].  A 192-column tile can straddle
 // the Q | K or the K | V boundary: both are multiples of 64, so every 64-column panel is of one kind.
-template <int RB, int CB, int NST>
-F5_DEVICE void g5_qk_rows(const GemmArgs& p, const float* slab, int m0, int n0, int wave, int lane) {
+// `sld` = row stride of the row-major slab in floats (C::SLD, or the compact stride of a tile that straddles K | V: gemm5_kernel).
+// write_slab() is the consumers' accumulators -> slab pass; this function owns the barrier behind it (E2), so that the rotary factors are
+// in flight across both.
+template <int RB, int CB, int NST, typename WriteSlab>
+F5_DEVICE void g5_qk_rows(const GemmArgs& p, const float* slab, int sld, int m0, int n0, int wave, int lane, WriteSlab write_slab) {
     using C = Gemm5Cfg<RB, CB, NST>;
     constexpr int NPAN = C::NPAN, NG = RB * 4, NT = (NG + 7) / 8;
     const int D = p.D, r_in = lane >> 4, c4 = (lane & 15) * 4;
@@ -350,18 +385,31 @@ F5_DEVICE void g5_qk_rows(const GemmArgs& p, const float* slab, int m0, int n0, 
         const int n_base = n0 + pn * 64;
         if (n_base == 0 || n_base == D) rot_pn = pn;
     }
-    // rotary factors of this wave's rows, all fetched up front (two dependent global loads per row group: inside the rolled loop they
-    // were ~1 us per group, and the 32 rotary tiles of the C2 launch finished 3 us behind the other 224)
+    // rotary factors of this wave's rows, all issued here, ahead of the slab write and its barrier, which hide their latency (a one-deep
+    // prefetch inside the loop would expose one load latency per row group: a group is ~0.2 us of work).
+    // The positions of ALL groups come first, then the factors of all groups: written as one loop (position, then factors, per group)
+    // hipcc put an s_waitcnt vmcnt(0) behind every position load -- executed with row_pos == null too, where it waited for the factors of
+    // the group before: NT serial round trips, most of the ~3.7 us by which the rotary tiles trailed the plain ones.
     float2 cs[NT], sn[NT];
     if (rot_pn >= 0) {
+        int pos[NT];
+#pragma unroll
+        for (int t = 0; t < NT; t++) pos[t] = m0 + (wave + 8 * t) * 4 + r_in;                 // (row_pos == null: the tables are per ROW, GemmArgs::rope_cos)
+        if (p.row_pos) {                                                                      // (workgroup-uniform)
+#pragma unroll
+            for (int t = 0; t < NT; t++)
+                if (wave + 8 * t < NG && pos[t] < p.M) pos[t] = p.row_pos[pos[t]];
+        }
 #pragma unroll
         for (int t = 0; t < NT; t++) {
             const int row = m0 + (wave + 8 * t) * 4 + r_in;
-            const int pos = (wave + 8 * t < NG && row < p.M) ? (p.row_pos ? p.row_pos[row] : row) : 0;   // (row_pos == null: the tables are per ROW, GemmArgs::rope_cos)
-            cs[t] = *reinterpret_cast<const float2*>(p.rope_cos + pos * 32 + (c4 >> 1));
-            sn[t] = *reinterpret_cast<const float2*>(p.rope_sin + pos * 32 + (c4 >> 1));
+            const int ps = (wave + 8 * t < NG && row < p.M) ? pos[t] : 0;
+            cs[t] = *reinterpret_cast<const float2*>(p.rope_cos + ps * 32 + (c4 >> 1));
+            sn[t] = *reinterpret_cast<const float2*>(p.rope_sin + ps * 32 + (c4 >> 1));
         }
     }
+    write_slab();
+    __syncthreads();                                               // E2: the slab is complete
     auto finish = [&](int g, bool rot, float2 c, float2 s2) {
         const int rl = g * 4 + r_in, row = m0 + rl;
         const bool rok = row < p.M;
@@ -370,7 +418,7 @@ F5_DEVICE void g5_qk_rows(const GemmArgs& p, const float* slab, int m0, int n0, 
             const int n_base = n0 + pn * 64;
             if (n_base < 2 * D) {                                  // (wave-uniform)
                 const int which = n_base / D, nd = n_base - which * D + c4;
-                const f32x4 v = *reinterpret_cast<const f32x4*>(slab + rl * C::SLD + pn * 64 + c4) + bv[pn];
+                const f32x4 v = *reinterpret_cast<const f32x4*>(slab + rl * sld + pn * 64 + c4) + bv[pn];
                 const float qs = which == 0 ? F5_Q_SCALE : 1.0f;
                 float o[4];
                 if (rot && pn == rot_pn) {
@@ -389,9 +437,14 @@ F5_DEVICE void g5_qk_rows(const GemmArgs& p, const float* slab, int m0, int n0, 
         }
     };
     if (rot_pn >= 0) {
+        // rolled like the plain tiles' loop (it was unrolled NT x NPAN; the epilogue's time follows its straight-line code); the factors
+        // sit in a shift register, group t's at the front in round t
+#pragma unroll 1
+        for (int g = wave; g < NG; g += 8) {
+            finish(g, true, cs[0], sn[0]);
 #pragma unroll
-        for (int t = 0; t < NT; t++)
-            if (wave + 8 * t < NG) finish(wave + 8 * t, true, cs[t], sn[t]);
+            for (int t = 0; t + 1 < NT; t++) { cs[t] = cs[t + 1]; sn[t] = sn[t + 1]; }
+        }
     } else {
 #pragma unroll 1
         for (int g = wave; g < NG; g += 8) finish(g, false, make_float2(1.f, 1.f), make_float2(0.f, 0.f));
@@ -527,16 +580,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // Q / K tile (possibly with V blocks behind the K | V boundary): row-major slab, rolled row phase; then the V blocks, if any
         const int f_lo = max(0, 2 * p.D - n0);                     // first V column of this tile (>= BN: none; 0: an all-V tile of a W-direct kernel)
         if (f_lo > 0) {                                            // (workgroup-uniform)
-            if (wave < 4) g5_write_slab<RB, CB, NST, WR, MRB, MCB, true, true>(acc, slab, rb0, nrb, cb0, lane, nullptr);
+            // A tile that straddles K | V (f_lo = 64 or 128 < BN) keeps both slabs at once: its K columns row-major with the compact
+            // stride f_lo + 4, its V columns transposed right behind them (feature f at tslab + f SLDT), so one write pass and one
+            // barrier serve both row phases (it used to write the whole row-major slab, then the V blocks again: three barriers).
+            const bool straddle = f_lo < BN;
+            const int sld = straddle ? f_lo + 4 : C::SLD;
+            float* tslab = slab + 4 * (BM - f_lo);                 // = slab + BM sld - f_lo SLDT
+            g5_qk_rows<RB, CB, NST>(p, slab, sld, m0, n0, wave, lane, [&]() {
+                if (wave < 4) {
+                    if (straddle) g5_write_straddle<RB, CB, NST, WR, MRB, MCB>(acc, slab, tslab, sld, f_lo, rb0, nrb, cb0, lane, p.bias + n0);
+                    else g5_write_slab<RB, CB, NST, WR, MRB, MCB, true, true>(acc, slab, rb0, nrb, cb0, lane, nullptr);
+                }
+            });
+            if (straddle) g5_v_rows<RB, CB, NST>(p, tslab, m0, n0, f_lo, wave, lane);
+        } else {                                                   // all-V tile of a W-direct kernel
+            if (wave < 4) g5_write_slab<RB, CB, NST, WR, MRB, MCB, true, false>(acc, slab, rb0, nrb, cb0, lane, p.bias + n0);
             __syncthreads();                                       // E2
-            g5_qk_rows<RB, CB, NST>(p, slab, m0, n0, wave, lane);
-        }
-        if (f_lo < BN) {                                           // (workgroup-uniform)
-            if (f_lo > 0) __syncthreads();                         // the Q / K rows are done with the slab
-            // column blocks at or behind the boundary (a multiple of 16) go to the transposed slab
-            if (wave < 4) g5_write_slab<RB, CB, NST, WR, MRB, MCB, true, false>(acc, slab, rb0, nrb, cb0, lane, p.bias + n0, max(0, f_lo / 16 - cb0));
-            __syncthreads();
-            g5_v_rows<RB, CB, NST>(p, slab, m0, n0, f_lo, wave, lane);
+            g5_v_rows<RB, CB, NST>(p, slab, m0, n0, 0, wave, lane);
         }
     } else {
         if (wave < 4) g5_write_slab<RB, CB, NST, WR, MRB, MCB, false, false>(acc, slab, rb0, nrb, cb0, lane, p.bias + n0);
@@ -559,7 +619,12 @@ static hipError_t launch_gemm5_t(const GemmArgs& a, int n_pad, hipStream_t st) {
     using C = Gemm5Cfg<RB, CB, NST>;
     // LDS: the ring (A rows only with W-direct) or the epilogue slab that aliases it, whichever is larger
     constexpr int ring = WD ? NST * (C::BM / 8) * 1024 : C::RING;
-    constexpr int lds = ring > C::SLAB ? (ring > C::SLAB_T ? ring : C::SLAB_T) : (C::SLAB > C::SLAB_T ? C::SLAB : C::SLAB_T);
+    constexpr int lds_rt = ring > C::SLAB ? (ring > C::SLAB_T ? ring : C::SLAB_T) : (C::SLAB > C::SLAB_T ? C::SLAB : C::SLAB_T);
+    // QKV tiles that straddle K | V at tile column f_lo (64, 128, ...) hold BM rows of stride f_lo + 4 and the transposed slab's rows
+    // f_lo .. BN - 1 behind them: 4 (BM - f_lo) + BN SLDT floats, largest at f_lo = 64
+    constexpr int slab_kv = (EPI == EPI_QKV && CB > 4) ? (4 * (C::BM - 64) + C::BN * C::SLDT) * 4 : 0;
+    static_assert(!(EPI == EPI_QKV && CB > 4) || C::BM >= C::BN - 64, "straddling tile: the transposed slab would start inside the row-major one");
+    constexpr int lds = lds_rt > slab_kv ? lds_rt : slab_kv;
     static_assert(lds <= 160 * 1024, "tile does not fit the LDS");
     if (WD && (!a.Wf || a.K % 128)) return hipErrorInvalidValue;
     static unsigned attr_mask = 0;
