@@ -544,6 +544,28 @@ int f5hip_wave_encode_tile(int32_t new_freq);
 int f5hip_wave_flac(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, int32_t sample_rate,
                     uint8_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, void* stream);
 
+/* f5hip_wave_flac with a FLAC level per request: byte for byte wave_codec.encode_flac(samples, sample_rate, level[i]).  Not in the reference.
+ *   level                  host int32 [n], each 0 or 1; NULL: all 0, which is f5hip_wave_flac (the same kernels, launches and counters)
+ * Level 0 is the format above.  Level 1 adds LPC subframes to the candidates of every full block of 4096 that is not constant; the short
+ * last block, the headers, the CONSTANT test, coding method 00, partition order 4 and the Rice parameter rule stay.  The candidates in
+ * order are FIXED 0 .. 4, then LPC order 6, 8, 10, 12 (precision 12), made so:
+ *   window     w[i] = (32768 (4095^2 - (2 i - 4095)^2)) / 4095^2 in integers; xw[i] = (x[i] w[i]) >> 15
+ *   autocorr   R[j] = sum_{i >= j} xw[i] xw[i - j], j in 0 .. 12, exact in int64; R[0] == 0: no LPC candidates
+ *   Levinson   fp64, every step one correctly rounded operation in the written order, nothing fused: err = R[0]; for m = 1 .. 12:
+ *              acc = R[m]; acc = acc - a[j] * R[m-1-j] for j = 0 .. m-2; k = acc / err; a'[j] = a[j] - k * a[m-2-j], a'[m-1] = k;
+ *              err = err * (1.0 - k * k); !(err > 0): order m and every higher order are no candidates
+ *   quantise   e = frexp(max |a[j]|)'s exponent (0 for 0), shift = min(11 - e, 15), negative: no candidate; q[j] = clip(rint(a[j] 2^shift),
+ *              -2048, 2047), half to even
+ *   residual   r[i] = x[i] - ((sum_j q[j] x[i-1-j]) >> shift), the sum inside int32; an order with any zigzag u >= 2^21 is no candidate
+ *              (every partition sum then stays below 2^29)
+ *   bits       8 + 16 o + 4 + 5 + 12 o + 2 + 4 + sum over partitions (4 + S_k); the fewest bits win, ties to the earlier candidate, VERBATIM
+ *              only when strictly smaller -- so a level-1 frame is never larger than the level-0 frame and f5hip_wave_flac_bound holds
+ *   on wire    subframe header (0x20 | (o - 1)) << 1, o warm-up samples, 0b1011, the shift in 5 bits, o coefficients of 12 bits, the residual
+ * A call in which no request asks for level 1 launches the level-0 kernel; otherwise one kernel serves both levels, block by block.  Three
+ * launches and no host sync either way.  Refused before the first launch, beside f5hip_wave_flac's list: a level outside {0, 1}. */
+int f5hip_wave_flac_levels(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
+                           int32_t sample_rate, const int32_t* level, uint8_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, void* stream);
+
 /* Upper bound of the bytes of a stream of max_len samples: 42 + 2 max_len + 16 ceil(max_len / 4096) (no frame is larger than its samples as
  * VERBATIM plus 16 bytes); 0 for a negative length. */
 int64_t f5hip_wave_flac_bound(int32_t max_len);

@@ -111,6 +111,8 @@ SYMBOLS = {
                                     C.c_void_p, C.c_void_p]),
     "f5hip_wave_encode_tile": (C.c_int, [C.c_int32]),
     "f5hip_wave_flac": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "f5hip_wave_flac_levels": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "f5hip_wave_flac_bound": (C.c_int64, [C.c_int32]),
     "f5hip_wave_loudness": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_wave_loudness_tile": (C.c_int, []),

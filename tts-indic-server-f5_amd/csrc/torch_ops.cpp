@@ -25,6 +25,7 @@
 //   torch.ops.f5hip.wave_finish_joins(chunks[], chunks_per_request, fade, chunk_fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/infer_cli.py:181-208
 //   torch.ops.f5hip.mel_spectrogram_ragged(waves[], n_fft, hop_length, n_mels, sample_rate, variant) -> Tensor mel [sum T, n_mels]   F/model/modules.py:30-143
 //   torch.ops.f5hip.wave_flac(pcm[], in_off, max_len, len_dev?, sample_rate) -> (Tensor streams uint8, Tensor lengths int32, Tensor offsets int64 host)
+//   torch.ops.f5hip.wave_flac_levels(pcm[], in_off, max_len, len_dev?, sample_rate, level int32 host) -> the same, each request at its FLAC level
 //   torch.ops.f5hip.flac_decode(data, begin, end, info, total, max_samples) -> (Tensor statuses and planes int32, Tensor offsets int64 host)
 //   torch.ops.f5hip.wave_encode(pcm[], in_off, max_len, len_dev?, new_freq, encoding, taps?) -> (Tensor bytes uint8, Tensor lengths int32, Tensor offsets int64 host)
 #include "../../include/f5hip.h"
@@ -395,10 +396,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_encode(at::TensorList pcm, c
 
 // pcm, in_off, max_len, len_dev as wave_encode's, the samples at `sample_rate` already -> (out uint8 device: request i's native FLAC stream at
 // byte out_off[i]; out_len [n] int32 device: its bytes; out_off [n] int64 host)
-std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_flac(at::TensorList pcm, const at::Tensor& in_off, const at::Tensor& max_len,
-                                                         const c10::optional<at::Tensor>& len_dev, int64_t sample_rate) {
+// level: null (all 0, f5hip_wave_flac) or int32 [n] on the host, each 0 or 1 (f5hip_wave_flac_levels)
+static std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_flac_impl(at::TensorList pcm, const at::Tensor& in_off, const at::Tensor& max_len,
+                                                                     const c10::optional<at::Tensor>& len_dev, int64_t sample_rate,
+                                                                     const at::Tensor* level) {
     check_host(in_off, at::kLong, "in_off"); check_host(max_len, at::kInt, "max_len");
     const int64_t n = max_len.numel();
+    if (level) {
+        check_host(*level, at::kInt, "level");
+        TORCH_CHECK(level->dim() == 1 && level->numel() == n, "f5hip::wave_flac_levels: level needs one value per request");
+    }
     TORCH_CHECK(max_len.dim() == 1 && n > 0 && in_off.numel() == n, "f5hip::wave_flac: in_off and max_len need one value per request");
     TORCH_CHECK((int64_t)pcm.size() == 1 || (int64_t)pcm.size() == n, "f5hip::wave_flac: pcm is one tensor or one per request (got ", pcm.size(), " for ", n, ")");
     TORCH_CHECK(sample_rate >= 1 && sample_rate <= INT32_MAX, "f5hip::wave_flac: the sample rate must be positive (got ", sample_rate, ")");
@@ -431,10 +438,24 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_flac(at::TensorList pcm, con
     }
     const c10::DeviceGuard guard(pcm[0].device());   // allocations and stream on the pcm's device
     at::Tensor out = at::empty({bytes}, pcm[0].options().dtype(at::kByte)), out_len = at::empty({n}, pcm[0].options().dtype(at::kInt));
-    const int rc = f5hip_wave_flac((int32_t)n, base, rel.data(), ml, len_dev.has_value() ? len_dev->data_ptr<int32_t>() : (const int32_t*)nullptr,
-                                   (int32_t)sample_rate, out.data_ptr<uint8_t>(), oo, out_len.data_ptr<int32_t>(), stream_of(pcm[0]));
-    TORCH_CHECK(rc == 0, "f5hip_wave_flac: ", f5hip_last_error());
+    const int32_t* ld = len_dev.has_value() ? len_dev->data_ptr<int32_t>() : (const int32_t*)nullptr;
+    const int rc = level ? f5hip_wave_flac_levels((int32_t)n, base, rel.data(), ml, ld, (int32_t)sample_rate, level->data_ptr<int32_t>(),
+                                                  out.data_ptr<uint8_t>(), oo, out_len.data_ptr<int32_t>(), stream_of(pcm[0]))
+                         : f5hip_wave_flac((int32_t)n, base, rel.data(), ml, ld, (int32_t)sample_rate, out.data_ptr<uint8_t>(), oo,
+                                           out_len.data_ptr<int32_t>(), stream_of(pcm[0]));
+    TORCH_CHECK(rc == 0, level ? "f5hip_wave_flac_levels: " : "f5hip_wave_flac: ", f5hip_last_error());
     return {out, out_len, out_off};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_flac(at::TensorList pcm, const at::Tensor& in_off, const at::Tensor& max_len,
+                                                         const c10::optional<at::Tensor>& len_dev, int64_t sample_rate) {
+    return wave_flac_impl(pcm, in_off, max_len, len_dev, sample_rate, nullptr);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_flac_levels(at::TensorList pcm, const at::Tensor& in_off, const at::Tensor& max_len,
+                                                                const c10::optional<at::Tensor>& len_dev, int64_t sample_rate,
+                                                                const at::Tensor& level) {
+    return wave_flac_impl(pcm, in_off, max_len, len_dev, sample_rate, &level);
 }
 
 // data: the packed streams, uint8 on the device; begin, end, total, max_samples [n] int64 host; info [n, 8] int32 host (channels, bits, rate,
@@ -523,6 +544,8 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("mel_spectrogram_ragged(Tensor[] waves, int n_fft, int hop_length, int n_mels, int sample_rate, int variant) -> Tensor", &mel_spectrogram_ragged);
     m.def("wave_encode(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int new_freq, int encoding, Tensor? taps) -> (Tensor, Tensor, Tensor)", &wave_encode);
     m.def("wave_flac(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int sample_rate) -> (Tensor, Tensor, Tensor)", &wave_flac);
+    m.def("wave_flac_levels(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int sample_rate, Tensor level) -> (Tensor, Tensor, Tensor)",
+          &wave_flac_levels);
     m.def("flac_decode(Tensor data, Tensor begin, Tensor end, Tensor info, Tensor total, Tensor max_samples) -> (Tensor, Tensor)", &flac_decode);
     m.def("wave_loudness(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor gain_k) -> Tensor", &wave_loudness);
 }

@@ -564,11 +564,19 @@ int f5hip_wave_encode(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, 
 //                           destination: bytes up to the first 4-byte boundary, 4-byte stores, bytes again.
 // Three launches whatever n (one when every request is empty by its bound), no host sync between them; a request's bytes depend on that
 // request alone.  Vector stores and LDS atomics in plain C++.
+// f5hip_wave_flac_levels: the same with a FLAC level per request (wave_codec.encode_flac(x, rate, level)).  A call with a level-1 request
+// launches wave_flac_frame_kernel<true>, in which the full blocks of such requests try four LPC candidates (flac_lpc_core.h) beside the five
+// fixed orders; every other block of the call, and every call without a level-1 request (<false>: the level-0 code), is as above.  The
+// level-0 candidates are a subset of the level-1 ones and VERBATIM still bounds the choice, so the size contract below holds unchanged.
+#include "flac_lpc_core.h"
+
 struct FlReq {
     long long in_off;    // its first sample, relative to pcm_dev
     long long out_off;   // its stream's first byte (a multiple of 16)
     int cap;             // upper bound of its length (the length itself without len_dev)
     int frame0;          // its first block of the frame and pack launches = its first scratch slot
+    int level;           // 0: fixed predictors; 1: LPC subframes among the candidates of its full blocks (wave_flac_frame_kernel<true>)
+    int pad;
 };
 
 constexpr int kFlBlock = 4096;
@@ -576,6 +584,7 @@ constexpr int kFlHeader = 42;
 constexpr int kFlSlot = 8208;                   // bytes of a scratch slot: header 11 + VERBATIM 1 + 8192 + CRC-16 2 = 8206, up to 16
 constexpr int kFlWords = kFlSlot / 4;
 constexpr int kFlOrders = 5, kFlParams = 15, kFlParts = 16;
+constexpr int kFlVerbatim = 5;                  // a block's kind: -1 CONSTANT, 0 .. 4 the fixed order, 5 VERBATIM, 6 + i LPC of order fl1_order(i)
 constexpr int kFlSlice = 33;                    // CRC-16 slice of a thread: 256 * 33 >= 8204
 // The size contract, in one place: a frame is at most 11 header bytes (2 sync, 2 codes, a frame number below 2^21 in 4, the 16-bit block
 // size, CRC-8), a subframe that is at most VERBATIM (1 + 2 b bytes: the choice rule takes FIXED only when it is no larger) and 2 bytes of
@@ -632,14 +641,49 @@ F5_DEVICE void fl_put(unsigned* w, int pos, unsigned v, int nbits) {
 F5_DEVICE unsigned fl_byte(const unsigned* w, int j) { return (w[j >> 2] >> (24 - 8 * (j & 3))) & 255u; }
 F5_DEVICE int fl_len(const int* len_dev, int r, int cap) { return len_dev ? min(max(len_dev[r], 0), cap) : cap; }
 
+// sum(u >> k) of a partition of 256 for every k: the thread's 16 codes, then one butterfly over the 16 threads that share the partition
+F5_DEVICE void fl_partition_sums(const unsigned* u, int tid, unsigned (*sums)[kFlParts]) {
+#pragma unroll
+    for (int k = 0; k < kFlParams; k++) {
+        unsigned s = 0;
+#pragma unroll
+        for (int e = 0; e < 16; e++) s += u[e] >> k;
+        s += __shfl_xor(s, 8);
+        s += __shfl_xor(s, 4);
+        s += __shfl_xor(s, 2);
+        s += __shfl_xor(s, 1);
+        if ((tid & 15) == 0) sums[k][tid >> 4] = s;
+    }
+}
+
+// the zigzag residuals of the thread's 16 samples under one LPC order: win[12 + e] is sample g0 + e, win[0 .. 11] the twelve before them
+// (zeros in front of the block).  Always twelve taps: q is zero behind the order, so the sum is the order's own.
+F5_DEVICE void fl_lpc_codes(const int* win, int g0, const Fl1Order& L, int order, unsigned* u) {
+    int q[kFl1MaxOrder];
+#pragma unroll
+    for (int j = 0; j < kFl1MaxOrder; j++) q[j] = L.q[j];
+    const int shift = L.shift;
+#pragma unroll
+    for (int e = 0; e < 16; e++) u[e] = g0 + e >= order ? fl1_residual(win + kFl1MaxOrder + e, q, kFl1MaxOrder, shift) : 0u;
+}
+
+// LPC = false is the level-0 encoder.  LPC = true adds, for the full blocks of a request at level 1, the four LPC candidates of
+// flac_lpc_core.h: the windowed samples to LDS, the 13 lags per thread over its 16 samples and an int64 reduction over the block, steps 3 and 4
+// on one lane, then per order the residuals (their maximum for the guard) and the same partition sums as a fixed order.
+template <bool LPC>
 __global__ __launch_bounds__(256) void wave_flac_frame_kernel(const FlReq* __restrict__ reqs, int n, const short* __restrict__ pcm,
                                                               const int* __restrict__ len_dev, int rate_code, unsigned* __restrict__ scratch,
                                                               int* __restrict__ sizes) {
+    constexpr int kCands = LPC ? kFlOrders + kFl1Orders : kFlOrders;   // FIXED 0 .. 4, then LPC 6, 8, 10, 12
     __shared__ short xs[kFlBlock];
     __shared__ __attribute__((aligned(16))) unsigned bitw[kFlWords];
-    __shared__ unsigned sums[kFlOrders][kFlParams][kFlParts];   // sum(u >> k) of the 256 samples of a partition (u = 0 before the order's first residual)
-    __shared__ unsigned best_s[kFlOrders][kFlParts];
-    __shared__ int best_k[kFlOrders][kFlParts];
+    __shared__ unsigned sums[kCands][kFlParams][kFlParts];   // sum(u >> k) of the 256 samples of a partition (u = 0 before the candidate's first residual)
+    __shared__ unsigned best_s[kCands][kFlParts];
+    __shared__ int best_k[kCands][kFlParts];
+    __shared__ short xw[LPC ? kFlBlock : 1];                 // the windowed samples
+    __shared__ unsigned long long lags[kFl1Lags];
+    __shared__ Fl1Order lpc[kFl1Orders];
+    __shared__ unsigned lpc_top[kFl1Orders];                 // the largest zigzag residual of an order, for the guard
     __shared__ int wave_total[4];
     __shared__ unsigned wave_crc[4];
     __shared__ int differs;
@@ -653,6 +697,7 @@ __global__ __launch_bounds__(256) void wave_flac_frame_kernel(const FlReq* __res
     const int b = (int)min((long long)kFlBlock, len - s0);
     const bool full = b == kFlBlock;
     const int parts = full ? kFlParts : 1, orders = min(kFlOrders, b);
+    const bool lpc_on = LPC && full && q.level == 1;
 
     // the thread's 16 samples: two 16-byte loads where the address allows and the block has them all
     const short* x = pcm + q.in_off + s0;
@@ -671,6 +716,14 @@ __global__ __launch_bounds__(256) void wave_flac_frame_kernel(const FlReq* __res
     for (int e = 0; e < 16; e++) xs[g0 + e] = (short)h[4 + e];
     for (int i = tid; i < kFlWords; i += 256) bitw[i] = 0;
     if (tid == 0) differs = 0;
+    if constexpr (LPC) {
+        if (lpc_on) {
+#pragma unroll
+            for (int e = 0; e < 16; e++) xw[g0 + e] = (short)fl1_windowed(h[4 + e], g0 + e);
+            if (tid < kFl1Lags) lags[tid] = 0;
+            if (tid < kFl1Orders) lpc_top[tid] = 0;
+        }
+    }
     __syncthreads();
 #pragma unroll
     for (int e = 0; e < 4; e++) h[e] = g0 + e - 4 >= 0 ? (int)xs[g0 + e - 4] : 0;
@@ -699,26 +752,69 @@ __global__ __launch_bounds__(256) void wave_flac_frame_kernel(const FlReq* __res
                 const int g = g0 + e, res = cur[4 + e];
                 u[e] = g >= o && g < b ? (unsigned)((res << 1) ^ (res >> 31)) : 0u;
             }
+            fl_partition_sums(u, tid, sums[o]);
+        }
+    }
+
+    // level 1: the LPC candidates of a full block
+    int win[kFl1MaxOrder + 16];                                         // win[12 + e] = sample g0 + e (LPC only)
+    if constexpr (LPC) {
+        if (lpc_on) {
+            {
+                int ww[kFl1MaxOrder + 16];
 #pragma unroll
-            for (int k = 0; k < kFlParams; k++) {
-                unsigned s = 0;
+                for (int j = 0; j < kFl1MaxOrder + 16; j++) {
+                    const int g = g0 - kFl1MaxOrder + j;
+                    win[j] = g >= 0 ? (int)xs[g] : 0;
+                    ww[j] = g >= 0 ? (int)xw[g] : 0;
+                }
 #pragma unroll
-                for (int e = 0; e < 16; e++) s += u[e] >> k;
-                s += __shfl_xor(s, 8);
-                s += __shfl_xor(s, 4);
-                s += __shfl_xor(s, 2);
-                s += __shfl_xor(s, 1);
-                if ((tid & 15) == 0) sums[o][k][tid >> 4] = s;
+                for (int j = 0; j < kFl1Lags; j++) {
+                    long long s = 0;
+#pragma unroll
+                    for (int e = 0; e < 16; e++) s += (long long)(ww[kFl1MaxOrder + e] * ww[kFl1MaxOrder + e - j]);   // (a product stays below 2^30)
+#pragma unroll
+                    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+                    if (lane == 0) atomicAdd(&lags[j], (unsigned long long)s);   // (exact integers: any order of summation)
+                }
+            }
+            __syncthreads();
+            if (tid == 0) {
+                long long R[kFl1Lags];
+#pragma unroll
+                for (int j = 0; j < kFl1Lags; j++) R[j] = (long long)lags[j];
+                fl1_levinson(R, lpc);
+            }
+            __syncthreads();
+            for (int c = 0; c < kFl1Orders; c++) {
+                if (!lpc[c].valid) continue;
+                unsigned u[16];
+                fl_lpc_codes(win, g0, lpc[c], fl1_order(c), u);
+                unsigned top = 0;
+#pragma unroll
+                for (int e = 0; e < 16; e++) top = max(top, u[e]);
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) top = max(top, (unsigned)__shfl_xor((int)top, d));
+                if (lane == 0) atomicMax(&lpc_top[c], top);
+                fl_partition_sums(u, tid, sums[kFlOrders + c]);
             }
         }
     }
     __syncthreads();
 
     // the Rice parameter of each (order, partition): the k that minimises S_k = sum(u >> k) + n (1 + k), ties to the smaller k
-    if (tid < kFlOrders * kFlParts) {
-        const int o = tid >> 4, p = tid & 15;
-        if (o < orders && p < parts) {
-            const unsigned cnt = full ? 256u - (p == 0 ? o : 0) : (unsigned)(b - o);
+    if (tid < kCands * kFlParts) {
+        const int o = tid >> 4, p = tid & 15;                             // o: the candidate's slot
+        bool live = o < orders;
+        int warm = o;                                                   // its warm-up samples
+        if constexpr (LPC) {
+            if (o >= kFlOrders) {
+                live = lpc_on && lpc[o - kFlOrders].valid && lpc_top[o - kFlOrders] < kFl1Guard;
+                warm = fl1_order(o - kFlOrders);
+            }
+        }
+        if (live && p < parts) {
+            const unsigned cnt = full ? 256u - (p == 0 ? warm : 0) : (unsigned)(b - o);
             unsigned bs = 0xffffffffu;
             int bk = 0;
             for (int k = 0; k < kFlParams; k++) {
@@ -743,7 +839,18 @@ __global__ __launch_bounds__(256) void wave_flac_frame_kernel(const FlReq* __res
         for (int p = 0; p < parts; p++) bits += 4 + (long long)best_s[o][p];
         if (o == 0 || bits < best_bits) { best_bits = bits; kind = o; }
     }
-    if (8 + 16LL * b < best_bits) kind = 5;
+    if constexpr (LPC) {
+        if (lpc_on) {
+            for (int c = 0; c < kFl1Orders; c++) {
+                if (!lpc[c].valid || lpc_top[c] >= kFl1Guard) continue;
+                const int o = fl1_order(c);
+                long long bits = 8 + 16 * o + 4 + 5 + kFl1Precision * o + 2 + 4;
+                for (int p = 0; p < parts; p++) bits += 4 + (long long)best_s[kFlOrders + c][p];
+                if (bits < best_bits) { best_bits = bits; kind = kFlVerbatim + 1 + c; }
+            }
+        }
+    }
+    if (8 + 16LL * b < best_bits) kind = kFlVerbatim;
     if (!differs) kind = -1;
 
     // the frame header: sync and fixed block size, block-size and rate codes, mono 16 bits, the frame number, b - 1 for a short block, CRC-8
@@ -770,30 +877,38 @@ __global__ __launch_bounds__(256) void wave_flac_frame_kernel(const FlReq* __res
     if (kind == -1) {
         if (tid == 0) fl_put(bitw, base0 + 8, (unsigned)xs[0] & 0xffffu, 16);   // (the subframe header byte is 0)
         nbits = base0 + 24;
-    } else if (kind == 5) {
+    } else if (kind == kFlVerbatim) {
         if (tid == 0) fl_put(bitw, base0, 0x02u, 8);
 #pragma unroll
         for (int e = 0; e < 16; e++)
             if (g0 + e < b) fl_put(bitw, base0 + 8 + 16 * (g0 + e), (unsigned)h[4 + e] & 0xffffu, 16);
         nbits = base0 + 8 + 16 * b;
     } else {
-        const int o = kind, p = full ? tid >> 4 : 0, k = best_k[o][p];
-        int cur[20];
-#pragma unroll
-        for (int j = 0; j < 20; j++) cur[j] = h[j];
-#pragma unroll
-        for (int d = 0; d < kFlOrders - 1; d++) {
-            if (d < o) {
-#pragma unroll
-                for (int j = 19; j >= 1; j--) cur[j] -= cur[j - 1];
-            }
-        }
+        const bool is_lpc = LPC && kind > kFlVerbatim;
+        const int slot = is_lpc ? kind - 1 : kind, o = is_lpc ? fl1_order(kind - kFlVerbatim - 1) : kind;
+        const int extra = is_lpc ? 4 + 5 + kFl1Precision * o : 0;        // precision, shift and coefficients of an LPC subframe
+        const int p = full ? tid >> 4 : 0, k = best_k[slot][p];
         unsigned u[16];
+        if (is_lpc) {
+            if constexpr (LPC) fl_lpc_codes(win, g0, lpc[slot - kFlOrders], o, u);
+        } else {
+            int cur[20];
+#pragma unroll
+            for (int j = 0; j < 20; j++) cur[j] = h[j];
+#pragma unroll
+            for (int d = 0; d < kFlOrders - 1; d++) {
+                if (d < o) {
+#pragma unroll
+                    for (int j = 19; j >= 1; j--) cur[j] -= cur[j - 1];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 16; e++) { const int res = cur[4 + e]; u[e] = (unsigned)((res << 1) ^ (res >> 31)); }
+        }
         int mine = 0;                                                    // bits of the thread's codes
 #pragma unroll
         for (int e = 0; e < 16; e++) {
-            const int g = g0 + e, res = cur[4 + e];
-            u[e] = (unsigned)((res << 1) ^ (res >> 31));
+            const int g = g0 + e;
             if (g >= o && g < b) mine += (int)(u[e] >> k) + 1 + k;
         }
         int incl = mine;                                                 // inclusive scan over the wave, then over the four waves
@@ -806,10 +921,19 @@ __global__ __launch_bounds__(256) void wave_flac_frame_kernel(const FlReq* __res
         __syncthreads();
         int before = incl - mine, total = 0;
         for (int w = 0; w < 4; w++) { if (w < wv) before += wave_total[w]; total += wave_total[w]; }
-        const int base = base0 + 8 + 16 * o + 6;                         // behind the subframe header, the warm-up, coding method 00 and the partition order
+        const int base = base0 + 8 + 16 * o + extra + 6;                 // behind the subframe header, the warm-up, an LPC subframe's fields, coding method 00 and the partition order
         if (tid == 0) {
-            fl_put(bitw, base0, (unsigned)((8 | o) << 1), 8);
+            fl_put(bitw, base0, (unsigned)((is_lpc ? 0x20 | (o - 1) : 8 | o) << 1), 8);
             for (int j = 0; j < o; j++) fl_put(bitw, base0 + 8 + 16 * j, (unsigned)xs[j] & 0xffffu, 16);
+            if constexpr (LPC) {
+                if (is_lpc) {
+                    const int at = base0 + 8 + 16 * o;
+                    fl_put(bitw, at, (unsigned)(kFl1Precision - 1), 4);
+                    fl_put(bitw, at + 4, (unsigned)lpc[slot - kFlOrders].shift & 31u, 5);
+                    for (int j = 0; j < o; j++)
+                        fl_put(bitw, at + 9 + kFl1Precision * j, (unsigned)lpc[slot - kFlOrders].q[j] & ((1u << kFl1Precision) - 1u), kFl1Precision);
+                }
+            }
             if (full) fl_put(bitw, base - 4, 4u, 4);
         }
         if (full ? (tid & 15) == 0 : tid == 0) fl_put(bitw, base + 4 * p + before, (unsigned)k, 4);
@@ -946,6 +1070,11 @@ int64_t f5hip_wave_flac_bound(int32_t max_len) {
 
 int f5hip_wave_flac(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, int32_t sample_rate,
                     uint8_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, void* stream) {
+    return f5hip_wave_flac_levels(n, pcm_dev, in_off, max_len, len_dev, sample_rate, nullptr, out_dev, out_off, out_len_dev, stream);
+}
+
+int f5hip_wave_flac_levels(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
+                           int32_t sample_rate, const int32_t* level, uint8_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, void* stream) {
     if (n < 1 || !pcm_dev || !in_off || !max_len || !out_dev || !out_off || !out_len_dev) return fail(-1, "wave_flac: bad argument");
     const int code = fl_rate_code(sample_rate);
     if (code < 0) return fail(-1, "wave_flac: the sample rate must be one of 8000, 16000, 22050, 24000, 32000, 44100, 48000 (got %d)", sample_rate);
@@ -955,12 +1084,16 @@ int f5hip_wave_flac(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, co
         return fail(-1, "wave_flac: the lengths must be 4-byte aligned");
     std::vector<FlReq> h(n);
     long long total_in = 0, total_out = 0, frames = 0;
+    bool any_lpc = false;
     for (int i = 0; i < n; i++) {
+        const int lv = level ? level[i] : 0;
+        if (lv != 0 && lv != 1) return fail(-1, "wave_flac: the level of request %d must be 0 or 1 (got %d)", i, lv);
+        any_lpc |= lv == 1;
         if (max_len[i] < 0) return fail(-1, "wave_flac: request %d has a negative length bound (%d)", i, max_len[i]);
         if (out_off[i] < 0 || (out_off[i] & 15)) return fail(-1, "wave_flac: the output offset of request %d is not a multiple of 16 bytes", i);
         total_in += max_len[i]; total_out += f5hip_wave_flac_bound(max_len[i]);
         if (total_in > 2147483647LL || total_out > 2147483647LL) return fail(-1, "wave_flac: the call exceeds 2^31 - 1 samples in or bytes out");
-        h[i] = FlReq{in_off[i], out_off[i], max_len[i], (int)frames};
+        h[i] = FlReq{in_off[i], out_off[i], max_len[i], (int)frames, lv, 0};
         frames += ((long long)max_len[i] + kFlBlock - 1) / kFlBlock;
     }
     FlWorkspace* const wsp = device_workspace<FlWorkspace>("wave_flac");
@@ -975,8 +1108,13 @@ int f5hip_wave_flac(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, co
     hipStream_t st = (hipStream_t)stream;
     if (upload_sync(st, ws.reqs, h) != hipSuccess) return fail(-6, "wave_flac metadata upload");
     if (frames) {
-        hipLaunchKernelGGL(wave_flac_frame_kernel, dim3((unsigned)frames), dim3(256), 0, st, ws.reqs, n, (const short*)pcm_dev, (const int*)len_dev, code,
-                           ws.scratch, ws.sizes);
+        // (the level-0 instantiation unless some request asks for level 1)
+        if (any_lpc)
+            hipLaunchKernelGGL(wave_flac_frame_kernel<true>, dim3((unsigned)frames), dim3(256), 0, st, ws.reqs, n, (const short*)pcm_dev,
+                               (const int*)len_dev, code, ws.scratch, ws.sizes);
+        else
+            hipLaunchKernelGGL(wave_flac_frame_kernel<false>, dim3((unsigned)frames), dim3(256), 0, st, ws.reqs, n, (const short*)pcm_dev,
+                               (const int*)len_dev, code, ws.scratch, ws.sizes);
         CKL("wave_flac_frame");
         g_counters[CNT_WAVE_FLAC_LAUNCHES]++;
     }

@@ -34,9 +34,9 @@ from . import wave_codec
 from .audio_prep import preprocess_ref_audio_text, remove_silence_edges, remove_silence_pcm  # noqa: F401  (F/infer/utils_infer.py:263-350)
 from .loaders import DiT, MMDiT, UNetT, load_checkpoint, load_model, load_vocoder  # noqa: F401  (F/infer/utils_infer.py:92-130,175-260)
 from .wave_codec import (ALL_ENCODINGS, FLAC_BLOCK, FLAC_ENCODINGS, FLAC_HEADER_BYTES, MAX_TAP_TABLE_BYTES, OUTPUT_ENCODINGS,  # noqa: F401
-                         OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, StreamFlacEncoder, StreamResampler, decode_flac, decode_g711, deliver_pcm16,
+                         OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, StreamFlacEncoder, StreamResampler, check_flac_level, decode_flac, decode_g711, deliver_pcm16,
                          delivery_format, encode_flac, encode_g711, flac_crc8, flac_crc16, flac_stream_header, load_audio, load_wav, quantise_pcm16, read_flac,
-                         rate_pair, resample_pcm16, resample_sinc_hann, resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
+                         rate_pair, request_flac_level, resample_pcm16, resample_sinc_hann, resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
 from .wave_codec import (LOUDNESS_GATE_ABS, LOUDNESS_PEAK_CEILING, LOUDNESS_RANGE, LOUDNESS_TAPS, check_loudness, loudness_gain,  # noqa: F401
                          loudness_gain_constant, loudness_lufs, loudness_taps, measure_loudness, normalise_loudness_pcm16)
 from .wave_codec import _device_taps, _tap_tables  # noqa: F401  (the two caches: used below, and read as infer._X by the tests that bound them)
@@ -565,7 +565,7 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 # per-request options of `infer_requests` (the fourth element of a request) and of the serving routes
 _PLAIN = (target_sample_rate, "pcm16")   # the delivery format of a request that sets neither `sample_rate` nor `encoding`
 REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "remove_silence", "sample_rate", "encoding",
-                   "loudness")
+                   "loudness", "flac_level")
 WHOLE_WAVE = ("remove_silence, sample_rate and encoding need the request's whole wave: they are not available for a list of chunk texts (a streamed "
               "request, whose owner applies the delivery format piece by piece: StreamResampler, encode_g711) or with join=False")
 WHOLE_WAVE_LOUDNESS = ("loudness is measured on the request's whole wave: it is not available for a list of chunk texts, on a streaming path or "
@@ -601,6 +601,7 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
         raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
     if opts.get("loudness") is not None:
         opts["loudness"] = check_loudness(opts["loudness"])
+    request_flac_level(opts.get("flac_level"), opts.get("encoding"))   # (a level beside another encoding is refused, never ignored)
     if needs_whole_wave(opts) and isinstance(request_text(request), (list, tuple)):
         raise ValueError(whole_wave_message(opts))
     # one (voice, units) part per segment; a plain request is its own single segment
@@ -656,7 +657,8 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     list of chunk texts.  `sample_rate` (one of OUTPUT_SAMPLE_RATES) and `encoding` ("pcm16", "mulaw", "alaw", "flac"), per request: the delivery
     format, a pure function of the request's 24 kHz int16 PCM (`deliver_pcm16`: after silence removal, `resample_pcm16`, then `encode_g711`
     or `encode_flac`); such a request's wave is int16 at that rate, uint8 code bytes or the uint8 bytes of a FLAC stream, its triple names that rate, and like `remove_silence` it needs the whole
-    wave.  `loudness` (LUFS, -40 .. -5, per request): the programme loudness (ITU-R BS.1770-4) the request's 24 kHz int16 PCM is moved to
+    wave.  `flac_level` (0 or 1, per request, only beside `encoding` "flac": ValueError otherwise): at 1 the stream's full blocks may be LPC
+    subframes (`encode_flac(..., level=1)`).  `loudness` (LUFS, -40 .. -5, per request): the programme loudness (ITU-R BS.1770-4) the request's 24 kHz int16 PCM is moved to
     after silence removal and before the delivery format (`normalise_loudness_pcm16`: the sample peak stays at or below -1 dBFS); such a
     request's wave is int16 PCM and it needs the whole wave.  A `ScriptRequest` (a multi-voice script: one segment per piece, each with its own voice) is accepted in place of a tuple: its
     segments' units ride in the same sampler call, one prompt per unit, and the same vocoder call, one group per segment; its triple is
@@ -702,30 +704,32 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     silence = [bool(plan.opts.get("remove_silence")) for plan in plans]
     formats = [delivery_format(plan.opts.get("sample_rate"), plan.opts.get("encoding")) for plan in plans]
     loud = [plan.opts.get("loudness") for plan in plans]
+    levels = [plan.opts.get("flac_level") for plan in plans]
     if finish is not None:
         backend = bool(finish.get("device_backend"))
         got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms, on_device=backend, want_specs=False)
         chunk_waves = [request_chunk_waves(plan, got[per_plan[i]:per_plan[i + 1]]) for i, plan in enumerate(plans)]
         return finish_requests(chunk_waves, [request_text(req) for req in requests], cross_fade_duration, silence, sample_rate=[f[0] for f in formats],
-                               encoding=[f[1] for f in formats], loudness=loud, **finish)
+                               encoding=[f[1] for f in formats], loudness=loud, flac_level=levels, **finish)
     whole = [needs_whole_wave(plan.opts) for plan in plans]
     if any(whole) and not join:
         raise ValueError(whole_wave_message(next(plan.opts for plan, w in zip(plans, whole) if w)))
     out = []
     got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms)
-    for i, (plan, needs, flag, fmt, lufs) in enumerate(zip(plans, whole, silence, formats, loud)):
+    for i, (plan, needs, flag, fmt, lufs, level) in enumerate(zip(plans, whole, silence, formats, loud, levels)):
         mine = got[per_plan[i]:per_plan[i + 1]]
         if plan.script is not None:   # (wave, rate, [spectrogram per segment]) like `infer_multi_voice`; join=False: per-segment lists
             seg_specs = [np.concatenate(specs, axis=1) for _, specs in mine]
             if needs or join:
-                wave, = finish_requests([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1], loudness=lufs)
+                wave, = finish_requests([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1], loudness=lufs,
+                                        flac_level=level)
                 out.append((wave, fmt[0], seg_specs))
             else:
                 out.append(([waves for waves, _ in mine], target_sample_rate, [specs for _, specs in mine]))
             continue
         (waves, specs), = mine
         if needs:
-            wave, = finish_requests([waves], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1], loudness=lufs)
+            wave, = finish_requests([waves], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1], loudness=lufs, flac_level=level)
             out.append((wave, fmt[0], np.concatenate(specs, axis=1)))
         elif join:
             out.append((cross_fade_concat(waves, cross_fade_duration), target_sample_rate, np.concatenate(specs, axis=1)))
@@ -765,7 +769,7 @@ def _per_request(value, n, what):
 
 
 def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cross_fade_duration, remove_silence=None, device_backend=False,
-                    want="float", sample_rate=None, encoding=None, loudness=None):
+                    want="float", sample_rate=None, encoding=None, loudness=None, flac_level=None):
     """From the chunk waves of several requests (rms restored; numpy, or tensors as `_chunk_waves(on_device=True)` leaves them) to what each
     request gets.  A request whose text is a list of chunk texts (a streamed request's head or tail) gets its chunk waves as they are, like
     `request_wave`; a script's (`SegmentedWaves`: one list of chunk waves per segment) as one list per segment.  Any other request gets its
@@ -792,6 +796,8 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     (`backend_stats["flac_calls"]`, `["flac_requests"]`), and two copies come back per rate: the streams' lengths, then the streams, joined
     on the device, in one download of exactly their bytes (`["flac_bytes"]`); on the host, or with a model without the device back-end,
     `encode_flac` makes the same bytes.  Every `wave_encode` / `wave_flac` call of the batch is queued before the first of these copies.
+    `flac_level`: one level (`check_flac_level`: 0, or 1 for LPC subframes) or one per request, None for level 0; only a "flac" request may
+    name one (ValueError otherwise).  The requests of a rate still share ONE `ops.wave_flac` call, whatever their levels.
 
     `loudness`: one target in LUFS (`check_loudness`) or one per request, None for a request that keeps its level.  Such a request's int16
     PCM (quantised whatever `want` says, after silence removal) goes through `normalise_loudness_pcm16` before the delivery format.  With
@@ -808,6 +814,7 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
         raise ValueError("finish_requests: one text and one remove_silence flag per request")
     formats = [delivery_format(r, e) for r, e in zip(_per_request(sample_rate, n, "sample_rate"), _per_request(encoding, n, "encoding"))]
     loud = [check_loudness(v) for v in _per_request(loudness, n, "loudness")]
+    levels = [request_flac_level(v, fmt[1]) for v, fmt in zip(_per_request(flac_level, n, "flac_level"), formats)]
     fade = int(cross_fade_duration * target_sample_rate) if cross_fade_duration > 0 else 0
     out, on_device = [None] * n, []
     for i, (waves, text) in enumerate(zip(chunk_waves_per_request, gen_texts)):
@@ -824,13 +831,13 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
             on_device.append(i)
             continue
         else:
-            out[i] = _finish_on_host(waves, text, cross_fade_duration, flags[i], formats[i], want, loud[i])
+            out[i] = _finish_on_host(waves, text, cross_fade_duration, flags[i], formats[i], want, loud[i], levels[i])
         backend_stats["host_requests"] += 1
     if on_device:
         # the plain requests first: their PCM is then one prefix of the packed buffer, and what comes down of it holds no other request's
         on_device.sort(key=lambda i: formats[i] != _PLAIN)
         done = _finish_on_device([_device_request(chunk_waves_per_request[i]) for i in on_device], fade, [flags[i] for i in on_device],
-                                 [formats[i] for i in on_device], [loud[i] for i in on_device])
+                                 [formats[i] for i in on_device], [loud[i] for i in on_device], [levels[i] for i in on_device])
         for i, wave in zip(on_device, done):
             out[i] = wave
     return out
@@ -860,7 +867,7 @@ def _device_request(waves):
     return chunks, fades
 
 
-def _finish_on_host(waves, text, cross_fade_duration, flag, fmt, want, loudness=None):
+def _finish_on_host(waves, text, cross_fade_duration, flag, fmt, want, loudness=None, flac_level=0):
     """`finish_requests` for one request on the host: join, quantisation, silence removal, the loudness target and the delivery format in
     numpy."""
     if isinstance(waves, SegmentedWaves):
@@ -873,16 +880,18 @@ def _finish_on_host(waves, text, cross_fade_duration, flag, fmt, want, loudness=
         wave = quantise_pcm16(wave)
     if loudness is not None:
         wave = normalise_loudness_pcm16(wave, loudness)
-    return wave if fmt == _PLAIN else deliver_pcm16(wave, *fmt)
+    return wave if fmt == _PLAIN else deliver_pcm16(wave, *fmt, flac_level=flac_level if fmt[1] in FLAC_ENCODINGS else None)
 
 
-def _finish_on_device(requests, fade, silence, formats, loudness=None):
+def _finish_on_device(requests, fade, silence, formats, loudness=None, flac_levels=None):
     """`finish_requests` for the requests the device back-end takes: `requests` = (chunk waves (device tensors), fades: `_device_request`), the
     plain-format ones first; `silence`, `formats` per request.  ONE `ops.wave_finish` call -- `ops.wave_finish_joins` when a script is among
     them -- then one `ops.wave_encode` call per distinct delivery format behind it on the same stream, and for the "flac" requests one
     `ops.wave_flac` call per distinct rate (behind a `wave_encode(..., "pcm16")` call where the rate is not 24 kHz).  `loudness`: a target per
     request or None; when any is set, ONE `ops.wave_loudness` call normalises those requests in place directly behind `wave_finish`, before
-    anything else is queued.  Returns one result per request."""
+    anything else is queued.  `flac_levels`: a FLAC level per request or None (all 0); the "flac" requests of a rate share their one call
+    through `ops.wave_flac`'s per-request levels, and a call in which no request asks for level 1 is the level-0 call.  Returns one
+    result per request."""
     from . import ops
     out = [None] * len(requests)
     plain = sum(fmt == _PLAIN for fmt in formats)
@@ -931,7 +940,8 @@ def _finish_on_device(requests, fade, silence, formats, loudness=None):
             bounds = [resampled_length(joined[k], target_sample_rate, rate) for k in ks]
             backend_stats["encode_calls"] += 1
             backend_stats["encode_requests"] += len(ks)
-        queued_flac.append((ks,) + tuple(ops.wave_flac(src, src_off, bounds, sel, rate)))
+        level = [flac_levels[k] for k in ks] if flac_levels is not None and any(flac_levels[k] for k in ks) else None
+        queued_flac.append((ks,) + tuple(ops.wave_flac(src, src_off, bounds, sel, rate, level=level)))
         backend_stats["flac_calls"] += 1
         backend_stats["flac_requests"] += len(ks)
     for (rate, enc), ks in groups.items():   # one call per delivery format, behind wave_finish on the same stream
@@ -978,6 +988,7 @@ class SpanTicket:
         self.parts = parts if parts is not None else [(voice, units)]   # [(voice, its units)]: one per segment of a script
         self.script = script
         self.sample_rate, self.encoding = delivery_format(opts.get("sample_rate"), opts.get("encoding"))
+        self.flac_level = opts.get("flac_level")
         self.loudness = check_loudness(opts.get("loudness"))
         self.in_flight = self.cancelled = self.done = False
         self.result = None
@@ -1078,7 +1089,7 @@ class SpanScheduler:
         chunk_waves = [request_chunk_waves(t, got[first[i]:first[i + 1]]) for i, t in enumerate(tickets)]
         results = finish_requests(chunk_waves, [request_text(t.request) for t in tickets], self.cross_fade_duration, [t.remove_silence for t in tickets],
                                   device_backend=self.device_backend, want="pcm16" if self.device_backend else "float",
-                                  sample_rate=[t.sample_rate for t in tickets], encoding=[t.encoding for t in tickets],
+                                  sample_rate=[t.sample_rate for t in tickets], encoding=[t.encoding for t in tickets], flac_level=[t.flac_level for t in tickets],
                                   loudness=[t.loudness for t in tickets])
         for t, result in zip(tickets, results):
             t.result, t.done, t.in_flight = result, True, False

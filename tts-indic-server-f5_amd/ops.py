@@ -500,18 +500,26 @@ def wave_encode(pcm, in_off, max_len, len_dev, sample_rate, encoding, taps=None)
     return data, out_len, out_off.tolist()
 
 
-def wave_flac(pcm, in_off, max_len, len_dev, sample_rate):
+def wave_flac(pcm, in_off, max_len, len_dev, sample_rate, level=None):
     """The FLAC streams of several finished requests in ONE library call and at most three launches (include/f5hip.h f5hip_wave_flac): their
     int16 PCM at `sample_rate`, on the device -> each request's complete native FLAC stream.  `pcm`, `in_off`, `max_len`, `len_dev` as in
     `wave_encode`: `wave_finish`'s packed PCM and device lengths at 24 kHz, or `wave_encode(..., "pcm16")`'s data viewed as int16 (offsets in
     samples) and its `out_len` at another rate.  Returns (data uint8 device, out_len int32 device [n], offsets): request i's stream is
-    data[offsets[i] : offsets[i] + out_len[i]], byte for byte `infer.encode_flac` of its samples."""
+    data[offsets[i] : offsets[i] + out_len[i]], byte for byte `infer.encode_flac` of its samples.  `level`: None (level 0, the entry point
+    f5hip_wave_flac), or the FLAC level (`wave_codec.check_flac_level`) of every request as one int or one int per request
+    (f5hip_wave_flac_levels: LPC subframes for the requests at level 1, the same three launches)."""
     tensors = [pcm] if torch.is_tensor(pcm) else list(pcm)
     io = np.ascontiguousarray(np.asarray(in_off, dtype=np.int64))
     ml = np.ascontiguousarray(np.asarray(max_len, dtype=np.int32))
     n, rate = len(ml), int(sample_rate)
     if n < 1 or len(io) != n or len(tensors) not in (1, n):
         raise _lib.F5HipError("wave_flac: one offset and one length bound per request; pcm is one tensor or one per request")
+    lv = None
+    if level is not None:
+        given = [level] * n if isinstance(level, (int, np.integer)) else list(level)
+        if len(given) != n or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in (0, 1) for v in given):
+            raise _lib.F5HipError(f"wave_flac: level is 0 or 1, one int or one per request (got {level!r} for {n} requests)")
+        lv = np.ascontiguousarray(np.asarray(given, dtype=np.int32))
     for t in tensors:
         if not (torch.is_tensor(t) and t.dtype == torch.int16 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.device == tensors[0].device):
             raise _lib.F5HipError("wave_flac: pcm must be contiguous 1-D int16 tensors on one device")
@@ -522,7 +530,11 @@ def wave_flac(pcm, in_off, max_len, len_dev, sample_rate):
         len_dev = len_dev.contiguous()
     if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
         try:
-            data, out_len, out_off = torch_ops.ops().wave_flac(tensors, torch.from_numpy(io), torch.from_numpy(ml), len_dev, rate)
+            if lv is None:
+                data, out_len, out_off = torch_ops.ops().wave_flac(tensors, torch.from_numpy(io), torch.from_numpy(ml), len_dev, rate)
+            else:
+                data, out_len, out_off = torch_ops.ops().wave_flac_levels(tensors, torch.from_numpy(io), torch.from_numpy(ml), len_dev, rate,
+                                                                          torch.from_numpy(lv))
         except RuntimeError as e:   # c10::Error from the operator's checks or the library
             raise _lib.F5HipError(str(e)) from e
         return data, out_len, out_off.tolist()
@@ -542,8 +554,12 @@ def wave_flac(pcm, in_off, max_len, len_dev, sample_rate):
     with torch.cuda.device(dev):
         data = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         out_len = torch.empty(n, device=dev, dtype=torch.int32)
-        _lib.check(_lib.lib().f5hip_wave_flac(n, C.c_void_p(base), _p(rel), _p(ml), _p(len_dev), rate, _p(data), _p(out_off), _p(out_len),
-                                              _lib.current_stream_ptr()), "f5hip_wave_flac")
+        if lv is None:
+            _lib.check(_lib.lib().f5hip_wave_flac(n, C.c_void_p(base), _p(rel), _p(ml), _p(len_dev), rate, _p(data), _p(out_off), _p(out_len),
+                                                  _lib.current_stream_ptr()), "f5hip_wave_flac")
+        else:
+            _lib.check(_lib.lib().f5hip_wave_flac_levels(n, C.c_void_p(base), _p(rel), _p(ml), _p(len_dev), rate, _p(lv), _p(data), _p(out_off),
+                                                         _p(out_len), _lib.current_stream_ptr()), "f5hip_wave_flac_levels")
     return data, out_len, out_off.tolist()
 
 

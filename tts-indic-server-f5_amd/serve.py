@@ -34,6 +34,7 @@ import queue
 import threading
 import time
 import types
+import typing
 from concurrent.futures import Future
 from dataclasses import dataclass, field
 from typing import Callable
@@ -47,7 +48,7 @@ from .wave_codec import delivery_bytes, pcm16, wav_bytes, wav_stream_header  # n
 
 log = logging.getLogger(__name__)
 
-EDIT_OPTIONS = ("nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method")   # a speech edit has no `speed`: its durations are planned
+EDIT_OPTIONS = ("nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "flac_level")   # a speech edit has no `speed`: its durations are planned
 # most ODE steps one library call accepts per method: 128 time points (f5hip precompute_time); midpoint uses 2 per step, RK4 3 per step + 1
 MAX_NFE_STEP = {"euler": 128, "midpoint": 64, "rk4": 42}
 
@@ -59,7 +60,9 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
     is the model's solver: `nfe_step`'s upper limit follows the request's own `ode_method` when it sets one, else the model's.
     `remove_silence` a bool (False is dropped like None: the request is then what it is without the option).  `sample_rate` an integer in
     `infer.OUTPUT_SAMPLE_RATES`, `encoding` one of `infer.OUTPUT_ENCODINGS` or "flac" (`infer.FLAC_ENCODINGS`); 24000 and "pcm16", what a
-    request gets anyway, are dropped too.  `loudness` a finite number of LUFS within `infer.LOUDNESS_RANGE` (`infer.check_loudness`), not a bool."""
+    request gets anyway, are dropped too.  `loudness` a finite number of LUFS within `infer.LOUDNESS_RANGE` (`infer.check_loudness`), not a bool.
+    `flac_level` the int 0 or 1 (`infer.check_flac_level`; not a bool, not "1"), and only beside `encoding` "flac": with any other encoding
+    it is refused, never ignored; 0, what a FLAC request gets anyway, is then dropped."""
     out = {}
     own = options.get("ode_method") if "ode_method" in allowed else None
     if own is not None:
@@ -86,6 +89,8 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
                 continue
         elif k == "loudness":
             v = infer.check_loudness(v)                 # ValueError: "loudness must be ..."
+        elif k == "flac_level":
+            v = infer.check_flac_level(v)               # ValueError: "flac_level must be one of ..."
         elif k in ("nfe_step", "seed"):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"{k} must be an integer (got {v!r})")
@@ -105,6 +110,10 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
             if k == "speed" and v <= 0:
                 raise ValueError(f"speed must be greater than 0 (got {v}).")
         out[k] = v
+    if "flac_level" in out:
+        infer.request_flac_level(out["flac_level"], out.get("encoding"))   # ValueError: "flac_level needs encoding 'flac' ..."
+        if out["flac_level"] == 0:
+            del out["flac_level"]
     return out
 
 
@@ -650,7 +659,8 @@ class TTSManager:
         `infer.OUTPUT_SAMPLE_RATES`) and `encoding` ("pcm16", "mulaw", "alaw", "flac"): the delivery format, `infer.deliver_pcm16` of the
         request's 24 kHz int16 PCM -- int16 at that rate, uint8 G.711 code bytes, or with "flac" a uint8 array that holds the lossless FLAC
         stream of the samples at that rate (`infer.encode_flac`) -- computed on the device with `device_backend`, the same bytes either way;
-        24000 and "pcm16" (or None) change nothing.  `loudness` (LUFS, -40 .. -5): the result is int16 PCM moved to that programme
+        24000 and "pcm16" (or None) change nothing.  `flac_level` (0 or 1, only beside "flac"): 1 adds LPC subframes to the stream's
+        candidates (`infer.encode_flac(..., level=1)`: never larger, the same samples).  `loudness` (LUFS, -40 .. -5): the result is int16 PCM moved to that programme
         loudness (ITU-R BS.1770-4; `infer.normalise_loudness_pcm16`, sample peak at most -1 dBFS) after silence removal and before the
         delivery format -- in the batch's one `ops.wave_loudness` call with `device_backend`, the same bytes either way."""
         if not self.model:
@@ -677,11 +687,13 @@ class TTSManager:
     def _stream(self, voice, ref_text, head, tail, opts=None):
         opts = dict(opts or {})               # the delivery format is applied here, piece by piece: the head and tail requests stay plain
         fmt = infer.delivery_format(opts.pop("sample_rate", None), opts.pop("encoding", None))
-        return self._stream_requests(self._request(voice, ref_text, head, opts), self._request(voice, ref_text, tail, opts) if tail else None, fmt)
+        level = infer.request_flac_level(opts.pop("flac_level", None), fmt[1])
+        return self._stream_requests(self._request(voice, ref_text, head, opts), self._request(voice, ref_text, tail, opts) if tail else None, fmt,
+                                     flac_level=level)
 
-    def _stream_requests(self, head_request, tail_request, fmt, tail_pieces=None):
+    def _stream_requests(self, head_request, tail_request, fmt, tail_pieces=None, flac_level=0):
         """A stream of two requests: the head's chunk waves, then (unless None) the tail's, through one `infer.StreamJoiner` and the delivery
-        format `fmt`.  `tail_pieces(joiner, result)`: the pieces the tail's result releases (default: its chunk waves pushed in order; a
+        format `fmt` (a FLAC stream at `flac_level`).  `tail_pieces(joiner, result)`: the pieces the tail's result releases (default: its chunk waves pushed in order; a
         script cuts the joiner between its segments)."""
         lock, state = threading.Lock(), {"closed": False, "tail": None, "error": None}
         started = threading.Event()
@@ -731,7 +743,7 @@ class TTSManager:
 
         def delivered():
             resampler = infer.StreamResampler(fmt[0])
-            flac = infer.StreamFlacEncoder(fmt[0]) if fmt[1] in infer.FLAC_ENCODINGS else None
+            flac = infer.StreamFlacEncoder(fmt[0], flac_level) if fmt[1] in infer.FLAC_ENCODINGS else None
             if flac is not None:                  # uint8 pieces: the frames each piece completes
                 encode = lambda pcm: np.frombuffer(flac.feed(pcm), dtype=np.uint8)   # noqa: E731
             else:
@@ -830,6 +842,7 @@ class TTSManager:
         if "seed" in opts:
             opts["generator"] = infer.request_generator(opts.pop("seed"))
         fmt = infer.delivery_format(opts.pop("sample_rate", None), opts.pop("encoding", None))
+        level = infer.request_flac_level(opts.pop("flac_level", None), fmt[1])
         chunked = [(voice, ref_text, infer.request_chunks(ref_text, voice.seconds, piece), speed) for voice, ref_text, piece, speed in segments]
         voice, ref_text, chunks, speed = chunked[0]
         head = self._request(voice, ref_text, chunks[:1], dict(opts, speed=speed) if speed is not None else opts)
@@ -845,21 +858,21 @@ class TTSManager:
                         yield from joiner.pieces([np.zeros(gap_samples, dtype=np.float32)], cut=True)
                 yield from joiner.pieces(waves)
 
-        return self._stream_requests(head, infer.ScriptRequest(rest, opts, gap) if rest else None, fmt, tail_pieces)
+        return self._stream_requests(head, infer.ScriptRequest(rest, opts, gap) if rest else None, fmt, tail_pieces, flac_level=level)
 
     def edit(self, audio, target_text, parts_to_edit, fix_duration=None, *, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
-             seed=None, ode_method=None, sample_rate=None, encoding=None, loudness=None):
+             seed=None, ode_method=None, sample_rate=None, encoding=None, loudness=None, flac_level=None):
         """Speech editing (`infer.speech_edit`, F/infer/speech_edit.py): regenerate `parts_to_edit` of the recording `audio` (a path, WAV
         bytes or a (tensor, sr) pair) so that it speaks `target_text`, with this manager's sampler settings unless the call sets its own
         (`seed`: the edit's noise from its own generator; `ode_method`: the edit's solver, handed on only when set).  The host preparation runs outside the device lock, the sampler and vocoder
         under it (not through the micro-batcher); with a `ShardedSampler` on rank 0's own model.  Returns the wave (float32, 24 kHz) -- with
         `sample_rate` / `encoding`, `infer.deliver_pcm16` of its int16 PCM (host functions); with `loudness` (LUFS), that PCM first goes through
-        `infer.normalise_loudness_pcm16` and the result is int16."""
+        `infer.normalise_loudness_pcm16` and the result is int16.  `flac_level` (0 or 1, only beside `encoding` "flac"): the FLAC stream's level."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = dict(self.opts, **self.request_options(EDIT_OPTIONS, nfe_step=nfe_step, cfg_strength=cfg_strength,
                                                       sway_sampling_coef=sway_sampling_coef, seed=seed, ode_method=ode_method))
-        fmt = self.request_options(("sample_rate", "encoding"), sample_rate=sample_rate, encoding=encoding)
+        fmt = self.request_options(("sample_rate", "encoding", "flac_level"), sample_rate=sample_rate, encoding=encoding, flac_level=flac_level)
         loudness = self.request_options(("loudness",), loudness=loudness).get("loudness")
         model_obj = getattr(self.model_obj, "local", self.model_obj)
         # host work (read, mono mix, resample, plan, tokens) and every rejection happen before the device lock is taken (a FLAC recording is
@@ -878,7 +891,7 @@ class TTSManager:
         if loudness is None and not fmt:
             return wave
         pcm = infer.normalise_loudness_pcm16(infer.quantise_pcm16(wave), loudness)       # (None: the PCM as it is)
-        return infer.deliver_pcm16(pcm, fmt.get("sample_rate"), fmt.get("encoding")) if fmt else pcm
+        return infer.deliver_pcm16(pcm, fmt.get("sample_rate"), fmt.get("encoding"), fmt.get("flac_level")) if fmt else pcm
 
 
 class HTTPError(Exception):
@@ -964,6 +977,7 @@ def request_models():
         sample_rate: int | None = None               # the delivery format (infer.deliver_pcm16); None = 24 kHz 16-bit PCM in a WAV
         encoding: str | None = None
         loudness: float | None = None                # programme loudness target in LUFS (infer.normalise_loudness_pcm16); None = the level as synthesized
+        flac_level: typing.Any = None                # 0 or 1 beside encoding "flac" (infer.check_flac_level); untyped, so that true and "1" arrive as sent and are refused
         response_format: str | None = None
 
     class SpeechFields(SamplerFields):               # what the three speech routes take on top: with SamplerFields, every infer.REQUEST_OPTIONS name
@@ -1026,6 +1040,8 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     for the headerless samples / code bytes as `audio/pcm`); streamed or not, the body's samples are the same bytes.  `encoding: "flac"` is
     its own container: the body is the native FLAC stream of the samples (`infer.encode_flac`, lossless) as `audio/flac` with a `.flac` file
     name, and `response_format` must be absent (400 with "wav" or "pcm" beside it); streamed, the stream header comes with the totals unknown.
+    `flac_level` (the integer 0 or 1, every route; absent means 0): at 1 the FLAC stream's full blocks may be LPC subframes, which makes it
+    smaller and never larger and decodes to the same samples; anything else, and a `flac_level` beside an `encoding` that is not "flac", is a 400.
     `loudness` (a number of LUFS from -40 to -5, every route): the body's samples are moved to that programme loudness (ITU-R BS.1770-4) with
     the sample peak at most -1 dBFS, after silence removal and before the delivery format; it is measured on the whole wave, so it is a 400
     together with `"stream": true` (`STREAM_LOUDNESS`)."""

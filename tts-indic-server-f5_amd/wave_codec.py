@@ -362,13 +362,15 @@ def delivery_format(sample_rate=None, encoding=None):
     return int(rate), enc
 
 
-def deliver_pcm16(pcm, sample_rate=None, encoding=None) -> np.ndarray:
+def deliver_pcm16(pcm, sample_rate=None, encoding=None, flac_level=None) -> np.ndarray:
     """The delivery format of a request's canonical result, its 24 kHz int16 PCM: `resample_pcm16`, then `encode_g711` or `encode_flac` --
-    int16 at `sample_rate`, uint8 code bytes, or a uint8 array that holds the FLAC stream.  (24000, "pcm16") returns the PCM itself."""
+    int16 at `sample_rate`, uint8 code bytes, or a uint8 array that holds the FLAC stream (at `flac_level`, which only a FLAC request may
+    name).  (24000, "pcm16") returns the PCM itself."""
     rate, enc = delivery_format(sample_rate, encoding)
+    level = request_flac_level(flac_level, enc)
     pcm = resample_pcm16(pcm, rate)
     if enc in FLAC_ENCODINGS:
-        return encode_flac(pcm, rate)
+        return encode_flac(pcm, rate, level)
     return pcm if enc == "pcm16" else encode_g711(pcm, enc)
 
 
@@ -577,11 +579,54 @@ def wav_stream_header(sample_rate: int = SAMPLE_RATE, encoding: str = "pcm16") -
 #   residual  coding method 00 (4-bit Rice parameters), never the escape code; a full block has partition order 4 (16 partitions of 256, the
 #             first with 256 - o residuals), the short last block partition order 0; per partition k in 0..14 minimises S_k = sum(u >> k) +
 #             n (1 + k) (ties: the smaller k), u = 2 r for r >= 0 and -2 r - 1 otherwise; a code is u >> k zero bits, a one, the low k bits
+#
+# Level 1 (`encode_flac(pcm, rate, level=1)`, a request's `flac_level`) adds LPC subframes to the candidates of every FULL block that is not
+# constant; everything else above -- stream and frame headers, the CONSTANT test, the short last block (level-0 rule only), coding method 00,
+# partition order 4, the Rice parameter rule -- stays.  The candidates in order: FIXED 0, 1, 2, 3, 4, then LPC order 6, 8, 10, 12, made so
+# (csrc/flac_lpc_core.h is the same text for the kernel and for tools/flac_lpc_check.cpp):
+#   window    w[i] = (32768 (4095^2 - (2 i - 4095)^2)) // 4095^2, a Welch window in integers; xw[i] = (x[i] w[i]) >> 15 (arithmetic)
+#   autocorr  R[j] = sum_{i >= j} xw[i] xw[i - j], j in 0..12, exact integers (below 2^43); R[0] == 0: no LPC candidates
+#   Levinson  in fp64, every step ONE correctly rounded operation in this order, no fused multiply-add, no reassociation:
+#             err = double(R[0]); for m = 1..12: acc = double(R[m]); for j = 0..m-2: acc = acc - a[j] * double(R[m-1-j]); k = acc / err;
+#             a'[j] = a[j] - k * a[m-2-j] for j < m-1, a'[m-1] = k; err = err * (1.0 - k * k); if not err > 0.0, order m and every higher
+#             order are no candidates.  Order m's coefficients are a[0..m-1] after step m; a[0] multiplies the most recent sample
+#   quantise  12 bits: cmax = max |a[j]|, e = frexp(cmax)'s exponent (0 for cmax = 0), shift = min(11 - e, 15), shift < 0: no candidate;
+#             q[j] = clip(rint(a[j] 2^shift), -2048, 2047), rint to even, the scaling exact.  (An order with a coefficient that is not finite is no
+#             candidate.  It cannot be reached -- err > 0 keeps |k| < 1 -- and is decided here so that both sides agree.)
+#   residual  r[i] = x[i] - ((sum_j q[j] x[i-1-j]) >> shift), i >= o, arithmetic shift; the sum stays below 12 2048 32768 < 2^31.  GUARD: an
+#             order with any zigzag u >= 2^21 is no candidate, which keeps every partition sum sum(u >> k) below 2^29 (exact in 32 bits)
+#   bits      8 + 16 o + 4 + 5 + 12 o + 2 + 4 + sum over partitions (4 + S_k), the first partition with 256 - o residuals
+#   choice    the fewest bits, ties to the earlier candidate of the list; VERBATIM only when strictly smaller, CONSTANT as before -- so a
+#             level-1 frame is never larger than the level-0 frame of the same block
+#   on wire   subframe header byte (0x20 | (o - 1)) << 1, o warm-up samples of 16 bits, 0b1011 (precision - 1), the shift in 5 signed bits,
+#             o coefficients of 12 signed bits (q[0] first), then the residual section exactly as in a FIXED subframe
 FLAC_BLOCK = 4096
 FLAC_HEADER_BYTES = 42
 FLAC_RATE_CODES = {8000: 4, 16000: 5, 22050: 6, 24000: 7, 32000: 8, 44100: 9, 48000: 10}
+FLAC_LEVELS = (0, 1)
+FLAC_LPC_ORDERS = (6, 8, 10, 12)
+FLAC_LPC_PRECISION = 12
+FLAC_LPC_GUARD = 1 << 21
 _FLAC_MAX_K = 14
 _FLAC_PARTITION_ORDER = 4
+_FLAC_VERBATIM = 5                                # `_flac_plan`'s kinds: -1 CONSTANT, 0..4 FIXED, 5 VERBATIM, 6 + i LPC of FLAC_LPC_ORDERS[i]
+
+
+def check_flac_level(level) -> int:
+    """A FLAC level as an int: 0 or 1, not a bool; None is 0."""
+    if level is None:
+        return 0
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or int(level) not in FLAC_LEVELS:
+        raise ValueError(f"flac_level must be one of {list(FLAC_LEVELS)} (got {level!r})")
+    return int(level)
+
+
+def request_flac_level(flac_level, encoding) -> int:
+    """`check_flac_level` for a request: a level beside an encoding that is not FLAC is refused, never ignored."""
+    level = check_flac_level(flac_level)
+    if flac_level is not None and (encoding if encoding is not None else "pcm16") not in FLAC_ENCODINGS:
+        raise ValueError(f"flac_level needs encoding 'flac' (got flac_level {flac_level!r} with encoding {encoding!r})")
+    return level
 
 
 def _crc_table(poly, bits):
@@ -638,40 +683,128 @@ def flac_stream_header(sample_rate, total=0, min_frame=0, max_frame=0) -> bytes:
     return b"fLaC" + bytes([0x80]) + len(info).to_bytes(3, "big") + info
 
 
-def _flac_plan(x):
-    """The choice rule on blocks x int64 [F, b] of one size: (kind [F]: -1 CONSTANT, 0..4 the fixed order, 5 VERBATIM; ks [F, P]: the chosen
-    order's Rice parameters; us: per order the zigzag residuals [F, b - o]).  About 75 passes over the blocks: 5 orders x 15 parameters."""
+def _flac_rice(u, o, parts, plen):
+    """(ks [F, parts], S [F, parts]) of zigzag residuals u [F, b - o]: per partition the parameter that minimises S_k, and that minimum."""
+    F = u.shape[0]
+    padded = np.concatenate([np.zeros((F, o), dtype=np.int64), u], axis=1).reshape(F, parts, plen)       # (a zero adds nothing to sum(u >> k))
+    n = np.full(parts, plen, dtype=np.int64)
+    n[0] -= o
+    s = np.stack([(padded >> k).sum(axis=2) + n * (1 + k) for k in range(_FLAC_MAX_K + 1)])            # [15, F, parts]
+    return s.argmin(axis=0), s.min(axis=0)                                                              # (the first minimum: the smaller k)
+
+
+def flac_lpc_window() -> np.ndarray:
+    """The level-1 window, int64 [4096]: a Welch window at 2^15 in integers."""
+    i = np.arange(FLAC_BLOCK, dtype=np.int64)
+    m = FLAC_BLOCK - 1
+    return (32768 * (m * m - (2 * i - m) ** 2)) // (m * m)
+
+
+def flac_lpc_autocorrelation(x) -> np.ndarray:
+    """R int64 [F, 13] of full blocks x int64 [F, 4096]: the windowed autocorrelation, exact."""
+    xw = (x * flac_lpc_window()) >> 15
+    return np.stack([(xw[:, j:] * xw[:, :FLAC_BLOCK - j]).sum(axis=1) for j in range(FLAC_LPC_ORDERS[-1] + 1)], axis=1)
+
+
+def flac_lpc_coefficients(R):
+    """{order: (q, shift)} of one block's autocorrelation R (13 ints): Levinson-Durbin and the quantisation of the level-1 rule, for the
+    orders that are candidates so far.  Scalar float64 arithmetic in a plain loop: one rounding per operation, in the written order."""
+    out = {}
+    R = [int(v) for v in R]
+    if R[0] == 0:
+        return out
+    Rf = [float(v) for v in R]
+    err, a = Rf[0], []
+    for m in range(1, FLAC_LPC_ORDERS[-1] + 1):
+        acc = Rf[m]
+        for j in range(m - 1):
+            acc = acc - a[j] * Rf[m - 1 - j]
+        k = acc / err
+        a = [a[j] - k * a[m - 2 - j] for j in range(m - 1)] + [k]
+        err = err * (1.0 - k * k)
+        if not err > 0.0:
+            break
+        if m in FLAC_LPC_ORDERS:
+            if not all(math.isfinite(v) for v in a):
+                continue
+            cmax = max(abs(v) for v in a)
+            shift = min(FLAC_LPC_PRECISION - 1 - math.frexp(cmax)[1], 15)
+            if shift < 0:
+                continue
+            lim = 1 << (FLAC_LPC_PRECISION - 1)
+            out[m] = ([min(max(int(round(math.ldexp(v, shift))), -lim), lim - 1) for v in a], shift)      # (round: half to even)
+    return out
+
+
+def flac_lpc_residual(x, q, shift):
+    """The zigzag residuals u int64 [F, 4096 - o] of blocks x int64 [F, 4096] under per-block coefficients q int64 [F, o] and shifts [F], and
+    the guard per block: False where some u reaches FLAC_LPC_GUARD (that order is no candidate for that block)."""
+    F, b = x.shape
+    o = q.shape[1]
+    pred = np.zeros((F, b - o), dtype=np.int64)
+    for j in range(o):
+        pred += q[:, j:j + 1] * x[:, o - 1 - j:b - 1 - j]
+    r = x[:, o:] - (pred >> np.asarray(shift, dtype=np.int64).reshape(F, 1))
+    u = np.where(r >= 0, 2 * r, -2 * r - 1)
+    return u, u.max(axis=1) < FLAC_LPC_GUARD
+
+
+def _flac_plan(x, level=0):
+    """The choice rule on blocks x int64 [F, b] of one size: (kind [F]: -1 CONSTANT, 0..4 the fixed order, 5 VERBATIM, 6 + i LPC of order
+    FLAC_LPC_ORDERS[i]; ks [F, P]: the chosen candidate's Rice parameters; us: per candidate the zigzag residuals [F, b - o]; lpc: per LPC
+    order (q [F, o], shift [F]), empty at level 0 and for a short block).  About 75 passes over the blocks: 5 orders x 15 parameters, and
+    60 more at level 1."""
     F, b = x.shape
     parts = 1 << _FLAC_PARTITION_ORDER if b == FLAC_BLOCK else 1
     plen = b // parts
     orders = min(5, b)
-    bits = np.empty((orders, F), dtype=np.int64)
-    ks = np.empty((orders, F, parts), dtype=np.int64)
-    us, r = [], x
+    bits, ks, us, lpc, r = [], [], [], [], x
     for o in range(orders):
         if o:
             r = np.diff(r, axis=1)
         u = np.where(r >= 0, 2 * r, -2 * r - 1)
         us.append(u)
-        padded = np.concatenate([np.zeros((F, o), dtype=np.int64), u], axis=1).reshape(F, parts, plen)   # (a zero adds nothing to sum(u >> k))
-        n = np.full(parts, plen, dtype=np.int64)
-        n[0] -= o
-        s = np.stack([(padded >> k).sum(axis=2) + n * (1 + k) for k in range(_FLAC_MAX_K + 1)])        # [15, F, parts]
-        ks[o] = s.argmin(axis=0)                                                                        # (the first minimum: the smaller k)
-        bits[o] = 8 + 16 * o + 2 + 4 + (4 + s.min(axis=0)).sum(axis=1)
-    kind = bits.argmin(axis=0)                                                                          # (the first minimum: the lower order)
-    best = bits[kind, np.arange(F)]
-    kind = np.where(8 + 16 * b < best, 5, kind)
+        k, s = _flac_rice(u, o, parts, plen)
+        ks.append(k)
+        bits.append(8 + 16 * o + 2 + 4 + (4 + s).sum(axis=1))
+    if level and b == FLAC_BLOCK and F:
+        coefs = [flac_lpc_coefficients(R) for R in flac_lpc_autocorrelation(x)]
+        for o in FLAC_LPC_ORDERS:
+            q, shift = np.zeros((F, o), dtype=np.int64), np.zeros(F, dtype=np.int64)
+            valid = np.zeros(F, dtype=bool)
+            for f, c in enumerate(coefs):
+                if o in c:
+                    q[f], shift[f], valid[f] = c[o][0], c[o][1], True
+            u, inside = flac_lpc_residual(x, q, shift)
+            valid &= inside
+            u = np.where(valid[:, None], u, 0)
+            k, s = _flac_rice(u, o, parts, plen)
+            us.append(u)
+            ks.append(k)
+            lpc.append((q, shift))
+            bits.append(np.where(valid, 8 + 16 * o + 4 + 5 + FLAC_LPC_PRECISION * o + 2 + 4 + (4 + s).sum(axis=1), np.iinfo(np.int64).max))
+    bits, ks = np.stack(bits), np.stack(ks)
+    cand = bits.argmin(axis=0)                                                                          # (the first minimum: the earlier candidate)
+    best = bits[cand, np.arange(F)]
+    kind = np.where(cand >= 5, cand + 1, cand)
+    kind = np.where(8 + 16 * b < best, _FLAC_VERBATIM, kind)
     kind = np.where((x == x[:, :1]).all(axis=1), -1, kind)
-    return kind, ks[np.minimum(np.maximum(kind, 0), orders - 1), np.arange(F)], us
+    return kind, ks[cand, np.arange(F)], us, lpc
 
 
 def _be16_bits(v):
     return np.unpackbits(np.asarray(v).astype(">i2").view(np.uint8))
 
 
-def _flac_frame(x, number, rate_code, kind, ks, u):
-    """One frame's bytes: block x (int64 [b]) as frame `number`, with `_flac_plan`'s choice for it (u: the chosen order's residuals)."""
+def _signed_bits(v, width):
+    """The `width`-bit two's complement of ints v, most significant bit first, as a flat uint8 array of bits."""
+    v = np.asarray(v, dtype=np.int64).reshape(-1, 1) & ((1 << width) - 1)
+    return ((v >> np.arange(width - 1, -1, -1)) & 1).astype(np.uint8).reshape(-1)
+
+
+def _flac_frame(x, number, rate_code, kind, ks, u, lpc=None):
+    """One frame's bytes: block x (int64 [b]) as frame `number`, with `_flac_plan`'s choice for it (u: the chosen candidate's residuals;
+    lpc: (q, shift) of an LPC choice)."""
     b = len(x)
     head = bytes([0xFF, 0xF8, ((0x0C if b == FLAC_BLOCK else 0x07) << 4) | rate_code, 0x08]) + _flac_number(number)
     if b != FLAC_BLOCK:
@@ -679,23 +812,30 @@ def _flac_frame(x, number, rate_code, kind, ks, u):
     head += bytes([flac_crc8(head)])
     if kind == -1:
         body = bytes([0x00]) + int(x[0]).to_bytes(2, "big", signed=True)
-    elif kind == 5:
+    elif kind == _FLAC_VERBATIM:
         body = bytes([0x02]) + x.astype(">i2").tobytes()
     else:
-        o, parts = int(kind), len(ks)
+        o = int(kind) if lpc is None else len(lpc[0])
+        parts = len(ks)
         plen = b // parts
         k = np.repeat(ks, plen)[o:]
         q = u >> k
         length = q + 1 + k
-        lead = 8 + 16 * o + 6                                    # subframe header, warm-up, coding method and partition order
+        extra = 0 if lpc is None else 4 + 5 + FLAC_LPC_PRECISION * o     # precision, shift and coefficients of an LPC subframe
+        lead = 8 + 16 * o + extra + 6                             # subframe header, warm-up, coding method and partition order
         bounds = np.concatenate([[0], np.cumsum(length)])        # code i starts at bounds[i] + lead + 4 * (partitions opened up to it)
         opened = np.repeat(np.arange(1, parts + 1), plen)[o:]
         start = lead + 4 * opened + bounds[:-1]
         nbits = lead + 4 * parts + int(bounds[-1])
         bit = np.zeros((nbits + 7) // 8 * 8, dtype=np.uint8)
-        bit[:8] = np.unpackbits(np.array([(8 | o) << 1], dtype=np.uint8))
+        bit[:8] = np.unpackbits(np.array([((8 | o) if lpc is None else (0x20 | (o - 1))) << 1], dtype=np.uint8))
         bit[8:8 + 16 * o] = _be16_bits(x[:o])
-        bit[8 + 16 * o + 2:lead] = np.unpackbits(np.array([_FLAC_PARTITION_ORDER if parts > 1 else 0], dtype=np.uint8))[4:]
+        if lpc is not None:
+            at = 8 + 16 * o
+            bit[at:at + 4] = _signed_bits(FLAC_LPC_PRECISION - 1, 4)
+            bit[at + 4:at + 9] = _signed_bits(lpc[1], 5)
+            bit[at + 9:at + 9 + FLAC_LPC_PRECISION * o] = _signed_bits(lpc[0], FLAC_LPC_PRECISION)
+        bit[lead - 4:lead] = np.unpackbits(np.array([_FLAC_PARTITION_ORDER if parts > 1 else 0], dtype=np.uint8))[4:]
         first = np.concatenate([[0], np.arange(1, parts) * plen - o])          # the first residual of each partition
         pstart = start[first] - 4
         for j in range(4):
@@ -709,7 +849,7 @@ def _flac_frame(x, number, rate_code, kind, ks, u):
     return frame + flac_crc16(frame).to_bytes(2, "big")
 
 
-def _flac_frames(pcm, first_number, rate_code):
+def _flac_frames(pcm, first_number, rate_code, level=0):
     """The frames of int16 PCM whose first block is frame `first_number`: whole blocks of 4096 and, if samples remain, one short block."""
     n = len(pcm)
     full, out = n // FLAC_BLOCK, []
@@ -719,24 +859,28 @@ def _flac_frames(pcm, first_number, rate_code):
     for x in groups:
         const = (x == x[:, :1]).all(axis=1)                       # (not planned: a long silence costs one comparison per sample)
         busy = np.flatnonzero(~const)
-        kind, ks, us = _flac_plan(x[busy]) if len(busy) else (None, None, None)
+        kind, ks, us, lpc = _flac_plan(x[busy], level) if len(busy) else (None, None, None, None)
         where = {int(f): i for i, f in enumerate(busy)}
         for f in range(len(x)):
             number = first_number + len(out)
             if const[f]:
                 out.append(_flac_frame(x[f], number, rate_code, -1, None, None))
+                continue
+            i, kd = where[f], int(kind[where[f]])
+            if kd > _FLAC_VERBATIM:
+                c = kd - 1
+                out.append(_flac_frame(x[f], number, rate_code, kd, ks[i], us[c][i], (lpc[c - 5][0][i], int(lpc[c - 5][1][i]))))
             else:
-                i = where[f]
-                out.append(_flac_frame(x[f], number, rate_code, int(kind[i]), ks[i], us[kind[i]][i] if 0 <= kind[i] < 5 else None))
+                out.append(_flac_frame(x[f], number, rate_code, kd, ks[i], us[kd][i] if 0 <= kd < 5 else None))
     return out
 
 
-def encode_flac(pcm, sample_rate) -> np.ndarray:
+def encode_flac(pcm, sample_rate, level=0) -> np.ndarray:
     """The native FLAC stream (uint8) of mono int16 PCM at `sample_rate` (one of OUTPUT_SAMPLE_RATES), in the subset and by the choice rule
-    written above this function: a pure function of the samples and the rate, which `ops.wave_flac` equals byte for byte.  An empty input
-    is the 42-byte header alone, with total 0 and frame sizes 0."""
-    pcm, rate = _as_pcm16(pcm), _flac_rate(sample_rate)
-    frames = _flac_frames(pcm, 0, FLAC_RATE_CODES[rate])
+    written above this function, at `level` 0 (fixed predictors) or 1 (LPC subframes too): a pure function of the samples, the rate and
+    the level, which `ops.wave_flac` equals byte for byte.  An empty input is the 42-byte header alone, with total 0 and frame sizes 0."""
+    pcm, rate, level = _as_pcm16(pcm), _flac_rate(sample_rate), check_flac_level(level)
+    frames = _flac_frames(pcm, 0, FLAC_RATE_CODES[rate], level)
     sizes = [len(f) for f in frames] or [0]
     return np.frombuffer(flac_stream_header(rate, len(pcm), min(sizes), max(sizes)) + b"".join(frames), dtype=np.uint8).copy()
 
@@ -744,11 +888,12 @@ def encode_flac(pcm, sample_rate) -> np.ndarray:
 class StreamFlacEncoder:
     """`encode_flac` one piece at a time: `header()` is the 42 bytes with total samples 0 and frame sizes 0 (unknown length), `feed(piece)`
     the bytes of every 4096-sample frame the piece completes, `flush()` the short last frame.  The concatenation of everything `feed` and
-    `flush` return equals `encode_flac(...)[42:]` of the concatenated input, whatever the piece sizes: a frame depends on its own samples
-    and its number alone."""
+    `flush` return equals `encode_flac(..., level)[42:]` of the concatenated input, whatever the piece sizes: a frame depends on its own
+    samples and its number alone."""
 
-    def __init__(self, sample_rate):
+    def __init__(self, sample_rate, level=0):
         self.sample_rate = _flac_rate(sample_rate)
+        self.level = check_flac_level(level)
         self.code = FLAC_RATE_CODES[self.sample_rate]
         self.pending = np.zeros(0, dtype=np.int16)
         self.frames = 0
@@ -757,7 +902,7 @@ class StreamFlacEncoder:
         return flac_stream_header(self.sample_rate)
 
     def _emit(self, pcm):
-        frames = _flac_frames(pcm, self.frames, self.code)
+        frames = _flac_frames(pcm, self.frames, self.code, self.level)
         self.frames += len(frames)
         return b"".join(frames)
 
