@@ -33,8 +33,9 @@ import torch
 from . import wave_codec
 from .audio_prep import preprocess_ref_audio_text, remove_silence_edges, remove_silence_pcm  # noqa: F401  (F/infer/utils_infer.py:263-350)
 from .loaders import DiT, MMDiT, UNetT, load_checkpoint, load_model, load_vocoder  # noqa: F401  (F/infer/utils_infer.py:92-130,175-260)
-from .wave_codec import (ALL_ENCODINGS, FLAC_BLOCK, FLAC_ENCODINGS, FLAC_HEADER_BYTES, MAX_TAP_TABLE_BYTES, OUTPUT_ENCODINGS,  # noqa: F401
-                         OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, StreamFlacEncoder, StreamResampler, check_flac_level, decode_flac, decode_g711, deliver_pcm16,
+from .wave_codec import (ALL_ENCODINGS, DELIVERY_OPTIONS, FLAC_BLOCK, FLAC_ENCODINGS, FLAC_HEADER_BYTES, MAX_TAP_TABLE_BYTES, OUTPUT_ENCODINGS,  # noqa: F401
+                         OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, WHOLE_WAVE, WHOLE_WAVE_LOUDNESS, StreamDelivery, StreamFlacEncoder,
+                         StreamResampler, WaveSpec, check_flac_level, decode_flac, decode_g711, deliver_pcm16,
                          delivery_format, encode_flac, encode_g711, flac_crc8, flac_crc16, flac_stream_header, load_audio, load_wav, quantise_pcm16, read_flac,
                          rate_pair, request_flac_level, resample_pcm16, resample_sinc_hann, resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
 from .wave_codec import (LOUDNESS_GATE_ABS, LOUDNESS_PEAK_CEILING, LOUDNESS_RANGE, LOUDNESS_TAPS, check_loudness, loudness_gain,  # noqa: F401
@@ -563,33 +564,25 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 
 
 # per-request options of `infer_requests` (the fourth element of a request) and of the serving routes
-_PLAIN = (target_sample_rate, "pcm16")   # the delivery format of a request that sets neither `sample_rate` nor `encoding`
 REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "remove_silence", "sample_rate", "encoding",
-                   "loudness", "flac_level")
-WHOLE_WAVE = ("remove_silence, sample_rate and encoding need the request's whole wave: they are not available for a list of chunk texts (a streamed "
-              "request, whose owner applies the delivery format piece by piece: StreamResampler, encode_g711) or with join=False")
-WHOLE_WAVE_LOUDNESS = ("loudness is measured on the request's whole wave: it is not available for a list of chunk texts, on a streaming path or "
-                       "with join=False")
+                   "loudness", "flac_level")   # the sampler's six, then `DELIVERY_OPTIONS` (`WaveSpec`)
 
 
 def needs_whole_wave(opts, streamed=False) -> bool:
-    """Whether a request's options apply to its joined wave, so that it cannot be handed out chunk by chunk (`WHOLE_WAVE`): `remove_silence`,
-    `loudness`, and a delivery format (`sample_rate`, `encoding`) other than 24 kHz "pcm16".  `streamed`: the format does not count -- a stream's owner
-    (`serve.TTSManager._stream`) takes it off the request and applies it to the pieces itself."""
-    if opts.get("remove_silence") or opts.get("loudness") is not None:
-        return True
-    return not streamed and delivery_format(opts.get("sample_rate"), opts.get("encoding")) != _PLAIN
+    """`WaveSpec.needs_whole_wave` of a dict of options: whether the request cannot be handed out chunk by chunk (`WHOLE_WAVE`)."""
+    return WaveSpec.of(opts).needs_whole_wave(streamed)
 
 
 def whole_wave_message(opts) -> str:
-    """The refusal of a request that `needs_whole_wave` where it cannot have it: `WHOLE_WAVE_LOUDNESS` when `loudness` is the reason."""
-    return WHOLE_WAVE_LOUDNESS if opts.get("loudness") is not None and not opts.get("remove_silence") else WHOLE_WAVE
+    """`WaveSpec.whole_wave_message` of a dict of options."""
+    return WaveSpec.of(opts).whole_wave_message()
 
 
 def plan_request(request, defaults, *, target_rms, fix_duration, device, tokenizer):
     """One request tuple (ref_audio, ref_text, gen_text[, options]) of `infer_requests` / `SpanScheduler.admit`, planned: `opts` (the
-    options over `defaults`, unknown ones rejected), `voice` (prepared), `units` (one per chunk; the text is chunked unless it is a list
-    of chunk texts) and `generator`, the request's noise source (None: the global one).  A `ScriptRequest` is planned segment by segment:
+    options over `defaults`, unknown ones rejected), `spec` (`WaveSpec.of(opts)`: what the finished wave has to be), `voice` (prepared),
+    `units` (one per chunk; the text is chunked unless it is a list of chunk texts) and `generator`, the request's noise source (None: the
+    global one).  A `ScriptRequest` is planned segment by segment:
     `parts` = [(voice, units)] per segment (a plain request has one part), `units` all of them in order -- one generator, so chunk k of the
     script draws after chunks 0..k-1 of the whole script -- `voice` the first segment's, `script` the request itself (None: a tuple).  A `generator` the request carries is drawn from
     on a copy: `commit()` moves the caller's to where the copy got, once the caller knows that the request went through."""
@@ -599,11 +592,9 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
     unknown = set(opts) - set(REQUEST_OPTIONS) - {"generator"}
     if unknown:
         raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
-    if opts.get("loudness") is not None:
-        opts["loudness"] = check_loudness(opts["loudness"])
-    request_flac_level(opts.get("flac_level"), opts.get("encoding"))   # (a level beside another encoding is refused, never ignored)
-    if needs_whole_wave(opts) and isinstance(request_text(request), (list, tuple)):
-        raise ValueError(whole_wave_message(opts))
+    spec = WaveSpec.of(opts)
+    if spec.needs_whole_wave() and isinstance(request_text(request), (list, tuple)):
+        raise ValueError(spec.whole_wave_message())
     # one (voice, units) part per segment; a plain request is its own single segment
     segments = script.segments if script is not None else [tuple(request[:3])]
     parts = [_plan_request(seg[0], seg[1], seg[2], target_rms, seg[3] if len(seg) > 3 and seg[3] is not None else opts["speed"], fix_duration,
@@ -615,7 +606,7 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
     def commit():
         if own is not None:
             own.set_state(gen.get_state())
-    return types.SimpleNamespace(voice=voice, units=units, opts=opts, generator=gen, commit=commit, parts=parts, script=script)
+    return types.SimpleNamespace(voice=voice, units=units, opts=opts, spec=spec, generator=gen, commit=commit, parts=parts, script=script)
 
 
 def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, target_rms=target_rms,
@@ -652,15 +643,10 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     from the global generator in flat request order (unit by unit, request after request) when there is one sampler call, i.e. always
     with a `per_unit_time_grids` model, and in sampler-call order otherwise.
 
-    `remove_silence` (bool, per request): the reference's `remove_silence_for_generated_wav` on the finished wave; such a request's wave is
-    int16 PCM (`audio_prep.remove_silence_pcm` of its quantised joined wave), and it needs the whole wave: ValueError with `join=False` or a
-    list of chunk texts.  `sample_rate` (one of OUTPUT_SAMPLE_RATES) and `encoding` ("pcm16", "mulaw", "alaw", "flac"), per request: the delivery
-    format, a pure function of the request's 24 kHz int16 PCM (`deliver_pcm16`: after silence removal, `resample_pcm16`, then `encode_g711`
-    or `encode_flac`); such a request's wave is int16 at that rate, uint8 code bytes or the uint8 bytes of a FLAC stream, its triple names that rate, and like `remove_silence` it needs the whole
-    wave.  `flac_level` (0 or 1, per request, only beside `encoding` "flac": ValueError otherwise): at 1 the stream's full blocks may be LPC
-    subframes (`encode_flac(..., level=1)`).  `loudness` (LUFS, -40 .. -5, per request): the programme loudness (ITU-R BS.1770-4) the request's 24 kHz int16 PCM is moved to
-    after silence removal and before the delivery format (`normalise_loudness_pcm16`: the sample peak stays at or below -1 dBFS); such a
-    request's wave is int16 PCM and it needs the whole wave.  A `ScriptRequest` (a multi-voice script: one segment per piece, each with its own voice) is accepted in place of a tuple: its
+    The `DELIVERY_OPTIONS` (`remove_silence`, `loudness`, `sample_rate`, `encoding`, `flac_level`), per request, say what its finished wave
+    is: see `WaveSpec`.  Such a request's wave is `finish_pcm16` of its quantised joined wave and its triple names the delivery rate; the
+    ones that need the whole wave are a ValueError with `join=False` or a list of chunk texts.  A `ScriptRequest` (a multi-voice script:
+    one segment per piece, each with its own voice) is accepted in place of a tuple: its
     segments' units ride in the same sampler call, one prompt per unit, and the same vocoder call, one group per segment; its triple is
     (`join_segments` of its segments' chunk waves, rate, [spectrogram per segment]), with `join=False` the chunk waves and spectrograms per
     segment, and its whole-wave options apply to the joined script.  `finish` = dict(device_backend=..., want=...): what the serving path asks for -- the list of `finish_requests`
@@ -701,40 +687,29 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
             groups.append((mels[k:k + len(units)], voice.ref_frames, voice.rms))
             k += len(units)
     per_plan = np.cumsum([0] + [len(plan.parts) for plan in plans])   # a plan's groups: [per_plan[i], per_plan[i + 1])
-    silence = [bool(plan.opts.get("remove_silence")) for plan in plans]
-    formats = [delivery_format(plan.opts.get("sample_rate"), plan.opts.get("encoding")) for plan in plans]
-    loud = [plan.opts.get("loudness") for plan in plans]
-    levels = [plan.opts.get("flac_level") for plan in plans]
     if finish is not None:
         backend = bool(finish.get("device_backend"))
         got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms, on_device=backend, want_specs=False)
         chunk_waves = [request_chunk_waves(plan, got[per_plan[i]:per_plan[i + 1]]) for i, plan in enumerate(plans)]
-        return finish_requests(chunk_waves, [request_text(req) for req in requests], cross_fade_duration, silence, sample_rate=[f[0] for f in formats],
-                               encoding=[f[1] for f in formats], loudness=loud, flac_level=levels, **finish)
-    whole = [needs_whole_wave(plan.opts) for plan in plans]
-    if any(whole) and not join:
-        raise ValueError(whole_wave_message(next(plan.opts for plan, w in zip(plans, whole) if w)))
+        return _finish_specs(chunk_waves, [request_text(req) for req in requests], cross_fade_duration, [plan.spec for plan in plans], **finish)
+    refused = next((plan.spec for plan in plans if plan.spec.needs_whole_wave()), None)
+    if refused is not None and not join:
+        raise ValueError(refused.whole_wave_message())
     out = []
     got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms)
-    for i, (plan, needs, flag, fmt, lufs, level) in enumerate(zip(plans, whole, silence, formats, loud, levels)):
-        mine = got[per_plan[i]:per_plan[i + 1]]
-        if plan.script is not None:   # (wave, rate, [spectrogram per segment]) like `infer_multi_voice`; join=False: per-segment lists
-            seg_specs = [np.concatenate(specs, axis=1) for _, specs in mine]
-            if needs or join:
-                wave, = finish_requests([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1], loudness=lufs,
-                                        flac_level=level)
-                out.append((wave, fmt[0], seg_specs))
+    for i, plan in enumerate(plans):
+        mine, script = got[per_plan[i]:per_plan[i + 1]], plan.script is not None
+        if join:   # a script: (wave, rate, [spectrogram per segment]) like `infer_multi_voice`
+            joined_specs = [np.concatenate(specs, axis=1) for _, specs in mine]
+            if script or plan.spec.needs_whole_wave():
+                wave, = _finish_specs([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [plan.spec])
             else:
-                out.append(([waves for waves, _ in mine], target_sample_rate, [specs for _, specs in mine]))
-            continue
-        (waves, specs), = mine
-        if needs:
-            wave, = finish_requests([waves], [""], cross_fade_duration, [flag], sample_rate=fmt[0], encoding=fmt[1], loudness=lufs, flac_level=level)
-            out.append((wave, fmt[0], np.concatenate(specs, axis=1)))
-        elif join:
-            out.append((cross_fade_concat(waves, cross_fade_duration), target_sample_rate, np.concatenate(specs, axis=1)))
+                wave = cross_fade_concat(mine[0][0], cross_fade_duration)
+            out.append((wave, plan.spec.sample_rate, joined_specs if script else joined_specs[0]))
+        elif script:   # join=False: the chunk waves and spectrograms per segment
+            out.append(([waves for waves, _ in mine], target_sample_rate, [specs for _, specs in mine]))
         else:
-            out.append((waves, target_sample_rate, specs))
+            out.append((mine[0][0], target_sample_rate, mine[0][1]))
     return out
 
 
@@ -783,46 +758,40 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     `backend_stats`): a list text, chunk waves that are not on a HIP device, and a request of several chunks with one shorter than twice the
     fade, where the reference's nested cross-fades overlap and the kernel's closed form does not hold.
 
-    `sample_rate` / `encoding`: one value or one per request; None, 24000 and "pcm16" mean the result described above.  Any other request
-    gets `deliver_pcm16` of its int16 PCM (quantised whatever `want` says, after silence removal): int16 at that rate, or uint8 G.711 codes.
-    With `device_backend` the requests `ops.wave_finish` finished go through ONE `ops.wave_encode` call per distinct (rate, encoding) pair,
-    chained on the same stream with no download in between (a flagged request's length stays on the device); per pair at most two copies come
-    back, the lengths (only with silence removal) and the encoded samples, and nothing of those requests' 24 kHz PCM.  Like every ragged call
-    of the library each `wave_encode` call copies its small request table on the stream and waits for that copy before it launches, so the
-    host does wait once per pair for what is queued in front of it (`wave_finish`'s kernels); no data comes back in that wait.
-
-    `encoding="flac"`: the request gets the uint8 array that holds `encode_flac` of its PCM at `sample_rate`.  With `device_backend` the flac
-    requests of a batch take ONE `ops.wave_flac` call per distinct rate behind `wave_finish` / `wave_encode` on the same stream
-    (`backend_stats["flac_calls"]`, `["flac_requests"]`), and two copies come back per rate: the streams' lengths, then the streams, joined
-    on the device, in one download of exactly their bytes (`["flac_bytes"]`); on the host, or with a model without the device back-end,
-    `encode_flac` makes the same bytes.  Every `wave_encode` / `wave_flac` call of the batch is queued before the first of these copies.
-    `flac_level`: one level (`check_flac_level`: 0, or 1 for LPC subframes) or one per request, None for level 0; only a "flac" request may
-    name one (ValueError otherwise).  The requests of a rate still share ONE `ops.wave_flac` call, whatever their levels.
-
-    `loudness`: one target in LUFS (`check_loudness`) or one per request, None for a request that keeps its level.  Such a request's int16
-    PCM (quantised whatever `want` says, after silence removal) goes through `normalise_loudness_pcm16` before the delivery format.  With
-    `device_backend` the flagged requests of the batch take ONE `ops.wave_loudness` call directly behind `wave_finish` on the same stream,
-    in place and before any `wave_encode` / `wave_flac` call is queued, with the lengths still on the device: no copy comes back for it
-    (`backend_stats["loudness_calls"]`, `["loudness_requests"]`), and a batch without a flagged request makes no call."""
-    if want not in ("float", "pcm16"):
-        raise ValueError(f'want must be "float" or "pcm16" (got {want!r})')
-    if device_backend and want != "pcm16":
-        raise ValueError('the device back-end produces int16 PCM: device_backend=True needs want="pcm16"')
+    `sample_rate` / `encoding`, `loudness`, `flac_level`: each one value or one per request, None for the default; with the flag they are
+    the request's `WaveSpec`, and a request that sets any of them gets `finish_pcm16` of its int16 PCM (quantised whatever `want` says).
+    With `device_backend` all of it stays on the device, chained on one stream behind `wave_finish`: the calls and the copies that come back
+    are `_finish_on_device`'s, and `backend_stats` counts them."""
+    _check_want(device_backend, want)   # (first, as ever: a bad `want` is reported before a bad option)
     n = len(chunk_waves_per_request)
     flags = [False] * n if remove_silence is None else [bool(f) for f in remove_silence]
     if len(gen_texts) != n or len(flags) != n:
         raise ValueError("finish_requests: one text and one remove_silence flag per request")
-    formats = [delivery_format(r, e) for r, e in zip(_per_request(sample_rate, n, "sample_rate"), _per_request(encoding, n, "encoding"))]
-    loud = [check_loudness(v) for v in _per_request(loudness, n, "loudness")]
-    levels = [request_flac_level(v, fmt[1]) for v, fmt in zip(_per_request(flac_level, n, "flac_level"), formats)]
+    keywords = (("sample_rate", sample_rate), ("encoding", encoding), ("loudness", loudness), ("flac_level", flac_level))
+    columns = [_per_request(value, n, name) for name, value in keywords]
+    specs = [WaveSpec.of(dict(remove_silence=flag, sample_rate=rate, encoding=enc, loudness=lufs, flac_level=level))
+             for flag, rate, enc, lufs, level in zip(flags, *columns)]
+    return _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend, want)
+
+
+def _check_want(device_backend, want):
+    if want not in ("float", "pcm16"):
+        raise ValueError(f'want must be "float" or "pcm16" (got {want!r})')
+    if device_backend and want != "pcm16":
+        raise ValueError('the device back-end produces int16 PCM: device_backend=True needs want="pcm16"')
+
+
+def _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend=False, want="float"):
+    """`finish_requests` with one planned `WaveSpec` per request in place of its option keywords: what `infer_requests` and
+    `SpanScheduler` call."""
+    _check_want(device_backend, want)
     fade = int(cross_fade_duration * target_sample_rate) if cross_fade_duration > 0 else 0
-    out, on_device = [None] * n, []
-    for i, (waves, text) in enumerate(zip(chunk_waves_per_request, gen_texts)):
+    out, on_device = [None] * len(specs), []
+    for i, (waves, text, spec) in enumerate(zip(chunk_waves_per_request, gen_texts, specs)):
         script = isinstance(waves, SegmentedWaves)
         if isinstance(text, (list, tuple)):
-            whole = dict(remove_silence=flags[i], sample_rate=formats[i][0], encoding=formats[i][1], loudness=loud[i])
-            if needs_whole_wave(whole):
-                raise ValueError(whole_wave_message(whole))
+            if spec.needs_whole_wave():
+                raise ValueError(spec.whole_wave_message())
             out[i] = [[_host_chunk(w) for w in seg] for seg in waves] if script else [_host_chunk(w) for w in waves]
         elif script and device_backend and _script_on_device(waves, fade):
             on_device.append(i)
@@ -831,13 +800,12 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
             on_device.append(i)
             continue
         else:
-            out[i] = _finish_on_host(waves, text, cross_fade_duration, flags[i], formats[i], want, loud[i], levels[i])
+            out[i] = _finish_on_host(waves, text, cross_fade_duration, spec, want)
         backend_stats["host_requests"] += 1
     if on_device:
         # the plain requests first: their PCM is then one prefix of the packed buffer, and what comes down of it holds no other request's
-        on_device.sort(key=lambda i: formats[i] != _PLAIN)
-        done = _finish_on_device([_device_request(chunk_waves_per_request[i]) for i in on_device], fade, [flags[i] for i in on_device],
-                                 [formats[i] for i in on_device], [loud[i] for i in on_device], [levels[i] for i in on_device])
+        on_device.sort(key=lambda i: not specs[i].plain_format)
+        done = _finish_on_device([_device_request(chunk_waves_per_request[i]) for i in on_device], fade, [specs[i] for i in on_device])
         for i, wave in zip(on_device, done):
             out[i] = wave
     return out
@@ -867,34 +835,43 @@ def _device_request(waves):
     return chunks, fades
 
 
-def _finish_on_host(waves, text, cross_fade_duration, flag, fmt, want, loudness=None, flac_level=0):
-    """`finish_requests` for one request on the host: join, quantisation, silence removal, the loudness target and the delivery format in
-    numpy."""
+def finish_pcm16(pcm, spec) -> np.ndarray:
+    """What a `WaveSpec` makes of a request's 24 kHz int16 PCM, the one host definition (the device back-end and `StreamDelivery` are held
+    to it byte for byte): `remove_silence_pcm` when flagged, `normalise_loudness_pcm16`, `deliver_pcm16`."""
+    if spec.remove_silence:
+        pcm = remove_silence_pcm(pcm, target_sample_rate)
+    pcm = normalise_loudness_pcm16(pcm, spec.loudness)
+    return deliver_pcm16(pcm, *spec.format, flac_level=spec.flac_level if spec.flac else None)
+
+
+def _finish_on_host(waves, text, cross_fade_duration, spec, want):
+    """`finish_requests` for one request on the host: join, quantisation where anything asks for PCM, `finish_pcm16`."""
     if isinstance(waves, SegmentedWaves):
         wave = join_segments([[_host_chunk(w) for w in seg] for seg in waves], cross_fade_duration, waves.gap_samples)
     else:
         wave = request_wave(text, [_host_chunk(w) for w in waves], cross_fade_duration)
-    if flag:
-        wave = remove_silence_pcm(quantise_pcm16(wave), target_sample_rate)
-    elif want == "pcm16" or fmt != _PLAIN or loudness is not None:
-        wave = quantise_pcm16(wave)
-    if loudness is not None:
-        wave = normalise_loudness_pcm16(wave, loudness)
-    return wave if fmt == _PLAIN else deliver_pcm16(wave, *fmt, flac_level=flac_level if fmt[1] in FLAC_ENCODINGS else None)
+    if spec.needs_whole_wave():
+        return finish_pcm16(quantise_pcm16(wave), spec)
+    return quantise_pcm16(wave) if want == "pcm16" else wave   # (nothing to finish: no pass through the three steps' own checks)
 
 
-def _finish_on_device(requests, fade, silence, formats, loudness=None, flac_levels=None):
-    """`finish_requests` for the requests the device back-end takes: `requests` = (chunk waves (device tensors), fades: `_device_request`), the
-    plain-format ones first; `silence`, `formats` per request.  ONE `ops.wave_finish` call -- `ops.wave_finish_joins` when a script is among
-    them -- then one `ops.wave_encode` call per distinct delivery format behind it on the same stream, and for the "flac" requests one
-    `ops.wave_flac` call per distinct rate (behind a `wave_encode(..., "pcm16")` call where the rate is not 24 kHz).  `loudness`: a target per
-    request or None; when any is set, ONE `ops.wave_loudness` call normalises those requests in place directly behind `wave_finish`, before
-    anything else is queued.  `flac_levels`: a FLAC level per request or None (all 0); the "flac" requests of a rate share their one call
-    through `ops.wave_flac`'s per-request levels, and a call in which no request asks for level 1 is the level-0 call.  Returns one
-    result per request."""
+def _finish_on_device(requests, fade, specs):
+    """`finish_requests` for the requests the device back-end takes: `requests` = (chunk waves (device tensors), fades: `_device_request`)
+    and their `specs`, the plain-format ones first.  ONE `ops.wave_finish` call -- `ops.wave_finish_joins` when a script is among them --;
+    directly behind it, when any request has a loudness target, ONE `ops.wave_loudness` call that normalises those in place; then on the
+    same stream one `ops.wave_flac` call per distinct rate of the "flac" requests (behind a `wave_encode(..., "pcm16")` call where the rate
+    is not 24 kHz; the requests of a rate share it through its per-request levels, and a call in which nobody asks for level 1 is the
+    level-0 call) and one `ops.wave_encode` call per other distinct delivery format.  Every call is queued before the first copy comes
+    back; a flagged request's length stays on the device in between.  Copies: the plain requests' lengths (only with silence removal) and
+    samples; per `wave_encode` format the lengths (only with silence removal) and the encoded samples, nothing of the 24 kHz PCM; per
+    FLAC rate the streams' lengths, then the streams, joined on the device, in one download of exactly their bytes; none for the loudness
+    call.  Like every ragged call of the library each `wave_encode` call copies its small request table on the stream and waits for that
+    copy before it launches, so the host does wait once per format for what is queued in front of it; no data comes back in that wait.
+    Returns one result per request."""
     from . import ops
     out = [None] * len(requests)
-    plain = sum(fmt == _PLAIN for fmt in formats)
+    silence = [spec.remove_silence for spec in specs]
+    plain = sum(spec.plain_format for spec in specs)
     chunks = [w.to(torch.float32).contiguous() for waves, _ in requests for w in waves]
     fades = [[False] + [True] * (len(waves) - 1) if f is None else f for waves, f in requests]
     joined = [sum(len(w) for w in waves) - sum(f[1:]) * fade for (waves, _), f in zip(requests, fades)]
@@ -903,10 +880,11 @@ def _finish_on_device(requests, fade, silence, formats, loudness=None, flac_leve
         pcm, lengths, offsets = ops.wave_finish(chunks, counts, fade, silence, target_sample_rate)
     else:
         pcm, lengths, offsets = ops.wave_finish_joins(chunks, counts, fade, [x for f in fades for x in f], silence, target_sample_rate)
-    if loudness is not None and any(v is not None for v in loudness):   # in place, lengths still on the device: nothing comes back for it
-        ops.wave_loudness(pcm, offsets, joined, lengths, [None if v is None else loudness_gain_constant(v) for v in loudness])
+    targets = [spec.gain_constant for spec in specs]
+    if any(t is not None for t in targets):   # in place, lengths still on the device: nothing comes back for it
+        ops.wave_loudness(pcm, offsets, joined, lengths, targets)
         backend_stats["loudness_calls"] += 1
-        backend_stats["loudness_requests"] += sum(v is not None for v in loudness)
+        backend_stats["loudness_requests"] += sum(t is not None for t in targets)
     if plain:
         if any(silence[:plain]):
             kept = lengths[:plain].cpu().tolist()
@@ -917,58 +895,53 @@ def _finish_on_device(requests, fade, silence, formats, loudness=None, flac_leve
         backend_stats["d2h_copies"] += 1
         for k, (off, length) in enumerate(zip(offsets, kept)):
             out[k] = host[off:off + length].copy()   # (a request's result does not keep the batch's buffer alive)
-    groups = {}
+    groups = {}   # delivery format -> its requests, in order of first appearance: the "flac" requests of a rate are one group
     for k in range(plain, len(requests)):
-        if formats[k][1] not in FLAC_ENCODINGS:
-            groups.setdefault(formats[k], []).append(k)
-    flac_rates = {}
-    for k in range(plain, len(requests)):
-        if formats[k][1] in FLAC_ENCODINGS:
-            flac_rates.setdefault(formats[k][0], []).append(k)
-    # every group's kernels are queued first, and only then does anything come down: a mixed micro-batch does not wait for one group's copies
-    # before the next group's launches
-    queued_flac, queued = [], []
-    for rate, ks in flac_rates.items():   # FLAC: one `ops.wave_flac` call per distinct rate, behind the resampler's where the rate is not 24 kHz
+        groups.setdefault(specs[k].format, []).append(k)
+
+    def gathered(ks):   # the requests' lengths, gathered on the device
         contiguous = ks == list(range(ks[0], ks[-1] + 1))
-        sel = lengths[ks[0]:ks[-1] + 1] if contiguous else lengths[torch.tensor(ks, device=lengths.device)]   # (gathered on the device)
-        if rate == target_sample_rate:
-            src, src_off, bounds = pcm, [offsets[k] for k in ks], [joined[k] for k in ks]
-        else:
-            data, sel, out_off = ops.wave_encode(pcm, [offsets[k] for k in ks], [joined[k] for k in ks], sel, rate, "pcm16",
-                                                 _device_taps(target_sample_rate, rate, pcm.device))
-            src, src_off = data.view(torch.int16), [off // 2 for off in out_off]
-            bounds = [resampled_length(joined[k], target_sample_rate, rate) for k in ks]
-            backend_stats["encode_calls"] += 1
-            backend_stats["encode_requests"] += len(ks)
-        level = [flac_levels[k] for k in ks] if flac_levels is not None and any(flac_levels[k] for k in ks) else None
-        queued_flac.append((ks,) + tuple(ops.wave_flac(src, src_off, bounds, sel, rate, level=level)))
-        backend_stats["flac_calls"] += 1
-        backend_stats["flac_requests"] += len(ks)
-    for (rate, enc), ks in groups.items():   # one call per delivery format, behind wave_finish on the same stream
+        return lengths[ks[0]:ks[-1] + 1] if contiguous else lengths[torch.tensor(ks, device=lengths.device)]
+
+    def encode(ks, rate, enc):   # one `ops.wave_encode` call, behind what is queued on the same stream
         taps = _device_taps(target_sample_rate, rate, pcm.device) if rate != target_sample_rate else None
-        contiguous = ks == list(range(ks[0], ks[-1] + 1))
-        sel = lengths[ks[0]:ks[-1] + 1] if contiguous else lengths[torch.tensor(ks, device=lengths.device)]   # (gathered on the device)
-        queued.append((rate, enc, ks) + tuple(ops.wave_encode(pcm, [offsets[k] for k in ks], [joined[k] for k in ks], sel, rate, enc, taps)))
+        got = ops.wave_encode(pcm, [offsets[k] for k in ks], [joined[k] for k in ks], gathered(ks), rate, enc, taps)
         backend_stats["encode_calls"] += 1
         backend_stats["encode_requests"] += len(ks)
-    for ks, streams, stream_len, stream_off in queued_flac:
-        sizes = stream_len.cpu().tolist()                                    # (a stream's length is known on the device alone)
-        # `wave_flac` puts each stream at the offset its VERBATIM bound allows for, so between two streams lies room that nobody wrote:
-        # the streams are joined on the device, and ONE download brings exactly their bytes and nothing of their PCM
-        slices = [streams[off:off + m] for off, m in zip(stream_off, sizes)]
-        host = (slices[0] if len(slices) == 1 else torch.cat(slices)).cpu().numpy()
-        backend_stats["d2h_copies"] += 2
-        backend_stats["flac_bytes"] += host.nbytes
-        at = 0
-        for k, m in zip(ks, sizes):
-            out[k] = host[at:at + m].copy()
-            at += m
+        return got
+
+    # every group's kernels are queued first, the FLAC groups' in front, and only then does anything come down: a mixed micro-batch does not
+    # wait for one group's copies before the next group's launches
+    queued = []
+    for (rate, enc), ks in sorted(groups.items(), key=lambda group: group[0][1] not in FLAC_ENCODINGS):
+        if enc not in FLAC_ENCODINGS:
+            queued.append((rate, enc, ks) + tuple(encode(ks, rate, enc)))
+            continue
+        if rate == target_sample_rate:   # one `ops.wave_flac` call per distinct rate, behind the resampler's where the rate is not 24 kHz
+            src, src_off, sel = pcm, [offsets[k] for k in ks], gathered(ks)
+        else:
+            data, sel, out_off = encode(ks, rate, "pcm16")
+            src, src_off = data.view(torch.int16), [off // 2 for off in out_off]
+        levels = [specs[k].flac_level for k in ks]
+        bounds = [resampled_length(joined[k], target_sample_rate, rate) for k in ks]
+        queued.append((rate, enc, ks) + tuple(ops.wave_flac(src, src_off, bounds, sel, rate, level=levels if any(levels) else None)))
+        backend_stats["flac_calls"] += 1
+        backend_stats["flac_requests"] += len(ks)
     for rate, enc, ks, data, out_len, out_off in queued:
-        if any(silence[k] for k in ks):
+        flac = enc in FLAC_ENCODINGS
+        if flac or any(silence[k] for k in ks):   # (a FLAC stream's length is known on the device alone)
             sizes = out_len.cpu().tolist()
             backend_stats["d2h_copies"] += 1
         else:
             sizes = [resampled_length(joined[k], target_sample_rate, rate) for k in ks]
+        if flac:
+            # `wave_flac` puts each stream at the offset its VERBATIM bound allows for, so between two streams lies room that nobody wrote:
+            # the streams are joined on the device, and ONE download brings exactly their bytes and nothing of their PCM
+            slices = [data[off:off + m] for off, m in zip(out_off, sizes)]
+            # from here on `data` is the joined streams and `out_off` where each starts in them, so that the download and the split
+            # below are the other formats' (a stream is uint8: one byte per unit of `sizes`)
+            data, out_off = slices[0] if len(slices) == 1 else torch.cat(slices), np.cumsum([0] + sizes[:-1]).tolist()
+            backend_stats["flac_bytes"] += sum(sizes)
         host = data.cpu().numpy()
         backend_stats["d2h_copies"] += 1
         for k, off, m in zip(ks, out_off, sizes):
@@ -980,16 +953,13 @@ def _finish_on_device(requests, fade, silence, formats, loudness=None, flac_leve
 
 
 class SpanTicket:
-    """One admitted request of a `SpanScheduler`: its planned units, what its planned options (`plan_request`'s `opts`) say about the finished
-    wave, and -- once the units have all ended -- `result` (`request_wave`)."""
+    """One admitted request of a `SpanScheduler`: its planned units, `spec` (`plan_request`'s `WaveSpec`: what the finished wave has to be),
+    and -- once the units have all ended -- `result` (`request_wave`)."""
 
-    def __init__(self, request, voice, units, opts, parts=None, script=None):
-        self.request, self.voice, self.units, self.remove_silence = request, voice, units, bool(opts.get("remove_silence"))
+    def __init__(self, request, voice, units, spec, parts=None, script=None):
+        self.request, self.voice, self.units, self.spec = request, voice, units, spec
         self.parts = parts if parts is not None else [(voice, units)]   # [(voice, its units)]: one per segment of a script
         self.script = script
-        self.sample_rate, self.encoding = delivery_format(opts.get("sample_rate"), opts.get("encoding"))
-        self.flac_level = opts.get("flac_level")
-        self.loudness = check_loudness(opts.get("loudness"))
         self.in_flight = self.cancelled = self.done = False
         self.result = None
 
@@ -1020,7 +990,7 @@ class SpanScheduler:
     profiles/r07_admission_bench.txt) that boundary cost is 3.3 ms with 8 units in flight, 2.3 % of an 8-step span (4.6 % of a 4-step one),
     and 8 is the shortest span whose median time to result on the trace was not above `MicroBatcher`'s.
 
-    Finished requests leave through `finish_requests` (a request's `remove_silence`, `loudness`, `sample_rate` and `encoding` options included); with `device_backend=True` their chunk
+    Finished requests leave through `finish_requests`' path with their planned `WaveSpec`; with `device_backend=True` their chunk
     waves stay on the device and their results are int16 PCM from one `ops.wave_finish` call per boundary."""
 
     def __init__(self, model_obj, vocoder, span_steps=span_steps, max_frames=None, max_requests=None, mel_spec_type=mel_spec_type, target_rms=target_rms,
@@ -1062,7 +1032,7 @@ class SpanScheduler:
                                                            sway_sampling_coef=opts["sway_sampling_coef"], generator=plan.generator, **extra)
                                   for tokens, frames in units]))
         plan.commit()   # every chunk was planned: the caller's generator moves
-        ticket = SpanTicket(request, plan.voice, [u for _, us in parts for u in us], opts, parts, plan.script)
+        ticket = SpanTicket(request, plan.voice, [u for _, us in parts for u in us], plan.spec, parts, plan.script)
         self.waiting.append(ticket)
         return ticket
 
@@ -1087,10 +1057,8 @@ class SpanScheduler:
         got = _chunk_waves(groups, self.vocoder, self.mel_spec_type, self.target_rms, on_device=self.device_backend, want_specs=False)
         first = np.cumsum([0] + [len(t.parts) for t in tickets])
         chunk_waves = [request_chunk_waves(t, got[first[i]:first[i + 1]]) for i, t in enumerate(tickets)]
-        results = finish_requests(chunk_waves, [request_text(t.request) for t in tickets], self.cross_fade_duration, [t.remove_silence for t in tickets],
-                                  device_backend=self.device_backend, want="pcm16" if self.device_backend else "float",
-                                  sample_rate=[t.sample_rate for t in tickets], encoding=[t.encoding for t in tickets], flac_level=[t.flac_level for t in tickets],
-                                  loudness=[t.loudness for t in tickets])
+        results = _finish_specs(chunk_waves, [request_text(t.request) for t in tickets], self.cross_fade_duration, [t.spec for t in tickets],
+                                self.device_backend, "pcm16" if self.device_backend else "float")
         for t, result in zip(tickets, results):
             t.result, t.done, t.in_flight = result, True, False
 

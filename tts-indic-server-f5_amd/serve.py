@@ -49,6 +49,8 @@ from .wave_codec import delivery_bytes, pcm16, wav_bytes, wav_stream_header  # n
 log = logging.getLogger(__name__)
 
 EDIT_OPTIONS = ("nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "flac_level")   # a speech edit has no `speed`: its durations are planned
+# the delivery options an edit takes, in the order the routes check them (`infer.REQUEST_OPTIONS`'): all but `remove_silence`, the recording keeps its pauses
+EDIT_DELIVERY = tuple(k for k in infer.REQUEST_OPTIONS if k in infer.DELIVERY_OPTIONS and k != "remove_silence")
 # most ODE steps one library call accepts per method: 128 time points (f5hip precompute_time); midpoint uses 2 per step, RK4 3 per step + 1
 MAX_NFE_STEP = {"euler": 128, "midpoint": 64, "rk4": 42}
 
@@ -58,11 +60,9 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
     the routes return as 400.  `speed` finite and > 0; `nfe_step` an integer in 1..MAX_NFE_STEP[ode_method]; `cfg_strength` and
     `sway_sampling_coef` finite; `seed` an integer in 0..2**63 - 1; `ode_method` one of MAX_NFE_STEP's names.  `ode_method` (the argument)
     is the model's solver: `nfe_step`'s upper limit follows the request's own `ode_method` when it sets one, else the model's.
-    `remove_silence` a bool (False is dropped like None: the request is then what it is without the option).  `sample_rate` an integer in
-    `infer.OUTPUT_SAMPLE_RATES`, `encoding` one of `infer.OUTPUT_ENCODINGS` or "flac" (`infer.FLAC_ENCODINGS`); 24000 and "pcm16", what a
-    request gets anyway, are dropped too.  `loudness` a finite number of LUFS within `infer.LOUDNESS_RANGE` (`infer.check_loudness`), not a bool.
-    `flac_level` the int 0 or 1 (`infer.check_flac_level`; not a bool, not "1"), and only beside `encoding` "flac": with any other encoding
-    it is refused, never ignored; 0, what a FLAC request gets anyway, is then dropped."""
+    The delivery options by `infer.WaveSpec`'s validators, one by one and then together (a `flac_level` beside another encoding is refused,
+    never ignored); `remove_silence` must be a bool, and `flac_level` is not "1".  What a request gets anyway -- False, 24000, "pcm16",
+    level 0 -- is dropped like None: the request is then what it is without the option."""
     out = {}
     own = options.get("ode_method") if "ode_method" in allowed else None
     if own is not None:
@@ -110,10 +110,9 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
             if k == "speed" and v <= 0:
                 raise ValueError(f"speed must be greater than 0 (got {v}).")
         out[k] = v
-    if "flac_level" in out:
-        infer.request_flac_level(out["flac_level"], out.get("encoding"))   # ValueError: "flac_level needs encoding 'flac' ..."
-        if out["flac_level"] == 0:
-            del out["flac_level"]
+    infer.WaveSpec.of(out)                              # the delivery options together.  ValueError: "flac_level needs encoding 'flac' ..."
+    if out.get("flac_level") == 0:
+        del out["flac_level"]
     return out
 
 
@@ -653,16 +652,9 @@ class TTSManager:
         options (`speed`, `nfe_step`, `cfg_strength`, `sway_sampling_coef`) are this request's own (None: `self.opts`); `seed` draws its noise from its own
         generator (`infer.request_generator`), so the same seeded request gives the same audio whatever it is batched with (shape-invariant
         attention, one GPU).  `ode_method` ("euler", "midpoint", "rk4"; None: the model's): requests of different solvers share a batch, and
-        the option reaches the model object only for a request that sets it.  `remove_silence=True`: the reference's
-        `remove_silence_for_generated_wav` -- pauses of 1 s or more shrink to 500 ms on each side -- and the result is int16 PCM
-        (`audio_prep.remove_silence_pcm` of the quantised wave); with `device_backend` every result is int16 PCM.  `sample_rate` (one of
-        `infer.OUTPUT_SAMPLE_RATES`) and `encoding` ("pcm16", "mulaw", "alaw", "flac"): the delivery format, `infer.deliver_pcm16` of the
-        request's 24 kHz int16 PCM -- int16 at that rate, uint8 G.711 code bytes, or with "flac" a uint8 array that holds the lossless FLAC
-        stream of the samples at that rate (`infer.encode_flac`) -- computed on the device with `device_backend`, the same bytes either way;
-        24000 and "pcm16" (or None) change nothing.  `flac_level` (0 or 1, only beside "flac"): 1 adds LPC subframes to the stream's
-        candidates (`infer.encode_flac(..., level=1)`: never larger, the same samples).  `loudness` (LUFS, -40 .. -5): the result is int16 PCM moved to that programme
-        loudness (ITU-R BS.1770-4; `infer.normalise_loudness_pcm16`, sample peak at most -1 dBFS) after silence removal and before the
-        delivery format -- in the batch's one `ops.wave_loudness` call with `device_backend`, the same bytes either way."""
+        the option reaches the model object only for a request that sets it.  The `infer.DELIVERY_OPTIONS` (`remove_silence`, `loudness`,
+        `sample_rate`, `encoding`, `flac_level`: see `infer.WaveSpec`) make the result `infer.finish_pcm16` of the wave's int16 PCM --
+        computed on the device with `device_backend`, where every result is int16 PCM, and the same bytes either way."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         return self.model(text, ref_audio_path=ref_audio_path, ref_text=ref_text, **options)   # (`_call`, which checks the options)
@@ -676,25 +668,22 @@ class TTSManager:
         if their batch has not started.  Errors about the model or the voice are raised here, not on the first `next()`.  Options as in
         `synthesize`; with a `seed`, the first chunk and the remaining chunks draw from the request's one generator in chunk order, so the
         pieces equal `synthesize`'s wave with that seed.  The remaining chunks keep the first chunk's `ode_method`.  With `sample_rate` /
-        `encoding` the pieces come in the delivery format (int16 at that rate, or uint8 code bytes): each float32 piece goes through
-        `infer.quantise_pcm16`, an `infer.StreamResampler` and the encoder on the host, and their concatenation equals `synthesize`'s result
-        with the same options byte for byte.  With "flac" the pieces are uint8: the 42-byte stream header with the totals unknown (zero)
-        first -- it comes from the first `next()` once the first chunk is synthesized, so a failing first chunk raises there before any
-        byte --, then the frames each piece completes (`infer.StreamFlacEncoder`), then the short last frame; behind the header they equal
-        `synthesize`'s stream, and both decode to the same samples.  `remove_silence` and `loudness` need the whole wave: ValueError."""
+        `encoding` the pieces come in the delivery format, each float32 piece through an `infer.StreamDelivery` on the host (int16 at that
+        rate, uint8 code bytes, or for "flac" the 42-byte stream header with the totals unknown and then the frames as they complete), and
+        their concatenation equals `synthesize`'s result with the same options byte for byte (for "flac": behind the header, and both decode
+        to the same samples).  The header comes from the first `next()` once the first chunk is synthesized, so a failing first chunk raises
+        there before any byte.  `remove_silence` and `loudness` need the whole wave: ValueError."""
         return self._serve(lambda: self._voice(ref_audio_path, ref_text), text, options, stream=True)
 
     def _stream(self, voice, ref_text, head, tail, opts=None):
-        opts = dict(opts or {})               # the delivery format is applied here, piece by piece: the head and tail requests stay plain
-        fmt = infer.delivery_format(opts.pop("sample_rate", None), opts.pop("encoding", None))
-        level = infer.request_flac_level(opts.pop("flac_level", None), fmt[1])
-        return self._stream_requests(self._request(voice, ref_text, head, opts), self._request(voice, ref_text, tail, opts) if tail else None, fmt,
-                                     flac_level=level)
+        spec = infer.WaveSpec.of(opts or {})   # the delivery format is applied here, piece by piece: the head and tail requests stay plain
+        opts = {k: v for k, v in (opts or {}).items() if k not in infer.DELIVERY_OPTIONS}
+        return self._stream_requests(self._request(voice, ref_text, head, opts), self._request(voice, ref_text, tail, opts) if tail else None, spec)
 
-    def _stream_requests(self, head_request, tail_request, fmt, tail_pieces=None, flac_level=0):
-        """A stream of two requests: the head's chunk waves, then (unless None) the tail's, through one `infer.StreamJoiner` and the delivery
-        format `fmt` (a FLAC stream at `flac_level`).  `tail_pieces(joiner, result)`: the pieces the tail's result releases (default: its chunk waves pushed in order; a
-        script cuts the joiner between its segments)."""
+    def _stream_requests(self, head_request, tail_request, spec, tail_pieces=None):
+        """A stream of two requests: the head's chunk waves, then (unless None) the tail's, through one `infer.StreamJoiner` and, unless
+        `spec` has the plain format, an `infer.StreamDelivery`.  `tail_pieces(joiner, result)`: the pieces the tail's result releases
+        (default: its chunk waves pushed in order; a script cuts the joiner between its segments)."""
         lock, state = threading.Lock(), {"closed": False, "tail": None, "error": None}
         started = threading.Event()
         tail = tail_request is not None
@@ -742,41 +731,15 @@ class TTSManager:
                 cancel()
 
         def delivered():
-            resampler = infer.StreamResampler(fmt[0])
-            flac = infer.StreamFlacEncoder(fmt[0], flac_level) if fmt[1] in infer.FLAC_ENCODINGS else None
-            if flac is not None:                  # uint8 pieces: the frames each piece completes
-                encode = lambda pcm: np.frombuffer(flac.feed(pcm), dtype=np.uint8)   # noqa: E731
-            else:
-                encode = (lambda pcm: pcm) if fmt[1] == "pcm16" else (lambda pcm: infer.encode_g711(pcm, fmt[1]))
-            gen = pieces()
+            delivery, gen = infer.StreamDelivery(spec), pieces()
             try:
-                # flac: the 42 bytes (totals unknown) go out once the first piece is there, never before it: the consumer's first `next()`
-                # still runs the head request, so a failing head is an exception there and not a body of a bare header
-                header = flac is not None
                 for piece in gen:
-                    if header:
-                        header = False
-                        yield np.frombuffer(flac.header(), dtype=np.uint8)
-                    out = resampler.feed(infer.quantise_pcm16(piece))
-                    if len(out):
-                        out = encode(out)
-                        if len(out):
-                            yield out
-                if header:                        # (a request without a piece is the header alone)
-                    yield np.frombuffer(flac.header(), dtype=np.uint8)
-                out = resampler.flush()
-                if len(out):
-                    out = encode(out)
-                    if len(out):
-                        yield out
-                if flac is not None:
-                    out = flac.flush()            # the short last frame
-                    if out:
-                        yield np.frombuffer(out, dtype=np.uint8)
+                    yield from delivery.feed(piece)
+                yield from delivery.finish()
             finally:
                 gen.close()
 
-        return SynthesisStream(pieces() if fmt == (infer.target_sample_rate, "pcm16") else delivered(), cancel)
+        return SynthesisStream(pieces() if spec.plain_format else delivered(), cancel)
 
     def _script_segments(self, text, voices, gap):
         """The host part of a script request, every refusal a ValueError before anything is queued: `voices` needs "main", `text` at least
@@ -841,8 +804,8 @@ class TTSManager:
             return self._run_batch([req])[0]
         if "seed" in opts:
             opts["generator"] = infer.request_generator(opts.pop("seed"))
-        fmt = infer.delivery_format(opts.pop("sample_rate", None), opts.pop("encoding", None))
-        level = infer.request_flac_level(opts.pop("flac_level", None), fmt[1])
+        spec = infer.WaveSpec.of(opts)            # (applied to the pieces, as in `_stream`)
+        opts = {k: v for k, v in opts.items() if k not in infer.DELIVERY_OPTIONS}
         chunked = [(voice, ref_text, infer.request_chunks(ref_text, voice.seconds, piece), speed) for voice, ref_text, piece, speed in segments]
         voice, ref_text, chunks, speed = chunked[0]
         head = self._request(voice, ref_text, chunks[:1], dict(opts, speed=speed) if speed is not None else opts)
@@ -858,7 +821,7 @@ class TTSManager:
                         yield from joiner.pieces([np.zeros(gap_samples, dtype=np.float32)], cut=True)
                 yield from joiner.pieces(waves)
 
-        return self._stream_requests(head, infer.ScriptRequest(rest, opts, gap) if rest else None, fmt, tail_pieces, flac_level=level)
+        return self._stream_requests(head, infer.ScriptRequest(rest, opts, gap) if rest else None, spec, tail_pieces)
 
     def edit(self, audio, target_text, parts_to_edit, fix_duration=None, *, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
              seed=None, ode_method=None, sample_rate=None, encoding=None, loudness=None, flac_level=None):
@@ -866,14 +829,12 @@ class TTSManager:
         bytes or a (tensor, sr) pair) so that it speaks `target_text`, with this manager's sampler settings unless the call sets its own
         (`seed`: the edit's noise from its own generator; `ode_method`: the edit's solver, handed on only when set).  The host preparation runs outside the device lock, the sampler and vocoder
         under it (not through the micro-batcher); with a `ShardedSampler` on rank 0's own model.  Returns the wave (float32, 24 kHz) -- with
-        `sample_rate` / `encoding`, `infer.deliver_pcm16` of its int16 PCM (host functions); with `loudness` (LUFS), that PCM first goes through
-        `infer.normalise_loudness_pcm16` and the result is int16.  `flac_level` (0 or 1, only beside `encoding` "flac"): the FLAC stream's level."""
+        any of `sample_rate`, `encoding`, `loudness` and `flac_level` (`infer.WaveSpec`), `infer.finish_pcm16` of its int16 PCM on the host."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = dict(self.opts, **self.request_options(EDIT_OPTIONS, nfe_step=nfe_step, cfg_strength=cfg_strength,
                                                       sway_sampling_coef=sway_sampling_coef, seed=seed, ode_method=ode_method))
-        fmt = self.request_options(("sample_rate", "encoding", "flac_level"), sample_rate=sample_rate, encoding=encoding, flac_level=flac_level)
-        loudness = self.request_options(("loudness",), loudness=loudness).get("loudness")
+        delivery = self.request_options(EDIT_DELIVERY, sample_rate=sample_rate, encoding=encoding, flac_level=flac_level, loudness=loudness)
         model_obj = getattr(self.model_obj, "local", self.model_obj)
         # host work (read, mono mix, resample, plan, tokens) and every rejection happen before the device lock is taken (a FLAC recording is
         # decoded under it with `device_decode`, after everything that needs no samples has been refused)
@@ -888,10 +849,7 @@ class TTSManager:
                                                     nfe_step=opts["nfe_step"], cfg_strength=opts["cfg_strength"],
                                                     sway_sampling_coef=opts["sway_sampling_coef"], **extra)
         wave = np.asarray(wave, dtype=np.float32)
-        if loudness is None and not fmt:
-            return wave
-        pcm = infer.normalise_loudness_pcm16(infer.quantise_pcm16(wave), loudness)       # (None: the PCM as it is)
-        return infer.deliver_pcm16(pcm, fmt.get("sample_rate"), fmt.get("encoding"), fmt.get("flac_level")) if fmt else pcm
+        return infer.finish_pcm16(infer.quantise_pcm16(wave), infer.WaveSpec.of(delivery)) if delivery else wave
 
 
 class HTTPError(Exception):
@@ -943,10 +901,8 @@ def container_format(response_format, encoding=None) -> str:
 def response_body(audio, options: dict, response_format: str = "wav") -> io.BytesIO:
     """The response body of a request's result in the delivery format its `options` name: a WAV file (`wav_bytes`), with "pcm" the
     headerless little-endian samples / code bytes, and for `encoding` "flac" the FLAC stream the result holds."""
-    rate, enc = infer.delivery_format(options.get("sample_rate"), options.get("encoding"))
-    if enc in infer.FLAC_ENCODINGS:
-        return io.BytesIO(delivery_bytes(audio, enc))
-    return io.BytesIO(delivery_bytes(audio, enc)) if response_format == "pcm" else wav_bytes(audio, rate, enc)
+    spec = infer.WaveSpec.of(options)
+    return io.BytesIO(delivery_bytes(audio, spec.encoding)) if spec.flac or response_format == "pcm" else wav_bytes(audio, *spec.format)
 
 
 def synthesize_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None,
@@ -1035,16 +991,12 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     `sway_sampling_coef`, `seed`, `ode_method` ("euler", "midpoint" or "rk4": the request's ODE solver) and (speech routes) `speed` and
     `remove_silence` (true: pauses of 1 s or more are cut down to 500 ms on each side; 400 together with `"stream": true`), checked
     before anything is queued (400 with `check_request_options`'s message); an omitted field is the manager's setting (`ode_method`: the
-    model's).  With a `seed`, the same request returns the same audio.  The delivery format, on every route: `sample_rate` (one of
-    `infer.OUTPUT_SAMPLE_RATES`), `encoding` ("pcm16", "mulaw" or "alaw": G.711, one byte per sample) and `response_format` ("wav", or "pcm"
-    for the headerless samples / code bytes as `audio/pcm`); streamed or not, the body's samples are the same bytes.  `encoding: "flac"` is
-    its own container: the body is the native FLAC stream of the samples (`infer.encode_flac`, lossless) as `audio/flac` with a `.flac` file
-    name, and `response_format` must be absent (400 with "wav" or "pcm" beside it); streamed, the stream header comes with the totals unknown.
-    `flac_level` (the integer 0 or 1, every route; absent means 0): at 1 the FLAC stream's full blocks may be LPC subframes, which makes it
-    smaller and never larger and decodes to the same samples; anything else, and a `flac_level` beside an `encoding` that is not "flac", is a 400.
-    `loudness` (a number of LUFS from -40 to -5, every route): the body's samples are moved to that programme loudness (ITU-R BS.1770-4) with
-    the sample peak at most -1 dBFS, after silence removal and before the delivery format; it is measured on the whole wave, so it is a 400
-    together with `"stream": true` (`STREAM_LOUDNESS`)."""
+    model's).  With a `seed`, the same request returns the same audio.  Every route takes `sample_rate`, `encoding`, `flac_level` and
+    `loudness` as `infer.WaveSpec` describes them (a bad value or combination is a 400; `loudness` is measured on the whole wave, so it is
+    a 400 together with `"stream": true`: `STREAM_LOUDNESS`) and `response_format` ("wav", or "pcm" for the headerless samples / code bytes
+    as `audio/pcm`); streamed or not, the body's samples are the same bytes.  `encoding: "flac"` is its own container: the body is the
+    native FLAC stream as `audio/flac` with a `.flac` file name, and `response_format` must be absent (400 with "wav" or "pcm" beside it);
+    streamed, the stream header comes with the totals unknown."""
     from fastapi import APIRouter, FastAPI, HTTPException
     from starlette.responses import StreamingResponse
 
@@ -1117,7 +1069,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         # the synthesis runs in the thread pool, one piece at a time; leaving early (client gone, error) closes the generator,
         # which cancels the request's remaining chunks if their batch has not started
         try:
-            rate, enc = infer.delivery_format(opts.get("sample_rate"), opts.get("encoding"))
+            rate, enc = infer.WaveSpec.of(opts).format
             if fmt == "wav":
                 yield wav_stream_header(rate, enc)
             if first is not None:
@@ -1189,7 +1141,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     def _run_edit(req):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
-        opts = _options(req, EDIT_OPTIONS + ("sample_rate", "encoding", "loudness"))
+        opts = _options(req, tuple(dict.fromkeys(EDIT_OPTIONS + EDIT_DELIVERY)))
         fmt = _response_format(req, opts)
         try:
             raw = base64.b64decode(req.audio, validate=True)

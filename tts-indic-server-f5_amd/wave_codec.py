@@ -1,11 +1,14 @@
 """Waves in and out of the server, with nothing of the model in it: reading WAV files (`load_wav`), torchaudio's polyphase sinc resampler
 (`rate_pair`, `resample_taps`, `resample_sinc_hann`) with its tap-table caches, the integer resampler of finished PCM (`resample_pcm16`,
-`StreamResampler`), the BS.1770 loudness meter and normaliser (`measure_loudness`, `normalise_loudness_pcm16`), G.711 (`encode_g711`, `decode_g711`), FLAC (`encode_flac`, `decode_flac`, `StreamFlacEncoder`; the whole format in: `read_flac`, `load_audio`), the delivery format of a request (`delivery_format`, `deliver_pcm16`) and the bytes
-of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
+`StreamResampler`), the BS.1770 loudness meter and normaliser (`measure_loudness`, `normalise_loudness_pcm16`), G.711 (`encode_g711`,
+`decode_g711`), FLAC (`encode_flac`, `decode_flac`, `StreamFlacEncoder`; the whole format in: `read_flac`, `load_audio`), the delivery
+format of a request (`delivery_format`, `deliver_pcm16`), its five delivery options as one value (`WaveSpec`; `StreamDelivery` applies it
+to a stream) and the bytes of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
 round; `infer` and `serve` hand every public name on (`infer.load_wav`, `serve.wav_bytes`, ...)."""
 from __future__ import annotations
 
 import collections
+import dataclasses
 import hashlib
 import io
 import math
@@ -372,6 +375,69 @@ def deliver_pcm16(pcm, sample_rate=None, encoding=None, flac_level=None) -> np.n
     if enc in FLAC_ENCODINGS:
         return encode_flac(pcm, rate, level)
     return pcm if enc == "pcm16" else encode_g711(pcm, enc)
+
+
+DELIVERY_OPTIONS = ("remove_silence", "loudness", "sample_rate", "encoding", "flac_level")
+WHOLE_WAVE = ("remove_silence, sample_rate and encoding need the request's whole wave: they are not available for a list of chunk texts (a streamed "
+              "request, whose owner applies the delivery format piece by piece: StreamResampler, encode_g711) or with join=False")
+WHOLE_WAVE_LOUDNESS = ("loudness is measured on the request's whole wave: it is not available for a list of chunk texts, on a streaming path or "
+                       "with join=False")
+
+
+@dataclasses.dataclass(frozen=True)
+class WaveSpec:
+    """What a request asks of its finished wave, the five `DELIVERY_OPTIONS` as one immutable value: the planner makes it (`WaveSpec.of`),
+    and every finishing path -- `infer.finish_pcm16` on the host, `infer._finish_on_device`, `StreamDelivery` for a stream -- reads it.
+    All five are pure functions of the request's canonical result, its joined 24 kHz wave quantised to int16 PCM, applied in this order:
+      `remove_silence`  the reference's `remove_silence_for_generated_wav` (`audio_prep.remove_silence_pcm`): pauses of 1 s or more shrink
+                        to 500 ms on each side; the result is int16 PCM whatever the caller wanted otherwise.
+      `loudness`        a programme loudness target in LUFS within LOUDNESS_RANGE (ITU-R BS.1770-4; `normalise_loudness_pcm16`: the sample
+                        peak stays at or below -1 dBFS); None keeps the level as synthesized.
+      `sample_rate`, `encoding`  the delivery format (`deliver_pcm16`): one of OUTPUT_SAMPLE_RATES (`resample_pcm16`), then "pcm16", "mulaw" /
+                        "alaw" (`encode_g711`: uint8 code bytes) or "flac" (`encode_flac`: a uint8 array that holds the whole stream).
+      `flac_level`      0, or 1 for LPC subframes among the candidates of the stream's full blocks (never larger, the same samples); only a
+                        "flac" request may name one: beside any other encoding a level is refused, never ignored.
+    The first two, and a format other than 24 kHz "pcm16", need the request's whole wave (`needs_whole_wave`): they are refused for a list
+    of chunk texts and with join=False; a stream applies the format piece by piece and refuses the other two."""
+    remove_silence: bool = False
+    loudness: float | None = None
+    sample_rate: int = SAMPLE_RATE
+    encoding: str = "pcm16"
+    flac_level: int = 0
+
+    @classmethod
+    def of(cls, options) -> "WaveSpec":
+        """The spec of a mapping of options: a missing key or None is the default, other keys are ignored.  The one place where the five are
+        checked together -- `check_loudness`, `request_flac_level`, `delivery_format`, in that order, with their messages (ValueError)."""
+        get = options.get
+        loudness = check_loudness(get("loudness"))
+        level = request_flac_level(get("flac_level"), get("encoding"))
+        return cls(bool(get("remove_silence")), loudness, *delivery_format(get("sample_rate"), get("encoding")), level)
+
+    @property
+    def format(self):
+        return self.sample_rate, self.encoding
+
+    @property
+    def plain_format(self) -> bool:
+        return self.format == (SAMPLE_RATE, "pcm16")
+
+    @property
+    def flac(self) -> bool:
+        return self.encoding in FLAC_ENCODINGS
+
+    @property
+    def gain_constant(self):
+        """`loudness_gain_constant` of the target, what `ops.wave_loudness` takes; None without one."""
+        return None if self.loudness is None else loudness_gain_constant(self.loudness)
+
+    def needs_whole_wave(self, streamed=False) -> bool:
+        """Whether the request cannot be handed out chunk by chunk.  `streamed`: the format does not count, the stream's owner applies it."""
+        return self.remove_silence or self.loudness is not None or not (streamed or self.plain_format)
+
+    def whole_wave_message(self) -> str:
+        """The refusal of a request that `needs_whole_wave` where it cannot have it: `WHOLE_WAVE_LOUDNESS` when `loudness` is the reason."""
+        return WHOLE_WAVE_LOUDNESS if self.loudness is not None and not self.remove_silence else WHOLE_WAVE
 
 
 # ----------------------------------------- loudness: the mono programme loudness of ITU-R BS.1770-4 on a request's 24 kHz int16 PCM, in integers
@@ -915,6 +981,38 @@ class StreamFlacEncoder:
     def flush(self) -> bytes:
         ready, self.pending = self.pending, np.zeros(0, dtype=np.int16)
         return self._emit(ready)
+
+
+class StreamDelivery:
+    """`deliver_pcm16` of a `WaveSpec` one float32 piece at a time: `feed(piece)` returns the output pieces that piece releases (the piece
+    through `quantise_pcm16`, a `StreamResampler`, and `encode_g711` or a `StreamFlacEncoder`; no empty ones), `finish()` the rest: the
+    resampler's flush and, for FLAC, the short last frame.  Their concatenation equals `deliver_pcm16` of the quantised whole byte for byte --
+    for FLAC from byte 42 on: the 42-byte header with the totals unknown comes in front of what the first piece releases, never before a
+    first piece exists (a stream's first `next()` still runs the request), and from `finish()` for a stream that never had a piece."""
+
+    def __init__(self, spec):
+        self.resampler, self.encoding = StreamResampler(spec.sample_rate), spec.encoding
+        self.flac = StreamFlacEncoder(spec.sample_rate, spec.flac_level) if spec.flac else None
+        self.header_due = self.flac is not None
+
+    def _header(self):
+        due, self.header_due = self.header_due, False
+        return [np.frombuffer(self.flac.header(), dtype=np.uint8)] if due else []
+
+    def _encoded(self, pcm):
+        if len(pcm) and self.flac is not None:
+            pcm = np.frombuffer(self.flac.feed(pcm), dtype=np.uint8)   # the frames the samples complete
+        elif len(pcm) and self.encoding != "pcm16":
+            pcm = encode_g711(pcm, self.encoding)
+        return [pcm] if len(pcm) else []
+
+    def feed(self, piece) -> list:
+        return self._header() + self._encoded(self.resampler.feed(quantise_pcm16(piece)))
+
+    def finish(self) -> list:
+        out = self._header() + self._encoded(self.resampler.flush())
+        last = self.flac.flush() if self.flac is not None else b""
+        return out + ([np.frombuffer(last, dtype=np.uint8)] if last else [])
 
 
 class _FlacBits:
