@@ -630,6 +630,32 @@ int f5hip_flac_decode(int32_t n, const uint8_t* data_dev, int64_t nbytes, const 
  * STREAMINFO declares, and never more than max_samples. */
 int64_t f5hip_flac_decode_bound(int64_t total, int64_t stream_bytes, int64_t max_samples);
 
+/* The reference-clip pre-step (F/infer/utils_infer.py:282-350 between reading the clip and writing the temporary WAV) for n uploaded clips
+ * of ONE sample rate in one call, bit for bit audio_prep.preprocess_ref_segment: clip at a pause (windows of 1000 ms below -50 dBFS, else of
+ * 100 ms below -40 dBFS, kept silence 1000 ms, seek step 10 ms, the "more than 6 s so far and more than 15 s with this chunk" stop, overlapping
+ * padded ranges split at their midpoint, else a hard cut at 15 000 ms), strip the silent edges (-42 dBFS: leading in 10 ms windows, trailing
+ * millisecond by millisecond with the reference's running subtraction), append 50 ms of silence.
+ *   n_in[i], channels[i]   host; clip i = n_in[i] frames (0 is valid) of channels[i] interleaved int16 samples, clips packed back to back
+ *   clip_short[i]          host; zero: the clip is not clipped at a pause (edges and tail only)
+ *   frames_dev, n_samples  the packed int16 samples and their count, which must equal sum(n_in * channels)
+ *   out_dev                fp32, room for f5hip_ref_prestep_bound samples: clip i as channels[i] planes of its output length, x / 32768,
+ *                          the clips packed back to back by their OUTPUT lengths -- f5hip_ref_frontend's `wave_dev` as it stands
+ *   info_dev               int32 [n][2]: the output frames of clip i (its 50 ms tail included) and whether any output sample is non-zero
+ * Every rms comparison is made on exact int64 sums of squares (rms = floor(sqrt(S / n)) >= r  <=>  S >= r^2 n for the thresholds 104, 328
+ * and 261 and fewer than 2^23 samples per window); fp64 appears only in the frame of a millisecond, the length in milliseconds and the
+ * running subtraction, each a single IEEE operation as on the host (csrc/ref_prestep_core.h, which tools/ref_prestep_check.cpp runs on the
+ * CPU under sanitizers).  THREE launches whatever n and whatever the clips hold (cells: the sum of squares of every millisecond; rule: one
+ * block per clip -- prefix sums, both parameter sets, the choice, the hard cut, the edges; gather: ranges to planar fp32, tail, flag), no
+ * host synchronisation once its workspace has grown to the call's size: the clip table goes through pinned staging on `stream` (counters
+ * ref_prestep_launches, ref_prestep_clips).  Clip i's output equals its own single-clip call's bit for bit.
+ * Refused before the first launch: n < 1, rate < 11 025, a negative frame count, channels[i] < 1, rate x channels[i] >= 2^23, counts that
+ * do not add up to n_samples, more than 2^31 - 1 samples in or out, a null pointer. */
+int f5hip_ref_prestep(int32_t n, const int32_t* n_in, const int32_t* channels, const uint8_t* clip_short, const int16_t* frames_dev, int64_t n_samples,
+                      int32_t rate, float* out_dev, int32_t* info_dev, void* stream);
+
+/* Samples out_dev needs: sum((n_in[i] + 50 ms of frames) * channels[i]); -1 for arguments f5hip_ref_prestep refuses. */
+int64_t f5hip_ref_prestep_bound(int32_t n, const int32_t* n_in, const int32_t* channels, int32_t rate);
+
 #ifdef __cplusplus
 }
 #endif

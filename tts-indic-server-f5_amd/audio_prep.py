@@ -234,6 +234,193 @@ def preprocess_ref_segment(seg: PcmSegment, clip_short: bool = True, show_info=p
     return remove_silence_edges(seg) + PcmSegment.silent(50, seg.rate, seg.frames.shape[1])
 
 
+# ---------------------------------------------------------------------------------------------- the pre-step as ranges
+# `preprocess_ref_ranges` restates `preprocess_ref_segment` as index arithmetic on the SOURCE frames: what the device call mirrors
+# (csrc/ref_prestep_core.h, csrc/ref_prestep.h, `ops.ref_prestep`).  `preprocess_ref_segment` stays the definition.
+#
+# Every rms comparison is made on integers.  A window of n samples with the exact integer sum of squares S has rms = floor(sqrt(S / n)) in
+# fp64 (`rms_ms`), and for an integer r
+#     floor(sqrt(S / n)) >= r   <=>   S >= r^2 n.
+# Why this is exact for the sums that can occur (r <= 328, n < 2^23 samples per window, i.e. rate x channels < 2^23):
+#   * S <= 2^30 n < 2^53, so S and n are exact in fp64, and S / n and its square root are single, correctly rounded operations, both
+#     monotone, with r^2 and r representable: S >= r^2 n gives S / n >= r^2, a quotient that rounds to at least r^2 and a root of at least r;
+#   * S < r^2 n gives S / n <= r^2 - 1 / n with 1 / n > 2^-23, while the fp64 spacing below r^2 <= 2^17 is 2^-36 or finer: the rounded
+#     quotient stays 2^-24 or more below r^2, its root 2^-24 / (2 r) >= 2^-34 or more below r, and the spacing below r < 2^9 is 2^-44:
+#     no integer square (and no integer) lies within reach of either rounding.
+# `rms <= thresh` of detect_silence is rms <= T with T = floor(thresh), i.e. S < (T + 1)^2 n: the form wave_silence_kernel uses.  The two
+# dBFS comparisons of the edge trim become rms < r and rms >= r for integer thresholds found by evaluating `_dbfs_of_rms` itself, which is
+# monotone in the integer rms.  fp64 remains only in the frame of a millisecond (`_frame`), the length in milliseconds (`__len__`) and the
+# running subtraction of the trailing trim: each a single IEEE operation here and on the device.
+REF_CLIP_PASSES = ((1000, -50), (100, -40))      # (min_silence_len ms, silence_thresh dBFS), tried in turn
+REF_KEEP_MS, REF_SEEK_MS, REF_MIN_MS, REF_MAX_MS, REF_EDGE_DBFS, REF_TAIL_MS = 1000, 10, 6000, 15000, -42, 50
+
+
+def silence_square(silence_thresh) -> int:
+    """(T + 1)^2 for T = floor of detect_silence's amplitude threshold: a window is silent iff S < silence_square * n."""
+    return (math.floor((10 ** (silence_thresh / 20.0)) * _MAX_AMP) + 1) ** 2
+
+
+def edge_rms_thresholds(silence_threshold=REF_EDGE_DBFS):
+    """(lead, trail): `dBFS(rms) < threshold` (leading silence) is rms < lead, `dBFS(rms) > threshold` (a loud trailing millisecond) is
+    rms >= trail, by the scalar rule itself evaluated from rms 0 upwards."""
+    lead = next(r for r in range(int(_MAX_AMP) + 2) if not _dbfs_of_rms(r) < silence_threshold)
+    trail = next(r for r in range(int(_MAX_AMP) + 2) if _dbfs_of_rms(r) > silence_threshold)
+    return lead, trail
+
+
+def _len_ms(frames: int, rate: int) -> int:
+    return int(round(1000.0 * frames / rate))
+
+
+class _ClipWalk:
+    """The sequential part of one `_clip_at_pause` pass over the silent window starts, with O(1) state: silent ranges -> non-silent
+    ranges -> padded chunks with midpoint splits -> the 6 s / 15 s stop -> frame ranges of the source (adjacent ones merged)."""
+
+    def __init__(self, n_frames, rate, msl):
+        self.N, self.rate, self.k, self.msl = n_frames, rate, rate / 1000.0, msl
+        self.L = _len_ms(n_frames, rate)
+        self.have_prev = self.first = self.pend = self.stopped = False
+        self.any_silent = False
+        self.first = True
+        self.prev = self.cur = self.prev_end = self.last_end = self.ps = self.pe = 0
+        self.ranges, self.frames = [], 0
+
+    def _frame(self, ms):
+        return min(max(int(ms * self.k), 0), self.N)
+
+    def silent_start(self, s):
+        if not self.have_prev:
+            self.cur = s
+        elif s != self.prev + REF_SEEK_MS and s > self.prev + self.msl:
+            self._silent_range(self.cur, self.prev + self.msl)
+            self.cur = s
+        self.prev, self.have_prev = s, True
+
+    def _silent_range(self, s, e):
+        self.any_silent = True
+        self._nonsilent(self.prev_end, s, True)
+        self.prev_end = self.last_end = e
+
+    def _nonsilent(self, p, s, droppable):
+        head = self.first and droppable and p == 0 and s == 0       # detect_nonsilent drops a leading [0, 0]
+        self.first = False
+        if head:
+            return
+        ns, ne = p - REF_KEEP_MS, s + REF_KEEP_MS
+        if self.pend:
+            if ns < self.pe:
+                self.pe = (self.pe + ns) // 2
+                ns = self.pe
+            self._chunk(max(self.ps, 0), min(self.pe, self.L))
+        self.ps, self.pe, self.pend = ns, ne, True
+
+    def _chunk(self, a_ms, b_ms):
+        if self.stopped:
+            return
+        fa, fb = self._frame(max(0, min(a_ms, self.L))), self._frame(max(0, min(b_ms, self.L)))
+        n = max(fb - fa, 0)
+        if _len_ms(self.frames, self.rate) > REF_MIN_MS and _len_ms(self.frames + n, self.rate) > REF_MAX_MS:
+            self.stopped = True
+            return
+        if n:
+            if self.ranges and self.ranges[-1][1] == fa:
+                self.ranges[-1][1] = fb
+            else:
+                self.ranges.append([fa, fb])
+            self.frames += n
+
+    def finish(self):
+        if self.have_prev:
+            self._silent_range(self.cur, self.prev + self.msl)
+        if not self.any_silent:
+            self._nonsilent(0, self.L, False)
+        elif self.last_end != self.L:
+            self._nonsilent(self.prev_end, self.L, True)
+        if self.pend:
+            self._chunk(max(self.ps, 0), min(self.pe, self.L))
+        return self.ranges, self.frames
+
+
+def _silent_starts(seg: PcmSegment, msl: int, square: int) -> np.ndarray:
+    """The window starts of detect_silence(seek_step 10) that are silent, by the integer comparison."""
+    L = len(seg)
+    if L < msl:
+        return np.zeros(0, dtype=np.int64)
+    last = L - msl
+    starts = np.arange(0, last + 1, REF_SEEK_MS, dtype=np.int64)
+    if last % REF_SEEK_MS:
+        starts = np.append(starts, last)
+    a, b = seg._frames(starts), seg._frames(starts + msl)
+    c = seg._cum_squares()
+    n = (b - a) * seg.frames.shape[1]
+    return starts[(n <= 0) | (c[b] - c[a] < square * n)]
+
+
+def _truncate(ranges, frames):
+    out, left = [], frames
+    for a, b in ranges:
+        if left <= 0:
+            break
+        b = min(b, a + left)
+        out.append([a, b])
+        left -= b - a
+    return out
+
+
+def preprocess_ref_ranges(seg: PcmSegment, clip_short: bool = True):
+    """`preprocess_ref_segment` as ranges: (ranges, tail_frames), the [a, b) frame ranges of `seg` whose frames, in order and followed by
+    `tail_frames` zero frames, are the frames of preprocess_ref_segment(seg, clip_short)."""
+    if seg.rate < 11025:
+        raise ValueError("reference audio below 11025 Hz is not supported on this path")
+    rate, N, C, k = seg.rate, seg.frames.shape[0], seg.frames.shape[1], seg.rate / 1000.0
+    ranges, total = ([[0, N]] if N else []), N
+    if clip_short:
+        for msl, db in REF_CLIP_PASSES:
+            walk = _ClipWalk(N, rate, msl)
+            for s in _silent_starts(seg, msl, silence_square(db)):
+                walk.silent_start(int(s))
+            ranges, total = walk.finish()
+            if _len_ms(total, rate) <= REF_MAX_MS:
+                break
+        if _len_ms(total, rate) > REF_MAX_MS:                        # slice_ms(0, 15000) of the concatenation
+            total = min(int(REF_MAX_MS * k), total)
+            ranges = _truncate(ranges, total)
+    # remove_silence_edges on the concatenation: its millisecond grid starts at its own frame 0
+    src = np.concatenate([np.arange(a, b, dtype=np.int64) for a, b in ranges]) if ranges else np.zeros(0, dtype=np.int64)
+    sq = np.diff(seg._cum_squares())[src]
+    csq = np.concatenate([[0], np.cumsum(sq)]).astype(np.int64)
+    lead_r, trail_r = edge_rms_thresholds()
+
+    def grid(ms, n_ms, n_frames):                                     # `_frames` of a segment of n_frames
+        return np.clip((np.clip(ms, 0, n_ms) * k).astype(np.int64), 0, n_frames)
+
+    L1 = _len_ms(total, rate)
+    trims = np.arange(0, L1, REF_SEEK_MS, dtype=np.int64)
+    a, b = grid(trims, L1, total), grid(trims + REF_SEEK_MS, L1, total)
+    n = (b - a) * C
+    loud = np.flatnonzero((n > 0) & (csq[b] - csq[a] >= lead_r * lead_r * n))
+    lead = int(trims[loud[0]]) if len(loud) else L1
+    x0 = int(grid(np.int64(lead), L1, total))
+    n2 = int(grid(np.int64(L1), L1, total)) - x0                      # slice_ms(lead, L1 + 1)
+    L2 = _len_ms(n2, rate)
+    end = n2 / rate
+    ms = np.arange(L2, dtype=np.int64)
+    a, b = x0 + grid(ms, L2, n2), x0 + grid(ms + 1, L2, n2)
+    n = (b - a) * C
+    loud = np.flatnonzero((n > 0) & (csq[b] - csq[a] >= trail_r * trail_r * n))
+    quiet_tail = L2 - 1 - int(loud[-1]) if len(loud) else L2
+    for _ in range(quiet_tail):                                       # the reference's own running subtraction, rounding included
+        end -= 0.001
+    x1 = x0 + int(grid(np.int64(int(end * 1000)), L2, n2))
+    out, at = [], 0
+    for a, b in ranges:                                               # concatenation frames [x0, x1) back to source frames
+        lo, hi = max(a, a + x0 - at), min(b, a + x1 - at)
+        if lo < hi:
+            out.append([int(lo), int(hi)])
+        at += b - a
+    return out, int(rate * REF_TAIL_MS / 1000.0)
+
+
 def normalize_ref_text(ref_text: str) -> str:
     """The ". " rule at the end of the reference text (F/infer/utils_infer.py:343-348)."""
     if not ref_text.endswith(". ") and not ref_text.endswith("。"):

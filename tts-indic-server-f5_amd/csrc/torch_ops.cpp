@@ -27,6 +27,7 @@
 //   torch.ops.f5hip.wave_flac(pcm[], in_off, max_len, len_dev?, sample_rate) -> (Tensor streams uint8, Tensor lengths int32, Tensor offsets int64 host)
 //   torch.ops.f5hip.wave_flac_levels(pcm[], in_off, max_len, len_dev?, sample_rate, level int32 host) -> the same, each request at its FLAC level
 //   torch.ops.f5hip.flac_decode(data, begin, end, info, total, max_samples) -> (Tensor statuses and planes int32, Tensor offsets int64 host)
+//   torch.ops.f5hip.ref_prestep(frames, n_in, channels, clip_short, rate) -> (Tensor planes fp32, Tensor info int32 [n, 2])   F/infer/utils_infer.py:282-350
 //   torch.ops.f5hip.wave_encode(pcm[], in_off, max_len, len_dev?, new_freq, encoding, taps?) -> (Tensor bytes uint8, Tensor lengths int32, Tensor offsets int64 host)
 #include "../../include/f5hip.h"
 #include "rate_pair.h"
@@ -490,6 +491,38 @@ std::tuple<at::Tensor, at::Tensor> flac_decode(const at::Tensor& data, const at:
     return {out, out_off};
 }
 
+// frames: the clips' interleaved int16 frames packed back to back, on the device; n_in, channels [n] int32 host; clip_short [n] uint8 host ->
+// (out fp32 device with room for f5hip_ref_prestep_bound samples: clip i as channels[i] planes of its output length, packed by the output
+// lengths; info int32 device [n, 2]: output frames and "any sample non-zero") as f5hip_ref_prestep's
+std::tuple<at::Tensor, at::Tensor> ref_prestep(const at::Tensor& frames, const at::Tensor& n_in, const at::Tensor& channels, const at::Tensor& clip_short,
+                                               int64_t rate) {
+    check_host(n_in, at::kInt, "n_in"); check_host(channels, at::kInt, "channels"); check_host(clip_short, at::kByte, "clip_short");
+    const int64_t n = n_in.numel();
+    TORCH_CHECK(n_in.dim() == 1 && n > 0 && n <= INT32_MAX / 2 && channels.numel() == n && clip_short.numel() == n,
+                "f5hip::ref_prestep: n_in, channels and clip_short need one value per clip, and at least one clip");
+    TORCH_CHECK(rate >= 11025 && rate <= INT32_MAX, "f5hip::ref_prestep: reference audio below 11025 Hz is not supported on this path (got ", rate, ")");
+    TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == at::kShort && frames.is_contiguous() && frames.dim() == 1,
+                "f5hip::ref_prestep: frames must be a contiguous 1-D int16 tensor on a HIP device");
+    const int32_t* ni = n_in.data_ptr<int32_t>();
+    const int32_t* ch = channels.data_ptr<int32_t>();
+    int64_t total = 0;
+    for (int64_t i = 0; i < n; i++) {
+        TORCH_CHECK(ni[i] >= 0 && ch[i] >= 1, "f5hip::ref_prestep: clip ", i, " has ", ni[i], " frames in ", ch[i], " channels");
+        total += (int64_t)ni[i] * ch[i];
+        TORCH_CHECK(total <= INT32_MAX, "f5hip::ref_prestep: the clips of the call exceed 2^31 - 1 samples");
+    }
+    TORCH_CHECK(frames.numel() == total, "f5hip::ref_prestep: the frames need sum(n_in * channels) = ", total, " samples (got ", frames.numel(), ")");
+    const int64_t bound = f5hip_ref_prestep_bound((int32_t)n, ni, ch, (int32_t)rate);
+    TORCH_CHECK(bound >= 0 && bound <= INT32_MAX, "f5hip::ref_prestep: the clips of the call exceed 2^31 - 1 samples");
+    const c10::DeviceGuard guard(frames.device());
+    at::Tensor out = at::empty({bound}, frames.options().dtype(at::kFloat));
+    at::Tensor info = at::empty({n, 2}, frames.options().dtype(at::kInt));
+    const int rc = f5hip_ref_prestep((int32_t)n, ni, ch, clip_short.data_ptr<uint8_t>(), total ? frames.data_ptr<int16_t>() : (const int16_t*)nullptr, total,
+                                     (int32_t)rate, out.data_ptr<float>(), info.data_ptr<int32_t>(), stream_of(frames));
+    TORCH_CHECK(rc == 0, "f5hip_ref_prestep: ", f5hip_last_error());
+    return {out, info};
+}
+
 // pcm: the int16 device tensor that holds every request (f5hip_wave_finish's packed PCM), normalised IN PLACE; in_off, max_len, len_dev as
 // wave_encode's; gain_k [n] float64 host: K_T per request, <= 0 leaves the request alone -> stats int64 device [n, 4]: n2, S2, peak, the bits
 // of g (zeros for a request that was left alone)
@@ -547,5 +580,6 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("wave_flac_levels(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int sample_rate, Tensor level) -> (Tensor, Tensor, Tensor)",
           &wave_flac_levels);
     m.def("flac_decode(Tensor data, Tensor begin, Tensor end, Tensor info, Tensor total, Tensor max_samples) -> (Tensor, Tensor)", &flac_decode);
+    m.def("ref_prestep(Tensor frames, Tensor n_in, Tensor channels, Tensor clip_short, int rate) -> (Tensor, Tensor)", &ref_prestep);
     m.def("wave_loudness(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor gain_k) -> Tensor", &wave_loudness);
 }

@@ -368,6 +368,66 @@ def ref_frontend(wave, n_in, channels, orig_freq, new_freq, taps=None, rms_floor
     return out, rms, n_out
 
 
+def ref_prestep(frames, n_in, channels, rate, clip_short=True, device=None):
+    """The reference-clip pre-step of several clips of ONE sample rate in one library call and three launches (include/f5hip.h
+    f5hip_ref_prestep): `audio_prep.preprocess_ref_segment` of each clip -- clip at a pause, strip the silent edges, append 50 ms of silence --
+    bit for bit.  frames: the clips' int16 frames, interleaved as `PcmSegment` holds them and packed back to back: a host array (uploaded
+    once, to `device`) or a 1-D int16 device tensor; n_in, channels: one value per clip (a clip of 0 frames is valid); clip_short: one bool, or
+    one per clip.  Returns (packed fp32 device tensor: clip i as channels[i] planes of lengths[i] samples, x / 32768, packed by those lengths
+    -- `ref_frontend`'s `wave` as it stands --, lengths [n], flags [n]: whether any output sample of the clip is non-zero).  One download:
+    the [n, 2] lengths and flags; the samples stay on the device."""
+    ni = np.ascontiguousarray(np.asarray(n_in, dtype=np.int32).reshape(-1))
+    ch = np.ascontiguousarray(np.asarray(channels, dtype=np.int32).reshape(-1))
+    cs = np.ascontiguousarray(np.broadcast_to(np.asarray(clip_short, dtype=bool), ni.shape).astype(np.uint8))
+    if len(ni) < 1 or len(ch) != len(ni):
+        raise _lib.F5HipError("ref_prestep: at least one clip, and one (n_in, channels) pair per clip")
+    if int(rate) < 11025:
+        raise _lib.F5HipError(f"ref_prestep: reference audio below 11025 Hz is not supported on this path (got {rate})")
+    if (ni < 0).any() or (ch < 1).any():
+        raise _lib.F5HipError("ref_prestep: a clip needs a frame count of 0 or more and at least one channel")
+    total = int((ni.astype(np.int64) * ch).sum())
+    if total > 2 ** 31 - 1:
+        raise _lib.F5HipError("ref_prestep: the clips of the call exceed 2^31 - 1 samples")
+    if not torch.is_tensor(frames):
+        host = np.ascontiguousarray(np.asarray(frames)).reshape(-1)
+        if host.dtype != np.int16:
+            raise _lib.F5HipError(f"ref_prestep: int16 frames expected (got {host.dtype})")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        frames = torch.from_numpy(host).to(dev)                   # the one upload
+    if frames.dtype != torch.int16 or not frames.is_cuda or not frames.is_contiguous() or frames.dim() != 1:
+        raise _lib.F5HipError("ref_prestep: frames must be a contiguous 1-D int16 tensor on the device")
+    if frames.numel() != total:
+        raise _lib.F5HipError(f"ref_prestep: the frames need sum(n_in * channels) = {total} samples (got {frames.numel()})")
+    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
+        try:
+            out, info = torch_ops.ops().ref_prestep(frames, torch.from_numpy(ni), torch.from_numpy(ch), torch.from_numpy(cs), int(rate))
+        except RuntimeError as e:   # c10::Error from the operator's checks or the library
+            raise _lib.F5HipError(str(e)) from e
+    else:
+        bound = int(_lib.lib().f5hip_ref_prestep_bound(len(ni), _p(ni), _p(ch), int(rate)))
+        if bound < 0 or bound > 2 ** 31 - 1:
+            raise _lib.F5HipError("ref_prestep: the clips of the call exceed 2^31 - 1 samples")
+        with torch.cuda.device(frames.device):
+            out = torch.empty(bound, device=frames.device, dtype=torch.float32)
+            info = torch.empty(len(ni), 2, device=frames.device, dtype=torch.int32)
+            _lib.check(_lib.lib().f5hip_ref_prestep(len(ni), _p(ni), _p(ch), _p(cs), _p(frames) if total else None, total, int(rate), _p(out), _p(info),
+                                                    _lib.current_stream_ptr()), "f5hip_ref_prestep")
+    got = info.cpu().numpy()                                      # the one download: lengths and flags
+    if (got[:, 0] < 0).any():
+        raise _lib.F5HipError("ref_prestep: a clip kept more ranges than the device holds")
+    lengths = [int(v) for v in got[:, 0]]
+    return out[:int((got[:, 0].astype(np.int64) * ch).sum())], lengths, [bool(v) for v in got[:, 1]]
+
+
+def ref_prestep_planes(packed, lengths, channels):
+    """Clip i's [channels[i], lengths[i]] view of `ref_prestep`'s packed output."""
+    out, at = [], 0
+    for n, c in zip(lengths, channels):
+        out.append(packed[at:at + int(n) * int(c)].view(int(c), int(n)))
+        at += int(n) * int(c)
+    return out
+
+
 def wave_finish(chunks, chunks_per_request, fade, remove_silence=None, sample_rate=24000):
     """The waveform back-end for several requests in ONE library call (include/f5hip.h f5hip_wave_finish): `chunks` = the chunk waves of all
     requests in request and chunk order, each a 1-D contiguous fp32 device tensor with the rms gain applied (views of a vocoder's packed

@@ -128,6 +128,10 @@ DEVICE_BACKEND_DEFAULT = False
 # 1426.2 ms (1423.3 .. 1434.7), device 13.7 ms (13.6 .. 13.9), upload, download and MD5 included (tools/flac_decode_bench.py,
 # profiles/flac_decode_bench.txt).  The samples are the same either way.
 DEVICE_DECODE_DEFAULT = True
+# Whether an uploaded clip's silence pre-step (clip at a pause, strip the edges, 50 ms tail) runs on the device (`ops.ref_prestep`) unless
+# `TTSManager(device_prestep=...)` says otherwise.  Off: the option is new, and its measurement (tools/ref_prestep_bench.py,
+# profiles/ref_prestep_bench.txt) decides nothing about the default.  The samples are the same either way.
+DEVICE_PRESTEP_DEFAULT = False
 STREAM_REMOVE_SILENCE = "remove_silence needs the request's whole wave: it is not available on a streaming path"
 STREAM_LOUDNESS = "loudness is measured on the request's whole wave: it is not available on a streaming path"
 
@@ -416,7 +420,7 @@ class TTSManager:
     def __init__(self, loader: Callable[[], tuple] | None = None, nfe_step: int = infer.nfe_step, cfg_strength: float = infer.cfg_strength,
                  sway_sampling_coef: float = infer.sway_sampling_coef, speed: float = infer.speed, mel_spec_type: str = "vocos",
                  micro_batch: dict | None = None, batch_invariant: bool = True, clip_cache: int = 64, device_frontend: bool | None = None,
-                 device_backend: bool | None = None, device_decode: bool | None = None):
+                 device_backend: bool | None = None, device_decode: bool | None = None, device_prestep: bool | None = None):
         self.loader = loader
         self.batch_invariant = batch_invariant   # False: leave the model's attention mode alone (fastest kernel per launch shape)
         self.micro_batch = micro_batch            # e.g. dict(max_requests=16, max_wait_ms=5): batch concurrent requests; with span_steps
@@ -448,6 +452,10 @@ class TTSManager:
         # `ShardedSampler` on rank 0's device); False: by `wave_codec.read_flac` on the host.  None: DEVICE_DECODE_DEFAULT.  WAV never
         # touches the device here.
         self.device_decode = DEVICE_DECODE_DEFAULT if device_decode is None else bool(device_decode)
+        # True: an uploaded clip's silence pre-step runs in `ops.ref_prestep` (one library call, three launches, under the device lock) and the
+        # clip stays on the device for the front-end; the new uploads of a script share ONE call per distinct rate.  Honoured only with
+        # `device_frontend` and a model on a GPU; else `audio_prep.preprocess_ref_segment` on the host.  None: DEVICE_PRESTEP_DEFAULT
+        self.device_prestep = DEVICE_PRESTEP_DEFAULT if device_prestep is None else bool(device_prestep)
         # The library allows ONE call in flight per handle (include/f5hip.h), the sampler keeps per-call state and noise comes from torch's
         # global generator: every entry into the device path takes this lock.  Without a batcher, concurrent HTTP requests therefore run one
         # after the other, like the reference's blocking `async def` handlers (S/routes/speech.py:19-41).
@@ -554,64 +562,119 @@ class TTSManager:
         (content, ref_text, clip_short) and kept in the LRU cache.  Host work only: read, quantise to int16 (16-bit PCM passes through bit for
         bit; any other format as clip(round(x * 32768), -32768, 32767) -- pydub would hand those to ffmpeg), the silence pre-step
         (`audio_prep.preprocess_ref_segment`), back to float32.  With `device_frontend` the voice is deferred: its mono mix / gain /
-        resampling run on the device with the batch it first rides in.  Everything that can be refused is refused here with ValueError,
-        before anything is queued: an empty `ref_text`, an unreadable WAV, a rate below 11 025 Hz, non-finite samples, a clip that is
-        empty or all-zero after the pre-step, a rate pair whose tap table is refused."""
+        resampling run on the device with the batch it first rides in; with `device_prestep` as well the int16 frames go through
+        `ops.ref_prestep` under the device lock and the clip never returns to the host.  Everything that can be refused is refused here with
+        ValueError, before anything is queued: an empty `ref_text`, an unreadable WAV, a rate below 11 025 Hz, non-finite samples, a clip
+        that is empty or all-zero after the pre-step, a rate pair whose tap table is refused."""
+        return self._clip_voices([(ref_audio, ref_text, clip_short)])[0]
+
+    def _prestep_device(self):
+        """The device `ops.ref_prestep` runs on, or None where the host pre-step runs: `device_prestep` needs `device_frontend` and a model on a GPU."""
         import torch
-        if not ref_text or not ref_text.strip():
-            raise ValueError("Reference text cannot be empty.")
-        h = hashlib.sha1()
+        if not (self.device_prestep and self.device_frontend):
+            return None
+        device = getattr(getattr(self.model_obj, "local", self.model_obj), "device", None)
+        return device if device is not None and torch.device(device).type == "cuda" else None
+
+    def _clip_pcm(self, ref_audio):
+        """(int16 frames [n, channels], sample_rate) of an upload: read, check, quantise."""
+        import torch
         if isinstance(ref_audio, tuple):
-            arr = np.ascontiguousarray(ref_audio[0].detach().cpu().numpy())
-            h.update(repr((arr.shape, str(arr.dtype), int(ref_audio[1]))).encode())
-            h.update(arr.tobytes())
+            wave, sr = ref_audio[0].detach().cpu().to(torch.float32), int(ref_audio[1])
         else:
-            ref_audio = bytes(ref_audio)
-            h.update(ref_audio)
-        key = (h.hexdigest(), ref_text, bool(clip_short))
-        with self._clip_lock:
-            if key in self._clip_cache:
-                self._clip_cache.move_to_end(key)
-                return self._clip_cache[key]
-            entry = self._clip_key_locks.setdefault(key, [threading.Lock(), 0])
-            entry[1] += 1
+            try:
+                wave, sr = self.decode_audio(ref_audio)
+            except ValueError as e:
+                raise ValueError(f"Invalid audio: {e}") from e
+        if wave.dim() != 2 or wave.shape[0] < 1:
+            raise ValueError(f"Invalid audio: expected [channels, samples] (got {tuple(wave.shape)})")
+        x = wave.numpy()
+        if not np.isfinite(x).all():
+            raise ValueError("Invalid audio: the clip has non-finite samples.")
+        pcm = np.clip(np.rint(x.astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
+        return np.ascontiguousarray(pcm.T), sr
+
+    def _clip_voices(self, specs):
+        """`_clip_voice` of several uploads, [(ref_audio, ref_text, clip_short)] -> [(PreparedVoice, normalised ref_text)].  The cache is
+        looked up per key and every new key is prepared under its own lock (taken in key order, so two callers never wait for each other
+        in a ring).  On the host path the new clips are prepared one after the other; with `device_prestep` they share ONE `ops.ref_prestep`
+        call per distinct sample rate."""
+        import torch
+        keys, audios = [], {}
+        for ref_audio, ref_text, clip_short in specs:
+            if not ref_text or not ref_text.strip():
+                raise ValueError("Reference text cannot be empty.")
+            h = hashlib.sha1()
+            if isinstance(ref_audio, tuple):
+                arr = np.ascontiguousarray(ref_audio[0].detach().cpu().numpy())
+                h.update(repr((arr.shape, str(arr.dtype), int(ref_audio[1]))).encode())
+                h.update(arr.tobytes())
+            else:
+                ref_audio = bytes(ref_audio)
+                h.update(ref_audio)
+            key = (h.hexdigest(), ref_text, bool(clip_short))
+            keys.append(key)
+            audios.setdefault(key, ref_audio)
+        results, entries = {}, []
         try:
-            with entry[0]:
+            for key in sorted(audios):
+                with self._clip_lock:
+                    if key in self._clip_cache:
+                        self._clip_cache.move_to_end(key)
+                        results[key] = self._clip_cache[key]
+                        continue
+                    entry = self._clip_key_locks.setdefault(key, [threading.Lock(), 0])
+                    entry[1] += 1
+                entries.append((key, entry, [False]))
+                entry[0].acquire()
+                entries[-1][2][0] = True
                 with self._clip_lock:
                     if key in self._clip_cache:      # prepared while this thread waited for the key
                         self._clip_cache.move_to_end(key)
-                        return self._clip_cache[key]
-                if isinstance(ref_audio, tuple):
-                    wave, sr = ref_audio[0].detach().cpu().to(torch.float32), int(ref_audio[1])
-                else:
-                    try:
-                        wave, sr = self.decode_audio(ref_audio)
-                    except ValueError as e:
-                        raise ValueError(f"Invalid audio: {e}") from e
-                if wave.dim() != 2 or wave.shape[0] < 1:
-                    raise ValueError(f"Invalid audio: expected [channels, samples] (got {tuple(wave.shape)})")
-                x = wave.numpy()
-                if not np.isfinite(x).all():
-                    raise ValueError("Invalid audio: the clip has non-finite samples.")
-                pcm = np.clip(np.rint(x.astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
-                seg = audio_prep.preprocess_ref_segment(audio_prep.PcmSegment(np.ascontiguousarray(pcm.T), sr), clip_short, show_info=lambda *_: None)
+                        results[key] = self._clip_cache[key]
+            new = [key for key, _, _ in entries if key not in results]
+            device = self._prestep_device() if new else None
+            clips, by_rate = {}, {}
+            for key in new:
+                pcm, sr = self._clip_pcm(audios[key])
+                if device is not None and sr >= 11025 and sr * pcm.shape[1] < 2 ** 23:      # (beyond that the device's exact window sums end)
+                    by_rate.setdefault(sr, []).append((key, pcm))
+                    continue
+                seg = audio_prep.preprocess_ref_segment(audio_prep.PcmSegment(pcm, sr), key[2], show_info=lambda *_: None)
                 if seg.frames.shape[0] == 0 or not seg.frames.any():
                     raise ValueError("Invalid audio: the clip is empty or silent.")
-                clip = (torch.from_numpy(np.ascontiguousarray((seg.frames.astype(np.float32) / 32768.0).T)), seg.rate)
-                if seg.rate != infer.target_sample_rate:
-                    infer.resample_taps(seg.rate, infer.target_sample_rate)      # refuses a rate pair it has no table for
+                clips[key] = (torch.from_numpy(np.ascontiguousarray((seg.frames.astype(np.float32) / 32768.0).T)), seg.rate)
+            if by_rate:
+                from . import ops
+                for sr, group in by_rate.items():
+                    n_in, channels = [pcm.shape[0] for _, pcm in group], [pcm.shape[1] for _, pcm in group]
+                    frames = np.concatenate([pcm.reshape(-1) for _, pcm in group])
+                    with self._device_lock:
+                        packed, lengths, flags = ops.ref_prestep(frames, n_in, channels, sr, [key[2] for key, _ in group], device=device)
+                    if not all(n > 0 and f for n, f in zip(lengths, flags)):
+                        raise ValueError("Invalid audio: the clip is empty or silent.")
+                    for (key, _), planes in zip(group, ops.ref_prestep_planes(packed, lengths, channels)):
+                        clips[key] = (planes, sr)
+            for key in new:
+                clip = clips[key]
+                if clip[1] != infer.target_sample_rate:
+                    infer.resample_taps(clip[1], infer.target_sample_rate)      # refuses a rate pair it has no table for
                 voice = infer.PreparedVoice.deferred(clip) if self.device_frontend else infer.PreparedVoice(clip)
-                value = (voice, audio_prep.normalize_ref_text(ref_text))
+                value = (voice, audio_prep.normalize_ref_text(key[1]))
                 with self._clip_lock:
                     self._clip_cache[key] = value
                     while len(self._clip_cache) > max(self.clip_cache, 0):
                         self._clip_cache.popitem(last=False)
-                return value
+                results[key] = value
+            return [results[key] for key in keys]
         finally:
-            with self._clip_lock:
-                entry[1] -= 1
-                if entry[1] == 0:
-                    self._clip_key_locks.pop(key, None)
+            for key, entry, held in reversed(entries):
+                if held[0]:
+                    entry[0].release()
+                with self._clip_lock:
+                    entry[1] -= 1
+                    if entry[1] == 0:
+                        self._clip_key_locks.pop(key, None)
 
     def _serve(self, resolve_voice, text, options, stream=False):
         """What the four `synthesize*` methods do once they know where the voice comes from (`resolve_voice`: `_voice` or `_clip_voice`, called
@@ -745,7 +808,8 @@ class TTSManager:
         """The host part of a script request, every refusal a ValueError before anything is queued: `voices` needs "main", `text` at least
         one non-empty piece and at most `infer.MAX_SCRIPT_SEGMENTS` (`infer.split_voice_tags`), `gap` its range; then each voice the text
         uses is resolved once -- a registered one by `_voice`, an uploaded one by `_clip_voice` (its SHA-1 LRU, deferred with
-        `device_frontend`: the new clips of the script are then prepared in the ONE front-end call of the batch the script rides in).
+        `device_frontend`: the new clips of the script are then prepared in the ONE front-end call of the batch the script rides in; with
+        `device_prestep` the uploads are resolved together, `_clip_voices`: one `ops.ref_prestep` call per distinct rate).
         Returns [(voice, ref_text, piece text, speed | None)]."""
         if not isinstance(voices, dict) or "main" not in voices:
             raise ValueError('voices needs a "main" entry')
@@ -757,7 +821,7 @@ class TTSManager:
         if len(pieces) > infer.MAX_SCRIPT_SEGMENTS:
             raise ValueError(f"a script needs between 1 and {infer.MAX_SCRIPT_SEGMENTS} pieces (got {len(pieces)})")
         infer.check_script_gap(gap)
-        resolved = {}
+        resolved, uploads, together = {}, [], self._prestep_device() is not None
         for tag in dict.fromkeys(tag for tag, _ in pieces):
             spec = dict(voices[tag])
             unknown = set(spec) - {"ref_audio_path", "ref_audio", "ref_text", "clip_short", "speed"}
@@ -769,9 +833,15 @@ class TTSManager:
                 raise ValueError("Reference text cannot be empty.")
             if "ref_audio_path" in spec:
                 voice, ref_text = self._voice(spec["ref_audio_path"], spec["ref_text"])
+            elif together:
+                uploads.append((tag, speed, (spec["ref_audio"], spec["ref_text"], spec.get("clip_short", True))))
+                continue
             else:
                 voice, ref_text = self._clip_voice(spec["ref_audio"], spec["ref_text"], spec.get("clip_short", True))
             resolved[tag] = (voice, ref_text, speed)
+        if uploads:                                  # the script's uploads together: one pre-step call per distinct rate for the new ones
+            for (tag, speed, _), (voice, ref_text) in zip(uploads, self._clip_voices([u for _, _, u in uploads])):
+                resolved[tag] = (voice, ref_text, speed)
         return [(resolved[tag][0], resolved[tag][1], piece, resolved[tag][2]) for tag, piece in pieces]
 
     def synthesize_script(self, text, voices, *, gap=0.0, **options):
