@@ -598,6 +598,48 @@ int f5hip_wave_loudness(int32_t n, int16_t* pcm_dev, const int64_t* in_off, cons
 /* Samples one block of f5hip_wave_loudness's first launch owns (two sub-blocks).  For tests, which place request lengths around it. */
 int f5hip_wave_loudness_tile(void);
 
+/* Prosody: the 24 kHz int16 PCM of n requests, still on the device (f5hip_wave_finish's pcm_dev), time-scale modified per request -- its
+ * `tempo` and `pitch` --, bit for bit wave_codec.shift_pcm16.  Not in the reference.  It runs behind f5hip_wave_finish and before
+ * f5hip_wave_loudness / f5hip_wave_encode / f5hip_wave_flac, which read its output, bounds and lengths as they read f5hip_wave_finish's.  The
+ * arithmetic, integers up to the resampler's exact fp64 sums (csrc/wave_prosody_core.h, which tools/wave_prosody_check.cpp runs on the CPU
+ * under sanitizers):
+ *   WSOLA        n samples -> m = ceil(n P / Q) at the same pitch.  L = 960, H = 480, D = 240; xt[j] = x[j] inside the request, else 0;
+ *                K = ceil(m / H) + 1 frames, nominal starts p_k = floor(k H Q / P) - H (64-bit products), s_0 = -H; for k >= 1, with
+ *                t = s_{k-1} + H: c(d) = sum_{i < L} |xt[p_k + d + i] - xt[t + i]| (< 2^26), d_k = the d in -D .. D that minimises it, ties
+ *                to the smaller |d|, then to the negative one; s_k = p_k + d_k
+ *   window       W[i] = rint(32768 sin^2(pi (2 i + 1) / (2 L))) for i < H (csrc/wsola_window.inc = wave_codec.wsola_window()), W[H + i] =
+ *                32768 - W[i]
+ *   output       y[j] = (W[H + i] xt[s_k + H + i] + W[i] xt[s_{k+1} + i] + 16384) >> 15, a floor shift, k = j / H, i = j - k H; the
+ *                numerator stays within 2^30 + 2^14 and y inside int16: no clip.  P == Q: the samples themselves
+ *   pitch        s semitones, s != 0: the m samples -> ceil(q m / p) by f5hip_wave_encode's polyphase arithmetic with the pair p : q in the
+ *                place of 24000 : new_freq (output j = b q + r is rint(sum_k (double)taps[r][k] * (double)ypad[b p + k]), half to even,
+ *                clipped); p / q = 18/17, 46/41, 44/37, 29/23, 4/3, 41/29 for s = 1 .. 6, the reciprocal for -s.  The caller has chosen
+ *                P / Q = (p / q) / tempo, so the duration is the tempo's alone
+ *   pcm_dev, in_off[i], max_len[i], len_dev    as in f5hip_wave_encode
+ *   stretch_p, stretch_q   host int32 [n]: P and Q of request i, 1 .. 2^20 each, 1/2 <= P / Q <= 2
+ *   pitch                  host int32 [n]: -6 .. 6
+ *   taps_dev               fp32, 16-byte aligned: the twelve tables wave_codec.resample_taps(p, q) of s = -6 .. -1, 1 .. 6, table s at float
+ *                          f5hip_wave_prosody_tap_offset(s); may be null when no request has a pitch
+ *   out_dev, out_off[i]    int16, 16-byte aligned: request i's samples at out_dev + out_off[i] (a multiple of 8), room for the length that
+ *                          max_len[i] gives
+ *   out_len_dev            int32 [n]: its samples
+ * Two launches whatever n, one when no request has a pitch (wave_wsola_kernel: one workgroup per request, frames in sequence, the 481
+ * candidates of a frame across the workgroup as packed 16-bit absolute differences, ONE min-reduction over the key cost * 2^9 + tie rank, so
+ * the choice cannot depend on lane order; wave_pitch_kernel: one block per tile of a pitched request, which reads the stretched PCM from the
+ * call's workspace), no host sync between them (counters wave_prosody_launches, wave_prosody_requests: the requests with P != Q or a pitch);
+ * no atomics, vector stores; a request's bytes depend on that request alone, and the input is not written; the request table is copied on
+ * `stream`, which the call waits for once before it launches.
+ * Refused before the first launch: n < 1, a null pointer (len_dev excepted, and taps_dev without a pitch), a negative max_len or offset, a
+ * misaligned pointer or output offset, P or Q < 1, a stretch outside [1/2, 2] or with a term above 2^20, a pitch outside -6 .. 6, more than
+ * 2^31 - 1 samples in or out. */
+int f5hip_wave_prosody(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
+                       const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const float* taps_dev, int16_t* out_dev,
+                       const int64_t* out_off, int32_t* out_len_dev, void* stream);
+
+/* First float of pitch step s's tap table in f5hip_wave_prosody's taps_dev (tables in the order -6 .. -1, 1 .. 6, each padded to a multiple
+ * of 4 floats); s = 0: the floats of the whole table; -1 for a step outside -6 .. 6. */
+int64_t f5hip_wave_prosody_tap_offset(int32_t pitch);
+
 /* FLAC in: n native FLAC streams (RFC 9639) -- uploaded reference clips and recordings, which the reference reads with torchaudio.load
  * (F/infer/utils_infer.py:376) -- packed at arbitrary byte offsets in one device buffer -> each stream's samples as int32 planes
  * [channels, total], bit for bit wave_codec.read_flac, which defines the format accepted: every subframe type, LPC order 1 .. 32, both Rice

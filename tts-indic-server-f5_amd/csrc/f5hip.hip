@@ -542,12 +542,13 @@ static GemmArgs gemm_base(const Plane2& A, int lda, const PackedW& W, int M) {
 // mel_ragged_launches / mel_ragged_items: launches of f5hip_mel_spectrogram_ragged and the clips they covered; wave_flac_launches /
 // wave_flac_requests: kernels f5hip_wave_flac launched and requests it encoded; wave_loudness_launches / wave_loudness_requests: kernels
 // f5hip_wave_loudness launched and the flagged requests it normalised; flac_decode_launches / flac_decode_streams: kernels f5hip_flac_decode
-// launched and the streams it was given; ref_prestep_launches / ref_prestep_clips: the same for f5hip_ref_prestep and its clips
+// launched and the streams it was given; ref_prestep_launches / ref_prestep_clips: the same for f5hip_ref_prestep and its clips;
+// wave_prosody_launches / wave_prosody_requests: kernels f5hip_wave_prosody launched and the requests whose tempo or pitch it changed
 enum { CNT_GEMM5_RB11, CNT_GEMM5_RB8, CNT_GEMM5_WIDE, CNT_GEMM3_WIDE, CNT_CONV5, CNT_GEMM6, CNT_GEMM6_R176, CNT_GEMM6_R256, CNT_GEMM5_CB12,
        CNT_GEMM3, CNT_GEMM_REG_BN64, CNT_GEMM_REG_BN128, CNT_DIT_ROWS, CNT_REF_LAUNCHES, CNT_REF_TAPS_LDS, CNT_REF_TAPS_L2, CNT_WAVE_LAUNCHES,
        CNT_WAVE_REQUESTS, CNT_WAVE_ENCODE_LAUNCHES, CNT_WAVE_ENCODE_REQUESTS, CNT_MEL_RAGGED_LAUNCHES, CNT_MEL_RAGGED_ITEMS, CNT_WAVE_FLAC_LAUNCHES,
        CNT_WAVE_FLAC_REQUESTS, CNT_WAVE_LOUDNESS_LAUNCHES, CNT_WAVE_LOUDNESS_REQUESTS, CNT_FLAC_DECODE_LAUNCHES, CNT_FLAC_DECODE_STREAMS,
-       CNT_REF_PRESTEP_LAUNCHES, CNT_REF_PRESTEP_CLIPS, CNT_COUNT };
+       CNT_REF_PRESTEP_LAUNCHES, CNT_REF_PRESTEP_CLIPS, CNT_WAVE_PROSODY_LAUNCHES, CNT_WAVE_PROSODY_REQUESTS, CNT_COUNT };
 static long long g_counters[CNT_COUNT] = {};
 
 // Kernel choice per GEMM (measured: profiles/r02_fillrate_microbench.txt, profiles/r01_gemm_microbench.txt):
@@ -652,7 +653,8 @@ extern "C" int f5hip_get_counter(const char* name, int64_t* value) {
                                            "ref_taps_lds", "ref_taps_l2", "wave_finish_launches", "wave_finish_requests",
                                            "wave_encode_launches", "wave_encode_requests", "mel_ragged_launches", "mel_ragged_items",
                                            "wave_flac_launches", "wave_flac_requests", "wave_loudness_launches", "wave_loudness_requests",
-                                           "flac_decode_launches", "flac_decode_streams", "ref_prestep_launches", "ref_prestep_clips"};
+                                           "flac_decode_launches", "flac_decode_streams", "ref_prestep_launches", "ref_prestep_clips",
+                                           "wave_prosody_launches", "wave_prosody_requests"};
     static const char* attn_names[F5_ATTN_CNT_COUNT] = {"attn_bal8", "attn_nw8_deep", "attn_nw8", "attn_nw6_deep", "attn_nw6", "attn_nw4", "attn_seg2"};
     long long* attn = f5_attn_counters();
     if (!name) return fail(-1, "get_counter: null name");

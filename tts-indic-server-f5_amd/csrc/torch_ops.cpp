@@ -31,6 +31,7 @@
 //   torch.ops.f5hip.wave_encode(pcm[], in_off, max_len, len_dev?, new_freq, encoding, taps?) -> (Tensor bytes uint8, Tensor lengths int32, Tensor offsets int64 host)
 #include "../../include/f5hip.h"
 #include "rate_pair.h"
+#include "wave_prosody_core.h"
 
 namespace {
 
@@ -559,6 +560,68 @@ at::Tensor wave_loudness(at::Tensor pcm, const at::Tensor& in_off, const at::Ten
     return stats;
 }
 
+// pcm: the int16 device tensor that holds every request (f5hip_wave_finish's packed PCM), read only; in_off, max_len, len_dev as wave_encode's;
+// stretch_p, stretch_q, pitch [n] int32 host; taps: the twelve pitch tables as one fp32 device tensor (f5hip_wave_prosody_tap_offset), needed
+// when a request has a pitch -> (out int16 device: request i's samples at out_off[i]; out_len [n] int32 device; out_off [n] int64 host, each
+// a multiple of 8; bounds [n] int32 host: the length that max_len[i] gives)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody(const at::Tensor& pcm, const at::Tensor& in_off, const at::Tensor& max_len,
+                                                                        const c10::optional<at::Tensor>& len_dev, const at::Tensor& stretch_p,
+                                                                        const at::Tensor& stretch_q, const at::Tensor& pitch,
+                                                                        const c10::optional<at::Tensor>& taps) {
+    check_host(in_off, at::kLong, "in_off"); check_host(max_len, at::kInt, "max_len"); check_host(stretch_p, at::kInt, "stretch_p");
+    check_host(stretch_q, at::kInt, "stretch_q"); check_host(pitch, at::kInt, "pitch");
+    const int64_t n = max_len.numel();
+    TORCH_CHECK(max_len.dim() == 1 && n > 0 && in_off.numel() == n && stretch_p.numel() == n && stretch_q.numel() == n && pitch.numel() == n,
+                "f5hip::wave_prosody: in_off, max_len, stretch_p, stretch_q and pitch need one value per request");
+    TORCH_CHECK(pcm.is_cuda() && pcm.scalar_type() == at::kShort && pcm.is_contiguous() && pcm.dim() == 1,
+                "f5hip::wave_prosody: pcm must be a contiguous 1-D int16 tensor on a HIP device");
+    if (len_dev.has_value())
+        TORCH_CHECK(len_dev->is_cuda() && len_dev->scalar_type() == at::kInt && len_dev->is_contiguous() && len_dev->numel() == n &&
+                    len_dev->device() == pcm.device(), "f5hip::wave_prosody: len_dev must be a contiguous int32 tensor with one value per request on the pcm's device");
+    const int64_t* io = in_off.data_ptr<int64_t>();
+    const int32_t* ml = max_len.data_ptr<int32_t>();
+    const int32_t* sp = stretch_p.data_ptr<int32_t>();
+    const int32_t* sq = stretch_q.data_ptr<int32_t>();
+    const int32_t* pt = pitch.data_ptr<int32_t>();
+    at::Tensor out_off = at::empty({n}, at::TensorOptions().dtype(at::kLong)), bounds = at::empty({n}, at::TensorOptions().dtype(at::kInt));
+    int64_t* oo = out_off.data_ptr<int64_t>();
+    int32_t* bd = bounds.data_ptr<int32_t>();
+    int64_t total_in = 0, total = 0;
+    bool pitched = false;
+    for (int64_t i = 0; i < n; i++) {
+        TORCH_CHECK(ml[i] >= 0 && io[i] >= 0 && io[i] + ml[i] <= pcm.numel(), "f5hip::wave_prosody: request ", i, " reads samples [", io[i], ", ",
+                    io[i] + ml[i], ") of a tensor of ", pcm.numel());
+        TORCH_CHECK(pr_stretch_ok(sp[i], sq[i]), "f5hip::wave_prosody: request ", i, " stretches by ", sp[i], "/", sq[i],
+                    ": positive terms up to 2^20 and a ratio from 1/2 to 2");
+        TORCH_CHECK(pt[i] >= -kPrPitchMax && pt[i] <= kPrPitchMax, "f5hip::wave_prosody: request ", i, " has a pitch of ", pt[i], " semitones (-6 to 6)");
+        int64_t m = pr_geom(ml[i], sp[i], sq[i]).m;
+        if (pt[i]) {
+            int p, q;
+            pr_pitch_ratio(pt[i], &p, &q);
+            m = (q * m + p - 1) / p;
+            pitched = true;
+        }
+        total_in += ml[i];
+        oo[i] = total;
+        total += (m + 7) & ~(int64_t)7;
+        TORCH_CHECK(m <= INT32_MAX && total_in <= INT32_MAX && total <= INT32_MAX, "f5hip::wave_prosody: the call exceeds 2^31 - 1 samples in or out");
+        bd[i] = (int32_t)m;
+    }
+    if (pitched)
+        TORCH_CHECK(taps.has_value() && taps->is_cuda() && taps->scalar_type() == at::kFloat && taps->is_contiguous() && taps->device() == pcm.device() &&
+                    taps->numel() == f5hip_wave_prosody_tap_offset(0),
+                    "f5hip::wave_prosody: a pitch needs taps, the contiguous fp32 table of ", f5hip_wave_prosody_tap_offset(0), " floats on the pcm's device");
+    const c10::DeviceGuard guard(pcm.device());
+    at::Tensor out = at::empty({std::max<int64_t>(total, 8)}, pcm.options()).slice(0, 0, total);   // (a call of empty requests still has an address to give)
+    at::Tensor out_len = at::empty({n}, pcm.options().dtype(at::kInt));
+    at::Tensor anchor = pcm.numel() ? pcm : at::zeros({8}, pcm.options());
+    const int rc = f5hip_wave_prosody((int32_t)n, anchor.data_ptr<int16_t>(), io, ml, len_dev.has_value() ? len_dev->data_ptr<int32_t>() : (const int32_t*)nullptr,
+                                      sp, sq, pt, pitched ? taps->data_ptr<float>() : (const float*)nullptr, out.data_ptr<int16_t>(), oo,
+                                      out_len.data_ptr<int32_t>(), stream_of(pcm));
+    TORCH_CHECK(rc == 0, "f5hip_wave_prosody: ", f5hip_last_error());
+    return {out, out_len, out_off, bounds};
+}
+
 }   // namespace
 
 TORCH_LIBRARY(f5hip, m) {
@@ -582,4 +645,6 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("flac_decode(Tensor data, Tensor begin, Tensor end, Tensor info, Tensor total, Tensor max_samples) -> (Tensor, Tensor)", &flac_decode);
     m.def("ref_prestep(Tensor frames, Tensor n_in, Tensor channels, Tensor clip_short, int rate) -> (Tensor, Tensor)", &ref_prestep);
     m.def("wave_loudness(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor gain_k) -> Tensor", &wave_loudness);
+    m.def("wave_prosody(Tensor pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor stretch_p, Tensor stretch_q, Tensor pitch, Tensor? taps) -> "
+          "(Tensor, Tensor, Tensor, Tensor)", &wave_prosody);
 }

@@ -20,6 +20,8 @@
 //                         launches whatever n: see "delivery format: FLAC" below.
 //   wave_kweight / wave_gate / wave_gain_kernel  (f5hip_wave_loudness) the finished 24 kHz PCM of the flagged requests, in place, to their
 //                         BS.1770 loudness targets, three launches whatever n: see "loudness" below.
+//   wave_wsola / wave_pitch_kernel  (f5hip_wave_prosody) the finished 24 kHz PCM of n requests -> each request's tempo and pitch (WSOLA, then
+//                         a rational resampler), two launches whatever n, one without a pitch: see "prosody" below.
 //
 // Exactness.  With every chunk at least 2 F samples long the nested fades of cross_fade_concat never overlap, so joined sample j is either one
 // chunk sample or one fade of two chunk samples, and the closed form above is the host's arithmetic operation for operation (ramp[i] =
@@ -32,6 +34,7 @@
 // an 8-sample group can span several chunks and the slow path walks them.
 #pragma once
 #include "ragged_util.h"
+#include "wave_prosody_core.h"
 
 struct WfChunk {
     const float* x;
@@ -422,29 +425,22 @@ F5_DEVICE int we_alaw(int s) {    // audioop.lin2alaw: 13-bit, a negative value 
     return ((seg << 4) | ((m >> (seg < 2 ? 1 : seg)) & 15)) ^ mask;
 }
 
-// RESAMPLE: the tap table staged in LDS (every rate the entry point accepts: a table that does not fit is refused); else new_freq == 24000
-// (no taps: the samples themselves)
+// One tile of one request, by a block of 256 threads: the outputs j0 = tile * tq * nf .. of its n_out, from its samples x[0 .. len), to the bytes
+// at dst (the request's first output byte).  What wave_encode_kernel (the pair and the table of the call) and wave_pitch_kernel (those of the
+// request) share.  RESAMPLE: the tap table staged in LDS; else the samples themselves.  sm: tq * of + 2 * width shorts, 2 * tq * nf bytes and
+// the table, in that order (we_tile).
 template <bool RESAMPLE>
-__global__ __launch_bounds__(256) void wave_encode_kernel(const WeReq* __restrict__ reqs, int n, const short* __restrict__ pcm,
-                                                          const int* __restrict__ len_dev, const float* __restrict__ taps, int of, int nf, int width,
-                                                          int L, int tq, int enc, unsigned char* __restrict__ out, int* __restrict__ out_len) {
-    extern __shared__ __attribute__((aligned(16))) char we_sm[];
+F5_DEVICE void we_tile_body(char* sm, const short* __restrict__ x, int len, long long n_out, int tile, const float* __restrict__ taps, int of, int nf,
+                            int width, int L, int tq, int enc, unsigned char* __restrict__ dst) {
     const int tid = threadIdx.x;
-    const int r = last_at_or_before<&WeReq::tile0>(reqs, n, (int)blockIdx.x);
-    const WeReq q = reqs[r];
-    const int tile = blockIdx.x - q.tile0;
-    const int len = len_dev ? min(max(len_dev[r], 0), q.cap) : q.cap;   // (never past what the host sized the buffers for)
-    const long long n_out = ((long long)nf * len + of - 1) / of;
-    if (tile == 0 && tid == 0) out_len[r] = (int)n_out;
     const int n_local = tq * nf;                                        // outputs of a full tile
     const long long j0 = (long long)tile * n_local;
     if (j0 >= n_out) return;                                            // a tile past the request's actual length (the whole block leaves)
 
     const int nx = tq * of + 2 * width;                                 // the window of xpad this tile reads: xpad[q0 * of .. q0 * of + nx)
-    short* xs = reinterpret_cast<short*>(we_sm);
-    unsigned char* ys = reinterpret_cast<unsigned char*>(we_sm + ((2 * nx + 15) & ~15));        // the tile's output bytes
+    short* xs = reinterpret_cast<short*>(sm);
+    unsigned char* ys = reinterpret_cast<unsigned char*>(sm + ((2 * nx + 15) & ~15));           // the tile's output bytes
     float* tp = reinterpret_cast<float*>(ys + 2 * n_local);            // (n_local is a multiple of 16: 16-byte aligned)
-    const short* x = pcm + q.in_off;
     const long long src0 = (long long)tile * tq * of - width;
     for (int i = tid; i < nx; i += 256) {
         const long long src = src0 + i;
@@ -472,14 +468,30 @@ __global__ __launch_bounds__(256) void wave_encode_kernel(const WeReq* __restric
     __syncthreads();
 
     const int bps = enc == 0 ? 2 : 1, nbytes = valid * bps;
-    unsigned char* dst = out + q.out_off + j0 * bps;                    // (16-byte aligned: out_off and j0 are multiples of 16)
+    unsigned char* out = dst + j0 * bps;                                // (16-byte aligned: the request's first byte and j0 are multiples of 16)
     for (int b = 16 * tid; b < nbytes; b += 16 * 256) {
         if (b + 16 <= nbytes) {
-            *reinterpret_cast<int4*>(dst + b) = *reinterpret_cast<const int4*>(ys + b);
+            *reinterpret_cast<int4*>(out + b) = *reinterpret_cast<const int4*>(ys + b);
         } else {
-            for (int e = b; e < nbytes; e++) dst[e] = ys[e];            // the ragged end of the request
+            for (int e = b; e < nbytes; e++) out[e] = ys[e];            // the ragged end of the request
         }
     }
+}
+
+// RESAMPLE: the tap table staged in LDS (every rate the entry point accepts: a table that does not fit is refused); else new_freq == 24000
+// (no taps: the samples themselves)
+template <bool RESAMPLE>
+__global__ __launch_bounds__(256) void wave_encode_kernel(const WeReq* __restrict__ reqs, int n, const short* __restrict__ pcm,
+                                                          const int* __restrict__ len_dev, const float* __restrict__ taps, int of, int nf, int width,
+                                                          int L, int tq, int enc, unsigned char* __restrict__ out, int* __restrict__ out_len) {
+    extern __shared__ __attribute__((aligned(16))) char we_sm[];
+    const int r = last_at_or_before<&WeReq::tile0>(reqs, n, (int)blockIdx.x);
+    const WeReq q = reqs[r];
+    const int tile = blockIdx.x - q.tile0;
+    const int len = len_dev ? min(max(len_dev[r], 0), q.cap) : q.cap;   // (never past what the host sized the buffers for)
+    const long long n_out = ((long long)nf * len + of - 1) / of;
+    if (tile == 0 && threadIdx.x == 0) out_len[r] = (int)n_out;
+    we_tile_body<RESAMPLE>(we_sm, pcm + q.in_off, len, n_out, tile, taps, of, nf, width, L, tq, enc, out + q.out_off);
 }
 
 struct WeWorkspace { WeReq* reqs = nullptr; size_t cap_reqs = 0; };
@@ -1371,5 +1383,245 @@ int f5hip_wave_loudness(int32_t n, int16_t* pcm_dev, const int64_t* in_off, cons
     CKL("wave_gain");
     g_counters[CNT_WAVE_LOUDNESS_LAUNCHES] += 3;
     g_counters[CNT_WAVE_LOUDNESS_REQUESTS] += nf;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ prosody: tempo and pitch of the finished PCM
+// f5hip_wave_prosody: the 24 kHz int16 PCM of n requests -> each request's time-scale modified PCM, bit for bit wave_codec.shift_pcm16 (the
+// definition is written down there and in include/f5hip.h; the index geometry, the tie rule and the blend are wave_prosody_core.h, which
+// tools/wave_prosody_check.cpp runs on the CPU under sanitizers).  Integers only in the first launch, the resampler's exact fp64 in the second.
+//   wave_wsola_kernel  one workgroup of 256 threads per request, its frames in sequence: frame k's start depends on frame k - 1's.  Per frame
+//                      the 1440 source samples that hold every candidate, xt[p_k - D .. p_k + D + L), go to LDS biased by 32768 (unsigned
+//                      order, the same differences) -- twice, the second copy one sample on, so that a candidate at an odd offset reads
+//                      aligned 32-bit words too -- beside the target xt[s_{k-1} + H ..).  The 481 candidates go across the threads, two a
+//                      thread that share the target's 16-byte reads; a cost is 480 v_sad_u16, two differences each.  Lanes 2 j and 2 j + 1
+//                      read word j + w of the even and of the odd copy, which lie 32 banks apart: no LDS bank conflict.  ONE min-reduction
+//                      over the packed key cost * 2^9 + rank(d) (64-bit shuffles, then 4 words of LDS), so the choice does not depend on lane
+//                      order.  Frame k's placement finalises the H outputs of frame k - 1, blended from the LDS copies -- no second read of
+//                      the samples, no accumulator buffer, no atomics --, 8 samples in a 16-byte vector store.  A request with P == Q is
+//                      copied through.  A request with a pitch leaves its stretched PCM in the workspace for the second launch.
+//   wave_pitch_kernel  wave_encode_kernel's tile body (we_tile_body) with the rate pair p : q, the tile size and the tap table of the
+//                      REQUEST: one block per tile of a pitched request, its table (below 11 KB) staged in LDS from the one device table
+//                      that holds all twelve.
+// Two launches whatever n, one when no request has a pitch; no host sync between them; a request's bytes depend on that request alone.
+constexpr int kPrThreads = 256;
+constexpr int kPrWords = kPrWindow / 2;         // 720 words hold the window
+constexpr int kPrOddBase = 736;                 // the odd copy's first word: 32 banks on from the even copy's (736 = 11 * 64 + 32)
+static_assert(kPrOddBase >= kPrWords && kPrOddBase % 64 == 32 && kPrFrame % 8 == 0 && kPrHop % 8 == 0 && kPrCands <= 2 * kPrThreads, "wave_prosody tiling");
+static_assert(960LL * 65535 < (1LL << 26) && 2 * kPrSearch < 512, "wave_prosody: the packed key");
+__device__ const int kPrRiseTable[kPrHop] = {
+#include "wsola_window.inc"
+};
+
+struct PrReq {
+    long long in_off;    // its first sample, relative to pcm_dev
+    long long out_off;   // its first output sample (a multiple of 8: 16-byte stores)
+    long long mid_off;   // pitched: its first stretched sample in the workspace (a multiple of 8)
+    int cap;             // upper bound of its length (the length itself without len_dev)
+    int req;             // its index in the call: len_dev and out_len
+    int P, Q;            // the stretch
+    int of, nf, width, L;// pitched: p : q and its tap table's shape; of == 0: no pitch
+    int tq, tap_off;     // pitched: polyphase blocks per tile, its table's first float in the device table
+    int tile0;           // pitched: its first block of the second launch
+    int pad;
+};
+
+F5_DEVICE int pr_len(const int* len_dev, const PrReq& q) { return len_dev ? min(max(len_dev[q.req], 0), q.cap) : q.cap; }
+
+__global__ __launch_bounds__(kPrThreads) void wave_wsola_kernel(const PrReq* __restrict__ reqs, const short* __restrict__ pcm,
+                                                                const int* __restrict__ len_dev, short* __restrict__ out, short* __restrict__ mid,
+                                                                int* __restrict__ out_len) {
+    __shared__ __attribute__((aligned(16))) unsigned wn[kPrOddBase + kPrWords];    // the window: even copy, then the odd copy
+    __shared__ __attribute__((aligned(16))) unsigned tg[kPrFrame / 2];             // the target
+    __shared__ int rise[kPrHop];
+    __shared__ unsigned long long red[kPrThreads / 64];
+    const int tid = threadIdx.x;
+    const PrReq q = reqs[blockIdx.x];
+    const int len = pr_len(len_dev, q);
+    const PrGeom g = pr_geom(len, q.P, q.Q);
+    const short* x = pcm + q.in_off;
+    short* y = q.of ? mid + q.mid_off : out + q.out_off;
+    if (!q.of && tid == 0) out_len[q.req] = (int)g.m;
+    if (q.P == q.Q) {                                                   // neutral: copied through (g.m == len)
+        const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+        for (long long j = 8LL * tid; j < len; j += 8 * kPrThreads) {
+            if (vec && j + 8 <= len) {
+                *reinterpret_cast<int4*>(y + j) = *reinterpret_cast<const int4*>(x + j);
+            } else {
+                for (int e = 0; e < 8 && j + e < len; e++) y[j + e] = x[j + e];
+            }
+        }
+        return;
+    }
+    unsigned short* const ev16 = reinterpret_cast<unsigned short*>(wn);
+    unsigned short* const od16 = reinterpret_cast<unsigned short*>(wn + kPrOddBase);
+    unsigned short* const tg16 = reinterpret_cast<unsigned short*>(tg);
+    for (int i = tid; i < kPrHop; i += kPrThreads) rise[i] = kPrRiseTable[i];
+    if (tid == 0) od16[kPrWindow - 1] = 0x8000;                         // (the sample behind the window: never part of a candidate)
+
+    // the thread's two candidates c = d + D: c0 = tid and c1 = tid + 256 (the threads past the last candidate repeat it and drop the result)
+    const int c0 = tid, c1 = min(tid + kPrThreads, kPrCands - 1);
+    const unsigned* const b0 = wn + ((c0 & 1) ? kPrOddBase : 0) + (c0 >> 1);
+    const unsigned* const b1 = wn + ((c1 & 1) ? kPrOddBase : 0) + (c1 >> 1);
+    long long s = -kPrHop;                                              // s_0
+    for (long long k = 1; k < g.K; k++) {
+        const long long pk = pr_nominal(g, k), t = s + kPrHop;
+        for (int i = tid; i < kPrWindow; i += kPrThreads) {
+            const unsigned short v = (unsigned short)pr_source(x, len, pk - kPrSearch + i);
+            ev16[i] = v;
+            if (i > 0) od16[i - 1] = v;
+        }
+        for (int i = tid; i < kPrFrame; i += kPrThreads) tg16[i] = (unsigned short)pr_source(x, len, t + i);
+        __syncthreads();
+
+        unsigned a0 = 0, a1 = 0;
+        const uint4* t4 = reinterpret_cast<const uint4*>(tg);
+#pragma unroll 4
+        for (int w = 0; w < kPrFrame / 8; w++) {
+            const uint4 tv = t4[w];
+            a0 = __builtin_amdgcn_sad_u16(b0[4 * w], tv.x, a0); a1 = __builtin_amdgcn_sad_u16(b1[4 * w], tv.x, a1);
+            a0 = __builtin_amdgcn_sad_u16(b0[4 * w + 1], tv.y, a0); a1 = __builtin_amdgcn_sad_u16(b1[4 * w + 1], tv.y, a1);
+            a0 = __builtin_amdgcn_sad_u16(b0[4 * w + 2], tv.z, a0); a1 = __builtin_amdgcn_sad_u16(b1[4 * w + 2], tv.z, a1);
+            a0 = __builtin_amdgcn_sad_u16(b0[4 * w + 3], tv.w, a0); a1 = __builtin_amdgcn_sad_u16(b1[4 * w + 3], tv.w, a1);
+        }
+        unsigned long long key = pr_key(a0, c0 - kPrSearch);
+        if (tid + kPrThreads < kPrCands) key = min(key, pr_key(a1, c1 - kPrSearch));
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) key = min(key, (unsigned long long)__shfl_xor(key, o));
+        if ((tid & 63) == 0) red[tid >> 6] = key;
+        __syncthreads();
+        key = min(min(red[0], red[1]), min(red[2], red[3]));
+        const int c = pr_key_offset(key) + kPrSearch;
+        s = pk + c - kPrSearch;
+
+        // frame k - 1's H outputs: its falling half (the target's first H samples) over frame k's rising half (the window from c on)
+        if (tid < kPrHop / 8) {
+            const int i0 = 8 * tid;
+            const long long j0 = (k - 1) * kPrHop + i0;
+            if (j0 < g.m) {
+                int v[8];
+#pragma unroll
+                for (int e = 0; e < 8; e++) v[e] = pr_blend(rise[i0 + e], pr_unbias(tg16[i0 + e]), pr_unbias(ev16[c + i0 + e]));
+                if (j0 + 8 <= g.m) {                                    // (y + j0 is 16-byte aligned: the request's first sample and j0 are multiples of 8)
+                    *reinterpret_cast<int4*>(y + j0) = make_int4((v[0] & 0xffff) | (v[1] << 16), (v[2] & 0xffff) | (v[3] << 16),
+                                                                 (v[4] & 0xffff) | (v[5] << 16), (v[6] & 0xffff) | (v[7] << 16));
+                } else {
+                    for (int e = 0; e < 8 && j0 + e < g.m; e++) y[j0 + e] = (short)v[e];
+                }
+            }
+        }
+        __syncthreads();                                                // the next frame overwrites the window and the target
+    }
+}
+
+__global__ __launch_bounds__(256) void wave_pitch_kernel(const PrReq* __restrict__ reqs, int np, const int* __restrict__ len_dev,
+                                                         const short* __restrict__ mid, const float* __restrict__ taps, short* __restrict__ out,
+                                                         int* __restrict__ out_len) {
+    extern __shared__ __attribute__((aligned(16))) char pr_sm[];
+    const int f = last_at_or_before<&PrReq::tile0>(reqs, np, (int)blockIdx.x);
+    const PrReq q = reqs[f];
+    const int tile = blockIdx.x - q.tile0;
+    const long long m = pr_geom(pr_len(len_dev, q), q.P, q.Q).m;        // what the first launch left in the workspace
+    const long long n_out = ((long long)q.nf * m + q.of - 1) / q.of;
+    if (tile == 0 && threadIdx.x == 0) out_len[q.req] = (int)n_out;
+    we_tile_body<true>(pr_sm, mid + q.mid_off, (int)m, n_out, tile, taps + q.tap_off, q.of, q.nf, q.width, q.L, q.tq, 0,
+                       reinterpret_cast<unsigned char*>(out + q.out_off));
+}
+
+struct PrWorkspace {
+    PrReq* reqs = nullptr; size_t cap_reqs = 0;
+    PrReq* pitched = nullptr; size_t cap_pitched = 0;
+    short* mid = nullptr; size_t cap_mid = 0;
+};
+
+// floats of a pitch step's tap table in the device table (a multiple of 4: every table starts on a 16-byte boundary)
+static long long pr_table_floats(int pitch) {
+    int p, q;
+    pr_pitch_ratio(pitch, &p, &q);
+    const RatePair rp = rate_pair(p, q);
+    return ((long long)rp.nf * rp.L + 3) & ~3LL;
+}
+
+int64_t f5hip_wave_prosody_tap_offset(int32_t pitch) {
+    if (pitch < -kPrPitchMax || pitch > kPrPitchMax) return -1;
+    long long at = 0;
+    for (int s = -kPrPitchMax; s <= kPrPitchMax; s++) {
+        if (s == 0) continue;
+        if (s == pitch) return at;
+        at += pr_table_floats(s);
+    }
+    return at;   // pitch == 0: the whole table
+}
+
+int f5hip_wave_prosody(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
+                       const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const float* taps_dev, int16_t* out_dev,
+                       const int64_t* out_off, int32_t* out_len_dev, void* stream) {
+    if (n < 1 || !pcm_dev || !in_off || !max_len || !stretch_p || !stretch_q || !pitch || !out_dev || !out_off || !out_len_dev)
+        return fail(-1, "wave_prosody: bad argument");
+    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 1) || (reinterpret_cast<uintptr_t>(len_dev) & 3) || (reinterpret_cast<uintptr_t>(taps_dev) & 15) ||
+        (reinterpret_cast<uintptr_t>(out_dev) & 15) || (reinterpret_cast<uintptr_t>(out_len_dev) & 3))
+        return fail(-1, "wave_prosody: the samples must be 2-byte aligned, the lengths 4-byte, the tap table and the output 16-byte");
+    std::vector<PrReq> h(n), hp;
+    long long total_in = 0, total_out = 0, mid = 0, tiles = 0, changed = 0;
+    int lds = 0;
+    for (int i = 0; i < n; i++) {
+        if (max_len[i] < 0) return fail(-1, "wave_prosody: request %d has a negative length bound (%d)", i, max_len[i]);
+        if (in_off[i] < 0) return fail(-1, "wave_prosody: request %d has a negative offset", i);
+        if (out_off[i] < 0 || (out_off[i] & 7)) return fail(-1, "wave_prosody: the output offset of request %d is not a multiple of 8 samples", i);
+        if (stretch_p[i] < 1 || stretch_q[i] < 1) return fail(-1, "wave_prosody: the stretch of request %d is not a pair of positive terms (%d/%d)", i, stretch_p[i], stretch_q[i]);
+        if (!pr_stretch_ok(stretch_p[i], stretch_q[i]))
+            return fail(-1, "wave_prosody: request %d stretches by %d/%d: outside 1/2 to 2 (terms up to %d)", i, stretch_p[i], stretch_q[i], kPrMaxTerm);
+        if (pitch[i] < -kPrPitchMax || pitch[i] > kPrPitchMax) return fail(-1, "wave_prosody: request %d has a pitch of %d semitones (-6 to 6)", i, pitch[i]);
+        PrReq& q = h[i];
+        memset(&q, 0, sizeof(q));
+        q.in_off = in_off[i]; q.out_off = out_off[i]; q.cap = max_len[i]; q.req = i; q.P = stretch_p[i]; q.Q = stretch_q[i];
+        long long m = pr_geom(max_len[i], q.P, q.Q).m;
+        if (m > 2147483647LL) return fail(-1, "wave_prosody: the call exceeds 2^31 - 1 samples in or out");
+        if (pitch[i]) {
+            if (!taps_dev) return fail(-1, "wave_prosody: request %d has a pitch: the call needs the tap table", i);
+            int p, qq;
+            pr_pitch_ratio(pitch[i], &p, &qq);
+            const RatePair rp = rate_pair(p, qq);
+            const WeTile t = we_tile(rp);
+            if (!t.tq) return fail(-7, "wave_prosody: the tile of pitch %d does not fit the LDS", pitch[i]);
+            q.of = rp.of; q.nf = rp.nf; q.width = rp.width; q.L = rp.L; q.tq = t.tq;
+            q.tap_off = (int)f5hip_wave_prosody_tap_offset(pitch[i]);
+            q.mid_off = mid; q.tile0 = (int)tiles;
+            mid += (m + 7) & ~7LL;
+            m = ((long long)rp.nf * m + rp.of - 1) / rp.of;
+            tiles += std::max<long long>(((m + rp.nf - 1) / rp.nf + t.tq - 1) / t.tq, 1);   // (an empty request keeps one block: it writes its length)
+            lds = std::max(lds, t.lds);
+            hp.push_back(q);
+        }
+        changed += q.P != q.Q || pitch[i] != 0;
+        total_in += max_len[i]; total_out += m;
+        if (total_in > 2147483647LL || total_out > 2147483647LL || mid > 2147483647LL)
+            return fail(-1, "wave_prosody: the call exceeds 2^31 - 1 samples in or out");
+    }
+    PrWorkspace* const wsp = device_workspace<PrWorkspace>("wave_prosody");
+    if (!wsp) return -6;
+    PrWorkspace& ws = *wsp;
+    CK(dev_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_prosody requests"));
+    if (!hp.empty()) {
+        CK(dev_reserve(&ws.pitched, &ws.cap_pitched, hp.size(), "wave_prosody pitched requests"));
+        CK(dev_reserve(&ws.mid, &ws.cap_mid, (size_t)std::max<long long>(mid, 8), "wave_prosody stretched PCM"));
+        static unsigned lds_attr_done = 0;
+        if (lds > 64 * 1024 && f5_set_lds_attr((const void*)wave_pitch_kernel, kLdsMax, lds_attr_done) != hipSuccess)
+            return fail(-7, "wave_prosody: LDS opt-in");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t up = hp.empty() ? upload_sync(st, ws.reqs, h) : upload_sync(st, ws.reqs, h, ws.pitched, hp);
+    if (up != hipSuccess) return fail(-6, "wave_prosody metadata upload");
+    hipLaunchKernelGGL(wave_wsola_kernel, dim3((unsigned)n), dim3(kPrThreads), 0, st, ws.reqs, (const short*)pcm_dev, (const int*)len_dev, (short*)out_dev,
+                       ws.mid, (int*)out_len_dev);
+    CKL("wave_wsola");
+    g_counters[CNT_WAVE_PROSODY_LAUNCHES]++;
+    if (!hp.empty()) {
+        hipLaunchKernelGGL(wave_pitch_kernel, dim3((unsigned)tiles), dim3(256), lds, st, ws.pitched, (int)hp.size(), (const int*)len_dev, (const short*)ws.mid,
+                           taps_dev, (short*)out_dev, (int*)out_len_dev);
+        CKL("wave_pitch");
+        g_counters[CNT_WAVE_PROSODY_LAUNCHES]++;
+    }
+    g_counters[CNT_WAVE_PROSODY_REQUESTS] += changed;
     return 0;
 }

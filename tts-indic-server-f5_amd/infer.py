@@ -38,6 +38,8 @@ from .wave_codec import (ALL_ENCODINGS, DELIVERY_OPTIONS, FLAC_BLOCK, FLAC_ENCOD
                          StreamResampler, WaveSpec, check_flac_level, decode_flac, decode_g711, deliver_pcm16,
                          delivery_format, encode_flac, encode_g711, flac_crc8, flac_crc16, flac_stream_header, load_audio, load_wav, quantise_pcm16, read_flac,
                          rate_pair, request_flac_level, resample_pcm16, resample_sinc_hann, resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
+from .wave_codec import (PITCH_RANGE, PITCH_RATIOS, PROSODY_OPTIONS, WHOLE_WAVE_PROSODY, check_pitch, check_tempo, shift_pcm16,  # noqa: F401
+                         shifted_length, wsola_pcm16)
 from .wave_codec import (LOUDNESS_GATE_ABS, LOUDNESS_PEAK_CEILING, LOUDNESS_RANGE, LOUDNESS_TAPS, check_loudness, loudness_gain,  # noqa: F401
                          loudness_gain_constant, loudness_lufs, loudness_taps, measure_loudness, normalise_loudness_pcm16)
 from .wave_codec import _device_taps, _tap_tables  # noqa: F401  (the two caches: used below, and read as infer._X by the tests that bound them)
@@ -565,7 +567,7 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 
 # per-request options of `infer_requests` (the fourth element of a request) and of the serving routes
 REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "remove_silence", "sample_rate", "encoding",
-                   "loudness", "flac_level")   # the sampler's six, then `DELIVERY_OPTIONS` (`WaveSpec`)
+                   "loudness", "flac_level") + PROSODY_OPTIONS   # the sampler's six, then `DELIVERY_OPTIONS` and `PROSODY_OPTIONS` (`WaveSpec`)
 
 
 def needs_whole_wave(opts, streamed=False) -> bool:
@@ -644,7 +646,8 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
     with a `per_unit_time_grids` model, and in sampler-call order otherwise.
 
     The `DELIVERY_OPTIONS` (`remove_silence`, `loudness`, `sample_rate`, `encoding`, `flac_level`), per request, say what its finished wave
-    is: see `WaveSpec`.  Such a request's wave is `finish_pcm16` of its quantised joined wave and its triple names the delivery rate; the
+    is, and the `PROSODY_OPTIONS` (`tempo`, `pitch`) move its duration and pitch behind the model (`shift_pcm16`, where `speed` asks the
+    sampler for another take): see `WaveSpec`.  Such a request's wave is `finish_pcm16` of its quantised joined wave and its triple names the delivery rate; the
     ones that need the whole wave are a ValueError with `join=False` or a list of chunk texts.  A `ScriptRequest` (a multi-voice script:
     one segment per piece, each with its own voice) is accepted in place of a tuple: its
     segments' units ride in the same sampler call, one prompt per unit, and the same vocoder call, one group per segment; its triple is
@@ -724,7 +727,8 @@ def request_wave(gen_text, waves, cross_fade_duration=cross_fade_duration):
 # What `finish_requests` and `_chunk_waves` did since the last `backend_stats.clear()`: requests finished on the device / on the host,
 # `ops.wave_finish` calls, `ops.wave_encode` calls and the requests they encoded (`encode_calls`, `encode_requests`), and device-to-host copies
 # (chunk waves, spectrograms, PCM, encoded samples, lengths); `flac_bytes` is the size of the FLAC stream downloads; `loudness_calls` /
-# `loudness_requests`: `ops.wave_loudness` calls and the requests they normalised
+# `loudness_requests`: `ops.wave_loudness` calls and the requests they normalised; `prosody_calls` / `prosody_requests`: `ops.wave_prosody`
+# calls and the requests whose tempo or pitch they changed
 backend_stats: collections.Counter = collections.Counter()
 
 
@@ -744,7 +748,7 @@ def _per_request(value, n, what):
 
 
 def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cross_fade_duration, remove_silence=None, device_backend=False,
-                    want="float", sample_rate=None, encoding=None, loudness=None, flac_level=None):
+                    want="float", sample_rate=None, encoding=None, loudness=None, flac_level=None, tempo=None, pitch=None):
     """From the chunk waves of several requests (rms restored; numpy, or tensors as `_chunk_waves(on_device=True)` leaves them) to what each
     request gets.  A request whose text is a list of chunk texts (a streamed request's head or tail) gets its chunk waves as they are, like
     `request_wave`; a script's (`SegmentedWaves`: one list of chunk waves per segment) as one list per segment.  Any other request gets its
@@ -758,7 +762,7 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     `backend_stats`): a list text, chunk waves that are not on a HIP device, and a request of several chunks with one shorter than twice the
     fade, where the reference's nested cross-fades overlap and the kernel's closed form does not hold.
 
-    `sample_rate` / `encoding`, `loudness`, `flac_level`: each one value or one per request, None for the default; with the flag they are
+    `sample_rate` / `encoding`, `loudness`, `flac_level`, `tempo`, `pitch`: each one value or one per request, None for the default; with the flag they are
     the request's `WaveSpec`, and a request that sets any of them gets `finish_pcm16` of its int16 PCM (quantised whatever `want` says).
     With `device_backend` all of it stays on the device, chained on one stream behind `wave_finish`: the calls and the copies that come back
     are `_finish_on_device`'s, and `backend_stats` counts them."""
@@ -767,10 +771,11 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     flags = [False] * n if remove_silence is None else [bool(f) for f in remove_silence]
     if len(gen_texts) != n or len(flags) != n:
         raise ValueError("finish_requests: one text and one remove_silence flag per request")
-    keywords = (("sample_rate", sample_rate), ("encoding", encoding), ("loudness", loudness), ("flac_level", flac_level))
+    keywords = (("sample_rate", sample_rate), ("encoding", encoding), ("loudness", loudness), ("flac_level", flac_level), ("tempo", tempo),
+                ("pitch", pitch))
     columns = [_per_request(value, n, name) for name, value in keywords]
-    specs = [WaveSpec.of(dict(remove_silence=flag, sample_rate=rate, encoding=enc, loudness=lufs, flac_level=level))
-             for flag, rate, enc, lufs, level in zip(flags, *columns)]
+    specs = [WaveSpec.of(dict(remove_silence=flag, sample_rate=rate, encoding=enc, loudness=lufs, flac_level=level, tempo=rate_of_speech, pitch=semitones))
+             for flag, rate, enc, lufs, level, rate_of_speech, semitones in zip(flags, *columns)]
     return _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend, want)
 
 
@@ -837,9 +842,10 @@ def _device_request(waves):
 
 def finish_pcm16(pcm, spec) -> np.ndarray:
     """What a `WaveSpec` makes of a request's 24 kHz int16 PCM, the one host definition (the device back-end and `StreamDelivery` are held
-    to it byte for byte): `remove_silence_pcm` when flagged, `normalise_loudness_pcm16`, `deliver_pcm16`."""
+    to it byte for byte): `remove_silence_pcm` when flagged, `shift_pcm16` (tempo and pitch), `normalise_loudness_pcm16`, `deliver_pcm16`."""
     if spec.remove_silence:
         pcm = remove_silence_pcm(pcm, target_sample_rate)
+    pcm = shift_pcm16(pcm, spec.tempo, spec.pitch)
     pcm = normalise_loudness_pcm16(pcm, spec.loudness)
     return deliver_pcm16(pcm, *spec.format, flac_level=spec.flac_level if spec.flac else None)
 
@@ -858,7 +864,9 @@ def _finish_on_host(waves, text, cross_fade_duration, spec, want):
 def _finish_on_device(requests, fade, specs):
     """`finish_requests` for the requests the device back-end takes: `requests` = (chunk waves (device tensors), fades: `_device_request`)
     and their `specs`, the plain-format ones first.  ONE `ops.wave_finish` call -- `ops.wave_finish_joins` when a script is among them --;
-    directly behind it, when any request has a loudness target, ONE `ops.wave_loudness` call that normalises those in place; then on the
+    directly behind it, when any request names a tempo or a pitch, ONE `ops.wave_prosody` call for the whole batch (the others are copied
+    through), whose buffer, offsets, bounds and device lengths everything downstream reads in the place of `wave_finish`'s;
+    then, when any request has a loudness target, ONE `ops.wave_loudness` call that normalises those in place; then on the
     same stream one `ops.wave_flac` call per distinct rate of the "flac" requests (behind a `wave_encode(..., "pcm16")` call where the rate
     is not 24 kHz; the requests of a rate share it through its per-request levels, and a call in which nobody asks for level 1 is the
     level-0 call) and one `ops.wave_encode` call per other distinct delivery format.  Every call is queued before the first copy comes
@@ -880,6 +888,10 @@ def _finish_on_device(requests, fade, specs):
         pcm, lengths, offsets = ops.wave_finish(chunks, counts, fade, silence, target_sample_rate)
     else:
         pcm, lengths, offsets = ops.wave_finish_joins(chunks, counts, fade, [x for f in fades for x in f], silence, target_sample_rate)
+    if any(spec.prosody for spec in specs):   # one call for the batch; lengths stay on the device, and `joined` becomes the new bounds
+        pcm, lengths, offsets, joined = ops.wave_prosody(pcm, offsets, joined, lengths, [spec.stretch for spec in specs], [spec.pitch for spec in specs])
+        backend_stats["prosody_calls"] += 1
+        backend_stats["prosody_requests"] += sum(spec.prosody for spec in specs)
     targets = [spec.gain_constant for spec in specs]
     if any(t is not None for t in targets):   # in place, lengths still on the device: nothing comes back for it
         ops.wave_loudness(pcm, offsets, joined, lengths, targets)

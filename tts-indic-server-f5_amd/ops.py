@@ -623,6 +623,81 @@ def wave_flac(pcm, in_off, max_len, len_dev, sample_rate, level=None):
     return data, out_len, out_off.tolist()
 
 
+_prosody_taps: dict = {}   # device -> the twelve pitch tables there, uploaded once
+
+
+def wave_prosody_taps(device):
+    """The tap tables of the twelve pitch steps as ONE fp32 tensor on `device` (include/f5hip.h f5hip_wave_prosody: table s =
+    `wave_codec.resample_taps(p, q)` of `wave_codec.PITCH_RATIOS[s]` at float f5hip_wave_prosody_tap_offset(s)); uploaded once per device."""
+    from . import wave_codec
+    key = str(torch.device(device))
+    hit = _prosody_taps.get(key)
+    if hit is None:
+        lib = _lib.lib()
+        host = torch.zeros(int(lib.f5hip_wave_prosody_tap_offset(0)), dtype=torch.float32)
+        for s, (p, q) in wave_codec.PITCH_RATIOS.items():
+            taps = wave_codec.resample_taps(p, q)[3].reshape(-1)
+            at = int(lib.f5hip_wave_prosody_tap_offset(s))
+            host[at:at + taps.numel()] = taps
+        hit = _prosody_taps[key] = host.to(device)
+    return hit
+
+
+def wave_prosody(pcm, in_off, max_len, len_dev, stretches, pitches):
+    """The tempo and pitch of several finished requests in ONE library call and two launches, one when no request has a pitch
+    (include/f5hip.h f5hip_wave_prosody): their 24 kHz int16 PCM on the device -> each request's `wave_codec.shift_pcm16`, bit for bit.
+    `pcm`: the int16 device tensor that holds every request (`wave_finish`'s packed PCM; request i starts at sample in_off[i]); `max_len`,
+    `len_dev` as in `wave_encode`; `stretches` [n]: (P, Q) of each request (`WaveSpec.stretch`; (1, 1) leaves the duration alone);
+    `pitches` [n]: semitones, 0 for none.  A neutral request is copied through.  Returns (pcm2 int16 device, lengths2 int32 device [n],
+    offsets2, bounds2): request i's samples are pcm2[offsets2[i] : offsets2[i] + lengths2[i]], and bounds2[i] is the length that max_len[i]
+    gives -- what `wave_loudness`, `wave_encode` and `wave_flac` take in the place of `wave_finish`'s buffer, offsets, bounds and lengths."""
+    io = np.ascontiguousarray(np.asarray(in_off, dtype=np.int64))
+    ml = np.ascontiguousarray(np.asarray(max_len, dtype=np.int32))
+    n = len(ml)
+    st = np.asarray([tuple(s) for s in stretches], dtype=np.int64).reshape(-1, 2) if len(stretches) else np.zeros((0, 2), dtype=np.int64)
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in pitches):
+        raise _lib.F5HipError(f"wave_prosody: a pitch is a whole number of semitones (got {list(pitches)!r})")
+    pt = np.ascontiguousarray(np.asarray(pitches, dtype=np.int64))
+    if n < 1 or len(io) != n or len(st) != n or len(pt) != n:
+        raise _lib.F5HipError("wave_prosody: one offset, one length bound, one stretch (P, Q) and one pitch per request")
+    if not (torch.is_tensor(pcm) and pcm.dtype == torch.int16 and pcm.is_cuda and pcm.dim() == 1 and pcm.is_contiguous()):
+        raise _lib.F5HipError("wave_prosody: pcm must be a contiguous 1-D int16 device tensor")
+    if len_dev is not None and not (torch.is_tensor(len_dev) and len_dev.dtype == torch.int32 and len_dev.is_cuda and len_dev.numel() == n
+                                    and len_dev.device == pcm.device):
+        raise _lib.F5HipError("wave_prosody: len_dev must be an int32 tensor with one value per request on the pcm's device")
+    if (np.abs(st) > 1 << 20).any() or (st < 1).any() or (st[:, 0] > 2 * st[:, 1]).any() or (st[:, 1] > 2 * st[:, 0]).any():
+        raise _lib.F5HipError(f"wave_prosody: a stretch is a pair of positive terms up to 2^20 with a ratio from 1/2 to 2 (got {st.tolist()})")
+    if (np.abs(pt) > 6).any():
+        raise _lib.F5HipError(f"wave_prosody: a pitch is -6 to 6 semitones (got {pt.tolist()})")
+    sp, sq, pt = (np.ascontiguousarray(a.astype(np.int32)) for a in (st[:, 0], st[:, 1], pt))
+    taps = wave_prosody_taps(pcm.device) if pt.any() else None
+    if len_dev is not None:
+        len_dev = len_dev.contiguous()
+    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
+        try:
+            pcm2, lengths2, offsets2, bounds2 = torch_ops.ops().wave_prosody(pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(sp),
+                                                                             torch.from_numpy(sq), torch.from_numpy(pt), taps)
+        except RuntimeError as e:   # c10::Error from the operator's checks or the library
+            raise _lib.F5HipError(str(e)) from e
+        return pcm2, lengths2, offsets2.tolist(), bounds2.tolist()
+    from . import wave_codec
+    offsets2, bounds2, total = [], [], 0
+    for i in range(n):
+        if ml[i] < 0 or io[i] < 0 or int(io[i]) + int(ml[i]) > pcm.numel():
+            raise _lib.F5HipError(f"wave_prosody: request {i} reads samples [{io[i]}, {int(io[i]) + int(ml[i])}) of a tensor of {pcm.numel()}")
+        bounds2.append(wave_codec.shifted_length(int(ml[i]), (int(sp[i]), int(sq[i])), int(pt[i])))
+        offsets2.append(total)
+        total += (bounds2[-1] + 7) & ~7
+    oo = np.ascontiguousarray(np.asarray(offsets2, dtype=np.int64))
+    with torch.cuda.device(pcm.device):
+        pcm2 = torch.empty(max(total, 8), device=pcm.device, dtype=torch.int16)[:total]   # (a call of empty requests still has an address to give)
+        lengths2 = torch.empty(n, device=pcm.device, dtype=torch.int32)
+        anchor = pcm if pcm.numel() else torch.zeros(8, device=pcm.device, dtype=torch.int16)
+        _lib.check(_lib.lib().f5hip_wave_prosody(n, _p(anchor), _p(io), _p(ml), _p(len_dev), _p(sp), _p(sq), _p(pt), _p(taps), _p(pcm2), _p(oo), _p(lengths2),
+                                                 _lib.current_stream_ptr()), "f5hip_wave_prosody")
+    return pcm2, lengths2, offsets2, bounds2
+
+
 def wave_loudness_tile():
     """Samples one block of `wave_loudness`'s first launch owns (two 100 ms sub-blocks)."""
     return int(_lib.lib().f5hip_wave_loudness_tile())

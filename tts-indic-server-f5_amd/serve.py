@@ -61,8 +61,9 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
     `sway_sampling_coef` finite; `seed` an integer in 0..2**63 - 1; `ode_method` one of MAX_NFE_STEP's names.  `ode_method` (the argument)
     is the model's solver: `nfe_step`'s upper limit follows the request's own `ode_method` when it sets one, else the model's.
     The delivery options by `infer.WaveSpec`'s validators, one by one and then together (a `flac_level` beside another encoding is refused,
-    never ignored); `remove_silence` must be a bool, and `flac_level` is not "1".  What a request gets anyway -- False, 24000, "pcm16",
-    level 0 -- is dropped like None: the request is then what it is without the option."""
+    never ignored; a `tempo` and a `pitch` whose combined stretch leaves 1/2 .. 2 likewise); `remove_silence` must be a bool, and `flac_level`
+    is not "1".  What a request gets anyway -- False, 24000, "pcm16", level 0, tempo 1.0, pitch 0 -- is dropped like None: the request is
+    then what it is without the option."""
     out = {}
     own = options.get("ode_method") if "ode_method" in allowed else None
     if own is not None:
@@ -91,6 +92,14 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
             v = infer.check_loudness(v)                 # ValueError: "loudness must be ..."
         elif k == "flac_level":
             v = infer.check_flac_level(v)               # ValueError: "flac_level must be one of ..."
+        elif k == "tempo":
+            v = infer.check_tempo(v) / 100              # ValueError: "tempo must be a number from 0.5 to 2 ..."
+            if v == 1.0:
+                continue
+        elif k == "pitch":
+            v = infer.check_pitch(v)                    # ValueError: "pitch must be a whole number of semitones ..."
+            if v == 0:
+                continue
         elif k in ("nfe_step", "seed"):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"{k} must be an integer (got {v!r})")
@@ -134,6 +143,7 @@ DEVICE_DECODE_DEFAULT = True
 DEVICE_PRESTEP_DEFAULT = False
 STREAM_REMOVE_SILENCE = "remove_silence needs the request's whole wave: it is not available on a streaming path"
 STREAM_LOUDNESS = "loudness is measured on the request's whole wave: it is not available on a streaming path"
+STREAM_PROSODY = "tempo and pitch are applied to the request's whole wave: they are not available on a streaming path"
 
 
 def stream_refusal(opts):
@@ -141,7 +151,9 @@ def stream_refusal(opts):
     delivery format does not count, a stream applies it piece by piece)."""
     if not infer.needs_whole_wave(opts, streamed=True):
         return None
-    return STREAM_REMOVE_SILENCE if opts.get("remove_silence") else STREAM_LOUDNESS
+    if opts.get("remove_silence"):
+        return STREAM_REMOVE_SILENCE
+    return STREAM_LOUDNESS if opts.get("loudness") is not None else STREAM_PROSODY
 
 
 @dataclass
@@ -716,7 +728,9 @@ class TTSManager:
         generator (`infer.request_generator`), so the same seeded request gives the same audio whatever it is batched with (shape-invariant
         attention, one GPU).  `ode_method` ("euler", "midpoint", "rk4"; None: the model's): requests of different solvers share a batch, and
         the option reaches the model object only for a request that sets it.  The `infer.DELIVERY_OPTIONS` (`remove_silence`, `loudness`,
-        `sample_rate`, `encoding`, `flac_level`: see `infer.WaveSpec`) make the result `infer.finish_pcm16` of the wave's int16 PCM --
+        `sample_rate`, `encoding`, `flac_level`) and the `infer.PROSODY_OPTIONS` (`tempo`: the duration divided by it at the same pitch, where
+        `speed` asks the sampler for another take; `pitch`: whole semitones at the same duration; see `infer.WaveSpec`) make the result
+        `infer.finish_pcm16` of the wave's int16 PCM --
         computed on the device with `device_backend`, where every result is int16 PCM, and the same bytes either way."""
         if not self.model:
             raise ValueError("TTS model not loaded")
@@ -735,12 +749,12 @@ class TTSManager:
         rate, uint8 code bytes, or for "flac" the 42-byte stream header with the totals unknown and then the frames as they complete), and
         their concatenation equals `synthesize`'s result with the same options byte for byte (for "flac": behind the header, and both decode
         to the same samples).  The header comes from the first `next()` once the first chunk is synthesized, so a failing first chunk raises
-        there before any byte.  `remove_silence` and `loudness` need the whole wave: ValueError."""
+        there before any byte.  `remove_silence`, `loudness`, `tempo` and `pitch` need the whole wave: ValueError."""
         return self._serve(lambda: self._voice(ref_audio_path, ref_text), text, options, stream=True)
 
     def _stream(self, voice, ref_text, head, tail, opts=None):
         spec = infer.WaveSpec.of(opts or {})   # the delivery format is applied here, piece by piece: the head and tail requests stay plain
-        opts = {k: v for k, v in (opts or {}).items() if k not in infer.DELIVERY_OPTIONS}
+        opts = {k: v for k, v in (opts or {}).items() if k not in infer.DELIVERY_OPTIONS + infer.PROSODY_OPTIONS}
         return self._stream_requests(self._request(voice, ref_text, head, opts), self._request(voice, ref_text, tail, opts) if tail else None, spec)
 
     def _stream_requests(self, head_request, tail_request, spec, tail_pieces=None):
@@ -875,7 +889,7 @@ class TTSManager:
         if "seed" in opts:
             opts["generator"] = infer.request_generator(opts.pop("seed"))
         spec = infer.WaveSpec.of(opts)            # (applied to the pieces, as in `_stream`)
-        opts = {k: v for k, v in opts.items() if k not in infer.DELIVERY_OPTIONS}
+        opts = {k: v for k, v in opts.items() if k not in infer.DELIVERY_OPTIONS + infer.PROSODY_OPTIONS}
         chunked = [(voice, ref_text, infer.request_chunks(ref_text, voice.seconds, piece), speed) for voice, ref_text, piece, speed in segments]
         voice, ref_text, chunks, speed = chunked[0]
         head = self._request(voice, ref_text, chunks[:1], dict(opts, speed=speed) if speed is not None else opts)
@@ -1009,6 +1023,8 @@ def request_models():
     class SpeechFields(SamplerFields):               # what the three speech routes take on top: with SamplerFields, every infer.REQUEST_OPTIONS name
         speed: float | None = None
         remove_silence: bool | None = None
+        tempo: typing.Any = None                     # 0.5 to 2 in steps of 0.01: the duration divided by it, the pitch kept (infer.shift_pcm16); untyped like flac_level
+        pitch: typing.Any = None                     # whole semitones, -6 to 6, the duration kept; untyped, so that true and 2.0 arrive as sent and are refused
 
     class KannadaSynthesizeRequest(SpeechFields):    # S/utils/tts_utils.py:27-28
         text: str
@@ -1063,7 +1079,9 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     before anything is queued (400 with `check_request_options`'s message); an omitted field is the manager's setting (`ode_method`: the
     model's).  With a `seed`, the same request returns the same audio.  Every route takes `sample_rate`, `encoding`, `flac_level` and
     `loudness` as `infer.WaveSpec` describes them (a bad value or combination is a 400; `loudness` is measured on the whole wave, so it is
-    a 400 together with `"stream": true`: `STREAM_LOUDNESS`) and `response_format` ("wav", or "pcm" for the headerless samples / code bytes
+    a 400 together with `"stream": true`: `STREAM_LOUDNESS`), the speech routes also `tempo` (0.5 to 2: the duration divided by it, the pitch
+    kept) and `pitch` (whole semitones, -6 to 6, the duration kept), applied to the finished wave (`infer.shift_pcm16`; 400 together with
+    `"stream": true`: `STREAM_PROSODY`; not on the edit route, which keeps the recording's timing), and `response_format` ("wav", or "pcm" for the headerless samples / code bytes
     as `audio/pcm`); streamed or not, the body's samples are the same bytes.  `encoding: "flac"` is its own container: the body is the
     native FLAC stream as `audio/flac` with a `.flac` file name, and `response_format` must be absent (400 with "wav" or "pcm" beside it);
     streamed, the stream header comes with the totals unknown."""

@@ -2,8 +2,8 @@
 (`rate_pair`, `resample_taps`, `resample_sinc_hann`) with its tap-table caches, the integer resampler of finished PCM (`resample_pcm16`,
 `StreamResampler`), the BS.1770 loudness meter and normaliser (`measure_loudness`, `normalise_loudness_pcm16`), G.711 (`encode_g711`,
 `decode_g711`), FLAC (`encode_flac`, `decode_flac`, `StreamFlacEncoder`; the whole format in: `read_flac`, `load_audio`), the delivery
-format of a request (`delivery_format`, `deliver_pcm16`), its five delivery options as one value (`WaveSpec`; `StreamDelivery` applies it
-to a stream) and the bytes of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
+format of a request (`delivery_format`, `deliver_pcm16`), time-scale modification of finished PCM (`wsola_pcm16`, `shift_pcm16`: a request's
+`tempo` and `pitch`), its five delivery and two prosody options as one value (`WaveSpec`; `StreamDelivery` applies it to a stream) and the bytes of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
 round; `infer` and `serve` hand every public name on (`infer.load_wav`, `serve.wav_bytes`, ...)."""
 from __future__ import annotations
 
@@ -231,6 +231,17 @@ def _polyphase_pcm(xpad, taps64, of, nq):
     return np.clip(np.rint(acc), -32768, 32767).astype(np.int16).reshape(-1)
 
 
+def _polyphase_whole(pcm, of, nf, width, taps64):
+    """A whole int16 wave through `_polyphase_pcm`: ceil(nf n / of) outputs, `width` zeros in front of the samples and zeros behind."""
+    m = -(-nf * len(pcm) // of)
+    if m == 0:
+        return np.zeros(0, dtype=np.int16)
+    nq = -(-m // nf)
+    xpad = np.zeros(nq * of + 2 * width, dtype=np.float64)
+    xpad[width:width + len(pcm)] = pcm
+    return _polyphase_pcm(xpad, taps64, of, nq)[:m]
+
+
 def _output_taps(new_freq):
     of, nf, width, taps = resample_taps(SAMPLE_RATE, delivery_format(new_freq)[0])
     return of, nf, width, taps.numpy().astype(np.float64)
@@ -252,14 +263,7 @@ def resample_pcm16(pcm, new_freq) -> np.ndarray:
     pcm = _as_pcm16(pcm)
     if int(new_freq) == SAMPLE_RATE:
         return pcm
-    of, nf, width, taps64 = _output_taps(new_freq)
-    m = resampled_length(len(pcm), SAMPLE_RATE, new_freq)
-    if m == 0:
-        return np.zeros(0, dtype=np.int16)
-    nq = -(-m // nf)
-    xpad = np.zeros(nq * of + 2 * width, dtype=np.float64)
-    xpad[width:width + len(pcm)] = pcm
-    return _polyphase_pcm(xpad, taps64, of, nq)[:m]
+    return _polyphase_whole(pcm, *_output_taps(new_freq))
 
 
 class StreamResampler:
@@ -378,41 +382,55 @@ def deliver_pcm16(pcm, sample_rate=None, encoding=None, flac_level=None) -> np.n
 
 
 DELIVERY_OPTIONS = ("remove_silence", "loudness", "sample_rate", "encoding", "flac_level")
+PROSODY_OPTIONS = ("tempo", "pitch")              # beside them: time-scale modification of the finished PCM (`shift_pcm16`)
 WHOLE_WAVE = ("remove_silence, sample_rate and encoding need the request's whole wave: they are not available for a list of chunk texts (a streamed "
               "request, whose owner applies the delivery format piece by piece: StreamResampler, encode_g711) or with join=False")
 WHOLE_WAVE_LOUDNESS = ("loudness is measured on the request's whole wave: it is not available for a list of chunk texts, on a streaming path or "
                        "with join=False")
+WHOLE_WAVE_PROSODY = ("tempo and pitch are applied to the request's whole wave: they are not available for a list of chunk texts, on a streaming "
+                      "path or with join=False")
 
 
 @dataclasses.dataclass(frozen=True)
 class WaveSpec:
-    """What a request asks of its finished wave, the five `DELIVERY_OPTIONS` as one immutable value: the planner makes it (`WaveSpec.of`),
-    and every finishing path -- `infer.finish_pcm16` on the host, `infer._finish_on_device`, `StreamDelivery` for a stream -- reads it.
-    All five are pure functions of the request's canonical result, its joined 24 kHz wave quantised to int16 PCM, applied in this order:
+    """What a request asks of its finished wave, the five `DELIVERY_OPTIONS` and the two `PROSODY_OPTIONS` as one immutable value: the
+    planner makes it (`WaveSpec.of`), and every finishing path -- `infer.finish_pcm16` on the host, `infer._finish_on_device`,
+    `StreamDelivery` for a stream -- reads it.
+    All are pure functions of the request's canonical result, its joined 24 kHz wave quantised to int16 PCM, applied in this order:
       `remove_silence`  the reference's `remove_silence_for_generated_wav` (`audio_prep.remove_silence_pcm`): pauses of 1 s or more shrink
                         to 500 ms on each side; the result is int16 PCM whatever the caller wanted otherwise.
+      `tempo`, `pitch`  time-scale modification (`shift_pcm16`: WSOLA, then a rational resampler for the pitch): the duration divided by
+                        `tempo` (0.5 to 2 in steps of 0.01) at the same pitch, the pitch moved by `pitch` whole semitones (-6 to 6) at the
+                        same duration; 1.0 and 0 keep the samples as they are.  So loudness is measured on what is delivered.
       `loudness`        a programme loudness target in LUFS within LOUDNESS_RANGE (ITU-R BS.1770-4; `normalise_loudness_pcm16`: the sample
                         peak stays at or below -1 dBFS); None keeps the level as synthesized.
       `sample_rate`, `encoding`  the delivery format (`deliver_pcm16`): one of OUTPUT_SAMPLE_RATES (`resample_pcm16`), then "pcm16", "mulaw" /
                         "alaw" (`encode_g711`: uint8 code bytes) or "flac" (`encode_flac`: a uint8 array that holds the whole stream).
       `flac_level`      0, or 1 for LPC subframes among the candidates of the stream's full blocks (never larger, the same samples); only a
                         "flac" request may name one: beside any other encoding a level is refused, never ignored.
-    The first two, and a format other than 24 kHz "pcm16", need the request's whole wave (`needs_whole_wave`): they are refused for a list
-    of chunk texts and with join=False; a stream applies the format piece by piece and refuses the other two."""
+    `remove_silence`, `loudness`, `tempo`, `pitch`, and a format other than 24 kHz "pcm16", need the request's whole wave
+    (`needs_whole_wave`): they are refused for a list of chunk texts and with join=False; a stream applies the format piece by piece and
+    refuses the others."""
     remove_silence: bool = False
     loudness: float | None = None
     sample_rate: int = SAMPLE_RATE
     encoding: str = "pcm16"
     flac_level: int = 0
+    tempo: float = 1.0
+    pitch: int = 0
 
     @classmethod
     def of(cls, options) -> "WaveSpec":
-        """The spec of a mapping of options: a missing key or None is the default, other keys are ignored.  The one place where the five are
-        checked together -- `check_loudness`, `request_flac_level`, `delivery_format`, in that order, with their messages (ValueError)."""
+        """The spec of a mapping of options: a missing key or None is the default, other keys are ignored.  The one place where they are
+        checked together -- `check_loudness`, `request_flac_level`, `delivery_format`, then `check_tempo`, `check_pitch` and
+        `prosody_stretch`, in that order, with their messages (ValueError)."""
         get = options.get
         loudness = check_loudness(get("loudness"))
         level = request_flac_level(get("flac_level"), get("encoding"))
-        return cls(bool(get("remove_silence")), loudness, *delivery_format(get("sample_rate"), get("encoding")), level)
+        fmt = delivery_format(get("sample_rate"), get("encoding"))
+        hundredths, pitch = check_tempo(get("tempo")), check_pitch(get("pitch"))
+        prosody_stretch(hundredths, pitch)
+        return cls(bool(get("remove_silence")), loudness, *fmt, level, hundredths / 100, pitch)
 
     @property
     def format(self):
@@ -431,12 +449,25 @@ class WaveSpec:
         """`loudness_gain_constant` of the target, what `ops.wave_loudness` takes; None without one."""
         return None if self.loudness is None else loudness_gain_constant(self.loudness)
 
+    @property
+    def prosody(self) -> bool:
+        """Whether `tempo` or `pitch` changes the samples."""
+        return self.tempo != 1.0 or self.pitch != 0
+
+    @property
+    def stretch(self):
+        """(P, Q) of `prosody_stretch`: what `ops.wave_prosody` takes beside the pitch."""
+        return prosody_stretch(check_tempo(self.tempo), self.pitch)
+
     def needs_whole_wave(self, streamed=False) -> bool:
         """Whether the request cannot be handed out chunk by chunk.  `streamed`: the format does not count, the stream's owner applies it."""
-        return self.remove_silence or self.loudness is not None or not (streamed or self.plain_format)
+        return self.remove_silence or self.loudness is not None or self.prosody or not (streamed or self.plain_format)
 
     def whole_wave_message(self) -> str:
-        """The refusal of a request that `needs_whole_wave` where it cannot have it: `WHOLE_WAVE_LOUDNESS` when `loudness` is the reason."""
+        """The refusal of a request that `needs_whole_wave` where it cannot have it: `WHOLE_WAVE_LOUDNESS` when `loudness` is the reason,
+        `WHOLE_WAVE_PROSODY` when `tempo` / `pitch` are the only one."""
+        if self.prosody and not self.remove_silence and self.loudness is None and self.plain_format:
+            return WHOLE_WAVE_PROSODY
         return WHOLE_WAVE_LOUDNESS if self.loudness is not None and not self.remove_silence else WHOLE_WAVE
 
 
@@ -572,6 +603,156 @@ def normalise_loudness_pcm16(pcm, target) -> np.ndarray:
         return pcm
     g = loudness_gain(n2, S2, peak, loudness_gain_constant(target))
     return np.clip(np.rint(pcm.astype(np.float64) * g), -32768, 32767).astype(np.int16)
+
+
+# ----------------------------------------- prosody: a request's `tempo` and `pitch`, time-scale modification of its 24 kHz int16 PCM (WSOLA,
+# then a rational resampler for the pitch) in integers with no freedom left -- so the device call (csrc/wave_out.h wave_wsola_kernel /
+# wave_pitch_kernel, f5hip_wave_prosody) is held to `shift_pcm16` bit for bit, like every other back-end stage.
+# `wsola_pcm16(x, P, Q)`: int16 x of length n -> int16 y of length m = ceil(n P / Q), the same pitch, 1/2 <= P / Q <= 2.
+#   constants  PROSODY_FRAME L = 960 (40 ms), PROSODY_HOP H = 480, PROSODY_SEARCH D = 240 (10 ms)
+#   window     W[i] = rint(32768 sin^2(pi (2 i + 1) / (2 L))) for i < H, in fp64, half to even; W[H + i] = 32768 - W[i]: two overlapping
+#              frames weigh exactly 2^15 (csrc/wsola_window.inc holds the 480 integers; a test equates the two, so no libm decides a sample)
+#   source     xt[j] = x[j] for 0 <= j < n, else 0
+#   frames     K = ceil(m / H) + 1 of them; frame k's nominal start is p_k = floor(k H Q / P) - H (64-bit products); s_0 = -H
+#   search     for k >= 1, with t = s_{k-1} + H (where frame k - 1 would go on): c(d) = sum_{i < L} |xt[p_k + d + i] - xt[t + i]|; d_k
+#              minimises it over -D .. D, ties to the smaller |d|, then to the negative one; s_k = p_k + d_k
+#   output     y[j] = (W[H + i] xt[s_k + H + i] + W[i] xt[s_{k+1} + i] + 16384) >> 15 (a floor shift), k = j // H, i = j - k H
+# Bit budget: c < 960 * 65535 < 2^26 (a packed key c 2^9 + rank(d) below 2^35 orders cost, then the tie rule: rank(d) = 2 |d| - (d < 0));
+# the numerator stays within 2^30 + 2^14; y is a convex combination up to rounding and never leaves int16: no clip.  P == Q gives the input
+# back through the search (cost 0 at d = 0, which the tie rule prefers): `_wsola_frames` is the entry without the identity shortcut.
+# Beyond a stretch of 2 the nominal starts advance by less than H / 2 = D and the search cannot reach the continuation of the frame before.
+# `shift_pcm16(pcm, tempo, pitch)`: T = rint(100 tempo), p / q = PITCH_RATIOS[pitch]; the stretch P / Q = reduce(100 p, T q);
+# `wsola_pcm16(pcm, P, Q)`, then for a pitch the polyphase arithmetic of `resample_pcm16` with the table `resample_taps(p, q)` (the pair
+# plays the role of the rates): ceil(q m / p) samples, the duration n 100 / T and the pitch times p / q.
+PROSODY_FRAME, PROSODY_HOP, PROSODY_SEARCH = 960, 480, 240
+PROSODY_TEMPO_RANGE = (0.5, 2.0)
+# p / q per semitone: within 2 cents of 2^(s / 12), each tap table (`rate_pair(p, q)`: q rows) below 11 KB; negative steps take the reciprocal
+PITCH_RATIOS = {1: (18, 17), 2: (46, 41), 3: (44, 37), 4: (29, 23), 5: (4, 3), 6: (41, 29)}
+PITCH_RATIOS.update({-s: (q, p) for s, (p, q) in list(PITCH_RATIOS.items())})
+PITCH_RANGE = (-6, 6)
+_wsola_window = None
+_pitch_tables: dict = {}
+
+
+def wsola_window() -> np.ndarray:
+    """The WSOLA window, int64 [PROSODY_FRAME] (read-only): the rising half rounded from fp64, the falling half its complement to 2^15."""
+    global _wsola_window
+    if _wsola_window is None:
+        i = np.arange(PROSODY_HOP, dtype=np.float64)
+        rise = np.rint(32768.0 * np.sin(np.pi * (2.0 * i + 1.0) / (2.0 * PROSODY_FRAME)) ** 2).astype(np.int64)
+        w = np.concatenate([rise, 32768 - rise])
+        w.setflags(write=False)
+        _wsola_window = w
+    return _wsola_window
+
+
+def check_tempo(tempo) -> int:
+    """A request's `tempo` option as whole hundredths T: None (absent) is 100; a number from 0.5 to 2 whose hundredfold is a whole number
+    (within 1e-9); a bool, any other type and any other value are a ValueError."""
+    if tempo is None:
+        return 100
+    bad = ValueError(f"tempo must be a number from 0.5 to 2 in steps of 0.01 (got {tempo!r})")
+    if isinstance(tempo, (bool, np.bool_)) or not isinstance(tempo, (int, float, np.integer, np.floating)):
+        raise bad
+    scaled = 100.0 * float(tempo)
+    if not math.isfinite(scaled) or abs(scaled - round(scaled)) > 1e-9 or not 50 <= round(scaled) <= 200:
+        raise bad
+    return int(round(scaled))
+
+
+def check_pitch(pitch) -> int:
+    """A request's `pitch` option: None (absent) is 0; an int of whole semitones within PITCH_RANGE; a bool, a float and anything else are
+    a ValueError."""
+    if pitch is None:
+        return 0
+    if isinstance(pitch, (bool, np.bool_)) or not isinstance(pitch, (int, np.integer)) or not PITCH_RANGE[0] <= int(pitch) <= PITCH_RANGE[1]:
+        raise ValueError(f"pitch must be a whole number of semitones from -6 to 6 (got {pitch!r})")
+    return int(pitch)
+
+
+def prosody_stretch(hundredths, pitch):
+    """(P, Q) of a tempo in hundredths (`check_tempo`) and a pitch (`check_pitch`): the one WSOLA stretch reduce(100 p, T q) that both
+    need; a stretch outside [1/2, 2] is a ValueError."""
+    p, q = PITCH_RATIOS[pitch] if pitch else (1, 1)
+    P, Q = 100 * p, int(hundredths) * q
+    g = math.gcd(P, Q)
+    P, Q = P // g, Q // g
+    if P > 2 * Q or Q > 2 * P:
+        raise ValueError(f"tempo {hundredths / 100} with pitch {pitch} stretches the wave by {P}/{Q}: outside 1/2 to 2")
+    return P, Q
+
+
+def wsola_rank(d):
+    """The tie rank of a search offset: 0, -1, 1, -2, 2, ... -> 0, 1, 2, 3, 4, ..."""
+    return 2 * np.abs(d) - (d < 0)
+
+
+def _wsola_frames(x, P, Q):
+    """(y int16 [ceil(n P / Q)], s: the frame starts s_0 .. s_{K-1}) of the definition above, with no shortcut for P == Q.  Per frame one
+    [481, 960] table of absolute differences."""
+    L, H, D = PROSODY_FRAME, PROSODY_HOP, PROSODY_SEARCH
+    n = len(x)
+    m = -(-n * P // Q)
+    if m == 0:
+        return np.zeros(0, dtype=np.int16), [-H]
+    K = -(-m // H) + 1
+    front = H + D                                                       # the least index read: p_1 - D >= -H - D
+    back = ((K - 1) * H * Q) // P - H + D + L + H                       # an index no read reaches
+    xt = np.zeros(front + max(back, n) + 1, dtype=np.int32)
+    xt[front:front + n] = x
+    rank = wsola_rank(np.arange(-D, D + 1, dtype=np.int64))
+    s = [-H]
+    for k in range(1, K):
+        p = (k * H * Q) // P - H
+        t = s[-1] + H
+        cands = np.lib.stride_tricks.sliding_window_view(xt[front + p - D:front + p + D + L], L)
+        cost = np.abs(cands - xt[front + t:front + t + L]).sum(axis=1, dtype=np.int64)
+        s.append(p - D + int(np.argmin(cost * 512 + rank)))
+    W = wsola_window()
+    at = np.asarray(s, dtype=np.int64)[:, None] + np.arange(H, dtype=np.int64)[None] + front
+    y = (W[H:] * xt[at[:-1] + H] + W[:H] * xt[at[1:]] + 16384) >> 15
+    return y.reshape(-1)[:m].astype(np.int16), s
+
+
+def wsola_pcm16(x, P, Q) -> np.ndarray:
+    """int16 PCM x [n] stretched to ceil(n P / Q) samples at the same pitch, by the definition above; P == Q returns the input."""
+    x = _as_pcm16(x)
+    if isinstance(P, bool) or isinstance(Q, bool) or not all(isinstance(v, (int, np.integer)) for v in (P, Q)) or P < 1 or Q < 1:
+        raise ValueError(f"wsola_pcm16: the stretch is a pair of positive ints (got {P!r}, {Q!r})")
+    P, Q = int(P), int(Q)
+    if P > 2 * Q or Q > 2 * P:
+        raise ValueError(f"wsola_pcm16: a stretch of {P}/{Q} is outside 1/2 to 2")
+    return x if P == Q else _wsola_frames(x, P, Q)[0]
+
+
+def pitch_taps(pitch):
+    """(of, nf, width, taps fp64 [nf, L]) of a pitch step: `resample_taps(p, q)` of its ratio, of = p, nf = q.  Computed once per step."""
+    hit = _pitch_tables.get(pitch)
+    if hit is None:
+        of, nf, width, taps = resample_taps(*PITCH_RATIOS[pitch])
+        hit = _pitch_tables[pitch] = (of, nf, width, taps.numpy().astype(np.float64))
+    return hit
+
+
+def shift_pcm16(pcm, tempo=None, pitch=None) -> np.ndarray:
+    """A request's `tempo` and `pitch` on its 24 kHz int16 PCM [n], the host definition above: about n 100 / T samples, ceil(q ceil(n P /
+    Q) / p) of them.  Both neutral (None, 1.0, 0) returns the input itself.  What `ops.wave_prosody` equals byte for byte."""
+    pcm = _as_pcm16(pcm)
+    hundredths, pitch = check_tempo(tempo), check_pitch(pitch)
+    P, Q = prosody_stretch(hundredths, pitch)
+    if hundredths == 100 and pitch == 0:
+        return pcm
+    y = wsola_pcm16(pcm, P, Q)
+    return _polyphase_whole(y, *pitch_taps(pitch)) if pitch else y
+
+
+def shifted_length(n, stretch, pitch) -> int:
+    """Samples `shift_pcm16` returns for n under `stretch` = (P, Q) and `pitch`."""
+    m = -(-int(n) * stretch[0] // stretch[1])
+    if pitch:
+        p, q = PITCH_RATIOS[pitch]
+        m = -(-q * m // p)
+    return m
 
 
 _G711_TAGS = {"mulaw": 7, "alaw": 6}   # WAVE_FORMAT_MULAW, WAVE_FORMAT_ALAW
