@@ -207,3 +207,42 @@ def test_torch_library_ops_register_without_a_gpu():
     assert schemas["bigvgan_forward"] == "f5hip::bigvgan_forward(int handle, Tensor mel, int total_upsample) -> Tensor"
     with pytest.raises(RuntimeError, match="must be a contiguous fp32 tensor on the HIP device"):   # argument checks run before any device work
         torch.ops.f5hip.vocos_decode(0, torch.zeros(1, 100, 8), 256)
+
+
+# the schemas of the wave operators as the TORCH_LIBRARY block registers them: part of the interface
+WAVE_OP_SCHEMAS = {
+    "wave_encode": "f5hip::wave_encode(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int new_freq, int encoding, Tensor? taps) -> "
+                   "(Tensor, Tensor, Tensor)",
+    "wave_flac": "f5hip::wave_flac(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int sample_rate) -> (Tensor, Tensor, Tensor)",
+    "wave_flac_levels": "f5hip::wave_flac_levels(Tensor[] pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, int sample_rate, Tensor level) -> "
+                        "(Tensor, Tensor, Tensor)",
+    "wave_loudness": "f5hip::wave_loudness(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor gain_k) -> Tensor",
+    "wave_prosody": "f5hip::wave_prosody(Tensor pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor stretch_p, Tensor stretch_q, Tensor pitch, "
+                    "Tensor? taps) -> (Tensor, Tensor, Tensor, Tensor)",
+}
+
+
+def test_wave_operators_report_their_own_name_from_the_shared_checks():
+    """The wave operators check their request table (pcm, in_off, max_len, len_dev) in one shared helper of csrc/torch_ops.cpp: a refusal must
+    still name the operator that was called, not the helper, and must come before any device call (there is no device here).  Two requests,
+    `in_off` one element short, then a host tensor as `pcm`.  wave_flac_levels shares wave_flac's body and reports the table as wave_flac."""
+    import torch
+    from tts_indic_server_f5_amd import torch_ops
+    assert torch_ops.load(), f"{torch_ops.TORCH_LIB_PATH} missing: run __graft_entry__.build()"
+    i32 = lambda *v: torch.tensor(v, dtype=torch.int32)   # noqa: E731
+    pcm, io, ml = torch.zeros(64, dtype=torch.int16), torch.zeros(2, dtype=torch.int64), i32(16, 16)
+    calls = {
+        "wave_encode": lambda p, o: torch.ops.f5hip.wave_encode([p], o, ml, None, 24000, 0, None),
+        "wave_flac": lambda p, o: torch.ops.f5hip.wave_flac([p], o, ml, None, 24000),
+        "wave_flac_levels": lambda p, o: torch.ops.f5hip.wave_flac_levels([p], o, ml, None, 24000, i32(0, 1)),
+        "wave_loudness": lambda p, o: torch.ops.f5hip.wave_loudness(p, o, ml, None, torch.zeros(2, dtype=torch.float64)),
+        "wave_prosody": lambda p, o: torch.ops.f5hip.wave_prosody(p, o, ml, None, i32(1, 1), i32(1, 1), i32(0, 0), None),
+    }
+    assert set(calls) == set(WAVE_OP_SCHEMAS)
+    for name, call in calls.items():
+        assert str(getattr(torch.ops.f5hip, name).default._schema) == WAVE_OP_SCHEMAS[name]
+        said = "wave_flac" if name == "wave_flac_levels" else name
+        for args, words in (((pcm, io[:1]), "one value per request"), ((pcm, io), "HIP device")):
+            with pytest.raises(RuntimeError) as e:
+                call(*args)
+            assert f"f5hip::{said}: " in str(e.value) and words in str(e.value), (name, words, str(e.value))

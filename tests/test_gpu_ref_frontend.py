@@ -122,6 +122,27 @@ def test_a_clip_in_a_batch_equals_its_own_call(sr):
             assert rms[k:k + 1].view(np.uint32) == solo[i][1].view(np.uint32), (sr, order, i)
 
 
+def test_ctypes_and_torch_op_paths_agree():
+    """`ops.ref_frontend` through the TORCH_LIBRARY operator and through ctypes: the same C entry point, so the same bits.  One call of a mono
+    clip of 3 001 samples and a stereo clip of 1 777 at 44 100 -> 24 000 Hz: odd lengths that are no multiple of the 147-sample polyphase
+    period, so the ragged tail and the channel mix are both exercised."""
+    from tts_indic_server_f5_amd import torch_ops
+    dev = torch.device("cuda:0")
+    clips = [_clip(3001, 1, 0.3, seed=71), _clip(1777, 2, 0.02, seed=72)]
+    packed = torch.from_numpy(np.concatenate([c.reshape(-1) for c in clips])).to(dev)
+    taps = infer.resample_taps(44100, 24000)[3].to(dev)
+    run = lambda: ops.ref_frontend(packed, [3001, 1777], [1, 2], 44100, 24000, taps, FLOOR)   # noqa: E731
+    out, rms, n_out = run()
+    assert torch_ops.load()
+    try:
+        torch_ops._loaded = False                      # force the ctypes binding
+        out2, rms2, n_out2 = run()
+    finally:
+        torch_ops._loaded = True
+    assert n_out == n_out2 == [-(-3001 * 80 // 147), -(-1777 * 80 // 147)] and out.numel() == sum(n_out)
+    assert torch.equal(out.view(torch.int32), out2.view(torch.int32)) and torch.equal(rms.view(torch.int32), rms2.view(torch.int32))
+
+
 def test_refusals_come_before_any_launch():
     lib = _lib.lib()
     dev = torch.device("cuda:0")

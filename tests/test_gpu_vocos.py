@@ -122,6 +122,23 @@ def test_vocos_decode_silence_frames(vocos):
     _within_model("vocos silence frames b2 t64", sd, mel, got)
 
 
+def test_decode_ragged_ctypes_and_torch_op_paths_agree(vocos):
+    """`decode_ragged` through the TORCH_LIBRARY operator and through ctypes: the same C entry point, so the same bits.  Items of 2 frames (the
+    minimum), 129 (one past a 128-row slab) and 5 (a short one behind it)."""
+    from tts_indic_server_f5_amd import torch_ops
+    g = torch.Generator().manual_seed(7)
+    mels = [torch.randn(100, t, generator=g) * 1.5 - 1.0 for t in (2, 129, 5)]
+    via_op = vocos.decode_ragged(mels)
+    assert torch_ops.load()
+    try:
+        torch_ops._loaded = False                      # force the ctypes binding
+        via_ctypes = vocos.decode_ragged(mels)
+    finally:
+        torch_ops._loaded = True
+    assert [tuple(w.shape) for w in via_op] == [(256 * (m.shape[1] - 1),) for m in mels]
+    assert len(via_ctypes) == len(via_op) and all(torch.equal(a, b) for a, b in zip(via_op, via_ctypes))
+
+
 def test_mel_then_vocos_roundtrip_lengths(vocos):
     from tts_indic_server_f5_amd.mel import mel_spectrogram
     wave = synth.ref_audio(24_000).cuda()

@@ -12,23 +12,26 @@
 //   torch.ops.f5hip.bigvgan_forward(handle, mel, total_upsample) -> Tensor                                       F/infer/utils_infer.py:474
 //   torch.ops.f5hip.bigvgan_forward_ragged(handle, mel, frames, channels, total_upsample) -> Tensor (packed)         F/infer/utils_infer.py:474
 //   torch.ops.f5hip.ref_frontend(wave, n_in, channels, orig_freq, new_freq, taps?, rms_floor) -> (Tensor packed, Tensor rms)   F/infer/utils_infer.py:423-433
+//   torch.ops.f5hip.wave_finish(chunks[], chunks_per_request, fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/utils_infer.py:485-519,530-539
+//   torch.ops.f5hip.wave_finish_joins(chunks[], chunks_per_request, fade, chunk_fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/infer_cli.py:181-208
+//   torch.ops.f5hip.mel_spectrogram_ragged(waves[], n_fft, hop_length, n_mels, sample_rate, variant) -> Tensor mel [sum T, n_mels]   F/model/modules.py:30-143
+//   torch.ops.f5hip.wave_encode(pcm[], in_off, max_len, len_dev?, new_freq, encoding, taps?) -> (Tensor bytes uint8, Tensor lengths int32, Tensor offsets int64 host)
+//   torch.ops.f5hip.wave_flac(pcm[], in_off, max_len, len_dev?, sample_rate) -> (Tensor streams uint8, Tensor lengths int32, Tensor offsets int64 host)
+//   torch.ops.f5hip.wave_flac_levels(pcm[], in_off, max_len, len_dev?, sample_rate, level int32 host) -> the same, each request at its FLAC level
+//   torch.ops.f5hip.flac_decode(data, begin, end, info, total, max_samples) -> (Tensor statuses and planes int32, Tensor offsets int64 host)
+//   torch.ops.f5hip.ref_prestep(frames, n_in, channels, clip_short, rate) -> (Tensor planes fp32, Tensor info int32 [n, 2])   F/infer/utils_infer.py:282-350
+//   torch.ops.f5hip.wave_loudness(pcm, in_off, max_len, len_dev?, gain_k) -> Tensor stats int64 [n, 4]; pcm is normalised in place
+//   torch.ops.f5hip.wave_prosody(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, taps?) -> (Tensor pcm int16, Tensor lengths int32, Tensor offsets int64 host, Tensor bounds int32 host)
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <cmath>
 #include <tuple>
 #include <vector>
 
-//   torch.ops.f5hip.wave_finish(chunks[], chunks_per_request, fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/utils_infer.py:485-519,530-539
-//   torch.ops.f5hip.wave_finish_joins(chunks[], chunks_per_request, fade, chunk_fade, remove_silence, sample_rate) -> (Tensor pcm int16, Tensor lengths int32)   F/infer/infer_cli.py:181-208
-//   torch.ops.f5hip.mel_spectrogram_ragged(waves[], n_fft, hop_length, n_mels, sample_rate, variant) -> Tensor mel [sum T, n_mels]   F/model/modules.py:30-143
-//   torch.ops.f5hip.wave_flac(pcm[], in_off, max_len, len_dev?, sample_rate) -> (Tensor streams uint8, Tensor lengths int32, Tensor offsets int64 host)
-//   torch.ops.f5hip.wave_flac_levels(pcm[], in_off, max_len, len_dev?, sample_rate, level int32 host) -> the same, each request at its FLAC level
-//   torch.ops.f5hip.flac_decode(data, begin, end, info, total, max_samples) -> (Tensor statuses and planes int32, Tensor offsets int64 host)
-//   torch.ops.f5hip.ref_prestep(frames, n_in, channels, clip_short, rate) -> (Tensor planes fp32, Tensor info int32 [n, 2])   F/infer/utils_infer.py:282-350
-//   torch.ops.f5hip.wave_encode(pcm[], in_off, max_len, len_dev?, new_freq, encoding, taps?) -> (Tensor bytes uint8, Tensor lengths int32, Tensor offsets int64 host)
 #include "../../include/f5hip.h"
 #include "rate_pair.h"
 #include "wave_prosody_core.h"
@@ -43,6 +46,90 @@ void check_dev_f32(const at::Tensor& t, const char* name) {
 void check_host(const at::Tensor& t, at::ScalarType ty, const char* name) {
     TORCH_CHECK(!t.is_cuda() && t.scalar_type() == ty && t.is_contiguous(), "f5hip: ", name, " must be a contiguous host tensor of the documented dtype");
 }
+template <class T>
+const T* opt_ptr(const c10::optional<at::Tensor>& t) { return t.has_value() ? t->data_ptr<T>() : nullptr; }
+
+// ---- the steps the audio operators share (ops.py holds the same helpers for the ctypes binding); `op` names the operator in the messages
+
+// The request table (pcm, in_off, max_len, len_dev) of the wave operators, checked: in_off [n] int64 host, max_len [n] int32 host; pcm one
+// contiguous 1-D int16 device tensor that holds every request or, where the operator allows `several`, one per request on one device;
+// len_dev None or [n] int32 on that device
+struct PcmRequests {
+    int64_t n;
+    const int64_t* io;
+    const int32_t* ml;
+    const int32_t* len_dev;   // or null
+    c10::Device device;
+};
+PcmRequests check_pcm_requests(const char* op, at::TensorList pcm, const at::Tensor& in_off, const at::Tensor& max_len, const c10::optional<at::Tensor>& len_dev,
+                               bool several) {
+    check_host(in_off, at::kLong, "in_off"); check_host(max_len, at::kInt, "max_len");
+    const int64_t n = max_len.numel();
+    TORCH_CHECK(max_len.dim() == 1 && n > 0 && in_off.numel() == n, "f5hip::", op, ": in_off and max_len need one value per request");
+    TORCH_CHECK(pcm.size() == 1 || (several && (int64_t)pcm.size() == n), "f5hip::", op, ": pcm is one tensor", several ? " or one per request" : "", " (got ",
+                pcm.size(), " for ", n, ")");
+    for (const at::Tensor& t : pcm)
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kShort && t.is_contiguous() && t.dim() == 1 && t.device() == pcm[0].device(), "f5hip::", op,
+                    ": pcm must be contiguous 1-D int16 tensors on one HIP device");
+    if (len_dev.has_value())
+        TORCH_CHECK(len_dev->is_cuda() && len_dev->scalar_type() == at::kInt && len_dev->is_contiguous() && len_dev->numel() == n &&
+                    len_dev->device() == pcm[0].device(), "f5hip::", op, ": len_dev must be a contiguous int32 tensor with one value per request on the pcm's device");
+    return {n, in_off.data_ptr<int64_t>(), max_len.data_ptr<int32_t>(), opt_ptr<int32_t>(len_dev), pcm[0].device()};
+}
+
+// Where a request table is read from: request i reads samples [io[i], io[i] + ml[i]) of its tensor (the one tensor, or tensor i), which must
+// hold them.  anchor: the first tensor that has an address -- the library's `pcm` --, rel[i]: request i's first sample relative to it
+struct PcmSources {
+    at::Tensor anchor;
+    std::vector<int64_t> rel;
+    int16_t* base() const { return anchor.data_ptr<int16_t>(); }
+};
+PcmSources pcm_sources(const char* op, at::TensorList pcm, const PcmRequests& rq) {
+    PcmSources s{at::Tensor(), std::vector<int64_t>(rq.n)};
+    for (const at::Tensor& t : pcm)
+        if (t.numel() && !s.anchor.defined()) s.anchor = t;
+    if (!s.anchor.defined()) s.anchor = at::zeros({8}, pcm[0].options());
+    for (int64_t i = 0; i < rq.n; i++) {
+        const at::Tensor& t = pcm[pcm.size() == 1 ? 0 : i];
+        TORCH_CHECK(rq.ml[i] >= 0 && rq.io[i] >= 0 && rq.io[i] + rq.ml[i] <= t.numel(), "f5hip::", op, ": request ", i, " reads samples [", rq.io[i], ", ",
+                    rq.io[i] + rq.ml[i], ") of a tensor of ", t.numel());
+        s.rel[i] = rq.ml[i] ? (t.data_ptr<int16_t>() - s.base()) + rq.io[i] : 0;   // (an empty tensor has no address to speak of)
+    }
+    return s;
+}
+
+// A Tensor[] argument the library reads through a pointer table: every `what` a contiguous 1-D fp32 tensor on the first one's device (views
+// of a packed buffer as they are).  The length rules are the caller's
+struct PointerTable {
+    std::vector<const float*> ptrs;
+    std::vector<int32_t> lens;
+};
+PointerTable pointer_table(const char* op, at::TensorList tensors, const char* what) {
+    PointerTable tb{std::vector<const float*>(tensors.size()), std::vector<int32_t>(tensors.size())};
+    for (size_t i = 0; i < tensors.size(); i++) {
+        const at::Tensor& t = tensors[i];
+        check_dev_f32(t, what);
+        TORCH_CHECK(t.dim() == 1 && t.numel() <= INT32_MAX && t.device() == tensors[0].device(), "f5hip::", op, ": ", what, " ", i,
+                    " must be a 1-D tensor on the first ", what, "'s device");
+        tb.ptrs[i] = t.data_ptr<float>(); tb.lens[i] = (int32_t)t.numel();
+    }
+    return tb;
+}
+
+// The arguments of the ragged vocoder operators: mel [n, channels, T_max] fp32 device, frames [n] int32 host with min_frames <= frames[i] <= T_max.
+// Returns sum(frames)
+int64_t check_ragged_frames(const char* op, const at::Tensor& mel, const at::Tensor& frames, int64_t channels, int64_t min_frames) {
+    check_dev_f32(mel, "mel"); check_host(frames, at::kInt, "frames");
+    TORCH_CHECK(mel.dim() == 3 && mel.size(1) == channels, "f5hip::", op, ": mel [n, ", channels, ", T_max]");
+    TORCH_CHECK(frames.dim() == 1 && frames.numel() == mel.size(0) && frames.numel() > 0, "f5hip::", op, ": frames.numel() == mel.size(0)");
+    const int32_t* f = frames.data_ptr<int32_t>();
+    int64_t sum = 0;
+    for (int64_t i = 0; i < frames.numel(); i++) {
+        TORCH_CHECK(f[i] >= min_frames && f[i] <= mel.size(2), "f5hip::", op, ": frames[", i, "] = ", f[i], " outside [", min_frames, ", mel.size(2) = ", mel.size(2), "]");
+        sum += f[i];
+    }
+    return sum;
+}
 
 // The ODE loop of CFM.sample over packed rows: dur [b] int32 host (rows laid out per item), kv_len [b] int32 host or None (valid frames per item:
 // the reference's padded-batch semantics), cond [sum(dur), mel] fp32 device, cond_mask [sum(dur)] uint8 host, text [b, nt] int32 host (-1 padded),
@@ -50,7 +137,7 @@ void check_host(const at::Tensor& t, at::ScalarType ty, const char* name) {
 struct SampleArgs {
     const at::Tensor &dur, &cond, &cond_mask, &text, &y0;
     const c10::optional<at::Tensor>& kv_len;
-    const int32_t* kv() const { return kv_len.has_value() ? kv_len->data_ptr<int32_t>() : nullptr; }
+    const int32_t* kv() const { return opt_ptr<int32_t>(kv_len); }
 };
 
 // The checks the sampler operators share; `op` names the operator in the messages
@@ -151,7 +238,7 @@ at::Tensor cfm_sample_methods(int64_t handle, const at::Tensor& dur, const c10::
     check_per_unit("cfm_sample_methods", method, at::kInt, "method", a);
     if (last.has_value()) check_per_unit("cfm_sample_methods", *last, at::kByte, "last", a);
     return run_sample("f5hip_cfm_sample_methods", f5hip_cfm_sample_methods, handle, a, steps.data_ptr<int32_t>(), t_grids.data_ptr<float>(),
-                      cfg_strength.data_ptr<float>(), method.data_ptr<int32_t>(), last.has_value() ? last->data_ptr<uint8_t>() : (const uint8_t*)nullptr);
+                      cfg_strength.data_ptr<float>(), method.data_ptr<int32_t>(), opt_ptr<uint8_t>(last));
 }
 
 at::Tensor vocos_decode(int64_t handle, const at::Tensor& mel, int64_t hop_length) {
@@ -166,18 +253,11 @@ at::Tensor vocos_decode(int64_t handle, const at::Tensor& mel, int64_t hop_lengt
 // mel [n, channels, T_max] fp32 device, frames [n] int32 host (item i valid for t < frames[i], each >= 2) -> packed wave
 // [hop_length * sum(frames[i] - 1)], item i at hop_length * sum_{j<i} (frames[j] - 1)
 at::Tensor vocos_decode_ragged(int64_t handle, const at::Tensor& mel, const at::Tensor& frames, int64_t channels, int64_t hop_length) {
-    check_dev_f32(mel, "mel"); check_host(frames, at::kInt, "frames");
-    TORCH_CHECK(mel.dim() == 3 && mel.size(1) == channels, "f5hip::vocos_decode_ragged: mel [n, ", channels, ", T_max]");
-    TORCH_CHECK(frames.dim() == 1 && frames.numel() == mel.size(0) && frames.numel() > 0, "f5hip::vocos_decode_ragged: frames.numel() == mel.size(0)");
-    const int32_t* f = frames.data_ptr<int32_t>();
-    int64_t total = 0;
-    for (int64_t i = 0; i < frames.numel(); i++) {
-        TORCH_CHECK(f[i] >= 2 && f[i] <= mel.size(2), "f5hip::vocos_decode_ragged: frames[", i, "] = ", f[i], " outside [2, mel.size(2) = ", mel.size(2), "]");
-        total += hop_length * (f[i] - 1);
-    }
+    const int64_t total = hop_length * (check_ragged_frames("vocos_decode_ragged", mel, frames, channels, 2) - frames.numel());
     const c10::DeviceGuard guard(mel.device());   // allocation and stream on the mel's device
     at::Tensor wave = at::empty({total}, mel.options());
-    const int rc = f5hip_vocos_decode_ragged((f5hip_vocos*)handle, (int32_t)frames.numel(), f, mel.data_ptr<float>(), wave.data_ptr<float>(), stream_of(mel));
+    const int rc = f5hip_vocos_decode_ragged((f5hip_vocos*)handle, (int32_t)frames.numel(), frames.data_ptr<int32_t>(), mel.data_ptr<float>(),
+                                             wave.data_ptr<float>(), stream_of(mel));
     TORCH_CHECK(rc == 0, "f5hip_vocos_decode_ragged: ", f5hip_last_error());
     return wave;
 }
@@ -194,16 +274,9 @@ at::Tensor bigvgan_forward(int64_t handle, const at::Tensor& mel, int64_t total_
 // mel [n, channels, T_max] fp32 device, frames [n] int32 host (item i valid for t < frames[i], each >= 1) -> packed wave
 // [total_upsample * sum(frames[i])], item i at total_upsample * sum_{j<i} frames[j]
 at::Tensor bigvgan_forward_ragged(int64_t handle, const at::Tensor& mel, const at::Tensor& frames, int64_t channels, int64_t total_upsample) {
-    check_dev_f32(mel, "mel"); check_host(frames, at::kInt, "frames");
-    TORCH_CHECK(mel.dim() == 3 && mel.size(1) == channels, "f5hip::bigvgan_forward_ragged: mel [n, ", channels, ", T_max]");
-    TORCH_CHECK(frames.dim() == 1 && frames.numel() == mel.size(0) && frames.numel() > 0, "f5hip::bigvgan_forward_ragged: frames.numel() == mel.size(0)");
+    const int64_t total = total_upsample * check_ragged_frames("bigvgan_forward_ragged", mel, frames, channels, 1);
     const int32_t* f = frames.data_ptr<int32_t>();
-    int64_t total = 0, t_max = 0;
-    for (int64_t i = 0; i < frames.numel(); i++) {
-        TORCH_CHECK(f[i] >= 1 && f[i] <= mel.size(2), "f5hip::bigvgan_forward_ragged: frames[", i, "] = ", f[i], " outside [1, mel.size(2) = ", mel.size(2), "]");
-        total += total_upsample * f[i];
-        t_max = std::max<int64_t>(t_max, f[i]);
-    }
+    const int64_t t_max = *std::max_element(f, f + frames.numel());
     TORCH_CHECK(t_max == mel.size(2), "f5hip::bigvgan_forward_ragged: mel.size(2) = ", mel.size(2), " must be the longest item's frames (", t_max, ")");
     const c10::DeviceGuard guard(mel.device());   // allocation and stream on the mel's device
     at::Tensor wave = at::empty({total}, mel.options());
@@ -265,30 +338,26 @@ static std::tuple<at::Tensor, at::Tensor> wave_finish_impl(at::TensorList chunks
         total_chunks += kp[i];
     }
     TORCH_CHECK((int64_t)chunks.size() == total_chunks, "f5hip::wave_finish: chunks needs sum(chunks_per_request) = ", total_chunks, " tensors (got ", chunks.size(), ")");
-    std::vector<const float*> ptrs(total_chunks);
-    std::vector<int32_t> lens(total_chunks);
+    const PointerTable tb = pointer_table("wave_finish", chunks, "chunk");
     int64_t total_out = 0, c = 0;
     for (int64_t i = 0; i < n; i++) {
         int64_t joined = 0;
         for (int32_t j = 0; j < kp[i]; j++, c++) {
-            const at::Tensor& w = chunks[c];
-            check_dev_f32(w, "chunk");
-            TORCH_CHECK(w.dim() == 1 && w.numel() >= 1 && w.numel() <= INT32_MAX && w.device() == chunks[0].device(),
-                        "f5hip::wave_finish: chunk ", j, " of request ", i, " must be a non-empty 1-D tensor on the first chunk's device");
-            TORCH_CHECK(chunk_fade || kp[i] == 1 || fade == 0 || w.numel() >= 2 * fade, "f5hip::wave_finish: chunk ", j, " of request ", i, " has ", w.numel(),
+            const int64_t len = tb.lens[c];
+            TORCH_CHECK(len >= 1, "f5hip::wave_finish: chunk ", j, " of request ", i, " is empty");
+            TORCH_CHECK(chunk_fade || kp[i] == 1 || fade == 0 || len >= 2 * fade, "f5hip::wave_finish: chunk ", j, " of request ", i, " has ", len,
                         " samples, fewer than 2 x fade = ", 2 * fade, ": its fades would overlap");
             const int64_t fin = j > 0 && (!chunk_fade || chunk_fade[c]) ? fade : 0, fout = j + 1 < kp[i] && (!chunk_fade || chunk_fade[c + 1]) ? fade : 0;
-            TORCH_CHECK(w.numel() >= fin + fout, "f5hip::wave_finish: chunk ", j, " of request ", i, " has ", w.numel(), " samples, fewer than its fades (", fin,
+            TORCH_CHECK(len >= fin + fout, "f5hip::wave_finish: chunk ", j, " of request ", i, " has ", len, " samples, fewer than its fades (", fin,
                         " in, ", fout, " out): they would overlap");
-            ptrs[c] = w.data_ptr<float>(); lens[c] = (int32_t)w.numel();
-            joined += w.numel() - fin;
+            joined += len - fin;
         }
         total_out += (joined + 7) & ~(int64_t)7;
         TORCH_CHECK(total_out <= INT32_MAX, "f5hip::wave_finish: the outputs of the call exceed 2^31 - 1 samples");
     }
     const c10::DeviceGuard guard(chunks[0].device());   // allocations and stream on the chunks' device
     at::Tensor pcm = at::empty({total_out}, chunks[0].options().dtype(at::kShort)), lengths = at::empty({n}, chunks[0].options().dtype(at::kInt));
-    const int rc = f5hip_wave_finish_joins((int32_t)n, kp, ptrs.data(), lens.data(), (int32_t)fade, chunk_fade, remove_silence.data_ptr<uint8_t>(),
+    const int rc = f5hip_wave_finish_joins((int32_t)n, kp, tb.ptrs.data(), tb.lens.data(), (int32_t)fade, chunk_fade, remove_silence.data_ptr<uint8_t>(),
                                            (int32_t)sample_rate, pcm.data_ptr<int16_t>(), lengths.data_ptr<int32_t>(), stream_of(chunks[0]));
     TORCH_CHECK(rc == 0, "f5hip_wave_finish: ", f5hip_last_error());
     return {pcm, lengths};
@@ -316,22 +385,18 @@ at::Tensor mel_spectrogram_ragged(at::TensorList waves, int64_t n_fft, int64_t h
     TORCH_CHECK(variant == 0 || variant == 1, "f5hip::mel_spectrogram_ragged: unknown variant ", variant, " (0 vocos, 1 bigvgan)");
     TORCH_CHECK(n_fft == 1024 && hop_length >= 1 && hop_length <= n_fft && n_mels >= 1 && n_mels <= 256, "f5hip::mel_spectrogram_ragged: only n_fft = 1024, 1 <= hop_length <= n_fft, 1 <= n_mels <= 256");
     const int64_t pad = (n_fft - hop_length) / 2;
-    std::vector<const float*> ptrs(n);
-    std::vector<int32_t> lens(n);
+    const PointerTable tb = pointer_table("mel_spectrogram_ragged", waves, "clip");
     int64_t rows = 0;
     for (int64_t i = 0; i < n; i++) {
-        const at::Tensor& w = waves[i];
-        check_dev_f32(w, "wave");
-        TORCH_CHECK(w.dim() == 1 && w.numel() <= INT32_MAX && w.device() == waves[0].device(), "f5hip::mel_spectrogram_ragged: clip ", i, " must be a 1-D tensor on the first clip's device");
-        TORCH_CHECK(variant ? w.numel() >= n_fft : w.numel() > n_fft / 2, "f5hip::mel_spectrogram_ragged: clip ", i, " has ", w.numel(), " samples (needs ",
+        const int64_t len = tb.lens[i];
+        TORCH_CHECK(variant ? len >= n_fft : len > n_fft / 2, "f5hip::mel_spectrogram_ragged: clip ", i, " has ", len, " samples (needs ",
                     variant ? ">= " : "> ", variant ? n_fft : n_fft / 2, ")");
-        ptrs[i] = w.data_ptr<float>(); lens[i] = (int32_t)w.numel();
-        rows += variant ? (w.numel() + 2 * pad - n_fft) / hop_length + 1 : 1 + w.numel() / hop_length;
+        rows += variant ? (len + 2 * pad - n_fft) / hop_length + 1 : 1 + len / hop_length;
     }
     TORCH_CHECK(rows * n_mels <= INT32_MAX, "f5hip::mel_spectrogram_ragged: the output exceeds 2^31 - 1 values");
     const c10::DeviceGuard guard(waves[0].device());
     at::Tensor mel = at::empty({rows, n_mels}, waves[0].options());
-    const int rc = f5hip_mel_spectrogram_ragged((int32_t)n, lens.data(), ptrs.data(), mel.data_ptr<float>(), (int32_t)n_fft, (int32_t)hop_length, (int32_t)n_mels,
+    const int rc = f5hip_mel_spectrogram_ragged((int32_t)n, tb.lens.data(), tb.ptrs.data(), mel.data_ptr<float>(), (int32_t)n_fft, (int32_t)hop_length, (int32_t)n_mels,
                                                 (int32_t)sample_rate, (int32_t)variant, stream_of(waves[0]));
     TORCH_CHECK(rc == 0, "f5hip_mel_spectrogram_ragged: ", f5hip_last_error());
     return mel;
@@ -343,10 +408,9 @@ at::Tensor mel_spectrogram_ragged(at::TensorList waves, int64_t n_fft, int64_t h
 std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_encode(at::TensorList pcm, const at::Tensor& in_off, const at::Tensor& max_len,
                                                            const c10::optional<at::Tensor>& len_dev, int64_t new_freq, int64_t encoding,
                                                            const c10::optional<at::Tensor>& taps) {
-    check_host(in_off, at::kLong, "in_off"); check_host(max_len, at::kInt, "max_len");
-    const int64_t n = max_len.numel();
-    TORCH_CHECK(max_len.dim() == 1 && n > 0 && in_off.numel() == n, "f5hip::wave_encode: in_off and max_len need one value per request");
-    TORCH_CHECK((int64_t)pcm.size() == 1 || (int64_t)pcm.size() == n, "f5hip::wave_encode: pcm is one tensor or one per request (got ", pcm.size(), " for ", n, ")");
+    const PcmRequests rq = check_pcm_requests("wave_encode", pcm, in_off, max_len, len_dev, true);
+    const int64_t n = rq.n;
+    const int32_t* ml = rq.ml;
     TORCH_CHECK(encoding >= 0 && encoding <= 2, "f5hip::wave_encode: unknown encoding ", encoding, " (0 pcm16, 1 mu-law, 2 A-law)");
     TORCH_CHECK(new_freq >= 1 && new_freq <= INT32_MAX, "f5hip::wave_encode: the sample rate must be positive (got ", new_freq, ")");
     const RatePair rp = rate_pair(24000, (int)new_freq);
@@ -357,41 +421,24 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_encode(at::TensorList pcm, c
         TORCH_CHECK(taps->dim() == 2 && taps->size(0) == nf && taps->size(1) == rp.L, "f5hip::wave_encode: taps must be [nf = ", nf,
                     "][2 * width + of = ", rp.L, "] (rate_pair.h: torchaudio's defaults); got ", taps->sizes());
     }
-    for (const at::Tensor& t : pcm)
-        TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kShort && t.is_contiguous() && t.dim() == 1 && t.device() == pcm[0].device(),
-                    "f5hip::wave_encode: pcm must be contiguous 1-D int16 tensors on one HIP device");
-    if (len_dev.has_value())
-        TORCH_CHECK(len_dev->is_cuda() && len_dev->scalar_type() == at::kInt && len_dev->is_contiguous() && len_dev->numel() == n &&
-                    len_dev->device() == pcm[0].device(), "f5hip::wave_encode: len_dev must be a contiguous int32 tensor with one value per request on the pcm's device");
-    const int64_t* io = in_off.data_ptr<int64_t>();
-    const int32_t* ml = max_len.data_ptr<int32_t>();
+    const PcmSources src = pcm_sources("wave_encode", pcm, rq);
     const int64_t bps = encoding == 0 ? 2 : 1;
-    at::Tensor anchor;                               // offsets are relative to the first tensor that has an address
-    for (const at::Tensor& t : pcm)
-        if (t.numel() && !anchor.defined()) anchor = t;
-    if (!anchor.defined()) anchor = at::zeros({8}, pcm[0].options());
-    const int16_t* base = anchor.data_ptr<int16_t>();
-    std::vector<int64_t> rel(n);
     at::Tensor out_off = at::empty({n}, at::TensorOptions().dtype(at::kLong));
     int64_t* oo = out_off.data_ptr<int64_t>();
     int64_t total_in = 0, total_out = 0, bytes = 0;
     for (int64_t i = 0; i < n; i++) {
-        const at::Tensor& t = pcm[pcm.size() == 1 ? 0 : i];
-        TORCH_CHECK(ml[i] >= 0 && io[i] >= 0 && io[i] + ml[i] <= t.numel(), "f5hip::wave_encode: request ", i, " reads samples [", io[i], ", ", io[i] + ml[i],
-                    ") of a tensor of ", t.numel());
-        rel[i] = ml[i] ? (t.data_ptr<int16_t>() - base) + io[i] : 0;   // (an empty tensor has no address to speak of)
         const int64_t n_out = (nf * ml[i] + of - 1) / of;
         total_in += ml[i]; total_out += n_out;
         TORCH_CHECK(total_in <= INT32_MAX && total_out <= INT32_MAX, "f5hip::wave_encode: the call exceeds 2^31 - 1 samples in or out");
         oo[i] = bytes;
         bytes += (n_out * bps + 15) & ~(int64_t)15;
     }
-    const c10::DeviceGuard guard(pcm[0].device());   // allocations and stream on the pcm's device
+    const c10::DeviceGuard guard(rq.device);   // allocations and stream on the pcm's device
     // (a call of empty requests still has an address to give)
     at::Tensor out = at::empty({std::max<int64_t>(bytes, 16)}, pcm[0].options().dtype(at::kByte)).narrow(0, 0, bytes), out_len = at::empty({n}, pcm[0].options().dtype(at::kInt));
-    const int rc = f5hip_wave_encode((int32_t)n, base, rel.data(), ml, len_dev.has_value() ? len_dev->data_ptr<int32_t>() : (const int32_t*)nullptr,
-                                     (int32_t)new_freq, (int32_t)encoding, new_freq != 24000 ? taps->data_ptr<float>() : (const float*)nullptr,
-                                     out.data_ptr<uint8_t>(), oo, out_len.data_ptr<int32_t>(), stream_of(pcm[0]));
+    const int rc = f5hip_wave_encode((int32_t)n, src.base(), src.rel.data(), ml, rq.len_dev, (int32_t)new_freq, (int32_t)encoding,
+                                     new_freq != 24000 ? taps->data_ptr<float>() : (const float*)nullptr, out.data_ptr<uint8_t>(), oo,
+                                     out_len.data_ptr<int32_t>(), stream_of(pcm[0]));
     TORCH_CHECK(rc == 0, "f5hip_wave_encode: ", f5hip_last_error());
     return {out, out_len, out_off};
 }
@@ -402,48 +449,29 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_encode(at::TensorList pcm, c
 static std::tuple<at::Tensor, at::Tensor, at::Tensor> wave_flac_impl(at::TensorList pcm, const at::Tensor& in_off, const at::Tensor& max_len,
                                                                      const c10::optional<at::Tensor>& len_dev, int64_t sample_rate,
                                                                      const at::Tensor* level) {
-    check_host(in_off, at::kLong, "in_off"); check_host(max_len, at::kInt, "max_len");
-    const int64_t n = max_len.numel();
+    const PcmRequests rq = check_pcm_requests("wave_flac", pcm, in_off, max_len, len_dev, true);
+    const int64_t n = rq.n;
+    const int32_t* ml = rq.ml;
     if (level) {
         check_host(*level, at::kInt, "level");
         TORCH_CHECK(level->dim() == 1 && level->numel() == n, "f5hip::wave_flac_levels: level needs one value per request");
     }
-    TORCH_CHECK(max_len.dim() == 1 && n > 0 && in_off.numel() == n, "f5hip::wave_flac: in_off and max_len need one value per request");
-    TORCH_CHECK((int64_t)pcm.size() == 1 || (int64_t)pcm.size() == n, "f5hip::wave_flac: pcm is one tensor or one per request (got ", pcm.size(), " for ", n, ")");
     TORCH_CHECK(sample_rate >= 1 && sample_rate <= INT32_MAX, "f5hip::wave_flac: the sample rate must be positive (got ", sample_rate, ")");
-    for (const at::Tensor& t : pcm)
-        TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kShort && t.is_contiguous() && t.dim() == 1 && t.device() == pcm[0].device(),
-                    "f5hip::wave_flac: pcm must be contiguous 1-D int16 tensors on one HIP device");
-    if (len_dev.has_value())
-        TORCH_CHECK(len_dev->is_cuda() && len_dev->scalar_type() == at::kInt && len_dev->is_contiguous() && len_dev->numel() == n &&
-                    len_dev->device() == pcm[0].device(), "f5hip::wave_flac: len_dev must be a contiguous int32 tensor with one value per request on the pcm's device");
-    const int64_t* io = in_off.data_ptr<int64_t>();
-    const int32_t* ml = max_len.data_ptr<int32_t>();
-    at::Tensor anchor;                               // offsets are relative to the first tensor that has an address
-    for (const at::Tensor& t : pcm)
-        if (t.numel() && !anchor.defined()) anchor = t;
-    if (!anchor.defined()) anchor = at::zeros({8}, pcm[0].options());
-    const int16_t* base = anchor.data_ptr<int16_t>();
-    std::vector<int64_t> rel(n);
+    const PcmSources src = pcm_sources("wave_flac", pcm, rq);
     at::Tensor out_off = at::empty({n}, at::TensorOptions().dtype(at::kLong));
     int64_t* oo = out_off.data_ptr<int64_t>();
     int64_t total_in = 0, bytes = 0;
     for (int64_t i = 0; i < n; i++) {
-        const at::Tensor& t = pcm[pcm.size() == 1 ? 0 : i];
-        TORCH_CHECK(ml[i] >= 0 && io[i] >= 0 && io[i] + ml[i] <= t.numel(), "f5hip::wave_flac: request ", i, " reads samples [", io[i], ", ", io[i] + ml[i],
-                    ") of a tensor of ", t.numel());
-        rel[i] = ml[i] ? (t.data_ptr<int16_t>() - base) + io[i] : 0;   // (an empty tensor has no address to speak of)
         total_in += ml[i];
         oo[i] = bytes;
         bytes += (f5hip_wave_flac_bound(ml[i]) + 15) & ~(int64_t)15;
         TORCH_CHECK(total_in <= INT32_MAX && bytes <= INT32_MAX, "f5hip::wave_flac: the call exceeds 2^31 - 1 samples in or bytes out");
     }
-    const c10::DeviceGuard guard(pcm[0].device());   // allocations and stream on the pcm's device
+    const c10::DeviceGuard guard(rq.device);   // allocations and stream on the pcm's device
     at::Tensor out = at::empty({bytes}, pcm[0].options().dtype(at::kByte)), out_len = at::empty({n}, pcm[0].options().dtype(at::kInt));
-    const int32_t* ld = len_dev.has_value() ? len_dev->data_ptr<int32_t>() : (const int32_t*)nullptr;
-    const int rc = level ? f5hip_wave_flac_levels((int32_t)n, base, rel.data(), ml, ld, (int32_t)sample_rate, level->data_ptr<int32_t>(),
+    const int rc = level ? f5hip_wave_flac_levels((int32_t)n, src.base(), src.rel.data(), ml, rq.len_dev, (int32_t)sample_rate, level->data_ptr<int32_t>(),
                                                   out.data_ptr<uint8_t>(), oo, out_len.data_ptr<int32_t>(), stream_of(pcm[0]))
-                         : f5hip_wave_flac((int32_t)n, base, rel.data(), ml, ld, (int32_t)sample_rate, out.data_ptr<uint8_t>(), oo,
+                         : f5hip_wave_flac((int32_t)n, src.base(), src.rel.data(), ml, rq.len_dev, (int32_t)sample_rate, out.data_ptr<uint8_t>(), oo,
                                            out_len.data_ptr<int32_t>(), stream_of(pcm[0]));
     TORCH_CHECK(rc == 0, level ? "f5hip_wave_flac_levels: " : "f5hip_wave_flac: ", f5hip_last_error());
     return {out, out_len, out_off};
@@ -529,33 +557,24 @@ std::tuple<at::Tensor, at::Tensor> ref_prestep(const at::Tensor& frames, const a
 // of g (zeros for a request that was left alone)
 at::Tensor wave_loudness(at::Tensor pcm, const at::Tensor& in_off, const at::Tensor& max_len, const c10::optional<at::Tensor>& len_dev,
                          const at::Tensor& gain_k) {
-    check_host(in_off, at::kLong, "in_off"); check_host(max_len, at::kInt, "max_len"); check_host(gain_k, at::kDouble, "gain_k");
-    const int64_t n = max_len.numel();
-    TORCH_CHECK(max_len.dim() == 1 && n > 0 && in_off.numel() == n && gain_k.numel() == n,
-                "f5hip::wave_loudness: in_off, max_len and gain_k need one value per request");
-    TORCH_CHECK(pcm.is_cuda() && pcm.scalar_type() == at::kShort && pcm.is_contiguous() && pcm.dim() == 1,
-                "f5hip::wave_loudness: pcm must be a contiguous 1-D int16 tensor on a HIP device");
-    if (len_dev.has_value())
-        TORCH_CHECK(len_dev->is_cuda() && len_dev->scalar_type() == at::kInt && len_dev->is_contiguous() && len_dev->numel() == n &&
-                    len_dev->device() == pcm.device(), "f5hip::wave_loudness: len_dev must be a contiguous int32 tensor with one value per request on the pcm's device");
-    const int64_t* io = in_off.data_ptr<int64_t>();
-    const int32_t* ml = max_len.data_ptr<int32_t>();
+    const PcmRequests rq = check_pcm_requests("wave_loudness", pcm, in_off, max_len, len_dev, false);
+    const int64_t n = rq.n;
+    check_host(gain_k, at::kDouble, "gain_k");
+    TORCH_CHECK(gain_k.numel() == n, "f5hip::wave_loudness: gain_k needs one value per request");
+    const PcmSources src = pcm_sources("wave_loudness", pcm, rq);
     const double* gk = gain_k.data_ptr<double>();
     int64_t total = 0;
     bool any = false;
     for (int64_t i = 0; i < n; i++) {
-        TORCH_CHECK(ml[i] >= 0 && io[i] >= 0 && io[i] + ml[i] <= pcm.numel(), "f5hip::wave_loudness: request ", i, " covers samples [", io[i], ", ",
-                    io[i] + ml[i], ") of a tensor of ", pcm.numel());
         TORCH_CHECK(std::isfinite(gk[i]), "f5hip::wave_loudness: the gain constant of request ", i, " is not finite");
-        total += ml[i];
+        total += rq.ml[i];
         TORCH_CHECK(total <= INT32_MAX, "f5hip::wave_loudness: the call exceeds 2^31 - 1 samples");
         any = any || gk[i] > 0.0;
     }
-    const c10::DeviceGuard guard(pcm.device());
+    const c10::DeviceGuard guard(rq.device);
     at::Tensor stats = at::zeros({n, 4}, pcm.options().dtype(at::kLong));
     if (!any || pcm.numel() == 0) return stats;      // nothing to launch (an empty tensor has no address to give)
-    const int rc = f5hip_wave_loudness((int32_t)n, pcm.data_ptr<int16_t>(), io, ml, len_dev.has_value() ? len_dev->data_ptr<int32_t>() : (const int32_t*)nullptr,
-                                       gk, stats.data_ptr<int64_t>(), stream_of(pcm));
+    const int rc = f5hip_wave_loudness((int32_t)n, src.base(), src.rel.data(), rq.ml, rq.len_dev, gk, stats.data_ptr<int64_t>(), stream_of(pcm));
     TORCH_CHECK(rc == 0, "f5hip_wave_loudness: ", f5hip_last_error());
     return stats;
 }
@@ -568,18 +587,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody(const at
                                                                         const c10::optional<at::Tensor>& len_dev, const at::Tensor& stretch_p,
                                                                         const at::Tensor& stretch_q, const at::Tensor& pitch,
                                                                         const c10::optional<at::Tensor>& taps) {
-    check_host(in_off, at::kLong, "in_off"); check_host(max_len, at::kInt, "max_len"); check_host(stretch_p, at::kInt, "stretch_p");
-    check_host(stretch_q, at::kInt, "stretch_q"); check_host(pitch, at::kInt, "pitch");
-    const int64_t n = max_len.numel();
-    TORCH_CHECK(max_len.dim() == 1 && n > 0 && in_off.numel() == n && stretch_p.numel() == n && stretch_q.numel() == n && pitch.numel() == n,
-                "f5hip::wave_prosody: in_off, max_len, stretch_p, stretch_q and pitch need one value per request");
-    TORCH_CHECK(pcm.is_cuda() && pcm.scalar_type() == at::kShort && pcm.is_contiguous() && pcm.dim() == 1,
-                "f5hip::wave_prosody: pcm must be a contiguous 1-D int16 tensor on a HIP device");
-    if (len_dev.has_value())
-        TORCH_CHECK(len_dev->is_cuda() && len_dev->scalar_type() == at::kInt && len_dev->is_contiguous() && len_dev->numel() == n &&
-                    len_dev->device() == pcm.device(), "f5hip::wave_prosody: len_dev must be a contiguous int32 tensor with one value per request on the pcm's device");
-    const int64_t* io = in_off.data_ptr<int64_t>();
-    const int32_t* ml = max_len.data_ptr<int32_t>();
+    const PcmRequests rq = check_pcm_requests("wave_prosody", pcm, in_off, max_len, len_dev, false);
+    const int64_t n = rq.n;
+    const int32_t* ml = rq.ml;
+    check_host(stretch_p, at::kInt, "stretch_p"); check_host(stretch_q, at::kInt, "stretch_q"); check_host(pitch, at::kInt, "pitch");
+    TORCH_CHECK(stretch_p.numel() == n && stretch_q.numel() == n && pitch.numel() == n,
+                "f5hip::wave_prosody: stretch_p, stretch_q and pitch need one value per request");
+    const PcmSources src = pcm_sources("wave_prosody", pcm, rq);
     const int32_t* sp = stretch_p.data_ptr<int32_t>();
     const int32_t* sq = stretch_q.data_ptr<int32_t>();
     const int32_t* pt = pitch.data_ptr<int32_t>();
@@ -589,8 +603,6 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody(const at
     int64_t total_in = 0, total = 0;
     bool pitched = false;
     for (int64_t i = 0; i < n; i++) {
-        TORCH_CHECK(ml[i] >= 0 && io[i] >= 0 && io[i] + ml[i] <= pcm.numel(), "f5hip::wave_prosody: request ", i, " reads samples [", io[i], ", ",
-                    io[i] + ml[i], ") of a tensor of ", pcm.numel());
         TORCH_CHECK(pr_stretch_ok(sp[i], sq[i]), "f5hip::wave_prosody: request ", i, " stretches by ", sp[i], "/", sq[i],
                     ": positive terms up to 2^20 and a ratio from 1/2 to 2");
         TORCH_CHECK(pt[i] >= -kPrPitchMax && pt[i] <= kPrPitchMax, "f5hip::wave_prosody: request ", i, " has a pitch of ", pt[i], " semitones (-6 to 6)");
@@ -611,13 +623,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody(const at
         TORCH_CHECK(taps.has_value() && taps->is_cuda() && taps->scalar_type() == at::kFloat && taps->is_contiguous() && taps->device() == pcm.device() &&
                     taps->numel() == f5hip_wave_prosody_tap_offset(0),
                     "f5hip::wave_prosody: a pitch needs taps, the contiguous fp32 table of ", f5hip_wave_prosody_tap_offset(0), " floats on the pcm's device");
-    const c10::DeviceGuard guard(pcm.device());
+    const c10::DeviceGuard guard(rq.device);
     at::Tensor out = at::empty({std::max<int64_t>(total, 8)}, pcm.options()).slice(0, 0, total);   // (a call of empty requests still has an address to give)
     at::Tensor out_len = at::empty({n}, pcm.options().dtype(at::kInt));
-    at::Tensor anchor = pcm.numel() ? pcm : at::zeros({8}, pcm.options());
-    const int rc = f5hip_wave_prosody((int32_t)n, anchor.data_ptr<int16_t>(), io, ml, len_dev.has_value() ? len_dev->data_ptr<int32_t>() : (const int32_t*)nullptr,
-                                      sp, sq, pt, pitched ? taps->data_ptr<float>() : (const float*)nullptr, out.data_ptr<int16_t>(), oo,
-                                      out_len.data_ptr<int32_t>(), stream_of(pcm));
+    const int rc = f5hip_wave_prosody((int32_t)n, src.base(), src.rel.data(), ml, rq.len_dev, sp, sq, pt, pitched ? taps->data_ptr<float>() : (const float*)nullptr,
+                                      out.data_ptr<int16_t>(), oo, out_len.data_ptr<int32_t>(), stream_of(pcm));
     TORCH_CHECK(rc == 0, "f5hip_wave_prosody: ", f5hip_last_error());
     return {out, out_len, out_off, bounds};
 }

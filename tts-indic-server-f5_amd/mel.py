@@ -5,9 +5,8 @@ import ctypes as C
 
 import torch
 
-import numpy as np
-
 from . import _lib, torch_ops
+from .ops import call_op, pointer_table
 
 
 def _out(b, n_mels, frames, device):
@@ -71,23 +70,16 @@ def mel_spectrogram_ragged(waves, variant="vocos", n_fft=1024, hop_length=256, n
     waves = list(waves)
     if not waves:
         raise _lib.F5HipError("mel_spectrogram_ragged: no clips")
-    for w in waves:
-        if not (torch.is_tensor(w) and w.dtype == torch.float32 and w.is_cuda and w.dim() == 1 and w.is_contiguous() and w.device == waves[0].device):
-            raise _lib.F5HipError("mel_spectrogram_ragged: every clip must be a contiguous 1-D fp32 tensor on one HIP device (no CPU fallback)")
+    ptrs, lens = pointer_table("mel_spectrogram_ragged", waves, "clip")
     code = MEL_VARIANTS.index(variant)
     short = n_fft if code else n_fft // 2 + 1
-    for i, w in enumerate(waves):
-        if w.numel() < short:
-            raise _lib.F5HipError(f"mel_spectrogram_ragged: clip {i} has {w.numel()} samples (the {variant} front-end needs at least {short})")
-    frames = [mel_frames(int(w.numel()), variant, n_fft, hop_length) if hop_length > 0 else 0 for w in waves]
-    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
-        try:
-            mel = torch_ops.ops().mel_spectrogram_ragged(waves, n_fft, hop_length, n_mel_channels, target_sample_rate, code)
-        except RuntimeError as e:   # c10::Error from the operator's checks or the library
-            raise _lib.F5HipError(str(e)) from e
+    for i, n in enumerate(lens.tolist()):
+        if n < short:
+            raise _lib.F5HipError(f"mel_spectrogram_ragged: clip {i} has {n} samples (the {variant} front-end needs at least {short})")
+    frames = [mel_frames(n, variant, n_fft, hop_length) if hop_length > 0 else 0 for n in lens.tolist()]
+    if torch_ops.load():
+        mel = call_op("mel_spectrogram_ragged", waves, n_fft, hop_length, n_mel_channels, target_sample_rate, code)
     else:
-        ptrs = np.array([w.data_ptr() for w in waves], dtype=np.uint64)
-        lens = np.array([w.numel() for w in waves], dtype=np.int32)
         with torch.cuda.device(waves[0].device):
             mel = torch.empty(max(sum(frames), 0), max(n_mel_channels, 0), device=waves[0].device, dtype=torch.float32)
             _lib.check(_lib.lib().f5hip_mel_spectrogram_ragged(len(waves), C.c_void_p(lens.ctypes.data), C.c_void_p(ptrs.ctypes.data), C.c_void_p(mel.data_ptr()),

@@ -1,5 +1,11 @@
-"""Python face of the per-kernel unit ops of the C ABI (include/f5hip.h): one production HIP kernel each, fp32 torch
-tensors on the HIP device in and out.  Used by the per-kernel parity tests and the timing tools; not on the hot path."""
+"""Python face of the operations of the C ABI (include/f5hip.h) on torch tensors on the HIP device.  Two families:
+  - the per-kernel unit ops (`gemm` .. `time_table`): one production HIP kernel each, fp32 in and out, called through ctypes.  Used by the
+    per-kernel parity tests and the timing tools; not on the hot path.
+  - the device audio path that every request takes (`ref_frontend`, `ref_prestep`, `wave_finish` .. `wave_loudness`, `flac_decode`): one
+    library call per batch.  Each is bound twice over the same C entry point: as a TORCH_LIBRARY operator (csrc/torch_ops.cpp), taken when
+    `torch_ops.load()`, and through ctypes otherwise; both return the same bits.  The steps the wrappers share -- the operator call, the
+    per-request host arrays, the PCM request table, its sources, the pointer table and the packing of the outputs -- are the helpers in
+    front of them, and csrc/torch_ops.cpp holds the same helpers in C++."""
 from __future__ import annotations
 
 import ctypes as C
@@ -336,30 +342,106 @@ def time_table(model, t):
     return sinus, mod, temb
 
 
+# ------------------------------------------------------------------------------------------------ the steps the audio operations share
+def call_op(name, *args):
+    """The TORCH_LIBRARY operator `name` over the same C entry point as the ctypes call next to it; a c10::Error from the operator's checks
+    or the library is an F5HipError, as the ctypes path raises."""
+    try:
+        return getattr(torch_ops.ops(), name)(*args)
+    except RuntimeError as e:
+        raise _lib.F5HipError(str(e)) from e
+
+
+def _per_request(op, what, values, dtype, n=None, per="request"):
+    """Contiguous host array of `dtype` with one value per request: `n` of them, or (None: the array that sets the count) at least one."""
+    a = np.ascontiguousarray(np.asarray(values, dtype=dtype))
+    if a.ndim < 1 or len(a) < 1 or (n is not None and len(a) != n):
+        raise _lib.F5HipError(f"{op}: {what} needs one value per {per} ({'at least one' if n is None else n}), got {a.shape}")
+    return a
+
+
+def _check_dev_f32(op, t, name):
+    if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda):
+        raise _lib.F5HipError(f"{op}: {name} must be a contiguous fp32 tensor on the HIP device")
+
+
+def pointer_table(op, tensors, what):
+    """A `Tensor[]` argument the library reads through a pointer table: every one a contiguous 1-D fp32 tensor on the first one's device.
+    Returns (pointers uint64, lengths int32) as the ctypes path passes them; the length rules are the caller's."""
+    for i, t in enumerate(tensors):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.device == tensors[0].device):
+            raise _lib.F5HipError(f"{op}: {what} {i} must be a contiguous 1-D fp32 tensor on one HIP device (no CPU fallback)")
+    return np.array([t.data_ptr() for t in tensors], dtype=np.uint64), np.array([t.numel() for t in tensors], dtype=np.int32)
+
+
+def _pcm_requests(op, pcm, in_off, max_len, len_dev, several=False):
+    """The request table (pcm, in_off, max_len, len_dev) of the wave operations: one offset and one length bound per request; `pcm` one
+    contiguous 1-D int16 device tensor or, where the operation allows `several`, one per request on one device; `len_dev` None or int32 on
+    that device with one value per request.  Returns (tensors, in_off int64, max_len int32, n, len_dev contiguous)."""
+    tensors = list(pcm) if several and not torch.is_tensor(pcm) else [pcm]
+    ml = _per_request(op, "max_len", max_len, np.int32)
+    n = len(ml)
+    io = _per_request(op, "in_off", in_off, np.int64, n)
+    if len(tensors) not in (1, n):
+        raise _lib.F5HipError(f"{op}: pcm is one tensor or one per request (got {len(tensors)} for {n})")
+    for t in tensors:
+        if not (torch.is_tensor(t) and t.dtype == torch.int16 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.device == tensors[0].device):
+            raise _lib.F5HipError(f"{op}: pcm must be contiguous 1-D int16 tensors on one HIP device")
+    if len_dev is not None:
+        if not (torch.is_tensor(len_dev) and len_dev.dtype == torch.int32 and len_dev.is_cuda and len_dev.numel() == n and len_dev.device == tensors[0].device):
+            raise _lib.F5HipError(f"{op}: len_dev must be an int32 tensor with one value per request on the pcm's device")
+        len_dev = len_dev.contiguous()
+    return tensors, io, ml, n, len_dev
+
+
+def _pcm_sources(op, tensors, io, ml):
+    """Where the ctypes path reads a request table from: request i reads samples [in_off[i], in_off[i] + max_len[i]) of its tensor (the one
+    tensor, or tensor i), which must hold them.  Returns (anchor, rel): the first tensor that has an address -- the library's `pcm` -- and
+    every request's first sample relative to it."""
+    anchor = next((t for t in tensors if t.numel()), None)
+    if anchor is None:
+        anchor = torch.zeros(8, device=tensors[0].device, dtype=torch.int16)
+    base, rel = anchor.data_ptr(), np.zeros(len(ml), dtype=np.int64)
+    for i in range(len(ml)):
+        t = tensors[0 if len(tensors) == 1 else i]
+        if ml[i] < 0 or io[i] < 0 or int(io[i]) + int(ml[i]) > t.numel():
+            raise _lib.F5HipError(f"{op}: request {i} reads samples [{io[i]}, {int(io[i]) + int(ml[i])}) of a tensor of {t.numel()}")
+        rel[i] = (t.data_ptr() - base) // 2 + int(io[i]) if ml[i] else 0   # (an empty tensor has no address to speak of)
+    return anchor, rel
+
+
+def _pack(sizes, align):
+    """Outputs packed in request order, each at a multiple of `align`: (offsets, total)."""
+    offsets, total = [], 0
+    for s in sizes:
+        offsets.append(total)
+        total += (int(s) + align - 1) & -align
+    return offsets, total
+
+
+# ------------------------------------------------------------------------------------------------ the audio operations
 def ref_frontend(wave, n_in, channels, orig_freq, new_freq, taps=None, rms_floor=0.1):
     """The reference-audio front-end of several clips of one sample-rate pair in ONE library call (include/f5hip.h f5hip_ref_frontend): mono
     mix, rms, gain up to `rms_floor`, polyphase sinc resampling.  wave: fp32 device tensor, the clips packed back to back, clip i as
     channels[i] planes of n_in[i] samples; taps: fp32 device [nf, 2 width + of] (`infer.resample_taps`), not needed when the rates are
     equal.  Returns (out packed fp32 device, rms [n] fp32 device -- measured before the gain --, [n_out_i]); clip i's part of `out` and its
     rms equal its own call's, bit for bit."""
-    ni = np.ascontiguousarray(np.asarray(n_in, dtype=np.int32))
-    ch = np.ascontiguousarray(np.asarray(channels, dtype=np.int32))
-    assert wave.dtype == torch.float32 and wave.is_contiguous() and wave.is_cuda
-    assert taps is None or (taps.dtype == torch.float32 and taps.is_contiguous() and taps.is_cuda)
+    ni = _per_request("ref_frontend", "n_in", n_in, np.int32, per="clip")
+    ch = _per_request("ref_frontend", "channels", channels, np.int32, len(ni), per="clip")
+    _check_dev_f32("ref_frontend", wave, "wave")
+    if taps is not None:
+        _check_dev_f32("ref_frontend", taps, "taps")
     of, nf, _, L = rate_pair(orig_freq, new_freq)
     n_out = [(nf * int(v) + of - 1) // of for v in ni]
     if of != nf:   # the library derives the row length itself (csrc/rate_pair.h): refuse a table of another shape
         if taps is None or tuple(taps.shape) != (nf, L):
             raise _lib.F5HipError(f"ref_frontend: taps must be [{nf}, {L}] for {orig_freq} -> {new_freq} Hz "
                                   f"(got {None if taps is None else tuple(taps.shape)})")
-    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
-        try:
-            out, rms = torch_ops.ops().ref_frontend(wave, torch.from_numpy(ni), torch.from_numpy(ch), int(orig_freq), int(new_freq), taps, float(rms_floor))
-        except RuntimeError as e:   # c10::Error from the operator's checks or the library
-            raise _lib.F5HipError(str(e)) from e
+    if torch_ops.load():
+        out, rms = call_op("ref_frontend", wave, torch.from_numpy(ni), torch.from_numpy(ch), int(orig_freq), int(new_freq), taps, float(rms_floor))
     else:
-        if len(ni) < 1 or len(ch) != len(ni) or int((ni.astype(np.int64) * ch).sum()) != wave.numel():
-            raise _lib.F5HipError("ref_frontend: wave needs sum(n_in * channels) samples, one (n_in, channels) pair per clip")
+        if int((ni.astype(np.int64) * ch).sum()) != wave.numel():
+            raise _lib.F5HipError("ref_frontend: wave needs sum(n_in * channels) samples")
         with torch.cuda.device(wave.device):
             out = torch.empty(max(sum(n_out), 0), device=wave.device, dtype=torch.float32)
             rms = torch.empty(len(ni), device=wave.device, dtype=torch.float32)
@@ -376,11 +458,9 @@ def ref_prestep(frames, n_in, channels, rate, clip_short=True, device=None):
     one per clip.  Returns (packed fp32 device tensor: clip i as channels[i] planes of lengths[i] samples, x / 32768, packed by those lengths
     -- `ref_frontend`'s `wave` as it stands --, lengths [n], flags [n]: whether any output sample of the clip is non-zero).  One download:
     the [n, 2] lengths and flags; the samples stay on the device."""
-    ni = np.ascontiguousarray(np.asarray(n_in, dtype=np.int32).reshape(-1))
-    ch = np.ascontiguousarray(np.asarray(channels, dtype=np.int32).reshape(-1))
+    ni = _per_request("ref_prestep", "n_in", np.asarray(n_in).reshape(-1), np.int32, per="clip")
+    ch = _per_request("ref_prestep", "channels", np.asarray(channels).reshape(-1), np.int32, len(ni), per="clip")
     cs = np.ascontiguousarray(np.broadcast_to(np.asarray(clip_short, dtype=bool), ni.shape).astype(np.uint8))
-    if len(ni) < 1 or len(ch) != len(ni):
-        raise _lib.F5HipError("ref_prestep: at least one clip, and one (n_in, channels) pair per clip")
     if int(rate) < 11025:
         raise _lib.F5HipError(f"ref_prestep: reference audio below 11025 Hz is not supported on this path (got {rate})")
     if (ni < 0).any() or (ch < 1).any():
@@ -398,11 +478,8 @@ def ref_prestep(frames, n_in, channels, rate, clip_short=True, device=None):
         raise _lib.F5HipError("ref_prestep: frames must be a contiguous 1-D int16 tensor on the device")
     if frames.numel() != total:
         raise _lib.F5HipError(f"ref_prestep: the frames need sum(n_in * channels) = {total} samples (got {frames.numel()})")
-    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
-        try:
-            out, info = torch_ops.ops().ref_prestep(frames, torch.from_numpy(ni), torch.from_numpy(ch), torch.from_numpy(cs), int(rate))
-        except RuntimeError as e:   # c10::Error from the operator's checks or the library
-            raise _lib.F5HipError(str(e)) from e
+    if torch_ops.load():
+        out, info = call_op("ref_prestep", frames, torch.from_numpy(ni), torch.from_numpy(ch), torch.from_numpy(cs), int(rate))
     else:
         bound = int(_lib.lib().f5hip_ref_prestep_bound(len(ni), _p(ni), _p(ch), int(rate)))
         if bound < 0 or bound > 2 ** 31 - 1:
@@ -447,40 +524,35 @@ def wave_finish_joins(chunks, chunks_per_request, fade, chunk_fade, remove_silen
     if its successor does)."""
     chunks = list(chunks)
     if chunk_fade is not None:
-        chunk_fade = np.ascontiguousarray(np.asarray(chunk_fade, dtype=bool).astype(np.uint8))
-        if chunk_fade.ndim != 1 or len(chunk_fade) != len(chunks):
-            raise _lib.F5HipError(f"wave_finish_joins: chunk_fade needs one value per chunk ({len(chunks)}), got {chunk_fade.shape}")
+        chunk_fade = _per_request("wave_finish_joins", "chunk_fade", np.asarray(chunk_fade, dtype=bool), np.uint8, len(chunks), per="chunk")
     return _wave_finish(chunks, chunks_per_request, fade, chunk_fade, remove_silence, sample_rate)
 
 
 def _wave_finish(chunks, chunks_per_request, fade, chunk_fade, remove_silence, sample_rate):
-    k = np.ascontiguousarray(np.asarray(chunks_per_request, dtype=np.int32))
-    flags = np.zeros(len(k), dtype=np.uint8) if remove_silence is None else np.ascontiguousarray(np.asarray(remove_silence, dtype=bool).astype(np.uint8))
+    k = _per_request("wave_finish", "chunks_per_request", chunks_per_request, np.int32)
+    flags = np.zeros(len(k), dtype=np.uint8) if remove_silence is None else _per_request("wave_finish", "remove_silence",
+                                                                                         np.asarray(remove_silence, dtype=bool), np.uint8, len(k))
     chunks = list(chunks)
-    if len(k) < 1 or len(flags) != len(k) or (k < 1).any() or int(k.sum()) != len(chunks):
-        raise _lib.F5HipError("wave_finish: one chunk count (>= 1) and one flag per request, sum(chunks_per_request) chunk waves")
-    for w in chunks:
-        if not (torch.is_tensor(w) and w.dtype == torch.float32 and w.is_cuda and w.dim() == 1 and w.is_contiguous() and w.numel() >= 1):
-            raise _lib.F5HipError("wave_finish: every chunk must be a non-empty contiguous 1-D fp32 device tensor")
+    if (k < 1).any() or int(k.sum()) != len(chunks):
+        raise _lib.F5HipError("wave_finish: a chunk count of 1 or more per request, sum(chunks_per_request) chunk waves")
+    ptrs, lens = pointer_table("wave_finish", chunks, "chunk")
+    samples = lens.tolist()
+    if min(samples) < 1:
+        raise _lib.F5HipError("wave_finish: every chunk must be a non-empty tensor")
     fade = int(fade)
-    offsets, off, c = [], 0, 0
-    for kk in k:
-        fading = int(kk) - 1 if chunk_fade is None else int(np.count_nonzero(chunk_fade[c + 1:c + kk]))
-        offsets.append(off)
-        off += (sum(int(w.numel()) for w in chunks[c:c + kk]) - fading * max(fade, 0) + 7) & ~7
-        c += int(kk)
-    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
-        try:
-            if chunk_fade is None:
-                pcm, lengths = torch_ops.ops().wave_finish(chunks, torch.from_numpy(k), fade, torch.from_numpy(flags), int(sample_rate))
-            else:
-                pcm, lengths = torch_ops.ops().wave_finish_joins(chunks, torch.from_numpy(k), fade, torch.from_numpy(chunk_fade), torch.from_numpy(flags),
-                                                                 int(sample_rate))
-        except RuntimeError as e:   # c10::Error from the operator's checks or the library
-            raise _lib.F5HipError(str(e)) from e
+    joined, c = [], 0
+    for kk in k.tolist():
+        fading = kk - 1 if chunk_fade is None else int(np.count_nonzero(chunk_fade[c + 1:c + kk]))
+        joined.append(sum(samples[c:c + kk]) - fading * max(fade, 0))
+        c += kk
+    offsets, off = _pack(joined, 8)
+    if torch_ops.load():
+        if chunk_fade is None:
+            pcm, lengths = call_op("wave_finish", chunks, torch.from_numpy(k), fade, torch.from_numpy(flags), int(sample_rate))
+        else:
+            pcm, lengths = call_op("wave_finish_joins", chunks, torch.from_numpy(k), fade, torch.from_numpy(chunk_fade), torch.from_numpy(flags),
+                                   int(sample_rate))
     else:
-        ptrs = np.array([w.data_ptr() for w in chunks], dtype=np.uint64)
-        lens = np.array([w.numel() for w in chunks], dtype=np.int32)
         dev = chunks[0].device
         with torch.cuda.device(dev):
             pcm = torch.empty(max(off, 0), device=dev, dtype=torch.int16)
@@ -507,22 +579,11 @@ def wave_encode(pcm, in_off, max_len, len_dev, sample_rate, encoding, taps=None)
     needed at 24 000.  Returns (data uint8 device, out_len int32 device [n], offsets): request i's result is
     data[offsets[i] : offsets[i] + out_len[i] * bytes_per_sample] -- little-endian int16 samples, or one code byte per sample --, bit for bit
     `infer.deliver_pcm16` of its PCM."""
-    tensors = [pcm] if torch.is_tensor(pcm) else list(pcm)
-    io = np.ascontiguousarray(np.asarray(in_off, dtype=np.int64))
-    ml = np.ascontiguousarray(np.asarray(max_len, dtype=np.int32))
-    n = len(ml)
+    tensors, io, ml, n, len_dev = _pcm_requests("wave_encode", pcm, in_off, max_len, len_dev, several=True)
     code = WAVE_ENCODINGS.index(encoding) if encoding in WAVE_ENCODINGS else encoding
     if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or not 0 <= int(code) <= 2:
         raise _lib.F5HipError(f"wave_encode: unknown encoding {encoding!r} (one of {list(WAVE_ENCODINGS)} or its code)")
     code, rate = int(code), int(sample_rate)
-    if n < 1 or len(io) != n or len(tensors) not in (1, n):
-        raise _lib.F5HipError("wave_encode: one offset and one length bound per request; pcm is one tensor or one per request")
-    for t in tensors:
-        if not (torch.is_tensor(t) and t.dtype == torch.int16 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.device == tensors[0].device):
-            raise _lib.F5HipError("wave_encode: pcm must be contiguous 1-D int16 tensors on one device")
-    if len_dev is not None and not (torch.is_tensor(len_dev) and len_dev.dtype == torch.int32 and len_dev.is_cuda and len_dev.numel() == n
-                                    and len_dev.device == tensors[0].device):
-        raise _lib.F5HipError("wave_encode: len_dev must be an int32 tensor with one value per request on the pcm's device")
     if rate < 1:
         raise _lib.F5HipError(f"wave_encode: the sample rate must be positive (got {sample_rate})")
     of, nf, _, L = rate_pair(24000, rate)
@@ -530,34 +591,19 @@ def wave_encode(pcm, in_off, max_len, len_dev, sample_rate, encoding, taps=None)
         if taps is None or not (taps.dtype == torch.float32 and taps.is_contiguous() and taps.is_cuda) or tuple(taps.shape) != (nf, L):
             raise _lib.F5HipError(f"wave_encode: taps must be a contiguous fp32 device tensor [{nf}, {L}] for 24000 -> {rate} Hz "
                                   f"(got {None if taps is None else tuple(taps.shape)})")
-    if len_dev is not None:
-        len_dev = len_dev.contiguous()
-    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
-        try:
-            data, out_len, out_off = torch_ops.ops().wave_encode(tensors, torch.from_numpy(io), torch.from_numpy(ml), len_dev, rate, code, taps)
-        except RuntimeError as e:   # c10::Error from the operator's checks or the library
-            raise _lib.F5HipError(str(e)) from e
+    if torch_ops.load():
+        data, out_len, out_off = call_op("wave_encode", tensors, torch.from_numpy(io), torch.from_numpy(ml), len_dev, rate, code, taps)
         return data, out_len, out_off.tolist()
-    bps = 2 if code == 0 else 1
-    anchor = next((t for t in tensors if t.numel()), None)   # offsets are relative to the first tensor that has an address
-    if anchor is None:
-        anchor = torch.zeros(8, device=tensors[0].device, dtype=torch.int16)
-    base = anchor.data_ptr()
-    rel, out_off, nbytes = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), 0
-    for i in range(n):
-        t = tensors[0 if len(tensors) == 1 else i]
-        if ml[i] < 0 or io[i] < 0 or int(io[i]) + int(ml[i]) > t.numel():
-            raise _lib.F5HipError(f"wave_encode: request {i} reads samples [{io[i]}, {int(io[i]) + int(ml[i])}) of a tensor of {t.numel()}")
-        rel[i] = (t.data_ptr() - base) // 2 + int(io[i]) if ml[i] else 0   # (an empty tensor has no address to speak of)
-        out_off[i] = nbytes
-        nbytes += (((nf * int(ml[i]) + of - 1) // of) * bps + 15) & ~15
+    anchor, rel = _pcm_sources("wave_encode", tensors, io, ml)
+    out_off, nbytes = _pack([((nf * int(m) + of - 1) // of) * (2 if code == 0 else 1) for m in ml], 16)
+    oo = np.asarray(out_off, dtype=np.int64)
     dev = tensors[0].device
     with torch.cuda.device(dev):
         data = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)[:nbytes]   # (a call of empty requests still has an address to give)
         out_len = torch.empty(n, device=dev, dtype=torch.int32)
-        _lib.check(_lib.lib().f5hip_wave_encode(n, C.c_void_p(base), _p(rel), _p(ml), _p(len_dev), rate, code, _p(taps) if rate != 24000 else None, _p(data),
-                                                _p(out_off), _p(out_len), _lib.current_stream_ptr()), "f5hip_wave_encode")
-    return data, out_len, out_off.tolist()
+        _lib.check(_lib.lib().f5hip_wave_encode(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), rate, code, _p(taps) if rate != 24000 else None, _p(data),
+                                                _p(oo), _p(out_len), _lib.current_stream_ptr()), "f5hip_wave_encode")
+    return data, out_len, out_off
 
 
 def wave_flac(pcm, in_off, max_len, len_dev, sample_rate, level=None):
@@ -568,59 +614,33 @@ def wave_flac(pcm, in_off, max_len, len_dev, sample_rate, level=None):
     data[offsets[i] : offsets[i] + out_len[i]], byte for byte `infer.encode_flac` of its samples.  `level`: None (level 0, the entry point
     f5hip_wave_flac), or the FLAC level (`wave_codec.check_flac_level`) of every request as one int or one int per request
     (f5hip_wave_flac_levels: LPC subframes for the requests at level 1, the same three launches)."""
-    tensors = [pcm] if torch.is_tensor(pcm) else list(pcm)
-    io = np.ascontiguousarray(np.asarray(in_off, dtype=np.int64))
-    ml = np.ascontiguousarray(np.asarray(max_len, dtype=np.int32))
-    n, rate = len(ml), int(sample_rate)
-    if n < 1 or len(io) != n or len(tensors) not in (1, n):
-        raise _lib.F5HipError("wave_flac: one offset and one length bound per request; pcm is one tensor or one per request")
-    lv = None
+    tensors, io, ml, n, len_dev = _pcm_requests("wave_flac", pcm, in_off, max_len, len_dev, several=True)
+    rate, lv = int(sample_rate), None
     if level is not None:
         given = [level] * n if isinstance(level, (int, np.integer)) else list(level)
         if len(given) != n or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in (0, 1) for v in given):
             raise _lib.F5HipError(f"wave_flac: level is 0 or 1, one int or one per request (got {level!r} for {n} requests)")
-        lv = np.ascontiguousarray(np.asarray(given, dtype=np.int32))
-    for t in tensors:
-        if not (torch.is_tensor(t) and t.dtype == torch.int16 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.device == tensors[0].device):
-            raise _lib.F5HipError("wave_flac: pcm must be contiguous 1-D int16 tensors on one device")
-    if len_dev is not None and not (torch.is_tensor(len_dev) and len_dev.dtype == torch.int32 and len_dev.is_cuda and len_dev.numel() == n
-                                    and len_dev.device == tensors[0].device):
-        raise _lib.F5HipError("wave_flac: len_dev must be an int32 tensor with one value per request on the pcm's device")
-    if len_dev is not None:
-        len_dev = len_dev.contiguous()
-    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
-        try:
-            if lv is None:
-                data, out_len, out_off = torch_ops.ops().wave_flac(tensors, torch.from_numpy(io), torch.from_numpy(ml), len_dev, rate)
-            else:
-                data, out_len, out_off = torch_ops.ops().wave_flac_levels(tensors, torch.from_numpy(io), torch.from_numpy(ml), len_dev, rate,
-                                                                          torch.from_numpy(lv))
-        except RuntimeError as e:   # c10::Error from the operator's checks or the library
-            raise _lib.F5HipError(str(e)) from e
+        lv = _per_request("wave_flac", "level", given, np.int32, n)
+    if torch_ops.load():
+        if lv is None:
+            data, out_len, out_off = call_op("wave_flac", tensors, torch.from_numpy(io), torch.from_numpy(ml), len_dev, rate)
+        else:
+            data, out_len, out_off = call_op("wave_flac_levels", tensors, torch.from_numpy(io), torch.from_numpy(ml), len_dev, rate, torch.from_numpy(lv))
         return data, out_len, out_off.tolist()
-    anchor = next((t for t in tensors if t.numel()), None)   # offsets are relative to the first tensor that has an address
-    if anchor is None:
-        anchor = torch.zeros(8, device=tensors[0].device, dtype=torch.int16)
-    base = anchor.data_ptr()
-    rel, out_off, nbytes = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), 0
-    for i in range(n):
-        t = tensors[0 if len(tensors) == 1 else i]
-        if ml[i] < 0 or io[i] < 0 or int(io[i]) + int(ml[i]) > t.numel():
-            raise _lib.F5HipError(f"wave_flac: request {i} reads samples [{io[i]}, {int(io[i]) + int(ml[i])}) of a tensor of {t.numel()}")
-        rel[i] = (t.data_ptr() - base) // 2 + int(io[i]) if ml[i] else 0   # (an empty tensor has no address to speak of)
-        out_off[i] = nbytes
-        nbytes += (int(_lib.lib().f5hip_wave_flac_bound(int(ml[i]))) + 15) & ~15
+    anchor, rel = _pcm_sources("wave_flac", tensors, io, ml)
+    out_off, nbytes = _pack([_lib.lib().f5hip_wave_flac_bound(int(m)) for m in ml], 16)
+    oo = np.asarray(out_off, dtype=np.int64)
     dev = tensors[0].device
     with torch.cuda.device(dev):
         data = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         out_len = torch.empty(n, device=dev, dtype=torch.int32)
         if lv is None:
-            _lib.check(_lib.lib().f5hip_wave_flac(n, C.c_void_p(base), _p(rel), _p(ml), _p(len_dev), rate, _p(data), _p(out_off), _p(out_len),
+            _lib.check(_lib.lib().f5hip_wave_flac(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), rate, _p(data), _p(oo), _p(out_len),
                                                   _lib.current_stream_ptr()), "f5hip_wave_flac")
         else:
-            _lib.check(_lib.lib().f5hip_wave_flac_levels(n, C.c_void_p(base), _p(rel), _p(ml), _p(len_dev), rate, _p(lv), _p(data), _p(out_off),
+            _lib.check(_lib.lib().f5hip_wave_flac_levels(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), rate, _p(lv), _p(data), _p(oo),
                                                          _p(out_len), _lib.current_stream_ptr()), "f5hip_wave_flac_levels")
-    return data, out_len, out_off.tolist()
+    return data, out_len, out_off
 
 
 _prosody_taps: dict = {}   # device -> the twelve pitch tables there, uploaded once
@@ -651,49 +671,30 @@ def wave_prosody(pcm, in_off, max_len, len_dev, stretches, pitches):
     `pitches` [n]: semitones, 0 for none.  A neutral request is copied through.  Returns (pcm2 int16 device, lengths2 int32 device [n],
     offsets2, bounds2): request i's samples are pcm2[offsets2[i] : offsets2[i] + lengths2[i]], and bounds2[i] is the length that max_len[i]
     gives -- what `wave_loudness`, `wave_encode` and `wave_flac` take in the place of `wave_finish`'s buffer, offsets, bounds and lengths."""
-    io = np.ascontiguousarray(np.asarray(in_off, dtype=np.int64))
-    ml = np.ascontiguousarray(np.asarray(max_len, dtype=np.int32))
-    n = len(ml)
-    st = np.asarray([tuple(s) for s in stretches], dtype=np.int64).reshape(-1, 2) if len(stretches) else np.zeros((0, 2), dtype=np.int64)
+    (pcm,), io, ml, n, len_dev = _pcm_requests("wave_prosody", pcm, in_off, max_len, len_dev)
     if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in pitches):
         raise _lib.F5HipError(f"wave_prosody: a pitch is a whole number of semitones (got {list(pitches)!r})")
-    pt = np.ascontiguousarray(np.asarray(pitches, dtype=np.int64))
-    if n < 1 or len(io) != n or len(st) != n or len(pt) != n:
-        raise _lib.F5HipError("wave_prosody: one offset, one length bound, one stretch (P, Q) and one pitch per request")
-    if not (torch.is_tensor(pcm) and pcm.dtype == torch.int16 and pcm.is_cuda and pcm.dim() == 1 and pcm.is_contiguous()):
-        raise _lib.F5HipError("wave_prosody: pcm must be a contiguous 1-D int16 device tensor")
-    if len_dev is not None and not (torch.is_tensor(len_dev) and len_dev.dtype == torch.int32 and len_dev.is_cuda and len_dev.numel() == n
-                                    and len_dev.device == pcm.device):
-        raise _lib.F5HipError("wave_prosody: len_dev must be an int32 tensor with one value per request on the pcm's device")
-    if (np.abs(st) > 1 << 20).any() or (st < 1).any() or (st[:, 0] > 2 * st[:, 1]).any() or (st[:, 1] > 2 * st[:, 0]).any():
+    pt = _per_request("wave_prosody", "pitches", pitches, np.int64, n)
+    st = _per_request("wave_prosody", "stretches", [tuple(s) for s in stretches], np.int64, n)
+    if st.shape != (n, 2) or (np.abs(st) > 1 << 20).any() or (st < 1).any() or (st[:, 0] > 2 * st[:, 1]).any() or (st[:, 1] > 2 * st[:, 0]).any():
         raise _lib.F5HipError(f"wave_prosody: a stretch is a pair of positive terms up to 2^20 with a ratio from 1/2 to 2 (got {st.tolist()})")
     if (np.abs(pt) > 6).any():
         raise _lib.F5HipError(f"wave_prosody: a pitch is -6 to 6 semitones (got {pt.tolist()})")
     sp, sq, pt = (np.ascontiguousarray(a.astype(np.int32)) for a in (st[:, 0], st[:, 1], pt))
     taps = wave_prosody_taps(pcm.device) if pt.any() else None
-    if len_dev is not None:
-        len_dev = len_dev.contiguous()
-    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
-        try:
-            pcm2, lengths2, offsets2, bounds2 = torch_ops.ops().wave_prosody(pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(sp),
-                                                                             torch.from_numpy(sq), torch.from_numpy(pt), taps)
-        except RuntimeError as e:   # c10::Error from the operator's checks or the library
-            raise _lib.F5HipError(str(e)) from e
+    if torch_ops.load():
+        pcm2, lengths2, offsets2, bounds2 = call_op("wave_prosody", pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(sp),
+                                                    torch.from_numpy(sq), torch.from_numpy(pt), taps)
         return pcm2, lengths2, offsets2.tolist(), bounds2.tolist()
     from . import wave_codec
-    offsets2, bounds2, total = [], [], 0
-    for i in range(n):
-        if ml[i] < 0 or io[i] < 0 or int(io[i]) + int(ml[i]) > pcm.numel():
-            raise _lib.F5HipError(f"wave_prosody: request {i} reads samples [{io[i]}, {int(io[i]) + int(ml[i])}) of a tensor of {pcm.numel()}")
-        bounds2.append(wave_codec.shifted_length(int(ml[i]), (int(sp[i]), int(sq[i])), int(pt[i])))
-        offsets2.append(total)
-        total += (bounds2[-1] + 7) & ~7
-    oo = np.ascontiguousarray(np.asarray(offsets2, dtype=np.int64))
+    anchor, rel = _pcm_sources("wave_prosody", [pcm], io, ml)
+    bounds2 = [wave_codec.shifted_length(int(m), (int(p), int(q)), int(s)) for m, p, q, s in zip(ml, sp, sq, pt)]
+    offsets2, total = _pack(bounds2, 8)
+    oo = np.asarray(offsets2, dtype=np.int64)
     with torch.cuda.device(pcm.device):
         pcm2 = torch.empty(max(total, 8), device=pcm.device, dtype=torch.int16)[:total]   # (a call of empty requests still has an address to give)
         lengths2 = torch.empty(n, device=pcm.device, dtype=torch.int32)
-        anchor = pcm if pcm.numel() else torch.zeros(8, device=pcm.device, dtype=torch.int16)
-        _lib.check(_lib.lib().f5hip_wave_prosody(n, _p(anchor), _p(io), _p(ml), _p(len_dev), _p(sp), _p(sq), _p(pt), _p(taps), _p(pcm2), _p(oo), _p(lengths2),
+        _lib.check(_lib.lib().f5hip_wave_prosody(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(sp), _p(sq), _p(pt), _p(taps), _p(pcm2), _p(oo), _p(lengths2),
                                                  _lib.current_stream_ptr()), "f5hip_wave_prosody")
     return pcm2, lengths2, offsets2, bounds2
 
@@ -711,33 +712,17 @@ def wave_loudness(pcm, in_off, max_len, len_dev, gain_k):
     stats, int64 device [n, 4]: n2, S2, peak and the bits of the gain g of each flagged request (zeros for the others) --
     `wave_codec.measure_loudness` and `loudness_gain` of its samples, and afterwards its samples are `normalise_loudness_pcm16`'s, bit for
     bit."""
-    io = np.ascontiguousarray(np.asarray(in_off, dtype=np.int64))
-    ml = np.ascontiguousarray(np.asarray(max_len, dtype=np.int32))
-    gk = np.ascontiguousarray(np.asarray([0.0 if k is None else k for k in gain_k], dtype=np.float64))
-    n = len(ml)
-    if n < 1 or len(io) != n or len(gk) != n:
-        raise _lib.F5HipError("wave_loudness: one offset, one length bound and one gain constant per request")
-    if not (torch.is_tensor(pcm) and pcm.dtype == torch.int16 and pcm.is_cuda and pcm.dim() == 1 and pcm.is_contiguous()):
-        raise _lib.F5HipError("wave_loudness: pcm must be a contiguous 1-D int16 device tensor")
-    if len_dev is not None and not (torch.is_tensor(len_dev) and len_dev.dtype == torch.int32 and len_dev.is_cuda and len_dev.numel() == n
-                                    and len_dev.device == pcm.device):
-        raise _lib.F5HipError("wave_loudness: len_dev must be an int32 tensor with one value per request on the pcm's device")
+    (pcm,), io, ml, n, len_dev = _pcm_requests("wave_loudness", pcm, in_off, max_len, len_dev)
+    gk = _per_request("wave_loudness", "gain_k", [0.0 if k is None else k for k in gain_k], np.float64, n)
     if not np.isfinite(gk).all():
         raise _lib.F5HipError("wave_loudness: a gain constant is not finite")
-    if len_dev is not None:
-        len_dev = len_dev.contiguous()
-    if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
-        try:
-            return torch_ops.ops().wave_loudness(pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(gk))
-        except RuntimeError as e:   # c10::Error from the operator's checks or the library
-            raise _lib.F5HipError(str(e)) from e
-    for i in range(n):
-        if ml[i] < 0 or io[i] < 0 or int(io[i]) + int(ml[i]) > pcm.numel():
-            raise _lib.F5HipError(f"wave_loudness: request {i} covers samples [{io[i]}, {int(io[i]) + int(ml[i])}) of a tensor of {pcm.numel()}")
+    if torch_ops.load():
+        return call_op("wave_loudness", pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(gk))
+    anchor, rel = _pcm_sources("wave_loudness", [pcm], io, ml)
     with torch.cuda.device(pcm.device):
         stats = torch.zeros(n, 4, device=pcm.device, dtype=torch.int64)
         if (gk > 0).any() and pcm.numel():
-            _lib.check(_lib.lib().f5hip_wave_loudness(n, _p(pcm), _p(io), _p(ml), _p(len_dev), _p(gk), _p(stats), _lib.current_stream_ptr()),
+            _lib.check(_lib.lib().f5hip_wave_loudness(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(gk), _p(stats), _lib.current_stream_ptr()),
                        "f5hip_wave_loudness")
     return stats
 
@@ -771,12 +756,9 @@ def flac_decode_packed(buffer, spans, device=None):
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         with torch.cuda.device(dev):
             data = torch.from_numpy(buf.copy()).to(dev)
-            if torch_ops.load():   # TORCH_LIBRARY operator over the same C entry point
-                try:
-                    out, out_off = torch_ops.ops().flac_decode(data, torch.from_numpy(begin), torch.from_numpy(end), torch.from_numpy(info),
-                                                               torch.from_numpy(total), torch.from_numpy(most))
-                except RuntimeError as e:   # c10::Error from the operator's checks or the library
-                    raise _lib.F5HipError(str(e)) from e
+            if torch_ops.load():
+                out, out_off = call_op("flac_decode", data, torch.from_numpy(begin), torch.from_numpy(end), torch.from_numpy(info), torch.from_numpy(total),
+                                       torch.from_numpy(most))
                 out_off = out_off.numpy()
             else:
                 out_off, words = np.zeros(n, dtype=np.int64), 2 * n

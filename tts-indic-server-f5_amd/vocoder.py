@@ -10,6 +10,16 @@ import numpy as np
 import torch
 
 from . import _lib, torch_ops
+from .ops import call_op
+
+
+def _ragged_mel(mels, frames, channels, device):
+    """What the ragged decodes hand the library: (mel [n, channels, max(frames)] fp32 on the device, item i in its first frames[i] columns and
+    zeros behind them; frames as the int32 host tensor)."""
+    mel = torch.zeros(len(mels), channels, max(frames), device=device, dtype=torch.float32)
+    for i, m in enumerate(mels):
+        mel[i, :, :frames[i]] = m
+    return mel, torch.tensor(frames, dtype=torch.int32)
 
 
 class F5HipVocos:
@@ -65,15 +75,9 @@ class F5HipVocos:
         c = int(mels[0].shape[0])
         if any(m.dim() != 2 or m.shape[0] != c for m in mels):
             raise _lib.F5HipError("decode_ragged: every mel must be [C, T] with the same C")
-        mel = torch.zeros(len(mels), c, max(frames), device=self.device, dtype=torch.float32)
-        for i, m in enumerate(mels):
-            mel[i, :, :frames[i]] = m
-        f = torch.tensor(frames, dtype=torch.int32)
+        mel, f = _ragged_mel(mels, frames, c, self.device)
         if torch_ops.load():
-            try:
-                wave = torch_ops.ops().vocos_decode_ragged(int(self._h), mel, f, c, self.hop_length)
-            except RuntimeError as e:   # c10::Error from the operator's checks or the library
-                raise _lib.F5HipError(str(e)) from e
+            wave = call_op("vocos_decode_ragged", int(self._h), mel, f, c, self.hop_length)
         else:
             wave = torch.empty(self.hop_length * sum(t - 1 for t in frames), device=self.device, dtype=torch.float32)
             _lib.check(self._lib.f5hip_vocos_decode_ragged(self._h, len(frames), C.c_void_p(f.data_ptr()), C.c_void_p(mel.data_ptr()),
@@ -177,15 +181,9 @@ class F5HipBigVGAN:
             return []
         if any(m.dim() != 2 or m.shape[0] != self.num_mels for m in mels) or min(frames) < 1:
             raise _lib.F5HipError(f"decode_ragged: every mel must be [{self.num_mels}, T] with T >= 1")
-        mel = torch.zeros(len(mels), self.num_mels, max(frames), device=self.device, dtype=torch.float32)
-        for i, m in enumerate(mels):
-            mel[i, :, :frames[i]] = m
-        f = torch.tensor(frames, dtype=torch.int32)
+        mel, f = _ragged_mel(mels, frames, self.num_mels, self.device)
         if torch_ops.load():
-            try:
-                wave = torch_ops.ops().bigvgan_forward_ragged(int(self._h), mel, f, self.num_mels, self.total_up)
-            except RuntimeError as e:   # c10::Error from the operator's checks or the library
-                raise _lib.F5HipError(str(e)) from e
+            wave = call_op("bigvgan_forward_ragged", int(self._h), mel, f, self.num_mels, self.total_up)
         else:
             wave = torch.empty(self.total_up * sum(frames), device=self.device, dtype=torch.float32)
             _lib.check(self._lib.f5hip_bigvgan_forward_ragged(self._h, len(frames), C.c_void_p(f.data_ptr()), C.c_void_p(mel.data_ptr()),
