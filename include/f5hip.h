@@ -321,6 +321,48 @@ int f5hip_op_bigvgan_upsample(int32_t batch, int32_t P, int32_t T, int32_t c_in,
  *   LDS-tiled kernel (fails when its tile exceeds 48 KB, C > 44), 2 = the kernel without the tile. */
 int f5hip_op_bigvgan_conv_post(int32_t batch, int32_t P, int32_t T, int32_t C, const float* a_dev, const float* w_dev, int32_t variant,
                                float* wave_dev, void* stream);
+/* Ragged forms of the four ops above: the layouts of f5hip_bigvgan_forward_ragged, in which every kernel of the generator finds an item's
+ *   rows through a small table instead of a uniform pitch.  The caller describes the layout in rows of the stage the op runs at (host int32
+ *   arrays of n_items entries); the op builds and uploads the kernel's table and launches as the generator does.  A layout the kernels'
+ *   contracts exclude is refused (nothing is launched).
+ * f5hip_op_conv1d_ragged: f5hip_op_conv1d over M rows (x_dev [M][c_in], res_dev / out_dev [M][c_out]) holding n_items items: item i owns
+ *   rows [item_row0[i], + item_rows[i]), the first item_valid[i] of them valid (item_rows NULL: valid rounded up to the alignment below).
+ *   The kernels read one [start, end) per block of blk rows (blk % 128 == 0, M % blk == 0).  Rules: every item starts at, and spans, a
+ *   multiple of blk rows; no block belongs to two items or to none; 1 <= valid <= rows.  impl 5 (conv5.h) takes the bounds of a 256-row
+ *   tile from the tile's first row, so there M % 256 == 0, blk is 128 or a multiple of 256, and with blk 128 every item starts at, and
+ *   spans, a multiple of 256 rows.  ups_rate > 0: the 3-tap form of an up-sampler as in f5hip_op_bigvgan_upsample (w_host [c_in][c_out]
+ *   [2 ups_rate], out_dev [M ups_rate][c_out], res_dev NULL; k and dil are not read).  impl 0 = gemm.h, 5 = conv5.h, never a fallback. */
+int f5hip_op_conv1d_ragged(int32_t n_items, const int32_t* item_row0, const int32_t* item_rows, const int32_t* item_valid, int32_t M,
+                           int32_t blk, int32_t c_in, int32_t c_out, int32_t k, int32_t dil, int32_t ups_rate, const float* x_dev,
+                           const float* w_host, const float* bias_host, const float* res_dev, float* out_dev, int32_t prec, int32_t impl,
+                           void* stream);
+/* f5hip_op_bigvgan_snake_ragged: f5hip_op_bigvgan_snake over x_dev [M][C] with item i = rows [item_row0[i], + item_valid[i]) (grid z = item,
+ *   the grid covers the longest item).  The kernel takes int4 items in first-stage rows and `scale` = the up-sampling so far: the op stores
+ *   row0 / scale and valid / scale, so both must be multiples of scale (>= 1), and every item must lie inside the M rows.  n_items <= 65535.
+ *   out_dev / out_rows (>= M) / out_format as in the uniform op: only the valid rows of the items are written. */
+int f5hip_op_bigvgan_snake_ragged(int32_t n_items, const int32_t* item_row0, const int32_t* item_valid, int32_t scale, int32_t M, int32_t C,
+                                  const float* x_dev, const float* alpha_log_dev, const float* beta_log_dev, int32_t out_format,
+                                  float* out_dev, int64_t out_rows, void* stream);
+/* f5hip_op_bigvgan_conv_post_ragged: f5hip_op_bigvgan_conv_post over a_dev [M][C] with items as above; item i writes samples
+ *   [item_wave_off[i], + item_valid[i]) of wave_dev (wave_len samples; the op writes nothing else).  Offsets are multiples of scale too,
+ *   and every item's samples lie inside wave_len; the order of the offsets is free. */
+int f5hip_op_bigvgan_conv_post_ragged(int32_t n_items, const int32_t* item_row0, const int32_t* item_valid, const int32_t* item_wave_off,
+                                      int32_t scale, int32_t M, int32_t C, const float* a_dev, const float* w_dev, int32_t variant,
+                                      float* wave_dev, int64_t wave_len, void* stream);
+/* f5hip_op_bigvgan_mean3: the generator's mean of the three AMP blocks of a stage, (y0 + y1 + y2) / 3 (n_in 3; n_in 1: the conversion of
+ *   y0 alone), fp32 [rows][C] (C % 4 == 0).  out_f32_dev [rows][C] or NULL receives fp32 rows.  mode 0: nothing else (out_f32_dev required);
+ *   1 / 2 / 3: split-bf16 planes / one fp16 plane (saturated) / the round-to-nearest bf16 hi plane, of pitch ldo >= C (ldo % 4 == 0).
+ *   The planes are loaded from planes_dev fp32 [rows][ldo] and read back into it as fp32, so the padding channels c >= C come back as
+ *   they were, up to the format's rounding. */
+int f5hip_op_bigvgan_mean3(int64_t rows, int32_t C, int32_t n_in, const float* y0_dev, const float* y1_dev, const float* y2_dev, int32_t mode,
+                           int32_t ldo, float* out_f32_dev, float* planes_dev, void* stream);
+/* f5hip_op_bigvgan_mel_rows: the generator's first operand planes, mel -> rows of 128 channels (C = num_mels <= 128; rows past an item's
+ *   frames and channels >= C are zero).  item_row0 NULL: n uniform sequences, mel_dev [n][C][T], pitch M0 / n >= T rows.  Else the ragged
+ *   kernel: item i has item_frames[i] <= T frames from row item_row0[i] (a multiple of 128; it owns ceil128(frames) rows; every 128-row
+ *   block of the M0 rows belongs to exactly one item), mel_dev [n][C][T] with T the column stride; columns past an item's frames are not
+ *   read.  f16 0 = split bf16 (out = hi + lo), 1 = the fp16 plane (saturated).  out_dev fp32 [M0][128]. */
+int f5hip_op_bigvgan_mel_rows(int32_t n, const int32_t* item_row0, const int32_t* item_frames, int32_t T, int32_t M0, int32_t C,
+                              const float* mel_dev, int32_t f16, float* out_dev, void* stream);
 /* f5hip_op_conv_pos_embed: the backbone's ConvPositionEmbedding, x + Mish(conv2(Mish(conv1(x)))) with two nn.Conv1d(D, D, 31, padding 15,
  *   groups 16), over n_seq sequences of seq_len[s] frames (zero padding at the sequence bounds) laid out as the backbone lays them out.
  *   x_dev fp32 [frames][D] (packed, D % 128 == 0, D <= 1024), w*_host [D][D / 16][31], b*_host [D].  lead = 1: a time-token row heads every

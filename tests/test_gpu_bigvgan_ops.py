@@ -3,73 +3,25 @@
 LDS-tiled and the naive kernel), each against the float64 oracle (oracle/bigvgan_oracle.py on float64 tensors) or torch's float64
 conv_transpose1d / conv1d, at the launch-geometry edges: channel counts that change the lane layout, lengths around a segment and a tile,
 sequences without padding rows, NaN in the padding rows."""
-import ctypes as C
 import math
 
 import pytest
 import torch
 
-from oracle import bigvgan_oracle as B
+from bigvgan_ref import DEV, SENTINEL, U32  # noqa: F401
+from bigvgan_ref import check_untouched as _check_untouched
+from bigvgan_ref import counter as _counter
+from bigvgan_ref import report as _report
+from bigvgan_ref import reset_counters as _reset_counters
+from bigvgan_ref import seq_view as _seq_view
+from bigvgan_ref import snake_bound as _snake_bound
+from bigvgan_ref import snake_nseg as _nseg
+from bigvgan_ref import snake_ref as _snake_ref
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-U32 = 2.0 ** -24            # fp32 unit roundoff
-SENTINEL = -321.5           # exact in fp32, split bf16 and fp16
-DELTA_SIN = 2.0 ** -18      # allowance for the absolute error of the hardware sine (v_sin_f32 is not correctly rounded)
-
-
-def _counter(name):
-    from tts_indic_server_f5_amd import _lib
-    v = C.c_int64(0)
-    _lib.check(_lib.lib().f5hip_get_counter(name.encode(), C.byref(v)), "get_counter")
-    return v.value
-
-
-def _reset_counters():
-    from tts_indic_server_f5_amd import _lib
-    _lib.check(_lib.lib().f5hip_get_counter(b"reset", None), "reset counters")
-
-
-def _report(tag, err):
-    mx, rms = err.abs().max().item(), err.pow(2).mean().sqrt().item()
-    print(f"[parity] {tag}: max err {mx:.3e} rms err {rms:.3e}")
-    return mx, rms
-
-
-def _seq_view(x, batch, P, T):
-    """channel-last rows [batch P, C] -> the valid rows as [batch, C, T]"""
-    return x.view(batch, P, -1)[:, :T].permute(0, 2, 1)
-
 
 # ---------------------------------------------------------------------------------------------------------------- SnakeBeta activation
-def _snake_ref(x, al, be, batch, P, T, dtype=torch.float64):
-    """Activation1d of the oracle in `dtype` over the valid rows -> [batch, T, C]"""
-    y = B.activation1d(_seq_view(x, batch, P, T).to(dtype), al.to(dtype), be.to(dtype))
-    return y.permute(0, 2, 1)
-
-
-def _snake_bound(x_amp, al, be):
-    """First-order worst-case error of aa_snake2_kernel's fp32 arithmetic, from |x| <= x_amp and the parameters:
-    up-sampled u = sum of 6 taps 2 f_k x: |u| <= F1 x_amp with F1 = max over the two phases of sum |2 f_k|, error du <= 7 u32 F1 x_amp (6 fused
-    products plus the filter's own fp32 rounding).  The sine argument in revolutions u e^a / 2 pi carries the rounding of expf, of the 1 / 2 pi
-    constant, of their product and of u e^a (<= 4 u32 relative) plus du, and the hardware sine adds DELTA_SIN; d sin^2(theta) <= |d theta|, so
-    d sin^2 <= min(e^a du + 4 u32 theta_max + 2 DELTA_SIN, 1).  The snake value a = u + sin^2 / (e^b + 1e-9) then has
-    da <= du + ib (d sin^2 + 3 u32) + u32 |a|_max (ib = its reciprocal's rounding, 3 u32), and the 12-tap low-pass adds
-    F2 da + 13 u32 F2 |a|_max with F2 = sum |f_k|.  Second-order terms are covered by a factor 2."""
-    f = B.aa_filter(torch.float64)
-    F1 = max(float((2 * f[0::2]).abs().sum()), float((2 * f[1::2]).abs().sum()))
-    F2 = float(f.abs().sum())
-    a_max, ib_max = math.exp(float(al.max())), math.exp(-float(be.min()))
-    u_max = F1 * x_amp
-    du = 7 * U32 * u_max
-    theta_max = a_max * u_max
-    dsn2 = min(a_max * du + 4 * U32 * theta_max + 2 * DELTA_SIN, 1.0)
-    v_max = u_max + ib_max
-    da = du + ib_max * (dsn2 + 3 * U32) + U32 * v_max
-    return 2 * (F2 * da + 13 * U32 * F2 * v_max)
-
-
 def _run_snake(x, al, be, batch, P, T, fmt, guard=64):
     """The op into an output pre-filled with SENTINEL (guard rows past batch P included); returns (valid rows [batch, T, C], the whole buffer)"""
     from tts_indic_server_f5_amd import ops
@@ -78,25 +30,6 @@ def _run_snake(x, al, be, batch, P, T, fmt, guard=64):
     ops.bigvgan_snake(x.to(DEV), al, be, batch=batch, valid=T, out_format=fmt, out=out)
     out = out.cpu()
     return out[: batch * P].view(batch, P, Cc)[:, :T].double(), out
-
-
-def _check_untouched(out, batch, P, T):
-    """no NaN anywhere; padding rows of every sequence and the guard rows still hold the sentinel"""
-    assert not torch.isnan(out).any()
-    Cc = out.shape[1]
-    body = out[: batch * P].view(batch, P, Cc)
-    assert (body[:, T:] == SENTINEL).all(), "a padding row was written"
-    assert (out[batch * P:] == SENTINEL).all(), "the guard past the last sequence was written"
-
-
-# cw / nseg of bv_snake_launch: cw = the largest divisor of C up to 64 (96 -> 32), nseg = 256 / cw segments of 16 steps per workgroup
-def _nseg(Cc):
-    cw = min(Cc, 64)
-    while Cc % cw:
-        cw -= 1
-    if Cc == 96:
-        cw = 32
-    return 256 // cw
 
 
 SNAKE_C = [768, 96, 48, 24, 16, 4, 40]   # cw 64 / 32 (the 96 case) / 48 (nseg 5) / 24 (nseg 10, 240 of 256 lanes) / 16 / 4 (nseg 64) / 40 (off list)

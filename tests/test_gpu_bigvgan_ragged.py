@@ -146,3 +146,25 @@ def test_argument_errors(vocs, mels, alone):
     assert lib.f5hip_bigvgan_forward_ragged(v._h, 2, None, C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()), None) != 0
     for t, a, got in zip(FRAMES, alone[2], v.decode_ragged(mels)):
         _same(got, a, f"after the errors T={t}")
+
+
+# ---------------------------------------------------------------------------------------------------------------- the default geometry
+FULL_FRAMES = [300, 1, 257, 256, 130]   # pitches 384 / 128 / 384 / 256 / 256: both first-stage paths, items over more than two first-stage blocks
+
+
+@pytest.mark.parametrize("planes", [2, 3])
+def test_default_geometry_items_equal_their_own_calls(planes):
+    """bigvgan_v2_24khz_100band_256x at full width (stage widths 768 ... 24: the wide conv5 tiles, several column tiles, the XCD-blocked tile
+    order): every item of one ragged call equals its own uniform call to the last bit, in the caller's order and permuted.  No oracle here:
+    tests/test_gpu_bigvgan.py pins the uniform call at this geometry."""
+    from tts_indic_server_f5_amd.vocoder import F5HipBigVGAN
+    voc = F5HipBigVGAN(synth.bigvgan_state_dict(), gemm_planes=planes)
+    g = torch.Generator().manual_seed(523)
+    mels = [torch.randn(100, t, generator=g) * 1.5 - 1.0 for t in FULL_FRAMES]
+    own = [voc(m[None]).reshape(-1).clone() for m in mels]
+    for order in (list(range(len(mels))), [3, 1, 0, 4, 2]):
+        got = voc.decode_ragged([mels[i] for i in order])
+        for i, w in zip(order, got):
+            assert w.shape == (UP * FULL_FRAMES[i],)
+            _same(w, own[i], f"full width planes {planes} order {order} T={FULL_FRAMES[i]}")
+        print(f"[parity] bigvgan ragged full width planes {planes} order {order}: {len(order)} items bit-equal to their own calls (bound 0)")

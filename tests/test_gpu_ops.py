@@ -472,16 +472,7 @@ def test_attention_unit_op(impl, lens, kv, heads, k_gain, hot, inv, instance):
 
 
 # ---------------------------------------------------------------------------------------------------------------- conv1d (BigVGAN convolutions)
-def _conv_ref(x, w, bias, res, batch, P, T, dil):
-    """nn.Conv1d on the valid rows of every sequence (zero padding at the sequence bounds), channel-last in / out."""
-    M, ci = x.shape
-    k = w.shape[-1]
-    xv = x.view(batch, P, ci)[:, :T].transpose(1, 2).double()
-    y = torch.nn.functional.conv1d(xv, w.double(), None if bias is None else bias.double(), dilation=dil, padding=dil * (k - 1) // 2)
-    y = y.transpose(1, 2)
-    if res is not None:
-        y = y + res.view(batch, P, -1)[:, :T].double()
-    return y
+from bigvgan_ref import conv_ref as _conv_ref  # noqa: E402
 
 
 @pytest.mark.parametrize("impl", [5, 0])

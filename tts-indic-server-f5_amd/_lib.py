@@ -81,6 +81,13 @@ SYMBOLS = {
     "f5hip_op_bigvgan_snake": (C.c_int, [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "f5hip_op_bigvgan_upsample": (C.c_int, [C.c_int32] * 6 + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
     "f5hip_op_bigvgan_conv_post": (C.c_int, [C.c_int32] * 4 + [C.c_void_p] * 2 + [C.c_int32, C.c_void_p, C.c_void_p]),
+    "f5hip_op_conv1d_ragged": (C.c_int, [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 7 + [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p]),
+    "f5hip_op_bigvgan_snake_ragged": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 3 +
+                                      [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "f5hip_op_bigvgan_conv_post_ragged": (C.c_int, [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p] * 2 +
+                                          [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "f5hip_op_bigvgan_mean3": (C.c_int, [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
+    "f5hip_op_bigvgan_mel_rows": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "f5hip_op_conv_pos_embed": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_void_p] * 3),
     "f5hip_op_convnext_block": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
     "f5hip_vocos_create": (C.c_void_p, [C.POINTER(VocosConfig)]),

@@ -540,6 +540,206 @@ extern "C" int f5hip_op_bigvgan_conv_post(int32_t batch, int32_t P, int32_t T, i
     return rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- BigVGAN unit ops, ragged forms
+// The layouts of f5hip_bigvgan_forward_ragged, described by the caller in rows of the stage the op runs at; the ops build the tables the
+// kernels take (BvRagged) and launch as bv_generate does.
+
+// One [start, end) per block of blk rows over M rows from n items (item i: rows [row0[i], row0[i] + rows[i]), the first valid[i] valid; rows
+// null: ceil(valid / align) align).  Every item starts at, and spans, a multiple of `align` rows (a multiple of blk), and every block belongs
+// to exactly one item.  tab = start [M / blk], end [M / blk].
+static int op_block_table(const char* name, int n, const int32_t* row0, const int32_t* rows, const int32_t* valid, int M, int blk, int align,
+                          std::vector<int>& tab) {
+    const int nblk = M / blk;
+    tab.assign((size_t)2 * nblk, -1);
+    for (int i = 0; i < n; i++) {
+        const long long r0 = row0[i], v = valid[i], p = rows ? rows[i] : (v + align - 1) / align * align;
+        if (r0 < 0 || v <= 0 || v > p || r0 + p > M) return fail(-1, "%s: item %d (rows %lld + %lld, %lld valid) outside the %d rows", name, i, r0, p, v, M);
+        if (r0 % align || p % align) return fail(-1, "%s: item %d (rows %lld + %lld) is not aligned to %d rows", name, i, r0, p, align);
+        for (int b = (int)(r0 / blk); b < (int)((r0 + p) / blk); b++) {
+            if (tab[b] >= 0) return fail(-1, "%s: block %d belongs to two items", name, b);
+            tab[b] = (int)r0; tab[nblk + b] = (int)(r0 + v);
+        }
+    }
+    for (int b = 0; b < nblk; b++)
+        if (tab[b] < 0) return fail(-1, "%s: block %d belongs to no item", name, b);
+    return 0;
+}
+
+// int4 items of BvRagged from n items given in rows at `scale`: (row0, valid, wave offset (0 when off is null), index) / scale.  Every
+// item lies inside the M rows, its wave inside wave_len samples, and all three are multiples of scale.  t_max = the longest item's rows.
+static int op_item_table(const char* name, int n, const int32_t* row0, const int32_t* valid, const int32_t* off, int scale, long long M, long long wave_len,
+                         std::vector<int>& h, int& t_max) {
+    if (n <= 0 || n > 65535 || !row0 || !valid || scale <= 0) return fail(-1, "%s: bad item table", name);
+    h.assign((size_t)4 * n, 0);
+    t_max = 0;
+    for (int i = 0; i < n; i++) {
+        const long long r0 = row0[i], v = valid[i], o = off ? off[i] : 0;
+        if (r0 < 0 || v <= 0 || r0 + v > M || o < 0 || (off && o + v > wave_len)) return fail(-1, "%s: item %d out of range", name, i);
+        if (r0 % scale || v % scale || o % scale) return fail(-1, "%s: item %d is not a multiple of scale %d", name, i, scale);
+        h[4 * i] = (int)(r0 / scale); h[4 * i + 1] = (int)(v / scale); h[4 * i + 2] = (int)(o / scale); h[4 * i + 3] = i;
+        t_max = std::max(t_max, (int)v);
+    }
+    return 0;
+}
+
+// f5hip_op_conv1d over ragged items: bounds per block of blk rows (GemmArgs::seq_blk), as bv_generate's convolutions pass them.  ups_rate > 0:
+// the 3-tap form of an up-sampler (w_host [c_in][c_out][2 ups_rate], out_dev [M ups_rate][c_out], no residual; k and dil are not read).
+extern "C" int f5hip_op_conv1d_ragged(int32_t n_items, const int32_t* item_row0, const int32_t* item_rows, const int32_t* item_valid, int32_t M,
+                                      int32_t blk, int32_t c_in, int32_t c_out, int32_t k, int32_t dil, int32_t ups_rate, const float* x_dev,
+                                      const float* w_host, const float* bias_host, const float* res_dev, float* out_dev, int32_t prec,
+                                      int32_t impl, void* stream) {
+    const bool ups = ups_rate > 0;
+    if (n_items <= 0 || !item_row0 || !item_valid || M <= 0 || blk <= 0 || blk % 128 || M % blk || c_in <= 0 || c_in % 4 || c_out <= 0 || !x_dev || !w_host ||
+        !out_dev || (prec != 2 && prec != 3) || (impl != 0 && impl != 5) || ups_rate < 0 ||
+        (ups ? (ups_rate < 2 || ups_rate % 2 || res_dev != nullptr) : (k < 1 || !(k & 1) || dil < 1)))
+        return fail(-1, "op_conv1d_ragged: bad argument");
+    // conv5.h takes a tile's bounds from its first row: the 256-row tile must lie in one item, so blk is 128 (two entries per tile, the
+    // items 256-aligned) or a multiple of 256
+    if (impl == 5 && (M % 256 || (blk != 128 && blk % 256))) return fail(-1, "op_conv1d_ragged: blk %d does not fit the 256-row tile of conv5", blk);
+    const int align = impl == 5 && blk == 128 ? 256 : blk;
+    std::vector<int> tab;
+    CK(op_block_table("op_conv1d_ragged", n_items, item_row0, item_rows, item_valid, M, blk, align, tab));
+    hipStream_t st = (hipStream_t)stream;
+    const int cpad = ceil_to(c_in, 32), nblk = M / blk;
+    std::vector<float> bias(c_out, 0.0f);
+    if (bias_host) bias.assign(bias_host, bias_host + c_out);
+    BvConv c;
+    if (ups) {
+        if (bv_pack_ups(c, w_host, bias.data(), c_in, c_out, ups_rate, prec == 3)) return -4;
+    } else {
+        const std::vector<float> w(w_host, w_host + (size_t)c_out * c_in * k);
+        if (bv_pack_conv(c, w, bias.data(), c_out, c_in, k, dil, prec == 3)) return -4;
+    }
+    OpBufs b;
+    Plane2 A;
+    A.hi = op_filled<__bf16>(b, (size_t)M * cpad + 4096, 0, st); A.lo = op_filled<__bf16>(b, (size_t)M * cpad + 4096, 0, st);
+    int* d_tab = b.get<int>(tab.size());
+    if (!A.hi || !A.lo || !d_tab) { bv_free_conv(c); return fail(-5, "op_conv1d_ragged: hipMalloc"); }
+    int rc = upload_sync(st, d_tab, tab) != hipSuccess ? fail(-6, "op_conv1d_ragged: upload") : 0;
+    if (!rc) {
+        const size_t n4 = (size_t)M * c_in / 4;
+        hipLaunchKernelGGL(bv_mean3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x_dev, x_dev, x_dev, 1, (size_t)M, c_in, (float*)nullptr, A.hi, A.lo,
+                           cpad, prec == 3 ? 2 : 1);
+        GemmArgs g = conv_args(c, A, M, align, 0, res_dev, out_dev, d_tab, d_tab + nblk, blk);
+        rc = run_conv(prec, g, c.w, impl == 5, false, c.w.n_pad % 128 ? 64 : 128, st);   // impl 5: conv5 or an error, never the gemm.h fallback
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(-6, "op_conv1d_ragged: sync");
+    bv_free_conv(c);
+    return rc;
+}
+
+// f5hip_op_bigvgan_snake over ragged items (grid z = item, bv_snake_launch with items / scale); x_dev fp32 [M][C], out_dev as in the uniform op
+extern "C" int f5hip_op_bigvgan_snake_ragged(int32_t n_items, const int32_t* item_row0, const int32_t* item_valid, int32_t scale, int32_t M, int32_t C,
+                                             const float* x_dev, const float* alpha_log_dev, const float* beta_log_dev, int32_t out_format,
+                                             float* out_dev, int64_t out_rows, void* stream) {
+    if (M <= 0 || C <= 0 || C % 4 || !x_dev || !alpha_log_dev || !beta_log_dev || !out_dev || out_format < 0 || out_format > 2 || out_rows < M)
+        return fail(-1, "op_bigvgan_snake_ragged: bad argument");
+    std::vector<int> h;
+    int t_max = 0;
+    CK(op_item_table("op_bigvgan_snake_ragged", n_items, item_row0, item_valid, nullptr, scale, M, 0, h, t_max));
+    hipStream_t st = (hipStream_t)stream;
+    AaFilt f;
+    bv_aa_filter(f.f);
+    OpBufs b;   // freed after the final synchronisation
+    int* items = b.get<int>(h.size());
+    if (!items) return fail(-5, "op_bigvgan_snake_ragged: hipMalloc");
+    if (upload_sync(st, items, h) != hipSuccess) return fail(-6, "op_bigvgan_snake_ragged: upload");
+    const int4* it = reinterpret_cast<const int4*>(items);
+    int rc;
+    if (out_format == 0) {
+        rc = bv_snake_launch(x_dev, C, M, 0, t_max, alpha_log_dev, beta_log_dev, f, 0, nullptr, nullptr, out_dev, C, st, it, n_items, scale);
+    } else {
+        const size_t n = (size_t)out_rows * C, n4 = n / 4;
+        __bf16* hi = b.get<__bf16>(n); __bf16* lo = b.get<__bf16>(n);
+        if (!hi || !lo) return fail(-5, "op_bigvgan_snake_ragged: hipMalloc");
+        hipLaunchKernelGGL(bv_mean3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, out_dev, out_dev, out_dev, 1, (size_t)out_rows, C, (float*)nullptr,
+                           hi, lo, C, out_format == 2 ? 2 : 1);
+        rc = bv_snake_launch(x_dev, C, M, 0, t_max, alpha_log_dev, beta_log_dev, f, out_format, hi, lo, nullptr, C, st, it, n_items, scale);
+        if (!rc) hipLaunchKernelGGL(op_planes_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, hi, lo, out_format == 2 ? 1 : 0, n, out_dev);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(-7, "op_bigvgan_snake_ragged: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// f5hip_op_bigvgan_conv_post over ragged items (grid y = item): a_dev fp32 [M][C]; item i writes wave_dev [item_wave_off[i], + item_valid[i])
+// of the wave_len samples and nothing else
+extern "C" int f5hip_op_bigvgan_conv_post_ragged(int32_t n_items, const int32_t* item_row0, const int32_t* item_valid, const int32_t* item_wave_off,
+                                                 int32_t scale, int32_t M, int32_t C, const float* a_dev, const float* w_dev, int32_t variant,
+                                                 float* wave_dev, int64_t wave_len, void* stream) {
+    if (M <= 0 || C <= 0 || !a_dev || !w_dev || !wave_dev || !item_wave_off || wave_len <= 0 || variant < 0 || variant > 2)
+        return fail(-1, "op_bigvgan_conv_post_ragged: bad argument");
+    std::vector<int> h;
+    int t_max = 0;
+    CK(op_item_table("op_bigvgan_conv_post_ragged", n_items, item_row0, item_valid, item_wave_off, scale, M, wave_len, h, t_max));
+    hipStream_t st = (hipStream_t)stream;
+    OpBufs b;
+    int* items = b.get<int>(h.size());
+    if (!items) return fail(-5, "op_bigvgan_conv_post_ragged: hipMalloc");
+    if (upload_sync(st, items, h) != hipSuccess) return fail(-6, "op_bigvgan_conv_post_ragged: upload");
+    int rc = bv_conv_post(a_dev, C, C, n_items, 0, t_max, w_dev, wave_dev, variant, st, reinterpret_cast<const int4*>(items), scale);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(-7, "op_bigvgan_conv_post_ragged: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// bv_mean3_kernel: (y0 + y1 + y2) / 3 (n_in 3) or y0 (n_in 1) over fp32 rows [rows][C] -> fp32 rows out_f32_dev [rows][C] (or null) and / or,
+// mode 1 / 2 / 3, split-bf16 / fp16 / bf16 planes of pitch ldo.  The planes are loaded from planes_dev fp32 [rows][ldo] first and read
+// back into it as fp32 (hi + lo; the lo plane starts as zero in mode 3), so the padding channels come back as they were, up to the format.
+extern "C" int f5hip_op_bigvgan_mean3(int64_t rows, int32_t C, int32_t n_in, const float* y0_dev, const float* y1_dev, const float* y2_dev,
+                                      int32_t mode, int32_t ldo, float* out_f32_dev, float* planes_dev, void* stream) {
+    if (rows <= 0 || C <= 0 || C % 4 || (n_in != 1 && n_in != 3) || !y0_dev || (n_in == 3 && (!y1_dev || !y2_dev)) || mode < 0 || mode > 3 ||
+        (mode == 0 ? !out_f32_dev : (!planes_dev || ldo < C || ldo % 4)) || rows * (int64_t)std::max(C, ldo) / 4 > (int64_t)256 * 2147483647)
+        return fail(-1, "op_bigvgan_mean3: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    OpBufs b;
+    __bf16 *hi = nullptr, *lo = nullptr;
+    const size_t n = mode ? (size_t)rows * ldo : 0;
+    if (mode) {
+        hi = b.get<__bf16>(n); lo = op_filled<__bf16>(b, n, 0, st);
+        if (!hi || !lo) return fail(-5, "op_bigvgan_mean3: hipMalloc");
+        hipLaunchKernelGGL(bv_mean3_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, planes_dev, planes_dev, planes_dev, 1, (size_t)rows, ldo,
+                           (float*)nullptr, hi, lo, ldo, mode);
+    }
+    const size_t n4 = (size_t)rows * C / 4;
+    hipLaunchKernelGGL(bv_mean3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, y0_dev, n_in == 3 ? y1_dev : y0_dev, n_in == 3 ? y2_dev : y0_dev, n_in,
+                       (size_t)rows, C, out_f32_dev, hi, lo, ldo, mode);
+    if (mode) hipLaunchKernelGGL(op_planes_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, hi, lo, mode == 2 ? 1 : 0, n, planes_dev);
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_bigvgan_mean3: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+// bv_mel_rows_kernel (item_row0 null: n uniform sequences of pitch M0 / n rows, mel_dev [n][C][T]) or bv_mel_rows_ragged_kernel (item i:
+// item_frames[i] frames from row item_row0[i], a multiple of 128; mel_dev [n][C][T], T = the column stride; every 128-row block belongs to
+// one item) -> out_dev fp32 [M0][128], the planes (split bf16 hi + lo, or the fp16 plane) the kernel wrote over planes of NaN.
+extern "C" int f5hip_op_bigvgan_mel_rows(int32_t n, const int32_t* item_row0, const int32_t* item_frames, int32_t T, int32_t M0, int32_t C,
+                                         const float* mel_dev, int32_t f16, float* out_dev, void* stream) {
+    if (n <= 0 || T <= 0 || M0 <= 0 || C <= 0 || C > 128 || !mel_dev || !out_dev || (item_row0 ? (!item_frames || M0 % 128) : (M0 % n || M0 / n < T)))
+        return fail(-1, "op_bigvgan_mel_rows: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    OpBufs b;
+    const size_t ne = (size_t)M0 * 128;
+    __bf16* hi = op_filled<__bf16>(b, ne, 0xff, st); __bf16* lo = op_filled<__bf16>(b, ne, 0xff, st);
+    if (!hi || !lo) return fail(-5, "op_bigvgan_mel_rows: hipMalloc");
+    if (item_row0) {
+        const int nblk = M0 / 128;
+        std::vector<int> tab, h((size_t)3 * nblk, 0);
+        for (int i = 0; i < n; i++)
+            if (item_frames[i] > T) return fail(-1, "op_bigvgan_mel_rows: item %d has %d frames, the column stride is %d", i, item_frames[i], T);
+        CK(op_block_table("op_bigvgan_mel_rows", n, item_row0, nullptr, item_frames, M0, 128, 128, tab));
+        std::copy(tab.begin(), tab.end(), h.begin());
+        for (int i = 0; i < n; i++)
+            for (int r = item_row0[i]; r < item_row0[i] + item_frames[i]; r += 128) h[(size_t)2 * nblk + r / 128] = i;
+        int* d = b.get<int>(h.size());
+        if (!d) return fail(-5, "op_bigvgan_mel_rows: hipMalloc");
+        if (upload_sync(st, d, h) != hipSuccess) return fail(-6, "op_bigvgan_mel_rows: upload");
+        hipLaunchKernelGGL(bv_mel_rows_ragged_kernel, dim3(M0), dim3(128), 0, st, mel_dev, C, T, d, d + nblk, d + 2 * nblk, hi, lo, f16 ? 1 : 0);
+    } else {
+        hipLaunchKernelGGL(bv_mel_rows_kernel, dim3(M0), dim3(128), 0, st, mel_dev, C, T, M0 / n, hi, lo, f16 ? 1 : 0);
+    }
+    hipLaunchKernelGGL(op_planes_to_f32_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, hi, lo, f16 ? 1 : 0, ne, out_dev);
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(-7, "op_bigvgan_mel_rows: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- DiT input-side unit ops
 // frame f of x [n][C] -> row frame_row[f] of dst (pitch ldd), and its split-bf16 planes (pitch ldd) when hi is not null
 __global__ __launch_bounds__(256) void op_scatter_rows_kernel(const float* x, int C, int n, const int* frame_row, float* dst, __bf16* hi, __bf16* lo,

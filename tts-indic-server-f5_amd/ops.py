@@ -165,6 +165,98 @@ def bigvgan_conv_post(a, weight, *, batch, valid, variant=0):
     return wave
 
 
+def conv1d_ragged(x, weight, bias=None, res=None, *, row0, valid, rows=None, blk, dilation=1, prec=2, impl=5, ups_rate=0):
+    """conv1d() over ragged items, the layout of the ragged BigVGAN forward: x fp32 [M, c_in]; item i owns rows [row0[i], + rows[i]) (rows
+    None: valid rounded up to the alignment), the first valid[i] of them real; the kernels read one [start, end) per block of blk rows.
+    ups_rate > 0: the 3-tap form of an up-sampler, weight [c_in, c_out, 2 ups_rate] as in bigvgan_upsample(), out [M ups_rate, c_out].
+    Layouts the kernels exclude are refused (include/f5hip.h).  Returns out."""
+    dev = x.device
+    x = _f32(x, dev)
+    M = x.shape[0]
+    if ups_rate:
+        c_in, c_out, k = weight.shape
+        assert k == 2 * ups_rate
+    else:
+        c_out, c_in, k = weight.shape
+    w = np.ascontiguousarray(weight.detach().to(torch.float32).cpu().numpy())
+    b = None if bias is None else np.ascontiguousarray(bias.detach().to(torch.float32).cpu().numpy())
+    r = None if res is None else _f32(res, dev)
+    r0, rw, vl = _i32(row0), _i32(rows), _i32(valid)
+    assert len(vl) == len(r0) and (rw is None or len(rw) == len(r0))
+    out = torch.empty(M * max(ups_rate, 1), c_out, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().f5hip_op_conv1d_ragged(len(r0), _p(r0), _p(rw), _p(vl), M, blk, c_in, c_out, k, dilation, ups_rate, _p(x), _p(w), _p(b),
+                                                 _p(r), _p(out), prec, impl, _lib.current_stream_ptr()), "f5hip_op_conv1d_ragged")
+    return out
+
+
+def bigvgan_snake_ragged(x, alpha_log, beta_log, *, row0, valid, scale, out_format=SNAKE_OUT_F32, out=None):
+    """bigvgan_snake() over ragged items: item i = rows [row0[i], + valid[i]) of x fp32 [M, C], multiples of `scale` (the kernel's item
+    table is in first-stage rows).  out as in bigvgan_snake(); returns it."""
+    dev = x.device
+    x, alpha_log, beta_log = (_f32(t, dev) for t in (x, alpha_log, beta_log))
+    M, Cc = x.shape
+    if out is None:
+        out = torch.zeros(M, Cc, dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[1] == Cc and out.shape[0] >= M
+    r0, vl = _i32(row0), _i32(valid)
+    assert len(vl) == len(r0)
+    _lib.check(_lib.lib().f5hip_op_bigvgan_snake_ragged(len(r0), _p(r0), _p(vl), scale, M, Cc, _p(x), _p(alpha_log), _p(beta_log), out_format,
+                                                        _p(out), out.shape[0], _lib.current_stream_ptr()), "f5hip_op_bigvgan_snake_ragged")
+    return out
+
+
+def bigvgan_conv_post_ragged(a, weight, wave, *, row0, valid, wave_off, scale, variant=0):
+    """bigvgan_conv_post() over ragged items: item i = rows [row0[i], + valid[i]) of a fp32 [M, C] -> samples [wave_off[i], + valid[i]) of
+    `wave` (fp32, 1-D, on the device; written in place, nothing else of it is touched).  Returns wave."""
+    dev = a.device
+    a = _f32(a, dev)
+    M, Cc = a.shape
+    w = _f32(weight.reshape(Cc, 7), dev)
+    assert wave.dtype == torch.float32 and wave.is_contiguous() and wave.dim() == 1 and wave.device == dev
+    r0, vl, wo = _i32(row0), _i32(valid), _i32(wave_off)
+    assert len(vl) == len(r0) == len(wo)
+    _lib.check(_lib.lib().f5hip_op_bigvgan_conv_post_ragged(len(r0), _p(r0), _p(vl), _p(wo), scale, M, Cc, _p(a), _p(w), variant, _p(wave),
+                                                            wave.numel(), _lib.current_stream_ptr()), "f5hip_op_bigvgan_conv_post_ragged")
+    return wave
+
+
+# plane modes of bigvgan_mean3: none, split bf16, one fp16 plane, the bf16 hi plane alone
+MEAN3_NONE, MEAN3_SPLIT, MEAN3_F16, MEAN3_BF16 = 0, 1, 2, 3
+
+
+def bigvgan_mean3(ys, *, mode=MEAN3_NONE, planes=None, want_f32=True):
+    """The generator's mean of a stage's three AMP blocks: ys = 3 fp32 [rows, C] tensors ((y0 + y1 + y2) / 3) or 1 (its conversion).
+    mode > 0: `planes` fp32 [rows, ldo >= C] is loaded into operand planes of that mode, the kernel writes channels < C, and the planes
+    come back in it as fp32.  Returns (fp32 rows [rows, C] | None, planes | None)."""
+    dev = ys[0].device
+    ys = [_f32(y, dev) for y in ys]
+    rows, Cc = ys[0].shape
+    out = torch.empty(rows, Cc, dtype=torch.float32, device=dev) if want_f32 or mode == 0 else None
+    ldo = 0
+    if mode:
+        assert planes.dtype == torch.float32 and planes.is_contiguous() and planes.shape[0] == rows and planes.device == dev
+        ldo = planes.shape[1]
+    y = ys + [None, None]
+    _lib.check(_lib.lib().f5hip_op_bigvgan_mean3(rows, Cc, len(ys), _p(y[0]), _p(y[1]), _p(y[2]), mode, ldo, _p(out), _p(planes) if mode else None,
+                                                 _lib.current_stream_ptr()), "f5hip_op_bigvgan_mean3")
+    return out, planes if mode else None
+
+
+def bigvgan_mel_rows(mel, *, rows, row0=None, frames=None, f16=False):
+    """The generator's first operand planes as fp32 [rows, 128]: mel fp32 [n, C, T] -> one row of 128 channels per frame.  row0 None: n
+    uniform sequences of T frames at pitch rows / n.  Else the ragged kernel: item i has frames[i] <= T frames from row row0[i] (a
+    multiple of 128) and T is the column stride."""
+    dev = mel.device
+    mel = _f32(mel, dev)
+    n, Cc, T = mel.shape
+    out = torch.empty(rows, 128, dtype=torch.float32, device=dev)
+    r0, fr = _i32(row0), _i32(frames)
+    assert r0 is None or (fr is not None and len(r0) == len(fr) == n)
+    _lib.check(_lib.lib().f5hip_op_bigvgan_mel_rows(n, _p(r0), _p(fr), T, rows, Cc, _p(mel), int(f16), _p(out), _lib.current_stream_ptr()),
+               "f5hip_op_bigvgan_mel_rows")
+    return out
+
+
 def joint_attention(q, k, v, x_len, c_len, x_kvlen=None, *, heads, shape_invariant=-1, out_format=ATTN_OUT_SPLIT):
     """MMDiT joint attention: per sequence softmax(q [x ; c] k^T / 8 + mask on the padded audio keys) v over the concatenation of its audio
     rows and its text rows.  q / k / v fp32 [sum(x_len) + sum(c_len), 64 * heads]: all audio frames first, then all text tokens.
@@ -225,7 +317,7 @@ def convnext_block(x, params, *, seq_len, taps=False, pad_nan=False):
 
 
 def _i32(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
+    return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.int32))
 
 
 def _col_ptr(table, col):
