@@ -740,6 +740,25 @@ int f5hip_ref_prestep(int32_t n, const int32_t* n_in, const int32_t* channels, c
 /* Samples out_dev needs: sum((n_in[i] + 50 ms of frames) * channels[i]); -1 for arguments f5hip_ref_prestep refuses. */
 int64_t f5hip_ref_prestep_bound(int32_t n, const int32_t* n_in, const int32_t* channels, int32_t rate);
 
+/* The per-voice denoiser of uploaded reference clips for n clips in one call, IN PLACE on mono 24 kHz fp32 samples (f5hip_ref_frontend's
+ * packed output): audio_prep.denoise_reference in fp32 -- quantile-based noise estimation (Stahl, Fischer, Bippus 2000) with power spectral
+ * subtraction.  F = ceil((len + 768) / 256) frames of 1024 samples at hop 256 under w[i] = sin(pi i / 1024), frame m = samples
+ * 256 m - 768 .. 256 m + 255 (zeros outside the clip); P = |rfft|^2; floor[k] = the ((F - 1) / 5)-th smallest of the clip's P[.][k], no
+ * interpolation; S = the mean of P over the 3 x 3 cells around (m, k), indices clamped; G = max(1/8, (S - 6.75 floor[k]) / S), 1/8 where
+ * S = 0; out = overlap_add(irfft(G X) w) / 2.  The length is kept, a silent clip stays silent.
+ *   offset[i], n_samples[i]   host; clip i is n_samples[i] samples at wave_dev + offset[i]; the ranges are disjoint and need not be adjacent:
+ *                             samples between them and clips left out of the table are not touched
+ *   wave_dev                  fp32, read and written
+ * FOUR launches whatever n (stft: one block per frame row of the packed batch, X float2 [rows][513], P [rows][516]; floor: the exact order
+ * statistic of the device's own P, bit by bit over the float's bit pattern, integer counts; gain: S, G, the Hermitian fill and the inverse
+ * transform, times w / 1024; ola: one thread per sample, its four frames in ascending order, halved), no host synchronisation once its
+ * workspace has grown to the call's size: the clip table goes through pinned staging on `stream` (counters ref_denoise_launches,
+ * ref_denoise_clips; geometry csrc/ref_denoise_core.h, which tools/ref_denoise_check.cpp walks on the CPU under sanitizers).  Clip i's
+ * output equals its own single-clip call's bit for bit.
+ * Refused before the first launch: n < 1, a length below 1 or above 1 440 000 (60 s), a negative offset, overlapping ranges, a null pointer,
+ * more than 2^31 - 1 frame rows. */
+int f5hip_ref_denoise(int32_t n, const int64_t* offset, const int32_t* n_samples, float* wave_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

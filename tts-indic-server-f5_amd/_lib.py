@@ -129,6 +129,7 @@ SYMBOLS = {
     "f5hip_flac_decode_bound": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "f5hip_ref_prestep": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_ref_prestep_bound": (C.c_int64, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
+    "f5hip_ref_denoise": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -461,3 +461,84 @@ def remove_silence_pcm(pcm_int16, rate: int = 24000) -> np.ndarray:
     if not pieces:
         return np.zeros(0, dtype=np.int16)
     return np.ascontiguousarray(np.concatenate([p.frames[:, 0] for p in pieces]))
+
+
+# ------------------------------------------------------------------------------------------------ denoising an uploaded reference clip
+# The definition of the per-voice `denoise` option (`infer.PreparedVoice(..., denoise=True)`; on the device `ops.ref_denoise`,
+# csrc/ref_denoise.h): quantile-based noise estimation (Stahl, Fischer, Bippus 2000) with power spectral subtraction, on the front-end's
+# output -- mono, 24 kHz, after the rms gain -- in float64:
+#   window     w[i] = sin(pi i / 1024), the square root of the periodic Hann window, for analysis and synthesis; four shifts of w^2 by 256
+#              sum to exactly 2
+#   frames     F = ceil((n + 768) / 256); frame m holds clip samples 256 m - 768 .. 256 m + 255, zeros outside the clip: every clip sample
+#              lies in exactly four frames
+#   spectrum   X[m, k] = rfft(frame_m * w), k = 0 .. 512; P = re^2 + im^2
+#   floor      r = (F - 1) // 5; floor[k] = the r-th smallest (0-based) of P[0 .. F - 1, k], no interpolation
+#   smoothing  S[m, k] = the sum of P over frames m - 1 .. m + 1 and bins k - 1 .. k + 1, indices clamped to the edges (always nine terms), / 9
+#   gain       G = max(0.125, (S - 6.75 floor[k]) / S) where S > 0, else 0.125
+#   synthesis  y_m = irfft(G * X)[0 .. 1023] * w; out = overlap_add(y) / 2, cropped to the clip's n samples
+# Every step is a continuous map of the samples, so the device's fp32 can be held to a tolerance.  6.75 is 1.5 times the bias
+# -1 / ln(0.8) = 4.48 of the 20 % quantile of an exponentially distributed power, rounded to a dyadic value; the gain floor of 1/8 caps the
+# attenuation at 18.06 dB.  The method treats whatever is there in every frame as noise: a buzz without pauses and with shallow modulation
+# is damaged, which is why the option is per voice and off unless asked for.
+DENOISE_N_FFT = 1024
+DENOISE_HOP = 256
+DENOISE_PAD = 768
+DENOISE_RANK_DIV = 5
+DENOISE_SUBTRACT = 6.75
+DENOISE_MIN_GAIN = 0.125
+DENOISE_MAX_SAMPLES = 1_440_000   # 60 s at 24 kHz
+
+
+def check_denoise_length(n: int) -> None:
+    """Refuses (ValueError) a clip of `n` samples at 24 kHz that the denoiser does not take."""
+    if n > DENOISE_MAX_SAMPLES:
+        raise ValueError(f"denoise: the reference clip has {n} samples at 24 kHz; at most DENOISE_MAX_SAMPLES = {DENOISE_MAX_SAMPLES} (60 s) are denoised")
+
+
+def denoise_frames(n: int) -> int:
+    return -(-(n + DENOISE_PAD) // DENOISE_HOP)
+
+
+def denoise_floor(P: np.ndarray) -> np.ndarray:
+    """floor[k]: the ((F - 1) // 5)-th smallest of P[:, k] (P [F, bins])."""
+    r = (P.shape[0] - 1) // DENOISE_RANK_DIV
+    return np.partition(P, r, axis=0)[r]
+
+
+def denoise_reference(wave) -> np.ndarray:
+    """The definition above of a mono 24 kHz clip `wave` [n] (or [1, n]), 1 <= n <= DENOISE_MAX_SAMPLES -> float32 [n]: `denoise_reference_f64`
+    rounded once to the samples' format.  The length is preserved; a silent clip stays silent; and where floor[k] = 0 for every bin (a clean
+    clip with pauses: G = 1 everywhere) the clip comes back up to rounding (a few 1e-16 relative in the float64 arithmetic), because
+    sum_m w^2 = 2 over a sample's four frames."""
+    return denoise_reference_f64(wave).astype(np.float32)
+
+
+def denoise_reference_f64(wave) -> np.ndarray:
+    """`denoise_reference` before its one rounding to float32: the definition's float64 samples [n]."""
+    x = np.asarray(wave, dtype=np.float64).reshape(-1)
+    n = len(x)
+    if n < 1:
+        raise ValueError("denoise: the reference clip is empty")
+    check_denoise_length(n)
+    N, H = DENOISE_N_FFT, DENOISE_HOP
+    F = denoise_frames(n)
+    w = np.sin(np.pi * np.arange(N) / N)
+    xp = np.zeros(H * (F - 1) + N)
+    xp[DENOISE_PAD:DENOISE_PAD + n] = x
+    X = np.fft.rfft(np.lib.stride_tricks.sliding_window_view(xp, N)[::H] * w, axis=1)
+    P = X.real ** 2 + X.imag ** 2
+    floor = denoise_floor(P)
+    Pe = np.pad(P, 1, mode="edge")
+    S = np.zeros_like(P)
+    for dm in range(3):
+        for dk in range(3):
+            S += Pe[dm:dm + F, dk:dk + P.shape[1]]
+    S /= 9.0
+    G = np.full_like(S, DENOISE_MIN_GAIN)
+    np.divide(S - DENOISE_SUBTRACT * floor, S, out=G, where=S > 0)
+    G = np.maximum(G, DENOISE_MIN_GAIN)
+    y = np.fft.irfft(G * X, n=N, axis=1) * w
+    out = np.zeros_like(xp)
+    for m in range(F):
+        out[H * m:H * m + N] += y[m]
+    return out[DENOISE_PAD:DENOISE_PAD + n] / 2.0

@@ -22,6 +22,7 @@
 //   torch.ops.f5hip.ref_prestep(frames, n_in, channels, clip_short, rate) -> (Tensor planes fp32, Tensor info int32 [n, 2])   F/infer/utils_infer.py:282-350
 //   torch.ops.f5hip.wave_loudness(pcm, in_off, max_len, len_dev?, gain_k) -> Tensor stats int64 [n, 4]; pcm is normalised in place
 //   torch.ops.f5hip.wave_prosody(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, taps?) -> (Tensor pcm int16, Tensor lengths int32, Tensor offsets int64 host, Tensor bounds int32 host)
+//   torch.ops.f5hip.ref_denoise(wave, offset, n_samples) -> ()   the flagged clips of wave (f5hip_ref_frontend's packed output) are denoised in place
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -35,6 +36,7 @@
 #include "../../include/f5hip.h"
 #include "rate_pair.h"
 #include "wave_prosody_core.h"
+#include "ref_denoise_core.h"
 
 namespace {
 
@@ -632,6 +634,27 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody(const at
     return {out, out_len, out_off, bounds};
 }
 
+// wave: the contiguous 1-D fp32 device tensor that holds every clip (f5hip_ref_frontend's packed output), denoised IN PLACE; offset [n] int64
+// host, n_samples [n] int32 host: clip i is wave[offset[i] : offset[i] + n_samples[i]]; the ranges are disjoint, whatever lies between them
+// is left alone
+void ref_denoise(at::Tensor wave, const at::Tensor& offset, const at::Tensor& n_samples) {
+    check_host(offset, at::kLong, "offset"); check_host(n_samples, at::kInt, "n_samples");
+    check_dev_f32(wave, "wave");
+    const int64_t n = n_samples.numel();
+    TORCH_CHECK(n_samples.dim() == 1 && n > 0 && n <= INT32_MAX && offset.numel() == n, "f5hip::ref_denoise: offset and n_samples need one value per clip, and at least one clip");
+    TORCH_CHECK(wave.dim() == 1, "f5hip::ref_denoise: wave must be a contiguous 1-D fp32 tensor on a HIP device");
+    const int64_t* off = offset.data_ptr<int64_t>();
+    const int32_t* ns = n_samples.data_ptr<int32_t>();
+    for (int64_t i = 0; i < n; i++) {
+        TORCH_CHECK(ns[i] >= 1 && ns[i] <= kRdMaxSamples, "f5hip::ref_denoise: clip ", i, " has ", ns[i], " samples (1 .. ", kRdMaxSamples, ")");
+        TORCH_CHECK(off[i] >= 0 && off[i] + ns[i] <= wave.numel(), "f5hip::ref_denoise: clip ", i, " is samples [", off[i], ", ", off[i] + ns[i], ") of a tensor of ",
+                    wave.numel());
+    }
+    const c10::DeviceGuard guard(wave.device());
+    const int rc = f5hip_ref_denoise((int32_t)n, off, ns, wave.data_ptr<float>(), stream_of(wave));
+    TORCH_CHECK(rc == 0, "f5hip_ref_denoise: ", f5hip_last_error());
+}
+
 }   // namespace
 
 TORCH_LIBRARY(f5hip, m) {
@@ -657,4 +680,5 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("wave_loudness(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor gain_k) -> Tensor", &wave_loudness);
     m.def("wave_prosody(Tensor pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor stretch_p, Tensor stretch_q, Tensor pitch, Tensor? taps) -> "
           "(Tensor, Tensor, Tensor, Tensor)", &wave_prosody);
+    m.def("ref_denoise(Tensor(a!) wave, Tensor offset, Tensor n_samples) -> ()", &ref_denoise);
 }

@@ -32,6 +32,7 @@ import torch
 
 from . import wave_codec
 from .audio_prep import preprocess_ref_audio_text, remove_silence_edges, remove_silence_pcm  # noqa: F401  (F/infer/utils_infer.py:263-350)
+from .audio_prep import DENOISE_MAX_SAMPLES, check_denoise_length, denoise_reference  # noqa: F401  (the per-voice `denoise` option of an uploaded clip)
 from .loaders import DiT, MMDiT, UNetT, load_checkpoint, load_model, load_vocoder  # noqa: F401  (F/infer/utils_infer.py:92-130,175-260)
 from .wave_codec import (ALL_ENCODINGS, DELIVERY_OPTIONS, FLAC_BLOCK, FLAC_ENCODINGS, FLAC_HEADER_BYTES, MAX_TAP_TABLE_BYTES, OUTPUT_ENCODINGS,  # noqa: F401
                          OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, WHOLE_WAVE, WHOLE_WAVE_LOUDNESS, StreamDelivery, StreamFlacEncoder,
@@ -374,24 +375,36 @@ class PreparedVoice:
 
     `PreparedVoice.deferred((wave, sr), target_rms)` is the same voice before any arithmetic on its samples: `seconds` and `ref_frames`
     follow from the clip's length alone (so a request can be planned), `audio` / `rms` / `mel` are filled in by `prepare_voices` -- one
-    ragged front-end call on the device for all deferred voices of a batch (`infer_requests`, `SpanScheduler`)."""
+    ragged front-end call on the device for all deferred voices of a batch (`infer_requests`, `SpanScheduler`).
 
-    def __init__(self, ref_audio, target_rms=0.1, device=None):
+    `denoise` (False): the voice's wave goes through `audio_prep.denoise_reference` behind the front-end -- for recordings with hiss, fan
+    noise or hum.  `rms`, `seconds` and `ref_frames` stay the front-end's; a clip longer than `DENOISE_MAX_SAMPLES` at 24 kHz is refused
+    by both constructors.  A deferred voice is denoised by `prepare_voices`: on the device in one `ops.ref_denoise` call per front-end call."""
+
+    def __init__(self, ref_audio, target_rms=0.1, device=None, denoise=False):
         wav, sr = ref_audio if isinstance(ref_audio, tuple) else load_audio(ref_audio)
+        if denoise:
+            check_denoise_length(resampled_length(wav.shape[-1], sr, target_sample_rate))
         self.seconds = wav.shape[-1] / sr
         self.audio, self.rms = _prepare_reference(wav, sr, target_rms, device)
+        self.denoise = bool(denoise)
+        if self.denoise:
+            self.audio = _denoise_host(self.audio)
         self.ref_frames = self.audio.shape[-1] // hop_length
         self.mel = None
         self.pending = None
 
     @classmethod
-    def deferred(cls, ref_audio, target_rms=0.1):
+    def deferred(cls, ref_audio, target_rms=0.1, denoise=False):
         wav, sr = ref_audio
         if wav.dim() != 2 or wav.shape[-1] < 1:
             raise ValueError(f"reference audio must be [channels, samples] with at least one sample (got {tuple(wav.shape)})")
         if sr != target_sample_rate:
             resample_taps(sr, target_sample_rate)   # an unsupported rate pair is refused here, before anything is queued
+        if denoise:
+            check_denoise_length(resampled_length(wav.shape[-1], sr, target_sample_rate))
         voice = cls.__new__(cls)
+        voice.denoise = bool(denoise)
         voice.seconds = wav.shape[-1] / sr
         voice.ref_frames = resampled_length(wav.shape[-1], sr, target_sample_rate) // hop_length
         voice.audio = voice.rms = voice.mel = None
@@ -409,6 +422,17 @@ class PreparedVoice:
         return self.mel
 
 
+# How often `prepare_voices` denoised: "host_clips" (one `denoise_reference` each) and "device_calls" (one `ops.ref_denoise` each, whatever
+# the number of flagged voices in it).  A batch without a flagged voice adds to neither.
+DENOISE_COUNTS = collections.Counter()
+
+
+def _denoise_host(audio):
+    """`audio_prep.denoise_reference` of a prepared wave [1, nw], back where it was."""
+    DENOISE_COUNTS["host_clips"] += 1
+    return torch.from_numpy(denoise_reference(audio[0].detach().cpu().numpy()))[None].to(audio.device)
+
+
 def prepare_voices(clips, target_rms=0.1, device="cuda"):
     """The reference-audio front-end (mono mix, rms, gain, resampling to 24 kHz) of several voices at once on the device: one upload of the
     packed clips and ONE `ops.ref_frontend` call (two launches) per distinct sample rate, then one download of all rms values.
@@ -416,13 +440,18 @@ def prepare_voices(clips, target_rms=0.1, device="cuda"):
     The mel stays lazy here (`cond`), one call per clip; a model object with `cond_mel_ragged` (`F5HipModel.prepare_voices`) fills the mel of
     every voice this call prepared in one launch behind it.  `device=None` runs the host `_prepare_reference` clip by clip instead (what a model
     object without the device front-end gets: the reference's modules, CPU stand-ins) and leaves the result on the host, like the eager
-    constructor does."""
+    constructor does.  Voices with `denoise` set are denoised behind the front-end: on the device the flagged voices of each front-end call
+    -- one per distinct (sample rate, rms floor) -- go through ONE `ops.ref_denoise` on that call's packed output, in place, so a voice's
+    `audio` view and the mel launch behind it see the denoised samples with no copy; a call without a flagged voice is followed by none.
+    With `device=None` the host `denoise_reference` runs clip by clip."""
     voices = [c if isinstance(c, PreparedVoice) else PreparedVoice.deferred(c, target_rms) for c in clips]
     todo = [v for v in voices if v.pending is not None]
     if device is None:
         for v in todo:
             wav, sr, floor = v.pending
             v.audio, v.rms = _prepare_reference(wav, sr, floor, None)
+            if getattr(v, "denoise", False):
+                v.audio = _denoise_host(v.audio)
             v.pending = None
         return voices
     from . import ops
@@ -435,6 +464,11 @@ def prepare_voices(clips, target_rms=0.1, device="cuda"):
         taps = None if sr == target_sample_rate else _device_taps(sr, target_sample_rate, packed.device)
         out, rms, n_out = ops.ref_frontend(packed, [v.pending[0].shape[-1] for v in vs], [v.pending[0].shape[0] for v in vs], sr,
                                            target_sample_rate, taps, floor)
+        starts = np.concatenate([[0], np.cumsum(n_out)[:-1]])
+        flagged = [i for i, v in enumerate(vs) if getattr(v, "denoise", False)]
+        if flagged:                                              # in place on the packed output: the views below are the denoised clips
+            ops.ref_denoise(out, [int(starts[i]) for i in flagged], [int(n_out[i]) for i in flagged])
+            DENOISE_COUNTS["device_calls"] += 1
         done.append((vs, out.split(n_out), rms))
     if done:
         all_rms = torch.cat([rms for _, _, rms in done]).cpu()   # the one download

@@ -1,7 +1,7 @@
 """Python face of the operations of the C ABI (include/f5hip.h) on torch tensors on the HIP device.  Two families:
   - the per-kernel unit ops (`gemm` .. `time_table`): one production HIP kernel each, fp32 in and out, called through ctypes.  Used by the
     per-kernel parity tests and the timing tools; not on the hot path.
-  - the device audio path that every request takes (`ref_frontend`, `ref_prestep`, `wave_finish` .. `wave_loudness`, `flac_decode`): one
+  - the device audio path that every request takes (`ref_frontend`, `ref_prestep`, `ref_denoise`, `wave_finish` .. `wave_loudness`, `flac_decode`): one
     library call per batch.  Each is bound twice over the same C entry point: as a TORCH_LIBRARY operator (csrc/torch_ops.cpp), taken when
     `torch_ops.load()`, and through ctypes otherwise; both return the same bits.  The steps the wrappers share -- the operator call, the
     per-request host arrays, the PCM request table, its sources, the pointer table and the packing of the outputs -- are the helpers in
@@ -595,6 +595,30 @@ def ref_prestep_planes(packed, lengths, channels):
         out.append(packed[at:at + int(n) * int(c)].view(int(c), int(n)))
         at += int(n) * int(c)
     return out
+
+
+def ref_denoise(wave, offsets, lengths):
+    """The per-voice denoiser of uploaded reference clips for several clips in ONE library call and four launches (include/f5hip.h
+    f5hip_ref_denoise): `audio_prep.denoise_reference` of each clip in fp32, IN PLACE.  wave: the contiguous 1-D fp32 device tensor that holds
+    the clips -- `ref_frontend`'s packed output as it stands --; clip i is wave[offsets[i] : offsets[i] + lengths[i]], mono at 24 kHz, 1 to
+    `audio_prep.DENOISE_MAX_SAMPLES` samples.  The ranges are disjoint and need not be adjacent: samples between them, and clips left out of
+    the table, keep their bits.  A clip's result equals its own single-clip call's bit for bit.  Returns `wave`."""
+    from .audio_prep import DENOISE_MAX_SAMPLES
+    ln = _per_request("ref_denoise", "lengths", lengths, np.int32, per="clip")
+    off = _per_request("ref_denoise", "offsets", offsets, np.int64, len(ln), per="clip")
+    if not (torch.is_tensor(wave) and wave.dtype == torch.float32 and wave.is_contiguous() and wave.is_cuda and wave.dim() == 1):
+        raise _lib.F5HipError("ref_denoise: wave must be a contiguous 1-D fp32 tensor on the HIP device")
+    if torch_ops.load():
+        call_op("ref_denoise", wave, torch.from_numpy(off), torch.from_numpy(ln))
+        return wave
+    for i in range(len(ln)):
+        if ln[i] < 1 or ln[i] > DENOISE_MAX_SAMPLES:
+            raise _lib.F5HipError(f"ref_denoise: clip {i} has {ln[i]} samples (1 .. {DENOISE_MAX_SAMPLES})")
+        if off[i] < 0 or int(off[i]) + int(ln[i]) > wave.numel():
+            raise _lib.F5HipError(f"ref_denoise: clip {i} is samples [{off[i]}, {int(off[i]) + int(ln[i])}) of a tensor of {wave.numel()}")
+    with torch.cuda.device(wave.device):
+        _lib.check(_lib.lib().f5hip_ref_denoise(len(ln), _p(off), _p(ln), _p(wave), _lib.current_stream_ptr()), "f5hip_ref_denoise")
+    return wave
 
 
 def wave_finish(chunks, chunks_per_request, fade, remove_silence=None, sample_rate=24000):

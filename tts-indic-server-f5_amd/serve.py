@@ -446,7 +446,7 @@ class TTSManager:
         self.mel_spec_type = mel_spec_type
         self._prep_cache: dict = {}   # prompt path -> (PreparedVoice, ref_text): clip / trim / resample / mel run once per voice
         self._prep_lock = threading.Lock()   # route handlers run in a thread pool: concurrent first requests of a voice prepare it once
-        # Uploaded clips (`synthesize_clip`): (sha1 of the upload, ref_text, clip_short) -> (PreparedVoice, ref_text), least recently used
+        # Uploaded clips (`synthesize_clip`): (sha1 of the upload, ref_text, clip_short, denoise) -> (PreparedVoice, ref_text), least recently used
         # first, at most `clip_cache` entries (each holds the prepared wave and its device mel).  `_clip_lock` guards the two tables only;
         # the preparation itself runs under the key's own lock, so one slow upload does not stall other voices.
         self.clip_cache = int(clip_cache)
@@ -569,16 +569,18 @@ class TTSManager:
     def _call(self, text, ref_audio_path, ref_text, **options):
         return self._serve(lambda: self._voice(ref_audio_path, ref_text), text, options)
 
-    def _clip_voice(self, ref_audio, ref_text, clip_short=True):
+    def _clip_voice(self, ref_audio, ref_text, clip_short=True, denoise=False):
         """(PreparedVoice, normalised ref_text) of an uploaded clip -- WAV bytes or a (wave [ch, n], sr) pair -- prepared once per
-        (content, ref_text, clip_short) and kept in the LRU cache.  Host work only: read, quantise to int16 (16-bit PCM passes through bit for
+        (content, ref_text, clip_short, denoise) and kept in the LRU cache: the same upload with and without `denoise` are two voices.  Host work only: read, quantise to int16 (16-bit PCM passes through bit for
         bit; any other format as clip(round(x * 32768), -32768, 32767) -- pydub would hand those to ffmpeg), the silence pre-step
         (`audio_prep.preprocess_ref_segment`), back to float32.  With `device_frontend` the voice is deferred: its mono mix / gain /
         resampling run on the device with the batch it first rides in; with `device_prestep` as well the int16 frames go through
         `ops.ref_prestep` under the device lock and the clip never returns to the host.  Everything that can be refused is refused here with
         ValueError, before anything is queued: an empty `ref_text`, an unreadable WAV, a rate below 11 025 Hz, non-finite samples, a clip
-        that is empty or all-zero after the pre-step, a rate pair whose tap table is refused."""
-        return self._clip_voices([(ref_audio, ref_text, clip_short)])[0]
+        that is empty or all-zero after the pre-step, a rate pair whose tap table is refused, a `denoise` that is not a bool or whose clip is
+        longer than `audio_prep.DENOISE_MAX_SAMPLES` at 24 kHz.  `denoise` (`infer.PreparedVoice`) acts behind the front-end: the silence
+        pre-step still sees the recording as it was uploaded."""
+        return self._clip_voices([(ref_audio, ref_text, clip_short, denoise)])[0]
 
     def _prestep_device(self):
         """The device `ops.ref_prestep` runs on, or None where the host pre-step runs: `device_prestep` needs `device_frontend` and a model on a GPU."""
@@ -607,13 +609,16 @@ class TTSManager:
         return np.ascontiguousarray(pcm.T), sr
 
     def _clip_voices(self, specs):
-        """`_clip_voice` of several uploads, [(ref_audio, ref_text, clip_short)] -> [(PreparedVoice, normalised ref_text)].  The cache is
+        """`_clip_voice` of several uploads, [(ref_audio, ref_text, clip_short[, denoise])] -> [(PreparedVoice, normalised ref_text)].  The cache is
         looked up per key and every new key is prepared under its own lock (taken in key order, so two callers never wait for each other
         in a ring).  On the host path the new clips are prepared one after the other; with `device_prestep` they share ONE `ops.ref_prestep`
         call per distinct sample rate."""
         import torch
         keys, audios = [], {}
-        for ref_audio, ref_text, clip_short in specs:
+        for ref_audio, ref_text, clip_short, *rest in specs:
+            denoise = rest[0] if rest else False
+            if not isinstance(denoise, bool):
+                raise ValueError(f"denoise must be true or false (got {denoise!r})")
             if not ref_text or not ref_text.strip():
                 raise ValueError("Reference text cannot be empty.")
             h = hashlib.sha1()
@@ -624,7 +629,7 @@ class TTSManager:
             else:
                 ref_audio = bytes(ref_audio)
                 h.update(ref_audio)
-            key = (h.hexdigest(), ref_text, bool(clip_short))
+            key = (h.hexdigest(), ref_text, bool(clip_short), denoise)
             keys.append(key)
             audios.setdefault(key, ref_audio)
         results, entries = {}, []
@@ -671,7 +676,7 @@ class TTSManager:
                 clip = clips[key]
                 if clip[1] != infer.target_sample_rate:
                     infer.resample_taps(clip[1], infer.target_sample_rate)      # refuses a rate pair it has no table for
-                voice = infer.PreparedVoice.deferred(clip) if self.device_frontend else infer.PreparedVoice(clip)
+                voice = infer.PreparedVoice.deferred(clip, denoise=key[3]) if self.device_frontend else infer.PreparedVoice(clip, denoise=key[3])
                 value = (voice, audio_prep.normalize_ref_text(key[1]))
                 with self._clip_lock:
                     self._clip_cache[key] = value
@@ -710,16 +715,18 @@ class TTSManager:
             return self.batcher.submit(req).result(timeout=self.request_timeout_s)
         return self._run_batch([req])[0]
 
-    def synthesize_clip(self, text, ref_audio, ref_text, *, clip_short=True, **options):
+    def synthesize_clip(self, text, ref_audio, ref_text, *, clip_short=True, denoise=False, **options):
         """`synthesize` with the caller's own reference clip instead of a registered voice: `ref_audio` is a WAV file's bytes or a
-        (wave [ch, n], sr) pair, `ref_text` its transcript; `clip_short` as in `preprocess_ref_audio_text`.  The clip never touches the
-        disk (`_clip_voice`); the request then takes the same batcher path as `synthesize`, with the same options."""
-        return self._serve(lambda: self._clip_voice(ref_audio, ref_text, clip_short), text, options)
+        (wave [ch, n], sr) pair, `ref_text` its transcript; `clip_short` as in `preprocess_ref_audio_text`; `denoise`: remove stationary
+        background noise (hiss, fan noise, hum) from the clip before it is cloned (`audio_prep.denoise_reference`; off unless asked for,
+        because a voice without pauses is taken for noise).  The clip never touches the disk (`_clip_voice`); the request then takes the
+        same batcher path as `synthesize`, with the same options."""
+        return self._serve(lambda: self._clip_voice(ref_audio, ref_text, clip_short, denoise), text, options)
 
-    def synthesize_clip_stream(self, text, ref_audio, ref_text, *, clip_short=True, **options):
+    def synthesize_clip_stream(self, text, ref_audio, ref_text, *, clip_short=True, denoise=False, **options):
         """`synthesize_stream` with an uploaded reference clip (`synthesize_clip`): an iterator of pieces (float32; in the delivery format
         with `sample_rate` / `encoding`) whose concatenation is `synthesize_clip`'s wave given the same noise."""
-        return self._serve(lambda: self._clip_voice(ref_audio, ref_text, clip_short), text, options, stream=True)
+        return self._serve(lambda: self._clip_voice(ref_audio, ref_text, clip_short, denoise), text, options, stream=True)
 
     def synthesize(self, text, ref_audio_path, ref_text, **options):
         """The wave of one request.  `options`: any of `infer.REQUEST_OPTIONS`, by keyword -- a name that is not among them is refused by
@@ -838,20 +845,24 @@ class TTSManager:
         resolved, uploads, together = {}, [], self._prestep_device() is not None
         for tag in dict.fromkeys(tag for tag, _ in pieces):
             spec = dict(voices[tag])
-            unknown = set(spec) - {"ref_audio_path", "ref_audio", "ref_text", "clip_short", "speed"}
+            unknown = set(spec) - {"ref_audio_path", "ref_audio", "ref_text", "clip_short", "denoise", "speed"}
             if unknown or ("ref_audio_path" in spec) == ("ref_audio" in spec):
-                raise ValueError(f"voice {tag!r}: give ref_audio_path or ref_audio, ref_text and optionally clip_short, speed "
+                raise ValueError(f"voice {tag!r}: give ref_audio_path or ref_audio, ref_text and optionally clip_short, speed, denoise "
                                  f"(got {sorted(spec)})")
+            if "denoise" in spec and not isinstance(spec["denoise"], bool):
+                raise ValueError(f"voice {tag!r}: denoise must be true or false (got {spec['denoise']!r})")
+            if "denoise" in spec and "ref_audio_path" in spec:
+                raise ValueError(f"voice {tag!r}: denoise is an option of an uploaded clip (ref_audio), not of a registered voice")
             speed = self.request_options(("speed",), speed=spec.get("speed")).get("speed")
             if not spec.get("ref_text") or not spec["ref_text"].strip():
                 raise ValueError("Reference text cannot be empty.")
             if "ref_audio_path" in spec:
                 voice, ref_text = self._voice(spec["ref_audio_path"], spec["ref_text"])
             elif together:
-                uploads.append((tag, speed, (spec["ref_audio"], spec["ref_text"], spec.get("clip_short", True))))
+                uploads.append((tag, speed, (spec["ref_audio"], spec["ref_text"], spec.get("clip_short", True), spec.get("denoise", False))))
                 continue
             else:
-                voice, ref_text = self._clip_voice(spec["ref_audio"], spec["ref_text"], spec.get("clip_short", True))
+                voice, ref_text = self._clip_voice(spec["ref_audio"], spec["ref_text"], spec.get("clip_short", True), spec.get("denoise", False))
             resolved[tag] = (voice, ref_text, speed)
         if uploads:                                  # the script's uploads together: one pre-step call per distinct rate for the new ones
             for (tag, speed, _), (voice, ref_text) in zip(uploads, self._clip_voices([u for _, _, u in uploads])):
@@ -861,7 +872,7 @@ class TTSManager:
     def synthesize_script(self, text, voices, *, gap=0.0, **options):
         """A multi-voice script (F/infer/infer_cli.py:166-208) as ONE request: `text` with `[tag]` marks (`infer.split_voice_tags`: a piece
         without a known tag is spoken by "main"), `voices` = {tag: dict(ref_audio_path=..., ref_text=...) | dict(ref_audio=<WAV bytes or
-        (wave, sr)>, ref_text=..., clip_short=True)}, each with an optional `speed`; `gap`: seconds of silence between pieces (0 to 5).
+        (wave, sr)>, ref_text=..., clip_short=True, denoise=False)}, each with an optional `speed`; `gap`: seconds of silence between pieces (0 to 5).
         `options`: `infer.REQUEST_OPTIONS` as in `synthesize`, for the whole script -- one `seed` for all its chunks in order, and
         `remove_silence` / `loudness` / `sample_rate` / `encoding` on the joined wave (so two voices of different prompt levels come out at one programme loudness).  The script is one item of its batch (`infer.ScriptRequest`): its
         pieces are sampled and vocoded with everything else in the batch, cross-faded inside a piece and concatenated between pieces
@@ -1006,7 +1017,7 @@ def stream_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, r
 
 def request_models():
     """The routes' request models by name (`create_app`): pydantic is imported here, on first use, like fastapi is there."""
-    from pydantic import BaseModel
+    from pydantic import BaseModel, ConfigDict
 
     class SamplerFields(BaseModel):                  # per-request sampler settings; None = the manager's (TTSManager.opts)
         nfe_step: int | None = None
@@ -1041,12 +1052,14 @@ def request_models():
         text: str
         parts_to_edit: list[list[float]]
         fix_duration: list[float] | None = None
+        denoise: typing.Any = None                   # not an option of this route (an edit keeps the recording): anything but an absent field is a 400
 
     class CloneRequest(SpeechFields):                # zero-shot cloning from the caller's own clip; JSON (base64 WAV), not multipart
         text: str
         ref_audio: str
         ref_text: str
         clip_short: bool = True
+        denoise: bool = False                        # remove stationary background noise from the clip (audio_prep.denoise_reference)
         stream: bool = False
 
     class ScriptVoice(BaseModel):                    # one voice of a script: a registered name, or the caller's own clip (base64 WAV)
@@ -1055,6 +1068,7 @@ def request_models():
         ref_text: str | None = None
         clip_short: bool = True
         speed: float | None = None
+        model_config = ConfigDict(extra="allow")     # `denoise` (true / false, of an uploaded clip only) is read from the extras: `_run_script`
 
     class ScriptRequest(SpeechFields):               # F/infer/infer_cli.py:166-208: `[tag]` text and a voices table; JSON, not TOML
         text: str
@@ -1070,9 +1084,11 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     """FastAPI app with the reference's `/v1/audio/speech` route (`S/routes/speech.py:19-41`) and `/v1/audio/edit` (speech editing:
     JSON body {"audio": base64 WAV, "text": the full new transcript, "parts_to_edit": [[start_s, end_s], ...], "fix_duration": [...] | null}
     -> the edited recording as WAV), plus `/v1/audio/speech/clone`: `/v1/audio/speech/voice` with the caller's own reference clip
-    ({"text", "ref_audio": base64 WAV, "ref_text", "clip_short": true, ...}) instead of a registered voice's name, and
+    ({"text", "ref_audio": base64 WAV, "ref_text", "clip_short": true, "denoise": false, ...}) instead of a registered voice's name
+    (`denoise`: remove stationary background noise from the clip first; an input-side option, so it works with `"stream": true`; the edit
+    route and the routes on registered voices do not take it), and
     `/v1/audio/speech/script`: a multi-voice script ({"text": "[main] ... [town] ...", "voices": {tag: {"ref_audio_name" | "ref_audio":
-    base64 WAV, "ref_text", "clip_short"?, "speed"?}}, "gap": seconds between pieces, ...}) as one request.  The speech routes take `"stream": true`: the WAV then arrives chunk by chunk (`_run_stream`), its
+    base64 WAV, "ref_text", "clip_short"?, "denoise"?, "speed"?}}, "gap": seconds between pieces, ...}) as one request.  The speech routes take `"stream": true`: the WAV then arrives chunk by chunk (`_run_stream`), its
     PCM samples identical to the unstreamed response's.  Every route also takes the optional sampler fields `nfe_step`, `cfg_strength`,
     `sway_sampling_coef`, `seed`, `ode_method` ("euler", "midpoint" or "rk4": the request's ODE solver) and (speech routes) `speed` and
     `remove_silence` (true: pauses of 1 s or more are cut down to 500 ms on each side; 400 together with `"stream": true`), checked
@@ -1184,10 +1200,10 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         headers = _headers("synthesized_speech.wav", fmt)
         try:
             if req.stream:
-                pieces = tts_manager.synthesize_clip_stream(req.text, raw, req.ref_text, clip_short=req.clip_short, **opts)
+                pieces = tts_manager.synthesize_clip_stream(req.text, raw, req.ref_text, clip_short=req.clip_short, denoise=req.denoise, **opts)
                 first = next(pieces, None)
                 return StreamingResponse(_pcm_body(first, pieces, opts, fmt), media_type=MEDIA_TYPES[fmt], headers=headers)
-            wave = tts_manager.synthesize_clip(req.text, raw, req.ref_text, clip_short=req.clip_short, **opts)
+            wave = tts_manager.synthesize_clip(req.text, raw, req.ref_text, clip_short=req.clip_short, denoise=req.denoise, **opts)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
         return StreamingResponse(_blocks(response_body(wave, opts, fmt)), media_type=MEDIA_TYPES[fmt], headers=headers)
@@ -1214,6 +1230,8 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
                     raise HTTPException(status_code=400, detail="Audio must be a base64-encoded WAV file.")
             if not spec["ref_text"] or not spec["ref_text"].strip():
                 raise HTTPException(status_code=400, detail="Reference text cannot be empty.")
+            if "denoise" in (v.model_extra or {}):   # checked by the manager: true or false, and of an uploaded clip only
+                spec.update(denoise=v.model_extra["denoise"])
             voices[tag] = spec
         headers = _headers("synthesized_script.wav", fmt)
         try:
@@ -1230,6 +1248,8 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
         opts = _options(req, tuple(dict.fromkeys(EDIT_OPTIONS + EDIT_DELIVERY)))
+        if req.denoise is not None:
+            raise HTTPException(status_code=400, detail="denoise is an option of an uploaded reference clip: the edit route keeps the recording")
         fmt = _response_format(req, opts)
         try:
             raw = base64.b64decode(req.audio, validate=True)
