@@ -707,6 +707,111 @@ def test_attention_neighbour_invariance(kind):
             _assert_same(outs[0], alone, f"{kind} S = {L} x {heads} heads, {what} neighbour: {instance} ({n_comp} companions) vs alone")
 
 
+# ---------------------------------------------------------------------------------------------------------------- poisoned neighbours
+# A sequence's attention output must not depend on the VALUES of the other sequences of its launch either, whatever they are: the serving
+# path packs unrelated requests into one launch and nothing on it rejects a non-finite mel.  Finite neighbours cannot show a leak that is
+# masked by multiplication (a probability of exactly 0 times a neighbour's value row changes nothing; times NaN it destroys the row), so
+# every other sequence is filled with NaN, or with 1e30 (finite in fp32; the fp16 operands saturate and every score against it overflows).
+# What the kernel reads: the op packs q / k / v as the QKV epilogue stores them, through sat_f16 = min(max(x, -65504), 65504), which maps
+# 1e30 to +65504 and NaN to -65504 (max(NaN, a) = a) -- attn3's operands are never NaN in this library, a poisoned row is a row at the fp16
+# limit, whose scores against finite keys overflow the fp16 probabilities (inf row sums: the redo vote).
+# One row per attn3 instance and one two-range row, shapes from the tables above.  "overhang": the finite sequence's last query tile
+# covers rows of the poisoned sequence behind it.  hot: one query block of the FIRST sequence takes the running-maximum redo.
+POISON_FILLS = [float("nan"), 1e30]
+ISO_ATTN = [
+    # (lens, kv, heads, hot, inv, instance)
+    pytest.param((300, 50, 257), (300, 41, 200), 4, (), -1, "nw4", id="nw4"),                           # 128-query tiles: no overhang
+    pytest.param((1404, 300), None, 4, ((640, 701),), 1, "nw4", id="nw4-hot-block"),
+    pytest.param(N6_LENS, N6_KV, 4, ((64, 201),), 1, "nw6", id="nw6-hot-block-overhang"),               # 385's last tile: 64 rows of the next
+    pytest.param((1404, 70, 130, 200), (1404, 65, 130, 129), 8, (), 1, "nw6_deep", id="nw6_deep-overhang"),   # 1404's last tile: 70 rows
+    pytest.param(N8_LENS, N8_KV, 12, ((288, 101),), -1, "nw8", id="nw8-hot-block-overhang"),            # 577's last tile: 128 rows
+    pytest.param(N8D_LENS, N8D_KV, 6, ((288, 101),), 0, "nw8_deep", id="nw8_deep-hot-block-overhang"),
+    pytest.param((1404, 70, 130, 200), (1404, 65, 130, 129), 8, (), -1, "bal8", id="bal8-overhang"),
+    pytest.param((1404, 1404), None, 16, BAL_HOT, 0, "bal8", id="bal8-hot-blocks-overhang"),            # 1404's last tile: 128 rows
+]
+ATTN_FORMATS = ("ATTN_OUT_SPLIT", "ATTN_OUT_F16", "ATTN_OUT_BF16")
+
+
+def _poison_rows(ts, bounds, parity, fill):
+    """Copies of the tensors `ts` with the rows [a, b) of every range of `bounds` whose index is = parity mod 2 filled with `fill`."""
+    out = [t.clone() for t in ts]
+    for i, (a, b) in enumerate(bounds):
+        if i % 2 == parity:
+            for t in out:
+                t[a:b] = fill
+    return out
+
+
+def _assert_isolated(run, instance, seg2, keep, poisoned, fill, label):
+    """run(poison, out_format) -> fp32 output rows of one launch.  In every output format the rows `keep` (the finite sequences') are
+    bit-identical with finite and with poisoned neighbours, the launch took `instance`, and the poisoned sequences' own rows changed (the
+    poison went in)."""
+    from tts_indic_server_f5_amd import ops
+    for name in ATTN_FORMATS:
+        fmt, outs = getattr(ops, name), []
+        for poison in (False, True):
+            _reset_counters()
+            outs.append(run(poison, fmt))
+            _assert_attn_path(instance, seg2)
+        clean, dirty = outs
+        assert torch.isfinite(clean).all(), (label, name)
+        assert not torch.equal(dirty[poisoned], clean[poisoned]), (label, name, "the poisoned sequences' outputs did not change: the poison never went in")
+        _assert_same(dirty[keep], clean[keep], f"{label} {instance} {name}: finite sequences next to {fill} neighbours vs finite neighbours")
+    print(f"[isolation] {label} {instance}{' seg2' if seg2 else ''} fill {fill}: {int(keep.sum())} finite rows bit-equal next to {int(poisoned.sum())} "
+          f"poisoned rows, formats {', '.join(ATTN_FORMATS)}")
+
+
+@pytest.mark.parametrize("fill", POISON_FILLS, ids=["nan", "1e30"])
+@pytest.mark.parametrize("parity", [1, 0], ids=["odd_poisoned", "even_poisoned"])
+@pytest.mark.parametrize("lens,kv,heads,hot,inv,instance", ISO_ATTN)
+def test_attention_poisoned_neighbours(lens, kv, heads, hot, inv, instance, parity, fill):
+    """The launch of test_attention_unit_op twice, identical but for the q, k and v rows of every other sequence (the odd ones, then the
+    even ones), which the second launch fills with NaN / 1e30: the other sequences' outputs are bit-identical in all three output formats.
+    With the odd sequences poisoned the first sequence keeps its hot block (the redo runs next to a poisoned neighbour) and its last
+    tile overhangs into poisoned rows; with the even ones poisoned a finite sequence sits behind poisoned rows, and the redo vote of a
+    poisoned sequence (NaN row sums) must not reach the finite blocks."""
+    from tts_indic_server_f5_amd import ops
+    g = torch.Generator().manual_seed(sum(lens) + heads)
+    n, D = sum(lens), 64 * heads
+    q = torch.randn(n, D, generator=g) * 1.5
+    k = torch.randn(n, D, generator=g) * 1.5
+    v = torch.randn(n, D, generator=g)
+    _hot_block(q, k, hot)
+    starts = [sum(lens[:i]) for i in range(len(lens))]
+    bounds = [(s, s + L) for s, L in zip(starts, lens)]
+    keep = torch.zeros(n, dtype=torch.bool)
+    for i, (a, b) in enumerate(bounds):
+        keep[a:b] = i % 2 != parity
+    dev = {False: [t.to(DEV) for t in (q, k, v)], True: [t.to(DEV) for t in _poison_rows((q, k, v), bounds, parity, fill)]}
+    run = lambda poison, fmt: ops.attention(*dev[poison], lens, kv, heads=heads, shape_invariant=inv, out_format=fmt)[0].cpu()
+    _assert_isolated(run, instance, False, keep, ~keep, fill, f"attention lens {lens[:4]} heads {heads} hot {hot}")
+
+
+@pytest.mark.parametrize("fill", POISON_FILLS, ids=["nan", "1e30"])
+@pytest.mark.parametrize("parity", [1, 0], ids=["odd_poisoned", "even_poisoned"])
+@pytest.mark.parametrize("x_len,c_len,x_kv,heads,inv,instance", [
+    pytest.param([1404, 257, 64], [240, 65, 7], [1404, 200, 33], 4, -1, "bal8", id="bal8-seg2"),        # 1404's last tile: 128 rows of the next
+    pytest.param([130, 129, 300], [128, 1, 21], [100, 129, 300], 4, 1, "nw4", id="nw4-seg2"),           # a text range of exactly 128 rows
+])
+def test_joint_attention_poisoned_neighbours(x_len, c_len, x_kv, heads, inv, instance, parity, fill):
+    """The same for the two-range kernels: every other sequence's audio AND text rows are poisoned; the audio and text rows of the others
+    are bit-identical.  A finite sequence's text queries run in pseudo-sequences of their own, between the poisoned ones' text rows."""
+    from tts_indic_server_f5_amd import ops
+    D = 64 * heads
+    g = torch.Generator().manual_seed(500 + sum(x_len))
+    Fx, Fc = sum(x_len), sum(c_len)
+    q, k, v = (torch.randn(Fx + Fc, D, generator=g) for _ in range(3))
+    xb = [(sum(x_len[:i]), sum(x_len[:i + 1])) for i in range(len(x_len))]
+    cb = [(Fx + sum(c_len[:i]), Fx + sum(c_len[:i + 1])) for i in range(len(c_len))]
+    keep = torch.zeros(Fx + Fc, dtype=torch.bool)
+    for i, ((a, b), (c, d)) in enumerate(zip(xb, cb)):
+        keep[a:b] = keep[c:d] = i % 2 != parity
+    dirty = _poison_rows(_poison_rows((q, k, v), xb, parity, fill), cb, parity, fill)
+    dev = {False: [t.to(DEV) for t in (q, k, v)], True: [t.to(DEV) for t in dirty]}
+    run = lambda poison, fmt: ops.joint_attention(*dev[poison], x_len, c_len, x_kv, heads=heads, shape_invariant=inv, out_format=fmt).cpu()
+    _assert_isolated(run, instance, True, keep, ~keep, fill, f"joint attention x {x_len} c {c_len} heads {heads}")
+
+
 def test_attention_random_shapes_invariant(monkeypatch):
     """tools/attn_fuzz.py as test_attention_random_shapes, every launch shape-invariant (no balanced 8-wave kernel; NW = 6 launches run
     the 6-wave instances)."""
