@@ -759,6 +759,60 @@ int64_t f5hip_ref_prestep_bound(int32_t n, const int32_t* n_in, const int32_t* c
  * more than 2^31 - 1 frame rows. */
 int f5hip_ref_denoise(int32_t n, const int64_t* offset, const int32_t* n_samples, float* wave_dev, void* stream);
 
+/* Provenance watermark, embedding: the 24 kHz int16 PCM of n requests, still on the device (f5hip_wave_finish's or f5hip_wave_prosody's
+ * buffer), IN PLACE, with the mark of each flagged request's key added -- bit for bit wave_codec.mark_pcm16.  Not in the reference.  It runs
+ * behind f5hip_wave_prosody and before f5hip_wave_loudness / f5hip_wave_encode / f5hip_wave_flac, which read the marked samples.  The
+ * arithmetic is integers only (csrc/wave_mark_core.h, which tools/wave_mark_check.cpp runs on the CPU under sanitizers):
+ *   carrier      c [16384] int16 of a key (f5hip_watermark_carrier): its SplitMix64 chips through the 129 band taps of
+ *                csrc/watermark_taps.inc, circularly, >> 3
+ *   block sums   A[b] = sum |x[j]| over block b of 240 samples of the request (the last one may be partial): below 2^23
+ *   envelope     E[b] = max(A[b-1], A[b], A[b+1]), a missing neighbour counting 0
+ *   output       y[j] = clip(x[j] + ((E[j / 240] c[j mod 16384]) >> 23), -32768, 32767): a 64-bit product, a floor shift; |y - x| < 4066
+ *   pcm_dev, in_off[i], max_len[i], len_dev    as in f5hip_wave_loudness: samples past a request's device length are not read or written
+ *   key_index      host int32 [n]: the row of carriers_dev for request i, or -1 to leave the request alone
+ *   carriers_dev   int16 [n_keys][16384], 16-byte aligned; may be null when no request is flagged
+ *   n_keys         0 .. 16
+ * TWO launches whatever n, none when no request is flagged (wave_mark_sum_kernel: one block per tile of 32 x 240 samples, the block sums into
+ * the call's workspace; wave_mark_add_kernel: one block per tile, 8 samples per 16-byte load and store), no host synchronisation once the
+ * workspace has grown to the call's size: the request table goes through pinned staging on `stream` (counters wave_mark_launches,
+ * wave_mark_requests: the flagged requests); no atomics, vector stores; a request's bytes depend on that request alone; unflagged requests
+ * and the bytes between requests are not written.
+ * Refused before the first launch: n < 1, a null pointer (len_dev excepted, and carriers_dev when nobody is flagged), a negative max_len or
+ * offset, misaligned samples, lengths or carriers, n_keys outside 0 .. 16, a key_index outside -1 .. n_keys - 1, more than 2^31 - 1
+ * samples. */
+int f5hip_wave_mark(int32_t n, int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, const int32_t* key_index,
+                    const int16_t* carriers_dev, int32_t n_keys, void* stream);
+
+/* Samples one block of f5hip_wave_mark's second launch owns (32 blocks of 240).  For tests, which place request lengths around it. */
+int f5hip_wave_mark_tile(void);
+
+/* The carrier of a key (1 .. 2^48 - 1) into carrier [16384] on the HOST: wave_codec.watermark_carrier(key), what a row of carriers_dev
+ * holds.  No device work.  Refused: a null pointer, a key outside the range. */
+int f5hip_watermark_carrier(uint64_t key, int16_t* carrier);
+
+/* Provenance watermark, detection: n mono 24 kHz fp32 clips of their own lengths scored against each of n_keys carriers in one call --
+ * wave_codec.detect_watermark in fp32.  Per clip: F = ceil((len + 768) / 256) frames of 1024 samples at hop 256 under w[i] = sin(pi i /
+ * 1024) (f5hip_ref_denoise's framing and FFT); U[k] = X[k] / sqrt(|X[k]|^2 + 1e-10) for bins 22 .. 136, 0 elsewhere; u = overlap_add(irfft(U)
+ * w) over the clip; Z[m] = sum of u[j] over j = m mod 16384; r[o] = sum_m Z[m] c[(m + o) mod 16384]; o* = the smallest argmax of r;
+ * z = (r[o*] - mean r) / (population deviation of r), 0 where that is 0.  A clip below 12 000 samples scores zeros.
+ *   wave_dev                  fp32, read only
+ *   offset[i], n_samples[i]   host; clip i is n_samples[i] samples at wave_dev + offset[i], disjoint ranges
+ *   carriers_dev              int16 [n_keys][16384], 16-byte aligned (f5hip_watermark_carrier)
+ *   scores_dev                fp32 [n][n_keys][4]: z, o*, r[o*], the deviation.  detected is z >= 7.0
+ * FOUR launches whatever n and n_keys (f5hip_watermark_detect_launches; frame: one block per frame row, forward FFT, unit-modulus band,
+ * Hermitian fill, inverse FFT, times w / 1024; fold: one thread per (clip, residue), samples and their four frames in ascending order;
+ * correlate: one block per (4 clips, key, 512 offsets), the clips' Z and the carrier window staged in LDS, residues ascending from 0;
+ * score: one block per (clip, key), fixed trees, moments in fp64), no host synchronisation once the workspace has grown to the call's size
+ * (counters watermark_detect_launches, watermark_detect_clips).  Every sum runs in an order fixed by the clip alone: clip i's row equals
+ * its own single-clip call's bit for bit.
+ * Refused before the first launch: n < 1, n_keys outside 1 .. 16, a length below 1 or above 1 440 000 (60 s), a negative offset,
+ * overlapping ranges, a null or misaligned pointer, more than 2^31 - 1 frame rows. */
+int f5hip_watermark_detect(int32_t n, const float* wave_dev, const int64_t* offset, const int32_t* n_samples, int32_t n_keys,
+                           const int16_t* carriers_dev, float* scores_dev, void* stream);
+
+/* Kernels one f5hip_watermark_detect call launches (4). */
+int f5hip_watermark_detect_launches(void);
+
 #ifdef __cplusplus
 }
 #endif

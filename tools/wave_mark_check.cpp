@@ -1,0 +1,95 @@
+// The watermark's mark (csrc/wave_mark.h wave_mark_sum_kernel / wave_mark_add_kernel: the tiles, the masked block sums, the envelope, the
+// groups of 8 samples, the carrier index) run serially on the CPU over csrc/wave_mark_core.h, the same text the kernels compile.  Built with
+// -fsanitize=address,undefined, this is the evidence for the core's bounds: the samples, the block sums, the chips and the carrier each live
+// in a heap block of exactly their size, so a read or write past an end is a sanitizer report.  tests/test_wave_mark_core.py builds and runs
+// it.
+//
+//   wave_mark_check --constants     "P block taps shift tile_blocks tile keys_max band_lo band_hi min_samples": the constants the core compiles
+//   wave_mark_check --carrier KEY   "sum sum_of_squares min max fnv1a" and then the first 16 values of the key's carrier
+//   wave_mark_check FILE...         FILE = little-endian uint64 key, int32 n, int32 len (the device length, <= n), then n int16 samples.
+//                                   One line per FILE: "n fnv1a changed y_0 .. y_{min(n, 64) - 1}": the digest of all n samples afterwards
+//                                   (the first len of them marked), how many changed, and the first samples
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "../tts-indic-server-f5_amd/csrc/wave_mark_core.h"
+
+static const int kTaps[kWmTaps] = {
+#include "../tts-indic-server-f5_amd/csrc/watermark_taps.inc"
+};
+
+static unsigned long long fnv1a(const short* v, long long n) {   // over the little-endian bytes of the samples
+    unsigned long long h = 0xcbf29ce484222325ULL;
+    for (long long i = 0; i < n; i++) {
+        const unsigned u = (unsigned short)v[i];
+        h = (h ^ (u & 0xff)) * 0x100000001b3ULL;
+        h = (h ^ (u >> 8)) * 0x100000001b3ULL;
+    }
+    return h;
+}
+
+static short* carrier_of(unsigned long long key) {
+    signed char* chips = (signed char*)malloc(kWmPeriod);
+    short* c = (short*)malloc(sizeof(short) * kWmPeriod);
+    wm_carrier(key, kTaps, chips, c);
+    free(chips);
+    return c;
+}
+
+int main(int argc, char** argv) {
+    if (argc == 2 && !strcmp(argv[1], "--constants")) {
+        printf("%d %d %d %d %d %d %d %d %d %d\n", kWmPeriod, kWmBlock, kWmTaps, kWmShift, kWmTileBlocks, kWmTile, kWmKeysMax, kWdBandLo, kWdBandHi,
+               kWdMinSamples);
+        return 0;
+    }
+    if (argc == 3 && !strcmp(argv[1], "--carrier")) {
+        const unsigned long long key = strtoull(argv[2], nullptr, 0);
+        if (!wm_key_ok(key)) { fprintf(stderr, "%s: refused\n", argv[2]); return 2; }
+        short* c = carrier_of(key);
+        long long sum = 0, sq = 0;
+        int lo = c[0], hi = c[0];
+        for (int m = 0; m < kWmPeriod; m++) { sum += c[m]; sq += (long long)c[m] * c[m]; lo = c[m] < lo ? c[m] : lo; hi = c[m] > hi ? c[m] : hi; }
+        printf("%lld %lld %d %d %llu", sum, sq, lo, hi, fnv1a(c, kWmPeriod));
+        for (int m = 0; m < 16; m++) printf(" %d", (int)c[m]);
+        printf("\n");
+        free(c);
+        return 0;
+    }
+    if (argc < 2) { fprintf(stderr, "usage: wave_mark_check --constants | --carrier KEY | FILE...\n"); return 2; }
+    for (int arg = 1; arg < argc; arg++) {
+        FILE* f = fopen(argv[arg], "rb");
+        if (!f) { perror(argv[arg]); return 2; }
+        unsigned long long key;
+        int32_t head[2];
+        if (fread(&key, sizeof key, 1, f) != 1 || fread(head, sizeof(int32_t), 2, f) != 2) { fprintf(stderr, "%s: short header\n", argv[arg]); return 2; }
+        const long long n = head[0], len = head[1];
+        if (!wm_key_ok(key) || n < 0 || len < 0 || len > n) { fprintf(stderr, "%s: refused\n", argv[arg]); return 2; }
+        short* x = (short*)malloc(sizeof(short) * (size_t)n);               // exactly the samples: the sanitizer guards their ends
+        if ((n && fread(x, sizeof(short), (size_t)n, f) != (size_t)n) || fgetc(f) != EOF) { fprintf(stderr, "%s: needs %lld samples\n", argv[arg], n); return 2; }
+        fclose(f);
+        short* before = (short*)malloc(sizeof(short) * (size_t)n);
+        if (n) memcpy(before, x, sizeof(short) * (size_t)n);
+        short* c = carrier_of(key);
+        const long long tiles = wm_tiles(n), nA = tiles * kWmTileBlocks;
+        int* A = (int*)malloc(sizeof(int) * (size_t)nA);
+        for (long long t = 0; t < tiles; t++)                                // launch 1: every block sum of every tile, masked by the length
+            for (int b = 0; b < kWmTileBlocks; b++) A[t * kWmTileBlocks + b] = wm_block_sum(x, len, t * kWmTileBlocks + b);
+        for (long long t = 0; t < tiles; t++)                                // launch 2: groups of 8 samples
+            for (int grp = 0; grp < kWmTile / 8; grp++) {
+                const long long j = t * kWmTile + 8LL * grp;
+                if (j >= len) break;
+                const int E = wm_envelope(A, nA, j / kWmBlock);
+                if (E == 0) continue;
+                const short* c8 = c + (j & (kWmPeriod - 1));                 // the kernel's 16-byte load: 8 values of the row
+                for (int e = 0; e < 8 && j + e < len; e++) x[j + e] = (short)wm_mark(x[j + e], E, c8[e]);
+            }
+        long long changed = 0;
+        for (long long j = 0; j < n; j++) changed += x[j] != before[j];
+        printf("%lld %llu %lld", n, fnv1a(x, n), changed);
+        for (long long j = 0; j < n && j < 64; j++) printf(" %d", (int)x[j]);
+        printf("\n");
+        free(x); free(before); free(c); free(A);
+    }
+    return 0;
+}

@@ -130,6 +130,11 @@ SYMBOLS = {
     "f5hip_ref_prestep": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_ref_prestep_bound": (C.c_int64, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     "f5hip_ref_denoise": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "f5hip_wave_mark": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "f5hip_wave_mark_tile": (C.c_int, []),
+    "f5hip_watermark_carrier": (C.c_int, [C.c_uint64, C.c_void_p]),
+    "f5hip_watermark_detect": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "f5hip_watermark_detect_launches": (C.c_int, []),
 }
 
 

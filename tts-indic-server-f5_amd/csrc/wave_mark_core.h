@@ -1,0 +1,95 @@
+// The provenance watermark, the part with no HIP in it: the constants, the carrier, the block geometry and the sample arithmetic of the mark
+// (wave_mark.h wave_mark_sum_kernel / wave_mark_add_kernel, f5hip_wave_mark) and the geometry and the tie rule of the detector
+// (f5hip_watermark_detect) as inline functions that a plain host compiler takes too.  tools/wave_mark_check.cpp runs them serially under
+// AddressSanitizer and UBSan over tables of exactly their size; that CPU run is the evidence for the bounds below.  The definition is
+// wave_codec.mark_pcm16 / detect_watermark (written down above wave_codec.check_watermark):
+//   chips    SplitMix64 with state `key`; bit i of output k is chip 64 k + i, +1 set and -1 clear; P = 16384 chips
+//   carrier  c[m] = (sum_k g[k] chip[(m - k + 64) mod P]) >> 3, g = watermark_taps.inc (129 taps, sum |g| = 34684): |c| <= 4336
+//   mark     A[b] = sum |x[j]| over block b of 240 samples; E[b] = max(A[b-1], A[b], A[b+1]), a missing neighbour counting 0;
+//            y[j] = clip(x[j] + ((E[j / 240] c[j mod P]) >> 23)), a 64-bit product and a floor shift
+//
+// Bounds, in one place:
+//   x        wm_block_sum reads x[j] only for j < len: a block past the length sums to 0, which is what a missing neighbour counts
+//   A        launch 1 writes all kWmTileBlocks sums of every tile, so A holds tiles * kWmTileBlocks values; wm_envelope reads A[b - 1 .. b + 1]
+//            only inside [0, nA)
+//   carrier  a sample j reads c[j & (P - 1)]; a group of 8 samples starts at a multiple of 8 and P is one, so it reads 8 values of one row
+//   sums     A <= 240 * 32768 < 2^23; |E c| < 2^23 * 2^13 = 2^36; |E c >> 23| <= 4336 * 0.9375 < 4066
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define WM_HD __host__ __device__ inline
+#else
+#define WM_HD inline
+#endif
+
+constexpr int kWmPeriod = 16384;                      // wave_codec.WATERMARK_PERIOD
+constexpr int kWmBlock = 240;                         // WATERMARK_BLOCK
+constexpr int kWmTaps = 129;                          // WATERMARK_TAPS
+constexpr int kWmShift = 23;                          // WATERMARK_SHIFT
+constexpr int kWmCarrierShift = 3;
+constexpr int kWmKeysMax = 16;                        // WATERMARK_KEYS_MAX
+constexpr unsigned long long kWmKeyMax = (1ULL << 48) - 1;
+constexpr int kWmTileBlocks = 32;                     // 240-sample blocks per tile of either launch
+constexpr int kWmTile = kWmBlock * kWmTileBlocks;     // 7680 samples: a multiple of 8, so a group of 8 samples lies in one block
+static_assert(kWmBlock % 8 == 0 && kWmPeriod % 8 == 0, "wave_mark: a group of 8 samples shares its block and its carrier row");
+
+constexpr int kWdBandLo = 22, kWdBandHi = 136;        // WATERMARK_BAND: bins of the 1024-point STFT
+constexpr int kWdMinSamples = 12000;                  // WATERMARK_MIN_SAMPLES
+constexpr float kWdThreshold = 7.0f;                  // WATERMARK_THRESHOLD
+constexpr float kWdEps = 1e-10f;                      // under the square root of the unit-modulus step
+constexpr int kWdOffTile = 512;                       // offsets one block of the correlation launch owns
+constexpr int kWdGroup = 4;                           // clips that share one staged carrier window there
+constexpr int kWdChunk = 512;                         // residues staged at a time there
+
+// ---- the mark
+WM_HD long long wm_tiles(long long cap) { return cap > 0 ? (cap + kWmTile - 1) / kWmTile : 1; }   // (an empty request keeps one block)
+
+// A[b] of a request of `len` samples: the masked sum of block b's magnitudes
+WM_HD int wm_block_sum(const short* x, long long len, long long b) {
+    int s = 0;
+    for (long long j = b * kWmBlock; j < (b + 1) * kWmBlock && j < len; j++) s += x[j] < 0 ? -(int)x[j] : (int)x[j];
+    return s;
+}
+
+// E[b] from the nA block sums of a request
+WM_HD int wm_envelope(const int* A, long long nA, long long b) {
+    int e = A[b];
+    if (b > 0 && A[b - 1] > e) e = A[b - 1];
+    if (b + 1 < nA && A[b + 1] > e) e = A[b + 1];
+    return e;
+}
+
+// one marked sample (>> on a negative long long is arithmetic: floor)
+WM_HD int wm_mark(int x, int E, int c) {
+    const long long y = (long long)x + (((long long)E * (long long)c) >> kWmShift);
+    return (int)(y < -32768 ? -32768 : (y > 32767 ? 32767 : y));
+}
+
+// ---- the detector
+// whether (v, i) takes the place of (bv, bi) as the maximum of r: the larger value, at equal values the smaller offset
+WM_HD bool wd_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+// ---- host only: the carrier of a key
+inline unsigned long long wm_splitmix64(unsigned long long* state) {
+    unsigned long long z = (*state += 0x9E3779B97F4A7C15ULL);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+inline bool wm_key_ok(unsigned long long key) { return key >= 1 && key <= kWmKeyMax; }
+
+// chips [kWmPeriod] (+1 / -1 as signed bytes) and carrier [kWmPeriod] of `key` from the taps g [kWmTaps]
+inline void wm_carrier(unsigned long long key, const int* g, signed char* chips, short* carrier) {
+    unsigned long long state = key;
+    for (int k = 0; k < kWmPeriod / 64; k++) {
+        const unsigned long long z = wm_splitmix64(&state);
+        for (int i = 0; i < 64; i++) chips[64 * k + i] = ((z >> i) & 1) ? 1 : -1;
+    }
+    for (int m = 0; m < kWmPeriod; m++) {
+        int acc = 0;
+        for (int k = 0; k < kWmTaps; k++) acc += g[k] * chips[(m - k + kWmTaps / 2 + kWmPeriod) & (kWmPeriod - 1)];
+        carrier[m] = (short)(acc >> kWmCarrierShift);   // (arithmetic: floor)
+    }
+}

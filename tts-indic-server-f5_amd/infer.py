@@ -41,6 +41,9 @@ from .wave_codec import (ALL_ENCODINGS, DELIVERY_OPTIONS, FLAC_BLOCK, FLAC_ENCOD
                          rate_pair, request_flac_level, resample_pcm16, resample_sinc_hann, resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
 from .wave_codec import (PITCH_RANGE, PITCH_RATIOS, PROSODY_OPTIONS, WHOLE_WAVE_PROSODY, check_pitch, check_tempo, shift_pcm16,  # noqa: F401
                          shifted_length, wsola_pcm16)
+from .wave_codec import (WATERMARK_BAND, WATERMARK_BLOCK, WATERMARK_KEYS_MAX, WATERMARK_MAX_SAMPLES, WATERMARK_MIN_SAMPLES,  # noqa: F401
+                         WATERMARK_OPTIONS, WATERMARK_PERIOD, WATERMARK_SHIFT, WATERMARK_TAPS, WATERMARK_THRESHOLD, WHOLE_WAVE_WATERMARK,
+                         WatermarkScore, check_watermark, check_watermark_keys, detect_watermark, mark_pcm16, watermark_carrier)
 from .wave_codec import (LOUDNESS_GATE_ABS, LOUDNESS_PEAK_CEILING, LOUDNESS_RANGE, LOUDNESS_TAPS, check_loudness, loudness_gain,  # noqa: F401
                          loudness_gain_constant, loudness_lufs, loudness_taps, measure_loudness, normalise_loudness_pcm16)
 from .wave_codec import _device_taps, _tap_tables  # noqa: F401  (the two caches: used below, and read as infer._X by the tests that bound them)
@@ -379,15 +382,22 @@ class PreparedVoice:
 
     `denoise` (False): the voice's wave goes through `audio_prep.denoise_reference` behind the front-end -- for recordings with hiss, fan
     noise or hum.  `rms`, `seconds` and `ref_frames` stay the front-end's; a clip longer than `DENOISE_MAX_SAMPLES` at 24 kHz is refused
-    by both constructors.  A deferred voice is denoised by `prepare_voices`: on the device in one `ops.ref_denoise` call per front-end call."""
+    by both constructors.  A deferred voice is denoised by `prepare_voices`: on the device in one `ops.ref_denoise` call per front-end call.
 
-    def __init__(self, ref_audio, target_rms=0.1, device=None, denoise=False):
+    `reject_marked` (None): watermark keys the clip must not carry.  The prepared 24 kHz wave is scored against them before the denoiser
+    (`check_unmarked`; a deferred voice by `prepare_voices`: on the device in one `ops.watermark_detect` call per front-end call), and a
+    clip that scores at or above `WATERMARK_THRESHOLD` for any key is a ValueError (`MARKED_REFERENCE`)."""
+
+    def __init__(self, ref_audio, target_rms=0.1, device=None, denoise=False, reject_marked=None):
         wav, sr = ref_audio if isinstance(ref_audio, tuple) else load_audio(ref_audio)
         if denoise:
             check_denoise_length(resampled_length(wav.shape[-1], sr, target_sample_rate))
         self.seconds = wav.shape[-1] / sr
         self.audio, self.rms = _prepare_reference(wav, sr, target_rms, device)
         self.denoise = bool(denoise)
+        self.reject_marked = None if reject_marked is None else tuple(check_watermark_keys(list(reject_marked)))
+        if self.reject_marked is not None:
+            check_unmarked(self.audio, self.reject_marked)
         if self.denoise:
             self.audio = _denoise_host(self.audio)
         self.ref_frames = self.audio.shape[-1] // hop_length
@@ -395,7 +405,7 @@ class PreparedVoice:
         self.pending = None
 
     @classmethod
-    def deferred(cls, ref_audio, target_rms=0.1, denoise=False):
+    def deferred(cls, ref_audio, target_rms=0.1, denoise=False, reject_marked=None):
         wav, sr = ref_audio
         if wav.dim() != 2 or wav.shape[-1] < 1:
             raise ValueError(f"reference audio must be [channels, samples] with at least one sample (got {tuple(wav.shape)})")
@@ -405,6 +415,7 @@ class PreparedVoice:
             check_denoise_length(resampled_length(wav.shape[-1], sr, target_sample_rate))
         voice = cls.__new__(cls)
         voice.denoise = bool(denoise)
+        voice.reject_marked = None if reject_marked is None else tuple(check_watermark_keys(list(reject_marked)))
         voice.seconds = wav.shape[-1] / sr
         voice.ref_frames = resampled_length(wav.shape[-1], sr, target_sample_rate) // hop_length
         voice.audio = voice.rms = voice.mel = None
@@ -427,6 +438,20 @@ class PreparedVoice:
 DENOISE_COUNTS = collections.Counter()
 
 
+# How often reference clips were scored against `reject_marked` keys: "host_clips" (one `detect_watermark` each) and "device_calls" (one
+# `ops.watermark_detect` each, whatever the number of clips and keys in it)
+WATERMARK_COUNTS = collections.Counter()
+MARKED_REFERENCE = "the reference clip carries this service's watermark"
+
+
+def check_unmarked(audio, keys):
+    """Refuses (ValueError, `MARKED_REFERENCE`: it names no key) a prepared 24 kHz wave [1, nw] that `detect_watermark` finds marked with any
+    of `keys`, on the host."""
+    WATERMARK_COUNTS["host_clips"] += 1
+    if any(score.detected for score in detect_watermark(audio[0].detach().cpu().numpy(), list(keys))):
+        raise ValueError(MARKED_REFERENCE)
+
+
 def _denoise_host(audio):
     """`audio_prep.denoise_reference` of a prepared wave [1, nw], back where it was."""
     DENOISE_COUNTS["host_clips"] += 1
@@ -443,13 +468,19 @@ def prepare_voices(clips, target_rms=0.1, device="cuda"):
     constructor does.  Voices with `denoise` set are denoised behind the front-end: on the device the flagged voices of each front-end call
     -- one per distinct (sample rate, rms floor) -- go through ONE `ops.ref_denoise` on that call's packed output, in place, so a voice's
     `audio` view and the mel launch behind it see the denoised samples with no copy; a call without a flagged voice is followed by none.
-    With `device=None` the host `denoise_reference` runs clip by clip."""
+    With `device=None` the host `denoise_reference` runs clip by clip.  Voices with `reject_marked` keys are scored in front of the denoiser:
+    the flagged voices of a front-end call in ONE `ops.watermark_detect` call on its packed output against the union of their keys, of which
+    only the score rows come down; a voice that carries one of its own keys is a ValueError (`MARKED_REFERENCE`) and the call's voices stay
+    deferred.  With `device=None` `check_unmarked` runs clip by clip."""
     voices = [c if isinstance(c, PreparedVoice) else PreparedVoice.deferred(c, target_rms) for c in clips]
     todo = [v for v in voices if v.pending is not None]
     if device is None:
         for v in todo:
             wav, sr, floor = v.pending
-            v.audio, v.rms = _prepare_reference(wav, sr, floor, None)
+            audio, rms = _prepare_reference(wav, sr, floor, None)
+            if getattr(v, "reject_marked", None) is not None:
+                check_unmarked(audio, v.reject_marked)
+            v.audio, v.rms = audio, rms
             if getattr(v, "denoise", False):
                 v.audio = _denoise_host(v.audio)
             v.pending = None
@@ -465,6 +496,17 @@ def prepare_voices(clips, target_rms=0.1, device="cuda"):
         out, rms, n_out = ops.ref_frontend(packed, [v.pending[0].shape[-1] for v in vs], [v.pending[0].shape[0] for v in vs], sr,
                                            target_sample_rate, taps, floor)
         starts = np.concatenate([[0], np.cumsum(n_out)[:-1]])
+        guarded = [i for i, v in enumerate(vs) if getattr(v, "reject_marked", None) is not None and n_out[i] > 0]
+        if guarded:                                              # in front of the denoiser; only the score rows come down
+            keys = sorted({k for i in guarded for k in vs[i].reject_marked})
+            if len(keys) > WATERMARK_KEYS_MAX:
+                raise ValueError(f"the voices of one front-end call name {len(keys)} watermark keys to reject; at most {WATERMARK_KEYS_MAX} in a call")
+            rows = ops.watermark_detect(out, [int(starts[i]) for i in guarded], [min(int(n_out[i]), WATERMARK_MAX_SAMPLES) for i in guarded],
+                                        ops.watermark_carriers(keys, out.device)).cpu().numpy()
+            WATERMARK_COUNTS["device_calls"] += 1
+            for i, row in zip(guarded, rows):
+                if any(score.detected and score.key in vs[i].reject_marked for score in ops.watermark_scores(row, keys)):
+                    raise ValueError(MARKED_REFERENCE)
         flagged = [i for i, v in enumerate(vs) if getattr(v, "denoise", False)]
         if flagged:                                              # in place on the packed output: the views below are the denoised clips
             ops.ref_denoise(out, [int(starts[i]) for i in flagged], [int(n_out[i]) for i in flagged])
@@ -601,22 +643,28 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 
 # per-request options of `infer_requests` (the fourth element of a request) and of the serving routes
 REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "remove_silence", "sample_rate", "encoding",
-                   "loudness", "flac_level") + PROSODY_OPTIONS   # the sampler's six, then `DELIVERY_OPTIONS` and `PROSODY_OPTIONS` (`WaveSpec`)
+                   "loudness", "flac_level") + WATERMARK_OPTIONS + PROSODY_OPTIONS   # the sampler's six, then `DELIVERY_OPTIONS`, `watermark` (carried
+#                                                                                       beside the spec) and `PROSODY_OPTIONS` (`WaveSpec`)
 
 
 def needs_whole_wave(opts, streamed=False) -> bool:
-    """`WaveSpec.needs_whole_wave` of a dict of options: whether the request cannot be handed out chunk by chunk (`WHOLE_WAVE`)."""
-    return WaveSpec.of(opts).needs_whole_wave(streamed)
+    """`WaveSpec.needs_whole_wave` of a dict of options, or a `watermark` among them (a mark needs the whole wave): whether the request
+    cannot be handed out chunk by chunk (`WHOLE_WAVE`)."""
+    return WaveSpec.of(opts).needs_whole_wave(streamed) or check_watermark(opts.get("watermark")) is not None
 
 
 def whole_wave_message(opts) -> str:
-    """`WaveSpec.whole_wave_message` of a dict of options."""
-    return WaveSpec.of(opts).whole_wave_message()
+    """`WaveSpec.whole_wave_message` of a dict of options; `WHOLE_WAVE_WATERMARK` when a `watermark` is the only reason."""
+    return _whole_wave_message(WaveSpec.of(opts), check_watermark(opts.get("watermark")))
+
+
+def _whole_wave_message(spec, watermark=None) -> str:
+    return WHOLE_WAVE_WATERMARK if watermark is not None and not spec.needs_whole_wave() else spec.whole_wave_message()
 
 
 def plan_request(request, defaults, *, target_rms, fix_duration, device, tokenizer):
     """One request tuple (ref_audio, ref_text, gen_text[, options]) of `infer_requests` / `SpanScheduler.admit`, planned: `opts` (the
-    options over `defaults`, unknown ones rejected), `spec` (`WaveSpec.of(opts)`: what the finished wave has to be), `voice` (prepared),
+    options over `defaults`, unknown ones rejected), `spec` (`WaveSpec.of(opts)`: what the finished wave has to be), `watermark` (the key of its mark, None without one), `voice` (prepared),
     `units` (one per chunk; the text is chunked unless it is a list of chunk texts) and `generator`, the request's noise source (None: the
     global one).  A `ScriptRequest` is planned segment by segment:
     `parts` = [(voice, units)] per segment (a plain request has one part), `units` all of them in order -- one generator, so chunk k of the
@@ -628,9 +676,9 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
     unknown = set(opts) - set(REQUEST_OPTIONS) - {"generator"}
     if unknown:
         raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
-    spec = WaveSpec.of(opts)
-    if spec.needs_whole_wave() and isinstance(request_text(request), (list, tuple)):
-        raise ValueError(spec.whole_wave_message())
+    spec, watermark = WaveSpec.of(opts), check_watermark(opts.get("watermark"))
+    if (spec.needs_whole_wave() or watermark is not None) and isinstance(request_text(request), (list, tuple)):   # (a mark needs the whole wave)
+        raise ValueError(_whole_wave_message(spec, watermark))
     # one (voice, units) part per segment; a plain request is its own single segment
     segments = script.segments if script is not None else [tuple(request[:3])]
     parts = [_plan_request(seg[0], seg[1], seg[2], target_rms, seg[3] if len(seg) > 3 and seg[3] is not None else opts["speed"], fix_duration,
@@ -642,7 +690,7 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
     def commit():
         if own is not None:
             own.set_state(gen.get_state())
-    return types.SimpleNamespace(voice=voice, units=units, opts=opts, spec=spec, generator=gen, commit=commit, parts=parts, script=script)
+    return types.SimpleNamespace(voice=voice, units=units, opts=opts, spec=spec, watermark=watermark, generator=gen, commit=commit, parts=parts, script=script)
 
 
 def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, target_rms=target_rms,
@@ -728,18 +776,19 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
         backend = bool(finish.get("device_backend"))
         got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms, on_device=backend, want_specs=False)
         chunk_waves = [request_chunk_waves(plan, got[per_plan[i]:per_plan[i + 1]]) for i, plan in enumerate(plans)]
-        return _finish_specs(chunk_waves, [request_text(req) for req in requests], cross_fade_duration, [plan.spec for plan in plans], **finish)
-    refused = next((plan.spec for plan in plans if plan.spec.needs_whole_wave()), None)
+        return _finish_specs(chunk_waves, [request_text(req) for req in requests], cross_fade_duration, [plan.spec for plan in plans],
+                             watermark=[plan.watermark for plan in plans], **finish)
+    refused = next((plan for plan in plans if plan.spec.needs_whole_wave() or plan.watermark is not None), None)
     if refused is not None and not join:
-        raise ValueError(refused.whole_wave_message())
+        raise ValueError(_whole_wave_message(refused.spec, refused.watermark))
     out = []
     got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms)
     for i, plan in enumerate(plans):
         mine, script = got[per_plan[i]:per_plan[i + 1]], plan.script is not None
         if join:   # a script: (wave, rate, [spectrogram per segment]) like `infer_multi_voice`
             joined_specs = [np.concatenate(specs, axis=1) for _, specs in mine]
-            if script or plan.spec.needs_whole_wave():
-                wave, = _finish_specs([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [plan.spec])
+            if script or plan.spec.needs_whole_wave() or plan.watermark is not None:
+                wave, = _finish_specs([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [plan.spec], watermark=[plan.watermark])
             else:
                 wave = cross_fade_concat(mine[0][0], cross_fade_duration)
             out.append((wave, plan.spec.sample_rate, joined_specs if script else joined_specs[0]))
@@ -762,7 +811,7 @@ def request_wave(gen_text, waves, cross_fade_duration=cross_fade_duration):
 # `ops.wave_finish` calls, `ops.wave_encode` calls and the requests they encoded (`encode_calls`, `encode_requests`), and device-to-host copies
 # (chunk waves, spectrograms, PCM, encoded samples, lengths); `flac_bytes` is the size of the FLAC stream downloads; `loudness_calls` /
 # `loudness_requests`: `ops.wave_loudness` calls and the requests they normalised; `prosody_calls` / `prosody_requests`: `ops.wave_prosody`
-# calls and the requests whose tempo or pitch they changed
+# calls and the requests whose tempo or pitch they changed; `mark_calls` / `mark_requests`: `ops.wave_mark` calls and the requests they marked
 backend_stats: collections.Counter = collections.Counter()
 
 
@@ -782,7 +831,7 @@ def _per_request(value, n, what):
 
 
 def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cross_fade_duration, remove_silence=None, device_backend=False,
-                    want="float", sample_rate=None, encoding=None, loudness=None, flac_level=None, tempo=None, pitch=None):
+                    want="float", sample_rate=None, encoding=None, loudness=None, flac_level=None, tempo=None, pitch=None, watermark=None):
     """From the chunk waves of several requests (rms restored; numpy, or tensors as `_chunk_waves(on_device=True)` leaves them) to what each
     request gets.  A request whose text is a list of chunk texts (a streamed request's head or tail) gets its chunk waves as they are, like
     `request_wave`; a script's (`SegmentedWaves`: one list of chunk waves per segment) as one list per segment.  Any other request gets its
@@ -798,6 +847,8 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
 
     `sample_rate` / `encoding`, `loudness`, `flac_level`, `tempo`, `pitch`: each one value or one per request, None for the default; with the flag they are
     the request's `WaveSpec`, and a request that sets any of them gets `finish_pcm16` of its int16 PCM (quantised whatever `want` says).
+    `watermark`: one key or one per request (`check_watermark`; None: no mark), carried beside the spec: the request's PCM gets `mark_pcm16`
+    between the prosody and the loudness steps.
     With `device_backend` all of it stays on the device, chained on one stream behind `wave_finish`: the calls and the copies that come back
     are `_finish_on_device`'s, and `backend_stats` counts them."""
     _check_want(device_backend, want)   # (first, as ever: a bad `want` is reported before a bad option)
@@ -810,7 +861,8 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     columns = [_per_request(value, n, name) for name, value in keywords]
     specs = [WaveSpec.of(dict(remove_silence=flag, sample_rate=rate, encoding=enc, loudness=lufs, flac_level=level, tempo=rate_of_speech, pitch=semitones))
              for flag, rate, enc, lufs, level, rate_of_speech, semitones in zip(flags, *columns)]
-    return _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend, want)
+    marks = [check_watermark(key) for key in _per_request(watermark, n, "watermark")]
+    return _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend, want, marks)
 
 
 def _check_want(device_backend, want):
@@ -820,17 +872,18 @@ def _check_want(device_backend, want):
         raise ValueError('the device back-end produces int16 PCM: device_backend=True needs want="pcm16"')
 
 
-def _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend=False, want="float"):
-    """`finish_requests` with one planned `WaveSpec` per request in place of its option keywords: what `infer_requests` and
-    `SpanScheduler` call."""
+def _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend=False, want="float", watermark=None):
+    """`finish_requests` with one planned `WaveSpec` per request in place of its option keywords, and beside them one watermark key per
+    request (None: no request is marked): what `infer_requests` and `SpanScheduler` call."""
     _check_want(device_backend, want)
+    marks = [None] * len(specs) if watermark is None else list(watermark)
     fade = int(cross_fade_duration * target_sample_rate) if cross_fade_duration > 0 else 0
     out, on_device = [None] * len(specs), []
     for i, (waves, text, spec) in enumerate(zip(chunk_waves_per_request, gen_texts, specs)):
         script = isinstance(waves, SegmentedWaves)
         if isinstance(text, (list, tuple)):
-            if spec.needs_whole_wave():
-                raise ValueError(spec.whole_wave_message())
+            if spec.needs_whole_wave() or marks[i] is not None:
+                raise ValueError(_whole_wave_message(spec, marks[i]))
             out[i] = [[_host_chunk(w) for w in seg] for seg in waves] if script else [_host_chunk(w) for w in waves]
         elif script and device_backend and _script_on_device(waves, fade):
             on_device.append(i)
@@ -839,12 +892,13 @@ def _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs
             on_device.append(i)
             continue
         else:
-            out[i] = _finish_on_host(waves, text, cross_fade_duration, spec, want)
+            out[i] = _finish_on_host(waves, text, cross_fade_duration, spec, want, marks[i])
         backend_stats["host_requests"] += 1
     if on_device:
         # the plain requests first: their PCM is then one prefix of the packed buffer, and what comes down of it holds no other request's
         on_device.sort(key=lambda i: not specs[i].plain_format)
-        done = _finish_on_device([_device_request(chunk_waves_per_request[i]) for i in on_device], fade, [specs[i] for i in on_device])
+        done = _finish_on_device([_device_request(chunk_waves_per_request[i]) for i in on_device], fade, [specs[i] for i in on_device],
+                                 [marks[i] for i in on_device])
         for i, wave in zip(on_device, done):
             out[i] = wave
     return out
@@ -874,32 +928,37 @@ def _device_request(waves):
     return chunks, fades
 
 
-def finish_pcm16(pcm, spec) -> np.ndarray:
-    """What a `WaveSpec` makes of a request's 24 kHz int16 PCM, the one host definition (the device back-end and `StreamDelivery` are held
-    to it byte for byte): `remove_silence_pcm` when flagged, `shift_pcm16` (tempo and pitch), `normalise_loudness_pcm16`, `deliver_pcm16`."""
+def finish_pcm16(pcm, spec, watermark=None) -> np.ndarray:
+    """What a `WaveSpec`, and the `watermark` key beside it, make of a request's 24 kHz int16 PCM, the one host definition (the device
+    back-end and `StreamDelivery` are held to it byte for byte): `remove_silence_pcm` when flagged, `shift_pcm16` (tempo and pitch),
+    `mark_pcm16` with a key -- so the loudness and the -1 dBFS peak cap are measured on the marked samples, and the one gain behind it does
+    not disturb the scale-invariant detector --, `normalise_loudness_pcm16`, `deliver_pcm16`."""
     if spec.remove_silence:
         pcm = remove_silence_pcm(pcm, target_sample_rate)
     pcm = shift_pcm16(pcm, spec.tempo, spec.pitch)
+    pcm = mark_pcm16(pcm, watermark)
     pcm = normalise_loudness_pcm16(pcm, spec.loudness)
     return deliver_pcm16(pcm, *spec.format, flac_level=spec.flac_level if spec.flac else None)
 
 
-def _finish_on_host(waves, text, cross_fade_duration, spec, want):
+def _finish_on_host(waves, text, cross_fade_duration, spec, want, watermark=None):
     """`finish_requests` for one request on the host: join, quantisation where anything asks for PCM, `finish_pcm16`."""
     if isinstance(waves, SegmentedWaves):
         wave = join_segments([[_host_chunk(w) for w in seg] for seg in waves], cross_fade_duration, waves.gap_samples)
     else:
         wave = request_wave(text, [_host_chunk(w) for w in waves], cross_fade_duration)
-    if spec.needs_whole_wave():
-        return finish_pcm16(quantise_pcm16(wave), spec)
+    if spec.needs_whole_wave() or watermark is not None:
+        return finish_pcm16(quantise_pcm16(wave), spec, watermark)
     return quantise_pcm16(wave) if want == "pcm16" else wave   # (nothing to finish: no pass through the three steps' own checks)
 
 
-def _finish_on_device(requests, fade, specs):
+def _finish_on_device(requests, fade, specs, watermark=None):
     """`finish_requests` for the requests the device back-end takes: `requests` = (chunk waves (device tensors), fades: `_device_request`)
     and their `specs`, the plain-format ones first.  ONE `ops.wave_finish` call -- `ops.wave_finish_joins` when a script is among them --;
     directly behind it, when any request names a tempo or a pitch, ONE `ops.wave_prosody` call for the whole batch (the others are copied
     through), whose buffer, offsets, bounds and device lengths everything downstream reads in the place of `wave_finish`'s;
+    then, when any request has a key in `watermark` (one per request, None: nobody), ONE `ops.wave_mark` call that marks those in place
+    (carriers cached on the device: nothing is uploaded for a key seen before, and nothing comes back);
     then, when any request has a loudness target, ONE `ops.wave_loudness` call that normalises those in place; then on the
     same stream one `ops.wave_flac` call per distinct rate of the "flac" requests (behind a `wave_encode(..., "pcm16")` call where the rate
     is not 24 kHz; the requests of a rate share it through its per-request levels, and a call in which nobody asks for level 1 is the
@@ -926,6 +985,11 @@ def _finish_on_device(requests, fade, specs):
         pcm, lengths, offsets, joined = ops.wave_prosody(pcm, offsets, joined, lengths, [spec.stretch for spec in specs], [spec.pitch for spec in specs])
         backend_stats["prosody_calls"] += 1
         backend_stats["prosody_requests"] += sum(spec.prosody for spec in specs)
+    marks = [None] * len(specs) if watermark is None else list(watermark)
+    if any(key is not None for key in marks):   # in place, lengths still on the device: nothing comes back for it
+        ops.wave_mark(pcm, offsets, joined, lengths, marks)
+        backend_stats["mark_calls"] += 1
+        backend_stats["mark_requests"] += sum(key is not None for key in marks)
     targets = [spec.gain_constant for spec in specs]
     if any(t is not None for t in targets):   # in place, lengths still on the device: nothing comes back for it
         ops.wave_loudness(pcm, offsets, joined, lengths, targets)
@@ -1002,8 +1066,8 @@ class SpanTicket:
     """One admitted request of a `SpanScheduler`: its planned units, `spec` (`plan_request`'s `WaveSpec`: what the finished wave has to be),
     and -- once the units have all ended -- `result` (`request_wave`)."""
 
-    def __init__(self, request, voice, units, spec, parts=None, script=None):
-        self.request, self.voice, self.units, self.spec = request, voice, units, spec
+    def __init__(self, request, voice, units, spec, parts=None, script=None, watermark=None):
+        self.request, self.voice, self.units, self.spec, self.watermark = request, voice, units, spec, watermark
         self.parts = parts if parts is not None else [(voice, units)]   # [(voice, its units)]: one per segment of a script
         self.script = script
         self.in_flight = self.cancelled = self.done = False
@@ -1078,7 +1142,7 @@ class SpanScheduler:
                                                            sway_sampling_coef=opts["sway_sampling_coef"], generator=plan.generator, **extra)
                                   for tokens, frames in units]))
         plan.commit()   # every chunk was planned: the caller's generator moves
-        ticket = SpanTicket(request, plan.voice, [u for _, us in parts for u in us], plan.spec, parts, plan.script)
+        ticket = SpanTicket(request, plan.voice, [u for _, us in parts for u in us], plan.spec, parts, plan.script, plan.watermark)
         self.waiting.append(ticket)
         return ticket
 
@@ -1104,7 +1168,7 @@ class SpanScheduler:
         first = np.cumsum([0] + [len(t.parts) for t in tickets])
         chunk_waves = [request_chunk_waves(t, got[first[i]:first[i + 1]]) for i, t in enumerate(tickets)]
         results = _finish_specs(chunk_waves, [request_text(t.request) for t in tickets], self.cross_fade_duration, [t.spec for t in tickets],
-                                self.device_backend, "pcm16" if self.device_backend else "float")
+                                self.device_backend, "pcm16" if self.device_backend else "float", [t.watermark for t in tickets])
         for t, result in zip(tickets, results):
             t.result, t.done, t.in_flight = result, True, False
 

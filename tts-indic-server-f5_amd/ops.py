@@ -843,6 +843,95 @@ def wave_loudness(pcm, in_off, max_len, len_dev, gain_k):
     return stats
 
 
+def wave_mark_tile():
+    """Samples one block of `wave_mark`'s second launch owns (32 blocks of 240)."""
+    return int(_lib.lib().f5hip_wave_mark_tile())
+
+
+def watermark_carriers(keys, device):
+    """The carriers of `keys` as ONE int16 tensor [len(keys), 16384] on `device`, what `wave_mark` and `watermark_detect` hand to the
+    library.  Each distinct key's carrier (`wave_codec.watermark_carrier`) is uploaded once per device and kept (the last
+    `wave_codec.TAP_TABLE_CACHE`, like `_device_taps`); several keys are stacked on the device."""
+    from . import wave_codec
+    rows = [wave_codec._device_carrier(k, device) for k in keys]
+    return rows[0].reshape(1, -1) if len(rows) == 1 else torch.stack(rows)
+
+
+def _check_carriers(op, carriers, device):
+    from . import wave_codec
+    if not (torch.is_tensor(carriers) and carriers.dtype == torch.int16 and carriers.is_cuda and carriers.is_contiguous() and carriers.dim() == 2
+            and carriers.shape[1] == wave_codec.WATERMARK_PERIOD and 1 <= carriers.shape[0] <= wave_codec.WATERMARK_KEYS_MAX and carriers.device == device):
+        raise _lib.F5HipError(f"{op}: carriers must be a contiguous int16 tensor [1 .. {wave_codec.WATERMARK_KEYS_MAX}, {wave_codec.WATERMARK_PERIOD}] "
+                              "on the samples' device")
+
+
+def wave_mark(pcm, in_off, max_len, len_dev, keys):
+    """The provenance watermark of several finished requests in ONE library call and two launches (include/f5hip.h f5hip_wave_mark): their
+    24 kHz int16 PCM on the device, marked IN PLACE.  `pcm`: the int16 device tensor that holds every request (`wave_finish`'s or
+    `wave_prosody`'s buffer; request i starts at sample in_off[i]); `max_len`, `len_dev` as in `wave_encode`; `keys` [n]: each request's key
+    (`wave_codec.check_watermark`), None for a request that is left alone.  A call without a flagged request launches nothing.  Afterwards a
+    flagged request's samples are `wave_codec.mark_pcm16`'s, bit for bit; the others and the samples between requests keep their bits.
+    Returns `pcm`."""
+    from . import wave_codec
+    (pcm,), io, ml, n, len_dev = _pcm_requests("wave_mark", pcm, in_off, max_len, len_dev)
+    keys = list(keys)
+    if len(keys) != n:
+        raise _lib.F5HipError(f"wave_mark: keys needs one value per request ({n}), got {len(keys)}")
+    try:
+        keys = [wave_codec.check_watermark(k) for k in keys]
+    except ValueError as e:
+        raise _lib.F5HipError(f"wave_mark: {e}") from e
+    distinct = sorted({k for k in keys if k is not None})
+    if len(distinct) > wave_codec.WATERMARK_KEYS_MAX:
+        raise _lib.F5HipError(f"wave_mark: at most {wave_codec.WATERMARK_KEYS_MAX} distinct keys in a call (got {len(distinct)})")
+    ki = np.ascontiguousarray(np.asarray([-1 if k is None else distinct.index(k) for k in keys], dtype=np.int32))
+    carriers = watermark_carriers(distinct, pcm.device) if distinct else None
+    if torch_ops.load():
+        call_op("wave_mark", pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(ki), carriers)
+        return pcm
+    anchor, rel = _pcm_sources("wave_mark", [pcm], io, ml)
+    if int(ml.astype(np.int64).sum()) > 2 ** 31 - 1:
+        raise _lib.F5HipError("wave_mark: the call exceeds 2^31 - 1 samples")
+    if distinct and pcm.numel():
+        with torch.cuda.device(pcm.device):
+            _lib.check(_lib.lib().f5hip_wave_mark(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(ki), _p(carriers), len(distinct), _lib.current_stream_ptr()),
+                       "f5hip_wave_mark")
+    return pcm
+
+
+def watermark_detect(wave, offsets, lengths, carriers):
+    """Several clips scored against several keys in ONE library call and four launches (include/f5hip.h f5hip_watermark_detect):
+    `wave_codec.detect_watermark` of each clip in fp32.  wave: the contiguous 1-D fp32 device tensor that holds the clips (mono, 24 kHz) --
+    `ref_frontend`'s packed output as it stands --, read only; clip i is wave[offsets[i] : offsets[i] + lengths[i]], 1 to
+    `wave_codec.WATERMARK_MAX_SAMPLES` samples, disjoint ranges; `carriers`: `watermark_carriers(keys, device)`.  Returns scores, fp32 device
+    [n, n_keys, 4]: z, the offset, r at the offset and the deviation of r; a clip below `wave_codec.WATERMARK_MIN_SAMPLES` scores zeros.  A
+    clip's rows equal its own single-clip call's bit for bit."""
+    from . import wave_codec
+    ln = _per_request("watermark_detect", "lengths", lengths, np.int32, per="clip")
+    off = _per_request("watermark_detect", "offsets", offsets, np.int64, len(ln), per="clip")
+    if not (torch.is_tensor(wave) and wave.dtype == torch.float32 and wave.is_contiguous() and wave.is_cuda and wave.dim() == 1):
+        raise _lib.F5HipError("watermark_detect: wave must be a contiguous 1-D fp32 tensor on the HIP device")
+    _check_carriers("watermark_detect", carriers, wave.device)
+    if torch_ops.load():
+        return call_op("watermark_detect", wave, torch.from_numpy(off), torch.from_numpy(ln), carriers)
+    for i in range(len(ln)):
+        if ln[i] < 1 or ln[i] > wave_codec.WATERMARK_MAX_SAMPLES:
+            raise _lib.F5HipError(f"watermark_detect: clip {i} has {ln[i]} samples (1 .. {wave_codec.WATERMARK_MAX_SAMPLES})")
+        if off[i] < 0 or int(off[i]) + int(ln[i]) > wave.numel():
+            raise _lib.F5HipError(f"watermark_detect: clip {i} is samples [{off[i]}, {int(off[i]) + int(ln[i])}) of a tensor of {wave.numel()}")
+    with torch.cuda.device(wave.device):
+        scores = torch.empty(len(ln), carriers.shape[0], 4, device=wave.device, dtype=torch.float32)
+        _lib.check(_lib.lib().f5hip_watermark_detect(len(ln), _p(wave), _p(off), _p(ln), carriers.shape[0], _p(carriers), _p(scores), _lib.current_stream_ptr()),
+                   "f5hip_watermark_detect")
+    return scores
+
+
+def watermark_scores(rows, keys) -> list:
+    """`wave_codec.WatermarkScore`s of one clip's downloaded score rows [n_keys, 4]."""
+    from . import wave_codec
+    return [wave_codec.WatermarkScore(k, float(z), int(o), bool(z >= wave_codec.WATERMARK_THRESHOLD)) for k, (z, o, _, _) in zip(keys, rows.tolist())]
+
+
 def flac_decode_packed(buffer, spans, device=None):
     """`flac_decode` of streams that already lie in one byte buffer: `spans[i] = (first, last + 1)` byte of stream i ("fLaC" included), in
     ascending order and not overlapping; whatever lies between them is not looked at."""

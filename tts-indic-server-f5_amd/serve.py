@@ -51,6 +51,7 @@ log = logging.getLogger(__name__)
 EDIT_OPTIONS = ("nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "flac_level")   # a speech edit has no `speed`: its durations are planned
 # the delivery options an edit takes, in the order the routes check them (`infer.REQUEST_OPTIONS`'): all but `remove_silence`, the recording keeps its pauses
 EDIT_DELIVERY = tuple(k for k in infer.REQUEST_OPTIONS if k in infer.DELIVERY_OPTIONS and k != "remove_silence")
+EDIT_MARK = infer.WATERMARK_OPTIONS   # beside them: the whole returned recording is marked (`infer.mark_pcm16`), on the host, as the route finishes
 # most ODE steps one library call accepts per method: 128 time points (f5hip precompute_time); midpoint uses 2 per step, RK4 3 per step + 1
 MAX_NFE_STEP = {"euler": 128, "midpoint": 64, "rk4": 42}
 
@@ -63,7 +64,7 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
     The delivery options by `infer.WaveSpec`'s validators, one by one and then together (a `flac_level` beside another encoding is refused,
     never ignored; a `tempo` and a `pitch` whose combined stretch leaves 1/2 .. 2 likewise); `remove_silence` must be a bool, and `flac_level`
     is not "1".  What a request gets anyway -- False, 24000, "pcm16", level 0, tempo 1.0, pitch 0 -- is dropped like None: the request is
-    then what it is without the option."""
+    then what it is without the option.  `watermark` by `infer.check_watermark`: an integer key from 1 to 2^48 - 1."""
     out = {}
     own = options.get("ode_method") if "ode_method" in allowed else None
     if own is not None:
@@ -100,6 +101,8 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
             v = infer.check_pitch(v)                    # ValueError: "pitch must be a whole number of semitones ..."
             if v == 0:
                 continue
+        elif k == "watermark":
+            v = infer.check_watermark(v)                # ValueError: "watermark must be an integer key ..."
         elif k in ("nfe_step", "seed"):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"{k} must be an integer (got {v!r})")
@@ -144,6 +147,8 @@ DEVICE_PRESTEP_DEFAULT = False
 STREAM_REMOVE_SILENCE = "remove_silence needs the request's whole wave: it is not available on a streaming path"
 STREAM_LOUDNESS = "loudness is measured on the request's whole wave: it is not available on a streaming path"
 STREAM_PROSODY = "tempo and pitch are applied to the request's whole wave: they are not available on a streaming path"
+STREAM_WATERMARK = "watermark marks the request's whole wave: it is not available on a streaming path"
+MARKED_REFERENCE = infer.MARKED_REFERENCE   # "the reference clip carries this service's watermark": `TTSManager(reject_marked=...)`
 
 
 def stream_refusal(opts):
@@ -153,7 +158,9 @@ def stream_refusal(opts):
         return None
     if opts.get("remove_silence"):
         return STREAM_REMOVE_SILENCE
-    return STREAM_LOUDNESS if opts.get("loudness") is not None else STREAM_PROSODY
+    if opts.get("loudness") is not None:
+        return STREAM_LOUDNESS
+    return STREAM_PROSODY if infer.WaveSpec.of(opts).prosody else STREAM_WATERMARK
 
 
 @dataclass
@@ -432,8 +439,15 @@ class TTSManager:
     def __init__(self, loader: Callable[[], tuple] | None = None, nfe_step: int = infer.nfe_step, cfg_strength: float = infer.cfg_strength,
                  sway_sampling_coef: float = infer.sway_sampling_coef, speed: float = infer.speed, mel_spec_type: str = "vocos",
                  micro_batch: dict | None = None, batch_invariant: bool = True, clip_cache: int = 64, device_frontend: bool | None = None,
-                 device_backend: bool | None = None, device_decode: bool | None = None, device_prestep: bool | None = None):
+                 device_backend: bool | None = None, device_decode: bool | None = None, device_prestep: bool | None = None,
+                 watermark: int | None = None, reject_marked=None):
         self.loader = loader
+        # The key (`infer.check_watermark`) every finished wave is marked with unless its request names its own; None: no mark.  A mark needs
+        # the whole wave, so with a key here the streaming paths are refused (`STREAM_WATERMARK`) rather than left unmarked.
+        self.watermark = infer.check_watermark(watermark)
+        # Keys (1 .. 16, or one) whose mark an uploaded reference clip must not carry: a new upload whose prepared 24 kHz wave scores at or
+        # above `infer.WATERMARK_THRESHOLD` for any of them is refused (`MARKED_REFERENCE`) before it is denoised, cached or queued.  None: no check
+        self.reject_marked = None if reject_marked is None else tuple(infer.check_watermark_keys(reject_marked))
         self.batch_invariant = batch_invariant   # False: leave the model's attention mode alone (fastest kernel per launch shape)
         self.micro_batch = micro_batch            # e.g. dict(max_requests=16, max_wait_ms=5): batch concurrent requests; with span_steps
         #                                           (dict(span_steps=8, max_frames=32768); span_steps=None: infer.span_steps) requests join a
@@ -482,7 +496,10 @@ class TTSManager:
 
     def request_options(self, allowed=infer.REQUEST_OPTIONS, **options) -> dict:
         """`check_request_options` for this manager's solver: the options a request sets (absent / None ones fall back to `self.opts`)."""
-        return check_request_options(options, self.ode_method, allowed)
+        out = check_request_options(options, self.ode_method, allowed)
+        if self.watermark is not None and "watermark" in allowed:
+            out.setdefault("watermark", self.watermark)   # the manager's key for a request that names none
+        return out
 
     def load(self, model_obj=None, vocoder=None):
         """Attach the sampler / vocoder objects (F5HipModel, F5HipVocos | F5HipBigVGAN), or build them with `loader`."""
@@ -672,11 +689,22 @@ class TTSManager:
                         raise ValueError("Invalid audio: the clip is empty or silent.")
                     for (key, _), planes in zip(group, ops.ref_prestep_planes(packed, lengths, channels)):
                         clips[key] = (planes, sr)
+            fresh = []
             for key in new:
                 clip = clips[key]
                 if clip[1] != infer.target_sample_rate:
                     infer.resample_taps(clip[1], infer.target_sample_rate)      # refuses a rate pair it has no table for
-                voice = infer.PreparedVoice.deferred(clip, denoise=key[3]) if self.device_frontend else infer.PreparedVoice(clip, denoise=key[3])
+                if self.device_frontend:
+                    voice = infer.PreparedVoice.deferred(clip, denoise=key[3], reject_marked=self.reject_marked)
+                else:
+                    voice = infer.PreparedVoice(clip, denoise=key[3], reject_marked=self.reject_marked)   # (scored here, before the denoiser)
+                fresh.append((key, voice))
+            if self.reject_marked is not None and any(voice.pending is not None for _, voice in fresh):
+                # the new uploads' front-end now, under the device lock: ONE `ops.watermark_detect` call per front-end call scores them on its
+                # device buffer (`infer.prepare_voices`), and a marked clip is refused here -- before it is cached or anything is queued
+                with self._device_lock:
+                    infer._prepare_deferred([voice for _, voice in fresh], self.model_obj)
+            for key, voice in fresh:
                 value = (voice, audio_prep.normalize_ref_text(key[1]))
                 with self._clip_lock:
                     self._clip_cache[key] = value
@@ -761,7 +789,7 @@ class TTSManager:
 
     def _stream(self, voice, ref_text, head, tail, opts=None):
         spec = infer.WaveSpec.of(opts or {})   # the delivery format is applied here, piece by piece: the head and tail requests stay plain
-        opts = {k: v for k, v in (opts or {}).items() if k not in infer.DELIVERY_OPTIONS + infer.PROSODY_OPTIONS}
+        opts = {k: v for k, v in (opts or {}).items() if k not in infer.DELIVERY_OPTIONS + infer.PROSODY_OPTIONS + infer.WATERMARK_OPTIONS}
         return self._stream_requests(self._request(voice, ref_text, head, opts), self._request(voice, ref_text, tail, opts) if tail else None, spec)
 
     def _stream_requests(self, head_request, tail_request, spec, tail_pieces=None):
@@ -900,7 +928,7 @@ class TTSManager:
         if "seed" in opts:
             opts["generator"] = infer.request_generator(opts.pop("seed"))
         spec = infer.WaveSpec.of(opts)            # (applied to the pieces, as in `_stream`)
-        opts = {k: v for k, v in opts.items() if k not in infer.DELIVERY_OPTIONS + infer.PROSODY_OPTIONS}
+        opts = {k: v for k, v in opts.items() if k not in infer.DELIVERY_OPTIONS + infer.PROSODY_OPTIONS + infer.WATERMARK_OPTIONS}
         chunked = [(voice, ref_text, infer.request_chunks(ref_text, voice.seconds, piece), speed) for voice, ref_text, piece, speed in segments]
         voice, ref_text, chunks, speed = chunked[0]
         head = self._request(voice, ref_text, chunks[:1], dict(opts, speed=speed) if speed is not None else opts)
@@ -919,17 +947,19 @@ class TTSManager:
         return self._stream_requests(head, infer.ScriptRequest(rest, opts, gap) if rest else None, spec, tail_pieces)
 
     def edit(self, audio, target_text, parts_to_edit, fix_duration=None, *, nfe_step=None, cfg_strength=None, sway_sampling_coef=None,
-             seed=None, ode_method=None, sample_rate=None, encoding=None, loudness=None, flac_level=None):
+             seed=None, ode_method=None, sample_rate=None, encoding=None, loudness=None, flac_level=None, watermark=None):
         """Speech editing (`infer.speech_edit`, F/infer/speech_edit.py): regenerate `parts_to_edit` of the recording `audio` (a path, WAV
         bytes or a (tensor, sr) pair) so that it speaks `target_text`, with this manager's sampler settings unless the call sets its own
         (`seed`: the edit's noise from its own generator; `ode_method`: the edit's solver, handed on only when set).  The host preparation runs outside the device lock, the sampler and vocoder
         under it (not through the micro-batcher); with a `ShardedSampler` on rank 0's own model.  Returns the wave (float32, 24 kHz) -- with
-        any of `sample_rate`, `encoding`, `loudness` and `flac_level` (`infer.WaveSpec`), `infer.finish_pcm16` of its int16 PCM on the host."""
+        any of `sample_rate`, `encoding`, `loudness` and `flac_level` (`infer.WaveSpec`), or with a `watermark` key (the manager's unless the
+        call names one: the whole returned recording is marked, kept parts included), `infer.finish_pcm16` of its int16 PCM on the host."""
         if not self.model:
             raise ValueError("TTS model not loaded")
         opts = dict(self.opts, **self.request_options(EDIT_OPTIONS, nfe_step=nfe_step, cfg_strength=cfg_strength,
                                                       sway_sampling_coef=sway_sampling_coef, seed=seed, ode_method=ode_method))
         delivery = self.request_options(EDIT_DELIVERY, sample_rate=sample_rate, encoding=encoding, flac_level=flac_level, loudness=loudness)
+        mark = self.request_options(EDIT_MARK, watermark=watermark).get("watermark")
         model_obj = getattr(self.model_obj, "local", self.model_obj)
         # host work (read, mono mix, resample, plan, tokens) and every rejection happen before the device lock is taken (a FLAC recording is
         # decoded under it with `device_decode`, after everything that needs no samples has been refused)
@@ -944,7 +974,31 @@ class TTSManager:
                                                     nfe_step=opts["nfe_step"], cfg_strength=opts["cfg_strength"],
                                                     sway_sampling_coef=opts["sway_sampling_coef"], **extra)
         wave = np.asarray(wave, dtype=np.float32)
-        return infer.finish_pcm16(infer.quantise_pcm16(wave), infer.WaveSpec.of(delivery)) if delivery else wave
+        if not delivery and mark is None:
+            return wave
+        return infer.finish_pcm16(infer.quantise_pcm16(wave), infer.WaveSpec.of(delivery), mark)
+
+    def detect_watermark(self, audio, keys=None) -> list:
+        """Whether a recording carries a mark: one `infer.WatermarkScore(key, z, offset, detected)` per key for `audio` -- a path, WAV or FLAC
+        bytes, or a (wave [ch, n], sr) pair --, read the way a reference upload is read: `decode_audio`, mono mix, sinc resampling to 24 kHz
+        (`infer.resample_sinc_hann`).  `keys`: 1 to 16 keys; None: this manager's own `watermark`.  ValueError when neither is given, for a bad
+        key and for audio that cannot be read.  Host arithmetic in fp64 (`infer.detect_watermark`)."""
+        import torch
+        if keys is None:
+            if self.watermark is None:
+                raise ValueError("detect_watermark needs keys: this manager has no watermark key of its own")
+            keys = [self.watermark]
+        keys = infer.check_watermark_keys(keys)
+        wave, sr = audio if isinstance(audio, tuple) else self.decode_audio(audio)
+        wave = torch.as_tensor(wave, dtype=torch.float32)
+        if wave.dim() == 1:
+            wave = wave[None]
+        if wave.dim() != 2 or wave.shape[0] < 1:
+            raise ValueError(f"Invalid audio: expected [channels, samples] (got {tuple(wave.shape)})")
+        mono = wave.mean(dim=0, keepdim=True)
+        if int(sr) != infer.target_sample_rate:
+            mono = infer.resample_sinc_hann(mono, int(sr), infer.target_sample_rate)
+        return infer.detect_watermark(mono[0].numpy(), keys)
 
 
 class HTTPError(Exception):
@@ -1036,6 +1090,7 @@ def request_models():
         remove_silence: bool | None = None
         tempo: typing.Any = None                     # 0.5 to 2 in steps of 0.01: the duration divided by it, the pitch kept (infer.shift_pcm16); untyped like flac_level
         pitch: typing.Any = None                     # whole semitones, -6 to 6, the duration kept; untyped, so that true and 2.0 arrive as sent and are refused
+        watermark: typing.Any = None                 # the key of a provenance mark, 1 to 2^48 - 1 (infer.mark_pcm16); untyped, so that true, 1.0 and "1" are refused
 
     class KannadaSynthesizeRequest(SpeechFields):    # S/utils/tts_utils.py:27-28
         text: str
@@ -1053,6 +1108,7 @@ def request_models():
         parts_to_edit: list[list[float]]
         fix_duration: list[float] | None = None
         denoise: typing.Any = None                   # not an option of this route (an edit keeps the recording): anything but an absent field is a 400
+        watermark: typing.Any = None                 # the key of a provenance mark on the whole returned recording (serve.EDIT_MARK)
 
     class CloneRequest(SpeechFields):                # zero-shot cloning from the caller's own clip; JSON (base64 WAV), not multipart
         text: str
@@ -1076,8 +1132,12 @@ def request_models():
         gap: float = 0.0
         stream: bool = False
 
+    class DetectRequest(BaseModel):                  # `/v1/audio/watermark/detect`: a recording (base64 WAV or FLAC) and the keys to score it against
+        audio: str
+        keys: typing.Any = None                      # 1 to 16 keys; absent: the manager's own.  Untyped, so that a bad key arrives as sent and is refused
+
     return types.SimpleNamespace(KannadaSynthesizeRequest=KannadaSynthesizeRequest, SynthesizeRequest=SynthesizeRequest, CloneRequest=CloneRequest,
-                                 EditRequest=EditRequest, ScriptRequest=ScriptRequest, ScriptVoice=ScriptVoice)
+                                 EditRequest=EditRequest, ScriptRequest=ScriptRequest, ScriptVoice=ScriptVoice, DetectRequest=DetectRequest)
 
 
 def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
@@ -1097,7 +1157,9 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     `loudness` as `infer.WaveSpec` describes them (a bad value or combination is a 400; `loudness` is measured on the whole wave, so it is
     a 400 together with `"stream": true`: `STREAM_LOUDNESS`), the speech routes also `tempo` (0.5 to 2: the duration divided by it, the pitch
     kept) and `pitch` (whole semitones, -6 to 6, the duration kept), applied to the finished wave (`infer.shift_pcm16`; 400 together with
-    `"stream": true`: `STREAM_PROSODY`; not on the edit route, which keeps the recording's timing), and `response_format` ("wav", or "pcm" for the headerless samples / code bytes
+    `"stream": true`: `STREAM_PROSODY`; not on the edit route, which keeps the recording's timing), every route `watermark` (a key, 1 to 2^48 - 1: the finished wave
+    carries that key's provenance mark, `infer.mark_pcm16`; a bad key is a 400, and so is the option together with `"stream": true`:
+    `STREAM_WATERMARK`; `/v1/audio/watermark/detect` scores a recording against keys), and `response_format` ("wav", or "pcm" for the headerless samples / code bytes
     as `audio/pcm`); streamed or not, the body's samples are the same bytes.  `encoding: "flac"` is its own container: the body is the
     native FLAC stream as `audio/flac` with a `.flac` file name, and `response_format` must be absent (400 with "wav" or "pcm" beside it);
     streamed, the stream header comes with the totals unknown."""
@@ -1247,7 +1309,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     def _run_edit(req):
         if not tts_manager.model:
             raise HTTPException(status_code=503, detail="TTS model not loaded")
-        opts = _options(req, tuple(dict.fromkeys(EDIT_OPTIONS + EDIT_DELIVERY)))
+        opts = _options(req, tuple(dict.fromkeys(EDIT_OPTIONS + EDIT_DELIVERY + EDIT_MARK)))
         if req.denoise is not None:
             raise HTTPException(status_code=400, detail="denoise is an option of an uploaded reference clip: the edit route keeps the recording")
         fmt = _response_format(req, opts)
@@ -1266,6 +1328,24 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
         return StreamingResponse(_blocks(response_body(wave, opts, fmt)), media_type=MEDIA_TYPES[fmt], headers=_headers("edited_speech.wav", fmt))
+
+    def _run_detect(req):
+        """`/v1/audio/watermark/detect`: {"audio": base64 WAV or FLAC, "keys"?: [1 .. 16 keys]} -> {"results": [{"key", "detected", "score",
+        "offset"}]}, one per key (`TTSManager.detect_watermark`; no key in the body: the manager's own).  Needs no loaded model."""
+        try:
+            raw = base64.b64decode(req.audio, validate=True)
+        except (binascii.Error, ValueError):
+            raise HTTPException(status_code=400, detail="Audio must be a base64-encoded WAV or FLAC file.")
+        try:
+            keys = None if req.keys is None else infer.check_watermark_keys(req.keys)   # (before the recording is decoded)
+            try:
+                audio = tts_manager.decode_audio(raw)
+            except ValueError as e:
+                raise ValueError(f"Invalid audio: {e}") from e
+            scores = tts_manager.detect_watermark(audio, keys)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        return {"results": [dict(key=s.key, detected=s.detected, score=s.z, offset=s.offset) for s in scores]}
 
     # The reference's handlers are `async def` around a blocking call, i.e. one request at a time.  Here the blocking part runs in
     # starlette's thread pool, so concurrent requests overlap and meet in the MicroBatcher queue (when the manager has one).
@@ -1292,6 +1372,10 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     @router.post("/audio/edit", response_class=StreamingResponse)
     async def edit_speech(request: models.EditRequest):                    # speech editing (F/infer/speech_edit.py) over the same manager
         return await run_in_threadpool(_run_edit, request)
+
+    @router.post("/audio/watermark/detect")
+    async def detect_watermark(request: models.DetectRequest):            # provenance: does this recording carry a key's mark?
+        return await run_in_threadpool(_run_detect, request)
 
     app = FastAPI(title="F5-TTS on MI355X (HIP path)")
     app.include_router(router)

@@ -3,7 +3,7 @@
 `StreamResampler`), the BS.1770 loudness meter and normaliser (`measure_loudness`, `normalise_loudness_pcm16`), G.711 (`encode_g711`,
 `decode_g711`), FLAC (`encode_flac`, `decode_flac`, `StreamFlacEncoder`; the whole format in: `read_flac`, `load_audio`), the delivery
 format of a request (`delivery_format`, `deliver_pcm16`), time-scale modification of finished PCM (`wsola_pcm16`, `shift_pcm16`: a request's
-`tempo` and `pitch`), its five delivery and two prosody options as one value (`WaveSpec`; `StreamDelivery` applies it to a stream) and the bytes of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
+`tempo` and `pitch`), the provenance watermark (`mark_pcm16`, `detect_watermark`: a request's `watermark` key), its five delivery and two prosody options as one value (`WaveSpec`; `StreamDelivery` applies it to a stream) and the bytes of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
 round; `infer` and `serve` hand every public name on (`infer.load_wav`, `serve.wav_bytes`, ...)."""
 from __future__ import annotations
 
@@ -753,6 +753,199 @@ def shifted_length(n, stretch, pitch) -> int:
         p, q = PITCH_RATIOS[pitch]
         m = -(-q * m // p)
     return m
+
+
+# ----------------------------------------- provenance watermark: a request's `watermark` option (a key) adds a keyed, speech-shaped,
+# spread-spectrum mark to its 24 kHz int16 PCM; `detect_watermark` scores a clip against keys.  The mark is integers only, so the device
+# call (csrc/wave_mark.h, f5hip_wave_mark) is held to `mark_pcm16` bit for bit; the detector is floating point and scale-invariant.
+#   constants  WATERMARK_PERIOD P = 16384 chips (0.68 s), WATERMARK_BLOCK = 240 (10 ms), WATERMARK_TAPS = 129, WATERMARK_SHIFT = 23,
+#              WATERMARK_BAND = (22, 136): STFT bins of 1024 at 24 kHz, 516 to 3188 Hz
+#   key        an int in 1 .. 2^48 - 1 (`check_watermark`)
+#   chips      SplitMix64 with state `key`: state += 0x9E3779B97F4A7C15; z = state; z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;
+#              z = (z ^ z >> 27) 0x94D049BB133111EB; z ^= z >> 31, all mod 2^64.  Bit i of output k is chip 64 k + i: +1 set, -1 clear
+#   band taps  g[k] = rint(2^14 hann[k] (2 f1 sinc(2 f1 (k - 64)) - 2 f0 sinc(2 f0 (k - 64)))), f1 = 3200/24000, f0 = 500/24000, hann[k] =
+#              0.5 - 0.5 cos(2 pi (k + 1) / 130), in fp64 (csrc/watermark_taps.inc holds the 129 integers; a test equates the two, so no
+#              libm decides a sample); sum |g| = 34684
+#   carrier    c[m] = (sum_k g[k] chip[(m - k + 64) mod P]) >> 3, a floor shift: |c| <= 4336 for any chips, int16
+#   mark       A[b] = sum |x[j]| over block b (240 samples, the last one may be partial); E[b] = max(A[b-1], A[b], A[b+1]), a missing
+#              neighbour counting 0; y[j] = clip(x[j] + ((E[j // 240] c[j mod P]) >> 23), -32768, 32767): 64-bit product, floor shift.
+#              E <= 240 * 32768 = 2^23 * 0.9375, so |y - x| <= 4336 * 0.9375 = 4065 for any chips, and <= 4064 for every carrier whose
+#              magnitude stays below 4335 (key 1: -2863 .. 3113); output block b depends on input blocks b-1 .. b+1 only
+#   detect     frames of 1024 at hop 256 behind 768 zeros, window w[i] = sin(pi i / 1024), F = ceil((n + 768) / 256) frames, zeros behind
+#              (`audio_prep.denoise_reference`'s framing); X = rfft(frame w); U[k] = X[k] / sqrt(|X[k]|^2 + 1e-10) inside the band, 0
+#              outside; u = overlap-add of irfft(U) w, cropped to the clip; Z[m] = sum of u[j] over j = m mod P; r[o] = sum_m Z[m]
+#              c[(m + o) mod P]; o* the smallest argmax; z = (r[o*] - mean r) / std r (population), 0 when std r = 0; detected = z >= 7.0.
+#              Sample 0 of the clip was sample o* (mod P) of the marked wave.
+# Threshold: r across offsets is close to Gaussian with about P 2.7 / 12 = 3700 independent values, so 7.0 gives about 5e-9 false alarms
+# per (clip, key).
+WATERMARK_PERIOD = 16384
+WATERMARK_BLOCK = 240
+WATERMARK_TAPS = 129
+WATERMARK_SHIFT = 23
+WATERMARK_BAND = (22, 136)
+WATERMARK_THRESHOLD = 7.0
+WATERMARK_MIN_SAMPLES = 12000
+WATERMARK_MAX_SAMPLES = 1_440_000
+WATERMARK_KEYS_MAX = 16
+WATERMARK_KEY_MAX = (1 << 48) - 1
+WATERMARK_OPTIONS = ("watermark",)                # beside DELIVERY_OPTIONS and PROSODY_OPTIONS; carried next to the WaveSpec, not in it
+WHOLE_WAVE_WATERMARK = ("watermark marks the request's whole wave: it is not available for a list of chunk texts, on a streaming path or "
+                        "with join=False")
+WatermarkScore = collections.namedtuple("WatermarkScore", "key z offset detected")
+_watermark_taps = None
+_watermark_carriers: collections.OrderedDict = collections.OrderedDict()   # key -> carrier; the last TAP_TABLE_CACHE keys: a request chooses its key
+_carriers_on_device: collections.OrderedDict = collections.OrderedDict()   # (key, device) -> the carrier there
+_M64 = (1 << 64) - 1
+
+
+def check_watermark(key):
+    """A request's `watermark` option: None (absent) stays None; an int in 1 .. 2^48 - 1 is the key; a bool, a float, a string and any
+    other value are a ValueError."""
+    if key is None:
+        return None
+    if isinstance(key, (bool, np.bool_)) or not isinstance(key, (int, np.integer)) or not 1 <= int(key) <= WATERMARK_KEY_MAX:
+        raise ValueError(f"watermark must be an integer key from 1 to 2^48 - 1 (got {key!r})")
+    return int(key)
+
+
+def check_watermark_keys(keys) -> list:
+    """The keys a clip is scored against: 1 .. WATERMARK_KEYS_MAX of them, each by `check_watermark` (one key may stand for its list)."""
+    if isinstance(keys, (int, np.integer)) and not isinstance(keys, (bool, np.bool_)):
+        keys = [keys]
+    if not isinstance(keys, (list, tuple)) or not 1 <= len(keys) <= WATERMARK_KEYS_MAX or any(k is None for k in keys):
+        raise ValueError(f"watermark keys must be a list of 1 to {WATERMARK_KEYS_MAX} keys (got {keys!r})")
+    return [check_watermark(k) for k in keys]
+
+
+def splitmix64(state: int):
+    """(next state, output) of one SplitMix64 step."""
+    state = (state + 0x9E3779B97F4A7C15) & _M64
+    z = state
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return state, z ^ (z >> 31)
+
+
+def watermark_chips(key) -> np.ndarray:
+    """The key's chips, int64 [WATERMARK_PERIOD] of +1 / -1."""
+    state, words = check_watermark(key), []
+    if state is None:
+        raise ValueError("watermark_chips: a key is needed")
+    for _ in range(WATERMARK_PERIOD // 64):
+        state, z = splitmix64(state)
+        words.append(z)
+    bits = (np.asarray(words, dtype=np.uint64)[:, None] >> np.arange(64, dtype=np.uint64)[None]) & np.uint64(1)
+    return bits.reshape(-1).astype(np.int64) * 2 - 1
+
+
+def watermark_taps() -> np.ndarray:
+    """The band taps g, int64 [WATERMARK_TAPS] (read-only)."""
+    global _watermark_taps
+    if _watermark_taps is None:
+        k = np.arange(WATERMARK_TAPS, dtype=np.float64)
+        half = WATERMARK_TAPS // 2
+        hann = 0.5 - 0.5 * np.cos(2.0 * np.pi * (k + 1.0) / (WATERMARK_TAPS + 1.0))
+        hi, lo = 2.0 * 3200.0 / SAMPLE_RATE, 2.0 * 500.0 / SAMPLE_RATE
+        g = np.rint(2.0 ** 14 * hann * (hi * np.sinc(hi * (k - half)) - lo * np.sinc(lo * (k - half)))).astype(np.int64)
+        g.setflags(write=False)
+        _watermark_taps = g
+    return _watermark_taps
+
+
+def watermark_carrier(key) -> np.ndarray:
+    """The key's carrier c, int16 [WATERMARK_PERIOD] (read-only): its chips through the band taps, circularly.  The last
+    TAP_TABLE_CACHE keys are kept."""
+    key = check_watermark(key)
+    hit = _lru_get(_watermark_carriers, key)
+    if hit is None:
+        chips, g, half = watermark_chips(key), watermark_taps(), WATERMARK_TAPS // 2
+        ext = np.concatenate([chips[-half:], chips, chips[:half]])                   # ext[i] = chip[(i - 64) mod P]
+        # c[m] = sum_k g[k] chip[m - k + 64] = sum_k g[k] ext[m + 128 - k]: a full convolution's samples 128 .. 128 + P - 1
+        hit = (np.convolve(ext, g)[WATERMARK_TAPS - 1:WATERMARK_TAPS - 1 + WATERMARK_PERIOD] >> 3).astype(np.int16)
+        hit.setflags(write=False)
+        _lru_put(_watermark_carriers, key, hit)
+    return hit
+
+
+def _device_carrier(key, device):
+    key = (check_watermark(key), str(device))
+    hit = _lru_get(_carriers_on_device, key)
+    return hit if hit is not None else _lru_put(_carriers_on_device, key, torch.from_numpy(watermark_carrier(key[0]).copy()).to(device))
+
+
+def mark_pcm16(pcm, key) -> np.ndarray:
+    """24 kHz int16 PCM [n] with the key's mark added, by the definition above: integers only, the length kept, silence left silent.
+    `key=None` returns the array itself.  What `ops.wave_mark` equals byte for byte."""
+    pcm, key = _as_pcm16(pcm), check_watermark(key)
+    if key is None or not len(pcm):
+        return pcm
+    n, B = len(pcm), WATERMARK_BLOCK
+    x = pcm.astype(np.int64)
+    A = np.add.reduceat(np.abs(x), np.arange(0, n, B))
+    Ap = np.concatenate([[0], A, [0]])
+    E = np.maximum(np.maximum(Ap[:-2], Ap[1:-1]), Ap[2:])
+    j = np.arange(n)
+    c = watermark_carrier(key).astype(np.int64)
+    return np.clip(x + ((E[j // B] * c[j % WATERMARK_PERIOD]) >> WATERMARK_SHIFT), -32768, 32767).astype(np.int16)
+
+
+def _watermark_samples(wave) -> np.ndarray:
+    """A clip as the detector reads it: fp64 [n], int16 scaled by 1 / 32768, only the first WATERMARK_MAX_SAMPLES samples."""
+    if torch.is_tensor(wave):
+        wave = wave.detach().cpu().numpy()
+    wave = np.asarray(wave)
+    if wave.dtype == np.int16:
+        x = wave.reshape(-1)[:WATERMARK_MAX_SAMPLES].astype(np.float64) / 32768.0
+    elif np.issubdtype(wave.dtype, np.floating):
+        x = wave.reshape(-1)[:WATERMARK_MAX_SAMPLES].astype(np.float64)
+    else:
+        raise ValueError(f"detect_watermark: the clip is int16 PCM or floating-point samples (got {wave.dtype})")
+    if not np.isfinite(x).all():
+        raise ValueError("detect_watermark: the clip has a sample that is not finite")
+    return x
+
+
+def watermark_fold(wave) -> np.ndarray:
+    """Z of the definition above, fp64 [WATERMARK_PERIOD]: the clip's whitened band, folded by the period."""
+    x = _watermark_samples(wave)
+    n, N, H, pad = len(x), 1024, 256, 768
+    F = -(-(n + pad) // H)
+    w = np.sin(np.pi * np.arange(N) / N)
+    xp = np.zeros(H * (F - 1) + N)
+    xp[pad:pad + n] = x
+    X = np.fft.rfft(np.lib.stride_tricks.sliding_window_view(xp, N)[::H] * w, axis=1)
+    U = np.zeros_like(X)
+    lo, hi = WATERMARK_BAND
+    band = X[:, lo:hi + 1]
+    U[:, lo:hi + 1] = band / np.sqrt(band.real ** 2 + band.imag ** 2 + 1e-10)
+    y = np.fft.irfft(U, n=N, axis=1) * w
+    u = np.zeros_like(xp)
+    for m in range(F):
+        u[H * m:H * m + N] += y[m]
+    u = u[pad:pad + n]
+    Z = np.zeros(-(-n // WATERMARK_PERIOD) * WATERMARK_PERIOD)
+    Z[:n] = u
+    return Z.reshape(-1, WATERMARK_PERIOD).sum(axis=0)
+
+
+def watermark_score(r, key) -> WatermarkScore:
+    """The score of a key from its correlation r [WATERMARK_PERIOD] over the offsets."""
+    o = int(np.argmax(r))                       # the smallest argmax
+    sigma = float(np.std(r))
+    z = (float(r[o]) - float(np.mean(r))) / sigma if sigma > 0 else 0.0
+    return WatermarkScore(key, z, o, bool(z >= WATERMARK_THRESHOLD))
+
+
+def detect_watermark(wave, keys) -> list:
+    """One `WatermarkScore(key, z, offset, detected)` per key for a mono 24 kHz clip, int16 PCM or float samples (scored in fp64), by the
+    definition above; a clip below WATERMARK_MIN_SAMPLES scores z = 0 and is not detected.  The correlation over all offsets is formed
+    with fp64 FFTs."""
+    keys = check_watermark_keys(keys)
+    x = _watermark_samples(wave)
+    if len(x) < WATERMARK_MIN_SAMPLES:
+        return [WatermarkScore(k, 0.0, 0, False) for k in keys]
+    FZ = np.conj(np.fft.rfft(watermark_fold(x)))
+    return [watermark_score(np.fft.irfft(FZ * np.fft.rfft(watermark_carrier(k).astype(np.float64)), n=WATERMARK_PERIOD), k) for k in keys]
 
 
 _G711_TAGS = {"mulaw": 7, "alaw": 6}   # WAVE_FORMAT_MULAW, WAVE_FORMAT_ALAW
