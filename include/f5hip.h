@@ -813,6 +813,34 @@ int f5hip_watermark_detect(int32_t n, const float* wave_dev, const int64_t* offs
 /* Kernels one f5hip_watermark_detect call launches (4). */
 int f5hip_watermark_detect_launches(void);
 
+/* Reference-clip report: is an uploaded clip fit to clone from?  The measures of audio_prep.assess_reference (the definition, written down
+ * above it) for n clips in one call, on the two buffers a front-end call holds.  Not in the reference.
+ *   raw_dev                   fp32, read only: the packed raw clips as f5hip_ref_frontend is handed them; clip i is channels[i] channels of
+ *                             raw_len[i] samples, channel after channel, at raw_dev + raw_offset[i] (host tables; disjoint ranges)
+ *   wave_dev                  fp32, read only: f5hip_ref_frontend's packed output (mono, 24 kHz); clip i is n_samples[i] samples at
+ *                             wave_dev + offset[i] (host tables; disjoint ranges): the caller passes min(length, 1 440 000)
+ *   rows_dev                  int64 [n][10], 8-byte aligned: clipped, the bit pattern of peak (fp32), the speech frames, k* (-1: an all-zero
+ *                             clip), then as fp64 bit patterns N, S, noise_db, snr_db, speech_ratio, bandwidth_hz
+ * peak = max |x| of the raw clip; a sample is hot when |x| >= peak * (1 - 2^-10) in fp32; clipped = the hot samples in runs of at least 3
+ * within one channel, 0 when peak < 0.25 or every sample is hot.  The spectrum is f5hip_ref_denoise's framing, P and floor (its stft and floor
+ * kernels, launched as they stand); over bins 3 .. 341: E[f] = sum_k P[f][k], N = -1 / ln(0.8) * sum_k floor[k], S = mean_f E[f];
+ * noise_db = 10 log10 N; snr_db = 10 log10(max(S - N, 0) / N); speech_ratio = the share of frames with E >= 4 N and > 0; m[k] = the mean
+ * over frames of the mean of P[f][k .. k + 7]; k* = the largest k with m[k] >= 1e-5 max m; bandwidth_hz = (k* + 8) * 24000 / 1024.
+ * peak and the counts are exact (integer atomics, order-free); the sums over frames run in fp64 in an order fixed by the clip alone (E in
+ * ascending frame order; m over tiles of 16 frame rows, rows and tiles ascending).
+ * SIX launches whatever n (f5hip_ref_assess_launches: peak, runs, stft, floor, frame sums per tile of 16 rows, per clip) behind one memset of the n accumulator
+ * cells, no host synchronisation once the workspace has grown to the call's size (counters ref_assess_launches, ref_assess_clips; geometry
+ * and run rule csrc/ref_assess_core.h, which tools/ref_assess_check.cpp runs on the CPU under sanitizers).  Clip i's row depends on clip i
+ * alone: it equals its own single-clip call's bit for bit.
+ * Refused before the first launch: n outside 1 .. 4096, channels outside 1 .. 8, a length below 1, a prepared length above 1 440 000, more
+ * than 2^31 - 1 raw samples in a clip, a negative offset, overlapping ranges on either side, a null or misaligned pointer, more than
+ * 2^31 - 1 frame rows. */
+int f5hip_ref_assess(int32_t n, const float* raw_dev, const int64_t* raw_offset, const int32_t* channels, const int32_t* raw_len,
+                     const float* wave_dev, const int64_t* offset, const int32_t* n_samples, int64_t* rows_dev, void* stream);
+
+/* Kernels one f5hip_ref_assess call launches (6). */
+int f5hip_ref_assess_launches(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ from __future__ import annotations
 import hashlib
 import math
 import tempfile
+import typing
 import wave as _wave
 
 import numpy as np
@@ -542,3 +543,170 @@ def denoise_reference_f64(wave) -> np.ndarray:
     for m in range(F):
         out[H * m:H * m + N] += y[m]
     return out[DENOISE_PAD:DENOISE_PAD + n] / 2.0
+
+
+# ------------------------------------------------------------------------------------------------ is an uploaded reference clip fit to clone from?
+# The definition of the reference-clip report (`infer.PreparedVoice(..., assess=True)`, `TTSManager.check_reference`, the upload gate
+# `TTSManager(reference_limits=...)`; on the device `ops.ref_assess`, csrc/ref_assess.h).  `raw` is the clip the front-end is handed,
+# float32 [ch, n] at its own rate; `prepared` is the front-end's output, mono at 24 kHz.
+#   peak         max |x| over all channels of raw, a float32 value
+#   hot          |x| >= peak * (1 - 2^-10), one float32 product and comparison (16-bit PCM tops at 32767 / 32768 against -1.0: both are hot)
+#   clipped      the hot samples that lie in a run of at least 3 consecutive hot samples WITHIN ONE CHANNEL: sample j counts when it is hot and
+#                (j - 1 and j + 1) or (j - 1 and j - 2) or (j + 1 and j + 2) are, a position outside the channel never being hot.  0 when
+#                peak < 0.25 (a quiet recording's tops are its loudest syllables, not the converter's rails) and 0 when EVERY sample is hot
+#                (zeros, DC, a full-scale square wave: there is no waveform to have been clipped)
+#   clip_ratio   clipped / (ch n), float64
+#   spectrum     the first ASSESS_MAX_SAMPLES samples of prepared, framed exactly as the denoiser frames them (sqrt-Hann frames of 1024 at
+#                hop 256 behind 768 zeros): P[f][k], F frames, floor[k] = the ((F - 1) // 5)-th smallest of P[.][k]
+#   band B       bins 3 .. 341 (70 Hz .. 8 kHz); E[f] = sum_{k in B} P[f][k], ascending k
+#   N            ASSESS_FLOOR_TO_MEAN * sum_{k in B} floor[k] (ascending k), ASSESS_FLOOR_TO_MEAN = -1 / ln(0.8) = 4.4814: the 20 % quantile of
+#                an exponentially distributed power is 0.2231 of its mean, so N estimates the mean noise power of a frame in the band
+#   S            (1 / F) * sum_f E[f], ascending f: the mean power of a frame in the band, noise included
+#   noise_db     10 log10(N); -inf when N == 0
+#   snr_db       10 log10(max(S - N, 0) / N); +inf when N == 0, -inf when S <= N
+#   speech_ratio the share of frames with E[f] >= 4 N and E[f] > 0
+#   bandwidth_hz m[k] = the mean over frames of the mean of P[f][k .. k + 7], k = 0 .. 505; k* = the largest k with m[k] >= 1e-5 max m;
+#                (k* + 8) * 24000 / 1024: the upper edge of the highest 8-bin window that still holds a 100 000th of the strongest one's
+#                power.  0 for an all-zero clip
+#   seconds, rms the front-end's values, handed through
+# The weak case is the denoiser's: a voice WITHOUT PAUSES has its own speech as the floor, so N is too high, `snr_db` reads low and
+# `speech_ratio` reads the share of frames above four times the speech's own quantile, which says nothing.  S includes the pauses, so a clip
+# that is 40 % pause reads 2.2 dB below the SNR of its speech alone.  Calibration on synthetic hosts: DESIGN.md §8.  No built-in thresholds:
+# `reference_limits` are the operator's.
+ASSESS_MAX_SAMPLES = DENOISE_MAX_SAMPLES
+ASSESS_HOT = 1.0 - 2.0 ** -10
+ASSESS_MIN_PEAK = 0.25
+ASSESS_MIN_RUN = 3
+ASSESS_BAND = (3, 341)
+ASSESS_FLOOR_TO_MEAN = -1.0 / math.log(0.8)
+ASSESS_SPEECH_FACTOR = 4.0
+ASSESS_MEAN_BINS = 8
+ASSESS_BANDWIDTH_REL = 1e-5
+ASSESS_MAX_CHANNELS = 8
+ASSESS_ROW = ("clipped", "peak_bits", "speech_frames", "k_star", "N", "S", "noise_db", "snr_db", "speech_ratio", "bandwidth_hz")
+REFERENCE_LIMITS = ("min_seconds", "max_clip_ratio", "min_snr_db", "min_speech_ratio", "min_bandwidth_hz")
+
+
+class ReferenceReport(typing.NamedTuple):
+    """The measures of one reference clip (the definition above).  `rms` is None where no front-end value was handed in."""
+    seconds: float
+    rms: float | None
+    peak: float
+    clipped: int
+    clip_ratio: float
+    noise_db: float
+    snr_db: float
+    speech_ratio: float
+    bandwidth_hz: float
+
+    def as_json(self) -> dict:
+        """The report as a JSON object: an infinite `noise_db` / `snr_db` is null."""
+        return {k: (None if isinstance(v, float) and not math.isfinite(v) else v) for k, v in self._asdict().items()}
+
+
+def check_reference_limits(limits):
+    """`TTSManager(reference_limits=...)` checked: None, or a dict of `REFERENCE_LIMITS` names to finite numbers -> a dict of floats.
+    ValueError for an unknown name or a value that is not a number."""
+    if limits is None:
+        return None
+    if not isinstance(limits, dict):
+        raise ValueError(f"reference_limits must be a dict of {', '.join(REFERENCE_LIMITS)} (got {type(limits).__name__})")
+    out = {}
+    for name, value in limits.items():
+        if name not in REFERENCE_LIMITS:
+            raise ValueError(f"reference_limits: unknown limit {name!r} (known: {', '.join(REFERENCE_LIMITS)})")
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value):
+            raise ValueError(f"reference_limits: {name} must be a finite number (got {value!r})")
+        out[name] = float(value)
+    return out
+
+
+def reference_problems(report: ReferenceReport, limits, denoise: bool = False) -> list:
+    """The limits of `limits` (a checked dict, or None) that `report` violates, one sentence each, naming the measure, its value and the
+    limit.  `min_snr_db` is not applied to a voice with `denoise`: the denoiser is the remedy."""
+    problems = []
+    for name, limit in (limits or {}).items():
+        kind, measure = name.split("_", 1)
+        if measure == "snr_db" and denoise:
+            continue
+        value = getattr(report, measure)
+        if (value < limit) if kind == "min" else (value > limit):
+            problems.append(f"the reference clip's {measure} is {value:.6g}, {'below' if kind == 'min' else 'above'} the limit {name} = {limit:.6g}")
+    return problems
+
+
+def assess_clipping(raw):
+    """(peak float32, clipped int) of raw [ch, n] by the definition above."""
+    x = np.abs(np.asarray(raw, dtype=np.float32))
+    x = x.reshape(1, -1) if x.ndim == 1 else x
+    if x.ndim != 2 or x.shape[1] < 1 or not 1 <= x.shape[0] <= ASSESS_MAX_CHANNELS:
+        raise ValueError(f"assess: the clip must be [1 .. {ASSESS_MAX_CHANNELS} channels, at least one sample] (got {x.shape})")
+    peak = np.float32(x.max())
+    hot = x >= peak * np.float32(ASSESS_HOT)
+    if peak < np.float32(ASSESS_MIN_PEAK) or hot.all():
+        return peak, 0
+    h = np.pad(hot, ((0, 0), (2, 2)))                     # outside the channel: never hot
+    l2, l1, me, r1, r2 = (h[:, i:i + x.shape[1]] for i in range(5))
+    return peak, int(np.count_nonzero(me & ((l1 & r1) | (l1 & l2) | (r1 & r2))))
+
+
+def denoise_power(x: np.ndarray) -> np.ndarray:
+    """P [F, 513] of a mono clip x [n] float64: the power of the denoiser's frames (`denoise_reference_f64`'s framing and window)."""
+    N, H = DENOISE_N_FFT, DENOISE_HOP
+    F = denoise_frames(len(x))
+    w = np.sin(np.pi * np.arange(N) / N)
+    xp = np.zeros(H * (F - 1) + N)
+    xp[DENOISE_PAD:DENOISE_PAD + len(x)] = x
+    X = np.fft.rfft(np.lib.stride_tricks.sliding_window_view(xp, N)[::H] * w, axis=1)
+    return X.real ** 2 + X.imag ** 2
+
+
+def assess_spectrum(prepared) -> dict:
+    """The spectral measures of a prepared 24 kHz mono wave by the definition above, with the intermediate values the tests read:
+    dict(F, E, N, S, noise_db, snr_db, speech_frames, speech_ratio, m, k_star, bandwidth_hz)."""
+    x = np.asarray(prepared, dtype=np.float64).reshape(-1)[:ASSESS_MAX_SAMPLES]
+    if len(x) < 1:
+        raise ValueError("assess: the reference clip is empty")
+    P = denoise_power(x)
+    F, (b0, b1) = P.shape[0], ASSESS_BAND
+    E = np.cumsum(P[:, b0:b1 + 1], axis=1)[:, -1]                              # ascending k
+    N = ASSESS_FLOOR_TO_MEAN * float(np.cumsum(denoise_floor(P)[b0:b1 + 1])[-1])
+    S = float(np.cumsum(E)[-1]) / F                                            # ascending f
+    speech = int(np.count_nonzero((E >= ASSESS_SPEECH_FACTOR * N) & (E > 0)))
+    m = np.lib.stride_tricks.sliding_window_view(P, ASSESS_MEAN_BINS, axis=1).mean(axis=2).mean(axis=0)
+    top = float(m.max())
+    k_star = int(np.flatnonzero(m >= ASSESS_BANDWIDTH_REL * top)[-1]) if top > 0 else -1
+    return dict(F=F, E=E, m=m, speech_frames=speech, k_star=k_star, **assess_ratios(N, S, speech, F, k_star))
+
+
+def assess_ratios(N: float, S: float, speech_frames: int, F: int, k_star: int) -> dict:
+    """N, S, the count of speech frames and k* -> dict(N, S, noise_db, snr_db, speech_ratio, bandwidth_hz)."""
+    noise_db = 10.0 * math.log10(N) if N > 0 else -math.inf
+    snr_db = math.inf if not N > 0 else (10.0 * math.log10((S - N) / N) if S > N else -math.inf)
+    return dict(N=N, S=S, noise_db=noise_db, snr_db=snr_db, speech_ratio=speech_frames / F,
+                bandwidth_hz=(k_star + ASSESS_MEAN_BINS) * 24000.0 / DENOISE_N_FFT if k_star >= 0 else 0.0)
+
+
+def assess_reference(raw, sr, prepared, rms=None) -> ReferenceReport:
+    """The report of one clip by the definition above: `raw` float32 [ch, n] at `sr` Hz as the front-end is handed it, `prepared` the
+    front-end's 24 kHz mono wave [nw] (or [1, nw]); `rms`: the front-end's measured rms, handed through (None: not reported).  Degenerate
+    clips have defined values: zeros (clipped 0, N = S = 0, noise_db -inf, snr_db +inf, speech_ratio 0, bandwidth 0), DC (clipped 0), one
+    sample (F = 4 frames, rank 0: the floor is each bin's smallest power)."""
+    raw = np.asarray(raw, dtype=np.float32)
+    raw = raw.reshape(1, -1) if raw.ndim == 1 else raw
+    peak, clipped = assess_clipping(raw)
+    s = assess_spectrum(prepared)
+    return ReferenceReport(seconds=raw.shape[1] / sr, rms=None if rms is None else float(rms), peak=float(peak), clipped=clipped,
+                           clip_ratio=clipped / float(raw.size), noise_db=s["noise_db"], snr_db=s["snr_db"], speech_ratio=s["speech_ratio"],
+                           bandwidth_hz=s["bandwidth_hz"])
+
+
+def report_from_row(row, seconds, rms, samples) -> ReferenceReport:
+    """One row of `ops.ref_assess` (int64 [len(ASSESS_ROW)], the float64 values as their bit patterns) -> the report; `samples` = ch * n of raw."""
+    row = np.ascontiguousarray(row, dtype=np.int64)
+    f = dict(zip(ASSESS_ROW, row.view(np.float64).tolist()))
+    clipped = int(row[0])
+    return ReferenceReport(seconds=float(seconds), rms=None if rms is None else float(rms),
+                           peak=float(np.array([row[1]], dtype=np.int64).astype(np.uint32).view(np.float32)[0]), clipped=clipped,
+                           clip_ratio=clipped / float(samples), noise_db=f["noise_db"], snr_db=f["snr_db"], speech_ratio=f["speech_ratio"],
+                           bandwidth_hz=f["bandwidth_hz"])

@@ -105,7 +105,7 @@ def build_torch_ops(verbose: bool = True) -> str:
     libf5hip.so (rpath $ORIGIN) and the torch libraries of this interpreter; rebuilt when the source, the header or libf5hip.so changed."""
     import torch
     src, hdr = os.path.join(CSRC, "torch_ops.cpp"), os.path.join(os.path.dirname(HERE), "include", "f5hip.h")
-    if os.path.exists(TORCH_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(TORCH_LIB) for d in (src, hdr, LIB, os.path.join(CSRC, "rate_pair.h"), os.path.join(CSRC, "wave_prosody_core.h"), os.path.join(CSRC, "ref_denoise_core.h"), os.path.join(CSRC, "wave_mark_core.h"))):
+    if os.path.exists(TORCH_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(TORCH_LIB) for d in (src, hdr, LIB, os.path.join(CSRC, "rate_pair.h"), os.path.join(CSRC, "wave_prosody_core.h"), os.path.join(CSRC, "ref_denoise_core.h"), os.path.join(CSRC, "wave_mark_core.h"), os.path.join(CSRC, "ref_assess_core.h"))):
         return TORCH_LIB
     tdir = os.path.dirname(torch.__file__)
     cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",

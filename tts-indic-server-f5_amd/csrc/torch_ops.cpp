@@ -24,6 +24,7 @@
 //   torch.ops.f5hip.wave_prosody(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, taps?) -> (Tensor pcm int16, Tensor lengths int32, Tensor offsets int64 host, Tensor bounds int32 host)
 //   torch.ops.f5hip.ref_denoise(wave, offset, n_samples) -> ()   the flagged clips of wave (f5hip_ref_frontend's packed output) are denoised in place
 //   torch.ops.f5hip.wave_mark(pcm, in_off, max_len, len_dev?, key_index, carriers?) -> ()   the flagged requests of pcm get their key's provenance mark in place
+//   torch.ops.f5hip.ref_assess(raw, raw_offset, channels, raw_len, wave, offset, n_samples) -> Tensor rows int64 [n, 10]: the reference-clip report
 //   torch.ops.f5hip.watermark_detect(wave, offset, n_samples, carriers) -> Tensor scores fp32 [n, n_keys, 4]: z, offset, r at the offset, the deviation
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
@@ -40,6 +41,7 @@
 #include "wave_prosody_core.h"
 #include "wave_mark_core.h"
 #include "ref_denoise_core.h"
+#include "ref_assess_core.h"
 
 namespace {
 
@@ -718,6 +720,35 @@ at::Tensor watermark_detect(const at::Tensor& wave, const at::Tensor& offset, co
     return scores;
 }
 
+// raw: the contiguous 1-D fp32 device tensor that holds the raw clips (what f5hip_ref_frontend is handed), read only; raw_offset [n] int64,
+// channels [n] int32, raw_len [n] int32 host: clip i is channels[i] x raw_len[i] samples at raw[raw_offset[i]]; wave, offset, n_samples as
+// ref_denoise's (read only) -> rows int64 device [n, 10] (include/f5hip.h f5hip_ref_assess)
+at::Tensor ref_assess(const at::Tensor& raw, const at::Tensor& raw_offset, const at::Tensor& channels, const at::Tensor& raw_len, const at::Tensor& wave,
+                      const at::Tensor& offset, const at::Tensor& n_samples) {
+    check_host(raw_offset, at::kLong, "raw_offset"); check_host(channels, at::kInt, "channels"); check_host(raw_len, at::kInt, "raw_len");
+    check_host(offset, at::kLong, "offset"); check_host(n_samples, at::kInt, "n_samples");
+    check_dev_f32(raw, "raw"); check_dev_f32(wave, "wave");
+    const int64_t n = n_samples.numel();
+    TORCH_CHECK(n_samples.dim() == 1 && n >= 1 && n <= kRaMaxClips && offset.numel() == n && raw_offset.numel() == n && channels.numel() == n && raw_len.numel() == n,
+                "f5hip::ref_assess: the five tables need one value per clip, 1 .. ", kRaMaxClips, " clips");
+    TORCH_CHECK(raw.dim() == 1 && wave.dim() == 1 && raw.device() == wave.device(), "f5hip::ref_assess: raw and wave must be contiguous 1-D fp32 tensors on one HIP device");
+    const int64_t *ro = raw_offset.data_ptr<int64_t>(), *off = offset.data_ptr<int64_t>();
+    const int32_t *ch = channels.data_ptr<int32_t>(), *rl = raw_len.data_ptr<int32_t>(), *ns = n_samples.data_ptr<int32_t>();
+    for (int64_t i = 0; i < n; i++) {
+        TORCH_CHECK(ch[i] >= 1 && ch[i] <= kRaMaxChannels, "f5hip::ref_assess: clip ", i, " has ", ch[i], " channels (1 .. ", kRaMaxChannels, ")");
+        TORCH_CHECK(rl[i] >= 1 && ro[i] >= 0 && ro[i] + (int64_t)rl[i] * ch[i] <= raw.numel(), "f5hip::ref_assess: raw clip ", i, " is ", ch[i], " x ", rl[i],
+                    " samples at ", ro[i], " of a tensor of ", raw.numel());
+        TORCH_CHECK(ns[i] >= 1 && ns[i] <= kRdMaxSamples, "f5hip::ref_assess: clip ", i, " has ", ns[i], " samples (1 .. ", kRdMaxSamples, ")");
+        TORCH_CHECK(off[i] >= 0 && off[i] + ns[i] <= wave.numel(), "f5hip::ref_assess: clip ", i, " is samples [", off[i], ", ", off[i] + ns[i], ") of a tensor of ",
+                    wave.numel());
+    }
+    const c10::DeviceGuard guard(wave.device());
+    at::Tensor rows = at::empty({n, kRaRowWords}, wave.options().dtype(at::kLong));
+    const int rc = f5hip_ref_assess((int32_t)n, raw.data_ptr<float>(), ro, ch, rl, wave.data_ptr<float>(), off, ns, rows.data_ptr<int64_t>(), stream_of(wave));
+    TORCH_CHECK(rc == 0, "f5hip_ref_assess: ", f5hip_last_error());
+    return rows;
+}
+
 }   // namespace
 
 TORCH_LIBRARY(f5hip, m) {
@@ -746,4 +777,5 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("ref_denoise(Tensor(a!) wave, Tensor offset, Tensor n_samples) -> ()", &ref_denoise);
     m.def("wave_mark(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor key_index, Tensor? carriers) -> ()", &wave_mark);
     m.def("watermark_detect(Tensor wave, Tensor offset, Tensor n_samples, Tensor carriers) -> Tensor", &watermark_detect);
+    m.def("ref_assess(Tensor raw, Tensor raw_offset, Tensor channels, Tensor raw_len, Tensor wave, Tensor offset, Tensor n_samples) -> Tensor", &ref_assess);
 }

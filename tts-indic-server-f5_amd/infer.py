@@ -33,6 +33,8 @@ import torch
 from . import wave_codec
 from .audio_prep import preprocess_ref_audio_text, remove_silence_edges, remove_silence_pcm  # noqa: F401  (F/infer/utils_infer.py:263-350)
 from .audio_prep import DENOISE_MAX_SAMPLES, check_denoise_length, denoise_reference  # noqa: F401  (the per-voice `denoise` option of an uploaded clip)
+from .audio_prep import (ASSESS_MAX_SAMPLES, REFERENCE_LIMITS, ReferenceReport, assess_reference, check_reference_limits,  # noqa: F401
+                         reference_problems, report_from_row)   # (the reference-clip report and the upload gate)
 from .loaders import DiT, MMDiT, UNetT, load_checkpoint, load_model, load_vocoder  # noqa: F401  (F/infer/utils_infer.py:92-130,175-260)
 from .wave_codec import (ALL_ENCODINGS, DELIVERY_OPTIONS, FLAC_BLOCK, FLAC_ENCODINGS, FLAC_HEADER_BYTES, MAX_TAP_TABLE_BYTES, OUTPUT_ENCODINGS,  # noqa: F401
                          OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, WHOLE_WAVE, WHOLE_WAVE_LOUDNESS, StreamDelivery, StreamFlacEncoder,
@@ -386,15 +388,28 @@ class PreparedVoice:
 
     `reject_marked` (None): watermark keys the clip must not carry.  The prepared 24 kHz wave is scored against them before the denoiser
     (`check_unmarked`; a deferred voice by `prepare_voices`: on the device in one `ops.watermark_detect` call per front-end call), and a
-    clip that scores at or above `WATERMARK_THRESHOLD` for any key is a ValueError (`MARKED_REFERENCE`)."""
+    clip that scores at or above `WATERMARK_THRESHOLD` for any key is a ValueError (`MARKED_REFERENCE`).
 
-    def __init__(self, ref_audio, target_rms=0.1, device=None, denoise=False, reject_marked=None):
+    `assess` (False): the clip is measured (`audio_prep.assess_reference`: clipping, noise floor, SNR, speech share, bandwidth) on the clip
+    the front-end is handed and its 24 kHz output, in front of the watermark check and the denoiser, and `report` holds the
+    `ReferenceReport`; it stays None until measured (a deferred voice: by `prepare_voices`, on the device in one `ops.ref_assess` call per
+    front-end call).  `limits` (None): a dict of `REFERENCE_LIMITS`; it implies `assess`, and a clip that violates one is a ValueError
+    naming the measure, its value and the limit (`min_snr_db` is not applied with `denoise`)."""
+
+    report = None
+
+    def __init__(self, ref_audio, target_rms=0.1, device=None, denoise=False, reject_marked=None, assess=False, limits=None):
         wav, sr = ref_audio if isinstance(ref_audio, tuple) else load_audio(ref_audio)
         if denoise:
             check_denoise_length(resampled_length(wav.shape[-1], sr, target_sample_rate))
         self.seconds = wav.shape[-1] / sr
         self.audio, self.rms = _prepare_reference(wav, sr, target_rms, device)
         self.denoise = bool(denoise)
+        self.limits = check_reference_limits(limits)
+        self.assess = bool(assess) or self.limits is not None
+        if self.assess:
+            self.report = _assess_host(wav, sr, self.audio, self.rms)
+            check_within_limits(self.report, self.limits, self.denoise)
         self.reject_marked = None if reject_marked is None else tuple(check_watermark_keys(list(reject_marked)))
         if self.reject_marked is not None:
             check_unmarked(self.audio, self.reject_marked)
@@ -405,7 +420,7 @@ class PreparedVoice:
         self.pending = None
 
     @classmethod
-    def deferred(cls, ref_audio, target_rms=0.1, denoise=False, reject_marked=None):
+    def deferred(cls, ref_audio, target_rms=0.1, denoise=False, reject_marked=None, assess=False, limits=None):
         wav, sr = ref_audio
         if wav.dim() != 2 or wav.shape[-1] < 1:
             raise ValueError(f"reference audio must be [channels, samples] with at least one sample (got {tuple(wav.shape)})")
@@ -415,6 +430,8 @@ class PreparedVoice:
             check_denoise_length(resampled_length(wav.shape[-1], sr, target_sample_rate))
         voice = cls.__new__(cls)
         voice.denoise = bool(denoise)
+        voice.limits = check_reference_limits(limits)
+        voice.assess = bool(assess) or voice.limits is not None
         voice.reject_marked = None if reject_marked is None else tuple(check_watermark_keys(list(reject_marked)))
         voice.seconds = wav.shape[-1] / sr
         voice.ref_frames = resampled_length(wav.shape[-1], sr, target_sample_rate) // hop_length
@@ -452,6 +469,24 @@ def check_unmarked(audio, keys):
         raise ValueError(MARKED_REFERENCE)
 
 
+# How often reference clips were measured: "host_clips" (one `assess_reference` each) and "device_calls" (one `ops.ref_assess` each, whatever
+# the number of clips in it).  Without a voice that asks for a report neither moves.
+ASSESS_COUNTS = collections.Counter()
+
+
+def _assess_host(wav, sr, audio, rms):
+    """`audio_prep.assess_reference` of a clip [ch, n] at `sr` and its prepared wave [1, nw], on the host."""
+    ASSESS_COUNTS["host_clips"] += 1
+    return assess_reference(wav.detach().cpu().to(torch.float32).numpy(), sr, audio[0].detach().cpu().numpy(), rms=float(rms))
+
+
+def check_within_limits(report, limits, denoise=False):
+    """Refuses (ValueError naming each violated measure, its value and the limit) a clip whose `report` violates `limits`."""
+    problems = reference_problems(report, limits, denoise)
+    if problems:
+        raise ValueError("; ".join(problems))
+
+
 def _denoise_host(audio):
     """`audio_prep.denoise_reference` of a prepared wave [1, nw], back where it was."""
     DENOISE_COUNTS["host_clips"] += 1
@@ -471,13 +506,20 @@ def prepare_voices(clips, target_rms=0.1, device="cuda"):
     With `device=None` the host `denoise_reference` runs clip by clip.  Voices with `reject_marked` keys are scored in front of the denoiser:
     the flagged voices of a front-end call in ONE `ops.watermark_detect` call on its packed output against the union of their keys, of which
     only the score rows come down; a voice that carries one of its own keys is a ValueError (`MARKED_REFERENCE`) and the call's voices stay
-    deferred.  With `device=None` `check_unmarked` runs clip by clip."""
+    deferred.  With `device=None` `check_unmarked` runs clip by clip.  Voices with `assess` are measured first of all: those of a front-end
+    call in ONE `ops.ref_assess` call on the call's two buffers (the packed upload and the packed output), of which only the rows come down;
+    a voice that violates one of its `limits` is a ValueError and the call's voices stay deferred.  With `device=None`
+    `audio_prep.assess_reference` runs clip by clip."""
     voices = [c if isinstance(c, PreparedVoice) else PreparedVoice.deferred(c, target_rms) for c in clips]
     todo = [v for v in voices if v.pending is not None]
     if device is None:
         for v in todo:
             wav, sr, floor = v.pending
             audio, rms = _prepare_reference(wav, sr, floor, None)
+            if getattr(v, "assess", False):
+                report = _assess_host(wav, sr, audio, rms)
+                check_within_limits(report, v.limits, getattr(v, "denoise", False))
+                v.report = report
             if getattr(v, "reject_marked", None) is not None:
                 check_unmarked(audio, v.reject_marked)
             v.audio, v.rms = audio, rms
@@ -496,6 +538,18 @@ def prepare_voices(clips, target_rms=0.1, device="cuda"):
         out, rms, n_out = ops.ref_frontend(packed, [v.pending[0].shape[-1] for v in vs], [v.pending[0].shape[0] for v in vs], sr,
                                            target_sample_rate, taps, floor)
         starts = np.concatenate([[0], np.cumsum(n_out)[:-1]])
+        measured = [i for i, v in enumerate(vs) if getattr(v, "assess", False) and n_out[i] > 0]
+        reports = {}
+        if measured:                                             # in front of the watermark check and the denoiser; only the rows come down
+            sizes = [int(v.pending[0].shape[0]) * int(v.pending[0].shape[-1]) for v in vs]
+            raw_at = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+            rows = ops.ref_assess(packed, [int(raw_at[i]) for i in measured], [int(vs[i].pending[0].shape[0]) for i in measured],
+                                  [int(vs[i].pending[0].shape[-1]) for i in measured], out, [int(starts[i]) for i in measured],
+                                  [min(int(n_out[i]), ASSESS_MAX_SAMPLES) for i in measured]).cpu().numpy()
+            ASSESS_COUNTS["device_calls"] += 1
+            for i, row in zip(measured, rows):
+                reports[i] = report_from_row(row, vs[i].seconds, None, sizes[i])
+                check_within_limits(reports[i], vs[i].limits, getattr(vs[i], "denoise", False))
         guarded = [i for i, v in enumerate(vs) if getattr(v, "reject_marked", None) is not None and n_out[i] > 0]
         if guarded:                                              # in front of the denoiser; only the score rows come down
             keys = sorted({k for i in guarded for k in vs[i].reject_marked})
@@ -511,13 +565,15 @@ def prepare_voices(clips, target_rms=0.1, device="cuda"):
         if flagged:                                              # in place on the packed output: the views below are the denoised clips
             ops.ref_denoise(out, [int(starts[i]) for i in flagged], [int(n_out[i]) for i in flagged])
             DENOISE_COUNTS["device_calls"] += 1
-        done.append((vs, out.split(n_out), rms))
+        done.append((vs, out.split(n_out), rms, reports))
     if done:
-        all_rms = torch.cat([rms for _, _, rms in done]).cpu()   # the one download
+        all_rms = torch.cat([rms for _, _, rms, _ in done]).cpu()   # the one download
         k = 0
-        for vs, outs, _ in done:
-            for v, audio in zip(vs, outs):
+        for vs, outs, _, reports in done:
+            for i, (v, audio) in enumerate(zip(vs, outs)):
                 v.audio, v.rms, v.pending = audio[None], all_rms[k], None
+                if i in reports:
+                    v.report = reports[i]._replace(rms=float(all_rms[k]))
                 k += 1
     return voices
 

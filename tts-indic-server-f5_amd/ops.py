@@ -1,7 +1,7 @@
 """Python face of the operations of the C ABI (include/f5hip.h) on torch tensors on the HIP device.  Two families:
   - the per-kernel unit ops (`gemm` .. `time_table`): one production HIP kernel each, fp32 in and out, called through ctypes.  Used by the
     per-kernel parity tests and the timing tools; not on the hot path.
-  - the device audio path that every request takes (`ref_frontend`, `ref_prestep`, `ref_denoise`, `wave_finish` .. `wave_loudness`, `flac_decode`): one
+  - the device audio path that every request takes (`ref_frontend`, `ref_prestep`, `ref_denoise`, `ref_assess`, `wave_finish` .. `wave_loudness`, `flac_decode`): one
     library call per batch.  Each is bound twice over the same C entry point: as a TORCH_LIBRARY operator (csrc/torch_ops.cpp), taken when
     `torch_ops.load()`, and through ctypes otherwise; both return the same bits.  The steps the wrappers share -- the operator call, the
     per-request host arrays, the PCM request table, its sources, the pointer table and the packing of the outputs -- are the helpers in
@@ -619,6 +619,43 @@ def ref_denoise(wave, offsets, lengths):
     with torch.cuda.device(wave.device):
         _lib.check(_lib.lib().f5hip_ref_denoise(len(ln), _p(off), _p(ln), _p(wave), _lib.current_stream_ptr()), "f5hip_ref_denoise")
     return wave
+
+
+def ref_assess(raw, raw_offsets, channels, raw_lengths, wave, offsets, lengths):
+    """The reference-clip report of several clips in ONE library call and six launches (include/f5hip.h f5hip_ref_assess):
+    `audio_prep.assess_reference` of each clip on the two buffers of a front-end call.  raw: the contiguous 1-D fp32 device tensor that holds
+    the raw clips as `ref_frontend` is handed them -- clip i is channels[i] channels of raw_lengths[i] samples, channel after channel, at
+    raw[raw_offsets[i]] --; wave, offsets, lengths as `ref_denoise` takes them (`ref_frontend`'s packed output; pass
+    min(length, `audio_prep.ASSESS_MAX_SAMPLES`)).  Both are read only.  Returns the rows, int64 [n, len(`audio_prep.ASSESS_ROW`)] on the
+    device (`audio_prep.report_from_row` reads one): counts and peak exactly the host's, and a clip's row equals its own single-clip call's
+    bit for bit."""
+    from .audio_prep import ASSESS_MAX_CHANNELS, ASSESS_MAX_SAMPLES, ASSESS_ROW
+    ln = _per_request("ref_assess", "lengths", lengths, np.int32, per="clip")
+    off = _per_request("ref_assess", "offsets", offsets, np.int64, len(ln), per="clip")
+    ro = _per_request("ref_assess", "raw_offsets", raw_offsets, np.int64, len(ln), per="clip")
+    ch = _per_request("ref_assess", "channels", channels, np.int32, len(ln), per="clip")
+    rl = _per_request("ref_assess", "raw_lengths", raw_lengths, np.int32, len(ln), per="clip")
+    for t, name in ((raw, "raw"), (wave, "wave")):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and t.dim() == 1):
+            raise _lib.F5HipError(f"ref_assess: {name} must be a contiguous 1-D fp32 tensor on the HIP device")
+    if raw.device != wave.device:
+        raise _lib.F5HipError("ref_assess: raw and wave must be on one HIP device")
+    if torch_ops.load():
+        return call_op("ref_assess", raw, torch.from_numpy(ro), torch.from_numpy(ch), torch.from_numpy(rl), wave, torch.from_numpy(off), torch.from_numpy(ln))
+    for i in range(len(ln)):
+        if ch[i] < 1 or ch[i] > ASSESS_MAX_CHANNELS:
+            raise _lib.F5HipError(f"ref_assess: clip {i} has {ch[i]} channels (1 .. {ASSESS_MAX_CHANNELS})")
+        if rl[i] < 1 or ro[i] < 0 or int(ro[i]) + int(rl[i]) * int(ch[i]) > raw.numel():
+            raise _lib.F5HipError(f"ref_assess: raw clip {i} is {ch[i]} x {rl[i]} samples at {ro[i]} of a tensor of {raw.numel()}")
+        if ln[i] < 1 or ln[i] > ASSESS_MAX_SAMPLES:
+            raise _lib.F5HipError(f"ref_assess: clip {i} has {ln[i]} samples (1 .. {ASSESS_MAX_SAMPLES})")
+        if off[i] < 0 or int(off[i]) + int(ln[i]) > wave.numel():
+            raise _lib.F5HipError(f"ref_assess: clip {i} is samples [{off[i]}, {int(off[i]) + int(ln[i])}) of a tensor of {wave.numel()}")
+    with torch.cuda.device(wave.device):
+        rows = torch.empty(len(ln), len(ASSESS_ROW), device=wave.device, dtype=torch.int64)
+        _lib.check(_lib.lib().f5hip_ref_assess(len(ln), _p(raw), _p(ro), _p(ch), _p(rl), _p(wave), _p(off), _p(ln), _p(rows), _lib.current_stream_ptr()),
+                   "f5hip_ref_assess")
+    return rows
 
 
 def wave_finish(chunks, chunks_per_request, fade, remove_silence=None, sample_rate=24000):

@@ -440,7 +440,7 @@ class TTSManager:
                  sway_sampling_coef: float = infer.sway_sampling_coef, speed: float = infer.speed, mel_spec_type: str = "vocos",
                  micro_batch: dict | None = None, batch_invariant: bool = True, clip_cache: int = 64, device_frontend: bool | None = None,
                  device_backend: bool | None = None, device_decode: bool | None = None, device_prestep: bool | None = None,
-                 watermark: int | None = None, reject_marked=None):
+                 watermark: int | None = None, reject_marked=None, reference_limits: dict | None = None):
         self.loader = loader
         # The key (`infer.check_watermark`) every finished wave is marked with unless its request names its own; None: no mark.  A mark needs
         # the whole wave, so with a key here the streaming paths are refused (`STREAM_WATERMARK`) rather than left unmarked.
@@ -448,6 +448,12 @@ class TTSManager:
         # Keys (1 .. 16, or one) whose mark an uploaded reference clip must not carry: a new upload whose prepared 24 kHz wave scores at or
         # above `infer.WATERMARK_THRESHOLD` for any of them is refused (`MARKED_REFERENCE`) before it is denoised, cached or queued.  None: no check
         self.reject_marked = None if reject_marked is None else tuple(infer.check_watermark_keys(reject_marked))
+        # The upload gate: any of `infer.REFERENCE_LIMITS` (min_seconds, max_clip_ratio, min_snr_db, min_speech_ratio, min_bandwidth_hz) -> number.
+        # A new clone or script upload is measured (`audio_prep.assess_reference`; with `device_frontend` one `ops.ref_assess` call per
+        # front-end call) and one that violates a limit is refused with a ValueError naming the measure, its value and the limit -- before the
+        # denoiser, the cache and the queue, once per upload.  `min_snr_db` is not applied to a voice with `denoise`.  There are no built-in
+        # thresholds: None means no gate, and nothing is measured.  Registered voices are not gated.
+        self.reference_limits = infer.check_reference_limits(reference_limits)
         self.batch_invariant = batch_invariant   # False: leave the model's attention mode alone (fastest kernel per launch shape)
         self.micro_batch = micro_batch            # e.g. dict(max_requests=16, max_wait_ms=5): batch concurrent requests; with span_steps
         #                                           (dict(span_steps=8, max_frames=32768); span_steps=None: infer.span_steps) requests join a
@@ -625,6 +631,34 @@ class TTSManager:
         pcm = np.clip(np.rint(x.astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
         return np.ascontiguousarray(pcm.T), sr
 
+    def _prestep_clips(self, new, audios, device):
+        """The silence pre-step of the new uploads `new` (keys whose third element is `clip_short`; `audios[key]`: the upload) -> key ->
+        (float32 clip [ch, n], sample_rate): on `device` (`_prestep_device`) ONE `ops.ref_prestep` call per distinct sample rate, else
+        `audio_prep.preprocess_ref_segment` on the host.  ValueError for an unreadable, non-finite, empty or silent clip."""
+        import torch
+        clips, by_rate = {}, {}
+        for key in new:
+            pcm, sr = self._clip_pcm(audios[key])
+            if device is not None and sr >= 11025 and sr * pcm.shape[1] < 2 ** 23:      # (beyond that the device's exact window sums end)
+                by_rate.setdefault(sr, []).append((key, pcm))
+                continue
+            seg = audio_prep.preprocess_ref_segment(audio_prep.PcmSegment(pcm, sr), key[2], show_info=lambda *_: None)
+            if seg.frames.shape[0] == 0 or not seg.frames.any():
+                raise ValueError("Invalid audio: the clip is empty or silent.")
+            clips[key] = (torch.from_numpy(np.ascontiguousarray((seg.frames.astype(np.float32) / 32768.0).T)), seg.rate)
+        if by_rate:
+            from . import ops
+            for sr, group in by_rate.items():
+                n_in, channels = [pcm.shape[0] for _, pcm in group], [pcm.shape[1] for _, pcm in group]
+                frames = np.concatenate([pcm.reshape(-1) for _, pcm in group])
+                with self._device_lock:
+                    packed, lengths, flags = ops.ref_prestep(frames, n_in, channels, sr, [key[2] for key, _ in group], device=device)
+                if not all(n > 0 and f for n, f in zip(lengths, flags)):
+                    raise ValueError("Invalid audio: the clip is empty or silent.")
+                for (key, _), planes in zip(group, ops.ref_prestep_planes(packed, lengths, channels)):
+                    clips[key] = (planes, sr)
+        return clips
+
     def _clip_voices(self, specs):
         """`_clip_voice` of several uploads, [(ref_audio, ref_text, clip_short[, denoise])] -> [(PreparedVoice, normalised ref_text)].  The cache is
         looked up per key and every new key is prepared under its own lock (taken in key order, so two callers never wait for each other
@@ -668,40 +702,21 @@ class TTSManager:
                         results[key] = self._clip_cache[key]
             new = [key for key, _, _ in entries if key not in results]
             device = self._prestep_device() if new else None
-            clips, by_rate = {}, {}
-            for key in new:
-                pcm, sr = self._clip_pcm(audios[key])
-                if device is not None and sr >= 11025 and sr * pcm.shape[1] < 2 ** 23:      # (beyond that the device's exact window sums end)
-                    by_rate.setdefault(sr, []).append((key, pcm))
-                    continue
-                seg = audio_prep.preprocess_ref_segment(audio_prep.PcmSegment(pcm, sr), key[2], show_info=lambda *_: None)
-                if seg.frames.shape[0] == 0 or not seg.frames.any():
-                    raise ValueError("Invalid audio: the clip is empty or silent.")
-                clips[key] = (torch.from_numpy(np.ascontiguousarray((seg.frames.astype(np.float32) / 32768.0).T)), seg.rate)
-            if by_rate:
-                from . import ops
-                for sr, group in by_rate.items():
-                    n_in, channels = [pcm.shape[0] for _, pcm in group], [pcm.shape[1] for _, pcm in group]
-                    frames = np.concatenate([pcm.reshape(-1) for _, pcm in group])
-                    with self._device_lock:
-                        packed, lengths, flags = ops.ref_prestep(frames, n_in, channels, sr, [key[2] for key, _ in group], device=device)
-                    if not all(n > 0 and f for n, f in zip(lengths, flags)):
-                        raise ValueError("Invalid audio: the clip is empty or silent.")
-                    for (key, _), planes in zip(group, ops.ref_prestep_planes(packed, lengths, channels)):
-                        clips[key] = (planes, sr)
+            clips = self._prestep_clips(new, audios, device)
             fresh = []
             for key in new:
                 clip = clips[key]
                 if clip[1] != infer.target_sample_rate:
                     infer.resample_taps(clip[1], infer.target_sample_rate)      # refuses a rate pair it has no table for
                 if self.device_frontend:
-                    voice = infer.PreparedVoice.deferred(clip, denoise=key[3], reject_marked=self.reject_marked)
-                else:
-                    voice = infer.PreparedVoice(clip, denoise=key[3], reject_marked=self.reject_marked)   # (scored here, before the denoiser)
+                    voice = infer.PreparedVoice.deferred(clip, denoise=key[3], reject_marked=self.reject_marked, limits=self.reference_limits)
+                else:                                                            # (measured and scored here, before the denoiser)
+                    voice = infer.PreparedVoice(clip, denoise=key[3], reject_marked=self.reject_marked, limits=self.reference_limits)
                 fresh.append((key, voice))
-            if self.reject_marked is not None and any(voice.pending is not None for _, voice in fresh):
-                # the new uploads' front-end now, under the device lock: ONE `ops.watermark_detect` call per front-end call scores them on its
-                # device buffer (`infer.prepare_voices`), and a marked clip is refused here -- before it is cached or anything is queued
+            if (self.reject_marked is not None or self.reference_limits is not None) and any(voice.pending is not None for _, voice in fresh):
+                # the new uploads' front-end now, under the device lock: ONE `ops.ref_assess` and ONE `ops.watermark_detect` call per front-end
+                # call measure and score them on its device buffers (`infer.prepare_voices`), and a clip over a limit or a marked clip is
+                # refused here -- before it is cached or anything is queued
                 with self._device_lock:
                     infer._prepare_deferred([voice for _, voice in fresh], self.model_obj)
             for key, voice in fresh:
@@ -1000,6 +1015,27 @@ class TTSManager:
             mono = infer.resample_sinc_hann(mono, int(sr), infer.target_sample_rate)
         return infer.detect_watermark(mono[0].numpy(), keys)
 
+    def check_reference(self, audio, clip_short=True):
+        """The `infer.ReferenceReport` of a would-be reference clip -- WAV or FLAC bytes, or a (wave [ch, n], sr) pair -- taken through
+        `decode_audio`, the silence pre-step and the front-end exactly as a clone upload is (`_clip_voice`; with `device_frontend` and a
+        loaded model the front-end and one `ops.ref_assess` call run on the device under the device lock), but neither cached nor gated:
+        `reference_problems` lists what this manager's limits would refuse.  ValueError for what the clone route refuses as unreadable."""
+        key = ("", "", bool(clip_short), False)
+        audio = audio if isinstance(audio, tuple) else bytes(audio)
+        clip = self._prestep_clips([key], {key: audio}, self._prestep_device())[key]
+        if clip[1] != infer.target_sample_rate:
+            infer.resample_taps(clip[1], infer.target_sample_rate)
+        if not self.device_frontend:
+            return infer.PreparedVoice(clip, assess=True).report
+        voice = infer.PreparedVoice.deferred(clip, assess=True)
+        with self._device_lock:
+            infer._prepare_deferred([voice], self.model_obj)
+        return voice.report
+
+    def reference_problems(self, report, denoise=False) -> list:
+        """What `reference_limits` would refuse `report` for, one sentence per violated limit; empty without limits."""
+        return infer.reference_problems(report, self.reference_limits, denoise)
+
 
 class HTTPError(Exception):
     """Carries (status_code, detail) out of `synthesize_speech`; the route turns it into fastapi.HTTPException."""
@@ -1136,8 +1172,13 @@ def request_models():
         audio: str
         keys: typing.Any = None                      # 1 to 16 keys; absent: the manager's own.  Untyped, so that a bad key arrives as sent and is refused
 
+    class ReferenceCheckRequest(BaseModel):          # `/v1/audio/reference/check`: a would-be reference clip (base64 WAV or FLAC)
+        audio: str
+        clip_short: bool = True
+
     return types.SimpleNamespace(KannadaSynthesizeRequest=KannadaSynthesizeRequest, SynthesizeRequest=SynthesizeRequest, CloneRequest=CloneRequest,
-                                 EditRequest=EditRequest, ScriptRequest=ScriptRequest, ScriptVoice=ScriptVoice, DetectRequest=DetectRequest)
+                                 EditRequest=EditRequest, ScriptRequest=ScriptRequest, ScriptVoice=ScriptVoice, DetectRequest=DetectRequest,
+                                 ReferenceCheckRequest=ReferenceCheckRequest)
 
 
 def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
@@ -1347,6 +1388,20 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
             raise HTTPException(status_code=400, detail=str(e))
         return {"results": [dict(key=s.key, detected=s.detected, score=s.z, offset=s.offset) for s in scores]}
 
+    def _run_check(req):
+        """`/v1/audio/reference/check`: {"audio": base64 WAV or FLAC, "clip_short"?: true} -> {"report": {seconds, rms, peak, clipped, clip_ratio,
+        noise_db, snr_db, speech_ratio, bandwidth_hz}, "problems": [...]}: the clip's measures (`TTSManager.check_reference`; an infinite
+        noise_db / snr_db is null) and the manager's limits it violates (none without limits).  A bad upload is the clone route's 400."""
+        try:
+            raw = base64.b64decode(req.audio, validate=True)
+        except (binascii.Error, ValueError):
+            raise HTTPException(status_code=400, detail="Audio must be a base64-encoded WAV file.")
+        try:
+            report = tts_manager.check_reference(raw, req.clip_short)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        return {"report": report.as_json(), "problems": tts_manager.reference_problems(report)}
+
     # The reference's handlers are `async def` around a blocking call, i.e. one request at a time.  Here the blocking part runs in
     # starlette's thread pool, so concurrent requests overlap and meet in the MicroBatcher queue (when the manager has one).
     from starlette.concurrency import run_in_threadpool
@@ -1376,6 +1431,10 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     @router.post("/audio/watermark/detect")
     async def detect_watermark(request: models.DetectRequest):            # provenance: does this recording carry a key's mark?
         return await run_in_threadpool(_run_detect, request)
+
+    @router.post("/audio/reference/check")
+    async def check_reference(request: models.ReferenceCheckRequest):      # is this clip fit to clone from?
+        return await run_in_threadpool(_run_check, request)
 
     app = FastAPI(title="F5-TTS on MI355X (HIP path)")
     app.include_router(router)
