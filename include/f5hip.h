@@ -194,6 +194,8 @@ int f5hip_get_profile(const char* kernel_class, double* total_ms, int64_t* launc
  * and of the attention dispatcher, one per attn3 instance: "attn_bal8" (SIMD-balanced 8-wave, 9-stage ring), "attn_nw8_deep" /
  * "attn_nw8" (8 waves, 9- / 5-stage ring), "attn_nw6_deep" / "attn_nw6" (6 waves, shape-invariant mode only), "attn_nw4", plus
  * "attn_seg2" (every two-range launch, whatever its instance), and "dit_rows" (the summed audio rows M of every backbone forward);
+ * "gemm3_thin" (the gemm3 launches, counted in "gemm3" too, that took the 32-row instance) and "time_table_builds" (sampler calls and
+ * forwards that built the handle's time tables: a whole-grid sampler call on the time points of the handle's last build reuses them);
  * name "reset" zeroes all of them (value may be NULL). */
 int f5hip_get_counter(const char* name, int64_t* value);
 
@@ -380,6 +382,10 @@ int f5hip_op_conv_pos_embed(int32_t n_seq, const int32_t* seq_len, int32_t lead,
  *   tap_grn_dev [tokens][2 Td] GRN. */
 int f5hip_op_convnext_block(int32_t n_seq, const int32_t* seq_len, int32_t Td, const float* x_dev, const float* const* params_host,
                             int32_t pad_nan, float* out_dev, float* tap_ln_dev, float* tap_ty_dev, float* tap_grn_dev, void* stream);
+/* f5hip_op_convnext_block_gx: the same, with one more tap: tap_gx_dev [n_seq][2 Td] (or NULL), the GRN column norms of every sequence. */
+int f5hip_op_convnext_block_gx(int32_t n_seq, const int32_t* seq_len, int32_t Td, const float* x_dev, const float* const* params_host,
+                               int32_t pad_nan, float* out_dev, float* tap_ln_dev, float* tap_ty_dev, float* tap_grn_dev, float* tap_gx_dev,
+                               void* stream);
 
 /* ---------------------------------------------------------------- Vocos vocoder ----------------------- */
 

@@ -90,6 +90,7 @@ SYMBOLS = {
     "f5hip_op_bigvgan_mel_rows": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "f5hip_op_conv_pos_embed": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_void_p] * 3),
     "f5hip_op_convnext_block": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
+    "f5hip_op_convnext_block_gx": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6),
     "f5hip_vocos_create": (C.c_void_p, [C.POINTER(VocosConfig)]),
     "f5hip_vocos_destroy": (None, [C.c_void_p]),
     "f5hip_vocos_load_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),

@@ -252,7 +252,7 @@ static int run_sampler(f5hip_dit* m, const SampleArgs& a, const int32_t* steps, 
     hipLaunchKernelGGL(split_rows_kernel, dim3(m->M), dim3(256), 0, st, m->xstate, mel, mel, m->M, m->d_row_frame, m->xs.hi, m->xs.lo, 128, 0);
     CKL("split x");
     CK(precompute_text_and_ce(m, a.cond_dev, st));
-    CK(precompute_time(m, P.pts.data(), (int)P.pts.size(), st));
+    CK(precompute_time(m, P.pts.data(), (int)P.pts.size(), st, /*reuse=*/a.last == nullptr));
 
     m->d_row_tp = T.row_tp;
     int n_act = n;

@@ -38,28 +38,44 @@ __global__ __launch_bounds__(256) void rope_rows_kernel(const int* row_pos, cons
 
 // ------------------------------------------------------------------------------------------------
 // GRN (F/model/modules.py:231-234): Gx[c] = ||y[:, c]||_2 over the frames of one sequence.
+// The sum of squares of a column is kept as eight partial sums a8[u]: rows r < (n & ~7) with r % 8 == u in ascending order, then the tail rows
+// n & ~7 .. n - 1 into a8[0]; combined by one fixed tree.  One thread per column walking all rows (8 loads in flight) put a 1404-row sequence
+// of 1024 columns on 4 workgroups for 61 us of load latency.  Here a workgroup is 32 columns x the eight partial sums, one lane each (32 x
+// n_seq workgroups at C = 1024), every lane with 8 loads of its own row class in flight: the same addends in the same order per partial sum.
+// Explicit fma: the one-thread-per-column form compiled `a += t * t` to fused multiply-adds, and left to the compiler this form does not
+// (it squares two values at a time and adds the rounded products).
 __global__ __launch_bounds__(256) void grn_stats_kernel(const float* y, int ldy, int C, const int* seq_row0,
                                                         const int* seq_len, float* gx /*[n_seq][C]*/) {
-    const int seq = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    const int r0 = seq_row0[seq], n = seq_len[seq];
-    // 8 independent loads in flight per thread: the serial one-row-at-a-time loop was pure load latency (327 us at N = 1404)
-    float a8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const float* col = y + (size_t)r0 * ldy + c;
-    int r = 0;
-    for (; r + 8 <= n; r += 8) {
-        float t[8];
+    __shared__ float part[8][32];
+    const int seq = blockIdx.y, cl = threadIdx.x & 31, u = threadIdx.x >> 5, c = blockIdx.x * 32 + cl;
+    const int r0 = seq_row0[seq], n = seq_len[seq], n8 = n & ~7;
+    float a = 0.f;
+    if (c < C) {
+        const float* col = y + (size_t)r0 * ldy + c;
+        int r = u;
+        for (; r + 56 < n8; r += 64) {
+            float t[8];
 #pragma unroll
-        for (int u = 0; u < 8; u++) t[u] = col[(size_t)(r + u) * ldy];
+            for (int i = 0; i < 8; i++) t[i] = col[(size_t)(r + 8 * i) * ldy];
 #pragma unroll
-        for (int u = 0; u < 8; u++) a8[u] += t[u] * t[u];
+            for (int i = 0; i < 8; i++) a = __builtin_fmaf(t[i], t[i], a);
+        }
+        for (; r < n8; r += 8) {
+            const float t = col[(size_t)r * ldy];
+            a = __builtin_fmaf(t, t, a);
+        }
+        if (u == 0)
+            for (r = n8; r < n; r++) {
+                const float t = col[(size_t)r * ldy];
+                a = __builtin_fmaf(t, t, a);
+            }
     }
-    for (; r < n; r++) {
-        const float t = col[(size_t)r * ldy];
-        a8[0] += t * t;
+    part[u][cl] = a;
+    __syncthreads();
+    if (u == 0 && c < C) {
+        const float acc = ((part[0][cl] + part[1][cl]) + (part[2][cl] + part[3][cl])) + ((part[4][cl] + part[5][cl]) + (part[6][cl] + part[7][cl]));
+        gx[(size_t)seq * C + c] = sqrtf(acc);
     }
-    const float acc = ((a8[0] + a8[1]) + (a8[2] + a8[3])) + ((a8[4] + a8[5]) + (a8[6] + a8[7]));
-    gx[(size_t)seq * C + c] = sqrtf(acc);
 }
 
 // y' = gamma * (y * Nx) + beta + y,  Nx = Gx / (mean_c(Gx) + 1e-6)  -> split bf16

@@ -96,6 +96,8 @@ struct f5hip_dit {
     int *d_j_row0 = nullptr, *d_j_len = nullptr, *d_j_kvlen = nullptr, *d_j_kv_row0 = nullptr, *d_j_kv2_row0 = nullptr, *d_j_kv2_len = nullptr;   // MMDiT joint attention: 2 n_seq pseudo-sequences
     bool any_masked = false;
     std::vector<int> h_seq_len;
+    // precompute_time: the time points whose tables sinp, t1, st, mod (UNetT: temb) hold -- empty: none
+    std::vector<float> time_key;
 };
 
 static int ceil_to(int v, int m) { return (v + m - 1) / m * m; }
@@ -396,7 +398,8 @@ static int ensure_workspace(f5hip_dit* m, int rows_pad, int frames, int n_seq) {
             // qk: +256 rows because the last query tile of the attention (up to 256 queries) may read (never store) past the padded rows
             m->qk = a.bf16((R + 256) * 2 * D); m->vt = a.bf16((size_t)D * R);
             m->rk_k2 = a.f32(U * c.mel_dim); m->rk_k3 = a.f32(U * c.mel_dim);
-        })) { m->cap_rows = 0; return -5; }
+        })) { m->cap_rows = 0; m->time_key.clear(); return -5; }
+    m->time_key.clear();   // the time tables moved with the arena
     m->cap_rows = (int)R; m->cap_frames = (int)U; m->cap_seq = (int)S;
     const int need = (int)MetaLayout(R, S, U, m->arch == 2).total;
     if (need > m->meta_cap) {
@@ -547,14 +550,15 @@ static GemmArgs gemm_base(const Plane2& A, int lda, const PackedW& W, int M) {
 // ref_denoise_launches / ref_denoise_clips: kernels f5hip_ref_denoise launched and the clips it denoised; wave_mark_launches /
 // wave_mark_requests: kernels f5hip_wave_mark launched and the requests it marked; watermark_detect_launches / watermark_detect_clips:
 // kernels f5hip_watermark_detect launched and the clips it scored; ref_assess_launches / ref_assess_clips: kernels f5hip_ref_assess launched
-// and the clips it measured
+// and the clips it measured; gemm3_thin: the gemm3 launches (counted in gemm3 too) that took the 32-row instance; time_table_builds: calls of
+// precompute_time that built the tables (the others found the handle's tables built for the same time points)
 enum { CNT_GEMM5_RB11, CNT_GEMM5_RB8, CNT_GEMM5_WIDE, CNT_GEMM3_WIDE, CNT_CONV5, CNT_GEMM6, CNT_GEMM6_R176, CNT_GEMM6_R256, CNT_GEMM5_CB12,
        CNT_GEMM3, CNT_GEMM_REG_BN64, CNT_GEMM_REG_BN128, CNT_DIT_ROWS, CNT_REF_LAUNCHES, CNT_REF_TAPS_LDS, CNT_REF_TAPS_L2, CNT_WAVE_LAUNCHES,
        CNT_WAVE_REQUESTS, CNT_WAVE_ENCODE_LAUNCHES, CNT_WAVE_ENCODE_REQUESTS, CNT_MEL_RAGGED_LAUNCHES, CNT_MEL_RAGGED_ITEMS, CNT_WAVE_FLAC_LAUNCHES,
        CNT_WAVE_FLAC_REQUESTS, CNT_WAVE_LOUDNESS_LAUNCHES, CNT_WAVE_LOUDNESS_REQUESTS, CNT_FLAC_DECODE_LAUNCHES, CNT_FLAC_DECODE_STREAMS,
        CNT_REF_PRESTEP_LAUNCHES, CNT_REF_PRESTEP_CLIPS, CNT_WAVE_PROSODY_LAUNCHES, CNT_WAVE_PROSODY_REQUESTS,
        CNT_REF_DENOISE_LAUNCHES, CNT_REF_DENOISE_CLIPS, CNT_WAVE_MARK_LAUNCHES, CNT_WAVE_MARK_REQUESTS, CNT_WATERMARK_DETECT_LAUNCHES,
-       CNT_WATERMARK_DETECT_CLIPS, CNT_REF_ASSESS_LAUNCHES, CNT_REF_ASSESS_CLIPS, CNT_COUNT };
+       CNT_WATERMARK_DETECT_CLIPS, CNT_REF_ASSESS_LAUNCHES, CNT_REF_ASSESS_CLIPS, CNT_GEMM3_THIN, CNT_TIME_TABLE_BUILDS, CNT_COUNT };
 static long long g_counters[CNT_COUNT] = {};
 
 // Kernel choice per GEMM (measured: profiles/r02_fillrate_microbench.txt, profiles/r01_gemm_microbench.txt):
@@ -562,6 +566,20 @@ static long long g_counters[CNT_COUNT] = {};
 //   else gemm3; implicit-GEMM convolutions in fp16 on gemm.h;
 //   one 128 x 128 tile per CU or fewer, generic epilogue, bf16 / split-bf16 operands: gemm3 (warp-specialised LDS-DMA ring);
 //   everything else (implicit-GEMM convolutions, QKV in split-bf16, many-tile shapes): gemm.h, two 4-wave workgroups per CU.
+// gemm3, generic epilogue: the thin 32-row instance while its grid is one round on the 256 CUs (one 8-wave workgroup per CU).  Measured per
+// shape in profiles/thin_tiles_unit_bench.txt: 0.49 - 0.73 of the 128-row instance's time up to 256 thin workgroups, 1.16 - 1.72 from 352 on
+// (a second round of 32-deep k-steps costs more than the idle CUs of the 128-row grid).  Both instances give a row the same bits, so the
+// choice may depend on M.
+static constexpr long long kThinMaxWorkgroups = 256;
+static int g_thin_force = -1;   // f5hip_op_gemm's timing of both instances on one shape (F5HIP_GEMM3_THIN=0|1, unit op only); -1 on the path
+static hipError_t launch_gemm3_generic_or_thin(int prec, int epi, int bn, const GemmArgs& a, int mp, int np, hipStream_t st) {
+    const long long thin_wgs = (long long)((a.M + 31) / 32) * (np / 128);
+    const bool thin = epi == EPI_GENERIC && bn == 128 && (g_thin_force >= 0 ? g_thin_force != 0 : thin_wgs <= kThinMaxWorkgroups);
+    g_counters[CNT_GEMM3]++;
+    if (!thin) return f5_launch_gemm3(prec, epi, bn, a, mp, np, st);
+    g_counters[CNT_GEMM3_THIN]++;
+    return f5_launch_gemm3_thin(prec, a, np, st);
+}
 static int run_gemm_n(int nsplit, int mp, GemmArgs& a, const PackedW& W, int epi, bool conv, int bn, hipStream_t st) {
     hipError_t e;
     const int np = W.n_pad;
@@ -587,12 +605,10 @@ static int run_gemm_n(int nsplit, int mp, GemmArgs& a, const PackedW& W, int epi
             // gemm3 (round 1): 128 x 256 tile in batch mode (>= 1024 tiles of 128 x 128), 128 x 128 otherwise
             const bool wide = tiles128 >= 1024 && np % 256 == 0;
             if (wide) g_counters[CNT_GEMM3_WIDE]++;
-            g_counters[CNT_GEMM3]++;
-            e = f5_launch_gemm3(3, epi, wide ? 256 : 128, a, mp, np, st);
+            e = launch_gemm3_generic_or_thin(3, epi, wide ? 256 : 128, a, mp, np, st);
         }
     } else if (!conv && tiles128 <= 256 && epi != EPI_QKV) {
-        g_counters[CNT_GEMM3]++;
-        e = f5_launch_gemm3(nsplit, epi, 128, a, mp, np, st);
+        e = launch_gemm3_generic_or_thin(nsplit, epi, 128, a, mp, np, st);
     } else {   // (fp16 convolutions included: BigVGAN in fp16 mode)
         g_counters[bn == 64 ? CNT_GEMM_REG_BN64 : CNT_GEMM_REG_BN128]++;
         e = f5_launch_gemm_reg(nsplit, bn, conv, epi, a, mp, np, st);
@@ -662,7 +678,7 @@ extern "C" int f5hip_get_counter(const char* name, int64_t* value) {
                                            "flac_decode_launches", "flac_decode_streams", "ref_prestep_launches", "ref_prestep_clips",
                                            "wave_prosody_launches", "wave_prosody_requests", "ref_denoise_launches", "ref_denoise_clips",
                                            "wave_mark_launches", "wave_mark_requests", "watermark_detect_launches", "watermark_detect_clips",
-                                           "ref_assess_launches", "ref_assess_clips"};
+                                           "ref_assess_launches", "ref_assess_clips", "gemm3_thin", "time_table_builds"};
     static const char* attn_names[F5_ATTN_CNT_COUNT] = {"attn_bal8", "attn_nw8_deep", "attn_nw8", "attn_nw6_deep", "attn_nw6", "attn_nw4", "attn_seg2"};
     long long* attn = f5_attn_counters();
     if (!name) return fail(-1, "get_counter: null name");
@@ -696,7 +712,7 @@ static int run_text_block(int nsplit, const TextBlock& b, int Td, int M, int n_s
     g1.act = ACT_GELU_ERF; g1.out_f32 = ty; g1.ldo = 2 * Td;
     CK(run_gemm_n(b.pw1.f16 ? 3 : nsplit, M, g1, b.pw1, EPI_GENERIC, false, 128, st));
     prof_begin(PROF_OTHER, st);
-    hipLaunchKernelGGL(grn_stats_kernel, dim3((2 * Td + 255) / 256, n_seq), dim3(256), 0, st, ty, 2 * Td, 2 * Td, seq_row0, seq_len, gx);
+    hipLaunchKernelGGL(grn_stats_kernel, dim3((2 * Td + 31) / 32, n_seq), dim3(256), 0, st, ty, 2 * Td, 2 * Td, seq_row0, seq_len, gx);
     CKL("grn_stats");
     hipLaunchKernelGGL(grn_apply_kernel, dim3((M + 3) / 4), dim3(256), 0, st, ty, 2 * Td, 2 * Td, M, row_seq, gx, b.gamma, b.beta, tg.hi, tg.lo,
                        2 * Td);
@@ -748,10 +764,21 @@ static int precompute_text_and_ce(f5hip_dit* m, const float* cond_dev, hipStream
 
 // time embedding + every AdaLN modulation vector for all steps at once (they depend on t only).  The GEMM chain runs once per block of 128
 // time points over 128 padded rows, so a time point's vectors come out of the same kernels whichever block it sits in.
-static int precompute_time(f5hip_dit* m, const float* t_host, int n_t, hipStream_t st) {
+// The tables depend on the time points and the weights only, and a serving process asks for the same grid (steps, sway, solver) call after
+// call: the handle keeps the list of points its tables were built for (time_key, compared by bytes), and a call with the same list leaves
+// them as they are.  Nothing else writes these buffers; the key is dropped where they move (ensure_workspace) and while a build is under way,
+// so a failed build is never taken for a finished one.  No path replaces a finalized handle's weights (f5hip_dit_load_param refuses after
+// f5hip_dit_finalize), so there is no weight change to drop it for.  The tables of the previous call were written in stream order, which
+// is the order every buffer of the handle relies on from one call to the next.
+// reuse: the whole-grid sampler calls.  Not f5hip_cfm_sample_span, which is handed a moving window of every unit's grid, nor the single
+// forward and the time-table unit op, the diagnostic entries whose launches the tests count call by call: those always build.
+static int precompute_time(f5hip_dit* m, const float* t_host, int n_t, hipStream_t st, bool reuse = false) {
     const f5hip_dit_config& c = m->cfg;
     const int D = c.dim;
     if (n_t > kMaxTimePoints) return fail(-8, "at most %d time points per call (got %d)", kMaxTimePoints, n_t);
+    if (reuse && n_t > 0 && (int)m->time_key.size() == n_t && !memcmp(m->time_key.data(), t_host, sizeof(float) * n_t)) return 0;
+    m->time_key.clear();
+    g_counters[CNT_TIME_TABLE_BUILDS]++;
     const int t_pad = ceil_to(n_t, 128);
     // SinusPositionEmbedding (F/model/modules.py:154-161) on the host: the table is n_t x 256
     std::vector<uint16_t> hi((size_t)t_pad * 256, 0), lo((size_t)t_pad * 256, 0);
@@ -783,6 +810,7 @@ static int precompute_time(f5hip_dit* m, const float* t_host, int n_t, hipStream
         g3.out_f32 = m->mod + (size_t)t0 * m->n_adaln; g3.ldo = m->n_adaln;
         CK(run_gemm(m, g3, m->adaln, EPI_GENERIC, false, 128, st, 128));
     }
+    m->time_key.assign(t_host, t_host + n_t);
     return 0;
 }
 

@@ -11,6 +11,8 @@ hipError_t f5_launch_gemm_reg(int prec, int bn, bool conv, int epi, const GemmAr
 // gemm3.h: warp-specialised LDS-DMA kernel, 128 x bn (128, or 256 for one-plane operands) x 32
 // (gemm.h, gemm3.h, gemm6.h: epi = EPI_GENERIC, EPI_QKV or EPI_GENERIC_ROWMUL -- the last without convolutions)
 hipError_t f5_launch_gemm3(int prec, int epi, int bn, const GemmArgs& a, int m_pad, int n_pad, hipStream_t st);
+// gemm3.h, thin instance: 32 x 128 x 32 tiles over the row tiles that hold a real row, EPI_GENERIC only; bit for bit the rows of f5_launch_gemm3(.., 128, ..)
+hipError_t f5_launch_gemm3_thin(int prec, const GemmArgs& a, int n_pad, hipStream_t st);
 // gemm5.h: exact-fit (16 rb) x (16 cb) tiles, 64-deep k-steps, fp16 operands
 hipError_t f5_launch_gemm5_generic(const GemmArgs& a, int rb, int cb, int n_pad, hipStream_t st);
 hipError_t f5_launch_gemm5_qkv(const GemmArgs& a, int rb, int cb, int n_pad, hipStream_t st);

@@ -1,4 +1,4 @@
-// translation unit: gemm3 kernels (warp-specialised 128 x {128, 256} x 32): bf16 / split-bf16 operands, fp16 when K % 64 != 0
+// translation unit: gemm3 kernels (warp-specialised 128 x {128, 256} x 32, and the thin 32 x 128 x 32): bf16 / split-bf16 operands, fp16 when K % 64 != 0
 #include "gemm3.h"
 #include "gemm_launch.h"
 
@@ -17,4 +17,10 @@ hipError_t f5_launch_gemm3(int prec, int epi, int bn, const GemmArgs& a, int m_p
     if (prec == 3) return qkv ? launch_gemm3_t<3, EPI_QKV>(a, m_pad, n_pad, st) : launch_gemm3_t<3, EPI_GENERIC>(a, m_pad, n_pad, st);
     if (prec == 2) return qkv ? launch_gemm3_t<2, EPI_QKV>(a, m_pad, n_pad, st) : launch_gemm3_t<2, EPI_GENERIC>(a, m_pad, n_pad, st);
     return qkv ? launch_gemm3_t<1, EPI_QKV>(a, m_pad, n_pad, st) : launch_gemm3_t<1, EPI_GENERIC>(a, m_pad, n_pad, st);
+}
+
+hipError_t f5_launch_gemm3_thin(int prec, const GemmArgs& a, int n_pad, hipStream_t st) {
+    if (prec == 3) return launch_gemm3_thin_t<3>(a, n_pad, st);
+    if (prec == 2) return launch_gemm3_thin_t<2>(a, n_pad, st);
+    return launch_gemm3_thin_t<1>(a, n_pad, st);
 }

@@ -133,6 +133,12 @@ static int op_gemm_run(int32_t M, int32_t N, int32_t K, const float* a_dev, cons
     const int M_pad = (M + 127) / 128 * 128, N_pad = (N + 127) / 128 * 128;
     const bool f16 = prec == 3;
     if (w_copies < 1) w_copies = 1;
+    // F5HIP_GEMM3_THIN=0|1: this call's gemm3 launches take the 128-row / the 32-row instance whatever the dispatch rule says (timing both
+    // on one shape: tools/thin_tiles_bench.py); the path never sets it
+    struct ThinForce {
+        ThinForce() { const char* e = getenv("F5HIP_GEMM3_THIN"); g_thin_force = e && *e ? (atoi(e) != 0) : -1; }
+        ~ThinForce() { g_thin_force = -1; }
+    } thin_force;
     OpBufs b;
     Plane2 A;
     A.hi = b.get<__bf16>((size_t)M_pad * K); A.lo = b.get<__bf16>((size_t)M_pad * K);
@@ -838,9 +844,9 @@ extern "C" int f5hip_op_conv_pos_embed(int32_t n_seq, const int32_t* seq_len, in
 // norm.bias [Td], pwconv1.weight [2 Td][Td], pwconv1.bias, grn.gamma, grn.beta [2 Td], pwconv2.weight [Td][2 Td], pwconv2.bias [Td].
 // pad_nan: the padding rows of every internal buffer hold NaN instead of 0.  out_dev fp32 [tokens][Td]; the stage taps (each fp32 or
 // null) as the next kernel reads them: tap_ln [tokens][Td] dwconv + LayerNorm (hi + lo), tap_ty [tokens][2 Td] pwconv1 + GELU, tap_grn
-// [tokens][2 Td] GRN (hi + lo).
-extern "C" int f5hip_op_convnext_block(int32_t n_seq, const int32_t* seq_len, int32_t Td, const float* x_dev, const float* const* params_host,
-                                       int32_t pad_nan, float* out_dev, float* tap_ln_dev, float* tap_ty_dev, float* tap_grn_dev, void* stream) {
+// [tokens][2 Td] GRN (hi + lo); f5hip_op_convnext_block_gx also tap_gx [n_seq][2 Td], the GRN column norms (grn_stats_kernel's output).
+static int op_convnext_block_run(int32_t n_seq, const int32_t* seq_len, int32_t Td, const float* x_dev, const float* const* params_host, int32_t pad_nan,
+                                 float* out_dev, float* tap_ln_dev, float* tap_ty_dev, float* tap_grn_dev, float* tap_gx_dev, void* stream) {
     if (n_seq <= 0 || !seq_len || Td <= 0 || Td % 32 || Td > 1536 || !x_dev || !params_host || !out_dev) return fail(-1, "op_convnext_block: bad argument");
     for (int i = 0; i < 10; i++) if (!params_host[i]) return fail(-1, "op_convnext_block: parameter %d is null", i);
     hipStream_t st = (hipStream_t)stream;
@@ -872,12 +878,22 @@ extern "C" int f5hip_op_convnext_block(int32_t n_seq, const int32_t* seq_len, in
         if (tap_ty_dev) hipLaunchKernelGGL(gather_rows_kernel, dim3(L.frames), dim3(128), 0, st, ty, 2 * Td, 2 * Td, L.frames, L.frame_row, tap_ty_dev, 2 * Td);
         if (tap_grn_dev) hipLaunchKernelGGL(op_gather_planes_kernel, dim3(L.frames), dim3(256), 0, st, tg.hi, tg.lo, 2 * Td, 2 * Td, L.frames, L.frame_row,
                                             tap_grn_dev);
+        if (tap_gx_dev) (void)hipMemcpyAsync(tap_gx_dev, gx, sizeof(float) * (size_t)n_seq * 2 * Td, hipMemcpyDeviceToDevice, st);
         if (hipGetLastError() != hipSuccess) rc = fail(-7, "op_convnext_block: gather launch");
     }
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(-7, "op_convnext_block: %s", hipGetErrorString(hipGetLastError()));
     for (float* p : {tb.dw_w, tb.dw_b, tb.ln_w, tb.ln_b, tb.gamma, tb.beta}) dev_free(p);
     free_packed(tb.pw1); free_packed(tb.pw2);
     return rc;
+}
+extern "C" int f5hip_op_convnext_block(int32_t n_seq, const int32_t* seq_len, int32_t Td, const float* x_dev, const float* const* params_host,
+                                       int32_t pad_nan, float* out_dev, float* tap_ln_dev, float* tap_ty_dev, float* tap_grn_dev, void* stream) {
+    return op_convnext_block_run(n_seq, seq_len, Td, x_dev, params_host, pad_nan, out_dev, tap_ln_dev, tap_ty_dev, tap_grn_dev, nullptr, stream);
+}
+extern "C" int f5hip_op_convnext_block_gx(int32_t n_seq, const int32_t* seq_len, int32_t Td, const float* x_dev, const float* const* params_host,
+                                          int32_t pad_nan, float* out_dev, float* tap_ln_dev, float* tap_ty_dev, float* tap_grn_dev,
+                                          float* tap_gx_dev, void* stream) {
+    return op_convnext_block_run(n_seq, seq_len, Td, x_dev, params_host, pad_nan, out_dev, tap_ln_dev, tap_ty_dev, tap_grn_dev, tap_gx_dev, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- ODE step and time-table unit ops

@@ -300,7 +300,8 @@ CONVNEXT_PARAMS = ("dwconv.weight", "dwconv.bias", "norm.weight", "norm.bias", "
 
 def convnext_block(x, params, *, seq_len, taps=False, pad_nan=False):
     """One ConvNeXtV2 text block of the backbone over packed sequences x fp32 [sum(seq_len), Td]; params: the block's tensors by their
-    state-dict suffix (CONVNEXT_PARAMS).  Returns out, or (out, {"ln", "ty", "grn"}) with taps: each stage as the next kernel reads it."""
+    state-dict suffix (CONVNEXT_PARAMS).  Returns out, or (out, {"ln", "ty", "grn", "gx"}) with taps: each stage as the next kernel reads it,
+    and gx [len(seq_len), 2 Td], the GRN column norms of every sequence."""
     dev = x.device
     x = _f32(x, dev)
     n, Td = x.shape
@@ -310,9 +311,10 @@ def convnext_block(x, params, *, seq_len, taps=False, pad_nan=False):
     arr = (C.c_void_p * 10)(*(a.ctypes.data for a in hp))
     out = torch.empty(n, Td, dtype=torch.float32, device=dev)
     tp = {"ln": torch.empty(n, Td, dtype=torch.float32, device=dev), "ty": torch.empty(n, 2 * Td, dtype=torch.float32, device=dev),
-          "grn": torch.empty(n, 2 * Td, dtype=torch.float32, device=dev)} if taps else {}
-    _lib.check(_lib.lib().f5hip_op_convnext_block(len(sl), _p(sl), Td, _p(x), arr, int(pad_nan), _p(out), _p(tp.get("ln")), _p(tp.get("ty")),
-                                                  _p(tp.get("grn")), _lib.current_stream_ptr()), "f5hip_op_convnext_block")
+          "grn": torch.empty(n, 2 * Td, dtype=torch.float32, device=dev),
+          "gx": torch.empty(len(sl), 2 * Td, dtype=torch.float32, device=dev)} if taps else {}
+    _lib.check(_lib.lib().f5hip_op_convnext_block_gx(len(sl), _p(sl), Td, _p(x), arr, int(pad_nan), _p(out), _p(tp.get("ln")), _p(tp.get("ty")),
+                                                     _p(tp.get("grn")), _p(tp.get("gx")), _lib.current_stream_ptr()), "f5hip_op_convnext_block_gx")
     return (out, tp) if taps else out
 
 
