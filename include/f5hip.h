@@ -688,6 +688,38 @@ int f5hip_wave_prosody(int32_t n, const int16_t* pcm_dev, const int64_t* in_off,
  * of 4 floats); s = 0: the floats of the whole table; -1 for a step outside -6 .. 6. */
 int64_t f5hip_wave_prosody_tap_offset(int32_t pitch);
 
+/* f5hip_wave_prosody with a per-request `keep_formants`: a flagged request's fundamental moves by its pitch step while its spectral envelope
+ * stays (time-domain pitch-synchronous overlap-add), bit for bit wave_codec.shift_pcm16(..., keep_formants=True) = wsola_pcm16 by the
+ * request's (P, Q) -- the caller passes the tempo's stretch alone, reduce(100, T) -- and then wave_codec.psola_pcm16, whose definition is
+ * written down above wave_codec.psola_window (csrc/wave_formant_core.h holds its rules; tools/wave_formant_check.cpp runs them on the CPU
+ * under sanitizers).  Integers only.  On the m = ceil(n P / Q) stretched samples x, xt = x inside the request and 0 elsewhere:
+ *   track        frame f at t = 120 f, ceil(m / 120) frames: d[l] = sum_{i < 480} |xt[t + i] - xt[t + l + i]|, l = 48 .. 400, E = sum_{i < 480}
+ *                |xt[t + i]|; lag = the smallest l with 8 d[l] <= 8 dmin + E, then upwards while d[l + 1] < d[l]; voiced iff E >= 30720 and
+ *                2 d[lag] <= E
+ *   marks        one chain from t = 0 while t < m, in the frame t / 120.  Unvoiced: a = t, T = 120.  Voiced, T = lag: a = the position of the
+ *                largest sample in [t, t + T) after an unvoiced mark or first, in [max(t - T / 8, a_prev + 24), t + T / 8] after a voiced
+ *                one; inside the wave, ties to the earlier position.  t = a + T
+ *   synthesis    u_0 = a_0; u takes the nearest analysis mark i, ties to the earlier; voiced: u += (T_i q + rem) / p, rem = (T_i q + rem) % p
+ *                (p / q as in f5hip_wave_prosody); unvoiced: u += 120; while u < m
+ *   output       over the marks with |j - u| <= T_i: w = M[(|j - u| 1024) / T_i] (csrc/psola_window.inc = wave_codec.psola_window()), num +=
+ *                w xt[a_i + j - u], den += w; y[j] = clip(floor((2 num + den) / (2 den))), y[j] = x[j] where den = 0.  m samples
+ *   keep_formants   host uint8 [n]: non-zero flags request i, which must have a pitch; every other argument as in f5hip_wave_prosody
+ * A call without a flagged request launches what f5hip_wave_prosody launches.  Otherwise THREE more launches whatever n
+ * (f5hip_wave_prosody_formants_launches), behind the WSOLA launch, which leaves the flagged requests' stretched samples in the workspace
+ * (wave_period_kernel: one block per tile of 5 frames of a flagged request, its 1360 samples in LDS biased by 32768 and twice, one sample
+ * apart, the 5 x 354 sums across the threads as packed 16-bit absolute differences, two min-reductions per frame; wave_marks_kernel: one
+ * wavefront per flagged request chains the analysis marks, the peak search across the lanes by a keyed maximum, and hands out the synthesis
+ * marks as it goes, the counts stay on the device; wave_psola_kernel: one block per 2048 outputs, the at most 87 marks around the tile by
+ * binary search, 8 samples a thread in a 16-byte store); the resampler launch only when another request has a plain pitch.  No atomics, no
+ * accumulator buffer, no host sync; a request's bytes depend on that request alone (counters wave_formant_launches, wave_formant_requests).
+ * Refused before the first launch: what f5hip_wave_prosody refuses, a null keep_formants, a flagged request without a pitch. */
+int f5hip_wave_prosody_formants(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
+                                const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const uint8_t* keep_formants,
+                                const float* taps_dev, int16_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, void* stream);
+
+/* Launches f5hip_wave_prosody_formants adds for a call with a flagged request (3).  For tests. */
+int f5hip_wave_prosody_formants_launches(void);
+
 /* FLAC in: n native FLAC streams (RFC 9639) -- uploaded reference clips and recordings, which the reference reads with torchaudio.load
  * (F/infer/utils_infer.py:376) -- packed at arbitrary byte offsets in one device buffer -> each stream's samples as int32 planes
  * [channels, total], bit for bit wave_codec.read_flac, which defines the format accepted: every subframe type, LPC order 1 .. 32, both Rice

@@ -126,6 +126,8 @@ SYMBOLS = {
     "f5hip_wave_loudness_tile": (C.c_int, []),
     "f5hip_wave_prosody": (C.c_int, [C.c_int32] + [C.c_void_p] * 12),
     "f5hip_wave_prosody_tap_offset": (C.c_int64, [C.c_int32]),
+    "f5hip_wave_prosody_formants": (C.c_int, [C.c_int32] + [C.c_void_p] * 13),
+    "f5hip_wave_prosody_formants_launches": (C.c_int, []),
     "f5hip_flac_decode": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 9),
     "f5hip_flac_decode_bound": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "f5hip_ref_prestep": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

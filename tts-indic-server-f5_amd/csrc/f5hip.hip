@@ -548,7 +548,8 @@ static GemmArgs gemm_base(const Plane2& A, int lda, const PackedW& W, int M) {
 // launched and the streams it was given; ref_prestep_launches / ref_prestep_clips: the same for f5hip_ref_prestep and its clips;
 // wave_prosody_launches / wave_prosody_requests: kernels f5hip_wave_prosody launched and the requests whose tempo or pitch it changed;
 // ref_denoise_launches / ref_denoise_clips: kernels f5hip_ref_denoise launched and the clips it denoised; wave_mark_launches /
-// wave_mark_requests: kernels f5hip_wave_mark launched and the requests it marked; watermark_detect_launches / watermark_detect_clips:
+// wave_mark_requests: kernels f5hip_wave_mark launched and the requests it marked; wave_formant_launches / wave_formant_requests: the
+// kernels f5hip_wave_prosody_formants launched beyond f5hip_wave_prosody's and the requests that kept their formants; watermark_detect_launches / watermark_detect_clips:
 // kernels f5hip_watermark_detect launched and the clips it scored; ref_assess_launches / ref_assess_clips: kernels f5hip_ref_assess launched
 // and the clips it measured; gemm3_thin: the gemm3 launches (counted in gemm3 too) that took the 32-row instance; time_table_builds: calls of
 // precompute_time that built the tables (the others found the handle's tables built for the same time points)
@@ -557,7 +558,8 @@ enum { CNT_GEMM5_RB11, CNT_GEMM5_RB8, CNT_GEMM5_WIDE, CNT_GEMM3_WIDE, CNT_CONV5,
        CNT_WAVE_REQUESTS, CNT_WAVE_ENCODE_LAUNCHES, CNT_WAVE_ENCODE_REQUESTS, CNT_MEL_RAGGED_LAUNCHES, CNT_MEL_RAGGED_ITEMS, CNT_WAVE_FLAC_LAUNCHES,
        CNT_WAVE_FLAC_REQUESTS, CNT_WAVE_LOUDNESS_LAUNCHES, CNT_WAVE_LOUDNESS_REQUESTS, CNT_FLAC_DECODE_LAUNCHES, CNT_FLAC_DECODE_STREAMS,
        CNT_REF_PRESTEP_LAUNCHES, CNT_REF_PRESTEP_CLIPS, CNT_WAVE_PROSODY_LAUNCHES, CNT_WAVE_PROSODY_REQUESTS,
-       CNT_REF_DENOISE_LAUNCHES, CNT_REF_DENOISE_CLIPS, CNT_WAVE_MARK_LAUNCHES, CNT_WAVE_MARK_REQUESTS, CNT_WATERMARK_DETECT_LAUNCHES,
+       CNT_REF_DENOISE_LAUNCHES, CNT_REF_DENOISE_CLIPS, CNT_WAVE_MARK_LAUNCHES, CNT_WAVE_MARK_REQUESTS, CNT_WAVE_FORMANT_LAUNCHES,
+       CNT_WAVE_FORMANT_REQUESTS, CNT_WATERMARK_DETECT_LAUNCHES,
        CNT_WATERMARK_DETECT_CLIPS, CNT_REF_ASSESS_LAUNCHES, CNT_REF_ASSESS_CLIPS, CNT_GEMM3_THIN, CNT_TIME_TABLE_BUILDS, CNT_COUNT };
 static long long g_counters[CNT_COUNT] = {};
 
@@ -677,7 +679,8 @@ extern "C" int f5hip_get_counter(const char* name, int64_t* value) {
                                            "wave_flac_launches", "wave_flac_requests", "wave_loudness_launches", "wave_loudness_requests",
                                            "flac_decode_launches", "flac_decode_streams", "ref_prestep_launches", "ref_prestep_clips",
                                            "wave_prosody_launches", "wave_prosody_requests", "ref_denoise_launches", "ref_denoise_clips",
-                                           "wave_mark_launches", "wave_mark_requests", "watermark_detect_launches", "watermark_detect_clips",
+                                           "wave_mark_launches", "wave_mark_requests", "wave_formant_launches", "wave_formant_requests",
+                                           "watermark_detect_launches", "watermark_detect_clips",
                                            "ref_assess_launches", "ref_assess_clips", "gemm3_thin", "time_table_builds"};
     static const char* attn_names[F5_ATTN_CNT_COUNT] = {"attn_bal8", "attn_nw8_deep", "attn_nw8", "attn_nw6_deep", "attn_nw6", "attn_nw4", "attn_seg2"};
     long long* attn = f5_attn_counters();
@@ -1150,3 +1153,4 @@ int f5hip_dit_set_ode_method(f5hip_dit* m, int32_t method) {
 #include "ref_denoise.h"
 #include "wave_mark.h"
 #include "ref_assess.h"
+#include "wave_formant.h"

@@ -22,6 +22,7 @@
 //   torch.ops.f5hip.ref_prestep(frames, n_in, channels, clip_short, rate) -> (Tensor planes fp32, Tensor info int32 [n, 2])   F/infer/utils_infer.py:282-350
 //   torch.ops.f5hip.wave_loudness(pcm, in_off, max_len, len_dev?, gain_k) -> Tensor stats int64 [n, 4]; pcm is normalised in place
 //   torch.ops.f5hip.wave_prosody(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, taps?) -> (Tensor pcm int16, Tensor lengths int32, Tensor offsets int64 host, Tensor bounds int32 host)
+//   torch.ops.f5hip.wave_prosody_formants(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, keep_formants, taps?) -> the same four
 //   torch.ops.f5hip.ref_denoise(wave, offset, n_samples) -> ()   the flagged clips of wave (f5hip_ref_frontend's packed output) are denoised in place
 //   torch.ops.f5hip.wave_mark(pcm, in_off, max_len, len_dev?, key_index, carriers?) -> ()   the flagged requests of pcm get their key's provenance mark in place
 //   torch.ops.f5hip.ref_assess(raw, raw_offset, channels, raw_len, wave, offset, n_samples) -> Tensor rows int64 [n, 10]: the reference-clip report
@@ -590,10 +591,12 @@ at::Tensor wave_loudness(at::Tensor pcm, const at::Tensor& in_off, const at::Ten
 // stretch_p, stretch_q, pitch [n] int32 host; taps: the twelve pitch tables as one fp32 device tensor (f5hip_wave_prosody_tap_offset), needed
 // when a request has a pitch -> (out int16 device: request i's samples at out_off[i]; out_len [n] int32 device; out_off [n] int64 host, each
 // a multiple of 8; bounds [n] int32 host: the length that max_len[i] gives)
-std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody(const at::Tensor& pcm, const at::Tensor& in_off, const at::Tensor& max_len,
-                                                                        const c10::optional<at::Tensor>& len_dev, const at::Tensor& stretch_p,
-                                                                        const at::Tensor& stretch_q, const at::Tensor& pitch,
-                                                                        const c10::optional<at::Tensor>& taps) {
+// keep: null for wave_prosody; wave_prosody_formants' uint8 [n] host flags (a flagged request keeps its formants: no resampler, the length
+// of its stretch alone)
+static std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody_call(const at::Tensor& pcm, const at::Tensor& in_off, const at::Tensor& max_len,
+                                                                                   const c10::optional<at::Tensor>& len_dev, const at::Tensor& stretch_p,
+                                                                                   const at::Tensor& stretch_q, const at::Tensor& pitch,
+                                                                                   const at::Tensor* keep, const c10::optional<at::Tensor>& taps) {
     const PcmRequests rq = check_pcm_requests("wave_prosody", pcm, in_off, max_len, len_dev, false);
     const int64_t n = rq.n;
     const int32_t* ml = rq.ml;
@@ -604,6 +607,12 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody(const at
     const int32_t* sp = stretch_p.data_ptr<int32_t>();
     const int32_t* sq = stretch_q.data_ptr<int32_t>();
     const int32_t* pt = pitch.data_ptr<int32_t>();
+    const uint8_t* kp = nullptr;
+    if (keep) {
+        check_host(*keep, at::kByte, "keep_formants");
+        TORCH_CHECK(keep->numel() == n, "f5hip::wave_prosody: keep_formants needs one value per request");
+        kp = keep->data_ptr<uint8_t>();
+    }
     at::Tensor out_off = at::empty({n}, at::TensorOptions().dtype(at::kLong)), bounds = at::empty({n}, at::TensorOptions().dtype(at::kInt));
     int64_t* oo = out_off.data_ptr<int64_t>();
     int32_t* bd = bounds.data_ptr<int32_t>();
@@ -614,7 +623,9 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody(const at
                     ": positive terms up to 2^20 and a ratio from 1/2 to 2");
         TORCH_CHECK(pt[i] >= -kPrPitchMax && pt[i] <= kPrPitchMax, "f5hip::wave_prosody: request ", i, " has a pitch of ", pt[i], " semitones (-6 to 6)");
         int64_t m = pr_geom(ml[i], sp[i], sq[i]).m;
-        if (pt[i]) {
+        if (kp && kp[i]) {
+            TORCH_CHECK(pt[i] != 0, "f5hip::wave_prosody: request ", i, " keeps its formants without a pitch");
+        } else if (pt[i]) {
             int p, q;
             pr_pitch_ratio(pt[i], &p, &q);
             m = (q * m + p - 1) / p;
@@ -633,10 +644,28 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody(const at
     const c10::DeviceGuard guard(rq.device);
     at::Tensor out = at::empty({std::max<int64_t>(total, 8)}, pcm.options()).slice(0, 0, total);   // (a call of empty requests still has an address to give)
     at::Tensor out_len = at::empty({n}, pcm.options().dtype(at::kInt));
-    const int rc = f5hip_wave_prosody((int32_t)n, src.base(), src.rel.data(), ml, rq.len_dev, sp, sq, pt, pitched ? taps->data_ptr<float>() : (const float*)nullptr,
-                                      out.data_ptr<int16_t>(), oo, out_len.data_ptr<int32_t>(), stream_of(pcm));
-    TORCH_CHECK(rc == 0, "f5hip_wave_prosody: ", f5hip_last_error());
+    const float* tp = pitched ? taps->data_ptr<float>() : (const float*)nullptr;
+    const int rc = kp ? f5hip_wave_prosody_formants((int32_t)n, src.base(), src.rel.data(), ml, rq.len_dev, sp, sq, pt, kp, tp, out.data_ptr<int16_t>(), oo,
+                                                    out_len.data_ptr<int32_t>(), stream_of(pcm))
+                      : f5hip_wave_prosody((int32_t)n, src.base(), src.rel.data(), ml, rq.len_dev, sp, sq, pt, tp, out.data_ptr<int16_t>(), oo,
+                                           out_len.data_ptr<int32_t>(), stream_of(pcm));
+    TORCH_CHECK(rc == 0, kp ? "f5hip_wave_prosody_formants: " : "f5hip_wave_prosody: ", f5hip_last_error());
     return {out, out_len, out_off, bounds};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody(const at::Tensor& pcm, const at::Tensor& in_off, const at::Tensor& max_len,
+                                                                        const c10::optional<at::Tensor>& len_dev, const at::Tensor& stretch_p,
+                                                                        const at::Tensor& stretch_q, const at::Tensor& pitch,
+                                                                        const c10::optional<at::Tensor>& taps) {
+    return wave_prosody_call(pcm, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, nullptr, taps);
+}
+
+// wave_prosody with keep_formants [n] uint8 host: a flagged request (it must have a pitch) keeps its spectral envelope (f5hip_wave_prosody_formants)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody_formants(const at::Tensor& pcm, const at::Tensor& in_off, const at::Tensor& max_len,
+                                                                                 const c10::optional<at::Tensor>& len_dev, const at::Tensor& stretch_p,
+                                                                                 const at::Tensor& stretch_q, const at::Tensor& pitch,
+                                                                                 const at::Tensor& keep_formants, const c10::optional<at::Tensor>& taps) {
+    return wave_prosody_call(pcm, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, &keep_formants, taps);
 }
 
 // wave: the contiguous 1-D fp32 device tensor that holds every clip (f5hip_ref_frontend's packed output), denoised IN PLACE; offset [n] int64
@@ -774,6 +803,8 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("wave_loudness(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor gain_k) -> Tensor", &wave_loudness);
     m.def("wave_prosody(Tensor pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor stretch_p, Tensor stretch_q, Tensor pitch, Tensor? taps) -> "
           "(Tensor, Tensor, Tensor, Tensor)", &wave_prosody);
+    m.def("wave_prosody_formants(Tensor pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor stretch_p, Tensor stretch_q, Tensor pitch, "
+          "Tensor keep_formants, Tensor? taps) -> (Tensor, Tensor, Tensor, Tensor)", &wave_prosody_formants);
     m.def("ref_denoise(Tensor(a!) wave, Tensor offset, Tensor n_samples) -> ()", &ref_denoise);
     m.def("wave_mark(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor key_index, Tensor? carriers) -> ()", &wave_mark);
     m.def("watermark_detect(Tensor wave, Tensor offset, Tensor n_samples, Tensor carriers) -> Tensor", &watermark_detect);

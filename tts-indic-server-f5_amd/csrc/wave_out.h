@@ -1399,7 +1399,8 @@ int f5hip_wave_loudness(int32_t n, int16_t* pcm_dev, const int64_t* in_off, cons
 //                      over the packed key cost * 2^9 + rank(d) (64-bit shuffles, then 4 words of LDS), so the choice does not depend on lane
 //                      order.  Frame k's placement finalises the H outputs of frame k - 1, blended from the LDS copies -- no second read of
 //                      the samples, no accumulator buffer, no atomics --, 8 samples in a 16-byte vector store.  A request with P == Q is
-//                      copied through.  A request with a pitch leaves its stretched PCM in the workspace for the second launch.
+//                      copied through.  A request with a pitch leaves its stretched PCM in the workspace for the second launch, and so does one that
+//                      keeps its formants (wave_formant.h), for the three launches of f5hip_wave_prosody_formants.
 //   wave_pitch_kernel  wave_encode_kernel's tile body (we_tile_body) with the rate pair p : q, the tile size and the tap table of the
 //                      REQUEST: one block per tile of a pitched request, its table (below 11 KB) staged in LDS from the one device table
 //                      that holds all twelve.
@@ -1423,7 +1424,7 @@ struct PrReq {
     int of, nf, width, L;// pitched: p : q and its tap table's shape; of == 0: no pitch
     int tq, tap_off;     // pitched: polyphase blocks per tile, its table's first float in the device table
     int tile0;           // pitched: its first block of the second launch
-    int pad;
+    int keep;            // it keeps its formants (wave_formant.h): its stretched PCM stays in the workspace like a pitched request's, of == 0
 };
 
 F5_DEVICE int pr_len(const int* len_dev, const PrReq& q) { return len_dev ? min(max(len_dev[q.req], 0), q.cap) : q.cap; }
@@ -1440,7 +1441,7 @@ __global__ __launch_bounds__(kPrThreads) void wave_wsola_kernel(const PrReq* __r
     const int len = pr_len(len_dev, q);
     const PrGeom g = pr_geom(len, q.P, q.Q);
     const short* x = pcm + q.in_off;
-    short* y = q.of ? mid + q.mid_off : out + q.out_off;
+    short* y = (q.of | q.keep) ? mid + q.mid_off : out + q.out_off;
     if (!q.of && tid == 0) out_len[q.req] = (int)g.m;
     if (q.P == q.Q) {                                                   // neutral: copied through (g.m == len)
         const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
@@ -1553,9 +1554,18 @@ int64_t f5hip_wave_prosody_tap_offset(int32_t pitch) {
     return at;   // pitch == 0: the whole table
 }
 
-int f5hip_wave_prosody(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
-                       const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const float* taps_dev, int16_t* out_dev,
-                       const int64_t* out_off, int32_t* out_len_dev, void* stream) {
+// a request that keeps its formants, as the WSOLA launch left it: what wave_formant.h's three launches start from
+struct PrKept {
+    long long mid_off, out_off;
+    int cap, req, P, Q, pitch;
+};
+
+// f5hip_wave_prosody, and with `keep` (per request; null: nobody) the first part of f5hip_wave_prosody_formants: a flagged request is
+// stretched by its (P, Q) into the workspace and listed in `kept`; *mid_out is the workspace's stretched PCM
+static int wave_prosody_run(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
+                            const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const uint8_t* keep, const float* taps_dev,
+                            int16_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, std::vector<PrKept>* kept, const short** mid_out,
+                            void* stream) {
     if (n < 1 || !pcm_dev || !in_off || !max_len || !stretch_p || !stretch_q || !pitch || !out_dev || !out_off || !out_len_dev)
         return fail(-1, "wave_prosody: bad argument");
     if ((reinterpret_cast<uintptr_t>(pcm_dev) & 1) || (reinterpret_cast<uintptr_t>(len_dev) & 3) || (reinterpret_cast<uintptr_t>(taps_dev) & 15) ||
@@ -1577,7 +1587,12 @@ int f5hip_wave_prosody(int32_t n, const int16_t* pcm_dev, const int64_t* in_off,
         q.in_off = in_off[i]; q.out_off = out_off[i]; q.cap = max_len[i]; q.req = i; q.P = stretch_p[i]; q.Q = stretch_q[i];
         long long m = pr_geom(max_len[i], q.P, q.Q).m;
         if (m > 2147483647LL) return fail(-1, "wave_prosody: the call exceeds 2^31 - 1 samples in or out");
-        if (pitch[i]) {
+        if (keep && keep[i]) {
+            if (!pitch[i]) return fail(-1, "wave_prosody: request %d keeps its formants without a pitch", i);
+            q.keep = 1; q.mid_off = mid;
+            mid += (m + 7) & ~7LL;
+            kept->push_back(PrKept{q.mid_off, q.out_off, q.cap, i, q.P, q.Q, pitch[i]});
+        } else if (pitch[i]) {
             if (!taps_dev) return fail(-1, "wave_prosody: request %d has a pitch: the call needs the tap table", i);
             int p, qq;
             pr_pitch_ratio(pitch[i], &p, &qq);
@@ -1602,9 +1617,9 @@ int f5hip_wave_prosody(int32_t n, const int16_t* pcm_dev, const int64_t* in_off,
     if (!wsp) return -6;
     PrWorkspace& ws = *wsp;
     CK(dev_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_prosody requests"));
+    if (!hp.empty() || (kept && !kept->empty())) CK(dev_reserve(&ws.mid, &ws.cap_mid, (size_t)std::max<long long>(mid, 8), "wave_prosody stretched PCM"));
     if (!hp.empty()) {
         CK(dev_reserve(&ws.pitched, &ws.cap_pitched, hp.size(), "wave_prosody pitched requests"));
-        CK(dev_reserve(&ws.mid, &ws.cap_mid, (size_t)std::max<long long>(mid, 8), "wave_prosody stretched PCM"));
         static unsigned lds_attr_done = 0;
         if (lds > 64 * 1024 && f5_set_lds_attr((const void*)wave_pitch_kernel, kLdsMax, lds_attr_done) != hipSuccess)
             return fail(-7, "wave_prosody: LDS opt-in");
@@ -1623,5 +1638,13 @@ int f5hip_wave_prosody(int32_t n, const int16_t* pcm_dev, const int64_t* in_off,
         g_counters[CNT_WAVE_PROSODY_LAUNCHES]++;
     }
     g_counters[CNT_WAVE_PROSODY_REQUESTS] += changed;
+    if (mid_out) *mid_out = ws.mid;
     return 0;
+}
+
+int f5hip_wave_prosody(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
+                       const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const float* taps_dev, int16_t* out_dev,
+                       const int64_t* out_off, int32_t* out_len_dev, void* stream) {
+    return wave_prosody_run(n, pcm_dev, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, nullptr, taps_dev, out_dev, out_off, out_len_dev, nullptr,
+                            nullptr, stream);
 }

@@ -41,6 +41,7 @@ from .wave_codec import (ALL_ENCODINGS, DELIVERY_OPTIONS, FLAC_BLOCK, FLAC_ENCOD
                          StreamResampler, WaveSpec, check_flac_level, decode_flac, decode_g711, deliver_pcm16,
                          delivery_format, encode_flac, encode_g711, flac_crc8, flac_crc16, flac_stream_header, load_audio, load_wav, quantise_pcm16, read_flac,
                          rate_pair, request_flac_level, resample_pcm16, resample_sinc_hann, resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
+from .wave_codec import FORMANT_OPTIONS, check_keep_formants, formant_stretch, psola_pcm16  # noqa: F401
 from .wave_codec import (PITCH_RANGE, PITCH_RATIOS, PROSODY_OPTIONS, WHOLE_WAVE_PROSODY, check_pitch, check_tempo, shift_pcm16,  # noqa: F401
                          shifted_length, wsola_pcm16)
 from .wave_codec import (WATERMARK_BAND, WATERMARK_BLOCK, WATERMARK_KEYS_MAX, WATERMARK_MAX_SAMPLES, WATERMARK_MIN_SAMPLES,  # noqa: F401
@@ -699,8 +700,8 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 
 # per-request options of `infer_requests` (the fourth element of a request) and of the serving routes
 REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "remove_silence", "sample_rate", "encoding",
-                   "loudness", "flac_level") + WATERMARK_OPTIONS + PROSODY_OPTIONS   # the sampler's six, then `DELIVERY_OPTIONS`, `watermark` (carried
-#                                                                                       beside the spec) and `PROSODY_OPTIONS` (`WaveSpec`)
+                   "loudness", "flac_level") + WATERMARK_OPTIONS + FORMANT_OPTIONS + PROSODY_OPTIONS   # the sampler's six, then `DELIVERY_OPTIONS`,
+#                                            `watermark` and `keep_formants` (both carried beside the spec) and `PROSODY_OPTIONS` (`WaveSpec`)
 
 
 def needs_whole_wave(opts, streamed=False) -> bool:
@@ -733,6 +734,7 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
     if unknown:
         raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
     spec, watermark = WaveSpec.of(opts), check_watermark(opts.get("watermark"))
+    keep_formants = check_keep_formants(opts.get("keep_formants"), spec.pitch)   # (with a pitch only: the whole-wave rule below is the pitch's)
     if (spec.needs_whole_wave() or watermark is not None) and isinstance(request_text(request), (list, tuple)):   # (a mark needs the whole wave)
         raise ValueError(_whole_wave_message(spec, watermark))
     # one (voice, units) part per segment; a plain request is its own single segment
@@ -746,7 +748,7 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
     def commit():
         if own is not None:
             own.set_state(gen.get_state())
-    return types.SimpleNamespace(voice=voice, units=units, opts=opts, spec=spec, watermark=watermark, generator=gen, commit=commit, parts=parts, script=script)
+    return types.SimpleNamespace(voice=voice, units=units, opts=opts, spec=spec, watermark=watermark, keep_formants=keep_formants, generator=gen, commit=commit, parts=parts, script=script)
 
 
 def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, target_rms=target_rms,
@@ -833,7 +835,7 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
         got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms, on_device=backend, want_specs=False)
         chunk_waves = [request_chunk_waves(plan, got[per_plan[i]:per_plan[i + 1]]) for i, plan in enumerate(plans)]
         return _finish_specs(chunk_waves, [request_text(req) for req in requests], cross_fade_duration, [plan.spec for plan in plans],
-                             watermark=[plan.watermark for plan in plans], **finish)
+                             watermark=[plan.watermark for plan in plans], keep_formants=[plan.keep_formants for plan in plans], **finish)
     refused = next((plan for plan in plans if plan.spec.needs_whole_wave() or plan.watermark is not None), None)
     if refused is not None and not join:
         raise ValueError(_whole_wave_message(refused.spec, refused.watermark))
@@ -844,7 +846,8 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
         if join:   # a script: (wave, rate, [spectrogram per segment]) like `infer_multi_voice`
             joined_specs = [np.concatenate(specs, axis=1) for _, specs in mine]
             if script or plan.spec.needs_whole_wave() or plan.watermark is not None:
-                wave, = _finish_specs([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [plan.spec], watermark=[plan.watermark])
+                wave, = _finish_specs([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [plan.spec], watermark=[plan.watermark],
+                                      keep_formants=[plan.keep_formants])
             else:
                 wave = cross_fade_concat(mine[0][0], cross_fade_duration)
             out.append((wave, plan.spec.sample_rate, joined_specs if script else joined_specs[0]))
@@ -887,7 +890,8 @@ def _per_request(value, n, what):
 
 
 def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cross_fade_duration, remove_silence=None, device_backend=False,
-                    want="float", sample_rate=None, encoding=None, loudness=None, flac_level=None, tempo=None, pitch=None, watermark=None):
+                    want="float", sample_rate=None, encoding=None, loudness=None, flac_level=None, tempo=None, pitch=None, watermark=None,
+                    keep_formants=None):
     """From the chunk waves of several requests (rms restored; numpy, or tensors as `_chunk_waves(on_device=True)` leaves them) to what each
     request gets.  A request whose text is a list of chunk texts (a streamed request's head or tail) gets its chunk waves as they are, like
     `request_wave`; a script's (`SegmentedWaves`: one list of chunk waves per segment) as one list per segment.  Any other request gets its
@@ -905,6 +909,8 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     the request's `WaveSpec`, and a request that sets any of them gets `finish_pcm16` of its int16 PCM (quantised whatever `want` says).
     `watermark`: one key or one per request (`check_watermark`; None: no mark), carried beside the spec: the request's PCM gets `mark_pcm16`
     between the prosody and the loudness steps.
+    `keep_formants`: one bool or one per request (`check_keep_formants`; None: no), carried beside the spec too: with it the request's
+    `pitch` keeps the spectral envelope (`shift_pcm16(..., keep_formants=True)`); without a pitch it is refused.
     With `device_backend` all of it stays on the device, chained on one stream behind `wave_finish`: the calls and the copies that come back
     are `_finish_on_device`'s, and `backend_stats` counts them."""
     _check_want(device_backend, want)   # (first, as ever: a bad `want` is reported before a bad option)
@@ -918,7 +924,8 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     specs = [WaveSpec.of(dict(remove_silence=flag, sample_rate=rate, encoding=enc, loudness=lufs, flac_level=level, tempo=rate_of_speech, pitch=semitones))
              for flag, rate, enc, lufs, level, rate_of_speech, semitones in zip(flags, *columns)]
     marks = [check_watermark(key) for key in _per_request(watermark, n, "watermark")]
-    return _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend, want, marks)
+    keeps = [check_keep_formants(keep, spec.pitch) for keep, spec in zip(_per_request(keep_formants, n, "keep_formants"), specs)]
+    return _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend, want, marks, keeps)
 
 
 def _check_want(device_backend, want):
@@ -928,11 +935,13 @@ def _check_want(device_backend, want):
         raise ValueError('the device back-end produces int16 PCM: device_backend=True needs want="pcm16"')
 
 
-def _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend=False, want="float", watermark=None):
+def _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend=False, want="float", watermark=None,
+                  keep_formants=None):
     """`finish_requests` with one planned `WaveSpec` per request in place of its option keywords, and beside them one watermark key per
-    request (None: no request is marked): what `infer_requests` and `SpanScheduler` call."""
+    request (None: no request is marked) and one `keep_formants` flag (None: nobody): what `infer_requests` and `SpanScheduler` call."""
     _check_want(device_backend, want)
     marks = [None] * len(specs) if watermark is None else list(watermark)
+    keeps = [False] * len(specs) if keep_formants is None else [bool(k) for k in keep_formants]
     fade = int(cross_fade_duration * target_sample_rate) if cross_fade_duration > 0 else 0
     out, on_device = [None] * len(specs), []
     for i, (waves, text, spec) in enumerate(zip(chunk_waves_per_request, gen_texts, specs)):
@@ -948,13 +957,13 @@ def _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs
             on_device.append(i)
             continue
         else:
-            out[i] = _finish_on_host(waves, text, cross_fade_duration, spec, want, marks[i])
+            out[i] = _finish_on_host(waves, text, cross_fade_duration, spec, want, marks[i], keeps[i])
         backend_stats["host_requests"] += 1
     if on_device:
         # the plain requests first: their PCM is then one prefix of the packed buffer, and what comes down of it holds no other request's
         on_device.sort(key=lambda i: not specs[i].plain_format)
         done = _finish_on_device([_device_request(chunk_waves_per_request[i]) for i in on_device], fade, [specs[i] for i in on_device],
-                                 [marks[i] for i in on_device])
+                                 [marks[i] for i in on_device], [keeps[i] for i in on_device])
         for i, wave in zip(on_device, done):
             out[i] = wave
     return out
@@ -984,35 +993,38 @@ def _device_request(waves):
     return chunks, fades
 
 
-def finish_pcm16(pcm, spec, watermark=None) -> np.ndarray:
-    """What a `WaveSpec`, and the `watermark` key beside it, make of a request's 24 kHz int16 PCM, the one host definition (the device
-    back-end and `StreamDelivery` are held to it byte for byte): `remove_silence_pcm` when flagged, `shift_pcm16` (tempo and pitch),
+def finish_pcm16(pcm, spec, watermark=None, keep_formants=False) -> np.ndarray:
+    """What a `WaveSpec`, and the `watermark` key and the `keep_formants` flag beside it, make of a request's 24 kHz int16 PCM, the one
+    host definition (the device back-end and `StreamDelivery` are held to it byte for byte): `remove_silence_pcm` when flagged,
+    `shift_pcm16` (tempo and pitch; with `keep_formants` the pitch by `psola_pcm16`, which keeps the spectral envelope),
     `mark_pcm16` with a key -- so the loudness and the -1 dBFS peak cap are measured on the marked samples, and the one gain behind it does
     not disturb the scale-invariant detector --, `normalise_loudness_pcm16`, `deliver_pcm16`."""
     if spec.remove_silence:
         pcm = remove_silence_pcm(pcm, target_sample_rate)
-    pcm = shift_pcm16(pcm, spec.tempo, spec.pitch)
+    pcm = shift_pcm16(pcm, spec.tempo, spec.pitch, keep_formants=keep_formants)
     pcm = mark_pcm16(pcm, watermark)
     pcm = normalise_loudness_pcm16(pcm, spec.loudness)
     return deliver_pcm16(pcm, *spec.format, flac_level=spec.flac_level if spec.flac else None)
 
 
-def _finish_on_host(waves, text, cross_fade_duration, spec, want, watermark=None):
+def _finish_on_host(waves, text, cross_fade_duration, spec, want, watermark=None, keep_formants=False):
     """`finish_requests` for one request on the host: join, quantisation where anything asks for PCM, `finish_pcm16`."""
     if isinstance(waves, SegmentedWaves):
         wave = join_segments([[_host_chunk(w) for w in seg] for seg in waves], cross_fade_duration, waves.gap_samples)
     else:
         wave = request_wave(text, [_host_chunk(w) for w in waves], cross_fade_duration)
     if spec.needs_whole_wave() or watermark is not None:
-        return finish_pcm16(quantise_pcm16(wave), spec, watermark)
+        return finish_pcm16(quantise_pcm16(wave), spec, watermark, keep_formants)
     return quantise_pcm16(wave) if want == "pcm16" else wave   # (nothing to finish: no pass through the three steps' own checks)
 
 
-def _finish_on_device(requests, fade, specs, watermark=None):
+def _finish_on_device(requests, fade, specs, watermark=None, keep_formants=None):
     """`finish_requests` for the requests the device back-end takes: `requests` = (chunk waves (device tensors), fades: `_device_request`)
     and their `specs`, the plain-format ones first.  ONE `ops.wave_finish` call -- `ops.wave_finish_joins` when a script is among them --;
     directly behind it, when any request names a tempo or a pitch, ONE `ops.wave_prosody` call for the whole batch (the others are copied
-    through), whose buffer, offsets, bounds and device lengths everything downstream reads in the place of `wave_finish`'s;
+    through), whose buffer, offsets, bounds and device lengths everything downstream reads in the place of `wave_finish`'s -- with a flag in
+    `keep_formants` (one per request, None: nobody) the same ONE call, flagged and unflagged requests together: a flagged request takes the
+    stretch of its tempo alone and keeps its spectral envelope (`backend_stats["formant_requests"]`);
     then, when any request has a key in `watermark` (one per request, None: nobody), ONE `ops.wave_mark` call that marks those in place
     (carriers cached on the device: nothing is uploaded for a key seen before, and nothing comes back);
     then, when any request has a loudness target, ONE `ops.wave_loudness` call that normalises those in place; then on the
@@ -1038,7 +1050,13 @@ def _finish_on_device(requests, fade, specs, watermark=None):
     else:
         pcm, lengths, offsets = ops.wave_finish_joins(chunks, counts, fade, [x for f in fades for x in f], silence, target_sample_rate)
     if any(spec.prosody for spec in specs):   # one call for the batch; lengths stay on the device, and `joined` becomes the new bounds
-        pcm, lengths, offsets, joined = ops.wave_prosody(pcm, offsets, joined, lengths, [spec.stretch for spec in specs], [spec.pitch for spec in specs])
+        keeps = [False] * len(specs) if keep_formants is None else list(keep_formants)
+        if any(keeps):
+            stretches = [formant_stretch(check_tempo(spec.tempo)) if keep else spec.stretch for spec, keep in zip(specs, keeps)]
+            pcm, lengths, offsets, joined = ops.wave_prosody(pcm, offsets, joined, lengths, stretches, [spec.pitch for spec in specs], keep_formants=keeps)
+            backend_stats["formant_requests"] += sum(keeps)
+        else:
+            pcm, lengths, offsets, joined = ops.wave_prosody(pcm, offsets, joined, lengths, [spec.stretch for spec in specs], [spec.pitch for spec in specs])
         backend_stats["prosody_calls"] += 1
         backend_stats["prosody_requests"] += sum(spec.prosody for spec in specs)
     marks = [None] * len(specs) if watermark is None else list(watermark)
@@ -1122,8 +1140,8 @@ class SpanTicket:
     """One admitted request of a `SpanScheduler`: its planned units, `spec` (`plan_request`'s `WaveSpec`: what the finished wave has to be),
     and -- once the units have all ended -- `result` (`request_wave`)."""
 
-    def __init__(self, request, voice, units, spec, parts=None, script=None, watermark=None):
-        self.request, self.voice, self.units, self.spec, self.watermark = request, voice, units, spec, watermark
+    def __init__(self, request, voice, units, spec, parts=None, script=None, watermark=None, keep_formants=False):
+        self.request, self.voice, self.units, self.spec, self.watermark, self.keep_formants = request, voice, units, spec, watermark, keep_formants
         self.parts = parts if parts is not None else [(voice, units)]   # [(voice, its units)]: one per segment of a script
         self.script = script
         self.in_flight = self.cancelled = self.done = False
@@ -1198,7 +1216,7 @@ class SpanScheduler:
                                                            sway_sampling_coef=opts["sway_sampling_coef"], generator=plan.generator, **extra)
                                   for tokens, frames in units]))
         plan.commit()   # every chunk was planned: the caller's generator moves
-        ticket = SpanTicket(request, plan.voice, [u for _, us in parts for u in us], plan.spec, parts, plan.script, plan.watermark)
+        ticket = SpanTicket(request, plan.voice, [u for _, us in parts for u in us], plan.spec, parts, plan.script, plan.watermark, plan.keep_formants)
         self.waiting.append(ticket)
         return ticket
 
@@ -1224,7 +1242,8 @@ class SpanScheduler:
         first = np.cumsum([0] + [len(t.parts) for t in tickets])
         chunk_waves = [request_chunk_waves(t, got[first[i]:first[i + 1]]) for i, t in enumerate(tickets)]
         results = _finish_specs(chunk_waves, [request_text(t.request) for t in tickets], self.cross_fade_duration, [t.spec for t in tickets],
-                                self.device_backend, "pcm16" if self.device_backend else "float", [t.watermark for t in tickets])
+                                self.device_backend, "pcm16" if self.device_backend else "float", [t.watermark for t in tickets],
+                                [t.keep_formants for t in tickets])
         for t, result in zip(tickets, results):
             t.result, t.done, t.in_flight = result, True, False
 

@@ -818,15 +818,28 @@ def wave_prosody_taps(device):
     return hit
 
 
-def wave_prosody(pcm, in_off, max_len, len_dev, stretches, pitches):
+def wave_prosody_formants_launches():
+    """Launches `wave_prosody` adds for a call in which a request keeps its formants (3)."""
+    return int(_lib.lib().f5hip_wave_prosody_formants_launches())
+
+
+def wave_prosody(pcm, in_off, max_len, len_dev, stretches, pitches, keep_formants=None):
     """The tempo and pitch of several finished requests in ONE library call and two launches, one when no request has a pitch
     (include/f5hip.h f5hip_wave_prosody): their 24 kHz int16 PCM on the device -> each request's `wave_codec.shift_pcm16`, bit for bit.
     `pcm`: the int16 device tensor that holds every request (`wave_finish`'s packed PCM; request i starts at sample in_off[i]); `max_len`,
     `len_dev` as in `wave_encode`; `stretches` [n]: (P, Q) of each request (`WaveSpec.stretch`; (1, 1) leaves the duration alone);
     `pitches` [n]: semitones, 0 for none.  A neutral request is copied through.  Returns (pcm2 int16 device, lengths2 int32 device [n],
     offsets2, bounds2): request i's samples are pcm2[offsets2[i] : offsets2[i] + lengths2[i]], and bounds2[i] is the length that max_len[i]
-    gives -- what `wave_loudness`, `wave_encode` and `wave_flac` take in the place of `wave_finish`'s buffer, offsets, bounds and lengths."""
+    gives -- what `wave_loudness`, `wave_encode` and `wave_flac` take in the place of `wave_finish`'s buffer, offsets, bounds and lengths.
+    `keep_formants` [n] of bools (None: the call above, unchanged): a flagged request needs a pitch, takes the stretch of its tempo alone
+    (`wave_codec.formant_stretch`) and keeps its spectral envelope -- `wave_codec.shift_pcm16(..., keep_formants=True)` bit for bit, three
+    more launches whatever n (include/f5hip.h f5hip_wave_prosody_formants), the resampler's only when another request has a plain pitch."""
     (pcm,), io, ml, n, len_dev = _pcm_requests("wave_prosody", pcm, in_off, max_len, len_dev)
+    kf = None
+    if keep_formants is not None:
+        if any(not isinstance(v, (bool, np.bool_)) for v in keep_formants):
+            raise _lib.F5HipError(f"wave_prosody: keep_formants is one bool per request (got {list(keep_formants)!r})")
+        kf = np.ascontiguousarray(_per_request("wave_prosody", "keep_formants", [bool(v) for v in keep_formants], np.int64, n).astype(np.uint8))
     if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in pitches):
         raise _lib.F5HipError(f"wave_prosody: a pitch is a whole number of semitones (got {list(pitches)!r})")
     pt = _per_request("wave_prosody", "pitches", pitches, np.int64, n)
@@ -836,21 +849,32 @@ def wave_prosody(pcm, in_off, max_len, len_dev, stretches, pitches):
     if (np.abs(pt) > 6).any():
         raise _lib.F5HipError(f"wave_prosody: a pitch is -6 to 6 semitones (got {pt.tolist()})")
     sp, sq, pt = (np.ascontiguousarray(a.astype(np.int32)) for a in (st[:, 0], st[:, 1], pt))
-    taps = wave_prosody_taps(pcm.device) if pt.any() else None
+    if kf is not None and (kf.astype(bool) & (pt == 0)).any():
+        raise _lib.F5HipError(f"wave_prosody: a request keeps its formants without a pitch (pitches {pt.tolist()}, keep_formants {kf.tolist()})")
+    plain = pt if kf is None else np.where(kf.astype(bool), 0, pt)     # the steps that go through the resampler
+    taps = wave_prosody_taps(pcm.device) if plain.any() else None
+    if torch_ops.load() and kf is not None:
+        pcm2, lengths2, offsets2, bounds2 = call_op("wave_prosody_formants", pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(sp),
+                                                    torch.from_numpy(sq), torch.from_numpy(pt), torch.from_numpy(kf), taps)
+        return pcm2, lengths2, offsets2.tolist(), bounds2.tolist()
     if torch_ops.load():
         pcm2, lengths2, offsets2, bounds2 = call_op("wave_prosody", pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(sp),
                                                     torch.from_numpy(sq), torch.from_numpy(pt), taps)
         return pcm2, lengths2, offsets2.tolist(), bounds2.tolist()
     from . import wave_codec
     anchor, rel = _pcm_sources("wave_prosody", [pcm], io, ml)
-    bounds2 = [wave_codec.shifted_length(int(m), (int(p), int(q)), int(s)) for m, p, q, s in zip(ml, sp, sq, pt)]
+    bounds2 = [wave_codec.shifted_length(int(m), (int(p), int(q)), int(s)) for m, p, q, s in zip(ml, sp, sq, plain)]
     offsets2, total = _pack(bounds2, 8)
     oo = np.asarray(offsets2, dtype=np.int64)
     with torch.cuda.device(pcm.device):
         pcm2 = torch.empty(max(total, 8), device=pcm.device, dtype=torch.int16)[:total]   # (a call of empty requests still has an address to give)
         lengths2 = torch.empty(n, device=pcm.device, dtype=torch.int32)
-        _lib.check(_lib.lib().f5hip_wave_prosody(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(sp), _p(sq), _p(pt), _p(taps), _p(pcm2), _p(oo), _p(lengths2),
-                                                 _lib.current_stream_ptr()), "f5hip_wave_prosody")
+        if kf is not None:
+            _lib.check(_lib.lib().f5hip_wave_prosody_formants(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(sp), _p(sq), _p(pt), _p(kf), _p(taps), _p(pcm2),
+                                                              _p(oo), _p(lengths2), _lib.current_stream_ptr()), "f5hip_wave_prosody_formants")
+        else:
+            _lib.check(_lib.lib().f5hip_wave_prosody(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(sp), _p(sq), _p(pt), _p(taps), _p(pcm2), _p(oo), _p(lengths2),
+                                                     _lib.current_stream_ptr()), "f5hip_wave_prosody")
     return pcm2, lengths2, offsets2, bounds2
 
 

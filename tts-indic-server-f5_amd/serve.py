@@ -64,7 +64,8 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
     The delivery options by `infer.WaveSpec`'s validators, one by one and then together (a `flac_level` beside another encoding is refused,
     never ignored; a `tempo` and a `pitch` whose combined stretch leaves 1/2 .. 2 likewise); `remove_silence` must be a bool, and `flac_level`
     is not "1".  What a request gets anyway -- False, 24000, "pcm16", level 0, tempo 1.0, pitch 0 -- is dropped like None: the request is
-    then what it is without the option.  `watermark` by `infer.check_watermark`: an integer key from 1 to 2^48 - 1."""
+    then what it is without the option.  `watermark` by `infer.check_watermark`: an integer key from 1 to 2^48 - 1.  `keep_formants` by
+    `infer.check_keep_formants`: a bool (false is dropped), and true only beside a non-zero `pitch`."""
     out = {}
     own = options.get("ode_method") if "ode_method" in allowed else None
     if own is not None:
@@ -103,6 +104,10 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
                 continue
         elif k == "watermark":
             v = infer.check_watermark(v)                # ValueError: "watermark must be an integer key ..."
+        elif k == "keep_formants":
+            if not infer.check_keep_formants(v):        # ValueError: "keep_formants must be true or false ..."
+                continue
+            v = True
         elif k in ("nfe_step", "seed"):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"{k} must be an integer (got {v!r})")
@@ -123,6 +128,7 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
                 raise ValueError(f"speed must be greater than 0 (got {v}).")
         out[k] = v
     infer.WaveSpec.of(out)                              # the delivery options together.  ValueError: "flac_level needs encoding 'flac' ..."
+    infer.check_keep_formants(out.get("keep_formants"), out.get("pitch", 0))   # ValueError: "keep_formants needs a non-zero pitch"
     if out.get("flac_level") == 0:
         del out["flac_level"]
     return out
@@ -779,7 +785,8 @@ class TTSManager:
         attention, one GPU).  `ode_method` ("euler", "midpoint", "rk4"; None: the model's): requests of different solvers share a batch, and
         the option reaches the model object only for a request that sets it.  The `infer.DELIVERY_OPTIONS` (`remove_silence`, `loudness`,
         `sample_rate`, `encoding`, `flac_level`) and the `infer.PROSODY_OPTIONS` (`tempo`: the duration divided by it at the same pitch, where
-        `speed` asks the sampler for another take; `pitch`: whole semitones at the same duration; see `infer.WaveSpec`) make the result
+        `speed` asks the sampler for another take; `pitch`: whole semitones at the same duration; see `infer.WaveSpec`) and, beside a non-zero
+        `pitch`, `keep_formants` (the voice's formants stay where they were: `infer.psola_pcm16`) make the result
         `infer.finish_pcm16` of the wave's int16 PCM --
         computed on the device with `device_backend`, where every result is int16 PCM, and the same bytes either way."""
         if not self.model:
@@ -804,7 +811,7 @@ class TTSManager:
 
     def _stream(self, voice, ref_text, head, tail, opts=None):
         spec = infer.WaveSpec.of(opts or {})   # the delivery format is applied here, piece by piece: the head and tail requests stay plain
-        opts = {k: v for k, v in (opts or {}).items() if k not in infer.DELIVERY_OPTIONS + infer.PROSODY_OPTIONS + infer.WATERMARK_OPTIONS}
+        opts = {k: v for k, v in (opts or {}).items() if k not in infer.DELIVERY_OPTIONS + infer.PROSODY_OPTIONS + infer.WATERMARK_OPTIONS + infer.FORMANT_OPTIONS}
         return self._stream_requests(self._request(voice, ref_text, head, opts), self._request(voice, ref_text, tail, opts) if tail else None, spec)
 
     def _stream_requests(self, head_request, tail_request, spec, tail_pieces=None):
@@ -943,7 +950,7 @@ class TTSManager:
         if "seed" in opts:
             opts["generator"] = infer.request_generator(opts.pop("seed"))
         spec = infer.WaveSpec.of(opts)            # (applied to the pieces, as in `_stream`)
-        opts = {k: v for k, v in opts.items() if k not in infer.DELIVERY_OPTIONS + infer.PROSODY_OPTIONS + infer.WATERMARK_OPTIONS}
+        opts = {k: v for k, v in opts.items() if k not in infer.DELIVERY_OPTIONS + infer.PROSODY_OPTIONS + infer.WATERMARK_OPTIONS + infer.FORMANT_OPTIONS}
         chunked = [(voice, ref_text, infer.request_chunks(ref_text, voice.seconds, piece), speed) for voice, ref_text, piece, speed in segments]
         voice, ref_text, chunks, speed = chunked[0]
         head = self._request(voice, ref_text, chunks[:1], dict(opts, speed=speed) if speed is not None else opts)
@@ -1127,6 +1134,7 @@ def request_models():
         tempo: typing.Any = None                     # 0.5 to 2 in steps of 0.01: the duration divided by it, the pitch kept (infer.shift_pcm16); untyped like flac_level
         pitch: typing.Any = None                     # whole semitones, -6 to 6, the duration kept; untyped, so that true and 2.0 arrive as sent and are refused
         watermark: typing.Any = None                 # the key of a provenance mark, 1 to 2^48 - 1 (infer.mark_pcm16); untyped, so that true, 1.0 and "1" are refused
+        keep_formants: typing.Any = None             # true beside a non-zero pitch: the voice's formants stay where they were (infer.psola_pcm16); untyped, so that 1 and "true" are refused
 
     class KannadaSynthesizeRequest(SpeechFields):    # S/utils/tts_utils.py:27-28
         text: str
@@ -1198,7 +1206,8 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     `loudness` as `infer.WaveSpec` describes them (a bad value or combination is a 400; `loudness` is measured on the whole wave, so it is
     a 400 together with `"stream": true`: `STREAM_LOUDNESS`), the speech routes also `tempo` (0.5 to 2: the duration divided by it, the pitch
     kept) and `pitch` (whole semitones, -6 to 6, the duration kept), applied to the finished wave (`infer.shift_pcm16`; 400 together with
-    `"stream": true`: `STREAM_PROSODY`; not on the edit route, which keeps the recording's timing), every route `watermark` (a key, 1 to 2^48 - 1: the finished wave
+    `"stream": true`: `STREAM_PROSODY`; not on the edit route, which keeps the recording's timing) and beside a non-zero `pitch` `keep_formants` (true: the
+    pitch moves and the voice's formants stay, `infer.psola_pcm16`; 400 for anything but a bool and without a pitch), every route `watermark` (a key, 1 to 2^48 - 1: the finished wave
     carries that key's provenance mark, `infer.mark_pcm16`; a bad key is a 400, and so is the option together with `"stream": true`:
     `STREAM_WATERMARK`; `/v1/audio/watermark/detect` scores a recording against keys), and `response_format` ("wav", or "pcm" for the headerless samples / code bytes
     as `audio/pcm`); streamed or not, the body's samples are the same bytes.  `encoding: "flac"` is its own container: the body is the

@@ -5,7 +5,7 @@ the extension is present and through ctypes otherwise -- the same C entry points
     `F5HipModel._call_sampler` is their one caller.
   - the vocoders: vocos_decode, vocos_decode_ragged, bigvgan_forward, bigvgan_forward_ragged (`vocoder.F5HipVocos`, `vocoder.F5HipBigVGAN`).
   - the device audio path: ref_prestep, ref_frontend, ref_assess, watermark_detect, ref_denoise, flac_decode, mel_spectrogram_ragged in front of the
-    model; wave_finish, wave_finish_joins, wave_prosody, wave_mark, wave_loudness, wave_encode, wave_flac and wave_flac_levels behind the
+    model; wave_finish, wave_finish_joins, wave_prosody, wave_prosody_formants, wave_mark, wave_loudness, wave_encode, wave_flac and wave_flac_levels behind the
     vocoder (`ops`, `mel`);
     `ops.call_op` calls them, and the ragged vocoder operators, and turns an operator's c10::Error into F5HipError."""
 from __future__ import annotations

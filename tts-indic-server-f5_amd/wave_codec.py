@@ -3,7 +3,7 @@
 `StreamResampler`), the BS.1770 loudness meter and normaliser (`measure_loudness`, `normalise_loudness_pcm16`), G.711 (`encode_g711`,
 `decode_g711`), FLAC (`encode_flac`, `decode_flac`, `StreamFlacEncoder`; the whole format in: `read_flac`, `load_audio`), the delivery
 format of a request (`delivery_format`, `deliver_pcm16`), time-scale modification of finished PCM (`wsola_pcm16`, `shift_pcm16`: a request's
-`tempo` and `pitch`), the provenance watermark (`mark_pcm16`, `detect_watermark`: a request's `watermark` key), its five delivery and two prosody options as one value (`WaveSpec`; `StreamDelivery` applies it to a stream) and the bytes of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
+`tempo` and `pitch`; `psola_pcm16`: a `pitch` that keeps the formants, a request's `keep_formants`), the provenance watermark (`mark_pcm16`, `detect_watermark`: a request's `watermark` key), its five delivery and two prosody options as one value (`WaveSpec`; `StreamDelivery` applies it to a stream) and the bytes of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
 round; `infer` and `serve` hand every public name on (`infer.load_wav`, `serve.wav_bytes`, ...)."""
 from __future__ import annotations
 
@@ -734,25 +734,194 @@ def pitch_taps(pitch):
     return hit
 
 
-def shift_pcm16(pcm, tempo=None, pitch=None) -> np.ndarray:
+def shift_pcm16(pcm, tempo=None, pitch=None, keep_formants=False) -> np.ndarray:
     """A request's `tempo` and `pitch` on its 24 kHz int16 PCM [n], the host definition above: about n 100 / T samples, ceil(q ceil(n P /
-    Q) / p) of them.  Both neutral (None, 1.0, 0) returns the input itself.  What `ops.wave_prosody` equals byte for byte."""
+    Q) / p) of them.  Both neutral (None, 1.0, 0) returns the input itself.  What `ops.wave_prosody` equals byte for byte.
+    `keep_formants` (with a non-zero pitch; `check_keep_formants`): WSOLA by the tempo alone (`formant_stretch`), then `psola_pcm16`
+    (defined below) in place of the extra stretch and the resampler: ceil(n 100 / T) samples.  The combined stretch is checked either way."""
     pcm = _as_pcm16(pcm)
     hundredths, pitch = check_tempo(tempo), check_pitch(pitch)
+    keep = check_keep_formants(keep_formants, pitch)
     P, Q = prosody_stretch(hundredths, pitch)
     if hundredths == 100 and pitch == 0:
         return pcm
+    if keep:
+        return psola_pcm16(wsola_pcm16(pcm, *formant_stretch(hundredths)), pitch)
     y = wsola_pcm16(pcm, P, Q)
     return _polyphase_whole(y, *pitch_taps(pitch)) if pitch else y
 
 
+def formant_stretch(hundredths):
+    """(P, Q) of a tempo alone, reduce(100, T): the WSOLA stretch of a request that keeps its formants."""
+    g = math.gcd(100, int(hundredths))
+    return 100 // g, int(hundredths) // g
+
+
 def shifted_length(n, stretch, pitch) -> int:
-    """Samples `shift_pcm16` returns for n under `stretch` = (P, Q) and `pitch`."""
+    """Samples `shift_pcm16` returns for n under `stretch` = (P, Q) and `pitch` (0 for a request that keeps its formants, with its
+    `formant_stretch`)."""
     m = -(-int(n) * stretch[0] // stretch[1])
     if pitch:
         p, q = PITCH_RATIOS[pitch]
         m = -(-q * m // p)
     return m
+
+
+# ----------------------------------------- formant-preserving pitch: a request's `keep_formants` beside a non-zero `pitch`.  Time-domain
+# pitch-synchronous overlap-add (TD-PSOLA) on the 24 kHz int16 PCM, in integers with no freedom left, so the device call
+# (csrc/wave_formant.h, f5hip_wave_prosody_formants; the rules are csrc/wave_formant_core.h) is held to `psola_pcm16` bit for bit.
+# `psola_pcm16(x, pitch)`: int16 x [n] -> int16 y [n], the fundamental times p / q = PITCH_RATIOS[pitch], the spectral envelope kept.
+#   source     xt[j] = x[j] for 0 <= j < n, else 0
+#   track      frame f starts at t = 120 f (PSOLA_HOP), F = ceil(n / 120) frames.  d[l] = sum_{i < 480} |xt[t + i] - xt[t + l + i]| for the lags
+#              l = 48 .. 400 (60 to 500 Hz), E = sum_{i < 480} |xt[t + i]|.  The lag: the smallest l with 8 d[l] <= 8 dmin + E, then upwards
+#              while d[l + 1] < d[l] (l + 1 <= 400): the first dip within E / 8 of the best one, at its bottom.  ("The smallest lag within
+#              25 % of dmin" locked onto 3 T on a 210 Hz vowel; a margin tied to the frame's level does not.)  Voiced iff E >= 64 * 480 and
+#              2 d[lag] <= E.  d < 480 * 65535 < 2^25: exact integers.
+#   marks      analysis marks (a, T, voiced) in one chain from t = 0, while t < n, the frame of t being t // 120:
+#                unvoiced frame   a = t, T = 120
+#                voiced frame     T = its lag.  After an unvoiced mark, or first: a = the position of the largest sample in [t, t + T).  After
+#                                 a voiced mark: of the largest sample in [max(t - T // 8, a_prev + 24), t + T // 8].  Positions outside
+#                                 the wave do not count; ties go to the earlier position.
+#              then t = a + T.  The lower bound a_prev + 24 (half the smallest lag, never above t) makes every mark at least 24 samples
+#              after the one before: at most ceil(n / 24) marks.
+#   synthesis  u_0 = a_0, rem = 0; mark u takes the nearest analysis mark i (ties to the earlier one).  After a voiced i: u += (T_i q + rem)
+#              // p, rem = (T_i q + rem) % p, so the mean spacing is exactly T q / p; after an unvoiced i: u += 120 and rem stays (noise is
+#              not shifted).  While u < n.  A step is at least 48 * 29 // 41 = 33 samples.
+#   window     w_T[k] = M[(|k| 1024) // T] for |k| <= T, M[j] = rint(32768 (1 + cos(pi j / 1024)) / 2), j = 0 .. 1024, in fp64, half to
+#              even (csrc/psola_window.inc holds the 1025 integers; a test equates the two, so no libm decides a sample).  M[j] >= 1 up to
+#              j = 1021, and (|k| 1024) // T <= 1021 for |k| < T <= 400: a grain weighs every sample inside it.
+#   output     num[j] = sum over the synthesis marks (u, i) with |j - u| <= T_i of w_{T_i}[j - u] xt[a_i + j - u], den[j] the same sum of
+#              the weights alone; y[j] = clip((2 num + den) // (2 den)) (a floor division: round half up) where den > 0, and y[j] = x[j]
+#              where no grain covers j.  64-bit integers; no sum depends on an order.
+# Consequences: len(y) == len(x); zeros stay zeros; a wave without a voiced frame comes back byte for byte (a_i = u_i = 120 i: every grain
+# maps a sample onto itself, num = x den); nothing but the request's own samples enters.
+PSOLA_HOP, PSOLA_WINDOW, PSOLA_LAG_MIN, PSOLA_LAG_MAX = 120, 480, 48, 400
+PSOLA_MIN_ADVANCE = 24
+PSOLA_TABLE = 1024
+FORMANT_OPTIONS = ("keep_formants",)              # beside PROSODY_OPTIONS; carried next to the WaveSpec, not in it
+_psola_window = None
+
+
+def psola_window() -> np.ndarray:
+    """The master Hann table M, int64 [PSOLA_TABLE + 1] (read-only): M[0] = 32768 down to M[1024] = 0."""
+    global _psola_window
+    if _psola_window is None:
+        j = np.arange(PSOLA_TABLE + 1, dtype=np.float64)
+        w = np.rint(32768.0 * (1.0 + np.cos(np.pi * j / PSOLA_TABLE)) / 2.0).astype(np.int64)
+        w.setflags(write=False)
+        _psola_window = w
+    return _psola_window
+
+
+def check_keep_formants(keep, pitch=None) -> bool:
+    """A request's `keep_formants` option: None (absent) is False; a bool; anything else is a ValueError.  With `pitch` given (an int by
+    `check_pitch`), True without a non-zero pitch is a ValueError too."""
+    if keep is None:
+        return False
+    if not isinstance(keep, (bool, np.bool_)):
+        raise ValueError(f"keep_formants must be true or false (got {keep!r})")
+    if keep and pitch is not None and pitch == 0:
+        raise ValueError("keep_formants needs a non-zero pitch")
+    return bool(keep)
+
+
+def psola_track(x):
+    """(lag int64 [F], voiced bool [F]) of int16 x: the period track of the definition above, F = ceil(n / PSOLA_HOP)."""
+    x = _as_pcm16(x)
+    n, H, W, lo, hi = len(x), PSOLA_HOP, PSOLA_WINDOW, PSOLA_LAG_MIN, PSOLA_LAG_MAX
+    F = -(-n // H)
+    if F == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=bool)
+    N = (F - 1) * H + W
+    xt = np.zeros(N + hi, dtype=np.int64)
+    xt[:n] = x
+    t = np.arange(F, dtype=np.int64) * H
+
+    def frame_sums(e):
+        cs = np.concatenate([[0], np.cumsum(e)])
+        return cs[t + W] - cs[t]
+
+    E = frame_sums(np.abs(xt[:N]))
+    d = np.empty((F, hi - lo + 1), dtype=np.int64)
+    for l in range(lo, hi + 1):
+        d[:, l - lo] = frame_sums(np.abs(xt[:N] - xt[l:l + N]))
+    first = np.argmax(8 * d <= (8 * d.min(axis=1) + E)[:, None], axis=1)
+    lag = np.empty(F, dtype=np.int64)
+    voiced = np.empty(F, dtype=bool)
+    for f in range(F):
+        row, l = d[f], int(first[f])
+        while l + 1 < len(row) and row[l + 1] < row[l]:
+            l += 1
+        lag[f] = l + lo
+        voiced[f] = E[f] >= 64 * W and 2 * row[l] <= E[f]
+    return lag, voiced
+
+
+def psola_marks(x, lag, voiced):
+    """The analysis marks of int16 x under its track: int64 arrays (a, T, v), by the definition above."""
+    x = _as_pcm16(x)
+    n, a, T, v = len(x), [], [], []
+    t, chained = 0, False
+    while t < n:
+        f = t // PSOLA_HOP
+        if voiced[f]:
+            L = int(lag[f])
+            b, e = (max(t - L // 8, a[-1] + PSOLA_MIN_ADVANCE), t + L // 8 + 1) if chained else (t, t + L)
+            e = min(e, n)
+            at = b + int(np.argmax(x[b:e]))
+            chained = True
+        else:
+            at, L, chained = t, PSOLA_HOP, False
+        a.append(at); T.append(L); v.append(int(chained))
+        t = at + L
+    return np.asarray(a, dtype=np.int64), np.asarray(T, dtype=np.int64), np.asarray(v, dtype=np.int64)
+
+
+def psola_synthesis(a, T, v, n, pitch):
+    """The synthesis marks: int64 arrays (u, i), i the analysis mark each takes."""
+    p, q = PITCH_RATIOS[pitch]
+    us, idx = [], []
+    if len(a):
+        u, rem, i = int(a[0]), 0, 0
+        while u < n:
+            while i + 1 < len(a) and abs(int(a[i + 1]) - u) < abs(int(a[i]) - u):
+                i += 1
+            us.append(u); idx.append(i)
+            if v[i]:
+                step, rem = divmod(int(T[i]) * q + rem, p)
+            else:
+                step = int(T[i])
+            u += step
+    return np.asarray(us, dtype=np.int64), np.asarray(idx, dtype=np.int64)
+
+
+def psola_pcm16(pcm, pitch) -> np.ndarray:
+    """int16 PCM [n] with its fundamental moved by `pitch` semitones (1 .. 6 either way) and its formants kept, by the definition above:
+    n samples.  What `ops.wave_prosody(..., keep_formants=...)` equals byte for byte."""
+    x = _as_pcm16(pcm)
+    pitch = check_pitch(pitch)
+    if pitch == 0:
+        raise ValueError("psola_pcm16: a non-zero pitch is needed")
+    n = len(x)
+    if n == 0:
+        return x
+    a, T, v = psola_marks(x, *psola_track(x))
+    u, idx = psola_synthesis(a, T, v, n, pitch)
+    M = psola_window()
+    x64 = x.astype(np.int64)
+    num, den = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    for at, i in zip(u.tolist(), idx.tolist()):
+        Ti, ai = int(T[i]), int(a[i])
+        k = np.arange(max(-Ti, -at), min(Ti, n - 1 - at) + 1, dtype=np.int64)          # the grain's offsets whose output lies in the wave
+        w = M[(np.abs(k) * PSOLA_TABLE) // Ti]
+        src = ai + k
+        inside = (src >= 0) & (src < n)
+        num[at + k[0]:at + k[-1] + 1] += w * np.where(inside, x64[np.clip(src, 0, n - 1)], 0)
+        den[at + k[0]:at + k[-1] + 1] += w
+    covered = den > 0
+    safe = np.where(covered, den, 1)
+    y = np.where(covered, (2 * num + safe) // (2 * safe), x64)
+    return np.clip(y, -32768, 32767).astype(np.int16)
 
 
 # ----------------------------------------- provenance watermark: a request's `watermark` option (a key) adds a keyed, speech-shaped,
