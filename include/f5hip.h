@@ -196,6 +196,7 @@ int f5hip_get_profile(const char* kernel_class, double* total_ms, int64_t* launc
  * "attn_seg2" (every two-range launch, whatever its instance), and "dit_rows" (the summed audio rows M of every backbone forward);
  * "gemm3_thin" (the gemm3 launches, counted in "gemm3" too, that took the 32-row instance) and "time_table_builds" (sampler calls and
  * forwards that built the handle's time tables: a whole-grid sampler call on the time points of the handle's last build reuses them);
+ * the audio calls' counters are named where each call is described;
  * name "reset" zeroes all of them (value may be NULL). */
 int f5hip_get_counter(const char* name, int64_t* value);
 
@@ -850,6 +851,50 @@ int f5hip_watermark_detect(int32_t n, const float* wave_dev, const int64_t* offs
 
 /* Kernels one f5hip_watermark_detect call launches (4). */
 int f5hip_watermark_detect_launches(void);
+
+/* Provenance watermark with trace ids, embedding: f5hip_wave_mark for requests whose mark also carries a 30-bit id -- bit for bit
+ * wave_codec.mark_pcm16 of a WatermarkTag(key, id).  Not in the reference.  The id is three symbols of 10 bits, s_d = (id >> 10 d) & 1023,
+ * each the rotation by 16 s_d samples of the carrier of one of the key's three sub-keys (wave_codec.watermark_subkey: ordinary keys, their
+ * carriers by f5hip_watermark_carrier) relative to the key's own (code-shift keying):
+ *   combined     C[m] = 2 c_K[m] + sum_d c_d[(m - 16 s_d) mod 16384]: |C| <= 5 * 4336
+ *   output       y[j] = clip(x[j] + ((E[j / 240] C[j mod 16384]) >> 24), -32768, 32767), A and E as f5hip_wave_mark's: |y - x| <= 10163.
+ *                Without an id the sum over d is absent and (2 c E) >> 24 == (c E) >> 23: f5hip_wave_mark's bytes
+ *   pcm_dev, in_off, max_len, len_dev, key_index   as f5hip_wave_mark's
+ *   id             host int32 [n]: -1, or the request's id, 0 .. 2^30 - 1
+ *   carriers_dev   int16 [n_keys][4][16384], 16-byte aligned: per key its own carrier, then its sub-keys' 0 .. 2
+ *   n_keys         0 .. 16
+ * TWO launches whatever n: wave_mark_sum_kernel, then wave_mark_id_add_kernel with wave_mark_add_kernel's tile geometry: per group of 8
+ * samples one 16-byte load of x and of the key's row and, for a request with an id, three of the rotated sub-key rows (rotations are
+ * multiples of 16 samples, so a group keeps its 16-byte alignment in all four rows and never straddles the wrap); unaligned requests and
+ * tails sample by sample; no atomics, vector stores; unflagged requests and the bytes between requests are not written (counters
+ * wave_mark_id_launches, wave_mark_id_requests: the flagged requests).  A call in which nobody has an id runs f5hip_wave_mark's two kernels
+ * and counts on its counters.
+ * Refused before the first launch: what f5hip_wave_mark refuses, a null id, an id outside -1 .. 2^30 - 1, an id on a request whose
+ * key_index is -1. */
+int f5hip_wave_mark_ids(int32_t n, int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, const int32_t* key_index,
+                        const int32_t* id, const int16_t* carriers_dev, int32_t n_keys, void* stream);
+
+/* Provenance watermark with trace ids, reading: f5hip_watermark_detect, and per (clip, key) the three symbols of the id its mark carries --
+ * wave_codec.read_watermark in fp32.  Z, r_K, o* and z as f5hip_watermark_detect's; r_d = the correlation of Z with sub-key d's carrier by the
+ * same formula; candidate s takes r_d[(o* - 16 s) mod 16384]; s_d = the smallest argmax over s = 0 .. 1023; z_d = (r_d there - mean r_d) /
+ * (population deviation of r_d), 0 where that is 0.  The id (sum_d s_d << 10 d) stands when z >= 7.0 and every z_d >= 6.0
+ * (ops.watermark_reads decides).  A clip below 12 000 samples gets zeros.
+ *   wave_dev, offset, n_samples   as f5hip_watermark_detect's
+ *   n_keys                    1 .. 4
+ *   carriers_dev              int16 [n_keys][4][16384], 16-byte aligned: f5hip_wave_mark_ids' layout
+ *   rows_dev                  fp32 [n][n_keys][10]: z, o*, r[o*], the deviation -- f5hip_watermark_detect's row of that clip and key bit
+ *                             for bit --, then s_0, z_0, s_1, z_1, s_2, z_2
+ * FOUR launches whatever n and n_keys (f5hip_watermark_read_ids_launches): f5hip_watermark_detect's frame, fold and correlate kernels over
+ * the 4 n_keys rows, then watermark_id_score_kernel, one block per (clip, key): the key's row by the detector's fixed trees and fp64 moments,
+ * each sub-key's row the same way with the maximum over its 1024 candidates, ties to the smaller symbol (counters
+ * watermark_read_ids_launches, watermark_read_ids_clips).  A clip's rows are bit-identical alone, in any batch and in any order; the
+ * input is never written.
+ * Refused before the first launch: what f5hip_watermark_detect refuses, with n_keys outside 1 .. 4. */
+int f5hip_watermark_read_ids(int32_t n, const float* wave_dev, const int64_t* offset, const int32_t* n_samples, int32_t n_keys,
+                             const int16_t* carriers_dev, float* rows_dev, void* stream);
+
+/* Kernels one f5hip_watermark_read_ids call launches (4). */
+int f5hip_watermark_read_ids_launches(void);
 
 /* Reference-clip report: is an uploaded clip fit to clone from?  The measures of audio_prep.assess_reference (the definition, written down
  * above it) for n clips in one call, on the two buffers a front-end call holds.  Not in the reference.

@@ -138,6 +138,9 @@ SYMBOLS = {
     "f5hip_watermark_carrier": (C.c_int, [C.c_uint64, C.c_void_p]),
     "f5hip_watermark_detect": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_watermark_detect_launches": (C.c_int, []),
+    "f5hip_wave_mark_ids": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "f5hip_watermark_read_ids": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "f5hip_watermark_read_ids_launches": (C.c_int, []),
     "f5hip_ref_assess": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_ref_assess_launches": (C.c_int, []),
 }

@@ -7,6 +7,9 @@
 //                         length, as magnitudes into LDS (coalesced), eight threads per block sum, A [tiles * 32] int to the workspace
 //   wave_mark_add_kernel  one block per tile: groups of 8 samples (one 16-byte load and store where the address allows), E from the three
 //                         block sums around the group, the carrier's 8 values as one 16-byte load, wm_mark per sample
+//   wave_mark_id_add_kernel  wave_mark_add_kernel for a call in which a request carries a trace id (f5hip_wave_mark_ids): the key's 8 carrier
+//                         values doubled, and for a request with an id three more 16-byte loads, its sub-key rows rotated by 16 s_d, added:
+//                         wm_mark_id per sample.  A request without an id skips the three loads and gets wave_mark_add_kernel's bytes
 // TWO launches whatever n, none when nobody is flagged.  Integers only: no sum depends on an order.
 //
 //   wd_frame_kernel       one block per frame row of the packed batch: the frame times w through fft1024_lds, X[k] / sqrt(|X[k]|^2 + 1e-10)
@@ -18,6 +21,9 @@
 //                         owns 2 offsets x 4 clips and adds Z[m] c[(m + o) mod P] for m ascending from 0: r [n][n_keys][P]
 //   wd_score_kernel       one block per (clip, key): the maximum of r (ties to the smaller offset), mean and population deviation in fp64
 //                         by fixed trees -> (z, offset, r[o*], sigma); a clip below WATERMARK_MIN_SAMPLES gets zeros
+//   watermark_id_score_kernel  f5hip_watermark_read_ids' fourth launch, one block per (clip, key) over the key's four rows of r: the key's row
+//                         as wd_score_kernel scores it (wd_moments, wd_grid_max: the same trees), then per sub-key row its moments and the
+//                         maximum over the 1024 offsets o* - 16 s (ties to the smaller s) -> (z, offset, r[o*], sigma, s_0, z_0, .., s_2, z_2)
 // FOUR launches whatever n.  Every sum runs in an order fixed by the clip alone, so a clip's row is bit-identical alone and in a batch.
 #pragma once
 #include "ragged_util.h"
@@ -31,7 +37,7 @@ struct WmReq {
     int key;             // its row of carriers_dev
     int tile0;           // its first block of either launch; its block sums start at kWmTileBlocks * tile0
     int tiles;
-    int pad_;
+    int id;              // its trace id, -1 without one (f5hip_wave_mark: always -1)
 };
 
 F5_DEVICE int wm_len(const int* len_dev, const WmReq& q) { return len_dev ? min(max(len_dev[q.req], 0), q.cap) : q.cap; }
@@ -103,6 +109,61 @@ __global__ __launch_bounds__(256) void wave_mark_add_kernel(const WmReq* __restr
     }
 }
 
+__global__ __launch_bounds__(256) void wave_mark_id_add_kernel(const WmReq* __restrict__ reqs, int nf, short* __restrict__ pcm,
+                                                               const int* __restrict__ len_dev, const int* __restrict__ A,
+                                                               const short* __restrict__ carriers) {
+    const WmReq q = reqs[last_at_or_before<&WmReq::tile0>(reqs, nf, (int)blockIdx.x)];
+    const int len = wm_len(len_dev, q);
+    const int tile = blockIdx.x - q.tile0;
+    const long long j0 = (long long)tile * kWmTile;
+    short* x = pcm + q.in_off;
+    const int* Aq = A + (long long)q.tile0 * kWmTileBlocks;
+    const long long nA = (long long)q.tiles * kWmTileBlocks;
+    const short* c = carriers + (long long)q.key * kWmPeriod;           // the key's row; its sub-keys' rows follow it
+    for (int grp = threadIdx.x; grp < kWmTile / 8; grp += 256) {
+        const long long j = j0 + 8 * grp;
+        if (j >= len) break;
+        const int E = wm_envelope(Aq, nA, j / kWmBlock);
+        if (E == 0) continue;                                           // silence around it: the samples stay
+        const int4 kv = *reinterpret_cast<const int4*>(c + (j & (kWmPeriod - 1)));
+        const int k8[4] = {kv.x, kv.y, kv.z, kv.w};
+        int C[8];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            C[2 * e] = 2 * (int)(short)(k8[e] & 0xffff);
+            C[2 * e + 1] = 2 * (k8[e] >> 16);
+        }
+        if (q.id >= 0) {                                                // (the same for the whole block)
+#pragma unroll
+            for (int d = 0; d < kWmIdSymbols; d++) {
+                const int4 dv = *reinterpret_cast<const int4*>(c + (long long)(1 + d) * kWmPeriod + wm_id_index(j, wm_id_symbol(q.id, d)));
+                const int d8[4] = {dv.x, dv.y, dv.z, dv.w};
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    C[2 * e] += (int)(short)(d8[e] & 0xffff);
+                    C[2 * e + 1] += d8[e] >> 16;
+                }
+            }
+        }
+        if (j + 8 <= len && (reinterpret_cast<uintptr_t>(x + j) & 15) == 0) {
+            const int4 in = *reinterpret_cast<const int4*>(x + j);
+            const int w8[4] = {in.x, in.y, in.z, in.w};
+            int o[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int lo = wm_mark_id((int)(short)(w8[e] & 0xffff), E, C[2 * e]);
+                const int hi = wm_mark_id(w8[e] >> 16, E, C[2 * e + 1]);
+                o[e] = (lo & 0xffff) | (hi << 16);
+            }
+            *reinterpret_cast<int4*>(x + j) = make_int4(o[0], o[1], o[2], o[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; e++)
+                if (j + e < len) x[j + e] = (short)wm_mark_id((int)x[j + e], E, C[e]);
+        }
+    }
+}
+
 struct WmWorkspace {
     WmReq* reqs = nullptr; size_t cap_reqs = 0;
     int* A = nullptr; size_t cap_A = 0;
@@ -122,27 +183,33 @@ int f5hip_watermark_carrier(uint64_t key, int16_t* carrier) {
     return 0;
 }
 
-int f5hip_wave_mark(int32_t n, int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, const int32_t* key_index,
-                    const int16_t* carriers_dev, int32_t n_keys, void* stream) {
-    if (n < 1 || !pcm_dev || !in_off || !max_len || !key_index) return fail(-1, "wave_mark: bad argument");
+// f5hip_wave_mark (id null, one carrier row per key) and f5hip_wave_mark_ids (kWmTagRows rows per key) under their names
+static int wave_mark_call(const char* op, int32_t n, int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
+                          const int32_t* key_index, const int32_t* id, const int16_t* carriers_dev, int32_t n_keys, int key_rows, void* stream) {
+    if (n < 1 || !pcm_dev || !in_off || !max_len || !key_index) return fail(-1, "%s: bad argument", op);
     if ((reinterpret_cast<uintptr_t>(pcm_dev) & 1) || (reinterpret_cast<uintptr_t>(len_dev) & 3))
-        return fail(-1, "wave_mark: the samples must be 2-byte aligned and the lengths 4-byte");
-    if (n_keys < 0 || n_keys > kWmKeysMax) return fail(-1, "wave_mark: 1 .. %d keys in a call (got %d)", kWmKeysMax, n_keys);
+        return fail(-1, "%s: the samples must be 2-byte aligned and the lengths 4-byte", op);
+    if (n_keys < 0 || n_keys > kWmKeysMax) return fail(-1, "%s: 1 .. %d keys in a call (got %d)", op, kWmKeysMax, n_keys);
     std::vector<WmReq> h;
     long long total = 0, tiles = 0;
+    int tagged = 0;
     for (int i = 0; i < n; i++) {
-        if (max_len[i] < 0) return fail(-1, "wave_mark: request %d has a negative length bound (%d)", i, max_len[i]);
-        if (in_off[i] < 0) return fail(-1, "wave_mark: request %d has a negative offset", i);
-        if (key_index[i] < -1 || key_index[i] >= n_keys) return fail(-1, "wave_mark: request %d names key %d of %d", i, key_index[i], n_keys);
+        if (max_len[i] < 0) return fail(-1, "%s: request %d has a negative length bound (%d)", op, i, max_len[i]);
+        if (in_off[i] < 0) return fail(-1, "%s: request %d has a negative offset", op, i);
+        if (key_index[i] < -1 || key_index[i] >= n_keys) return fail(-1, "%s: request %d names key %d of %d", op, i, key_index[i], n_keys);
+        const int tag = id ? id[i] : -1;
+        if (tag < -1 || tag > kWmIdMax) return fail(-1, "%s: request %d has id %d (-1, or 0 .. %d)", op, i, tag, kWmIdMax);
+        if (tag >= 0 && key_index[i] < 0) return fail(-1, "%s: request %d has an id and no key", op, i);
         total += max_len[i];
-        if (total > 2147483647LL) return fail(-1, "wave_mark: the call exceeds 2^31 - 1 samples");
+        if (total > 2147483647LL) return fail(-1, "%s: the call exceeds 2^31 - 1 samples", op);
         if (key_index[i] < 0) continue;                                 // -1: the request is left alone
         const long long t = wm_tiles(max_len[i]);
-        h.push_back(WmReq{in_off[i], max_len[i], i, key_index[i], (int)tiles, (int)t, 0});
+        h.push_back(WmReq{in_off[i], max_len[i], i, key_index[i] * key_rows, (int)tiles, (int)t, tag});
         tiles += t;
+        tagged += tag >= 0;
     }
     if (h.empty()) return 0;
-    if (!carriers_dev || (reinterpret_cast<uintptr_t>(carriers_dev) & 15)) return fail(-1, "wave_mark: the carriers must be 16-byte aligned");
+    if (!carriers_dev || (reinterpret_cast<uintptr_t>(carriers_dev) & 15)) return fail(-1, "%s: the carriers must be 16-byte aligned", op);
     WmWorkspace* const wsp = device_workspace<WmWorkspace>("wave_mark");
     if (!wsp) return -6;
     WmWorkspace& ws = *wsp;
@@ -153,12 +220,31 @@ int f5hip_wave_mark(int32_t n, int16_t* pcm_dev, const int64_t* in_off, const in
     const int nf = (int)h.size();
     hipLaunchKernelGGL(wave_mark_sum_kernel, dim3((unsigned)tiles), dim3(256), 0, st, ws.reqs, nf, (const short*)pcm_dev, (const int*)len_dev, ws.A);
     CKL("wave_mark_sum");
+    if (tagged) {
+        hipLaunchKernelGGL(wave_mark_id_add_kernel, dim3((unsigned)tiles), dim3(256), 0, st, ws.reqs, nf, (short*)pcm_dev, (const int*)len_dev,
+                           (const int*)ws.A, (const short*)carriers_dev);
+        CKL("wave_mark_id_add");
+        g_counters[CNT_WAVE_MARK_ID_LAUNCHES] += 2;
+        g_counters[CNT_WAVE_MARK_ID_REQUESTS] += nf;
+        return 0;
+    }
     hipLaunchKernelGGL(wave_mark_add_kernel, dim3((unsigned)tiles), dim3(256), 0, st, ws.reqs, nf, (short*)pcm_dev, (const int*)len_dev,
                        (const int*)ws.A, (const short*)carriers_dev);
     CKL("wave_mark_add");
     g_counters[CNT_WAVE_MARK_LAUNCHES] += 2;
     g_counters[CNT_WAVE_MARK_REQUESTS] += nf;
     return 0;
+}
+
+int f5hip_wave_mark(int32_t n, int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, const int32_t* key_index,
+                    const int16_t* carriers_dev, int32_t n_keys, void* stream) {
+    return wave_mark_call("wave_mark", n, pcm_dev, in_off, max_len, len_dev, key_index, nullptr, carriers_dev, n_keys, 1, stream);
+}
+
+int f5hip_wave_mark_ids(int32_t n, int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev, const int32_t* key_index,
+                        const int32_t* id, const int16_t* carriers_dev, int32_t n_keys, void* stream) {
+    if (!id) return fail(-1, "wave_mark_ids: bad argument");
+    return wave_mark_call("wave_mark_ids", n, pcm_dev, in_off, max_len, len_dev, key_index, id, carriers_dev, n_keys, kWmTagRows, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ the detector
@@ -250,6 +336,40 @@ __global__ __launch_bounds__(256) void wd_corr_kernel(int n, int n_keys, const f
     }
 }
 
+// mean and population deviation of a row of r [P] in fp64 by a block of 256 threads: thread t adds offsets t, t + 256, ... ascending, then
+// block_sum's fixed tree; every thread returns both
+F5_DEVICE void wd_moments(const float* __restrict__ row, double* red, int tid, double* mean_out, double* sigma_out) {
+    constexpr int kPer = kWmPeriod / 256;
+    double sum = 0.0;
+    for (int i = 0; i < kPer; i++) sum += (double)row[tid + 256 * i];
+    const double mean = block_sum(red, tid, sum) / (double)kWmPeriod;
+    double sq = 0.0;
+    for (int i = 0; i < kPer; i++) {
+        const double d = (double)row[tid + 256 * i] - mean;
+        sq += d * d;
+    }
+    *mean_out = mean;
+    *sigma_out = sqrt(block_sum(red, tid, sq) / (double)kWmPeriod);
+}
+
+// the maximum of row[(base - step * s) mod P] over s = 0 .. count - 1 (count a multiple of 256) with ties to the smaller s (wd_better), by a
+// block of 256 threads: thread t holds s = t, t + 256, ..., then a fixed tree; the value is left in bv[0] and s in bi[0] for every thread
+F5_DEVICE void wd_grid_max(const float* __restrict__ row, int base, int step, int count, float* bv, int* bi, int tid) {
+    float best = row[(base - step * tid) & (kWmPeriod - 1)];
+    int at = tid;
+    for (int s = tid + 256; s < count; s += 256) {
+        const float v = row[(base - step * s) & (kWmPeriod - 1)];
+        if (wd_better(v, s, best, at)) { best = v; at = s; }
+    }
+    __syncthreads();                                                     // (bv, bi of an earlier call have been read)
+    bv[tid] = best; bi[tid] = at;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s && wd_better(bv[tid + s], bi[tid + s], bv[tid], bi[tid])) { bv[tid] = bv[tid + s]; bi[tid] = bi[tid + s]; }
+        __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(256) void wd_score_kernel(const RdClip* __restrict__ clips, int n_keys, const float* __restrict__ r,
                                                        float* __restrict__ scores) {
     __shared__ double red[256];
@@ -263,33 +383,48 @@ __global__ __launch_bounds__(256) void wd_score_kernel(const RdClip* __restrict_
         return;
     }
     const float* row = r + (size_t)blockIdx.x * kWmPeriod;
-    constexpr int kPer = kWmPeriod / 256;                                // thread t holds offsets t, t + 256, ...
-    float best = row[tid];
-    int at = tid;
-    double sum = 0.0;
-    for (int i = 0; i < kPer; i++) {
-        const float v = row[tid + 256 * i];
-        sum += (double)v;
-        if (wd_better(v, tid + 256 * i, best, at)) { best = v; at = tid + 256 * i; }
-    }
-    const double mean = block_sum(red, tid, sum) / (double)kWmPeriod;
-    double sq = 0.0;
-    for (int i = 0; i < kPer; i++) {
-        const double d = (double)row[tid + 256 * i] - mean;
-        sq += d * d;
-    }
-    const double sigma = sqrt(block_sum(red, tid, sq) / (double)kWmPeriod);
-    bv[tid] = best; bi[tid] = at;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s && wd_better(bv[tid + s], bi[tid + s], bv[tid], bi[tid])) { bv[tid] = bv[tid + s]; bi[tid] = bi[tid + s]; }
-        __syncthreads();
-    }
+    double mean, sigma;
+    wd_moments(row, red, tid, &mean, &sigma);
+    wd_grid_max(row, 0, -1, kWmPeriod, bv, bi, tid);                     // every offset: s is the offset
     if (tid == 0) {
         out[0] = sigma > 0.0 ? (float)(((double)bv[0] - mean) / sigma) : 0.0f;
         out[1] = (float)bi[0];
         out[2] = bv[0];
         out[3] = (float)sigma;
+    }
+}
+
+__global__ __launch_bounds__(256) void watermark_id_score_kernel(const RdClip* __restrict__ clips, int n_keys, const float* __restrict__ r,
+                                                                 float* __restrict__ rows) {
+    __shared__ double red[256];
+    __shared__ float bv[256];
+    __shared__ int bi[256];
+    const int tid = threadIdx.x;
+    const int clip = blockIdx.x / n_keys;
+    float* out = rows + kWdIdRowWords * (size_t)blockIdx.x;
+    if (clips[clip].n < kWdMinSamples) {                                 // (the same for the whole block)
+        if (tid < kWdIdRowWords) out[tid] = 0.0f;
+        return;
+    }
+    const float* row = r + (size_t)blockIdx.x * kWmTagRows * kWmPeriod;  // the key's row of r; its sub-keys' rows follow it
+    double mean, sigma;
+    wd_moments(row, red, tid, &mean, &sigma);
+    wd_grid_max(row, 0, -1, kWmPeriod, bv, bi, tid);
+    const int o = bi[0];
+    if (tid == 0) {
+        out[0] = sigma > 0.0 ? (float)(((double)bv[0] - mean) / sigma) : 0.0f;
+        out[1] = (float)o;
+        out[2] = bv[0];
+        out[3] = (float)sigma;
+    }
+    for (int d = 0; d < kWmIdSymbols; d++) {
+        const float* rd = row + (size_t)(1 + d) * kWmPeriod;
+        wd_moments(rd, red, tid, &mean, &sigma);
+        wd_grid_max(rd, o, kWmIdStep, kWmIdSymbolCount, bv, bi, tid);    // offset wd_id_offset(o, s)
+        if (tid == 0) {
+            out[4 + 2 * d] = (float)bi[0];
+            out[5 + 2 * d] = sigma > 0.0 ? (float)(((double)bv[0] - mean) / sigma) : 0.0f;
+        }
     }
 }
 
@@ -301,25 +436,26 @@ struct WdWorkspace {
     HostStage stage;
 };
 
-int f5hip_watermark_detect(int32_t n, const float* wave_dev, const int64_t* offset, const int32_t* n_samples, int32_t n_keys,
-                           const int16_t* carriers_dev, float* scores_dev, void* stream) {
-    if (n_keys < 1 || n_keys > kWmKeysMax) return fail(-1, "watermark_detect: 1 .. %d keys in a call (got %d)", kWmKeysMax, n_keys);
+// The three launches f5hip_watermark_detect and f5hip_watermark_read_ids share, under the caller's name: the call's checks, then frame, fold
+// and correlate over n_rows carrier rows -> ws.r [n][n_rows][P], ws.clips
+static int wd_correlate(const char* op, int32_t n, const float* wave_dev, const int64_t* offset, const int32_t* n_samples, int32_t n_rows,
+                        const int16_t* carriers_dev, const float* out_dev, hipStream_t st, WdWorkspace** out_ws) {
     std::vector<RdClip> h;
     long long rows = 0, total = 0;
     int bad = 0;
     switch (rd_layout(n, offset, n_samples, h, &rows, &total, &bad)) {
         case RD_OK: break;
-        case RD_NO_CLIPS: return fail(-1, "watermark_detect: at least one clip (got %d)", n);
-        case RD_NULL: return fail(-1, "watermark_detect: bad argument");
-        case RD_LENGTH: return fail(-1, "watermark_detect: clip %d has %d samples (1 .. %d)", bad, n_samples[bad], kRdMaxSamples);
-        case RD_OFFSET: return fail(-1, "watermark_detect: clip %d starts at %lld", bad, (long long)offset[bad]);
-        case RD_OVERLAP: return fail(-1, "watermark_detect: clip %d overlaps another clip of the call", bad);
-        default: return fail(-1, "watermark_detect: the clips of the call exceed 2^31 - 1 frames");
+        case RD_NO_CLIPS: return fail(-1, "%s: at least one clip (got %d)", op, n);
+        case RD_NULL: return fail(-1, "%s: bad argument", op);
+        case RD_LENGTH: return fail(-1, "%s: clip %d has %d samples (1 .. %d)", op, bad, n_samples[bad], kRdMaxSamples);
+        case RD_OFFSET: return fail(-1, "%s: clip %d starts at %lld", op, bad, (long long)offset[bad]);
+        case RD_OVERLAP: return fail(-1, "%s: clip %d overlaps another clip of the call", op, bad);
+        default: return fail(-1, "%s: the clips of the call exceed 2^31 - 1 frames", op);
     }
-    if (!wave_dev || !carriers_dev || !scores_dev) return fail(-1, "watermark_detect: bad argument");
-    if ((reinterpret_cast<uintptr_t>(wave_dev) & 3) || (reinterpret_cast<uintptr_t>(carriers_dev) & 15) || (reinterpret_cast<uintptr_t>(scores_dev) & 3))
-        return fail(-1, "watermark_detect: the carriers must be 16-byte aligned, the samples and the scores 4-byte");
-    if ((n + kWdGroup - 1) / kWdGroup > 65535) return fail(-1, "watermark_detect: at most %d clips in a call", 65535 * kWdGroup);
+    if (!wave_dev || !carriers_dev || !out_dev) return fail(-1, "%s: bad argument", op);
+    if ((reinterpret_cast<uintptr_t>(wave_dev) & 3) || (reinterpret_cast<uintptr_t>(carriers_dev) & 15) || (reinterpret_cast<uintptr_t>(out_dev) & 3))
+        return fail(-1, "%s: the carriers must be 16-byte aligned, the samples and the scores 4-byte", op);
+    if ((n + kWdGroup - 1) / kWdGroup > 65535) return fail(-1, "%s: at most %d clips in a call", op, 65535 * kWdGroup);
     RdWorkspace* const tables = device_workspace<RdWorkspace>("watermark_detect");   // the window and the twiddles of the denoiser's FFT
     WdWorkspace* const wsp = device_workspace<WdWorkspace>("watermark_detect");
     if (!tables || !wsp) return -6;
@@ -328,18 +464,27 @@ int f5hip_watermark_detect(int32_t n, const float* wave_dev, const int64_t* offs
     CK(dev_reserve(&ws.clips, &ws.cap_clips, (size_t)n, "watermark_detect clips"));
     CK(dev_reserve(&ws.fw, &ws.cap_fw, (size_t)rows * kRdNfft, "watermark_detect frames"));
     CK(dev_reserve(&ws.Z, &ws.cap_Z, (size_t)n * kWmPeriod, "watermark_detect folds"));
-    CK(dev_reserve(&ws.r, &ws.cap_r, (size_t)n * n_keys * kWmPeriod, "watermark_detect correlations"));
-    hipStream_t st = (hipStream_t)stream;
+    CK(dev_reserve(&ws.r, &ws.cap_r, (size_t)n * n_rows * kWmPeriod, "watermark_detect correlations"));
     CK(ws.stage.upload(ws.clips, h.data(), sizeof(RdClip) * (size_t)n, st));   // pinned staging, queued on `stream`: no wait
 
     hipLaunchKernelGGL(wd_frame_kernel, dim3((unsigned)rows), dim3(256), 0, st, ws.clips, n, wave_dev, tables->window, tables->twiddle, ws.fw);
     CKL("wd_frame");
     hipLaunchKernelGGL(wd_fold_kernel, dim3(kWmPeriod / 256, (unsigned)n), dim3(256), 0, st, ws.clips, (const float*)ws.fw, ws.Z);
     CKL("wd_fold");
-    hipLaunchKernelGGL(wd_corr_kernel, dim3(kWmPeriod / kWdOffTile, (unsigned)n_keys, (unsigned)((n + kWdGroup - 1) / kWdGroup)), dim3(256), 0, st, n,
-                       n_keys, (const float*)ws.Z, (const short*)carriers_dev, ws.r);
+    hipLaunchKernelGGL(wd_corr_kernel, dim3(kWmPeriod / kWdOffTile, (unsigned)n_rows, (unsigned)((n + kWdGroup - 1) / kWdGroup)), dim3(256), 0, st, n,
+                       n_rows, (const float*)ws.Z, (const short*)carriers_dev, ws.r);
     CKL("wd_corr");
-    hipLaunchKernelGGL(wd_score_kernel, dim3((unsigned)(n * n_keys)), dim3(256), 0, st, ws.clips, n_keys, (const float*)ws.r, scores_dev);
+    *out_ws = wsp;
+    return 0;
+}
+
+int f5hip_watermark_detect(int32_t n, const float* wave_dev, const int64_t* offset, const int32_t* n_samples, int32_t n_keys,
+                           const int16_t* carriers_dev, float* scores_dev, void* stream) {
+    if (n_keys < 1 || n_keys > kWmKeysMax) return fail(-1, "watermark_detect: 1 .. %d keys in a call (got %d)", kWmKeysMax, n_keys);
+    hipStream_t st = (hipStream_t)stream;
+    WdWorkspace* ws = nullptr;
+    CK(wd_correlate("watermark_detect", n, wave_dev, offset, n_samples, n_keys, carriers_dev, scores_dev, st, &ws));
+    hipLaunchKernelGGL(wd_score_kernel, dim3((unsigned)(n * n_keys)), dim3(256), 0, st, ws->clips, n_keys, (const float*)ws->r, scores_dev);
     CKL("wd_score");
     g_counters[CNT_WATERMARK_DETECT_LAUNCHES] += 4;
     g_counters[CNT_WATERMARK_DETECT_CLIPS] += n;
@@ -347,3 +492,18 @@ int f5hip_watermark_detect(int32_t n, const float* wave_dev, const int64_t* offs
 }
 
 int f5hip_watermark_detect_launches(void) { return 4; }
+
+int f5hip_watermark_read_ids(int32_t n, const float* wave_dev, const int64_t* offset, const int32_t* n_samples, int32_t n_keys,
+                             const int16_t* carriers_dev, float* rows_dev, void* stream) {
+    if (n_keys < 1 || n_keys > kWdIdKeysMax) return fail(-1, "watermark_read_ids: 1 .. %d keys in a call (got %d)", kWdIdKeysMax, n_keys);
+    hipStream_t st = (hipStream_t)stream;
+    WdWorkspace* ws = nullptr;
+    CK(wd_correlate("watermark_read_ids", n, wave_dev, offset, n_samples, n_keys * kWmTagRows, carriers_dev, rows_dev, st, &ws));
+    hipLaunchKernelGGL(watermark_id_score_kernel, dim3((unsigned)(n * n_keys)), dim3(256), 0, st, ws->clips, n_keys, (const float*)ws->r, rows_dev);
+    CKL("watermark_id_score");
+    g_counters[CNT_WATERMARK_READ_IDS_LAUNCHES] += 4;
+    g_counters[CNT_WATERMARK_READ_IDS_CLIPS] += n;
+    return 0;
+}
+
+int f5hip_watermark_read_ids_launches(void) { return 4; }

@@ -14,6 +14,16 @@
 //            only inside [0, nA)
 //   carrier  a sample j reads c[j & (P - 1)]; a group of 8 samples starts at a multiple of 8 and P is one, so it reads 8 values of one row
 //   sums     A <= 240 * 32768 < 2^23; |E c| < 2^23 * 2^13 = 2^36; |E c >> 23| <= 4336 * 0.9375 < 4066
+//
+// Trace ids (wave_mark_id_add_kernel / f5hip_wave_mark_ids, watermark_id_score_kernel / f5hip_watermark_read_ids; the definition is written
+// down in wave_codec.py beside the mark's): a key has kWmTagRows = 4 carrier rows, its own and its three sub-keys';
+//   symbols  s_d = (id >> 10 d) & 1023; C[m] = 2 c_K[m] + sum_d c_d[(m - 16 s_d) mod P]; y[j] = clip(x[j] + ((E C[j mod P]) >> 24))
+//   read     candidate s of sub-key d is r_d[(o* - 16 s) mod P]; ties to the smaller s
+// Bounds:
+//   rows     a group of 8 samples starts at j = 0 mod 8 and 16 s_d = 0 mod 8, so wm_id_index is a multiple of 8 at most P - 8: 8 values of
+//            one row, 16-byte aligned when the rows are; a request of key k reads rows 4 k .. 4 k + 3 of n_keys * 4
+//   sums     |C| <= 5 * 4336 = 21680; |E C| < 2^23 * 2^15 = 2^38; |E C >> 24| <= 21680 * 0.9375 / 2 = 10162.5, so |y - x| <= 10163
+//   grid     wd_id_offset is in [0, P) for o* in [0, P) and s in [0, 1024)
 #pragma once
 #include <stdint.h>
 
@@ -33,6 +43,17 @@ constexpr unsigned long long kWmKeyMax = (1ULL << 48) - 1;
 constexpr int kWmTileBlocks = 32;                     // 240-sample blocks per tile of either launch
 constexpr int kWmTile = kWmBlock * kWmTileBlocks;     // 7680 samples: a multiple of 8, so a group of 8 samples lies in one block
 static_assert(kWmBlock % 8 == 0 && kWmPeriod % 8 == 0, "wave_mark: a group of 8 samples shares its block and its carrier row");
+
+constexpr int kWmIdSymbols = 3;                       // WATERMARK_ID_SYMBOLS
+constexpr int kWmIdStep = 16;                         // WATERMARK_ID_STEP
+constexpr int kWmIdSymbolBits = 10;                   // WATERMARK_ID_BITS / WATERMARK_ID_SYMBOLS
+constexpr int kWmIdSymbolCount = 1 << kWmIdSymbolBits;
+constexpr int kWmIdMax = (1 << (kWmIdSymbols * kWmIdSymbolBits)) - 1;   // WATERMARK_ID_MAX
+constexpr int kWmIdShift = kWmShift + 1;              // WATERMARK_ID_SHIFT: the key's carrier counts twice in C
+constexpr int kWmTagRows = 1 + kWmIdSymbols;          // carrier rows of a key: its own, then its sub-keys 0 .. 2
+constexpr int kWdIdKeysMax = kWmKeysMax / kWmTagRows; // WATERMARK_ID_KEYS_MAX: keys of one f5hip_watermark_read_ids call
+constexpr int kWdIdRowWords = 4 + 2 * kWmIdSymbols;   // z, o*, r[o*], sigma, then (s_d, z_d) per symbol
+static_assert(kWmIdStep % 8 == 0 && kWmIdStep * kWmIdSymbolCount == kWmPeriod, "wave_mark: a rotation keeps a group of 8 samples in one row, and the symbols cover the period");
 
 constexpr int kWdBandLo = 22, kWdBandHi = 136;        // WATERMARK_BAND: bins of the 1024-point STFT
 constexpr int kWdMinSamples = 12000;                  // WATERMARK_MIN_SAMPLES
@@ -66,7 +87,20 @@ WM_HD int wm_mark(int x, int E, int c) {
     return (int)(y < -32768 ? -32768 : (y > 32767 ? 32767 : y));
 }
 
+// symbol d of a trace id, and where sample j of a request reads sub-key row d rotated by symbol s
+WM_HD int wm_id_symbol(int id, int d) { return (id >> (kWmIdSymbolBits * d)) & (kWmIdSymbolCount - 1); }
+WM_HD int wm_id_index(long long j, int s) { return (int)((j - (long long)kWmIdStep * s) & (kWmPeriod - 1)); }
+
+// one marked sample from the combined carrier C = 2 c_K (+ the rotated sub-key carriers): wm_mark(x, E, c) when C = 2 c
+WM_HD int wm_mark_id(int x, int E, int C) {
+    const long long y = (long long)x + (((long long)E * (long long)C) >> kWmIdShift);
+    return (int)(y < -32768 ? -32768 : (y > 32767 ? 32767 : y));
+}
+
 // ---- the detector
+// the offset of sub-key d's correlation that candidate symbol s reads, o the key's offset
+WM_HD int wd_id_offset(int o, int s) { return (o - kWmIdStep * s) & (kWmPeriod - 1); }
+
 // whether (v, i) takes the place of (bv, bi) as the maximum of r: the larger value, at equal values the smaller offset
 WM_HD bool wd_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
@@ -79,6 +113,13 @@ inline unsigned long long wm_splitmix64(unsigned long long* state) {
 }
 
 inline bool wm_key_ok(unsigned long long key) { return key >= 1 && key <= kWmKeyMax; }
+
+// sub-key d of a key (wave_codec.watermark_subkey): output number P / 64 + 1 + d of the generator whose first P / 64 outputs are the chips
+inline unsigned long long wm_subkey(unsigned long long key, int d) {
+    unsigned long long state = key, z = 0;
+    for (int k = 0; k < kWmPeriod / 64 + 1 + d; k++) z = wm_splitmix64(&state);
+    return 1 + z % kWmKeyMax;
+}
 
 // chips [kWmPeriod] (+1 / -1 as signed bytes) and carrier [kWmPeriod] of `key` from the taps g [kWmTaps]
 inline void wm_carrier(unsigned long long key, const int* g, signed char* chips, short* carrier) {

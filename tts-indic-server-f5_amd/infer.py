@@ -47,6 +47,8 @@ from .wave_codec import (PITCH_RANGE, PITCH_RATIOS, PROSODY_OPTIONS, WHOLE_WAVE_
 from .wave_codec import (WATERMARK_BAND, WATERMARK_BLOCK, WATERMARK_KEYS_MAX, WATERMARK_MAX_SAMPLES, WATERMARK_MIN_SAMPLES,  # noqa: F401
                          WATERMARK_OPTIONS, WATERMARK_PERIOD, WATERMARK_SHIFT, WATERMARK_TAPS, WATERMARK_THRESHOLD, WHOLE_WAVE_WATERMARK,
                          WatermarkScore, check_watermark, check_watermark_keys, detect_watermark, mark_pcm16, watermark_carrier)
+from .wave_codec import (WATERMARK_ID_BITS, WATERMARK_ID_KEYS_MAX, WATERMARK_ID_MAX, WATERMARK_ID_THRESHOLD, WatermarkRead, WatermarkTag,  # noqa: F401
+                         check_watermark_id, read_watermark, watermark_key, watermark_subkey)
 from .wave_codec import (LOUDNESS_GATE_ABS, LOUDNESS_PEAK_CEILING, LOUDNESS_RANGE, LOUDNESS_TAPS, check_loudness, loudness_gain,  # noqa: F401
                          loudness_gain_constant, loudness_lufs, loudness_taps, measure_loudness, normalise_loudness_pcm16)
 from .wave_codec import _device_taps, _tap_tables  # noqa: F401  (the two caches: used below, and read as infer._X by the tests that bound them)
@@ -908,7 +910,8 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     `sample_rate` / `encoding`, `loudness`, `flac_level`, `tempo`, `pitch`: each one value or one per request, None for the default; with the flag they are
     the request's `WaveSpec`, and a request that sets any of them gets `finish_pcm16` of its int16 PCM (quantised whatever `want` says).
     `watermark`: one key or one per request (`check_watermark`; None: no mark), carried beside the spec: the request's PCM gets `mark_pcm16`
-    between the prosody and the loudness steps.
+    between the prosody and the loudness steps.  In the place of a key a `WatermarkTag(key, id)` (or `{"key": K, "id": I}`) makes the mark
+    carry the request's trace id too (`read_watermark` reads it back): still one mark call for the batch, tagged and untagged together.
     `keep_formants`: one bool or one per request (`check_keep_formants`; None: no), carried beside the spec too: with it the request's
     `pitch` keeps the spectral envelope (`shift_pcm16(..., keep_formants=True)`); without a pitch it is refused.
     With `device_backend` all of it stays on the device, chained on one stream behind `wave_finish`: the calls and the copies that come back
@@ -923,7 +926,8 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     columns = [_per_request(value, n, name) for name, value in keywords]
     specs = [WaveSpec.of(dict(remove_silence=flag, sample_rate=rate, encoding=enc, loudness=lufs, flac_level=level, tempo=rate_of_speech, pitch=semitones))
              for flag, rate, enc, lufs, level, rate_of_speech, semitones in zip(flags, *columns)]
-    marks = [check_watermark(key) for key in _per_request(watermark, n, "watermark")]
+    one = isinstance(watermark, (WatermarkTag, dict))   # (a tag is a tuple: one value, not one per request)
+    marks = [check_watermark(key) for key in ([watermark] * n if one else _per_request(watermark, n, "watermark"))]
     keeps = [check_keep_formants(keep, spec.pitch) for keep, spec in zip(_per_request(keep_formants, n, "keep_formants"), specs)]
     return _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend, want, marks, keeps)
 
@@ -1025,7 +1029,8 @@ def _finish_on_device(requests, fade, specs, watermark=None, keep_formants=None)
     through), whose buffer, offsets, bounds and device lengths everything downstream reads in the place of `wave_finish`'s -- with a flag in
     `keep_formants` (one per request, None: nobody) the same ONE call, flagged and unflagged requests together: a flagged request takes the
     stretch of its tempo alone and keeps its spectral envelope (`backend_stats["formant_requests"]`);
-    then, when any request has a key in `watermark` (one per request, None: nobody), ONE `ops.wave_mark` call that marks those in place
+    then, when any request has a key or a `WatermarkTag` in `watermark` (one per request, None: nobody), ONE `ops.wave_mark` call that marks
+    those in place, with their trace ids where they have one (f5hip_wave_mark_ids then; the same two launches, no copy more)
     (carriers cached on the device: nothing is uploaded for a key seen before, and nothing comes back);
     then, when any request has a loudness target, ONE `ops.wave_loudness` call that normalises those in place; then on the
     same stream one `ops.wave_flac` call per distinct rate of the "flac" requests (behind a `wave_encode(..., "pcm16")` call where the rate

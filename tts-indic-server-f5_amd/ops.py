@@ -920,12 +920,23 @@ def watermark_carriers(keys, device):
     return rows[0].reshape(1, -1) if len(rows) == 1 else torch.stack(rows)
 
 
-def _check_carriers(op, carriers, device):
+def watermark_tag_carriers(keys, device):
+    """The carriers of `keys` for calls with trace ids as ONE int16 tensor [len(keys), 4, 16384] on `device`, what `wave_mark` (for tags)
+    and `watermark_read_ids` hand to the library: per key its own carrier, then those of its sub-keys 0 .. 2
+    (`wave_codec.watermark_subkey`).  Each distinct key's four rows are uploaded once per device and kept (the last
+    `wave_codec.TAP_TABLE_CACHE`); several keys are stacked on the device."""
     from . import wave_codec
-    if not (torch.is_tensor(carriers) and carriers.dtype == torch.int16 and carriers.is_cuda and carriers.is_contiguous() and carriers.dim() == 2
-            and carriers.shape[1] == wave_codec.WATERMARK_PERIOD and 1 <= carriers.shape[0] <= wave_codec.WATERMARK_KEYS_MAX and carriers.device == device):
-        raise _lib.F5HipError(f"{op}: carriers must be a contiguous int16 tensor [1 .. {wave_codec.WATERMARK_KEYS_MAX}, {wave_codec.WATERMARK_PERIOD}] "
-                              "on the samples' device")
+    rows = [wave_codec._device_tag_carriers(k, device) for k in keys]
+    return rows[0][None] if len(rows) == 1 else torch.stack(rows)
+
+
+def _check_carriers(op, carriers, device, tagged=False):
+    from . import wave_codec
+    most = wave_codec.WATERMARK_ID_KEYS_MAX if op == "watermark_read_ids" else wave_codec.WATERMARK_KEYS_MAX
+    shape = (4, wave_codec.WATERMARK_PERIOD) if tagged else (wave_codec.WATERMARK_PERIOD,)
+    if not (torch.is_tensor(carriers) and carriers.dtype == torch.int16 and carriers.is_cuda and carriers.is_contiguous() and tuple(carriers.shape[1:]) == shape
+            and 1 <= carriers.shape[0] <= most and carriers.device == device):
+        raise _lib.F5HipError(f"{op}: carriers must be a contiguous int16 tensor [1 .. {most}, {', '.join(map(str, shape))}] on the samples' device")
 
 
 def wave_mark(pcm, in_off, max_len, len_dev, keys):
@@ -934,7 +945,8 @@ def wave_mark(pcm, in_off, max_len, len_dev, keys):
     `wave_prosody`'s buffer; request i starts at sample in_off[i]); `max_len`, `len_dev` as in `wave_encode`; `keys` [n]: each request's key
     (`wave_codec.check_watermark`), None for a request that is left alone.  A call without a flagged request launches nothing.  Afterwards a
     flagged request's samples are `wave_codec.mark_pcm16`'s, bit for bit; the others and the samples between requests keep their bits.
-    Returns `pcm`."""
+    A value of `keys` may be a `wave_codec.WatermarkTag(key, id)` (or its dict): that request's mark carries the trace id too, and the call
+    is f5hip_wave_mark_ids', still two launches; with no tag among them nothing changes.  Returns `pcm`."""
     from . import wave_codec
     (pcm,), io, ml, n, len_dev = _pcm_requests("wave_mark", pcm, in_off, max_len, len_dev)
     keys = list(keys)
@@ -944,22 +956,54 @@ def wave_mark(pcm, in_off, max_len, len_dev, keys):
         keys = [wave_codec.check_watermark(k) for k in keys]
     except ValueError as e:
         raise _lib.F5HipError(f"wave_mark: {e}") from e
+    tagged = any(isinstance(k, wave_codec.WatermarkTag) for k in keys)
+    ids = np.ascontiguousarray(np.asarray([k.id if isinstance(k, wave_codec.WatermarkTag) else -1 for k in keys], dtype=np.int32))
+    keys = [wave_codec.watermark_key(k) for k in keys]
     distinct = sorted({k for k in keys if k is not None})
     if len(distinct) > wave_codec.WATERMARK_KEYS_MAX:
         raise _lib.F5HipError(f"wave_mark: at most {wave_codec.WATERMARK_KEYS_MAX} distinct keys in a call (got {len(distinct)})")
     ki = np.ascontiguousarray(np.asarray([-1 if k is None else distinct.index(k) for k in keys], dtype=np.int32))
-    carriers = watermark_carriers(distinct, pcm.device) if distinct else None
+    carriers = None if not distinct else watermark_tag_carriers(distinct, pcm.device) if tagged else watermark_carriers(distinct, pcm.device)
     if torch_ops.load():
-        call_op("wave_mark", pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(ki), carriers)
+        if tagged:
+            call_op("wave_mark_ids", pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(ki), torch.from_numpy(ids), carriers)
+        else:
+            call_op("wave_mark", pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(ki), carriers)
         return pcm
     anchor, rel = _pcm_sources("wave_mark", [pcm], io, ml)
     if int(ml.astype(np.int64).sum()) > 2 ** 31 - 1:
         raise _lib.F5HipError("wave_mark: the call exceeds 2^31 - 1 samples")
     if distinct and pcm.numel():
         with torch.cuda.device(pcm.device):
-            _lib.check(_lib.lib().f5hip_wave_mark(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(ki), _p(carriers), len(distinct), _lib.current_stream_ptr()),
-                       "f5hip_wave_mark")
+            if tagged:
+                _lib.check(_lib.lib().f5hip_wave_mark_ids(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(ki), _p(ids), _p(carriers), len(distinct),
+                                                          _lib.current_stream_ptr()), "f5hip_wave_mark_ids")
+            else:
+                _lib.check(_lib.lib().f5hip_wave_mark(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(ki), _p(carriers), len(distinct), _lib.current_stream_ptr()),
+                           "f5hip_wave_mark")
     return pcm
+
+
+def _watermark_rows(op, wave, offsets, lengths, carriers, ids):
+    """`watermark_detect` (ids False) and `watermark_read_ids` under their names: the clip checks, then either binding."""
+    from . import wave_codec
+    ln = _per_request(op, "lengths", lengths, np.int32, per="clip")
+    off = _per_request(op, "offsets", offsets, np.int64, len(ln), per="clip")
+    if not (torch.is_tensor(wave) and wave.dtype == torch.float32 and wave.is_contiguous() and wave.is_cuda and wave.dim() == 1):
+        raise _lib.F5HipError(f"{op}: wave must be a contiguous 1-D fp32 tensor on the HIP device")
+    _check_carriers(op, carriers, wave.device, ids)
+    if torch_ops.load():
+        return call_op(op, wave, torch.from_numpy(off), torch.from_numpy(ln), carriers)
+    for i in range(len(ln)):
+        if ln[i] < 1 or ln[i] > wave_codec.WATERMARK_MAX_SAMPLES:
+            raise _lib.F5HipError(f"{op}: clip {i} has {ln[i]} samples (1 .. {wave_codec.WATERMARK_MAX_SAMPLES})")
+        if off[i] < 0 or int(off[i]) + int(ln[i]) > wave.numel():
+            raise _lib.F5HipError(f"{op}: clip {i} is samples [{off[i]}, {int(off[i]) + int(ln[i])}) of a tensor of {wave.numel()}")
+    call = _lib.lib().f5hip_watermark_read_ids if ids else _lib.lib().f5hip_watermark_detect
+    with torch.cuda.device(wave.device):
+        rows = torch.empty(len(ln), carriers.shape[0], 10 if ids else 4, device=wave.device, dtype=torch.float32)
+        _lib.check(call(len(ln), _p(wave), _p(off), _p(ln), carriers.shape[0], _p(carriers), _p(rows), _lib.current_stream_ptr()), f"f5hip_{op}")
+    return rows
 
 
 def watermark_detect(wave, offsets, lengths, carriers):
@@ -969,30 +1013,38 @@ def watermark_detect(wave, offsets, lengths, carriers):
     `wave_codec.WATERMARK_MAX_SAMPLES` samples, disjoint ranges; `carriers`: `watermark_carriers(keys, device)`.  Returns scores, fp32 device
     [n, n_keys, 4]: z, the offset, r at the offset and the deviation of r; a clip below `wave_codec.WATERMARK_MIN_SAMPLES` scores zeros.  A
     clip's rows equal its own single-clip call's bit for bit."""
-    from . import wave_codec
-    ln = _per_request("watermark_detect", "lengths", lengths, np.int32, per="clip")
-    off = _per_request("watermark_detect", "offsets", offsets, np.int64, len(ln), per="clip")
-    if not (torch.is_tensor(wave) and wave.dtype == torch.float32 and wave.is_contiguous() and wave.is_cuda and wave.dim() == 1):
-        raise _lib.F5HipError("watermark_detect: wave must be a contiguous 1-D fp32 tensor on the HIP device")
-    _check_carriers("watermark_detect", carriers, wave.device)
-    if torch_ops.load():
-        return call_op("watermark_detect", wave, torch.from_numpy(off), torch.from_numpy(ln), carriers)
-    for i in range(len(ln)):
-        if ln[i] < 1 or ln[i] > wave_codec.WATERMARK_MAX_SAMPLES:
-            raise _lib.F5HipError(f"watermark_detect: clip {i} has {ln[i]} samples (1 .. {wave_codec.WATERMARK_MAX_SAMPLES})")
-        if off[i] < 0 or int(off[i]) + int(ln[i]) > wave.numel():
-            raise _lib.F5HipError(f"watermark_detect: clip {i} is samples [{off[i]}, {int(off[i]) + int(ln[i])}) of a tensor of {wave.numel()}")
-    with torch.cuda.device(wave.device):
-        scores = torch.empty(len(ln), carriers.shape[0], 4, device=wave.device, dtype=torch.float32)
-        _lib.check(_lib.lib().f5hip_watermark_detect(len(ln), _p(wave), _p(off), _p(ln), carriers.shape[0], _p(carriers), _p(scores), _lib.current_stream_ptr()),
-                   "f5hip_watermark_detect")
-    return scores
+    return _watermark_rows("watermark_detect", wave, offsets, lengths, carriers, False)
 
 
 def watermark_scores(rows, keys) -> list:
     """`wave_codec.WatermarkScore`s of one clip's downloaded score rows [n_keys, 4]."""
     from . import wave_codec
     return [wave_codec.WatermarkScore(k, float(z), int(o), bool(z >= wave_codec.WATERMARK_THRESHOLD)) for k, (z, o, _, _) in zip(keys, rows.tolist())]
+
+
+def watermark_read_ids_launches():
+    """Launches of one `watermark_read_ids` call (4)."""
+    return int(_lib.lib().f5hip_watermark_read_ids_launches())
+
+
+def watermark_read_ids(wave, offsets, lengths, carriers):
+    """Several clips scored against 1 to 4 keys and read for the trace ids their marks carry in ONE library call and four launches
+    (include/f5hip.h f5hip_watermark_read_ids): `wave_codec.read_watermark` of each clip in fp32.  `wave`, `offsets`, `lengths` as
+    `watermark_detect`'s; `carriers`: `watermark_tag_carriers(keys, device)`.  Returns rows, fp32 device [n, n_keys, 10]: `watermark_detect`'s
+    four words of that clip and key, bit for bit, then (s_d, z_d) of the three symbols; `watermark_reads` turns a clip's rows into
+    `WatermarkRead`s.  A clip's rows equal its own single-clip call's bit for bit."""
+    return _watermark_rows("watermark_read_ids", wave, offsets, lengths, carriers, True)
+
+
+def watermark_reads(rows, keys) -> list:
+    """`wave_codec.WatermarkRead`s of one clip's downloaded rows [n_keys, 10], by `wave_codec.watermark_read`'s rule: the id only when the
+    key is detected and every symbol scores `WATERMARK_ID_THRESHOLD`."""
+    from . import wave_codec
+    out = []
+    for k, row in zip(keys, rows.tolist()):
+        score = wave_codec.WatermarkScore(k, float(row[0]), int(row[1]), bool(row[0] >= wave_codec.WATERMARK_THRESHOLD))
+        out.append(wave_codec.watermark_read(score, [(int(row[4 + 2 * d]), float(row[5 + 2 * d])) for d in range(wave_codec.WATERMARK_ID_SYMBOLS)]))
+    return out
 
 
 def flac_decode_packed(buffer, spans, device=None):

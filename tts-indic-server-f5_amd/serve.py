@@ -56,7 +56,7 @@ EDIT_MARK = infer.WATERMARK_OPTIONS   # beside them: the whole returned recordin
 MAX_NFE_STEP = {"euler": 128, "midpoint": 64, "rk4": 42}
 
 
-def check_request_options(options: dict, ode_method: str = "euler", allowed=infer.REQUEST_OPTIONS) -> dict:
+def check_request_options(options: dict, ode_method: str = "euler", allowed=infer.REQUEST_OPTIONS, watermark=None) -> dict:
     """The per-request sampler options a client set (None = not set, dropped), checked before anything is queued: ValueError with a message
     the routes return as 400.  `speed` finite and > 0; `nfe_step` an integer in 1..MAX_NFE_STEP[ode_method]; `cfg_strength` and
     `sway_sampling_coef` finite; `seed` an integer in 0..2**63 - 1; `ode_method` one of MAX_NFE_STEP's names.  `ode_method` (the argument)
@@ -64,7 +64,9 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
     The delivery options by `infer.WaveSpec`'s validators, one by one and then together (a `flac_level` beside another encoding is refused,
     never ignored; a `tempo` and a `pitch` whose combined stretch leaves 1/2 .. 2 likewise); `remove_silence` must be a bool, and `flac_level`
     is not "1".  What a request gets anyway -- False, 24000, "pcm16", level 0, tempo 1.0, pitch 0 -- is dropped like None: the request is
-    then what it is without the option.  `watermark` by `infer.check_watermark`: an integer key from 1 to 2^48 - 1.  `keep_formants` by
+    then what it is without the option.  `watermark` by `infer.check_watermark`: an integer key from 1 to 2^48 - 1, or `{"key": K, "id": I}`
+    with a trace id from 0 to 2^30 - 1 (an `infer.WatermarkTag`); `{"id": I}` alone takes the key of `watermark` (the argument: the
+    service's own key or tag) and is refused without one.  `keep_formants` by
     `infer.check_keep_formants`: a bool (false is dropped), and true only beside a non-zero `pitch`."""
     out = {}
     own = options.get("ode_method") if "ode_method" in allowed else None
@@ -103,7 +105,7 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
             if v == 0:
                 continue
         elif k == "watermark":
-            v = infer.check_watermark(v)                # ValueError: "watermark must be an integer key ..."
+            v = infer.check_watermark(v, watermark)     # ValueError: "watermark must be an integer key ...", "watermark id must be ..."
         elif k == "keep_formants":
             if not infer.check_keep_formants(v):        # ValueError: "keep_formants must be true or false ..."
                 continue
@@ -446,10 +448,12 @@ class TTSManager:
                  sway_sampling_coef: float = infer.sway_sampling_coef, speed: float = infer.speed, mel_spec_type: str = "vocos",
                  micro_batch: dict | None = None, batch_invariant: bool = True, clip_cache: int = 64, device_frontend: bool | None = None,
                  device_backend: bool | None = None, device_decode: bool | None = None, device_prestep: bool | None = None,
-                 watermark: int | None = None, reject_marked=None, reference_limits: dict | None = None):
+                 watermark=None, reject_marked=None, reference_limits: dict | None = None):
         self.loader = loader
         # The key (`infer.check_watermark`) every finished wave is marked with unless its request names its own; None: no mark.  A mark needs
-        # the whole wave, so with a key here the streaming paths are refused (`STREAM_WATERMARK`) rather than left unmarked.
+        # the whole wave, so with a key here the streaming paths are refused (`STREAM_WATERMARK`) rather than left unmarked.  A tag
+        # (`{"key": K, "id": I}`, e.g. one id per deployment) marks every such wave with its trace id too; a request's `{"id": I}` takes
+        # the key from here.
         self.watermark = infer.check_watermark(watermark)
         # Keys (1 .. 16, or one) whose mark an uploaded reference clip must not carry: a new upload whose prepared 24 kHz wave scores at or
         # above `infer.WATERMARK_THRESHOLD` for any of them is refused (`MARKED_REFERENCE`) before it is denoised, cached or queued.  None: no check
@@ -508,7 +512,7 @@ class TTSManager:
 
     def request_options(self, allowed=infer.REQUEST_OPTIONS, **options) -> dict:
         """`check_request_options` for this manager's solver: the options a request sets (absent / None ones fall back to `self.opts`)."""
-        out = check_request_options(options, self.ode_method, allowed)
+        out = check_request_options(options, self.ode_method, allowed, self.watermark)
         if self.watermark is not None and "watermark" in allowed:
             out.setdefault("watermark", self.watermark)   # the manager's key for a request that names none
         return out
@@ -1005,11 +1009,16 @@ class TTSManager:
         bytes, or a (wave [ch, n], sr) pair --, read the way a reference upload is read: `decode_audio`, mono mix, sinc resampling to 24 kHz
         (`infer.resample_sinc_hann`).  `keys`: 1 to 16 keys; None: this manager's own `watermark`.  ValueError when neither is given, for a bad
         key and for audio that cannot be read.  Host arithmetic in fp64 (`infer.detect_watermark`)."""
+        keys, mono = self._watermark_clip("detect_watermark", audio, keys)
+        return infer.detect_watermark(mono, keys)
+
+    def _watermark_clip(self, what, audio, keys):
+        """(keys, the recording as mono 24 kHz fp32 [n]) of `detect_watermark` and `read_watermark`."""
         import torch
         if keys is None:
             if self.watermark is None:
-                raise ValueError("detect_watermark needs keys: this manager has no watermark key of its own")
-            keys = [self.watermark]
+                raise ValueError(f"{what} needs keys: this manager has no watermark key of its own")
+            keys = [infer.watermark_key(self.watermark)]
         keys = infer.check_watermark_keys(keys)
         wave, sr = audio if isinstance(audio, tuple) else self.decode_audio(audio)
         wave = torch.as_tensor(wave, dtype=torch.float32)
@@ -1020,7 +1029,26 @@ class TTSManager:
         mono = wave.mean(dim=0, keepdim=True)
         if int(sr) != infer.target_sample_rate:
             mono = infer.resample_sinc_hann(mono, int(sr), infer.target_sample_rate)
-        return infer.detect_watermark(mono[0].numpy(), keys)
+        return keys, mono[0].numpy()
+
+    def read_watermark(self, audio, keys=None) -> list:
+        """Which request a recording came from: one `infer.WatermarkRead(key, z, offset, detected, id, id_z)` per key -- `detect_watermark`'s
+        score and the trace id the key's mark carries (None when the key is not detected or a symbol stays below
+        `infer.WATERMARK_ID_THRESHOLD`) with the smallest symbol score.  `audio` and `keys` as `detect_watermark`'s.  With `device_frontend` and
+        a model on a GPU the clip is read there, the way uploads are scored for `reject_marked`: ONE `ops.watermark_read_ids` call per four
+        keys under the device lock, fp32; otherwise on the host in fp64 (`infer.read_watermark`)."""
+        import torch
+        keys, mono = self._watermark_clip("read_watermark", audio, keys)
+        device = getattr(getattr(self.model_obj, "local", self.model_obj), "device", None)
+        if not (self.device_frontend and device is not None and torch.device(device).type == "cuda") or not np.isfinite(mono).all():
+            return infer.read_watermark(mono, keys)              # (a sample that is not finite is the host's ValueError)
+        from . import ops
+        n, most, out = min(len(mono), infer.WATERMARK_MAX_SAMPLES), infer.WATERMARK_ID_KEYS_MAX, []
+        with self._device_lock:
+            wave = torch.from_numpy(mono[:n].copy()).to(device)
+            rows = [ops.watermark_read_ids(wave, [0], [n], ops.watermark_tag_carriers(keys[at:at + most], wave.device)) for at in range(0, len(keys), most)]
+            rows = torch.cat(rows, dim=1)[0].cpu().numpy()
+        return ops.watermark_reads(rows, keys)
 
     def check_reference(self, audio, clip_short=True):
         """The `infer.ReferenceReport` of a would-be reference clip -- WAV or FLAC bytes, or a (wave [ch, n], sr) pair -- taken through
@@ -1133,7 +1161,7 @@ def request_models():
         remove_silence: bool | None = None
         tempo: typing.Any = None                     # 0.5 to 2 in steps of 0.01: the duration divided by it, the pitch kept (infer.shift_pcm16); untyped like flac_level
         pitch: typing.Any = None                     # whole semitones, -6 to 6, the duration kept; untyped, so that true and 2.0 arrive as sent and are refused
-        watermark: typing.Any = None                 # the key of a provenance mark, 1 to 2^48 - 1 (infer.mark_pcm16); untyped, so that true, 1.0 and "1" are refused
+        watermark: typing.Any = None                 # the key of a provenance mark, 1 to 2^48 - 1, or {"key": K, "id": I} with a trace id (infer.mark_pcm16); untyped, so that true, 1.0 and "1" are refused
         keep_formants: typing.Any = None             # true beside a non-zero pitch: the voice's formants stay where they were (infer.psola_pcm16); untyped, so that 1 and "true" are refused
 
     class KannadaSynthesizeRequest(SpeechFields):    # S/utils/tts_utils.py:27-28
@@ -1179,6 +1207,7 @@ def request_models():
     class DetectRequest(BaseModel):                  # `/v1/audio/watermark/detect`: a recording (base64 WAV or FLAC) and the keys to score it against
         audio: str
         keys: typing.Any = None                      # 1 to 16 keys; absent: the manager's own.  Untyped, so that a bad key arrives as sent and is refused
+        ids: typing.Any = None                       # true: also read the trace id each key's mark carries (TTSManager.read_watermark)
 
     class ReferenceCheckRequest(BaseModel):          # `/v1/audio/reference/check`: a would-be reference clip (base64 WAV or FLAC)
         audio: str
@@ -1209,7 +1238,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     `"stream": true`: `STREAM_PROSODY`; not on the edit route, which keeps the recording's timing) and beside a non-zero `pitch` `keep_formants` (true: the
     pitch moves and the voice's formants stay, `infer.psola_pcm16`; 400 for anything but a bool and without a pitch), every route `watermark` (a key, 1 to 2^48 - 1: the finished wave
     carries that key's provenance mark, `infer.mark_pcm16`; a bad key is a 400, and so is the option together with `"stream": true`:
-    `STREAM_WATERMARK`; `/v1/audio/watermark/detect` scores a recording against keys), and `response_format` ("wav", or "pcm" for the headerless samples / code bytes
+    `STREAM_WATERMARK`; `{"key": K, "id": I}` in its place makes the mark carry a trace id from 0 to 2^30 - 1, `{"id": I}` alone with the manager's key; `/v1/audio/watermark/detect` scores a recording against keys and with `"ids": true` reads the ids back), and `response_format` ("wav", or "pcm" for the headerless samples / code bytes
     as `audio/pcm`); streamed or not, the body's samples are the same bytes.  `encoding: "flac"` is its own container: the body is the
     native FLAC stream as `audio/flac` with a `.flac` file name, and `response_format` must be absent (400 with "wav" or "pcm" beside it);
     streamed, the stream header comes with the totals unknown."""
@@ -1381,20 +1410,25 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
 
     def _run_detect(req):
         """`/v1/audio/watermark/detect`: {"audio": base64 WAV or FLAC, "keys"?: [1 .. 16 keys]} -> {"results": [{"key", "detected", "score",
-        "offset"}]}, one per key (`TTSManager.detect_watermark`; no key in the body: the manager's own).  Needs no loaded model."""
+        "offset"}]}, one per key (`TTSManager.detect_watermark`; no key in the body: the manager's own).  Needs no loaded model.  With "ids": true
+        each result also has "id" (the trace id the key's mark carries, or null) and "id_score" (`TTSManager.read_watermark`)."""
         try:
             raw = base64.b64decode(req.audio, validate=True)
         except (binascii.Error, ValueError):
             raise HTTPException(status_code=400, detail="Audio must be a base64-encoded WAV or FLAC file.")
         try:
             keys = None if req.keys is None else infer.check_watermark_keys(req.keys)   # (before the recording is decoded)
+            if req.ids is not None and not isinstance(req.ids, bool):
+                raise ValueError(f"ids must be true or false (got {req.ids!r})")
             try:
                 audio = tts_manager.decode_audio(raw)
             except ValueError as e:
                 raise ValueError(f"Invalid audio: {e}") from e
-            scores = tts_manager.detect_watermark(audio, keys)
+            scores = tts_manager.read_watermark(audio, keys) if req.ids else tts_manager.detect_watermark(audio, keys)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
+        if req.ids:
+            return {"results": [dict(key=s.key, detected=s.detected, score=s.z, offset=s.offset, id=s.id, id_score=s.id_z) for s in scores]}
         return {"results": [dict(key=s.key, detected=s.detected, score=s.z, offset=s.offset) for s in scores]}
 
     def _run_check(req):

@@ -947,6 +947,25 @@ def psola_pcm16(pcm, pitch) -> np.ndarray:
 #              Sample 0 of the clip was sample o* (mod P) of the marked wave.
 # Threshold: r across offsets is close to Gaussian with about P 2.7 / 12 = 3700 independent values, so 7.0 gives about 5e-9 false alarms
 # per (clip, key).
+#
+# Trace ids: a 30-bit payload beside the key (`WatermarkTag(key, id)`, `read_watermark`), carried as the rotation of three more carriers
+# relative to the key's (code-shift keying).  Everything above stays; a key alone marks and scores as before.
+#   constants  WATERMARK_ID_BITS = 30, WATERMARK_ID_SYMBOLS D = 3, WATERMARK_ID_STEP G = 16 (1024 rotations per symbol, 10 bits each),
+#              WATERMARK_ID_MAX = 2^30 - 1, WATERMARK_ID_THRESHOLD = 6.0
+#   sub-keys   `watermark_subkey(K, d)`, d = 0, 1, 2: 1 + (z mod (2^48 - 1)), z the SplitMix64 output number 257 + d of the generator
+#              started at state K (outputs 1 .. 256 are the key's chips).  A sub-key is an ordinary key: its carrier c_d is
+#              `watermark_carrier(subkey)`.  K = 1: 160832003273966, 194807364317806, 17338898203305
+#   symbols    s_d = (id >> 10 d) & 1023
+#   carrier    C[m] = 2 c_K[m] + sum_d c_d[(m - 16 s_d) mod P], int32, |C| <= 5 * 4336 = 21680
+#   mark       A, E as above; y[j] = clip(x[j] + ((E[j // 240] C[j mod P]) >> 24), -32768, 32767): 64-bit product, floor shift.  Without an
+#              id the sum over d is absent, and (2 c E) >> 24 == (c E) >> 23: a key alone is the mark above byte for byte.  E <= 2^23 *
+#              0.9375, so |E C| / 2^24 <= 21680 * 0.9375 / 2 = 10162.5 and |y - x| <= 10163 (`WATERMARK_ID_DELTA_MAX`; the floor of a
+#              negative half) for any chips.  The length is kept, zeros stay zeros, block b depends on blocks b-1 .. b+1 only
+#   read       Z, the key's r_K, o* and z as above.  r_d = the correlation of Z with c_d by the same formula; candidate s takes
+#              r_d[(o* - 16 s) mod P]; s_d = the smallest argmax over s = 0 .. 1023; z_d = (r_d there - mean r_d) / std r_d (population,
+#              over all P offsets), 0 when std r_d = 0; id_z = min_d z_d.  The id (sum_d s_d << 10 d) is reported only when the key is
+#              detected (z >= 7.0) and every z_d >= 6.0, otherwise None
+# Threshold: the best of 1024 candidates at 6 sigma is about 1024 * 1e-9 = 1e-6 false symbols per symbol.
 WATERMARK_PERIOD = 16384
 WATERMARK_BLOCK = 240
 WATERMARK_TAPS = 129
@@ -960,30 +979,75 @@ WATERMARK_KEY_MAX = (1 << 48) - 1
 WATERMARK_OPTIONS = ("watermark",)                # beside DELIVERY_OPTIONS and PROSODY_OPTIONS; carried next to the WaveSpec, not in it
 WHOLE_WAVE_WATERMARK = ("watermark marks the request's whole wave: it is not available for a list of chunk texts, on a streaming path or "
                         "with join=False")
+WATERMARK_ID_BITS = 30
+WATERMARK_ID_SYMBOLS = 3
+WATERMARK_ID_STEP = 16
+WATERMARK_ID_MAX = (1 << WATERMARK_ID_BITS) - 1
+WATERMARK_ID_THRESHOLD = 6.0
+WATERMARK_ID_SHIFT = WATERMARK_SHIFT + 1           # the key's carrier counts twice in C
+WATERMARK_ID_DELTA_MAX = 10163                     # |y - x| of a tagged request, for any chips
+WATERMARK_ID_KEYS_MAX = 4                          # keys of one `ops.watermark_read_ids` call: four carrier rows each
+_ID_SYMBOL_BITS = WATERMARK_ID_BITS // WATERMARK_ID_SYMBOLS
+_ID_SYMBOL_COUNT = 1 << _ID_SYMBOL_BITS
 WatermarkScore = collections.namedtuple("WatermarkScore", "key z offset detected")
+WatermarkTag = collections.namedtuple("WatermarkTag", "key id")                    # a key and the trace id its mark carries
+WatermarkRead = collections.namedtuple("WatermarkRead", "key z offset detected id id_z")
 _watermark_taps = None
 _watermark_carriers: collections.OrderedDict = collections.OrderedDict()   # key -> carrier; the last TAP_TABLE_CACHE keys: a request chooses its key
 _carriers_on_device: collections.OrderedDict = collections.OrderedDict()   # (key, device) -> the carrier there
+_tag_carriers_on_device: collections.OrderedDict = collections.OrderedDict()   # (key, device) -> its four rows there: its own, then its sub-keys'
 _M64 = (1 << 64) - 1
 
 
-def check_watermark(key):
-    """A request's `watermark` option: None (absent) stays None; an int in 1 .. 2^48 - 1 is the key; a bool, a float, a string and any
-    other value are a ValueError."""
-    if key is None:
-        return None
+def _check_key(key) -> int:
     if isinstance(key, (bool, np.bool_)) or not isinstance(key, (int, np.integer)) or not 1 <= int(key) <= WATERMARK_KEY_MAX:
         raise ValueError(f"watermark must be an integer key from 1 to 2^48 - 1 (got {key!r})")
     return int(key)
 
 
+def check_watermark_id(value) -> int:
+    """A trace id: an int in 0 .. 2^30 - 1; a bool, a float and a value out of range are a ValueError."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) <= WATERMARK_ID_MAX:
+        raise ValueError(f"watermark id must be an integer from 0 to 2^30 - 1 (got {value!r})")
+    return int(value)
+
+
+def watermark_key(mark):
+    """The key of a checked `watermark` value (an int or a `WatermarkTag`), None of None."""
+    return mark.key if isinstance(mark, WatermarkTag) else mark
+
+
+def check_watermark(key, default=None):
+    """A request's `watermark` option: None (absent) stays None; an int in 1 .. 2^48 - 1 is the key; a bool, a float, a string and any
+    other value are a ValueError.  `{"key": K, "id": I}` (or a `WatermarkTag`) is a key with a trace id, 0 .. 2^30 - 1, and gives
+    `WatermarkTag(K, I)`; `{"id": I}` alone takes the key of `default` (a checked value: a service's own key) and is a ValueError without
+    one; `{"key": K}` is the key K.  Any other entry of the dict is a ValueError that names it."""
+    if key is None:
+        return None
+    if isinstance(key, WatermarkTag):
+        key = {"key": key.key, "id": key.id}
+    if isinstance(key, dict):
+        unknown = [k for k in key if k not in ("key", "id")]
+        if unknown:
+            raise ValueError(f"watermark has an unknown entry {unknown[0]!r}: a key with a trace id is {{\"key\": K, \"id\": I}}")
+        k, i = key.get("key"), key.get("id")
+        if k is None:
+            k = watermark_key(default)
+            if k is None:
+                raise ValueError(f"watermark names an id without a key, and the service has no key of its own (got {key!r})")
+        k = _check_key(k)
+        return k if i is None else WatermarkTag(k, check_watermark_id(i))
+    return _check_key(key)
+
+
 def check_watermark_keys(keys) -> list:
-    """The keys a clip is scored against: 1 .. WATERMARK_KEYS_MAX of them, each by `check_watermark` (one key may stand for its list)."""
+    """The keys a clip is scored against: 1 .. WATERMARK_KEYS_MAX of them, each an int by `check_watermark` (one key may stand for its
+    list)."""
     if isinstance(keys, (int, np.integer)) and not isinstance(keys, (bool, np.bool_)):
         keys = [keys]
     if not isinstance(keys, (list, tuple)) or not 1 <= len(keys) <= WATERMARK_KEYS_MAX or any(k is None for k in keys):
         raise ValueError(f"watermark keys must be a list of 1 to {WATERMARK_KEYS_MAX} keys (got {keys!r})")
-    return [check_watermark(k) for k in keys]
+    return [_check_key(k) for k in keys]
 
 
 def splitmix64(state: int):
@@ -1042,9 +1106,51 @@ def _device_carrier(key, device):
     return hit if hit is not None else _lru_put(_carriers_on_device, key, torch.from_numpy(watermark_carrier(key[0]).copy()).to(device))
 
 
+def watermark_subkey(key, d) -> int:
+    """Sub-key d (0 .. WATERMARK_ID_SYMBOLS - 1) of a key: an ordinary key, whose carrier holds symbol d of a trace id."""
+    state = _check_key(key)
+    if isinstance(d, (bool, np.bool_)) or not isinstance(d, (int, np.integer)) or not 0 <= d < WATERMARK_ID_SYMBOLS:
+        raise ValueError(f"watermark_subkey: d is 0 .. {WATERMARK_ID_SYMBOLS - 1} (got {d!r})")
+    for _ in range(WATERMARK_PERIOD // 64 + 1 + int(d)):                               # output number 257 + d
+        state, z = splitmix64(state)
+    return 1 + z % WATERMARK_KEY_MAX
+
+
+def watermark_subkeys(key) -> list:
+    return [watermark_subkey(key, d) for d in range(WATERMARK_ID_SYMBOLS)]
+
+
+def watermark_id_symbols(value) -> list:
+    """s_d of a trace id, d = 0 .. WATERMARK_ID_SYMBOLS - 1."""
+    value = check_watermark_id(value)
+    return [(value >> (_ID_SYMBOL_BITS * d)) & (_ID_SYMBOL_COUNT - 1) for d in range(WATERMARK_ID_SYMBOLS)]
+
+
+def watermark_tag_carrier(mark) -> np.ndarray:
+    """C of the definition above, int64 [WATERMARK_PERIOD]: 2 c_K, and with an id the three rotated sub-key carriers added."""
+    mark = check_watermark(mark)
+    C = 2 * watermark_carrier(watermark_key(mark)).astype(np.int64)
+    if isinstance(mark, WatermarkTag):
+        for sub, s in zip(watermark_subkeys(mark.key), watermark_id_symbols(mark.id)):
+            C += np.roll(watermark_carrier(sub).astype(np.int64), WATERMARK_ID_STEP * s)   # roll(c, k)[m] = c[(m - k) mod P]
+    return C
+
+
+def _device_tag_carriers(key, device):
+    """int16 [4, WATERMARK_PERIOD] on `device`: the key's carrier, then its sub-keys' 0 .. 2; the last TAP_TABLE_CACHE keys are kept, so a
+    key seen before costs neither the sub-key arithmetic nor an upload."""
+    key = (_check_key(key), str(device))
+    hit = _lru_get(_tag_carriers_on_device, key)
+    if hit is None:
+        rows = np.stack([watermark_carrier(k) for k in [key[0]] + watermark_subkeys(key[0])])
+        hit = _lru_put(_tag_carriers_on_device, key, torch.from_numpy(rows).to(device))
+    return hit
+
+
 def mark_pcm16(pcm, key) -> np.ndarray:
-    """24 kHz int16 PCM [n] with the key's mark added, by the definition above: integers only, the length kept, silence left silent.
-    `key=None` returns the array itself.  What `ops.wave_mark` equals byte for byte."""
+    """24 kHz int16 PCM [n] with the key's mark added, by the definitions above: integers only, the length kept, silence left silent.
+    `key`: a key, or a `WatermarkTag` (or its dict) whose trace id the mark carries too; None returns the array itself.  What
+    `ops.wave_mark` equals byte for byte."""
     pcm, key = _as_pcm16(pcm), check_watermark(key)
     if key is None or not len(pcm):
         return pcm
@@ -1054,8 +1160,8 @@ def mark_pcm16(pcm, key) -> np.ndarray:
     Ap = np.concatenate([[0], A, [0]])
     E = np.maximum(np.maximum(Ap[:-2], Ap[1:-1]), Ap[2:])
     j = np.arange(n)
-    c = watermark_carrier(key).astype(np.int64)
-    return np.clip(x + ((E[j // B] * c[j % WATERMARK_PERIOD]) >> WATERMARK_SHIFT), -32768, 32767).astype(np.int16)
+    C = watermark_tag_carrier(key)              # a key alone: (E 2 c) >> 24 == (E c) >> 23
+    return np.clip(x + ((E[j // B] * C[j % WATERMARK_PERIOD]) >> WATERMARK_ID_SHIFT), -32768, 32767).astype(np.int16)
 
 
 def _watermark_samples(wave) -> np.ndarray:
@@ -1115,6 +1221,40 @@ def detect_watermark(wave, keys) -> list:
         return [WatermarkScore(k, 0.0, 0, False) for k in keys]
     FZ = np.conj(np.fft.rfft(watermark_fold(x)))
     return [watermark_score(np.fft.irfft(FZ * np.fft.rfft(watermark_carrier(k).astype(np.float64)), n=WATERMARK_PERIOD), k) for k in keys]
+
+
+def watermark_symbol(r, offset):
+    """(s_d, z_d) of a sub-key from its correlation r [WATERMARK_PERIOD] and the key's offset o*."""
+    grid = (offset - WATERMARK_ID_STEP * np.arange(_ID_SYMBOL_COUNT)) % WATERMARK_PERIOD
+    s = int(np.argmax(r[grid]))                 # the smallest argmax
+    sigma = float(np.std(r))
+    return s, (float(r[grid[s]]) - float(np.mean(r))) / sigma if sigma > 0 else 0.0
+
+
+def watermark_read(score, symbols) -> WatermarkRead:
+    """The `WatermarkRead` of a key from its `WatermarkScore` and its three (s_d, z_d): the id only when the key is detected and every
+    z_d >= WATERMARK_ID_THRESHOLD."""
+    id_z = min(z for _, z in symbols)
+    found = score.detected and all(z >= WATERMARK_ID_THRESHOLD for _, z in symbols)
+    value = sum(int(s) << (_ID_SYMBOL_BITS * d) for d, (s, _) in enumerate(symbols)) if found else None
+    return WatermarkRead(score.key, score.z, score.offset, score.detected, value, float(id_z))
+
+
+def read_watermark(wave, keys) -> list:
+    """One `WatermarkRead(key, z, offset, detected, id, id_z)` per key for a mono 24 kHz clip: `detect_watermark`'s score of the key, and
+    the trace id its mark carries (None when the key is not detected or a symbol stays below WATERMARK_ID_THRESHOLD) with the smallest
+    symbol score, by the definition above.  A clip below WATERMARK_MIN_SAMPLES reads z = 0, id None, id_z = 0."""
+    keys = check_watermark_keys(keys)
+    x = _watermark_samples(wave)
+    if len(x) < WATERMARK_MIN_SAMPLES:
+        return [WatermarkRead(k, 0.0, 0, False, None, 0.0) for k in keys]
+    FZ = np.conj(np.fft.rfft(watermark_fold(x)))
+    corr = lambda k: np.fft.irfft(FZ * np.fft.rfft(watermark_carrier(k).astype(np.float64)), n=WATERMARK_PERIOD)
+    out = []
+    for k in keys:
+        score = watermark_score(corr(k), k)
+        out.append(watermark_read(score, [watermark_symbol(corr(sub), score.offset) for sub in watermark_subkeys(k)]))
+    return out
 
 
 _G711_TAGS = {"mulaw": 7, "alaw": 6}   # WAVE_FORMAT_MULAW, WAVE_FORMAT_ALAW
