@@ -896,6 +896,43 @@ int f5hip_watermark_read_ids(int32_t n, const float* wave_dev, const int64_t* of
 /* Kernels one f5hip_watermark_read_ids call launches (4). */
 int f5hip_watermark_read_ids_launches(void);
 
+/* Provenance watermark, the scan of ONE long or spliced recording: f5hip_watermark_detect's (with_ids = 0) or f5hip_watermark_read_ids'
+ * (with_ids = 1) row for any number of ranges of the recording -- the device half of wave_codec.scan_watermark, where the definition is
+ * written down.  Not in the reference.  The recording's n_samples samples are S = ceil(n_samples / 16384) segments of 16384, the last one
+ * zero-filled; range i is segments first_segment[i] .. first_segment[i] + n_segments[i] - 1.  u = the whitened band of the WHOLE recording
+ * (f5hip_watermark_detect's framing: 768 zeros in front, frames of 1024 at hop 256); a range's row is Z[m] = sum over its segments s,
+ * ascending, of u[16384 s + m] -- the fold of those samples by their absolute index, so a reported offset refers to sample 0 of the
+ * recording --, then correlated and scored as a clip's Z is.  A range that holds fewer than 12 000 of the recording's samples
+ * (min(n_samples, (first + count) 16384) - first 16384) gets zeros.
+ *   wave_dev                  fp32 [n_samples], mono 24 kHz, 4-byte aligned, read only; n_samples 1 .. 14 400 000 (600 s)
+ *   first_segment, n_segments host int32 [n_ranges], n_ranges 1 .. 4096: 0 <= first, 1 <= count, first + count <= S; ranges may overlap,
+ *                             repeat and come in any order
+ *   with_ids = 0              carriers_dev int16 [n_keys][16384], n_keys 1 .. 16; rows_dev fp32 [n_ranges][n_keys][4]: f5hip_watermark_detect's row
+ *   with_ids = 1              carriers_dev int16 [n_keys][4][16384] (f5hip_wave_mark_ids' layout), n_keys 1 .. 4; rows_dev fp32
+ *                             [n_ranges][n_keys][10]: f5hip_watermark_read_ids' row, its first four words the with_ids = 0 row bit for bit
+ * Launches: wd_frame_kernel once over the ceil((n_samples + 768) / 256) frames of the recording; ws_range_fold_kernel once, one thread per
+ * (range, residue): the range's segments ascending, each sample's four frames ascending, as f5hip_watermark_detect folds a clip (a range of
+ * all S segments of a recording of at most 1 440 000 samples gives that call's row bit for bit); then the detector's correlate kernel and
+ * wd_score_kernel / watermark_id_score_kernel once per SLAB of ranges.  With R = n_keys (4 n_keys with ids) carrier rows a slab is
+ * floor(4096 / R) ranges, taken in the call's order, so a call launches 2 + 2 ceil(n_ranges / floor(4096 / R)) kernels -- a function of
+ * (n_ranges, n_keys, with_ids) alone, FOUR whenever n_ranges R <= 4096 (f5hip_watermark_scan_launches; f5hip_watermark_scan_slabs gives the
+ * slab count): every window of 600 s against four keys is one slab, against sixteen keys four.  Every sum runs in an order fixed by the range
+ * alone, so a range's rows are bit-identical alone, with any other ranges, in any order of ranges and whichever slab they fall in.
+ * Workspace (the detector's buffers, grown and kept): frames 4 KiB per frame (230 MB at 600 s), Z 64 KiB per range (at most 256 MiB), r 64 KiB
+ * per (range of a slab, carrier row) and never more than 4096 rows (256 MiB): below 0.8 GiB at every admitted size, by construction.
+ * Counters watermark_scan_launches, watermark_scan_ranges.  The input is never written.
+ * Refused before the first launch: n_samples outside 1 .. 14 400 000; n_ranges outside 1 .. 4096; a range that is empty or not inside the
+ * S segments; with_ids other than 0 and 1; n_keys outside 1 .. 16 (1 .. 4 with ids); a null pointer; carriers not 16-byte aligned, samples
+ * or rows not 4-byte aligned. */
+int f5hip_watermark_scan(const float* wave_dev, int64_t n_samples, int32_t n_ranges, const int32_t* first_segment, const int32_t* n_segments,
+                         int32_t n_keys, int32_t with_ids, const int16_t* carriers_dev, float* rows_dev, void* stream);
+
+/* Kernels an f5hip_watermark_scan call of one slab launches (4); a call of s slabs launches 2 + 2 s. */
+int f5hip_watermark_scan_launches(void);
+
+/* Slabs of an f5hip_watermark_scan call: ceil(n_ranges / floor(4096 / R)), R = n_keys or 4 n_keys with ids; -1 for a bad argument. */
+int f5hip_watermark_scan_slabs(int32_t n_ranges, int32_t n_keys, int32_t with_ids);
+
 /* Reference-clip report: is an uploaded clip fit to clone from?  The measures of audio_prep.assess_reference (the definition, written down
  * above it) for n clips in one call, on the two buffers a front-end call holds.  Not in the reference.
  *   raw_dev                   fp32, read only: the packed raw clips as f5hip_ref_frontend is handed them; clip i is channels[i] channels of

@@ -141,6 +141,9 @@ SYMBOLS = {
     "f5hip_wave_mark_ids": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "f5hip_watermark_read_ids": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_watermark_read_ids_launches": (C.c_int, []),
+    "f5hip_watermark_scan": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "f5hip_watermark_scan_launches": (C.c_int, []),
+    "f5hip_watermark_scan_slabs": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "f5hip_ref_assess": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_ref_assess_launches": (C.c_int, []),
 }

@@ -555,7 +555,7 @@ static GemmArgs gemm_base(const Plane2& A, int lda, const PackedW& W, int M) {
 // precompute_time that built the tables (the others found the handle's tables built for the same time points); wave_mark_id_launches /
 // wave_mark_id_requests: kernels f5hip_wave_mark_ids launched in calls where a request carried a trace id and the requests such calls marked
 // (a call without an id counts on wave_mark_*); watermark_read_ids_launches / watermark_read_ids_clips: kernels f5hip_watermark_read_ids
-// launched and the clips it read
+// launched and the clips it read; watermark_scan_launches / watermark_scan_ranges: kernels f5hip_watermark_scan launched and the ranges it scored
 enum { CNT_GEMM5_RB11, CNT_GEMM5_RB8, CNT_GEMM5_WIDE, CNT_GEMM3_WIDE, CNT_CONV5, CNT_GEMM6, CNT_GEMM6_R176, CNT_GEMM6_R256, CNT_GEMM5_CB12,
        CNT_GEMM3, CNT_GEMM_REG_BN64, CNT_GEMM_REG_BN128, CNT_DIT_ROWS, CNT_REF_LAUNCHES, CNT_REF_TAPS_LDS, CNT_REF_TAPS_L2, CNT_WAVE_LAUNCHES,
        CNT_WAVE_REQUESTS, CNT_WAVE_ENCODE_LAUNCHES, CNT_WAVE_ENCODE_REQUESTS, CNT_MEL_RAGGED_LAUNCHES, CNT_MEL_RAGGED_ITEMS, CNT_WAVE_FLAC_LAUNCHES,
@@ -564,7 +564,8 @@ enum { CNT_GEMM5_RB11, CNT_GEMM5_RB8, CNT_GEMM5_WIDE, CNT_GEMM3_WIDE, CNT_CONV5,
        CNT_REF_DENOISE_LAUNCHES, CNT_REF_DENOISE_CLIPS, CNT_WAVE_MARK_LAUNCHES, CNT_WAVE_MARK_REQUESTS, CNT_WAVE_FORMANT_LAUNCHES,
        CNT_WAVE_FORMANT_REQUESTS, CNT_WATERMARK_DETECT_LAUNCHES,
        CNT_WATERMARK_DETECT_CLIPS, CNT_REF_ASSESS_LAUNCHES, CNT_REF_ASSESS_CLIPS, CNT_GEMM3_THIN, CNT_TIME_TABLE_BUILDS,
-       CNT_WAVE_MARK_ID_LAUNCHES, CNT_WAVE_MARK_ID_REQUESTS, CNT_WATERMARK_READ_IDS_LAUNCHES, CNT_WATERMARK_READ_IDS_CLIPS, CNT_COUNT };
+       CNT_WAVE_MARK_ID_LAUNCHES, CNT_WAVE_MARK_ID_REQUESTS, CNT_WATERMARK_READ_IDS_LAUNCHES, CNT_WATERMARK_READ_IDS_CLIPS,
+       CNT_WATERMARK_SCAN_LAUNCHES, CNT_WATERMARK_SCAN_RANGES, CNT_COUNT };
 static long long g_counters[CNT_COUNT] = {};
 
 // Kernel choice per GEMM (measured: profiles/r02_fillrate_microbench.txt, profiles/r01_gemm_microbench.txt):
@@ -687,7 +688,7 @@ extern "C" int f5hip_get_counter(const char* name, int64_t* value) {
                                            "watermark_detect_launches", "watermark_detect_clips",
                                            "ref_assess_launches", "ref_assess_clips", "gemm3_thin", "time_table_builds",
                                            "wave_mark_id_launches", "wave_mark_id_requests", "watermark_read_ids_launches",
-                                           "watermark_read_ids_clips"};
+                                           "watermark_read_ids_clips", "watermark_scan_launches", "watermark_scan_ranges"};
     static const char* attn_names[F5_ATTN_CNT_COUNT] = {"attn_bal8", "attn_nw8_deep", "attn_nw8", "attn_nw6_deep", "attn_nw6", "attn_nw4", "attn_seg2"};
     long long* attn = f5_attn_counters();
     if (!name) return fail(-1, "get_counter: null name");

@@ -29,6 +29,7 @@
 //   torch.ops.f5hip.watermark_detect(wave, offset, n_samples, carriers) -> Tensor scores fp32 [n, n_keys, 4]: z, offset, r at the offset, the deviation
 //   torch.ops.f5hip.wave_mark_ids(pcm, in_off, max_len, len_dev?, key_index, id, carriers?) -> ()   wave_mark whose marks also carry each request's trace id
 //   torch.ops.f5hip.watermark_read_ids(wave, offset, n_samples, carriers) -> Tensor rows fp32 [n, n_keys, 10]: watermark_detect's four, then (s_d, z_d) x 3
+//   torch.ops.f5hip.watermark_scan(wave, first_segment, n_segments, carriers) -> Tensor rows fp32 [n_ranges, n_keys, 4 or 10]: segment ranges of ONE recording
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -798,6 +799,33 @@ at::Tensor watermark_read_ids(const at::Tensor& wave, const at::Tensor& offset, 
     return watermark_rows("watermark_read_ids", wave, offset, n_samples, carriers, true);
 }
 
+// wave: ONE recording, a contiguous 1-D fp32 device tensor (mono, 24 kHz, 1 .. 14 400 000 samples), read only; first_segment, n_segments [n_ranges]
+// int32 host: range i is that many segments of 16384 samples from that segment; carriers int16 device [n_keys, 16384] (1 .. 16 keys) ->
+// rows fp32 device [n_ranges, n_keys, 4], watermark_detect's row per range, or [n_keys, 4, 16384] (1 .. 4 keys) -> [n_ranges, n_keys, 10],
+// watermark_read_ids' (include/f5hip.h f5hip_watermark_scan)
+at::Tensor watermark_scan(const at::Tensor& wave, const at::Tensor& first_segment, const at::Tensor& n_segments, const at::Tensor& carriers) {
+    check_host(first_segment, at::kInt, "first_segment"); check_host(n_segments, at::kInt, "n_segments");
+    check_dev_f32(wave, "wave");
+    const int64_t n = n_segments.numel();
+    TORCH_CHECK(n_segments.dim() == 1 && n >= 1 && n <= kWsRangesMax && first_segment.numel() == n,
+                "f5hip::watermark_scan: first_segment and n_segments need one value per range, 1 .. ", kWsRangesMax, " ranges");
+    TORCH_CHECK(wave.dim() == 1 && wave.numel() >= 1 && wave.numel() <= kWsMaxSamples,
+                "f5hip::watermark_scan: wave must be a contiguous 1-D fp32 tensor of 1 .. ", kWsMaxSamples, " samples on a HIP device (got ", wave.numel(), ")");
+    const bool ids = carriers.dim() == 3;
+    const int16_t* cp = check_carriers("watermark_scan", carriers, wave.device(), ids, ids ? kWdIdKeysMax : kWmKeysMax);
+    const int32_t* first = first_segment.data_ptr<int32_t>();
+    const int32_t* count = n_segments.data_ptr<int32_t>();
+    for (int64_t i = 0; i < n; i++)
+        TORCH_CHECK(ws_range_ok(wave.numel(), first[i], count[i]), "f5hip::watermark_scan: range ", i, " is ", count[i], " segments from segment ", first[i],
+                    " of a recording of ", ws_segments(wave.numel()));
+    const c10::DeviceGuard guard(wave.device());
+    at::Tensor rows = at::empty({n, carriers.size(0), ids ? kWdIdRowWords : 4}, wave.options());
+    const int rc = f5hip_watermark_scan(wave.data_ptr<float>(), wave.numel(), (int32_t)n, first, count, (int32_t)carriers.size(0), ids ? 1 : 0, cp,
+                                        rows.data_ptr<float>(), stream_of(wave));
+    TORCH_CHECK(rc == 0, "f5hip_watermark_scan: ", f5hip_last_error());
+    return rows;
+}
+
 // raw: the contiguous 1-D fp32 device tensor that holds the raw clips (what f5hip_ref_frontend is handed), read only; raw_offset [n] int64,
 // channels [n] int32, raw_len [n] int32 host: clip i is channels[i] x raw_len[i] samples at raw[raw_offset[i]]; wave, offset, n_samples as
 // ref_denoise's (read only) -> rows int64 device [n, 10] (include/f5hip.h f5hip_ref_assess)
@@ -859,5 +887,6 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("watermark_detect(Tensor wave, Tensor offset, Tensor n_samples, Tensor carriers) -> Tensor", &watermark_detect);
     m.def("wave_mark_ids(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor key_index, Tensor id, Tensor? carriers) -> ()", &wave_mark_ids);
     m.def("watermark_read_ids(Tensor wave, Tensor offset, Tensor n_samples, Tensor carriers) -> Tensor", &watermark_read_ids);
+    m.def("watermark_scan(Tensor wave, Tensor first_segment, Tensor n_segments, Tensor carriers) -> Tensor", &watermark_scan);
     m.def("ref_assess(Tensor raw, Tensor raw_offset, Tensor channels, Tensor raw_len, Tensor wave, Tensor offset, Tensor n_samples) -> Tensor", &ref_assess);
 }

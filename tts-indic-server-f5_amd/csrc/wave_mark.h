@@ -25,6 +25,14 @@
 //                         as wd_score_kernel scores it (wd_moments, wd_grid_max: the same trees), then per sub-key row its moments and the
 //                         maximum over the 1024 offsets o* - 16 s (ties to the smaller s) -> (z, offset, r[o*], sigma, s_0, z_0, .., s_2, z_2)
 // FOUR launches whatever n.  Every sum runs in an order fixed by the clip alone, so a clip's row is bit-identical alone and in a batch.
+//
+//   ws_range_fold_kernel  f5hip_watermark_scan's second launch (wave_codec.scan_watermark: ONE recording of up to 600 s, any number of ranges of
+//                         whole segments of P samples): wd_fold_kernel over a range -- one thread per (range, residue m), the range's segments
+//                         ascending, each sample's four frames ascending -- on the frames wd_frame_kernel wrote for the whole recording, so
+//                         Z[m] folds the samples by their absolute index
+// wd_frame_kernel and ws_range_fold_kernel once, then wd_corr_kernel and wd_score_kernel / watermark_id_score_kernel as they stand once per slab
+// of ws_slab_ranges(carrier rows) ranges: 2 + 2 slabs launches, FOUR for a call of one slab.  A range's row is bit-identical alone, with any
+// other ranges, in any order and in any slab.
 #pragma once
 #include "ragged_util.h"
 #include "ref_denoise_core.h"
@@ -507,3 +515,103 @@ int f5hip_watermark_read_ids(int32_t n, const float* wave_dev, const int64_t* of
 }
 
 int f5hip_watermark_read_ids_launches(void) { return 4; }
+
+// ------------------------------------------------------------------------------------------------ the scan of one long recording
+static_assert(kWsNfft == kRdNfft && kWsHop == kRdHop && kWsPad == kRdPad && kWsFramesPerSample == kRdFramesPerSample,
+              "watermark_scan: the ranges fold the frames wd_frame_kernel writes");
+static_assert(kWsMaxSamples % kRdHop == 0 && (long long)(kWsMaxSamples / kRdHop + 3) * kRdNfft < (1LL << 31), "watermark_scan: a frame index fits an int");
+
+// wd_fold_kernel for ranges of whole segments of ONE recording: one thread per (range, residue m).  ranges[i].off is the range's first
+// sample (a multiple of P) and ranges[i].n its samples (ws_range_samples: nothing at or past the recording's end is read).  For the range's
+// segments ascending, u[j] = its four frames added in ascending frame order, Z[m] = their sum in that order: the order is the range's alone,
+// so its row does not depend on the other ranges of the call
+__global__ __launch_bounds__(256) void ws_range_fold_kernel(const RdClip* __restrict__ ranges, const float* __restrict__ fw, float* __restrict__ Z) {
+    const RdClip c = ranges[blockIdx.y];
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    const long long end = c.off + c.n;
+    float acc = 0.0f;
+    for (int k = 0;; k++) {
+        const long long j = ws_fold_sample(c.off, m, k);
+        if (j >= end) break;
+        const int f0 = ws_sample_frame0(j);
+        float u = 0.0f;
+#pragma unroll
+        for (int d = 0; d < kWsFramesPerSample; d++) u += fw[(size_t)(f0 + d) * kWsNfft + ws_sample_offset(j, f0 + d)];
+        acc += u;
+    }
+    Z[(size_t)blockIdx.y * kWmPeriod + m] = acc;
+}
+
+struct WsWorkspace {
+    RdClip* table = nullptr; size_t cap_table = 0;                       // entry 0: the recording (wd_frame_kernel's clip), then the ranges
+    HostStage stage;
+};
+
+// Launches: wd_frame_kernel and ws_range_fold_kernel once, then wd_corr_kernel and the score kernel once per slab of ws_slab_ranges(rows)
+// ranges: 2 + 2 ws_slabs(n_ranges, rows), a function of (n_ranges, n_keys, with_ids) alone; a call of one slab launches four.
+int f5hip_watermark_scan(const float* wave_dev, int64_t n_samples, int32_t n_ranges, const int32_t* first_segment, const int32_t* n_segments,
+                         int32_t n_keys, int32_t with_ids, const int16_t* carriers_dev, float* rows_dev, void* stream) {
+    const char* op = "watermark_scan";
+    if (with_ids != 0 && with_ids != 1) return fail(-1, "%s: with_ids is 0 or 1 (got %d)", op, with_ids);
+    const int keys_max = with_ids ? kWdIdKeysMax : kWmKeysMax;
+    if (n_keys < 1 || n_keys > keys_max) return fail(-1, "%s: 1 .. %d keys in a call%s (got %d)", op, keys_max, with_ids ? " with ids" : "", n_keys);
+    if (n_samples < 1 || n_samples > kWsMaxSamples) return fail(-1, "%s: the recording has %lld samples (1 .. %d)", op, (long long)n_samples, kWsMaxSamples);
+    if (n_ranges < 1 || n_ranges > kWsRangesMax) return fail(-1, "%s: 1 .. %d ranges in a call (got %d)", op, kWsRangesMax, n_ranges);
+    if (!wave_dev || !first_segment || !n_segments || !carriers_dev || !rows_dev) return fail(-1, "%s: bad argument", op);
+    if ((reinterpret_cast<uintptr_t>(wave_dev) & 3) || (reinterpret_cast<uintptr_t>(carriers_dev) & 15) || (reinterpret_cast<uintptr_t>(rows_dev) & 3))
+        return fail(-1, "%s: the carriers must be 16-byte aligned, the samples and the rows 4-byte", op);
+    const int S = ws_segments(n_samples), F = ws_frames(n_samples);
+    std::vector<RdClip> h((size_t)n_ranges + 1, RdClip());
+    h[0].n = (int)n_samples; h[0].F = F;
+    for (int i = 0; i < n_ranges; i++) {
+        if (!ws_range_ok(n_samples, first_segment[i], n_segments[i]))
+            return fail(-1, "%s: range %d is %d segments from segment %d of a recording of %d", op, i, n_segments[i], first_segment[i], S);
+        h[(size_t)i + 1].off = ws_range_first(first_segment[i]);
+        h[(size_t)i + 1].n = ws_range_samples(n_samples, first_segment[i], n_segments[i]);
+    }
+    const int rows_per_key = with_ids ? kWmTagRows : 1, n_rows = n_keys * rows_per_key, words = with_ids ? kWdIdRowWords : 4;
+    const int per_slab = ws_slab_ranges(n_rows), slabs = ws_slabs(n_ranges, n_rows);
+    RdWorkspace* const tables = device_workspace<RdWorkspace>("watermark_detect");   // the window and the twiddles of the denoiser's FFT
+    WdWorkspace* const wdp = device_workspace<WdWorkspace>("watermark_detect");      // fw, Z and r are the detector's buffers
+    WsWorkspace* const wsp = device_workspace<WsWorkspace>("watermark_scan");
+    if (!tables || !wdp || !wsp) return -6;
+    WdWorkspace& wd = *wdp;
+    WsWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    CK(rd_tables(*tables));
+    CK(dev_reserve(&ws.table, &ws.cap_table, h.size(), "watermark_scan ranges"));
+    CK(dev_reserve(&wd.fw, &wd.cap_fw, (size_t)F * kRdNfft, "watermark_scan frames"));
+    CK(dev_reserve(&wd.Z, &wd.cap_Z, (size_t)n_ranges * kWmPeriod, "watermark_scan folds"));
+    CK(dev_reserve(&wd.r, &wd.cap_r, (size_t)(n_ranges < per_slab ? n_ranges : per_slab) * n_rows * kWmPeriod, "watermark_scan correlations"));
+    CK(ws.stage.upload(ws.table, h.data(), sizeof(RdClip) * h.size(), st));   // pinned staging, queued on `stream`: no wait
+    const RdClip* ranges = ws.table + 1;
+
+    hipLaunchKernelGGL(wd_frame_kernel, dim3((unsigned)F), dim3(256), 0, st, (const RdClip*)ws.table, 1, wave_dev, tables->window, tables->twiddle, wd.fw);
+    CKL("wd_frame");
+    hipLaunchKernelGGL(ws_range_fold_kernel, dim3(kWmPeriod / 256, (unsigned)n_ranges), dim3(256), 0, st, ranges, (const float*)wd.fw, wd.Z);
+    CKL("ws_range_fold");
+    for (int s = 0; s < slabs; s++) {
+        const int r0 = s * per_slab, nr = n_ranges - r0 < per_slab ? n_ranges - r0 : per_slab;
+        hipLaunchKernelGGL(wd_corr_kernel, dim3(kWmPeriod / kWdOffTile, (unsigned)n_rows, (unsigned)((nr + kWdGroup - 1) / kWdGroup)), dim3(256), 0, st, nr,
+                           n_rows, (const float*)wd.Z + (size_t)r0 * kWmPeriod, (const short*)carriers_dev, wd.r);
+        CKL("wd_corr");
+        float* out = rows_dev + (size_t)r0 * n_keys * words;
+        if (with_ids) {
+            hipLaunchKernelGGL(watermark_id_score_kernel, dim3((unsigned)(nr * n_keys)), dim3(256), 0, st, ranges + r0, n_keys, (const float*)wd.r, out);
+            CKL("watermark_id_score");
+        } else {
+            hipLaunchKernelGGL(wd_score_kernel, dim3((unsigned)(nr * n_keys)), dim3(256), 0, st, ranges + r0, n_keys, (const float*)wd.r, out);
+            CKL("wd_score");
+        }
+    }
+    g_counters[CNT_WATERMARK_SCAN_LAUNCHES] += 2 + 2 * slabs;
+    g_counters[CNT_WATERMARK_SCAN_RANGES] += n_ranges;
+    return 0;
+}
+
+int f5hip_watermark_scan_launches(void) { return 4; }
+
+int f5hip_watermark_scan_slabs(int32_t n_ranges, int32_t n_keys, int32_t with_ids) {
+    if (n_ranges < 1 || n_keys < 1 || n_keys > (with_ids ? kWdIdKeysMax : kWmKeysMax)) return fail(-1, "watermark_scan_slabs: bad argument");
+    return ws_slabs(n_ranges, n_keys * (with_ids ? kWmTagRows : 1));
+}

@@ -24,6 +24,19 @@
 //            one row, 16-byte aligned when the rows are; a request of key k reads rows 4 k .. 4 k + 3 of n_keys * 4
 //   sums     |C| <= 5 * 4336 = 21680; |E C| < 2^23 * 2^15 = 2^38; |E C >> 24| <= 21680 * 0.9375 / 2 = 10162.5, so |y - x| <= 10163
 //   grid     wd_id_offset is in [0, P) for o* in [0, P) and s in [0, 1024)
+//
+// The scan of one long recording (ws_range_fold_kernel / f5hip_watermark_scan; the definition is wave_codec.scan_watermark, written down
+// above it): the recording of n samples is S = ws_segments(n) segments of P samples, the last one zero-filled; a range is `count`
+// consecutive segments from segment `first`; its row is Z[m] = sum over its segments s ascending of u[s P + m], u the whitened band of the
+// whole recording, u[j] = its four frames added in ascending frame order (the detector's framing: 768 zeros in front, 1024 at hop 256).
+// Bounds:
+//   range    ws_range_ok admits 0 <= first, 1 <= count, first + count <= S, so ws_range_first < n and 1 <= ws_range_samples <= count P
+//   samples  residue m of a range reads u[j] for j = first P + m + k P < first P + ws_range_samples = min(n, (first + count) P): only j < n;
+//            a sample at or past n is the zero fill and is not read
+//   frames   sample j < n lies in frames ws_sample_frame0(j) .. + 3 at offsets ws_sample_offset in [0, 1024); the last of them is
+//            (n - 1) / 256 + 3 <= ws_frames(n) - 1, so every read stays inside fw [ws_frames(n)][1024]
+//   slabs    the correlate and score launches take ws_slab_ranges(n_rows) ranges at a time, a function of the carrier rows alone: r never
+//            holds more than kWsSlabRows rows of P floats (256 MiB)
 #pragma once
 #include <stdint.h>
 
@@ -103,6 +116,33 @@ WM_HD int wd_id_offset(int o, int s) { return (o - kWmIdStep * s) & (kWmPeriod -
 
 // whether (v, i) takes the place of (bv, bi) as the maximum of r: the larger value, at equal values the smaller offset
 WM_HD bool wd_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+// ---- the scan of one recording: ranges of whole segments
+constexpr int kWsWindow = 2;                          // WATERMARK_SCAN_WINDOW: segments per window
+constexpr int kWsSlack = 2;                           // WATERMARK_SCAN_SLACK
+constexpr int kWsMaxSamples = 14400000;               // WATERMARK_SCAN_MAX_SAMPLES: 600 s at 24 kHz
+constexpr int kWsRangesMax = 4096;                    // ranges of one call: Z [ranges][P] stays within 256 MiB
+constexpr int kWsSlabRows = 4096;                     // rows of r [P] one correlate launch writes: 256 MiB
+constexpr int kWsNfft = 1024, kWsHop = 256, kWsPad = 768;   // the detector's framing (ref_denoise_core.h kRdNfft, kRdHop, kRdPad)
+constexpr int kWsFramesPerSample = kWsNfft / kWsHop;
+
+WM_HD int ws_segments(long long n) { return (int)((n + kWmPeriod - 1) / kWmPeriod); }
+WM_HD int ws_frames(long long n) { return (int)((n + kWsPad + kWsHop - 1) / kWsHop); }
+WM_HD bool ws_range_ok(long long n, long long first, long long count) { return first >= 0 && count >= 1 && first + count <= ws_segments(n); }
+// the first sample of a range, and how many of the recording's n samples it holds (the rest of its last segment is the zero fill)
+WM_HD long long ws_range_first(int first) { return (long long)first * kWmPeriod; }
+WM_HD int ws_range_samples(long long n, int first, int count) {
+    const long long end = (long long)(first + count) * kWmPeriod;
+    return (int)((end < n ? end : n) - ws_range_first(first));
+}
+// the sample that segment k of a range starting at sample j0 adds to residue m (at or past j0 + the range's samples: the zero fill)
+WM_HD long long ws_fold_sample(long long j0, int m, int k) { return j0 + m + (long long)k * kWmPeriod; }
+// the first of the four frames that hold sample j, and j's position in frame f
+WM_HD int ws_sample_frame0(long long j) { return (int)(j / kWsHop); }
+WM_HD int ws_sample_offset(long long j, int f) { return (int)(j + kWsPad - (long long)f * kWsHop); }
+// ranges per correlate / score launch of a call with n_rows carrier rows (1 .. 16), and the slabs of a call
+WM_HD int ws_slab_ranges(int n_rows) { return kWsSlabRows / n_rows; }
+WM_HD int ws_slabs(int n_ranges, int n_rows) { return (n_ranges + ws_slab_ranges(n_rows) - 1) / ws_slab_ranges(n_rows); }
 
 // ---- host only: the carrier of a key
 inline unsigned long long wm_splitmix64(unsigned long long* state) {

@@ -49,6 +49,8 @@ from .wave_codec import (WATERMARK_BAND, WATERMARK_BLOCK, WATERMARK_KEYS_MAX, WA
                          WatermarkScore, check_watermark, check_watermark_keys, detect_watermark, mark_pcm16, watermark_carrier)
 from .wave_codec import (WATERMARK_ID_BITS, WATERMARK_ID_KEYS_MAX, WATERMARK_ID_MAX, WATERMARK_ID_THRESHOLD, WatermarkRead, WatermarkTag,  # noqa: F401
                          check_watermark_id, read_watermark, watermark_key, watermark_subkey)
+from .wave_codec import (WATERMARK_SCAN_MAX_SAMPLES, WATERMARK_SCAN_SLACK, WATERMARK_SCAN_WINDOW, WatermarkRange, WatermarkSpan,  # noqa: F401
+                         scan_watermark, watermark_spans, watermark_windows)
 from .wave_codec import (LOUDNESS_GATE_ABS, LOUDNESS_PEAK_CEILING, LOUDNESS_RANGE, LOUDNESS_TAPS, check_loudness, loudness_gain,  # noqa: F401
                          loudness_gain_constant, loudness_lufs, loudness_taps, measure_loudness, normalise_loudness_pcm16)
 from .wave_codec import _device_taps, _tap_tables  # noqa: F401  (the two caches: used below, and read as infer._X by the tests that bound them)

@@ -932,7 +932,7 @@ def watermark_tag_carriers(keys, device):
 
 def _check_carriers(op, carriers, device, tagged=False):
     from . import wave_codec
-    most = wave_codec.WATERMARK_ID_KEYS_MAX if op == "watermark_read_ids" else wave_codec.WATERMARK_KEYS_MAX
+    most = wave_codec.WATERMARK_ID_KEYS_MAX if op == "watermark_read_ids" or (op == "watermark_scan" and tagged) else wave_codec.WATERMARK_KEYS_MAX
     shape = (4, wave_codec.WATERMARK_PERIOD) if tagged else (wave_codec.WATERMARK_PERIOD,)
     if not (torch.is_tensor(carriers) and carriers.dtype == torch.int16 and carriers.is_cuda and carriers.is_contiguous() and tuple(carriers.shape[1:]) == shape
             and 1 <= carriers.shape[0] <= most and carriers.device == device):
@@ -1044,6 +1044,85 @@ def watermark_reads(rows, keys) -> list:
     for k, row in zip(keys, rows.tolist()):
         score = wave_codec.WatermarkScore(k, float(row[0]), int(row[1]), bool(row[0] >= wave_codec.WATERMARK_THRESHOLD))
         out.append(wave_codec.watermark_read(score, [(int(row[4 + 2 * d]), float(row[5 + 2 * d])) for d in range(wave_codec.WATERMARK_ID_SYMBOLS)]))
+    return out
+
+
+WATERMARK_SCAN_RANGES_MAX = 4096                  # ranges of one `watermark_scan_rows` call (csrc/wave_mark_core.h kWsRangesMax)
+
+
+def watermark_scan_launches(n_ranges=1, n_keys=1, ids=False):
+    """Launches of one `watermark_scan_rows` call: 2 + 2 slabs (include/f5hip.h f5hip_watermark_scan), four for a call of one slab."""
+    slabs = int(_lib.lib().f5hip_watermark_scan_slabs(int(n_ranges), int(n_keys), int(bool(ids))))
+    if slabs < 1:
+        raise _lib.F5HipError(f"watermark_scan_launches: {_lib.lib().f5hip_last_error().decode(errors='replace')}")
+    return int(_lib.lib().f5hip_watermark_scan_launches()) + 2 * (slabs - 1)
+
+
+def watermark_scan_rows(wave, ranges, carriers, ids=False):
+    """Segment ranges of ONE recording scored against several keys in one library call (include/f5hip.h f5hip_watermark_scan), the raw
+    call under `watermark_scan`.  wave: a contiguous 1-D fp32 device tensor, mono 24 kHz, 1 to `wave_codec.WATERMARK_SCAN_MAX_SAMPLES`
+    samples, read only; `ranges`: (first segment, segments) pairs, 1 to 4096 of them, each inside the recording's ceil(n / 16384) segments;
+    `carriers`: `watermark_carriers(keys, device)` (1 to 16 keys) -> rows fp32 device [n_ranges, n_keys, 4], `watermark_detect`'s row of the
+    range's fold; with `ids`, `watermark_tag_carriers(keys, device)` (1 to 4 keys) -> [n_ranges, n_keys, 10], `watermark_read_ids`' row.  A
+    range's rows equal its own single-range call's bit for bit."""
+    from . import wave_codec
+    op = "watermark_scan"
+    rg = np.asarray(ranges, dtype=np.int64)
+    if rg.ndim != 2 or rg.shape[1] != 2 or not 1 <= len(rg) <= WATERMARK_SCAN_RANGES_MAX:
+        raise _lib.F5HipError(f"{op}: ranges are 1 .. {WATERMARK_SCAN_RANGES_MAX} (first segment, segments) pairs (got shape {rg.shape})")
+    if not (torch.is_tensor(wave) and wave.dtype == torch.float32 and wave.is_contiguous() and wave.is_cuda and wave.dim() == 1
+            and 1 <= wave.numel() <= wave_codec.WATERMARK_SCAN_MAX_SAMPLES):
+        raise _lib.F5HipError(f"{op}: wave must be a contiguous 1-D fp32 tensor of 1 .. {wave_codec.WATERMARK_SCAN_MAX_SAMPLES} samples on the HIP device")
+    _check_carriers(op, carriers, wave.device, bool(ids))
+    S = -(-wave.numel() // wave_codec.WATERMARK_PERIOD)
+    for i, (first, count) in enumerate(rg.tolist()):
+        if first < 0 or count < 1 or first + count > S:
+            raise _lib.F5HipError(f"{op}: range {i} is {count} segments from segment {first} of a recording of {S}")
+    first = np.ascontiguousarray(rg[:, 0], dtype=np.int32)
+    count = np.ascontiguousarray(rg[:, 1], dtype=np.int32)
+    if torch_ops.load():
+        return call_op(op, wave, torch.from_numpy(first), torch.from_numpy(count), carriers)
+    with torch.cuda.device(wave.device):
+        rows = torch.empty(len(rg), carriers.shape[0], 10 if ids else 4, device=wave.device, dtype=torch.float32)
+        _lib.check(_lib.lib().f5hip_watermark_scan(_p(wave), wave.numel(), len(rg), _p(first), _p(count), carriers.shape[0], int(bool(ids)), _p(carriers),
+                                                   _p(rows), _lib.current_stream_ptr()), "f5hip_watermark_scan")
+    return rows
+
+
+def watermark_scan(wave, keys) -> list:
+    """`wave_codec.scan_watermark` of one recording on the device, fp32: the `wave_codec.WatermarkSpan`s of `keys` (1 to 16) in `wave`, a
+    contiguous 1-D fp32 device tensor (mono 24 kHz, finite, at most `wave_codec.WATERMARK_SCAN_MAX_SAMPLES` samples).  ONE
+    `watermark_scan_rows` call scores every window against every key; the rows come down and `wave_codec.watermark_spans` runs on the host;
+    then at most one more call per four keys reads the spans with their ids, decided by `watermark_reads`.  Below
+    `wave_codec.WATERMARK_MIN_SAMPLES` the answer is [] and no device call is made."""
+    from . import wave_codec
+    keys = wave_codec.check_watermark_keys(keys)
+    if not (torch.is_tensor(wave) and wave.dim() == 1):
+        raise _lib.F5HipError("watermark_scan: wave must be a contiguous 1-D fp32 tensor on the HIP device")
+    n = wave.numel()
+    if n > wave_codec.WATERMARK_SCAN_MAX_SAMPLES:
+        raise _lib.F5HipError(f"watermark_scan: the recording has {n} samples; at most {wave_codec.WATERMARK_SCAN_MAX_SAMPLES} (600 s at 24 kHz) are scanned")
+    if n < wave_codec.WATERMARK_MIN_SAMPLES:
+        return []
+    W, most = wave_codec.WATERMARK_SCAN_WINDOW, wave_codec.WATERMARK_ID_KEYS_MAX
+    S = -(-n // wave_codec.WATERMARK_PERIOD)
+    windows = [(w, min(w + W, S) - w) for w in range(wave_codec.watermark_windows(n))]
+    rows = watermark_scan_rows(wave, windows, watermark_carriers(keys, wave.device)).cpu().numpy()
+    found = wave_codec.watermark_spans([watermark_scores(rows[w], keys) for w in range(len(windows))], n)
+    reads = {}
+    for at in range(0, len(keys), most):                            # the spans of four keys at a time: one call with ids
+        group = keys[at:at + most]
+        mine = [i for i, g in enumerate(found) if g.key in group]
+        if not mine:
+            continue
+        got = watermark_scan_rows(wave, [(found[i].first, found[i].count) for i in mine], watermark_tag_carriers(group, wave.device), ids=True).cpu().numpy()
+        for j, i in enumerate(mine):
+            reads[i] = watermark_reads(got[j], group)[group.index(found[i].key)]
+    out = []
+    for i, g in enumerate(found):
+        read = reads[i]
+        if read.detected:                                           # (a span whose own fold stays below the threshold is dropped)
+            out.append(wave_codec.WatermarkSpan(g.key, g.start, g.end, read.z, read.offset, read.id, read.id_z))
     return out
 
 

@@ -1050,6 +1050,25 @@ class TTSManager:
             rows = torch.cat(rows, dim=1)[0].cpu().numpy()
         return ops.watermark_reads(rows, keys)
 
+    def scan_watermark(self, audio, keys=None) -> list:
+        """Where a long or spliced recording carries a mark, and whose: one `infer.WatermarkSpan(key, start, end, z, offset, id, id_z)` per
+        marked stretch and key, start and end in samples at 24 kHz, sorted by (start, the key's position) -- `infer.scan_watermark`, which
+        folds windows of two periods instead of the whole clip, so stretches cut together are told apart and nothing is cut at 60 s.
+        `audio` and `keys` as `detect_watermark`'s.  ValueError for a recording over 600 s (never truncated).  With `device_frontend` and a
+        model on a GPU the recording is scanned there under the device lock (`ops.watermark_scan`: one call over every window, then at most
+        one per four keys over the spans, fp32); otherwise on the host in fp64."""
+        import torch
+        keys, mono = self._watermark_clip("scan_watermark", audio, keys)
+        device = getattr(getattr(self.model_obj, "local", self.model_obj), "device", None)
+        if (not (self.device_frontend and device is not None and torch.device(device).type == "cuda") or len(mono) > infer.WATERMARK_SCAN_MAX_SAMPLES
+                or not np.isfinite(mono).all()):
+            return infer.scan_watermark(mono, keys)              # (too long, or a sample that is not finite: the host's ValueError)
+        if len(mono) < infer.WATERMARK_MIN_SAMPLES:
+            return []
+        from . import ops
+        with self._device_lock:
+            return ops.watermark_scan(torch.from_numpy(np.ascontiguousarray(mono)).to(device), keys)
+
     def check_reference(self, audio, clip_short=True):
         """The `infer.ReferenceReport` of a would-be reference clip -- WAV or FLAC bytes, or a (wave [ch, n], sr) pair -- taken through
         `decode_audio`, the silence pre-step and the front-end exactly as a clone upload is (`_clip_voice`; with `device_frontend` and a
@@ -1209,13 +1228,17 @@ def request_models():
         keys: typing.Any = None                      # 1 to 16 keys; absent: the manager's own.  Untyped, so that a bad key arrives as sent and is refused
         ids: typing.Any = None                       # true: also read the trace id each key's mark carries (TTSManager.read_watermark)
 
+    class ScanRequest(BaseModel):                    # `/v1/audio/watermark/scan`: a long or spliced recording (base64 WAV or FLAC) and the keys to look for
+        audio: str
+        keys: typing.Any = None                      # 1 to 16 keys; absent: the manager's own.  Untyped, as DetectRequest's
+
     class ReferenceCheckRequest(BaseModel):          # `/v1/audio/reference/check`: a would-be reference clip (base64 WAV or FLAC)
         audio: str
         clip_short: bool = True
 
     return types.SimpleNamespace(KannadaSynthesizeRequest=KannadaSynthesizeRequest, SynthesizeRequest=SynthesizeRequest, CloneRequest=CloneRequest,
                                  EditRequest=EditRequest, ScriptRequest=ScriptRequest, ScriptVoice=ScriptVoice, DetectRequest=DetectRequest,
-                                 ReferenceCheckRequest=ReferenceCheckRequest)
+                                 ReferenceCheckRequest=ReferenceCheckRequest, ScanRequest=ScanRequest)
 
 
 def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
@@ -1238,7 +1261,7 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     `"stream": true`: `STREAM_PROSODY`; not on the edit route, which keeps the recording's timing) and beside a non-zero `pitch` `keep_formants` (true: the
     pitch moves and the voice's formants stay, `infer.psola_pcm16`; 400 for anything but a bool and without a pitch), every route `watermark` (a key, 1 to 2^48 - 1: the finished wave
     carries that key's provenance mark, `infer.mark_pcm16`; a bad key is a 400, and so is the option together with `"stream": true`:
-    `STREAM_WATERMARK`; `{"key": K, "id": I}` in its place makes the mark carry a trace id from 0 to 2^30 - 1, `{"id": I}` alone with the manager's key; `/v1/audio/watermark/detect` scores a recording against keys and with `"ids": true` reads the ids back), and `response_format` ("wav", or "pcm" for the headerless samples / code bytes
+    `STREAM_WATERMARK`; `{"key": K, "id": I}` in its place makes the mark carry a trace id from 0 to 2^30 - 1, `{"id": I}` alone with the manager's key; `/v1/audio/watermark/detect` scores a recording against keys and with `"ids": true` reads the ids back; `/v1/audio/watermark/scan` finds the marked stretches of a long or spliced recording, each with its place and id), and `response_format` ("wav", or "pcm" for the headerless samples / code bytes
     as `audio/pcm`); streamed or not, the body's samples are the same bytes.  `encoding: "flac"` is its own container: the body is the
     native FLAC stream as `audio/flac` with a `.flac` file name, and `response_format` must be absent (400 with "wav" or "pcm" beside it);
     streamed, the stream header comes with the totals unknown."""
@@ -1431,6 +1454,28 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
             return {"results": [dict(key=s.key, detected=s.detected, score=s.z, offset=s.offset, id=s.id, id_score=s.id_z) for s in scores]}
         return {"results": [dict(key=s.key, detected=s.detected, score=s.z, offset=s.offset) for s in scores]}
 
+    def _run_scan(req):
+        """`/v1/audio/watermark/scan`: {"audio": base64 WAV or FLAC, "keys"?: [1 .. 16 keys]} -> {"seconds", "spans": [{"key", "start", "end",
+        "score", "offset", "id", "id_score"}]}: the marked stretches of a long or spliced recording (`TTSManager.scan_watermark`; no key in the
+        body: the manager's own), start and end in seconds of the recording at 24 kHz, "id" the stretch's trace id or null.  Needs no loaded
+        model.  400 for bad keys, no key anywhere, audio that cannot be read and a recording over 600 s."""
+        try:
+            raw = base64.b64decode(req.audio, validate=True)
+        except (binascii.Error, ValueError):
+            raise HTTPException(status_code=400, detail="Audio must be a base64-encoded WAV or FLAC file.")
+        try:
+            keys = None if req.keys is None else infer.check_watermark_keys(req.keys)   # (before the recording is decoded)
+            try:
+                wave, sr = tts_manager.decode_audio(raw)
+            except ValueError as e:
+                raise ValueError(f"Invalid audio: {e}") from e
+            spans = tts_manager.scan_watermark((wave, sr), keys)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        rate = float(infer.target_sample_rate)
+        return {"seconds": wave.shape[-1] / float(sr),
+                "spans": [dict(key=s.key, start=s.start / rate, end=s.end / rate, score=s.z, offset=s.offset, id=s.id, id_score=s.id_z) for s in spans]}
+
     def _run_check(req):
         """`/v1/audio/reference/check`: {"audio": base64 WAV or FLAC, "clip_short"?: true} -> {"report": {seconds, rms, peak, clipped, clip_ratio,
         noise_db, snr_db, speech_ratio, bandwidth_hz}, "problems": [...]}: the clip's measures (`TTSManager.check_reference`; an infinite
@@ -1474,6 +1519,10 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     @router.post("/audio/watermark/detect")
     async def detect_watermark(request: models.DetectRequest):            # provenance: does this recording carry a key's mark?
         return await run_in_threadpool(_run_detect, request)
+
+    @router.post("/audio/watermark/scan")
+    async def scan_watermark(request: models.ScanRequest):                # provenance: where in this recording are the marked stretches, and whose?
+        return await run_in_threadpool(_run_scan, request)
 
     @router.post("/audio/reference/check")
     async def check_reference(request: models.ReferenceCheckRequest):      # is this clip fit to clone from?

@@ -4,7 +4,7 @@ the extension is present and through ctypes otherwise -- the same C entry points
   - the samplers: cfm_sample, cfm_sample_units, cfm_sample_grids, cfm_sample_span and cfm_sample_methods (one ODE method per unit);
     `F5HipModel._call_sampler` is their one caller.
   - the vocoders: vocos_decode, vocos_decode_ragged, bigvgan_forward, bigvgan_forward_ragged (`vocoder.F5HipVocos`, `vocoder.F5HipBigVGAN`).
-  - the device audio path: ref_prestep, ref_frontend, ref_assess, watermark_detect, watermark_read_ids, ref_denoise, flac_decode, mel_spectrogram_ragged in front of the
+  - the device audio path: ref_prestep, ref_frontend, ref_assess, watermark_detect, watermark_read_ids, watermark_scan, ref_denoise, flac_decode, mel_spectrogram_ragged in front of the
     model; wave_finish, wave_finish_joins, wave_prosody, wave_prosody_formants, wave_mark, wave_mark_ids, wave_loudness, wave_encode, wave_flac and wave_flac_levels behind the
     vocoder (`ops`, `mel`);
     `ops.call_op` calls them, and the ragged vocoder operators, and turns an operator's c10::Error into F5HipError."""
