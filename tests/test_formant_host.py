@@ -281,8 +281,9 @@ def test_the_options_table_and_the_wave_spec():
     assert wave_codec.FORMANT_OPTIONS == infer.FORMANT_OPTIONS == ("keep_formants",)
     assert infer.REQUEST_OPTIONS.index("watermark") == 11 and infer.REQUEST_OPTIONS.index("keep_formants") == 12
     assert infer.REQUEST_OPTIONS[-2:] == infer.PROSODY_OPTIONS == ("tempo", "pitch") and len(infer.REQUEST_OPTIONS) == 15
-    assert [f.name for f in dataclasses.fields(infer.WaveSpec)] == list(wave_codec.DELIVERY_OPTIONS) + ["tempo", "pitch"]   # beside the spec, not in it
-    assert infer.WaveSpec.of(dict(pitch=2, keep_formants=True)) == infer.WaveSpec(pitch=2)
+    assert [f.name for f in dataclasses.fields(infer.WaveSpec)] == list(wave_codec.DELIVERY_OPTIONS) + ["tempo", "pitch", "watermark", "keep_formants"]   # the last field
+    assert infer.WaveSpec.of(dict(pitch=2, keep_formants=True)) == infer.WaveSpec(pitch=2, keep_formants=True) != infer.WaveSpec(pitch=2)
+    assert infer.WaveSpec.of(dict(pitch=2, keep_formants=False)) == infer.WaveSpec(pitch=2)
     assert "keep_formants" not in serve.EDIT_OPTIONS + serve.EDIT_DELIVERY + serve.EDIT_MARK
 
 
@@ -324,10 +325,10 @@ def test_finish_pcm16_is_the_composition_with_the_new_step():
             x = cut if spec.remove_silence else pause
             y = wave_codec.mark_pcm16(wave_codec.shift_pcm16(x, spec.tempo, spec.pitch, keep_formants=True), key)
             want = infer.deliver_pcm16(infer.normalise_loudness_pcm16(y, spec.loudness), *spec.format, flac_level=spec.flac_level if spec.flac else None)
-            got = infer.finish_pcm16(pause, spec, key, True)
+            got = infer.finish_pcm16(pause, dataclasses.replace(spec, watermark=key, keep_formants=True))
             assert got.dtype == want.dtype and np.array_equal(got, want), opts
-            today = infer.finish_pcm16(pause, spec, key)
-            assert np.array_equal(today, infer.finish_pcm16(pause, spec, key, False)) and not (len(today) == len(got) and np.array_equal(today, got))
+            today = infer.finish_pcm16(pause, dataclasses.replace(spec, watermark=key))
+            assert np.array_equal(today, infer.finish_pcm16(pause, dataclasses.replace(spec, watermark=key, keep_formants=False))) and not (len(today) == len(got) and np.array_equal(today, got))
 
 
 def test_finish_requests_takes_the_option_per_request():
@@ -362,8 +363,8 @@ def test_the_planner_carries_the_flag_beside_the_spec(tmp_path):
     plan = lambda text, opts: infer.plan_request((voice, "reference words", text, opts), DEFAULTS, target_rms=0.1, fix_duration=None, device=None,   # noqa: E731
                                                  tokenizer=infer.text_to_tokens)
     got = plan("some text.", dict(pitch=1, keep_formants=True))
-    assert got.spec == infer.WaveSpec(pitch=1) and got.keep_formants is True
-    assert plan("some text.", dict(pitch=1)).keep_formants is False and plan("some text.", {}).keep_formants is False
+    assert dataclasses.replace(got.spec, keep_formants=False) == infer.WaveSpec(pitch=1) and got.spec.keep_formants is True   # the flag leaves every other field alone
+    assert plan("some text.", dict(pitch=1)).spec.keep_formants is False and plan("some text.", {}).spec.keep_formants is False
     with pytest.raises(ValueError) as e:
         plan("text.", dict(keep_formants=True))
     assert str(e.value) == "keep_formants needs a non-zero pitch"
@@ -440,14 +441,14 @@ def test_script_route_and_method(script_client):
 
 
 def test_span_scheduler_carries_the_flag():
-    """`SpanScheduler.admit` plans the flag beside the spec and its tickets hand it to the finishing chain: with the same seed the kept
+    """`SpanScheduler.admit` plans the flag into the spec and its tickets hand it to the finishing chain: with the same seed the kept
     request is `shift_pcm16(..., keep_formants=True)` of the request without options, and the plain pitch is today's."""
     from test_spans import FakeModel, FakeVocoder, _request as span_request, _voice as span_voice
     voice = span_voice()
     sched = infer.SpanScheduler(FakeModel(), FakeVocoder(), span_steps=3, nfe_step=4)
     text = "A sentence for the scheduler."
     tickets = [sched.admit(span_request(voice, text, seed=3, **opts)) for opts in ({}, dict(pitch=3), dict(pitch=3, keep_formants=True), dict(tempo=0.9, pitch=-2, keep_formants=True))]
-    assert [t.keep_formants for t in tickets] == [False, False, True, True]
+    assert [t.spec.keep_formants for t in tickets] == [False, False, True, True]
     while sched.busy:
         sched.step()
     plain = infer.quantise_pcm16(tickets[0].result)

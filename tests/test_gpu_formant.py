@@ -6,6 +6,7 @@ between `ops.wave_finish` and `ops.wave_mark` / `ops.wave_loudness` / `ops.wave_
 
 Every comparison is equality of bytes and of lengths: there is no tolerance anywhere."""
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import pytest
@@ -241,7 +242,7 @@ def test_chain_behind_wave_finish_equals_the_host_pipeline():
     joined_pcm = infer.finish_requests(reqs, ["x"] * len(reqs), FADE_S, want="pcm16")
     specs = [infer.WaveSpec.of(dict(remove_silence=flag, tempo=o[0], pitch=o[1], loudness=t, sample_rate=8000, encoding="mulaw"))
              for flag, o, t in zip(flags, opts, targets)]
-    want = [infer.finish_pcm16(x, spec, key, o[2]) for x, spec, key, o in zip(joined_pcm, specs, keys, opts)]
+    want = [infer.finish_pcm16(x, dataclasses.replace(spec, watermark=key, keep_formants=o[2])) for x, spec, key, o in zip(joined_pcm, specs, keys, opts)]
     cut = infer.remove_silence_pcm(joined_pcm[0], RATE)
     assert len(cut) < len(joined_pcm[0]) and not np.array_equal(infer.shift_pcm16(cut, 1.0, 4, keep_formants=True), cut)   # (cut, and voiced)
     chunks = [torch.from_numpy(c).to(dev) for r in reqs for c in r]

@@ -4,6 +4,7 @@ through `infer.finish_requests` with the device back-end, and through `TTSManage
 
 Every comparison is equality of bytes: there is no tolerance anywhere."""
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import pytest
@@ -258,7 +259,7 @@ def test_finish_requests_makes_one_mark_call_and_no_copy_for_it():
     for i, key in enumerate(keys):
         assert np.array_equal(want[i], unmarked[i]) == (key is None), i
     spec = infer.WaveSpec.of(dict(loudness=-16.0, pitch=2))
-    assert np.array_equal(got[3], infer.finish_pcm16(infer.quantise_pcm16(reqs[3][0]), spec, K1))
+    assert np.array_equal(got[3], infer.finish_pcm16(infer.quantise_pcm16(reqs[3][0]), dataclasses.replace(spec, watermark=K1)))
     assert wave_codec.detect_watermark(got[3], [K1])[0].detected
 
 

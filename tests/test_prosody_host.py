@@ -235,7 +235,7 @@ def test_refusals_character_for_character():
 
 def test_wave_spec_fields_and_the_whole_wave_rule():
     names = [f.name for f in dataclasses.fields(infer.WaveSpec)]
-    assert names == list(wave_codec.DELIVERY_OPTIONS) + ["tempo", "pitch"]
+    assert names == list(wave_codec.DELIVERY_OPTIONS) + ["tempo", "pitch", "watermark", "keep_formants"]
     spec = infer.WaveSpec(True, -16.0, 8000, "mulaw", 0)                 # the five-argument positional form keeps its meaning
     assert (spec.tempo, spec.pitch, spec.prosody) == (1.0, 0, False) and spec == infer.WaveSpec.of(dict(remove_silence=True, loudness=-16.0, sample_rate=8000,
                                                                                                        encoding="mulaw"))

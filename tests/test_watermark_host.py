@@ -226,7 +226,7 @@ def test_robustness_through_the_delivery_chain():
     loud = infer.normalise_loudness_pcm16(y, -30.0)
     assert not np.array_equal(loud, y) and _z(loud).z >= 10
     spec = infer.WaveSpec.of(dict(tempo=1.25, sample_rate=8000, encoding="mulaw"))
-    sent = infer.finish_pcm16(x, spec, KEY)                                            # tempo in front of the mark, 8 kHz mu-law behind it
+    sent = infer.finish_pcm16(x, dataclasses.replace(spec, watermark=KEY))                                         # tempo in front of the mark, 8 kHz mu-law behind it
     assert sent.dtype == np.uint8 and abs(len(sent) - len(x) / 1.25 / 3) <= 2
     got = _z(_to_24k(infer.decode_g711(sent, "mulaw")))
     assert got.z >= 10 and got.detected
@@ -240,7 +240,7 @@ def test_request_options_layout():
     assert infer.REQUEST_OPTIONS[6:11] == ("remove_silence", "sample_rate", "encoding", "loudness", "flac_level")
     assert infer.DELIVERY_OPTIONS == ("remove_silence", "loudness", "sample_rate", "encoding", "flac_level") and infer.PROSODY_OPTIONS == ("tempo", "pitch")
     assert serve.EDIT_DELIVERY == ("sample_rate", "encoding", "loudness", "flac_level") and serve.EDIT_MARK == ("watermark",)
-    assert [f.name for f in dataclasses.fields(infer.WaveSpec)] == ["remove_silence", "loudness", "sample_rate", "encoding", "flac_level", "tempo", "pitch"]
+    assert [f.name for f in dataclasses.fields(infer.WaveSpec)] == ["remove_silence", "loudness", "sample_rate", "encoding", "flac_level", "tempo", "pitch", "watermark", "keep_formants"]
     models = serve.request_models()
     for name in ("KannadaSynthesizeRequest", "SynthesizeRequest", "CloneRequest", "ScriptRequest", "EditRequest"):
         assert "watermark" in getattr(models, name).model_fields, name
@@ -273,12 +273,12 @@ def test_finish_pcm16_marks_between_prosody_and_loudness():
         pcm = infer.remove_silence_pcm(pause, RATE) if spec.remove_silence else pause
         marked = wave_codec.mark_pcm16(wave_codec.shift_pcm16(pcm, spec.tempo, spec.pitch), 9)
         want = infer.deliver_pcm16(infer.normalise_loudness_pcm16(marked, spec.loudness), *spec.format, flac_level=spec.flac_level if spec.flac else None)
-        got = infer.finish_pcm16(pause, spec, 9)
+        got = infer.finish_pcm16(pause, dataclasses.replace(spec, watermark=9))
         assert got.dtype == want.dtype and np.array_equal(got, want), opts
-        assert np.array_equal(infer.finish_pcm16(pause, spec, None), infer.finish_pcm16(pause, spec))   # no key: as before
+        assert np.array_equal(infer.finish_pcm16(pause, dataclasses.replace(spec, watermark=None)), infer.finish_pcm16(pause, spec))   # no key: as before
     # the loudness target and the peak cap are measured on the marked samples
     spec = infer.WaveSpec.of(dict(loudness=-20.0))
-    assert not np.array_equal(infer.finish_pcm16(pause, spec, 9), wave_codec.mark_pcm16(infer.normalise_loudness_pcm16(pause, -20.0), 9))
+    assert not np.array_equal(infer.finish_pcm16(pause, dataclasses.replace(spec, watermark=9)), wave_codec.mark_pcm16(infer.normalise_loudness_pcm16(pause, -20.0), 9))
 
 
 def test_finish_requests_takes_the_key_per_request():
@@ -312,7 +312,8 @@ def test_planner_carries_the_key_and_refuses_chunk_texts_and_join_false(tmp_path
             plan(text, dict(watermark=5))
         assert str(e.value) == infer.WHOLE_WAVE_WATERMARK
     p = plan("some text.", dict(watermark=5))
-    assert p.watermark == 5 and p.spec == infer.WaveSpec() and plan("some text.", {}).watermark is None
+    assert p.spec.watermark == 5 and p.spec == infer.WaveSpec(watermark=5) and plan("some text.", {}).spec.watermark is None
+    assert dataclasses.replace(p.spec, watermark=None) == infer.WaveSpec() == plan("some text.", {}).spec   # the key leaves every other field at its default
     with pytest.raises(ValueError, match="watermark must be an integer key"):
         plan("text.", dict(watermark="5"))
     from test_serve import FakeModel, FakeVocoder
@@ -327,7 +328,7 @@ def test_span_scheduler_carries_the_key():
     text = "This is sentence one, quite long. And here is the second sentence, also long. A third one follows. " * 3
     _, sched = spans._scheduler(span_steps=2, nfe_step=4)
     plain, marked = sched.admit(spans._request(voice, text, seed=1)), sched.admit(spans._request(voice, text, seed=1, watermark=17))
-    assert plain.watermark is None and marked.watermark == 17
+    assert plain.spec.watermark is None and marked.spec.watermark == 17
     with pytest.raises(ValueError) as e:
         sched.admit(spans._request(voice, ["One.", "Two."], watermark=17))
     assert str(e.value) == infer.WHOLE_WAVE_WATERMARK

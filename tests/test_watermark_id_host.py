@@ -9,6 +9,7 @@ z >= 10 for the key of a tagged 1 s clip; definition against restatement: the sa
 direct sums).  The twelve ids are the first twelve draws of `numpy.random.default_rng(0)`; the smallest id_z of twelve clips moves by about
 +- 0.6 with the ids drawn (measured on the host over seven id streams: 3 s cut by 7001 samples 6.40 .. 8.01, 1 s clean 6.11 .. 6.95)."""
 import base64
+import dataclasses
 
 import numpy as np
 import pytest
@@ -271,15 +272,16 @@ def test_finish_requests_and_finish_pcm16_take_tags():
     x = ref.host(2 * RATE, 4)
     spec = infer.WaveSpec.of(dict(tempo=1.25, loudness=-20.0))
     want = infer.normalise_loudness_pcm16(wave_codec.mark_pcm16(wave_codec.shift_pcm16(x, spec.tempo, spec.pitch), WatermarkTag(9, 4)), -20.0)
-    assert np.array_equal(infer.finish_pcm16(x, spec, WatermarkTag(9, 4)), want)
+    assert np.array_equal(infer.finish_pcm16(x, dataclasses.replace(spec, watermark=WatermarkTag(9, 4))), want)
 
 
 def test_planner_carries_the_tag(tmp_path):
     voice = infer.PreparedVoice(_voice(tmp_path))
     plan = lambda text, opts: infer.plan_request((voice, "reference words", text, opts), DEFAULTS, target_rms=0.1, fix_duration=None, device=None,   # noqa: E731
                                                  tokenizer=infer.text_to_tokens)
-    assert plan("some text.", dict(watermark={"key": 5, "id": 8})).watermark == WatermarkTag(5, 8) == plan("some text.", dict(watermark=WatermarkTag(5, 8))).watermark
-    assert plan("some text.", dict(watermark=5)).watermark == 5
+    assert plan("some text.", dict(watermark={"key": 5, "id": 8})).spec.watermark == WatermarkTag(5, 8) == plan("some text.", dict(watermark=WatermarkTag(5, 8))).spec.watermark
+    assert plan("some text.", dict(watermark=5)).spec.watermark == 5
+    assert dataclasses.replace(plan("some text.", dict(watermark={"key": 5, "id": 8})).spec, watermark=None) == infer.WaveSpec()   # a tag leaves every other field at its default
     with pytest.raises(ValueError) as e:
         plan(["one chunk.", "another chunk."], dict(watermark={"key": 5, "id": 8}))
     assert str(e.value) == infer.WHOLE_WAVE_WATERMARK
@@ -297,7 +299,7 @@ def test_span_scheduler_carries_the_tag():
     text = "This is sentence one, quite long. And here is the second sentence, also long. A third one follows. " * 3
     _, sched = spans._scheduler(span_steps=2, nfe_step=4)
     plain, marked = sched.admit(spans._request(voice, text, seed=1)), sched.admit(spans._request(voice, text, seed=1, watermark={"key": 17, "id": 4}))
-    assert marked.watermark == WatermarkTag(17, 4)
+    assert marked.spec.watermark == WatermarkTag(17, 4)
     while sched.busy:
         sched.step()
     assert np.array_equal(marked.result, wave_codec.mark_pcm16(infer.quantise_pcm16(plain.result), WatermarkTag(17, 4)))

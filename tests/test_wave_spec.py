@@ -1,7 +1,8 @@
-"""`wave_codec.WaveSpec` (the five delivery options as one value), `infer.finish_pcm16` (the host definition of "finish this PCM") and
+"""`wave_codec.WaveSpec` (the five delivery options, the two prosody options, the watermark and `keep_formants` as one value), `infer.finish_pcm16` (the host definition of "finish this PCM") and
 `wave_codec.StreamDelivery` (the same, piece by piece) against the separate validators and functions they are made of (CPU).
 
 Every comparison is equality of values, messages and bytes."""
+import dataclasses
 import itertools
 
 import numpy as np
@@ -66,6 +67,33 @@ REFUSALS = [
     (dict(loudness=0, flac_level=1, encoding="mp3"), "loudness must be between -40 and -5 LUFS (got 0.0)."),
     (dict(flac_level=1, encoding="mp3"), "flac_level needs encoding 'flac' (got flac_level 1 with encoding 'mp3')"),
     (dict(flac_level=3, sample_rate=1), "flac_level must be one of [0, 1] (got 3)"),
+    # the other four of the nine (the strings of tests/test_prosody_host.py, test_watermark_host.py, test_watermark_id_host.py, test_formant_host.py)
+    (dict(tempo=True), "tempo must be a number from 0.5 to 2 in steps of 0.01 (got True)"),
+    (dict(tempo=2.01), "tempo must be a number from 0.5 to 2 in steps of 0.01 (got 2.01)"),
+    (dict(tempo="1.0"), "tempo must be a number from 0.5 to 2 in steps of 0.01 (got '1.0')"),
+    (dict(pitch=7), "pitch must be a whole number of semitones from -6 to 6 (got 7)"),
+    (dict(pitch=1.0), "pitch must be a whole number of semitones from -6 to 6 (got 1.0)"),
+    (dict(pitch=True), "pitch must be a whole number of semitones from -6 to 6 (got True)"),
+    (dict(tempo=0.5, pitch=3), "tempo 0.5 with pitch 3 stretches the wave by 88/37: outside 1/2 to 2"),
+    (dict(watermark=True), "watermark must be an integer key from 1 to 2^48 - 1 (got True)"),
+    (dict(watermark=1.5), "watermark must be an integer key from 1 to 2^48 - 1 (got 1.5)"),
+    (dict(watermark="7"), "watermark must be an integer key from 1 to 2^48 - 1 (got '7')"),
+    (dict(watermark=0), "watermark must be an integer key from 1 to 2^48 - 1 (got 0)"),
+    (dict(watermark=2 ** 48), f"watermark must be an integer key from 1 to 2^48 - 1 (got {2 ** 48})"),
+    (dict(watermark={"key": 0, "id": 1}), "watermark must be an integer key from 1 to 2^48 - 1 (got 0)"),
+    (dict(watermark={"key": 7, "id": 2 ** 30}), f"watermark id must be an integer from 0 to 2^30 - 1 (got {2 ** 30})"),
+    (dict(watermark={"key": 7, "id": True}), "watermark id must be an integer from 0 to 2^30 - 1 (got True)"),
+    (dict(watermark={"key": 7, "id": 1, "tenant": 3}), "watermark has an unknown entry 'tenant': a key with a trace id is {\"key\": K, \"id\": I}"),
+    (dict(watermark={"id": 3}), "watermark names an id without a key, and the service has no key of its own (got {'id': 3})"),   # only `serve` knows a default key
+    (dict(pitch=2, keep_formants=1), "keep_formants must be true or false (got 1)"),
+    (dict(pitch=2, keep_formants="true"), "keep_formants must be true or false (got 'true')"),
+    (dict(keep_formants=True), "keep_formants needs a non-zero pitch"),
+    (dict(keep_formants=True, pitch=0, tempo=1.25), "keep_formants needs a non-zero pitch"),
+    # two at once, within one request: the five, the tempo, the pitch, their stretch, then the key, then the flag
+    (dict(loudness=True, watermark=True), "loudness must be a number of LUFS (got True)"),
+    (dict(pitch=9, watermark=True, keep_formants=1), "pitch must be a whole number of semitones from -6 to 6 (got 9)"),
+    (dict(tempo=0.5, pitch=3, watermark=0, keep_formants=True), "tempo 0.5 with pitch 3 stretches the wave by 88/37: outside 1/2 to 2"),
+    (dict(watermark=0, keep_formants=True), "watermark must be an integer key from 1 to 2^48 - 1 (got 0)"),
 ]
 
 
@@ -121,6 +149,70 @@ def test_whole_wave_rule_on_every_combination():
         assert infer.needs_whole_wave(opts) is W.WaveSpec.of(opts).needs_whole_wave()
         message = infer.WHOLE_WAVE_LOUDNESS if loud is not None and cut is not True else infer.WHOLE_WAVE
         assert infer.whole_wave_message(opts) == W.WaveSpec.of(opts).whole_wave_message() == message
+
+
+def test_wave_options_are_the_fields_and_the_four_tuples():
+    names = tuple(f.name for f in dataclasses.fields(W.WaveSpec))
+    assert W.WAVE_OPTIONS == infer.WAVE_OPTIONS == names == W.DELIVERY_OPTIONS + W.PROSODY_OPTIONS + W.WATERMARK_OPTIONS + W.FORMANT_OPTIONS
+    assert len(names) == 9 and set(names) == set(infer.REQUEST_OPTIONS[6:])
+    spec = W.WaveSpec(True, -16.0, 8000, "mulaw", 0, 1.25, 2)                          # the seven-argument positional form keeps its meaning
+    assert (spec.tempo, spec.pitch, spec.watermark, spec.keep_formants) == (1.25, 2, None, False)
+    assert W.WaveSpec.of(dict(watermark={"key": 5, "id": 8})) == W.WaveSpec(watermark=W.WatermarkTag(5, 8)) == W.WaveSpec.of(dict(watermark=W.WatermarkTag(5, 8)))
+    assert W.WaveSpec.of(dict(watermark={"key": 5})) == W.WaveSpec(watermark=5) == W.WaveSpec.of(dict(watermark=np.int64(5)))
+    assert W.WaveSpec.of(dict(watermark=None, keep_formants=None)) == W.WaveSpec()
+
+
+MARKS = (None, 5, W.WatermarkTag(5, 8), {"key": 5, "id": 8})
+# every other reason alone: (options, whether it counts for a streamed request, its message without a mark)
+REASONS = [
+    (dict(), None, None),
+    (dict(remove_silence=True), True, W.WHOLE_WAVE),
+    (dict(loudness=-20.0), True, W.WHOLE_WAVE_LOUDNESS),
+    (dict(tempo=1.25), True, W.WHOLE_WAVE_PROSODY),
+    (dict(pitch=-2), True, W.WHOLE_WAVE_PROSODY),
+    (dict(pitch=2, keep_formants=True), True, W.WHOLE_WAVE_PROSODY),
+    (dict(sample_rate=8000), False, W.WHOLE_WAVE),
+    (dict(encoding="flac", flac_level=1), False, W.WHOLE_WAVE),
+    (dict(loudness=-20.0, remove_silence=True), True, W.WHOLE_WAVE),
+    (dict(tempo=1.25, loudness=-20.0), True, W.WHOLE_WAVE_LOUDNESS),
+]
+
+
+def test_a_mark_in_the_whole_wave_rule():
+    """A mark always needs the whole wave, streamed or not, and it has the message exactly when it is the only reason; `infer`'s two
+    functions of a dict of options are the spec's."""
+    for reason, streamed_too, message in REASONS:
+        for mark in MARKS:
+            opts = dict(reason, watermark=mark, speed=1.0)
+            spec = W.WaveSpec.of(opts)
+            for streamed in (False, True):
+                want = mark is not None or (message is not None and (streamed_too or not streamed))
+                assert infer.needs_whole_wave(opts, streamed) is spec.needs_whole_wave(streamed) is want, (opts, streamed)
+            if mark is None and message is None:
+                continue   # (nothing to refuse)
+            only = mark is not None and message is None
+            assert infer.whole_wave_message(opts) == spec.whole_wave_message() == (W.WHOLE_WAVE_WATERMARK if only else message), opts
+            assert (spec.whole_wave_message() == W.WHOLE_WAVE_WATERMARK) == only
+
+
+def test_the_stretch_is_the_tempos_alone_with_keep_formants():
+    assert W.WaveSpec.of(dict(tempo=1.25, pitch=2, keep_formants=True)).stretch == W.formant_stretch(125) == (4, 5)
+    assert W.WaveSpec.of(dict(tempo=1.25, pitch=2)).stretch == W.prosody_stretch(125, 2) == (184, 205)
+    assert W.WaveSpec.of(dict(pitch=2, keep_formants=True)).stretch == (1, 1)
+
+
+def test_key_and_flag_count_in_equality_and_hash():
+    base = W.WaveSpec.of(dict(tempo=1.25, pitch=2, loudness=-20.0))
+    others = [dataclasses.replace(base, watermark=5), dataclasses.replace(base, watermark=6), dataclasses.replace(base, watermark=W.WatermarkTag(5, 0)),
+              dataclasses.replace(base, watermark=W.WatermarkTag(5, 1)), dataclasses.replace(base, keep_formants=True),
+              dataclasses.replace(base, watermark=5, keep_formants=True)]
+    specs = [base] + others
+    assert len(set(specs)) == len(specs) == len({hash(s) for s in specs})
+    assert all(a != b for a, b in itertools.combinations(specs, 2))
+    table = {W.WaveSpec.of(dict(watermark={"key": 5, "id": 1})): "tagged"}                # a spec with a tag is a dict key
+    assert table[W.WaveSpec(watermark=W.WatermarkTag(5, 1))] == "tagged" and W.WaveSpec(watermark=5) not in table
+    with pytest.raises(AttributeError):
+        base.watermark = 5                                                            # frozen
 
 
 def _paused_pcm():

@@ -37,7 +37,7 @@ from .audio_prep import (ASSESS_MAX_SAMPLES, REFERENCE_LIMITS, ReferenceReport, 
                          reference_problems, report_from_row)   # (the reference-clip report and the upload gate)
 from .loaders import DiT, MMDiT, UNetT, load_checkpoint, load_model, load_vocoder  # noqa: F401  (F/infer/utils_infer.py:92-130,175-260)
 from .wave_codec import (ALL_ENCODINGS, DELIVERY_OPTIONS, FLAC_BLOCK, FLAC_ENCODINGS, FLAC_HEADER_BYTES, MAX_TAP_TABLE_BYTES, OUTPUT_ENCODINGS,  # noqa: F401
-                         OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, WHOLE_WAVE, WHOLE_WAVE_LOUDNESS, StreamDelivery, StreamFlacEncoder,
+                         OUTPUT_SAMPLE_RATES, TAP_TABLE_CACHE, WAVE_OPTIONS, WHOLE_WAVE, WHOLE_WAVE_LOUDNESS, StreamDelivery, StreamFlacEncoder,
                          StreamResampler, WaveSpec, check_flac_level, decode_flac, decode_g711, deliver_pcm16,
                          delivery_format, encode_flac, encode_g711, flac_crc8, flac_crc16, flac_stream_header, load_audio, load_wav, quantise_pcm16, read_flac,
                          rate_pair, request_flac_level, resample_pcm16, resample_sinc_hann, resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
@@ -704,28 +704,23 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 
 # per-request options of `infer_requests` (the fourth element of a request) and of the serving routes
 REQUEST_OPTIONS = ("speed", "nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "remove_silence", "sample_rate", "encoding",
-                   "loudness", "flac_level") + WATERMARK_OPTIONS + FORMANT_OPTIONS + PROSODY_OPTIONS   # the sampler's six, then `DELIVERY_OPTIONS`,
-#                                            `watermark` and `keep_formants` (both carried beside the spec) and `PROSODY_OPTIONS` (`WaveSpec`)
+                   "loudness", "flac_level") + WATERMARK_OPTIONS + FORMANT_OPTIONS + PROSODY_OPTIONS   # the sampler's six, then the nine of
+#                                            `WaveSpec` (`WAVE_OPTIONS`): `DELIVERY_OPTIONS`, `watermark`, `keep_formants` and `PROSODY_OPTIONS`
 
 
 def needs_whole_wave(opts, streamed=False) -> bool:
-    """`WaveSpec.needs_whole_wave` of a dict of options, or a `watermark` among them (a mark needs the whole wave): whether the request
-    cannot be handed out chunk by chunk (`WHOLE_WAVE`)."""
-    return WaveSpec.of(opts).needs_whole_wave(streamed) or check_watermark(opts.get("watermark")) is not None
+    """`WaveSpec.needs_whole_wave` of a dict of options: whether the request cannot be handed out chunk by chunk (`WHOLE_WAVE`)."""
+    return WaveSpec.of(opts).needs_whole_wave(streamed)
 
 
 def whole_wave_message(opts) -> str:
-    """`WaveSpec.whole_wave_message` of a dict of options; `WHOLE_WAVE_WATERMARK` when a `watermark` is the only reason."""
-    return _whole_wave_message(WaveSpec.of(opts), check_watermark(opts.get("watermark")))
-
-
-def _whole_wave_message(spec, watermark=None) -> str:
-    return WHOLE_WAVE_WATERMARK if watermark is not None and not spec.needs_whole_wave() else spec.whole_wave_message()
+    """`WaveSpec.whole_wave_message` of a dict of options."""
+    return WaveSpec.of(opts).whole_wave_message()
 
 
 def plan_request(request, defaults, *, target_rms, fix_duration, device, tokenizer):
     """One request tuple (ref_audio, ref_text, gen_text[, options]) of `infer_requests` / `SpanScheduler.admit`, planned: `opts` (the
-    options over `defaults`, unknown ones rejected), `spec` (`WaveSpec.of(opts)`: what the finished wave has to be), `watermark` (the key of its mark, None without one), `voice` (prepared),
+    options over `defaults`, unknown ones rejected), `spec` (`WaveSpec.of(opts)`: what the finished wave has to be, its mark and `keep_formants` included), `voice` (prepared),
     `units` (one per chunk; the text is chunked unless it is a list of chunk texts) and `generator`, the request's noise source (None: the
     global one).  A `ScriptRequest` is planned segment by segment:
     `parts` = [(voice, units)] per segment (a plain request has one part), `units` all of them in order -- one generator, so chunk k of the
@@ -737,10 +732,9 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
     unknown = set(opts) - set(REQUEST_OPTIONS) - {"generator"}
     if unknown:
         raise ValueError(f"unknown request option(s) {sorted(unknown)}; known: {list(REQUEST_OPTIONS)}")
-    spec, watermark = WaveSpec.of(opts), check_watermark(opts.get("watermark"))
-    keep_formants = check_keep_formants(opts.get("keep_formants"), spec.pitch)   # (with a pitch only: the whole-wave rule below is the pitch's)
-    if (spec.needs_whole_wave() or watermark is not None) and isinstance(request_text(request), (list, tuple)):   # (a mark needs the whole wave)
-        raise ValueError(_whole_wave_message(spec, watermark))
+    spec = WaveSpec.of(opts)
+    if spec.needs_whole_wave() and isinstance(request_text(request), (list, tuple)):
+        raise ValueError(spec.whole_wave_message())
     # one (voice, units) part per segment; a plain request is its own single segment
     segments = script.segments if script is not None else [tuple(request[:3])]
     parts = [_plan_request(seg[0], seg[1], seg[2], target_rms, seg[3] if len(seg) > 3 and seg[3] is not None else opts["speed"], fix_duration,
@@ -752,7 +746,7 @@ def plan_request(request, defaults, *, target_rms, fix_duration, device, tokeniz
     def commit():
         if own is not None:
             own.set_state(gen.get_state())
-    return types.SimpleNamespace(voice=voice, units=units, opts=opts, spec=spec, watermark=watermark, keep_formants=keep_formants, generator=gen, commit=commit, parts=parts, script=script)
+    return types.SimpleNamespace(voice=voice, units=units, opts=opts, spec=spec, generator=gen, commit=commit, parts=parts, script=script)
 
 
 def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, target_rms=target_rms,
@@ -838,20 +832,18 @@ def infer_requests(requests, model_obj, vocoder, mel_spec_type=mel_spec_type, ta
         backend = bool(finish.get("device_backend"))
         got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms, on_device=backend, want_specs=False)
         chunk_waves = [request_chunk_waves(plan, got[per_plan[i]:per_plan[i + 1]]) for i, plan in enumerate(plans)]
-        return _finish_specs(chunk_waves, [request_text(req) for req in requests], cross_fade_duration, [plan.spec for plan in plans],
-                             watermark=[plan.watermark for plan in plans], keep_formants=[plan.keep_formants for plan in plans], **finish)
-    refused = next((plan for plan in plans if plan.spec.needs_whole_wave() or plan.watermark is not None), None)
+        return _finish_specs(chunk_waves, [request_text(req) for req in requests], cross_fade_duration, [plan.spec for plan in plans], **finish)
+    refused = next((plan for plan in plans if plan.spec.needs_whole_wave()), None)
     if refused is not None and not join:
-        raise ValueError(_whole_wave_message(refused.spec, refused.watermark))
+        raise ValueError(refused.spec.whole_wave_message())
     out = []
     got = _chunk_waves(groups, vocoder, mel_spec_type, target_rms)
     for i, plan in enumerate(plans):
         mine, script = got[per_plan[i]:per_plan[i + 1]], plan.script is not None
         if join:   # a script: (wave, rate, [spectrogram per segment]) like `infer_multi_voice`
             joined_specs = [np.concatenate(specs, axis=1) for _, specs in mine]
-            if script or plan.spec.needs_whole_wave() or plan.watermark is not None:
-                wave, = _finish_specs([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [plan.spec], watermark=[plan.watermark],
-                                      keep_formants=[plan.keep_formants])
+            if script or plan.spec.needs_whole_wave():
+                wave, = _finish_specs([request_chunk_waves(plan, mine)], [""], cross_fade_duration, [plan.spec])
             else:
                 wave = cross_fade_concat(mine[0][0], cross_fade_duration)
             out.append((wave, plan.spec.sample_rate, joined_specs if script else joined_specs[0]))
@@ -909,12 +901,13 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     `backend_stats`): a list text, chunk waves that are not on a HIP device, and a request of several chunks with one shorter than twice the
     fade, where the reference's nested cross-fades overlap and the kernel's closed form does not hold.
 
-    `sample_rate` / `encoding`, `loudness`, `flac_level`, `tempo`, `pitch`: each one value or one per request, None for the default; with the flag they are
-    the request's `WaveSpec`, and a request that sets any of them gets `finish_pcm16` of its int16 PCM (quantised whatever `want` says).
-    `watermark`: one key or one per request (`check_watermark`; None: no mark), carried beside the spec: the request's PCM gets `mark_pcm16`
+    `sample_rate` / `encoding`, `loudness`, `flac_level`, `tempo`, `pitch`, `watermark`, `keep_formants`: each one value or one per request, None for the
+    default; with the flag they are the request's `WaveSpec` (one `WaveSpec.of` per request, so of several bad requests the first one
+    reports), and a request that sets any of them gets `finish_pcm16` of its int16 PCM (quantised whatever `want` says).
+    `watermark`: one key or one per request (`check_watermark`; None: no mark): the request's PCM gets `mark_pcm16`
     between the prosody and the loudness steps.  In the place of a key a `WatermarkTag(key, id)` (or `{"key": K, "id": I}`) makes the mark
     carry the request's trace id too (`read_watermark` reads it back): still one mark call for the batch, tagged and untagged together.
-    `keep_formants`: one bool or one per request (`check_keep_formants`; None: no), carried beside the spec too: with it the request's
+    `keep_formants`: one bool or one per request (`check_keep_formants`; None: no): with it the request's
     `pitch` keeps the spectral envelope (`shift_pcm16(..., keep_formants=True)`); without a pitch it is refused.
     With `device_backend` all of it stays on the device, chained on one stream behind `wave_finish`: the calls and the copies that come back
     are `_finish_on_device`'s, and `backend_stats` counts them."""
@@ -923,15 +916,12 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     flags = [False] * n if remove_silence is None else [bool(f) for f in remove_silence]
     if len(gen_texts) != n or len(flags) != n:
         raise ValueError("finish_requests: one text and one remove_silence flag per request")
-    keywords = (("sample_rate", sample_rate), ("encoding", encoding), ("loudness", loudness), ("flac_level", flac_level), ("tempo", tempo),
-                ("pitch", pitch))
-    columns = [_per_request(value, n, name) for name, value in keywords]
-    specs = [WaveSpec.of(dict(remove_silence=flag, sample_rate=rate, encoding=enc, loudness=lufs, flac_level=level, tempo=rate_of_speech, pitch=semitones))
-             for flag, rate, enc, lufs, level, rate_of_speech, semitones in zip(flags, *columns)]
     one = isinstance(watermark, (WatermarkTag, dict))   # (a tag is a tuple: one value, not one per request)
-    marks = [check_watermark(key) for key in ([watermark] * n if one else _per_request(watermark, n, "watermark"))]
-    keeps = [check_keep_formants(keep, spec.pitch) for keep, spec in zip(_per_request(keep_formants, n, "keep_formants"), specs)]
-    return _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend, want, marks, keeps)
+    keywords = dict(sample_rate=sample_rate, encoding=encoding, loudness=loudness, flac_level=flac_level, tempo=tempo, pitch=pitch,
+                    watermark=[watermark] * n if one else watermark, keep_formants=keep_formants)
+    columns = [_per_request(value, n, name) for name, value in keywords.items()]
+    specs = [WaveSpec.of(dict(zip(keywords, row), remove_silence=flag)) for flag, *row in zip(flags, *columns)]
+    return _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend, want)
 
 
 def _check_want(device_backend, want):
@@ -941,20 +931,16 @@ def _check_want(device_backend, want):
         raise ValueError('the device back-end produces int16 PCM: device_backend=True needs want="pcm16"')
 
 
-def _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend=False, want="float", watermark=None,
-                  keep_formants=None):
-    """`finish_requests` with one planned `WaveSpec` per request in place of its option keywords, and beside them one watermark key per
-    request (None: no request is marked) and one `keep_formants` flag (None: nobody): what `infer_requests` and `SpanScheduler` call."""
+def _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs, device_backend=False, want="float"):
+    """`finish_requests` with one planned `WaveSpec` per request in place of its option keywords: what `infer_requests` and `SpanScheduler` call."""
     _check_want(device_backend, want)
-    marks = [None] * len(specs) if watermark is None else list(watermark)
-    keeps = [False] * len(specs) if keep_formants is None else [bool(k) for k in keep_formants]
     fade = int(cross_fade_duration * target_sample_rate) if cross_fade_duration > 0 else 0
     out, on_device = [None] * len(specs), []
     for i, (waves, text, spec) in enumerate(zip(chunk_waves_per_request, gen_texts, specs)):
         script = isinstance(waves, SegmentedWaves)
         if isinstance(text, (list, tuple)):
-            if spec.needs_whole_wave() or marks[i] is not None:
-                raise ValueError(_whole_wave_message(spec, marks[i]))
+            if spec.needs_whole_wave():
+                raise ValueError(spec.whole_wave_message())
             out[i] = [[_host_chunk(w) for w in seg] for seg in waves] if script else [_host_chunk(w) for w in waves]
         elif script and device_backend and _script_on_device(waves, fade):
             on_device.append(i)
@@ -963,13 +949,12 @@ def _finish_specs(chunk_waves_per_request, gen_texts, cross_fade_duration, specs
             on_device.append(i)
             continue
         else:
-            out[i] = _finish_on_host(waves, text, cross_fade_duration, spec, want, marks[i], keeps[i])
+            out[i] = _finish_on_host(waves, text, cross_fade_duration, spec, want)
         backend_stats["host_requests"] += 1
     if on_device:
         # the plain requests first: their PCM is then one prefix of the packed buffer, and what comes down of it holds no other request's
         on_device.sort(key=lambda i: not specs[i].plain_format)
-        done = _finish_on_device([_device_request(chunk_waves_per_request[i]) for i in on_device], fade, [specs[i] for i in on_device],
-                                 [marks[i] for i in on_device], [keeps[i] for i in on_device])
+        done = _finish_on_device([_device_request(chunk_waves_per_request[i]) for i in on_device], fade, [specs[i] for i in on_device])
         for i, wave in zip(on_device, done):
             out[i] = wave
     return out
@@ -999,39 +984,39 @@ def _device_request(waves):
     return chunks, fades
 
 
-def finish_pcm16(pcm, spec, watermark=None, keep_formants=False) -> np.ndarray:
-    """What a `WaveSpec`, and the `watermark` key and the `keep_formants` flag beside it, make of a request's 24 kHz int16 PCM, the one
+def finish_pcm16(pcm, spec) -> np.ndarray:
+    """What a `WaveSpec` makes of a request's 24 kHz int16 PCM, the one
     host definition (the device back-end and `StreamDelivery` are held to it byte for byte): `remove_silence_pcm` when flagged,
     `shift_pcm16` (tempo and pitch; with `keep_formants` the pitch by `psola_pcm16`, which keeps the spectral envelope),
     `mark_pcm16` with a key -- so the loudness and the -1 dBFS peak cap are measured on the marked samples, and the one gain behind it does
     not disturb the scale-invariant detector --, `normalise_loudness_pcm16`, `deliver_pcm16`."""
     if spec.remove_silence:
         pcm = remove_silence_pcm(pcm, target_sample_rate)
-    pcm = shift_pcm16(pcm, spec.tempo, spec.pitch, keep_formants=keep_formants)
-    pcm = mark_pcm16(pcm, watermark)
+    pcm = shift_pcm16(pcm, spec.tempo, spec.pitch, spec.keep_formants)
+    pcm = mark_pcm16(pcm, spec.watermark)
     pcm = normalise_loudness_pcm16(pcm, spec.loudness)
     return deliver_pcm16(pcm, *spec.format, flac_level=spec.flac_level if spec.flac else None)
 
 
-def _finish_on_host(waves, text, cross_fade_duration, spec, want, watermark=None, keep_formants=False):
+def _finish_on_host(waves, text, cross_fade_duration, spec, want):
     """`finish_requests` for one request on the host: join, quantisation where anything asks for PCM, `finish_pcm16`."""
     if isinstance(waves, SegmentedWaves):
         wave = join_segments([[_host_chunk(w) for w in seg] for seg in waves], cross_fade_duration, waves.gap_samples)
     else:
         wave = request_wave(text, [_host_chunk(w) for w in waves], cross_fade_duration)
-    if spec.needs_whole_wave() or watermark is not None:
-        return finish_pcm16(quantise_pcm16(wave), spec, watermark, keep_formants)
+    if spec.needs_whole_wave():
+        return finish_pcm16(quantise_pcm16(wave), spec)
     return quantise_pcm16(wave) if want == "pcm16" else wave   # (nothing to finish: no pass through the three steps' own checks)
 
 
-def _finish_on_device(requests, fade, specs, watermark=None, keep_formants=None):
+def _finish_on_device(requests, fade, specs):
     """`finish_requests` for the requests the device back-end takes: `requests` = (chunk waves (device tensors), fades: `_device_request`)
     and their `specs`, the plain-format ones first.  ONE `ops.wave_finish` call -- `ops.wave_finish_joins` when a script is among them --;
     directly behind it, when any request names a tempo or a pitch, ONE `ops.wave_prosody` call for the whole batch (the others are copied
-    through), whose buffer, offsets, bounds and device lengths everything downstream reads in the place of `wave_finish`'s -- with a flag in
-    `keep_formants` (one per request, None: nobody) the same ONE call, flagged and unflagged requests together: a flagged request takes the
+    through), whose buffer, offsets, bounds and device lengths everything downstream reads in the place of `wave_finish`'s -- with a spec that
+    has `keep_formants` the same ONE call, flagged and unflagged requests together: a flagged request takes the
     stretch of its tempo alone and keeps its spectral envelope (`backend_stats["formant_requests"]`);
-    then, when any request has a key or a `WatermarkTag` in `watermark` (one per request, None: nobody), ONE `ops.wave_mark` call that marks
+    then, when any spec has a key or a `WatermarkTag` for its `watermark`, ONE `ops.wave_mark` call that marks
     those in place, with their trace ids where they have one (f5hip_wave_mark_ids then; the same two launches, no copy more)
     (carriers cached on the device: nothing is uploaded for a key seen before, and nothing comes back);
     then, when any request has a loudness target, ONE `ops.wave_loudness` call that normalises those in place; then on the
@@ -1057,16 +1042,15 @@ def _finish_on_device(requests, fade, specs, watermark=None, keep_formants=None)
     else:
         pcm, lengths, offsets = ops.wave_finish_joins(chunks, counts, fade, [x for f in fades for x in f], silence, target_sample_rate)
     if any(spec.prosody for spec in specs):   # one call for the batch; lengths stay on the device, and `joined` becomes the new bounds
-        keeps = [False] * len(specs) if keep_formants is None else list(keep_formants)
+        keeps = [spec.keep_formants for spec in specs]
+        flagged = {}   # (nobody flagged: the argument is left out, and the call is the older entry point with its launch count)
         if any(keeps):
-            stretches = [formant_stretch(check_tempo(spec.tempo)) if keep else spec.stretch for spec, keep in zip(specs, keeps)]
-            pcm, lengths, offsets, joined = ops.wave_prosody(pcm, offsets, joined, lengths, stretches, [spec.pitch for spec in specs], keep_formants=keeps)
+            flagged = {"keep_formants": keeps}
             backend_stats["formant_requests"] += sum(keeps)
-        else:
-            pcm, lengths, offsets, joined = ops.wave_prosody(pcm, offsets, joined, lengths, [spec.stretch for spec in specs], [spec.pitch for spec in specs])
+        pcm, lengths, offsets, joined = ops.wave_prosody(pcm, offsets, joined, lengths, [spec.stretch for spec in specs], [spec.pitch for spec in specs], **flagged)
         backend_stats["prosody_calls"] += 1
         backend_stats["prosody_requests"] += sum(spec.prosody for spec in specs)
-    marks = [None] * len(specs) if watermark is None else list(watermark)
+    marks = [spec.watermark for spec in specs]
     if any(key is not None for key in marks):   # in place, lengths still on the device: nothing comes back for it
         ops.wave_mark(pcm, offsets, joined, lengths, marks)
         backend_stats["mark_calls"] += 1
@@ -1147,8 +1131,8 @@ class SpanTicket:
     """One admitted request of a `SpanScheduler`: its planned units, `spec` (`plan_request`'s `WaveSpec`: what the finished wave has to be),
     and -- once the units have all ended -- `result` (`request_wave`)."""
 
-    def __init__(self, request, voice, units, spec, parts=None, script=None, watermark=None, keep_formants=False):
-        self.request, self.voice, self.units, self.spec, self.watermark, self.keep_formants = request, voice, units, spec, watermark, keep_formants
+    def __init__(self, request, voice, units, spec, parts=None, script=None):
+        self.request, self.voice, self.units, self.spec = request, voice, units, spec
         self.parts = parts if parts is not None else [(voice, units)]   # [(voice, its units)]: one per segment of a script
         self.script = script
         self.in_flight = self.cancelled = self.done = False
@@ -1223,7 +1207,7 @@ class SpanScheduler:
                                                            sway_sampling_coef=opts["sway_sampling_coef"], generator=plan.generator, **extra)
                                   for tokens, frames in units]))
         plan.commit()   # every chunk was planned: the caller's generator moves
-        ticket = SpanTicket(request, plan.voice, [u for _, us in parts for u in us], plan.spec, parts, plan.script, plan.watermark, plan.keep_formants)
+        ticket = SpanTicket(request, plan.voice, [u for _, us in parts for u in us], plan.spec, parts, plan.script)
         self.waiting.append(ticket)
         return ticket
 
@@ -1249,8 +1233,7 @@ class SpanScheduler:
         first = np.cumsum([0] + [len(t.parts) for t in tickets])
         chunk_waves = [request_chunk_waves(t, got[first[i]:first[i + 1]]) for i, t in enumerate(tickets)]
         results = _finish_specs(chunk_waves, [request_text(t.request) for t in tickets], self.cross_fade_duration, [t.spec for t in tickets],
-                                self.device_backend, "pcm16" if self.device_backend else "float", [t.watermark for t in tickets],
-                                [t.keep_formants for t in tickets])
+                                self.device_backend, "pcm16" if self.device_backend else "float")
         for t, result in zip(tickets, results):
             t.result, t.done, t.in_flight = result, True, False
 

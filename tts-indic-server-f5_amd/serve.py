@@ -51,7 +51,7 @@ log = logging.getLogger(__name__)
 EDIT_OPTIONS = ("nfe_step", "cfg_strength", "sway_sampling_coef", "seed", "ode_method", "flac_level")   # a speech edit has no `speed`: its durations are planned
 # the delivery options an edit takes, in the order the routes check them (`infer.REQUEST_OPTIONS`'): all but `remove_silence`, the recording keeps its pauses
 EDIT_DELIVERY = tuple(k for k in infer.REQUEST_OPTIONS if k in infer.DELIVERY_OPTIONS and k != "remove_silence")
-EDIT_MARK = infer.WATERMARK_OPTIONS   # beside them: the whole returned recording is marked (`infer.mark_pcm16`), on the host, as the route finishes
+EDIT_MARK = infer.WATERMARK_OPTIONS   # and the mark, in the same `infer.WaveSpec`: the whole returned recording is marked (`infer.mark_pcm16`), on the host, as the route finishes
 # most ODE steps one library call accepts per method: 128 time points (f5hip precompute_time); midpoint uses 2 per step, RK4 3 per step + 1
 MAX_NFE_STEP = {"euler": 128, "midpoint": 64, "rk4": 42}
 
@@ -129,8 +129,7 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
             if k == "speed" and v <= 0:
                 raise ValueError(f"speed must be greater than 0 (got {v}).")
         out[k] = v
-    infer.WaveSpec.of(out)                              # the delivery options together.  ValueError: "flac_level needs encoding 'flac' ..."
-    infer.check_keep_formants(out.get("keep_formants"), out.get("pitch", 0))   # ValueError: "keep_formants needs a non-zero pitch"
+    infer.WaveSpec.of(out)                              # the wave options together.  ValueError: "flac_level needs encoding 'flac' ...", then "keep_formants needs a non-zero pitch"
     if out.get("flac_level") == 0:
         del out["flac_level"]
     return out
@@ -162,13 +161,14 @@ MARKED_REFERENCE = infer.MARKED_REFERENCE   # "the reference clip carries this s
 def stream_refusal(opts):
     """The message a streaming path refuses `opts` with, or None: an option that needs the whole wave (`infer.needs_whole_wave`; the
     delivery format does not count, a stream applies it piece by piece)."""
-    if not infer.needs_whole_wave(opts, streamed=True):
+    spec = infer.WaveSpec.of(opts)
+    if not spec.needs_whole_wave(streamed=True):
         return None
-    if opts.get("remove_silence"):
+    if spec.remove_silence:
         return STREAM_REMOVE_SILENCE
-    if opts.get("loudness") is not None:
+    if spec.loudness is not None:
         return STREAM_LOUDNESS
-    return STREAM_PROSODY if infer.WaveSpec.of(opts).prosody else STREAM_WATERMARK
+    return STREAM_PROSODY if spec.prosody else STREAM_WATERMARK
 
 
 @dataclass
@@ -815,7 +815,7 @@ class TTSManager:
 
     def _stream(self, voice, ref_text, head, tail, opts=None):
         spec = infer.WaveSpec.of(opts or {})   # the delivery format is applied here, piece by piece: the head and tail requests stay plain
-        opts = {k: v for k, v in (opts or {}).items() if k not in infer.DELIVERY_OPTIONS + infer.PROSODY_OPTIONS + infer.WATERMARK_OPTIONS + infer.FORMANT_OPTIONS}
+        opts = {k: v for k, v in (opts or {}).items() if k not in infer.WAVE_OPTIONS}
         return self._stream_requests(self._request(voice, ref_text, head, opts), self._request(voice, ref_text, tail, opts) if tail else None, spec)
 
     def _stream_requests(self, head_request, tail_request, spec, tail_pieces=None):
@@ -954,7 +954,7 @@ class TTSManager:
         if "seed" in opts:
             opts["generator"] = infer.request_generator(opts.pop("seed"))
         spec = infer.WaveSpec.of(opts)            # (applied to the pieces, as in `_stream`)
-        opts = {k: v for k, v in opts.items() if k not in infer.DELIVERY_OPTIONS + infer.PROSODY_OPTIONS + infer.WATERMARK_OPTIONS + infer.FORMANT_OPTIONS}
+        opts = {k: v for k, v in opts.items() if k not in infer.WAVE_OPTIONS}
         chunked = [(voice, ref_text, infer.request_chunks(ref_text, voice.seconds, piece), speed) for voice, ref_text, piece, speed in segments]
         voice, ref_text, chunks, speed = chunked[0]
         head = self._request(voice, ref_text, chunks[:1], dict(opts, speed=speed) if speed is not None else opts)
@@ -985,7 +985,7 @@ class TTSManager:
         opts = dict(self.opts, **self.request_options(EDIT_OPTIONS, nfe_step=nfe_step, cfg_strength=cfg_strength,
                                                       sway_sampling_coef=sway_sampling_coef, seed=seed, ode_method=ode_method))
         delivery = self.request_options(EDIT_DELIVERY, sample_rate=sample_rate, encoding=encoding, flac_level=flac_level, loudness=loudness)
-        mark = self.request_options(EDIT_MARK, watermark=watermark).get("watermark")
+        spec = infer.WaveSpec.of(dict(delivery, **self.request_options(EDIT_MARK, watermark=watermark)))
         model_obj = getattr(self.model_obj, "local", self.model_obj)
         # host work (read, mono mix, resample, plan, tokens) and every rejection happen before the device lock is taken (a FLAC recording is
         # decoded under it with `device_decode`, after everything that needs no samples has been refused)
@@ -1000,9 +1000,9 @@ class TTSManager:
                                                     nfe_step=opts["nfe_step"], cfg_strength=opts["cfg_strength"],
                                                     sway_sampling_coef=opts["sway_sampling_coef"], **extra)
         wave = np.asarray(wave, dtype=np.float32)
-        if not delivery and mark is None:
+        if not spec.needs_whole_wave():   # (nothing named, no mark: the float wave)
             return wave
-        return infer.finish_pcm16(infer.quantise_pcm16(wave), infer.WaveSpec.of(delivery), mark)
+        return infer.finish_pcm16(infer.quantise_pcm16(wave), spec)
 
     def detect_watermark(self, audio, keys=None) -> list:
         """Whether a recording carries a mark: one `infer.WatermarkScore(key, z, offset, detected)` per key for `audio` -- a path, WAV or FLAC
@@ -1140,8 +1140,8 @@ def container_format(response_format, encoding=None) -> str:
 def response_body(audio, options: dict, response_format: str = "wav") -> io.BytesIO:
     """The response body of a request's result in the delivery format its `options` name: a WAV file (`wav_bytes`), with "pcm" the
     headerless little-endian samples / code bytes, and for `encoding` "flac" the FLAC stream the result holds."""
-    spec = infer.WaveSpec.of(options)
-    return io.BytesIO(delivery_bytes(audio, spec.encoding)) if spec.flac or response_format == "pcm" else wav_bytes(audio, *spec.format)
+    rate, enc = infer.delivery_format(options.get("sample_rate"), options.get("encoding"))   # (the format alone: checked or not, nothing else of them counts here)
+    return io.BytesIO(delivery_bytes(audio, enc)) if enc in infer.FLAC_ENCODINGS or response_format == "pcm" else wav_bytes(audio, rate, enc)
 
 
 def synthesize_speech(tts_manager: TTSManager, registry: VoiceRegistry, text: str, ref_audio_name: str, ref_text: str | None,

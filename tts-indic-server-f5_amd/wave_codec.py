@@ -3,7 +3,7 @@
 `StreamResampler`), the BS.1770 loudness meter and normaliser (`measure_loudness`, `normalise_loudness_pcm16`), G.711 (`encode_g711`,
 `decode_g711`), FLAC (`encode_flac`, `decode_flac`, `StreamFlacEncoder`; the whole format in: `read_flac`, `load_audio`), the delivery
 format of a request (`delivery_format`, `deliver_pcm16`), time-scale modification of finished PCM (`wsola_pcm16`, `shift_pcm16`: a request's
-`tempo` and `pitch`; `psola_pcm16`: a `pitch` that keeps the formants, a request's `keep_formants`), the provenance watermark (`mark_pcm16`, `detect_watermark`: a request's `watermark` key), its five delivery and two prosody options as one value (`WaveSpec`; `StreamDelivery` applies it to a stream) and the bytes of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
+`tempo` and `pitch`; `psola_pcm16`: a `pitch` that keeps the formants, a request's `keep_formants`), the provenance watermark (`mark_pcm16`, `detect_watermark`: a request's `watermark` key), all nine of these options -- five of delivery, two of prosody, the key and the flag -- as one value (`WaveSpec`, `WAVE_OPTIONS`; `StreamDelivery` applies it to a stream) and the bytes of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
 round; `infer` and `serve` hand every public name on (`infer.load_wav`, `serve.wav_bytes`, ...)."""
 from __future__ import annotations
 
@@ -393,8 +393,8 @@ WHOLE_WAVE_PROSODY = ("tempo and pitch are applied to the request's whole wave: 
 
 @dataclasses.dataclass(frozen=True)
 class WaveSpec:
-    """What a request asks of its finished wave, the five `DELIVERY_OPTIONS` and the two `PROSODY_OPTIONS` as one immutable value: the
-    planner makes it (`WaveSpec.of`), and every finishing path -- `infer.finish_pcm16` on the host, `infer._finish_on_device`,
+    """What a request asks of its finished wave, the five `DELIVERY_OPTIONS`, the two `PROSODY_OPTIONS`, its `watermark` and its
+    `keep_formants` flag (`WAVE_OPTIONS`) as one immutable, hashable value: the planner makes it (`WaveSpec.of`), and every finishing path -- `infer.finish_pcm16` on the host, `infer._finish_on_device`,
     `StreamDelivery` for a stream -- reads it.
     All are pure functions of the request's canonical result, its joined 24 kHz wave quantised to int16 PCM, applied in this order:
       `remove_silence`  the reference's `remove_silence_for_generated_wav` (`audio_prep.remove_silence_pcm`): pauses of 1 s or more shrink
@@ -402,13 +402,17 @@ class WaveSpec:
       `tempo`, `pitch`  time-scale modification (`shift_pcm16`: WSOLA, then a rational resampler for the pitch): the duration divided by
                         `tempo` (0.5 to 2 in steps of 0.01) at the same pitch, the pitch moved by `pitch` whole semitones (-6 to 6) at the
                         same duration; 1.0 and 0 keep the samples as they are.  So loudness is measured on what is delivered.
+      `keep_formants`   beside a non-zero `pitch` only (`check_keep_formants`): the pitch moves by `psola_pcm16` and the spectral envelope
+                        stays; WSOLA then stretches by the tempo alone (`stretch`).
+      `watermark`       a key, or a `WatermarkTag(key, id)` with a trace id (`check_watermark`): `mark_pcm16` behind the prosody step and in
+                        front of the loudness step, so the level and the -1 dBFS peak cap are measured on the marked samples; None: no mark.
       `loudness`        a programme loudness target in LUFS within LOUDNESS_RANGE (ITU-R BS.1770-4; `normalise_loudness_pcm16`: the sample
                         peak stays at or below -1 dBFS); None keeps the level as synthesized.
       `sample_rate`, `encoding`  the delivery format (`deliver_pcm16`): one of OUTPUT_SAMPLE_RATES (`resample_pcm16`), then "pcm16", "mulaw" /
                         "alaw" (`encode_g711`: uint8 code bytes) or "flac" (`encode_flac`: a uint8 array that holds the whole stream).
       `flac_level`      0, or 1 for LPC subframes among the candidates of the stream's full blocks (never larger, the same samples); only a
                         "flac" request may name one: beside any other encoding a level is refused, never ignored.
-    `remove_silence`, `loudness`, `tempo`, `pitch`, and a format other than 24 kHz "pcm16", need the request's whole wave
+    `remove_silence`, `loudness`, `tempo`, `pitch`, `watermark`, and a format other than 24 kHz "pcm16", need the request's whole wave
     (`needs_whole_wave`): they are refused for a list of chunk texts and with join=False; a stream applies the format piece by piece and
     refuses the others."""
     remove_silence: bool = False
@@ -418,19 +422,23 @@ class WaveSpec:
     flac_level: int = 0
     tempo: float = 1.0
     pitch: int = 0
+    watermark: int | WatermarkTag | None = None
+    keep_formants: bool = False
 
     @classmethod
     def of(cls, options) -> "WaveSpec":
         """The spec of a mapping of options: a missing key or None is the default, other keys are ignored.  The one place where they are
-        checked together -- `check_loudness`, `request_flac_level`, `delivery_format`, then `check_tempo`, `check_pitch` and
-        `prosody_stretch`, in that order, with their messages (ValueError)."""
+        checked together -- `check_loudness`, `request_flac_level`, `delivery_format`, then `check_tempo`, `check_pitch`,
+        `prosody_stretch`, `check_watermark` and `check_keep_formants`, in that order, with their messages (ValueError).  A `watermark` of
+        `{"id": I}` alone is refused here: only a service knows a key of its own (`serve.check_request_options` resolves it first)."""
         get = options.get
         loudness = check_loudness(get("loudness"))
         level = request_flac_level(get("flac_level"), get("encoding"))
         fmt = delivery_format(get("sample_rate"), get("encoding"))
         hundredths, pitch = check_tempo(get("tempo")), check_pitch(get("pitch"))
         prosody_stretch(hundredths, pitch)
-        return cls(bool(get("remove_silence")), loudness, *fmt, level, hundredths / 100, pitch)
+        return cls(bool(get("remove_silence")), loudness, *fmt, level, hundredths / 100, pitch, check_watermark(get("watermark")),
+                   check_keep_formants(get("keep_formants"), pitch))
 
     @property
     def format(self):
@@ -456,19 +464,25 @@ class WaveSpec:
 
     @property
     def stretch(self):
-        """(P, Q) of `prosody_stretch`: what `ops.wave_prosody` takes beside the pitch."""
-        return prosody_stretch(check_tempo(self.tempo), self.pitch)
+        """(P, Q) of the WSOLA step, what `ops.wave_prosody` takes beside the pitch; with `keep_formants` the tempo's alone."""
+        hundredths = check_tempo(self.tempo)
+        return formant_stretch(hundredths) if self.keep_formants else prosody_stretch(hundredths, self.pitch)
 
     def needs_whole_wave(self, streamed=False) -> bool:
         """Whether the request cannot be handed out chunk by chunk.  `streamed`: the format does not count, the stream's owner applies it."""
-        return self.remove_silence or self.loudness is not None or self.prosody or not (streamed or self.plain_format)
+        return self.remove_silence or self.loudness is not None or self.prosody or self.watermark is not None or not (streamed or self.plain_format)
 
     def whole_wave_message(self) -> str:
         """The refusal of a request that `needs_whole_wave` where it cannot have it: `WHOLE_WAVE_LOUDNESS` when `loudness` is the reason,
-        `WHOLE_WAVE_PROSODY` when `tempo` / `pitch` are the only one."""
+        `WHOLE_WAVE_PROSODY` when `tempo` / `pitch` are the only one, `WHOLE_WAVE_WATERMARK` when the mark is."""
+        if self.watermark is not None and not dataclasses.replace(self, watermark=None).needs_whole_wave():
+            return WHOLE_WAVE_WATERMARK
         if self.prosody and not self.remove_silence and self.loudness is None and self.plain_format:
             return WHOLE_WAVE_PROSODY
         return WHOLE_WAVE_LOUDNESS if self.loudness is not None and not self.remove_silence else WHOLE_WAVE
+
+
+WAVE_OPTIONS = tuple(f.name for f in dataclasses.fields(WaveSpec))   # DELIVERY_OPTIONS + PROSODY_OPTIONS + WATERMARK_OPTIONS + FORMANT_OPTIONS
 
 
 # ----------------------------------------- loudness: the mono programme loudness of ITU-R BS.1770-4 on a request's 24 kHz int16 PCM, in integers
@@ -798,7 +812,7 @@ def shifted_length(n, stretch, pitch) -> int:
 PSOLA_HOP, PSOLA_WINDOW, PSOLA_LAG_MIN, PSOLA_LAG_MAX = 120, 480, 48, 400
 PSOLA_MIN_ADVANCE = 24
 PSOLA_TABLE = 1024
-FORMANT_OPTIONS = ("keep_formants",)              # beside PROSODY_OPTIONS; carried next to the WaveSpec, not in it
+FORMANT_OPTIONS = ("keep_formants",)              # beside PROSODY_OPTIONS: the last `WaveSpec` field
 _psola_window = None
 
 
@@ -976,7 +990,7 @@ WATERMARK_MIN_SAMPLES = 12000
 WATERMARK_MAX_SAMPLES = 1_440_000
 WATERMARK_KEYS_MAX = 16
 WATERMARK_KEY_MAX = (1 << 48) - 1
-WATERMARK_OPTIONS = ("watermark",)                # beside DELIVERY_OPTIONS and PROSODY_OPTIONS; carried next to the WaveSpec, not in it
+WATERMARK_OPTIONS = ("watermark",)                # beside DELIVERY_OPTIONS and PROSODY_OPTIONS: a `WaveSpec` field like them
 WHOLE_WAVE_WATERMARK = ("watermark marks the request's whole wave: it is not available for a list of chunk texts, on a streaming path or "
                         "with join=False")
 WATERMARK_ID_BITS = 30
