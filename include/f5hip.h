@@ -5,6 +5,14 @@
  * hipStream_t passed as void* (NULL = default stream).  Every function returns 0 on success and a negative
  * code on failure; f5hip_last_error() gives the message.  Nothing here falls back to the CPU.
  *
+ * Streams.  A handle (f5hip_dit, f5hip_vocos, f5hip_bigvgan) has one call in flight: issue its next call on the same stream, or
+ * after the caller has ordered the two.  The calls that take no handle (the mel front-ends, f5hip_ref_*, f5hip_flac_decode,
+ * f5hip_wave_*, f5hip_watermark_*) keep their request tables and scratch in one workspace per device and kind of call.  They are
+ * issued one at a time per device from the host (no two threads inside such calls on one device at once) and may be issued on any
+ * streams: a call whose workspace was last used on another stream makes its own stream wait for that use on the device
+ * (hipStreamWaitEvent, no host wait), so a call's result does not depend on which stream the next call uses.  On one stream that
+ * costs one event record per call.
+ *
  * Each entry point names the reference interface it replaces (F/ = src/server/f5_tts/ of
  * dwani-ai/tts-indic-server-f5); INTEGRATION.md shows the ctypes binding a maintainer would add.
  */

@@ -270,6 +270,7 @@ struct FiWorkspace {
     long long* sbase = nullptr; size_t cap_sbase = 0;
     FiFrame* frames = nullptr; size_t cap_frames = 0;
     int32_t* pool = nullptr; size_t cap_pool = 0;
+    WorkspaceUse use;
 };
 
 // samples per channel the output must have room for: STREAMINFO's total, or for a stream that does not name it twice its bytes plus a block;
@@ -312,6 +313,9 @@ int f5hip_flac_decode(int32_t n, const uint8_t* data_dev, int64_t nbytes, const 
     FiWorkspace* const wsp = device_workspace<FiWorkspace>("flac_decode");
     if (!wsp) return -6;
     FiWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(dev_reserve(&ws.streams, &ws.cap_streams, (size_t)n, "flac_decode streams"));
     CK(dev_reserve(&ws.cand_local, &ws.cap_local, (size_t)nbytes, "flac_decode candidate map"));
     CK(dev_reserve(&ws.chunk_list, &ws.cap_list, (size_t)nchunks * kFiChunk, "flac_decode candidate lists"));
@@ -322,7 +326,6 @@ int f5hip_flac_decode(int32_t n, const uint8_t* data_dev, int64_t nbytes, const 
     CK(dev_reserve(&ws.sbase, &ws.cap_sbase, (size_t)nchunks, "flac_decode slot bases"));
     CK(dev_reserve(&ws.frames, &ws.cap_frames, (size_t)maxc, "flac_decode frame records"));
     CK(dev_reserve(&ws.pool, &ws.cap_pool, (size_t)pool_words, "flac_decode slot pool"));
-    hipStream_t st = (hipStream_t)stream;
     if (upload_sync(st, ws.streams, h) != hipSuccess) return fail(-6, "flac_decode metadata upload");
     hipLaunchKernelGGL(flac_in_scan_kernel, dim3((unsigned)nchunks), dim3(kFiChunk), 0, st, ws.streams, n, (const uint8_t*)data_dev, (long long)nbytes,
                        ws.cand_local, ws.chunk_list, ws.chunk_slot, ws.chunk_count, ws.chunk_words);

@@ -61,3 +61,22 @@ static W* device_workspace(const char* call) {
     if (hipGetDevice(&dev) != hipSuccess) { fail(-6, "%s: hipGetDevice", call); return nullptr; }
     return &table[dev & 31];
 }
+
+// A per-device workspace is one set of tables and scratch for every call of its kind, whatever stream the call names.  Its calls take turns:
+// WorkspaceTurn turn(ws.use, st) right after device_workspace<W>() makes st wait (on the device, never on the host) for the workspace's
+// previous use where that went to another stream, and on every exit of the scope records the end of this use behind what the call queued.
+// On one stream a turn is one event record.  The calls themselves arrive one at a time per device from the host (include/f5hip.h).
+struct WorkspaceUse { hipEvent_t done = nullptr; hipStream_t last = nullptr; bool recorded = false; };
+struct WorkspaceTurn {
+    WorkspaceUse& use; hipStream_t st; int rc = 0;
+    WorkspaceTurn(WorkspaceUse& u, hipStream_t s) : use(u), st(s) {
+        if (!use.done && hipEventCreateWithFlags(&use.done, hipEventDisableTiming) != hipSuccess) { use.done = nullptr; rc = fail(-5, "hipEventCreate workspace turn"); return; }
+        if (use.recorded && use.last != st && hipStreamWaitEvent(st, use.done, 0) != hipSuccess) rc = fail(-6, "workspace turn: hipStreamWaitEvent");
+    }
+    ~WorkspaceTurn() {
+        if (!use.done || rc) return;
+        if (hipEventRecord(use.done, st) == hipSuccess) { use.recorded = true; use.last = st; }
+    }
+    WorkspaceTurn(const WorkspaceTurn&) = delete;
+    WorkspaceTurn& operator=(const WorkspaceTurn&) = delete;
+};

@@ -195,6 +195,7 @@ struct RaWorkspace {
     double* E = nullptr; size_t cap_E = 0;
     double* T = nullptr; size_t cap_T = 0;
     HostStage stage, stage_raw;
+    WorkspaceUse use;
 };
 
 int f5hip_ref_assess(int32_t n, const float* raw_dev, const int64_t* raw_offset, const int32_t* channels, const int32_t* raw_len, const float* wave_dev,
@@ -228,6 +229,9 @@ int f5hip_ref_assess(int32_t n, const float* raw_dev, const int64_t* raw_offset,
     RaWorkspace* const wsp = device_workspace<RaWorkspace>("ref_assess");
     if (!tables || !wsp) return -6;
     RaWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(rd_tables(*tables));
     CK(dev_reserve(&ws.clips, &ws.cap_clips, (size_t)n, "ref_assess clips"));
     CK(dev_reserve(&ws.raws, &ws.cap_raws, (size_t)n, "ref_assess raw clips"));
@@ -238,7 +242,6 @@ int f5hip_ref_assess(int32_t n, const float* raw_dev, const int64_t* raw_offset,
     CK(dev_reserve(&ws.E, &ws.cap_E, (size_t)rows, "ref_assess band sums"));
     const long long tiles = ra_tile_layout(h, hr);
     CK(dev_reserve(&ws.T, &ws.cap_T, (size_t)tiles * kRaWStride, "ref_assess window sums"));
-    hipStream_t st = (hipStream_t)stream;
     CK(ws.stage.upload(ws.clips, h.data(), sizeof(RdClip) * (size_t)n, st));       // pinned staging, queued on `stream`: no wait
     CK(ws.stage_raw.upload(ws.raws, hr.data(), sizeof(RaClip) * (size_t)n, st));
     if (hipMemsetAsync(ws.acc, 0, sizeof(RaAcc) * (size_t)n, st) != hipSuccess) return fail(-6, "ref_assess: memset");

@@ -116,6 +116,7 @@ struct RdWorkspace {
     float* window = nullptr;        // sin(pi i / 1024): the square root of the periodic Hann window
     float2* twiddle = nullptr;
     HostStage stage;
+    WorkspaceUse use;               // of the denoiser's own buffers; window and twiddle never change once built, and their readers take no turn
 };
 
 static int rd_tables(RdWorkspace& ws) {
@@ -152,13 +153,15 @@ int f5hip_ref_denoise(int32_t n, const int64_t* offset, const int32_t* n_samples
     RdWorkspace* const wsp = device_workspace<RdWorkspace>("ref_denoise");
     if (!wsp) return -6;
     RdWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(rd_tables(ws));
     CK(dev_reserve(&ws.clips, &ws.cap_clips, (size_t)n, "ref_denoise clips"));
     CK(dev_reserve(&ws.X, &ws.cap_X, (size_t)rows * kRdBins, "ref_denoise spectra"));
     CK(dev_reserve(&ws.P, &ws.cap_P, (size_t)rows * kRdPStride, "ref_denoise powers"));
     CK(dev_reserve(&ws.fw, &ws.cap_fw, (size_t)rows * kRdNfft, "ref_denoise frames"));
     CK(dev_reserve(&ws.floor_, &ws.cap_floor, (size_t)n * kRdPStride, "ref_denoise noise floors"));
-    hipStream_t st = (hipStream_t)stream;
     CK(ws.stage.upload(ws.clips, h.data(), sizeof(RdClip) * (size_t)n, st));   // pinned staging, queued on `stream`: no wait
 
     hipLaunchKernelGGL(rd_stft_kernel, dim3((unsigned)rows), dim3(256), 0, st, ws.clips, n, wave_dev, ws.window, ws.twiddle, ws.X, ws.P);

@@ -176,6 +176,7 @@ struct RpWorkspace {
     uint8_t* flags = nullptr; size_t cap_flags = 0;
     RpRanges* ranges = nullptr; size_t cap_ranges = 0;
     HostStage stage;
+    WorkspaceUse use;
 };
 
 int64_t f5hip_ref_prestep_bound(int32_t n, const int32_t* n_in, const int32_t* channels, int32_t rate) {
@@ -218,11 +219,13 @@ int f5hip_ref_prestep(int32_t n, const int32_t* n_in, const int32_t* channels, c
     RpWorkspace* const wsp = device_workspace<RpWorkspace>("ref_prestep");
     if (!wsp) return -6;
     RpWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(dev_reserve(&ws.clips, &ws.cap_clips, (size_t)n, "ref_prestep clips"));
     CK(dev_reserve(&ws.P, &ws.cap_P, (size_t)p_off, "ref_prestep prefix sums"));
     CK(dev_reserve(&ws.flags, &ws.cap_flags, (size_t)std::max(f_off, 1LL), "ref_prestep window flags"));
     CK(dev_reserve(&ws.ranges, &ws.cap_ranges, (size_t)n, "ref_prestep ranges"));
-    hipStream_t st = (hipStream_t)stream;
     CK(ws.stage.upload(ws.clips, h.data(), sizeof(RpClip) * (size_t)n, st));   // pinned staging, queued on `stream`: no wait
 
     const short* x = (const short*)frames_dev;

@@ -129,6 +129,7 @@ struct RefWorkspace {
     RefClip* clips = nullptr; size_t cap_clips = 0;
     double* partials = nullptr; size_t cap_parts = 0;
     int2* range = nullptr; size_t cap_range = 0;
+    WorkspaceUse use;
 };
 int f5hip_ref_frontend(int32_t n, const int32_t* n_in, const int32_t* channels, const float* wave_dev, int32_t orig_freq, int32_t new_freq,
                        const float* taps_dev, float rms_floor, float* out_dev, float* rms_dev, void* stream) {
@@ -172,13 +173,15 @@ int f5hip_ref_frontend(int32_t n, const int32_t* n_in, const int32_t* channels, 
     RefWorkspace* const wsp = device_workspace<RefWorkspace>("ref_frontend");
     if (!wsp) return -6;
     RefWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(dev_reserve(&ws.clips, &ws.cap_clips, (size_t)n, "ref_frontend clips"));
     CK(dev_reserve(&ws.partials, &ws.cap_parts, (size_t)parts, "ref_frontend partials"));
     CK(dev_reserve(&ws.range, &ws.cap_range, (size_t)nf, "ref_frontend tap ranges"));
     static unsigned lds_attr_done = 0;
     if (taps_lds && lds > 64 * 1024 && f5_set_lds_attr((const void*)ref_resample_kernel<0>, kLdsMax, lds_attr_done) != hipSuccess)
         return fail(-7, "ref_frontend: LDS opt-in");
-    hipStream_t st = (hipStream_t)stream;
     if (upload_sync(st, ws.clips, h) != hipSuccess) return fail(-6, "ref_frontend metadata upload");
 
     hipLaunchKernelGGL(ref_reduce_kernel, dim3((unsigned)(parts + range_blocks)), dim3(256), 0, st, ws.clips, n, (int)parts, wave_dev, ws.partials,

@@ -459,7 +459,7 @@ int f5hip_mel_spectrogram_bigvgan(int32_t batch, int32_t n_samples, const float*
 }
 
 // ---- both front-ends for n clips of their own lengths, one launch (F5HipModel.prepare_voices: the reference mels of a batch's new voices)
-struct MelRaggedWorkspace { MelItem* items = nullptr; size_t cap_items = 0; };
+struct MelRaggedWorkspace { MelItem* items = nullptr; size_t cap_items = 0; WorkspaceUse use; };
 
 int f5hip_mel_spectrogram_ragged(int32_t n, const int32_t* n_samples, const float* const* wave_dev, float* mel_dev, int32_t n_fft, int32_t hop_length,
                                  int32_t n_mels, int32_t sample_rate, int32_t variant, void* stream) {
@@ -483,8 +483,10 @@ int f5hip_mel_spectrogram_ragged(int32_t n, const int32_t* n_samples, const floa
     CK(mel_tables(t, variant ? slaney_filterbank : htk_filterbank, n_fft, n_mels, sample_rate));
     MelRaggedWorkspace* const ws = device_workspace<MelRaggedWorkspace>("mel_spectrogram_ragged");
     if (!ws) return -6;
-    CK(dev_reserve(&ws->items, &ws->cap_items, (size_t)n, "mel_spectrogram_ragged clips"));
     hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws->use, st);
+    CK(turn.rc);
+    CK(dev_reserve(&ws->items, &ws->cap_items, (size_t)n, "mel_spectrogram_ragged clips"));
     if (upload_sync(st, ws->items, h) != hipSuccess) return fail(-6, "mel_spectrogram_ragged metadata upload");
     prof_begin(PROF_OTHER, st);
     hipLaunchKernelGGL(mel_frame_ragged_kernel, dim3((unsigned)rows), dim3(256), 0, st, ws->items, n, hop_length, n_mels, t.window, t.twiddle, t.fb, mel_dev,

@@ -229,18 +229,24 @@ struct FpWorkspace {
     FpMark* marks = nullptr; size_t cap_marks = 0;
     FpSynth* synth = nullptr; size_t cap_synth = 0;
     int* counts = nullptr; size_t cap_counts = 0;
+    WorkspaceUse use;
 };
 
 int f5hip_wave_prosody_formants_launches(void) { return 3; }
+
+static int wave_formant_launches(const std::vector<PrKept>& kept, const short* mid, const int32_t* len_dev, int16_t* out_dev, void* stream);
 
 int f5hip_wave_prosody_formants(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
                                 const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const uint8_t* keep_formants,
                                 const float* taps_dev, int16_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, void* stream) {
     if (!keep_formants) return fail(-1, "wave_prosody: bad argument");
     std::vector<PrKept> kept;
-    const short* mid = nullptr;
-    CK(wave_prosody_run(n, pcm_dev, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, keep_formants, taps_dev, out_dev, out_off, out_len_dev, &kept,
-                        &mid, stream));
+    // (the three launches below read the stretched PCM of wave_prosody's workspace: they run inside its turn, and inside their own)
+    return wave_prosody_run(n, pcm_dev, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, keep_formants, taps_dev, out_dev, out_off, out_len_dev, &kept,
+                            stream, [&](const short* mid) { return wave_formant_launches(kept, mid, len_dev, out_dev, stream); });
+}
+
+static int wave_formant_launches(const std::vector<PrKept>& kept, const short* mid, const int32_t* len_dev, int16_t* out_dev, void* stream) {
     if (kept.empty()) return 0;
     std::vector<FpReq> h;
     long long ptiles = 0, frames = 0, nmarks = 0, nsynth = 0, otiles = 0;
@@ -257,12 +263,14 @@ int f5hip_wave_prosody_formants(int32_t n, const int16_t* pcm_dev, const int64_t
     FpWorkspace* const wsp = device_workspace<FpWorkspace>("wave_prosody_formants");
     if (!wsp) return -6;
     FpWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(dev_reserve(&ws.reqs, &ws.cap_reqs, h.size(), "wave_prosody_formants requests"));
     CK(dev_reserve(&ws.track, &ws.cap_track, (size_t)std::max<long long>(frames, 1), "wave_prosody_formants track"));
     CK(dev_reserve(&ws.marks, &ws.cap_marks, (size_t)std::max<long long>(nmarks, 1), "wave_prosody_formants analysis marks"));
     CK(dev_reserve(&ws.synth, &ws.cap_synth, (size_t)std::max<long long>(nsynth, 1), "wave_prosody_formants synthesis marks"));
     CK(dev_reserve(&ws.counts, &ws.cap_counts, 2 * h.size(), "wave_prosody_formants counts"));
-    hipStream_t st = (hipStream_t)stream;
     if (upload_sync(st, ws.reqs, h) != hipSuccess) return fail(-6, "wave_prosody_formants metadata upload");
     const int nf = (int)h.size();
     // (a call whose flagged requests are all empty keeps one block a launch: it finds its tile past the length and leaves)

@@ -173,6 +173,7 @@ __global__ __launch_bounds__(256) void wave_mark_id_add_kernel(const WmReq* __re
 }
 
 struct WmWorkspace {
+    WorkspaceUse use;
     WmReq* reqs = nullptr; size_t cap_reqs = 0;
     int* A = nullptr; size_t cap_A = 0;
     HostStage stage;
@@ -221,9 +222,11 @@ static int wave_mark_call(const char* op, int32_t n, int16_t* pcm_dev, const int
     WmWorkspace* const wsp = device_workspace<WmWorkspace>("wave_mark");
     if (!wsp) return -6;
     WmWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(dev_reserve(&ws.reqs, &ws.cap_reqs, h.size(), "wave_mark requests"));
     CK(dev_reserve(&ws.A, &ws.cap_A, (size_t)(tiles * kWmTileBlocks), "wave_mark block sums"));
-    hipStream_t st = (hipStream_t)stream;
     CK(ws.stage.upload(ws.reqs, h.data(), sizeof(WmReq) * h.size(), st));   // pinned staging, queued on `stream`: no wait
     const int nf = (int)h.size();
     hipLaunchKernelGGL(wave_mark_sum_kernel, dim3((unsigned)tiles), dim3(256), 0, st, ws.reqs, nf, (const short*)pcm_dev, (const int*)len_dev, ws.A);
@@ -437,6 +440,7 @@ __global__ __launch_bounds__(256) void watermark_id_score_kernel(const RdClip* _
 }
 
 struct WdWorkspace {
+    WorkspaceUse use;
     RdClip* clips = nullptr; size_t cap_clips = 0;
     float* fw = nullptr; size_t cap_fw = 0;
     float* Z = nullptr; size_t cap_Z = 0;
@@ -445,9 +449,11 @@ struct WdWorkspace {
 };
 
 // The three launches f5hip_watermark_detect and f5hip_watermark_read_ids share, under the caller's name: the call's checks, then frame, fold
-// and correlate over n_rows carrier rows -> ws.r [n][n_rows][P], ws.clips
+// and correlate over n_rows carrier rows -> ws.r [n][n_rows][P], ws.clips; then score(ws), the caller's own launch over them (an int, 0 =
+// success), inside the same turn of the workspace
+template <typename Score>
 static int wd_correlate(const char* op, int32_t n, const float* wave_dev, const int64_t* offset, const int32_t* n_samples, int32_t n_rows,
-                        const int16_t* carriers_dev, const float* out_dev, hipStream_t st, WdWorkspace** out_ws) {
+                        const int16_t* carriers_dev, const float* out_dev, hipStream_t st, Score score) {
     std::vector<RdClip> h;
     long long rows = 0, total = 0;
     int bad = 0;
@@ -468,6 +474,8 @@ static int wd_correlate(const char* op, int32_t n, const float* wave_dev, const 
     WdWorkspace* const wsp = device_workspace<WdWorkspace>("watermark_detect");
     if (!tables || !wsp) return -6;
     WdWorkspace& ws = *wsp;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(rd_tables(*tables));
     CK(dev_reserve(&ws.clips, &ws.cap_clips, (size_t)n, "watermark_detect clips"));
     CK(dev_reserve(&ws.fw, &ws.cap_fw, (size_t)rows * kRdNfft, "watermark_detect frames"));
@@ -482,18 +490,18 @@ static int wd_correlate(const char* op, int32_t n, const float* wave_dev, const 
     hipLaunchKernelGGL(wd_corr_kernel, dim3(kWmPeriod / kWdOffTile, (unsigned)n_rows, (unsigned)((n + kWdGroup - 1) / kWdGroup)), dim3(256), 0, st, n,
                        n_rows, (const float*)ws.Z, (const short*)carriers_dev, ws.r);
     CKL("wd_corr");
-    *out_ws = wsp;
-    return 0;
+    return score(ws);
 }
 
 int f5hip_watermark_detect(int32_t n, const float* wave_dev, const int64_t* offset, const int32_t* n_samples, int32_t n_keys,
                            const int16_t* carriers_dev, float* scores_dev, void* stream) {
     if (n_keys < 1 || n_keys > kWmKeysMax) return fail(-1, "watermark_detect: 1 .. %d keys in a call (got %d)", kWmKeysMax, n_keys);
     hipStream_t st = (hipStream_t)stream;
-    WdWorkspace* ws = nullptr;
-    CK(wd_correlate("watermark_detect", n, wave_dev, offset, n_samples, n_keys, carriers_dev, scores_dev, st, &ws));
-    hipLaunchKernelGGL(wd_score_kernel, dim3((unsigned)(n * n_keys)), dim3(256), 0, st, ws->clips, n_keys, (const float*)ws->r, scores_dev);
-    CKL("wd_score");
+    CK(wd_correlate("watermark_detect", n, wave_dev, offset, n_samples, n_keys, carriers_dev, scores_dev, st, [&](WdWorkspace& ws) {
+        hipLaunchKernelGGL(wd_score_kernel, dim3((unsigned)(n * n_keys)), dim3(256), 0, st, ws.clips, n_keys, (const float*)ws.r, scores_dev);
+        CKL("wd_score");
+        return 0;
+    }));
     g_counters[CNT_WATERMARK_DETECT_LAUNCHES] += 4;
     g_counters[CNT_WATERMARK_DETECT_CLIPS] += n;
     return 0;
@@ -505,10 +513,11 @@ int f5hip_watermark_read_ids(int32_t n, const float* wave_dev, const int64_t* of
                              const int16_t* carriers_dev, float* rows_dev, void* stream) {
     if (n_keys < 1 || n_keys > kWdIdKeysMax) return fail(-1, "watermark_read_ids: 1 .. %d keys in a call (got %d)", kWdIdKeysMax, n_keys);
     hipStream_t st = (hipStream_t)stream;
-    WdWorkspace* ws = nullptr;
-    CK(wd_correlate("watermark_read_ids", n, wave_dev, offset, n_samples, n_keys * kWmTagRows, carriers_dev, rows_dev, st, &ws));
-    hipLaunchKernelGGL(watermark_id_score_kernel, dim3((unsigned)(n * n_keys)), dim3(256), 0, st, ws->clips, n_keys, (const float*)ws->r, rows_dev);
-    CKL("watermark_id_score");
+    CK(wd_correlate("watermark_read_ids", n, wave_dev, offset, n_samples, n_keys * kWmTagRows, carriers_dev, rows_dev, st, [&](WdWorkspace& ws) {
+        hipLaunchKernelGGL(watermark_id_score_kernel, dim3((unsigned)(n * n_keys)), dim3(256), 0, st, ws.clips, n_keys, (const float*)ws.r, rows_dev);
+        CKL("watermark_id_score");
+        return 0;
+    }));
     g_counters[CNT_WATERMARK_READ_IDS_LAUNCHES] += 4;
     g_counters[CNT_WATERMARK_READ_IDS_CLIPS] += n;
     return 0;
@@ -543,6 +552,7 @@ __global__ __launch_bounds__(256) void ws_range_fold_kernel(const RdClip* __rest
 }
 
 struct WsWorkspace {
+    WorkspaceUse use;
     RdClip* table = nullptr; size_t cap_table = 0;                       // entry 0: the recording (wd_frame_kernel's clip), then the ranges
     HostStage stage;
 };
@@ -578,6 +588,9 @@ int f5hip_watermark_scan(const float* wave_dev, int64_t n_samples, int32_t n_ran
     WdWorkspace& wd = *wdp;
     WsWorkspace& ws = *wsp;
     hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn_wd(wd.use, st), turn(ws.use, st);
+    CK(turn_wd.rc);
+    CK(turn.rc);
     CK(rd_tables(*tables));
     CK(dev_reserve(&ws.table, &ws.cap_table, h.size(), "watermark_scan ranges"));
     CK(dev_reserve(&wd.fw, &wd.cap_fw, (size_t)F * kRdNfft, "watermark_scan frames"));

@@ -297,6 +297,7 @@ struct WfWorkspace {
     int2* buckets = nullptr; size_t cap_buckets = 0;
     WfRange* ranges = nullptr; size_t cap_ranges = 0;
     int* nranges = nullptr; size_t cap_nranges = 0;
+    WorkspaceUse use;
 };
 
 int f5hip_wave_finish_joins(int32_t n, const int32_t* chunks_per_request, const float* const* chunk_dev, const int32_t* chunk_len, int32_t fade,
@@ -358,6 +359,9 @@ int f5hip_wave_finish_joins(int32_t n, const int32_t* chunks_per_request, const 
     WfWorkspace* const wsp = device_workspace<WfWorkspace>("wave_finish");
     if (!wsp) return -6;
     WfWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(dev_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_finish requests"));
     CK(dev_reserve(&ws.chunks, &ws.cap_chunks, hc.size(), "wave_finish chunks"));
     if (!hf.empty()) {
@@ -369,7 +373,6 @@ int f5hip_wave_finish_joins(int32_t n, const int32_t* chunks_per_request, const 
         CK(dev_reserve(&ws.ranges, &ws.cap_ranges, (size_t)nrange, "wave_finish ranges"));
         CK(dev_reserve(&ws.nranges, &ws.cap_nranges, (size_t)n, "wave_finish range counts"));
     }
-    hipStream_t st = (hipStream_t)stream;
     const hipError_t up = hf.empty() ? upload_sync(st, ws.reqs, h, ws.chunks, hc) : upload_sync(st, ws.reqs, h, ws.chunks, hc, ws.flagged, hf);
     if (up != hipSuccess) return fail(-6, "wave_finish metadata upload");
 
@@ -494,7 +497,7 @@ __global__ __launch_bounds__(256) void wave_encode_kernel(const WeReq* __restric
     we_tile_body<RESAMPLE>(we_sm, pcm + q.in_off, len, n_out, tile, taps, of, nf, width, L, tq, enc, out + q.out_off);
 }
 
-struct WeWorkspace { WeReq* reqs = nullptr; size_t cap_reqs = 0; };
+struct WeWorkspace { WeReq* reqs = nullptr; size_t cap_reqs = 0; WorkspaceUse use; };
 
 // (tq, LDS bytes) of a rate pair; tq = 0: window, output tile and tap table do not fit the LDS together
 struct WeTile { int tq, lds; };
@@ -538,11 +541,13 @@ int f5hip_wave_encode(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, 
     WeWorkspace* const wsp = device_workspace<WeWorkspace>("wave_encode");
     if (!wsp) return -6;
     WeWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(dev_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_encode requests"));
     static unsigned lds_attr_done = 0;
     if (t.lds > 64 * 1024 && f5_set_lds_attr((const void*)wave_encode_kernel<true>, kLdsMax, lds_attr_done) != hipSuccess)
         return fail(-7, "wave_encode: LDS opt-in");
-    hipStream_t st = (hipStream_t)stream;
     if (upload_sync(st, ws.reqs, h) != hipSuccess) return fail(-6, "wave_encode metadata upload");
 #define F5_WE_LAUNCH(RESAMPLE)                                                                                                                 \
     hipLaunchKernelGGL(wave_encode_kernel<RESAMPLE>, dim3((unsigned)tiles), dim3(256), t.lds, st, ws.reqs, n, (const short*)pcm_dev, (const int*)len_dev, \
@@ -1065,6 +1070,7 @@ struct FlWorkspace {
     unsigned* scratch = nullptr; size_t cap_scratch = 0;
     int* sizes = nullptr; size_t cap_sizes = 0;
     unsigned* frame_off = nullptr; size_t cap_frame_off = 0;
+    WorkspaceUse use;
 };
 
 static int fl_rate_code(int rate) {
@@ -1111,13 +1117,15 @@ int f5hip_wave_flac_levels(int32_t n, const int16_t* pcm_dev, const int64_t* in_
     FlWorkspace* const wsp = device_workspace<FlWorkspace>("wave_flac");
     if (!wsp) return -6;
     FlWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(dev_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_flac requests"));
     if (frames) {
         CK(dev_reserve(&ws.scratch, &ws.cap_scratch, (size_t)frames * kFlWords, "wave_flac frames"));
         CK(dev_reserve(&ws.sizes, &ws.cap_sizes, (size_t)frames, "wave_flac frame sizes"));
         CK(dev_reserve(&ws.frame_off, &ws.cap_frame_off, (size_t)frames, "wave_flac frame offsets"));
     }
-    hipStream_t st = (hipStream_t)stream;
     if (upload_sync(st, ws.reqs, h) != hipSuccess) return fail(-6, "wave_flac metadata upload");
     if (frames) {
         // (the level-0 instantiation unless some request asks for level 1)
@@ -1341,6 +1349,7 @@ struct LdWorkspace {
     LdReq* reqs = nullptr; size_t cap_reqs = 0;
     long long* sub = nullptr; size_t cap_sub = 0;
     int* peaks = nullptr; size_t cap_peaks = 0;
+    WorkspaceUse use;
 };
 
 int f5hip_wave_loudness_tile(void) { return kLdTile; }
@@ -1367,10 +1376,12 @@ int f5hip_wave_loudness(int32_t n, int16_t* pcm_dev, const int64_t* in_off, cons
     LdWorkspace* const wsp = device_workspace<LdWorkspace>("wave_loudness");
     if (!wsp) return -6;
     LdWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(dev_reserve(&ws.reqs, &ws.cap_reqs, h.size(), "wave_loudness requests"));
     CK(dev_reserve(&ws.sub, &ws.cap_sub, (size_t)(2 * tiles), "wave_loudness sub-block sums"));
     CK(dev_reserve(&ws.peaks, &ws.cap_peaks, (size_t)tiles, "wave_loudness peaks"));
-    hipStream_t st = (hipStream_t)stream;
     if (upload_sync(st, ws.reqs, h) != hipSuccess) return fail(-6, "wave_loudness metadata upload");
     const int nf = (int)h.size();
     hipLaunchKernelGGL(wave_kweight_kernel, dim3((unsigned)tiles), dim3(kLdThreads), 0, st, ws.reqs, nf, (const short*)pcm_dev, (const int*)len_dev, ws.sub,
@@ -1533,6 +1544,7 @@ struct PrWorkspace {
     PrReq* reqs = nullptr; size_t cap_reqs = 0;
     PrReq* pitched = nullptr; size_t cap_pitched = 0;
     short* mid = nullptr; size_t cap_mid = 0;
+    WorkspaceUse use;
 };
 
 // floats of a pitch step's tap table in the device table (a multiple of 4: every table starts on a 16-byte boundary)
@@ -1561,11 +1573,12 @@ struct PrKept {
 };
 
 // f5hip_wave_prosody, and with `keep` (per request; null: nobody) the first part of f5hip_wave_prosody_formants: a flagged request is
-// stretched by its (P, Q) into the workspace and listed in `kept`; *mid_out is the workspace's stretched PCM
+// stretched by its (P, Q) into the workspace and listed in `kept`; then then(mid), the caller's own launches over the workspace's stretched
+// PCM (an int, 0 = success), inside the same turn of the workspace
+template <typename Then>
 static int wave_prosody_run(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
                             const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const uint8_t* keep, const float* taps_dev,
-                            int16_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, std::vector<PrKept>* kept, const short** mid_out,
-                            void* stream) {
+                            int16_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, std::vector<PrKept>* kept, void* stream, Then then) {
     if (n < 1 || !pcm_dev || !in_off || !max_len || !stretch_p || !stretch_q || !pitch || !out_dev || !out_off || !out_len_dev)
         return fail(-1, "wave_prosody: bad argument");
     if ((reinterpret_cast<uintptr_t>(pcm_dev) & 1) || (reinterpret_cast<uintptr_t>(len_dev) & 3) || (reinterpret_cast<uintptr_t>(taps_dev) & 15) ||
@@ -1616,6 +1629,9 @@ static int wave_prosody_run(int32_t n, const int16_t* pcm_dev, const int64_t* in
     PrWorkspace* const wsp = device_workspace<PrWorkspace>("wave_prosody");
     if (!wsp) return -6;
     PrWorkspace& ws = *wsp;
+    hipStream_t st = (hipStream_t)stream;
+    WorkspaceTurn turn(ws.use, st);
+    CK(turn.rc);
     CK(dev_reserve(&ws.reqs, &ws.cap_reqs, (size_t)n, "wave_prosody requests"));
     if (!hp.empty() || (kept && !kept->empty())) CK(dev_reserve(&ws.mid, &ws.cap_mid, (size_t)std::max<long long>(mid, 8), "wave_prosody stretched PCM"));
     if (!hp.empty()) {
@@ -1624,7 +1640,6 @@ static int wave_prosody_run(int32_t n, const int16_t* pcm_dev, const int64_t* in
         if (lds > 64 * 1024 && f5_set_lds_attr((const void*)wave_pitch_kernel, kLdsMax, lds_attr_done) != hipSuccess)
             return fail(-7, "wave_prosody: LDS opt-in");
     }
-    hipStream_t st = (hipStream_t)stream;
     const hipError_t up = hp.empty() ? upload_sync(st, ws.reqs, h) : upload_sync(st, ws.reqs, h, ws.pitched, hp);
     if (up != hipSuccess) return fail(-6, "wave_prosody metadata upload");
     hipLaunchKernelGGL(wave_wsola_kernel, dim3((unsigned)n), dim3(kPrThreads), 0, st, ws.reqs, (const short*)pcm_dev, (const int*)len_dev, (short*)out_dev,
@@ -1638,13 +1653,12 @@ static int wave_prosody_run(int32_t n, const int16_t* pcm_dev, const int64_t* in
         g_counters[CNT_WAVE_PROSODY_LAUNCHES]++;
     }
     g_counters[CNT_WAVE_PROSODY_REQUESTS] += changed;
-    if (mid_out) *mid_out = ws.mid;
-    return 0;
+    return then((const short*)ws.mid);
 }
 
 int f5hip_wave_prosody(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
                        const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const float* taps_dev, int16_t* out_dev,
                        const int64_t* out_off, int32_t* out_len_dev, void* stream) {
     return wave_prosody_run(n, pcm_dev, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, nullptr, taps_dev, out_dev, out_off, out_len_dev, nullptr,
-                            nullptr, stream);
+                            stream, [](const short*) { return 0; });
 }
