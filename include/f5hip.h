@@ -729,6 +729,27 @@ int f5hip_wave_prosody_formants(int32_t n, const int16_t* pcm_dev, const int64_t
 /* Launches f5hip_wave_prosody_formants adds for a call with a flagged request (3).  For tests. */
 int f5hip_wave_prosody_formants_launches(void);
 
+/* f5hip_wave_prosody_formants with a per-request formant step: request i's spectral envelope moves by formant[i] semitones on its own, bit
+ * for bit wave_codec.shift_pcm16(pcm, tempo, PitchTag(pitch[i], formant[i])) = wsola_pcm16 by the request's (P, Q) -- the tempo's stretch
+ * alone -- and then wave_codec.psola_shape_pcm16, written down above that function (csrc/wave_formant_core.h holds its rules;
+ * tools/wave_shape_check.cpp runs them on the CPU under sanitizers).  Track and analysis marks as above; the synthesis marks by the pitch's
+ * p / q, (1, 1) without a pitch; then, (P, Q) the ratio of the formant step, Pg = P for a voiced mark and Q for an unvoiced one:
+ *   grain        outputs u + k with |k| Pg <= T_i Q: w = M[(|k| Pg 1024) / (Q T_i)]; k Pg = c Q + r (floor): v = xt[a_i + c] (Q - r) +
+ *                xt[a_i + c + 1] r; num += w v, den += w Q
+ *   output       y[j] = clip(floor((2 num + den) / (2 den))), y[j] = x[j] where den = 0.  m samples
+ *   formant      host int32 [n]: -6 .. 6, at most 6 semitones from pitch[i]; 0: the request is what f5hip_wave_prosody_formants makes of it.
+ *                A request with a step is kept whatever keep_formants[i] says and may have no pitch
+ * A call without a step launches what f5hip_wave_prosody_formants launches.  Otherwise the same THREE launches behind the WSOLA launch, the
+ * third being wave_shape_kernel for every kept request of the call: one block per 2048 outputs stages their source window, xt[j0 - 568,
+ * j0 + 2616), in LDS once and the at most 97 marks around the tile as grains; a thread gathers 8 consecutive outputs, two divisions per
+ * grain and run, the source split and the window index stepped per output; a block of a request without a step runs wave_psola_kernel's
+ * tile.  No atomics, no accumulator buffer, no host sync; a request's bytes depend on that request alone (the same counters).
+ * Refused before the first launch: what f5hip_wave_prosody_formants refuses, a null formant, a step outside -6 .. 6 or more than 6
+ * semitones from the pitch. */
+int f5hip_wave_prosody_shape(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
+                             const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const uint8_t* keep_formants,
+                             const int32_t* formant, const float* taps_dev, int16_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, void* stream);
+
 /* FLAC in: n native FLAC streams (RFC 9639) -- uploaded reference clips and recordings, which the reference reads with torchaudio.load
  * (F/infer/utils_infer.py:376) -- packed at arbitrary byte offsets in one device buffer -> each stream's samples as int32 planes
  * [channels, total], bit for bit wave_codec.read_flac, which defines the format accepted: every subframe type, LPC order 1 .. 32, both Rice

@@ -23,6 +23,7 @@
 //   torch.ops.f5hip.wave_loudness(pcm, in_off, max_len, len_dev?, gain_k) -> Tensor stats int64 [n, 4]; pcm is normalised in place
 //   torch.ops.f5hip.wave_prosody(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, taps?) -> (Tensor pcm int16, Tensor lengths int32, Tensor offsets int64 host, Tensor bounds int32 host)
 //   torch.ops.f5hip.wave_prosody_formants(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, keep_formants, taps?) -> the same four
+//   torch.ops.f5hip.wave_prosody_shape(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, keep_formants, formant, taps?) -> the same four
 //   torch.ops.f5hip.ref_denoise(wave, offset, n_samples) -> ()   the flagged clips of wave (f5hip_ref_frontend's packed output) are denoised in place
 //   torch.ops.f5hip.wave_mark(pcm, in_off, max_len, len_dev?, key_index, carriers?) -> ()   the flagged requests of pcm get their key's provenance mark in place
 //   torch.ops.f5hip.ref_assess(raw, raw_offset, channels, raw_len, wave, offset, n_samples) -> Tensor rows int64 [n, 10]: the reference-clip report
@@ -595,11 +596,12 @@ at::Tensor wave_loudness(at::Tensor pcm, const at::Tensor& in_off, const at::Ten
 // when a request has a pitch -> (out int16 device: request i's samples at out_off[i]; out_len [n] int32 device; out_off [n] int64 host, each
 // a multiple of 8; bounds [n] int32 host: the length that max_len[i] gives)
 // keep: null for wave_prosody; wave_prosody_formants' uint8 [n] host flags (a flagged request keeps its formants: no resampler, the length
-// of its stretch alone)
+// of its stretch alone); formant: null, or wave_prosody_shape's int32 [n] host steps beside keep (a request with a step is kept too)
 static std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody_call(const at::Tensor& pcm, const at::Tensor& in_off, const at::Tensor& max_len,
                                                                                    const c10::optional<at::Tensor>& len_dev, const at::Tensor& stretch_p,
                                                                                    const at::Tensor& stretch_q, const at::Tensor& pitch,
-                                                                                   const at::Tensor* keep, const c10::optional<at::Tensor>& taps) {
+                                                                                   const at::Tensor* keep, const at::Tensor* formant,
+                                                                                   const c10::optional<at::Tensor>& taps) {
     const PcmRequests rq = check_pcm_requests("wave_prosody", pcm, in_off, max_len, len_dev, false);
     const int64_t n = rq.n;
     const int32_t* ml = rq.ml;
@@ -616,6 +618,12 @@ static std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody_c
         TORCH_CHECK(keep->numel() == n, "f5hip::wave_prosody: keep_formants needs one value per request");
         kp = keep->data_ptr<uint8_t>();
     }
+    const int32_t* fm = nullptr;
+    if (formant) {
+        check_host(*formant, at::kInt, "formant");
+        TORCH_CHECK(keep && formant->numel() == n, "f5hip::wave_prosody: formant needs one value per request, beside keep_formants");
+        fm = formant->data_ptr<int32_t>();
+    }
     at::Tensor out_off = at::empty({n}, at::TensorOptions().dtype(at::kLong)), bounds = at::empty({n}, at::TensorOptions().dtype(at::kInt));
     int64_t* oo = out_off.data_ptr<int64_t>();
     int32_t* bd = bounds.data_ptr<int32_t>();
@@ -626,7 +634,11 @@ static std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody_c
                     ": positive terms up to 2^20 and a ratio from 1/2 to 2");
         TORCH_CHECK(pt[i] >= -kPrPitchMax && pt[i] <= kPrPitchMax, "f5hip::wave_prosody: request ", i, " has a pitch of ", pt[i], " semitones (-6 to 6)");
         int64_t m = pr_geom(ml[i], sp[i], sq[i]).m;
-        if (kp && kp[i]) {
+        if (fm && fm[i]) {
+            TORCH_CHECK(fm[i] >= -kPrPitchMax && fm[i] <= kPrPitchMax && fm[i] - pt[i] <= kPrPitchMax && pt[i] - fm[i] <= kPrPitchMax,
+                        "f5hip::wave_prosody: request ", i, " has a formant step of ", fm[i], " semitones beside a pitch of ", pt[i],
+                        " (-6 to 6, at most 6 apart)");
+        } else if (kp && kp[i]) {
             TORCH_CHECK(pt[i] != 0, "f5hip::wave_prosody: request ", i, " keeps its formants without a pitch");
         } else if (pt[i]) {
             int p, q;
@@ -648,11 +660,13 @@ static std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody_c
     at::Tensor out = at::empty({std::max<int64_t>(total, 8)}, pcm.options()).slice(0, 0, total);   // (a call of empty requests still has an address to give)
     at::Tensor out_len = at::empty({n}, pcm.options().dtype(at::kInt));
     const float* tp = pitched ? taps->data_ptr<float>() : (const float*)nullptr;
-    const int rc = kp ? f5hip_wave_prosody_formants((int32_t)n, src.base(), src.rel.data(), ml, rq.len_dev, sp, sq, pt, kp, tp, out.data_ptr<int16_t>(), oo,
+    const int rc = fm ? f5hip_wave_prosody_shape((int32_t)n, src.base(), src.rel.data(), ml, rq.len_dev, sp, sq, pt, kp, fm, tp, out.data_ptr<int16_t>(), oo,
+                                                 out_len.data_ptr<int32_t>(), stream_of(pcm))
+                 : kp ? f5hip_wave_prosody_formants((int32_t)n, src.base(), src.rel.data(), ml, rq.len_dev, sp, sq, pt, kp, tp, out.data_ptr<int16_t>(), oo,
                                                     out_len.data_ptr<int32_t>(), stream_of(pcm))
                       : f5hip_wave_prosody((int32_t)n, src.base(), src.rel.data(), ml, rq.len_dev, sp, sq, pt, tp, out.data_ptr<int16_t>(), oo,
                                            out_len.data_ptr<int32_t>(), stream_of(pcm));
-    TORCH_CHECK(rc == 0, kp ? "f5hip_wave_prosody_formants: " : "f5hip_wave_prosody: ", f5hip_last_error());
+    TORCH_CHECK(rc == 0, fm ? "f5hip_wave_prosody_shape: " : kp ? "f5hip_wave_prosody_formants: " : "f5hip_wave_prosody: ", f5hip_last_error());
     return {out, out_len, out_off, bounds};
 }
 
@@ -660,7 +674,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody(const at
                                                                         const c10::optional<at::Tensor>& len_dev, const at::Tensor& stretch_p,
                                                                         const at::Tensor& stretch_q, const at::Tensor& pitch,
                                                                         const c10::optional<at::Tensor>& taps) {
-    return wave_prosody_call(pcm, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, nullptr, taps);
+    return wave_prosody_call(pcm, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, nullptr, nullptr, taps);
 }
 
 // wave_prosody with keep_formants [n] uint8 host: a flagged request (it must have a pitch) keeps its spectral envelope (f5hip_wave_prosody_formants)
@@ -668,7 +682,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody_formants
                                                                                  const c10::optional<at::Tensor>& len_dev, const at::Tensor& stretch_p,
                                                                                  const at::Tensor& stretch_q, const at::Tensor& pitch,
                                                                                  const at::Tensor& keep_formants, const c10::optional<at::Tensor>& taps) {
-    return wave_prosody_call(pcm, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, &keep_formants, taps);
+    return wave_prosody_call(pcm, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, &keep_formants, nullptr, taps);
+}
+
+// wave_prosody_formants with formant [n] int32 host: a request with a step moves its spectral envelope on its own (f5hip_wave_prosody_shape)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody_shape(const at::Tensor& pcm, const at::Tensor& in_off, const at::Tensor& max_len,
+                                                                              const c10::optional<at::Tensor>& len_dev, const at::Tensor& stretch_p,
+                                                                              const at::Tensor& stretch_q, const at::Tensor& pitch,
+                                                                              const at::Tensor& keep_formants, const at::Tensor& formant,
+                                                                              const c10::optional<at::Tensor>& taps) {
+    return wave_prosody_call(pcm, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, &keep_formants, &formant, taps);
 }
 
 // wave: the contiguous 1-D fp32 device tensor that holds every clip (f5hip_ref_frontend's packed output), denoised IN PLACE; offset [n] int64
@@ -882,6 +905,8 @@ TORCH_LIBRARY(f5hip, m) {
           "(Tensor, Tensor, Tensor, Tensor)", &wave_prosody);
     m.def("wave_prosody_formants(Tensor pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor stretch_p, Tensor stretch_q, Tensor pitch, "
           "Tensor keep_formants, Tensor? taps) -> (Tensor, Tensor, Tensor, Tensor)", &wave_prosody_formants);
+    m.def("wave_prosody_shape(Tensor pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor stretch_p, Tensor stretch_q, Tensor pitch, "
+          "Tensor keep_formants, Tensor formant, Tensor? taps) -> (Tensor, Tensor, Tensor, Tensor)", &wave_prosody_shape);
     m.def("ref_denoise(Tensor(a!) wave, Tensor offset, Tensor n_samples) -> ()", &ref_denoise);
     m.def("wave_mark(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor key_index, Tensor? carriers) -> ()", &wave_mark);
     m.def("watermark_detect(Tensor wave, Tensor offset, Tensor n_samples, Tensor carriers) -> Tensor", &watermark_detect);

@@ -26,10 +26,14 @@
 #pragma once
 #include <stdint.h>
 
+#include "wave_prosody_core.h"
+
 #if defined(__HIPCC__)
 #define FP_HD __host__ __device__ inline
+#define FS_HD __host__ __device__ __forceinline__      // the gather: its sums stay in the caller's registers
 #else
 #define FP_HD inline
+#define FS_HD inline
 #endif
 
 constexpr int kFpHop = 120, kFpWin = 480, kFpLagMin = 48, kFpLagMax = 400;   // wave_codec.PSOLA_HOP, PSOLA_WINDOW, PSOLA_LAG_MIN, PSOLA_LAG_MAX
@@ -159,6 +163,107 @@ FP_HD int fp_output(const short* x, long long n, long long j, const FpGrain* g, 
         den += w;
     }
     if (den == 0) return fp_sample_at(x, n, j);
+    const long long a = 2 * num + den, b = 2 * den;
+    long long v = a / b;
+    if (a % b < 0) v--;                                                 // a floor division
+    return (int)(v < -32768 ? -32768 : v > 32767 ? 32767 : v);
+}
+
+// ---- The formant shift (wave_codec.psola_shape_pcm16, wave_formant.h wave_shape_kernel): the same track and marks, and a grain that is read
+// Pg / Q times faster than it is laid down.  (P, Q) is the request's formant ratio; Pg = P for a voiced mark and Pg = Q for an unvoiced one,
+// whose grain is then the plain one scaled by Q.  Per grain and output offset k with |k| Pg <= T Q:
+//   weight   w = M[(|k| Pg 1024) / (Q T)]
+//   source   k Pg = c Q + r (floor), v = xt[a + c] (Q - r) + xt[a + c + 1] r;  num += w v, den += w Q
+// Bounds:
+//   half     a grain reaches H = T Q / Pg <= 400 * 41 / 29 = kFsHalfMax outputs either way: the marks of a tile lie in a closed range of
+//            kFpOutTile + 2 kFsHalfMax positions, at least kFpMinStep apart: at most kFsTileGrains
+//   source   |a - u| < 400: u takes the nearest analysis mark, marks are at most 120 + 399 apart, u_0 = a_0, and behind the last mark u < n <=
+//            a + T.  c - k = floor(k (Pg - Q) / Q) and |k| <= T Q / Pg, so |c - k| <= 400 * 12 / 29 + 1 = kFsDrift.  Every index a + c and
+//            a + c + 1 of an output j lies in [j - kFsReach, j + kFsReach): a tile stages xt[j0 - kFsReach, j0 + kFpOutTile + kFsReach)
+//   weight   |k| Pg 1024 <= (H + 7) 46 * 1024 < 2^25 and Q T <= 46 * 400: unsigned 32-bit; the index is at most 1024 inside the grain
+//   blend    at most 2 kFsHalfMax / kFpMinStep + 1 = 35 grains a sample: |num| < 35 * 2^15 * (2^15 * 46) < 2^41, den < 2^26: 64-bit
+constexpr int kFsRatioP = 41, kFsRatioQ = 29;                                       // the widest formant ratio (6 semitones)
+constexpr int kFsHalfMax = kFpLagMax * kFsRatioP / kFsRatioQ;                       // 565
+constexpr int kFsTileGrains = (kFpOutTile + 2 * kFsHalfMax - 1) / kFpMinStep + 1;   // 97
+constexpr int kFsDrift = kFpLagMax * (kFsRatioP - kFsRatioQ) / kFsRatioQ + 2;       // 167
+constexpr int kFsReach = (kFpLagMax + kFsDrift + 1 + 7) & ~7;                       // 568: a multiple of 8, so the staged window starts on 16 bytes
+constexpr int kFsStage = kFpOutTile + 2 * kFsReach;                                 // 3184 samples of a tile's source window
+constexpr int kFsRun = 8;                                                           // consecutive outputs one thread gathers
+static_assert(kFsRatioP == kPrPitchP[kPrPitchMax - 1] && kFsRatioQ == kPrPitchQ[kPrPitchMax - 1], "wave_shape: the widest ratio is the table's last");
+static_assert(kFsHalfMax == 565 && kFsTileGrains == 97 && kFsReach % 8 == 0 && kFsStage % 8 == 0 && kFpOutTile % kFsRun == 0, "wave_shape geometry");
+static_assert((long long)(kFsHalfMax + kFsRun) * 46 * kFpTable < (1LL << 31) && 35LL * 46 << 30 < (1LL << 62), "wave_shape: the weight index in 32 bits");
+
+struct FsGrain {
+    int u, a;       // the synthesis mark; the analysis mark it reads
+    int H;          // outputs it reaches either way, T Q / Pg
+    int Pg, D;      // its read rate over Q; Q T, the divisor of the weight index
+    int wq, wr;     // Pg 1024 = wq D + wr: the step of the weight index per output
+    int pad_;
+};
+
+// whether (p, q) is one of the twelve ratios or (1, 1), the widest being 41 / 29: what bounds every table above
+FP_HD bool fs_ratio_ok(int P, int Q) { return P >= 1 && Q >= 1 && P <= 46 && Q <= 46 && P * kFsRatioQ <= Q * kFsRatioP && Q * kFsRatioQ <= P * kFsRatioP; }
+
+FS_HD FsGrain fs_grain(int u, int a, int T, bool voiced, int P, int Q) {
+    FsGrain g;
+    g.u = u; g.a = a; g.Pg = voiced ? P : Q;
+    g.H = T * Q / g.Pg;
+    if (a - u >= kFpLagMax || u - a >= kFpLagMax) g.H = -1;             // outside the bound kFsReach rests on (never, by the marks' rules above): the grain touches nothing, and no index leaves the staged window
+    g.D = Q * T;
+    g.wq = g.Pg * kFpTable / g.D;
+    g.wr = g.Pg * kFpTable - g.wq * g.D;
+    g.pad_ = 0;
+    return g;
+}
+
+// the marks [*m0, *m0 + count) that may touch the outputs [j0, j1): those with j0 - kFsHalfMax <= u <= j1 - 1 + kFsHalfMax
+FP_HD int fs_tile_marks(const FpSynth* s, int ns, long long j0, long long j1, int* m0) {
+    *m0 = fp_first_at_or_after(s, ns, j0 - kFsHalfMax);
+    const int count = fp_first_at_or_after(s, ns, j1 + kFsHalfMax) - *m0;
+    return count < kFsTileGrains ? count : kFsTileGrains;               // (the bound above: never more)
+}
+
+// the first sample of a tile's staged window, and xt there
+FP_HD long long fs_stage_base(long long j0) { return j0 - kFsReach; }
+FP_HD short fs_stage_sample(const short* x, long long n, long long pos) { return pos >= 0 && pos < n ? x[pos] : (short)0; }
+
+// grain g over the kFsRun consecutive outputs from j: num[e] += w v, den[e] += w Q.  `stage` holds xt from `base` (fs_stage_base of the
+// output's tile).  Two divisions for the run, at its first output; from there the source split (c, r) and the weight index (qi, ri) move by
+// their per-output steps, the index downwards while k < 0.
+FS_HD void fs_gather(const FsGrain& g, int Q, long long j, const short* stage, long long base, const unsigned short* M, long long* num, long long* den) {
+    int k = (int)(j - g.u);
+    if (g.H < 0 || k > g.H || k + kFsRun - 1 < -g.H) return;          // (H < 0: fs_grain's refusal -- no index is formed)
+    const int t = k * g.Pg;
+    int c = t / Q, r = t - c * Q;
+    if (r < 0) { r += Q; c--; }                                         // a floor division
+    const int dc = g.Pg >= Q ? 1 : 0, dr = g.Pg - dc * Q;               // Pg / Q lies in [29 / 41, 41 / 29]: the split moves by dc, then by r's carry
+    const unsigned ak = (unsigned)(k < 0 ? -k : k), wn = ak * (unsigned)g.Pg * kFpTable, D = (unsigned)g.D;
+    unsigned qi = wn / D, ri = wn - qi * D;
+    int at = (int)(g.a + c - base);
+#pragma unroll
+    for (int e = 0; e < kFsRun; e++) {
+        if (k >= -g.H && k <= g.H) {
+            const long long w = M[qi];
+            const int v = stage[at] * (Q - r) + stage[at + 1] * r;
+            num[e] += w * v;
+            den[e] += w * Q;
+        }
+        if (k < 0) {
+            if (ri < (unsigned)g.wr) { ri += D; qi--; }
+            ri -= (unsigned)g.wr; qi -= (unsigned)g.wq;
+        } else {
+            qi += (unsigned)g.wq; ri += (unsigned)g.wr;
+            if (ri >= D) { ri -= D; qi++; }
+        }
+        k++;
+        at += dc; r += dr;
+        if (r >= Q) { r -= Q; at++; }
+    }
+}
+
+// the rounded divide of one output; `own` is x[j], what an uncovered sample keeps
+FS_HD int fs_finish(long long num, long long den, int own) {
+    if (den == 0) return own;
     const long long a = 2 * num + den, b = 2 * den;
     long long v = a / b;
     if (a % b < 0) v--;                                                 // a floor division

@@ -1569,16 +1569,17 @@ int64_t f5hip_wave_prosody_tap_offset(int32_t pitch) {
 // a request that keeps its formants, as the WSOLA launch left it: what wave_formant.h's three launches start from
 struct PrKept {
     long long mid_off, out_off;
-    int cap, req, P, Q, pitch;
+    int cap, req, P, Q, pitch, formant;
 };
 
 // f5hip_wave_prosody, and with `keep` (per request; null: nobody) the first part of f5hip_wave_prosody_formants: a flagged request is
 // stretched by its (P, Q) into the workspace and listed in `kept`; then then(mid), the caller's own launches over the workspace's stretched
-// PCM (an int, 0 = success), inside the same turn of the workspace
+// PCM (an int, 0 = success), inside the same turn of the workspace.  `formant` (per request; null: nobody) is f5hip_wave_prosody_shape's: a
+// request with a formant step is kept like a flagged one, with or without a pitch
 template <typename Then>
 static int wave_prosody_run(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
-                            const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const uint8_t* keep, const float* taps_dev,
-                            int16_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, std::vector<PrKept>* kept, void* stream, Then then) {
+                            const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const uint8_t* keep, const int32_t* formant,
+                            const float* taps_dev, int16_t* out_dev, const int64_t* out_off, int32_t* out_len_dev, std::vector<PrKept>* kept, void* stream, Then then) {
     if (n < 1 || !pcm_dev || !in_off || !max_len || !stretch_p || !stretch_q || !pitch || !out_dev || !out_off || !out_len_dev)
         return fail(-1, "wave_prosody: bad argument");
     if ((reinterpret_cast<uintptr_t>(pcm_dev) & 1) || (reinterpret_cast<uintptr_t>(len_dev) & 3) || (reinterpret_cast<uintptr_t>(taps_dev) & 15) ||
@@ -1600,11 +1601,15 @@ static int wave_prosody_run(int32_t n, const int16_t* pcm_dev, const int64_t* in
         q.in_off = in_off[i]; q.out_off = out_off[i]; q.cap = max_len[i]; q.req = i; q.P = stretch_p[i]; q.Q = stretch_q[i];
         long long m = pr_geom(max_len[i], q.P, q.Q).m;
         if (m > 2147483647LL) return fail(-1, "wave_prosody: the call exceeds 2^31 - 1 samples in or out");
-        if (keep && keep[i]) {
-            if (!pitch[i]) return fail(-1, "wave_prosody: request %d keeps its formants without a pitch", i);
+        const int shape = formant ? formant[i] : 0;
+        if (shape < -kPrPitchMax || shape > kPrPitchMax) return fail(-1, "wave_prosody: request %d has a formant step of %d semitones (-6 to 6)", i, shape);
+        if (shape && (shape - pitch[i] > kPrPitchMax || pitch[i] - shape > kPrPitchMax))
+            return fail(-1, "wave_prosody: request %d moves its formants by %d beside a pitch of %d: more than 6 semitones apart", i, shape, pitch[i]);
+        if ((keep && keep[i]) || shape) {
+            if (!pitch[i] && !shape) return fail(-1, "wave_prosody: request %d keeps its formants without a pitch", i);
             q.keep = 1; q.mid_off = mid;
             mid += (m + 7) & ~7LL;
-            kept->push_back(PrKept{q.mid_off, q.out_off, q.cap, i, q.P, q.Q, pitch[i]});
+            kept->push_back(PrKept{q.mid_off, q.out_off, q.cap, i, q.P, q.Q, pitch[i], shape});
         } else if (pitch[i]) {
             if (!taps_dev) return fail(-1, "wave_prosody: request %d has a pitch: the call needs the tap table", i);
             int p, qq;
@@ -1621,7 +1626,7 @@ static int wave_prosody_run(int32_t n, const int16_t* pcm_dev, const int64_t* in
             lds = std::max(lds, t.lds);
             hp.push_back(q);
         }
-        changed += q.P != q.Q || pitch[i] != 0;
+        changed += q.P != q.Q || pitch[i] != 0 || shape != 0;
         total_in += max_len[i]; total_out += m;
         if (total_in > 2147483647LL || total_out > 2147483647LL || mid > 2147483647LL)
             return fail(-1, "wave_prosody: the call exceeds 2^31 - 1 samples in or out");
@@ -1659,6 +1664,6 @@ static int wave_prosody_run(int32_t n, const int16_t* pcm_dev, const int64_t* in
 int f5hip_wave_prosody(int32_t n, const int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
                        const int32_t* stretch_p, const int32_t* stretch_q, const int32_t* pitch, const float* taps_dev, int16_t* out_dev,
                        const int64_t* out_off, int32_t* out_len_dev, void* stream) {
-    return wave_prosody_run(n, pcm_dev, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, nullptr, taps_dev, out_dev, out_off, out_len_dev, nullptr,
+    return wave_prosody_run(n, pcm_dev, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, nullptr, nullptr, taps_dev, out_dev, out_off, out_len_dev, nullptr,
                             stream, [](const short*) { return 0; });
 }

@@ -42,6 +42,7 @@ from .wave_codec import (ALL_ENCODINGS, DELIVERY_OPTIONS, FLAC_BLOCK, FLAC_ENCOD
                          delivery_format, encode_flac, encode_g711, flac_crc8, flac_crc16, flac_stream_header, load_audio, load_wav, quantise_pcm16, read_flac,
                          rate_pair, request_flac_level, resample_pcm16, resample_sinc_hann, resample_taps, resampled_length)   # (handed on: every public name of wave_codec is infer.X too)
 from .wave_codec import FORMANT_OPTIONS, check_keep_formants, formant_stretch, psola_pcm16  # noqa: F401
+from .wave_codec import PITCH_FORMANT_SPAN, PitchTag, psola_shape_pcm16  # noqa: F401
 from .wave_codec import (PITCH_RANGE, PITCH_RATIOS, PROSODY_OPTIONS, WHOLE_WAVE_PROSODY, check_pitch, check_tempo, shift_pcm16,  # noqa: F401
                          shifted_length, wsola_pcm16)
 from .wave_codec import (WATERMARK_BAND, WATERMARK_BLOCK, WATERMARK_KEYS_MAX, WATERMARK_MAX_SAMPLES, WATERMARK_MIN_SAMPLES,  # noqa: F401
@@ -909,6 +910,8 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     carry the request's trace id too (`read_watermark` reads it back): still one mark call for the batch, tagged and untagged together.
     `keep_formants`: one bool or one per request (`check_keep_formants`; None: no): with it the request's
     `pitch` keeps the spectral envelope (`shift_pcm16(..., keep_formants=True)`); without a pitch it is refused.
+    A `pitch` of `{"semitones": s, "formant": f}` (or a `PitchTag`; `check_pitch`) moves the envelope by f semitones on its own
+    (`psola_shape_pcm16`); f = 0 is the int s.
     With `device_backend` all of it stays on the device, chained on one stream behind `wave_finish`: the calls and the copies that come back
     are `_finish_on_device`'s, and `backend_stats` counts them."""
     _check_want(device_backend, want)   # (first, as ever: a bad `want` is reported before a bad option)
@@ -917,6 +920,8 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     if len(gen_texts) != n or len(flags) != n:
         raise ValueError("finish_requests: one text and one remove_silence flag per request")
     one = isinstance(watermark, (WatermarkTag, dict))   # (a tag is a tuple: one value, not one per request)
+    if isinstance(pitch, (PitchTag, dict)):             # (likewise `{"semitones": s, "formant": f}`: one value)
+        pitch = [pitch] * n
     keywords = dict(sample_rate=sample_rate, encoding=encoding, loudness=loudness, flac_level=flac_level, tempo=tempo, pitch=pitch,
                     watermark=[watermark] * n if one else watermark, keep_formants=keep_formants)
     columns = [_per_request(value, n, name) for name, value in keywords.items()]
@@ -987,7 +992,8 @@ def _device_request(waves):
 def finish_pcm16(pcm, spec) -> np.ndarray:
     """What a `WaveSpec` makes of a request's 24 kHz int16 PCM, the one
     host definition (the device back-end and `StreamDelivery` are held to it byte for byte): `remove_silence_pcm` when flagged,
-    `shift_pcm16` (tempo and pitch; with `keep_formants` the pitch by `psola_pcm16`, which keeps the spectral envelope),
+    `shift_pcm16` (tempo and pitch; with `keep_formants` the pitch by `psola_pcm16`, which keeps the spectral envelope; with a `PitchTag`
+    by `psola_shape_pcm16`, which moves it on its own),
     `mark_pcm16` with a key -- so the loudness and the -1 dBFS peak cap are measured on the marked samples, and the one gain behind it does
     not disturb the scale-invariant detector --, `normalise_loudness_pcm16`, `deliver_pcm16`."""
     if spec.remove_silence:
@@ -1015,7 +1021,8 @@ def _finish_on_device(requests, fade, specs):
     directly behind it, when any request names a tempo or a pitch, ONE `ops.wave_prosody` call for the whole batch (the others are copied
     through), whose buffer, offsets, bounds and device lengths everything downstream reads in the place of `wave_finish`'s -- with a spec that
     has `keep_formants` the same ONE call, flagged and unflagged requests together: a flagged request takes the
-    stretch of its tempo alone and keeps its spectral envelope (`backend_stats["formant_requests"]`);
+    stretch of its tempo alone and keeps its spectral envelope (`backend_stats["formant_requests"]`); a spec whose pitch is a `PitchTag`
+    rides in that ONE call too, with its formant step (`ops.wave_prosody(..., formant=)`: `backend_stats["shape_requests"]`);
     then, when any spec has a key or a `WatermarkTag` for its `watermark`, ONE `ops.wave_mark` call that marks
     those in place, with their trace ids where they have one (f5hip_wave_mark_ids then; the same two launches, no copy more)
     (carriers cached on the device: nothing is uploaded for a key seen before, and nothing comes back);
@@ -1047,7 +1054,11 @@ def _finish_on_device(requests, fade, specs):
         if any(keeps):
             flagged = {"keep_formants": keeps}
             backend_stats["formant_requests"] += sum(keeps)
-        pcm, lengths, offsets, joined = ops.wave_prosody(pcm, offsets, joined, lengths, [spec.stretch for spec in specs], [spec.pitch for spec in specs], **flagged)
+        shapes = [spec.formant for spec in specs]
+        if any(shapes):
+            flagged.update(keep_formants=keeps, formant=shapes)
+            backend_stats["shape_requests"] += sum(f != 0 for f in shapes)
+        pcm, lengths, offsets, joined = ops.wave_prosody(pcm, offsets, joined, lengths, [spec.stretch for spec in specs], [spec.semitones for spec in specs], **flagged)
         backend_stats["prosody_calls"] += 1
         backend_stats["prosody_requests"] += sum(spec.prosody for spec in specs)
     marks = [spec.watermark for spec in specs]

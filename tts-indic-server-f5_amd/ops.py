@@ -823,7 +823,7 @@ def wave_prosody_formants_launches():
     return int(_lib.lib().f5hip_wave_prosody_formants_launches())
 
 
-def wave_prosody(pcm, in_off, max_len, len_dev, stretches, pitches, keep_formants=None):
+def wave_prosody(pcm, in_off, max_len, len_dev, stretches, pitches, keep_formants=None, formant=None):
     """The tempo and pitch of several finished requests in ONE library call and two launches, one when no request has a pitch
     (include/f5hip.h f5hip_wave_prosody): their 24 kHz int16 PCM on the device -> each request's `wave_codec.shift_pcm16`, bit for bit.
     `pcm`: the int16 device tensor that holds every request (`wave_finish`'s packed PCM; request i starts at sample in_off[i]); `max_len`,
@@ -833,9 +833,19 @@ def wave_prosody(pcm, in_off, max_len, len_dev, stretches, pitches, keep_formant
     gives -- what `wave_loudness`, `wave_encode` and `wave_flac` take in the place of `wave_finish`'s buffer, offsets, bounds and lengths.
     `keep_formants` [n] of bools (None: the call above, unchanged): a flagged request needs a pitch, takes the stretch of its tempo alone
     (`wave_codec.formant_stretch`) and keeps its spectral envelope -- `wave_codec.shift_pcm16(..., keep_formants=True)` bit for bit, three
-    more launches whatever n (include/f5hip.h f5hip_wave_prosody_formants), the resampler's only when another request has a plain pitch."""
+    more launches whatever n (include/f5hip.h f5hip_wave_prosody_formants), the resampler's only when another request has a plain pitch.
+    `formant` [n] of ints (None: the calls above, unchanged): a request with a non-zero step, -6 .. 6 and at most 6 semitones from its
+    pitch, moves its spectral envelope by that step on its own -- `wave_codec.shift_pcm16(pcm, tempo, PitchTag(pitch, step))` bit for bit;
+    it takes the stretch of its tempo alone, may have no pitch, and its `keep_formants` changes nothing.  The same three launches
+    (include/f5hip.h f5hip_wave_prosody_shape); `keep_formants` may then be left out."""
     (pcm,), io, ml, n, len_dev = _pcm_requests("wave_prosody", pcm, in_off, max_len, len_dev)
-    kf = None
+    kf = fm = None
+    if formant is not None:
+        if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in formant):
+            raise _lib.F5HipError(f"wave_prosody: a formant step is a whole number of semitones (got {list(formant)!r})")
+        fm = np.ascontiguousarray(_per_request("wave_prosody", "formant", formant, np.int64, n).astype(np.int32))
+        if keep_formants is None:
+            keep_formants = [False] * n
     if keep_formants is not None:
         if any(not isinstance(v, (bool, np.bool_)) for v in keep_formants):
             raise _lib.F5HipError(f"wave_prosody: keep_formants is one bool per request (got {list(keep_formants)!r})")
@@ -849,10 +859,17 @@ def wave_prosody(pcm, in_off, max_len, len_dev, stretches, pitches, keep_formant
     if (np.abs(pt) > 6).any():
         raise _lib.F5HipError(f"wave_prosody: a pitch is -6 to 6 semitones (got {pt.tolist()})")
     sp, sq, pt = (np.ascontiguousarray(a.astype(np.int32)) for a in (st[:, 0], st[:, 1], pt))
-    if kf is not None and (kf.astype(bool) & (pt == 0)).any():
+    if fm is not None and ((np.abs(fm) > 6) | ((fm != 0) & (np.abs(fm - pt) > 6))).any():
+        raise _lib.F5HipError(f"wave_prosody: a formant step is -6 to 6 semitones, at most 6 from the pitch (pitches {pt.tolist()}, formant {fm.tolist()})")
+    shaped = np.zeros(n, dtype=bool) if fm is None else fm != 0
+    if kf is not None and (kf.astype(bool) & (pt == 0) & ~shaped).any():
         raise _lib.F5HipError(f"wave_prosody: a request keeps its formants without a pitch (pitches {pt.tolist()}, keep_formants {kf.tolist()})")
-    plain = pt if kf is None else np.where(kf.astype(bool), 0, pt)     # the steps that go through the resampler
+    plain = pt if kf is None else np.where(kf.astype(bool) | shaped, 0, pt)     # the steps that go through the resampler
     taps = wave_prosody_taps(pcm.device) if plain.any() else None
+    if torch_ops.load() and fm is not None:
+        pcm2, lengths2, offsets2, bounds2 = call_op("wave_prosody_shape", pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(sp),
+                                                    torch.from_numpy(sq), torch.from_numpy(pt), torch.from_numpy(kf), torch.from_numpy(fm), taps)
+        return pcm2, lengths2, offsets2.tolist(), bounds2.tolist()
     if torch_ops.load() and kf is not None:
         pcm2, lengths2, offsets2, bounds2 = call_op("wave_prosody_formants", pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(sp),
                                                     torch.from_numpy(sq), torch.from_numpy(pt), torch.from_numpy(kf), taps)
@@ -869,7 +886,10 @@ def wave_prosody(pcm, in_off, max_len, len_dev, stretches, pitches, keep_formant
     with torch.cuda.device(pcm.device):
         pcm2 = torch.empty(max(total, 8), device=pcm.device, dtype=torch.int16)[:total]   # (a call of empty requests still has an address to give)
         lengths2 = torch.empty(n, device=pcm.device, dtype=torch.int32)
-        if kf is not None:
+        if fm is not None:
+            _lib.check(_lib.lib().f5hip_wave_prosody_shape(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(sp), _p(sq), _p(pt), _p(kf), _p(fm), _p(taps), _p(pcm2),
+                                                           _p(oo), _p(lengths2), _lib.current_stream_ptr()), "f5hip_wave_prosody_shape")
+        elif kf is not None:
             _lib.check(_lib.lib().f5hip_wave_prosody_formants(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(sp), _p(sq), _p(pt), _p(kf), _p(taps), _p(pcm2),
                                                               _p(oo), _p(lengths2), _lib.current_stream_ptr()), "f5hip_wave_prosody_formants")
         else:

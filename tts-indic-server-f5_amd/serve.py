@@ -101,7 +101,7 @@ def check_request_options(options: dict, ode_method: str = "euler", allowed=infe
             if v == 1.0:
                 continue
         elif k == "pitch":
-            v = infer.check_pitch(v)                    # ValueError: "pitch must be a whole number of semitones ..."
+            v = infer.check_pitch(v)                    # ValueError: "pitch must be a whole number of semitones ..."; {"semitones": s, "formant": f}: an infer.PitchTag, or the int s when f is 0
             if v == 0:
                 continue
         elif k == "watermark":
@@ -1179,7 +1179,7 @@ def request_models():
         speed: float | None = None
         remove_silence: bool | None = None
         tempo: typing.Any = None                     # 0.5 to 2 in steps of 0.01: the duration divided by it, the pitch kept (infer.shift_pcm16); untyped like flac_level
-        pitch: typing.Any = None                     # whole semitones, -6 to 6, the duration kept; untyped, so that true and 2.0 arrive as sent and are refused
+        pitch: typing.Any = None                     # whole semitones, -6 to 6, the duration kept, or {"semitones": s, "formant": f}: the spectral envelope moves by f on its own (infer.psola_shape_pcm16); untyped, so that true and 2.0 arrive as sent and are refused
         watermark: typing.Any = None                 # the key of a provenance mark, 1 to 2^48 - 1, or {"key": K, "id": I} with a trace id (infer.mark_pcm16); untyped, so that true, 1.0 and "1" are refused
         keep_formants: typing.Any = None             # true beside a non-zero pitch: the voice's formants stay where they were (infer.psola_pcm16); untyped, so that 1 and "true" are refused
 

@@ -404,6 +404,9 @@ class WaveSpec:
                         same duration; 1.0 and 0 keep the samples as they are.  So loudness is measured on what is delivered.
       `keep_formants`   beside a non-zero `pitch` only (`check_keep_formants`): the pitch moves by `psola_pcm16` and the spectral envelope
                         stays; WSOLA then stretches by the tempo alone (`stretch`).
+      `pitch` as `PitchTag(semitones, formant)` (a request's `{"semitones": s, "formant": f}` with f != 0; `check_pitch`): the fundamental
+                        moves by s with the envelope held and the envelope then moves by f (`psola_shape_pcm16`); WSOLA stretches by the
+                        tempo alone, and `keep_formants` beside it changes nothing.
       `watermark`       a key, or a `WatermarkTag(key, id)` with a trace id (`check_watermark`): `mark_pcm16` behind the prosody step and in
                         front of the loudness step, so the level and the -1 dBFS peak cap are measured on the marked samples; None: no mark.
       `loudness`        a programme loudness target in LUFS within LOUDNESS_RANGE (ITU-R BS.1770-4; `normalise_loudness_pcm16`: the sample
@@ -421,7 +424,7 @@ class WaveSpec:
     encoding: str = "pcm16"
     flac_level: int = 0
     tempo: float = 1.0
-    pitch: int = 0
+    pitch: int | PitchTag = 0
     watermark: int | WatermarkTag | None = None
     keep_formants: bool = False
 
@@ -436,9 +439,11 @@ class WaveSpec:
         level = request_flac_level(get("flac_level"), get("encoding"))
         fmt = delivery_format(get("sample_rate"), get("encoding"))
         hundredths, pitch = check_tempo(get("tempo")), check_pitch(get("pitch"))
-        prosody_stretch(hundredths, pitch)
+        shaped = isinstance(pitch, PitchTag)             # (its stretch is the tempo's alone: always inside 1/2 to 2)
+        if not shaped:
+            prosody_stretch(hundredths, pitch)
         return cls(bool(get("remove_silence")), loudness, *fmt, level, hundredths / 100, pitch, check_watermark(get("watermark")),
-                   check_keep_formants(get("keep_formants"), pitch))
+                   check_keep_formants(get("keep_formants"), pitch) and not shaped)
 
     @property
     def format(self):
@@ -463,10 +468,20 @@ class WaveSpec:
         return self.tempo != 1.0 or self.pitch != 0
 
     @property
+    def semitones(self) -> int:
+        """The fundamental's move, whichever form `pitch` has."""
+        return self.pitch.semitones if isinstance(self.pitch, PitchTag) else self.pitch
+
+    @property
+    def formant(self) -> int:
+        """The envelope's own move in semitones: 0 unless `pitch` is a `PitchTag`."""
+        return self.pitch.formant if isinstance(self.pitch, PitchTag) else 0
+
+    @property
     def stretch(self):
-        """(P, Q) of the WSOLA step, what `ops.wave_prosody` takes beside the pitch; with `keep_formants` the tempo's alone."""
+        """(P, Q) of the WSOLA step, what `ops.wave_prosody` takes beside the pitch; with `keep_formants` or a formant the tempo's alone."""
         hundredths = check_tempo(self.tempo)
-        return formant_stretch(hundredths) if self.keep_formants else prosody_stretch(hundredths, self.pitch)
+        return formant_stretch(hundredths) if self.keep_formants or self.formant else prosody_stretch(hundredths, self.pitch)
 
     def needs_whole_wave(self, streamed=False) -> bool:
         """Whether the request cannot be handed out chunk by chunk.  `streamed`: the format does not count, the stream's owner applies it."""
@@ -644,6 +659,8 @@ PROSODY_TEMPO_RANGE = (0.5, 2.0)
 PITCH_RATIOS = {1: (18, 17), 2: (46, 41), 3: (44, 37), 4: (29, 23), 5: (4, 3), 6: (41, 29)}
 PITCH_RATIOS.update({-s: (q, p) for s, (p, q) in list(PITCH_RATIOS.items())})
 PITCH_RANGE = (-6, 6)
+PitchTag = collections.namedtuple("PitchTag", "semitones formant")   # a pitch whose spectral envelope moves on its own, formant != 0
+PITCH_FORMANT_SPAN = 6                             # |formant - semitones| at most: the grain spacing over the grain half-width stays within 41/29
 _wsola_window = None
 _pitch_tables: dict = {}
 
@@ -674,11 +691,31 @@ def check_tempo(tempo) -> int:
     return int(round(scaled))
 
 
-def check_pitch(pitch) -> int:
+def _check_semitones(value, what) -> int:
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not PITCH_RANGE[0] <= int(value) <= PITCH_RANGE[1]:
+        raise ValueError(f"pitch {what} must be a whole number of semitones from -6 to 6 (got {value!r})")
+    return int(value)
+
+
+def check_pitch(pitch):
     """A request's `pitch` option: None (absent) is 0; an int of whole semitones within PITCH_RANGE; a bool, a float and anything else are
-    a ValueError."""
+    a ValueError.  `{"semitones": s, "formant": f}` (or a `PitchTag`) moves the spectral envelope by f semitones on its own, each entry
+    -6 .. 6 and 0 when absent: the int s when f == 0, else `PitchTag(s, f)`.  An unknown entry, an empty dict and |f - s| >
+    PITCH_FORMANT_SPAN are a ValueError."""
     if pitch is None:
         return 0
+    if isinstance(pitch, PitchTag):
+        pitch = pitch._asdict()
+    if isinstance(pitch, dict):
+        unknown = [k for k in pitch if k not in PitchTag._fields]
+        if unknown:
+            raise ValueError(f"pitch has an unknown entry {unknown[0]!r}: a pitch with a formant shift is {{\"semitones\": s, \"formant\": f}}")
+        if not pitch:
+            raise ValueError("pitch as a mapping needs semitones or formant (got {})")
+        s, f = (0 if pitch.get(k) is None else _check_semitones(pitch[k], k) for k in PitchTag._fields)
+        if abs(f - s) > PITCH_FORMANT_SPAN:
+            raise ValueError(f"pitch formant {f} beside semitones {s} is {abs(f - s)} semitones apart: at most {PITCH_FORMANT_SPAN}, or the grains leave gaps")
+        return PitchTag(s, f) if f else s
     if isinstance(pitch, (bool, np.bool_)) or not isinstance(pitch, (int, np.integer)) or not PITCH_RANGE[0] <= int(pitch) <= PITCH_RANGE[1]:
         raise ValueError(f"pitch must be a whole number of semitones from -6 to 6 (got {pitch!r})")
     return int(pitch)
@@ -756,6 +793,8 @@ def shift_pcm16(pcm, tempo=None, pitch=None, keep_formants=False) -> np.ndarray:
     pcm = _as_pcm16(pcm)
     hundredths, pitch = check_tempo(tempo), check_pitch(pitch)
     keep = check_keep_formants(keep_formants, pitch)
+    if isinstance(pitch, PitchTag):                  # its own envelope move: WSOLA by the tempo alone, then `psola_shape_pcm16` (defined below)
+        return psola_shape_pcm16(wsola_pcm16(pcm, *formant_stretch(hundredths)), *pitch)
     P, Q = prosody_stretch(hundredths, pitch)
     if hundredths == 100 and pitch == 0:
         return pcm
@@ -834,7 +873,7 @@ def check_keep_formants(keep, pitch=None) -> bool:
         return False
     if not isinstance(keep, (bool, np.bool_)):
         raise ValueError(f"keep_formants must be true or false (got {keep!r})")
-    if keep and pitch is not None and pitch == 0:
+    if keep and pitch is not None and pitch == 0:     # (a `PitchTag` is never 0: its formant moves)
         raise ValueError("keep_formants needs a non-zero pitch")
     return bool(keep)
 
@@ -893,7 +932,7 @@ def psola_marks(x, lag, voiced):
 
 def psola_synthesis(a, T, v, n, pitch):
     """The synthesis marks: int64 arrays (u, i), i the analysis mark each takes."""
-    p, q = PITCH_RATIOS[pitch]
+    p, q = PITCH_RATIOS[pitch] if pitch else (1, 1)
     us, idx = [], []
     if len(a):
         u, rem, i = int(a[0]), 0, 0
@@ -935,6 +974,64 @@ def psola_pcm16(pcm, pitch) -> np.ndarray:
     covered = den > 0
     safe = np.where(covered, den, 1)
     y = np.where(covered, (2 * num + safe) // (2 * safe), x64)
+    return np.clip(y, -32768, 32767).astype(np.int16)
+
+
+# ----------------------------------------- formant shift: a request's `pitch` as `{"semitones": s, "formant": f}` with f != 0.  The PSOLA
+# above with a grain that is READ at another rate than it is laid down, in integers with no freedom left, so the device call
+# (csrc/wave_formant.h wave_shape_kernel, f5hip_wave_prosody_shape; the rules are csrc/wave_formant_core.h) is held to it bit for bit.
+# `psola_shape_pcm16(x, s, f)`: int16 x [n] -> int16 y [n], the fundamental times PITCH_RATIOS[s] and the spectral envelope times PITCH_RATIOS[f].
+#   track, marks  `psola_track` / `psola_marks`, unchanged
+#   synthesis     `psola_synthesis`'s rule with (p, q) = PITCH_RATIOS[s], (1, 1) for s = 0: the marks keep the pitch move and the length
+#   grain         of a synthesis mark (u, i), (P, Q) = PITCH_RATIOS[f]; Pg = P when i is voiced and Pg = Q when it is not (noise is not
+#                 shifted: the grain below is then `psola_pcm16`'s, v = xt[a_i + k] Q over |k| <= T_i)
+#                   offsets   k with |k| Pg <= T_i Q
+#                   weight    w = M[(|k| Pg 1024) // (Q T_i)]
+#                   source    k Pg = c Q + r by floor division, 0 <= r < Q: v = xt[a_i + c] (Q - r) + xt[a_i + c + 1] r (linear
+#                             interpolation at a_i + k Pg / Q, scaled by Q)
+#                   num[u + k] += w v, den[u + k] += w Q
+#                 reading the grain Pg / Q times faster scales its spectrum by Pg / Q
+#   output        y[j] = clip((2 num + den) // (2 den)) where den > 0 (a floor division), else x[j]
+# Bit budget: a sample lies under at most 2 * 565 // 33 + 1 = 35 grains (half-widths up to 400 * 41 // 29 = 565, steps of 33 at least),
+# |v| <= 2^15 Q <= 2^15 * 46, w <= 2^15: |num| < 35 * 46 * 2^30 < 2^41, den < 35 * 46 * 2^15 < 2^26; 64-bit integers, no sum depends on
+# an order.  A source index stays within 400 + 166 + 1 samples of its output: |a_i - u| < 400 (u takes the nearest mark) and
+# |c - k| <= 400 * 12 // 29 + 1.  With |f - s| <= 6 the marks' spacing over the grain half-width, (q / p) / (Q / P), stays within the 41 / 29
+# that `psola_pcm16` reaches at -6: no gaps in the cover.
+# Consequences: f = 0 (P = Q = 1) is `psola_pcm16(x, s)` byte for byte; len(y) == len(x); zeros stay zeros; a wave without a voiced frame
+# comes back byte for byte (every grain is the unvoiced one: num = x den); nothing but the request's own samples enters.
+# Limits: the interpolation is linear, about 1 dB of droop at 4 kHz, and content above 12 kHz * Q / P aliases when a grain is read faster;
+# unvoiced sound is not shifted.
+
+
+def psola_shape_pcm16(pcm, semitones, formant) -> np.ndarray:
+    """int16 PCM [n] with its fundamental moved by `semitones` (envelope held) and its spectral envelope then moved by `formant` semitones
+    (each -6 .. 6, at most PITCH_FORMANT_SPAN apart), by the definition above: n samples.  What `ops.wave_prosody(..., formant=...)` equals
+    byte for byte."""
+    x = _as_pcm16(pcm)
+    s, f = _check_semitones(semitones, "semitones"), _check_semitones(formant, "formant")
+    check_pitch({"semitones": s, "formant": f})
+    n = len(x)
+    if n == 0:
+        return x
+    a, T, v = psola_marks(x, *psola_track(x))
+    u, idx = psola_synthesis(a, T, v, n, s)
+    P, Q = PITCH_RATIOS[f] if f else (1, 1)
+    M = psola_window()
+    xt = np.zeros(n + 2, dtype=np.int64)               # xt[-1] and xt[n]: the zeros around the wave (index -1 is the last element)
+    xt[:n] = x
+    num, den = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    for at, i in zip(u.tolist(), idx.tolist()):
+        Ti, ai, Pg = int(T[i]), int(a[i]), P if v[i] else Q
+        H = Ti * Q // Pg
+        k = np.arange(max(-H, -at), min(H, n - 1 - at) + 1, dtype=np.int64)            # the grain's offsets whose output lies in the wave
+        w = M[(np.abs(k) * Pg * PSOLA_TABLE) // (Q * Ti)]
+        c, r = np.divmod(k * Pg, Q)
+        lo, hi = np.clip(ai + c, -1, n), np.clip(ai + c + 1, -1, n)                     # every index outside the wave reads a zero
+        num[at + k[0]:at + k[-1] + 1] += w * (xt[lo] * (Q - r) + xt[hi] * r)
+        den[at + k[0]:at + k[-1] + 1] += w * Q
+    covered = den > 0
+    safe = np.where(covered, den, 1)
+    y = np.where(covered, (2 * num + safe) // (2 * safe), x.astype(np.int64))
     return np.clip(y, -32768, 32767).astype(np.int16)
 
 
