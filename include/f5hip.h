@@ -655,6 +655,39 @@ int f5hip_wave_loudness(int32_t n, int16_t* pcm_dev, const int64_t* in_off, cons
 /* Samples one block of f5hip_wave_loudness's first launch owns (two sub-blocks).  For tests, which place request lengths around it. */
 int f5hip_wave_loudness_tile(void);
 
+/* True-peak limiter beside the loudness target: f5hip_wave_loudness with a ceiling per request, IN PLACE, in one call.  A request with
+ * ceiling[i] == 0 is f5hip_wave_loudness's (its target alone, or left alone), bit for bit; a call in which no request has a ceiling IS
+ * f5hip_wave_loudness.  A request with a ceiling becomes wave_codec.limit_pcm16 bit for bit: its target reached with no sample-peak cap
+ * (unity gain when gain_k[i] <= 0), and the reconstructed waveform held at or below the ceiling by a look-ahead gain reduction.  Not in the
+ * reference.  The arithmetic, integers up to the gain's one sqrt; x = 0 outside the request:
+ *   true peak    v_p[j] = sum_k t[p][k] x[j - 5 + k], p = 1, 2, 3: the points j + p / 4 of a 4-phase, 12-tap Kaiser-windowed sinc at 2^14
+ *                (csrc/truepeak_taps.inc = wave_codec.truepeak_taps(); sum |t[p]| < 2^15); m[j] = max(2^14 |x[j]|, |v_1|, |v_2|, |v_3|) < 2^30
+ *   gain         G = min(rint(2^16 sqrt(K_T n2 / S2)), 2^22) of the meter's n2, S2 (above); 2^16 without a target or when n2 == 0
+ *   reduction    r[j] = 2^16 where m[j] G <= c 2^30, else floor(c 2^46 / (m[j] G)) (>= 181); 2^16 outside the request
+ *   hold         s[j] = min r[j - 240 .. j + 240]
+ *   release      a[j] = (sum_k w[k] s[j + k]) >> 16, |k| <= 240, w the 481 Hann weights of csrc/limit_window.inc (their sum is 2^16): a <= r
+ *   output       x[j] <- clip(x[j] G a[j] / 2^32), half to even: a 64-bit product, + 2^31 - 1 + bit 32 of it, a floor shift
+ *   pcm_dev, in_off, max_len, len_dev, gain_k   as in f5hip_wave_loudness
+ *   ceiling      host int32 [n]: c = floor(32767 10^(C / 20)) of request i's ceiling C in dBTP, 11626 (-9) .. 32767 (0); 0: no limiter
+ *   stats_dev    as in f5hip_wave_loudness: the meter's row (n2, S2, peak, the bits of the capped g) of every request with a target, with or
+ *                without a ceiling; the row of a request without a target is not written
+ * Four launches whatever n, two when no request has a target (f5hip_wave_loudness_limit_launches reports the four): the meter's two as they
+ * stand over the requests with a target; wave_truepeak_kernel, one block per tile of 2048 samples of a request with a ceiling (m by packed
+ * 16-bit dot products from LDS, a division only where the ceiling is exceeded, r and a flag per tile to a workspace); wave_limit_apply_kernel
+ * over every request's tiles (a target alone: f5hip_wave_loudness's gain; a tile whose flag and neighbours' flags are clear: clip(rint(x G /
+ * 2^16)) and nothing for G = 2^16; else hold and release from LDS).  No atomics, vector stores, no host sync: the request table goes through
+ * pinned staging on `stream` (counters wave_limit_launches, wave_limit_requests).  A request's bytes depend on that request alone; an
+ * unflagged request and the bytes between requests are not written.  Refused before the first launch: f5hip_wave_loudness's list, a null
+ * ceiling, a ceiling outside 0 and 11626 .. 32767. */
+int f5hip_wave_loudness_limit(int32_t n, int16_t* pcm_dev, const int64_t* in_off, const int32_t* max_len, const int32_t* len_dev,
+                              const double* gain_k, const int32_t* ceiling, int64_t* stats_dev, void* stream);
+
+/* Kernels a f5hip_wave_loudness_limit call launches when a request has a ceiling and a request has a target (4). */
+int f5hip_wave_loudness_limit_launches(void);
+
+/* Samples one block of f5hip_wave_loudness_limit's last two launches owns.  For tests, which place request lengths around it. */
+int f5hip_wave_loudness_limit_tile(void);
+
 /* Prosody: the 24 kHz int16 PCM of n requests, still on the device (f5hip_wave_finish's pcm_dev), time-scale modified per request -- its
  * `tempo` and `pitch` --, bit for bit wave_codec.shift_pcm16.  Not in the reference.  It runs behind f5hip_wave_finish and before
  * f5hip_wave_loudness / f5hip_wave_encode / f5hip_wave_flac, which read its output, bounds and lengths as they read f5hip_wave_finish's.  The

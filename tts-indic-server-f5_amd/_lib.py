@@ -124,6 +124,9 @@ SYMBOLS = {
     "f5hip_wave_flac_bound": (C.c_int64, [C.c_int32]),
     "f5hip_wave_loudness": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f5hip_wave_loudness_tile": (C.c_int, []),
+    "f5hip_wave_loudness_limit": (C.c_int, [C.c_int32] + [C.c_void_p] * 8),
+    "f5hip_wave_loudness_limit_launches": (C.c_int, []),
+    "f5hip_wave_loudness_limit_tile": (C.c_int, []),
     "f5hip_wave_prosody": (C.c_int, [C.c_int32] + [C.c_void_p] * 12),
     "f5hip_wave_prosody_tap_offset": (C.c_int64, [C.c_int32]),
     "f5hip_wave_prosody_formants": (C.c_int, [C.c_int32] + [C.c_void_p] * 13),

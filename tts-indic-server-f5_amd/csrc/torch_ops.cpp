@@ -21,6 +21,7 @@
 //   torch.ops.f5hip.flac_decode(data, begin, end, info, total, max_samples) -> (Tensor statuses and planes int32, Tensor offsets int64 host)
 //   torch.ops.f5hip.ref_prestep(frames, n_in, channels, clip_short, rate) -> (Tensor planes fp32, Tensor info int32 [n, 2])   F/infer/utils_infer.py:282-350
 //   torch.ops.f5hip.wave_loudness(pcm, in_off, max_len, len_dev?, gain_k) -> Tensor stats int64 [n, 4]; pcm is normalised in place
+//   torch.ops.f5hip.wave_loudness_limit(pcm, in_off, max_len, len_dev?, gain_k, ceiling) -> the same, with a true-peak ceiling per request
 //   torch.ops.f5hip.wave_prosody(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, taps?) -> (Tensor pcm int16, Tensor lengths int32, Tensor offsets int64 host, Tensor bounds int32 host)
 //   torch.ops.f5hip.wave_prosody_formants(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, keep_formants, taps?) -> the same four
 //   torch.ops.f5hip.wave_prosody_shape(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, keep_formants, formant, taps?) -> the same four
@@ -567,12 +568,17 @@ std::tuple<at::Tensor, at::Tensor> ref_prestep(const at::Tensor& frames, const a
 // pcm: the int16 device tensor that holds every request (f5hip_wave_finish's packed PCM), normalised IN PLACE; in_off, max_len, len_dev as
 // wave_encode's; gain_k [n] float64 host: K_T per request, <= 0 leaves the request alone -> stats int64 device [n, 4]: n2, S2, peak, the bits
 // of g (zeros for a request that was left alone)
-at::Tensor wave_loudness(at::Tensor pcm, const at::Tensor& in_off, const at::Tensor& max_len, const c10::optional<at::Tensor>& len_dev,
-                         const at::Tensor& gain_k) {
+// ceiling: null for wave_loudness; wave_loudness_limit's int32 [n] host ceilings (f5hip_wave_loudness_limit: 0 for a request without one)
+static at::Tensor wave_loudness_impl(at::Tensor pcm, const at::Tensor& in_off, const at::Tensor& max_len, const c10::optional<at::Tensor>& len_dev,
+                                     const at::Tensor& gain_k, const at::Tensor* ceiling) {
     const PcmRequests rq = check_pcm_requests("wave_loudness", pcm, in_off, max_len, len_dev, false);
     const int64_t n = rq.n;
     check_host(gain_k, at::kDouble, "gain_k");
     TORCH_CHECK(gain_k.numel() == n, "f5hip::wave_loudness: gain_k needs one value per request");
+    if (ceiling) {
+        check_host(*ceiling, at::kInt, "ceiling");
+        TORCH_CHECK(ceiling->dim() == 1 && ceiling->numel() == n, "f5hip::wave_loudness_limit: ceiling needs one value per request");
+    }
     const PcmSources src = pcm_sources("wave_loudness", pcm, rq);
     const double* gk = gain_k.data_ptr<double>();
     int64_t total = 0;
@@ -581,14 +587,26 @@ at::Tensor wave_loudness(at::Tensor pcm, const at::Tensor& in_off, const at::Ten
         TORCH_CHECK(std::isfinite(gk[i]), "f5hip::wave_loudness: the gain constant of request ", i, " is not finite");
         total += rq.ml[i];
         TORCH_CHECK(total <= INT32_MAX, "f5hip::wave_loudness: the call exceeds 2^31 - 1 samples");
-        any = any || gk[i] > 0.0;
+        any = any || gk[i] > 0.0 || (ceiling && ceiling->data_ptr<int32_t>()[i] != 0);
     }
     const c10::DeviceGuard guard(rq.device);
     at::Tensor stats = at::zeros({n, 4}, pcm.options().dtype(at::kLong));
     if (!any || pcm.numel() == 0) return stats;      // nothing to launch (an empty tensor has no address to give)
-    const int rc = f5hip_wave_loudness((int32_t)n, src.base(), src.rel.data(), rq.ml, rq.len_dev, gk, stats.data_ptr<int64_t>(), stream_of(pcm));
-    TORCH_CHECK(rc == 0, "f5hip_wave_loudness: ", f5hip_last_error());
+    const int rc = ceiling ? f5hip_wave_loudness_limit((int32_t)n, src.base(), src.rel.data(), rq.ml, rq.len_dev, gk, ceiling->data_ptr<int32_t>(),
+                                                       stats.data_ptr<int64_t>(), stream_of(pcm))
+                           : f5hip_wave_loudness((int32_t)n, src.base(), src.rel.data(), rq.ml, rq.len_dev, gk, stats.data_ptr<int64_t>(), stream_of(pcm));
+    TORCH_CHECK(rc == 0, ceiling ? "f5hip_wave_loudness_limit: " : "f5hip_wave_loudness: ", f5hip_last_error());
     return stats;
+}
+
+at::Tensor wave_loudness(at::Tensor pcm, const at::Tensor& in_off, const at::Tensor& max_len, const c10::optional<at::Tensor>& len_dev,
+                         const at::Tensor& gain_k) {
+    return wave_loudness_impl(pcm, in_off, max_len, len_dev, gain_k, nullptr);
+}
+
+at::Tensor wave_loudness_limit(at::Tensor pcm, const at::Tensor& in_off, const at::Tensor& max_len, const c10::optional<at::Tensor>& len_dev,
+                               const at::Tensor& gain_k, const at::Tensor& ceiling) {
+    return wave_loudness_impl(pcm, in_off, max_len, len_dev, gain_k, &ceiling);
 }
 
 // pcm: the int16 device tensor that holds every request (f5hip_wave_finish's packed PCM), read only; in_off, max_len, len_dev as wave_encode's;
@@ -901,6 +919,7 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("flac_decode(Tensor data, Tensor begin, Tensor end, Tensor info, Tensor total, Tensor max_samples) -> (Tensor, Tensor)", &flac_decode);
     m.def("ref_prestep(Tensor frames, Tensor n_in, Tensor channels, Tensor clip_short, int rate) -> (Tensor, Tensor)", &ref_prestep);
     m.def("wave_loudness(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor gain_k) -> Tensor", &wave_loudness);
+    m.def("wave_loudness_limit(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor gain_k, Tensor ceiling) -> Tensor", &wave_loudness_limit);
     m.def("wave_prosody(Tensor pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor stretch_p, Tensor stretch_q, Tensor pitch, Tensor? taps) -> "
           "(Tensor, Tensor, Tensor, Tensor)", &wave_prosody);
     m.def("wave_prosody_formants(Tensor pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor stretch_p, Tensor stretch_q, Tensor pitch, "

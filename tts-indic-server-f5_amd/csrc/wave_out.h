@@ -1198,6 +1198,8 @@ struct LdReq {
     int req;             // its index in the call: len_dev and stats row
     int tile0;           // its first block of launches 1 and 3 = its first peak slot; its sub-block sums start at 2 * tile0
     int tiles;
+    int ltile0, ltiles;  // f5hip_wave_loudness_limit only (wave_limit.h): its first block of the limiter's launches, and how many
+    int ceiling;         // likewise: c of a request with a true-peak ceiling, 0 for a request with a loudness target alone
 };
 
 F5_DEVICE int ld_len(const int* len_dev, const LdReq& q) { return len_dev ? min(max(len_dev[q.req], 0), q.cap) : q.cap; }
@@ -1315,17 +1317,10 @@ __global__ __launch_bounds__(256) void wave_gate_kernel(const LdReq* __restrict_
     row[0] = n2; row[1] = S2; row[2] = peak; row[3] = __double_as_longlong(g);
 }
 
-__global__ __launch_bounds__(256) void wave_gain_kernel(const LdReq* __restrict__ reqs, int nf, short* __restrict__ pcm,
-                                                        const int* __restrict__ len_dev, const long long* __restrict__ stats) {
-    const int f = last_at_or_before<&LdReq::tile0>(reqs, nf, (int)blockIdx.x);
-    const LdReq q = reqs[f];
-    const long long* row = stats + 4LL * q.req;
-    if (row[0] == 0) return;                                            // nothing passed the gates: the request stays as it is
-    const double g = __longlong_as_double(row[3]);
-    const int len = ld_len(len_dev, q);
-    const long long j0 = (long long)(blockIdx.x - q.tile0) * kLdTile;
-    short* x = pcm + q.in_off;
-    for (int grp = threadIdx.x; grp < kLdTile / 8; grp += 256) {
+// x[j] <- clip(rint(x[j] g)) for the `tile` samples from j0 that lie below len, by a block of 256 threads (wave_gain_kernel's body; the
+// limiter's second launch runs it too: wave_limit.h)
+F5_DEVICE void ld_gain_tile(short* x, int len, long long j0, int tile, double g) {
+    for (int grp = threadIdx.x; grp < tile / 8; grp += 256) {
         const long long j = j0 + 8 * grp;
         if (j >= len) break;
         if (j + 8 <= len && (reinterpret_cast<uintptr_t>(x + j) & 15) == 0) {
@@ -1343,6 +1338,15 @@ __global__ __launch_bounds__(256) void wave_gain_kernel(const LdReq* __restrict_
             for (int e = 0; e < 8 && j + e < len; e++) x[j + e] = (short)(int)fmax(fmin(rint((double)x[j + e] * g), 32767.0), -32768.0);
         }
     }
+}
+
+__global__ __launch_bounds__(256) void wave_gain_kernel(const LdReq* __restrict__ reqs, int nf, short* __restrict__ pcm,
+                                                        const int* __restrict__ len_dev, const long long* __restrict__ stats) {
+    const int f = last_at_or_before<&LdReq::tile0>(reqs, nf, (int)blockIdx.x);
+    const LdReq q = reqs[f];
+    const long long* row = stats + 4LL * q.req;
+    if (row[0] == 0) return;                                            // nothing passed the gates: the request stays as it is
+    ld_gain_tile(pcm + q.in_off, ld_len(len_dev, q), (long long)(blockIdx.x - q.tile0) * kLdTile, kLdTile, __longlong_as_double(row[3]));
 }
 
 struct LdWorkspace {

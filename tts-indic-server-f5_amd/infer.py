@@ -54,6 +54,8 @@ from .wave_codec import (WATERMARK_SCAN_MAX_SAMPLES, WATERMARK_SCAN_SLACK, WATER
                          scan_watermark, watermark_spans, watermark_windows)
 from .wave_codec import (LOUDNESS_GATE_ABS, LOUDNESS_PEAK_CEILING, LOUDNESS_RANGE, LOUDNESS_TAPS, check_loudness, loudness_gain,  # noqa: F401
                          loudness_gain_constant, loudness_lufs, loudness_taps, measure_loudness, normalise_loudness_pcm16)
+from .wave_codec import (LIMIT_HOLD, TRUE_PEAK_RANGE, LoudnessTag, check_true_peak, limit_envelope, limit_gain, limit_pcm16,  # noqa: F401
+                         limit_samples, limit_window, true_peak_ceiling, true_peak_db, true_peak_pcm16, truepeak_taps)
 from .wave_codec import _device_taps, _tap_tables  # noqa: F401  (the two caches: used below, and read as infer._X by the tests that bound them)
 
 # ----------------------------------------- F/infer/utils_infer.py:40-53
@@ -867,7 +869,8 @@ def request_wave(gen_text, waves, cross_fade_duration=cross_fade_duration):
 # `ops.wave_finish` calls, `ops.wave_encode` calls and the requests they encoded (`encode_calls`, `encode_requests`), and device-to-host copies
 # (chunk waves, spectrograms, PCM, encoded samples, lengths); `flac_bytes` is the size of the FLAC stream downloads; `loudness_calls` /
 # `loudness_requests`: `ops.wave_loudness` calls and the requests they normalised; `prosody_calls` / `prosody_requests`: `ops.wave_prosody`
-# calls and the requests whose tempo or pitch they changed; `mark_calls` / `mark_requests`: `ops.wave_mark` calls and the requests they marked
+# calls and the requests whose tempo or pitch they changed; `mark_calls` / `mark_requests`: `ops.wave_mark` calls and the requests they marked;
+# `limit_requests`: the requests among `loudness_requests` that had a true-peak ceiling (a `LoudnessTag`)
 backend_stats: collections.Counter = collections.Counter()
 
 
@@ -922,6 +925,8 @@ def finish_requests(chunk_waves_per_request, gen_texts, cross_fade_duration=cros
     one = isinstance(watermark, (WatermarkTag, dict))   # (a tag is a tuple: one value, not one per request)
     if isinstance(pitch, (PitchTag, dict)):             # (likewise `{"semitones": s, "formant": f}`: one value)
         pitch = [pitch] * n
+    if isinstance(loudness, (LoudnessTag, dict)):       # (likewise `{"target": L, "true_peak": C}`)
+        loudness = [loudness] * n
     keywords = dict(sample_rate=sample_rate, encoding=encoding, loudness=loudness, flac_level=flac_level, tempo=tempo, pitch=pitch,
                     watermark=[watermark] * n if one else watermark, keep_formants=keep_formants)
     columns = [_per_request(value, n, name) for name, value in keywords.items()]
@@ -995,12 +1000,13 @@ def finish_pcm16(pcm, spec) -> np.ndarray:
     `shift_pcm16` (tempo and pitch; with `keep_formants` the pitch by `psola_pcm16`, which keeps the spectral envelope; with a `PitchTag`
     by `psola_shape_pcm16`, which moves it on its own),
     `mark_pcm16` with a key -- so the loudness and the -1 dBFS peak cap are measured on the marked samples, and the one gain behind it does
-    not disturb the scale-invariant detector --, `normalise_loudness_pcm16`, `deliver_pcm16`."""
+    not disturb the scale-invariant detector --, `limit_pcm16` (`normalise_loudness_pcm16` for a number, the true-peak limiter for a
+    `LoudnessTag`), `deliver_pcm16`."""
     if spec.remove_silence:
         pcm = remove_silence_pcm(pcm, target_sample_rate)
     pcm = shift_pcm16(pcm, spec.tempo, spec.pitch, spec.keep_formants)
     pcm = mark_pcm16(pcm, spec.watermark)
-    pcm = normalise_loudness_pcm16(pcm, spec.loudness)
+    pcm = limit_pcm16(pcm, spec.loudness)
     return deliver_pcm16(pcm, *spec.format, flac_level=spec.flac_level if spec.flac else None)
 
 
@@ -1026,7 +1032,9 @@ def _finish_on_device(requests, fade, specs):
     then, when any spec has a key or a `WatermarkTag` for its `watermark`, ONE `ops.wave_mark` call that marks
     those in place, with their trace ids where they have one (f5hip_wave_mark_ids then; the same two launches, no copy more)
     (carriers cached on the device: nothing is uploaded for a key seen before, and nothing comes back);
-    then, when any request has a loudness target, ONE `ops.wave_loudness` call that normalises those in place; then on the
+    then, when any request has a loudness target, ONE `ops.wave_loudness` call that normalises those in place -- with a spec whose
+    `loudness` is a `LoudnessTag` the same ONE call (`ops.wave_loudness(..., true_peak=)`: number, tag and plain requests together,
+    `backend_stats["limit_requests"]`) --; then on the
     same stream one `ops.wave_flac` call per distinct rate of the "flac" requests (behind a `wave_encode(..., "pcm16")` call where the rate
     is not 24 kHz; the requests of a rate share it through its per-request levels, and a call in which nobody asks for level 1 is the
     level-0 call) and one `ops.wave_encode` call per other distinct delivery format.  Every call is queued before the first copy comes
@@ -1066,11 +1074,14 @@ def _finish_on_device(requests, fade, specs):
         ops.wave_mark(pcm, offsets, joined, lengths, marks)
         backend_stats["mark_calls"] += 1
         backend_stats["mark_requests"] += sum(key is not None for key in marks)
-    targets = [spec.gain_constant for spec in specs]
-    if any(t is not None for t in targets):   # in place, lengths still on the device: nothing comes back for it
-        ops.wave_loudness(pcm, offsets, joined, lengths, targets)
+    targets, ceilings = [spec.gain_constant for spec in specs], [spec.ceiling for spec in specs]
+    if any(v is not None for v in targets + ceilings):   # in place, lengths still on the device: nothing comes back for it
+        limited = {"true_peak": ceilings} if any(c is not None for c in ceilings) else {}   # (nobody limited: the older entry point)
+        ops.wave_loudness(pcm, offsets, joined, lengths, targets, **limited)
         backend_stats["loudness_calls"] += 1
-        backend_stats["loudness_requests"] += sum(t is not None for t in targets)
+        backend_stats["loudness_requests"] += sum(spec.loudness is not None for spec in specs)
+        if limited:
+            backend_stats["limit_requests"] += sum(c is not None for c in ceilings)
     if plain:
         if any(silence[:plain]):
             kept = lengths[:plain].cpu().tolist()

@@ -903,24 +903,48 @@ def wave_loudness_tile():
     return int(_lib.lib().f5hip_wave_loudness_tile())
 
 
-def wave_loudness(pcm, in_off, max_len, len_dev, gain_k):
+def wave_loudness_limit_tile():
+    """Samples one block of the limiter's two launches owns (`wave_loudness(..., true_peak=)`)."""
+    return int(_lib.lib().f5hip_wave_loudness_limit_tile())
+
+
+def wave_loudness_limit_launches():
+    """Launches of a `wave_loudness(..., true_peak=)` call in which a request has a ceiling and a request has a target (4)."""
+    return int(_lib.lib().f5hip_wave_loudness_limit_launches())
+
+
+def wave_loudness(pcm, in_off, max_len, len_dev, gain_k, true_peak=None):
     """The loudness target of several finished requests in ONE library call and three launches (include/f5hip.h f5hip_wave_loudness): their
     24 kHz int16 PCM on the device, normalised IN PLACE.  `pcm`: the int16 device tensor that holds every request (`wave_finish`'s packed
     PCM; request i starts at sample in_off[i]); `max_len`, `len_dev` as in `wave_encode`; `gain_k` [n]: `wave_codec.loudness_gain_constant`
     of each request's target, 0 (or None) for a request that is left alone.  A call without a flagged request launches nothing.  Returns
     stats, int64 device [n, 4]: n2, S2, peak and the bits of the gain g of each flagged request (zeros for the others) --
     `wave_codec.measure_loudness` and `loudness_gain` of its samples, and afterwards its samples are `normalise_loudness_pcm16`'s, bit for
-    bit."""
+    bit.
+    `true_peak` [n] (None: the call above, unchanged): `wave_codec.true_peak_ceiling` of each request's ceiling, 0 (or None) for a request
+    without one.  A request with a ceiling becomes `wave_codec.limit_pcm16` of its `LoudnessTag`, bit for bit -- its target (unity gain
+    where `gain_k` has none) with no sample-peak cap, limited to the ceiling --; the others are as above, in the same ONE call and four
+    launches (include/f5hip.h f5hip_wave_loudness_limit).  The stats row of a request with a target is the meter's, ceiling or not."""
     (pcm,), io, ml, n, len_dev = _pcm_requests("wave_loudness", pcm, in_off, max_len, len_dev)
     gk = _per_request("wave_loudness", "gain_k", [0.0 if k is None else k for k in gain_k], np.float64, n)
     if not np.isfinite(gk).all():
         raise _lib.F5HipError("wave_loudness: a gain constant is not finite")
+    tp = None
+    if true_peak is not None:
+        if any(c is not None and (isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer))) for c in true_peak):
+            raise _lib.F5HipError(f"wave_loudness: true_peak is wave_codec.true_peak_ceiling of each ceiling, an int or None (got {list(true_peak)!r})")
+        tp = np.ascontiguousarray(_per_request("wave_loudness", "true_peak", [0 if c is None else int(c) for c in true_peak], np.int64, n).astype(np.int32))
     if torch_ops.load():
+        if tp is not None:
+            return call_op("wave_loudness_limit", pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(gk), torch.from_numpy(tp))
         return call_op("wave_loudness", pcm, torch.from_numpy(io), torch.from_numpy(ml), len_dev, torch.from_numpy(gk))
     anchor, rel = _pcm_sources("wave_loudness", [pcm], io, ml)
     with torch.cuda.device(pcm.device):
         stats = torch.zeros(n, 4, device=pcm.device, dtype=torch.int64)
-        if (gk > 0).any() and pcm.numel():
+        if tp is not None and ((gk > 0).any() or tp.any()) and pcm.numel():
+            _lib.check(_lib.lib().f5hip_wave_loudness_limit(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(gk), _p(tp), _p(stats),
+                                                            _lib.current_stream_ptr()), "f5hip_wave_loudness_limit")
+        elif tp is None and (gk > 0).any() and pcm.numel():
             _lib.check(_lib.lib().f5hip_wave_loudness(n, _p(anchor), _p(rel), _p(ml), _p(len_dev), _p(gk), _p(stats), _lib.current_stream_ptr()),
                        "f5hip_wave_loudness")
     return stats

@@ -1171,7 +1171,7 @@ def request_models():
         ode_method: str | None = None
         sample_rate: int | None = None               # the delivery format (infer.deliver_pcm16); None = 24 kHz 16-bit PCM in a WAV
         encoding: str | None = None
-        loudness: float | None = None                # programme loudness target in LUFS (infer.normalise_loudness_pcm16); None = the level as synthesized
+        loudness: float | dict | None = None         # programme loudness target in LUFS (infer.normalise_loudness_pcm16), or {"target": L, "true_peak": C} / {"true_peak": C}: the target with a true-peak limiter at C dBTP (infer.limit_pcm16); None = the level as synthesized
         flac_level: typing.Any = None                # 0 or 1 beside encoding "flac" (infer.check_flac_level); untyped, so that true and "1" arrive as sent and are refused
         response_format: str | None = None
 

@@ -1,6 +1,6 @@
 """Waves in and out of the server, with nothing of the model in it: reading WAV files (`load_wav`), torchaudio's polyphase sinc resampler
 (`rate_pair`, `resample_taps`, `resample_sinc_hann`) with its tap-table caches, the integer resampler of finished PCM (`resample_pcm16`,
-`StreamResampler`), the BS.1770 loudness meter and normaliser (`measure_loudness`, `normalise_loudness_pcm16`), G.711 (`encode_g711`,
+`StreamResampler`), the BS.1770 loudness meter and normaliser (`measure_loudness`, `normalise_loudness_pcm16`) and the true-peak limiter beside it (`true_peak_pcm16`, `limit_pcm16`), G.711 (`encode_g711`,
 `decode_g711`), FLAC (`encode_flac`, `decode_flac`, `StreamFlacEncoder`; the whole format in: `read_flac`, `load_audio`), the delivery
 format of a request (`delivery_format`, `deliver_pcm16`), time-scale modification of finished PCM (`wsola_pcm16`, `shift_pcm16`: a request's
 `tempo` and `pitch`; `psola_pcm16`: a `pitch` that keeps the formants, a request's `keep_formants`), the provenance watermark (`mark_pcm16`, `detect_watermark`: a request's `watermark` key), all nine of these options -- five of delivery, two of prosody, the key and the flag -- as one value (`WaveSpec`, `WAVE_OPTIONS`; `StreamDelivery` applies it to a stream) and the bytes of a response (`delivery_bytes`, `wav_bytes`, `wav_stream_header`).  A leaf module: `infer`, `serve` and `ops` import it, never the other way
@@ -410,7 +410,9 @@ class WaveSpec:
       `watermark`       a key, or a `WatermarkTag(key, id)` with a trace id (`check_watermark`): `mark_pcm16` behind the prosody step and in
                         front of the loudness step, so the level and the -1 dBFS peak cap are measured on the marked samples; None: no mark.
       `loudness`        a programme loudness target in LUFS within LOUDNESS_RANGE (ITU-R BS.1770-4; `normalise_loudness_pcm16`: the sample
-                        peak stays at or below -1 dBFS); None keeps the level as synthesized.
+                        peak stays at or below -1 dBFS); None keeps the level as synthesized.  As `LoudnessTag(target, true_peak)` (a
+                        request's `{"target": L, "true_peak": C}` or `{"true_peak": C}`; `check_loudness`): the target with no peak cap
+                        and a look-ahead limiter that holds the true peak at C dBTP (`limit_pcm16`); without a target the gain is unity.
       `sample_rate`, `encoding`  the delivery format (`deliver_pcm16`): one of OUTPUT_SAMPLE_RATES (`resample_pcm16`), then "pcm16", "mulaw" /
                         "alaw" (`encode_g711`: uint8 code bytes) or "flac" (`encode_flac`: a uint8 array that holds the whole stream).
       `flac_level`      0, or 1 for LPC subframes among the candidates of the stream's full blocks (never larger, the same samples); only a
@@ -419,7 +421,7 @@ class WaveSpec:
     (`needs_whole_wave`): they are refused for a list of chunk texts and with join=False; a stream applies the format piece by piece and
     refuses the others."""
     remove_silence: bool = False
-    loudness: float | None = None
+    loudness: float | LoudnessTag | None = None
     sample_rate: int = SAMPLE_RATE
     encoding: str = "pcm16"
     flac_level: int = 0
@@ -460,7 +462,13 @@ class WaveSpec:
     @property
     def gain_constant(self):
         """`loudness_gain_constant` of the target, what `ops.wave_loudness` takes; None without one."""
-        return None if self.loudness is None else loudness_gain_constant(self.loudness)
+        target = self.loudness.target if isinstance(self.loudness, LoudnessTag) else self.loudness
+        return None if target is None else loudness_gain_constant(target)
+
+    @property
+    def ceiling(self):
+        """`true_peak_ceiling` of a `LoudnessTag`, what `ops.wave_loudness(..., true_peak=)` takes; None without one."""
+        return true_peak_ceiling(self.loudness.true_peak) if isinstance(self.loudness, LoudnessTag) else None
 
     @property
     def prosody(self) -> bool:
@@ -594,9 +602,23 @@ def loudness_lufs(n2, S2):
 
 def check_loudness(target):
     """A request's `loudness` option: None (absent), or a finite number of LUFS within LOUDNESS_RANGE, returned as float; a bool, any
-    other type and a value outside the range are a ValueError."""
+    other type and a value outside the range are a ValueError.  `{"target": L, "true_peak": C}` or `{"true_peak": C}` (or a `LoudnessTag`)
+    asks for the true-peak limiter (`limit_pcm16`) and gives `LoudnessTag(L or None, C)`, C by `check_true_peak`; `{"target": L}` alone is
+    the float L.  An unknown entry and an empty mapping are a ValueError."""
     if target is None:
         return None
+    if isinstance(target, LoudnessTag):
+        target = target._asdict()
+    if isinstance(target, dict):
+        unknown = [k for k in target if k not in LoudnessTag._fields]
+        if unknown:
+            raise ValueError(f"loudness must be a number of LUFS or {{\"target\": L, \"true_peak\": C}} (unknown entry {unknown[0]!r})")
+        if isinstance(target.get("target"), (dict, LoudnessTag)):
+            raise ValueError(f"loudness must be a number of LUFS (got {target['target']!r})")
+        level, ceiling = check_loudness(target.get("target")), target.get("true_peak")
+        if level is None and ceiling is None:
+            raise ValueError("loudness must be a number of LUFS or a mapping with target or true_peak (got {})")
+        return level if ceiling is None else LoudnessTag(level, check_true_peak(ceiling))
     if isinstance(target, (bool, np.bool_)) or not isinstance(target, (int, float, np.integer, np.floating)):
         raise ValueError(f"loudness must be a number of LUFS (got {target!r})")
     target = float(target)
@@ -632,6 +654,151 @@ def normalise_loudness_pcm16(pcm, target) -> np.ndarray:
         return pcm
     g = loudness_gain(n2, S2, peak, loudness_gain_constant(target))
     return np.clip(np.rint(pcm.astype(np.float64) * g), -32768, 32767).astype(np.int16)
+
+
+# ----------------------------------------- true-peak limiter: a request's `loudness` as `LoudnessTag(target, true_peak)` -- the loudness target
+# reached without the sample-peak cap, and the reconstructed waveform held at or below `true_peak` dBTP by a look-ahead gain reduction.
+# Integers plus single correctly rounded fp64 operations, so that the device call (csrc/wave_limit.h wave_truepeak_kernel /
+# wave_limit_apply_kernel, f5hip_wave_loudness_limit) is held to `limit_pcm16` bit for bit.  x[j] = 0 outside the wave.
+#   true peak   a 4-phase interpolator, LIMIT_PHASE_TAPS = 12 taps a phase.  Phase 0 is the sample; phase p = 1, 2, 3 is the point i + p / 4:
+#               v_p[i] = sum_k t[p][k] x[i - 5 + k], t[p][k] = rint(2^14 c_k / sum_k c_k), c_k = sinc(d) I0(5 sqrt(1 - (d / 6)^2)) / I0(5) at
+#               d = k - 5 - p / 4 (`truepeak_taps()`, csrc/truepeak_taps.inc); m[i] = max(2^14 |x[i]|, |v_1[i]|, |v_2[i]|, |v_3[i]|)
+#   gain        G in Q16: 2^16 without a target or when nothing passes the meter's gates; else min(rint(2^16 sqrt(K_T n2 / S2)), 2^22), of
+#               `measure_loudness`'s (n2, S2) and `loudness_gain_constant`: int -> fp64, *, /, sqrt, * 2^16 (exact), rint.  No peak cap.
+#   reduction   c = floor(32767 10^(C / 20)) (`true_peak_ceiling`); r[i] = 2^16 where m[i] G <= c 2^30, else floor(c 2^46 / (m[i] G)); 2^16
+#               outside the wave
+#   hold        s[i] = min r[j] over |j - i| <= M, M = LIMIT_HOLD = 240 samples (10 ms look-ahead, 10 ms hold)
+#   release     a[i] = (sum_k w[k] s[i + k]) >> 16 over |k| <= M; w = `limit_window()`: 481 Hann weights that sum to exactly 2^16
+#               (csrc/limit_window.inc).  Every s[i + k] is a minimum over a window that holds i, so a[i] <= r[i] and m[i] G a[i] <= c 2^46.
+#   output      y[i] = clip(q), q = x[i] G a[i] / 2^32 rounded half to even (a 64-bit sum and a floor shift).  Where a = 2^16 that is rint(x G / 2^16).
+# Bit budget: sum_k |t[p][k]| < 2^15 (asserted), so |v_p| < 2^30 and m < 2^30 fit 32 bits; m G < 2^52; c 2^46 < 2^61; m G > c 2^30 gives
+# r >= floor(11626 2^46 / 2^52) = 181 > 0, so 2^16 - s < 2^16 and sum_k w[k] (2^16 - s[i + k]) < 2^32 (the device's 32-bit form of a);
+# |x G a| <= 2^15 2^22 2^16 = 2^53.
+# M is a design choice, not tuned on real speech: +-10 ms spans two pitch periods at 100 Hz, so the gain does not breathe with the glottal pulse.
+LoudnessTag = collections.namedtuple("LoudnessTag", "target true_peak")   # a loudness target (or None) beside a true-peak ceiling in dBTP
+LIMIT_PHASES, LIMIT_PHASE_TAPS, LIMIT_TAP_SHIFT, LIMIT_KAISER_BETA = 4, 12, 14, 5.0
+LIMIT_HOLD = 240
+LIMIT_UNITY, LIMIT_GAIN_MAX = 1 << 16, 1 << 22
+TRUE_PEAK_RANGE = (-9.0, 0.0)                      # ceilings a request may name, dBTP, in steps of 0.1
+_limit_tables: dict = {}
+
+
+def _bessel_i0(x: float) -> float:
+    """I0(x) by its power series, sum_k ((x / 2)^k / k!)^2, in fp64: 40 terms are past the last bit for x <= 5."""
+    total, term = 1.0, 1.0
+    for k in range(1, 40):
+        term *= (x / 2.0) / k
+        total += term * term
+    return total
+
+
+def truepeak_taps() -> np.ndarray:
+    """The interpolator's phases 1 .. 3 as int64 [3, 12] (read-only) by the formula above.  Computed once."""
+    if "taps" not in _limit_tables:
+        rows = []
+        for p in range(1, LIMIT_PHASES):
+            d = [k - 5 - p / LIMIT_PHASES for k in range(LIMIT_PHASE_TAPS)]
+            c = [math.sin(math.pi * v) / (math.pi * v) * _bessel_i0(LIMIT_KAISER_BETA * math.sqrt(1.0 - (v / 6.0) ** 2)) / _bessel_i0(LIMIT_KAISER_BETA)
+                 for v in d]
+            rows.append([round(2.0 ** LIMIT_TAP_SHIFT * v / sum(c)) for v in c])          # (round: half to even)
+        taps = np.asarray(rows, dtype=np.int64)
+        assert int(np.abs(taps).sum(axis=1).max()) < 1 << 15, taps                         # the bit budget: |v_p| < 2^30
+        taps.setflags(write=False)
+        _limit_tables["taps"] = taps
+    return _limit_tables["taps"]
+
+
+def limit_window() -> np.ndarray:
+    """The release window, int64 [2 M + 1] (read-only): w[k] = rint(2^16 (1 + cos(pi k / (M + 1))) / (2 (M + 1))) for |k| <= M -- the real
+    weights sum to 1 --, and the centre weight takes what the rounding left, so that the sum is exactly 2^16."""
+    if "window" not in _limit_tables:
+        M = LIMIT_HOLD
+        w = np.asarray([round(65536.0 * (1.0 + math.cos(math.pi * k / (M + 1))) / (2.0 * (M + 1))) for k in range(-M, M + 1)], dtype=np.int64)
+        w[M] += LIMIT_UNITY - int(w.sum())
+        assert int(w.sum()) == LIMIT_UNITY and int(w.min()) >= 0 and (w == w[::-1]).all()
+        w.setflags(write=False)
+        _limit_tables["window"] = w
+    return _limit_tables["window"]
+
+
+def check_true_peak(value) -> float:
+    """A `true_peak` ceiling in dBTP: a multiple of 0.1 (within 1e-9) inside TRUE_PEAK_RANGE, as float; anything else is a ValueError."""
+    bad = ValueError(f"loudness must have a true_peak that is a multiple of 0.1 dBTP from -9 to 0 (got {value!r})")
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise bad
+    tenths = 10.0 * float(value)
+    if not math.isfinite(tenths) or abs(tenths - round(tenths)) > 1e-9 or not 10 * TRUE_PEAK_RANGE[0] <= round(tenths) <= 10 * TRUE_PEAK_RANGE[1]:
+        raise bad
+    return round(tenths) / 10.0
+
+
+def true_peak_ceiling(true_peak) -> int:
+    """c of a ceiling in dBTP: floor(32767 10^(C / 20)) in fp64, 11626 .. 32767 -- what the device call takes per request (-1.0 gives
+    LOUDNESS_PEAK_CEILING)."""
+    return math.floor(32767.0 * 10.0 ** (check_true_peak(true_peak) / 20.0))
+
+
+def true_peak_pcm16(pcm) -> np.ndarray:
+    """m of 24 kHz int16 PCM by the definition above, int64 [n] at the taps' scale (2^14 times a sample): the largest magnitude of sample
+    i and of the three interpolated points between i and i + 1."""
+    x = _as_pcm16(pcm).astype(np.int64)
+    m = np.abs(x) << LIMIT_TAP_SHIFT
+    if len(x):
+        xp = np.concatenate([np.zeros(5, np.int64), x, np.zeros(6, np.int64)])
+        for t in truepeak_taps():
+            m = np.maximum(m, np.abs(np.correlate(xp, t, "valid")))
+    return m
+
+
+def true_peak_db(m) -> float:
+    """The reading of `true_peak_pcm16`'s largest m in dBTP (re 32767); -inf for silence."""
+    top = int(np.max(m)) if len(m) else 0
+    return 20.0 * math.log10(top / (32767.0 * 2.0 ** LIMIT_TAP_SHIFT)) if top else -math.inf
+
+
+def limit_gain(n2, S2, gain_k) -> int:
+    """G of `measure_loudness`'s (n2, S2) and K_T = `gain_k` (None: no target), Q16, by the definition above."""
+    if gain_k is None or not n2:
+        return LIMIT_UNITY
+    return min(int(np.rint(65536.0 * math.sqrt(gain_k * float(n2) / float(S2)))), LIMIT_GAIN_MAX)
+
+
+def limit_envelope(m, G, c) -> np.ndarray:
+    """a of the readings m, the gain G and the ceiling c, int64 [n] in Q16: reduction, hold and release by the definition above."""
+    M, n = LIMIT_HOLD, len(m)
+    mg = np.asarray(m, dtype=np.int64) * int(G)
+    over = mg > c << 30
+    if not over.any():
+        return np.full(n, LIMIT_UNITY, dtype=np.int64)
+    r = np.full(n + 4 * M, LIMIT_UNITY, dtype=np.int64)                  # r over [-2 M, n + 2 M)
+    r[2 * M:2 * M + n][over] = (c << 46) // mg[over]
+    span, width = r, 1                                                   # minima over [j, j + width), doubled up to 256; then two of them make 481
+    while width < 256:
+        span = np.minimum(span[:-width], span[width:])
+        width *= 2
+    s = np.minimum(span[:n + 2 * M], span[2 * M + 1 - width:][:n + 2 * M])   # s over [-M, n + M)
+    # w <= 2^16 / 241 and s <= 2^16: every product and partial sum is an integer below 2^53, so the fp64 convolution is exact in any order
+    return np.convolve(s.astype(np.float64), limit_window().astype(np.float64), "valid").astype(np.int64) >> 16
+
+
+def limit_samples(pcm, G, c) -> np.ndarray:
+    """The limiter's output for the gain G (Q16) and the ceiling c by the definition above: reading, reduction, hold, release, output."""
+    pcm = _as_pcm16(pcm)
+    p = pcm.astype(np.int64) * int(G) * limit_envelope(true_peak_pcm16(pcm), G, c)
+    q = (p + (1 << 31) - 1 + ((p >> 32) & 1)) >> 32                       # p / 2^32, half to even
+    return np.clip(q, -32768, 32767).astype(np.int16)
+
+
+def limit_pcm16(pcm, loudness) -> np.ndarray:
+    """What a request's `loudness` (`check_loudness`) makes of its 24 kHz int16 PCM.  None returns the input and a number is
+    `normalise_loudness_pcm16`; a `LoudnessTag` is the limiter defined above: the gain of its target (unity without one) with no peak cap,
+    reduced around every stretch whose true-peak reading times the gain stands above its ceiling.  The length is kept and zeros stay
+    zeros.  What `ops.wave_loudness(..., true_peak=)` equals byte for byte."""
+    pcm, loudness = _as_pcm16(pcm), check_loudness(loudness)
+    if not isinstance(loudness, LoudnessTag):
+        return normalise_loudness_pcm16(pcm, loudness)
+    G = LIMIT_UNITY if loudness.target is None else limit_gain(*measure_loudness(pcm)[:2], loudness_gain_constant(loudness.target))
+    return limit_samples(pcm, G, true_peak_ceiling(loudness.true_peak))
 
 
 # ----------------------------------------- prosody: a request's `tempo` and `pitch`, time-scale modification of its 24 kHz int16 PCM (WSOLA,
