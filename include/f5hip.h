@@ -40,7 +40,15 @@ typedef struct f5hip_dit_config {
                             3 = mixed: fp16 operands for the transformer-block GEMMs (QKV, out, FF1, FF2), bf16x3 for every GEMM that
                                 touches the ODE state / embeddings / U-skips (3.1e-4 mel RMS for F5-Base at 32 NFE, 4.9e-4 for E2-Base
                                 at 64 NFE, against the reference's own CFM.sample outputs: inside the 1e-3 bound);
-                            1 = plain bf16 (fast, ~8e-3 mel RMS: outside the bound) */
+                            1 = plain bf16 (fast, ~8e-3 mel RMS: outside the bound);
+                            4 = mode 3 with the out, FF1 and FF2 projections of every block in MXFP8 (OCP Microscaling v1.0: E4M3 elements,
+                                one E8M0 scale per 32 elements along K; v_mfma_scale_f32_16x16x128_f8f6f4, csrc/gemm8.h).  The weights are
+                                quantised once at finalize and kept in MXFP8 only; the fp16 activations are quantised inside the kernel.  QKV
+                                stays fp16 (its rotary / transposed-V epilogue is tied to the fp16 kernels' tile layout), as does any shape
+                                gemm8 does not cover (K % 128, N padded % 128).  Opt-in, far outside the bound and today slower than mode 3
+                                (profiles/gemm8_bench.txt: 1.2-1.8x per GEMM): measured on the same fixtures in one run, mel RMS mode 1 /
+                                3 / 4 = 8.3e-3 / 2.9e-4 / 3.3e-2 for F5-Base at 32 NFE, 6.3e-3 / 3.4e-4 / 4.5e-2 for the F5-Small forward,
+                                6.0e-3 / 4.8e-4 / 6.1e-2 for the tiny UNetT */
     int32_t arch;        /* 0 = DiT (F5-TTS, F/model/backbones/dit.py), 1 = UNetT (E2-TTS, F/model/backbones/unett.py: text_dim = mel_dim, conv_layers = 0),
                             2 = MMDiT (F/model/backbones/mmdit.py: text_dim = dim, conv_layers = 0; state_dict keys transformer.audio_embed.*,
                                 transformer.transformer_blocks.{i}.attn_norm_{c,x} / attn.to_{q,k,v}[_c] / attn.to_out[_c] / ff_{c,x}) */
@@ -215,7 +223,9 @@ int f5hip_get_counter(const char* name, int64_t* value);
  * f5hip_op_gemm: out = (act(A W^T + bias), rows with row_keep == 0 zeroed) * mul + res   -- nn.Linear + the fused epilogue of
  *   Attention.to_out / FeedForward (F/model/modules.py:324-328,441-447,566-571).
  *   a_dev [M][K], w_dev [N][K] (nn.Linear layout), bias_dev [N] | NULL, mul_dev [N] | NULL (AdaLN gate), res_dev [M][N] | NULL,
- *   row_keep_host uint8 [M] | NULL (host); prec 1 = bf16, 2 = split bf16 (bf16x3), 3 = fp16 operands, fp32 accumulate;
+ *   row_keep_host uint8 [M] | NULL (host); prec 1 = bf16, 2 = split bf16 (bf16x3), 3 = fp16 operands, fp32 accumulate; 4 = MXFP8 operands
+ *   (a block GEMM of gemm_planes == 4: W quantised from its fp32 values, A from its fp16 plane; counter "gemm8"), where K % 128 == 0 --
+ *   any other shape takes the prec 3 path, bit for bit;
  *   act 0 none, 1 GELU(tanh), 2 GELU(erf), 3 Mish, 4 SiLU.  out_dev fp32 [M][N], or out16_dev: one fp16 plane [M][N] (the operand the
  *   next fp16 GEMM reads; saturates at +-65504).  iters > 0: also times `iters` launches with HIP events on `stream`, cycling through
  *   w_copies copies of the packed weights (a pool larger than the Infinity Cache makes them HBM-cold as in the real forward).

@@ -47,7 +47,9 @@ struct f5hip_dit {
     ProfState* prof = nullptr;        // f5hip_dit_set_profiling: this handle's own HIP-event spans and totals (null: the process-wide state)
     HostStage up_meta, up_time[2], up_grid;   // pinned staging of the per-call uploads (row metadata; the two planes of the sinusoid table;
                                               // f5hip_cfm_sample_grids' unit tables)
-    bool blk_f16 = false; // gemm_planes == 3: transformer-block GEMMs (QKV, out, FF1, FF2) take one fp16 plane per operand
+    bool blk_f16 = false; // gemm_planes >= 3: transformer-block GEMMs (QKV, out, FF1, FF2) take one fp16 plane per operand
+    bool blk_mx8 = false; // gemm_planes == 4: ... and out, FF1, FF2 multiply in MXFP8 (gemm8.h): their weights are packed as E4M3 + E8M0 planes
+                          // (pack_mx8_host), their A operand stays the fp16 plane.  QKV stays fp16: its rotary / transposed-V slabs are gemm5's own
     ParamStore params;
     bool finalized = false;
     // packed weights
@@ -105,7 +107,7 @@ static int ceil_to(int v, int m) { return (v + m - 1) / m * m; }
 f5hip_dit* f5hip_dit_create(const f5hip_dit_config* cfg) {
     if (!cfg) { set_error("null config"); return nullptr; }
     if (cfg->dim % 128 || cfg->dim != cfg->heads * 64 || cfg->dim % 16 || cfg->text_dim % 4 || cfg->mel_dim > 128 || cfg->mel_dim % 4 ||
-        cfg->dim / 16 > 64 || cfg->gemm_planes < 1 || cfg->gemm_planes > 3 || cfg->arch < 0 || cfg->arch > 2 ||
+        cfg->dim / 16 > 64 || cfg->gemm_planes < 1 || cfg->gemm_planes > 4 || cfg->arch < 0 || cfg->arch > 2 ||
         (cfg->arch == 1 && (cfg->conv_layers != 0 || cfg->depth % 2)) || (cfg->conv_layers > 0 && cfg->text_dim % 32) ||
         (cfg->arch == 2 && (cfg->conv_layers != 0 || cfg->text_dim != cfg->dim || cfg->depth < 1))) {
         set_error("unsupported backbone geometry (need dim %% 128 == 0, dim == 64*heads, dim/16 <= 64, mel_dim <= 128, text conv needs text_dim %% 32 == 0; UNetT: even depth, no text conv)");
@@ -118,10 +120,11 @@ f5hip_dit* f5hip_dit_create(const f5hip_dit_config* cfg) {
     }
     f5hip_dit* m = new f5hip_dit();
     m->cfg = *cfg;
-    m->nsplit = cfg->gemm_planes == 3 ? 2 : cfg->gemm_planes;
+    m->nsplit = cfg->gemm_planes >= 3 ? 2 : cfg->gemm_planes;
     // both backbones: against the reference's own digests mixed mode measures 3.1e-4 rms (F5-Base, 32 NFE) and 4.9e-4 (E2-Base, N = 2340,
     // 64 NFE) of the 1e-3 bound; the U-skip projections, the final norm + proj_out and the input embedding stay split bf16
-    m->blk_f16 = cfg->gemm_planes == 3;
+    m->blk_f16 = cfg->gemm_planes >= 3;
+    m->blk_mx8 = cfg->gemm_planes == 4;
     m->arch = cfg->arch;
     m->td_pad = cfg->arch == 2 ? 0 : ceil_to(cfg->text_dim, 32);   // MMDiT: the text never enters the input projection (mmdit.py:64-70)
     m->gw = cfg->dim / 16;
@@ -137,7 +140,7 @@ f5hip_dit* f5hip_dit_create(const f5hip_dit_config* cfg) {
     return m;
 }
 
-static void free_packed(PackedW& w) { dev_free(w.hi); dev_free(w.lo); dev_free(w.bias); dev_free(w.frag); w = PackedW(); }
+static void free_packed(PackedW& w) { dev_free(w.hi); dev_free(w.lo); dev_free(w.bias); dev_free(w.frag); dev_free(w.w8); dev_free(w.s8); w = PackedW(); }
 
 void f5hip_dit_destroy(f5hip_dit* m) {
     if (!m) return;
@@ -199,11 +202,11 @@ static int pack_block(f5hip_dit* m, BlockWeights& w, int l, const std::string& a
     if (pack_linear(w.qkv[l], wq.data(), 3 * D, D, D, bq.data(), 128, m->blk_f16) || pack_frag(w.qkv[l])) return -4;
     if (out.empty()) return 0;
     GET_PARAM(wo, P, out + ".weight", (int64_t)D * D); GET_PARAM(bo, P, out + ".bias", D);
-    if (pack_linear(w.out[l], wo->data(), D, D, D, bo->data(), 128, m->blk_f16)) return -4;
+    if (pack_linear(w.out[l], wo->data(), D, D, D, bo->data(), 128, m->blk_f16) || (m->blk_mx8 && pack_mx8_host(w.out[l], wo->data()))) return -4;
     GET_PARAM(w1, P, ff + "ff.0.0.weight", (int64_t)F * D); GET_PARAM(b1, P, ff + "ff.0.0.bias", F);
-    if (pack_linear(w.ff1[l], w1->data(), F, D, D, b1->data(), 128, m->blk_f16) || pack_frag(w.ff1[l])) return -4;
+    if (pack_linear(w.ff1[l], w1->data(), F, D, D, b1->data(), 128, m->blk_f16) || (m->blk_mx8 && pack_mx8_host(w.ff1[l], w1->data())) || pack_frag(w.ff1[l])) return -4;
     GET_PARAM(w2, P, ff + "ff.2.weight", (int64_t)D * F); GET_PARAM(b2, P, ff + "ff.2.bias", D);
-    if (pack_linear(w.ff2[l], w2->data(), D, F, F, b2->data(), 128, m->blk_f16)) return -4;
+    if (pack_linear(w.ff2[l], w2->data(), D, F, F, b2->data(), 128, m->blk_f16) || (m->blk_mx8 && pack_mx8_host(w.ff2[l], w2->data()))) return -4;
     return 0;
 }
 
@@ -557,7 +560,8 @@ static GemmArgs gemm_base(const Plane2& A, int lda, const PackedW& W, int M) {
 // (a call without an id counts on wave_mark_*); watermark_read_ids_launches / watermark_read_ids_clips: kernels f5hip_watermark_read_ids
 // launched and the clips it read; watermark_scan_launches / watermark_scan_ranges: kernels f5hip_watermark_scan launched and the ranges it scored;
 // wave_limit_launches / wave_limit_requests: kernels f5hip_wave_loudness_limit launched in calls where a request had a true-peak ceiling and
-// the requests with one (such a call's requests with a target alone count on wave_loudness_requests; a call without a ceiling on wave_loudness_*)
+// the requests with one (such a call's requests with a target alone count on wave_loudness_requests; a call without a ceiling on wave_loudness_*);
+// gemm8: launches of the MXFP8 kernel (gemm8.h)
 enum { CNT_GEMM5_RB11, CNT_GEMM5_RB8, CNT_GEMM5_WIDE, CNT_GEMM3_WIDE, CNT_CONV5, CNT_GEMM6, CNT_GEMM6_R176, CNT_GEMM6_R256, CNT_GEMM5_CB12,
        CNT_GEMM3, CNT_GEMM_REG_BN64, CNT_GEMM_REG_BN128, CNT_DIT_ROWS, CNT_REF_LAUNCHES, CNT_REF_TAPS_LDS, CNT_REF_TAPS_L2, CNT_WAVE_LAUNCHES,
        CNT_WAVE_REQUESTS, CNT_WAVE_ENCODE_LAUNCHES, CNT_WAVE_ENCODE_REQUESTS, CNT_MEL_RAGGED_LAUNCHES, CNT_MEL_RAGGED_ITEMS, CNT_WAVE_FLAC_LAUNCHES,
@@ -567,10 +571,11 @@ enum { CNT_GEMM5_RB11, CNT_GEMM5_RB8, CNT_GEMM5_WIDE, CNT_GEMM3_WIDE, CNT_CONV5,
        CNT_WAVE_FORMANT_REQUESTS, CNT_WATERMARK_DETECT_LAUNCHES,
        CNT_WATERMARK_DETECT_CLIPS, CNT_REF_ASSESS_LAUNCHES, CNT_REF_ASSESS_CLIPS, CNT_GEMM3_THIN, CNT_TIME_TABLE_BUILDS,
        CNT_WAVE_MARK_ID_LAUNCHES, CNT_WAVE_MARK_ID_REQUESTS, CNT_WATERMARK_READ_IDS_LAUNCHES, CNT_WATERMARK_READ_IDS_CLIPS,
-       CNT_WATERMARK_SCAN_LAUNCHES, CNT_WATERMARK_SCAN_RANGES, CNT_WAVE_LIMIT_LAUNCHES, CNT_WAVE_LIMIT_REQUESTS, CNT_COUNT };
+       CNT_WATERMARK_SCAN_LAUNCHES, CNT_WATERMARK_SCAN_RANGES, CNT_WAVE_LIMIT_LAUNCHES, CNT_WAVE_LIMIT_REQUESTS, CNT_GEMM8, CNT_COUNT };
 static long long g_counters[CNT_COUNT] = {};
 
 // Kernel choice per GEMM (measured: profiles/r02_fillrate_microbench.txt, profiles/r01_gemm_microbench.txt):
+//   MXFP8 weight planes present (gemm_planes / prec 4) and a shape gemm8 covers: gemm8; else
 //   fp16 one-plane operands: gemm6 for the batch-mode shapes (gemm6_choose_rows), else gemm5 (exact-fit tiles) when K % 64 == 0,
 //   else gemm3; implicit-GEMM convolutions in fp16 on gemm.h;
 //   one 128 x 128 tile per CU or fewer, generic epilogue, bf16 / split-bf16 operands: gemm3 (warp-specialised LDS-DMA ring);
@@ -595,7 +600,10 @@ static int run_gemm_n(int nsplit, int mp, GemmArgs& a, const PackedW& W, int epi
     if (mp % 128 || np % bn || a.K % 32) return fail(-7, "gemm: bad padded shape %d x %d x %d", mp, np, a.K);
     prof_begin(PROF_GEMM, st);
     const long long tiles128 = (long long)(mp / 128) * (np / 128);
-    if (nsplit == 3 && !conv) {   // fp16 operands, one plane each
+    if (nsplit == 3 && !conv && W.w8 && gemm8_covers(epi, a.K, np)) {   // MXFP8 weights; A = the fp16 plane
+        e = f5_launch_gemm8(epi, a, W.w8, W.s8, np, st);
+        g_counters[CNT_GEMM8]++;
+    } else if (nsplit == 3 && !conv) {   // fp16 operands, one plane each
         const Gemm5Choice c5 = gemm5_choose(a.M, np);
         // gemm6 (256 x 256 ping-pong tiles): the batch-mode shapes -- enough tiles to occupy the chip in their first round
         const bool legal6 = a.K % 64 == 0 && np % 256 == 0 && (epi != EPI_QKV || a.D % 256 == 0);
@@ -691,7 +699,7 @@ extern "C" int f5hip_get_counter(const char* name, int64_t* value) {
                                            "ref_assess_launches", "ref_assess_clips", "gemm3_thin", "time_table_builds",
                                            "wave_mark_id_launches", "wave_mark_id_requests", "watermark_read_ids_launches",
                                            "watermark_read_ids_clips", "watermark_scan_launches", "watermark_scan_ranges", "wave_limit_launches",
-                                           "wave_limit_requests"};
+                                           "wave_limit_requests", "gemm8"};
     static const char* attn_names[F5_ATTN_CNT_COUNT] = {"attn_bal8", "attn_nw8_deep", "attn_nw8", "attn_nw6_deep", "attn_nw6", "attn_nw4", "attn_seg2"};
     long long* attn = f5_attn_counters();
     if (!name) return fail(-1, "get_counter: null name");

@@ -27,6 +27,13 @@ static inline int gemm6_choose_rows(int m_rows, int n_pad) {
     const double c256 = (double)((t256 + 255) / 256), c176 = 0.85 * (double)((t176 + 255) / 256);
     return c176 < c256 ? 176 : 256;
 }
+// gemm8.h: MXFP8 operands (gemm_planes == 4), 64 x {256, 128} tiles, 128-deep k-steps: W from the fragment-ordered E4M3 plane w8 and its E8M0
+// scale plane s8 (f5_launch_quant_w8), A from the fp16 plane a.A[0], quantised on the way in; a.W / a.Wf are not read.
+// Shapes: K a multiple of 128, n_pad of 128; EPI_GENERIC and EPI_GENERIC_ROWMUL (QKV stays on the fp16 kernels)
+static inline bool gemm8_covers(int epi, int K, int n_pad) { return epi != EPI_QKV && K >= 128 && K % 128 == 0 && n_pad >= 128 && n_pad % 128 == 0; }
+hipError_t f5_launch_gemm8(int epi, const GemmArgs& a, const unsigned char* w8, const unsigned int* s8, int n_pad, hipStream_t st);
+// w fp32 [N][K] (device, row stride ldw) -> w8 [n_pad x K bytes], s8 [(n_pad / 16) x ceil(K / 512) x 64 dwords, zeroed by the caller]; K % 128 == 0
+hipError_t f5_launch_quant_w8(const float* w, int N, int n_pad, int K, int ldw, unsigned char* w8, unsigned int* s8, hipStream_t st);
 // conv5.h: sliding-window Conv1d (the window of a 256-row tile once in LDS, taps served from it); hipErrorInvalidValue = shape not covered
 hipError_t f5_launch_conv5(int prec, const GemmArgs& a, int n_pad, hipStream_t st);
 // attn3.h: flash attention forward, 256 queries per workgroup

@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "elementwise.h"
+#include "gemm_launch.h"
 
 // ---------------------------------------------------------------- errors
 static thread_local char g_err[512] = "";
@@ -41,6 +42,9 @@ struct PackedW {
     __bf16* frag = nullptr;   // f16 weights once more in MFMA-fragment order (pack_frag: the W-direct gemm5 kernels), or null
     int n = 0, k = 0, n_pad = 0, k_pad = 0, ld = 0;
     bool f16 = false;   // hi holds one fp16 plane, lo == nullptr
+    // MXFP8 (gemm_planes == 4, pack_mx8): the E4M3 plane in gemm8.h's fragment order and its E8M0 scale plane, or null
+    unsigned char* w8 = nullptr;
+    unsigned int* s8 = nullptr;
 };
 
 template <typename T> static void dev_free(T* p) { if (p) (void)hipFree((void*)p); }
@@ -186,6 +190,29 @@ static int pack_frag(PackedW& w, hipStream_t st = 0) {
     if (hipMalloc((void**)&w.frag, n * 2) != hipSuccess) { w.frag = nullptr; return fail(-4, "hipMalloc fragment-ordered weight %d x %d", w.n_pad, w.k_pad); }
     hipLaunchKernelGGL(pack_frag_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, st, w.hi, w.n_pad, w.k_pad, w.ld, w.frag);
     return hipGetLastError() == hipSuccess ? 0 : fail(-4, "pack_frag_kernel");
+}
+
+// MXFP8 planes of a weight (gemm8.h) from its fp32 values on the DEVICE, w_dev [w.n][w.k] with row stride ldw, for the shapes gemm8 covers
+// (others: nothing happens, the GEMM stays on the fp16 plane).  Waits for the quantiser and checks it before returning.
+static int pack_mx8(PackedW& w, const float* w_dev, int ldw, hipStream_t st = 0) {
+    if (w.w8 || w.k != w.k_pad || !gemm8_covers(EPI_GENERIC, w.k_pad, w.n_pad)) return 0;
+    const size_t sbytes = (size_t)(w.n_pad / 16) * ((w.k_pad / 128 + 3) / 4) * 64 * 4;
+    if (hipMalloc((void**)&w.w8, (size_t)w.n_pad * w.k_pad) != hipSuccess) { w.w8 = nullptr; return fail(-4, "hipMalloc MXFP8 weight %d x %d", w.n_pad, w.k_pad); }
+    if (hipMalloc((void**)&w.s8, sbytes) != hipSuccess) { w.s8 = nullptr; return fail(-4, "hipMalloc MXFP8 scales %d x %d", w.n_pad, w.k_pad); }
+    hipError_t e = hipMemsetAsync(w.s8, 0, sbytes, st);
+    if (e == hipSuccess) e = f5_launch_quant_w8(w_dev, w.n, w.n_pad, w.k_pad, ldw, w.w8, w.s8, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e == hipSuccess ? 0 : fail(-4, "quant_w8_kernel: %s", hipGetErrorString(e));
+}
+// ... from host values: the block weights of f5hip_dit_finalize.  A covered weight keeps ONLY its MXFP8 planes (the fp16 plane is freed)
+static int pack_mx8_host(PackedW& w, const float* w_host) {
+    if (w.k != w.k_pad || !gemm8_covers(EPI_GENERIC, w.k_pad, w.n_pad)) return 0;
+    float* tmp = nullptr;
+    if (upload_f32(&tmp, w_host, (size_t)w.n * w.k)) { dev_free(tmp); return -4; }
+    const int rc = pack_mx8(w, tmp, w.k);
+    dev_free(tmp);
+    if (!rc) { dev_free(w.hi); w.hi = nullptr; }
+    return rc;
 }
 
 // Runs launch(i) for i = 0 .. warmup + iters - 1 (an int-returning launch, 0 = success) and writes the average time of the last `iters`,

@@ -124,8 +124,10 @@ static int op_gemm_run(int32_t M, int32_t N, int32_t K, const float* a_dev, cons
                        const float* mul_dev, const int32_t* row_mod_host, int32_t mod_ld, const float* res_dev, const uint8_t* row_keep_host,
                        float* out_dev, uint16_t* out16_dev, int32_t w_copies, int32_t iters, double* avg_us, void* stream, int32_t bn) {
     const int epi = row_mod_host ? EPI_GENERIC_ROWMUL : EPI_GENERIC;
-    if (M <= 0 || N <= 0 || K <= 0 || K % 32 || N % 4 || !a_dev || !w_dev || prec < 1 || prec > 3 || (!out_dev && !out16_dev))
-        return fail(-1, "op_gemm: bad argument (need K %% 32 == 0, N %% 4 == 0, prec 1..3)");
+    if (M <= 0 || N <= 0 || K <= 0 || K % 32 || N % 4 || !a_dev || !w_dev || prec < 1 || prec > 4 || (!out_dev && !out16_dev))
+        return fail(-1, "op_gemm: bad argument (need K %% 32 == 0, N %% 4 == 0, prec 1..4)");
+    const bool mx8 = prec == 4;   // prec 3 with the weights' MXFP8 planes beside the fp16 one, like a block GEMM of gemm_planes == 4
+    if (mx8) prec = 3;
     if (bn == 0) bn = 128;
     if (bn != 64 && bn != 128) return fail(-1, "op_gemm: bn must be 0, 64 or 128 (got %d)", bn);
     if (out16_dev && (res_dev || out_dev)) return fail(-1, "op_gemm: the 16-bit output is the (no residual, no fp32 output) epilogue");
@@ -153,6 +155,12 @@ static int op_gemm_run(int32_t M, int32_t N, int32_t K, const float* a_dev, cons
         op_pack_planes(w_dev, N, K, N_pad, W.hi, W.lo, f16, st);
         if (f16 && N >= 2048 && pack_frag(W, st)) return -5;   // like the model's FF1 weights: fragment order for the W-direct kernels (freed with b)
         if (W.frag) b.ptrs.push_back(W.frag);
+        if (mx8) {
+            const int rc = pack_mx8(W, w_dev, K, st);
+            if (W.w8) b.ptrs.push_back(W.w8);
+            if (W.s8) b.ptrs.push_back(W.s8);
+            if (rc) return rc;
+        }
     }
     op_pack_planes(a_dev, M, K, M_pad, A.hi, A.lo, f16, st);
     (void)hipMemsetAsync(bias, 0, sizeof(float) * N_pad, st);

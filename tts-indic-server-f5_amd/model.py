@@ -224,7 +224,7 @@ class F5HipModel:
         self.vocab_char_map = vocab_char_map
         self.mel_spec_type = mel_spec_type
         self.num_channels = arch.mel_dim
-        self.gemm_planes = gemm_planes   # 3 = mixed parity mode (default), 2 = bf16x3 everywhere, 1 = plain bf16 (include/f5hip.h)
+        self.gemm_planes = gemm_planes   # 3 = mixed parity mode (default), 2 = bf16x3 everywhere, 1 = plain bf16, 4 = mode 3 with MXFP8 out / FF1 / FF2 (opt-in; include/f5hip.h)
         self._lib = _lib.lib()
         if self.device.type != "cuda":
             raise _lib.F5HipError("F5HipModel needs a HIP device (no CPU fallback)")
