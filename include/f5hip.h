@@ -870,6 +870,26 @@ int64_t f5hip_ref_prestep_bound(int32_t n, const int32_t* n_in, const int32_t* c
  * more than 2^31 - 1 frame rows. */
 int f5hip_ref_denoise(int32_t n, const int64_t* offset, const int32_t* n_samples, float* wave_dev, void* stream);
 
+/* The per-voice dereverberator of uploaded reference clips for n clips in one call, IN PLACE on mono 24 kHz fp32 samples (f5hip_ref_frontend's
+ * packed output, in front of f5hip_ref_denoise): audio_prep.dereverb_reference in fp32 -- weighted prediction error (WPE), a delayed linear
+ * prediction fitted and subtracted per frequency bin.  f5hip_ref_denoise's framing and X; x~[f][j] = X[f - 4 - j], j = 0 .. 15, zero before
+ * the clip; three iterations from Y = X of lam[f] = max(mean |Y|^2 over frames f - 1 .. f + 1 (edges repeated), 1e-3 mean_f |X|^2 + 1e-20),
+ * R = sum_f x~ x~^H / lam, p = sum_f x~ conj(X) / lam, R += (1e-3 tr R / 16 + 1e-20) I, g = R^-1 p, Y = X - g^H x~; out = overlap_add(irfft(Y) w)
+ * / 2.  The length is kept, a silent clip stays silent, a clip of at most four frames is its own STFT round trip.
+ *   offset[i], n_samples[i], wave_dev   as f5hip_ref_denoise takes them: samples between the ranges and clips left out of the table are not touched
+ * FOUR launches whatever n (f5hip_ref_dereverb_launches; stft: f5hip_ref_denoise's; wpe: one workgroup per (clip, 8 bins), a wave per bin through
+ * all three iterations -- the bin's frames staged in LDS in chunks of f5hip_ref_dereverb_chunk() frames, ascending, the 32 x 32 real embedding
+ * of R accumulated by v_mfma_f32_32x32x2_f32 on fp32 operands, a 16 x 16 complex Cholesky solve and the filter in LDS; inverse: the Hermitian
+ * fill and the inverse transform, times w / 1024; ola: f5hip_ref_denoise's), no host synchronisation once its workspace has grown to the
+ * call's size (counters ref_dereverb_launches, ref_dereverb_clips; geometry csrc/ref_dereverb_core.h, which tools/ref_dereverb_check.cpp
+ * walks on the CPU under sanitizers).  Clip i's output equals its own single-clip call's bit for bit.
+ * Refused before the first launch: what f5hip_ref_denoise refuses. */
+int f5hip_ref_dereverb(int32_t n, const int64_t* offset, const int32_t* n_samples, float* wave_dev, void* stream);
+
+/* Kernels one f5hip_ref_dereverb call launches (4), and the frames its Gram pass stages at a time (128). */
+int f5hip_ref_dereverb_launches(void);
+int f5hip_ref_dereverb_chunk(void);
+
 /* Provenance watermark, embedding: the 24 kHz int16 PCM of n requests, still on the device (f5hip_wave_finish's or f5hip_wave_prosody's
  * buffer), IN PLACE, with the mark of each flagged request's key added -- bit for bit wave_codec.mark_pcm16.  Not in the reference.  It runs
  * behind f5hip_wave_prosody and before f5hip_wave_loudness / f5hip_wave_encode / f5hip_wave_flac, which read the marked samples.  The

@@ -545,6 +545,77 @@ def denoise_reference_f64(wave) -> np.ndarray:
     return out[DENOISE_PAD:DENOISE_PAD + n] / 2.0
 
 
+# ------------------------------------------------------------------------------------------------ dereverberating an uploaded reference clip
+# The definition of the per-voice `dereverb` option (`infer.PreparedVoice(..., dereverb=True)`; on the device `ops.ref_dereverb`,
+# csrc/ref_dereverb.h): weighted prediction error (WPE; Nakatani, Yoshioka, Kinoshita, Miyoshi, Juang 2010), single channel -- a delayed
+# linear prediction fitted and subtracted per frequency bin -- on the front-end's output, in front of the denoiser, in float64:
+#   framing     the denoiser's, so that its STFT and overlap-add serve both: DENOISE_PAD zeros in front, F = denoise_frames(n) frames of 1024
+#               at hop 256, w[i] = sin(pi i / 1024), X[f, k] = rfft(frame_f * w), k = 0 .. 512
+#   taps        x~[f, k, j] = X[f - D - j, k] for j = 0 .. K - 1, zero where the index is negative; D = 4 frames, so the first tap does not
+#               overlap the current frame, K = 16
+#   iterations  I = 3, from Y = X; each, per bin k:
+#                 lam[f] = max((|Y[f-1]|^2 + |Y[f]|^2 + |Y[f+1]|^2) / 3, 1e-3 * mean_f |X[f]|^2 + 1e-20), edge frames repeated
+#                 R = sum_f x~ x~^H / lam[f];  p = sum_f x~ conj(X[f]) / lam[f], f ascending
+#                 R += (1e-3 * tr(R) / K + 1e-20) I;  g = R^-1 p;  Y[f] = X[f] - g^H x~[f]
+#   synthesis   y_f = irfft(Y[f])[0 .. 1023] * w; out = overlap_add(y) / 2 in ascending frame order, cropped to the clip's n samples
+# What follows from the rule: a clip with F <= D has no tap (x~ = 0, so p = 0 and g = 0) and comes back as its own STFT round trip, which is
+# the clip up to rounding; an all-zero clip stays zero (R is the 1e-20 load alone, p = 0).  The prediction is linear in X, so there is no
+# musical noise; it models a tail of at most (D + K) frames = 213 ms, one channel, and a steady tone predicts itself from its own past and is
+# attenuated with the tail -- the weak case, which is why the option is per voice and off unless asked for.
+DEREVERB_DELAY = 4
+DEREVERB_TAPS = 16
+DEREVERB_ITERATIONS = 3
+DEREVERB_FLOOR = 1e-3
+DEREVERB_LOAD = 1e-3
+DEREVERB_TINY = 1e-20
+DEREVERB_MAX_SAMPLES = DENOISE_MAX_SAMPLES
+
+
+def check_dereverb_length(n: int) -> None:
+    """Refuses (ValueError) a clip of `n` samples at 24 kHz that the dereverberator does not take."""
+    if n > DEREVERB_MAX_SAMPLES:
+        raise ValueError(f"dereverb: the reference clip has {n} samples at 24 kHz; at most DEREVERB_MAX_SAMPLES = {DEREVERB_MAX_SAMPLES} (60 s) are dereverberated")
+
+
+def dereverb_reference(wave) -> np.ndarray:
+    """The definition above of a mono 24 kHz clip `wave` [n] (or [1, n]), 1 <= n <= DEREVERB_MAX_SAMPLES -> float32 [n]:
+    `dereverb_reference_f64` rounded once to the samples' format.  The length is preserved and a silent clip stays silent."""
+    return dereverb_reference_f64(wave).astype(np.float32)
+
+
+def dereverb_reference_f64(wave) -> np.ndarray:
+    """`dereverb_reference` before its one rounding to float32: the definition's float64 samples [n]."""
+    x = np.asarray(wave, dtype=np.float64).reshape(-1)
+    n = len(x)
+    if n < 1:
+        raise ValueError("dereverb: the reference clip is empty")
+    check_dereverb_length(n)
+    N, H, D, K = DENOISE_N_FFT, DENOISE_HOP, DEREVERB_DELAY, DEREVERB_TAPS
+    F = denoise_frames(n)
+    w = np.sin(np.pi * np.arange(N) / N)
+    xp = np.zeros(H * (F - 1) + N)
+    xp[DENOISE_PAD:DENOISE_PAD + n] = x
+    X = np.fft.rfft(np.lib.stride_tricks.sliding_window_view(xp, N)[::H] * w, axis=1)
+    Xz = np.concatenate([np.zeros((D + K - 1, X.shape[1]), dtype=X.dtype), X])       # frame f of X is row f + D + K - 1
+    floor = DEREVERB_FLOOR * np.mean(np.abs(X) ** 2, axis=0) + DEREVERB_TINY
+    Y = X.copy()
+    for _ in range(DEREVERB_ITERATIONS):
+        Pe = np.pad(np.abs(Y) ** 2, ((1, 1), (0, 0)), mode="edge")
+        lam = np.maximum((Pe[:-2] + Pe[1:-1] + Pe[2:]) / 3.0, floor)
+        for k in range(X.shape[1]):
+            taps = np.lib.stride_tricks.sliding_window_view(Xz[:F + K - 1, k], K)[:, ::-1]   # [F, K]: column j is X[f - D - j, k]
+            weighted = taps / lam[:, k, None]
+            R = weighted.T @ taps.conj()
+            p = weighted.T @ X[:, k].conj()
+            R = R + (DEREVERB_LOAD * np.trace(R).real / K + DEREVERB_TINY) * np.eye(K)
+            Y[:, k] = X[:, k] - taps @ np.linalg.solve(R, p).conj()
+    y = np.fft.irfft(Y, n=N, axis=1) * w
+    out = np.zeros_like(xp)
+    for m in range(F):
+        out[H * m:H * m + N] += y[m]
+    return out[DENOISE_PAD:DENOISE_PAD + n] / 2.0
+
+
 # ------------------------------------------------------------------------------------------------ is an uploaded reference clip fit to clone from?
 # The definition of the reference-clip report (`infer.PreparedVoice(..., assess=True)`, `TTSManager.check_reference`, the upload gate
 # `TTSManager(reference_limits=...)`; on the device `ops.ref_assess`, csrc/ref_assess.h).  `raw` is the clip the front-end is handed,

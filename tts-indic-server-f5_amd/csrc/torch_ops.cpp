@@ -26,6 +26,7 @@
 //   torch.ops.f5hip.wave_prosody_formants(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, keep_formants, taps?) -> the same four
 //   torch.ops.f5hip.wave_prosody_shape(pcm, in_off, max_len, len_dev?, stretch_p, stretch_q, pitch, keep_formants, formant, taps?) -> the same four
 //   torch.ops.f5hip.ref_denoise(wave, offset, n_samples) -> ()   the flagged clips of wave (f5hip_ref_frontend's packed output) are denoised in place
+//   torch.ops.f5hip.ref_dereverb(wave, offset, n_samples) -> ()   the same table; the flagged clips are dereverberated in place (in front of ref_denoise)
 //   torch.ops.f5hip.wave_mark(pcm, in_off, max_len, len_dev?, key_index, carriers?) -> ()   the flagged requests of pcm get their key's provenance mark in place
 //   torch.ops.f5hip.ref_assess(raw, raw_offset, channels, raw_len, wave, offset, n_samples) -> Tensor rows int64 [n, 10]: the reference-clip report
 //   torch.ops.f5hip.watermark_detect(wave, offset, n_samples, carriers) -> Tensor scores fp32 [n, n_keys, 4]: z, offset, r at the offset, the deviation
@@ -712,26 +713,31 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> wave_prosody_shape(co
     return wave_prosody_call(pcm, in_off, max_len, len_dev, stretch_p, stretch_q, pitch, &keep_formants, &formant, taps);
 }
 
-// wave: the contiguous 1-D fp32 device tensor that holds every clip (f5hip_ref_frontend's packed output), denoised IN PLACE; offset [n] int64
-// host, n_samples [n] int32 host: clip i is wave[offset[i] : offset[i] + n_samples[i]]; the ranges are disjoint, whatever lies between them
-// is left alone
-void ref_denoise(at::Tensor wave, const at::Tensor& offset, const at::Tensor& n_samples) {
+// wave: the contiguous 1-D fp32 device tensor that holds every clip (f5hip_ref_frontend's packed output), processed IN PLACE by `call`
+// (f5hip_ref_denoise, f5hip_ref_dereverb); offset [n] int64 host, n_samples [n] int32 host: clip i is wave[offset[i] : offset[i] + n_samples[i]];
+// the ranges are disjoint, whatever lies between them is left alone
+void clip_table_call(const char* op, int (*call)(int32_t, const int64_t*, const int32_t*, float*, void*), at::Tensor& wave, const at::Tensor& offset,
+                     const at::Tensor& n_samples) {
     check_host(offset, at::kLong, "offset"); check_host(n_samples, at::kInt, "n_samples");
     check_dev_f32(wave, "wave");
     const int64_t n = n_samples.numel();
-    TORCH_CHECK(n_samples.dim() == 1 && n > 0 && n <= INT32_MAX && offset.numel() == n, "f5hip::ref_denoise: offset and n_samples need one value per clip, and at least one clip");
-    TORCH_CHECK(wave.dim() == 1, "f5hip::ref_denoise: wave must be a contiguous 1-D fp32 tensor on a HIP device");
+    TORCH_CHECK(n_samples.dim() == 1 && n > 0 && n <= INT32_MAX && offset.numel() == n, "f5hip::", op, ": offset and n_samples need one value per clip, and at least one clip");
+    TORCH_CHECK(wave.dim() == 1, "f5hip::", op, ": wave must be a contiguous 1-D fp32 tensor on a HIP device");
     const int64_t* off = offset.data_ptr<int64_t>();
     const int32_t* ns = n_samples.data_ptr<int32_t>();
     for (int64_t i = 0; i < n; i++) {
-        TORCH_CHECK(ns[i] >= 1 && ns[i] <= kRdMaxSamples, "f5hip::ref_denoise: clip ", i, " has ", ns[i], " samples (1 .. ", kRdMaxSamples, ")");
-        TORCH_CHECK(off[i] >= 0 && off[i] + ns[i] <= wave.numel(), "f5hip::ref_denoise: clip ", i, " is samples [", off[i], ", ", off[i] + ns[i], ") of a tensor of ",
+        TORCH_CHECK(ns[i] >= 1 && ns[i] <= kRdMaxSamples, "f5hip::", op, ": clip ", i, " has ", ns[i], " samples (1 .. ", kRdMaxSamples, ")");
+        TORCH_CHECK(off[i] >= 0 && off[i] + ns[i] <= wave.numel(), "f5hip::", op, ": clip ", i, " is samples [", off[i], ", ", off[i] + ns[i], ") of a tensor of ",
                     wave.numel());
     }
     const c10::DeviceGuard guard(wave.device());
-    const int rc = f5hip_ref_denoise((int32_t)n, off, ns, wave.data_ptr<float>(), stream_of(wave));
-    TORCH_CHECK(rc == 0, "f5hip_ref_denoise: ", f5hip_last_error());
+    const int rc = call((int32_t)n, off, ns, wave.data_ptr<float>(), stream_of(wave));
+    TORCH_CHECK(rc == 0, "f5hip_", op, ": ", f5hip_last_error());
 }
+
+void ref_denoise(at::Tensor wave, const at::Tensor& offset, const at::Tensor& n_samples) { clip_table_call("ref_denoise", f5hip_ref_denoise, wave, offset, n_samples); }
+
+void ref_dereverb(at::Tensor wave, const at::Tensor& offset, const at::Tensor& n_samples) { clip_table_call("ref_dereverb", f5hip_ref_dereverb, wave, offset, n_samples); }
 
 // The carriers of a watermark call, checked: a contiguous int16 device tensor [n_keys, 16384] on `device`, 1 .. 16 keys; with trace ids
 // (`tagged`) [n_keys, 4, 16384], 1 .. max_keys keys: per key its own row, then its sub-keys'
@@ -927,6 +933,7 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("wave_prosody_shape(Tensor pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor stretch_p, Tensor stretch_q, Tensor pitch, "
           "Tensor keep_formants, Tensor formant, Tensor? taps) -> (Tensor, Tensor, Tensor, Tensor)", &wave_prosody_shape);
     m.def("ref_denoise(Tensor(a!) wave, Tensor offset, Tensor n_samples) -> ()", &ref_denoise);
+    m.def("ref_dereverb(Tensor(a!) wave, Tensor offset, Tensor n_samples) -> ()", &ref_dereverb);
     m.def("wave_mark(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor key_index, Tensor? carriers) -> ()", &wave_mark);
     m.def("watermark_detect(Tensor wave, Tensor offset, Tensor n_samples, Tensor carriers) -> Tensor", &watermark_detect);
     m.def("wave_mark_ids(Tensor(a!) pcm, Tensor in_off, Tensor max_len, Tensor? len_dev, Tensor key_index, Tensor id, Tensor? carriers) -> ()", &wave_mark_ids);

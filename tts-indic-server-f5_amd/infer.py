@@ -33,6 +33,7 @@ import torch
 from . import wave_codec
 from .audio_prep import preprocess_ref_audio_text, remove_silence_edges, remove_silence_pcm  # noqa: F401  (F/infer/utils_infer.py:263-350)
 from .audio_prep import DENOISE_MAX_SAMPLES, check_denoise_length, denoise_reference  # noqa: F401  (the per-voice `denoise` option of an uploaded clip)
+from .audio_prep import DEREVERB_MAX_SAMPLES, check_dereverb_length, dereverb_reference  # noqa: F401  (the per-voice `dereverb` option of an uploaded clip)
 from .audio_prep import (ASSESS_MAX_SAMPLES, REFERENCE_LIMITS, ReferenceReport, assess_reference, check_reference_limits,  # noqa: F401
                          reference_problems, report_from_row)   # (the reference-clip report and the upload gate)
 from .loaders import DiT, MMDiT, UNetT, load_checkpoint, load_model, load_vocoder  # noqa: F401  (F/infer/utils_infer.py:92-130,175-260)
@@ -394,6 +395,11 @@ class PreparedVoice:
     noise or hum.  `rms`, `seconds` and `ref_frames` stay the front-end's; a clip longer than `DENOISE_MAX_SAMPLES` at 24 kHz is refused
     by both constructors.  A deferred voice is denoised by `prepare_voices`: on the device in one `ops.ref_denoise` call per front-end call.
 
+    `dereverb` (False): the voice's wave goes through `audio_prep.dereverb_reference` (single-channel WPE) behind the front-end and in front of
+    the denoiser, whose floor estimate then sees what is left -- for recordings made in a reverberant room.  `rms`, `seconds` and `ref_frames`
+    stay the front-end's; a clip longer than `DEREVERB_MAX_SAMPLES` at 24 kHz is refused by both constructors.  A deferred voice is
+    dereverberated by `prepare_voices`: on the device in one `ops.ref_dereverb` call per front-end call.
+
     `reject_marked` (None): watermark keys the clip must not carry.  The prepared 24 kHz wave is scored against them before the denoiser
     (`check_unmarked`; a deferred voice by `prepare_voices`: on the device in one `ops.watermark_detect` call per front-end call), and a
     clip that scores at or above `WATERMARK_THRESHOLD` for any key is a ValueError (`MARKED_REFERENCE`).
@@ -406,13 +412,16 @@ class PreparedVoice:
 
     report = None
 
-    def __init__(self, ref_audio, target_rms=0.1, device=None, denoise=False, reject_marked=None, assess=False, limits=None):
+    def __init__(self, ref_audio, target_rms=0.1, device=None, denoise=False, reject_marked=None, assess=False, limits=None, dereverb=False):
         wav, sr = ref_audio if isinstance(ref_audio, tuple) else load_audio(ref_audio)
         if denoise:
             check_denoise_length(resampled_length(wav.shape[-1], sr, target_sample_rate))
+        if dereverb:
+            check_dereverb_length(resampled_length(wav.shape[-1], sr, target_sample_rate))
         self.seconds = wav.shape[-1] / sr
         self.audio, self.rms = _prepare_reference(wav, sr, target_rms, device)
         self.denoise = bool(denoise)
+        self.dereverb = bool(dereverb)
         self.limits = check_reference_limits(limits)
         self.assess = bool(assess) or self.limits is not None
         if self.assess:
@@ -421,6 +430,8 @@ class PreparedVoice:
         self.reject_marked = None if reject_marked is None else tuple(check_watermark_keys(list(reject_marked)))
         if self.reject_marked is not None:
             check_unmarked(self.audio, self.reject_marked)
+        if self.dereverb:
+            self.audio = _dereverb_host(self.audio)
         if self.denoise:
             self.audio = _denoise_host(self.audio)
         self.ref_frames = self.audio.shape[-1] // hop_length
@@ -428,7 +439,7 @@ class PreparedVoice:
         self.pending = None
 
     @classmethod
-    def deferred(cls, ref_audio, target_rms=0.1, denoise=False, reject_marked=None, assess=False, limits=None):
+    def deferred(cls, ref_audio, target_rms=0.1, denoise=False, reject_marked=None, assess=False, limits=None, dereverb=False):
         wav, sr = ref_audio
         if wav.dim() != 2 or wav.shape[-1] < 1:
             raise ValueError(f"reference audio must be [channels, samples] with at least one sample (got {tuple(wav.shape)})")
@@ -436,8 +447,11 @@ class PreparedVoice:
             resample_taps(sr, target_sample_rate)   # an unsupported rate pair is refused here, before anything is queued
         if denoise:
             check_denoise_length(resampled_length(wav.shape[-1], sr, target_sample_rate))
+        if dereverb:
+            check_dereverb_length(resampled_length(wav.shape[-1], sr, target_sample_rate))
         voice = cls.__new__(cls)
         voice.denoise = bool(denoise)
+        voice.dereverb = bool(dereverb)
         voice.limits = check_reference_limits(limits)
         voice.assess = bool(assess) or voice.limits is not None
         voice.reject_marked = None if reject_marked is None else tuple(check_watermark_keys(list(reject_marked)))
@@ -461,6 +475,8 @@ class PreparedVoice:
 # How often `prepare_voices` denoised: "host_clips" (one `denoise_reference` each) and "device_calls" (one `ops.ref_denoise` each, whatever
 # the number of flagged voices in it).  A batch without a flagged voice adds to neither.
 DENOISE_COUNTS = collections.Counter()
+# The same for the `dereverb` option: "host_clips" (one `dereverb_reference` each) and "device_calls" (one `ops.ref_dereverb` each)
+DEREVERB_COUNTS = collections.Counter()
 
 
 # How often reference clips were scored against `reject_marked` keys: "host_clips" (one `detect_watermark` each) and "device_calls" (one
@@ -501,6 +517,12 @@ def _denoise_host(audio):
     return torch.from_numpy(denoise_reference(audio[0].detach().cpu().numpy()))[None].to(audio.device)
 
 
+def _dereverb_host(audio):
+    """`audio_prep.dereverb_reference` of a prepared wave [1, nw], back where it was."""
+    DEREVERB_COUNTS["host_clips"] += 1
+    return torch.from_numpy(dereverb_reference(audio[0].detach().cpu().numpy()))[None].to(audio.device)
+
+
 def prepare_voices(clips, target_rms=0.1, device="cuda"):
     """The reference-audio front-end (mono mix, rms, gain, resampling to 24 kHz) of several voices at once on the device: one upload of the
     packed clips and ONE `ops.ref_frontend` call (two launches) per distinct sample rate, then one download of all rms values.
@@ -511,7 +533,9 @@ def prepare_voices(clips, target_rms=0.1, device="cuda"):
     constructor does.  Voices with `denoise` set are denoised behind the front-end: on the device the flagged voices of each front-end call
     -- one per distinct (sample rate, rms floor) -- go through ONE `ops.ref_denoise` on that call's packed output, in place, so a voice's
     `audio` view and the mel launch behind it see the denoised samples with no copy; a call without a flagged voice is followed by none.
-    With `device=None` the host `denoise_reference` runs clip by clip.  Voices with `reject_marked` keys are scored in front of the denoiser:
+    With `device=None` the host `denoise_reference` runs clip by clip.  Voices with `dereverb` set are treated the same way in front of the
+    denoiser: ONE `ops.ref_dereverb` on the call's packed output for its flagged voices, or the host `dereverb_reference` clip by clip.
+    Voices with `reject_marked` keys are scored in front of the denoiser:
     the flagged voices of a front-end call in ONE `ops.watermark_detect` call on its packed output against the union of their keys, of which
     only the score rows come down; a voice that carries one of its own keys is a ValueError (`MARKED_REFERENCE`) and the call's voices stay
     deferred.  With `device=None` `check_unmarked` runs clip by clip.  Voices with `assess` are measured first of all: those of a front-end
@@ -531,6 +555,8 @@ def prepare_voices(clips, target_rms=0.1, device="cuda"):
             if getattr(v, "reject_marked", None) is not None:
                 check_unmarked(audio, v.reject_marked)
             v.audio, v.rms = audio, rms
+            if getattr(v, "dereverb", False):
+                v.audio = _dereverb_host(v.audio)
             if getattr(v, "denoise", False):
                 v.audio = _denoise_host(v.audio)
             v.pending = None
@@ -569,6 +595,10 @@ def prepare_voices(clips, target_rms=0.1, device="cuda"):
             for i, row in zip(guarded, rows):
                 if any(score.detected and score.key in vs[i].reject_marked for score in ops.watermark_scores(row, keys)):
                     raise ValueError(MARKED_REFERENCE)
+        flagged = [i for i, v in enumerate(vs) if getattr(v, "dereverb", False)]
+        if flagged:                                              # the linear stage first: the denoiser's floor sees what it leaves
+            ops.ref_dereverb(out, [int(starts[i]) for i in flagged], [int(n_out[i]) for i in flagged])
+            DEREVERB_COUNTS["device_calls"] += 1
         flagged = [i for i, v in enumerate(vs) if getattr(v, "denoise", False)]
         if flagged:                                              # in place on the packed output: the views below are the denoised clips
             ops.ref_denoise(out, [int(starts[i]) for i in flagged], [int(n_out[i]) for i in flagged])

@@ -1,7 +1,7 @@
 """Python face of the operations of the C ABI (include/f5hip.h) on torch tensors on the HIP device.  Two families:
   - the per-kernel unit ops (`gemm` .. `time_table`): one production HIP kernel each, fp32 in and out, called through ctypes.  Used by the
     per-kernel parity tests and the timing tools; not on the hot path.
-  - the device audio path that every request takes (`ref_frontend`, `ref_prestep`, `ref_denoise`, `ref_assess`, `wave_finish` .. `wave_loudness`, `flac_decode`): one
+  - the device audio path that every request takes (`ref_frontend`, `ref_prestep`, `ref_dereverb`, `ref_denoise`, `ref_assess`, `wave_finish` .. `wave_loudness`, `flac_decode`): one
     library call per batch.  Each is bound twice over the same C entry point: as a TORCH_LIBRARY operator (csrc/torch_ops.cpp), taken when
     `torch_ops.load()`, and through ctypes otherwise; both return the same bits.  The steps the wrappers share -- the operator call, the
     per-request host arrays, the PCM request table, its sources, the pointer table and the packing of the outputs -- are the helpers in
@@ -605,21 +605,44 @@ def ref_denoise(wave, offsets, lengths):
     the clips -- `ref_frontend`'s packed output as it stands --; clip i is wave[offsets[i] : offsets[i] + lengths[i]], mono at 24 kHz, 1 to
     `audio_prep.DENOISE_MAX_SAMPLES` samples.  The ranges are disjoint and need not be adjacent: samples between them, and clips left out of
     the table, keep their bits.  A clip's result equals its own single-clip call's bit for bit.  Returns `wave`."""
+    return _clip_table_call("ref_denoise", wave, offsets, lengths)
+
+
+def ref_dereverb(wave, offsets, lengths):
+    """The per-voice dereverberator of uploaded reference clips for several clips in ONE library call and four launches (include/f5hip.h
+    f5hip_ref_dereverb): `audio_prep.dereverb_reference` (single-channel WPE) of each clip in fp32, IN PLACE, in front of `ref_denoise`.
+    wave, offsets, lengths as `ref_denoise` takes them, 1 to `audio_prep.DEREVERB_MAX_SAMPLES` samples a clip: samples between the ranges, and
+    clips left out of the table, keep their bits.  A clip's result equals its own single-clip call's bit for bit.  Returns `wave`."""
+    return _clip_table_call("ref_dereverb", wave, offsets, lengths)
+
+
+def ref_dereverb_launches():
+    """Kernels one `ref_dereverb` call launches, whatever the number of clips."""
+    return int(_lib.lib().f5hip_ref_dereverb_launches())
+
+
+def ref_dereverb_chunk():
+    """Frames the dereverberator's Gram pass stages at a time: a clip's frames are consumed in chunks of this many, in ascending order."""
+    return int(_lib.lib().f5hip_ref_dereverb_chunk())
+
+
+def _clip_table_call(name, wave, offsets, lengths):
+    """`ref_denoise` / `ref_dereverb`: the checked clip table and the in-place call, through the operator where it is registered."""
     from .audio_prep import DENOISE_MAX_SAMPLES
-    ln = _per_request("ref_denoise", "lengths", lengths, np.int32, per="clip")
-    off = _per_request("ref_denoise", "offsets", offsets, np.int64, len(ln), per="clip")
+    ln = _per_request(name, "lengths", lengths, np.int32, per="clip")
+    off = _per_request(name, "offsets", offsets, np.int64, len(ln), per="clip")
     if not (torch.is_tensor(wave) and wave.dtype == torch.float32 and wave.is_contiguous() and wave.is_cuda and wave.dim() == 1):
-        raise _lib.F5HipError("ref_denoise: wave must be a contiguous 1-D fp32 tensor on the HIP device")
+        raise _lib.F5HipError(f"{name}: wave must be a contiguous 1-D fp32 tensor on the HIP device")
     if torch_ops.load():
-        call_op("ref_denoise", wave, torch.from_numpy(off), torch.from_numpy(ln))
+        call_op(name, wave, torch.from_numpy(off), torch.from_numpy(ln))
         return wave
     for i in range(len(ln)):
         if ln[i] < 1 or ln[i] > DENOISE_MAX_SAMPLES:
-            raise _lib.F5HipError(f"ref_denoise: clip {i} has {ln[i]} samples (1 .. {DENOISE_MAX_SAMPLES})")
+            raise _lib.F5HipError(f"{name}: clip {i} has {ln[i]} samples (1 .. {DENOISE_MAX_SAMPLES})")
         if off[i] < 0 or int(off[i]) + int(ln[i]) > wave.numel():
-            raise _lib.F5HipError(f"ref_denoise: clip {i} is samples [{off[i]}, {int(off[i]) + int(ln[i])}) of a tensor of {wave.numel()}")
+            raise _lib.F5HipError(f"{name}: clip {i} is samples [{off[i]}, {int(off[i]) + int(ln[i])}) of a tensor of {wave.numel()}")
     with torch.cuda.device(wave.device):
-        _lib.check(_lib.lib().f5hip_ref_denoise(len(ln), _p(off), _p(ln), _p(wave), _lib.current_stream_ptr()), "f5hip_ref_denoise")
+        _lib.check(getattr(_lib.lib(), "f5hip_" + name)(len(ln), _p(off), _p(ln), _p(wave), _lib.current_stream_ptr()), "f5hip_" + name)
     return wave
 
 
