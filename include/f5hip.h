@@ -1053,6 +1053,32 @@ int f5hip_ref_assess(int32_t n, const float* raw_dev, const int64_t* raw_offset,
 /* Kernels one f5hip_ref_assess call launches (6). */
 int f5hip_ref_assess_launches(void);
 
+/* The cleanest stretch of n long reference recordings in ONE call (csrc/ref_select.h; the definition is audio_prep.select_reference): the
+ * report's measures over every window of window_frames frames at hop hop_frames of each recording, and the window its key picks.  The raw
+ * side (raw_dev, raw_offset, channels, raw_len) and the prepared side (wave_dev, offset, n_samples) are f5hip_ref_assess's, both read only,
+ * except that a prepared recording has 1 .. 14 400 000 samples (600 s); sample_rate [n] host: the raw side's rates.  A recording of F frames
+ * (the denoiser's framing) has (F - window_frames) / hop_frames + 1 windows, window w = frames [hop w, hop w + window_frames), or ONE window of
+ * all its frames where F < window_frames; the recordings' windows follow each other in table order.
+ * rows_dev: int64 [windows][5] = clipped, speech frames, then the bit patterns of the float64 N, S, snr_db of the window (floor = the
+ * ((Wc - 1) / 5)-th smallest of the window's P[.][k] per band bin 3 .. 341, exactly; N = 4.4814 sum_k floor, ascending k; S = the mean of
+ * E over the window, ascending f; clipped = the recording's clipped samples (f5hip_ref_assess's rule, against the whole recording's peak)
+ * inside the window's source range).  choice_dev: int64 [n], each recording's window with the smallest key (clipped, -snr_db, w).
+ * floor_dev (may be null): float [windows][340], the windows' floors of the 339 band bins.  power_dev (may be null, 16-byte aligned): the band
+ * power as the floor launch read it, recording after recording, each [339][Fs] bin-major with Fs = F rounded up to 4.
+ * TEN launches whatever n, no memset, no host synchronisation once the workspace has grown to the call's size.  A recording's rows depend
+ * on that recording alone: they equal its own single-recording call's bit for bit.  Geometry, digits and row arithmetic:
+ * csrc/ref_select_core.h, which tools/ref_select_check.cpp runs on the CPU under sanitizers.
+ * Refused before the first launch: n outside 1 .. 64, what f5hip_ref_assess refuses of the raw side, window_frames outside 1 .. 1407,
+ * hop_frames outside 1 .. 2^20, a rate outside 1 .. 768 000, a length outside 1 .. 14 400 000, more than 57 600 000 prepared samples in
+ * all (the workspace grows by about 29 bytes a sample, of which 16 are the STFT's spectrum that only the denoiser reads: 1.7 GB at that
+ * cap), a negative offset, overlapping ranges, a null or misaligned pointer. */
+int f5hip_ref_select(int32_t n, const float* raw_dev, const int64_t* raw_offset, const int32_t* channels, const int32_t* raw_len,
+                     const int32_t* sample_rate, const float* wave_dev, const int64_t* offset, const int32_t* n_samples, int32_t window_frames,
+                     int32_t hop_frames, int64_t* rows_dev, int64_t* choice_dev, float* floor_dev, float* power_dev, void* stream);
+
+/* Windows one workgroup of f5hip_ref_select's floor launch owns for this window and hop (16 where they fit its stage); negative when refused. */
+int f5hip_ref_select_run(int32_t window_frames, int32_t hop_frames);
+
 #ifdef __cplusplus
 }
 #endif

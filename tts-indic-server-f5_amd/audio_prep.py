@@ -781,3 +781,155 @@ def report_from_row(row, seconds, rms, samples) -> ReferenceReport:
                            peak=float(np.array([row[1]], dtype=np.int64).astype(np.uint32).view(np.float32)[0]), clipped=clipped,
                            clip_ratio=clipped / float(samples), noise_db=f["noise_db"], snr_db=f["snr_db"], speech_ratio=f["speech_ratio"],
                            bandwidth_hz=f["bandwidth_hz"])
+
+
+# ------------------------------------------------------------------------------------------------ which stretch of a long recording to clone from?
+# The definition of the reference-stretch selection (`TTSManager.select_reference`, `POST /v1/audio/reference/select`; on the device
+# `ops.ref_select`, csrc/ref_select.h): the report's measures above over EVERY window of a long recording, and a rule that picks one.
+# `raw` is the recording the front-end is handed, float32 [ch, n] at `sr`; `prepared` is the front-end's 24 kHz mono wave of all of it, at
+# most SELECT_MAX_SAMPLES samples (600 s): a longer recording is refused, never truncated.
+#   frames     P[f][k] = denoise_power(prepared) over the whole recording, F frames; E[f] = sum_{k in B} P[f][k], ascending k (B = ASSESS_BAND)
+#   windows    W = floor(seconds * 93.75) frames, seconds a multiple of 0.5 from 3 to 15 (12); window w = frames [48 w, 48 w + W) for every w
+#              that fits (SELECT_HOP = 48: about half a second).  A recording of fewer than W frames has ONE window over all F frames.  W_w
+#              is the window's frame count
+#   floor_w[k] the ((W_w - 1) // 5)-th smallest of P[f][k] over the window's frames
+#   N_w        ASSESS_FLOOR_TO_MEAN * sum_{k in B} floor_w[k], ascending k
+#   S_w        (1 / W_w) * sum_f E[f] over the window, ascending f
+#   speech_w   the window's frames with E[f] >= 4 N_w and E[f] > 0
+#   snr_w      `assess_ratios`' snr_db of (N_w, S_w): +inf when N_w == 0, -inf when S_w <= N_w
+#   source     the window's samples of raw: [floor(s0 sr / 24000), floor(s1 sr / 24000)), s0 = max(0, 256 f0 - 768), s1 = min(len, 256 (f0 + W_w)),
+#              f0 the window's first frame and len the prepared wave's length
+#   clipped_w  `assess_clipping`'s clipped samples of the WHOLE recording (hot against the whole recording's peak, runs within one channel, 0
+#              everywhere when the report's clipped is 0) whose index lies in the source range, summed over channels
+#   choice     the window with the smallest key (clipped_w, -snr_w, w), compared as a tuple: +inf snr first, -inf last, the earliest on ties
+# The result names the source range of the chosen window and carries `assess_reference` of that crop, raw[:, start:end] and its own prepared
+# wave: what the upload gate would see of it.  The weak cases are the report's: a stretch without pauses has its own speech as the floor and
+# reads a low snr_w, so a window of continuous speech loses to one with pauses; and a SILENT window (N_w = 0) wins on +inf.  Nothing is built
+# in against either: `min_speech_ratio` drops the windows whose speech_w / W_w is below it before the choice.
+SELECT_MAX_SAMPLES = 14_400_000    # 600 s at 24 kHz
+SELECT_HOP = 48
+SELECT_FRAMES_PER_SECOND = 24000 / DENOISE_HOP       # 93.75
+SELECT_SECONDS = (3.0, 15.0, 12.0)                   # least, most, default; multiples of 0.5
+SELECT_ROW = ("clipped", "speech", "N", "S", "snr_db")
+
+
+class ReferenceSelection(typing.NamedTuple):
+    """The stretch `select_reference` picked: raw[:, start:end] (sample indices into the recording as uploaded), the chosen window, the table
+    of every window ([windows, 5] float64: clipped, speech frames, N, S, snr_db) and the `ReferenceReport` of the crop."""
+    start: int
+    end: int
+    window: int
+    windows: np.ndarray
+    report: ReferenceReport
+
+
+def select_window_frames(seconds=SELECT_SECONDS[2]) -> int:
+    """W of `seconds` (ValueError unless a multiple of 0.5 from 3 to 15)."""
+    lo, hi, _ = SELECT_SECONDS
+    if isinstance(seconds, bool) or not isinstance(seconds, (int, float)) or not math.isfinite(seconds) or not lo <= seconds <= hi or seconds * 2 != int(seconds * 2):
+        raise ValueError(f"select: seconds must be a multiple of 0.5 from {lo:g} to {hi:g} (got {seconds!r})")
+    return int(math.floor(seconds * SELECT_FRAMES_PER_SECOND))
+
+
+def check_select_length(n: int) -> None:
+    """Refuses (ValueError) a recording of `n` samples at 24 kHz that the selection does not take."""
+    if n > SELECT_MAX_SAMPLES:
+        raise ValueError(f"select: the recording has {n} samples at 24 kHz; at most SELECT_MAX_SAMPLES = {SELECT_MAX_SAMPLES} (600 s) are searched")
+
+
+def check_min_speech_ratio(r):
+    if r is None:
+        return None
+    if isinstance(r, bool) or not isinstance(r, (int, float)) or not 0.0 <= r <= 1.0:
+        raise ValueError(f"select: min_speech_ratio must be a number from 0 to 1 (got {r!r})")
+    return float(r)
+
+
+def select_windows(F: int, W: int, hop: int = SELECT_HOP) -> list:
+    """[(first frame, frames)] of the windows of a recording of F frames."""
+    return [(0, F)] if F < W else [(hop * w, W) for w in range((F - W) // hop + 1)]
+
+
+def select_source_range(f0: int, frames: int, length: int, sr: int) -> tuple:
+    """The window's samples [start, end) of the recording at `sr`; `length`: the prepared wave's."""
+    s0, s1 = max(0, DENOISE_HOP * f0 - DENOISE_PAD), min(length, DENOISE_HOP * (f0 + frames))
+    return s0 * sr // 24000, s1 * sr // 24000
+
+
+def select_clipped_flags(raw) -> np.ndarray:
+    """bool [ch, n]: the samples `assess_clipping` counts, none where it reports 0."""
+    x = np.abs(np.asarray(raw, dtype=np.float32))
+    x = x.reshape(1, -1) if x.ndim == 1 else x
+    peak, clipped = assess_clipping(x)
+    if clipped == 0:
+        return np.zeros(x.shape, dtype=bool)
+    h = np.pad(x >= peak * np.float32(ASSESS_HOT), ((0, 0), (2, 2)))
+    l2, l1, me, r1, r2 = (h[:, i:i + x.shape[1]] for i in range(5))
+    return me & ((l1 & r1) | (l1 & l2) | (r1 & r2))
+
+
+def select_table(raw, sr, prepared, window_frames, hop_frames=SELECT_HOP) -> np.ndarray:
+    """The per-window table [windows, 5] (SELECT_ROW) by the definition above, for any window and hop in frames."""
+    x = np.asarray(prepared, dtype=np.float64).reshape(-1)
+    if len(x) < 1:
+        raise ValueError("select: the recording is empty")
+    check_select_length(len(x))
+    P = denoise_power(x)
+    b0, b1 = ASSESS_BAND
+    E = np.cumsum(P[:, b0:b1 + 1], axis=1)[:, -1]
+    flags = np.concatenate([[0], np.cumsum(select_clipped_flags(raw).sum(axis=0))])
+    rows = []
+    for f0, Ww in select_windows(P.shape[0], int(window_frames), int(hop_frames)):
+        N = ASSESS_FLOOR_TO_MEAN * float(np.cumsum(denoise_floor(P[f0:f0 + Ww, b0:b1 + 1]))[-1])
+        Ew = E[f0:f0 + Ww]
+        S = float(np.cumsum(Ew)[-1]) / Ww
+        speech = int(np.count_nonzero((Ew >= ASSESS_SPEECH_FACTOR * N) & (Ew > 0)))
+        j0, j1 = (min(j, len(flags) - 1) for j in select_source_range(f0, Ww, len(x), int(sr)))
+        rows.append([float(flags[max(j1, j0)] - flags[j0]), float(speech), N, S, assess_ratios(N, S, speech, Ww, -1)["snr_db"]])
+    return np.array(rows, dtype=np.float64)
+
+
+def select_key(row, w):
+    """The key of window w with the table row `row`: the smallest wins."""
+    return (row[0], -row[4], w)
+
+
+def select_choice(table, frames, min_speech_ratio=None) -> int:
+    """The chosen window of a table [windows, 5]; `frames` [windows]: each window's frame count.  `min_speech_ratio` drops the windows below
+    it first; ValueError, naming the best ratio seen, when none is left."""
+    r = check_min_speech_ratio(min_speech_ratio)
+    ratios = [row[1] / f for row, f in zip(table, frames)]
+    left = [w for w in range(len(table)) if r is None or ratios[w] >= r]
+    if not left:
+        raise ValueError(f"select: no window has a speech_ratio of at least {r:g} (the best of {len(table)} is {max(ratios):.6g})")
+    return min(left, key=lambda w: select_key(table[w], w))
+
+
+def select_result(raw, sr, length, table, window_frames, choice, prepare=None, prepared=None) -> ReferenceSelection:
+    """The `ReferenceSelection` of window `choice` of `table`: its source range and the report of the crop.  `prepare(crop) -> (wave, rms)` is
+    the front-end of the crop; without one the crop's stretch of `prepared` stands in and no rms is reported."""
+    raw = np.asarray(raw, dtype=np.float32)
+    raw = raw.reshape(1, -1) if raw.ndim == 1 else raw
+    f0, Ww = select_windows(denoise_frames(length), int(window_frames))[choice]
+    start, end = (min(j, raw.shape[1]) for j in select_source_range(f0, Ww, length, int(sr)))
+    if end <= start:
+        raise ValueError("select: the chosen window holds no sample of the recording")
+    crop = raw[:, start:end]
+    if prepare is not None:
+        wave, rms = prepare(crop)
+    else:
+        wave, rms = np.asarray(prepared).reshape(-1)[max(0, DENOISE_HOP * f0 - DENOISE_PAD):min(length, DENOISE_HOP * (f0 + Ww))], None
+    return ReferenceSelection(start=int(start), end=int(end), window=int(choice), windows=np.asarray(table, dtype=np.float64),
+                              report=assess_reference(crop, sr, wave, rms=rms))
+
+
+def select_reference(raw, sr, prepared, seconds=SELECT_SECONDS[2], min_speech_ratio=None, prepare=None) -> ReferenceSelection:
+    """The cleanest stretch of `seconds` of a long recording by the definition above: `raw` float32 [ch, n] at `sr` Hz as the front-end is
+    handed it, `prepared` the front-end's 24 kHz mono wave of all of it.  ValueError for a recording over SELECT_MAX_SAMPLES, a bad `seconds`
+    or `min_speech_ratio`, or when `min_speech_ratio` leaves no window.  `prepare`: `select_result`'s."""
+    W = select_window_frames(seconds)
+    check_min_speech_ratio(min_speech_ratio)
+    x = np.asarray(prepared, dtype=np.float64).reshape(-1)
+    table = select_table(raw, sr, x, W)
+    frames = [f for _, f in select_windows(denoise_frames(len(x)), W)]
+    return select_result(raw, sr, len(x), table, W, select_choice(table, frames, min_speech_ratio), prepare, x)

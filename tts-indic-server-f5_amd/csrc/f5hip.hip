@@ -1174,5 +1174,6 @@ int f5hip_dit_set_ode_method(f5hip_dit* m, int32_t method) {
 #include "ref_dereverb.h"
 #include "wave_mark.h"
 #include "ref_assess.h"
+#include "ref_select.h"
 #include "wave_formant.h"
 #include "wave_limit.h"

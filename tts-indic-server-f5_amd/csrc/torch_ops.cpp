@@ -29,6 +29,7 @@
 //   torch.ops.f5hip.ref_dereverb(wave, offset, n_samples) -> ()   the same table; the flagged clips are dereverberated in place (in front of ref_denoise)
 //   torch.ops.f5hip.wave_mark(pcm, in_off, max_len, len_dev?, key_index, carriers?) -> ()   the flagged requests of pcm get their key's provenance mark in place
 //   torch.ops.f5hip.ref_assess(raw, raw_offset, channels, raw_len, wave, offset, n_samples) -> Tensor rows int64 [n, 10]: the reference-clip report
+//   torch.ops.f5hip.ref_select(raw, raw_offset, channels, raw_len, sample_rate, wave, offset, n_samples, window_frames, hop_frames, taps) -> (rows int64 [windows, 5], choice int64 [n], floors, power): the cleanest stretch
 //   torch.ops.f5hip.watermark_detect(wave, offset, n_samples, carriers) -> Tensor scores fp32 [n, n_keys, 4]: z, offset, r at the offset, the deviation
 //   torch.ops.f5hip.wave_mark_ids(pcm, in_off, max_len, len_dev?, key_index, id, carriers?) -> ()   wave_mark whose marks also carry each request's trace id
 //   torch.ops.f5hip.watermark_read_ids(wave, offset, n_samples, carriers) -> Tensor rows fp32 [n, n_keys, 10]: watermark_detect's four, then (s_d, z_d) x 3
@@ -49,6 +50,7 @@
 #include "wave_mark_core.h"
 #include "ref_denoise_core.h"
 #include "ref_assess_core.h"
+#include "ref_select_core.h"
 
 namespace {
 
@@ -902,6 +904,49 @@ at::Tensor ref_assess(const at::Tensor& raw, const at::Tensor& raw_offset, const
     return rows;
 }
 
+// raw, raw_offset, channels, raw_len, wave, offset, n_samples as ref_assess's, a prepared recording up to 600 s; sample_rate [n] int32 host; taps:
+// whether the windows' floors and the band power come back too -> (rows int64 device [windows, 5], choice int64 device [n], floors fp32
+// [windows, 340] or [0], power fp32 [sum 339 Fs] or [0]) (include/f5hip.h f5hip_ref_select)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> ref_select(const at::Tensor& raw, const at::Tensor& raw_offset, const at::Tensor& channels,
+                                                                      const at::Tensor& raw_len, const at::Tensor& sample_rate, const at::Tensor& wave,
+                                                                      const at::Tensor& offset, const at::Tensor& n_samples, int64_t window_frames,
+                                                                      int64_t hop_frames, bool taps) {
+    check_host(raw_offset, at::kLong, "raw_offset"); check_host(channels, at::kInt, "channels"); check_host(raw_len, at::kInt, "raw_len");
+    check_host(sample_rate, at::kInt, "sample_rate"); check_host(offset, at::kLong, "offset"); check_host(n_samples, at::kInt, "n_samples");
+    check_dev_f32(raw, "raw"); check_dev_f32(wave, "wave");
+    const int64_t n = n_samples.numel();
+    TORCH_CHECK(n_samples.dim() == 1 && n >= 1 && n <= kRsMaxRecs && offset.numel() == n && raw_offset.numel() == n && channels.numel() == n && raw_len.numel() == n &&
+                sample_rate.numel() == n, "f5hip::ref_select: the six tables need one value per recording, 1 .. ", kRsMaxRecs, " recordings");
+    TORCH_CHECK(raw.dim() == 1 && wave.dim() == 1 && raw.device() == wave.device(), "f5hip::ref_select: raw and wave must be contiguous 1-D fp32 tensors on one HIP device");
+    TORCH_CHECK(window_frames >= 1 && window_frames <= kRsMaxWindow, "f5hip::ref_select: window_frames must be 1 .. ", kRsMaxWindow, " (got ", window_frames, ")");
+    TORCH_CHECK(hop_frames >= 1 && hop_frames <= kRsMaxHop, "f5hip::ref_select: hop_frames must be 1 .. ", kRsMaxHop, " (got ", hop_frames, ")");
+    const int64_t *ro = raw_offset.data_ptr<int64_t>(), *off = offset.data_ptr<int64_t>();
+    const int32_t *ch = channels.data_ptr<int32_t>(), *rl = raw_len.data_ptr<int32_t>(), *ns = n_samples.data_ptr<int32_t>(), *sr = sample_rate.data_ptr<int32_t>();
+    int64_t windows = 0, cols = 0;
+    for (int64_t i = 0; i < n; i++) {
+        TORCH_CHECK(ch[i] >= 1 && ch[i] <= kRaMaxChannels, "f5hip::ref_select: recording ", i, " has ", ch[i], " channels (1 .. ", kRaMaxChannels, ")");
+        TORCH_CHECK(rl[i] >= 1 && ro[i] >= 0 && ro[i] + (int64_t)rl[i] * ch[i] <= raw.numel(), "f5hip::ref_select: raw recording ", i, " is ", ch[i], " x ", rl[i],
+                    " samples at ", ro[i], " of a tensor of ", raw.numel());
+        TORCH_CHECK(ns[i] >= 1 && ns[i] <= kRsMaxSamples, "f5hip::ref_select: recording ", i, " has ", ns[i], " samples (1 .. ", kRsMaxSamples, ")");
+        TORCH_CHECK(off[i] >= 0 && off[i] + ns[i] <= wave.numel(), "f5hip::ref_select: recording ", i, " is samples [", off[i], ", ", off[i] + ns[i],
+                    ") of a tensor of ", wave.numel());
+        TORCH_CHECK(sr[i] >= 1 && sr[i] <= kRsMaxRate, "f5hip::ref_select: recording ", i, " has the sample rate ", sr[i], " (1 .. ", kRsMaxRate, ")");
+        const int F = rd_frames(ns[i]);
+        windows += rs_windows(F, (int)window_frames, (int)hop_frames);
+        cols += (int64_t)kRsBand * rs_padded(F);
+    }
+    const c10::DeviceGuard guard(wave.device());
+    at::Tensor rows = at::empty({windows, kRsRowWords}, wave.options().dtype(at::kLong));
+    at::Tensor choice = at::empty({n}, wave.options().dtype(at::kLong));
+    at::Tensor floors = at::empty({taps ? windows : 0, kRsFloorStride}, wave.options());
+    at::Tensor power = at::empty({taps ? cols : 0}, wave.options());
+    const int rc = f5hip_ref_select((int32_t)n, raw.data_ptr<float>(), ro, ch, rl, sr, wave.data_ptr<float>(), off, ns, (int32_t)window_frames, (int32_t)hop_frames,
+                                    rows.data_ptr<int64_t>(), choice.data_ptr<int64_t>(), taps ? floors.data_ptr<float>() : nullptr,
+                                    taps ? power.data_ptr<float>() : nullptr, stream_of(wave));
+    TORCH_CHECK(rc == 0, "f5hip_ref_select: ", f5hip_last_error());
+    return std::make_tuple(rows, choice, floors, power);
+}
+
 }   // namespace
 
 TORCH_LIBRARY(f5hip, m) {
@@ -940,4 +985,6 @@ TORCH_LIBRARY(f5hip, m) {
     m.def("watermark_read_ids(Tensor wave, Tensor offset, Tensor n_samples, Tensor carriers) -> Tensor", &watermark_read_ids);
     m.def("watermark_scan(Tensor wave, Tensor first_segment, Tensor n_segments, Tensor carriers) -> Tensor", &watermark_scan);
     m.def("ref_assess(Tensor raw, Tensor raw_offset, Tensor channels, Tensor raw_len, Tensor wave, Tensor offset, Tensor n_samples) -> Tensor", &ref_assess);
+    m.def("ref_select(Tensor raw, Tensor raw_offset, Tensor channels, Tensor raw_len, Tensor sample_rate, Tensor wave, Tensor offset, Tensor n_samples, "
+          "int window_frames, int hop_frames, bool taps) -> (Tensor, Tensor, Tensor, Tensor)", &ref_select);
 }

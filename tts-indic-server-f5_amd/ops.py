@@ -9,6 +9,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import typing
 
 import numpy as np
 import torch
@@ -681,6 +682,91 @@ def ref_assess(raw, raw_offsets, channels, raw_lengths, wave, offsets, lengths):
         _lib.check(_lib.lib().f5hip_ref_assess(len(ln), _p(raw), _p(ro), _p(ch), _p(rl), _p(wave), _p(off), _p(ln), _p(rows), _lib.current_stream_ptr()),
                    "f5hip_ref_assess")
     return rows
+
+
+class RefSelectClip(typing.NamedTuple):
+    """One recording handed to `ref_select`: the two buffers of a front-end call and where the recording lies in them."""
+    raw: torch.Tensor          # contiguous 1-D fp32 on the device: the packed upload, channel after channel
+    raw_offset: int
+    channels: int
+    raw_length: int            # samples per channel
+    sample_rate: int
+    wave: torch.Tensor         # contiguous 1-D fp32 on the device: `ref_frontend`'s packed output
+    offset: int
+    length: int
+
+
+def ref_select_run(window_frames, hop_frames=48) -> int:
+    """Windows one workgroup of `ref_select`'s floor launch owns (include/f5hip.h f5hip_ref_select_run)."""
+    run = int(_lib.lib().f5hip_ref_select_run(int(window_frames), int(hop_frames)))
+    if run < 1:
+        raise _lib.F5HipError(f"ref_select_run: {_lib.lib().f5hip_last_error().decode(errors='replace')}")
+    return run
+
+
+def ref_select(clips, window_frames, hop_frames=48, taps=False):
+    """The report's measures over every window of several recordings in ONE library call and ten launches (include/f5hip.h
+    f5hip_ref_select): `audio_prep.select_table` and the unfiltered `select_choice` of each.  clips: `RefSelectClip`s (or tuples in that
+    order) that share ONE raw and ONE wave tensor, both read only; a prepared recording has 1 to `audio_prep.SELECT_MAX_SAMPLES` samples, a call four times
+    that in all.
+    window_frames 1 .. 1407 and hop_frames are in frames of 256 samples.  Returns (tables, choices): per recording the rows int64
+    [windows, 5] on the device (clipped, speech frames, then the bit patterns of the float64 N, S, snr_db: `ref_select_table` reads them) and
+    the choices int64 [n] on the device.  taps=True: also per recording the floors fp32 [windows, 339] and the band power fp32 [339, F] as
+    the floor launch read it, views of device tensors.  A recording's rows equal its own single-recording call's bit for bit."""
+    from .audio_prep import ASSESS_MAX_CHANNELS, SELECT_MAX_SAMPLES, denoise_frames
+    clips = [c if isinstance(c, RefSelectClip) else RefSelectClip(*c) for c in clips]
+    if not clips:
+        raise _lib.F5HipError("ref_select: at least one recording")
+    raw, wave = clips[0].raw, clips[0].wave
+    for t, name in ((raw, "raw"), (wave, "wave")):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and t.dim() == 1):
+            raise _lib.F5HipError(f"ref_select: {name} must be a contiguous 1-D fp32 tensor on the HIP device")
+    if raw.device != wave.device or any(c.raw is not raw or c.wave is not wave for c in clips):
+        raise _lib.F5HipError("ref_select: the recordings of a call share one raw and one wave tensor on one HIP device")
+    W, hop = int(window_frames), int(hop_frames)
+    if not 1 <= W <= 1407 or not 1 <= hop <= 1 << 20:
+        raise _lib.F5HipError(f"ref_select: window_frames must be 1 .. 1407 and hop_frames 1 .. 2^20 (got {window_frames}, {hop_frames})")
+    ln = _per_request("ref_select", "lengths", [c.length for c in clips], np.int32, per="recording")
+    off = _per_request("ref_select", "offsets", [c.offset for c in clips], np.int64, len(ln), per="recording")
+    ro = _per_request("ref_select", "raw_offsets", [c.raw_offset for c in clips], np.int64, len(ln), per="recording")
+    ch = _per_request("ref_select", "channels", [c.channels for c in clips], np.int32, len(ln), per="recording")
+    rl = _per_request("ref_select", "raw_lengths", [c.raw_length for c in clips], np.int32, len(ln), per="recording")
+    sr = _per_request("ref_select", "sample_rates", [c.sample_rate for c in clips], np.int32, len(ln), per="recording")
+    for i in range(len(ln)):
+        if ch[i] < 1 or ch[i] > ASSESS_MAX_CHANNELS:
+            raise _lib.F5HipError(f"ref_select: recording {i} has {ch[i]} channels (1 .. {ASSESS_MAX_CHANNELS})")
+        if rl[i] < 1 or ro[i] < 0 or int(ro[i]) + int(rl[i]) * int(ch[i]) > raw.numel():
+            raise _lib.F5HipError(f"ref_select: raw recording {i} is {ch[i]} x {rl[i]} samples at {ro[i]} of a tensor of {raw.numel()}")
+        if ln[i] < 1 or ln[i] > SELECT_MAX_SAMPLES:
+            raise _lib.F5HipError(f"ref_select: recording {i} has {ln[i]} samples (1 .. {SELECT_MAX_SAMPLES})")
+        if off[i] < 0 or int(off[i]) + int(ln[i]) > wave.numel():
+            raise _lib.F5HipError(f"ref_select: recording {i} is samples [{off[i]}, {int(off[i]) + int(ln[i])}) of a tensor of {wave.numel()}")
+    frames = [denoise_frames(int(v)) for v in ln]
+    windows = [1 if F < W else (F - W) // hop + 1 for F in frames]
+    cols = [339 * ((F + 3) & ~3) for F in frames]
+    if torch_ops.load():
+        rows, choice, floors, power = call_op("ref_select", raw, torch.from_numpy(ro), torch.from_numpy(ch), torch.from_numpy(rl), torch.from_numpy(sr), wave,
+                                              torch.from_numpy(off), torch.from_numpy(ln), W, hop, bool(taps))
+    else:
+        with torch.cuda.device(wave.device):
+            rows = torch.empty(sum(windows), 5, device=wave.device, dtype=torch.int64)
+            choice = torch.empty(len(ln), device=wave.device, dtype=torch.int64)
+            floors = torch.empty(sum(windows) if taps else 0, 340, device=wave.device, dtype=torch.float32)
+            power = torch.empty(sum(cols) if taps else 0, device=wave.device, dtype=torch.float32)
+            _lib.check(_lib.lib().f5hip_ref_select(len(ln), _p(raw), _p(ro), _p(ch), _p(rl), _p(sr), _p(wave), _p(off), _p(ln), W, hop, _p(rows), _p(choice),
+                                                   _p(floors) if taps else None, _p(power) if taps else None, _lib.current_stream_ptr()), "f5hip_ref_select")
+    tables = list(rows.split(windows))
+    if not taps:
+        return tables, choice
+    return tables, choice, [f[:, :339] for f in floors.split(windows)], [p.view(339, -1)[:, :F] for p, F in zip(power.split(cols), frames)]
+
+
+def ref_select_table(rows) -> np.ndarray:
+    """One recording's rows of `ref_select` (int64 [windows, 5], on either side) -> `audio_prep.select_table`'s float64 [windows, 5]."""
+    rows = np.ascontiguousarray(rows.cpu().numpy() if torch.is_tensor(rows) else rows, dtype=np.int64)
+    out = rows.view(np.float64).copy()
+    out[:, :2] = rows[:, :2]
+    return out
 
 
 def wave_finish(chunks, chunks_per_request, fade, remove_silence=None, sample_rate=24000):

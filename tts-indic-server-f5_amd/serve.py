@@ -1090,6 +1090,57 @@ class TTSManager:
             infer._prepare_deferred([voice], self.model_obj)
         return voice.report
 
+    def select_reference(self, audio, seconds=12.0, min_speech_ratio=None):
+        """The cleanest stretch of `seconds` of a long recording -- WAV or FLAC bytes, or a (wave [ch, n], sr) pair -- as an
+        `audio_prep.ReferenceSelection`: the sample range of the upload to crop to, the table of every window and the `ReferenceReport` of
+        the crop (`audio_prep.select_reference`, whose weak cases are the report's; `min_speech_ratio` drops windows below it before the
+        choice).  Nothing is cached, gated or cloned: a client selects first, then uploads the crop.  With `device_frontend` and a model on
+        a GPU the whole recording takes ONE front-end call and ONE `ops.ref_select` call under the device lock, and only the table and the
+        choice come down; otherwise the host definition runs.  The crop's report is measured on the host either way.  ValueError for
+        unreadable, non-finite or silent audio, more than 8 channels, a recording over 600 s at 24 kHz (never truncated), a `seconds` that is not a multiple of
+        0.5 from 3 to 15, and a `min_speech_ratio` that leaves no window."""
+        import torch
+        W = audio_prep.select_window_frames(seconds)
+        ratio = audio_prep.check_min_speech_ratio(min_speech_ratio)
+        if isinstance(audio, tuple):
+            wave, sr = audio[0].detach().cpu().to(torch.float32), int(audio[1])
+        else:
+            try:
+                wave, sr = self.decode_audio(bytes(audio))
+            except ValueError as e:
+                raise ValueError(f"Invalid audio: {e}") from e
+        if wave.dim() != 2 or not 1 <= wave.shape[0] <= audio_prep.ASSESS_MAX_CHANNELS or wave.shape[1] < 1:
+            raise ValueError(f"Invalid audio: expected [1 .. {audio_prep.ASSESS_MAX_CHANNELS} channels, samples] (got {tuple(wave.shape)})")
+        wave = wave.contiguous()
+        x = wave.numpy()
+        if not np.isfinite(x).all():
+            raise ValueError("Invalid audio: the clip has non-finite samples.")
+        if not x.any():
+            raise ValueError("Invalid audio: the clip is empty or silent.")
+        audio_prep.check_select_length(infer.resampled_length(wave.shape[1], sr, infer.target_sample_rate))
+        if sr != infer.target_sample_rate:
+            infer.resample_taps(sr, infer.target_sample_rate)
+
+        def prepare(crop):
+            out, rms = infer._prepare_reference(torch.from_numpy(np.ascontiguousarray(crop)), sr, 0.1, None)
+            return out[0].numpy(), float(rms)
+
+        device = getattr(getattr(self.model_obj, "local", self.model_obj), "device", None)
+        if not (self.device_frontend and device is not None and torch.device(device).type == "cuda"):
+            return audio_prep.select_reference(x, sr, prepare(x)[0], seconds, ratio, prepare)
+        from . import ops
+        with self._device_lock:
+            packed = wave.reshape(-1).to(device)
+            taps = None if sr == infer.target_sample_rate else infer._device_taps(sr, infer.target_sample_rate, packed.device)
+            out, _, n_out = ops.ref_frontend(packed, [wave.shape[1]], [wave.shape[0]], sr, infer.target_sample_rate, taps, 0.1)
+            length = int(n_out[0])
+            tables, choices = ops.ref_select([ops.RefSelectClip(packed, 0, wave.shape[0], wave.shape[1], sr, out, 0, length)], W)
+            table, choice = ops.ref_select_table(tables[0]), int(choices.cpu()[0])
+        if ratio is not None:
+            frames = [f for _, f in audio_prep.select_windows(audio_prep.denoise_frames(length), W)]
+            choice = audio_prep.select_choice(table, frames, ratio)
+        return audio_prep.select_result(x, sr, length, table, W, choice, prepare)
+
     def reference_problems(self, report, denoise=False) -> list:
         """What `reference_limits` would refuse `report` for, one sentence per violated limit; empty without limits."""
         return infer.reference_problems(report, self.reference_limits, denoise)
@@ -1242,9 +1293,14 @@ def request_models():
         audio: str
         clip_short: bool = True
 
+    class ReferenceSelectRequest(BaseModel):         # `/v1/audio/reference/select`: a long recording (base64 WAV or FLAC) to find a stretch in
+        audio: str
+        seconds: typing.Any = 12.0                   # untyped: a value the manager refuses is its 400, not pydantic's 422
+        min_speech_ratio: typing.Any = None
+
     return types.SimpleNamespace(KannadaSynthesizeRequest=KannadaSynthesizeRequest, SynthesizeRequest=SynthesizeRequest, CloneRequest=CloneRequest,
                                  EditRequest=EditRequest, ScriptRequest=ScriptRequest, ScriptVoice=ScriptVoice, DetectRequest=DetectRequest,
-                                 ReferenceCheckRequest=ReferenceCheckRequest, ScanRequest=ScanRequest)
+                                 ReferenceCheckRequest=ReferenceCheckRequest, ScanRequest=ScanRequest, ReferenceSelectRequest=ReferenceSelectRequest)
 
 
 def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
@@ -1498,6 +1554,29 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
             raise HTTPException(status_code=400, detail=str(e))
         return {"report": report.as_json(), "problems": tts_manager.reference_problems(report)}
 
+    def _run_select(req):
+        """`/v1/audio/reference/select`: {"audio": base64 WAV or FLAC, "seconds"?: 12, "min_speech_ratio"?: null} -> {"seconds", "start",
+        "end", "window", "report", "windows": [{start, clipped, speech_frames, snr_db}]}: the cleanest stretch of a long recording
+        (`TTSManager.select_reference`), start and end in seconds of the upload; the client crops and uploads that.  400 for unreadable
+        audio, audio over 600 s, a bad `seconds` or `min_speech_ratio`, or no window left."""
+        try:
+            raw = base64.b64decode(req.audio, validate=True)
+        except (binascii.Error, ValueError):
+            raise HTTPException(status_code=400, detail="Audio must be a base64-encoded WAV file.")
+        try:
+            wave, sr = tts_manager.decode_audio(raw)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"Invalid audio: {e}")
+        try:
+            sel = tts_manager.select_reference((wave, sr), req.seconds, req.min_speech_ratio)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        finite = lambda v: v if math.isfinite(v) else None
+        starts =[max(0, audio_prep.DENOISE_HOP * audio_prep.SELECT_HOP * w - audio_prep.DENOISE_PAD) / float(infer.target_sample_rate) for w in range(len(sel.windows))]
+        return {"seconds": wave.shape[-1] / float(sr), "start": sel.start / float(sr), "end": sel.end / float(sr), "window": sel.window,
+                "report": sel.report.as_json(),
+                "windows": [dict(start=s, clipped=int(row[0]), speech_frames=int(row[1]), snr_db=finite(row[4])) for s, row in zip(starts, sel.windows)]}
+
     # The reference's handlers are `async def` around a blocking call, i.e. one request at a time.  Here the blocking part runs in
     # starlette's thread pool, so concurrent requests overlap and meet in the MicroBatcher queue (when the manager has one).
     from starlette.concurrency import run_in_threadpool
@@ -1535,6 +1614,10 @@ def create_app(tts_manager: TTSManager, registry: VoiceRegistry):
     @router.post("/audio/reference/check")
     async def check_reference(request: models.ReferenceCheckRequest):      # is this clip fit to clone from?
         return await run_in_threadpool(_run_check, request)
+
+    @router.post("/audio/reference/select")
+    async def select_reference(request: models.ReferenceSelectRequest):    # which stretch of this long recording to clone from?
+        return await run_in_threadpool(_run_select, request)
 
     app = FastAPI(title="F5-TTS on MI355X (HIP path)")
     app.include_router(router)
